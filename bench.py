@@ -13,28 +13,35 @@ BASELINE.json configs[1]: mnet25, fp16, 448x448, batch 8 on one MI355X.
   With N > 1 the RESULT GATHER of the sharded detectBatchImages -- fixed-size records, one RCCL all_gather per global
   super-batch, retinaface_amd/shard.py -- runs inside the timed region.  Timing: barrier + synchronize on both sides, MAX over ranks.
 
-The timed region runs at least K steps and at least --min-seconds (default 1 s): a step is 33 us and the engine's pipeline holds
-3 x 16 of them, so K = 20 would time pipeline fill and drain, not throughput.  `steps` in the JSON is the number actually timed,
-`steps_requested` what was asked for; the one-super-batch burst is reported separately (`burst`).
+A plain run (no --full) does only what the headline figure needs: set up, W warm-up steps, EXACTLY K timed steps in one region,
+--dump-outputs if given, and the JSON line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds per
+timed step).  The engine's pipeline holds 3 x 16 steps of 33 us, so a small K times pipeline fill and drain as well as throughput;
+--min-seconds S stretches the region to at least S seconds (then `steps` > `steps_requested`).  --full adds everything else below:
+the median of 3 regions of the same K steps (`regions`), the one-super-batch burst (`burst`), the latency and host-frame legs, the
+roofline and its counter passes, the other configurations, the CPU baseline and the N > 1 legs.
+
+--dump-outputs DIR writes what the timed path returned for its last step -- `counts.npy` (faces per image, float64) and `faces.npy`
+(float32, batch x max_detections x 15: score, x1 y1 x2 y2, 5 landmark x, 5 landmark y; rows past an image's count are zero) -- so that two builds can be
+compared output for output (the input frames are seeded: the same arguments give the same frames).
 
 Input frames come from a ring of distinct frames larger than the 256 MiB Infinity Cache, so every step reads its pixels from
 HBM (`cache_resident_input` reports the old number: the same 8 frames re-submitted).  `host_frames` is the same loop with the
 frames in HOST memory (rf_enqueue_batch: pinned staging, one DMA per enqueue, upload overlapped with compute) -- what the
-reference's API hands over; it is PCIe-bound and never `value`.
+reference's API hands over; it is PCIe-bound and never `value`.  (--full)
 
-Prints ONE JSON line (rank 0): metric faces/sec (BASELINE.json), images/sec and ms/frame beside it, the pre/infer/post split,
+Prints ONE JSON line (rank 0): metric faces/sec (BASELINE.json), images/sec and ms/frame beside it; with --full also the pre/infer/post split,
 `roofline` for the dominant kernel (HIP-event timed inside this process, algorithmic bytes per SURVEY.md 8d) and `cpu_baseline`
 (the CPU oracle = restatement of the reference's Caffe path, timed on the host cores on a bounded sample of the same frames;
 N = 1, rank 0 only).  --dry runs the launcher / sharding / gather / JSON plumbing with a stub engine on gloo (CPU tests).
 
-The default invocation (N = 1, the metric point) also times the OTHER BASELINE.json configurations in the same run and reports them
+With --full, the invocation at the metric point (N = 1) also times the OTHER BASELINE.json configurations in the same run and reports them
 in `configs`: [2] mnet-deconv-0517 int8 batch 32, [3] mnet25 fp16 1280x896 batch 1, [4]'s per-GPU shape mnet25 int8 batch 32 -- a
 timed region of >= --extra-seconds each with images/s, faces/s, dtype, the dominant kernel and (one extra set of counter passes,
 collected while the CPU baseline runs) its binding resource.  With N > 1 a short STRONG-scaling leg of configs[4] as stated (one
 global batch of 256 int8 images per step split over the ranks) follows the weak-scaling measurement (`configs4_strong`), and
 `result_gather` says which backend carried the gather, the communicator size seen through an RCCL collective and the RCCL version.
 
-`configs` also carries north_star's batch x frame-size matrix (round 5): fp16 448x448 at batch 1 and 32, 1280x896 at batch 8 and 32 -- the
+`configs` (--full) also carries north_star's batch x frame-size matrix (round 5): fp16 448x448 at batch 1 and 32, 1280x896 at batch 8 and 32 -- the
 cells that are not BASELINE.json configs themselves -- and every entry has `sync_batch`: ONE synchronous rf_detect_batch_device call of that
 batch at a time, the reference's own calling convention (RetinaFace.cpp:749-940).
 
@@ -46,7 +53,7 @@ is the same kernel's average duration in a single-lane rocprofv3 kernel trace of
 back-to-back HIP-event figure.  The layer-wise algorithmic-bytes figure of SURVEY.md 8d, which counts bytes a fused kernel never moves
 and therefore exceeds 1, stays as `frac_layerwise_credit` / `hbm_layerwise`.
 
-With N > 1 rank 0 finally runs the LIBRARY leg (`library_multi_device`): ONE handle over devices [0 .. N-1] (rf_options.devices, multi.cpp:
+With N > 1 and --full, rank 0 finally runs the LIBRARY leg (`library_multi_device`): ONE handle over devices [0 .. N-1] (rf_options.devices, multi.cpp:
 one engine + host thread per GPU, contiguous image slices), every frame resident on GPU 0, BASELINE.json configs[4] as stated -- 256 int8
 images per rf_detect_batch_device call -- so that the in-library split and the xGMI peer scatter are measured by the same run that
 measures the ranks (peer-access matrix, bytes scattered per call, images/s).  `--library-devices N` runs that leg alone (rehearsal on one
@@ -83,9 +90,15 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=400)
-    ap.add_argument("--min-seconds", type=float, default=1.0, help="lower bound on the timed region (0 = exactly --steps)")
-    ap.add_argument("--exact-steps", action="store_true", help="time EXACTLY --steps steps in ONE region (no --min-seconds stretch, no repeats): the "
-                                                               "line then says burst_only = true -- at the driver's --steps 20 that is 0.5 ms of pipeline fill, not throughput")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also measure everything else this benchmark reports (repeated regions, burst / latency / "
+                         "host-frame legs, roofline and counter passes, the other BASELINE.json configurations, the CPU baseline, the N > 1 legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned for the last timed step (per-image face counts and face rows) as DIR/<name>.npy")
+    ap.add_argument("--min-seconds", type=float, default=None,
+                    help="stretch the timed region to at least this long (more steps than --steps); default: exactly --steps steps")
+    ap.add_argument("--exact-steps", action="store_true", help="time EXACTLY --steps steps in ONE region (no --min-seconds stretch, no repeats); "
+                                                               "the line then says burst_only = true")
     ap.add_argument("--batch", type=int, default=8, help="images per GPU per step")
     ap.add_argument("--height", type=int, default=448)
     ap.add_argument("--width", type=int, default=448)
@@ -108,7 +121,8 @@ def parse_args(argv=None):
     ap.add_argument("--global-batch", type=int, default=0,
                     help="STRONG scaling: a step is ONE batch of this many images split over the ranks by shard_range (BASELINE.json "
                          "configs[4]: --global-batch 256 --gpus 8 --precision int8); 0 = weak scaling, --batch images per rank")
-    ap.add_argument("--regions", type=int, default=3, help="timed regions; `value` is the median one, min / max are reported beside it")
+    ap.add_argument("--regions", type=int, default=None,
+                    help="timed regions of the same steps; `value` is the median one, min / max are reported beside it (default: 1, 3 with --full)")
     ap.add_argument("--extra-seconds", type=float, default=0.4,
                     help="timed region of each additional BASELINE.json config the default invocation also measures (`configs`); 0 = skip")
     ap.add_argument("--no-extra-configs", action="store_true", help="measure only the configuration named by the flags")
@@ -116,7 +130,10 @@ def parse_args(argv=None):
                     help="run ONLY the library leg: one handle over this many device ordinals (wrapping around the visible GPUs), 256 int8 images per call")
     ap.add_argument("--no-pipeline-trace", action="store_true", help="skip the single-lane rocprofv3 --kernel-trace pass (roofline.kernel_ms_in_pipeline)")
     ap.add_argument("--master-port", type=int, default=0)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.regions is None:
+        args.regions = 3 if args.full else 1
+    return args
 
 
 def free_port() -> int:
@@ -184,6 +201,17 @@ class Runner:
         self.rec_w = 1 + GATHER_CAP * shard.RECORD_FLOATS
         self.gs = {"buf": np.zeros((per_launch * B_pad, self.rec_w), np.float32), "fill": 0, "handle": None, "out": None, "block": None,
                    "gathers": 0, "images": torch.zeros((), dtype=torch.int64, device=cdev)}
+        self.keep_last = False          # --dump-outputs: keep a copy of the last step's results (counts, face rows)
+        self.last = None
+
+    def keep(self, counts):
+        """Copy what the caller of the timed path received for this step: per-image face counts and the (B, max_detections, 15)
+        face rows, rows past an image's count zeroed (the result block is reused from step to step)."""
+        np = self.np
+        faces = np.array((self.det.last_faces if self.dry else self.det.last_wait_faces())[:self.B], dtype=np.float32)
+        for i, c in enumerate(counts):
+            faces[i, c:] = 0.0
+        self.last = {"counts": np.asarray(counts, dtype=np.float64), "faces": faces}
 
     def record_step(self, counts, n):
         """Append this step's per-image records (count + first GATHER_CAP faces) to the rank's block; all_gather it when the
@@ -241,6 +269,8 @@ class Runner:
             faces += sum(c)
             if gather:
                 self.record_step(c, B)
+            if self.keep_last and not inflight:
+                self.keep(c)
         if gather:
             self.flush_gather(final=True)
         return faces
@@ -257,7 +287,7 @@ def main() -> int:
     import torch.distributed as dist
 
     if args.library_devices > 0 and env_world is None:
-        leg = library_leg(args, args.library_devices, float(args.threshold), seconds=max(args.min_seconds, 0.3))
+        leg = library_leg(args, args.library_devices, float(args.threshold), seconds=max(1.0 if args.min_seconds is None else args.min_seconds, 0.3))
         print(json.dumps({"metric": "faces/sec", "value": leg.get("faces_per_sec"), "unit": "faces/s", "n_gpus": leg.get("visible_gpus", 0),
                           "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "i8", "data": "synthetic",
                           "config": {"workload": leg.get("workload", "library leg (dry)")}, "library_multi_device": leg}), flush=True)
@@ -358,10 +388,12 @@ def main() -> int:
     t0 = time.perf_counter()
     run(max(args.warmup, 1), prepared_ring, do_gather)
     warm_dt = time.perf_counter() - t0
-    # at least --steps, at least --min-seconds (estimated from the warm-up rate), in whole super-batches
+    # exactly --steps; only an explicit --min-seconds stretches the region (estimated from the warm-up rate, in whole super-batches)
     steps = args.steps
+    if args.exact_steps or args.min_seconds is None:
+        args.min_seconds = 0.0
     if args.exact_steps:
-        args.min_seconds, args.regions = 0.0, 1
+        args.regions = 1
     if args.min_seconds > 0 and not args.dry:
         est = warm_dt / max(args.warmup, 1)
         steps = max(steps, int(np.ceil(args.min_seconds / max(est, 1e-7))))
@@ -382,6 +414,7 @@ def main() -> int:
         barrier()
         return time.perf_counter() - t0, faces
 
+    R.keep_last = bool(args.dump_outputs)
     for attempt in range(4):
         dt, faces = timed_region(steps)
         if args.dry or args.min_seconds <= 0:
@@ -410,11 +443,15 @@ def main() -> int:
     med = order[len(order) // 2]
     dt, faces = regions[med]
     region_rates = [regions_all[i][1] / regions_all[i][0] for i in range(len(regions_all))]
+    R.keep_last = False
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, R.last, "" if world == 1 else f"_rank{rank}")
+    full = args.full and not args.timed_only           # everything below that is not the headline figure
 
     # N > 1: every rank's own rate over the median region (a straggler GPU is invisible in MAX / SUM), then rank 0 ALONE -- the other ranks idle at
     # the barrier -- for the same loop without the gather: `scaling_efficiency` = value / (N x that rate), measured inside this run
     per_rank = None
-    if world > 1:
+    if world > 1 and full:
         mine = torch.tensor([[float(rank), dt, float(faces), float(steps * B)]], dtype=torch.float64, device=cdev)
         allr = torch.empty((world, 4), dtype=torch.float64, device=cdev)
         dist.all_gather_into_tensor(allr, mine)
@@ -441,17 +478,17 @@ def main() -> int:
 
     # N > 1: the BATCH SPLIT north_star prescribes, A/B'd between the ranks (every rank takes part): see split_ab()
     split_leg = None
-    if world > 1 and not strong and not args.timed_only and not args.no_extra_configs and args.extra_seconds > 0:
+    if world > 1 and not strong and full and not args.no_extra_configs and args.extra_seconds > 0:
         split_leg = split_ab(args, world, rank, dev, cdev, barrier, backend, thr)
 
     # N > 1, weak-scaling invocation (what the driver's SCALE run types): a short STRONG-scaling leg of BASELINE.json configs[4] as stated
     # follows -- ONE global batch of 256 int8 images per step, rank r runs shard_range(256, r, N) of it, records gathered in the region
     strong_leg = None
-    if world > 1 and not strong and not args.timed_only and not args.no_extra_configs and args.extra_seconds > 0:
+    if world > 1 and not strong and full and not args.no_extra_configs and args.extra_seconds > 0:
         strong_leg = strong_config4(args, world, rank, dev, cdev, barrier, frames if not args.dry else None, thr)
 
     extra = {}
-    if not args.dry and not args.timed_only:
+    if not args.dry and full:
         # burst: ONE super-batch through an empty pipeline, start to finish (what --steps 16 used to time)
         lat = []
         for _ in range(10):
@@ -490,7 +527,7 @@ def main() -> int:
                                                                model_stem=args.model, lanes=args.lanes, coalesce=args.coalesce))
 
     # N > 1 (the driver's SCALE run): after everything the ranks measure together, rank 0 times the in-library split over the same N devices
-    with_library_leg = world > 1 and not strong and not args.timed_only and not args.no_extra_configs and args.extra_seconds > 0
+    with_library_leg = world > 1 and not strong and full and not args.no_extra_configs and args.extra_seconds > 0
 
     tt = torch.tensor([dt, float(faces)], dtype=torch.float64, device=cdev)
     if world > 1:
@@ -533,6 +570,7 @@ def main() -> int:
                                     "bytes_per_rank_per_gather": int(per_launch * B_pad * R.rec_w * 4),
                                     "records_gathered": int(gather_state["images"].item()), "expected": images_total,
                                     "per_rank": per_rank}
+        if per_rank is not None:
             alone_ips = per_rank["rank0_alone"]["images_per_sec"]
             out["scaling_efficiency"] = {"value": out["images_per_sec"] / max(world * alone_ips, 1e-12), "n_gpus": world,
                                          "is": "images/s of the N-rank job / (N x images/s of rank 0 running ALONE in this same run)",
@@ -551,11 +589,12 @@ def main() -> int:
                 # the other ranks wait on the rendezvous store for exactly this leg (their GPUs had to be free for it); what rank 0 still measures
                 # alone afterwards (per-kernel profile, counter passes) they sit out in the closing barrier, whose watchdog is minutes, not this wait
                 dist.distributed_c10d._get_default_store().set("rf_library_leg", "done")
+        out["full"] = full
         if args.dry:
             out["dry"] = True
         elif args.timed_only:
             out["timed_only"] = True
-        else:
+        elif full:
             out.update(extra)
             out.update(device_side_report(args, det, frames, B, H, W, per_launch, prec, images_total, world, dt_max))
             with_configs = (world == 1 and not args.no_extra_configs and args.extra_seconds > 0 and
@@ -595,6 +634,23 @@ def main() -> int:
         dist.barrier()
         dist.destroy_process_group()
     return 0
+
+
+def dump_outputs(d, last, suffix=""):
+    """--dump-outputs: the last timed step's results as <d>/<name><suffix>.npy (float32 / float64), at most 64 MB in all; a larger
+    batch is cut to a fixed, seeded sample of its images (their indices in image_index.npy)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = dict(last)
+    B = len(arrays["counts"])
+    per_image = sum(a.nbytes for a in arrays.values()) / max(B, 1)
+    keep = int(min(B, (64 << 20) // max(per_image, 1)))
+    if keep < B:
+        idx = np.sort(np.random.default_rng(0).choice(B, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["image_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, f"{name}{suffix}.npy"), a)
 
 
 def sync_batch_measure(det, ptrs, H, W, thr, reps=120, seconds=None):

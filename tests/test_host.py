@@ -279,7 +279,7 @@ def test_bench_self_launches_n_ranks_and_gathers_results():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry", "--steps", "100", "--warmup", "10"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry", "--steps", "100", "--warmup", "10", "--full"],
                          capture_output=True, text=True, env=env, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -329,13 +329,40 @@ def test_bench_strong_mode_shards_one_global_batch(gpus, gbatch):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--dry", "--global-batch", str(gbatch),
-                          "--steps", "12", "--warmup", "2"], capture_output=True, text=True, env=env, timeout=600)
+                          "--steps", "12", "--warmup", "2", "--full"], capture_output=True, text=True, env=env, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     j = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     assert j["n_gpus"] == gpus and j["scaling"] == "strong" and j["config"]["global_batch"] == gbatch
     assert j["result_gather"]["records_gathered"] == j["result_gather"]["expected"] == gbatch * j["steps"]
     assert abs(j["images_per_sec"] * j["timed_seconds"] - gbatch * j["steps"]) < 1e-3 * gbatch * j["steps"]
     assert j["regions"]["n"] == 3 and j["regions"]["min"] <= j["value"] <= j["regions"]["max"]
+
+
+def test_bench_plain_run_times_exact_steps_and_dumps_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps in one region, reports ms_per_step for them and measures nothing else;
+    --dump-outputs writes the last timed step's results, the same from run to run.  --dry: stub engine."""
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"out{run}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dry", "--steps", "37", "--warmup", "3",
+                              "--dump-outputs", str(d)], capture_output=True, text=True, env=env, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        j = json.loads(lines[0])
+        assert j["steps"] == j["steps_requested"] == 37 and j["regions"]["n"] == 1 and j["full"] is False
+        assert j["metric"] == "faces/sec" and j["unit"] == "faces/s" and j["higher_is_better"] is True and j["dtype"] == "f16"
+        assert abs(j["ms_per_step"] - j["timed_seconds"] / 37 * 1e3) < 1e-9 and j["value"] > 0
+        assert not {"burst", "sync_batch", "roofline", "configs", "cpu_baseline"} & set(j)
+        assert sorted(os.listdir(d)) == ["counts.npy", "faces.npy"]
+        dumps.append({n: np.load(d / f"{n}.npy") for n in ("counts", "faces")})
+    counts, faces = dumps[0]["counts"], dumps[0]["faces"]
+    assert counts.dtype == np.float64 and counts.shape == (8,) and faces.dtype == np.float32 and faces.shape == (8, 256, 15)
+    for i, c in enumerate(counts.astype(int)):
+        assert c > 0 and faces[i, :c, 0].min() > 0 and not faces[i, c:].any()
+    assert all(np.array_equal(dumps[0][n], dumps[1][n]) for n in dumps[0])
 
 
 def test_rfw_reader_rejects_corrupt_files(built_lib, tmp_path):

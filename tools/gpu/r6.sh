@@ -33,7 +33,7 @@ for recipe in "$@"; do
     kbench_fp16)
       timeout 200 python tools/kbench.py --n 256 --tag r6_${TAG}_fp16 > $O/kbench_fp16.txt 2>&1; cat $O/kbench_fp16.txt | cut -c1-70 ;;
     bench)
-      ( time timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err ) 2> $O/bench_time.txt
+      ( time timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err ) 2> $O/bench_time.txt
       cp gpurun_out/bench_kernels.json $O/bench_kernels.json 2>/dev/null; cp gpurun_out/bench_pipeline_trace.json $O/ 2>/dev/null
       tail -3 $O/bench_time.txt
       python - <<PY
@@ -53,7 +53,7 @@ PY
       ( time timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -q -s -x -k "split_upload or rehearsal or concurrent or composition_invariant or two_ranks" ) > $O/pytest_new.log 2>&1; echo "rc $?" >> $O/pytest_new.log
       grep -E "passed|failed|Error|assert|^rc|real" $O/pytest_new.log | tail -20 ;;
     multi_rehearsal)  # the N > 1 line on the one-GPU box: 2 ranks sharing the GPU (gloo), library leg over 8 ordinals with forced scatter
-      timeout 600 python bench.py --gpus 2 --oversubscribe --no-cpu-baseline --host-seconds 0 --no-pmc --no-pipeline-trace --profile-iters 5 --ring-mb 80 --min-seconds 0.5 \
+      timeout 600 python bench.py --full --gpus 2 --oversubscribe --no-cpu-baseline --host-seconds 0 --no-pmc --no-pipeline-trace --profile-iters 5 --ring-mb 80 --min-seconds 0.5 \
           > $O/bench_2ranks_one_gpu.json 2> $O/bench_2ranks_one_gpu.err; echo "2 ranks rc $?"
       timeout 300 python bench.py --library-devices 8 > $O/bench_library_leg_8_engines_one_gpu.json 2> $O/bench_library_leg.err; echo "library leg rc $?"
       python - <<PY
@@ -71,7 +71,7 @@ PY
     sync_pieces)    # piece-count sweep of the pipelined staging (RF_SYNC_PIECES), batch 8 and 32 at 448 x 448, one 1280 x 896 frame
       for pc in 1 2 4 8 16; do RF_SYNC_PIECES=$pc timeout 120 python tools/probes/sync_host_pieces.py; done > $O/sync_host_pieces.txt 2>&1; cat $O/sync_host_pieces.txt ;;
     sync_host)      # one synchronous host-frame call, pipelined staging vs RF_SYNC_SPLIT=0, every config
-      timeout 600 python bench.py --no-cpu-baseline --no-pmc --no-pipeline-trace --profile-iters 5 > $O/bench_sync_host.json 2> $O/bench_sync_host.err; echo "rc $?"
+      timeout 600 python bench.py --full --no-cpu-baseline --no-pmc --no-pipeline-trace --profile-iters 5 > $O/bench_sync_host.json 2> $O/bench_sync_host.err; echo "rc $?"
       python - <<PY
 import json
 j=json.loads(open("$O/bench_sync_host.json").read().strip().splitlines()[-1])
@@ -114,8 +114,8 @@ PY
       rm -rf /tmp/kt2; ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/kt2 -o kt -- python $R/bench.py --timed-only --lanes 1 --no-pmc --precision int8 --batch 32 > $O/trace1_int8_bench.json 2> $O/trace1_int8.err )
       db=$(find /tmp/kt2 -name "*.db" | head -1); python tools/rocpd_summary.py $db $O/kernel_trace_lanes1_int8.txt > /dev/null; head -26 $O/kernel_trace_lanes1_int8.txt | cut -c1-60,104-190 ;;
     bench_int8)     # the dedicated lines of configs[4] (per-GPU shape) and configs[2]
-      timeout 400 python bench.py --precision int8 --model mnet25 --batch 32 --no-cpu-baseline --no-extra-configs > $O/bench_int8_mnet25_b32.json 2> $O/bench_int8_mnet25.err
-      timeout 400 python bench.py --precision int8 --model mnet-deconv-0517 --batch 32 --no-cpu-baseline --no-extra-configs > $O/bench_int8_0517_b32.json 2> $O/bench_int8_0517.err
+      timeout 400 python bench.py --full --precision int8 --model mnet25 --batch 32 --no-cpu-baseline --no-extra-configs > $O/bench_int8_mnet25_b32.json 2> $O/bench_int8_mnet25.err
+      timeout 400 python bench.py --full --precision int8 --model mnet-deconv-0517 --batch 32 --no-cpu-baseline --no-extra-configs > $O/bench_int8_0517_b32.json 2> $O/bench_int8_0517.err
       for f in bench_int8_mnet25_b32 bench_int8_0517_b32; do python -c "import json;j=json.loads(open('$O/$f.json').read().strip().splitlines()[-1]);print('$f', round(j['images_per_sec']), 'img/s', j['roofline']['kernel_instance'], round(j['roofline']['kernel_ms']*1e3,1), 'us')"; done ;;
     inst_classes)   # VALU instruction classes per kernel (conversion / integer / fp arithmetic / MFMA), product library, fp16 then int8
       for v in fp16 int8; do
@@ -138,7 +138,7 @@ PY
       done; done ;;
     gridfrac)       # persistent grids sized for a FRACTION of the resident slots, so that another lane's kernel can be co-resident (RF_GRID_FRAC, probe build), x lanes
       for rep in 1 2; do for cfg in "1.0 3" "0.75 3" "0.5 3" "0.5 4" "0.5 6" "0.67 4" "0.34 6" "1.0 3"; do set -- $cfg
-        env RETINAFACE_AMD_LIB=$R/retinaface_amd/lib/libretinaface_amd_probe.so RF_GRID_FRAC=$1 timeout 200 python bench.py --lanes $2 --no-cpu-baseline --no-extra-configs --no-pmc --no-pipeline-trace --host-seconds 0 --regions 2 --profile-iters 3 > $O/bench_frac$1_lanes$2_$rep.json 2> $O/bench_frac$1_lanes$2_$rep.err
+        env RETINAFACE_AMD_LIB=$R/retinaface_amd/lib/libretinaface_amd_probe.so RF_GRID_FRAC=$1 timeout 200 python bench.py --full --lanes $2 --no-cpu-baseline --no-extra-configs --no-pmc --no-pipeline-trace --host-seconds 0 --regions 2 --profile-iters 3 > $O/bench_frac$1_lanes$2_$rep.json 2> $O/bench_frac$1_lanes$2_$rep.err
         python -c "import json;j=json.loads(open('$O/bench_frac$1_lanes$2_$rep.json').read().strip().splitlines()[-1]);print('frac $1 lanes $2 rep $rep:', round(j['images_per_sec']), 'img/s  burst', round(j['burst']['ms'],3), 'ms  sync', round(j['sync_batch']['ms_per_call'],4))" 2>&1 | tail -1
       done; done ;;
     wide128)        # fp16 plain 128-channel blocks: K_b 4x8 (product) | K_b 4x16 | K_b(8) 4x8 | K_b(8) 4x16 (probe build)
@@ -149,7 +149,7 @@ PY
     upmerge)        # (round 6, rejected and removed from engine.cpp: see profiles/r06_sync_host_call_ab.txt (d); the knob no longer exists)
                     # pipelined host frames (rf_enqueue_batch, pageable): one DMA per enqueue (0) vs merged uploads of >= N MB (RF_UPLOAD_MERGE_MB)
       for rep in 1 2; do for mb in 0 8 16 32 64 0; do
-        RF_UPLOAD_MERGE_MB=$mb timeout 200 python bench.py --no-cpu-baseline --no-extra-configs --no-pmc --no-pipeline-trace --host-seconds 3 --profile-iters 3 --regions 1 --min-seconds 0.3 > $O/bench_upmerge${mb}_$rep.json 2> $O/bench_upmerge${mb}_$rep.err
+        RF_UPLOAD_MERGE_MB=$mb timeout 200 python bench.py --full --no-cpu-baseline --no-extra-configs --no-pmc --no-pipeline-trace --host-seconds 3 --profile-iters 3 --regions 1 --min-seconds 0.3 > $O/bench_upmerge${mb}_$rep.json 2> $O/bench_upmerge${mb}_$rep.err
         python -c "import json;j=json.loads(open('$O/bench_upmerge${mb}_$rep.json').read().strip().splitlines()[-1]);h=j['host_frames'];print('merge $mb MB rep $rep: pageable', round(h['pageable']['images_per_sec']), 'img/s', round(h['pageable']['pcie_GBs'],1), 'GB/s | registered', round(h['registered']['images_per_sec']), '| pinned copy', round(h['pinned_copy_GBs_measured'],1), 'GB/s | device-frame value', round(j['images_per_sec']))" 2>&1 | tail -1
       done; done ;;
     driver_cmd)     # the driver's exact round-end commands, timed
@@ -164,7 +164,7 @@ PY
       done | tee -a $O/stress.txt
       timeout 400 python tools/probes/stress.py --threads 3 --seconds ${STRESS_S:-60} --precision fp16 --seed 7 --max-batch 8 2>&1 | grep -E "stress|Error|error" | tee -a $O/stress.txt ;;      # three threads, three handles, one GPU
     ranks8)         # the whole `--gpus 8` flow with REAL engines, eight ranks sharing the one GPU (gloo; RCCL refuses duplicates): launcher, legs, accounting
-      ( time timeout 900 python bench.py --gpus 8 --oversubscribe --no-cpu-baseline --host-seconds 0 --no-pmc --no-pipeline-trace --profile-iters 3 --ring-mb 40 --min-seconds 0.3 --regions 1 \
+      ( time timeout 900 python bench.py --full --gpus 8 --oversubscribe --no-cpu-baseline --host-seconds 0 --no-pmc --no-pipeline-trace --profile-iters 3 --ring-mb 40 --min-seconds 0.3 --regions 1 \
           > $O/bench_8ranks_one_gpu.json 2> $O/bench_8ranks_one_gpu.err ) 2> $O/bench_8ranks_time.txt; echo "8 ranks rc $?"; tail -3 $O/bench_8ranks_time.txt
       python - <<PY
 import json

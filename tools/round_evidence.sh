@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out
 mkdir -p $O
 cd $R
-b() { name=$1; shift; timeout 400 python bench.py "$@" > $O/${TAG}_bench_$name.json 2> $O/${TAG}_bench_$name.err; python - <<PY
+b() { name=$1; shift; timeout 400 python bench.py --full "$@" > $O/${TAG}_bench_$name.json 2> $O/${TAG}_bench_$name.err; python - <<PY
 import json
 try:
     j = json.load(open("$O/${TAG}_bench_$name.json"))
@@ -24,7 +24,7 @@ b 1280x896_b1_fp16 --height 896 --width 1280 --batch 1 --no-cpu-baseline
 b b32_448_fp16 --batch 32 --no-cpu-baseline --host-seconds 0
 b fp32 --precision fp32 --no-cpu-baseline --host-seconds 0
 cp $O/bench_kernels.json $O/${TAG}_bench_kernels_hip_events_fp32.json 2>/dev/null
-timeout 200 python bench.py --no-cpu-baseline --host-seconds 0 > /dev/null 2>&1; cp $O/bench_kernels.json $O/${TAG}_bench_kernels_hip_events.json
+timeout 200 python bench.py --full --no-cpu-baseline --host-seconds 0 > /dev/null 2>&1; cp $O/bench_kernels.json $O/${TAG}_bench_kernels_hip_events.json
 # kernel trace of the headline bench (no counters in this run)
 cd /tmp && export TMPDIR=/tmp
 for cfg in "b8_448_fp16:" "int8_mnet25_b32:--precision int8 --model mnet25 --batch 32" "1280x896_b1_fp16:--height 896 --width 1280 --batch 1"; do
