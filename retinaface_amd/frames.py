@@ -7,6 +7,11 @@ the fp32 oracle finds there, each expanded 1.5x, resampled by an integer factor 
 nearest) and pasted at random non-overlapping positions.  Frames are generated AT net size, so preprocess is the
 identity-resize path (what BASELINE.json's configs use).  Everything is seeded: frame i of config c uses
 numpy.random.default_rng(1000*c + i).
+
+`canvas` (the grey level under the noise) and `background` ("photo": tiles cut from the face-free regions of the fixture;
+"uniform": i.i.d. 0..255 pixels) vary the canvas for the photometric parity tests (tests/frame_variants.py).  The
+background draws from its own generator, default_rng((1000*c + i, 1)), so the noise and the face placement stay those of
+the plain frame; with the defaults every frame is byte-identical to what this module always produced.
 """
 from __future__ import annotations
 
@@ -49,6 +54,36 @@ def _patches(base: np.ndarray) -> List[np.ndarray]:
     return out
 
 
+BG_TILE = 64
+
+
+def _face_free_origins(base: np.ndarray, tile: int = BG_TILE) -> np.ndarray:
+    """(y, x) origins, on a 16-pixel grid, of every tile x tile crop of the fixture that overlaps none of FACE_BOXES expanded 1.5x"""
+    H, W = base.shape[:2]
+    boxes = []
+    for x1, y1, x2, y2 in FACE_BOXES:
+        cx, cy, w, h = (x1 + x2) / 2, (y1 + y2) / 2, (x2 - x1) * 1.5, (y2 - y1) * 1.5
+        boxes.append((cx - w / 2, cy - h / 2, cx + w / 2, cy + h / 2))
+    out = [(y, x) for y in range(0, H - tile + 1, 16) for x in range(0, W - tile + 1, 16)
+           if all(x + tile <= a or c <= x or y + tile <= b or d <= y for a, b, c, d in boxes)]
+    return np.array(out, np.int64)
+
+
+def _background(base: np.ndarray, h: int, w: int, kind: str, rng) -> np.ndarray:
+    if kind == "uniform":
+        return rng.integers(0, 256, size=(h, w, 3)).astype(np.float64)
+    if kind != "photo":
+        raise ValueError(f"background must be None, 'photo' or 'uniform' (got {kind!r})")
+    origins = _face_free_origins(base)
+    out = np.empty((h, w, 3), np.float64)
+    for ty in range(0, h, BG_TILE):
+        for tx in range(0, w, BG_TILE):
+            y, x = origins[int(rng.integers(0, len(origins)))]
+            th, tw = min(BG_TILE, h - ty), min(BG_TILE, w - tx)
+            out[ty:ty + th, tx:tx + tw] = base[y:y + th, x:x + tw]
+    return out
+
+
 def _rescale(p: np.ndarray, num: int, den: int) -> np.ndarray:
     if den == 2:   # x0.5, 2x2 area average
         h, w = p.shape[0] // 2 * 2, p.shape[1] // 2 * 2
@@ -59,9 +94,11 @@ def _rescale(p: np.ndarray, num: int, den: int) -> np.ndarray:
     return p
 
 
-def synth_frames(h: int, w: int, n: int, config: int = 0, base: np.ndarray = None, faces=None) -> List[np.ndarray]:
+def synth_frames(h: int, w: int, n: int, config: int = 0, base: np.ndarray = None, faces=None, canvas: float = 128,
+                 background: str = None) -> List[np.ndarray]:
     """n seeded BGR uint8 frames of h x w with 1..6 pasted faces each.  `faces` restricts the patches to a subset of the six
-    fixture faces (indices into FACE_BOXES): the int8 calibration set and the held-out int8 parity frames use disjoint subsets."""
+    fixture faces (indices into FACE_BOXES): the int8 calibration set and the held-out int8 parity frames use disjoint subsets.
+    `canvas` / `background`: see the module docstring (background replaces the flat canvas; the noise is added to either)."""
     if base is None:
         base = load_base_frame()
     patches = _patches(base)
@@ -70,7 +107,12 @@ def synth_frames(h: int, w: int, n: int, config: int = 0, base: np.ndarray = Non
     frames = []
     for i in range(n):
         rng = np.random.default_rng(1000 * config + i)
-        img = np.clip(128.0 + rng.normal(0.0, 8.0, size=(h, w, 3)), 0, 255).astype(np.uint8)
+        noise = rng.normal(0.0, 8.0, size=(h, w, 3))
+        if background is not None:
+            noise += _background(base, h, w, background, np.random.default_rng((1000 * config + i, 1)))
+            img = np.clip(noise, 0, 255).astype(np.uint8)
+        else:
+            img = np.clip(float(canvas) + noise, 0, 255).astype(np.uint8)
         k = int(rng.integers(1, 7))
         placed: List[Tuple[int, int, int, int]] = []
         for _ in range(k):

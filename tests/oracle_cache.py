@@ -18,8 +18,10 @@ import numpy as np
 from oracle.retinaface_post import Detection
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "contract_oracle_1280x896.npz")
+# the photometric variants' 448 x 448 frames (tests/frame_variants.py; tools/make_contract_golden.py --variants)
+GOLDEN_VARIANTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "contract_oracle_variants.npz")
 SCORE_NOISE = 2e-3            # = tests/test_gpu_parity.py SCORE_NOISE (asserted there)
-_file = None
+_files = None
 
 
 def frame_key(stem, hw, cfg, faces, i) -> str:
@@ -69,15 +71,48 @@ def pack(ref, frame) -> dict:
             "cand_idx": np.array([d.anchor_index for d in ref.candidates], np.int32), "band": np.int32(band_of(ref.heads)), "sha1": frame_hash(frame)}
 
 
+def pack_blob(arrays: dict) -> np.ndarray:
+    """pack()'s six arrays as ONE uint8 array (the variants' file: one archive member per frame instead of six keeps it small):
+    int32 (band, #detections, #candidates), the 20-byte SHA-1, int32 detection / candidate anchors, float32 detection / candidate rows."""
+    nd, nc = len(arrays["det_idx"]), len(arrays["cand_idx"])
+    parts = [np.array([arrays["band"], nd, nc], "<i4"), np.asarray(arrays["sha1"], np.uint8), np.asarray(arrays["det_idx"], "<i4"),
+             np.asarray(arrays["cand_idx"], "<i4"), np.asarray(arrays["det_rows"], "<f4").reshape(nd, 15),
+             np.asarray(arrays["cand_rows"], "<f4").reshape(nc, 15)]
+    return np.concatenate([np.frombuffer(np.ascontiguousarray(p).tobytes(), np.uint8) for p in parts])
+
+
+def unpack_blob(blob: np.ndarray) -> dict:
+    b = np.ascontiguousarray(blob, np.uint8).tobytes()
+    band, nd, nc = np.frombuffer(b, "<i4", 3)
+    o = 12
+    sha1 = np.frombuffer(b, np.uint8, 20, o)
+    o += 20
+    det_idx = np.frombuffer(b, "<i4", nd, o)
+    o += 4 * nd
+    cand_idx = np.frombuffer(b, "<i4", nc, o)
+    o += 4 * nc
+    det_rows = np.frombuffer(b, "<f4", 15 * nd, o).reshape(nd, 15)
+    o += 60 * nd
+    cand_rows = np.frombuffer(b, "<f4", 15 * nc, o).reshape(nc, 15)
+    assert o + 60 * nc == len(b)
+    return dict(det_rows=det_rows, det_idx=det_idx, cand_rows=cand_rows, cand_idx=cand_idx, band=band, sha1=sha1)
+
+
 def lookup(key, frame, hw):
-    global _file
-    if _file is None:
-        _file = np.load(GOLDEN) if os.path.exists(GOLDEN) else {}
-    files = getattr(_file, "files", ())
-    if key + "/sha1" not in files or not np.array_equal(_file[key + "/sha1"], frame_hash(frame)):
-        return None
-    g = lambda n: _file[f"{key}/{n}"]          # noqa: E731
-    return CachedResult(hw[0], hw[1], g("det_rows"), g("det_idx"), g("cand_rows"), g("cand_idx"), g("band"))
+    global _files
+    if _files is None:
+        _files = [np.load(p) for p in (GOLDEN, GOLDEN_VARIANTS) if os.path.exists(p)]
+    for f in _files:
+        if key + "/sha1" in f.files:
+            g = {n: f[f"{key}/{n}"] for n in ("det_rows", "det_idx", "cand_rows", "cand_idx", "band", "sha1")}
+        elif key + "/blob" in f.files:
+            g = unpack_blob(f[key + "/blob"])
+        else:
+            continue
+        if not np.array_equal(g["sha1"], frame_hash(frame)):
+            return None
+        return CachedResult(hw[0], hw[1], g["det_rows"], g["det_idx"], g["cand_rows"], g["cand_idx"], g["band"])
+    return None
 
 
 def detect(oracle, stem, frame, hw, cfg, faces, i, thr=0.5, nms=0.4):

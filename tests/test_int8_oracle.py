@@ -203,3 +203,35 @@ def test_u8_mid_algebra_and_calibrated_weights(nets):
         moved = np.mean([np.mean(a.wq != b.wq) for a, b in zip(q8.pw[1:], q0.pw[1:])])
         assert 0.03 < moved < 0.4, moved
         assert all(np.abs(a.wq - b.wq).max() <= 3 for a, b in zip(q8.pw[1:], q0.pw[1:]))
+
+
+def test_variant_frames_drive_the_int8_epilogues_into_their_top_clamp(nets, oracles):
+    """Every requantising epilogue of the int8 engine clamps at the top code: fmed3(v, 0, 127) + v_cvt_pk_u8_f32 for block outputs, FPN
+    and SSH tensors, and the 0..255 depthwise mid store (q - 128), which relies on the conversion's own clamp.  On the plain contract
+    frames those clamps are almost never reached, so the GPU's bit-exactness against this oracle says little about them.  The frames of
+    tests/frame_variants.py (fed to the GPU's int8 bit-exact test) must reach them: on the first frame of every variant, continued from
+    the quantised fp32 front end as the engine is, at least one variant puts >= 0.1 % of some block output's quanta at 127, and at least
+    one does so for a depthwise intermediate."""
+    import frame_variants as fv
+    start = "mobilenet0_relu2_fwd"            # the int8 engine's first int8 activation
+    best_block, best_dw = (0.0, ""), (0.0, "")
+    for stem in STEMS:
+        q = i8.Int8Net(nets[stem])
+        for name in fv.ALL:
+            f = fv.variant_frames(name, 1)[0]
+            blobs = oracles[stem].forward(preprocess_trt_identity(f, *fv.HW), keep_all=True)
+            acts = q.forward_from(start, q.quantise_blob(start, blobs[start][0].transpose(1, 2, 0)))
+            top_b, top_d = (0.0, ""), (0.0, "")
+            for n, a in acts.items():
+                if n in ("__heads__", start) or n.startswith("_plus"):
+                    continue
+                frac = (float((a == 127).mean()), f"{stem} {name} {n}")
+                dw = n.startswith("mobilenet0_relu") and int(n[len("mobilenet0_relu"):].split("_")[0]) % 2 == 1
+                if dw:
+                    top_d = max(top_d, frac)
+                else:
+                    top_b = max(top_b, frac)
+            print(f"int8 top code {stem} {name:8s}: block / FPN / SSH {top_b[0]:.5f} ({top_b[1].split()[-1]}), depthwise {top_d[0]:.5f} ({top_d[1].split()[-1]})")
+            best_block, best_dw = max(best_block, top_b), max(best_dw, top_d)
+    assert best_block[0] >= 1e-3, best_block
+    assert best_dw[0] >= 1e-3, best_dw

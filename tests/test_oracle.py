@@ -322,3 +322,57 @@ def test_contract_golden_equals_a_live_oracle_run(oracles):
         g = f.copy()
         g[0, 0, 0] ^= 1
         assert oracle_cache.lookup(oracle_cache.frame_key(stem, hw, cfg, faces, i), g, hw) is None
+
+
+def test_variant_golden_equals_a_live_oracle_run(oracles):
+    """tests/golden/contract_oracle_variants.npz (tools/make_contract_golden.py --variants) serves the GPU tests the oracle's results on the
+    photometric variants of tests/frame_variants.py: re-derive one entry per variant live, alternating the models and walking the frame
+    index, with the checks of the 1280 x 896 file above; every variant holds FRAMES frames per model, and a frame whose pixels differ from
+    the minted one is not served."""
+    import oracle_cache
+    import frame_variants as fv
+    assert os.path.getsize(oracle_cache.GOLDEN_VARIANTS) <= 1_000_000
+    configs = [v.config for v in fv.VARIANTS.values()]
+    assert len(set(configs)) == len(configs) and not set(configs) & {300, 301, 305, 400, 401, 402, 403, 404, 410, 411}
+    for k, name in enumerate(fv.ALL):
+        stem = STEMS[k % 2]
+        frames = fv.variant_frames(name)
+        assert len(frames) == fv.FRAMES and all(f.shape == fv.HW + (3,) and f.dtype == np.uint8 for f in frames)
+        assert all(oracle_cache.lookup(fv.frame_key(s, name, j), f, fv.HW) is not None for s in STEMS for j, f in enumerate(frames)), name
+        i = (3 * k) % fv.FRAMES
+        f = frames[i]
+        hit = oracle_cache.lookup(fv.frame_key(stem, name, i), f, fv.HW)
+        live = oracles[stem].detect(f, 0.5, 0.4, net_hw=fv.HW)
+        assert np.allclose(hit.rows(), live.rows(), rtol=0, atol=2e-3) and np.array_equal(hit.anchor_indices(), live.anchor_indices()), (stem, name)
+        assert [c.anchor_index for c in hit.candidates] == [c.anchor_index for c in live.candidates], (stem, name)
+        assert all(np.allclose(a.as_row(), b.as_row(), rtol=0, atol=2e-3) for a, b in zip(hit.candidates, live.candidates)) and len(hit.detections) >= 1
+        assert abs(hit.band - oracle_cache.band_of(live.heads)) <= 1
+        g = f.copy()
+        g[0, 0, 0] ^= 1
+        assert oracle_cache.lookup(fv.frame_key(stem, name, i), g, fv.HW) is None
+
+
+def test_frame_variants_defaults_and_transforms():
+    """synth_frames' canvas / background options: the defaults reproduce the plain frames byte for byte, the photo background is cut from
+    face-free regions only, an unknown background is refused, and every variant is off the mid-grey band in the direction it is named for."""
+    import frame_variants as fv
+    from retinaface_amd.frames import BG_TILE, FACE_BOXES, _face_free_origins, load_base_frame, synth_frames
+    plain = synth_frames(256, 320, 2, config=7, faces=[1, 3, 5])
+    assert all(np.array_equal(a, b) for a, b in zip(plain, synth_frames(256, 320, 2, config=7, faces=[1, 3, 5], canvas=128, background=None)))
+    org = _face_free_origins(load_base_frame())
+    assert len(org) > 100
+    for x1, y1, x2, y2 in FACE_BOXES:
+        cx, cy, w, h = (x1 + x2) / 2, (y1 + y2) / 2, (x2 - x1) * 1.5, (y2 - y1) * 1.5
+        clear = (org[:, 1] + BG_TILE <= cx - w / 2) | (cx + w / 2 <= org[:, 1]) | (org[:, 0] + BG_TILE <= cy - h / 2) | (cy + h / 2 <= org[:, 0])
+        assert clear.all()
+    with pytest.raises(ValueError, match="background"):
+        synth_frames(448, 448, 1, background="stripes")
+    mean = {n: float(np.mean([f.mean() for f in fv.variant_frames(n, 4)])) for n in fv.NAMES}
+    std = {n: float(np.mean([f.std() for f in fv.variant_frames(n, 4)])) for n in fv.NAMES}
+    assert mean["dark"] < 60 and mean["bright"] > 180 and mean["gamma05"] > mean["gamma20"] + 60, mean
+    assert std["lowcon"] < 0.3 * std["highcon"] and mean["black"] < 40 and mean["white"] > 190 and std["noise"] > 60 and std["photo"] > 2 * std["lowcon"], (mean, std)
+    # the lookup tables round to nearest and clip: dark 0.4 * 133 = 53.2 -> 53; lowcon 128 + 0.4 * (5 - 128) = 78.8 -> 79; bright 1.6 * 255 -> 255
+    probe = np.array([[[5, 15, 133], [125, 0, 255]]], np.uint8)
+    assert fv.VARIANTS["dark"].transform(probe).tolist() == [[[2, 6, 53], [50, 0, 102]]]
+    assert fv.VARIANTS["lowcon"].transform(probe).tolist() == [[[79, 83, 130], [127, 77, 179]]]
+    assert fv.VARIANTS["bright"].transform(probe).tolist() == [[[8, 24, 213], [200, 0, 255]]]
