@@ -155,10 +155,7 @@ public:
         // treats every device frame as foreign so the scatter path runs on a one-GPU box)
         force_scatter_ = knob(K_FORCE_SCATTER) != 0;
         scatter_per_frame_ = knob(K_SCATTER_PER_FRAME) != 0;
-        if (knob(K_SYNC_SPLIT) == 0) stage_pieces_ = 1;
-        else if (const char *e = getenv("RF_SYNC_PIECES")) { const int v = atoi(e); if (v >= 1 && v <= 64) stage_pieces_ = v; }      // measurement knob of the A/B
-        head_start_max_ = knob(K_HEAD_START) ? opt_.max_batch : 0;      // launches of up to max_batch images = synchronous calls and un-coalesced tickets
-        copy_streams_ = knob(K_COPY_STREAMS) > 1 ? 2 : 1;       // probe knob RF_COPY_STREAMS (tools/probes/host_rate.py)
+        stage_pieces_ = knob(K_SYNC_SPLIT) == 0 ? 1 : knob(K_SYNC_PIECES);      // RF_SYNC_PIECES: measurement knob of the A/B
         check_residency_ = ndev > 1 || force_scatter_;
         DeviceGuard guard(device_);                  // the caller's current device is put back when construction ends
         if (sizeof(T) == 1) {
@@ -193,7 +190,7 @@ public:
         }
         const int hw = (int)std::thread::hardware_concurrency();
         const int helpers = opt_.copy_threads > 0 ? opt_.copy_threads - 1 : std::max(0, std::min(8, hw / 4) - 1);
-        copier_.reset(new ParallelCopier(helpers, knob(K_NT_COPY) != 0));       // RF_NT_COPY=0 (probe knob): plain memcpy into the staging block
+        copier_.reset(new ParallelCopier(helpers, true));       // non-temporal stores into the staging block
     }
 
     ~EngineImpl() override {
@@ -448,10 +445,9 @@ private:
         bool built = false;
         std::vector<void *> dev_allocs, host_allocs;      // what build_lane allocated for this lane
         hipStream_t stream = nullptr;
-        int cus = 0;                          // CUs the stream may use (0 = all): persistent grids of this lane's launches are sized by it
         unsigned long long launch_seq = 0;    // order of this lane's last launch among all launches of the engine (pick_lane)
         // host-frame uploads from the pinned staging block alternate between the lane's stream and a second one (a second SDMA
-        // engine); the launch waits for both.  RF_COPY_STREAMS=1 (probe knob) switches the second stream off
+        // engine); the launch waits for both
         hipStream_t copy2 = nullptr;
         hipEvent_t copy2_done = nullptr;
         bool copy2_used = false;
@@ -571,24 +567,11 @@ private:
         const int mb = cap_images_;           // images per launch: max_batch * coalesce
         const int H = net_h_, W = net_w_;
         const double P = (double)H * W;
-        // RF_CU_SPLIT=1 (probe knob): lane l runs on one half of every XCD's CUs (the mask's low / high 128 bits: measured with
-        // tools/probes/cu_mask.cpp -- 128 distinct CUs, all 8 XCDs, honoured by graph replays), halves alternating by lane, so that two lanes'
-        // DIFFERENT kernels (a VALU-bound stem beside an HBM-bound block) share the chip spatially instead of queueing for each other's slots
-        const int lane_index = (int)(&L - lanes_.data());
-        if (knob(K_CU_SPLIT) == 1 && lanes_.size() > 1) {
-            uint32_t mask[8];
-            for (int i = 0; i < 8; i++) mask[i] = ((lane_index & 1) == 0) == (i < 4) ? 0xffffffffu : 0u;
-            RF_HIP(hipExtStreamCreateWithCUMask(&L.stream, 8, mask));
-            L.cus = 128;
-        } else {
-            RF_HIP(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
-        }
+        RF_HIP(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
         for (auto &e : L.time_ev) RF_HIP(hipEventCreate(&e));
         RF_HIP(hipEventCreateWithFlags(&L.done, hipEventDisableTiming));
-        if (copy_streams_ > 1) {
-            RF_HIP(hipStreamCreateWithFlags(&L.copy2, hipStreamNonBlocking));
-            RF_HIP(hipEventCreateWithFlags(&L.copy2_done, hipEventDisableTiming));
-        }
+        RF_HIP(hipStreamCreateWithFlags(&L.copy2, hipStreamNonBlocking));
+        RF_HIP(hipEventCreateWithFlags(&L.copy2_done, hipEventDisableTiming));
 
         L.table_bytes = 2 * mb * sizeof(FrameDesc) + sizeof(RunParams);
         unsigned char *htab = halloc<unsigned char>(L.table_bytes);
@@ -617,74 +600,68 @@ private:
         T *cur = nullptr;
         size_t first_block = 0;
         int c = 8;
-        bool fused2 = false;
-        if constexpr (std::is_same<T, half_t>::value) fused2 = stem2_variant() != 0;
-        if (fused2) {
-            if constexpr (std::is_same<T, half_t>::value) {
-                // fp16 engine: preprocess + conv0 + blocks 0 and 1 (conv1..conv4) are ONE launch (stem2_kernel): the 224^2 x 16 map of
-                // the net never exists in HBM
-                const auto &b0 = plan.blocks[0], &b1 = plan.blocks[1];
-                const int h4 = H / 4, w4 = W / 4;
-                T *out = act(b1.pw.out_blob, h4, w4, b1.pw.cout);
-                Stem2Params sp;
-                sp.frames = L.d_frames + mb; sp.out = out;
-                sp.w0 = arena_.template ptr<half_t>(c0_hi_); sp.b0 = arena_.template ptr<float>(WP::c0_b_mma_);
-                sp.w0_raw = arena_.template ptr<half_t>(WP::c0_raw_);
-                sp.c0_tab = arena_.template ptr<uint32_t>(WP::stem2_c0tab_); sp.dw1_mma4 = arena_.template ptr<uint32_t>(WP::stem2_dw4_);
-                sp.dw0_w = arena_.template ptr<float>(stem_dw_.w); sp.dw0_b = arena_.template ptr<float>(stem_dw_.b);
-                sp.pw0_w = arena_.template ptr<half_t>(stem_pw_.w); sp.pw0_b = arena_.template ptr<float>(WP::stem2_c2_b_);
-                sp.c2_floor = arena_.template ptr<uint32_t>(WP::stem2_c2_floor_); sp.c3_floor = arena_.template ptr<uint32_t>(WP::stem2_c3_floor_);
-                sp.dw1_mma = arena_.template ptr<uint32_t>(stem2_dw_.mma); sp.dw1_b = arena_.template ptr<float>(stem2_dw_.b);
-                sp.pw1_w = arena_.template ptr<half_t>(stem2_pw_.w); sp.pw1_b = arena_.template ptr<float>(stem2_pw_.b);
-                sp.n = 0; sp.net_h = H; sp.net_w = W;
-                OpInfo op;
-                op.name = "pre+" + plan.conv0.name + "+" + b0.dw.name + "+" + b0.pw.name + "+" + b1.dw.name + "+" + b1.pw.name;
-                op.kernel = "stem2";
-                op.alg_u8_in = 3.0 * P;
-                // layer-wise accounting: every covered layer's input + output elements, fused or not
-                op.alg_elems_in = 8.0 * h * w + 8.0 * h * w + 16.0 * h * w + 16.0 * h4 * w4;                       // conv1, conv2, conv3, conv4 inputs
-                op.alg_elems_out = 8.0 * h * w + 8.0 * h * w + 16.0 * h * w + 16.0 * h4 * w4 + 32.0 * h4 * w4;     // conv0 .. conv4 outputs
-                op.macs = (plan.conv0.macs_per_out_pixel() + b0.dw.macs_per_out_pixel() + b0.pw.macs_per_out_pixel()) * h * w +
-                          (b1.dw.macs_per_out_pixel() + b1.pw.macs_per_out_pixel()) * h4 * w4;
-                op.hbm_elems_out = 32.0 * h4 * w4;                        // the frame in (alg_u8_in), the 32-channel net/4 map out
-                op.launch = [sp](hipStream_t s, int n) { Stem2Params q = sp; q.n = n; launch_stem2(s, q); };
-                L.ops.push_back(op);
-                cur = out; c = b1.pw.cout; first_block = 2; h = h4; w = w4;
-                if (dwpw2_variant() && plan.blocks.size() > 3 && plan.blocks[2].dw.cout == 32 && plan.blocks[2].pw.cout == 32 &&
-                    plan.blocks[3].dw.stride == 2 && plan.blocks[3].pw.cout == 64) {
-                    // blocks 2 and 3 (conv5..conv8) as ONE launch (dwpw2_kernel): the 112^2 x 32 map between them stays in LDS
-                    const auto &ba = plan.blocks[2], &bb = plan.blocks[3];
-                    T *out2 = act(bb.pw.out_blob, h / 2, w / 2, bb.pw.cout);
-                    DwPw2Params dp;
-                    dp.in = cur; dp.out = out2;
-                    dp.dwa_mma = arena_.template ptr<uint32_t>(dw_w_[2].mma); dp.dwa_b = arena_.template ptr<float>(dw_w_[2].b);
-                    dp.pwa_w = arena_.template ptr<half_t>(pw_w_[2].w); dp.pwa_b = arena_.template ptr<float>(pw_w_[2].b);
-                    dp.dwb_mma = arena_.template ptr<uint32_t>(dw_w_[3].mma); dp.dwb_b = arena_.template ptr<float>(dw_w_[3].b);
-                    dp.pwb_w = arena_.template ptr<half_t>(pw_w_[3].w); dp.pwb_b = arena_.template ptr<float>(pw_w_[3].b);
-                    dp.n = 0; dp.hin = h; dp.win = w;
-                    OpInfo o2;
-                    o2.name = ba.dw.name + "+" + ba.pw.name + "+" + bb.dw.name + "+" + bb.pw.name;
-                    o2.kernel = "dwpw2<32,32,64>";
-                    const double pa = (double)h * w, pb = (double)(h / 2) * (w / 2);
-                    o2.alg_elems_in = 32.0 * pa + 32.0 * pa + 32.0 * pa + 32.0 * pb;          // dw A, pw A, dw B, pw B inputs (layer-wise)
-                    o2.alg_elems_out = 32.0 * pa + 32.0 * pa + 32.0 * pb + 64.0 * pb;
-                    o2.macs = (ba.dw.macs_per_out_pixel() + ba.pw.macs_per_out_pixel()) * pa + (bb.dw.macs_per_out_pixel() + bb.pw.macs_per_out_pixel()) * pb;
-                    o2.hbm_elems_in = 32.0 * pa; o2.hbm_elems_out = 64.0 * pb;
-                    o2.launch = [dp](hipStream_t s, int n) { DwPw2Params q = dp; q.n = n; launch_dwpw2(s, q); };
-                    L.ops.push_back(o2);
-                    cur = out2; c = bb.pw.cout; first_block = 4; h /= 2; w /= 2;
-                }
+        if constexpr (std::is_same<T, half_t>::value) {
+            // fp16 engine: preprocess + conv0 + blocks 0 and 1 (conv1..conv4) are ONE launch (stem2_kernel): the 224^2 x 16 map of
+            // the net never exists in HBM
+            const auto &b0 = plan.blocks[0], &b1 = plan.blocks[1];
+            const int h4 = H / 4, w4 = W / 4;
+            T *out = act(b1.pw.out_blob, h4, w4, b1.pw.cout);
+            Stem2Params sp;
+            sp.frames = L.d_frames + mb; sp.out = out;
+            sp.w0 = arena_.template ptr<half_t>(c0_hi_); sp.b0 = arena_.template ptr<float>(WP::c0_b_mma_);
+            sp.w0_raw = arena_.template ptr<half_t>(WP::c0_raw_);
+            sp.dw0_w = arena_.template ptr<float>(stem_dw_.w); sp.dw0_b = arena_.template ptr<float>(stem_dw_.b);
+            sp.pw0_w = arena_.template ptr<half_t>(stem_pw_.w); sp.pw0_b = arena_.template ptr<float>(WP::stem2_c2_b_);
+            sp.c2_floor = arena_.template ptr<uint32_t>(WP::stem2_c2_floor_); sp.c3_floor = arena_.template ptr<uint32_t>(WP::stem2_c3_floor_);
+            sp.dw1_mma = arena_.template ptr<uint32_t>(stem2_dw_.mma); sp.dw1_b = arena_.template ptr<float>(stem2_dw_.b);
+            sp.pw1_w = arena_.template ptr<half_t>(stem2_pw_.w); sp.pw1_b = arena_.template ptr<float>(stem2_pw_.b);
+            sp.n = 0; sp.net_h = H; sp.net_w = W;
+            OpInfo op;
+            op.name = "pre+" + plan.conv0.name + "+" + b0.dw.name + "+" + b0.pw.name + "+" + b1.dw.name + "+" + b1.pw.name;
+            op.kernel = "stem2";
+            op.alg_u8_in = 3.0 * P;
+            // layer-wise accounting: every covered layer's input + output elements, fused or not
+            op.alg_elems_in = 8.0 * h * w + 8.0 * h * w + 16.0 * h * w + 16.0 * h4 * w4;                       // conv1, conv2, conv3, conv4 inputs
+            op.alg_elems_out = 8.0 * h * w + 8.0 * h * w + 16.0 * h * w + 16.0 * h4 * w4 + 32.0 * h4 * w4;     // conv0 .. conv4 outputs
+            op.macs = (plan.conv0.macs_per_out_pixel() + b0.dw.macs_per_out_pixel() + b0.pw.macs_per_out_pixel()) * h * w +
+                      (b1.dw.macs_per_out_pixel() + b1.pw.macs_per_out_pixel()) * h4 * w4;
+            op.hbm_elems_out = 32.0 * h4 * w4;                        // the frame in (alg_u8_in), the 32-channel net/4 map out
+            op.launch = [sp](hipStream_t s, int n) { Stem2Params q = sp; q.n = n; launch_stem2(s, q); };
+            L.ops.push_back(op);
+            cur = out; c = b1.pw.cout; first_block = 2; h = h4; w = w4;
+            if (plan.blocks.size() > 3 && plan.blocks[2].dw.cout == 32 && plan.blocks[2].pw.cout == 32 &&
+                plan.blocks[3].dw.stride == 2 && plan.blocks[3].pw.cout == 64) {
+                // blocks 2 and 3 (conv5..conv8) as ONE launch (dwpw2_kernel): the 112^2 x 32 map between them stays in LDS
+                const auto &ba = plan.blocks[2], &bb = plan.blocks[3];
+                T *out2 = act(bb.pw.out_blob, h / 2, w / 2, bb.pw.cout);
+                DwPw2Params dp;
+                dp.in = cur; dp.out = out2;
+                dp.dwa_mma = arena_.template ptr<uint32_t>(dw_w_[2].mma); dp.dwa_b = arena_.template ptr<float>(dw_w_[2].b);
+                dp.pwa_w = arena_.template ptr<half_t>(pw_w_[2].w); dp.pwa_b = arena_.template ptr<float>(pw_w_[2].b);
+                dp.dwb_mma = arena_.template ptr<uint32_t>(dw_w_[3].mma); dp.dwb_b = arena_.template ptr<float>(dw_w_[3].b);
+                dp.pwb_w = arena_.template ptr<half_t>(pw_w_[3].w); dp.pwb_b = arena_.template ptr<float>(pw_w_[3].b);
+                dp.n = 0; dp.hin = h; dp.win = w;
+                OpInfo o2;
+                o2.name = ba.dw.name + "+" + ba.pw.name + "+" + bb.dw.name + "+" + bb.pw.name;
+                o2.kernel = "dwpw2<32,32,64>";
+                const double pa = (double)h * w, pb = (double)(h / 2) * (w / 2);
+                o2.alg_elems_in = 32.0 * pa + 32.0 * pa + 32.0 * pa + 32.0 * pb;          // dw A, pw A, dw B, pw B inputs (layer-wise)
+                o2.alg_elems_out = 32.0 * pa + 32.0 * pa + 32.0 * pb + 64.0 * pb;
+                o2.macs = (ba.dw.macs_per_out_pixel() + ba.pw.macs_per_out_pixel()) * pa + (bb.dw.macs_per_out_pixel() + bb.pw.macs_per_out_pixel()) * pb;
+                o2.hbm_elems_in = 32.0 * pa; o2.hbm_elems_out = 64.0 * pb;
+                o2.launch = [dp](hipStream_t s, int n) { DwPw2Params q = dp; q.n = n; launch_dwpw2(s, q); };
+                L.ops.push_back(o2);
+                cur = out2; c = bb.pw.cout; first_block = 4; h /= 2; w /= 2;
             }
-        } else if constexpr (sizeof(T) == 1 || (sizeof(T) == 2 && kProbeBuild)) {
-            // int8 engine (and the fp16 engine of the probe build with RF_STEM2=0): preprocess + conv0 + the first depthwise/pointwise
+        } else if constexpr (sizeof(T) == 1) {
+            // int8 engine: preprocess + conv0 + the first depthwise/pointwise
             // block are ONE launch (stem_kernel); it computes in fp16 and stores its 16-channel output in the engine's storage type
             const auto &blk = plan.blocks[0];
             T *out = act(blk.pw.out_blob, h, w, blk.pw.cout);
             StemParams<T> sp;
             sp.frames = L.d_frames + mb; sp.out = out;
             sp.w0 = arena_.template ptr<half_t>(c0_hi_); sp.b0 = arena_.template ptr<float>(WP::c0_b_mma_);
-            sp.w0_raw = knob(K_STEM_RAW) ? arena_.template ptr<half_t>(WP::c0_raw_) : nullptr;
-            sp.c0_tab = knob(K_STEM_RAW) == 2 ? arena_.template ptr<uint32_t>(WP::stem_c0tab_) : nullptr;
+            sp.w0_raw = arena_.template ptr<half_t>(WP::c0_raw_);
             sp.dw_w = arena_.template ptr<float>(stem_dw_.w); sp.dw_b = arena_.template ptr<float>(stem_dw_.b);
             sp.pw_w = arena_.template ptr<half_t>(stem_pw_.w); sp.pw_b = arena_.template ptr<float>(stem_pw_.b);
             sp.pw_m = mult_ptr(stem_pw_);
@@ -788,8 +765,7 @@ private:
         Level3 lv_a, lv_b, lv_c;
         OpInfo op_a, op_b, op_c, op_h;
         // fp16 / int8: conv_b and conv_c of the context module are ONE launch (ssh_tail_kernel); context_conv3_1 stays in LDS
-        bool fuse_tail = false;
-        if constexpr (sizeof(T) <= 2) fuse_tail = ssh_tail_variant() != 0;
+        constexpr bool fuse_tail = sizeof(T) <= 2;
         struct Tail3 { SshTailParams<T> p[3]; } tl;
         struct HeadLevels { HeadParams<T> p[3]; } hl;
         int anchor_off = 0;
@@ -1112,17 +1088,7 @@ private:
         }
         const bool eager_timed = s.timed;
         if (eager_timed) RF_HIP(hipEventRecord(s.time_ev[1], s.stream));
-        bind_launch_cus(s.cus);
-        struct Unbind { ~Unbind() { bind_launch_cus(0); } } unbind;
-        if (opt_.use_graph && s.warmed.count(n) && n <= head_start_max_ && s.ops.size() > 2) {
-            // Head start for small launches (round 5, RF_HEAD_START): hipGraphLaunch costs the host ~16 us before the first kernel can start, a
-            // tenth of a synchronous batch-8 call.  The first kernel (the stem: the longest of a small launch, 13 us at batch 8) is launched
-            // eagerly -- ~3 us of host time -- and the graph of the remaining launches is submitted while it runs.
-            auto it = s.graphs.find(-n);
-            if (it == s.graphs.end()) it = s.graphs.emplace(-n, capture(s, n, 1)).first;
-            s.ops[0].launch(s.stream, n);
-            RF_HIP(hipGraphLaunch(it->second, s.stream));
-        } else if (opt_.use_graph && s.warmed.count(n)) {
+        if (opt_.use_graph && s.warmed.count(n)) {
             auto it = s.graphs.find(n);
             if (it == s.graphs.end()) it = s.graphs.emplace(n, capture(s, n)).first;
             RF_HIP(hipGraphLaunch(it->second, s.stream));
@@ -1324,13 +1290,13 @@ private:
         }
     }
 
-    hipGraphExec_t capture(Lane &L, int n, size_t first_op = 0) {
+    hipGraphExec_t capture(Lane &L, int n) {
         hipGraph_t g = nullptr;
         hipGraphExec_t ge = nullptr;
         RF_HIP(hipStreamBeginCapture(L.stream, hipStreamCaptureModeThreadLocal));
         std::string err;
         try {
-            for (size_t k = first_op; k < L.ops.size(); k++) L.ops[k].launch(L.stream, n);
+            for (size_t k = 0; k < L.ops.size(); k++) L.ops[k].launch(L.stream, n);
         } catch (const std::exception &e) { err = e.what(); }
         hipError_t end = hipStreamEndCapture(L.stream, &g);
         if (!err.empty() || end != hipSuccess || !g)
@@ -1348,8 +1314,6 @@ private:
     int stage_pieces_ = 4;                    // most pieces a synchronous host-frame call is staged + sent in (RF_SYNC_SPLIT=0: one, as rounds 1-5; RF_SYNC_PIECES=n)
     static constexpr size_t kStagePieceBytes = 1200 << 10;      // ~2 frames of 448 x 448: 24 us on the bus, ~15 us of staging
     long staged_pieces_ = 0;
-    int copy_streams_ = 2;
-    int head_start_max_ = 0;                   // launches of at most this many images start their first kernel eagerly ahead of the graph
     long scattered_frames_ = 0;               // device frames that arrived from another device
     long peer_copies_ = 0;                    // ... in this many hipMemcpyPeerAsync calls (one per contiguous run of frames)
     std::vector<float> ratios_;                // the network preset's anchor ratios (empty: a preset without anchors)
@@ -1395,8 +1359,6 @@ void prepare_pack(const std::string &model_dir, const EngineOptions &opt, Plan *
     key.build = 1469598103934665603ull;
     for (const char *c = __DATE__ " " __TIME__ " " __FILE__; *c; c++) { key.build ^= (unsigned char)*c; key.build *= 1099511628211ull; }
     key.precision = opt.precision;
-    key.stem2 = std::is_same<T, half_t>::value ? stem2_variant() : 0;
-    if (knob(K_STEM2_DC) == 0) key.stem2 |= 0x100;     // probe knob RF_STEM2_DC: another packed image
     const std::string path = opt.plan_cache_path.empty() ? plan_cache_path(model_dir, opt.model_stem, opt.precision) : opt.plan_cache_path;
     *from_cache = false;
     if (opt.plan_cache) {

@@ -11,13 +11,6 @@ namespace rf {
 
 typedef _Float16 half_t;
 
-// RF_PROBES: the probe build (make probe), which also holds the measured-and-rejected kernel variants and the RF_* probe knobs (knobs.h)
-#ifdef RF_PROBES
-constexpr bool kProbeBuild = true;
-#else
-constexpr bool kProbeBuild = false;
-#endif
-
 // a request the engine has no kernel instance / configuration for (C ABI: RF_ERR_UNSUPPORTED)
 struct Unsupported : std::runtime_error { using std::runtime_error::runtime_error; };
 
@@ -28,8 +21,6 @@ template <> struct DwWeightT<int8_t> { typedef float type; };
 // The launch helpers keep per-device state (CU count, LDS attribute / occupancy of each kernel instance); the engine tells
 // them which device the calling thread is bound to (engine.cpp DeviceGuard).
 void bind_launch_device(int device);
-// ... and how many CUs the stream it is about to launch on may use (0 = all of the device's): persistent grids are sized by it
-void bind_launch_cus(int cus);
 // int8 engines: 0 when v_cvt_pk_u8_f32 on the bound device rounds to nearest even and saturates (what the requantising epilogues rely on),
 // 1 when it does not (cached per device), -1 when the probe could not run (a runtime error: not cached)
 int cvt_pk_u8_selfcheck();
@@ -64,13 +55,13 @@ template <typename T>
 void launch_conv0(hipStream_t s, const FrameDesc *frames, T *out, const float *w, const float *b, int n, int net_h,
                   int net_w);
 
-// ---- K_a' (fp16 engine): K_a fused with the first depthwise/pointwise block; conv0 on MFMA (hi+lo split weights).
+// ---- K_a' (int8 engine): K_a fused with the first depthwise/pointwise block; conv0 on MFMA (hi+lo split weights), computed in fp16.
 template <typename TO>
 struct StemParams {
     const FrameDesc *frames; TO *out;              // out: [n][net_h/2][net_w/2][16], fp16 or int8
     const half_t *w0; const float *b0;             // conv0: 4 A fragments (hi/lo x k<32/k>=32), K = (ky,kx,BGRX) 36 -> 64
     const half_t *w0_raw = nullptr;                // ... for the raw-row staging (weights.h c0_raw_), nullptr = general path only
-    const uint32_t *c0_tab = nullptr;              // conv0 pixel table of the raw path (pack.h stem_conv0_table), nullptr = index arithmetic
+    const uint32_t *c0_tab = nullptr;              // conv0 pixel table of the raw path (measured slower; the engine passes nullptr = index arithmetic)
     const float *dw_w; const float *dw_b;          // depthwise taps [9][8], fp32
     const half_t *pw_w; const float *pw_b;         // pointwise 16 x 8 as one A fragment with K slots [hi | hi | lo | 0] (pack.h)
     const float *pw_m = nullptr;                   // int8 output: 1 / out_scale per channel (pw_b pre-divided)
@@ -83,8 +74,6 @@ struct Stem2Params {
     const FrameDesc *frames; half_t *out;          // out: [n][net_h/4][net_w/4][32]
     const half_t *w0; const float *b0;
     const half_t *w0_raw = nullptr;                // conv0 fragments of the raw-row staging (weights.h c0_raw_): [2 parities][4][64][8]
-    const uint32_t *c0_tab = nullptr;              // conv0 pixel table of the raw path (pack.h stem2_conv0_table): [4][6][64] x uint2
-    const uint32_t *dw1_mma4 = nullptr;            // conv3's diagonal A fragments expanded: [5][64][4] dwords (weights.h stem2_dw4_)
     const float *dw0_w; const float *dw0_b; const half_t *pw0_w; const float *pw0_b;
     const uint32_t *dw1_mma; const float *dw1_b;   // conv3: taps as diagonal MFMA A fragments [5][64] dwords (pack.h), bias [16]
     const half_t *pw1_w; const float *pw1_b;       // conv4: 32 x 16 as hi | lo along K (k < 16: rn16(w), k >= 16: rn16(w - hi)), MFMA-fragment packed, bias [32]
@@ -93,7 +82,6 @@ struct Stem2Params {
     int n, net_h, net_w;
 };
 void launch_stem2(hipStream_t s, const Stem2Params &p);
-int stem2_variant();      // 0 = off (K_a' + a separate dwpw<16,32,s2> launch), 1 = 7x8 tiles, 2 = 7x16, 3 = 7x8 fp16 patch (probe knob RF_STEM2)
 
 // ---- K_b: depthwise 3x3 (+BN+ReLU) -> pointwise 1x1 (+BN+ReLU), the intermediate never leaves LDS.
 //      has_dw = false gives a plain 1x1 conv (+bias, +ReLU): the FPN laterals.
@@ -123,7 +111,6 @@ struct DwPw2Params {
     int n, hin, win;
 };
 void launch_dwpw2(hipStream_t s, const DwPw2Params &p);
-int dwpw2_variant();     // probe knob RF_DWPW2: 0 = off
 
 // ---- K_c: dense 3x3 p1 s1 conv as an implicit GEMM on MFMA (+bias +ReLU).  Optional fused input
 //      "lateral + bilinear x2 upsample(coarser)" (Deconvolution k4 s2 p1 + Crop + Eltwise SUM,
@@ -154,7 +141,6 @@ struct SshTailParams {
     int n, h, w_;
 };
 template <typename T> void launch_ssh_tail(hipStream_t s, const SshTailParams<T> *levels, int nlevels);   // 1..3 FPN levels per launch
-int ssh_tail_variant();     // probe knob RF_SSHTAIL: 0 = off (two conv3x3<16,*> launches)
 
 // ---- K_d: the three 1x1 heads of one stride as one 64->32 GEMM + 2-class softmax + anchor decode +
 //      bbox / landmark regression + clip + threshold compaction (RetinaFace.cpp:666-724, 378-432, 179-199).

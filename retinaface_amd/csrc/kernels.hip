@@ -12,13 +12,7 @@
 
 #include <atomic>
 
-#include "knobs.h"
 #include "pack.h"
-
-// RF_PROBES (make probe -> libretinaface_amd_probe.so): the measured-and-rejected kernel variants DESIGN.md cites and the RF_* probe knobs that
-// select them.  The product library is compiled WITHOUT them: every `#ifdef RF_PROBES` block below is a variant that lost its A/B measurement
-// (profiles/r0N_*), kept buildable so the evidence stays reproducible (tests/test_gpu_parity.py::test_probe_knob_kernel_variants_stay_correct
-// runs them through the probe build).
 
 namespace rf {
 
@@ -85,10 +79,10 @@ template <typename V, int N> __device__ __forceinline__ V vzero() {
 
 constexpr int kThreads = 256;   // 4 wavefronts
 
-// Phase timeline of a workgroup (probe builds only: make TRACE=1 -> libretinaface_amd_trace.so, tools/probes/phase_trace.py).
+// Phase timeline of a workgroup (trace build only: make trace -> libretinaface_amd_trace.so, tools/probes/phase_trace.py).
 // Wave 0 of every workgroup stamps s_memtime at each phase boundary of the kernel selected by g_trace_kernel.
 #ifdef RF_KERNEL_TRACE
-// probe build only (make trace; tools/probes/phase_trace.py): thread 0 of every workgroup stamps s_memtime at phase
+// trace build only (make trace; tools/probes/phase_trace.py): thread 0 of every workgroup stamps s_memtime at phase
 // boundaries of the launch whose tile count equals g_trace_key (tile counts identify a launch; grids are derived)
 constexpr int kTraceSlots = 12, kTraceBlocks = 8192;
 __device__ unsigned long long g_trace[kTraceBlocks * kTraceSlots];
@@ -138,11 +132,7 @@ typedef Unsupported LaunchUnsupported;
 // Persistent grid: as many workgroups as the chip keeps resident (CUs x RESIDENT), trimmed so every workgroup walks the
 // same number of tiles (no nearly-empty last round).  Launches with fewer tiles than that get one tile per workgroup.
 static std::atomic<int> g_num_cus[kMaxDevices] = {};
-// a lane whose stream is confined to a subset of the CUs (hipExtStreamCreateWithCUMask, engine.cpp RF_CU_SPLIT) sizes its persistent grids for that subset
-static thread_local int t_launch_cus = 0;
-void bind_launch_cus(int cus) { t_launch_cus = cus; }
 static int num_cus() {
-    if (t_launch_cus > 0) return t_launch_cus;
     const int dev = launch_device();
     int cus = g_num_cus[dev].load(std::memory_order_relaxed);
     if (!cus) {
@@ -156,13 +146,7 @@ static int num_cus() {
 // Below `min_rounds` x resident tiles the hardware dispatcher's dynamic one-tile-per-workgroup schedule is at least as
 // good as walking two tiles in sequence, so the grid stays one workgroup per tile.
 static int persistent_grid(int tiles, int resident_per_cu) {
-    const float frac = knob_grid_frac();           // probe knob RF_GRID_FRAC (1 in the product): leave a share of the resident slots to the other lanes' kernels
-    if (frac < 1.f) {
-        const int slots = num_cus() * (resident_per_cu > 0 ? resident_per_cu : 1);
-        const int part = (int)((float)slots * frac);
-        return persistent_grid_size(tiles, part > 0 ? part : 1, 0.f);
-    }
-    return persistent_grid_size(tiles, num_cus() * (resident_per_cu > 0 ? resident_per_cu : 1), knob_persist_min_rounds());      // (probe knob RF_PERSIST_MIN_ROUNDS; 1 measured on MI355X)
+    return persistent_grid_size(tiles, num_cus() * (resident_per_cu > 0 ? resident_per_cu : 1), 1.0f);      // min_rounds 1: measured on MI355X
 }
 template <typename F> static int resident_per_cu(F kern, size_t lds_bytes) {
     int nb = 0;
@@ -572,7 +556,7 @@ struct StemArgs {
     const FrameDesc *frames; TO *out;
     const half_t *w0;                 // conv0 weights: 4 A fragments [hi k<32 | lo k<32 | hi k>=32 | lo k>=32][64 lanes][8]
     const half_t *w0_raw;             // the same for the raw-row staging: [2 window types][4][64][8] (weights.h c0_raw_), or nullptr
-    const uint2 *c0_tab;              // conv0 pixel table of the raw path [4 waves][6 tiles][64 lanes] (pack.h stem_conv0_table), or nullptr
+    const uint2 *c0_tab;              // conv0 pixel table of the raw path [4 waves][6 tiles][64 lanes]; the engine passes nullptr
     const float *b0;                  // [8]
     const float *dw_w; const float *dw_b;     // depthwise taps [9][8] fp32
     const half_t *pw_w; const float *pw_b;    // pointwise 16 x 8 as ONE A fragment, K slots [hi | hi | lo | 0] (stem_pw_fragment, pack.h)
@@ -641,8 +625,10 @@ __global__ __launch_bounds__(kThreads, (StemCfg<TO>::OCC)) void stem_kernel(Stem
     // 3..11 of it for even conv0 columns (weights.h c0_raw_ set 1), 1..9 for odd ones (set 0).  Waves 0,1: even columns, 2,3: odd.
     const bool raw = ((((uintptr_t)fd.ptr) | (uintptr_t)(unsigned)fd.step) & 15u) == 0 && fd.cols == 2 * a.wo && a.w0_raw != nullptr;
 
-    // conv0's pixel table (as stem2_kernel, V2 bit 4): which pixel a lane of the wave's k-th tile computes comes from memory, not from the VALU
-    static_assert(ST_HR == kStemR0H && ST_HC == kStemR0W && C0_PLANE == kStemC0Plane, "pack.h stem_conv0_table is built for this geometry");
+    // conv0's pixel table ([4 waves][kStemC0Tiles][64 lanes] x uint2, measured slower than index arithmetic): which pixel a lane of the wave's k-th
+    // tile computes comes from memory, not from the VALU.  The engine passes no table (c0_tab = nullptr); the path stays only because removing it
+    // changes this kernel's code.
+    static_assert(ST_HR == kStemR0H && ST_HC == kStemR0W && C0_PLANE == kStemC0Plane, "stem geometry (pack.h)");
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     const bool tab = raw && a.c0_tab != nullptr;
     const uint2 *c0_tab = a.c0_tab + (wave_u * kStemC0Tiles) * 64;
@@ -898,9 +884,6 @@ template <typename TO> void launch_stem(hipStream_t s, const StemParams<TO> &p) 
     a.nblk = p.n * a.tiles_x * a.tiles_y;
     hipLaunchKernelGGL(stem_kernel<TO>, dim3(a.nblk), dim3(kThreads), 0, s, a);
 }
-#ifdef RF_PROBES
-template void launch_stem<half_t>(hipStream_t, const StemParams<half_t> &);       // fp16 engine with RF_STEM2=0 (K_a' + separate blocks)
-#endif
 template void launch_stem<int8_t>(hipStream_t, const StemParams<int8_t> &);
 
 // =============================================================================================
@@ -914,24 +897,21 @@ template void launch_stem<int8_t>(hipStream_t, const StemParams<int8_t> &);
 //   out) | 4 pointwise conv2 on MFMA -> fp16 tile (zero outside the map: it is conv3's padding) | 5 depthwise conv3 stride 2
 //   | 6 pointwise conv4 on MFMA | 7 coalesced NHWC store.  Numerics of phases 1-4 are exactly K_a' (same rounding points).
 // =============================================================================================
-template <int TW_, bool F16P, int PADKB = 0> struct Stem2Cfg {     // F16P: the staged patch holds fp16 (converted once) instead of u8; PADKB: unused LDS (occupancy probe)
-    static constexpr int TH = 7, TW = TW_, P4 = TH * TW;                // conv4 output tile
+struct Stem2Cfg {
+    static constexpr int TH = 7, TW = 8, P4 = TH * TW;                  // conv4 output tile
     static constexpr int R2H = 2 * TH + 1, R2W = 2 * TW + 1, N2 = R2H * R2W;     // conv2 pixels the tile needs
     static constexpr int R0H = R2H + 2, R0W = R2W + 2, N0 = R0H * R0W;           // conv0 / conv1-input pixels
     static constexpr int T0 = (N0 + 15) / 16, T2 = (N2 + 15) / 16, T4 = (P4 + 15) / 16;   // MFMA pixel tiles of conv0 / conv2 / conv4
     static constexpr int IR = 2 * R0H + 1, IPX = 2 * R0W + 1;                    // input rows / pixels per row
     static constexpr int GRP = (IPX + 3) / 4, ROWD = GRP * 4;                    // staging groups of 4 pixels, dwords per staged row
     static constexpr int LDA1 = 24, LDO = 40;                                    // conv3 result / output tile row pitch (fp16 elements)
-    static constexpr int IN_BYTES = IR * ROWD * (F16P ? 8 : 4), A_BYTES = T2 * 16 * 32;       // region A: patch (4 x fp16 per pixel) -> conv1 result (hi|lo, 32 B / pixel)
+    static constexpr int IN_BYTES = IR * ROWD * 4, A_BYTES = T2 * 16 * 32;       // region A: patch (BGRX u8 per pixel) -> conv1 result (hi|lo, 32 B / pixel)
     static constexpr int A1_BYTES = T4 * 16 * LDA1 * 2, OUT_BYTES = T4 * 16 * LDO * 2;   //           -> conv3 result + output tile
     static constexpr int C0_BYTES = T0 * 16 * 32, C2_BYTES = T2 * 16 * 32;       // region B: fp32 conv0 tile -> fp16 conv2 tile
-    static constexpr int MAX3(int a, int b, int c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }
-    static constexpr int REGION_A = MAX3(IN_BYTES, A_BYTES, A1_BYTES + OUT_BYTES);
+    static constexpr int REGION_A_ = IN_BYTES > A_BYTES ? IN_BYTES : A_BYTES;
+    static constexpr int REGION_A = REGION_A_ > A1_BYTES + OUT_BYTES ? REGION_A_ : A1_BYTES + OUT_BYTES;
     static constexpr int REGION_B = C0_BYTES > C2_BYTES ? C0_BYTES : C2_BYTES;
-    static constexpr int LDS_BYTES = REGION_A + REGION_B + 9 * 8 * 4 + PADKB * 1024;
-    // 7 x 8 tiles: 4 waves per workgroup; 7 x 16 tiles: the same work per thread with 8 waves (half the horizontal halo per output,
-    // twice the LDS per workgroup, the same 32 waves per CU)
-    static constexpr int THREADS = TW_ >= 16 ? 512 : 256;
+    static constexpr int LDS_BYTES = REGION_A + REGION_B + 9 * 8 * 4;
     static constexpr int OCC = LDS_BYTES <= 20 * 1024 ? 8 : LDS_BYTES <= 23 * 1024 ? 7 : (160 * 1024 / LDS_BYTES);
     static_assert(REGION_A % 16 == 0 && REGION_B % 16 == 0 && A1_BYTES % 16 == 0, "LDS carve must stay 16-byte aligned");
 };
@@ -940,8 +920,7 @@ struct Stem2Args {
     const FrameDesc *frames; half_t *out;           // out: [n][ho4][wo4][32]
     const half_t *w0; const float *b0;              // conv0 (as StemArgs)
     const half_t *w0_raw;                           // conv0 for the raw-row staging: [2 column parities][4 fragments][64][8] (weights.h c0_raw_)
-    const uint2 *c0_tab;                            // ... its pixel table [4 waves][6 tiles][64 lanes] (pack.h stem2_conv0_table)
-    const u32x4 *dw1_mma4;                          // conv3's diagonal A fragments expanded to 4 dwords per lane [5][64]
+    const void *unused_;                            // kernarg padding: without it the kernel compiles to 59 instead of 53 SGPRs
     const float *dw0_w; const float *dw0_b; const half_t *pw0_w; const float *pw0_b;     // conv1 / conv2 (as StemArgs)
     const uint32_t *dw1_mma; const float *dw1_b;    // conv3 taps as diagonal MFMA A fragments [5][64] dwords (pack.h dw_mma_dword), bias [16]
     const half_t *pw1_w; const float *pw1_b;        // conv4: 32 x 16 as hi | lo along K (32 K slots, all used), bias [32]
@@ -949,34 +928,31 @@ struct Stem2Args {
     int ho, wo, ho4, wo4, tiles_x, tiles_y, nblk;   // ho x wo = conv0 / conv2 map (net / 2), ho4 x wo4 = conv4 map (net / 4)
 };
 
-template <int TW_, bool F16P, int PADKB = 0, int V2 = 1>
-__global__ __launch_bounds__((Stem2Cfg<TW_, F16P, PADKB>::THREADS), (Stem2Cfg<TW_, F16P, PADKB>::OCC)) void stem2_kernel(Stem2Args a) {
-    typedef Stem2Cfg<TW_, F16P, PADKB> C;
-    constexpr int NT = C::THREADS, NW = NT / 64;         // threads / waves per workgroup
+__global__ __launch_bounds__(kThreads, Stem2Cfg::OCC) void stem2_kernel(Stem2Args a) {
+    typedef Stem2Cfg C;
+    constexpr int NT = kThreads, NW = NT / 64;           // threads / waves per workgroup
     typedef half_t T;
     typedef Mma<T> M;
     constexpr int TW = C::TW, P4 = C::P4, R2W = C::R2W, N2 = C::N2, R0W = C::R0W;
-    constexpr int ROWD = C::ROWD, GRP = C::GRP, IR = C::IR, LDA1 = C::LDA1, LDO = C::LDO;
+    constexpr int ROWD = C::ROWD, GRP = C::GRP, IR = C::IR, LDO = C::LDO;
     // fp32 conv0 tile as two channel planes [channels 0-3 | channels 4-7][pixel][4]: 16 consecutive pixels of a plane are 256
     // contiguous bytes (every ds_read/write_b128 of a 16-lane group is conflict-free) and a depthwise tap is the thread's base
     // address + a compile-time offset (the XOR-swizzled single plane of K_a' cost ~50 address instructions per pixel here)
     constexpr int C0_PLANE = C::T0 * 16 * 4;
     __shared__ __attribute__((aligned(16))) unsigned char s_raw[C::LDS_BYTES];
-    uint2 *s_in = (uint2 *)s_raw;                                // BGRX patch, 4 x fp16 per pixel  (phases 1-2)
-    uint32_t *s_in8 = (uint32_t *)s_raw;                         // ... or (!F16P) 4 x u8 per pixel
+    uint32_t *s_in = (uint32_t *)s_raw;                          // BGRX patch, 4 x u8 per pixel    (phases 1-2)
     T *s_a = (T *)s_raw;                                         // conv1 result hi|lo              (phases 3-4)
-    T *s_a1 = (T *)s_raw;                                        // conv3 result                    (phases 5-6)
-    T *s_out = (T *)(s_raw + C::A1_BYTES);                       // conv4 tile                      (phases 6-7)
+    T *s_out = (T *)(s_raw + C::A1_BYTES);                       // conv4 tile                      (phases 5-7)
     float *s_c0 = (float *)(s_raw + C::REGION_A);                // fp32 conv0 tile                 (phases 2-3)
     T *s_c2 = (T *)(s_raw + C::REGION_A);                        // fp16 conv2 tile                 (phases 4-5)
-    // V2 (round 4, from the LDS counters: this kernel's LDS pipe is busy 0.79 of the time, 0.31 in conflict cycles): (1) the conv2 tile as two 8-channel
+    // Round 4, from the LDS counters (this kernel's LDS pipe was busy 0.79 of the time, 0.31 in conflict cycles): (1) the conv2 tile as two 8-channel
     // PLANES of 16 bytes per pixel instead of 32-byte pixels -- its 8-byte epilogue writes were 4-way bank conflicts at the 32-byte pitch, 2-way now, the
-    // stride-2 fragment reads of conv3 are unchanged (2-way); (2) conv3 -> conv4 chained in registers (see K_b2c): conv4's K axis is re-ordered so that a
-    // lane's conv3 accumulator IS its conv4 B fragment {d0, d1, d0, d1} (hi | lo weights): no conv3 tile in LDS, one barrier less.
-    constexpr bool PLANAR = (V2 & 1) != 0, CHAIN = (V2 & 2) != 0;      // V2: bit 0 = (1), bit 1 = (2)
-    constexpr bool ROT = (V2 & 4) != 0 && C::R2W == 17 && NT == 256;   //     bit 2 = the depthwise-1 phase's thread -> pixel map (phase 3)
-    constexpr int C2_PLANE = PLANAR ? C::T2 * 16 * 8 + 8 : 0;    // halfs; an odd number of 16-byte slots, so the two planes' lanes never share a slot
-    static_assert(!PLANAR || 2 * C2_PLANE * 2 <= C::REGION_B, "planar conv2 tile fits region B");
+    // stride-2 fragment reads of conv3 are unchanged (2-way); (2) conv3 -> conv4 chained in registers: conv4's K axis is re-ordered so that a
+    // lane's conv3 accumulator IS its conv4 B fragment {d0, d1, d0, d1} (hi | lo weights): no conv3 tile in LDS, one barrier less; (3) the
+    // depthwise-1 phase's thread -> pixel map rotated (phase 3).
+    constexpr int C2_PLANE = C::T2 * 16 * 8 + 8;                 // halfs; an odd number of 16-byte slots, so the two planes' lanes never share a slot
+    static_assert(2 * C2_PLANE * 2 <= C::REGION_B, "planar conv2 tile fits region B");
+    static_assert(C::R2W == 17 && NT == 256, "the rotated phase-3 map is built for 17-wide regions and 256 threads");
     float *s_dw0 = (float *)(s_raw + C::REGION_A + C::REGION_B);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -993,7 +969,7 @@ __global__ __launch_bounds__((Stem2Cfg<TW_, F16P, PADKB>::THREADS), (Stem2Cfg<TW
     RF_TRACE_KEY(a.nblk);
     RF_TRACE(4, 0);
 
-    // RAW staging (round 6, V2 bit 3): frames whose base and row pitch are multiples of 16 B and that fill the net's
+    // RAW staging (round 6): frames whose base and row pitch are multiples of 16 B and that fill the net's
     // width (every BASELINE shape: 448 x 3 = 1344 = 16 x 84, 1280 x 3 = 3840) bring their patch rows into LDS as they are -- 3 bytes per
     // pixel, `buffer_load_dwordx4 ... lds`, no VGPR round trip, rows above / below the frame zero-filled by the descriptor's range check --
     // instead of the load / realign / border-mask / BGR -> BGRX repack of the general path (~100 of this kernel's ~584 VALU instructions per
@@ -1001,22 +977,7 @@ __global__ __launch_bounds__((Stem2Cfg<TW_, F16P, PADKB>::THREADS), (Stem2Cfg<TW
     // (weights.h c0_raw_: one fragment set per column parity, waves 0-1 take the even conv0 columns, waves 2-3 the odd ones).  Anything
     // else (odd pointers, ROIs, frames narrower than the net) takes the general path: tests/test_gpu_parity.py
     // test_device_frames_unaligned_pointer_odd_step_and_roi.  Wave-uniform per workgroup.
-    constexpr bool RAWCAP = (V2 & 8) != 0 && !F16P && NT == 256 && TW == 8;
-    const bool raw = RAWCAP && ((((uintptr_t)fd.ptr) | (uintptr_t)(unsigned)fd.step) & 15u) == 0 && fd.cols == 2 * a.wo && a.w0_raw != nullptr;
-    // V2 bits 4 / 5 / 6 (round 6, MEASURED AND REJECTED, probe build only): index arithmetic that is the same for every workgroup taken from memory instead of the
-    // VALU -- bit 4: conv0's pixel table on the raw path (pack.h stem2_conv0_table: 30 -> 19 VALU instructions per MFMA tile), bit 5: conv3's diagonal A fragments
-    // already expanded (20 v_cndmask per wave less), bit 6: the table path's LDS reads as explicit ds_read2_b32.  All bit-identical, all slower: 234.5 us base ->
-    // 239.7 (bit 5), 241.7 (4 + 6), 257.9 (all); and 407 us with bit 4 alone, because the compiler reads the 4-byte-aligned dword pair with ONE ds_read_b64, which
-    // this chip executes at a fraction of the rate of ds_read2_b32 when the address is not 8-byte aligned.  The kernel is VALU-bound at 0.86, not VALU-ONLY-bound: a
-    // dependent global load per tile costs more than the 11 instructions it replaces (profiles/r06_stem_index_tables_rejected.txt).
-    constexpr bool TAB = (V2 & 16) != 0 && RAWCAP;
-    constexpr bool TABASM = (V2 & 64) != 0;                      // the table path's two LDS reads as explicit ds_read2_b32 (the compiler picks ds_read_b64 at 4-byte alignment)
-    static_assert(!TAB || (C::R0H == kStem2R0H && C::R0W == kStem2R0W && C0_PLANE == kStem2C0Plane), "pack.h stem2_conv0_table is built for this geometry");
-    // (the wave index as a scalar: the table pointer of tile k is then base + SGPR arithmetic + one constant per-lane offset, no VALU per tile)
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    const uint2 *c0_tab = a.c0_tab + (wave_u * kStem2C0Tiles) * 64;
-    uint2 c0_e = {0u, 0u};
-    if (TAB && raw) c0_e = c0_tab[lane];                         // the first tile's entry: requested before the patch is staged
+    const bool raw = ((((uintptr_t)fd.ptr) | (uintptr_t)(unsigned)fd.step) & 15u) == 0 && fd.cols == 2 * a.wo && a.w0_raw != nullptr;
 
     // ---- phase 0: operands that depend only on kernel arguments
     const f16x8 *wf = (raw ? (const f16x8 *)a.w0_raw + (wave >> 1) * 256 : (const f16x8 *)a.w0) + lane;
@@ -1086,23 +1047,11 @@ __global__ __launch_bounds__((Stem2Cfg<TW_, F16P, PADKB>::THREADS), (Stem2Cfg<TW
             }
             // 12 bytes -> 4 BGRX dwords; the X byte is left as it falls (see K_a': zero weight x finite fp16 = exact +0): three v_and_b32 per item less
             uint4 o4;
-            o4.x = F16P ? (w0 & 0x00ffffffu) : w0;
-            o4.y = F16P ? (((w0 >> 24) | (w1 << 8)) & 0x00ffffffu) : __builtin_amdgcn_alignbyte(w1, w0, 3);
-            o4.z = F16P ? (((w1 >> 16) | (w2 << 16)) & 0x00ffffffu) : __builtin_amdgcn_alignbyte(w2, w1, 2);
+            o4.x = w0;
+            o4.y = __builtin_amdgcn_alignbyte(w1, w0, 3);
+            o4.z = __builtin_amdgcn_alignbyte(w2, w1, 2);
             o4.w = w2 >> 8;
-            // u8 -> fp16 HERE, once per input pixel (conv0 reads every pixel 2.25 times on average: converting in phase 2 was
-            // 12 of its 30 VALU instructions per MFMA tile); the X byte becomes the half 0 = the K padding
-            if constexpr (F16P) {
-                f16x8 h01, h23;
-                u8x4_to_f16(o4.x, h01, 0);
-                u8x4_to_f16(o4.y, h01, 4);
-                u8x4_to_f16(o4.z, h23, 0);
-                u8x4_to_f16(o4.w, h23, 4);
-                *(f16x8 *)(s_in + r * ROWD + g * 4) = h01;
-                *(f16x8 *)(s_in + r * ROWD + g * 4 + 2) = h23;
-            } else {
-                *(uint4 *)(s_in8 + r * ROWD + g * 4) = o4;
-            }
+            *(uint4 *)(s_in + r * ROWD + g * 4) = o4;
         }
     }
     if (tid < 18) *(f32x4 *)(s_dw0 + tid * 4) = *(const f32x4 *)(a.dw0_w + tid * 4);
@@ -1115,49 +1064,6 @@ __global__ __launch_bounds__((Stem2Cfg<TW_, F16P, PADKB>::THREADS), (Stem2Cfg<TW
         // MFMA 2 = kernel row 2 (kb 0,1; kb 2,3 meet zero weights).  A lane reads two consecutive dwords per MFMA (ds_read2_b32).
         typedef uint32_t u32x2a4 __attribute__((ext_vector_type(2), aligned(4)));
         const uint32_t *s_rows = (const uint32_t *)s_raw;
-        if constexpr (TAB) {
-            const int n = wave_u == 0 ? kStem2C0Tiles : kStem2C0Tiles - 1;    // 11 even-column tiles over waves 0,1; 10 odd-column tiles over waves 2,3
-            const unsigned p2d = (unsigned)(2 - (kb >> 1)) * 128u;            // MFMA 2 reads kernel row 2: two rows (kb 0,1) / one row (kb 2,3: zero weights) further down
-#pragma unroll 1
-            for (int k = 0; k < n; k++) {
-                const uint2 e = c0_e;
-                c0_e = c0_tab[(k + 1) * 64 + lane];                           // next tile's entry, in flight during this tile's MFMAs (entry n of the
-                                                                              // last tile's prefetch exists: an unused slot or the next wave's first)
-                const unsigned p1 = e.x & 0xffffu, ob = e.x >> 16;
-                u32x2a4 d1, d2;
-                if constexpr (TABASM) {
-                    typedef uint32_t u32x2r __attribute__((ext_vector_type(2)));
-                    u32x2r r1, r2;
-                    const unsigned l1 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)s_raw + p1;
-                    asm volatile("ds_read2_b32 %0, %2 offset1:1\n\tds_read2_b32 %1, %3 offset1:1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(r1), "=&v"(r2) : "v"(l1), "v"(l1 + p2d) : "memory");
-                    d1[0] = r1[0]; d1[1] = r1[1]; d2[0] = r2[0]; d2[1] = r2[1];
-                } else {
-                    d1 = *(const u32x2a4 *)(s_raw + p1); d2 = *(const u32x2a4 *)(s_raw + p1 + p2d);
-                }
-                f16x8 x1, x2;
-                u8x4_to_f16(d1[0], x1, 0);
-                u8x4_to_f16(d1[1], x1, 4);
-                u8x4_to_f16(d2[0], x2, 0);
-                u8x4_to_f16(d2[1], x2, 4);
-                f32x4 acc = b0;
-                acc = M::mma(w_hi1, x1, acc);
-                acc = M::mma(w_lo1, x1, acc);
-                acc = M::mma(w_hi2, x2, acc);
-                acc = M::mma(w_lo2, x2, acc);
-                if (e.y >> 16) {
-                    float lim = __builtin_inff();
-                    if (!interior) {
-                        asm volatile("" ::: "memory");
-                        const int cy = 2 * oy0 - 2 + (int)(e.y & 0xffu), cx = 2 * ox0 - 2 + (int)((e.y >> 8) & 0xffu);
-                        lim = ((unsigned)cy < (unsigned)a.ho && (unsigned)cx < (unsigned)a.wo) ? __builtin_inff() : 0.f;
-                    }
-                    f32x4 h;
-#pragma unroll
-                    for (int r = 0; r < 4; r++) h[r] = __builtin_amdgcn_fmed3f(acc[r], 0.f, lim);
-                    *(f32x4 *)((unsigned char *)s_c0 + ob) = h;
-                }
-            }
-        } else {
         // waves 0,1: even conv0 columns (10 of the 19), waves 2,3: odd ones (9); the parity is a compile-time constant of each copy of the
         // loop, so the pixel -> (row, column) division is by a constant
         auto conv0_raw = [&](auto parity) {
@@ -1198,7 +1104,6 @@ __global__ __launch_bounds__((Stem2Cfg<TW_, F16P, PADKB>::THREADS), (Stem2Cfg<TW
         };
         if (wave < 2) conv0_raw(std::integral_constant<int, 0>());
         else conv0_raw(std::integral_constant<int, 1>());
-        }
     } else {
         const int ppA = 2 * kb, ppB = 2 * kb + 1;
         const int offA = (ppA / 3) * ROWD + ppA % 3, offB = (ppB / 3) * ROWD + ppB % 3, offC = 2 * ROWD + 2;
@@ -1206,22 +1111,14 @@ __global__ __launch_bounds__((Stem2Cfg<TW_, F16P, PADKB>::THREADS), (Stem2Cfg<TW
         for (int t = wave; t < C::T0; t += NW) {
             const int q = t * 16 + (lane & 15);
             const int hy = q / R0W, hx = q % R0W;
-            f16x8 x1, x2;
-            if constexpr (F16P) {
-            const uint2 *pp = s_in + (2 * hy) * ROWD + 2 * hx;
             // No masks on the reads: the pixels q >= N0 of the last MFMA tile read rows past the patch (still inside this
             // workgroup's LDS; whatever they hold only reaches their own columns of the result, which phase 3 never reads) and
-            // every lane group reads window pixel 8 (a finite fp16), whose K slots 36..63 meet zero weights (weights.h)
-            const uint2 vA = pp[offA], vB = pp[offB], vC = pp[offC];
-            const uint4 u1 = {vA.x, vA.y, vB.x, vB.y}, u2 = {vC.x, vC.y, 0u, 0u};
-            x1 = __builtin_bit_cast(f16x8, u1); x2 = __builtin_bit_cast(f16x8, u2);
-            } else {
-                const uint32_t *pp = s_in8 + (2 * hy) * ROWD + 2 * hx;
-                x2 = vzero<f16x8, 8>();
-                u8x4_to_f16(pp[offA], x1, 0);
-                u8x4_to_f16(pp[offB], x1, 4);
-                u8x4_to_f16(pp[offC], x2, 0);
-            }
+            // every lane group reads window pixel 8 (finite), whose K slots 36..63 meet zero weights (weights.h)
+            const uint32_t *pp = s_in + (2 * hy) * ROWD + 2 * hx;
+            f16x8 x1, x2 = vzero<f16x8, 8>();
+            u8x4_to_f16(pp[offA], x1, 0);
+            u8x4_to_f16(pp[offB], x1, 4);
+            u8x4_to_f16(pp[offC], x2, 0);
             f32x4 acc = b0;                                   // bias rides in the accumulator (lanes >= 32 hold padding rows)
             acc = M::mma(w_hi1, x1, acc);
             acc = M::mma(w_lo1, x1, acc);
@@ -1253,17 +1150,13 @@ __global__ __launch_bounds__((Stem2Cfg<TW_, F16P, PADKB>::THREADS), (Stem2Cfg<TW
         for (int e = 0; e < 8; e++) dw_bias[e] = a.dw0_b[e];
 #pragma unroll 1
         for (int i = tid; i < C::T2 * 16; i += NT) {
-            // which region pixel a thread computes.  V2 bit 2 (ROT, 17-wide regions): rows of 16 lanes with the column ROTATED by 3 per row, so that
+            // which region pixel a thread computes: rows of 16 lanes with the column ROTATED by 3 per row, so that
             // a lane's conv0-tile slot (19 ry + rx) mod 16 is its lane index mod 16 whatever the row -- every 16-lane group of the 18 ds_read_b128 per
             // thread then meets 16 distinct slots; with pixel = thread index the groups straddled a 17-pixel row and every read was 2-way (tools/lds_model.py:
             // 144 -> 72 LDS cycles per wave).  The 17th column goes to threads 240..254.  Same arithmetic per pixel: bit-identical.
             auto pixel_of = [&](int &ry, int &rx) {
-                if constexpr (ROT) {
-                    if (i < 240) { ry = i >> 4; rx = ((i & 15) - 3 * ry) & 15; }
-                    else { ry = i - 240; rx = 16; }
-                } else {
-                    ry = i / R2W; rx = i % R2W;
-                }
+                if (i < 240) { ry = i >> 4; rx = ((i & 15) - 3 * ry) & 15; }
+                else { ry = i - 240; rx = 16; }
             };
             int ry, rx;
             pixel_of(ry, rx);
@@ -1290,13 +1183,11 @@ __global__ __launch_bounds__((Stem2Cfg<TW_, F16P, PADKB>::THREADS), (Stem2Cfg<TW
                 hi[e] = (half_t)v;
                 lo[e] = (half_t)(v - (float)hi[e]);
             }
-            int po = i;                               // the pixel's slot in the conv1 tile (recomputed here: one register less across the taps)
-            if constexpr (ROT) {
-                asm volatile("" ::: "memory");
-                int ry2, rx2;
-                pixel_of(ry2, rx2);
-                po = i < N2 ? ry2 * R2W + rx2 : i;        // (thread 255 owns no pixel: it keeps its old slot)
-            }
+            // the pixel's slot in the conv1 tile (recomputed here: one register less across the taps)
+            asm volatile("" ::: "memory");
+            int ry2, rx2;
+            pixel_of(ry2, rx2);
+            const int po = i < N2 ? ry2 * R2W + rx2 : i;        // (thread 255 owns no pixel: it keeps its old slot)
             *(f16x8 *)(s_a + po * 16) = hi;          // region A: the staged patch is dead since the barrier after phase 2
             *(f16x8 *)(s_a + po * 16 + 8) = lo;
         }
@@ -1329,23 +1220,17 @@ __global__ __launch_bounds__((Stem2Cfg<TW_, F16P, PADKB>::THREADS), (Stem2Cfg<TW
         uint2 h;
         h.x = inside ? pack_f16_floor(acc[0], acc[1], c2_floor.x) : c2_floor.x;
         h.y = inside ? pack_f16_floor(acc[2], acc[3], c2_floor.y) : c2_floor.y;
-        if constexpr (PLANAR) *(uint2 *)(s_c2 + (kb >> 1) * C2_PLANE + i * 8 + (kb & 1) * 4) = h;
-        else *(uint2 *)(s_c2 + i * 16 + kb * 4) = h;
+        *(uint2 *)(s_c2 + (kb >> 1) * C2_PLANE + i * 8 + (kb & 1) * 4) = h;
     }
-    constexpr bool DW4 = (V2 & 32) != 0;                     // conv3's A fragments arrive expanded (4 dwords per lane and chunk): no v_cndmask in phase 5
     uint32_t dw1v[kDwMmaChunks];                             // phase 5's operands: requested before the barrier
-    u32x4 dw1v4[kDwMmaChunks];
 #pragma unroll
-    for (int kc = 0; kc < kDwMmaChunks; kc++) {
-        if constexpr (DW4) dw1v4[kc] = a.dw1_mma4[kc * 64 + lane];
-        else dw1v[kc] = a.dw1_mma[kc * 64 + lane];
-    }
+    for (int kc = 0; kc < kDwMmaChunks; kc++) dw1v[kc] = a.dw1_mma[kc * 64 + lane];
     const f32x4 dbias = *(const f32x4 *)(a.dw1_b + kb * 4);           // bias + mu2 * sum(taps) - mu3 (host)
     const uint2 c3_floor = *(const uint2 *)(a.c3_floor + kb * 2);     // the conv3 result is stored centred as well (conv4 is 1x1: its bias takes W mu3)
-    // V2: conv4's operands too (its A fragments in the chained K order: halves 0-3 = W_hi of channels 4 kb .., 4-7 = W_lo of the same channels)
+    // conv4's operands too (its A fragments in the chained K order: halves 0-3 = W_hi of channels 4 kb .., 4-7 = W_lo of the same channels)
     M::Frag pw1c[2];
     f32x4 pw1cb[2];
-    if constexpr (CHAIN) {
+    {
         const uint2 *w8 = (const uint2 *)a.pw1_w;
 #pragma unroll
         for (int ct = 0; ct < 2; ct++) {
@@ -1371,8 +1256,8 @@ __global__ __launch_bounds__((Stem2Cfg<TW_, F16P, PADKB>::THREADS), (Stem2Cfg<TW
         for (int pt = wave; pt < C::T4; pt += NW) {
             const int p = pt * 16 + (lane & 15);
             const int py = p / TW, px = p % TW;             // p >= P4: reads past the tile's last row (inside this workgroup's LDS), result never stored
-            constexpr int PXH = PLANAR ? 8 : 16;            // halfs per pixel of the tile (plane)
-            const T *src = PLANAR ? s_c2 + (kb & 1) * C2_PLANE + ((2 * py) * R2W + 2 * px) * 8 : s_c2 + ((2 * py) * R2W + 2 * px) * 16 + (kb & 1) * 8;
+            constexpr int PXH = 8;                          // halfs per pixel of the tile plane
+            const T *src = s_c2 + (kb & 1) * C2_PLANE + ((2 * py) * R2W + 2 * px) * 8;
             M::Frag bf[kDwMmaChunks];
 #pragma unroll
             for (int kc = 0; kc < kDwMmaChunks; kc++) {
@@ -1385,55 +1270,28 @@ __global__ __launch_bounds__((Stem2Cfg<TW_, F16P, PADKB>::THREADS), (Stem2Cfg<TW
             for (int kc = 0; kc < kDwMmaChunks; kc++) {
                 typedef uint32_t u32x4_ __attribute__((ext_vector_type(4)));
                 u32x4_ wa;
-                if constexpr (DW4) {
-                    wa = dw1v4[kc];
-                } else {
-                    const uint32_t wd = dw1v[kc];
+                const uint32_t wd = dw1v[kc];
 #pragma unroll
-                    for (int d = 0; d < 4; d++) wa[d] = dsel == d ? wd : 0u;
-                }
+                for (int d = 0; d < 4; d++) wa[d] = dsel == d ? wd : 0u;
                 acc = M::mma(__builtin_bit_cast(M::Frag, wa), bf[kc], acc);
             }
             uint2 h;
             h.x = pack_f16_floor(acc[0], acc[1], c3_floor.x);
             h.y = pack_f16_floor(acc[2], acc[3], c3_floor.y);
-            if constexpr (CHAIN) {
-                const uint4 u = {h.x, h.y, h.x, h.y};
-                const M::Frag x = __builtin_bit_cast(M::Frag, u);
+            const uint4 u = {h.x, h.y, h.x, h.y};
+            const M::Frag x = __builtin_bit_cast(M::Frag, u);
 #pragma unroll
-                for (int ct = 0; ct < 2; ct++) {
-                    const f32x4 o = M::mma(pw1c[ct], x, pw1cb[ct]);
-                    uint2 g;
-                    g.x = pack_f16(o[0], o[1], true);
-                    g.y = pack_f16(o[2], o[3], true);
-                    *(uint2 *)(s_out + p * LDO + ct * 16 + kb * 4) = g;      // region A: the conv1 result is dead since the barrier after phase 4
-                }
-            } else {
-                *(uint2 *)(s_a1 + p * LDA1 + kb * 4) = h;      // region A again: the conv1 result is dead since the barrier after phase 4
+            for (int ct = 0; ct < 2; ct++) {
+                const f32x4 o = M::mma(pw1c[ct], x, pw1cb[ct]);
+                uint2 g;
+                g.x = pack_f16(o[0], o[1], true);
+                g.y = pack_f16(o[2], o[3], true);
+                *(uint2 *)(s_out + p * LDO + ct * 16 + kb * 4) = g;      // region A: the conv1 result is dead since the barrier after phase 4
             }
         }
     }
     RF_TRACE(4, 5);
     __syncthreads();
-    if constexpr (!CHAIN) {
-    const f16x8 pw1_frag0 = ((const f16x8 *)a.pw1_w)[lane], pw1_frag1 = ((const f16x8 *)a.pw1_w)[64 + lane];      // phase 6's operands
-    const f32x4 pw1_bias0 = *(const f32x4 *)(a.pw1_b + kb * 4), pw1_bias1 = *(const f32x4 *)(a.pw1_b + 16 + kb * 4);
-
-    // ---- phase 6: pointwise conv4 (16 -> 32) on MFMA: 2 channel tiles x T4 pixel tiles.  K = 16, and the MFMA has 32 slots: the
-    //      weights ride as an fp16 hi | lo pair along K (both halves read the same 16 inputs), so their rounding costs nothing
-#pragma unroll 1
-    for (int pr = wave; pr < 2 * C::T4; pr += NW) {
-        const int ct = pr & 1, pt = pr >> 1;
-        const M::Frag x = *(const M::Frag *)(s_a1 + (pt * 16 + (lane & 15)) * LDA1 + (kb & 1) * 8);
-        const f32x4 acc = M::mma(ct ? pw1_frag1 : pw1_frag0, x, ct ? pw1_bias1 : pw1_bias0);
-        uint2 h;
-        h.x = pack_f16(acc[0], acc[1], true);
-        h.y = pack_f16(acc[2], acc[3], true);
-        *(uint2 *)(s_out + (pt * 16 + (lane & 15)) * LDO + ct * 16 + kb * 4) = h;
-    }
-    RF_TRACE(4, 6);
-    __syncthreads();
-    }
 
     // ---- phase 7: tile -> HBM, 16 B per lane; rows below the map fall outside the descriptor, columns need the test
     {
@@ -1449,55 +1307,22 @@ __global__ __launch_bounds__((Stem2Cfg<TW_, F16P, PADKB>::THREADS), (Stem2Cfg<TW
     RF_TRACE(4, 7);
 }
 
-int stem2_variant() { return knob(K_STEM2); }      // probe knob RF_STEM2: 1 = 7x8 tiles (the product), 0 = off, 2 = 7x16, 3 = 7x8 with the patch converted to fp16 at staging (7 workgroups / CU: measured slower)
-
 void launch_stem2(hipStream_t s, const Stem2Params &p) {
     Stem2Args a;
     a.frames = p.frames; a.out = p.out; a.w0 = p.w0; a.b0 = p.b0; a.w0_raw = p.w0_raw;
-    a.c0_tab = (const uint2 *)p.c0_tab; a.dw1_mma4 = (const u32x4 *)p.dw1_mma4;
     a.dw0_w = p.dw0_w; a.dw0_b = p.dw0_b; a.pw0_w = p.pw0_w; a.pw0_b = p.pw0_b;
     a.dw1_mma = p.dw1_mma; a.dw1_b = p.dw1_b; a.pw1_w = p.pw1_w; a.pw1_b = p.pw1_b;
     a.c2_floor = p.c2_floor; a.c3_floor = p.c3_floor;
     a.ho = p.net_h / 2; a.wo = p.net_w / 2; a.ho4 = p.net_h / 4; a.wo4 = p.net_w / 4;
-    int tw = 8;
-#ifdef RF_PROBES
-    const int v = stem2_variant();
-    tw = v == 2 ? 16 : 8;
-#endif
-    a.tiles_x = (a.wo4 + tw - 1) / tw; a.tiles_y = (a.ho4 + 6) / 7;
+    a.tiles_x = (a.wo4 + Stem2Cfg::TW - 1) / Stem2Cfg::TW; a.tiles_y = (a.ho4 + Stem2Cfg::TH - 1) / Stem2Cfg::TH;
     a.nblk = p.n * a.tiles_x * a.tiles_y;
-#ifdef RF_PROBES
-    if (tw == 16) { hipLaunchKernelGGL((stem2_kernel<16, false, 0, 0>), dim3(a.nblk), dim3(Stem2Cfg<16, false>::THREADS), 0, s, a); return; }
-    if (v == 3) { hipLaunchKernelGGL((stem2_kernel<8, true, 0, 0>), dim3(a.nblk), dim3(kThreads), 0, s, a); return; }
-    // RF_STEM2_PAD (probe knob): 3 / 7 KB of unused LDS per workgroup = 7 / 6 workgroups per CU instead of 8: stem2 alone gets slower
-    // (+3.5 % / +10 %), but at 8 it owns every wave slot of the chip and nothing of another lane can run beside it
-    const int pad = knob(K_STEM2_PAD);
-    if (pad == 3) { hipLaunchKernelGGL((stem2_kernel<8, false, 3, 0>), dim3(a.nblk), dim3(kThreads), 0, s, a); return; }
-    if (pad == 7) { hipLaunchKernelGGL((stem2_kernel<8, false, 7, 0>), dim3(a.nblk), dim3(kThreads), 0, s, a); return; }
-    // RF_STEM2_V2 (probe knob): bit 0 = planar conv2 tile, bit 1 = conv3 -> conv4 chained in registers, bit 2 = rotated thread -> pixel map of the
-    // depthwise-1 phase; 0 = round 3; 5 = round 4's default (bit-identical to round 3: 250.3 -> 246.5 -> 238.6 us, tools/gpu/rounds_3_4.sh r4_call30, r4_call32)
-    switch (knob(K_STEM2_V2)) {
-        case 15: hipLaunchKernelGGL((stem2_kernel<8, false, 0, 15>), dim3(a.nblk), dim3(kThreads), 0, s, a); return;    // raw-row staging without the index tables
-        case 31: hipLaunchKernelGGL((stem2_kernel<8, false, 0, 31>), dim3(a.nblk), dim3(kThreads), 0, s, a); return;    // + conv0 pixel table
-        case 47: hipLaunchKernelGGL((stem2_kernel<8, false, 0, 47>), dim3(a.nblk), dim3(kThreads), 0, s, a); return;    // + expanded conv3 fragments only
-        case 95: hipLaunchKernelGGL((stem2_kernel<8, false, 0, 95>), dim3(a.nblk), dim3(kThreads), 0, s, a); return;    // + table with explicit ds_read2_b32
-        case 127: hipLaunchKernelGGL((stem2_kernel<8, false, 0, 127>), dim3(a.nblk), dim3(kThreads), 0, s, a); return;  // all
-        case 7: hipLaunchKernelGGL((stem2_kernel<8, false, 0, 7>), dim3(a.nblk), dim3(kThreads), 0, s, a); return;      // round 5's product
-        case 5: hipLaunchKernelGGL((stem2_kernel<8, false, 0, 5>), dim3(a.nblk), dim3(kThreads), 0, s, a); return;
-        case 3: hipLaunchKernelGGL((stem2_kernel<8, false, 0, 3>), dim3(a.nblk), dim3(kThreads), 0, s, a); return;
-        case 2: hipLaunchKernelGGL((stem2_kernel<8, false, 0, 2>), dim3(a.nblk), dim3(kThreads), 0, s, a); return;
-        case 1: hipLaunchKernelGGL((stem2_kernel<8, false, 0, 1>), dim3(a.nblk), dim3(kThreads), 0, s, a); return;
-        case 0: hipLaunchKernelGGL((stem2_kernel<8, false, 0, 0>), dim3(a.nblk), dim3(kThreads), 0, s, a); return;
-        default: break;
-    }
-#endif
-    // The product: V2 = 7 -- planar conv2 tile, rotated depthwise-1 map and (round 5) conv3 -> conv4 chained in registers: 239.3 -> 235.1 us
+    // Planar conv2 tile, rotated depthwise-1 map and (round 5) conv3 -> conv4 chained in registers: 239.3 -> 235.1 us
     // (tools/gpu/rounds_3_4.sh r4_call35).  The chain permutes conv4's K order, i.e. re-rolls its fp32 summation: on one of the 208 contract frames the
     // NMS winner moves between twin anchors 300 / 301 whose oracle scores are 0.997809 / 0.997806 -- which the anchor-twin band of the parity
     // tests (tests/anchor_twins.py) admits, and nothing else.
-    // V2 = 15 (round 6): + bit 3, the raw-row staging of aligned full-width frames (see the kernel; it re-orders conv0's K axis as well).  Bits 4-6 (index
-    // tables from memory instead of index arithmetic, bit-identical) measured slower and live in the probe build: profiles/r06_stem_index_tables_rejected.txt.
-    hipLaunchKernelGGL((stem2_kernel<8, false, 0, 15>), dim3(a.nblk), dim3(kThreads), 0, s, a);
+    // Round 6: + the raw-row staging of aligned full-width frames (see the kernel; it re-orders conv0's K axis as well).  Index tables from memory
+    // instead of index arithmetic (bit-identical) measured slower (profiles/r06_stem_index_tables_rejected.txt) and were removed.
+    hipLaunchKernelGGL(stem2_kernel, dim3(a.nblk), dim3(kThreads), 0, s, a);
 }
 
 // =============================================================================================
@@ -1533,7 +1358,7 @@ template <typename T, int CIN, int COUT, int STRIDE, bool HAS_DW, int TH, int TW
     // Halo tile as the depthwise MFMA's B operand: pixel pitch 32 mod 64 bytes and (TW = 8, stride 1: a 16-pixel MFMA tile spans
     // two halo rows) a row pitch that is a multiple of the 256-byte bank row make every B-fragment ds_read_b128 conflict-free
     // (see Conv3Cfg::ROWP).  The halo tile is written with contiguous 128-byte runs, so unlike s_a / s_out it has no write-side
-    // preference.  PADROW = false keeps the round-1 layout (probe knob RF_DWPAD=0).
+    // preference.  PADROW = false keeps the round-1 layout.
     static constexpr int LDIN = DWMMA ? (!PADROW && CIN * sizeof(T) >= 256 ? CIN + VEC : lds_row<T>(CIN)) : CIN;
     static constexpr int ROWP = PADROW && DWMMA && TW == 8 && STRIDE == 1 ? (HC * LDIN * (int)sizeof(T) + 255) / 256 * 256 / (int)sizeof(T) : HC * LDIN;
     static constexpr size_t IN_BYTES = sizeof(T) * (size_t)(HR * ROWP);
@@ -2191,351 +2016,6 @@ static void dwpw_wide_launch(hipStream_t s, const DwPwParams<T> *p, int tiles_x,
     hipLaunchKernelGGL(kern, dim3(persistent_grid(a.nblk, resident)), dim3(kWideThreads), C::LDS_BYTES, s, a);
 }
 
-#ifdef RF_PROBES      // measured and rejected (profiles/r04_rejected_ws_variants.txt): probe build only
-// =============================================================================================
-// K_b'  depthwise + pointwise (+ lateral) block WAVE-SPECIALISED (round 4): K_b's phases with the memory side taken off the four
-//   GEMM waves.  A fifth wave (the producer) owns every global-memory instruction of the tile loop: it stores the previous tile's
-//   result(s) from LDS and brings the halo of the tile DIST = NBUF - 1 steps ahead into one of NBUF LDS buffers by LDS-DMA
-//   (buffer_load ... lds: no VGPRs, no ds_write pass, zero padding by the descriptor's range check); the consumers run
-//   depthwise (diagonal MFMA) -> barrier -> pointwise GEMM -> [barrier -> lateral GEMM] -> barrier on LDS only.  The producer joins the
-//   consumers' barriers (s_barrier is workgroup wide) but waits only for the halo the NEXT interval needs, with a counted vmcnt: its own
-//   stores and the younger DMA stay in flight across the barrier.  Same tile geometry, LDS pitches, weight packing and arithmetic as
-//   K_b: the results are bit-identical (the int8 instance is held to the integer oracle like K_b's).
-//   What it took off the critical path in the merged SSH conv (K_c'): 104 -> 56 us.
-// =============================================================================================
-template <typename T, int CIN, int COUT, int STRIDE, int TH, int TW, bool LAT, int NBUF, bool PADROW, bool PROD = true> struct DwPwWsCfg {
-    typedef DwPwCfg<T, CIN, COUT, STRIDE, true, TH, TW, PADROW> B;
-    static constexpr int VEC = B::VEC, P = B::P;
-    static constexpr int CPP = B::LDIN / VEC;                          // 16-byte chunks per halo pixel, padding included
-    static constexpr int CPR = B::ROWP / VEC;                          // chunks per halo row, padding included
-    static constexpr int DPP = CIN / VEC;                              // data chunks per pixel
-    static constexpr int SLOTS = B::HR * CPR;
-    // PROD: a fifth wave owns the memory side.  !PROD (K_b''): no producer wave -- each of the four waves issues a quarter of the halo DMA and of the
-    // stores (a 320-thread workgroup at this register budget is resident once per CU; 256-thread ones pack)
-    static constexpr int NW = PROD ? 1 : 4;                            // waves that share the memory side
-    static constexpr int PIECES = ((SLOTS + 63) / 64 + NW - 1) / NW * NW;      // DMA wave-instructions per halo tile (whole pieces per wave)
-    static constexpr int PPW = PIECES / NW;
-    static constexpr int LDL = 64 + VEC;
-    static constexpr int NST_OUT = P * (COUT / VEC) / 64, NST_LAT = LAT ? P * (64 / VEC) / 64 : 0;
-    static constexpr int NSTORE = NST_OUT + NST_LAT;                   // store wave-instructions per tile
-    static constexpr int NSTW = NSTORE / NW;
-    static constexpr bool SPLIT_OK = NST_OUT % NW == 0 && NST_LAT % NW == 0;      // the same number of vmcnt events in every wave
-    static constexpr size_t IN_BYTES = (size_t)PIECES * 1024;
-    static constexpr size_t A_BYTES = B::A_BYTES, O_BYTES = B::O_BYTES;
-    static constexpr size_t L_BYTES = LAT ? sizeof(T) * (size_t)(P * LDL) : 0;
-    static constexpr size_t LDS_BYTES = NBUF * IN_BYTES + A_BYTES + O_BYTES + L_BYTES;
-    static constexpr int THREADS = PROD ? 320 : 256;                   // 4 GEMM waves (+ the producer)
-    static constexpr int WG_CAP = LAT ? 2 : 3;                         // (the lateral's second GEMM needs ~140 VGPRs: 3 workgroups of 5 waves would spill)
-    static constexpr int WG_PER_CU = (int)(160 * 1024 / LDS_BYTES) > WG_CAP ? WG_CAP : (int)(160 * 1024 / LDS_BYTES);
-    static constexpr int WAVES_PER_EU = PROD ? (WG_PER_CU * 5 + 3) / 4 : WG_PER_CU;      // what __launch_bounds__ needs for WG_PER_CU resident workgroups
-    static_assert(B::DWMMA && B::STAT && sizeof(T) <= 2, "only the shapes whose depthwise stage runs on MFMA with stationary pointwise weights");
-    static_assert(B::LDIN % VEC == 0 && B::ROWP % VEC == 0 && IN_BYTES >= B::IN_BYTES, "halo layout in whole 16-byte slots");
-    static_assert((P * (COUT / VEC)) % 64 == 0 && (!LAT || (P * (64 / VEC)) % 64 == 0), "whole store instructions per tile");
-    static_assert(NBUF == 2 || NBUF == 3, "prefetch distance 1 or 2");
-    static_assert(!LAT || (COUT + Mma<T>::K - 1) / Mma<T>::K <= 8, "lateral weights stationary");
-};
-
-template <typename T, int CIN, int COUT, int STRIDE, int TH, int TW, bool LAT, int NBUF, bool PADROW, bool PROD = true>
-__global__ __launch_bounds__((DwPwWsCfg<T, CIN, COUT, STRIDE, TH, TW, LAT, NBUF, PADROW, PROD>::THREADS), (DwPwWsCfg<T, CIN, COUT, STRIDE, TH, TW, LAT, NBUF, PADROW, PROD>::WAVES_PER_EU))
-void dwpw_ws_kernel(DwPwArgs<T> a) {
-    typedef DwPwWsCfg<T, CIN, COUT, STRIDE, TH, TW, LAT, NBUF, PADROW, PROD> W;
-    typedef typename W::B C;
-    typedef typename Vec<T>::type V;
-    typedef Mma<T> M;
-    typedef typename M::Frag Frag;
-    typedef typename C::WS WS;
-    constexpr int VEC = C::VEC, P = C::P, HC = C::HC, LDA = C::LDA, LDO = C::LDO, LDIN = C::LDIN, ROWP = C::ROWP;
-    constexpr int PT = C::PT, KCH = C::KCH, LDL = W::LDL;
-    constexpr int DIST = NBUF - 1, NW = W::NW, PPW = W::PPW;
-    constexpr bool I8 = sizeof(T) == 1;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int IN_ELEMS = (int)(W::IN_BYTES / sizeof(T));
-    T *s_in = (T *)smem;                                                           // [NBUF][IN_ELEMS]
-    T *s_a = (T *)(smem + NBUF * W::IN_BYTES);                                     // depthwise result
-    T *s_out = (T *)(smem + NBUF * W::IN_BYTES + W::A_BYTES);                      // block output tile
-    T *s_lat = (T *)(smem + NBUF * W::IN_BYTES + W::A_BYTES + W::O_BYTES);         // lateral output tile (LAT)
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int G = gridDim.x;
-    const int first = xcd_remap(blockIdx.x, G);
-    const int n_my = first < a.nblk ? (a.nblk - 1 - first) / G + 1 : 0;
-
-    // ---- the memory side: the producer wave's (PROD) or this wave's quarter (!PROD) of the halo DMA and of the stores
-    const int mw = PROD ? 0 : wave;                                    // index among the NW waves that share it
-    int kpack[PPW];                                                    // byte offset inside the image | halo column << 26 (63 = no pixel)
-#pragma unroll
-    for (int i = 0; i < PPW; i++) {
-        const int s = (mw * PPW + i) * 64 + lane;
-        const int row = s / W::CPR, rem = s % W::CPR;
-        const int px = rem / W::CPP, ch = rem % W::CPP;
-        const bool real = row < C::HR && px < HC && ch < W::DPP;
-        kpack[i] = real ? ((((row * a.win + px) * CIN + ch * VEC) * (int)sizeof(T)) | (px << 26)) : (int)(63u << 26);
-    }
-    const unsigned in_img_bytes = (unsigned)(a.hin * a.win * CIN) * (unsigned)sizeof(T);
-    const unsigned out_img_bytes = (unsigned)(a.hout * a.wout * COUT) * (unsigned)sizeof(T);
-    auto dma = [&](int tx, int ty, int img, T *dst) {
-        const auto rs = image_rsrc(a.in + (size_t)img * a.hin * a.win * CIN, in_img_bytes);
-        const int iy0 = ty * TH * STRIDE - 1, ix0 = tx * TW * STRIDE - 1;
-        const int sbase = (iy0 * a.win + ix0) * CIN * (int)sizeof(T);
-#pragma unroll
-        for (int i = 0; i < PPW; i++) {
-            const int dx = (int)((unsigned)kpack[i] >> 26);
-            const unsigned off = (dx != 63 && (unsigned)(ix0 + dx) < (unsigned)a.win) ? (unsigned)((kpack[i] & 0x03ffffff) + sbase) : kOobOffset;
-            lds_dma16(rs, (unsigned char *)dst + (mw * PPW + i) * 1024, off);
-        }
-    };
-    auto store_tile = [&](int img, int oy0, int ox0) {
-        constexpr int OPV = COUT / VEC;
-        const auto ro = image_rsrc(a.out + (size_t)img * a.hout * a.wout * COUT, out_img_bytes);
-        const int obase = (oy0 * a.wout + ox0) * COUT * (int)sizeof(T);
-#pragma unroll
-        for (int j = 0; j < W::NST_OUT / NW; j++) {
-            const int i = lane + 64 * (mw + NW * j);
-            const int p = i / OPV, cv = i % OPV;
-            const int py = p / TW, px = p % TW;
-            const unsigned off = ox0 + px < a.wout ? (unsigned)(((py * a.wout + px) * COUT + cv * VEC) * (int)sizeof(T) + obase) : kOobOffset;
-            buf_store16(ro, off, *(const V *)(s_out + p * LDO + cv * VEC));
-        }
-        if constexpr (LAT) {
-            constexpr int LPV = 64 / VEC;
-            const auto rl = image_rsrc(a.lat_out + (size_t)img * a.hout * a.wout * 64, (unsigned)(a.hout * a.wout * 64) * (unsigned)sizeof(T));
-            const int lbase = (oy0 * a.wout + ox0) * 64 * (int)sizeof(T);
-#pragma unroll
-            for (int j = 0; j < W::NST_LAT / NW; j++) {
-                const int i = lane + 64 * (mw + NW * j);
-                const int p = i / LPV, cv = i % LPV;
-                const int py = p / TW, px = p % TW;
-                const unsigned off = ox0 + px < a.wout ? (unsigned)(((py * a.wout + px) * 64 + cv * VEC) * (int)sizeof(T) + lbase) : kOobOffset;
-                buf_store16(rl, off, *(const V *)(s_lat + p * LDL + cv * VEC));
-            }
-        }
-    };
-    const TileStep step(G, a.tiles_x, a.tiles_y);
-    TileCoord cur(first, a.tiles_x, a.tiles_y), pf = cur;             // cur: the tile being computed; pf: the next tile to fetch
-    int p_img = 0, p_oy0 = 0, p_ox0 = 0;                               // the tile whose result is still in LDS
-    // what may stay in flight when tile k + 1 has to have landed: this interval's own stores and DMA (vmcnt is in order)
-    auto wait_next_halo = [&](bool st, bool ld) {
-        if (DIST == 1) wait_vmcnt<0>();
-        else if (st && ld) wait_vmcnt<(W::NSTW + PPW < 63 ? W::NSTW + PPW : 63)>();
-        else if (ld) wait_vmcnt<PPW>();
-        else if (st) wait_vmcnt<W::NSTW>();
-        else wait_vmcnt<0>();
-    };
-
-    if constexpr (PROD) {
-      if (wave == 4) {
-        // ================================================= producer
-#pragma unroll
-        for (int d = 0; d < DIST; d++)
-            if (d < n_my) { dma(pf.tx, pf.ty, pf.img, s_in + d * IN_ELEMS); step.advance(pf); }
-        if (DIST == 2 && n_my >= 2) wait_vmcnt<PPW>();
-        else wait_vmcnt<0>();
-        lds_barrier();
-        for (int k = 0; k < n_my; k++) {
-            const bool st = k > 0, ld = k + DIST < n_my;
-            // the previous tile's result(s): s_out / s_lat are rewritten by this interval's pointwise / lateral phase, i.e. after the
-            // barrier below, which this wave passes only with its LDS reads complete
-            if (st) store_tile(p_img, p_oy0, p_ox0);
-            lds_barrier();                                             // (depthwise -> pointwise)
-            if (ld) { dma(pf.tx, pf.ty, pf.img, s_in + ((k + DIST) % NBUF) * IN_ELEMS); step.advance(pf); }      // (issued under the pointwise phase)
-            p_img = cur.img; p_oy0 = cur.ty * TH; p_ox0 = cur.tx * TW;
-            step.advance(cur);
-            if constexpr (LAT) lds_barrier();                          // (pointwise -> lateral)
-            // tile k + 1 must have landed before the closing barrier; what was issued in THIS interval may stay in flight (DIST == 2)
-            wait_next_halo(st, ld);
-            lds_barrier();
-        }
-        if (n_my > 0) store_tile(p_img, p_oy0, p_ox0);                // (the consumers' last writes precede the closing barrier)
-        return;
-      }
-    } else {
-        // K_b'': every wave brings in its quarter of the first DIST halos; the wait below (weights + these) and the barrier publish them
-#pragma unroll
-        for (int d = 0; d < DIST; d++)
-            if (d < n_my) { dma(pf.tx, pf.ty, pf.img, s_in + d * IN_ELEMS); step.advance(pf); }
-    }
-
-    // ================================================= consumers (waves 0-3): once per workgroup, weights and per-lane constants as in K_b
-    const int wn = wave % WS::WN, wp = wave / WS::WN;
-    Frag wst[WS::NI][KCH];
-    {
-        const Frag *wsrc = (const Frag *)a.pw_w + (size_t)wn * KCH * 64 + lane;
-#pragma unroll
-        for (int i = 0; i < WS::NI; i++)
-#pragma unroll
-            for (int kc = 0; kc < KCH; kc++) wst[i][kc] = wsrc[((i * WS::WN) * KCH + kc) * 64];
-    }
-    f32x4 pw_bias[WS::NI], pw_mult[WS::NI];
-#pragma unroll
-    for (int i = 0; i < WS::NI; i++) {
-        pw_bias[i] = *(const f32x4 *)(a.pw_b + acc_cout(wn + i * WS::WN, lane, 0));
-        pw_mult[i] = load_mult(a.pw_m, acc_cout(wn + i * WS::WN, lane, 0));
-    }
-    constexpr int LKCH = (COUT + M::K - 1) / M::K;
-    Frag lst[1][LAT ? LKCH : 1];
-    f32x4 lat_bias = vzero<f32x4, 4>(), lat_mult = vzero<f32x4, 4>();
-    if constexpr (LAT) {
-        const Frag *lsrc = (const Frag *)a.lat_w + (size_t)wave * LKCH * 64 + lane;
-#pragma unroll
-        for (int kc = 0; kc < LKCH; kc++) lst[0][kc] = lsrc[kc * 64];
-        lat_bias = *(const f32x4 *)(a.lat_b + acc_cout(wave, lane, 0));
-        lat_mult = load_mult(a.lat_m, acc_cout(wave, lane, 0));
-    }
-    constexpr int NG = CIN / 16, DKCH = I8 ? kDwMmaChunksI8 : kDwMmaChunks;
-    constexpr int DPARTS = I8 ? 2 : 1;
-    constexpr int GW = NG >= 4 ? NG / 4 : 1;
-    constexpr int PW = (NG * PT / 4) / GW;
-    uint32_t dwv[GW][DKCH][DPARTS];
-    f32x4 dwb4[GW], dwm4[GW];
-    int dpix[PW], dtap[DKCH];
-    const int dsel = I8 ? dw_mma_dword_index_i8(lane) : dw_mma_dword_index(lane);
-#pragma unroll
-    for (int gi = 0; gi < GW; gi++) {
-        const int g = NG >= 4 ? wave + 4 * gi : wave % NG;
-#pragma unroll
-        for (int kc = 0; kc < DKCH; kc++)
-#pragma unroll
-            for (int hl = 0; hl < DPARTS; hl++) dwv[gi][kc][hl] = a.dw_mma[((g * DKCH + kc) * DPARTS + hl) * 64 + lane];
-        dwb4[gi] = *(const f32x4 *)(a.dw_b + acc_cout(g, lane, 0));
-        dwm4[gi] = load_mult(I8 ? a.dw_m : nullptr, acc_cout(g, lane, 0));
-    }
-#pragma unroll
-    for (int pi = 0; pi < PW; pi++) {
-        const int pt = NG >= 4 ? pi : wave / NG + pi * (4 / NG);
-        const int p = acc_pixel(pt, lane);
-        dpix[pi] = (p / TW) * STRIDE * ROWP + (p % TW) * STRIDE * LDIN + (I8 ? 0 : ((lane >> 4) & 1) * 8);
-    }
-#pragma unroll
-    for (int kc = 0; kc < DKCH; kc++) {
-        const int tap = I8 ? kc * 4 + (lane >> 4) : kc * 2 + (lane >> 5);
-        dtap[kc] = tap < 9 ? (tap / 3) * ROWP + (tap % 3) * LDIN : -1;
-    }
-    __builtin_amdgcn_s_waitcnt(0x0F70);                                // everything above is in registers: no global access below this line
-    lds_barrier();                                                     // (the producer's prologue: tile 0 has landed)
-
-    for (int k = 0; k < n_my; k++) {
-        const T *s_in_b = s_in + (k % NBUF) * IN_ELEMS;
-        const bool st = k > 0, ld = k + DIST < n_my;
-        if constexpr (!PROD) {
-            // this wave's quarter of the previous tile's stores (s_out / s_lat are rewritten after the next barrier, which the wave passes only
-            // with these LDS reads complete) and of the halo DIST tiles ahead (its buffer was last read before the previous interval's first barrier)
-            if (st) store_tile(p_img, p_oy0, p_ox0);
-            if (ld) { dma(pf.tx, pf.ty, pf.img, s_in + ((k + DIST) % NBUF) * IN_ELEMS); step.advance(pf); }
-            p_img = cur.img; p_oy0 = cur.ty * TH; p_ox0 = cur.tx * TW;
-            step.advance(cur);
-        }
-        // ---- depthwise 3x3 as diagonal-weight implicit GEMM (K_b phase 2)
-#pragma unroll
-        for (int gi = 0; gi < GW; gi++) {
-            const int g = NG >= 4 ? wave + 4 * gi : wave % NG;
-            typename M::Acc dacc[DPARTS][PW];
-#pragma unroll
-            for (int hl = 0; hl < DPARTS; hl++)
-#pragma unroll
-                for (int pi = 0; pi < PW; pi++) dacc[hl][pi] = acc_init<T>(dwb4[gi]);
-            constexpr int NB = DKCH * PW, DDEPTH = NB < 4 ? NB : 4;
-            Frag bq[DDEPTH];
-            auto bload = [&](int idx) -> Frag {
-                const int kc = idx / PW, pi = idx % PW;
-                return dtap[kc] >= 0 ? *(const Frag *)(s_in_b + dpix[pi] + dtap[kc] + g * 16) : M::zero();
-            };
-#pragma unroll
-            for (int d = 0; d < DDEPTH - 1; d++) bq[d] = bload(d);
-#pragma unroll
-            for (int kc = 0; kc < DKCH; kc++) {
-                typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-                Frag af[DPARTS];
-#pragma unroll
-                for (int hl = 0; hl < DPARTS; hl++) {
-                    u32x4 wa;
-                    uint32_t wd = dwv[gi][kc][hl];
-                    asm volatile("" : "+v"(wd));
-#pragma unroll
-                    for (int d = 0; d < 4; d++) wa[d] = dsel == d ? wd : 0u;
-                    af[hl] = __builtin_bit_cast(Frag, wa);
-                }
-#pragma unroll
-                for (int pi = 0; pi < PW; pi++) {
-                    const int idx = kc * PW + pi;
-                    if (idx + DDEPTH - 1 < NB) bq[(idx + DDEPTH - 1) % DDEPTH] = bload(idx + DDEPTH - 1);
-#pragma unroll
-                    for (int hl = 0; hl < DPARTS; hl++) dacc[hl][pi] = M::mma(af[hl], bq[idx % DDEPTH], dacc[hl][pi]);
-                }
-            }
-#pragma unroll
-            for (int pi = 0; pi < PW; pi++) {
-                const int pt = NG >= 4 ? pi : wave / NG + pi * (4 / NG);
-                if constexpr (I8) {
-                    typename M::Acc tot;
-#pragma unroll
-                    for (int r = 0; r < 4; r++) tot[r] = dacc[0][pi][r] * 128 + dacc[DPARTS - 1][pi][r];
-                    store_mid_u8<LDA>(s_a, dwm4[gi], dwb4[gi], tot, g, pt, lane);
-                } else {
-                    store_acc<T, LDA>(s_a, dwm4[gi], dwb4[gi], dacc[0][pi], g, pt, lane, true);
-                }
-            }
-        }
-        lds_barrier();
-        // ---- pointwise GEMM + epilogue (K_b phases 3-4)
-        {
-            typename M::Acc acc[WS::NI][WS::NJ];
-#pragma unroll
-            for (int i = 0; i < WS::NI; i++)
-#pragma unroll
-                for (int j = 0; j < WS::NJ; j++) acc[i][j] = acc_init<T>(pw_bias[i]);
-            gemm_stationary<T, WS::NI, WS::NJ, KCH>(acc, wst, [&](int j, int kc) -> Frag {
-                const int kb = kc * M::K + (lane >> 4) * M::KPL;
-                const int p = acc_pixel(wp + j * WS::WP, lane);
-                return kb < CIN ? *(const Frag *)(s_a + p * LDA + kb) : M::zero();
-            });
-#pragma unroll
-            for (int i = 0; i < WS::NI; i++)
-#pragma unroll
-                for (int j = 0; j < WS::NJ; j++)
-                    store_acc<T, LDO>(s_out, pw_mult[i], pw_bias[i], acc[i][j], wn + i * WS::WN, wp + j * WS::WP, lane, true);
-        }
-        if constexpr (LAT) {
-            lds_barrier();
-            // ---- fused lateral on the LDS-resident output tile (K_b phase 5): wave = output-channel tile, all pixel tiles
-            typename M::Acc acc2[1][PT];
-#pragma unroll
-            for (int j = 0; j < PT; j++) acc2[0][j] = acc_init<T>(lat_bias);
-            gemm_stationary<T, 1, PT, LKCH>(acc2, lst, [&](int j, int kc) -> Frag {
-                const int kb = kc * M::K + (lane >> 4) * M::KPL;
-                return *(const Frag *)(s_out + acc_pixel(j, lane) * LDO + kb);
-            });
-#pragma unroll
-            for (int j = 0; j < PT; j++) store_acc<T, LDL>(s_lat, lat_mult, lat_bias, acc2[0][j], wave, j, lane, true);
-        }
-        if constexpr (!PROD) wait_next_halo(st, ld);                   // this wave's quarter of tile k + 1; the barrier publishes all four
-        lds_barrier();
-    }
-    if constexpr (!PROD) { if (n_my > 0) store_tile(p_img, p_oy0, p_ox0); }
-}
-
-// probe knob RF_DWPWWS: 0 = off (K_b everywhere); 2 / 3 = halo buffers of the warp-specialised blocks
-static int dwpw_ws_variant() { return knob(K_DWPWWS); }
-
-template <typename T, int CIN, int COUT, int STRIDE, int TH, int TW, bool LAT, int NBUF, bool PADROW, bool PROD = true>
-static void dwpw_ws_launch(hipStream_t s, const DwPwParams<T> *p, int tiles_x, int tiles_y) {
-    typedef DwPwWsCfg<T, CIN, COUT, STRIDE, TH, TW, LAT, NBUF, PADROW, PROD> W;
-    auto kern = dwpw_ws_kernel<T, CIN, COUT, STRIDE, TH, TW, LAT, NBUF, PADROW, PROD>;
-    static std::atomic<int> resident_cache[kMaxDevices] = {};
-    const int dev = launch_device();
-    int resident = resident_cache[dev].load(std::memory_order_acquire);
-    if (!resident) {
-        set_max_lds(kern, W::LDS_BYTES);
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kern, W::THREADS, W::LDS_BYTES) != hipSuccess || nb < 1) nb = 1;
-        resident = nb;
-        resident_cache[dev].store(resident, std::memory_order_release);
-    }
-    DwPwArgs<T> a{p->in, p->out, p->dw_w, p->dw_b, p->dw_mma, p->pw_w, p->pw_b, p->lat_w, p->lat_b, p->lat_out, p->pw_m, p->lat_m, p->dw_m,
-                  p->hin, p->win, p->hout, p->wout, tiles_x, tiles_y, p->n * tiles_x * tiles_y};
-    hipLaunchKernelGGL(kern, dim3(persistent_grid(a.nblk, resident)), dim3(W::THREADS), W::LDS_BYTES, s, a);
-}
-#endif  // RF_PROBES
 
 template <typename T, int CIN, int COUT, int STRIDE, bool HAS_DW, int TH, int TW, bool LAT, bool PADROW>
 static void dwpw_launch(hipStream_t s, const DwPwParams<T> *p, int tiles_x, int tiles_y) {
@@ -2549,77 +2029,32 @@ static void dwpw_launch(hipStream_t s, const DwPwParams<T> *p, int tiles_x, int 
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), C::LDS_BYTES, s, a);
 }
 
-template <typename T, int CIN, int COUT, int STRIDE, bool HAS_DW, int TH, int TW, bool PADROW = false>
+template <typename T, int CIN, int COUT, int STRIDE, bool HAS_DW, int TH, int TW>
 static TileInfo dwpw_dispatch(hipStream_t s, const DwPwParams<T> *p, int hout, int wout) {
+    // halo rows padded to the bank row (PADROW) wherever a 16-pixel MFMA tile spans two halo rows
+    constexpr bool PADROW = sizeof(T) <= 2 && HAS_DW && STRIDE == 1 && TW == 8 && CIN >= 32;
     typedef DwPwCfg<T, CIN, COUT, STRIDE, HAS_DW, TH, TW, PADROW> C;
-    // halo rows padded to the bank row (PADROW) wherever a 16-pixel MFMA tile spans two halo rows; RF_DWPAD=0 (probe knob): round-1 layout
-    constexpr bool WANTS_PADROW = !PADROW && sizeof(T) <= 2 && HAS_DW && STRIDE == 1 && TW == 8 && CIN >= 32;
-#ifdef RF_PROBES
-    if constexpr (WANTS_PADROW) {
-        if (p && knob(K_DWPAD)) return dwpw_dispatch<T, CIN, COUT, STRIDE, HAS_DW, TH, TW, true>(s, p, hout, wout);
-    }
-#else
-    if constexpr (WANTS_PADROW) return dwpw_dispatch<T, CIN, COUT, STRIDE, HAS_DW, TH, TW, true>(s, p, hout, wout);
-    else {
-#endif
     int tiles_x = (wout + TW - 1) / TW, tiles_y = (hout + TH - 1) / TH;
     TileInfo ti{TH, TW, C::LDS_BYTES, tiles_x * tiles_y};
     if (!p) return ti;
-#ifdef RF_PROBES
-    // warp-specialised instances (K_b'): the stride-1 blocks with 64 / 128 channels, with or without the fused lateral
-    if constexpr (sizeof(T) <= 2 && HAS_DW && STRIDE == 1 && CIN == COUT && (CIN == 64 || CIN == 128) && C::DWMMA && C::STAT) {
-        const int v = dwpw_ws_variant();
-        if (v == 12 || v == 13) {           // K_b'': the memory side spread over the four GEMM waves (no producer wave)
-            if constexpr (DwPwWsCfg<T, CIN, COUT, STRIDE, TH, TW, true, 2, PADROW, false>::SPLIT_OK) {
-                if (p->lat_out) {
-                    if (v == 12) dwpw_ws_launch<T, CIN, COUT, STRIDE, TH, TW, true, 2, PADROW, false>(s, p, tiles_x, tiles_y);
-                    else dwpw_ws_launch<T, CIN, COUT, STRIDE, TH, TW, true, 3, PADROW, false>(s, p, tiles_x, tiles_y);
-                    return ti;
-                }
-            }
-            if constexpr (DwPwWsCfg<T, CIN, COUT, STRIDE, TH, TW, false, 2, PADROW, false>::SPLIT_OK) {
-                if (!p->lat_out) {
-                    if (v == 12) dwpw_ws_launch<T, CIN, COUT, STRIDE, TH, TW, false, 2, PADROW, false>(s, p, tiles_x, tiles_y);
-                    else dwpw_ws_launch<T, CIN, COUT, STRIDE, TH, TW, false, 3, PADROW, false>(s, p, tiles_x, tiles_y);
-                    return ti;
-                }
-            }
-        }
-        if (v == 2 || v == 3) {
-            if (p->lat_out) {
-                if (v == 2) dwpw_ws_launch<T, CIN, COUT, STRIDE, TH, TW, true, 2, PADROW>(s, p, tiles_x, tiles_y);
-                else dwpw_ws_launch<T, CIN, COUT, STRIDE, TH, TW, true, 3, PADROW>(s, p, tiles_x, tiles_y);
-            } else {
-                if (v == 2) dwpw_ws_launch<T, CIN, COUT, STRIDE, TH, TW, false, 2, PADROW>(s, p, tiles_x, tiles_y);
-                else dwpw_ws_launch<T, CIN, COUT, STRIDE, TH, TW, false, 3, PADROW>(s, p, tiles_x, tiles_y);
-            }
-            return ti;
-        }
-    }
-#endif
     // K_b(8) for the 128-channel blocks, where it measured faster (A/B inside one call each, tools/gpu/r5.sh c4 / c7, profiles/r05_wide_blocks_ab.txt;
-    // every variant bit-identical, tools/probes/knob_equal.py):
+    // every variant bit-identical):
     //   fp16: the block WITH the fused lateral (conv21 + conv22 + rf_c2_lateral) -- at 126 VGPRs two 8-wave workgroups share a CU (16 waves) where K_b's
     //         182-VGPR build has two 4-wave ones: 34.8 -> 33.0 us; the plain blocks 27.7 -> 28.0 us: they stay on K_b;
     //   int8: the other way round -- the four plain blocks 25.0 -> 23.1 us each (121 VGPRs), the lateral block 29.0 -> 30.6 us (148 VGPRs: one workgroup per CU).
-    // Probe knobs: RF_WIDE128 (fp16) 0 = none, 1 = lateral block, 2 = all five; RF_WIDE_I8 bit 0 = 256-channel block, bit 1 = plain blocks, bit 2 = lateral block.
-    if constexpr (HAS_DW && STRIDE == 1 && CIN == 128 && COUT == 128 && ((sizeof(T) == 2 && TH == 4 && (TW == 8 || (kProbeBuild && TW == 16))) || (sizeof(T) == 1 && TH == 4 && TW == 16))) {
-        constexpr bool I8W = sizeof(T) == 1;
-        const int v = I8W ? knob(K_WIDE_I8) : knob(K_WIDE128);
-        const bool lat_wide = I8W ? (v & 4) != 0 : v >= 1, plain_wide = I8W ? (v & 2) != 0 : v == 2;
-        if constexpr (!I8W || kProbeBuild) {
-            if (lat_wide && p->lat_out) { dwpw_wide_launch<T, CIN, COUT, TH, TW, true, PADROW, 2>(s, p, tiles_x, tiles_y); return ti; }
-        }
-        if constexpr (I8W || kProbeBuild) {
-            if (plain_wide && !p->lat_out) { dwpw_wide_launch<T, CIN, COUT, TH, TW, false, PADROW, 2>(s, p, tiles_x, tiles_y); return ti; }
-        }
+    if constexpr (HAS_DW && STRIDE == 1 && CIN == 128 && COUT == 128 && sizeof(T) == 2 && TH == 4 && TW == 8) {
+        if (p->lat_out) { dwpw_wide_launch<T, CIN, COUT, TH, TW, true, PADROW, 2>(s, p, tiles_x, tiles_y); return ti; }
+    }
+    if constexpr (HAS_DW && STRIDE == 1 && CIN == 128 && COUT == 128 && sizeof(T) == 1 && TH == 4 && TW == 16) {
+        if (!p->lat_out) { dwpw_wide_launch<T, CIN, COUT, TH, TW, false, PADROW, 2>(s, p, tiles_x, tiles_y); return ti; }
     }
     if (p->lat_out) {
         // laterals tap the outputs of blocks 4 (64ch), 10 (128ch) and 12 (256ch)
-        // fp16 256-channel block: eight waves, every weight stationary (K_b(8), round 5); RF_WIDE256=0 (probe knob): K_b with the streamed matrix
+        // 256-channel block: eight waves, every weight stationary (K_b(8), round 5)
         if constexpr (HAS_DW && STRIDE == 1 && CIN == 256 && COUT == 256 && ((sizeof(T) == 2 && TH == 4 && TW == 8) || (sizeof(T) == 1 && TH == 8 && TW == 8))) {
             // fp16 37.3 -> 26.6 us (tools/gpu/r5.sh c2), int8 23.6 -> 20.4 us (c7)
-            if (sizeof(T) == 2 ? knob(K_WIDE256) != 0 : (knob(K_WIDE_I8) & 1) != 0) { dwpw_wide_launch<T, CIN, COUT, TH, TW, true, PADROW>(s, p, tiles_x, tiles_y); return ti; }
+            dwpw_wide_launch<T, CIN, COUT, TH, TW, true, PADROW>(s, p, tiles_x, tiles_y);
+            return ti;
         }
         if constexpr (HAS_DW && STRIDE == 1 && CIN == COUT && COUT >= 64) dwpw_launch<T, CIN, COUT, STRIDE, HAS_DW, TH, TW, true, PADROW>(s, p, tiles_x, tiles_y);
         else throw LaunchUnsupported("fused lateral: only stride-1 blocks with cin == cout >= 64 have a kernel instance");
@@ -2627,41 +2062,23 @@ static TileInfo dwpw_dispatch(hipStream_t s, const DwPwParams<T> *p, int hout, i
         dwpw_launch<T, CIN, COUT, STRIDE, HAS_DW, TH, TW, false, PADROW>(s, p, tiles_x, tiles_y);
     }
     return ti;
-#ifndef RF_PROBES
-    }
-#endif
 }
 
-// the layer table of SURVEY.md App. A -> tile geometry.  The product build holds ONE tile shape per (precision, layer) -- the winner of the A/B
-// measurements cited below -- and only the layers that precision's engine launches through K_b; the probe build (RF_PROBES) adds the shapes that lost,
-// selected by the RF_TILE* knobs, the fp16 instances of the front blocks (RF_STEM2=0 / RF_DWPW2=0 un-fuse them) and the plain 1x1 instances.
+// the layer table of SURVEY.md App. A -> tile geometry: ONE tile shape per (precision, layer) -- the winner of the A/B measurements cited below --
+// and only the layers that precision's engine launches through K_b.
 template <typename T>
 static TileInfo dwpw_select(hipStream_t s, const DwPwParams<T> *p, int cin, int cout, int stride, bool has_dw, int hout,
                             int wout) {
 #define RF_DWPW(CI, CO, ST, DW, TH_, TW_) \
     if (cin == CI && cout == CO && stride == ST && has_dw == DW) return dwpw_dispatch<T, CI, CO, ST, DW, TH_, TW_>(s, p, hout, wout);
     constexpr bool I8 = sizeof(T) == 1;
-#ifdef RF_PROBES
-    constexpr bool FRONT = sizeof(T) >= 2;       // fp16 with RF_STEM2=0 / RF_DWPW2=0 runs blocks 0-3 through K_b as well
-#else
     constexpr bool FRONT = sizeof(T) == 4;                  // fp16: blocks 0-3 live in stem2 / dwpw2; int8: block 0 lives in the stem, 1-3 have their own shapes below
-#endif
     if constexpr (FRONT) { RF_DWPW(8, 16, 1, true, 8, 32) }
     if constexpr (I8) {
         // Tile shapes of the int8 engine's big-map blocks (fp16 runs them inside stem2 / dwpw2).  These kernels spend their time in the requantising
         // epilogue (VALU-active 0.5-0.64 of the chip), which is per element, so the tile shape moves little; measured one by one inside one call
         // (tools/gpu/rounds_3_4.sh r4_call18, us per 256 images, all bit-identical): 16->32 s2 8x8 56.2 | 8x16 53.5 | 16x16 57.2;  32->32 8x8 68.6 | 8x16 67.1 |
         // 16x16 69.6;  32->64 s2 4x8 32.7 | 8x8 30.5 | 8x16 34.4;  64->128 s2 4x8 18.6 | 8x8 22.1.  The product = the best of each.
-#ifdef RF_PROBES
-        const int va = knob(K_TILE_A), vb = knob(K_TILE_B), vc = knob(K_TILE_C), vd = knob(K_TILE_D);      // 0 = round-3 shapes
-        if (va == 2) { RF_DWPW(16, 32, 2, true, 16, 16) }
-        if (va == 0) { RF_DWPW(16, 32, 2, true, 8, 8) }
-        if (vb == 2) { RF_DWPW(32, 32, 1, true, 16, 16) }
-        if (vb == 0) { RF_DWPW(32, 32, 1, true, 8, 8) }
-        if (vc == 2) { RF_DWPW(32, 64, 2, true, 8, 16) }
-        if (vc == 0) { RF_DWPW(32, 64, 2, true, 4, 8) }
-        if (vd == 1) { RF_DWPW(64, 128, 2, true, 8, 8) }
-#endif
         RF_DWPW(16, 32, 2, true, 8, 16)
         RF_DWPW(32, 32, 1, true, 8, 16)
         RF_DWPW(32, 64, 2, true, 8, 8)
@@ -2671,46 +2088,16 @@ static TileInfo dwpw_select(hipStream_t s, const DwPwParams<T> *p, int cin, int 
         RF_DWPW(32, 32, 1, true, 8, 8)
         RF_DWPW(32, 64, 2, true, 4, 8)
     }
-#ifdef RF_PROBES
-    if constexpr (sizeof(T) <= 2) {
-        const int v64 = knob(K_TILE64);
-        if (v64 == 1) { RF_DWPW(64, 64, 1, true, 8, 8) }
-        if (v64 == 2) { RF_DWPW(64, 64, 1, true, 8, 16) }
-    }
-#endif
     RF_DWPW(64, 64, 1, true, 4, 8)
     RF_DWPW(64, 128, 2, true, 4, 8)
     // 128-channel blocks: 4x16 tiles for the int8 engine (26.0 -> 24.9 us each, tools/gpu/rounds_3_4.sh r4_call16, r4_call18); fp16: 27.7 -> 28.3, stays 4x8.
-    // RF_TILE128 = 0 / 1 / 2 / 3 forces 4x8 / 8x8 / 4x16 / 8x16 (probe knob; -1 = the per-precision default)
-#ifdef RF_PROBES
-    if constexpr (sizeof(T) <= 2) {
-        const int v128 = knob(K_TILE128) < 0 ? (I8 ? 2 : 0) : knob(K_TILE128);
-        if (v128 == 1) { RF_DWPW(128, 128, 1, true, 8, 8) }
-        if (v128 == 2) { RF_DWPW(128, 128, 1, true, 4, 16) }
-        if (v128 == 3) { RF_DWPW(128, 128, 1, true, 8, 16) }
-        RF_DWPW(128, 128, 1, true, 4, 8)
-    }
-#endif
     if constexpr (I8) { RF_DWPW(128, 128, 1, true, 4, 16) }
     else { RF_DWPW(128, 128, 1, true, 4, 8) }
     RF_DWPW(128, 256, 2, true, 4, 8)
     // 256-channel block, 8x8 tiles: the streamed 256 x 256 weight matrix is read once per 64 pixels instead of 32.  Measured (tools/gpu/rounds_3_4.sh r4_call13):
     // int8 26.4 -> 24.4 us, fp16 35.5 -> 35.6 (its 64 accumulator registers on top of the fragment stream: 2-14 spills with the lateral): int8 only.
-    // RF_TILE256 = 0 / 1 forces 4x8 / 8x8 (probe knob; 2 = the per-precision default)
-#ifdef RF_PROBES
-    if constexpr (sizeof(T) <= 2) {
-        const int v256 = knob(K_TILE256);
-        if (v256 == 1) { RF_DWPW(256, 256, 1, true, 8, 8) }
-        if (v256 == 0) { RF_DWPW(256, 256, 1, true, 4, 8) }
-    }
-#endif
     if constexpr (I8) { RF_DWPW(256, 256, 1, true, 8, 8) }
     else { RF_DWPW(256, 256, 1, true, 4, 8) }
-#ifdef RF_PROBES
-    RF_DWPW(256, 64, 1, false, 4, 8)          // plain 1x1 instances (the engines fuse the laterals into the producing block)
-    RF_DWPW(128, 64, 1, false, 4, 8)
-    RF_DWPW(64, 64, 1, false, 8, 8)
-#endif
 #undef RF_DWPW
     return TileInfo{0, 0, 0, 0};
 }
@@ -2745,10 +2132,8 @@ struct DwPw2Args {
     const uint32_t *dwa_mma; const float *dwa_b; const half_t *pwa_w; const float *pwa_b;
     const uint32_t *dwb_mma; const float *dwb_b; const half_t *pwb_w; const float *pwb_b;
     int hin, win, hout, wout, tiles_x, tiles_y, nblk;
-    int ring;                                           // 1 = depthwise A as one ring pipeline (round 4), 0 = chunk by chunk (probe knob RF_DWPW2_RING)
 };
 
-template <bool RINGP, bool HPAD = true, bool LAY2 = true>
 __global__ __launch_bounds__(kThreads, 3) void dwpw2_kernel(DwPw2Args a) {
     typedef half_t T;
     typedef Mma<T> M;
@@ -2761,22 +2146,22 @@ __global__ __launch_bounds__(kThreads, 3) void dwpw2_kernel(DwPw2Args a) {
     constexpr int PTA = (NR + 15) / 16;                                // 10 MFMA pixel tiles of block A
     constexpr int UA = PTA / 2;                                        // units (pixel tiles) of block A per wave: 5
     constexpr int LD = lds_row<T>(32);                                 // 48 halfs = 96 B per pixel: conflict-free B-fragment pitch
-    // LAY2 (round 4, from the same counters): every 8-byte epilogue write of 16 pixels at a 96-byte pitch is a 4-way bank conflict (24 banks per pixel:
+    // Round 4, from the same counters: every 8-byte epilogue write of 16 pixels at a 96-byte pitch is a 4-way bank conflict (24 banks per pixel:
     // four distinct bank positions), and block B's stride-2 depthwise fragments collide 2-way on the contiguous block-A tile.  The depthwise-A tile
     // therefore sits at 80 bytes per pixel (writes 2-way, the pointwise reads 2-way instead of free: 5 x 8 + 5 x 8 instead of 5 x 16 + 5 x 4 LDS cycles per
     // wave), the block-A tile at 80 bytes per pixel in rows of 88 slots (writes 2-way, block B's stride-2 reads conflict-free) and the output tile at
     // 144 bytes per pixel (writes 2-way).
-    constexpr int LDO = LAY2 ? 72 : lds_row<T>(CB);                    // 72 / 80
-    constexpr int LDSA = LAY2 ? 40 : LD;                               // depthwise-A result: pixel pitch
-    constexpr int LDM = LAY2 ? 40 : LD, MROW = LAY2 ? 88 * 8 : RW * LD;      // block-A tile: pixel pitch, row pitch (halfs)
+    constexpr int LDO = 72;                                            // output tile: pixel pitch (halfs)
+    constexpr int LDSA = 40;                                           // depthwise-A result: pixel pitch
+    constexpr int LDM = 40, MROW = 88 * 8;                             // block-A tile: pixel pitch, row pitch (halfs)
     // Halo rows are padded by 4 slots of 16 B (HROW = 118 slots = 6 mod 16): a depthwise-A pixel tile is 16 consecutive pixels of the 17-wide region, so
     // nearly every tile wraps from one halo row to the next; with the plain 19-pixel pitch (114 slots = 2 mod 16) the wrap shifted the second part of
     // the tile by 12 slots and its ds_read_b128 lane groups collided 2-way (SQ_LDS_BANK_CONFLICT 0.42 of this kernel's cycles, LDS busy 0.75:
     // tools/gpu/rounds_3_4.sh r4_call22); 118 makes the wrap look like 17 contiguous pixels to the bank function (6 slots per pixel).
-    constexpr int HROW = HW * LD + (HPAD ? 32 : 0);                    // halfs per halo row
+    constexpr int HROW = HW * LD + 32;                                 // halfs per halo row
     constexpr int IN_BYTES = HH * HROW * 2, A_BYTES = PTA * 16 * LDSA * 2, B_BYTES = P * LD * 2, OUT_BYTES = P * LDO * 2;
     constexpr int NPF = (NH * 4 + kThreads - 1) / kThreads;            // halo items (16 B) per thread: 4
-    static_assert(PTA % 2 == 0 && (LAY2 ? RH * MROW * 2 : PTA * 16 * LD * 2) <= IN_BYTES && B_BYTES + OUT_BYTES <= A_BYTES && RW * LDM <= MROW, "region reuse");
+    static_assert(PTA % 2 == 0 && RH * MROW * 2 <= IN_BYTES && B_BYTES + OUT_BYTES <= A_BYTES && RW * LDM <= MROW, "region reuse");
     __shared__ __attribute__((aligned(16))) unsigned char s_raw[IN_BYTES + A_BYTES];
     T *s_in = (T *)s_raw;                              // halo                       (phases 1-2)
     T *s_mid = (T *)s_raw;                             // block-A output tile        (phases 3-4)
@@ -2879,38 +2264,14 @@ __global__ __launch_bounds__(kThreads, 3) void dwpw2_kernel(DwPw2Args a) {
             M::Acc acc[UA];
 #pragma unroll
             for (int i = 0; i < UA; i++) acc[i] = dwa_b;                 // bias rides in the accumulator (acc_init)
-            if constexpr (RINGP) {
-                // round 4: the 25 (chunk, pixel tile) steps as ONE software pipeline -- B fragments run RING - 1 reads ahead of their
-                // MFMAs across chunk boundaries (round 3 read a chunk's five fragments, multiplied, and only then read the next chunk's:
-                // one exposed LDS round trip per chunk)
-                constexpr int NB = kDwMmaChunks * UA, RING = 4;
-                Frag bq[RING];
-                auto bload = [&](int idx) -> Frag {
-                    const int kc = idx / UA, i = idx % UA;
-                    return tap_a(kc) >= 0 ? *(const Frag *)(s_in + pa_base[i] + tap_a(kc)) : M::zero();
-                };
 #pragma unroll
-                for (int d = 0; d < RING - 1; d++) bq[d] = bload(d);
+            for (int kc = 0; kc < kDwMmaChunks; kc++) {
+                Frag bf[UA];
 #pragma unroll
-                for (int kc = 0; kc < kDwMmaChunks; kc++) {
-                    const Frag af = dw_frag(dwa[kc]);
+                for (int i = 0; i < UA; i++) bf[i] = tap_a(kc) >= 0 ? *(const Frag *)(s_in + pa_base[i] + tap_a(kc)) : M::zero();
+                const Frag af = dw_frag(dwa[kc]);
 #pragma unroll
-                    for (int i = 0; i < UA; i++) {
-                        const int idx = kc * UA + i;
-                        if (idx + RING - 1 < NB) bq[(idx + RING - 1) % RING] = bload(idx + RING - 1);
-                        acc[i] = M::mma(af, bq[idx % RING], acc[i]);
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int kc = 0; kc < kDwMmaChunks; kc++) {
-                    Frag bf[UA];
-#pragma unroll
-                    for (int i = 0; i < UA; i++) bf[i] = tap_a(kc) >= 0 ? *(const Frag *)(s_in + pa_base[i] + tap_a(kc)) : M::zero();
-                    const Frag af = dw_frag(dwa[kc]);
-#pragma unroll
-                    for (int i = 0; i < UA; i++) acc[i] = M::mma(af, bf[i], acc[i]);
-                }
+                for (int i = 0; i < UA; i++) acc[i] = M::mma(af, bf[i], acc[i]);
             }
 #pragma unroll
             for (int i = 0; i < UA; i++) store_acc<T, LDSA>(s_a, ones, dwa_b, acc[i], g, (wave >> 1) + 2 * i, lane, true);
@@ -2932,11 +2293,7 @@ __global__ __launch_bounds__(kThreads, 3) void dwpw2_kernel(DwPw2Args a) {
                 uint2 h;
                 h.x = inside ? pack_f16(acc[0], acc[1], true) : 0u;
                 h.y = inside ? pack_f16(acc[2], acc[3], true) : 0u;
-                if constexpr (LAY2) {
-                    if (ry < 0x4000) *(uint2 *)(s_mid + ry * MROW + rx * LDM + acc_cout(g, lane, 0)) = h;     // (tail lanes own no pixel of the 2-D tile)
-                } else {
-                    *(uint2 *)(s_mid + (((wave >> 1) + 2 * i) * 16 + (lane & 15)) * LD + acc_cout(g, lane, 0)) = h;     // the halo is dead since the last barrier
-                }
+                if (ry < 0x4000) *(uint2 *)(s_mid + ry * MROW + rx * LDM + acc_cout(g, lane, 0)) = h;     // (tail lanes own no pixel of the 2-D tile)
             }
         }
         RF_TRACE(5, 3);
@@ -2978,243 +2335,6 @@ __global__ __launch_bounds__(kThreads, 3) void dwpw2_kernel(DwPw2Args a) {
     }
 }
 
-#ifdef RF_PROBES      // K_b2c: measured and rejected (110.8 vs 90.8 us), probe build only
-// =============================================================================================
-// K_b2c  dwpw2 with the depthwise -> pointwise hops CHAINED IN REGISTERS (round 4).
-//   In the swapped GEMM (D[cout][pixel]) a lane's accumulator registers hold 4 consecutive channels of the SAME pixel (column) the lane feeds
-//   as a B operand: D rows 4 kb .. 4 kb + 3 of two 16-channel groups ARE the lane's 8 K slots of the next GEMM, if that GEMM's K axis is
-//   ordered  k = 8 kb + e  <->  channel 4 kb + e (e < 4), 16 + 4 kb + (e - 4) (e >= 4).  The permutation is applied to the pointwise weights when
-//   their A fragments are loaded (two 8-byte loads instead of one 16-byte load, once per workgroup), so the depthwise result never goes through
-//   LDS: no s_a / s_b tiles, 13 -> 8 ds_write_b64 and 37 -> 30 ds_read_b128 per wave and tile, 5 -> 3 barriers.
-//   Why it matters: SQ_LDS_IDX_ACTIVE said the LDS pipe of K_b2 was busy 0.75 of the kernel's time, 0.41 in bank-conflict cycles
-//   (tools/gpu/rounds_3_4.sh r4_call22): 4-way conflicts of every 8-byte epilogue write at a 96-byte pixel pitch, 2-way conflicts of the depthwise reads on
-//   tiles that wrap a halo row.  Layouts here: halo rows padded to 118 slots of 16 B (= 6 mod 16: a wrap looks like contiguous pixels, see K_b2);
-//   the block-A tile at an 80-byte pixel pitch and 88 slots per row (its only readers are block B's stride-2 depthwise fragments: conflict-free;
-//   writes 2-way instead of 4-way); the output tile at 144 bytes per pixel (2-way writes).
-//   Work split: phase A  wave w -> region pixel tiles w, w + 4, w + 8 (both channel groups, both output-channel tiles: 10 + 2 MFMAs per tile);
-//   phase B  wave w -> pixel tile w & 1, output-channel tiles 2 (w >> 1), +1 (the depthwise part is computed by both waves of a pixel tile).
-// =============================================================================================
-__global__ __launch_bounds__(kThreads, 3) void dwpw2c_kernel(DwPw2Args a) {
-    typedef half_t T;
-    typedef Mma<T> M;
-    typedef M::Frag Frag;
-    typedef f16x8 V;
-    constexpr int CI = 32, CB = 64;
-    constexpr int TH = 4, TW = 8, P = TH * TW;
-    constexpr int RH = 2 * TH + 1, RW = 2 * TW + 1, NR = RH * RW;      // block-A outputs the tile needs: 9 x 17 = 153
-    constexpr int HH = RH + 2, HW = RW + 2, NH = HH * HW;              // input halo: 11 x 19 = 209
-    constexpr int PTA = (NR + 15) / 16, UA = (PTA + 3) / 4;            // 10 region pixel tiles, up to 3 per wave
-    constexpr int LD = 48, HROW = HW * LD + 32;                        // halo: 96 B per pixel, 118 slots per row
-    constexpr int LDM = 40, MROW = 88 * 8;                             // block-A tile: 80 B per pixel, 88 slots per row
-    constexpr int LDO = 72;                                            // output tile: 144 B per pixel
-    constexpr int IN_BYTES = HH * HROW * 2, MID_BYTES = RH * MROW * 2, OUT_BYTES = P * LDO * 2;
-    constexpr int NPF = (NH * 4 + kThreads - 1) / kThreads;            // halo items (16 B) per thread: 4
-    // Per-phase constants live in LDS, not in registers (the kernel needs 212 VGPRs with them resident, 168 is the budget of 3 workgroups per CU and at
-    // 2 the chain is slower than K_b2: 127 vs 102 us): bias vectors [10][16] fp32, the chained pointwise fragments [2 + 4][64 lanes] and block B's
-    // depthwise dwords [2][5][64]; each phase reads its share once per tile (4 + 2 (+ 10 narrow) reads per wave).
-    constexpr int BIAS_BYTES = 10 * 16 * 4, PWF_BYTES = 6 * 64 * 16, DWB_BYTES = 2 * 2 * kDwMmaChunks * 64 * 4;
-    static_assert(RW * LDM <= MROW && IN_BYTES % 16 == 0 && MID_BYTES % 16 == 0 && OUT_BYTES % 16 == 0 && BIAS_BYTES % 16 == 0, "LDS carve");
-    __shared__ __attribute__((aligned(16))) unsigned char s_raw[IN_BYTES + MID_BYTES + OUT_BYTES + BIAS_BYTES + PWF_BYTES + DWB_BYTES];
-    T *s_in = (T *)s_raw;                              // halo                (written in phase 1, read in phase A)
-    T *s_mid = (T *)(s_raw + IN_BYTES);                // block-A output tile (written in phase A, read in phase B)
-    T *s_out = (T *)(s_raw + IN_BYTES + MID_BYTES);    // output tile         (written in phase B, read by the store)
-    float *s_bias = (float *)(s_raw + IN_BYTES + MID_BYTES + OUT_BYTES);                       // [dwa 0,1 | pwa 0,1 | dwb 0,1 | pwb 0..3][16]
-    Frag *s_pwf = (Frag *)(s_raw + IN_BYTES + MID_BYTES + OUT_BYTES + BIAS_BYTES);             // [pwa 0,1 | pwb 0..3][64]
-    uint32_t *s_dwb = (uint32_t *)(s_raw + IN_BYTES + MID_BYTES + OUT_BYTES + BIAS_BYTES + PWF_BYTES);      // [block A | block B][2][5][64]
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int G = gridDim.x;
-    const int first = xcd_remap(blockIdx.x, G);
-    const int kb = lane >> 4, m16 = lane & 15;
-    const int dsel = dw_mma_dword_index(lane);
-    RF_TRACE_KEY(a.nblk);
-
-    // ---- once per workgroup: weights.  Pointwise A fragments in the chained K order: halves 0-3 = channels 4 kb .. of group 0, 4-7 = of group 1
-    for (int i = tid; i < 2 * kDwMmaChunks * 64; i += kThreads) { s_dwb[i] = a.dwa_mma[i]; s_dwb[2 * kDwMmaChunks * 64 + i] = a.dwb_mma[i]; }
-    auto chained_frag = [&](const half_t *packed, int ct) -> Frag {
-        const uint2 *w8 = (const uint2 *)packed;
-        const uint2 lo = w8[((ct * 64) + (kb >> 1) * 16 + m16) * 2 + (kb & 1)];
-        const uint2 hi = w8[((ct * 64) + (2 + (kb >> 1)) * 16 + m16) * 2 + (kb & 1)];
-        const uint4 u = {lo.x, lo.y, hi.x, hi.y};
-        return __builtin_bit_cast(Frag, u);
-    };
-    const int cp = wave >> 1;                                          // phase B: this wave's pair of output-channel tiles
-    if (wave < 2) s_pwf[wave * 64 + lane] = chained_frag(a.pwa_w, wave);
-    s_pwf[(2 + wave) * 64 + lane] = chained_frag(a.pwb_w, wave);
-    if (tid < 160) {
-        const int v = tid >> 4, c = tid & 15;
-        s_bias[tid] = v < 2 ? a.dwa_b[v * 16 + c] : v < 4 ? a.pwa_b[(v - 2) * 16 + c] : v < 6 ? a.dwb_b[(v - 4) * 16 + c] : a.pwb_b[(v - 6) * 16 + c];
-    }
-    auto bias_of = [&](int v) -> f32x4 { return *(const f32x4 *)(s_bias + v * 16 + kb * 4); };       // (first read after the loop's first barrier)
-    auto dw_frag = [&](uint32_t wd) -> Frag {          // diagonal depthwise A fragment from its one dword per lane
-        typedef uint32_t u32x4_ __attribute__((ext_vector_type(4)));
-        asm volatile("" : "+v"(wd));
-        u32x4_ wa;
-#pragma unroll
-        for (int d = 0; d < 4; d++) wa[d] = dsel == d ? wd : 0u;
-        return __builtin_bit_cast(Frag, wa);
-    };
-    auto chain = [&](const M::Acc &g0, const M::Acc &g1) -> Frag {     // two ReLU'd fp16 accumulator tiles = the next GEMM's B fragment
-        const uint4 u = {pack_f16(g0[0], g0[1], true), pack_f16(g0[2], g0[3], true), pack_f16(g1[0], g1[1], true), pack_f16(g1[2], g1[3], true)};
-        return __builtin_bit_cast(Frag, u);
-    };
-    // per-lane constants of the wave's phase-A pixel tiles
-    int pa_base[UA], pa_yx[UA];                                        // pa_yx: (ry << 16 | rx), ry poisoned for tail lanes (p >= NR)
-#pragma unroll
-    for (int i = 0; i < UA; i++) {
-        const int p = (wave + 4 * i) * 16 + m16;
-        const int pc = p < NR ? p : NR - 1;
-        const int ry = pc / RW, rx = pc % RW;
-        pa_yx[i] = ((p < NR ? ry : 0x4000) << 16) | rx;
-        pa_base[i] = ry * HROW + rx * LD + (kb & 1) * 8;
-    }
-    const bool hi = lane >= 32;                                        // chunk kc carries tap 2 kc (lanes 0..31) and 2 kc + 1 (lanes 32..63)
-    auto tap_a = [&](int kc) -> int { const int t0 = 2 * kc, t1 = 2 * kc + 1; return hi ? (t1 < 9 ? (t1 / 3) * HROW + (t1 % 3) * LD : -1) : (t0 / 3) * HROW + (t0 % 3) * LD; };
-    auto tap_b = [&](int kc) -> int { const int t0 = 2 * kc, t1 = 2 * kc + 1; return hi ? (t1 < 9 ? (t1 / 3) * MROW + (t1 % 3) * LDM : -1) : (t0 / 3) * MROW + (t0 % 3) * LDM; };
-    const int pb = (wave & 1) * 16 + m16;                              // phase B: the lane's output pixel
-    const int pb_base = ((pb / TW) * 2) * MROW + ((pb % TW) * 2) * LDM + (kb & 1) * 8;
-    const int pb_out = pb * LDO + kb * 4;
-
-    // halo of a tile -> registers (unconditional buffer loads; rows / columns outside the map read as zero = depthwise A's padding)
-    V pre[NPF];
-    int kdx[NPF];                                                      // halo column | halo row << 5 | LDS offset of the item (halfs) << 9
-#pragma unroll
-    for (int k = 0; k < NPF; k++) {
-        int i = tid + k * kThreads;
-        i = i < NH * 4 ? i : NH * 4 - 1;
-        const int pix = i >> 2, cv = i & 3;
-        kdx[k] = (pix % HW) | ((pix / HW) << 5) | (((pix / HW) * HROW + (pix % HW) * LD + cv * 8) << 9);
-    }
-    const int cv16 = (tid & 3) * 16;                                   // the item's 16-byte channel chunk (kThreads is a multiple of 4)
-    const unsigned in_img_bytes = (unsigned)(a.hin * a.win * CI) * 2u;
-    auto fetch = [&](int tx, int ty, int img) {
-        const auto rs = image_rsrc(a.in + (size_t)img * a.hin * a.win * CI, in_img_bytes);
-        const int iy0 = 2 * ty * TH - 2, ix0 = 2 * tx * TW - 2;
-        const int sbase = (iy0 * a.win + ix0) * CI * 2 + cv16;
-        const int rowb = a.win * CI * 2;
-#pragma unroll
-        for (int k = 0; k < NPF; k++) {
-            const int col = kdx[k] & 31, row = (kdx[k] >> 5) & 15;
-            const unsigned off = (unsigned)(ix0 + col) < (unsigned)a.win ? (unsigned)(row * rowb + col * (CI * 2) + sbase) : kOobOffset;
-            pre[k] = buf_load16<V>(rs, off);
-        }
-    };
-    const TileStep step(G, a.tiles_x, a.tiles_y);
-    TileCoord cur(first, a.tiles_x, a.tiles_y), nxt = cur;
-    step.advance(nxt);
-    if (first < a.nblk) fetch(cur.tx, cur.ty, cur.img);
-    __builtin_amdgcn_s_waitcnt(0x0F70);       // vmcnt(0): the once-per-workgroup loads have landed; in the loop only the prefetch is in flight
-
-    for (int t = first; t < a.nblk; t += G) {
-        const int oy0 = cur.ty * TH, ox0 = cur.tx * TW, img = cur.img;
-        // ---- phase 1: prefetched halo -> LDS, next tile's halo requested
-#pragma unroll
-        for (int k = 0; k < NPF; k++) {
-            const int i = tid + k * kThreads;
-            if (i < NH * 4) *(V *)(s_in + (kdx[k] >> 9)) = pre[k];
-        }
-        if (t + G < a.nblk) fetch(nxt.tx, nxt.ty, nxt.img);
-        cur = nxt;
-        step.advance(nxt);
-        __syncthreads();
-
-        // ---- phase A: depthwise A (both channel groups) -> registers -> pointwise A (both channel tiles) -> block-A tile, zero outside the map
-        {
-            M::Acc acc[UA][2];
-            {
-                const f32x4 b0 = bias_of(0), b1 = bias_of(1);
-#pragma unroll
-                for (int i = 0; i < UA; i++) { acc[i][0] = b0; acc[i][1] = b1; }
-            }
-            // one chunk's six B fragments ahead of the MFMAs, pinned: left alone the scheduler hoists all five chunks' reads (120 registers) and spills
-            Frag bf[2][UA][2];
-            uint32_t dwd[2][2];
-            auto load_chunk = [&](int kc, Frag (&b)[UA][2], uint32_t (&d)[2]) {
-#pragma unroll
-                for (int i = 0; i < UA; i++)
-#pragma unroll
-                    for (int g = 0; g < 2; g++) b[i][g] = tap_a(kc) >= 0 ? *(const Frag *)(s_in + pa_base[i] + tap_a(kc) + g * 16) : M::zero();
-                d[0] = s_dwb[kc * 64 + lane]; d[1] = s_dwb[(kDwMmaChunks + kc) * 64 + lane];
-            };
-            load_chunk(0, bf[0], dwd[0]);
-#pragma unroll
-            for (int kc = 0; kc < kDwMmaChunks; kc++) {
-                if (kc + 1 < kDwMmaChunks) load_chunk(kc + 1, bf[(kc + 1) & 1], dwd[(kc + 1) & 1]);
-                __builtin_amdgcn_sched_barrier(0);
-                const Frag af0 = dw_frag(dwd[kc & 1][0]), af1 = dw_frag(dwd[kc & 1][1]);
-#pragma unroll
-                for (int i = 0; i < UA; i++) {
-                    acc[i][0] = M::mma(af0, bf[kc & 1][i][0], acc[i][0]);
-                    acc[i][1] = M::mma(af1, bf[kc & 1][i][1], acc[i][1]);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            const Frag pwa[2] = {s_pwf[lane], s_pwf[64 + lane]};
-            const f32x4 pwa_b[2] = {bias_of(2), bias_of(3)};
-#pragma unroll
-            for (int i = 0; i < UA; i++) {                 // (pixel tiles 10 and 11 of waves 2 and 3 do not exist: computed on the last pixel, never stored)
-                {
-                    const Frag x = chain(acc[i][0], acc[i][1]);
-                    const int ry = pa_yx[i] >> 16, rx = pa_yx[i] & 0xffff;
-                    const int y = 2 * oy0 - 1 + ry, xx = 2 * ox0 - 1 + rx;
-                    T *const dst = s_mid + ry * MROW + rx * LDM + kb * 4;
-                    const bool inside = (unsigned)y < (unsigned)a.hin && (unsigned)xx < (unsigned)a.win;
-#pragma unroll
-                    for (int ct = 0; ct < 2; ct++) {
-                        const M::Acc o = M::mma(pwa[ct], x, pwa_b[ct]);
-                        uint2 h;
-                        h.x = inside ? pack_f16(o[0], o[1], true) : 0u;
-                        h.y = inside ? pack_f16(o[2], o[3], true) : 0u;
-                        if (ry < 0x4000) *(uint2 *)(dst + ct * 16) = h;      // (tail lanes of the last tile own no pixel)
-                    }
-                }
-            }
-        }
-        __syncthreads();
-
-        // ---- phase B: depthwise B (stride 2, both groups) -> registers -> pointwise B (this wave's two channel tiles) -> output tile
-        {
-            M::Acc d0 = bias_of(4), d1 = bias_of(5);
-            uint32_t dwb[2][kDwMmaChunks];
-#pragma unroll
-            for (int g = 0; g < 2; g++)
-#pragma unroll
-                for (int kc = 0; kc < kDwMmaChunks; kc++) dwb[g][kc] = s_dwb[((2 + g) * kDwMmaChunks + kc) * 64 + lane];
-            const Frag pwb[2] = {s_pwf[(2 + 2 * cp) * 64 + lane], s_pwf[(3 + 2 * cp) * 64 + lane]};
-            const f32x4 pwb_b[2] = {bias_of(6 + 2 * cp), bias_of(7 + 2 * cp)};
-            Frag bf[kDwMmaChunks][2];
-#pragma unroll
-            for (int kc = 0; kc < kDwMmaChunks; kc++)
-#pragma unroll
-                for (int g = 0; g < 2; g++) bf[kc][g] = tap_b(kc) >= 0 ? *(const Frag *)(s_mid + pb_base + tap_b(kc) + g * 16) : M::zero();
-#pragma unroll
-            for (int kc = 0; kc < kDwMmaChunks; kc++) {
-                d0 = M::mma(dw_frag(dwb[0][kc]), bf[kc][0], d0);
-                d1 = M::mma(dw_frag(dwb[1][kc]), bf[kc][1], d1);
-            }
-            const Frag x = chain(d0, d1);
-#pragma unroll
-            for (int j = 0; j < 2; j++) {
-                const M::Acc o = M::mma(pwb[j], x, pwb_b[j]);
-                uint2 h;
-                h.x = pack_f16(o[0], o[1], true);
-                h.y = pack_f16(o[2], o[3], true);
-                *(uint2 *)(s_out + pb_out + (2 * cp + j) * 16) = h;
-            }
-        }
-        __syncthreads();
-
-        // ---- store: 32 px x 64 ch tile -> HBM, one 16-byte item per thread (s_out is next written after two more barriers)
-        {
-            const auto ro = image_rsrc(a.out + (size_t)img * a.hout * a.wout * CB, (unsigned)(a.hout * a.wout * CB) * 2u);
-            const int p = tid >> 3, cv = tid & 7;
-            const int py = p / TW, px = p % TW;
-            const unsigned off = ox0 + px < a.wout ? (unsigned)((((oy0 + py) * a.wout + ox0 + px) * CB + cv * 8) * 2) : kOobOffset;
-            buf_store16(ro, off, *(const V *)(s_out + p * LDO + cv * 8));
-        }
-    }
-}
-#endif  // RF_PROBES
 
 void launch_dwpw2(hipStream_t s, const DwPw2Params &p) {
     DwPw2Args a;
@@ -3224,44 +2344,10 @@ void launch_dwpw2(hipStream_t s, const DwPw2Params &p) {
     a.hin = p.hin; a.win = p.win; a.hout = p.hin / 2; a.wout = p.win / 2;
     a.tiles_x = (a.wout + 7) / 8; a.tiles_y = (a.hout + 3) / 4;
     a.nblk = p.n * a.tiles_x * a.tiles_y;
-    a.ring = 0;
-#ifdef RF_PROBES
-    // probe knobs (each measured and rejected): RF_DWPW2_RING=1: depthwise A as one ring pipeline (107 -> 232 us: 8 registers more than the
-    // 168-VGPR budget of 3 workgroups per CU, spills); RF_DWPW2_CHAIN=1: K_b2c, the register-chained form (LDS cycles halved, 110.8 vs 100.5 us: longer serial
-    // chains); RF_DWPW2_HPAD=0: unpadded halo rows (round 3); RF_DWPW2_LAY2=0: 96-byte pitches everywhere (round 3)
-    const int ring = knob(K_DWPW2_RING);
-    a.ring = ring;
-    if (knob(K_DWPW2_CHAIN) && !ring) {
-        static std::atomic<int> resident_cachec[kMaxDevices] = {};
-        const int resident = kernel_residency(resident_cachec, dwpw2c_kernel, 0);
-        hipLaunchKernelGGL(dwpw2c_kernel, dim3(persistent_grid(a.nblk, resident)), dim3(kThreads), 0, s, a);
-        return;
-    }
-    if (ring) {
-        static std::atomic<int> resident_cacher[kMaxDevices] = {};
-        const int resident = kernel_residency(resident_cacher, dwpw2_kernel<true, true, false>, 0);
-        hipLaunchKernelGGL((dwpw2_kernel<true, true, false>), dim3(persistent_grid(a.nblk, resident)), dim3(kThreads), 0, s, a);
-        return;
-    }
-    if (!knob(K_DWPW2_HPAD)) {
-        static std::atomic<int> resident_cache1[kMaxDevices] = {};
-        const int resident = kernel_residency(resident_cache1, dwpw2_kernel<false, false, false>, 0);
-        hipLaunchKernelGGL((dwpw2_kernel<false, false, false>), dim3(persistent_grid(a.nblk, resident)), dim3(kThreads), 0, s, a);
-        return;
-    }
-    if (!knob(K_DWPW2_LAY2)) {
-        static std::atomic<int> resident_cache2[kMaxDevices] = {};
-        const int resident = kernel_residency(resident_cache2, dwpw2_kernel<false, true, false>, 0);
-        hipLaunchKernelGGL((dwpw2_kernel<false, true, false>), dim3(persistent_grid(a.nblk, resident)), dim3(kThreads), 0, s, a);
-        return;
-    }
-#endif
-    static std::atomic<int> resident_cache0[kMaxDevices] = {};
-    const int resident = kernel_residency(resident_cache0, dwpw2_kernel<false, true, true>, 0);
-    hipLaunchKernelGGL((dwpw2_kernel<false, true, true>), dim3(persistent_grid(a.nblk, resident)), dim3(kThreads), 0, s, a);
+    static std::atomic<int> resident_cache[kMaxDevices] = {};
+    const int resident = kernel_residency(resident_cache, dwpw2_kernel, 0);
+    hipLaunchKernelGGL(dwpw2_kernel, dim3(persistent_grid(a.nblk, resident)), dim3(kThreads), 0, s, a);
 }
-
-int dwpw2_variant() { return knob(K_DWPW2); }      // probe knob RF_DWPW2: 0 = two separate K_b launches
 
 // Input of the FPN aggregation convs: lateral + bilinear x2 upsample of the coarser level (Deconvolution k4 s2 p1 g64 + Crop + Eltwise SUM,
 // prototxt :1553-1592 / :1948-1987, closed form SURVEY.md App. B.6), one 16-byte item: `lat` = the lateral's channels, u0..u3 = the four
@@ -3359,7 +2445,7 @@ __device__ __forceinline__ typename Vec<T>::type upadd_blend(typename Vec<T>::ty
 //   One launch can cover up to 3 FPN levels (same conv shape, different maps / weights): the SSH module of
 //   strides 32, 16 and 8 is 3 launches, not 9.
 // =============================================================================================
-template <typename T, int CIN, int COUT, int TH, int TW, bool ALLC = false, bool PADROW = false> struct Conv3Cfg {
+template <typename T, int CIN, int COUT, int TH, int TW, bool PADROW = false> struct Conv3Cfg {
     typedef Mma<T> M;
     static constexpr int VEC = Vec<T>::N;
     static constexpr int P = TH * TW;
@@ -3384,23 +2470,18 @@ template <typename T, int CIN, int COUT, int TH, int TW, bool ALLC = false, bool
     static constexpr int NT = COUT / 16, PT = P / 16;
     static constexpr int KTOT = 9 * CIN;
     static constexpr int KCH = (KTOT + M::K - 1) / M::K;
-    // Wave split.  ALLC ("all channels"): every wave owns ALL output-channel tiles of its own pixel tiles, the whole weight
-    // matrix stationary in its registers (64 -> 64: 4 x 18 A fragments = 288 VGPRs, one workgroup per CU).  A B fragment is then
-    // read from LDS ONCE per workgroup and feeds NT MFMAs; with the channel tiles split over the waves instead (the round-1
-    // layout, kept for the fp32 parity engine) every wave re-read every pixel's fragments: one 1 KB ds_read_b128 per MFMA, which
-    // made these kernels LDS-bound at 9-25 % of the MFMA rate (SQ counters, profiles/r01_pmc_sq_n128_448_fp16.json).
-    // !ALLC: output-channel tiles first; 3 channel tiles (the merged 64->48 SSH conv) run on 3 of the 4 waves.
-    static constexpr bool ODD = !ALLC && NT == 3;
-    typedef WaveSplit<(ODD || ALLC) ? 4 : NT, PT> WS;
-    static constexpr int WN = ALLC ? 1 : (ODD ? 3 : WS::WN), WP = ALLC ? 4 : (ODD ? 1 : WS::WP);
-    static constexpr int NI = ALLC ? NT : (ODD ? 1 : WS::NI), NJ = ALLC ? PT / 4 : (ODD ? PT : WS::NJ);
-    static_assert(!ALLC || (PT % 4 == 0 && PT >= 4), "ALLC needs the pixel tiles to split over 4 waves");
-    static constexpr int WREGS = NI * KCH * 4;                              // VGPRs of stationary weights per lane
-    static constexpr bool STAT = sizeof(T) <= 2 && (ALLC ? WREGS <= 300 : NI * KCH <= 18);
+    // Wave split (the round-1 layout): output-channel tiles first; 3 channel tiles (the merged 64->48 SSH conv) run on 3 of the 4 waves.
+    // (Every wave owning ALL output-channel tiles of its own pixel tiles reads each B fragment once per workgroup, but holds the whole weight
+    // matrix in 288 VGPRs = one workgroup per CU: measured slower and removed, docs/HISTORY.md.)
+    static constexpr bool ODD = NT == 3;
+    typedef WaveSplit<ODD ? 4 : NT, PT> WS;
+    static constexpr int WN = ODD ? 3 : WS::WN, WP = ODD ? 1 : WS::WP;
+    static constexpr int NI = ODD ? 1 : WS::NI, NJ = ODD ? PT : WS::NJ;
+    static constexpr bool STAT = sizeof(T) <= 2 && NI * KCH <= 18;                 // weights stationary in registers
     static constexpr int STAGE_ITEMS = HR * HC * (CIN / VEC);
     static constexpr int NPF = (STAGE_ITEMS + kThreads - 1) / kThreads;
     // register budget -> workgroups per CU (512 / 256 / 168 / 128 / 96 VGPRs per lane at 1 / 2 / 3 / 4 / 5)
-    static constexpr int OCC = sizeof(T) > 2 ? 1 : ALLC ? (WREGS > 160 ? 1 : WREGS > 64 ? 2 : 5) : (CIN >= 64 ? 3 : 5);
+    static constexpr int OCC = sizeof(T) > 2 ? 1 : (CIN >= 64 ? 3 : 5);
     static constexpr int GFRAGS = 12;                                      // streamed case only
 };
 
@@ -3418,9 +2499,9 @@ struct Conv3Args {
     Conv3Level<T> lv[3];
 };
 
-template <typename T, int CIN, int COUT, int TH, int TW, bool UPADD, bool ALLC, bool PADROW>
-__global__ __launch_bounds__(kThreads, (Conv3Cfg<T, CIN, COUT, TH, TW, ALLC, PADROW>::OCC)) void conv3x3_kernel(Conv3Args<T> a) {
-    typedef Conv3Cfg<T, CIN, COUT, TH, TW, ALLC, PADROW> C;
+template <typename T, int CIN, int COUT, int TH, int TW, bool UPADD, bool PADROW>
+__global__ __launch_bounds__(kThreads, (Conv3Cfg<T, CIN, COUT, TH, TW, PADROW>::OCC)) void conv3x3_kernel(Conv3Args<T> a) {
+    typedef Conv3Cfg<T, CIN, COUT, TH, TW, PADROW> C;
     typedef typename Vec<T>::type V;
     typedef Mma<T> M;
     typedef typename M::Frag Frag;
@@ -3446,7 +2527,7 @@ __global__ __launch_bounds__(kThreads, (Conv3Cfg<T, CIN, COUT, TH, TW, ALLC, PAD
     RF_TRACE(3, 0);
 
     // ---- once per workgroup: this wave's weight share and biases
-    const int wn = C::ODD ? wave : wave % WN, wp = C::ODD ? 0 : wave / WN;      // ALLC: wn = 0, wp = wave
+    const int wn = C::ODD ? wave : wave % WN, wp = C::ODD ? 0 : wave / WN;
     const bool gemm_wave = !C::ODD || wave < 3;
     const int wnc = gemm_wave ? wn : 0;            // the idle wave reads tile 0's constants and never uses them
     Frag wst[STAT ? NI : 1][STAT ? KCH : 1];
@@ -3634,8 +2715,8 @@ __global__ __launch_bounds__(kThreads, (Conv3Cfg<T, CIN, COUT, TH, TW, ALLC, PAD
 //   16 B), so the padded layout of K_c (pixel pitch 32 mod 64 bytes, row pitch a multiple of 256 bytes: conflict-free B fragments)
 //   is kept by giving the pad chunks slots of their own that load nothing.
 // =============================================================================================
-template <typename T, int NBUF> struct Conv3WsCfg {
-    typedef Conv3Cfg<T, 64, 48, 8, 8, false, true> B;                  // tile geometry, LDS pitches, wave split (ODD: 3 GEMM waves)
+template <typename T> struct Conv3WsCfg {
+    typedef Conv3Cfg<T, 64, 48, 8, 8, true> B;                  // tile geometry, LDS pitches, wave split (ODD: 3 GEMM waves)
     static constexpr int VEC = B::VEC;
     static constexpr int CPP = B::LDI / VEC;                           // 16-byte chunks per halo pixel, padding included
     static constexpr int CPR = B::ROWP / VEC;                          // chunks per halo row, padding included
@@ -3645,15 +2726,16 @@ template <typename T, int NBUF> struct Conv3WsCfg {
     static constexpr int NSTORE = B::P * (48 / VEC) / 64;              // store wave-instructions per result tile (producer wave)
     static constexpr size_t IN_BYTES = (size_t)PIECES * 1024;          // whole KiB: the last piece may overhang the image
     static constexpr size_t O_BYTES = B::O_BYTES;
-    static constexpr size_t LDS_BYTES = NBUF * IN_BYTES + 2 * O_BYTES; // NBUF halo tiles (prefetch distance NBUF - 1), result tile double buffered
+    static constexpr int NBUF = 3;                                     // halo tiles in LDS: prefetch distance NBUF - 1 (see conv3_ws_launch)
+    static constexpr size_t LDS_BYTES = NBUF * IN_BYTES + 2 * O_BYTES; // NBUF halo tiles, result tile double buffered
     static_assert(B::LDI % VEC == 0 && B::ROWP % VEC == 0 && B::ODD && B::STAT, "layout assumptions of the warp-specialised conv");
-    static_assert(IN_BYTES >= B::IN_BYTES && O_BYTES % 16 == 0 && (NBUF == 2 || NBUF == 3), "LDS carve");
+    static_assert(IN_BYTES >= B::IN_BYTES && O_BYTES % 16 == 0, "LDS carve");
     static_assert(NSTORE + PIECES < 64, "counted vmcnt");
 };
 
-template <typename T, int DEPTH, int NBUF, int SPLIT = 0>
-__global__ __launch_bounds__(kThreads, (SPLIT ? 2 : (NBUF == 2 || sizeof(T) == 1 ? 3 : 2))) void conv3x3_ws_kernel(Conv3Args<T> a) {
-    typedef Conv3WsCfg<T, NBUF> W;
+template <typename T>
+__global__ __launch_bounds__(kThreads, 2) void conv3x3_ws_kernel(Conv3Args<T> a) {
+    typedef Conv3WsCfg<T> W;
     typedef typename W::B C;
     typedef typename Vec<T>::type V;
     typedef Mma<T> M;
@@ -3661,7 +2743,8 @@ __global__ __launch_bounds__(kThreads, (SPLIT ? 2 : (NBUF == 2 || sizeof(T) == 1
     constexpr int CIN = 64, COUT = 48, TH = 8, TW = 8;
     constexpr int VEC = C::VEC, P = C::P, HC = C::HC, LDI = C::LDI, LDO = C::LDO, ROWP = C::ROWP;
     constexpr int KTOT = C::KTOT, KCH = C::KCH, NJ = C::NJ;
-    constexpr int DIST = NBUF - 1;                                     // the producer runs DIST tiles ahead of the consumers
+    constexpr int NBUF = W::NBUF, DIST = NBUF - 1;                     // the producer runs DIST = 2 tiles ahead of the consumers
+    constexpr int DEPTH = 2;                                           // B-fragment prefetch depth of the single-channel-tile consumer
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int IN_ELEMS = (int)(W::IN_BYTES / sizeof(T)), O_ELEMS = (int)(W::O_BYTES / sizeof(T));
     T *s_in = (T *)smem;                                               // [NBUF][IN_ELEMS]
@@ -3732,7 +2815,7 @@ __global__ __launch_bounds__(kThreads, (SPLIT ? 2 : (NBUF == 2 || sizeof(T) == 1
 #pragma unroll
         for (int d = 0; d < DIST; d++)
             if (d < n_my) { dma(pf.tx, pf.ty, pf.img, s_in + d * IN_ELEMS); step.advance(pf); }
-        if (DIST == 2 && n_my >= 2) wait_vmcnt<W::PIECES>();
+        if (n_my >= 2) wait_vmcnt<W::PIECES>();
         else wait_vmcnt<0>();
         lds_barrier();
         int p_img = 0, p_oy0 = 0, p_ox0 = 0;
@@ -3742,18 +2825,17 @@ __global__ __launch_bounds__(kThreads, (SPLIT ? 2 : (NBUF == 2 || sizeof(T) == 1
             if (ld) { dma(pf.tx, pf.ty, pf.img, s_in + ((k + DIST) % NBUF) * IN_ELEMS); step.advance(pf); }
             p_img = cur.img; p_oy0 = cur.ty * TH; p_ox0 = cur.tx * TW;
             step.advance(cur);
-            // tile k + 1 must have landed before the barrier.  DIST == 1: it is the request just made.  DIST == 2: it was requested one
-            // interval ago; everything issued in THIS interval (NSTORE stores, PIECES loads) may stay in flight (the counter is in order)
-            if (DIST == 1) wait_vmcnt<0>();
-            else if (st && ld) wait_vmcnt<W::NSTORE + W::PIECES>();
+            // tile k + 1 must have landed before the barrier: it was requested one interval ago; everything issued in THIS interval
+            // (NSTORE stores, PIECES loads) may stay in flight (the counter is in order)
+            if (st && ld) wait_vmcnt<W::NSTORE + W::PIECES>();
             else if (ld) wait_vmcnt<W::PIECES>();
             else if (st) wait_vmcnt<W::NSTORE>();
             else wait_vmcnt<0>();
             lds_barrier();
         }
         if (n_my > 0) store_tile(s_out + ((n_my - 1) & 1) * O_ELEMS, p_img, p_oy0, p_ox0, lane, 64);
-    } else if (SPLIT && wave < 2) {
-        // ================================================= consumers 0 / 1 (SPLIT): output-channel tiles 0 and 1, pixel tiles 2 wave, 2 wave + 1.
+    } else if (wave < 2) {
+        // ================================================= consumers 0 / 1: output-channel tiles 0 and 1, pixel tiles 2 wave, 2 wave + 1.
         // With the plain split (wave = channel tile) every B fragment is read from LDS by all three GEMM waves: 216 KB per tile for
         // 72 MFMAs each, and LDS bandwidth is as loaded as the matrix pipe.  Here channels [0, 32) belong to two waves that split the
         // PIXELS (each reads half of the fragments, uses each twice) and channels [32, 48) to the third: 144 KB, the same 72 MFMAs each.
@@ -3784,7 +2866,7 @@ __global__ __launch_bounds__(kThreads, (SPLIT ? 2 : (NBUF == 2 || sizeof(T) == 1
             for (int i = 0; i < 2; i++)
 #pragma unroll
                 for (int j = 0; j < 2; j++) acc[i][j] = acc_init<T>(bias[i]);
-            gemm_stationary<T, 2, 2, KCH, (DEPTH > 2 ? DEPTH : 3), true>(acc, wst, [&](int j, int kc) -> Frag {
+            gemm_stationary<T, 2, 2, KCH, 3, true>(acc, wst, [&](int j, int kc) -> Frag {
                 const int kb = kc * M::K + (lane >> 4) * M::KPL;
                 const int tap = kb / CIN, c = kb % CIN;
                 const int koff = (tap / 3) * ROWP + (tap % 3) * LDI + c;
@@ -3797,7 +2879,7 @@ __global__ __launch_bounds__(kThreads, (SPLIT ? 2 : (NBUF == 2 || sizeof(T) == 1
             lds_barrier();
         }
     } else {
-        // ================================================= consumers: wave = output-channel tile (SPLIT: only wave 2 = tile 2), all pixel tiles
+        // ================================================= consumer 2: output-channel tile 2, all pixel tiles
         const int wn = wave;
         Frag wst[1][KCH];
         {
@@ -3843,8 +2925,8 @@ __global__ __launch_bounds__(kThreads, (SPLIT ? 2 : (NBUF == 2 || sizeof(T) == 1
 //   place (same arithmetic: upadd_blend), barrier, multiply (8 x 8 tiles: 72 MFMAs per wave and tile, pinned B-fragment pipeline), write
 //   the result over the coarse patch's space, barrier.  One LDS ring of NBUF x [halo | coarse patch / result tile].
 // =============================================================================================
-template <typename T, int NBUF> struct Conv3UpWsCfg {
-    typedef Conv3Cfg<T, 64, 64, 8, 8, false, true> B;                  // 8 x 8 tile geometry and LDS pitches of the halo; wave = channel tile
+template <typename T> struct Conv3UpWsCfg {
+    typedef Conv3Cfg<T, 64, 64, 8, 8, true> B;                  // 8 x 8 tile geometry and LDS pitches of the halo; wave = channel tile
     static constexpr int VEC = B::VEC, P = B::P;
     static constexpr int CPP = B::LDI / VEC, CPR = B::ROWP / VEC, DPP = 64 / VEC;
     static constexpr int SLOTS = B::HR * CPR, PIECES = (SLOTS + 63) / 64;
@@ -3856,211 +2938,13 @@ template <typename T, int NBUF> struct Conv3UpWsCfg {
     static constexpr size_t C_BYTES = (size_t)CSLOTS * 16, O_BYTES = sizeof(T) * (size_t)(P * LDO);
     static constexpr size_t X_BYTES = C_BYTES > O_BYTES ? C_BYTES : O_BYTES;       // coarse patch, then (after the blend) the result tile
     static constexpr size_t BUF_BYTES = L_BYTES + X_BYTES;
+    static constexpr int NBUF = 2;                                     // ring buffers: the next tile is fetched one interval ahead
     static constexpr size_t LDS_BYTES = NBUF * BUF_BYTES;
-    static constexpr int THREADS = 320;
-    static constexpr int WG_CAP = sizeof(T) == 2 ? 2 : 3;              // fp16: 18 stationary A fragments + the blend's operands need ~165 VGPRs
-    static constexpr int WG_PER_CU = (int)(160 * 1024 / LDS_BYTES) > WG_CAP ? WG_CAP : (int)(160 * 1024 / LDS_BYTES);
-    static constexpr int WAVES_PER_EU = (WG_PER_CU * 5 + 3) / 4;
     static constexpr int NBL = (B::HR * B::HC * DPP + 255) / 256;      // blend items per consumer thread
     static_assert(B::NI == 1 && B::NJ == 4 && B::WN == 4 && B::STAT && !B::ODD, "wave = output-channel tile, all four pixel tiles");
     static_assert(L_BYTES % 16 == 0 && X_BYTES % 16 == 0 && CSLOTS % 64 == 0 && PIECES + CPIECES + NSTORE < 63, "LDS carve / counted vmcnt");
 };
 
-#ifdef RF_PROBES      // producer-wave form: measured and rejected (c1 78 -> 110 us), probe build only
-template <typename T, int DEPTH, int NBUF>
-__global__ __launch_bounds__(320, (Conv3UpWsCfg<T, NBUF>::WAVES_PER_EU)) void conv3x3_up_ws_kernel(Conv3Args<T> a) {
-    typedef Conv3UpWsCfg<T, NBUF> W;
-    typedef typename W::B C;
-    typedef typename Vec<T>::type V;
-    typedef Mma<T> M;
-    typedef typename M::Frag Frag;
-    constexpr int CIN = 64, TH = 8, TW = 8;
-    constexpr int VEC = C::VEC, P = C::P, HC = C::HC, HR = C::HR, LDI = C::LDI, ROWP = C::ROWP, LDO = W::LDO;
-    constexpr int KTOT = C::KTOT, KCH = C::KCH, NJ = C::NJ, DPP = W::DPP, CW = W::CW;
-    constexpr int DIST = NBUF - 1;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const Conv3Level<T> &L = a.lv[0];                                  // one level per launch (the aggregation convs are separate layers)
-    const int G = gridDim.x;
-    const int first = xcd_remap(blockIdx.x, G), ntiles = L.ntiles;
-    const int lh = L.h, lw = L.w_, hh = lh >> 1, wh = lw >> 1;
-    const int n_my = first < ntiles ? (ntiles - 1 - first) / G + 1 : 0;
-    const TileStep step(G, L.tiles_x, L.tiles_y);
-    auto halo_of = [&](int b) -> T * { return (T *)(smem + (size_t)b * W::BUF_BYTES); };
-    auto aux_of = [&](int b) -> T * { return (T *)(smem + (size_t)b * W::BUF_BYTES + W::L_BYTES); };
-
-    if (wave == 4) {
-        // ================================================= producer
-        int kl[W::PIECES], kc[W::CPIECES];                             // byte offset inside the image | column << 26 (63 = not a pixel)
-        const int in_ld = L.in_ld;
-#pragma unroll
-        for (int i = 0; i < W::PIECES; i++) {
-            const int s = i * 64 + lane;
-            const int row = s / W::CPR, rem = s % W::CPR;
-            const int px = rem / W::CPP, ch = rem % W::CPP;
-            const bool real = row < HR && px < HC && ch < DPP;
-            kl[i] = real ? ((((row * lw + px) * in_ld + ch * VEC) * (int)sizeof(T)) | (px << 26)) : (int)(63u << 26);
-        }
-#pragma unroll
-        for (int i = 0; i < W::CPIECES; i++) {
-            const int s = i * 64 + lane;
-            const int cpix = s / DPP, ch = s % DPP;
-            const int cy = cpix / CW, cx = cpix % CW;
-            kc[i] = (((cy * wh + cx) * CIN + ch * VEC) * (int)sizeof(T)) | (cx << 26);
-        }
-        const unsigned lat_bytes = (unsigned)(lh * lw * in_ld - L.in_off) * (unsigned)sizeof(T);
-        const unsigned up_bytes = (unsigned)(hh * wh * CIN) * (unsigned)sizeof(T);
-        const T *in = L.in + L.in_off;
-        auto dma = [&](int tx, int ty, int img, int b) {
-            const auto rs = image_rsrc(in + (size_t)img * lh * lw * in_ld, lat_bytes);
-            const auto ru = image_rsrc(L.up + (size_t)img * hh * wh * CIN, up_bytes);
-            const int iy0 = ty * TH - 1, ix0 = tx * TW - 1;
-            const int sbase = (iy0 * lw + ix0) * in_ld * (int)sizeof(T);
-            unsigned char *hd = (unsigned char *)halo_of(b), *cd = (unsigned char *)aux_of(b);
-#pragma unroll
-            for (int i = 0; i < W::PIECES; i++) {
-                const int dx = (int)((unsigned)kl[i] >> 26);
-                const unsigned off = (dx != 63 && (unsigned)(ix0 + dx) < (unsigned)lw) ? (unsigned)((kl[i] & 0x03ffffff) + sbase) : kOobOffset;
-                if (i * 64 + lane < W::SLOTS) lds_dma16(rs, hd + i * 1024, off);        // (only the last piece is partial)
-            }
-            const int cy0 = ty * (TH / 2) - 2, cx0 = tx * (TW / 2) - 2;
-            const int cbase = (cy0 * wh + cx0) * CIN * (int)sizeof(T);
-#pragma unroll
-            for (int i = 0; i < W::CPIECES; i++) {
-                const int cx = (int)((unsigned)kc[i] >> 26);
-                const unsigned off = (unsigned)(cx0 + cx) < (unsigned)wh ? (unsigned)((kc[i] & 0x03ffffff) + cbase) : kOobOffset;
-                lds_dma16(ru, cd + i * 1024, off);
-            }
-        };
-        T *out0 = L.out0;
-        const int ld0 = L.ld0, off0 = L.off0;
-        auto store_tile = [&](int b, int img, int oy0, int ox0) {
-            constexpr int OPV = 64 / VEC;
-            const T *s_res = aux_of(b);
-            const auto r0 = image_rsrc(out0 + (size_t)img * lh * lw * ld0 + off0, (unsigned)(lh * lw * ld0 - off0) * (unsigned)sizeof(T));
-            const int pbase = oy0 * lw + ox0;
-#pragma unroll
-            for (int i = lane; i < P * OPV; i += 64) {
-                const int p = i / OPV, c = (i % OPV) * VEC;
-                const int py = p / TW, px = p % TW;
-                buf_store16(r0, ox0 + px < lw ? (unsigned)(((pbase + py * lw + px) * ld0 + c) * (int)sizeof(T)) : kOobOffset, *(const V *)(s_res + p * LDO + c));
-            }
-        };
-        TileCoord cur(first, L.tiles_x, L.tiles_y), pf = cur;
-#pragma unroll
-        for (int d = 0; d < DIST; d++)
-            if (d < n_my) { dma(pf.tx, pf.ty, pf.img, d); step.advance(pf); }
-        if (DIST == 2 && n_my >= 2) wait_vmcnt<W::PIECES + W::CPIECES>();
-        else wait_vmcnt<0>();
-        lds_barrier();
-        int p_img = 0, p_oy0 = 0, p_ox0 = 0;
-        for (int k = 0; k < n_my; k++) {
-            const bool st = k > 0, ld = k + DIST < n_my;
-            RF_TRACE_T(6, 5, 256);
-            // the previous result sits in the aux space of buffer (k - 1) % NBUF == (k + DIST) % NBUF: it is read out (LDS reads complete
-            // before the stores that carry the data are issued) BEFORE the coarse patch of tile k + DIST is requested into the same space
-            lds_barrier();
-            RF_TRACE_T(6, 6, 256);                                             // (blend -> GEMM): joined FIRST -- this wave's issue work (~300 instructions)
-                                                                       // then overlaps the consumers' GEMM instead of holding up their short blend pass
-            if (st) store_tile((k - 1) % NBUF, p_img, p_oy0, p_ox0);
-            RF_TRACE_T(6, 7, 256);
-            if (ld) { dma(pf.tx, pf.ty, pf.img, (k + DIST) % NBUF); step.advance(pf); }
-            RF_TRACE_T(6, 8, 256);
-            p_img = cur.img; p_oy0 = cur.ty * TH; p_ox0 = cur.tx * TW;
-            step.advance(cur);
-            if (DIST == 1) wait_vmcnt<0>();
-            else if (st && ld) wait_vmcnt<W::NSTORE + W::PIECES + W::CPIECES>();
-            else if (ld) wait_vmcnt<W::PIECES + W::CPIECES>();
-            else if (st) wait_vmcnt<W::NSTORE>();
-            else wait_vmcnt<0>();
-            RF_TRACE_T(6, 9, 256);
-            lds_barrier();
-            RF_TRACE_T(6, 10, 256);
-        }
-        if (n_my > 0) store_tile((n_my - 1) % NBUF, p_img, p_oy0, p_ox0);
-        return;
-    }
-
-    // ================================================= consumers: wave = output-channel tile
-    const int wn = wave;
-    Frag wst[1][KCH];
-    {
-        const Frag *wsrc = (const Frag *)L.w + (size_t)wn * KCH * 64 + lane;
-#pragma unroll
-        for (int kc2 = 0; kc2 < KCH; kc2++) wst[0][kc2] = wsrc[kc2 * 64];
-    }
-    const f32x4 bias = *(const f32x4 *)(L.b + acc_cout(wn, lane, 0));
-    const f32x4 mult = load_mult(L.m, acc_cout(wn, lane, 0));
-    const float a_lat = L.a_lat, a_up = L.a_up;
-    const bool int_blend = L.int_blend != 0;
-    int pbase[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; j++) {
-        const int p = acc_pixel(j, lane);
-        pbase[j] = (p / TW) * ROWP + (p % TW) * LDI;
-    }
-    // blend items of this thread: halo pixel (dy, dx), 16-byte chunk cv -> element offsets of the lateral item and of the coarse patch's
-    // tap (my, mx); the other three taps are one row / one column further in the direction the pixel's parity picks (tile origins are
-    // multiples of 8: the parities are thread constants)
-    int b_lat[W::NBL], b_c0[W::NBL], b_step[W::NBL], b_yx[W::NBL];
-#pragma unroll
-    for (int m = 0; m < W::NBL; m++) {
-        int i = tid + m * 256;
-        const bool real = i < HR * HC * DPP;
-        i = real ? i : 0;
-        const int pix = i / DPP, cv = i % DPP;
-        const int dy = pix / HC, dx = pix % HC;
-        const int ly = 2 + ((dy - 1) >> 1), lx = 2 + ((dx - 1) >> 1);
-        const int sy = ((dy - 1) & 1) ? 1 : -1, sx = ((dx - 1) & 1) ? 1 : -1;
-        b_lat[m] = dy * ROWP + dx * LDI + cv * VEC;
-        b_c0[m] = (ly * CW + lx) * CIN + cv * VEC;
-        b_step[m] = (sy * CW * CIN) * 65536 + (sx * CIN + 32768);      // row step in the high half, column step (+32768) in the low half
-        b_yx[m] = real ? (dy << 8 | dx) : -1;
-    }
-    __builtin_amdgcn_s_waitcnt(0x0F70);                                // weights are in registers: no global access below this line
-    lds_barrier();
-    TileCoord cur(first, L.tiles_x, L.tiles_y);
-    for (int k = 0; k < n_my; k++) {
-        const int b = k % NBUF;
-        T *s_in_b = halo_of(b);
-        T *s_x = aux_of(b);
-        const int iy0 = cur.ty * TH - 1, ix0 = cur.tx * TW - 1;
-        step.advance(cur);
-        RF_TRACE_T(6, 0, 0);
-        // ---- blend: lateral + upsample(coarse) -> the halo tile, in place (K_c's staging arithmetic, operands from LDS)
-#pragma unroll
-        for (int m = 0; m < W::NBL; m++) {
-            if (b_yx[m] < 0) continue;
-            const int rs_ = b_step[m] >> 16, cs_ = (b_step[m] & 0xffff) - 32768;
-            const V lat = *(const V *)(s_in_b + b_lat[m]);
-            const V u0 = *(const V *)(s_x + b_c0[m]), u1 = *(const V *)(s_x + b_c0[m] + cs_);
-            const V u2 = *(const V *)(s_x + b_c0[m] + rs_), u3 = *(const V *)(s_x + b_c0[m] + rs_ + cs_);
-            const bool ok = (unsigned)(iy0 + (b_yx[m] >> 8)) < (unsigned)lh && (unsigned)(ix0 + (b_yx[m] & 0xff)) < (unsigned)lw;
-            *(V *)(s_in_b + b_lat[m]) = upadd_blend<T>(lat, u0, u1, u2, u3, ok, int_blend, a_lat, a_up);
-        }
-        RF_TRACE_T(6, 1, 0);
-        lds_barrier();
-        RF_TRACE_T(6, 2, 0);
-        // ---- GEMM on the blended halo tile, result over the (dead) coarse patch
-        typename M::Acc acc[1][NJ];
-#pragma unroll
-        for (int j = 0; j < NJ; j++) acc[0][j] = acc_init<T>(bias);
-        gemm_stationary<T, 1, NJ, KCH, DEPTH, true>(acc, wst, [&](int j, int kc2) -> Frag {
-            const int kb = kc2 * M::K + (lane >> 4) * M::KPL;
-            const int tap = kb / CIN, c = kb % CIN;
-            const int koff = (tap / 3) * ROWP + (tap % 3) * LDI + c;
-            return kb < KTOT ? *(const Frag *)(s_in_b + pbase[j] + koff) : M::zero();
-        });
-#pragma unroll
-        for (int j = 0; j < NJ; j++) store_acc<T, LDO>(s_x, mult, bias, acc[0][j], wn, j, lane, true);
-        RF_TRACE_T(6, 3, 0);
-        lds_barrier();
-        RF_TRACE_T(6, 4, 0);
-    }
-}
-#endif  // RF_PROBES
 
 // =============================================================================================
 // K_c3  the aggregation convs with LDS-DMA staging and NO dedicated producer wave (round 4, after the phase stamps of K_c'': a five-wave
@@ -4068,12 +2952,11 @@ __global__ __launch_bounds__(320, (Conv3UpWsCfg<T, NBUF>::WAVES_PER_EU)) void co
 //   different SIMDs -- and its single producer wave spent 0.7 us per tile reading the result tile back from LDS store by store).
 //   Same LDS ring, same blend, same GEMM as K_c''; every one of the four waves (= output-channel tiles) issues a quarter of the
 //   tile's memory traffic itself: its share of the previous result's stores at the top of the interval, its share of the DMA for
-//   the tile DIST steps ahead right after the blend barrier -- i.e. under its own GEMM -- and waits (counted vmcnt) only for the share
-//   of the NEXT tile's halo it requested one interval earlier.
+//   the next tile right after the blend barrier -- i.e. under its own GEMM -- and waits for it at the end of the interval.
 // =============================================================================================
-template <typename T, int DEPTH, int NBUF>
+template <typename T>
 __global__ __launch_bounds__(kThreads, 2) void conv3x3_up_dma_kernel(Conv3Args<T> a) {
-    typedef Conv3UpWsCfg<T, NBUF> W;
+    typedef Conv3UpWsCfg<T> W;
     typedef typename W::B C;
     typedef typename Vec<T>::type V;
     typedef Mma<T> M;
@@ -4081,9 +2964,9 @@ __global__ __launch_bounds__(kThreads, 2) void conv3x3_up_dma_kernel(Conv3Args<T
     constexpr int CIN = 64, TH = 8, TW = 8;
     constexpr int VEC = C::VEC, P = C::P, HC = C::HC, HR = C::HR, LDI = C::LDI, ROWP = C::ROWP, LDO = W::LDO;
     constexpr int KTOT = C::KTOT, KCH = C::KCH, NJ = C::NJ, DPP = W::DPP, CW = W::CW;
-    constexpr int DIST = NBUF - 1;
+    constexpr int NBUF = W::NBUF, DIST = NBUF - 1;
+    constexpr int DEPTH = 2;                                                       // B-fragment prefetch depth of the GEMM
     constexpr int LPW = (W::PIECES + 3) / 4, CPW = (W::CPIECES + 3) / 4;          // DMA pieces per wave: halo, coarse patch
-    constexpr int LMIN = W::PIECES / 4, CMIN = W::CPIECES / 4;                     // ... the fewest any wave issues
     constexpr int SPW = P * (64 / VEC) / kThreads;                                 // store instructions per wave and tile
     static_assert(P * (64 / VEC) % kThreads == 0 && SPW + LPW + CPW < 63, "whole store instructions per wave");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -4201,8 +3084,7 @@ __global__ __launch_bounds__(kThreads, 2) void conv3x3_up_dma_kernel(Conv3Args<T
 #pragma unroll
     for (int d = 0; d < DIST; d++)
         if (d < n_my) { dma(pf.tx, pf.ty, pf.img, d); step.advance(pf); }
-    if (DIST == 2 && n_my >= 2) wait_vmcnt<LMIN + CMIN>();            // tile 0's share has landed (at most the younger request is outstanding)
-    else wait_vmcnt<0>();
+    wait_vmcnt<0>();
     lds_barrier();
     int p_img = 0, p_oy0 = 0, p_ox0 = 0;
     for (int k = 0; k < n_my; k++) {
@@ -4240,26 +3122,22 @@ __global__ __launch_bounds__(kThreads, 2) void conv3x3_up_dma_kernel(Conv3Args<T
         });
 #pragma unroll
         for (int j = 0; j < NJ; j++) store_acc<T, LDO>(s_x, mult, bias, acc[0][j], wn, j, lane, true);
-        // tile k + 1's share must have landed before the barrier.  DIST == 1: it is the request just made.  DIST == 2: it was made one
-        // interval ago; this interval's stores (SPW) and requests (>= LMIN + CMIN) may stay in flight
-        if (DIST == 1) wait_vmcnt<0>();
-        else if (st && ld) wait_vmcnt<SPW + LMIN + CMIN>();
-        else if (ld) wait_vmcnt<LMIN + CMIN>();
-        else if (st) wait_vmcnt<SPW>();
-        else wait_vmcnt<0>();
+        wait_vmcnt<0>();                                               // tile k + 1's share (the request just made) must have landed before the barrier
         lds_barrier();
     }
     if (n_my > 0) store_tile((n_my - 1) % NBUF, p_img, p_oy0, p_ox0);
 }
 
-#ifdef RF_PROBES
-static int conv3_ws_variant() { return knob(K_CONV3WS); }        // probe knob RF_CONV3WS: 1 = the product; 0 = K_c for the merged SSH conv as well; 22 / 23 / 32 / 33 / 122 / 132: see conv3_ws_launch
-#endif
 
-template <typename T, int DEPTH, int NBUF, int SPLIT = 0>
-static void conv3_ws_launch_v(hipStream_t s, Conv3Args<T> &a, int nlv, int total_tiles) {
-    typedef Conv3WsCfg<T, NBUF> W;
-    auto kern = conv3x3_ws_kernel<T, DEPTH, NBUF, SPLIT>;
+// Halo buffers and B-fragment prefetch depth, measured per 256 images
+// (tools/gpu/rounds_3_4.sh r4_call5, 4 repetitions each, profiles/r04_ws_conv_ab.txt): fp16 lock-step 87-90 us (100-104 before its pipeline was pinned),
+// two halo buffers 75-85 (bimodal: the interval is then one memory round trip), THREE 56-58 at either depth; int8 37.2 lock-step, 39-41 /
+// 44 warp-specialised (its GEMM is too short to hide one producer wave's issue work): int8 stays on K_c.  The product: three halo buffers,
+// depth 2, 2 + 2 + 1 roles (57.1 -> 54.5 us, tools/gpu/rounds_3_4.sh r4_call14).
+template <typename T>
+static void conv3_ws_launch(hipStream_t s, Conv3Args<T> &a, int nlv, int total_tiles) {
+    typedef Conv3WsCfg<T> W;
+    auto kern = conv3x3_ws_kernel<T>;
     static std::atomic<int> resident_cache[kMaxDevices] = {};
     const int resident = kernel_residency(resident_cache, kern, W::LDS_BYTES);
     const int want = persistent_grid(total_tiles, resident);
@@ -4276,41 +3154,18 @@ static void conv3_ws_launch_v(hipStream_t s, Conv3Args<T> &a, int nlv, int total
     }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), W::LDS_BYTES, s, a);
 }
-// RF_CONV3WS = 10 * halo buffers + B-fragment prefetch depth (probe knob): 22, 23, 32, 33; 1 = the default = 32.  Measured per 256 images
-// (tools/gpu/rounds_3_4.sh r4_call5, 4 repetitions each, profiles/r04_ws_conv_ab.txt): fp16 lock-step 87-90 us (100-104 before its pipeline was pinned),
-// two halo buffers 75-85 (bimodal: the interval is then one memory round trip), THREE 56-58 at either depth; int8 37.2 lock-step, 39-41 /
-// 44 warp-specialised (its GEMM is too short to hide one producer wave's issue work): int8 stays on K_c.
-template <typename T>
-static void conv3_ws_launch(hipStream_t s, Conv3Args<T> &a, int nlv, int total_tiles) {
-#ifdef RF_PROBES
-    switch (conv3_ws_variant()) {
-        case 22: conv3_ws_launch_v<T, 2, 2>(s, a, nlv, total_tiles); return;
-        case 23: conv3_ws_launch_v<T, 3, 2>(s, a, nlv, total_tiles); return;
-        case 33: conv3_ws_launch_v<T, 3, 3>(s, a, nlv, total_tiles); return;
-        case 122: conv3_ws_launch_v<T, 2, 2, 1>(s, a, nlv, total_tiles); return;     // 1xx: the 2 + 2 + 1 role split of the GEMM waves
-        case 32: conv3_ws_launch_v<T, 2, 3>(s, a, nlv, total_tiles); return;
-        default: break;
-    }
-#endif
-    conv3_ws_launch_v<T, 2, 3, 1>(s, a, nlv, total_tiles);       // = 132: three halo buffers, 2 + 2 + 1 roles (57.1 -> 54.5 us over 32, tools/gpu/rounds_3_4.sh r4_call14)
-}
 
-template <typename T, int CIN, int COUT, int TH, int TW, bool UPADD, bool ALLC, bool PADROW>
+template <typename T, int CIN, int COUT, int TH, int TW, bool UPADD, bool PADROW>
 static void conv3_launch(hipStream_t s, Conv3Args<T> &a, int nlv, int total_tiles) {
-    typedef Conv3Cfg<T, CIN, COUT, TH, TW, ALLC, PADROW> C;
-    if constexpr (sizeof(T) <= 2 && CIN == 64 && COUT == 48 && TH == 8 && TW == 8 && !UPADD && !ALLC && PADROW) {
+    typedef Conv3Cfg<T, CIN, COUT, TH, TW, PADROW> C;
+    if constexpr (sizeof(T) <= 2 && CIN == 64 && COUT == 48 && TH == 8 && TW == 8 && !UPADD && PADROW) {
         bool split32 = true;
         for (int l = 0; l < nlv; l++) split32 = split32 && a.lv[l].n0 == 32 && a.lv[l].out1 != nullptr;
-#ifdef RF_PROBES
-        const bool want = conv3_ws_variant() > 1 || (conv3_ws_variant() == 1 && sizeof(T) == 2);       // default: fp16 only (see conv3_ws_launch)
-        if (want && split32) { conv3_ws_launch<T>(s, a, nlv, total_tiles); return; }
-#else
         if constexpr (sizeof(T) == 2) {
             if (split32) { conv3_ws_launch<T>(s, a, nlv, total_tiles); return; }
         }
-#endif
     }
-    auto kern = conv3x3_kernel<T, CIN, COUT, TH, TW, UPADD, ALLC, PADROW>;
+    auto kern = conv3x3_kernel<T, CIN, COUT, TH, TW, UPADD, PADROW>;
     static std::atomic<int> resident_cache[kMaxDevices] = {};
     const int resident = kernel_residency(resident_cache, kern, C::LDS_BYTES);
     // grid: persistent size for the whole launch, shared out to the levels in proportion to their tiles
@@ -4329,9 +3184,9 @@ static void conv3_launch(hipStream_t s, Conv3Args<T> &a, int nlv, int total_tile
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), C::LDS_BYTES, s, a);
 }
 
-template <typename T, int CIN, int COUT, int TH, int TW, bool ALLC = false, bool PADROW = false>
+template <typename T, int CIN, int COUT, int TH, int TW, bool PADROW = false>
 static TileInfo conv3_dispatch(hipStream_t s, const Conv3Params<T> *p, int nlv, int h, int w) {
-    typedef Conv3Cfg<T, CIN, COUT, TH, TW, ALLC, PADROW> C;
+    typedef Conv3Cfg<T, CIN, COUT, TH, TW, PADROW> C;
     TileInfo ti{TH, TW, C::LDS_BYTES, ((w + TW - 1) / TW) * ((h + TH - 1) / TH)};
     if (!p) return ti;
     Conv3Args<T> a;
@@ -4345,38 +3200,25 @@ static TileInfo conv3_dispatch(hipStream_t s, const Conv3Params<T> *p, int nlv, 
         if (l < nlv) total += q.n * tiles_x * tiles_y;
     }
     if (p[0].up) {
-        if constexpr (CIN == 64 && COUT == 64) conv3_launch<T, CIN, COUT, TH, TW, true, ALLC, PADROW>(s, a, nlv, total);
+        if constexpr (CIN == 64 && COUT == 64) conv3_launch<T, CIN, COUT, TH, TW, true, PADROW>(s, a, nlv, total);
         else throw LaunchUnsupported("fused upsample + add: only the 64 -> 64 aggregation conv has a kernel instance");
     } else {
-        conv3_launch<T, CIN, COUT, TH, TW, false, ALLC, PADROW>(s, a, nlv, total);
+        conv3_launch<T, CIN, COUT, TH, TW, false, PADROW>(s, a, nlv, total);
     }
     return ti;
 }
 
-// probe knob (tools/probes): RF_CONV3=0 selects the round-1 wave split (channel tiles over the waves) for A/B measurements; -1 = the product
-#ifdef RF_PROBES
-static int conv3_variant() { return knob(K_CONV3); }
-#endif
-// probe knob RF_CONV3UPWS: 1 = auto (see conv3_select); 0 = K_c for the aggregation convs; 2 / 3 = halo buffers of the producer-wave kernel (K_c''); 12 / 13: per-wave DMA
-static int conv3_up_ws_variant() { return knob(K_CONV3UPWS); }
-
-template <typename T, int DEPTH, int NBUF, bool PRODUCER_WAVE>
+template <typename T>
 static void conv3_up_ws_launch(hipStream_t s, const Conv3Params<T> &q) {
-    typedef Conv3UpWsCfg<T, NBUF> W;
-#ifdef RF_PROBES
-    auto kern = PRODUCER_WAVE ? conv3x3_up_ws_kernel<T, DEPTH, NBUF> : conv3x3_up_dma_kernel<T, DEPTH, NBUF>;
-#else
-    static_assert(!PRODUCER_WAVE, "the producer-wave aggregation conv is a probe-build kernel");
-    auto kern = conv3x3_up_dma_kernel<T, DEPTH, NBUF>;
-#endif
-    constexpr int THREADS = PRODUCER_WAVE ? W::THREADS : kThreads;
+    typedef Conv3UpWsCfg<T> W;
+    auto kern = conv3x3_up_dma_kernel<T>;
     static std::atomic<int> resident_cache[kMaxDevices] = {};
     const int dev = launch_device();
     int resident = resident_cache[dev].load(std::memory_order_acquire);
     if (!resident) {
         set_max_lds(kern, W::LDS_BYTES);
         int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kern, THREADS, W::LDS_BYTES) != hipSuccess || nb < 1) nb = 1;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kern, kThreads, W::LDS_BYTES) != hipSuccess || nb < 1) nb = 1;
         resident = nb;
         resident_cache[dev].store(resident, std::memory_order_release);
     }
@@ -4389,7 +3231,7 @@ static void conv3_up_ws_launch(hipStream_t s, const Conv3Params<T> &q) {
     const int total = q.n * tiles_x * tiles_y;
     if (total == 0) return;
     a.lv[0].gsz = persistent_grid(total, resident);
-    hipLaunchKernelGGL(kern, dim3(a.lv[0].gsz), dim3(THREADS), W::LDS_BYTES, s, a);
+    hipLaunchKernelGGL(kern, dim3(a.lv[0].gsz), dim3(kThreads), W::LDS_BYTES, s, a);
 }
 
 template <typename T>
@@ -4397,52 +3239,22 @@ static TileInfo conv3_select(hipStream_t s, const Conv3Params<T> *p, int nlv, in
     if constexpr (sizeof(T) <= 2) {
         // the aggregation convs (fused upsample + add), warp-specialised: maps whose sides are even (tile origins must be: the upsample's
         // parities are thread constants) and a single output tensor
-        // Default (RF_CONV3UPWS unset = 1): fp16 maps of >= 48 x 48 pixels take the variant where every wave issues its own share of the
+        // fp16 maps of >= 48 x 48 pixels take the variant where every wave issues its own share of the
         // LDS-DMA (two ring buffers): rf_c1_aggr 77.8 -> 73.6 us per 256 images; the 28 x 28 map of rf_c2_aggr and the int8 engine measured
         // equal or slower and stay on K_c (tools/gpu/rounds_3_4.sh r4_call12, profiles/r04_rejected_ws_variants.txt).
-        const int upv = conv3_up_ws_variant() == 1 ? ((sizeof(T) == 2 && p && (long)p[0].h * p[0].w_ >= 48 * 48) ? 12 : 0) : conv3_up_ws_variant();
-        if (p && nlv == 1 && p[0].up && cin == 64 && cout == 64 && upv >= 2 && p[0].h % 2 == 0 && p[0].w_ % 2 == 0 &&
+        const bool up_ws = sizeof(T) == 2 && p && (long)p[0].h * p[0].w_ >= 48 * 48;
+        if (p && nlv == 1 && p[0].up && cin == 64 && cout == 64 && up_ws && p[0].h % 2 == 0 && p[0].w_ % 2 == 0 &&
             p[0].n0 == 64 && p[0].in_ld == 64) {
-#ifdef RF_PROBES
-            switch (upv) {                                             // 2 / 3: producer wave, 2 / 3 ring buffers; 12 / 13: every wave its own share
-                case 2: conv3_up_ws_launch<T, 2, 2, true>(s, p[0]); break;
-                case 3: conv3_up_ws_launch<T, 2, 3, true>(s, p[0]); break;
-                case 12: conv3_up_ws_launch<T, 2, 2, false>(s, p[0]); break;
-                default: conv3_up_ws_launch<T, 2, 3, false>(s, p[0]); break;
-            }
-#else
-            conv3_up_ws_launch<T, 2, 2, false>(s, p[0]);
-#endif
-            return TileInfo{8, 8, Conv3UpWsCfg<T, 3>::LDS_BYTES, ((w + 7) / 8) * ((h + 7) / 8)};
+            conv3_up_ws_launch<T>(s, p[0]);
+            return TileInfo{8, 8, Conv3UpWsCfg<T>::LDS_BYTES, ((w + 7) / 8) * ((h + 7) / 8)};
         }
-#ifdef RF_PROBES
-        // fp16 / int8: every wave owns all output channels of its pixels (Conv3Cfg ALLC), 8x8 tiles
-        const int v = conv3_variant();
-        if (v >= 1) {
-            if (cin == 64 && cout == 64) return v == 2 ? conv3_dispatch<T, 64, 64, 4, 16, true>(s, p, nlv, h, w) : conv3_dispatch<T, 64, 64, 8, 8, true>(s, p, nlv, h, w);
-            if (cin == 64 && cout == 48) return v == 2 ? conv3_dispatch<T, 64, 48, 8, 16, true>(s, p, nlv, h, w) : conv3_dispatch<T, 64, 48, 8, 8, true>(s, p, nlv, h, w);
-            if (cin == 16 && cout == 32) return conv3_dispatch<T, 16, 32, 8, 8, true>(s, p, nlv, h, w);
-            if (cin == 16 && cout == 16) return conv3_dispatch<T, 16, 16, 8, 8, true>(s, p, nlv, h, w);
-            return TileInfo{0, 0, 0, 0};
-        }
-        if (v == -1) {          // round-1 wave split, halo rows padded to the bank row (conflict-free B-fragment reads)
-            if (cin == 64 && cout == 64) return conv3_dispatch<T, 64, 64, 4, 8, false, true>(s, p, nlv, h, w);
-            if (cin == 16 && cout == 32) return conv3_dispatch<T, 16, 32, 8, 8, false, true>(s, p, nlv, h, w);
-            if (cin == 64 && cout == 48) return conv3_dispatch<T, 64, 48, 8, 8, false, true>(s, p, nlv, h, w);
-            if (cin == 16 && cout == 16) return conv3_dispatch<T, 16, 16, 8, 8, false, true>(s, p, nlv, h, w);
-        }
-#else
         // the product: round-1 wave split, halo rows padded to the bank row (conflict-free B-fragment reads); the 16-channel convs of the SSH tail
         // live in ssh_tail_kernel (fp16 / int8), so only the aggregation conv and the merged SSH 64 -> 48 conv have instances here
-        if (cin == 64 && cout == 64) return conv3_dispatch<T, 64, 64, 4, 8, false, true>(s, p, nlv, h, w);
-        if (cin == 64 && cout == 48) return conv3_dispatch<T, 64, 48, 8, 8, false, true>(s, p, nlv, h, w);
+        if (cin == 64 && cout == 64) return conv3_dispatch<T, 64, 64, 4, 8, true>(s, p, nlv, h, w);
+        if (cin == 64 && cout == 48) return conv3_dispatch<T, 64, 48, 8, 8, true>(s, p, nlv, h, w);
         return TileInfo{0, 0, 0, 0};
-#endif
     }
-#ifndef RF_PROBES
-    if constexpr (sizeof(T) > 2)          // (fp16 / int8 returned above; RF_CONV3=0 of the probe build sends them here too)
-#endif
-    {
+    else {
         // single-level small maps (stride 32 / 16 at 448^2: 14x14, 28x28) get 4x8 tiles for more workgroups where the
         // channel tiles still split over 4 waves (COUT % 32 == 0); everything else 8x8
         const bool small = nlv == 1 && (size_t)h * w <= 32 * 32;
@@ -4501,6 +3313,8 @@ template <typename T> struct SshTailCfg {
                             OUT_BYTES = sizeof(T) * (size_t)(P * LDO);
     static constexpr size_t LDS_BYTES = IN_BYTES + MID_BYTES + 2 * OUT_BYTES;      // the out tile is double buffered (2 barriers per tile)
     static_assert(IN_BYTES % 16 == 0 && MID_BYTES % 16 == 0, "LDS carve must stay 16-byte aligned");
+    // 4 workgroups per CU (128 VGPRs); 3 per CU (155 VGPRs, no spill) measured slower
+    static constexpr int OCC = 4;
 };
 
 template <typename T>
@@ -4530,8 +3344,8 @@ template <typename T> __device__ __forceinline__ void store_packed4(T *dst, uint
     else *(uint32_t *)dst = h.x;
 }
 
-template <typename T, int OCC>
-__global__ __launch_bounds__(kThreads, OCC) void ssh_tail_kernel(SshTailArgs<T> a) {
+template <typename T>
+__global__ __launch_bounds__(kThreads, SshTailCfg<T>::OCC) void ssh_tail_kernel(SshTailArgs<T> a) {
     typedef SshTailCfg<T> C;
     typedef typename Vec<T>::type V;
     typedef Mma<T> M;
@@ -4693,21 +3507,12 @@ __global__ __launch_bounds__(kThreads, OCC) void ssh_tail_kernel(SshTailArgs<T> 
     if (p_img >= 0) store_tile(s_out + (buf ^ 1) * O_ELEMS, p_img, p_oy0, p_ox0);
 }
 
-int ssh_tail_variant() { return knob(K_SSHTAIL); }      // probe knob RF_SSHTAIL: 1 = the product; 0 = two conv3x3<16,*> launches, 2 = 3 workgroups per CU
-
 template <typename T> void launch_ssh_tail(hipStream_t s, const SshTailParams<T> *levels, int nlevels) {
     typedef SshTailCfg<T> C;
     if (nlevels < 1 || nlevels > 3) throw LaunchUnsupported("ssh tail: 1..3 levels per launch");
-    // RF_SSHTAIL=2 (probe knob): the 3-workgroups-per-CU build (155 VGPRs, no spill) instead of the 4-per-CU one (128 VGPRs)
-#ifdef RF_PROBES
-    const bool occ3 = ssh_tail_variant() == 2;
-    auto kern = occ3 ? ssh_tail_kernel<T, 3> : ssh_tail_kernel<T, 4>;
-#else
-    constexpr bool occ3 = false;
-    auto kern = ssh_tail_kernel<T, 4>;
-#endif
-    static std::atomic<int> resident_cache[2][kMaxDevices] = {};
-    const int resident = kernel_residency(resident_cache[occ3 ? 1 : 0], kern, C::LDS_BYTES);
+    auto kern = ssh_tail_kernel<T>;
+    static std::atomic<int> resident_cache[kMaxDevices] = {};
+    const int resident = kernel_residency(resident_cache, kern, C::LDS_BYTES);
     SshTailArgs<T> a;
     int total = 0;
     for (int l = 0; l < 3; l++) {

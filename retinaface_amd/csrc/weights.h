@@ -19,7 +19,6 @@
 #include <vector>
 
 #include "kernels.h"
-#include "knobs.h"
 #include "model.h"
 #include "pack.h"
 #include "plan.h"
@@ -132,8 +131,6 @@ struct WeightPack {
     Arena arena_;
     size_t c0_w_ = 0, c0_b_ = 0, c0_hi_ = 0, c0_b_mma_ = 0;      // c0_b_mma_: conv0 bias of the MFMA stems (offset-folded, see pack())
     size_t c0_raw_ = 0;                                          // conv0 fragments for the raw-row staging of stem2 (two column parities, see pack())
-    size_t stem_c0tab_ = 0;                                      // the int8 stem's conv0 pixel table (pack.h stem_conv0_table)
-    size_t stem2_dw4_ = 0, stem2_c0tab_ = 0;                     // stem2: conv3's diagonal A fragments expanded to 4 dwords per lane; conv0's pixel table (see pack())
     DwW stem_dw_{0, 0}, stem2_dw_{0, 0};
     GemmW stem_pw_{0, 0}, stem2_pw_{0, 0};
     size_t stem2_c2_b_ = 0, stem2_c2_floor_ = 0, stem2_c3_floor_ = 0;      // stem2's DC-centred tiles (pack())
@@ -397,7 +394,6 @@ struct WeightPack {
                             raw[(((size_t)par * 4 + half * 2 + 1) * 64 + lane) * 8 + el] = (half_t)(w - (float)h);
                         }
             c0_raw_ = arena_.put(raw);
-            stem_c0tab_ = arena_.put(stem_conv0_table());
             // the stems feed 1024 + pixel into those fragments (kernels.hip u8x4_to_f16): bias - 1024 * sum of the hi + lo weights
             {
                 std::vector<float> bm(plan.conv0.b);
@@ -446,7 +442,7 @@ struct WeightPack {
             dw_w_.push_back(DwW{0, 0});
             pw_w_.push_back(GemmW{0, 0});
             if constexpr (std::is_same<T, half_t>::value) {
-                if (stem2_variant()) {
+                {
                     // stem2 also runs the first stride-2 block: conv3 taps as diagonal MFMA fragments (equalised per channel like every
                     // other depthwise stage, see equalize_depthwise), conv4 as a standard packed 32 x 16 GEMM
                     FoldedConv dwq = plan.blocks[1].dw, pwq = plan.blocks[1].pw;
@@ -455,10 +451,9 @@ struct WeightPack {
                     // pixel 128: the interior of every map is then one constant per channel), rounded to fp16 so that the shift
                     // itself is exact.  Shifting a tensor by a per-channel constant is exact algebra as long as its consumer's bias
                     // takes the constant back: conv3 (depthwise, taps t): + mu2 * sum(t); conv4 (1x1, W): + W mu3.  Both sums use
-                    // the weights AS THE KERNEL SEES THEM (fp16-rounded taps, hi + lo pointwise weights).  RF_STEM2_DC=0: mu = 0
-                    // (probe / test knob: the tiles are then plain ReLU outputs as in round 2).
+                    // the weights AS THE KERNEL SEES THEM (fp16-rounded taps, hi + lo pointwise weights).
                     std::vector<float> mu2(16, 0.f), mu3(16, 0.f);
-                    if (knob(K_STEM2_DC) != 0) {
+                    {
                         double y0[8], y1[8];
                         for (int c = 0; c < 8; c++) {
                             double sw = 0.0;
@@ -500,15 +495,6 @@ struct WeightPack {
                         dwq.b[c] = (float)((double)dwq.b[c] + (double)mu2[c] * st - (double)mu3[c]);
                     }
                     stem2_dw_ = put_dw(dwq);
-                    {   // round 6: the same diagonal A fragments EXPANDED to the four dwords a lane feeds the MFMA -- [5][64][4] dwords, one 16-byte load
-                        // per chunk instead of one dword + four v_cndmask (20 VALU instructions per wave of stem2's conv3 phase)
-                        const uint32_t *mm = (const uint32_t *)(arena_.host().data() + stem2_dw_.mma);
-                        std::vector<uint32_t> ex((size_t)kDwMmaChunks * 64 * 4, 0u);
-                        for (int kc = 0; kc < kDwMmaChunks; kc++)
-                            for (int lane = 0; lane < 64; lane++) ex[((size_t)kc * 64 + lane) * 4 + dw_mma_dword_index(lane)] = mm[kc * 64 + lane];
-                        stem2_dw4_ = arena_.put(ex);
-                    }
-                    stem2_c0tab_ = arena_.put(stem2_conv0_table());
                     // conv4: K = 16 of the MFMA's 32 slots -> the weights ride as hi | lo along K; bias + (hi + lo) mu3
                     std::vector<float> w2((size_t)pwq.cout * 32, 0.f), b4(pwq.b);
                     for (int o = 0; o < pwq.cout; o++) {
@@ -626,7 +612,7 @@ struct WeightPack {
 
     // ------------------------------------------------------------------------------------------ (de)serialisation
     template <class Ar> void io(Ar &ar) {
-        ar.pod(c0_w_); ar.pod(c0_b_); ar.pod(c0_hi_); ar.pod(c0_b_mma_); ar.pod(c0_raw_); ar.pod(stem_c0tab_); ar.pod(stem2_dw4_); ar.pod(stem2_c0tab_);
+        ar.pod(c0_w_); ar.pod(c0_b_); ar.pod(c0_hi_); ar.pod(c0_b_mma_); ar.pod(c0_raw_);
         ar.pod(stem_dw_); ar.pod(stem2_dw_); ar.pod(stem_pw_); ar.pod(stem2_pw_);
         ar.pod(stem2_c2_b_); ar.pod(stem2_c2_floor_); ar.pod(stem2_c3_floor_);
         ar.pod(aggr_a_lat_); ar.pod(aggr_a_up_); ar.pod(head_a_);
@@ -650,7 +636,7 @@ struct WeightPack {
         auto ok = [n](size_t off) { return off == kNone || off < n; };
         auto okg = [&](const GemmW &g) { return ok(g.w) && ok(g.b) && ok(g.m); };
         auto okd = [&](const DwW &d) { return ok(d.w) && ok(d.b) && ok(d.mma) && ok(d.m); };
-        bool good = ok(c0_w_) && ok(c0_b_) && ok(c0_hi_) && ok(c0_b_mma_) && ok(c0_raw_) && ok(stem_c0tab_) && ok(stem2_dw4_) && ok(stem2_c0tab_) && okd(stem_dw_) && okd(stem2_dw_) && okg(stem_pw_) && okg(stem2_pw_) &&
+        bool good = ok(c0_w_) && ok(c0_b_) && ok(c0_hi_) && ok(c0_b_mma_) && ok(c0_raw_) && okd(stem_dw_) && okd(stem2_dw_) && okg(stem_pw_) && okg(stem2_pw_) &&
                     ok(stem2_c2_b_) && ok(stem2_c2_floor_) && ok(stem2_c3_floor_);
         for (const auto &d : dw_w_) good = good && okd(d);
         for (const auto &g : pw_w_) good = good && okg(g);
@@ -671,7 +657,7 @@ inline uint64_t fnv1a64(const char *p, size_t n) {
 struct PlanCacheKey {
     uint64_t source_hash = 0;          // FNV-1a of the model files' bytes (model.cpp model_source_hash)
     uint64_t build = 0;                // fingerprint of the library build that packed it: a rebuilt library never trusts an old image
-    int32_t precision = 0, stem2 = 0;
+    int32_t precision = 0;
 };
 
 // <model_dir>/<stem>.<fp32|fp16|int8>.rfplan
@@ -703,7 +689,7 @@ template <typename T> bool load_plan_cache(const std::string &bytes, const PlanC
     if (ver != kPlanCacheVersion) return false;
     PlanCacheKey k;
     ar.pod(k);
-    if (k.source_hash != key.source_hash || k.build != key.build || k.precision != key.precision || k.stem2 != key.stem2) return false;
+    if (k.source_hash != key.source_hash || k.build != key.build || k.precision != key.precision) return false;
     uint64_t len = 0, sum = 0;
     ar.pod(len);
     ar.pod(sum);

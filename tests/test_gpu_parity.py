@@ -228,59 +228,6 @@ def test_synthetic_batch8_against_golden(rfa, stem, prec):
             assert abs(ncand[i] - int(g[f"ncand{tag}_{i}"])) <= ncand_band(prec, f"{stem}/synth448_{i}/{tag}"), (stem, tag, i, ncand[i])
 
 
-PROBE_LIB = os.path.join(ROOT, "retinaface_amd", "lib", "libretinaface_amd_probe.so")
-
-
-@pytest.mark.skipif(os.environ.get("RF_PROBE_TESTS") != "1",
-                    reason="23 subprocesses against the PROBE build (make probe): run with RF_PROBE_TESTS=1 (tools/gpu/r6.sh <tag> probes; the result is committed "
-                           "under profiles/); kept out of the driver's -m gpu run, which tests the product library")
-@pytest.mark.parametrize("knob", ["RF_STEM2=0", "RF_STEM2=2", "RF_STEM2=3", "RF_DWPW2=0", "RF_CONV3=0", "RF_STEM2_DC=0", "RF_SSHTAIL=0", "RF_CONV3WS=0", "RF_CONV3WS=32",
-                                  "RF_CONV3UPWS=0", "RF_CONV3UPWS=3", "RF_CONV3UPWS=13", "RF_DWPWWS=3", "RF_DWPWWS=13", "RF_TILE256=1", "RF_DWPW2_RING=1",
-                                  "RF_DWPW2_CHAIN=1", "RF_DWPW2_LAY2=0", "RF_DWPW2_HPAD=0", "RF_STEM2_V2=0", "RF_STEM2_V2=1", "RF_STEM2_V2=5", "RF_STEM2_V2=7"])
-def test_probe_knob_kernel_variants_stay_correct(rfa, knob):
-    """The measured-and-rejected kernel variants DESIGN.md cites stay buildable and correct: they live in the PROBE build only since round 5
-    (libretinaface_amd_probe.so, -DRF_PROBES; the product library has neither the kernels nor the knobs, csrc/knobs.h).  Each RF_* probe knob is
-    held to the same fp16 parity bar as the default path, in a subprocess so that the knob is seen at library start-up.
-    RF_STEM2=0: K_a' stem + separate dwpw<16,32,s2>; 2: 7x16 tiles, 8 waves; 3: fp16 patch; RF_DWPW2=0: blocks 2 and 3 as two
-    launches; RF_CONV3=0: 3x3 convs without the bank-row padding; RF_STEM2_DC=0: stem2's LDS tiles without the DC centring; RF_CONV3WS=0: the merged
-    SSH conv on the lock-step K_c kernel instead of the warp-specialised one (round 4), 32: wave = channel tile instead of the 2 + 2 + 1 roles;
-    RF_CONV3UPWS=0 / 3 / 13: the aggregation convs on K_c / with a producer wave / with per-wave LDS-DMA and three ring buffers; RF_DWPWWS=3: the
-    64- and 128-channel blocks warp-specialised (13: the memory side spread over the four GEMM waves); RF_TILE256=1: 8 x 8 tiles for the 256-channel block;
-    RF_DWPW2_RING=1: dwpw2's depthwise A as a ring; RF_DWPW2_CHAIN=1: dwpw2 with the depthwise -> pointwise hops chained in registers (permuted K order);
-    RF_DWPW2_LAY2=0 / RF_DWPW2_HPAD=0: dwpw2 with round 3's LDS pitches / unpadded halo rows; RF_STEM2_V2=0: stem2's conv2 tile as 32-byte pixels and pixel = thread index
-    in its depthwise-1 phase (round 3), 1: planar conv2 tile only, 5: both layout changes without the conv3 -> conv4 register chain (round 4's default), 7: with the
-    chain (round 5's default); 15 = 7 + the raw-row staging of aligned full-width frames is the default since round 6 (frames that are NOT aligned take the general
-    path in the product too: test_device_frames_unaligned_pointer_odd_step_and_roi)."""
-    code = (
-        "import sys, json; sys.path.insert(0, %r)\n"
-        "import retinaface_amd\n"
-        "from retinaface_amd.frames import synth_frames\n"
-        "det = retinaface_amd.RetinaFace(%r, 'net3', 0.4, precision=1, net_hw=(448, 448), model_stem='mnet25')\n"
-        "res = det.detectBatchImages(synth_frames(448, 448, 8, config=1), 0.5)\n"
-        "print('RESULT ' + json.dumps([[[d.anchor_index] + [float(v) for v in d.as_row()] for d in r] for r in res]))\n"
-    ) % (ROOT, ASSETS)
-    assert os.path.exists(PROBE_LIB), "build the probe library first: make -C retinaface_amd/csrc probe"
-    env = dict(os.environ, RETINAFACE_AMD_LIB=PROBE_LIB)
-    k, v = knob.split("=")
-    env[k] = v
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert "is not a value this knob knows" not in out.stderr and "ignored: probe knobs" not in out.stderr, out.stderr[-500:]
-    line = [l for l in out.stdout.splitlines() if l.startswith("RESULT ")][-1]
-    res = json.loads(line[len("RESULT "):])
-    g = golden("synth448_mnet25.npz")
-    t = TOL[FP16]
-    for i in range(8):
-        ref_rows, ref_idx = g[f"det05_{i}"], g[f"idx05_{i}"]
-        got_idx = [int(r[0]) for r in res[i]]
-        if got_idx != list(ref_idx):             # only the oracle's own near-tie twins may differ (tests/anchor_twins.py)
-            ref_rows, _, canon = resolve(got_idx, ref_rows, ref_idx, twin_band(f"mnet25/synth448_{i}/05"))
-            assert canon == list(ref_idx), (knob, i)
-        for got, ref in zip(res[i], ref_rows):
-            assert iou_plus1(got[2:6], ref[1:5]) >= 1 - t["iou"], (knob, i)
-            assert abs(got[1] - ref[0]) <= score_tol(FP16, ref[0])
-
-
 @pytest.mark.parametrize("thr", [0.5, 0.1, 0.02, 0.004, 0.0015])
 def test_postprocessing_is_exact_given_the_gpu_head_blobs(rfa, crop448, thr):
     """Decode + regression + clip + NMS on the device vs the plain-C restatement fed the device's own head blobs:

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Per-kernel HIP-event timing table of one engine configuration (rf_profile), for A/B runs of kernel variants selected by
-environment knobs (RF_CONV3, RF_PERSIST_MIN_ROUNDS, ...).  Usage on the GPU box:
+"""Per-kernel HIP-event timing table of one engine configuration (rf_profile), for A/B runs of library builds or
+environment knobs (RF_BLEND_FP32, RF_SYNC_PIECES, ...).  Usage on the GPU box:
     python tools/kbench.py [--precision fp16|int8|fp32] [--model mnet25] [--hw 448 448] [--n 128] [--iters 30] [--tag name]
 Writes gpurun_out/kbench_<tag>.json and prints the table."""
 import argparse

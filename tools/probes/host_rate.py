@@ -1,5 +1,5 @@
 """Probe: host-frame pipeline rate (rf_enqueue_batch, batch 8, 448 x 448, fp16) with pageable and with registered caller memory.
-usage: [RF_COPY_STREAMS=2] python tools/probes/host_rate.py [seconds]"""
+usage: python tools/probes/host_rate.py [seconds]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -27,6 +27,6 @@ for label, reg in (("pageable", False), ("registered", True)):
     while time.perf_counter() - t0 < secs:
         run(slots, ring); n += slots
     torch.cuda.synchronize(); dt = time.perf_counter() - t0
-    print(f"RF_COPY_STREAMS={os.environ.get('RF_COPY_STREAMS', '1')} {label}: {n * B / dt:.0f} images/s  {n * B * H * W * 3 / dt / 1e9:.1f} GB/s", flush=True)
+    print(f"{label}: {n * B / dt:.0f} images/s  {n * B * H * W * 3 / dt / 1e9:.1f} GB/s", flush=True)
     if reg: det.host_unregister(buf)
 det.close()
