@@ -11,6 +11,7 @@
  *   - a second constructor takes rf_options (precision, net size, batch, model stem) -- the reference bakes
  *     these in at compile time / in prototxt line 7.
  *   - errors throw std::runtime_error instead of abort()/exit(0).
+ *   - detectAndAlign() also returns each face as an aligned crop, the input of the recogniser that usually follows.
  */
 #ifndef RETINAFACE_H
 #define RETINAFACE_H
@@ -61,6 +62,12 @@ public:
        the TensorRT-build signature above, RetinaFace.h:70): no resize, pad to x32, run at that size; result in lastResult() */
     void detectPad32(const Mat &img, float threshold = 0.5);
 
+    /* additive: detect() + the faces warped onto the five-landmark recognition template (rf_detect_align_batch): one
+       cropSize x cropSize CV_8UC3 BGR crop per face of lastResult(), in the same order, sampled from `img` at its full
+       resolution; alignMatrices() holds their forward matrices (source pixels -> crop pixels, 6 doubles each) */
+    vector<cv::Mat> detectAndAlign(const Mat &img, float threshold = 0.5, int cropSize = 112);
+    const vector<double> &alignMatrices() const { return alignMats_; }
+
     /* `scale` of RetinaFace.cpp:585-589: multiply lastResult() coordinates by it for source-frame pixels (:732-739, commented) */
     float frameScale(const Mat &img) const { return rf_frame_scale(h_, img.rows, img.cols); }
 
@@ -79,6 +86,7 @@ private:
     float nms_threshold;
     vector<FaceDetectInfo> last_;
     vector<vector<FaceDetectInfo>> lastBatch_;
+    vector<double> alignMats_;
 };
 
 #endif /* RETINAFACE_H */

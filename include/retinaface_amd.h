@@ -152,6 +152,48 @@ int rf_detect_batch_device(rf_handle h, const void *const *d_bgr, const int *row
                            const int *steps, int n, float threshold,
                            rf_face *out, int cap_per_image, int *counts);
 
+/* ---- Face alignment (no reference equivalent: the reference stops at detection; the step its users run next, an ArcFace-style
+ * recogniser, takes crops warped onto a five-landmark template).  A crop is crop_size x crop_size x 3 u8 BGR, dense, row-major;
+ * crop_size S is 16..512 (112 is the usual one).  DESIGN.md "Face alignment" holds the full definition; every result is
+ * byte-exact against it (tests/align_ref.py restates it in numpy):
+ *   template   x = {38.2946, 73.5318, 56.0252, 41.5493, 70.7299}, y = {51.6963, 51.5014, 71.7366, 92.3655, 92.2041} (left eye,
+ *              right eye, nose, mouth left, mouth right: the order of rf_face.px / py), times S / 112;
+ *   transform  the least-squares similarity without reflection from the landmarks times coord_scale onto the template, in IEEE
+ *              double with + - * / in a fixed order and no fused multiply-add; a face whose landmarks do not span a plane
+ *              (all equal, NaN, infinite) is INVALID: zero matrix, all-zero crop;
+ *   sampling   crop pixel (u, v) is mapped back with the inverse similarity, the position rounded to 1/1024 pixel and the four
+ *              neighbours blended in integers, (sum w * pix + 2^19) >> 20; taps outside the frame count as 0 (constant border);
+ *              no half-pixel shift, no prefilter (cv::warpAffine-style bilinear).
+ *
+ * rf_align_matrix: host only, no GPU, no handle.  The forward matrix (source pixels -> crop pixels, row-major 2 x 3) of one face.
+ * Returns 1 (valid), 0 (invalid face: fwd is all zero) or RF_ERR_INVALID_ARG (NULL argument, crop_size outside 16..512). */
+int rf_align_matrix(const rf_face *face, float coord_scale, int crop_size, double fwd[6]);
+
+/* Aligned crops of faces the CALLER supplies -- faces[i * cap_per_image + k], k < counts[i], e.g. the result of an earlier detect
+ * call -- from frames resident on the engine's device.  coord_scale[i] multiplies image i's landmarks into source-frame pixels
+ * (rf_frame_scale for results of rf_detect_batch*; NULL = 1 for all, which is also right for rf_detect_batch_pad32 results).
+ * The crop of face k of image i is slot i * max_faces + k, for k < min(counts[i], max_faces); the other slots are unspecified.
+ * d_crops (device memory on the engine's device) and crops (host memory) hold n * max_faces slots of 3 * S * S bytes, matrices
+ * (host) n * max_faces * 6 doubles; each may be NULL.  max_faces is 1..4096.
+ * Multi-device handles (options.n_devices > 1) return RF_ERR_UNSUPPORTED from this and the next two calls. */
+int rf_align_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                          const rf_face *faces, int cap_per_image, const int *counts, const float *coord_scale, int crop_size,
+                          int max_faces, void *d_crops, uint8_t *crops, double *matrices);
+
+/* rf_detect_batch_device + the aligned crops of what it finds, in one call: detection runs exactly as in rf_detect_batch_device
+ * (out / counts / rf_last_anchor_indices are the same bytes), and the alignment launches follow each detection launch on its
+ * stream with no host synchronisation in between -- they read the faces from the device-visible result block.  coord_scale is each
+ * frame's rf_frame_scale, so a frame the engine shrank is sampled at its full source resolution.  n may exceed max_batch.
+ * Slots, buffers and max_faces as above; faces beyond max_faces (score order) get no crop. */
+int rf_detect_align_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                 float threshold, rf_face *out, int cap_per_image, int *counts, int crop_size, int max_faces,
+                                 void *d_crops, uint8_t *crops, double *matrices);
+
+/* The same with frames in HOST memory (rf_detect_batch's convention): they are uploaded once and both stages read that copy. */
+int rf_detect_align_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                          float threshold, rf_face *out, int cap_per_image, int *counts, int crop_size, int max_faces,
+                          void *d_crops, uint8_t *crops, double *matrices);
+
 /* Asynchronous form of rf_detect_batch_device for serving loops: enqueue returns as soon as the
  * batch is queued on the engine's stream (n <= max_batch); `ticket` identifies one of
  * rf_num_slots() result slots.  rf_wait blocks until that batch has finished and copies its results.

@@ -50,6 +50,16 @@ SYMBOLS = {
     "rf_detect_batch_pad32": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
                                         C.c_int, C.c_float, _PP(rf_face), C.c_int, _PP(C.c_int)]),
     "rf_frame_scale": (C.c_float, [C.c_void_p, C.c_int, C.c_int]),
+    "rf_align_matrix": (C.c_int, [_PP(rf_face), C.c_float, C.c_int, _PP(C.c_double)]),
+    "rf_align_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                        _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_float), C.c_int, C.c_int,
+                                        C.c_void_p, C.c_void_p, _PP(C.c_double)]),
+    "rf_detect_align_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                               C.c_float, _PP(rf_face), C.c_int, _PP(C.c_int), C.c_int, C.c_int,
+                                               C.c_void_p, C.c_void_p, _PP(C.c_double)]),
+    "rf_detect_align_batch": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                        C.c_float, _PP(rf_face), C.c_int, _PP(C.c_int), C.c_int, C.c_int,
+                                        C.c_void_p, C.c_void_p, _PP(C.c_double)]),
     "rf_num_slots": (C.c_int, [C.c_void_p]),
     "rf_enqueue_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int),
                                           C.c_int, C.c_float, _PP(C.c_int)]),

@@ -70,3 +70,29 @@ void RetinaFace::detect(const Mat &img, float threshold, float /*scales: unused 
     last_.resize(k);
     if (k) memcpy(last_.data(), faces.data(), (size_t)k * sizeof(rf_face));
 }
+
+vector<cv::Mat> RetinaFace::detectAndAlign(const Mat &img, float threshold, int cropSize) {
+    last_.clear();
+    alignMats_.clear();
+    vector<cv::Mat> crops;
+    if (img.empty()) return crops;
+    const uint8_t *ptr = img.data;
+    int rows = img.rows, cols = img.cols, step = (int)(size_t)img.step, count = 0;
+    if (cropSize < 16 || cropSize > 512) throw std::runtime_error("RetinaFace::detectAndAlign: cropSize must be in [16, 512]");
+    const size_t cb = (size_t)cropSize * cropSize * 3;
+    vector<rf_face> faces(maxDet_);
+    vector<uint8_t> buf((size_t)maxDet_ * cb);
+    vector<double> mats((size_t)maxDet_ * 6);
+    check(rf_detect_align_batch(h_, &ptr, &rows, &cols, &step, 1, threshold, faces.data(), maxDet_, &count, cropSize, maxDet_, nullptr,
+                                buf.data(), mats.data()), h_, "RetinaFace::detectAndAlign");
+    int k = count < maxDet_ ? count : maxDet_;
+    last_.resize(k);
+    if (k) memcpy(last_.data(), faces.data(), (size_t)k * sizeof(rf_face));
+    alignMats_.assign(mats.begin(), mats.begin() + (size_t)k * 6);
+    for (int i = 0; i < k; i++) {
+        cv::Mat m(cropSize, cropSize, CV_8UC3);
+        memcpy(m.data, buf.data() + (size_t)i * cb, cb);
+        crops.push_back(m);
+    }
+    return crops;
+}

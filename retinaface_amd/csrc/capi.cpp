@@ -57,6 +57,14 @@ template <typename F> int guarded(rf_engine *h, F &&f) {
     } catch (const std::exception &e) { err = e.what(); return RF_ERR_INVALID_ARG; }
 }
 
+
+rf::AlignRequest align_request(int crop_size, int max_faces, void *d_crops, uint8_t *crops, double *matrices) {
+    rf::AlignRequest rq;
+    rq.crop = crop_size; rq.max_faces = max_faces;
+    rq.d_crops = (uint8_t *)d_crops; rq.crops = crops; rq.matrices = matrices;
+    return rq;
+}
+
 }  // namespace
 
 extern "C" {
@@ -215,9 +223,53 @@ int rf_detect_batch_pad32(rf_handle h, const uint8_t *const *bgr, const int *row
 
 float rf_frame_scale(rf_handle h, int rows, int cols) {
     if (!h || rows <= 0 || cols <= 0) return 1.f;
-    const float sw = (float)cols / (float)h->eng->net_w(), sh = (float)rows / (float)h->eng->net_h();     // RetinaFace.cpp:585-589
-    const float sc = sw > sh ? sw : sh;
-    return sc > 1.f ? sc : 1.f;
+    return rf::frame_scale(rows, cols, h->eng->net_h(), h->eng->net_w());     // RetinaFace.cpp:585-589
+}
+
+int rf_align_matrix(const rf_face *face, float coord_scale, int crop_size, double fwd[6]) {
+    if (!face || !fwd || crop_size < rf::kAlignMinCrop || crop_size > rf::kAlignMaxCrop) return RF_ERR_INVALID_ARG;
+    rf::AlignXform t;
+    rf::align_estimate(face->px, face->py, coord_scale, crop_size, &t);
+    memcpy(fwd, t.fwd, sizeof(t.fwd));
+    return t.valid;
+}
+
+namespace {
+int detect_align_common(rf_handle h, const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n,
+                        bool on_device, float thr, rf_face *out, int cap, int *counts, const rf::AlignRequest &rq) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        bool tr = false;
+        h->eng->detect_align(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, rq);
+        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+}  // namespace
+
+int rf_align_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                          const rf_face *faces, int cap_per_image, const int *counts, const float *coord_scale, int crop_size,
+                          int max_faces, void *d_crops, uint8_t *crops, double *matrices) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        h->eng->align(d_bgr, rows, cols, steps, n, faces, cap_per_image, counts, coord_scale,
+                      align_request(crop_size, max_faces, d_crops, crops, matrices));
+        return RF_OK;
+    });
+}
+
+int rf_detect_align_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                 float threshold, rf_face *out, int cap_per_image, int *counts, int crop_size, int max_faces,
+                                 void *d_crops, uint8_t *crops, double *matrices) {
+    return detect_align_common(h, (const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, out, cap_per_image, counts,
+                               align_request(crop_size, max_faces, d_crops, crops, matrices));
+}
+
+int rf_detect_align_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                          float threshold, rf_face *out, int cap_per_image, int *counts, int crop_size, int max_faces,
+                          void *d_crops, uint8_t *crops, double *matrices) {
+    return detect_align_common(h, bgr, rows, cols, steps, n, false, threshold, out, cap_per_image, counts,
+                               align_request(crop_size, max_faces, d_crops, crops, matrices));
 }
 
 int rf_num_slots(rf_handle h) { return h ? h->eng->num_slots() : RF_ERR_INVALID_ARG; }

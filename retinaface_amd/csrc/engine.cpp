@@ -200,6 +200,8 @@ public:
         for (auto &l : lanes_) free_lane(l);
         for (void *p : dev_allocs_) (void)hipFree(p);
         for (void *p : host_allocs_) (void)hipHostFree(p);
+        if (align_stream_) { (void)hipStreamSynchronize(align_stream_); (void)hipStreamDestroy(align_stream_); }
+        for (DeviceScratch *b : {&align_crops_, &align_mats_, &align_tab_}) b->release();
         arena_.release();
         for (auto &e : prof_ev_) (void)hipEventDestroy(e);
     }
@@ -275,6 +277,88 @@ public:
         if (cap_per_image < 0 || (cap_per_image > 0 && !out)) throw ArgError("wait: out is null");
         DeviceGuard guard(device_);
         wait_impl(ticket, out, cap_per_image, counts, truncated);
+    }
+
+    // -------------------------------------------------------------------------------- face alignment
+    static void check_align_request(const AlignRequest &rq) {
+        if (rq.crop < kAlignMinCrop || rq.crop > kAlignMaxCrop) throw ArgError("crop_size must be in [16, 512]");
+        if (rq.max_faces < 1 || rq.max_faces > kAlignMaxFaces) throw ArgError("max_faces must be in [1, 4096]");
+    }
+
+    void detect_align(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,
+                      float threshold, rf_face *out, int cap_per_image, int *counts, bool *truncated, const AlignRequest &rq) override {
+        check_align_request(rq);
+        if (n < 0 || (n > 0 && (!frames || !rows || !cols || !counts))) throw ArgError("null argument");
+        if ((long)n * rq.max_faces > (1L << 24)) throw ArgError("n x max_faces: more than 2^24 crop slots in one call");
+        DeviceGuard guard(device_);
+        // a super-batch of earlier enqueues that is still being assembled starts now: from here on every launch carries images of
+        // this call only, in call order, so image i of a launch is slot image align_.next_image + i
+        launch_pending();
+        align_.rq = rq;
+        align_.d_crops = rq.d_crops;
+        if (!rq.d_crops && rq.crops) align_.d_crops = align_crops_.reserve((size_t)n * rq.max_faces * rq.crop * rq.crop * 3);
+        align_.d_mats = rq.matrices ? (double *)align_mats_.reserve((size_t)n * rq.max_faces * 6 * sizeof(double)) : nullptr;
+        align_.next_image = 0;
+        align_.on = align_.d_crops || align_.d_mats;
+        struct Off { bool &on; ~Off() { on = false; } } off{align_.on};
+        detect(frames, rows, cols, steps, n, on_device, threshold, out, cap_per_image, counts, truncated);
+        align_.on = false;
+        // every launch of the call has been waited for (its `done` event follows the alignment launch)
+        align_copy_out(rq, align_.d_crops, align_.d_mats, n, counts, opt_.max_detections);
+    }
+
+    void align(const void *const *frames, const int *rows, const int *cols, const int *steps, int n, const rf_face *faces,
+               int cap_per_image, const int *counts, const float *coord_scale, const AlignRequest &rq) override {
+        check_align_request(rq);
+        if (n < 0 || (n > 0 && (!frames || !rows || !cols || !counts || !faces))) throw ArgError("null argument");
+        if (cap_per_image < 1) throw ArgError("cap_per_image must be >= 1");
+        if ((long)n * rq.max_faces > (1L << 24)) throw ArgError("n x max_faces: more than 2^24 crop slots in one call");
+        if (n == 0) return;
+        DeviceGuard guard(device_);
+        const int fpi = std::min(cap_per_image, rq.max_faces);          // records per image that travel to the device
+        // one table: frames | counts | scales | faces (60-byte records)
+        const size_t o_cnt = align256((size_t)n * sizeof(FrameDesc)), o_sc = o_cnt + align256((size_t)n * sizeof(int)),
+                     o_face = o_sc + align256((size_t)n * sizeof(float)), total = o_face + (size_t)n * fpi * sizeof(rf_face);
+        align_host_.assign(total, 0);
+        FrameDesc *fd = (FrameDesc *)align_host_.data();
+        int *cnt = (int *)(align_host_.data() + o_cnt);
+        float *sc = (float *)(align_host_.data() + o_sc);
+        for (int i = 0; i < n; i++) {
+            const int st = steps ? steps[i] : cols[i] * 3;
+            const uint8_t *p = (const uint8_t *)frames[i];
+            check_frame(p, rows[i], cols[i], st);
+            const bool empty = !p || rows[i] <= 0 || cols[i] <= 0;
+            if (!empty && check_residency_) {
+                const int where = foreign_device_of(p);
+                if (where >= 0 && where != device_) throw ArgError("align: frame is resident on another device");
+            }
+            fd[i] = empty ? FrameDesc{nullptr, 0, 0, 0, 0} : FrameDesc{p, rows[i], cols[i], st, 0};
+            cnt[i] = empty ? 0 : std::max(0, std::min(counts[i], fpi));
+            sc[i] = coord_scale ? coord_scale[i] : 1.f;
+            if (cnt[i]) memcpy(align_host_.data() + o_face + (size_t)i * fpi * sizeof(rf_face), faces + (size_t)i * cap_per_image, (size_t)cnt[i] * sizeof(rf_face));
+        }
+        uint8_t *d_tab = align_tab_.reserve(total);
+        uint8_t *d_crops = rq.d_crops;
+        if (!d_crops && rq.crops) d_crops = align_crops_.reserve((size_t)n * rq.max_faces * rq.crop * rq.crop * 3);
+        double *d_mats = rq.matrices ? (double *)align_mats_.reserve((size_t)n * rq.max_faces * 6 * sizeof(double)) : nullptr;
+        if (!d_crops && !d_mats) return;
+        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+        RF_HIP(hipMemcpyAsync(d_tab, align_host_.data(), total, hipMemcpyHostToDevice, align_stream_));
+        for (int base = 0; base < n; base += kAlignImagesPerLaunch) {
+            AlignParams ap;
+            ap.frames = (const FrameDesc *)d_tab + base;
+            ap.faces = d_tab + o_face + (size_t)base * fpi * sizeof(rf_face);
+            ap.face_stride = (int)sizeof(rf_face); ap.faces_per_image = fpi;
+            ap.counts = (const int *)(d_tab + o_cnt) + base;
+            ap.scale = (const float *)(d_tab + o_sc) + base;
+            ap.n = std::min(kAlignImagesPerLaunch, n - base); ap.max_faces = rq.max_faces; ap.crop = rq.crop;
+            ap.first_image = base;
+            ap.crops = d_crops; ap.mats = d_mats;
+            launch_align(align_stream_, ap);
+        }
+        RF_HIP(hipGetLastError());
+        RF_HIP(hipStreamSynchronize(align_stream_));
+        align_copy_out(rq, d_crops, d_mats, n, cnt, rq.max_faces);
     }
 
     void host_register(const void *ptr, size_t bytes) override {
@@ -478,6 +562,7 @@ private:
         uint8_t *h_stage = nullptr, *d_stage = nullptr;
         size_t stage_cap = 0, stage_used = 0;
         float *d_dump[3][3] = {};
+        float *h_align_scale = nullptr;       // detect_align(): pinned, per image of the launch its frame_scale (allocated on first use)
         bool busy = false;                    // a launched super-batch whose results have not been harvested yet
         int n_images = 0;                     // images of the super-batch being assembled / in flight on this lane
         float threshold = 0.f;
@@ -1103,11 +1188,63 @@ private:
         trace_.add(3, tt);
         tt = trace_.on ? HostTrace::now() : 0.0;
         if (eager_timed) RF_HIP(hipEventRecord(s.time_ev[3], s.stream));
+        if (align_.on) launch_lane_align(s, n);      // ordinary launches behind the graph, before `done`: nothing waits in between
         RF_HIP(hipEventRecord(s.done, s.stream));
         trace_.add(4, tt);
         s.busy = true;
         s.launch_seq = ++launch_counter_;
         for (int id : s.tickets) tickets_[id].state = Ticket::LAUNCHED;
+    }
+
+    // The alignment launch of a super-batch of detect_align(): source frames from the launch's own frame table (the first half:
+    // full-resolution frames, also when the stem reads a shrunk canvas), faces and counts from the pinned result block the NMS
+    // kernel of the same stream has just written, each frame's coordinate scale from a pinned per-lane array.
+    void launch_lane_align(Lane &s, int n) {
+        if (!s.h_align_scale) {
+            void *p = nullptr;
+            RF_HIP(hipHostMalloc(&p, std::max<size_t>((size_t)cap_images_ * sizeof(float), 256), hipHostMallocDefault));
+            s.host_allocs.push_back(p);
+            s.h_align_scale = (float *)p;
+        }
+        for (int i = 0; i < n; i++) {
+            const FrameDesc &f = s.h_frames[i];
+            s.h_align_scale[i] = f.ptr ? frame_scale(f.rows, f.cols, net_h_, net_w_) : 1.f;
+        }
+        AlignParams ap;
+        ap.frames = s.d_frames;
+        ap.faces = (const uint8_t *)s.h_out;
+        ap.face_stride = (int)sizeof(Candidate); ap.faces_per_image = opt_.max_detections;
+        ap.counts = s.h_counts;
+        ap.scale = s.h_align_scale;
+        ap.n = n; ap.max_faces = align_.rq.max_faces; ap.crop = align_.rq.crop;
+        ap.first_image = align_.next_image;
+        ap.crops = align_.d_crops; ap.mats = align_.d_mats;
+        launch_align(s.stream, ap);
+        RF_HIP(hipGetLastError());
+        align_.next_image += n;
+    }
+
+    // results of an alignment call to the caller's host buffers: per image the slots that hold faces (the others are unspecified)
+    // (`limit`: the most faces per image the launch can have seen).  A block that is at least half full, and a small matrix block,
+    // travel as one copy instead of one per image.
+    void align_copy_out(const AlignRequest &rq, const uint8_t *d_crops, const double *d_mats, int n, const int *counts, int limit) {
+        const size_t cb = (size_t)rq.crop * rq.crop * 3, mbytes = 6 * sizeof(double);
+        const bool want_crops = rq.crops && d_crops, want_mats = rq.matrices && d_mats;
+        if (!want_crops && !want_mats) return;
+        std::vector<size_t> k(n);
+        size_t used = 0;
+        for (int i = 0; i < n; i++) used += k[i] = (size_t)std::max(0, std::min(std::min(counts[i], rq.max_faces), limit));
+        if (!used) return;
+        const size_t slots = (size_t)n * rq.max_faces;
+        const bool crops_whole = 2 * used >= slots, mats_whole = crops_whole || slots * mbytes <= (1u << 20);
+        if (want_crops && crops_whole) RF_HIP(hipMemcpy(rq.crops, d_crops, slots * cb, hipMemcpyDeviceToHost));
+        if (want_mats && mats_whole) RF_HIP(hipMemcpy(rq.matrices, d_mats, slots * mbytes, hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; i++) {
+            const size_t slot = (size_t)i * rq.max_faces;
+            if (!k[i]) continue;
+            if (want_crops && !crops_whole) RF_HIP(hipMemcpy(rq.crops + slot * cb, d_crops + slot * cb, k[i] * cb, hipMemcpyDeviceToHost));
+            if (want_mats && !mats_whole) RF_HIP(hipMemcpy(rq.matrices + slot * 6, d_mats + slot * 6, k[i] * mbytes, hipMemcpyDeviceToHost));
+        }
     }
 
     // One enqueue / one chunk of a synchronous call joins the super-batch being assembled (or opens the next lane).  Everything
@@ -1336,6 +1473,28 @@ private:
     int cap_images_ = 0;                      // images per launch = max_batch * coalesce
     std::vector<Ticket> tickets_;
     int next_ticket_ = 0;
+
+    // face alignment: device scratch that grows to the largest call seen (every alignment call is synchronous, so nothing is in
+    // flight on a block when it is replaced), the stream of the standalone call, and the request detect_align() has open
+    struct DeviceScratch {
+        uint8_t *ptr = nullptr; size_t cap = 0;
+        uint8_t *reserve(size_t bytes) {
+            if (bytes > cap) {
+                if (ptr) (void)hipFree(ptr);
+                ptr = nullptr; cap = 0;
+                const size_t want = (std::max<size_t>(bytes, 4096) + 4095) / 4096 * 4096;
+                RF_HIP(hipMalloc((void **)&ptr, want));
+                cap = want;
+            }
+            return ptr;
+        }
+        void release() { if (ptr) (void)hipFree(ptr); ptr = nullptr; cap = 0; }
+    };
+    DeviceScratch align_crops_, align_mats_, align_tab_;
+    std::vector<uint8_t> align_host_;
+    hipStream_t align_stream_ = nullptr;
+    static constexpr int kAlignImagesPerLaunch = 32768;       // grid.z limit of one launch
+    struct { bool on = false; AlignRequest rq; uint8_t *d_crops = nullptr; double *d_mats = nullptr; int next_image = 0; } align_;
 
     int last_n_ = 0;
     std::vector<int> last_cand_counts_;

@@ -65,6 +65,22 @@ void preset_base_anchors(const std::vector<float> &ratios, int level, float out[
 // host-only test hook: runs the host half of engine start-up (plan cache or model -> packed image); 1 = served from the cache
 int plan_cache_probe(const std::string &model_dir, const EngineOptions &opt, size_t *arena_bytes);
 
+// `scale` of RetinaFace.cpp:585-589 (rf_frame_scale): what network-input coordinates of a rows x cols frame are multiplied by to
+// land in source-frame pixels; the alignment kernel applies the same float
+inline float frame_scale(int rows, int cols, int net_h, int net_w) {
+    const float sw = (float)cols / (float)net_w, sh = (float)rows / (float)net_h;
+    const float sc = sw > sh ? sw : sh;
+    return sc > 1.f ? sc : 1.f;
+}
+
+// Where the aligned crops of a call go (rf_align_batch_device / rf_detect_align_batch*): the crop of face k of image i is slot
+// i * max_faces + k of d_crops (device) and / or crops (host), its forward matrix the 6 doubles at matrices + 6 * slot
+struct AlignRequest {
+    int crop = 112, max_faces = 0;
+    uint8_t *d_crops = nullptr, *crops = nullptr;
+    double *matrices = nullptr;
+};
+
 class Engine {
 public:
     // opt.devices.size() > 1 gives the image-sharding multi-device engine (multi.cpp), otherwise one single-device engine
@@ -78,6 +94,19 @@ public:
     virtual void detect(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n,
                         bool on_device, float threshold, rf_face *out, int cap_per_image, int *counts,
                         bool *truncated) = 0;
+    // detect() + aligned crops of the faces it finds: the alignment launches follow each detection launch on its stream and read
+    // faces and counts from the device-visible result block (no host synchronisation in between); coordinates are scaled by each
+    // frame's frame_scale, so frames the engine shrank are sampled at full source resolution.  Single-device engines only.
+    virtual void detect_align(const uint8_t *const *, const int *, const int *, const int *, int, bool, float, rf_face *, int, int *,
+                              bool *, const AlignRequest &) {
+        throw Unsupported("face alignment is not available on a multi-device handle");
+    }
+    // aligned crops of faces the caller supplies (faces[i * cap_per_image + k], k < counts[i]) from device-resident frames;
+    // coord_scale: per image, nullptr = 1
+    virtual void align(const void *const *, const int *, const int *, const int *, int, const rf_face *, int, const int *,
+                       const float *, const AlignRequest &) {
+        throw Unsupported("face alignment is not available on a multi-device handle");
+    }
     // asynchronous: frames on host (staged through pinned memory before the call returns, unless the caller registered
     // them with host_register) or on the device
     virtual int enqueue(const void *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,

@@ -7,6 +7,8 @@
 
 #include <stdexcept>
 
+#include "align.h"
+
 namespace rf {
 
 typedef _Float16 half_t;
@@ -175,6 +177,22 @@ void launch_nms(hipStream_t s, const NmsParams &p);
 void launch_resize_area(hipStream_t s, const FrameDesc *src, uint8_t *dst, int n, int net_h, int net_w);
 // The same step in the reference's build without NPP: cv::resize bilinear (RetinaFace.cpp:611-620), OpenCV's fixed-point algorithm.
 void launch_resize_bilinear(hipStream_t s, const FrameDesc *src, uint8_t *dst, int n, int net_h, int net_w);
+
+// ---- K_f: 5-point face alignment -- S x S x 3 u8 BGR crops of the source frames, warped onto the recognition template by the
+//      similarity of align.h; one workgroup per (image, face slot, band of crop rows).  Every pointer is device-visible memory
+//      (the fused call reads faces and counts straight from the pinned result block the NMS kernel wrote).
+struct AlignParams {
+    const FrameDesc *frames;              // [n] SOURCE frames (full resolution, before any shrink)
+    const uint8_t *faces;                 // image i, face k: an rf_face at faces + (i * faces_per_image + k) * face_stride
+    int face_stride, faces_per_image;     // bytes per record (rf_face 60, Candidate 64); records per image
+    const int *counts;                    // [n] faces of each image (clamped to faces_per_image and max_faces here)
+    const float *scale;                   // [n] coordinate scale per image (rf_frame_scale), nullptr = 1
+    int n, max_faces, crop;               // crop slots per image; crop edge S (kAlignMinCrop..kAlignMaxCrop)
+    int first_image;                      // slot of (image i, face k) = (first_image + i) * max_faces + k
+    uint8_t *crops;                       // [slots][S][S][3], or nullptr
+    double *mats;                         // [slots][6] forward matrices (source -> crop), or nullptr
+};
+void launch_align(hipStream_t s, const AlignParams &p);
 
 // LDS bytes / tile geometry chosen for a layer (exposed for tests and DESIGN.md tables)
 struct TileInfo { int th, tw; size_t lds_bytes; int blocks_per_image; };

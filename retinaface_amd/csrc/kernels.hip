@@ -4015,6 +4015,98 @@ int cvt_pk_u8_selfcheck() {
     return r == 1 ? 0 : 1;
 }
 
+// =============================================================================================
+// K_f: 5-point face alignment (no reference equivalent: the reference stops at detection; its downstream is an ArcFace-style
+//      recogniser that takes 112 x 112 crops warped onto the five-landmark template).  One workgroup = one (image, face slot,
+//      band of kAlignBandRows crop rows).  Thread 0 estimates the similarity (align.h: double arithmetic in a fixed order, no
+//      contraction) into LDS; every thread then maps its crop pixels back into the source frame and blends the four taps in
+//      10-bit fixed point (warpAffine-style bilinear, constant zero border).  The source taps are byte gathers: a face's
+//      footprint is a few tens of KB, read once from HBM and then served by L2.  The band is assembled in LDS at the same
+//      16-byte phase as its place in the crop buffer, so the store is whole aligned 16-byte vectors per lane whatever the
+//      alignment of the caller's buffer; the unaligned head and tail go out as bytes.
+//      A slot at or beyond its image's face count exits at once: the count is read here, on the device, which is what lets the
+//      launch follow detection on the same stream without the host looking at the result first.
+// =============================================================================================
+constexpr int kAlignBandRows = 8;
+constexpr int kAlignBandBytes = kAlignBandRows * kAlignMaxCrop * 3;
+
+__global__ __launch_bounds__(kThreads) void align_kernel(AlignParams a) {
+#pragma clang fp contract(off)
+    __shared__ AlignXform xf;
+    __shared__ uint4 band_buf[kAlignBandBytes / 16 + 1];
+    const int band = blockIdx.x, k = blockIdx.y, img = blockIdx.z;
+    int cnt = a.counts[img];
+    cnt = cnt < a.faces_per_image ? cnt : a.faces_per_image;
+    if (k >= cnt) return;
+    const FrameDesc fd = a.frames[img];
+    if (fd.ptr == nullptr || fd.rows <= 0 || fd.cols <= 0) return;
+    const int S = a.crop;
+    const size_t slot = (size_t)(a.first_image + img) * a.max_faces + k;
+    if (threadIdx.x == 0) {
+        const float *f = (const float *)(a.faces + ((size_t)img * a.faces_per_image + k) * a.face_stride);
+        float px[5], py[5];
+        for (int i = 0; i < 5; i++) { px[i] = f[5 + i]; py[i] = f[10 + i]; }
+        align_estimate(px, py, a.scale ? a.scale[img] : 1.f, S, &xf);
+        if (band == 0 && a.mats)
+            for (int i = 0; i < 6; i++) a.mats[slot * 6 + i] = xf.fwd[i];
+    }
+    if (a.crops == nullptr) return;
+    __syncthreads();
+    const int r0 = band * kAlignBandRows;
+    const int nrows = S - r0 < kAlignBandRows ? S - r0 : kAlignBandRows;
+    const int npix = nrows * S, nbytes = npix * 3;
+    uint8_t *dst = a.crops + slot * (size_t)S * S * 3 + (size_t)r0 * S * 3;
+    const int mis = (int)((uintptr_t)dst & 15);
+    uint8_t *lds = (uint8_t *)band_buf + mis;
+    const int valid = xf.valid;
+    const double ia = xf.ia, ib = xf.ib, mpx = xf.mpx, mpy = xf.mpy, mqx = xf.mqx, mqy = xf.mqy;
+    const double xmax = (double)(fd.cols + 1), ymax = (double)(fd.rows + 1);
+    for (int p = threadIdx.x; p < npix; p += kThreads) {
+        const int v = r0 + p / S, u = p % S;
+        unsigned acc[3] = {0u, 0u, 0u};
+        const double du = (double)u - mqx, dv = (double)v - mqy;
+        const double x = (ia * du - ib * dv) + mpx;
+        const double y = (ib * du + ia * dv) + mpy;
+        if (valid && x > -2.0 && x < xmax && y > -2.0 && y < ymax) {
+            const long long X = (long long)floor(x * 1024.0 + 0.5), Y = (long long)floor(y * 1024.0 + 0.5);
+            const int x0 = (int)(X >> 10), y0 = (int)(Y >> 10);
+            const unsigned fx = (unsigned)(X & 1023), fy = (unsigned)(Y & 1023);
+#pragma unroll
+            for (int t = 0; t < 4; t++) {
+                const int xx = x0 + (t & 1), yy = y0 + (t >> 1);
+                if (xx < 0 || xx >= fd.cols || yy < 0 || yy >= fd.rows) continue;
+                const unsigned w = ((t & 1) ? fx : 1024u - fx) * ((t >> 1) ? fy : 1024u - fy);
+                const uint8_t *sp = fd.ptr + (size_t)yy * fd.step + (size_t)xx * 3;
+                acc[0] += w * sp[0]; acc[1] += w * sp[1]; acc[2] += w * sp[2];
+            }
+#pragma unroll
+            for (int c = 0; c < 3; c++) acc[c] = (acc[c] + (1u << 19)) >> 20;
+        }
+        lds[3 * p + 0] = (uint8_t)acc[0]; lds[3 * p + 1] = (uint8_t)acc[1]; lds[3 * p + 2] = (uint8_t)acc[2];
+    }
+    __syncthreads();
+    // [0, head) bytes up to the first 16-byte boundary of the destination, whole vectors, then the tail
+    int head = (16 - mis) & 15;
+    head = head < nbytes ? head : nbytes;
+    const int nvec = (nbytes - head) / 16, tail0 = head + nvec * 16;
+    if ((int)threadIdx.x < head) dst[threadIdx.x] = lds[threadIdx.x];
+    const uint4 *lv = band_buf + (mis + head) / 16;
+    uint4 *gv = (uint4 *)(dst + head);
+    for (int i = threadIdx.x; i < nvec; i += kThreads) gv[i] = lv[i];
+    if ((int)threadIdx.x < nbytes - tail0) dst[tail0 + threadIdx.x] = lds[tail0 + threadIdx.x];
+}
+
+void launch_align(hipStream_t s, const AlignParams &p) {
+    if (p.n <= 0 || p.max_faces <= 0) return;
+    if (p.crop < kAlignMinCrop || p.crop > kAlignMaxCrop || p.max_faces > kAlignMaxFaces || p.n > 65535)
+        throw Unsupported("align: crop size, face slots or images per launch out of range");
+    const int slots = p.max_faces < p.faces_per_image ? p.max_faces : p.faces_per_image;
+    if (slots <= 0) return;
+    // matrices only: one band per face is enough
+    dim3 grid(p.crops ? (p.crop + kAlignBandRows - 1) / kAlignBandRows : 1, slots, p.n);
+    hipLaunchKernelGGL(align_kernel, grid, dim3(kThreads), 0, s, p);
+}
+
 #ifdef RF_KERNEL_TRACE
 extern "C" int rf_trace_select(int kernel_id, unsigned grid) {
     static unsigned long long zeros[kTraceBlocks * kTraceSlots];

@@ -32,6 +32,28 @@ class Detection:
         return np.array([self.score, *self.rect, *self.xs, *self.ys], dtype=np.float32)
 
 
+def _face_rows(faces) -> np.ndarray:
+    """(k, 15) float32 rows from an array, a list of rows or a list of Detection."""
+    if isinstance(faces, np.ndarray):
+        return np.ascontiguousarray(faces, np.float32).reshape(-1, 15)
+    rows = [f.as_row() if isinstance(f, Detection) else np.asarray(f, np.float32) for f in faces]
+    return np.stack(rows).astype(np.float32).reshape(-1, 15) if rows else np.zeros((0, 15), np.float32)
+
+
+def align_matrix(face, coord_scale: float = 1.0, crop_size: int = 112):
+    """rf_align_matrix (host only, no GPU): (valid, forward matrix) of one face -- a Detection or 15 floats (score, box,
+    5 landmark x, 5 landmark y).  The matrix maps source-frame pixels to crop pixels, row-major 2 x 3 float64; it is all zero
+    for an invalid face (landmarks that do not span a plane)."""
+    lib = _lib.load_library()
+    row = _face_rows([face])[0]
+    f = rf_face.from_buffer_copy(row.tobytes())
+    m = (C.c_double * 6)()
+    st = lib.rf_align_matrix(C.byref(f), float(coord_scale), int(crop_size), m)
+    if st < 0:
+        raise _lib.RFError(st, "rf_align_matrix: bad argument (crop_size must be in [16, 512])")
+    return bool(st), np.array(m, np.float64).reshape(2, 3)
+
+
 def _faces_to_array(buf, n: int) -> np.ndarray:
     return np.ctypeslib.as_array(C.cast(buf, C.POINTER(C.c_float)), shape=(n, 15)).copy()
 
@@ -150,6 +172,95 @@ class RetinaFace:
         r, c = (C.c_int * n)(*rows), (C.c_int * n)(*cols)
         s = (C.c_int * n)(*(steps if steps is not None else [3 * x for x in cols]))
         return self._run(self._lib.rf_detect_batch_device, p, r, c, s, n, threshold)
+
+    # ------------------------------------------------------------------ face alignment
+    def align(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], faces, *, steps: Optional[Sequence[int]] = None,
+              coord_scale: Optional[Sequence[float]] = None, crop_size: int = 112, max_faces: Optional[int] = None,
+              d_crops: Optional[int] = None, host: bool = True):
+        """rf_align_batch_device: aligned crops of faces the caller supplies, from device-resident frames.  faces[i]: the faces of
+        image i (a (k, 15) array, rows of 15 floats or Detections).  coord_scale[i] multiplies image i's landmarks into source
+        pixels (frame_scale() for detect results of an oversize frame; default 1).  Returns (crops, matrices): per image a
+        (k, S, S, 3) uint8 array (None with host=False) and a (k, 2, 3) float64 array, k = min(len(faces[i]), max_faces).
+        d_crops: a device buffer of n * max_faces * 3 * S * S bytes that receives the crops as well (slot i * max_faces + k)."""
+        n = len(ptrs)
+        rows_f = [_face_rows(f) for f in faces]
+        if len(rows_f) != n:
+            raise ValueError("faces must hold one entry per frame")
+        cap = max(1, max((len(r) for r in rows_f), default=1))
+        mf = int(max_faces) if max_faces else cap
+        flat = np.zeros((n, cap, 15), np.float32)
+        counts = (C.c_int * max(n, 1))()
+        for i, r in enumerate(rows_f):
+            flat[i, :len(r)] = r
+            counts[i] = len(r)
+        p = (C.c_void_p * max(n, 1))(*ptrs)
+        r_, c_ = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
+        s_ = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        cs = None
+        if coord_scale is not None:
+            cs = (C.c_float * max(n, 1))(*[float(v) for v in coord_scale])
+        S = int(crop_size)
+        crops = np.zeros((n, mf, S, S, 3), np.uint8) if host else None
+        mats = np.zeros((n, mf, 2, 3), np.float64)
+        _lib.check(self._lib.rf_align_batch_device(
+            self._h, p, r_, c_, s_, n, flat.ctypes.data_as(C.POINTER(rf_face)), cap, counts, cs, S, mf,
+            C.c_void_p(d_crops) if d_crops else None, crops.ctypes.data if host else None,
+            mats.ctypes.data_as(C.POINTER(C.c_double))), self._h)
+        ks = [min(counts[i], mf) for i in range(n)]
+        return ([crops[i, :ks[i]] for i in range(n)] if host else None), [mats[i, :ks[i]] for i in range(n)]
+
+    def detect_aligned(self, imgs: Sequence[np.ndarray], threshold: float = 0.5, crop_size: int = 112,
+                       max_faces: Optional[int] = None):
+        """rf_detect_align_batch: detectBatchImages + the aligned crop of every face, in one call.  Returns (detections, crops,
+        matrices): crops[i] is (k, S, S, 3) uint8 and matrices[i] (k, 2, 3) float64 for the first k = min(faces, max_faces)
+        detections of image i (score order); frames larger than the net are sampled at their full resolution."""
+        n = len(imgs)
+        if n == 0:
+            return [], [], []
+        ptrs = (C.c_void_p * n)()
+        rows, cols, steps = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
+        keep = []
+        for i, im in enumerate(imgs):
+            if im is None or im.size == 0:
+                ptrs[i], rows[i], cols[i], steps[i] = None, 0, 0, 0
+                continue
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
+            if im.strides[2] != 1 or im.strides[1] != 3:
+                im = np.ascontiguousarray(im)
+            keep.append(im)
+            ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
+        return self._run_aligned(self._lib.rf_detect_align_batch, ptrs, rows, cols, steps, n, threshold, crop_size, max_faces, None, True)
+
+    def detect_aligned_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], threshold: float = 0.5,
+                              steps: Optional[Sequence[int]] = None, crop_size: int = 112, max_faces: Optional[int] = None,
+                              d_crops: Optional[int] = None, host: bool = True):
+        """rf_detect_align_batch_device: detect_aligned for frames resident in device memory.  d_crops: a device buffer of
+        n * max_faces * 3 * S * S bytes that receives the crops (slot i * max_faces + k); host=False skips the host copy of
+        the crops (crops is then None)."""
+        n = len(ptrs)
+        if n == 0:
+            return [], [], []
+        p = (C.c_void_p * n)(*ptrs)
+        r, c = (C.c_int * n)(*rows), (C.c_int * n)(*cols)
+        s = (C.c_int * n)(*(steps if steps is not None else [3 * x for x in cols]))
+        return self._run_aligned(self._lib.rf_detect_align_batch_device, p, r, c, s, n, threshold, crop_size, max_faces, d_crops, host)
+
+    def _run_aligned(self, fn, ptrs, rows, cols, steps, n, threshold, crop_size, max_faces, d_crops, host):
+        cap = self.max_detections
+        mf = int(max_faces) if max_faces else cap
+        S = int(crop_size)
+        out = (rf_face * (n * cap))()
+        counts = (C.c_int * n)()
+        crops = np.zeros((n, mf, S, S, 3), np.uint8) if host else None
+        mats = np.zeros((n, mf, 2, 3), np.float64)
+        st = _lib.check(fn(self._h, ptrs, rows, cols, steps, n, float(threshold), out, cap, counts, S, mf,
+                           C.c_void_p(d_crops) if d_crops else None, crops.ctypes.data if host else None,
+                           mats.ctypes.data_as(C.POINTER(C.c_double))), self._h)
+        self.truncated = st == _lib.RF_ERR_TRUNCATED
+        dets = self._collect(out, counts, n, cap)
+        ks = [min(len(d), mf) for d in dets]
+        return dets, ([crops[i, :ks[i]] for i in range(n)] if host else None), [mats[i, :ks[i]] for i in range(n)]
 
     def enqueue_device(self, ptrs, rows, cols, threshold: float = 0.5) -> int:
         n = len(ptrs)
