@@ -11,8 +11,10 @@
 
 #include "copier.h"
 #include "knobs.h"
+#include "net.h"
 #include "pack.h"
-#include "weights.h"
+#include "residency.h"
+#include "staging.h"
 
 namespace rf {
 
@@ -105,20 +107,24 @@ namespace {
 // lanes overlap on the GPU (most kernels of a batch-8 pass fill only a fraction of the 256 CUs); weights are shared.
 constexpr int kMaxCoalesce = 256;       // enqueues merged into one launch: a batch-1 caller still fills a 256-image super-batch
 
-template <typename T>
-class EngineImpl final : public Engine, private WeightPack<T> {
-    typedef WeightPack<T> WP;
-    using typename WP::GemmW;
-    using typename WP::DwW;
-    using WP::kNone;
-    using WP::arena_; using WP::c0_w_; using WP::c0_b_; using WP::c0_hi_; using WP::stem_dw_; using WP::stem2_dw_; using WP::stem_pw_;
-    using WP::stem2_pw_; using WP::aggr_a_lat_; using WP::aggr_a_up_; using WP::act_scale_; using WP::dw_w_; using WP::pw_w_; using WP::lat_w_;
-    using WP::aggr_w_; using WP::ssh_w_; using WP::head_a_; using WP::mult_ptr;
+// Everything the engine knows about its element type (filled by make_engine<T>): the scheduler, staging and result paths are the
+// same code for fp32, fp16 and int8.
+struct NetKind {
+    size_t elem_bytes = 0;
+    const char *tag = "";                                          // RF_HOST_TRACE report
+    bool cvt_selfcheck = false;                                    // int8: the requantising epilogues' rounding probe runs at create
+    void (*to_float)(const void *raw, size_t n, float *dst) = nullptr;      // stored elements -> float (debug_activation)
+    Arena *arena = nullptr;                                        // the weight image of the pack that build_net's closure owns
+    int head_a = 2;                                                // anchors per cell the model's heads carry
+    std::function<void(const Plan &, const NetSite &, LaneNet *)> build_net;
+};
+
+class EngineImpl final : public Engine {
 public:
-    // `plan` may be a skeleton (no weights): everything weight-related comes packed in `pack` (built from the model or read from
-    // the plan cache, weights.h)
-    EngineImpl(const Plan &plan, WeightPack<T> &&pack, float nms, const EngineOptions &opt, const std::vector<float> &ratios)
-        : WeightPack<T>(std::move(pack)) {
+    // `plan` may be a skeleton (no weights): everything weight-related comes packed in the WeightPack behind `kind` (built from
+    // the model or read from the plan cache, weights.h)
+    EngineImpl(const Plan &plan, NetKind kind, float nms, const EngineOptions &opt, const std::vector<float> &ratios)
+        : kind_(std::move(kind)) {
         opt_ = opt;
         nms_threshold_ = nms;
         ratios_ = ratios;
@@ -158,12 +164,12 @@ public:
         stage_pieces_ = knob(K_SYNC_SPLIT) == 0 ? 1 : knob(K_SYNC_PIECES);      // RF_SYNC_PIECES: measurement knob of the A/B
         check_residency_ = ndev > 1 || force_scatter_;
         DeviceGuard guard(device_);                  // the caller's current device is put back when construction ends
-        if (sizeof(T) == 1) {
+        if (kind_.cvt_selfcheck) {
             const int chk = cvt_pk_u8_selfcheck();
             if (chk < 0) throw HipError("int8: the v_cvt_pk_u8_f32 rounding probe could not run on this device (allocation, launch or copy failed)");
             if (chk > 0) throw Unsupported("int8: v_cvt_pk_u8_f32 on this device does not round to nearest even / saturate as the requantising epilogues assume");
         }
-        try { arena_.upload(); } catch (const std::exception &e) { throw HipError(e.what()); }
+        try { kind_.arena->upload(); } catch (const std::exception &e) { throw HipError(e.what()); }
         // Lanes are built on first use: a caller that only makes synchronous calls of <= max_batch images keeps re-using lane 0 and
         // never pays for the other lanes' activation buffers (~13 MB per 448 x 448 image in fp16 x the super-batch size).  Lane 0
         // is built now; if its buffers do not fit the device (a small or shared GPU) the super-batch is halved until they do.
@@ -195,14 +201,14 @@ public:
 
     ~EngineImpl() override {
         DeviceGuard guard(device_);
-        trace_.report(sizeof(T) == 1 ? "int8" : sizeof(T) == 2 ? "fp16" : "fp32");
+        trace_.report(kind_.tag);
         for (auto &r : registered_) if (r.owned) (void)hipHostUnregister((void *)r.base);
         for (auto &l : lanes_) free_lane(l);
         for (void *p : dev_allocs_) (void)hipFree(p);
         for (void *p : host_allocs_) (void)hipHostFree(p);
         if (align_stream_) { (void)hipStreamSynchronize(align_stream_); (void)hipStreamDestroy(align_stream_); }
         for (DeviceScratch *b : {&align_crops_, &align_mats_, &align_tab_}) b->release();
-        arena_.release();
+        kind_.arena->release();
         for (auto &e : prof_ev_) (void)hipEventDestroy(e);
     }
 
@@ -403,13 +409,13 @@ public:
         DeviceGuard guard(device_);
         static const char *kinds[3] = {"face_rpn_cls_prob_reshape_stride", "face_rpn_bbox_pred_stride",
                                        "face_rpn_landmark_pred_stride"};
-        const int chans[3] = {2 * head_a_, 4 * head_a_, 10 * head_a_};
+        const int chans[3] = {2 * kind_.head_a, 4 * kind_.head_a, 10 * kind_.head_a};
         Lane &l = lanes_[last_lane_];
         for (int si = 0; si < 3; si++)
             for (int k = 0; k < 3; k++) {
-                if (blob != std::string(kinds[k]) + std::to_string(strides_[si])) continue;
+                if (blob != std::string(kinds[k]) + std::to_string(kStrides[si])) continue;
                 if (image < 0 || image >= last_n_ || last_first_image_ < 0) throw ArgError("image index out of range");
-                size_t hw = (size_t)(net_h_ / strides_[si]) * (net_w_ / strides_[si]);
+                size_t hw = (size_t)(net_h_ / kStrides[si]) * (net_w_ / kStrides[si]);
                 size_t cnt = hw * chans[k];
                 if (!dst) return (long)cnt;
                 if (cap < cnt) throw ArgError("destination too small");
@@ -450,10 +456,12 @@ public:
         if (!dst) return (long)cnt;
         if (cap < cnt) throw ArgError("destination too small");
         RF_HIP(hipStreamSynchronize(l.stream));
-        std::vector<T> tmp(cnt);
-        RF_HIP(hipMemcpy(tmp.data(), (const T *)ai.ptr + (size_t)(last_first_image_ + image) * cnt, cnt * sizeof(T),
-                         hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < cnt; i++) dst[i] = Cast<T>::to(tmp[i]) * (raw || ai.scale.empty() ? 1.f : ai.scale[i % ai.c]);      // NHWC: channel = i % c
+        const size_t eb = kind_.elem_bytes;
+        std::vector<uint8_t> tmp(cnt * eb);
+        RF_HIP(hipMemcpy(tmp.data(), (const uint8_t *)ai.ptr + (size_t)(last_first_image_ + image) * cnt * eb, cnt * eb, hipMemcpyDeviceToHost));
+        kind_.to_float(tmp.data(), cnt, dst);
+        if (!raw && !ai.scale.empty())
+            for (size_t i = 0; i < cnt; i++) dst[i] *= ai.scale[i % ai.c];      // NHWC: channel = i % c
         return (long)cnt;
     }
 
@@ -510,7 +518,7 @@ public:
             if (names) names[k] = l.ops[k].name.c_str();
             if (kernels) kernels[k] = l.ops[k].kernel.c_str();
             if (avg_ms) avg_ms[k] = (float)(sum[k] / iters);
-            if (alg_bytes) alg_bytes[k] = n * (l.ops[k].alg_u8_in + sizeof(T) * (l.ops[k].alg_elems_in + l.ops[k].alg_elems_out));
+            if (alg_bytes) alg_bytes[k] = n * (l.ops[k].alg_u8_in + kind_.elem_bytes * (l.ops[k].alg_elems_in + l.ops[k].alg_elems_out));
             if (macs) macs[k] = n * l.ops[k].macs;
         }
         return (int)nops;
@@ -520,12 +528,12 @@ public:
         if (n < 0 || (cap > 0 && !bytes)) throw ArgError("null argument");
         const Lane &l = lanes_[0];
         for (size_t k = 0; k < l.ops.size() && (int)k < cap; k++)
-            bytes[k] = n * (l.ops[k].alg_u8_in + sizeof(T) * (l.ops[k].hbm_elems_in + l.ops[k].hbm_elems_out));
+            bytes[k] = n * (l.ops[k].alg_u8_in + kind_.elem_bytes * (l.ops[k].hbm_elems_in + l.ops[k].hbm_elems_out));
         return (int)l.ops.size();
     }
 
 private:
-    struct Lane {
+    struct Lane : LaneNet {                   // + the ops, activations and dump buffers build_net fills (net.h)
         bool built = false;
         std::vector<void *> dev_allocs, host_allocs;      // what build_lane allocated for this lane
         hipStream_t stream = nullptr;
@@ -540,9 +548,6 @@ private:
         hipEvent_t done = nullptr;
         std::map<int, hipGraphExec_t> graphs;
         std::set<int> warmed;
-        std::map<std::string, ActInfo> acts;
-        std::vector<OpInfo> ops;              // launch order
-        size_t first_post = 0;                // index of the first post-processing launch (heads)
         // pinned host staging of the per-launch table: [0,mb) source frames, [mb,2mb) what the stem reads, then RunParams;
         // ONE small H2D copy per launch puts it in HBM (a launch covers up to max_batch*coalesce images, so the copy is
         // amortised; reading it from the kernels over PCIe instead cost every workgroup a PCIe round trip)
@@ -561,7 +566,6 @@ private:
         // it back to back and cross PCIe as one DMA per enqueue
         uint8_t *h_stage = nullptr, *d_stage = nullptr;
         size_t stage_cap = 0, stage_used = 0;
-        float *d_dump[3][3] = {};
         float *h_align_scale = nullptr;       // detect_align(): pinned, per image of the launch its frame_scale (allocated on first use)
         bool busy = false;                    // a launched super-batch whose results have not been harvested yet
         int n_images = 0;                     // images of the super-batch being assembled / in flight on this lane
@@ -645,13 +649,9 @@ private:
         return oldest;
     }
 
-    static constexpr bool kInt8 = sizeof(T) == 1;
-    typedef typename DwWeightT<T>::type DWT;
-
     void build_lane(Lane &L, const Plan &plan) {
         const int mb = cap_images_;           // images per launch: max_batch * coalesce
         const int H = net_h_, W = net_w_;
-        const double P = (double)H * W;
         RF_HIP(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
         for (auto &e : L.time_ev) RF_HIP(hipEventCreate(&e));
         RF_HIP(hipEventCreateWithFlags(&L.done, hipEventDisableTiming));
@@ -674,277 +674,17 @@ private:
         L.d_cand = dalloc<Candidate>((size_t)mb * opt_.max_candidates);
         L.d_canvas = dalloc<uint8_t>((size_t)mb * H * W * 3);
 
-        auto act = [&](const std::string &name, int h, int w, int c) {
-            T *p = dalloc<T>((size_t)mb * h * w * c);
-            auto sc = act_scale_.find(name);
-            L.acts[name] = ActInfo{p, h, w, c, sc == act_scale_.end() ? std::vector<float>() : sc->second};
-            return p;
-        };
-        // activations: one buffer per reference blob that survives fusion (288 GB of HBM: nothing is recycled)
-        int h = H / 2, w = W / 2;
-        T *cur = nullptr;
-        size_t first_block = 0;
-        int c = 8;
-        if constexpr (std::is_same<T, half_t>::value) {
-            // fp16 engine: preprocess + conv0 + blocks 0 and 1 (conv1..conv4) are ONE launch (stem2_kernel): the 224^2 x 16 map of
-            // the net never exists in HBM
-            const auto &b0 = plan.blocks[0], &b1 = plan.blocks[1];
-            const int h4 = H / 4, w4 = W / 4;
-            T *out = act(b1.pw.out_blob, h4, w4, b1.pw.cout);
-            Stem2Params sp;
-            sp.frames = L.d_frames + mb; sp.out = out;
-            sp.w0 = arena_.template ptr<half_t>(c0_hi_); sp.b0 = arena_.template ptr<float>(WP::c0_b_mma_);
-            sp.w0_raw = arena_.template ptr<half_t>(WP::c0_raw_);
-            sp.dw0_w = arena_.template ptr<float>(stem_dw_.w); sp.dw0_b = arena_.template ptr<float>(stem_dw_.b);
-            sp.pw0_w = arena_.template ptr<half_t>(stem_pw_.w); sp.pw0_b = arena_.template ptr<float>(WP::stem2_c2_b_);
-            sp.c2_floor = arena_.template ptr<uint32_t>(WP::stem2_c2_floor_); sp.c3_floor = arena_.template ptr<uint32_t>(WP::stem2_c3_floor_);
-            sp.dw1_mma = arena_.template ptr<uint32_t>(stem2_dw_.mma); sp.dw1_b = arena_.template ptr<float>(stem2_dw_.b);
-            sp.pw1_w = arena_.template ptr<half_t>(stem2_pw_.w); sp.pw1_b = arena_.template ptr<float>(stem2_pw_.b);
-            sp.n = 0; sp.net_h = H; sp.net_w = W;
-            OpInfo op;
-            op.name = "pre+" + plan.conv0.name + "+" + b0.dw.name + "+" + b0.pw.name + "+" + b1.dw.name + "+" + b1.pw.name;
-            op.kernel = "stem2";
-            op.alg_u8_in = 3.0 * P;
-            // layer-wise accounting: every covered layer's input + output elements, fused or not
-            op.alg_elems_in = 8.0 * h * w + 8.0 * h * w + 16.0 * h * w + 16.0 * h4 * w4;                       // conv1, conv2, conv3, conv4 inputs
-            op.alg_elems_out = 8.0 * h * w + 8.0 * h * w + 16.0 * h * w + 16.0 * h4 * w4 + 32.0 * h4 * w4;     // conv0 .. conv4 outputs
-            op.macs = (plan.conv0.macs_per_out_pixel() + b0.dw.macs_per_out_pixel() + b0.pw.macs_per_out_pixel()) * h * w +
-                      (b1.dw.macs_per_out_pixel() + b1.pw.macs_per_out_pixel()) * h4 * w4;
-            op.hbm_elems_out = 32.0 * h4 * w4;                        // the frame in (alg_u8_in), the 32-channel net/4 map out
-            op.launch = [sp](hipStream_t s, int n) { Stem2Params q = sp; q.n = n; launch_stem2(s, q); };
-            L.ops.push_back(op);
-            cur = out; c = b1.pw.cout; first_block = 2; h = h4; w = w4;
-            if (plan.blocks.size() > 3 && plan.blocks[2].dw.cout == 32 && plan.blocks[2].pw.cout == 32 &&
-                plan.blocks[3].dw.stride == 2 && plan.blocks[3].pw.cout == 64) {
-                // blocks 2 and 3 (conv5..conv8) as ONE launch (dwpw2_kernel): the 112^2 x 32 map between them stays in LDS
-                const auto &ba = plan.blocks[2], &bb = plan.blocks[3];
-                T *out2 = act(bb.pw.out_blob, h / 2, w / 2, bb.pw.cout);
-                DwPw2Params dp;
-                dp.in = cur; dp.out = out2;
-                dp.dwa_mma = arena_.template ptr<uint32_t>(dw_w_[2].mma); dp.dwa_b = arena_.template ptr<float>(dw_w_[2].b);
-                dp.pwa_w = arena_.template ptr<half_t>(pw_w_[2].w); dp.pwa_b = arena_.template ptr<float>(pw_w_[2].b);
-                dp.dwb_mma = arena_.template ptr<uint32_t>(dw_w_[3].mma); dp.dwb_b = arena_.template ptr<float>(dw_w_[3].b);
-                dp.pwb_w = arena_.template ptr<half_t>(pw_w_[3].w); dp.pwb_b = arena_.template ptr<float>(pw_w_[3].b);
-                dp.n = 0; dp.hin = h; dp.win = w;
-                OpInfo o2;
-                o2.name = ba.dw.name + "+" + ba.pw.name + "+" + bb.dw.name + "+" + bb.pw.name;
-                o2.kernel = "dwpw2<32,32,64>";
-                const double pa = (double)h * w, pb = (double)(h / 2) * (w / 2);
-                o2.alg_elems_in = 32.0 * pa + 32.0 * pa + 32.0 * pa + 32.0 * pb;          // dw A, pw A, dw B, pw B inputs (layer-wise)
-                o2.alg_elems_out = 32.0 * pa + 32.0 * pa + 32.0 * pb + 64.0 * pb;
-                o2.macs = (ba.dw.macs_per_out_pixel() + ba.pw.macs_per_out_pixel()) * pa + (bb.dw.macs_per_out_pixel() + bb.pw.macs_per_out_pixel()) * pb;
-                o2.hbm_elems_in = 32.0 * pa; o2.hbm_elems_out = 64.0 * pb;
-                o2.launch = [dp](hipStream_t s, int n) { DwPw2Params q = dp; q.n = n; launch_dwpw2(s, q); };
-                L.ops.push_back(o2);
-                cur = out2; c = bb.pw.cout; first_block = 4; h /= 2; w /= 2;
-            }
-        } else if constexpr (sizeof(T) == 1) {
-            // int8 engine: preprocess + conv0 + the first depthwise/pointwise
-            // block are ONE launch (stem_kernel); it computes in fp16 and stores its 16-channel output in the engine's storage type
-            const auto &blk = plan.blocks[0];
-            T *out = act(blk.pw.out_blob, h, w, blk.pw.cout);
-            StemParams<T> sp;
-            sp.frames = L.d_frames + mb; sp.out = out;
-            sp.w0 = arena_.template ptr<half_t>(c0_hi_); sp.b0 = arena_.template ptr<float>(WP::c0_b_mma_);
-            sp.w0_raw = arena_.template ptr<half_t>(WP::c0_raw_);
-            sp.dw_w = arena_.template ptr<float>(stem_dw_.w); sp.dw_b = arena_.template ptr<float>(stem_dw_.b);
-            sp.pw_w = arena_.template ptr<half_t>(stem_pw_.w); sp.pw_b = arena_.template ptr<float>(stem_pw_.b);
-            sp.pw_m = mult_ptr(stem_pw_);
-            sp.n = 0; sp.net_h = H; sp.net_w = W;
-            OpInfo op;
-            op.name = "pre+" + plan.conv0.name + "+" + blk.dw.name + "+" + blk.pw.name;
-            op.kernel = "stem";
-            op.alg_u8_in = 3.0 * P;
-            op.alg_elems_in = 8.0 * h * w + 8.0 * h * w;                       // dw input, pw input
-            op.alg_elems_out = 8.0 * h * w + 8.0 * h * w + 16.0 * h * w;       // conv0, dw, pw outputs
-            op.macs = (plan.conv0.macs_per_out_pixel() + blk.dw.macs_per_out_pixel() + blk.pw.macs_per_out_pixel()) * h * w;
-            op.hbm_elems_out = 16.0 * h * w;
-            op.launch = [sp](hipStream_t s, int n) { StemParams<T> q = sp; q.n = n; launch_stem<T>(s, q); };
-            L.ops.push_back(op);
-            cur = out; c = blk.pw.cout; first_block = 1;
-        } else if constexpr (sizeof(T) == 2) {
-            throw Unsupported("fp16 engine without stem2: a probe-build configuration (RF_STEM2=0)");
-        } else {
-            cur = act(plan.conv0.out_blob, h, w, 8);
-            OpInfo op;
-            op.name = "pre+" + plan.conv0.name;
-            op.kernel = "conv0";
-            op.alg_u8_in = 3.0 * P;
-            op.alg_elems_out = 8.0 * h * w;
-            op.macs = plan.conv0.macs_per_out_pixel() * h * w;
-            op.hbm_elems_out = 8.0 * h * w;
-            const float *wp = arena_.template ptr<float>(c0_w_), *bp = arena_.template ptr<float>(c0_b_);
-            const FrameDesc *fr = L.d_frames + mb;
-            T *o = cur;
-            op.launch = [=](hipStream_t s, int n) { launch_conv0<T>(s, fr, o, wp, bp, n, H, W); };
-            L.ops.push_back(op);
-        }
-        // FPN tap -> lateral index: block 4 (stride 8) -> lateral[2], block 10 (stride 16) -> [1], block 12 (stride 32) -> [0]
-        T *lat[3] = {nullptr, nullptr, nullptr};
-        for (size_t i = first_block; i < plan.blocks.size(); i++) {
-            const auto &blk = plan.blocks[i];
-            int ho = h / blk.dw.stride, wo = w / blk.dw.stride;
-            T *out = act(blk.pw.out_blob, ho, wo, blk.pw.cout);
-            if (dwpw_tile_info<T>(c, blk.pw.cout, blk.dw.stride, true, ho, wo).th == 0)
-                throw ModelError("no kernel instance for depthwise/pointwise block " + blk.dw.name);
-            DwPwParams<T> p;
-            p.in = cur; p.out = out;
-            p.dw_w = arena_.template ptr<DWT>(dw_w_[i].w); p.dw_b = arena_.template ptr<float>(dw_w_[i].b);
-            if (dw_w_[i].mma) p.dw_mma = arena_.template ptr<uint32_t>(dw_w_[i].mma);
-            if (dw_w_[i].m != kNone) p.dw_m = arena_.template ptr<float>(dw_w_[i].m);
-            p.pw_w = arena_.template ptr<T>(pw_w_[i].w); p.pw_b = arena_.template ptr<float>(pw_w_[i].b); p.pw_m = mult_ptr(pw_w_[i]);
-            p.n = 0; p.hin = h; p.win = w; p.hout = ho; p.wout = wo;
-            p.cin = c; p.cout = blk.pw.cout; p.stride = blk.dw.stride; p.has_dw = true;
-            OpInfo op;
-            op.name = blk.dw.name + "+" + blk.pw.name;
-            op.kernel = "dwpw<" + std::to_string(c) + "," + std::to_string(blk.pw.cout) + ",s" + std::to_string(blk.dw.stride) + ">";
-            op.alg_elems_in = (double)c * h * w + (double)c * ho * wo;
-            op.alg_elems_out = (double)c * ho * wo + (double)blk.pw.cout * ho * wo;
-            op.macs = (blk.dw.macs_per_out_pixel() + blk.pw.macs_per_out_pixel()) * ho * wo;
-            op.hbm_elems_in = (double)c * h * w; op.hbm_elems_out = (double)blk.pw.cout * ho * wo;
-            const int li = i == 4 ? 2 : i == 10 ? 1 : i == 12 ? 0 : -1;
-            if (li >= 0) {          // the lateral 1x1 is computed from this block's output tile while it is in LDS
-                const FoldedConv &lf = plan.lateral[li];
-                lat[li] = act(lf.out_blob, ho, wo, 64);
-                p.lat_w = arena_.template ptr<T>(lat_w_[li].w); p.lat_b = arena_.template ptr<float>(lat_w_[li].b); p.lat_out = lat[li];
-                p.lat_m = mult_ptr(lat_w_[li]);
-                op.name += "+" + lf.name;
-                op.kernel.insert(op.kernel.size() - 1, ",lat");
-                op.alg_elems_in += (double)blk.pw.cout * ho * wo;
-                op.alg_elems_out += 64.0 * ho * wo;
-                op.hbm_elems_out += 64.0 * ho * wo;
-                op.macs += lf.macs_per_out_pixel() * ho * wo;
-            }
-            op.launch = [p](hipStream_t s, int n) { DwPwParams<T> q = p; q.n = n; launch_dwpw<T>(s, q); };
-            L.ops.push_back(op);
-            cur = out; h = ho; w = wo; c = blk.pw.cout;
-        }
-        // FPN: P3 = c3 lateral; P2 / P1 = aggr conv with "lateral + bilinear x2 upsample(coarser)" fused into its input staging
-        T *feat[3];
-        feat[0] = lat[0];
-        for (int i = 0; i < 2; i++) {
-            int fh = H / strides_[i + 1], fw = W / strides_[i + 1];
-            feat[i + 1] = act(plan.aggr[i].out_blob, fh, fw, 64);
-            Conv3Params<T> p;
-            p.in = lat[i + 1]; p.in_ld = 64; p.in_off = 0; p.up = feat[i];
-            p.w = arena_.template ptr<T>(aggr_w_[i].w); p.b = arena_.template ptr<float>(aggr_w_[i].b); p.m = mult_ptr(aggr_w_[i]);
-            p.a_lat = aggr_a_lat_[i]; p.a_up = aggr_a_up_[i];
-            p.blend_fp32 = knob(K_BLEND_FP32) != 0;            // read once per lane (not per launch)
-            p.out0 = feat[i + 1]; p.ld0 = 64; p.off0 = 0; p.n0 = 64; p.out1 = nullptr; p.ld1 = 0; p.off1 = 0;
-            p.n = 0; p.h = fh; p.w_ = fw; p.cin = 64; p.cout = 64;
-            OpInfo op;
-            op.name = std::string(i == 0 ? "rf_c3_upsampling" : "rf_c2_upsampling") + "+" + plan.aggr[i].name;
-            {
-                TileInfo ti = conv3x3_tile_info<T>(64, 64, fh, fw);
-                op.kernel = "conv3x3<64,64," + std::to_string(ti.th) + "x" + std::to_string(ti.tw) + ",up>";
-            }
-            op.alg_elems_in = 64.0 * (fh / 2) * (fw / 2) + 64.0 * fh * fw;     // deconv input + conv input
-            op.alg_elems_out = 64.0 * fh * fw + 64.0 * fh * fw;               // deconv output + conv output
-            op.macs = plan.aggr[i].macs_per_out_pixel() * fh * fw + 16.0 * 64 * (fh / 2) * (fw / 2);
-            op.hbm_elems_in = 64.0 * (fh / 2) * (fw / 2) + 64.0 * fh * fw; op.hbm_elems_out = 64.0 * fh * fw;
-            op.launch = [p](hipStream_t s, int n) { Conv3Params<T> q = p; q.n = n; launch_conv3x3<T>(s, &q, 1); };
-            L.ops.push_back(op);
-        }
-        // SSH context modules: each of the three merged convs is ONE launch covering strides 32, 16 and 8
-        struct Level3 { Conv3Params<T> p[3]; };
-        Level3 lv_a, lv_b, lv_c;
-        OpInfo op_a, op_b, op_c, op_h;
-        // fp16 / int8: conv_b and conv_c of the context module are ONE launch (ssh_tail_kernel); context_conv3_1 stays in LDS
-        constexpr bool fuse_tail = sizeof(T) <= 2;
-        struct Tail3 { SshTailParams<T> p[3]; } tl;
-        struct HeadLevels { HeadParams<T> p[3]; } hl;
-        int anchor_off = 0;
-        for (int i = 0; i < 3; i++) {
-            const SshModule &m = plan.ssh[i];
-            int fh = H / strides_[i], fw = W / strides_[i];
-            std::string pre = "rf_c" + std::to_string(3 - i) + "_det_";
-            T *cat = act(pre + "concat_relu", fh, fw, 64);
-            T *ctx1 = act(pre + "context_conv1_relu", fh, fw, 16);
-            T *ctx31 = fuse_tail ? nullptr : act(pre + "context_conv3_1_relu", fh, fw, 16);
-            auto fill = [&](Conv3Params<T> &p, OpInfo &op, const FoldedConv &f, const GemmW &gw, const T *in, int cin, T *o0,
-                            int ld0, int off0, int n0, T *o1, int ld1, int off1, int nlayers) {
-                p.in = in; p.in_ld = cin; p.in_off = 0; p.up = nullptr;
-                p.w = arena_.template ptr<T>(gw.w); p.b = arena_.template ptr<float>(gw.b); p.m = mult_ptr(gw);
-                p.out0 = o0; p.ld0 = ld0; p.off0 = off0; p.n0 = n0; p.out1 = o1; p.ld1 = ld1; p.off1 = off1;
-                p.n = 0; p.h = fh; p.w_ = fw; p.cin = cin; p.cout = f.cout;
-                op.name += (op.name.empty() ? "" : " | ") + f.name;
-                op.alg_elems_in += (double)nlayers * cin * fh * fw;   // each merged sibling reads the input once, layer-wise
-                op.alg_elems_out += (double)f.cout * fh * fw;
-                op.hbm_elems_in += (double)cin * fh * fw;              // merged siblings share ONE read of the input
-                op.hbm_elems_out += (double)f.cout * fh * fw;
-                op.macs += f.macs_per_out_pixel() * fh * fw;
-            };
-            fill(lv_a.p[i], op_a, m.conv_a, ssh_w_[i][0], feat[i], 64, cat, 64, 0, 32, ctx1, 16, 0, 2);
-            fill(lv_b.p[i], op_b, m.conv_b, ssh_w_[i][1], ctx1, 16, cat, 64, 32, 16, ctx31, 16, 0, 2);
-            fill(lv_c.p[i], op_c, m.conv_c, ssh_w_[i][2], ctx31, 16, cat, 64, 48, 16, nullptr, 0, 0, 1);
-            if constexpr (sizeof(T) <= 2) {
-                SshTailParams<T> &tp = tl.p[i];
-                tp.in = ctx1; tp.cat = cat; tp.n = 0; tp.h = fh; tp.w_ = fw;
-                tp.wb = arena_.template ptr<T>(ssh_w_[i][1].w); tp.bb = arena_.template ptr<float>(ssh_w_[i][1].b); tp.mb = mult_ptr(ssh_w_[i][1]);
-                tp.wc = arena_.template ptr<T>(ssh_w_[i][2].w); tp.bc = arena_.template ptr<float>(ssh_w_[i][2].b); tp.mc = mult_ptr(ssh_w_[i][2]);
-            }
-            HeadParams<T> &hp = hl.p[i];
-            hp.in = cat; hp.w = arena_.template ptr<T>(ssh_w_[i][3].w); hp.b = arena_.template ptr<float>(ssh_w_[i][3].b);
-            hp.m = mult_ptr(ssh_w_[i][3]);
-            hp.n = 0; hp.h = fh; hp.w_ = fw; hp.stride = strides_[i]; hp.anchor_offset = anchor_off;
-            hp.num_anchors = na_;
-            memset(hp.base, 0, sizeof(hp.base));
-            preset_base_anchors(ratios_, i, hp.base);
-            hp.net_h = H; hp.net_w = W; hp.params = L.d_params;
-            hp.cand = L.d_cand; hp.cand_count = L.d_cand_count; hp.cap = opt_.max_candidates;
-            hp.dump_prob = hp.dump_bbox = hp.dump_lmk = nullptr;
-            if (opt_.keep_outputs) {
-                const int chans[3] = {2 * head_a_, 4 * head_a_, 10 * head_a_};
-                for (int k = 0; k < 3; k++) L.d_dump[i][k] = dalloc<float>((size_t)mb * chans[k] * fh * fw);
-                hp.dump_prob = L.d_dump[i][0]; hp.dump_bbox = L.d_dump[i][1]; hp.dump_lmk = L.d_dump[i][2];
-            }
-            op_h.name += (op_h.name.empty() ? "" : " | ") + m.head.name;
-            op_h.alg_elems_in += 3.0 * 64 * fh * fw;
-            op_h.alg_elems_out += 16.0 * head_a_ * fh * fw;
-            op_h.hbm_elems_in += 64.0 * fh * fw;                       // the concat tensor in; candidates out: a few KB
-            op_h.macs += m.head.macs_per_out_pixel() * fh * fw;
-            anchor_off += na_ * fh * fw;
-        }
-        op_a.launch = [lv_a](hipStream_t s, int n) { Level3 q = lv_a; for (auto &p : q.p) p.n = n; launch_conv3x3<T>(s, q.p, 3); };
-        op_b.launch = [lv_b](hipStream_t s, int n) { Level3 q = lv_b; for (auto &p : q.p) p.n = n; launch_conv3x3<T>(s, q.p, 3); };
-        op_c.launch = [lv_c](hipStream_t s, int n) { Level3 q = lv_c; for (auto &p : q.p) p.n = n; launch_conv3x3<T>(s, q.p, 3); };
-        op_a.kernel = "conv3x3<64,48,8x8>";
-        op_b.kernel = "conv3x3<16,32,8x8>";
-        op_c.kernel = "conv3x3<16,16,8x8>";
-        op_h.kernel = "head";
-        L.ops.push_back(op_a);
-        if (fuse_tail) {
-            if constexpr (sizeof(T) <= 2) {
-                OpInfo op_t;
-                op_t.name = op_b.name + " | " + op_c.name;
-                op_t.kernel = "ssh_tail<16,32,16>";
-                op_t.alg_elems_in = op_b.alg_elems_in + op_c.alg_elems_in;       // layer-wise accounting, fused or not
-                op_t.alg_elems_out = op_b.alg_elems_out + op_c.alg_elems_out;
-                op_t.macs = op_b.macs + op_c.macs;
-                op_t.hbm_elems_in = op_b.hbm_elems_in;                 // context_conv1 in; context_conv3_1 stays in LDS
-                op_t.hbm_elems_out = op_b.hbm_elems_out + op_c.hbm_elems_out - op_c.hbm_elems_in;      // concat[32:64]: 16 + 16 channels
-                op_t.launch = [tl](hipStream_t s, int n) { Tail3 q = tl; for (auto &p : q.p) p.n = n; launch_ssh_tail<T>(s, q.p, 3); };
-                L.ops.push_back(op_t);
-            }
-        } else {
-            L.ops.push_back(op_b);
-            L.ops.push_back(op_c);
-        }
-        L.first_post = L.ops.size();
-        op_h.name += " +softmax+decode";
-        op_h.launch = [hl](hipStream_t s, int n) { HeadLevels q = hl; for (auto &p : q.p) p.n = n; launch_head<T>(s, q.p, 3); };
-        L.ops.push_back(op_h);
-        {
-            NmsParams np;
-            np.cand = L.d_cand; np.cand_count = L.d_cand_count; np.cap = opt_.max_candidates; np.params = L.d_params;
-            np.out = L.h_out; np.out_count = L.h_counts; np.out_cand_count = L.h_counts + mb;
-            np.max_det = opt_.max_detections; np.n = 0;
-            OpInfo op;
-            op.name = "sort+nms";
-            op.kernel = "nms";
-            op.launch = [np](hipStream_t s, int n) { NmsParams q = np; q.n = n; launch_nms(s, q); };
-            L.ops.push_back(op);
-        }
+        NetSite site;
+        site.mb = mb; site.net_h = H; site.net_w = W;
+        site.frames = L.d_frames + mb;
+        site.d_params = L.d_params;
+        site.d_cand = L.d_cand; site.d_cand_count = L.d_cand_count;
+        site.h_out = L.h_out; site.h_counts = L.h_counts;
+        site.max_candidates = opt_.max_candidates; site.max_detections = opt_.max_detections; site.num_anchors = na_;
+        site.keep_outputs = opt_.keep_outputs;
+        site.ratios = &ratios_;
+        site.dalloc = [this](size_t bytes) { return (void *)dalloc<uint8_t>(bytes); };
+        kind_.build_net(plan, site, &L);
     }
 
     // ------------------------------------------------------------------------------------------ run
@@ -976,19 +716,7 @@ private:
     // engine's kernels (its own device's memory, or pinned / managed host memory); >= 0: the ordinal of ANOTHER device of the
     // node -- the frame is then scattered to this device over xGMI before the launch (submit()).  Anything the runtime does not
     // know as device-accessible memory is refused here instead of faulting inside a kernel.
-    // The answer is cached per ALLOCATION (hipMemGetAddressRange: base + size of the allocation the pointer lies in), so a camera
-    // ring or a frame tensor costs one runtime lookup, not one per frame per call (hipPointerGetAttributes takes the runtime's
-    // allocation-map lock: ~1 us x 256 frames per super-batch).  Round 4 cached per 2 MiB page and never looked again: a buffer
-    // freed and re-allocated under the same address on another device kept its old answer.  Now (1) an entry covers
-    // exactly one allocation, so two small allocations sharing a page cannot alias; (2) an entry is re-validated against the
-    // runtime once it is older than kResidencyTtlUs -- base, size and owner must still match or the entry is dropped and the
-    // pointer looked up afresh -- which bounds the lifetime of a stale answer to 2 ms of wall clock and costs one runtime call
-    // per 2 ms per allocation; (3) rf_invalidate_residency() drops the cache at once for callers that free or re-home frame
-    // buffers while the handle lives (documented in include/retinaface_amd.h).  Host / managed memory and pointers the runtime
-    // rejects are never cached.
-    static constexpr double kResidencyTtlUs = 2000.0;
-    struct Residency { uintptr_t base; size_t bytes; int where; int owner; double checked_us; };
-    static double now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+    // The answer is cached per allocation and re-validated every kResidencyTtlUs (residency.h).
 
     // one runtime lookup; returns false for host / managed memory (answer in *where, not cacheable)
     bool lookup_residency(const uint8_t *p, Residency *out) {
@@ -1000,7 +728,7 @@ private:
         }
         if (attr.type == hipMemoryTypeUnregistered) throw ArgError("device frame pointer is unregistered host memory");
         out->owner = attr.device;
-        out->checked_us = now_us();
+        out->checked_us = HostTrace::now();
         if (attr.type == hipMemoryTypeHost || attr.type == hipMemoryTypeManaged) { out->where = -1; out->base = 0; out->bytes = 0; return false; }
         out->where = attr.device == device_ ? (force_scatter_ ? device_ : -1) : attr.device;
         hipDeviceptr_t base = nullptr;
@@ -1015,34 +743,7 @@ private:
     }
 
     int foreign_device_of(const uint8_t *p) {
-        const uintptr_t a = (uintptr_t)p;
-        auto it = residency_.upper_bound(a);
-        if (it != residency_.begin()) {
-            --it;
-            Residency &r = it->second;
-            if (a >= r.base && a < r.base + r.bytes) {
-                if (now_us() - r.checked_us <= kResidencyTtlUs) return r.where;
-                Residency fresh;                                  // stale: the allocation must still be the one that was cached
-                const bool cacheable = lookup_residency(p, &fresh);
-                if (cacheable && fresh.base == r.base && fresh.bytes == r.bytes && fresh.owner == r.owner) { r.checked_us = fresh.checked_us; return r.where; }
-                residency_.erase(it);
-                residency_revalidation_misses_++;
-                if (cacheable) insert_residency(fresh);
-                return fresh.where;
-            }
-        }
-        Residency fresh;
-        if (lookup_residency(p, &fresh)) insert_residency(fresh);
-        return fresh.where;
-    }
-    // a new allocation may overlap stale entries of freed ones: drop every entry that intersects it (both the miss path and the
-    // stale-revalidation path come through here)
-    void insert_residency(const Residency &fresh) {
-        if (residency_.size() > 4096) residency_.clear();
-        auto lo = residency_.lower_bound(fresh.base);
-        if (lo != residency_.begin()) { auto pv = std::prev(lo); if (pv->second.base + pv->second.bytes > fresh.base) lo = pv; }
-        while (lo != residency_.end() && lo->second.base < fresh.base + fresh.bytes) lo = residency_.erase(lo);
-        residency_[fresh.base] = fresh;
+        return residency_.where((uintptr_t)p, [this](uintptr_t a, Residency *out) { return lookup_residency((const uint8_t *)a, out); }, HostTrace::now);
     }
 
     bool is_registered(const uint8_t *p, size_t bytes) const {
@@ -1323,7 +1024,7 @@ private:
                 hipStream_t up = s.stream;
                 // staged (pageable) frames: measured 69-74 k -> 76-81 k images/s at 448 x 448 with the second stream (48.6 GB/s = 0.9 of
                 // the box's pinned-copy rate); frames in rf_host_register'ed memory got SLOWER with it (75.6 k -> 69.4 k) and stay on one
-                if (s.copy2 && !on_device && !all_registered && (s.uploads++ & 1)) { up = s.copy2; s.copy2_used = true; }
+                if (!on_device && !all_registered && (s.uploads++ & 1)) { up = s.copy2; s.copy2_used = true; }
                 if (on_device) {
                     // the batch split of a multi-GPU node: frames resident on another device cross xGMI as one peer copy each
                     // (SDMA, on this lane's stream: it overlaps the compute of the super-batches in flight on the other lanes)
@@ -1332,16 +1033,12 @@ private:
                     // sharded batch is one SDMA descriptor instead of 32 (round 6; RF_SCATTER_PER_FRAME=1 keeps one copy per frame for the A/B).
                     for (int i = 0; i < n; i++) {
                         if (empty[i] || src_dev[i] < 0) continue;
-                        size_t run = (size_t)(rows[i] - 1) * steps[i] + (size_t)cols[i] * 3;
-                        int j = i + 1;
-                        if (!scatter_per_frame_ && steps[i] == cols[i] * 3)
-                            while (j < n && !empty[j] && src_dev[j] == src_dev[i] && steps[j] == cols[j] * 3 && frames[j] == frames[i] + run &&
-                                   off[j] == off[i] + run)
-                                run += (size_t)rows[j] * cols[j] * 3, j++;
-                        RF_HIP(hipMemcpyPeerAsync(dbase + off[i], device_, frames[i], src_dev[i], run, s.stream));
-                        scattered_frames_ += j - i;
+                        const FrameRun run = frame_run(frames, rows, cols, steps, empty.data(), off.data(), i, n, scatter_per_frame_,
+                                                       [&](int a, int b) { return src_dev[a] == src_dev[b]; });
+                        RF_HIP(hipMemcpyPeerAsync(dbase + off[i], device_, frames[i], src_dev[i], run.bytes, s.stream));
+                        scattered_frames_ += run.end - i;
                         peer_copies_++;
-                        i = j - 1;
+                        i = run.end - 1;
                     }
                 } else if (all_registered) {
                     // caller buffers pinned with rf_host_register: the DMA engine reads them in place.  Frames with dense rows
@@ -1365,29 +1062,11 @@ private:
                         copier_->run(copy_jobs_);          // the caller's buffers are free again when this returns
                         RF_HIP(hipMemcpyAsync(dbase, hbase, stage_need, hipMemcpyHostToDevice, up));
                     } else {
-                        // piece boundaries are byte positions of the staging block cut at row granularity: a piece is whole frames and / or a
-                        // row range of a frame, so ONE large frame (1280 x 896 = 3.4 MB) is pipelined as well
-                        size_t sent = 0;
-                        int i = 0, r = 0;                          // next frame / next row of it to stage
-                        for (int pc = 0; pc < pieces; pc++) {
-                            const size_t goal = pc == pieces - 1 ? stage_need : stage_need * (pc + 1) / pieces;
-                            copy_jobs_.clear();
-                            size_t end = sent;
-                            while (i < n && end < goal) {
-                                if (empty[i]) { i++; r = 0; continue; }
-                                const size_t rb = (size_t)cols[i] * 3, at = off[i] + (size_t)r * rb;
-                                int take = rows[i] - r;
-                                if (at + (size_t)take * rb > goal) take = (int)std::max<size_t>(1, (goal - std::min(goal, at) + rb - 1) / rb);
-                                take = std::min(take, rows[i] - r);
-                                copy_jobs_.push_back(ParallelCopier::Job{hbase + at, frames[i] + (size_t)r * steps[i], rb, (size_t)take, (size_t)steps[i]});
-                                end = at + (size_t)take * rb;
-                                r += take;
-                                if (r == rows[i]) { i++; r = 0; }
-                            }
-                            if (copy_jobs_.empty()) continue;
-                            copier_->run(copy_jobs_);      // the caller's rows of this piece are free again when this returns
-                            RF_HIP(hipMemcpyAsync(dbase + sent, hbase + sent, end - sent, hipMemcpyHostToDevice, up));
-                            sent = end;
+                        // staging.h cuts the block into the pieces; while piece k crosses the bus the host stages piece k + 1
+                        for (const StagePiece &pc : stage_piece_plan(frames, rows, cols, steps, empty.data(), off.data(), n, stage_need, pieces, hbase)) {
+                            if (pc.jobs.empty()) continue;
+                            copier_->run(pc.jobs);         // the caller's rows of this piece are free again when this returns
+                            RF_HIP(hipMemcpyAsync(dbase + pc.sent, hbase + pc.sent, pc.end - pc.sent, hipMemcpyHostToDevice, up));
                         }
                         staged_pieces_ += pieces;
                     }
@@ -1412,18 +1091,14 @@ private:
                            const std::vector<size_t> &off, int a, int b, uint8_t *dbase, hipStream_t up) {
         for (int i = a; i < b; i++) {
             if (empty[i]) continue;
-            const size_t fb = (size_t)rows[i] * cols[i] * 3;
             if (steps[i] != cols[i] * 3) {
                 RF_HIP(hipMemcpy2DAsync(dbase + off[i], (size_t)cols[i] * 3, frames[i], (size_t)steps[i], (size_t)cols[i] * 3,
                                         (size_t)rows[i], hipMemcpyHostToDevice, up));
                 continue;
             }
-            size_t run = fb;
-            int j = i + 1;
-            while (j < b && !empty[j] && steps[j] == cols[j] * 3 && frames[j] == frames[i] + run && off[j] == off[i] + run)
-                run += (size_t)rows[j] * cols[j] * 3, j++;
-            RF_HIP(hipMemcpyAsync(dbase + off[i], frames[i], run, hipMemcpyHostToDevice, up));
-            i = j - 1;
+            const FrameRun run = frame_run(frames, rows, cols, steps, empty.data(), off.data(), i, b, false, [](int, int) { return true; });
+            RF_HIP(hipMemcpyAsync(dbase + off[i], frames[i], run.bytes, hipMemcpyHostToDevice, up));
+            i = run.end - 1;
         }
     }
 
@@ -1461,15 +1136,14 @@ private:
     std::vector<HostRange> registered_;       // rf_host_register ranges (pinned caller memory; owned = pinned by this engine)
     std::vector<hipEvent_t> prof_ev_;
     std::vector<void *> dev_allocs_, host_allocs_;
-    const int strides_[3] = {32, 16, 8};
 
+    NetKind kind_;
     Plan plan_;                               // skeleton (shapes, names): what build_lane needs when a lane is built later
     Lane *building_ = nullptr;
     std::vector<Lane> lanes_;
     int next_lane_ = 0, last_lane_ = 0, last_first_image_ = 0, pending_lane_ = -1;
     unsigned long long launch_counter_ = 0;
-    std::map<uintptr_t, Residency> residency_;          // allocation base -> where it lives (foreign_device_of)
-    long residency_revalidation_misses_ = 0;            // cached entries whose allocation had changed when they were re-validated
+    ResidencyCache residency_;                // where the allocations behind device frame pointers live (foreign_device_of)
     int cap_images_ = 0;                      // images per launch = max_batch * coalesce
     std::vector<Ticket> tickets_;
     int next_ticket_ = 0;
@@ -1552,7 +1226,16 @@ static std::unique_ptr<Engine> make_engine(const std::string &model_dir, const s
                          "heads carry " + std::to_string(plan.anchors_per_cell));
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw HipError("no HIP device available");
-    return std::unique_ptr<Engine>(new EngineImpl<T>(plan, std::move(pack), nms, opt, ratios));
+    auto wp = std::make_shared<WeightPack<T>>(std::move(pack));
+    NetKind kind;
+    kind.elem_bytes = sizeof(T);
+    kind.tag = sizeof(T) == 1 ? "int8" : sizeof(T) == 2 ? "fp16" : "fp32";
+    kind.cvt_selfcheck = sizeof(T) == 1;
+    kind.to_float = [](const void *raw, size_t n, float *dst) { for (size_t i = 0; i < n; i++) dst[i] = Cast<T>::to(((const T *)raw)[i]); };
+    kind.arena = &wp->arena_;
+    kind.head_a = wp->head_a_;
+    kind.build_net = [wp](const Plan &p, const NetSite &site, LaneNet *net) { build_net<T>(p, *wp, site, net); };
+    return std::unique_ptr<Engine>(new EngineImpl(plan, std::move(kind), nms, opt, ratios));
 }
 
 // test hook (host only): build / validate the plan cache of one model without creating an engine

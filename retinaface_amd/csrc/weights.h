@@ -6,7 +6,7 @@
 // "<name>.cache", later runs deserialize it): save() / load() write and read "<stem>.<precision>.rfplan" next to the model --
 // keyed by a hash of the model files, the precision, the packing version and the fused-stem variant -- so a warm start is
 // read file -> hipMemcpy, with no parse, no BN fold and no packing.  The Plan travels in the file as a skeleton (layer names,
-// shapes, strides: what build_lane needs), without weights.
+// shapes, strides: what build_net needs), without weights.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -263,6 +263,30 @@ def test_staging_copier_and_shard_rule_host_unit(tmp_path):
     assert out.returncode == 0 and "ok" in out.stdout, out.stdout
 
 
+def _host_unit(tmp_path, name):
+    exe = str(tmp_path / name)
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe,
+                           os.path.join(ROOT, "tests", "csrc", name + ".cpp")])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and "ok" in out.stdout, (out.stdout[-2000:], out.stderr[-2000:])
+
+
+def test_residency_cache_host_unit_under_sanitizers(tmp_path):
+    """csrc/residency.h, the engine's per-allocation cache of where device frame pointers live, against a fake runtime lookup that counts its
+    calls and a fake clock: young hits cost no lookup, stale hits are re-validated (kept if base, size and owner still match, else dropped,
+    counted and replaced), a new allocation evicts exactly the entries it overlaps, one byte past an allocation misses, non-cacheable answers
+    are never stored, the 4098th entry empties the map first, clear forgets everything."""
+    _host_unit(tmp_path, "test_residency")
+
+
+def test_staging_runs_and_piece_plan_host_unit_under_sanitizers(tmp_path):
+    """csrc/staging.h on 300 seeded batches of 1-32 frames (empty, pitched, 1x1 to 1280x896, scattered or back to back in one buffer): the runs
+    of the peer / registered uploads partition the eligible frames in order, are contiguous in source and staging block, dense and maximal
+    (length one with the per-frame flag); the piece plan of a pipelined synchronous upload covers every row of every frame exactly once for
+    1, 2, 3, 4, 7 and 64 pieces, with back-to-back byte ranges that contain their own jobs; one 1280x896 frame is cut into several pieces."""
+    _host_unit(tmp_path, "test_staging")
+
+
 def test_bench_self_launches_n_ranks_and_gathers_results():
     """`bench.py --gpus 2` with no launcher around it must start 2 ranks itself (round 1 ignored N), run the sharded loop with
     the result all_gather inside the timed region and report n_gpus == 2.  --dry swaps the HIP engine for a stub and RCCL for

@@ -3,7 +3,7 @@
 
 The fp16 engine keeps fp32 accumulators and rounds to fp16 exactly where an activation is STORED (LDS tile or HBM)
 and where a weight is packed.  This tool replays the engine's fused-op sequence (same BN folding: the host plan via
-rf_plan_folded, same fusion boundaries as engine.cpp::build_lane) with PyTorch-CPU fp32 convolutions and a switchable
+rf_plan_folded, same fusion boundaries as net.cpp::build_net) with PyTorch-CPU fp32 convolutions and a switchable
 `round to fp16` at every one of those points, decodes with the oracle's literal decode/NMS and reports, per face,
 1 - IoU against the all-fp32 run.  It answers: which rounding points carry the box error of the fp16 engine, and which
 cheap subset has to be kept wider to get every face inside north_star's 1e-3 IoU.
@@ -130,7 +130,7 @@ class Sim:
         return acts, wts
 
 
-# storage point of the simulation -> the reference blob the engine's debug accessor serves (engine.cpp act() names)
+# storage point of the simulation -> the reference blob the engine's debug accessor serves (net.cpp act() names)
 def blob_of_point(p: str):
     if p == "conv0":
         return "mobilenet0_relu0_fwd", None

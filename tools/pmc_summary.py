@@ -10,7 +10,7 @@ import sys
 
 
 def descriptor(mangled: str) -> str:
-    """Same kernel-instance string as rf_profile reports (engine.cpp OpInfo.kernel); template tails added in later rounds
+    """Same kernel-instance string as rf_profile reports (net.cpp fills OpInfo.kernel); template tails added in later rounds
     (padded-row / wave-split booleans) are ignored."""
     m = re.search(r"dwpw_kernelI(?:DF16_|f|a)Li(\d+)ELi(\d+)ELi(\d+)ELb(\d)ELi(\d+)ELi(\d+)ELb(\d)E", mangled)
     if m:
