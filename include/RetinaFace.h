@@ -11,7 +11,8 @@
  *   - a second constructor takes rf_options (precision, net size, batch, model stem) -- the reference bakes
  *     these in at compile time / in prototxt line 7.
  *   - errors throw std::runtime_error instead of abort()/exit(0).
- *   - detectAndAlign() also returns each face as an aligned crop, the input of the recogniser that usually follows.
+ *   - detectAndAlign() also returns each face as an aligned crop, the input of the recogniser that usually follows;
+ *     detectFaceBatch() returns the faces of a batch of frames as one dense tensor in the recogniser's layout and number format.
  */
 #ifndef RETINAFACE_H
 #define RETINAFACE_H
@@ -68,6 +69,15 @@ public:
     vector<cv::Mat> detectAndAlign(const Mat &img, float threshold = 0.5, int cropSize = 112);
     const vector<double> &alignMatrices() const { return alignMats_; }
 
+    /* additive: detectBatchImages() + the faces it finds as ONE dense, packed, normalised tensor (rf_detect_face_batch): the bytes of
+       min(total, spec.capacity) faces of 3 x S x S elements each in the spec's format; face k of image i is packed face
+       faceBatchOffsets()[i] + k, faceBatchMatrices() holds 6 doubles per packed face.  Fills lastBatchResult().
+       faceBatchTruncated(): more faces than spec.capacity (the first `capacity` are returned). */
+    vector<uint8_t> detectFaceBatch(const vector<cv::Mat> &imgs, float threshold, const rf_face_batch_spec &spec);
+    const vector<int> &faceBatchOffsets() const { return faceOffsets_; }
+    const vector<double> &faceBatchMatrices() const { return faceMats_; }
+    bool faceBatchTruncated() const { return faceTruncated_; }
+
     /* `scale` of RetinaFace.cpp:585-589: multiply lastResult() coordinates by it for source-frame pixels (:732-739, commented) */
     float frameScale(const Mat &img) const { return rf_frame_scale(h_, img.rows, img.cols); }
 
@@ -87,6 +97,9 @@ private:
     vector<FaceDetectInfo> last_;
     vector<vector<FaceDetectInfo>> lastBatch_;
     vector<double> alignMats_;
+    vector<int> faceOffsets_;
+    vector<double> faceMats_;
+    bool faceTruncated_ = false;
 };
 
 #endif /* RETINAFACE_H */

@@ -194,6 +194,62 @@ int rf_detect_align_batch(rf_handle h, const uint8_t *const *bgr, const int *row
                           float threshold, rf_face *out, int cap_per_image, int *counts, int crop_size, int max_faces,
                           void *d_crops, uint8_t *crops, double *matrices);
 
+/* ---- Face batches: the aligned faces of one call as ONE dense tensor in a recogniser's layout and number format, written by the
+ * engine directly (the u8 slot array of the calls above is never materialised).  DESIGN.md "Face batches" holds the definition;
+ * every result is byte-exact against it (tests/face_batch_ref.py restates it in numpy):
+ *   packed order  m_i = min(counts[i], max_faces); offsets[0] = 0, offsets[i+1] = offsets[i] + m_i; face k of image i is packed
+ *                 face j = offsets[i] + k (images in call order, faces in score order); total = offsets[n].  The tensor holds the
+ *                 packed faces j < min(total, capacity); nothing at or beyond that many faces is written.  total > capacity:
+ *                 the call returns RF_ERR_TRUNCATED; detections, offsets (the true numbers) and the first `capacity` faces are valid.
+ *                 (A detect call holds at most max_detections records per image: m_i is clamped to that as well.)
+ *   value         q = the u8 value of crop pixel (u, v), source channel b of B, G, R, exactly as the crops above (0 everywhere
+ *                 for an invalid face).  Output channel c takes source channel c (rgb == 0) or 2 - c (rgb == 1).
+ *                 RF_FACES_U8_HWC: q itself, layout [j][v][u][c]; mean / scale unused.
+ *                 RF_FACES_F32_CHW: ((float)q - mean[c]) * scale[c], one fp32 subtract then one fp32 multiply, layout [j][c][v][u].
+ *                 RF_FACES_F16_CHW: the same value converted to IEEE half, round to nearest even.
+ *                 All three scale entries 0: mean 127.5 and scale 1/128 for every channel.
+ *   matrices      packed the same way: matrices[j*6 .. j*6+5] holds the doubles rf_align_matrix gives for that face. */
+typedef enum rf_face_format { RF_FACES_U8_HWC = 0, RF_FACES_F16_CHW = 1, RF_FACES_F32_CHW = 2 } rf_face_format;
+typedef struct rf_face_batch_spec {
+    uint32_t struct_size;   /* sizeof(rf_face_batch_spec) */
+    int32_t crop_size;      /* 16..512, 0 = 112 */
+    int32_t format;         /* rf_face_format */
+    int32_t rgb;            /* 0 = frame order (BGR), 1 = RGB */
+    float mean[3], scale[3];/* per OUTPUT channel */
+    int32_t max_faces;      /* per image, 1..4096; 0 = the engine's max_detections */
+    int32_t capacity;       /* packed faces the tensor holds, >= 1 */
+} rf_face_batch_spec;
+
+/* Host only, no GPU, no handle.  rf_face_batch_plan: what a call with these per-image counts packs -- fills offsets (n + 1 ints, may
+ * be NULL) and bytes_per_face (may be NULL) and returns total (NOT clamped to capacity), or RF_ERR_INVALID_ARG for a bad
+ * struct_size / crop_size / format / max_faces / capacity, a non-finite mean or scale, or a negative count.  max_faces == 0
+ * stands for the default max_detections (256) here.
+ * rf_face_value_table: the 256 output values (q = 0..255) of output channel `channel` (0..2) in the spec's element type (u8, half
+ * or float) -- the same code the kernel runs, compiled for the host. */
+long rf_face_batch_plan(const rf_face_batch_spec *spec, const int *counts, int n, int *offsets, size_t *bytes_per_face);
+int rf_face_value_table(const rf_face_batch_spec *spec, int channel, void *out256);
+
+/* rf_detect_batch_device + the face batch of what it finds, in one call.  Detection runs exactly as in rf_detect_batch_device (out /
+ * counts / rf_last_anchor_indices are the same bytes); the packing and the tensor launches follow each detection launch on its
+ * stream with no host synchronisation in between, and each frame's rf_frame_scale is applied as in rf_detect_align_batch_device.
+ * d_tensor: device memory on the engine's device, aligned to the element size, `capacity` faces; tensor: host memory of the same
+ * size; matrices: host, capacity * 6 doubles; offsets: host, n + 1 ints.  Each may be NULL.  n may exceed max_batch.
+ * A bad spec is refused before any state changes.  Multi-device handles return RF_ERR_UNSUPPORTED from these three calls. */
+int rf_detect_face_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                float threshold, rf_face *out, int cap_per_image, int *counts, const rf_face_batch_spec *spec,
+                                void *d_tensor, void *tensor, double *matrices, int *offsets);
+
+/* The same with frames in HOST memory (rf_detect_batch's convention). */
+int rf_detect_face_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                         float threshold, rf_face *out, int cap_per_image, int *counts, const rf_face_batch_spec *spec,
+                         void *d_tensor, void *tensor, double *matrices, int *offsets);
+
+/* The face batch of faces the CALLER supplies (the packed counterpart of rf_align_batch_device; faces, counts and coord_scale as
+ * there).  RF_ERR_TRUNCATED when total > capacity. */
+int rf_face_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                         const rf_face *faces, int cap_per_image, const int *counts, const float *coord_scale,
+                         const rf_face_batch_spec *spec, void *d_tensor, void *tensor, double *matrices, int *offsets);
+
 /* Asynchronous form of rf_detect_batch_device for serving loops: enqueue returns as soon as the
  * batch is queued on the engine's stream (n <= max_batch); `ticket` identifies one of
  * rf_num_slots() result slots.  rf_wait blocks until that batch has finished and copies its results.

@@ -34,6 +34,13 @@ class rf_options(C.Structure):
                 ("plan_cache", C.c_int32), ("oversize_resize", C.c_int32)]
 
 
+class rf_face_batch_spec(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("crop_size", C.c_int32), ("format", C.c_int32), ("rgb", C.c_int32),
+                ("mean", C.c_float * 3), ("scale", C.c_float * 3), ("max_faces", C.c_int32), ("capacity", C.c_int32)]
+
+
+RF_FACES_U8_HWC, RF_FACES_F16_CHW, RF_FACES_F32_CHW = 0, 1, 2
+
 # every symbol include/retinaface_amd.h declares: name -> (restype, argtypes)
 _PP = C.POINTER
 SYMBOLS = {
@@ -60,6 +67,17 @@ SYMBOLS = {
     "rf_detect_align_batch": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
                                         C.c_float, _PP(rf_face), C.c_int, _PP(C.c_int), C.c_int, C.c_int,
                                         C.c_void_p, C.c_void_p, _PP(C.c_double)]),
+    "rf_face_batch_plan": (C.c_long, [_PP(rf_face_batch_spec), _PP(C.c_int), C.c_int, _PP(C.c_int), _PP(C.c_size_t)]),
+    "rf_face_value_table": (C.c_int, [_PP(rf_face_batch_spec), C.c_int, C.c_void_p]),
+    "rf_detect_face_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                              C.c_float, _PP(rf_face), C.c_int, _PP(C.c_int), _PP(rf_face_batch_spec),
+                                              C.c_void_p, C.c_void_p, _PP(C.c_double), _PP(C.c_int)]),
+    "rf_detect_face_batch": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                       C.c_float, _PP(rf_face), C.c_int, _PP(C.c_int), _PP(rf_face_batch_spec),
+                                       C.c_void_p, C.c_void_p, _PP(C.c_double), _PP(C.c_int)]),
+    "rf_face_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                       _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_float), _PP(rf_face_batch_spec),
+                                       C.c_void_p, C.c_void_p, _PP(C.c_double), _PP(C.c_int)]),
     "rf_num_slots": (C.c_int, [C.c_void_p]),
     "rf_enqueue_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int),
                                           C.c_int, C.c_float, _PP(C.c_int)]),

@@ -96,3 +96,35 @@ vector<cv::Mat> RetinaFace::detectAndAlign(const Mat &img, float threshold, int 
     }
     return crops;
 }
+
+vector<uint8_t> RetinaFace::detectFaceBatch(const vector<cv::Mat> &imgs, float threshold, const rf_face_batch_spec &spec) {
+    const int n = (int)imgs.size();
+    lastBatch_.assign(n, vector<FaceDetectInfo>());
+    faceOffsets_.assign((size_t)n + 1, 0);
+    faceMats_.clear();
+    faceTruncated_ = false;
+    vector<const uint8_t *> ptrs(n);
+    vector<int> rows(n), cols(n), steps(n), counts(n, 0);
+    for (int i = 0; i < n; i++) {
+        ptrs[i] = imgs[i].empty() ? nullptr : imgs[i].data;
+        rows[i] = imgs[i].rows; cols[i] = imgs[i].cols; steps[i] = (int)(size_t)imgs[i].step;
+    }
+    size_t bpf = 0;
+    if (rf_face_batch_plan(&spec, nullptr, 0, nullptr, &bpf) < 0) throw std::runtime_error("RetinaFace::detectFaceBatch: bad rf_face_batch_spec");
+    vector<rf_face> faces((size_t)n * maxDet_);
+    vector<uint8_t> tensor((size_t)spec.capacity * bpf);
+    vector<double> mats((size_t)spec.capacity * 6);
+    check(rf_detect_face_batch(h_, ptrs.data(), rows.data(), cols.data(), steps.data(), n, threshold, faces.data(), maxDet_, counts.data(),
+                               &spec, nullptr, tensor.data(), mats.data(), faceOffsets_.data()), h_, "RetinaFace::detectFaceBatch");
+    for (int i = 0; i < n; i++) {
+        int k = counts[i] < maxDet_ ? counts[i] : maxDet_;
+        lastBatch_[i].resize(k);
+        if (k) memcpy(lastBatch_[i].data(), &faces[(size_t)i * maxDet_], (size_t)k * sizeof(rf_face));
+    }
+    const int total = faceOffsets_[n];
+    faceTruncated_ = total > spec.capacity;
+    const size_t got = (size_t)(faceTruncated_ ? spec.capacity : total);
+    tensor.resize(got * bpf);
+    faceMats_.assign(mats.begin(), mats.begin() + got * 6);
+    return tensor;
+}

@@ -272,6 +272,90 @@ int rf_detect_align_batch(rf_handle h, const uint8_t *const *bgr, const int *row
                                align_request(crop_size, max_faces, d_crops, crops, matrices));
 }
 
+namespace {
+// a caller's spec, checked and with its defaults applied, and the buffers of the call
+void face_batch_request(const rf_face_batch_spec *spec, int default_max_faces, void *d_tensor, void *tensor, double *matrices,
+                        int *offsets, rf::FaceBatchRequest *rq) {
+    if (const char *bad = rf::face_batch_resolve(spec, default_max_faces, &rq->spec)) throw rf::ArgError(bad);
+    rq->d_tensor = (uint8_t *)d_tensor; rq->tensor = (uint8_t *)tensor; rq->matrices = matrices; rq->offsets = offsets;
+}
+
+const char kFaceOverflow[] = "more packed faces than the face batch's capacity";
+
+int detect_face_batch_common(rf_handle h, const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n,
+                             bool on_device, float thr, rf_face *out, int cap, int *counts, const rf_face_batch_spec *spec,
+                             void *d_tensor, void *tensor, double *matrices, int *offsets) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        rf::FaceBatchRequest rq;
+        face_batch_request(spec, h->eng->default_max_faces(), d_tensor, tensor, matrices, offsets, &rq);
+        bool tr = false, over = false;
+        h->eng->detect_face_batch(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, rq, &over);
+        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        if (over) { h->error = kFaceOverflow; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+}  // namespace
+
+long rf_face_batch_plan(const rf_face_batch_spec *spec, const int *counts, int n, int *offsets, size_t *bytes_per_face) {
+    rf::FaceBatchSpec sp;
+    if (rf::face_batch_resolve(spec, 256, &sp) || n < 0 || (n > 0 && !counts)) return RF_ERR_INVALID_ARG;
+    long total = 0;
+    for (int i = 0; i < n; i++) {                       // checked before anything is written
+        if (counts[i] < 0) return RF_ERR_INVALID_ARG;
+        total += std::min(counts[i], sp.max_faces);
+    }
+    if (total > 0x7fffffffL) return RF_ERR_INVALID_ARG;
+    rf::face_batch_offsets(counts, n, sp.max_faces, offsets);
+    if (bytes_per_face) *bytes_per_face = sp.bytes_per_face();
+    return total;
+}
+
+int rf_face_value_table(const rf_face_batch_spec *spec, int channel, void *out256) {
+    rf::FaceBatchSpec sp;
+    rf_face_batch_spec any;
+    if (!spec || !out256 || channel < 0 || channel > 2) return RF_ERR_INVALID_ARG;
+    any = *spec;
+    if (any.struct_size == sizeof(any) && any.capacity == 0) any.capacity = 1;      // the table does not depend on it
+    if (rf::face_batch_resolve(&any, 256, &sp)) return RF_ERR_INVALID_ARG;
+    const float m = sp.mean[channel], k = sp.scale[channel];
+    for (unsigned q = 0; q < 256; q++) {
+        if (sp.format == RF_FACES_U8_HWC) ((uint8_t *)out256)[q] = rf::face_value<uint8_t>(q, m, k);
+        else if (sp.format == RF_FACES_F16_CHW) ((_Float16 *)out256)[q] = rf::face_value<_Float16>(q, m, k);
+        else ((float *)out256)[q] = rf::face_value<float>(q, m, k);
+    }
+    return RF_OK;
+}
+
+int rf_detect_face_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                float threshold, rf_face *out, int cap_per_image, int *counts, const rf_face_batch_spec *spec,
+                                void *d_tensor, void *tensor, double *matrices, int *offsets) {
+    return detect_face_batch_common(h, (const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, out, cap_per_image, counts,
+                                    spec, d_tensor, tensor, matrices, offsets);
+}
+
+int rf_detect_face_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                         float threshold, rf_face *out, int cap_per_image, int *counts, const rf_face_batch_spec *spec,
+                         void *d_tensor, void *tensor, double *matrices, int *offsets) {
+    return detect_face_batch_common(h, bgr, rows, cols, steps, n, false, threshold, out, cap_per_image, counts, spec, d_tensor, tensor,
+                                    matrices, offsets);
+}
+
+int rf_face_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                         const rf_face *faces, int cap_per_image, const int *counts, const float *coord_scale,
+                         const rf_face_batch_spec *spec, void *d_tensor, void *tensor, double *matrices, int *offsets) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        rf::FaceBatchRequest rq;
+        face_batch_request(spec, h->eng->default_max_faces(), d_tensor, tensor, matrices, offsets, &rq);
+        bool over = false;
+        h->eng->face_batch(d_bgr, rows, cols, steps, n, faces, cap_per_image, counts, coord_scale, rq, &over);
+        if (over) { h->error = kFaceOverflow; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+
 int rf_num_slots(rf_handle h) { return h ? h->eng->num_slots() : RF_ERR_INVALID_ARG; }
 
 int rf_enqueue_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps,

@@ -207,7 +207,7 @@ public:
         for (void *p : dev_allocs_) (void)hipFree(p);
         for (void *p : host_allocs_) (void)hipHostFree(p);
         if (align_stream_) { (void)hipStreamSynchronize(align_stream_); (void)hipStreamDestroy(align_stream_); }
-        for (DeviceScratch *b : {&align_crops_, &align_mats_, &align_tab_}) b->release();
+        for (DeviceScratch *b : {&align_crops_, &align_mats_, &align_tab_, &fb_state_}) b->release();
         kind_.arena->release();
         for (auto &e : prof_ev_) (void)hipEventDestroy(e);
     }
@@ -365,6 +365,127 @@ public:
         RF_HIP(hipGetLastError());
         RF_HIP(hipStreamSynchronize(align_stream_));
         align_copy_out(rq, d_crops, d_mats, n, cnt, rq.max_faces);
+    }
+
+    // -------------------------------------------------------------------------------- face batches
+    static void check_face_batch_request(const FaceBatchRequest &rq) {
+        const FaceBatchSpec &sp = rq.spec;
+        if (sp.crop < kAlignMinCrop || sp.crop > kAlignMaxCrop) throw ArgError("crop_size must be in [16, 512]");
+        if (sp.max_faces < 1 || sp.max_faces > kAlignMaxFaces) throw ArgError("max_faces must be in [1, 4096]");
+        if (sp.capacity < 1) throw ArgError("capacity must be >= 1");
+        if (rq.d_tensor && ((uintptr_t)rq.d_tensor & (uintptr_t)(sp.elem_bytes() - 1))) throw ArgError("d_tensor is not aligned to its element size");
+    }
+
+    // device blocks of a face-batch call: the caller's tensor or scratch for the host copy, scratch for the matrices
+    void face_batch_open(const FaceBatchRequest &rq, uint8_t **d_tensor, double **d_mats) {
+        const size_t cap = (size_t)rq.spec.capacity;
+        *d_tensor = rq.d_tensor;
+        if (!rq.d_tensor && rq.tensor) *d_tensor = align_crops_.reserve(cap * rq.spec.bytes_per_face());
+        *d_mats = rq.matrices ? (double *)align_mats_.reserve(cap * 6 * sizeof(double)) : nullptr;
+        if (!fb_state_.ptr) RF_HIP(hipMemset(fb_state_.reserve(256), 0, 256));
+    }
+
+    // results of a finished face-batch call to the caller's host buffers: the packed faces that exist, nothing behind them
+    void face_batch_copy_out(const FaceBatchRequest &rq, const uint8_t *d_tensor, const double *d_mats, const int *counts, int n, int limit,
+                             bool *overflow) {
+        std::vector<int> off((size_t)n + 1, 0);
+        const long total = face_batch_offsets(counts, n, limit, off.data());
+        if (rq.offsets) memcpy(rq.offsets, off.data(), off.size() * sizeof(int));
+        const size_t written = (size_t)std::min<long>(total, rq.spec.capacity);
+        *overflow = total > rq.spec.capacity;
+        if (!written) return;
+        if (rq.tensor && d_tensor) RF_HIP(hipMemcpy(rq.tensor, d_tensor, written * rq.spec.bytes_per_face(), hipMemcpyDeviceToHost));
+        if (rq.matrices && d_mats) RF_HIP(hipMemcpy(rq.matrices, d_mats, written * 6 * sizeof(double), hipMemcpyDeviceToHost));
+    }
+
+    void detect_face_batch(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,
+                           float threshold, rf_face *out, int cap_per_image, int *counts, bool *truncated, const FaceBatchRequest &rq,
+                           bool *overflow) override {
+        check_face_batch_request(rq);
+        if (n < 0 || (n > 0 && (!frames || !rows || !cols || !counts))) throw ArgError("null argument");
+        if ((long)n * rq.spec.max_faces > (1L << 24)) throw ArgError("n x max_faces: more than 2^24 faces in one call");
+        DeviceGuard guard(device_);
+        // as in detect_align(): a super-batch of earlier enqueues starts now, every later launch carries images of this call only
+        launch_pending();
+        uint8_t *d_tensor = nullptr;
+        double *d_mats = nullptr;
+        face_batch_open(rq, &d_tensor, &d_mats);
+        fb_.rq = rq;
+        fb_.d_tensor = d_tensor; fb_.d_mats = d_mats;
+        fb_.first = true; fb_.prev_scan = nullptr;
+        fb_.on = true;
+        struct Off { bool &on; ~Off() { on = false; } } off{fb_.on};
+        detect(frames, rows, cols, steps, n, on_device, threshold, out, cap_per_image, counts, truncated);
+        fb_.on = false;
+        // every launch of the call has been waited for (its `done` event follows the tensor launch); an empty frame has count 0
+        face_batch_copy_out(rq, d_tensor, d_mats, counts, n, std::min(rq.spec.max_faces, opt_.max_detections), overflow);
+    }
+
+    void face_batch(const void *const *frames, const int *rows, const int *cols, const int *steps, int n, const rf_face *faces,
+                    int cap_per_image, const int *counts, const float *coord_scale, const FaceBatchRequest &rq, bool *overflow) override {
+        check_face_batch_request(rq);
+        if (n < 0 || (n > 0 && (!frames || !rows || !cols || !counts || !faces))) throw ArgError("null argument");
+        if (cap_per_image < 1) throw ArgError("cap_per_image must be >= 1");
+        if ((long)n * rq.spec.max_faces > (1L << 24)) throw ArgError("n x max_faces: more than 2^24 faces in one call");
+        for (int i = 0; i < n; i++)
+            if (counts[i] < 0) throw ArgError("negative face count");
+        *overflow = false;
+        if (n == 0) { if (rq.offsets) rq.offsets[0] = 0; return; }
+        DeviceGuard guard(device_);
+        const int fpi = std::min(cap_per_image, rq.spec.max_faces);     // records per image that travel to the device
+        // one table: frames | counts | scales | offsets (written by the scan) | faces (60-byte records)
+        const int per = std::min(n, kAlignImagesPerLaunch);
+        const size_t o_cnt = align256((size_t)n * sizeof(FrameDesc)), o_sc = o_cnt + align256((size_t)n * sizeof(int)),
+                     o_off = o_sc + align256((size_t)n * sizeof(float)), o_face = o_off + align256(((size_t)per + 1) * sizeof(int)),
+                     total = o_face + (size_t)n * fpi * sizeof(rf_face);
+        align_host_.assign(total, 0);
+        FrameDesc *fd = (FrameDesc *)align_host_.data();
+        int *cnt = (int *)(align_host_.data() + o_cnt);
+        float *sc = (float *)(align_host_.data() + o_sc);
+        for (int i = 0; i < n; i++) {
+            const int st = steps ? steps[i] : cols[i] * 3;
+            const uint8_t *p = (const uint8_t *)frames[i];
+            check_frame(p, rows[i], cols[i], st);
+            const bool empty = !p || rows[i] <= 0 || cols[i] <= 0;
+            if (!empty && check_residency_) {
+                const int where = foreign_device_of(p);
+                if (where >= 0 && where != device_) throw ArgError("face batch: frame is resident on another device");
+            }
+            fd[i] = empty ? FrameDesc{nullptr, 0, 0, 0, 0} : FrameDesc{p, rows[i], cols[i], st, 0};
+            cnt[i] = empty ? 0 : std::min(counts[i], fpi);
+            sc[i] = coord_scale ? coord_scale[i] : 1.f;
+            if (cnt[i]) memcpy(align_host_.data() + o_face + (size_t)i * fpi * sizeof(rf_face), faces + (size_t)i * cap_per_image, (size_t)cnt[i] * sizeof(rf_face));
+        }
+        uint8_t *d_tab = align_tab_.reserve(total);
+        uint8_t *d_tensor = nullptr;
+        double *d_mats = nullptr;
+        face_batch_open(rq, &d_tensor, &d_mats);
+        if (d_tensor || d_mats) {
+            if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+            RF_HIP(hipMemcpyAsync(d_tab, align_host_.data(), total, hipMemcpyHostToDevice, align_stream_));
+            for (int base = 0; base < n; base += per) {          // one stream: the scans and the tensor launches run in order
+                FaceScanParams sp;
+                sp.frames = (const FrameDesc *)d_tab + base;
+                sp.counts = (const int *)(d_tab + o_cnt) + base;
+                sp.n = std::min(per, n - base); sp.faces_per_image = fpi; sp.max_faces = rq.spec.max_faces;
+                sp.running = (int *)fb_state_.ptr; sp.first = base == 0;
+                sp.offsets = (int *)(d_tab + o_off);
+                launch_face_scan(align_stream_, sp);
+                FaceBatchParams bp;
+                bp.frames = sp.frames;
+                bp.faces = d_tab + o_face + (size_t)base * fpi * sizeof(rf_face);
+                bp.face_stride = (int)sizeof(rf_face); bp.faces_per_image = fpi;
+                bp.scale = (const float *)(d_tab + o_sc) + base;
+                bp.offsets = sp.offsets;
+                bp.n = sp.n; bp.max_faces = rq.spec.max_faces;
+                bp.spec = rq.spec;
+                bp.tensor = d_tensor; bp.mats = d_mats;
+                launch_face_batch(align_stream_, bp);
+            }
+            RF_HIP(hipGetLastError());
+            RF_HIP(hipStreamSynchronize(align_stream_));
+        }
+        face_batch_copy_out(rq, d_tensor, d_mats, cnt, n, rq.spec.max_faces, overflow);
     }
 
     void host_register(const void *ptr, size_t bytes) override {
@@ -567,6 +688,8 @@ private:
         uint8_t *h_stage = nullptr, *d_stage = nullptr;
         size_t stage_cap = 0, stage_used = 0;
         float *h_align_scale = nullptr;       // detect_align(): pinned, per image of the launch its frame_scale (allocated on first use)
+        int *d_face_off = nullptr;            // detect_face_batch(): packed offsets of the launch's images, written by its scan kernel (first use)
+        hipEvent_t face_scan_done = nullptr;  // ... recorded behind that scan: the call's next launch (another lane) waits for it on the device
         bool busy = false;                    // a launched super-batch whose results have not been harvested yet
         int n_images = 0;                     // images of the super-batch being assembled / in flight on this lane
         float threshold = 0.f;
@@ -607,6 +730,7 @@ private:
         for (hipEvent_t &e : l.time_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
         if (l.done) (void)hipEventDestroy(l.done);
         if (l.copy2_done) (void)hipEventDestroy(l.copy2_done);
+        if (l.face_scan_done) (void)hipEventDestroy(l.face_scan_done);
         if (l.copy2) { (void)hipStreamSynchronize(l.copy2); (void)hipStreamDestroy(l.copy2); }
         if (l.d_stage) (void)hipFree(l.d_stage);
         if (l.h_stage) (void)hipHostFree(l.h_stage);
@@ -890,6 +1014,7 @@ private:
         tt = trace_.on ? HostTrace::now() : 0.0;
         if (eager_timed) RF_HIP(hipEventRecord(s.time_ev[3], s.stream));
         if (align_.on) launch_lane_align(s, n);      // ordinary launches behind the graph, before `done`: nothing waits in between
+        if (fb_.on) launch_lane_face_batch(s, n);
         RF_HIP(hipEventRecord(s.done, s.stream));
         trace_.add(4, tt);
         s.busy = true;
@@ -901,16 +1026,7 @@ private:
     // full-resolution frames, also when the stem reads a shrunk canvas), faces and counts from the pinned result block the NMS
     // kernel of the same stream has just written, each frame's coordinate scale from a pinned per-lane array.
     void launch_lane_align(Lane &s, int n) {
-        if (!s.h_align_scale) {
-            void *p = nullptr;
-            RF_HIP(hipHostMalloc(&p, std::max<size_t>((size_t)cap_images_ * sizeof(float), 256), hipHostMallocDefault));
-            s.host_allocs.push_back(p);
-            s.h_align_scale = (float *)p;
-        }
-        for (int i = 0; i < n; i++) {
-            const FrameDesc &f = s.h_frames[i];
-            s.h_align_scale[i] = f.ptr ? frame_scale(f.rows, f.cols, net_h_, net_w_) : 1.f;
-        }
+        fill_lane_align_scale(s, n);
         AlignParams ap;
         ap.frames = s.d_frames;
         ap.faces = (const uint8_t *)s.h_out;
@@ -923,6 +1039,58 @@ private:
         launch_align(s.stream, ap);
         RF_HIP(hipGetLastError());
         align_.next_image += n;
+    }
+
+    // pinned per-lane array of each image's coordinate scale (rf_frame_scale), allocated on first use
+    void fill_lane_align_scale(Lane &s, int n) {
+        if (!s.h_align_scale) {
+            void *p = nullptr;
+            RF_HIP(hipHostMalloc(&p, std::max<size_t>((size_t)cap_images_ * sizeof(float), 256), hipHostMallocDefault));
+            s.host_allocs.push_back(p);
+            s.h_align_scale = (float *)p;
+        }
+        for (int i = 0; i < n; i++) {
+            const FrameDesc &f = s.h_frames[i];
+            s.h_align_scale[i] = f.ptr ? frame_scale(f.rows, f.cols, net_h_, net_w_) : 1.f;
+        }
+    }
+
+    // The face-batch launches of a super-batch of detect_face_batch(): frames, faces, counts and scales as launch_lane_align().
+    // Packed offsets continue across the launches of a call through ONE running base in device memory: this launch's scan waits
+    // (on the device: hipStreamWaitEvent) for the scan of the call's previous launch, which ran on another lane's stream; the
+    // detection launches in front of it do not wait and keep overlapping.  No host wait anywhere.
+    void launch_lane_face_batch(Lane &s, int n) {
+        fill_lane_align_scale(s, n);
+        if (!s.d_face_off) {
+            void *p = nullptr;
+            RF_HIP(hipMalloc(&p, std::max<size_t>(((size_t)cap_images_ + 1) * sizeof(int), 256)));
+            s.dev_allocs.push_back(p);
+            s.d_face_off = (int *)p;
+            RF_HIP(hipEventCreateWithFlags(&s.face_scan_done, hipEventDisableTiming));
+        }
+        const FaceBatchSpec &spec = fb_.rq.spec;
+        if (fb_.prev_scan && fb_.prev_scan != s.face_scan_done) RF_HIP(hipStreamWaitEvent(s.stream, fb_.prev_scan, 0));
+        FaceScanParams sp;
+        sp.frames = s.d_frames;
+        sp.counts = s.h_counts;
+        sp.n = n; sp.faces_per_image = opt_.max_detections; sp.max_faces = spec.max_faces;
+        sp.running = (int *)fb_state_.ptr; sp.first = fb_.first;
+        sp.offsets = s.d_face_off;
+        launch_face_scan(s.stream, sp);
+        RF_HIP(hipEventRecord(s.face_scan_done, s.stream));
+        fb_.prev_scan = s.face_scan_done;
+        fb_.first = false;
+        FaceBatchParams bp;
+        bp.frames = s.d_frames;
+        bp.faces = (const uint8_t *)s.h_out;
+        bp.face_stride = (int)sizeof(Candidate); bp.faces_per_image = opt_.max_detections;
+        bp.scale = s.h_align_scale;
+        bp.offsets = s.d_face_off;
+        bp.n = n; bp.max_faces = spec.max_faces;
+        bp.spec = spec;
+        bp.tensor = fb_.d_tensor; bp.mats = fb_.d_mats;
+        launch_face_batch(s.stream, bp);
+        RF_HIP(hipGetLastError());
     }
 
     // results of an alignment call to the caller's host buffers: per image the slots that hold faces (the others are unspecified)
@@ -1169,6 +1337,9 @@ private:
     hipStream_t align_stream_ = nullptr;
     static constexpr int kAlignImagesPerLaunch = 32768;       // grid.z limit of one launch
     struct { bool on = false; AlignRequest rq; uint8_t *d_crops = nullptr; double *d_mats = nullptr; int next_image = 0; } align_;
+    // face batches: the running base of packed offsets (one device int), and the request detect_face_batch() has open
+    DeviceScratch fb_state_;
+    struct { bool on = false, first = true; FaceBatchRequest rq; uint8_t *d_tensor = nullptr; double *d_mats = nullptr; hipEvent_t prev_scan = nullptr; } fb_;
 
     int last_n_ = 0;
     std::vector<int> last_cand_counts_;

@@ -81,6 +81,15 @@ struct AlignRequest {
     double *matrices = nullptr;
 };
 
+// Where the face batch of a call goes (rf_detect_face_batch* / rf_face_batch_device): packed face j is element block j of d_tensor
+// (device) and / or tensor (host), its forward matrix the 6 doubles at matrices + 6 * j; offsets: n + 1 packed offsets (host)
+struct FaceBatchRequest {
+    FaceBatchSpec spec;
+    uint8_t *d_tensor = nullptr, *tensor = nullptr;
+    double *matrices = nullptr;
+    int *offsets = nullptr;
+};
+
 class Engine {
 public:
     // opt.devices.size() > 1 gives the image-sharding multi-device engine (multi.cpp), otherwise one single-device engine
@@ -107,6 +116,19 @@ public:
                        const float *, const AlignRequest &) {
         throw Unsupported("face alignment is not available on a multi-device handle");
     }
+    // detect() + the face batch of what it finds (face_batch.h): per launch a scan kernel packs the counts on the device and the
+    // tensor kernel follows, on the launch's stream, with no host synchronisation; *overflow: more packed faces than the capacity.
+    // max_faces 0 in the spec has been replaced by the caller with default_max_faces().  Single-device engines only.
+    virtual void detect_face_batch(const uint8_t *const *, const int *, const int *, const int *, int, bool, float, rf_face *, int,
+                                   int *, bool *, const FaceBatchRequest &, bool * /*overflow*/) {
+        throw Unsupported("face batches are not available on a multi-device handle");
+    }
+    // the face batch of faces the caller supplies, from device-resident frames
+    virtual void face_batch(const void *const *, const int *, const int *, const int *, int, const rf_face *, int, const int *,
+                            const float *, const FaceBatchRequest &, bool * /*overflow*/) {
+        throw Unsupported("face batches are not available on a multi-device handle");
+    }
+    int default_max_faces() const { return opt_.max_detections; }
     // asynchronous: frames on host (staged through pinned memory before the call returns, unless the caller registered
     // them with host_register) or on the device
     virtual int enqueue(const void *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,

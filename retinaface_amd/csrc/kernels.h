@@ -8,6 +8,7 @@
 #include <stdexcept>
 
 #include "align.h"
+#include "face_batch.h"
 
 namespace rf {
 
@@ -193,6 +194,34 @@ struct AlignParams {
     double *mats;                         // [slots][6] forward matrices (source -> crop), or nullptr
 };
 void launch_align(hipStream_t s, const AlignParams &p);
+
+// ---- K_g: face batches -- the aligned faces of a launch packed into one dense tensor in the recogniser's layout and number format
+//      (face_batch.h; same transform and sampling as K_f).  launch_face_scan turns the per-image counts into packed offsets on
+//      the device and advances the call's running base; launch_face_batch writes the tensor: one workgroup per (image, face,
+//      band of crop rows), a workgroup whose packed face is at or beyond min(total, capacity) exits at once.
+struct FaceScanParams {
+    const FrameDesc *frames;              // [n]: an empty frame (ptr == nullptr) packs no faces
+    const int *counts;                    // [n] faces of each image (clamped to faces_per_image and max_faces here)
+    int n, faces_per_image, max_faces;
+    int *running;                         // device int: packed faces of the call's earlier launches; advanced by this launch's total
+    int first;                            // != 0: the call's first launch, the base is 0 whatever *running holds
+    int *offsets;                         // [n + 1] out: packed index of each image's first face, offsets[n] = the next launch's base
+};
+void launch_face_scan(hipStream_t s, const FaceScanParams &p);
+
+struct FaceBatchParams {
+    const FrameDesc *frames;              // as AlignParams
+    const uint8_t *faces;
+    int face_stride, faces_per_image;
+    const float *scale;
+    const int *offsets;                   // [n + 1], what launch_face_scan wrote
+    int n, max_faces;
+    FaceBatchSpec spec;                   // crop edge, format, channel order, mean / scale, capacity
+    void *tensor;                         // [capacity] faces of 3 * S * S elements, aligned to the element size, or nullptr
+    double *mats;                         // [capacity][6], or nullptr
+};
+void launch_face_batch(hipStream_t s, const FaceBatchParams &p);
+int face_batch_band_rows(int crop, int format);      // crop rows one workgroup covers (exposed for tests and DESIGN.md)
 
 // LDS bytes / tile geometry chosen for a layer (exposed for tests and DESIGN.md tables)
 struct TileInfo { int th, tw; size_t lds_bytes; int blocks_per_image; };

@@ -4030,6 +4030,39 @@ int cvt_pk_u8_selfcheck() {
 constexpr int kAlignBandRows = 8;
 constexpr int kAlignBandBytes = kAlignBandRows * kAlignMaxCrop * 3;
 
+// The sampling half of alignment, shared by K_f and K_g: crop pixel (u, v) mapped back into the source frame with the inverse
+// similarity (double, fixed order, no contraction), the position rounded to 1/1024 pixel, the four taps blended in integers.
+struct AlignSampler {
+    int valid;
+    double ia, ib, mpx, mpy, mqx, mqy, xmax, ymax;
+    __device__ AlignSampler(const AlignXform &xf, const FrameDesc &fd)
+        : valid(xf.valid), ia(xf.ia), ib(xf.ib), mpx(xf.mpx), mpy(xf.mpy), mqx(xf.mqx), mqy(xf.mqy), xmax((double)(fd.cols + 1)),
+          ymax((double)(fd.rows + 1)) {}
+};
+
+__device__ __forceinline__ void align_sample(const FrameDesc &fd, const AlignSampler &sm, int u, int v, unsigned acc[3]) {
+#pragma clang fp contract(off)
+    acc[0] = acc[1] = acc[2] = 0u;
+    const double du = (double)u - sm.mqx, dv = (double)v - sm.mqy;
+    const double x = (sm.ia * du - sm.ib * dv) + sm.mpx;
+    const double y = (sm.ib * du + sm.ia * dv) + sm.mpy;
+    if (sm.valid && x > -2.0 && x < sm.xmax && y > -2.0 && y < sm.ymax) {
+        const long long X = (long long)floor(x * 1024.0 + 0.5), Y = (long long)floor(y * 1024.0 + 0.5);
+        const int x0 = (int)(X >> 10), y0 = (int)(Y >> 10);
+        const unsigned fx = (unsigned)(X & 1023), fy = (unsigned)(Y & 1023);
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const int xx = x0 + (t & 1), yy = y0 + (t >> 1);
+            if (xx < 0 || xx >= fd.cols || yy < 0 || yy >= fd.rows) continue;
+            const unsigned w = ((t & 1) ? fx : 1024u - fx) * ((t >> 1) ? fy : 1024u - fy);
+            const uint8_t *sp = fd.ptr + (size_t)yy * fd.step + (size_t)xx * 3;
+            acc[0] += w * sp[0]; acc[1] += w * sp[1]; acc[2] += w * sp[2];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; c++) acc[c] = (acc[c] + (1u << 19)) >> 20;
+    }
+}
+
 __global__ __launch_bounds__(kThreads) void align_kernel(AlignParams a) {
 #pragma clang fp contract(off)
     __shared__ AlignXform xf;
@@ -4058,30 +4091,10 @@ __global__ __launch_bounds__(kThreads) void align_kernel(AlignParams a) {
     uint8_t *dst = a.crops + slot * (size_t)S * S * 3 + (size_t)r0 * S * 3;
     const int mis = (int)((uintptr_t)dst & 15);
     uint8_t *lds = (uint8_t *)band_buf + mis;
-    const int valid = xf.valid;
-    const double ia = xf.ia, ib = xf.ib, mpx = xf.mpx, mpy = xf.mpy, mqx = xf.mqx, mqy = xf.mqy;
-    const double xmax = (double)(fd.cols + 1), ymax = (double)(fd.rows + 1);
+    const AlignSampler sm(xf, fd);
     for (int p = threadIdx.x; p < npix; p += kThreads) {
-        const int v = r0 + p / S, u = p % S;
-        unsigned acc[3] = {0u, 0u, 0u};
-        const double du = (double)u - mqx, dv = (double)v - mqy;
-        const double x = (ia * du - ib * dv) + mpx;
-        const double y = (ib * du + ia * dv) + mpy;
-        if (valid && x > -2.0 && x < xmax && y > -2.0 && y < ymax) {
-            const long long X = (long long)floor(x * 1024.0 + 0.5), Y = (long long)floor(y * 1024.0 + 0.5);
-            const int x0 = (int)(X >> 10), y0 = (int)(Y >> 10);
-            const unsigned fx = (unsigned)(X & 1023), fy = (unsigned)(Y & 1023);
-#pragma unroll
-            for (int t = 0; t < 4; t++) {
-                const int xx = x0 + (t & 1), yy = y0 + (t >> 1);
-                if (xx < 0 || xx >= fd.cols || yy < 0 || yy >= fd.rows) continue;
-                const unsigned w = ((t & 1) ? fx : 1024u - fx) * ((t >> 1) ? fy : 1024u - fy);
-                const uint8_t *sp = fd.ptr + (size_t)yy * fd.step + (size_t)xx * 3;
-                acc[0] += w * sp[0]; acc[1] += w * sp[1]; acc[2] += w * sp[2];
-            }
-#pragma unroll
-            for (int c = 0; c < 3; c++) acc[c] = (acc[c] + (1u << 19)) >> 20;
-        }
+        unsigned acc[3];
+        align_sample(fd, sm, p % S, r0 + p / S, acc);
         lds[3 * p + 0] = (uint8_t)acc[0]; lds[3 * p + 1] = (uint8_t)acc[1]; lds[3 * p + 2] = (uint8_t)acc[2];
     }
     __syncthreads();
@@ -4105,6 +4118,136 @@ void launch_align(hipStream_t s, const AlignParams &p) {
     // matrices only: one band per face is enough
     dim3 grid(p.crops ? (p.crop + kAlignBandRows - 1) / kAlignBandRows : 1, slots, p.n);
     hipLaunchKernelGGL(align_kernel, grid, dim3(kThreads), 0, s, p);
+}
+
+// =============================================================================================
+// K_g: face batches (face_batch.h): the aligned faces of a launch, packed, in the recogniser's layout and number format.
+//      face_scan_kernel (one workgroup) turns the counts the NMS kernel wrote into packed offsets -- the host never looks at
+//      them -- and advances the call's running base, which the next launch of the call (another lane, another stream, ordered
+//      behind this kernel by an event) starts from.
+//      face_batch_kernel: one workgroup = one (image, face, band of crop rows), transform and sampling of K_f (align_estimate,
+//      align_sample).  A band is one contiguous run of the destination for HWC and three for CHW, one per plane; each run is
+//      assembled in LDS at its destination's 16-byte phase and leaves as whole 16-byte vectors per lane, its unaligned head and
+//      tail as elements.  The band height shrinks with the element size so that the three runs of S = 512 fp32 fit 12 KB of LDS.
+// =============================================================================================
+constexpr int kFaceRunBytes = 4096;                              // LDS bytes of one CHW run (a band of one plane)
+constexpr int kFaceLdsVecs = 3 * (kFaceRunBytes / 16 + 1);       // three runs + 16 bytes of phase each; one HWC run of 8 x 512 x 3 fits too
+static_assert(kAlignBandBytes + 16 <= kFaceLdsVecs * 16, "the u8 HWC band must fit the face-batch LDS block");
+
+int face_batch_band_rows(int crop, int format) {
+    if (format == RF_FACES_U8_HWC) return kAlignBandRows;
+    const int rows = kFaceRunBytes / (crop * (format == RF_FACES_F32_CHW ? 4 : 2));
+    return rows < kAlignBandRows ? rows : kAlignBandRows;
+}
+
+__global__ __launch_bounds__(kThreads) void face_scan_kernel(FaceScanParams a) {
+    __shared__ int part[kThreads];
+    const int limit = a.max_faces < a.faces_per_image ? a.max_faces : a.faces_per_image;
+    const int chunk = (a.n + kThreads - 1) / kThreads;
+    const int i0 = (int)threadIdx.x * chunk, i1 = i0 + chunk < a.n ? i0 + chunk : a.n;
+    auto faces_of = [&](int i) {
+        int c = a.counts[i];
+        c = c < 0 ? 0 : c < limit ? c : limit;
+        return a.frames[i].ptr == nullptr ? 0 : c;
+    };
+    int sum = 0;
+    for (int i = i0; i < i1; i++) sum += faces_of(i);
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    int base = a.first ? 0 : *a.running;
+    for (int t = 0; t < (int)threadIdx.x; t++) base += part[t];
+    for (int i = i0; i < i1; i++) { a.offsets[i] = base; base += faces_of(i); }
+    __syncthreads();                                             // every thread has read *running before it is advanced
+    if (threadIdx.x == kThreads - 1) { a.offsets[a.n] = base; *a.running = base; }
+}
+
+void launch_face_scan(hipStream_t s, const FaceScanParams &p) {
+    if (p.n <= 0) return;
+    hipLaunchKernelGGL(face_scan_kernel, dim3(1), dim3(kThreads), 0, s, p);
+}
+
+// one run of a band: nbytes at dst, assembled in LDS at lds (same 16-byte phase as dst); E = the element type
+template <typename E>
+__device__ __forceinline__ void face_store_run(uint8_t *dst, const uint8_t *lds, int nbytes) {
+    const int mis = (int)((uintptr_t)dst & 15);
+    int head = (16 - mis) & 15;
+    head = head < nbytes ? head : nbytes;
+    const int nvec = (nbytes - head) / 16, tail0 = head + nvec * 16;
+    const int t = (int)threadIdx.x * (int)sizeof(E);
+    if (t < head) *(E *)(dst + t) = *(const E *)(lds + t);
+    const uint4 *lv = (const uint4 *)(lds + head);
+    uint4 *gv = (uint4 *)(dst + head);
+    for (int i = threadIdx.x; i < nvec; i += kThreads) gv[i] = lv[i];
+    if (t < nbytes - tail0) *(E *)(dst + tail0 + t) = *(const E *)(lds + tail0 + t);
+}
+
+template <typename E, bool CHW>
+__global__ __launch_bounds__(kThreads) void face_batch_kernel(FaceBatchParams a, int band_rows) {
+#pragma clang fp contract(off)
+    __shared__ AlignXform xf;
+    __shared__ uint4 band_buf[kFaceLdsVecs];
+    const int band = blockIdx.x, k = blockIdx.y, img = blockIdx.z;
+    const int first = a.offsets[img];
+    if (k >= a.offsets[img + 1] - first) return;
+    const int j = first + k;
+    if (j >= a.spec.capacity) return;
+    const FrameDesc fd = a.frames[img];
+    if (fd.ptr == nullptr || fd.rows <= 0 || fd.cols <= 0) return;
+    const int S = a.spec.crop;
+    if (threadIdx.x == 0) {
+        const float *f = (const float *)(a.faces + ((size_t)img * a.faces_per_image + k) * a.face_stride);
+        float px[5], py[5];
+        for (int i = 0; i < 5; i++) { px[i] = f[5 + i]; py[i] = f[10 + i]; }
+        align_estimate(px, py, a.scale ? a.scale[img] : 1.f, S, &xf);
+        if (band == 0 && a.mats)
+            for (int i = 0; i < 6; i++) a.mats[(size_t)j * 6 + i] = xf.fwd[i];
+    }
+    if (a.tensor == nullptr) return;
+    __syncthreads();
+    const int r0 = band * band_rows;
+    const int nrows = S - r0 < band_rows ? S - r0 : band_rows;
+    const int npix = nrows * S;
+    constexpr int ES = (int)sizeof(E), RUNS = CHW ? 3 : 1;
+    const int run_bytes = npix * ES * (CHW ? 1 : 3);
+    uint8_t *face = (uint8_t *)a.tensor + (size_t)j * 3 * S * S * ES;
+    uint8_t *dst[RUNS], *lds[RUNS];
+#pragma unroll
+    for (int r = 0; r < RUNS; r++) {
+        dst[r] = face + (CHW ? ((size_t)r * S * S + (size_t)r0 * S) * ES : (size_t)r0 * S * 3 * ES);
+        lds[r] = (uint8_t *)band_buf + r * (kFaceRunBytes + 16) + ((uintptr_t)dst[r] & 15);
+    }
+    const int flip = a.spec.rgb ? 2 : 0;
+    const AlignSampler sm(xf, fd);
+    for (int p = threadIdx.x; p < npix; p += kThreads) {
+        unsigned acc[3];
+        align_sample(fd, sm, p % S, r0 + p / S, acc);
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const E val = face_value<E>(acc[flip ? 2 - c : c], a.spec.mean[c], a.spec.scale[c]);
+            if (CHW) ((E *)lds[CHW ? c : 0])[p] = val;
+            else ((E *)lds[0])[3 * p + c] = val;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < RUNS; r++) face_store_run<E>(dst[r], lds[r], run_bytes);
+}
+
+void launch_face_batch(hipStream_t s, const FaceBatchParams &p) {
+    if (p.n <= 0 || p.max_faces <= 0) return;
+    const FaceBatchSpec &sp = p.spec;
+    if (sp.crop < kAlignMinCrop || sp.crop > kAlignMaxCrop || p.max_faces > kAlignMaxFaces || p.n > 65535 || sp.capacity < 1)
+        throw Unsupported("face batch: crop size, faces per image or images per launch out of range");
+    if (p.tensor && ((uintptr_t)p.tensor & (uintptr_t)(sp.elem_bytes() - 1))) throw Unsupported("face batch: the tensor is not aligned to its element size");
+    const int slots = p.max_faces < p.faces_per_image ? p.max_faces : p.faces_per_image;
+    if (slots <= 0) return;
+    const int rows = face_batch_band_rows(sp.crop, sp.format);
+    // matrices only: one band per face is enough
+    dim3 grid(p.tensor ? (sp.crop + rows - 1) / rows : 1, slots, p.n);
+    if (sp.format == RF_FACES_U8_HWC) hipLaunchKernelGGL((face_batch_kernel<uint8_t, false>), grid, dim3(kThreads), 0, s, p, rows);
+    else if (sp.format == RF_FACES_F16_CHW) hipLaunchKernelGGL((face_batch_kernel<half_t, true>), grid, dim3(kThreads), 0, s, p, rows);
+    else if (sp.format == RF_FACES_F32_CHW) hipLaunchKernelGGL((face_batch_kernel<float, true>), grid, dim3(kThreads), 0, s, p, rows);
+    else throw Unsupported("face batch: unknown format");
 }
 
 #ifdef RF_KERNEL_TRACE

@@ -14,7 +14,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import rf_face, rf_options
+from ._lib import rf_face, rf_face_batch_spec, rf_options
 
 PRECISION_FP32, PRECISION_FP16, PRECISION_INT8 = 0, 1, 2
 
@@ -52,6 +52,55 @@ def align_matrix(face, coord_scale: float = 1.0, crop_size: int = 112):
     if st < 0:
         raise _lib.RFError(st, "rf_align_matrix: bad argument (crop_size must be in [16, 512])")
     return bool(st), np.array(m, np.float64).reshape(2, 3)
+
+
+_FACE_FORMATS = {"u8": (_lib.RF_FACES_U8_HWC, np.uint8), "f16": (_lib.RF_FACES_F16_CHW, np.float16),
+                 "f32": (_lib.RF_FACES_F32_CHW, np.float32)}
+
+
+def face_batch_spec(crop_size: int = 112, dtype: str = "f16", rgb: bool = True, mean=None, scale=None, max_faces: int = 0,
+                    capacity: int = 1) -> rf_face_batch_spec:
+    """An rf_face_batch_spec: dtype "u8" (HWC), "f16" or "f32" (CHW); mean / scale: one number or three, per OUTPUT channel
+    (both None = (v - 127.5) / 128); max_faces 0 = the engine's max_detections."""
+    if dtype not in _FACE_FORMATS:
+        raise ValueError('dtype must be "u8", "f16" or "f32"')
+    sp = rf_face_batch_spec()
+    sp.struct_size = C.sizeof(rf_face_batch_spec)
+    sp.crop_size, sp.format, sp.rgb = int(crop_size), _FACE_FORMATS[dtype][0], 1 if rgb else 0
+    if scale is not None:
+        m = np.broadcast_to(np.asarray(0.0 if mean is None else mean, np.float32), (3,))
+        k = np.broadcast_to(np.asarray(scale, np.float32), (3,))
+        sp.mean, sp.scale = (C.c_float * 3)(*m), (C.c_float * 3)(*k)
+    elif mean is not None:
+        raise ValueError("mean without scale")
+    sp.max_faces, sp.capacity = int(max_faces), int(capacity)
+    return sp
+
+
+def face_batch_plan(counts: Sequence[int], *, crop_size: int = 112, dtype: str = "f16", max_faces: int = 0, capacity: int = 1):
+    """rf_face_batch_plan (host only, no GPU): (total, offsets[n + 1], bytes_per_face) of a call that finds counts[i] faces in
+    image i; total is not clamped to the capacity."""
+    lib = _lib.load_library()
+    sp = face_batch_spec(crop_size, dtype, max_faces=max_faces, capacity=capacity)
+    n = len(counts)
+    cnt = (C.c_int * max(n, 1))(*[int(c) for c in counts])
+    off = (C.c_int * (n + 1))()
+    bpf = C.c_size_t()
+    total = lib.rf_face_batch_plan(C.byref(sp), cnt, n, off, C.byref(bpf))
+    if total < 0:
+        raise _lib.RFError(int(total), "rf_face_batch_plan: bad spec or a negative count")
+    return int(total), np.array(off[:n + 1], np.int32), int(bpf.value)
+
+
+def face_value_table(channel: int, *, dtype: str = "f16", rgb: bool = True, mean=None, scale=None) -> np.ndarray:
+    """rf_face_value_table (host only, no GPU): the 256 output values of one output channel, as the kernel computes them."""
+    lib = _lib.load_library()
+    sp = face_batch_spec(112, dtype, rgb, mean, scale)
+    out = np.zeros(256, _FACE_FORMATS[dtype][1])
+    st = lib.rf_face_value_table(C.byref(sp), int(channel), out.ctypes.data)
+    if st < 0:
+        raise _lib.RFError(st, "rf_face_value_table: bad spec or channel")
+    return out
 
 
 def _faces_to_array(buf, n: int) -> np.ndarray:
@@ -261,6 +310,93 @@ class RetinaFace:
         dets = self._collect(out, counts, n, cap)
         ks = [min(len(d), mf) for d in dets]
         return dets, ([crops[i, :ks[i]] for i in range(n)] if host else None), [mats[i, :ks[i]] for i in range(n)]
+
+    # ------------------------------------------------------------------ face batches
+    def detect_face_batch(self, imgs: Sequence[np.ndarray], threshold: float = 0.5, **kw):
+        """rf_detect_face_batch: detectBatchImages + the faces it finds as ONE dense recogniser-ready tensor.  Keywords:
+        crop_size (112), dtype ("u8" HWC | "f16" | "f32" CHW; default "f16"), rgb (True), mean / scale (per output channel; default
+        (v - 127.5) / 128), max_faces (per image; default max_detections), capacity (packed faces the tensor holds; default
+        n * max_faces), d_out (a device buffer of capacity faces that receives the tensor as well), host (False skips the host
+        copy).  Returns (detections, tensor, matrices, offsets): tensor is [min(total, capacity), 3, S, S] (u8: [.., S, S, 3]),
+        matrices [.., 2, 3] float64, offsets [n + 1]: face k of image i is tensor[offsets[i] + k].  self.faces_truncated tells
+        whether total exceeded the capacity."""
+        n = len(imgs)
+        ptrs = (C.c_void_p * max(n, 1))()
+        rows, cols, steps = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
+        keep = []
+        for i, im in enumerate(imgs):
+            if im is None or im.size == 0:
+                ptrs[i], rows[i], cols[i], steps[i] = None, 0, 0, 0
+                continue
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
+            if im.strides[2] != 1 or im.strides[1] != 3:
+                im = np.ascontiguousarray(im)
+            keep.append(im)
+            ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
+        return self._run_face_batch(self._lib.rf_detect_face_batch, ptrs, rows, cols, steps, n, threshold, **kw)
+
+    def detect_face_batch_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], threshold: float = 0.5,
+                                 steps: Optional[Sequence[int]] = None, **kw):
+        """rf_detect_face_batch_device: detect_face_batch for frames resident in device memory."""
+        n = len(ptrs)
+        p = (C.c_void_p * max(n, 1))(*ptrs)
+        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
+        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        return self._run_face_batch(self._lib.rf_detect_face_batch_device, p, r, c, s, n, threshold, **kw)
+
+    def face_batch(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], faces, *, steps: Optional[Sequence[int]] = None,
+                   coord_scale: Optional[Sequence[float]] = None, **kw):
+        """rf_face_batch_device: the face batch of faces the caller supplies (faces / coord_scale as align()).  Returns
+        (None, tensor, matrices, offsets)."""
+        n = len(ptrs)
+        rows_f = [_face_rows(f) for f in faces]
+        if len(rows_f) != n:
+            raise ValueError("faces must hold one entry per frame")
+        cap = max(1, max((len(r) for r in rows_f), default=1))
+        flat = np.zeros((max(n, 1), cap, 15), np.float32)
+        counts = (C.c_int * max(n, 1))()
+        for i, r in enumerate(rows_f):
+            flat[i, :len(r)] = r
+            counts[i] = len(r)
+        p = (C.c_void_p * max(n, 1))(*ptrs)
+        r_, c_ = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
+        s_ = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        cs = (C.c_float * max(n, 1))(*[float(v) for v in coord_scale]) if coord_scale is not None else None
+
+        def fn(h, spec, d_out, tensor, mats, offsets):
+            return self._lib.rf_face_batch_device(h, p, r_, c_, s_, n, flat.ctypes.data_as(C.POINTER(rf_face)), cap, counts, cs,
+                                                  spec, d_out, tensor, mats, offsets)
+        kw.setdefault("max_faces", cap)
+        return (None,) + self._face_batch_call(fn, n, **kw)
+
+    def _run_face_batch(self, fn, ptrs, rows, cols, steps, n, threshold, **kw):
+        cap = self.max_detections
+        out = (rf_face * max(n * cap, 1))()
+        counts = (C.c_int * max(n, 1))()
+
+        def call(h, spec, d_out, tensor, mats, offsets):
+            return fn(h, ptrs, rows, cols, steps, n, float(threshold), out, cap, counts, spec, d_out, tensor, mats, offsets)
+        tensor, mats, offsets = self._face_batch_call(call, n, **kw)
+        return self._collect(out, counts, n, cap), tensor, mats, offsets
+
+    def _face_batch_call(self, call, n, crop_size: int = 112, dtype: str = "f16", rgb: bool = True, mean=None, scale=None,
+                         max_faces: Optional[int] = None, capacity: Optional[int] = None, d_out: Optional[int] = None, host: bool = True):
+        mf = int(max_faces) if max_faces else self.max_detections
+        capacity = int(capacity) if capacity is not None else max(1, n * mf)
+        sp = face_batch_spec(crop_size, dtype, rgb, mean, scale, mf, capacity)
+        S = int(crop_size) if crop_size else 112
+        shape = (S, S, 3) if dtype == "u8" else (3, S, S)
+        tensor = np.zeros((max(capacity, 0),) + shape, _FACE_FORMATS[dtype][1]) if host else None
+        mats = np.zeros((max(capacity, 0), 2, 3), np.float64)
+        offsets = (C.c_int * (n + 1))()
+        st = _lib.check(call(self._h, C.byref(sp), C.c_void_p(d_out) if d_out else None, tensor.ctypes.data if host else None,
+                             mats.ctypes.data_as(C.POINTER(C.c_double)), offsets), self._h)
+        offsets = np.array(offsets[:n + 1], np.int32)
+        got = min(int(offsets[n]), capacity)
+        self.truncated = st == _lib.RF_ERR_TRUNCATED
+        self.faces_truncated = int(offsets[n]) > capacity
+        return (tensor[:got] if host else None), mats[:got], offsets
 
     def enqueue_device(self, ptrs, rows, cols, threshold: float = 0.5) -> int:
         n = len(ptrs)
