@@ -78,6 +78,15 @@ public:
     const vector<double> &faceBatchMatrices() const { return faceMats_; }
     bool faceBatchTruncated() const { return faceTruncated_; }
 
+    /* additive: detectFaceBatch() behind a quality gate (rf_detect_face_batch_gated): only the faces the gate keeps are packed, the
+       offsets count kept faces.  gate may be nullptr (every face is kept: the bytes of detectFaceBatch).  faceBatchQuality() holds
+       n x faceBatchQualityStride() records: the record of face k of image i, kept or dropped, is [i * stride + k] for
+       k < min(faces of image i, stride); the other records are zero. */
+    vector<uint8_t> detectFaceBatchGated(const vector<cv::Mat> &imgs, float threshold, const rf_face_batch_spec &spec,
+                                         const rf_face_gate *gate);
+    const vector<rf_face_quality> &faceBatchQuality() const { return faceQuality_; }
+    int faceBatchQualityStride() const { return faceQualityStride_; }
+
     /* `scale` of RetinaFace.cpp:585-589: multiply lastResult() coordinates by it for source-frame pixels (:732-739, commented) */
     float frameScale(const Mat &img) const { return rf_frame_scale(h_, img.rows, img.cols); }
 
@@ -100,6 +109,10 @@ private:
     vector<int> faceOffsets_;
     vector<double> faceMats_;
     bool faceTruncated_ = false;
+    vector<rf_face_quality> faceQuality_;
+    int faceQualityStride_ = 0;
+    vector<uint8_t> faceBatchCall(const vector<cv::Mat> &imgs, float threshold, const rf_face_batch_spec &spec, bool gated,
+                                  const rf_face_gate *gate);
 };
 
 #endif /* RETINAFACE_H */

@@ -250,6 +250,68 @@ int rf_face_batch_device(rf_handle h, const void *const *d_bgr, const int *rows,
                          const rf_face *faces, int cap_per_image, const int *counts, const float *coord_scale,
                          const rf_face_batch_spec *spec, void *d_tensor, void *tensor, double *matrices, int *offsets);
 
+/* ---- Face quality: a few exact numbers per aligned face, and face batches that pack only the faces that pass a gate on them, all on
+ * the device (DESIGN.md "Face quality" holds the definition; tests/face_quality_ref.py restates it in numpy; nothing carries a tolerance).
+ * For a face with crop size S (the crop is exactly the one of the calls above):
+ *   luma          Y = (29 B + 150 G + 77 R + 128) >> 8 of the u8 BGR crop pixel;  sum_luma = the sum of Y over the S x S crop
+ *   Laplacian     L = 4 Y(u,v) - Y(u-1,v) - Y(u+1,v) - Y(u,v-1) - Y(u,v+1) on 1 <= u, v <= S - 2; sum_lap, sum_lap2 = the sums of L, L^2
+ *   sharpness     the variance of L: (double)(n sum_lap2 - sum_lap^2) / ((double)n (double)n), n = (S - 2)^2, the integers in int64
+ *   covered       crop pixels sampled inside the frame (the in-range test of the crop holds and the top-left tap is a frame pixel)
+ *   iod2          squared distance of the eyes in source pixels;  yaw: the nose's offset from the eyes' midpoint along the eye axis,
+ *                 in eye distances (0 frontal, +-0.5 over an eye);  sin2_roll: sin^2 of the in-plane rotation
+ * An invalid face (rf_align_matrix returns 0) has every number 0. */
+typedef struct rf_face_quality {   /* 64 bytes */
+    int32_t flags;                 /* 0 = kept; else OR of the RF_GATE_* that failed */
+    int32_t covered;
+    int64_t sum_luma, sum_lap, sum_lap2;
+    double sharpness, iod2, yaw, sin2_roll;
+} rf_face_quality;
+enum { RF_GATE_INVALID = 1, RF_GATE_SHARPNESS = 2, RF_GATE_IOD = 4, RF_GATE_YAW = 8, RF_GATE_ROLL = 16, RF_GATE_COVERED = 32,
+       RF_GATE_DARK = 64, RF_GATE_BRIGHT = 128 };
+/* Every field: 0 = that gate is off.  Floats are widened to double before use; the comparisons are written so that NaN and infinity
+ * fail; ALL failing bits are set.  With a gate, an invalid face always fails with RF_GATE_INVALID (and whatever its zeros fail). */
+typedef struct rf_face_gate {
+    uint32_t struct_size;          /* sizeof(rf_face_gate) */
+    float min_sharpness;           /* fails if !(sharpness >= min) */
+    float min_iod;                 /* source pixels; fails if !(iod2 >= (double)min * (double)min) */
+    float max_abs_yaw;             /* fails if !(yaw >= -max && yaw <= max) */
+    float max_sin2_roll;           /* fails if !(sin2_roll <= max) */
+    float min_covered;             /* fraction of the crop; fails if !((double)covered >= (double)min * (double)(S * S)) */
+    float min_luma, max_luma;      /* mean luma: (double)sum_luma against (double)x * (double)(S * S); RF_GATE_DARK / RF_GATE_BRIGHT */
+} rf_face_gate;
+
+/* Host only, no GPU, no handle -- the same code the kernel runs, compiled for the host.
+ * rf_face_pose: zeroes *q, then fills iod2, yaw, sin2_roll, and flags = RF_GATE_INVALID for an invalid face.  crop_size 0 = 112.
+ * rf_face_gate_eval: the flags the gate gives record q (q->flags & RF_GATE_INVALID marks an invalid face); a NULL gate gives 0.
+ * RF_ERR_INVALID_ARG: a wrong struct_size, a negative or non-finite field, min_covered > 1, a crop_size outside 16..512. */
+int rf_face_pose(const rf_face *face, float coord_scale, int crop_size, rf_face_quality *q);
+int rf_face_gate_eval(const rf_face_gate *gate, const rf_face_quality *q, int crop_size);
+
+/* The quality records of faces the CALLER supplies (arguments as rf_align_batch_device); no tensor is written.  quality: host,
+ * n * max_faces records; face k < min(counts[i], max_faces) of image i is record i * max_faces + k, the other records are
+ * unspecified.  gate may be NULL (flags 0).  A bad gate is refused before any state changes. */
+int rf_face_quality_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                           const rf_face *faces, int cap_per_image, const int *counts, const float *coord_scale, int crop_size,
+                           int max_faces, const rf_face_gate *gate, rf_face_quality *quality);
+
+/* The face-batch calls above behind a quality gate.  Face k of image i is CONSIDERED when k < m_i and KEPT when its flags are 0;
+ * offsets[i+1] = offsets[i] + kept_i, the kept faces of an image stay in score order; tensor, matrices, total, capacity and
+ * RF_ERR_TRUNCATED behave as above, counted over kept faces.  quality (host, n * max_faces records with the spec's max_faces, may
+ * be NULL) receives the record of every considered face, kept or dropped, at i * max_faces + k.  A NULL gate keeps every face: the
+ * tensor, matrices and offsets are the bytes of the ungated call.  Gating never changes out / counts / rf_last_anchor_indices. */
+int rf_face_batch_gated_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                               const rf_face *faces, int cap_per_image, const int *counts, const float *coord_scale,
+                               const rf_face_batch_spec *spec, void *d_tensor, void *tensor, double *matrices, int *offsets,
+                               const rf_face_gate *gate, rf_face_quality *quality);
+int rf_detect_face_batch_gated_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                      float threshold, rf_face *out, int cap_per_image, int *counts, const rf_face_batch_spec *spec,
+                                      void *d_tensor, void *tensor, double *matrices, int *offsets, const rf_face_gate *gate,
+                                      rf_face_quality *quality);
+int rf_detect_face_batch_gated(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                               float threshold, rf_face *out, int cap_per_image, int *counts, const rf_face_batch_spec *spec,
+                               void *d_tensor, void *tensor, double *matrices, int *offsets, const rf_face_gate *gate,
+                               rf_face_quality *quality);
+
 /* Asynchronous form of rf_detect_batch_device for serving loops: enqueue returns as soon as the
  * batch is queued on the engine's stream (n <= max_batch); `ticket` identifies one of
  * rf_num_slots() result slots.  rf_wait blocks until that batch has finished and copies its results.

@@ -41,6 +41,20 @@ class rf_face_batch_spec(C.Structure):
 
 RF_FACES_U8_HWC, RF_FACES_F16_CHW, RF_FACES_F32_CHW = 0, 1, 2
 
+
+class rf_face_quality(C.Structure):
+    _fields_ = [("flags", C.c_int32), ("covered", C.c_int32), ("sum_luma", C.c_int64), ("sum_lap", C.c_int64), ("sum_lap2", C.c_int64),
+                ("sharpness", C.c_double), ("iod2", C.c_double), ("yaw", C.c_double), ("sin2_roll", C.c_double)]
+
+
+class rf_face_gate(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("min_sharpness", C.c_float), ("min_iod", C.c_float), ("max_abs_yaw", C.c_float),
+                ("max_sin2_roll", C.c_float), ("min_covered", C.c_float), ("min_luma", C.c_float), ("max_luma", C.c_float)]
+
+
+RF_GATE_INVALID, RF_GATE_SHARPNESS, RF_GATE_IOD, RF_GATE_YAW, RF_GATE_ROLL, RF_GATE_COVERED, RF_GATE_DARK, RF_GATE_BRIGHT = (
+    1, 2, 4, 8, 16, 32, 64, 128)
+
 # every symbol include/retinaface_amd.h declares: name -> (restype, argtypes)
 _PP = C.POINTER
 SYMBOLS = {
@@ -78,6 +92,23 @@ SYMBOLS = {
     "rf_face_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
                                        _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_float), _PP(rf_face_batch_spec),
                                        C.c_void_p, C.c_void_p, _PP(C.c_double), _PP(C.c_int)]),
+    "rf_face_pose": (C.c_int, [_PP(rf_face), C.c_float, C.c_int, _PP(rf_face_quality)]),
+    "rf_face_gate_eval": (C.c_int, [_PP(rf_face_gate), _PP(rf_face_quality), C.c_int]),
+    "rf_face_quality_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                         _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_float), C.c_int, C.c_int,
+                                         _PP(rf_face_gate), _PP(rf_face_quality)]),
+    "rf_face_batch_gated_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                             _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_float), _PP(rf_face_batch_spec),
+                                             C.c_void_p, C.c_void_p, _PP(C.c_double), _PP(C.c_int), _PP(rf_face_gate),
+                                             _PP(rf_face_quality)]),
+    "rf_detect_face_batch_gated_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                                    C.c_float, _PP(rf_face), C.c_int, _PP(C.c_int), _PP(rf_face_batch_spec),
+                                                    C.c_void_p, C.c_void_p, _PP(C.c_double), _PP(C.c_int), _PP(rf_face_gate),
+                                                    _PP(rf_face_quality)]),
+    "rf_detect_face_batch_gated": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                             C.c_float, _PP(rf_face), C.c_int, _PP(C.c_int), _PP(rf_face_batch_spec),
+                                             C.c_void_p, C.c_void_p, _PP(C.c_double), _PP(C.c_int), _PP(rf_face_gate),
+                                             _PP(rf_face_quality)]),
     "rf_num_slots": (C.c_int, [C.c_void_p]),
     "rf_enqueue_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int),
                                           C.c_int, C.c_float, _PP(C.c_int)]),

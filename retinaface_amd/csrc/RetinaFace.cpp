@@ -98,7 +98,19 @@ vector<cv::Mat> RetinaFace::detectAndAlign(const Mat &img, float threshold, int 
 }
 
 vector<uint8_t> RetinaFace::detectFaceBatch(const vector<cv::Mat> &imgs, float threshold, const rf_face_batch_spec &spec) {
+    return faceBatchCall(imgs, threshold, spec, false, nullptr);
+}
+
+vector<uint8_t> RetinaFace::detectFaceBatchGated(const vector<cv::Mat> &imgs, float threshold, const rf_face_batch_spec &spec,
+                                                 const rf_face_gate *gate) {
+    return faceBatchCall(imgs, threshold, spec, true, gate);
+}
+
+vector<uint8_t> RetinaFace::faceBatchCall(const vector<cv::Mat> &imgs, float threshold, const rf_face_batch_spec &spec, bool gated,
+                                          const rf_face_gate *gate) {
     const int n = (int)imgs.size();
+    faceQuality_.clear();
+    faceQualityStride_ = 0;
     lastBatch_.assign(n, vector<FaceDetectInfo>());
     faceOffsets_.assign((size_t)n + 1, 0);
     faceMats_.clear();
@@ -114,10 +126,20 @@ vector<uint8_t> RetinaFace::detectFaceBatch(const vector<cv::Mat> &imgs, float t
     vector<rf_face> faces((size_t)n * maxDet_);
     vector<uint8_t> tensor((size_t)spec.capacity * bpf);
     vector<double> mats((size_t)spec.capacity * 6);
-    check(rf_detect_face_batch(h_, ptrs.data(), rows.data(), cols.data(), steps.data(), n, threshold, faces.data(), maxDet_, counts.data(),
-                               &spec, nullptr, tensor.data(), mats.data(), faceOffsets_.data()), h_, "RetinaFace::detectFaceBatch");
+    if (gated) {
+        faceQualityStride_ = spec.max_faces ? spec.max_faces : maxDet_;
+        faceQuality_.assign((size_t)n * faceQualityStride_, rf_face_quality());
+        check(rf_detect_face_batch_gated(h_, ptrs.data(), rows.data(), cols.data(), steps.data(), n, threshold, faces.data(), maxDet_,
+                                         counts.data(), &spec, nullptr, tensor.data(), mats.data(), faceOffsets_.data(), gate,
+                                         faceQuality_.data()), h_, "RetinaFace::detectFaceBatchGated");
+    } else {
+        check(rf_detect_face_batch(h_, ptrs.data(), rows.data(), cols.data(), steps.data(), n, threshold, faces.data(), maxDet_, counts.data(),
+                                   &spec, nullptr, tensor.data(), mats.data(), faceOffsets_.data()), h_, "RetinaFace::detectFaceBatch");
+    }
     for (int i = 0; i < n; i++) {
         int k = counts[i] < maxDet_ ? counts[i] : maxDet_;
+        for (int j = k < faceQualityStride_ ? k : faceQualityStride_; j < faceQualityStride_; j++)
+            faceQuality_[(size_t)i * faceQualityStride_ + j] = rf_face_quality();      // slots without a considered face
         lastBatch_[i].resize(k);
         if (k) memcpy(lastBatch_[i].data(), &faces[(size_t)i * maxDet_], (size_t)k * sizeof(rf_face));
     }

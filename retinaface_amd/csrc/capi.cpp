@@ -356,6 +356,106 @@ int rf_face_batch_device(rf_handle h, const void *const *d_bgr, const int *rows,
     });
 }
 
+// ---- face quality and gated face batches (face_quality.h)
+namespace {
+// the gate half of a gated request; a bad gate is refused here, before the engine is touched
+void face_gate_request(const rf_face_gate *gate, rf_face_quality *quality, rf::FaceBatchRequest *rq) {
+    rq->gated = true;
+    rq->has_gate = gate != nullptr;
+    if (gate)
+        if (const char *bad = rf::face_gate_resolve(gate, &rq->gate)) throw rf::ArgError(bad);
+    rq->quality = quality;
+}
+
+int detect_face_batch_gated_common(rf_handle h, const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n,
+                                   bool on_device, float thr, rf_face *out, int cap, int *counts, const rf_face_batch_spec *spec,
+                                   void *d_tensor, void *tensor, double *matrices, int *offsets, const rf_face_gate *gate,
+                                   rf_face_quality *quality) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        rf::FaceBatchRequest rq;
+        face_batch_request(spec, h->eng->default_max_faces(), d_tensor, tensor, matrices, offsets, &rq);
+        face_gate_request(gate, quality, &rq);
+        bool tr = false, over = false;
+        h->eng->detect_face_batch(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, rq, &over);
+        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        if (over) { h->error = kFaceOverflow; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+}  // namespace
+
+int rf_face_pose(const rf_face *face, float coord_scale, int crop_size, rf_face_quality *q) {
+    if (!face || !q) return RF_ERR_INVALID_ARG;
+    const int S = crop_size ? crop_size : rf::kFaceBatchDefaultCrop;
+    if (S < rf::kAlignMinCrop || S > rf::kAlignMaxCrop) return RF_ERR_INVALID_ARG;
+    rf::AlignXform t;
+    const int ok = rf::align_estimate(face->px, face->py, coord_scale, S, &t);
+    memset(q, 0, sizeof(*q));
+    rf::face_pose(face->px, face->py, coord_scale, t, q);
+    q->flags = ok ? 0 : RF_GATE_INVALID;
+    return RF_OK;
+}
+
+int rf_face_gate_eval(const rf_face_gate *gate, const rf_face_quality *q, int crop_size) {
+    if (!q) return RF_ERR_INVALID_ARG;
+    const int S = crop_size ? crop_size : rf::kFaceBatchDefaultCrop;
+    if (S < rf::kAlignMinCrop || S > rf::kAlignMaxCrop) return RF_ERR_INVALID_ARG;
+    if (!gate) return 0;
+    rf::FaceGate g;
+    if (rf::face_gate_resolve(gate, &g)) return RF_ERR_INVALID_ARG;
+    return rf::face_gate_eval(g, *q, (q->flags & RF_GATE_INVALID) != 0, S);
+}
+
+int rf_face_quality_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                           const rf_face *faces, int cap_per_image, const int *counts, const float *coord_scale, int crop_size,
+                           int max_faces, const rf_face_gate *gate, rf_face_quality *quality) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        if (!quality) throw rf::ArgError("quality is null");
+        rf::FaceBatchRequest rq;                       // no tensor, no matrices: the records alone
+        rq.spec.crop = crop_size ? crop_size : rf::kFaceBatchDefaultCrop;
+        rq.spec.max_faces = max_faces;
+        rq.spec.capacity = 1;
+        face_gate_request(gate, quality, &rq);
+        bool over = false;
+        h->eng->face_batch(d_bgr, rows, cols, steps, n, faces, cap_per_image, counts, coord_scale, rq, &over);
+        return RF_OK;
+    });
+}
+
+int rf_face_batch_gated_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                               const rf_face *faces, int cap_per_image, const int *counts, const float *coord_scale,
+                               const rf_face_batch_spec *spec, void *d_tensor, void *tensor, double *matrices, int *offsets,
+                               const rf_face_gate *gate, rf_face_quality *quality) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        rf::FaceBatchRequest rq;
+        face_batch_request(spec, h->eng->default_max_faces(), d_tensor, tensor, matrices, offsets, &rq);
+        face_gate_request(gate, quality, &rq);
+        bool over = false;
+        h->eng->face_batch(d_bgr, rows, cols, steps, n, faces, cap_per_image, counts, coord_scale, rq, &over);
+        if (over) { h->error = kFaceOverflow; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+
+int rf_detect_face_batch_gated_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                      float threshold, rf_face *out, int cap_per_image, int *counts, const rf_face_batch_spec *spec,
+                                      void *d_tensor, void *tensor, double *matrices, int *offsets, const rf_face_gate *gate,
+                                      rf_face_quality *quality) {
+    return detect_face_batch_gated_common(h, (const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, out, cap_per_image,
+                                          counts, spec, d_tensor, tensor, matrices, offsets, gate, quality);
+}
+
+int rf_detect_face_batch_gated(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                               float threshold, rf_face *out, int cap_per_image, int *counts, const rf_face_batch_spec *spec,
+                               void *d_tensor, void *tensor, double *matrices, int *offsets, const rf_face_gate *gate,
+                               rf_face_quality *quality) {
+    return detect_face_batch_gated_common(h, bgr, rows, cols, steps, n, false, threshold, out, cap_per_image, counts, spec, d_tensor,
+                                          tensor, matrices, offsets, gate, quality);
+}
+
 int rf_num_slots(rf_handle h) { return h ? h->eng->num_slots() : RF_ERR_INVALID_ARG; }
 
 int rf_enqueue_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps,

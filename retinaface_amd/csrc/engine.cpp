@@ -207,7 +207,7 @@ public:
         for (void *p : dev_allocs_) (void)hipFree(p);
         for (void *p : host_allocs_) (void)hipHostFree(p);
         if (align_stream_) { (void)hipStreamSynchronize(align_stream_); (void)hipStreamDestroy(align_stream_); }
-        for (DeviceScratch *b : {&align_crops_, &align_mats_, &align_tab_, &fb_state_}) b->release();
+        for (DeviceScratch *b : {&align_crops_, &align_mats_, &align_tab_, &fb_state_, &fq_records_, &fq_packed_, &fq_offsets_}) b->release();
         kind_.arena->release();
         for (auto &e : prof_ev_) (void)hipEventDestroy(e);
     }
@@ -385,6 +385,45 @@ public:
         if (!fb_state_.ptr) RF_HIP(hipMemset(fb_state_.reserve(256), 0, 256));
     }
 
+    // device blocks of a gated call: quality records and packed indices per face slot, the call's packed offsets
+    void face_gate_open(const FaceBatchRequest &rq, int n) {
+        const size_t slots = (size_t)std::max(n, 1) * rq.spec.max_faces;
+        fq_records_.reserve(slots * sizeof(rf_face_quality));
+        fq_packed_.reserve(slots * sizeof(int));
+        fq_offsets_.reserve(((size_t)n + 1) * sizeof(int));
+    }
+
+    // results of a finished gated call: the device's offsets (the host cannot derive them from counts), the packed faces that exist,
+    // the records of the considered slots (counts[i] clamped to limit).  A record block that is small or at least half
+    // considered travels as one copy instead of one per image.
+    void face_gated_copy_out(const FaceBatchRequest &rq, const uint8_t *d_tensor, const double *d_mats, const int *counts, int n, int limit,
+                             bool *overflow) {
+        std::vector<int> off((size_t)n + 1, 0);
+        if (n > 0) RF_HIP(hipMemcpy(off.data(), fq_offsets_.ptr, off.size() * sizeof(int), hipMemcpyDeviceToHost));
+        if (rq.offsets) memcpy(rq.offsets, off.data(), off.size() * sizeof(int));
+        const long total = off[n];
+        const size_t written = (size_t)std::min<long>(total, rq.spec.capacity);
+        *overflow = total > rq.spec.capacity;
+        if (written) {
+            if (rq.tensor && d_tensor) RF_HIP(hipMemcpy(rq.tensor, d_tensor, written * rq.spec.bytes_per_face(), hipMemcpyDeviceToHost));
+            if (rq.matrices && d_mats) RF_HIP(hipMemcpy(rq.matrices, d_mats, written * 6 * sizeof(double), hipMemcpyDeviceToHost));
+        }
+        if (!rq.quality || n == 0) return;
+        const size_t mf = (size_t)rq.spec.max_faces, all = (size_t)n * mf;
+        size_t considered = 0;
+        for (int i = 0; i < n; i++) considered += (size_t)std::max(0, std::min(counts[i], limit));
+        if (!considered) return;
+        const rf_face_quality *d_rec = (const rf_face_quality *)fq_records_.ptr;
+        if (all * sizeof(rf_face_quality) <= (1u << 20) || considered * 2 >= all) {
+            RF_HIP(hipMemcpy(rq.quality, d_rec, all * sizeof(rf_face_quality), hipMemcpyDeviceToHost));
+            return;
+        }
+        for (int i = 0; i < n; i++) {
+            const int m = std::max(0, std::min(counts[i], limit));
+            if (m) RF_HIP(hipMemcpy(rq.quality + i * mf, d_rec + i * mf, (size_t)m * sizeof(rf_face_quality), hipMemcpyDeviceToHost));
+        }
+    }
+
     // results of a finished face-batch call to the caller's host buffers: the packed faces that exist, nothing behind them
     void face_batch_copy_out(const FaceBatchRequest &rq, const uint8_t *d_tensor, const double *d_mats, const int *counts, int n, int limit,
                              bool *overflow) {
@@ -410,15 +449,18 @@ public:
         uint8_t *d_tensor = nullptr;
         double *d_mats = nullptr;
         face_batch_open(rq, &d_tensor, &d_mats);
+        if (rq.gated) face_gate_open(rq, n);
         fb_.rq = rq;
         fb_.d_tensor = d_tensor; fb_.d_mats = d_mats;
-        fb_.first = true; fb_.prev_scan = nullptr;
+        fb_.first = true; fb_.prev_scan = nullptr; fb_.next_image = 0;
         fb_.on = true;
         struct Off { bool &on; ~Off() { on = false; } } off{fb_.on};
         detect(frames, rows, cols, steps, n, on_device, threshold, out, cap_per_image, counts, truncated);
         fb_.on = false;
         // every launch of the call has been waited for (its `done` event follows the tensor launch); an empty frame has count 0
-        face_batch_copy_out(rq, d_tensor, d_mats, counts, n, std::min(rq.spec.max_faces, opt_.max_detections), overflow);
+        // (under a gate: the images of an empty frame hold no considered face either)
+        if (rq.gated) face_gated_copy_out(rq, d_tensor, d_mats, counts, n, std::min(rq.spec.max_faces, opt_.max_detections), overflow);
+        else face_batch_copy_out(rq, d_tensor, d_mats, counts, n, std::min(rq.spec.max_faces, opt_.max_detections), overflow);
     }
 
     void face_batch(const void *const *frames, const int *rows, const int *cols, const int *steps, int n, const rf_face *faces,
@@ -432,6 +474,7 @@ public:
         *overflow = false;
         if (n == 0) { if (rq.offsets) rq.offsets[0] = 0; return; }
         DeviceGuard guard(device_);
+        if (rq.gated) face_gate_open(rq, n);
         const int fpi = std::min(cap_per_image, rq.spec.max_faces);     // records per image that travel to the device
         // one table: frames | counts | scales | offsets (written by the scan) | faces (60-byte records)
         const int per = std::min(n, kAlignImagesPerLaunch);
@@ -460,10 +503,42 @@ public:
         uint8_t *d_tensor = nullptr;
         double *d_mats = nullptr;
         face_batch_open(rq, &d_tensor, &d_mats);
-        if (d_tensor || d_mats) {
+        if (d_tensor || d_mats || rq.gated) {
             if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
             RF_HIP(hipMemcpyAsync(d_tab, align_host_.data(), total, hipMemcpyHostToDevice, align_stream_));
             for (int base = 0; base < n; base += per) {          // one stream: the scans and the tensor launches run in order
+                if (rq.gated) {
+                    FaceQualityParams qp;
+                    qp.frames = (const FrameDesc *)d_tab + base;
+                    qp.faces = d_tab + o_face + (size_t)base * fpi * sizeof(rf_face);
+                    qp.face_stride = (int)sizeof(rf_face); qp.faces_per_image = fpi;
+                    qp.counts = (const int *)(d_tab + o_cnt) + base;
+                    qp.scale = (const float *)(d_tab + o_sc) + base;
+                    qp.n = std::min(per, n - base); qp.max_faces = rq.spec.max_faces; qp.crop = rq.spec.crop;
+                    qp.has_gate = rq.has_gate ? 1 : 0; qp.gate = rq.gate;
+                    qp.records = (rf_face_quality *)fq_records_.ptr + (size_t)base * rq.spec.max_faces;
+                    launch_face_quality(align_stream_, qp);
+                    FaceGateScanParams gp;
+                    gp.frames = qp.frames; gp.counts = qp.counts;
+                    gp.n = qp.n; gp.faces_per_image = fpi; gp.max_faces = rq.spec.max_faces;
+                    gp.records = qp.records;
+                    gp.running = (int *)fb_state_.ptr; gp.first = base == 0;
+                    gp.offsets = (int *)fq_offsets_.ptr + base;
+                    gp.packed = (int *)fq_packed_.ptr + (size_t)base * rq.spec.max_faces;
+                    launch_face_gate_scan(align_stream_, gp);
+                    if (d_tensor || d_mats) {
+                        FaceBatchParams bp;
+                        bp.frames = qp.frames; bp.faces = qp.faces;
+                        bp.face_stride = qp.face_stride; bp.faces_per_image = fpi;
+                        bp.scale = qp.scale;
+                        bp.offsets = gp.offsets; bp.packed = gp.packed;
+                        bp.n = qp.n; bp.max_faces = rq.spec.max_faces;
+                        bp.spec = rq.spec;
+                        bp.tensor = d_tensor; bp.mats = d_mats;
+                        launch_face_batch(align_stream_, bp);
+                    }
+                    continue;
+                }
                 FaceScanParams sp;
                 sp.frames = (const FrameDesc *)d_tab + base;
                 sp.counts = (const int *)(d_tab + o_cnt) + base;
@@ -485,7 +560,8 @@ public:
             RF_HIP(hipGetLastError());
             RF_HIP(hipStreamSynchronize(align_stream_));
         }
-        face_batch_copy_out(rq, d_tensor, d_mats, cnt, n, rq.spec.max_faces, overflow);
+        if (rq.gated) face_gated_copy_out(rq, d_tensor, d_mats, cnt, n, rq.spec.max_faces, overflow);
+        else face_batch_copy_out(rq, d_tensor, d_mats, cnt, n, rq.spec.max_faces, overflow);
     }
 
     void host_register(const void *ptr, size_t bytes) override {
@@ -1069,6 +1145,47 @@ private:
             RF_HIP(hipEventCreateWithFlags(&s.face_scan_done, hipEventDisableTiming));
         }
         const FaceBatchSpec &spec = fb_.rq.spec;
+        if (fb_.rq.gated) {
+            // quality kernel first: it needs nothing of the call's earlier launches and runs while their scans finish
+            const size_t slot0 = (size_t)fb_.next_image * spec.max_faces;
+            FaceQualityParams qp;
+            qp.frames = s.d_frames;
+            qp.faces = (const uint8_t *)s.h_out;
+            qp.face_stride = (int)sizeof(Candidate); qp.faces_per_image = opt_.max_detections;
+            qp.counts = s.h_counts;
+            qp.scale = s.h_align_scale;
+            qp.n = n; qp.max_faces = spec.max_faces; qp.crop = spec.crop;
+            qp.has_gate = fb_.rq.has_gate ? 1 : 0; qp.gate = fb_.rq.gate;
+            qp.records = (rf_face_quality *)fq_records_.ptr + slot0;
+            launch_face_quality(s.stream, qp);
+            if (fb_.prev_scan && fb_.prev_scan != s.face_scan_done) RF_HIP(hipStreamWaitEvent(s.stream, fb_.prev_scan, 0));
+            FaceGateScanParams gp;
+            gp.frames = s.d_frames; gp.counts = s.h_counts;
+            gp.n = n; gp.faces_per_image = opt_.max_detections; gp.max_faces = spec.max_faces;
+            gp.records = qp.records;
+            gp.running = (int *)fb_state_.ptr; gp.first = fb_.first;
+            gp.offsets = (int *)fq_offsets_.ptr + fb_.next_image;
+            gp.packed = (int *)fq_packed_.ptr + slot0;
+            launch_face_gate_scan(s.stream, gp);
+            RF_HIP(hipEventRecord(s.face_scan_done, s.stream));
+            fb_.prev_scan = s.face_scan_done;
+            fb_.first = false;
+            fb_.next_image += n;
+            if (fb_.d_tensor || fb_.d_mats) {
+                FaceBatchParams bp;
+                bp.frames = s.d_frames;
+                bp.faces = (const uint8_t *)s.h_out;
+                bp.face_stride = (int)sizeof(Candidate); bp.faces_per_image = opt_.max_detections;
+                bp.scale = s.h_align_scale;
+                bp.offsets = gp.offsets; bp.packed = gp.packed;
+                bp.n = n; bp.max_faces = spec.max_faces;
+                bp.spec = spec;
+                bp.tensor = fb_.d_tensor; bp.mats = fb_.d_mats;
+                launch_face_batch(s.stream, bp);
+            }
+            RF_HIP(hipGetLastError());
+            return;
+        }
         if (fb_.prev_scan && fb_.prev_scan != s.face_scan_done) RF_HIP(hipStreamWaitEvent(s.stream, fb_.prev_scan, 0));
         FaceScanParams sp;
         sp.frames = s.d_frames;
@@ -1339,7 +1456,10 @@ private:
     struct { bool on = false; AlignRequest rq; uint8_t *d_crops = nullptr; double *d_mats = nullptr; int next_image = 0; } align_;
     // face batches: the running base of packed offsets (one device int), and the request detect_face_batch() has open
     DeviceScratch fb_state_;
-    struct { bool on = false, first = true; FaceBatchRequest rq; uint8_t *d_tensor = nullptr; double *d_mats = nullptr; hipEvent_t prev_scan = nullptr; } fb_;
+    struct { bool on = false, first = true; FaceBatchRequest rq; uint8_t *d_tensor = nullptr; double *d_mats = nullptr; hipEvent_t prev_scan = nullptr;
+             int next_image = 0; } fb_;
+    // gated face batches: quality records and packed indices per face slot of the call, the call's packed offsets
+    DeviceScratch fq_records_, fq_packed_, fq_offsets_;
 
     int last_n_ = 0;
     std::vector<int> last_cand_counts_;

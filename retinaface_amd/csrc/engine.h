@@ -88,6 +88,10 @@ struct FaceBatchRequest {
     uint8_t *d_tensor = nullptr, *tensor = nullptr;
     double *matrices = nullptr;
     int *offsets = nullptr;
+    // the gated calls (face_quality.h): quality records of every considered face, only the faces whose flags are 0 are packed
+    bool gated = false, has_gate = false;       // has_gate false: flags stay 0, every face is kept
+    FaceGate gate;
+    rf_face_quality *quality = nullptr;         // host, n * spec.max_faces records, or nullptr
 };
 
 class Engine {

@@ -9,6 +9,7 @@
 
 #include "align.h"
 #include "face_batch.h"
+#include "face_quality.h"
 
 namespace rf {
 
@@ -214,14 +215,45 @@ struct FaceBatchParams {
     const uint8_t *faces;
     int face_stride, faces_per_image;
     const float *scale;
-    const int *offsets;                   // [n + 1], what launch_face_scan wrote
+    const int *offsets;                   // [n + 1], what launch_face_scan wrote (not read when packed is set)
     int n, max_faces;
     FaceBatchSpec spec;                   // crop edge, format, channel order, mean / scale, capacity
     void *tensor;                         // [capacity] faces of 3 * S * S elements, aligned to the element size, or nullptr
     double *mats;                         // [capacity][6], or nullptr
+    const int *packed = nullptr;          // gated: packed index of (image i, face k) at packed[i * max_faces + k], -1 = not packed
+                                          // (what launch_face_gate_scan wrote); nullptr: offsets[i] + k
 };
 void launch_face_batch(hipStream_t s, const FaceBatchParams &p);
 int face_batch_band_rows(int crop, int format);      // crop rows one workgroup covers (exposed for tests and DESIGN.md)
+
+// ---- K_h: face quality (face_quality.h) -- one 64-byte record per considered face: integer sums over the luma of its crop (the
+//      transform and sampling of K_f), landmark numbers, and the flags of the call's gate.  launch_face_gate_scan is the keep-mask
+//      counterpart of launch_face_scan: it packs the faces whose flags are 0.
+struct FaceQualityParams {
+    const FrameDesc *frames;              // as AlignParams
+    const uint8_t *faces;
+    int face_stride, faces_per_image;
+    const int *counts;                    // [n] faces of each image (clamped to faces_per_image and max_faces here)
+    const float *scale;
+    int n, max_faces, crop;
+    int has_gate;                         // 0: flags stay 0
+    FaceGate gate;
+    rf_face_quality *records;             // [n * max_faces] out: (image i, face k) at i * max_faces + k; considered faces only
+};
+void launch_face_quality(hipStream_t s, const FaceQualityParams &p);
+
+struct FaceGateScanParams {
+    const FrameDesc *frames;              // as FaceScanParams
+    const int *counts;
+    int n, faces_per_image, max_faces;
+    const rf_face_quality *records;       // [n * max_faces], what launch_face_quality wrote
+    int *running;                         // as FaceScanParams
+    int first;
+    int *offsets;                         // [n + 1] out: packed index of each image's first kept face
+    int *packed;                          // [n * max_faces] out: packed index of every slot k < min(max_faces, faces_per_image), -1 = none
+};
+void launch_face_gate_scan(hipStream_t s, const FaceGateScanParams &p);
+int face_quality_ring_rows(int crop);                // luma rows the quality kernel holds in LDS (exposed for tests and DESIGN.md)
 
 // LDS bytes / tile geometry chosen for a layer (exposed for tests and DESIGN.md tables)
 struct TileInfo { int th, tw; size_t lds_bytes; int blocks_per_image; };

@@ -4187,9 +4187,15 @@ __global__ __launch_bounds__(kThreads) void face_batch_kernel(FaceBatchParams a,
     __shared__ AlignXform xf;
     __shared__ uint4 band_buf[kFaceLdsVecs];
     const int band = blockIdx.x, k = blockIdx.y, img = blockIdx.z;
-    const int first = a.offsets[img];
-    if (k >= a.offsets[img + 1] - first) return;
-    const int j = first + k;
+    int j;
+    if (a.packed) {
+        j = a.packed[(size_t)img * a.max_faces + k];
+        if (j < 0) return;
+    } else {
+        const int first = a.offsets[img];
+        if (k >= a.offsets[img + 1] - first) return;
+        j = first + k;
+    }
     if (j >= a.spec.capacity) return;
     const FrameDesc fd = a.frames[img];
     if (fd.ptr == nullptr || fd.rows <= 0 || fd.cols <= 0) return;
@@ -4248,6 +4254,161 @@ void launch_face_batch(hipStream_t s, const FaceBatchParams &p) {
     else if (sp.format == RF_FACES_F16_CHW) hipLaunchKernelGGL((face_batch_kernel<half_t, true>), grid, dim3(kThreads), 0, s, p, rows);
     else if (sp.format == RF_FACES_F32_CHW) hipLaunchKernelGGL((face_batch_kernel<float, true>), grid, dim3(kThreads), 0, s, p, rows);
     else throw Unsupported("face batch: unknown format");
+}
+
+// =============================================================================================
+// K_h: face quality (face_quality.h): one workgroup = one (image, considered face).  Thread 0 estimates the similarity and the
+//      landmark numbers; the workgroup walks the crop in bands of rows, samples each pixel with align_sample and keeps only its
+//      luma, in a ring of rows in LDS: a band's Laplacian needs one row above and one below, and the last two rows of the previous
+//      band are still in the ring, so no row is sampled twice.  Every statistic is an integer sum: 64-bit per thread where a
+//      thread's share can pass 2^31, reduced with wave shuffles and one LDS step -- the same integers whatever the order, no
+//      atomics, nothing to zero beforehand.  Thread 0 finishes the record, evaluates the gate and stores the 64 bytes.
+//      face_gate_scan_kernel (one workgroup): kept faces per image from the records' flags, their prefix sum on top of the call's
+//      running base (the protocol of face_scan_kernel), and the packed index of every face slot for face_batch_kernel.
+// =============================================================================================
+constexpr int kQualityRingBytes = 8192;
+
+int face_quality_ring_rows(int crop) {
+    const int rows = kQualityRingBytes / crop;
+    return rows < crop + 2 ? rows : crop + 2;
+}
+
+// Whether align_sample's crop pixel (u, v) is sampled inside the frame: its in-range test holds and its rounded top-left tap (x0, y0)
+// is a pixel of the frame.  The position is align_sample's own arithmetic, expression for expression (inlined next to it, the compiler
+// shares the two); align_sample itself stays as K_f and K_g use it.
+__device__ __forceinline__ int align_covered(const FrameDesc &fd, const AlignSampler &sm, int u, int v) {
+#pragma clang fp contract(off)
+    const double du = (double)u - sm.mqx, dv = (double)v - sm.mqy;
+    const double x = (sm.ia * du - sm.ib * dv) + sm.mpx;
+    const double y = (sm.ib * du + sm.ia * dv) + sm.mpy;
+    if (!(sm.valid && x > -2.0 && x < sm.xmax && y > -2.0 && y < sm.ymax)) return 0;
+    const long long X = (long long)floor(x * 1024.0 + 0.5), Y = (long long)floor(y * 1024.0 + 0.5);
+    const int x0 = (int)(X >> 10), y0 = (int)(Y >> 10);
+    return (x0 >= 0 && x0 < fd.cols && y0 >= 0 && y0 < fd.rows) ? 1 : 0;
+}
+
+__device__ __forceinline__ long long wave_sum(long long v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(kThreads) void face_quality_kernel(FaceQualityParams a, int ring_rows) {
+#pragma clang fp contract(off)
+    __shared__ AlignXform xf;
+    __shared__ rf_face_quality rec;
+    __shared__ uint8_t ring[kQualityRingBytes];
+    __shared__ long long part[4][kThreads / 64];
+    const int k = blockIdx.x, img = blockIdx.y;
+    int cnt = a.counts[img];
+    cnt = cnt < a.faces_per_image ? cnt : a.faces_per_image;
+    cnt = cnt < a.max_faces ? cnt : a.max_faces;
+    if (k >= cnt) return;
+    const FrameDesc fd = a.frames[img];
+    if (fd.ptr == nullptr || fd.rows <= 0 || fd.cols <= 0) return;
+    const int S = a.crop;
+    if (threadIdx.x == 0) {
+        const float *f = (const float *)(a.faces + ((size_t)img * a.faces_per_image + k) * a.face_stride);
+        float px[5], py[5];
+        for (int i = 0; i < 5; i++) { px[i] = f[5 + i]; py[i] = f[10 + i]; }
+        const float cs = a.scale ? a.scale[img] : 1.f;
+        align_estimate(px, py, cs, S, &xf);
+        face_pose(px, py, cs, xf, &rec);
+    }
+    __syncthreads();
+    const AlignSampler sm(xf, fd);
+    const int R = ring_rows - 2, W = S - 2;                       // new rows per band; interior columns
+    long long s_luma = 0, s_lap = 0, s_lap2 = 0, s_cov = 0;
+    if (xf.valid) {                                               // uniform: an invalid face has every sum 0
+        for (int v0 = 0; v0 < S; v0 += R) {
+            const int hi = v0 + R < S ? v0 + R : S;
+            const int npix = (hi - v0) * S;
+            for (int p = threadIdx.x; p < npix; p += kThreads) {
+                const int v = v0 + p / S, u = p % S;
+                unsigned acc[3];
+                align_sample(fd, sm, u, v, acc);
+                const int cov = align_covered(fd, sm, u, v);
+                const unsigned y = face_luma(acc[0], acc[1], acc[2]);
+                ring[(v % ring_rows) * S + u] = (uint8_t)y;
+                s_luma += y; s_cov += cov;
+            }
+            __syncthreads();
+            // centre rows whose lower neighbour has just arrived: [max(v0 - 1, 1), hi - 1)
+            const int c0 = v0 - 1 > 1 ? v0 - 1 : 1;
+            const int nlap = (hi - 1 - c0) * W;
+            for (int p = threadIdx.x; p < nlap; p += kThreads) {
+                const int c = c0 + p / W, u = 1 + p % W;
+                const uint8_t *mid = ring + (c % ring_rows) * S + u;
+                const int L = 4 * (int)mid[0] - (int)mid[-1] - (int)mid[1] - (int)ring[((c - 1) % ring_rows) * S + u] -
+                              (int)ring[((c + 1) % ring_rows) * S + u];
+                s_lap += L; s_lap2 += (long long)(L * L);
+            }
+            __syncthreads();                                      // the next band overwrites rows this one has read
+        }
+    }
+    s_luma = wave_sum(s_luma); s_lap = wave_sum(s_lap); s_lap2 = wave_sum(s_lap2); s_cov = wave_sum(s_cov);
+    if ((threadIdx.x & 63) == 0) {
+        const int w = threadIdx.x >> 6;
+        part[0][w] = s_luma; part[1][w] = s_lap; part[2][w] = s_lap2; part[3][w] = s_cov;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long t[4];
+        for (int i = 0; i < 4; i++) t[i] = (part[i][0] + part[i][1]) + (part[i][2] + part[i][3]);
+        rf_face_quality q;
+        q.covered = (int)t[3];
+        q.sum_luma = t[0]; q.sum_lap = t[1]; q.sum_lap2 = t[2];
+        q.sharpness = xf.valid ? face_quality_finish(t[1], t[2], S) : 0.0;
+        q.iod2 = rec.iod2; q.yaw = rec.yaw; q.sin2_roll = rec.sin2_roll;
+        q.flags = a.has_gate ? face_gate_eval(a.gate, q, !xf.valid, S) : 0;
+        a.records[(size_t)img * a.max_faces + k] = q;
+    }
+}
+
+void launch_face_quality(hipStream_t s, const FaceQualityParams &p) {
+    if (p.n <= 0 || p.max_faces <= 0) return;
+    if (p.crop < kAlignMinCrop || p.crop > kAlignMaxCrop || p.max_faces > kAlignMaxFaces || p.n > 65535)
+        throw Unsupported("face quality: crop size, faces per image or images per launch out of range");
+    if (!p.records) throw Unsupported("face quality: no record buffer");
+    const int slots = p.max_faces < p.faces_per_image ? p.max_faces : p.faces_per_image;
+    if (slots <= 0) return;
+    hipLaunchKernelGGL(face_quality_kernel, dim3(slots, p.n), dim3(kThreads), 0, s, p, face_quality_ring_rows(p.crop));
+}
+
+__global__ __launch_bounds__(kThreads) void face_gate_scan_kernel(FaceGateScanParams a) {
+    __shared__ int part[kThreads];
+    const int limit = a.max_faces < a.faces_per_image ? a.max_faces : a.faces_per_image;
+    const int chunk = (a.n + kThreads - 1) / kThreads;
+    const int i0 = (int)threadIdx.x * chunk, i1 = i0 + chunk < a.n ? i0 + chunk : a.n;
+    auto faces_of = [&](int i) {
+        int c = a.counts[i];
+        c = c < 0 ? 0 : c < limit ? c : limit;
+        return a.frames[i].ptr == nullptr ? 0 : c;
+    };
+    int sum = 0;
+    for (int i = i0; i < i1; i++) {
+        const int m = faces_of(i);
+        const rf_face_quality *r = a.records + (size_t)i * a.max_faces;
+        for (int k = 0; k < m; k++) sum += r[k].flags == 0 ? 1 : 0;
+    }
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    int base = a.first ? 0 : *a.running;
+    for (int t = 0; t < (int)threadIdx.x; t++) base += part[t];
+    for (int i = i0; i < i1; i++) {
+        const int m = faces_of(i);
+        const rf_face_quality *r = a.records + (size_t)i * a.max_faces;
+        int *pk = a.packed + (size_t)i * a.max_faces;
+        a.offsets[i] = base;
+        for (int k = 0; k < limit; k++) pk[k] = (k < m && r[k].flags == 0) ? base++ : -1;
+    }
+    __syncthreads();                                             // every thread has read *running before it is advanced
+    if (threadIdx.x == kThreads - 1) { a.offsets[a.n] = base; *a.running = base; }
+}
+
+void launch_face_gate_scan(hipStream_t s, const FaceGateScanParams &p) {
+    if (p.n <= 0) return;
+    hipLaunchKernelGGL(face_gate_scan_kernel, dim3(1), dim3(kThreads), 0, s, p);
 }
 
 #ifdef RF_KERNEL_TRACE

@@ -14,7 +14,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import rf_face, rf_face_batch_spec, rf_options
+from ._lib import rf_face, rf_face_batch_spec, rf_face_gate, rf_face_quality, rf_options
 
 PRECISION_FP32, PRECISION_FP16, PRECISION_INT8 = 0, 1, 2
 
@@ -101,6 +101,55 @@ def face_value_table(channel: int, *, dtype: str = "f16", rgb: bool = True, mean
     if st < 0:
         raise _lib.RFError(st, "rf_face_value_table: bad spec or channel")
     return out
+
+
+# one rf_face_quality record (64 bytes)
+QUALITY_DTYPE = np.dtype([("flags", "<i4"), ("covered", "<i4"), ("sum_luma", "<i8"), ("sum_lap", "<i8"), ("sum_lap2", "<i8"),
+                          ("sharpness", "<f8"), ("iod2", "<f8"), ("yaw", "<f8"), ("sin2_roll", "<f8")])
+_GATE_FIELDS = ("min_sharpness", "min_iod", "max_abs_yaw", "max_sin2_roll", "min_covered", "min_luma", "max_luma")
+
+
+def face_gate(**kw) -> rf_face_gate:
+    """An rf_face_gate.  Keywords (each 0 / absent = that gate is off): min_sharpness (variance of the luma Laplacian of the crop),
+    min_iod (eye distance in source pixels), max_abs_yaw (nose offset along the eye axis, in eye distances), max_sin2_roll,
+    min_covered (fraction of the crop sampled inside the frame), min_luma / max_luma (mean luma of the crop)."""
+    g = rf_face_gate()
+    g.struct_size = C.sizeof(rf_face_gate)
+    for k, v in kw.items():
+        if k not in _GATE_FIELDS:
+            raise TypeError(f"face_gate: unknown field {k!r}")
+        setattr(g, k, float(v))
+    return g
+
+
+def _as_gate(gate):
+    if gate is None or isinstance(gate, rf_face_gate):
+        return gate
+    return face_gate(**gate)
+
+
+def face_pose(face, coord_scale: float = 1.0, crop_size: int = 112) -> np.ndarray:
+    """rf_face_pose (host only, no GPU): a QUALITY_DTYPE record with the landmark numbers of one face (iod2, yaw, sin2_roll) and
+    flags = RF_GATE_INVALID for an invalid face; the image numbers are 0."""
+    lib = _lib.load_library()
+    f = rf_face.from_buffer_copy(_face_rows([face])[0].tobytes())
+    q = np.zeros(1, QUALITY_DTYPE)
+    st = lib.rf_face_pose(C.byref(f), float(coord_scale), int(crop_size), q.ctypes.data_as(C.POINTER(rf_face_quality)))
+    if st < 0:
+        raise _lib.RFError(st, "rf_face_pose: bad argument (crop_size must be 0 or in [16, 512])")
+    return q[0]
+
+
+def face_gate_eval(gate, q, crop_size: int = 112) -> int:
+    """rf_face_gate_eval (host only, no GPU): the RF_GATE_* flags the gate (an rf_face_gate, a dict of face_gate() keywords or None)
+    gives a QUALITY_DTYPE record."""
+    lib = _lib.load_library()
+    rec = np.array([q], QUALITY_DTYPE) if not (isinstance(q, np.ndarray) and q.dtype == QUALITY_DTYPE) else np.ascontiguousarray(q).reshape(-1)[:1].copy()
+    g = _as_gate(gate)
+    st = lib.rf_face_gate_eval(C.byref(g) if g is not None else None, rec.ctypes.data_as(C.POINTER(rf_face_quality)), int(crop_size))
+    if st < 0:
+        raise _lib.RFError(st, "rf_face_gate_eval: bad gate or crop_size")
+    return int(st)
 
 
 def _faces_to_array(buf, n: int) -> np.ndarray:
@@ -319,7 +368,10 @@ class RetinaFace:
         n * max_faces), d_out (a device buffer of capacity faces that receives the tensor as well), host (False skips the host
         copy).  Returns (detections, tensor, matrices, offsets): tensor is [min(total, capacity), 3, S, S] (u8: [.., S, S, 3]),
         matrices [.., 2, 3] float64, offsets [n + 1]: face k of image i is tensor[offsets[i] + k].  self.faces_truncated tells
-        whether total exceeded the capacity."""
+        whether total exceeded the capacity.
+        gate= (an rf_face_gate from face_gate(), or a dict of its keywords) packs only the faces that pass it;
+        return_quality=True appends a fifth result: per image a QUALITY_DTYPE array with the record of every considered face
+        (k < min(faces, max_faces)), kept or dropped.  With neither, the ungated C entry point is called."""
         n = len(imgs)
         ptrs = (C.c_void_p * max(n, 1))()
         rows, cols, steps = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
@@ -334,7 +386,8 @@ class RetinaFace:
                 im = np.ascontiguousarray(im)
             keep.append(im)
             ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
-        return self._run_face_batch(self._lib.rf_detect_face_batch, ptrs, rows, cols, steps, n, threshold, **kw)
+        return self._run_face_batch(self._lib.rf_detect_face_batch, self._lib.rf_detect_face_batch_gated, ptrs, rows, cols, steps, n,
+                                    threshold, **kw)
 
     def detect_face_batch_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], threshold: float = 0.5,
                                  steps: Optional[Sequence[int]] = None, **kw):
@@ -343,7 +396,8 @@ class RetinaFace:
         p = (C.c_void_p * max(n, 1))(*ptrs)
         r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
         s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
-        return self._run_face_batch(self._lib.rf_detect_face_batch_device, p, r, c, s, n, threshold, **kw)
+        return self._run_face_batch(self._lib.rf_detect_face_batch_device, self._lib.rf_detect_face_batch_gated_device, p, r, c, s, n,
+                                    threshold, **kw)
 
     def face_batch(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], faces, *, steps: Optional[Sequence[int]] = None,
                    coord_scale: Optional[Sequence[float]] = None, **kw):
@@ -364,24 +418,62 @@ class RetinaFace:
         s_ = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
         cs = (C.c_float * max(n, 1))(*[float(v) for v in coord_scale]) if coord_scale is not None else None
 
-        def fn(h, spec, d_out, tensor, mats, offsets):
-            return self._lib.rf_face_batch_device(h, p, r_, c_, s_, n, flat.ctypes.data_as(C.POINTER(rf_face)), cap, counts, cs,
-                                                  spec, d_out, tensor, mats, offsets)
+        def fn(h, spec, d_out, tensor, mats, offsets, gate=None, quality=None):
+            if gate is None and quality is None:
+                return self._lib.rf_face_batch_device(h, p, r_, c_, s_, n, flat.ctypes.data_as(C.POINTER(rf_face)), cap, counts, cs,
+                                                      spec, d_out, tensor, mats, offsets)
+            return self._lib.rf_face_batch_gated_device(h, p, r_, c_, s_, n, flat.ctypes.data_as(C.POINTER(rf_face)), cap, counts, cs,
+                                                        spec, d_out, tensor, mats, offsets, gate, quality)
         kw.setdefault("max_faces", cap)
-        return (None,) + self._face_batch_call(fn, n, **kw)
+        res = self._face_batch_call(fn, n, **kw)
+        if len(res) == 4:
+            res = res[:3] + ([res[3][i, :min(counts[i], res[3].shape[1])] for i in range(n)],)
+        return (None,) + res
 
-    def _run_face_batch(self, fn, ptrs, rows, cols, steps, n, threshold, **kw):
+    def face_quality(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], faces, *, steps: Optional[Sequence[int]] = None,
+                     coord_scale: Optional[Sequence[float]] = None, crop_size: int = 112, max_faces: Optional[int] = None, gate=None):
+        """rf_face_quality_device: the quality records of faces the caller supplies (faces / coord_scale as align()); no tensor is
+        written.  Returns per image a QUALITY_DTYPE array of k = min(len(faces[i]), max_faces) records; flags are those of `gate`."""
+        n = len(ptrs)
+        rows_f = [_face_rows(f) for f in faces]
+        if len(rows_f) != n:
+            raise ValueError("faces must hold one entry per frame")
+        cap = max(1, max((len(r) for r in rows_f), default=1))
+        mf = int(max_faces) if max_faces else cap
+        flat = np.zeros((max(n, 1), cap, 15), np.float32)
+        counts = (C.c_int * max(n, 1))()
+        for i, r in enumerate(rows_f):
+            flat[i, :len(r)] = r
+            counts[i] = len(r)
+        p = (C.c_void_p * max(n, 1))(*ptrs)
+        r_, c_ = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
+        s_ = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        cs = (C.c_float * max(n, 1))(*[float(v) for v in coord_scale]) if coord_scale is not None else None
+        g = _as_gate(gate)
+        q = np.zeros((max(n, 1), max(mf, 1)), QUALITY_DTYPE)
+        _lib.check(self._lib.rf_face_quality_device(self._h, p, r_, c_, s_, n, flat.ctypes.data_as(C.POINTER(rf_face)), cap, counts, cs,
+                                                    int(crop_size), mf, C.byref(g) if g is not None else None,
+                                                    q.ctypes.data_as(C.POINTER(rf_face_quality))), self._h)
+        return [q[i, :min(counts[i], mf)].copy() for i in range(n)]
+
+    def _run_face_batch(self, fn, gated_fn, ptrs, rows, cols, steps, n, threshold, **kw):
         cap = self.max_detections
         out = (rf_face * max(n * cap, 1))()
         counts = (C.c_int * max(n, 1))()
 
-        def call(h, spec, d_out, tensor, mats, offsets):
-            return fn(h, ptrs, rows, cols, steps, n, float(threshold), out, cap, counts, spec, d_out, tensor, mats, offsets)
-        tensor, mats, offsets = self._face_batch_call(call, n, **kw)
-        return self._collect(out, counts, n, cap), tensor, mats, offsets
+        def call(h, spec, d_out, tensor, mats, offsets, gate=None, quality=None):
+            if gate is None and quality is None:
+                return fn(h, ptrs, rows, cols, steps, n, float(threshold), out, cap, counts, spec, d_out, tensor, mats, offsets)
+            return gated_fn(h, ptrs, rows, cols, steps, n, float(threshold), out, cap, counts, spec, d_out, tensor, mats, offsets,
+                            gate, quality)
+        res = self._face_batch_call(call, n, **kw)
+        if len(res) == 4:
+            res = res[:3] + ([res[3][i, :min(counts[i], res[3].shape[1], cap)] for i in range(n)],)
+        return (self._collect(out, counts, n, cap),) + res
 
     def _face_batch_call(self, call, n, crop_size: int = 112, dtype: str = "f16", rgb: bool = True, mean=None, scale=None,
-                         max_faces: Optional[int] = None, capacity: Optional[int] = None, d_out: Optional[int] = None, host: bool = True):
+                         max_faces: Optional[int] = None, capacity: Optional[int] = None, d_out: Optional[int] = None, host: bool = True,
+                         gate=None, return_quality: bool = False):
         mf = int(max_faces) if max_faces else self.max_detections
         capacity = int(capacity) if capacity is not None else max(1, n * mf)
         sp = face_batch_spec(crop_size, dtype, rgb, mean, scale, mf, capacity)
@@ -390,13 +482,21 @@ class RetinaFace:
         tensor = np.zeros((max(capacity, 0),) + shape, _FACE_FORMATS[dtype][1]) if host else None
         mats = np.zeros((max(capacity, 0), 2, 3), np.float64)
         offsets = (C.c_int * (n + 1))()
-        st = _lib.check(call(self._h, C.byref(sp), C.c_void_p(d_out) if d_out else None, tensor.ctypes.data if host else None,
-                             mats.ctypes.data_as(C.POINTER(C.c_double)), offsets), self._h)
+        args = (self._h, C.byref(sp), C.c_void_p(d_out) if d_out else None, tensor.ctypes.data if host else None,
+                mats.ctypes.data_as(C.POINTER(C.c_double)), offsets)
+        quality = None
+        if gate is not None or return_quality:
+            g = _as_gate(gate)
+            quality = np.zeros((max(n, 1), max(mf, 1)), QUALITY_DTYPE)
+            # (the records are always fetched: they are what makes this the gated entry point when the gate is None)
+            args += (C.byref(g) if g is not None else None, quality.ctypes.data_as(C.POINTER(rf_face_quality)))
+        st = _lib.check(call(*args), self._h)
         offsets = np.array(offsets[:n + 1], np.int32)
         got = min(int(offsets[n]), capacity)
         self.truncated = st == _lib.RF_ERR_TRUNCATED
         self.faces_truncated = int(offsets[n]) > capacity
-        return (tensor[:got] if host else None), mats[:got], offsets
+        res = (tensor[:got] if host else None), mats[:got], offsets
+        return res + (quality,) if return_quality else res
 
     def enqueue_device(self, ptrs, rows, cols, threshold: float = 0.5) -> int:
         n = len(ptrs)
