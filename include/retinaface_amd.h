@@ -413,7 +413,9 @@ int rf_plan_int8_gemm(const char *model_dir, const char *stem, const char *int8_
 /* Offline: <model_dir>/<stem> (an .rfw or prototxt + caffemodel) re-packed into out_rfw with a new calibration: int8_table (text,
  * the reference's format; NULL keeps the model's) and qweights ("<stem>.qweights.int8", the calibrated int8 weights tools/
  * calibrate_int8.py --gptq writes; NULL keeps the model's unless the table changed, which drops them).  The result is checked by
- * compiling and packing the int8 plan on the host; no GPU needed. */
+ * compiling and packing the int8 plan on the host; no GPU needed.  A scale that is not a positive finite number (zero, negative, NaN, inf)
+ * is refused with RF_ERR_MODEL naming the tensor -- here for a table line or a scale the model carries, and by rf_create for an int8
+ * engine; fp32 / fp16 engines never read the scales and still build from such a container. */
 int rf_attach_calibration(const char *model_dir, const char *stem, const char *int8_table, const char *qweights, const char *out_rfw);
 
 /* Host-only test hook: the host half of rf_create (plan cache or model -> packed weight image) for <model_dir>/<stem> at a

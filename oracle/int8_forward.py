@@ -128,6 +128,7 @@ class QGemm:
         q = np.rint((ws_in / s_w.reshape(cout, 1, 1, 1)).astype(F32))          # np.rint = round half to even = nearbyintf
         self.wq = np.clip(q, -127, 127).astype(np.int32)
         os_ = np.ones(cout, F32) if s_out is None else s_out.astype(F32)
+        self.s_w = s_w                                   # the weight grid: what the C++ packer's row scales are pinned against
         self.mult = (s_w / os_).astype(F32)
         b = b.astype(F32)
         if calibrated is not None:                       # integers + bias correction chosen by the calibration run, same grid

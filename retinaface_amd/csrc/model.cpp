@@ -8,6 +8,7 @@
 #include <unistd.h>
 
 #include <atomic>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -323,6 +324,14 @@ void attach_caffemodel(Model &m, const std::string &path) {
     }
 }
 
+// An activation scale is a quantum size: the int8 packer divides biases and weights by it (weights.h), so it has to be a positive finite
+// number.  Returns what is wrong with `v`, or nothing.
+static std::string bad_int8_scale(const std::string &tensor, float v) {
+    if (std::isfinite(v) && v > 0.f) return std::string();
+    return "calibration scale of '" + tensor + "' is " + (std::isnan(v) ? std::string("NaN") : std::isinf(v) ? std::string(v < 0.f ? "-inf" : "inf") : std::to_string(v)) +
+           ": a scale must be a positive finite number";
+}
+
 void attach_int8_table(Model &m, const std::string &path) {
     std::string text = slurp(path, false);
     std::istringstream ss(text);
@@ -330,6 +339,7 @@ void attach_int8_table(Model &m, const std::string &path) {
     if (!std::getline(ss, line) || line.compare(0, 4, "TRT-") != 0)
         throw ModelError("'" + path + "' is not a TensorRT calibration cache");
     m.int8_scales.clear();
+    m.int8_scale_error.clear();
     while (std::getline(ss, line)) {
         while (!line.empty() && (line.back() == '\r' || line.back() == ' ')) line.pop_back();
         if (line.empty()) continue;
@@ -343,6 +353,8 @@ void attach_int8_table(Model &m, const std::string &path) {
         uint32_t bits = (uint32_t)std::stoul(hex, nullptr, 16);
         float f;
         memcpy(&f, &bits, 4);    // the hex text is the big-endian spelling of the IEEE-754 word
+        const std::string bad = bad_int8_scale(name, f);
+        if (!bad.empty()) throw ModelError("'" + path + "': " + bad);
         m.int8_scales.emplace_back(name, f);
     }
 }
@@ -536,6 +548,7 @@ Model load_rfw(const std::string &path) {
     for (uint32_t i = 0; i < ns; i++) {
         std::string k = in.str();
         float v = in.f32();
+        if (m.int8_scale_error.empty()) m.int8_scale_error = bad_int8_scale(k, v);      // refused where the scales are used: the int8 packer
         m.int8_scales.emplace_back(k, v);
     }
     if (in.p < buf.size()) read_qweights(in, m);              // optional trailing section: calibrated int8 weights

@@ -50,6 +50,9 @@ struct Model {
     std::vector<Layer> layers;
     std::vector<std::pair<std::string, float>> int8_scales;   // file order preserved
     std::vector<QWeights> int8_qweights;                       // optional (empty: round to nearest)
+    // RFW1 only: what is wrong with the first calibration scale that is not a positive finite number (empty: all are usable).  The file
+    // still loads, because the fp32 / fp16 engines never read the scales; the int8 weight packer refuses it (ModelError).
+    std::string int8_scale_error;
 
     const Layer *find(const std::string &layer_name) const;
     const Layer &get(const std::string &layer_name) const;     // throws ModelError

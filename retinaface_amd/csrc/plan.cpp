@@ -253,6 +253,7 @@ static Plan compile_plan_checked(const Model &m) {
         s.conv_c.out_blob = cat_out;
     }
     p.int8_scales = m.int8_scales;
+    p.int8_scale_error = m.int8_scale_error;
     p.int8_qweights = m.int8_qweights;
     return p;
 }

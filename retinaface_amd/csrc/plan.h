@@ -44,6 +44,7 @@ struct Plan {
     // TensorRT calibration cache: tensor (blob) name -> per-tensor activation scale, real ~= q * scale (SURVEY App. B.7;
     // consumed by the int8 engine).  Empty when the model carries no table.
     std::vector<std::pair<std::string, float>> int8_scales;
+    std::string int8_scale_error;         // Model::int8_scale_error: non-empty = the int8 packer refuses the table
     // calibrated int8 weights per fused dense conv (model.h QWeights; empty: the int8 engine rounds to nearest)
     std::vector<QWeights> int8_qweights;
 };

@@ -355,6 +355,8 @@ struct WeightPack {
         plan_ = &plan;
         if constexpr (kInt8)
             if (plan.int8_scales.empty()) throw Unsupported("int8 precision needs a calibration table (<stem>.table.int8)");
+        if constexpr (kInt8)
+            if (!plan.int8_scale_error.empty()) throw ModelError("int8: " + plan.int8_scale_error);
         c0_w_ = arena_.put(plan.conv0.w);
         c0_b_ = arena_.put(plan.conv0.b);
         size_t first_block = 0;

@@ -235,3 +235,284 @@ def test_variant_frames_drive_the_int8_epilogues_into_their_top_clamp(nets, orac
             best_block, best_dw = max(best_block, top_b), max(best_dw, top_d)
     assert best_block[0] >= 1e-3, best_block
     assert best_dw[0] >= 1e-3, best_dw
+
+
+# ------------------------------------------------------------------------------------------------ derived tables and weight sets
+# tests/int8_derived.py: the branches of the int8 path that the shipped tables (25 % head-room) and the trained weights leave cold.
+# Here: the conditions on the INPUTS of tests/test_int8_derived_gpu.py (checked on the reference alone), the C++ packer against the
+# oracle on every derived set, and the refusal of unusable scales.
+
+import ctypes as C  # noqa: E402
+
+import int8_derived as drv  # noqa: E402
+from conftest import ASSETS  # noqa: E402
+from test_gpu_parity import _edge_frame  # noqa: E402  (the GPU tests' own frame; importing that module needs no GPU)
+
+COVERAGE_HW = (352, 608)          # at 64 x 96 one or two tensors stay unsaturated under the same tables
+START = "mobilenet0_relu2_fwd"
+
+
+def _is_mid(name):
+    return name.startswith("mobilenet0_relu") and int(name[len("mobilenet0_relu"):].split("_")[0]) % 2 == 1
+
+
+@pytest.fixture(scope="module")
+def coverage_blobs(oracles, base_frame):
+    """the fp32 oracle's activations on the coverage frame, once per model"""
+    f = _edge_frame(base_frame, COVERAGE_HW)
+    return {stem: oracles[stem].forward(preprocess_trt_identity(f, *COVERAGE_HW), keep_all=True) for stem in STEMS}
+
+
+def _continue_from_fp32(q, blobs):
+    return q.forward_from(START, q.quantise_blob(START, blobs[START][0].transpose(1, 2, 0)))
+
+
+def _top_code_report(stem, name, acts):
+    """(share of top codes per tensor, printed summary): 127 is the top code of every tensor -- a depthwise mid's 255 is stored as 127"""
+    share = {n: float((a == 127).mean()) for n, a in acts.items() if n != "__heads__"}
+    relu = [v for n, v in share.items() if not _is_mid(n)]
+    mids = [v for n, v in share.items() if _is_mid(n)]
+    quanta = sum(a.size for n, a in acts.items() if n != "__heads__")
+    total = sum(int((a == 127).sum()) for n, a in acts.items() if n != "__heads__") / quanta
+    low = min(share, key=share.get)
+    print(f"int8 derived {stem} {name}: {total:.4f} of all quanta at the top code; ReLU tensors mean {np.mean(relu):.4f}, depthwise mids mean "
+          f"{np.mean(mids):.4f}; lowest {share[low]:.5f} ({low})")
+    return share
+
+
+@pytest.mark.parametrize("name", ["pc_half", "pt_quarter"])
+@pytest.mark.parametrize("stem", STEMS)
+def test_derived_tables_put_every_int8_tensor_at_its_top_code(nets, coverage_blobs, stem, name):
+    """Under `pc_half` (per-channel path) and `pt_quarter` (per-tensor path), on the GPU test's own 352 x 608 frame continued from the
+    quantised fp32 front end, EVERY int8 tensor of the network -- the 28 ReLU tensors behind the start blob, `_plus0` / `_plus1` included,
+    and all 12 depthwise mids -- has quanta at its top code, so a bit-exact pass of the engine on these tables exercises the top clamp of
+    every requantising epilogue.  A condition on the inputs, checked on the reference alone."""
+    q = i8.Int8Net(drv.derive(nets[stem], name))
+    assert q.per_channel == name.startswith("pc_")
+    acts = _continue_from_fp32(q, coverage_blobs[stem])
+    share = _top_code_report(stem, name, acts)
+    cand = list(decode({k: v[None] for k, v in acts["__heads__"].items()}, *COVERAGE_HW, 0.02))
+    print(f"int8 derived {stem} {name}: {len(cand)} candidates at 0.02, {len(nms(cand, 0.4))} kept")
+    relu = [n for n in share if not _is_mid(n) and n != START]
+    mids = [n for n in share if _is_mid(n)]
+    assert len(relu) == 28 and {"_plus0", "_plus1"} <= set(relu) and len(mids) == 12
+    unsaturated = [n for n, v in share.items() if v == 0.0]
+    assert not unsaturated, unsaturated
+
+
+@pytest.mark.parametrize("stem", STEMS)
+def test_derived_tables_reach_the_front_end_clamp_and_the_bitonic_nms(nets, coverage_blobs, stem):
+    """`pc_quarter`: at least 1000 positions of relu2 and of relu4 (the two blobs at which the engine's float front end may hand over) lie
+    at or above 135 quanta of the fp32 oracle -- 127 + 8, twice what a 1 LSB error at the shipped scale can move a value at a quarter of
+    that scale -- so the front end's own top clamp is pinned there whatever its rounding.  `pt_eighth`: more than 256 candidates at
+    threshold 0.02, the NMS kernel's bitonic path, with the tied scores int8 heads give."""
+    q = i8.Int8Net(drv.derive(nets[stem], "pc_quarter"))
+    for blob in ("mobilenet0_relu2_fwd", "mobilenet0_relu4_fwd"):
+        r = coverage_blobs[stem][blob][0].transpose(1, 2, 0).astype(np.float32)
+        over = int(((r * (np.float32(1) / q.scale_of_blob[blob]).reshape(1, 1, -1)).astype(np.float32) >= 135).sum())
+        print(f"int8 derived {stem} pc_quarter: {over} of {r.size} positions of {blob} at or above 135 quanta")
+        assert over >= 1000, (blob, over)
+    q = i8.Int8Net(drv.derive(nets[stem], "pt_eighth"))
+    acts = _continue_from_fp32(q, coverage_blobs[stem])
+    _top_code_report(stem, "pt_eighth", acts)
+    heads = {k: v[None] for k, v in acts["__heads__"].items()}
+    cand = list(decode(heads, *COVERAGE_HW, 0.02))
+    kept = nms(cand, 0.4)
+    scores = np.array([c.score for c in cand], np.float32)
+    print(f"int8 derived {stem} pt_eighth: {len(cand)} candidates at 0.02 ({len(np.unique(scores))} distinct scores), {len(kept)} kept")
+    assert len(cand) > 256
+
+
+@pytest.mark.parametrize("stem", STEMS)
+def test_remaining_derived_sets_are_what_they_say(nets, coverage_blobs, stem):
+    """The other sets on the same frame (their shares of top codes are printed for DESIGN.md section 5).  `pc_coarse` is the low end:
+    nothing saturates and no ReLU tensor uses even half of its codes (the shipped table's ~100 quanta of range become ~25).  `pc_ragged`: in each FPN add the three calibrated scales of a
+    channel really differ, in most channels, so the max-merge picks different tensors in neighbouring channels.  `pc_quarter` saturates
+    more than `pc_half` does; `degenerate` runs on the shipped table."""
+    shares = {}
+    for name in ("pc_quarter", "pc_coarse", "pc_ragged", "degenerate"):
+        net = drv.derive(nets[stem], name)
+        acts = _continue_from_fp32(i8.Int8Net(net), coverage_blobs[stem])
+        shares[name] = _top_code_report(stem, name, acts)
+        heads = {k: v[None] for k, v in acts["__heads__"].items()}
+        cand = list(decode(heads, *COVERAGE_HW, 0.02))
+        print(f"int8 derived {stem} {name}: {len(cand)} candidates at 0.02, {len(nms(cand, 0.4))} kept")
+        if name == "pc_coarse":
+            assert max(shares[name].values()) == 0.0
+            assert max(int(a.max()) for n, a in acts.items() if n != "__heads__" and not _is_mid(n)) < 64
+        if name == "pc_ragged":
+            t = net.int8_scales
+            for group in (("rf_c3_lateral_relu", "rf_c2_lateral_relu", "_plus0"), ("rf_c2_aggr_relu", "rf_c1_red_conv_relu", "_plus1")):
+                s = np.array([[t[f"{g}#{c}"] for c in range(64)] for g in group], np.float32)
+                winners = s.argmax(axis=0)
+                assert len(set(winners.tolist())) == 3 and np.mean(s.max(axis=0) > s.min(axis=0)) > 0.5, group
+    assert np.mean(list(shares["pc_quarter"].values())) > 0.05
+
+
+def _oracle_gemms(q):
+    """fused-op name (as plan.h names it: reference layer names, '+'-joined for merged siblings) -> the oracle's QGemm"""
+    ops = {f"mobilenet0_conv{2 * i + 2}_fwd": q.pw[i] for i in range(1, 13)}
+    ops.update(zip(("rf_c3_lateral", "rf_c2_lateral", "rf_c1_red_conv"), q.lat))
+    ops.update(zip(("rf_c2_aggr", "rf_c1_aggr"), q.aggr))
+    for m in q.ssh:
+        pre, st = m["pre"], f"stride{m['stride']}"
+        ops[pre + "conv1+" + pre + "context_conv1"] = m["a"]
+        ops[pre + "context_conv2+" + pre + "context_conv3_1"] = m["b"]
+        ops[pre + "context_conv3_2"] = m["c"]
+        ops[f"face_rpn_cls_score_{st}+face_rpn_bbox_pred_{st}+face_rpn_landmark_pred_{st}"] = m["head"]
+    return ops
+
+
+def _packer_gemms(lib, model_dir, stem, shapes):
+    """every fused dense conv `rf_plan_int8_gemm` enumerates ("?i") for <model_dir>/<stem>.rfw: name -> (unrounded quanta, row scales);
+    `shapes` (name -> (cout, ktot), the oracle's) sizes the buffers and is checked against the packer's own dims"""
+    F = C.POINTER(C.c_float)
+    d, s = str(model_dir).encode(), stem.encode()
+    out = {}
+    for i in range(64):
+        dims = (C.c_int * 4)()
+        buf = np.zeros(64, np.float32)
+        st = lib.rf_plan_int8_gemm(d, s, None, f"?{i}".encode(), buf.ctypes.data_as(F), buf.size, None, 0, None, None, 0, dims)
+        if st != 0:
+            break
+        op = buf.tobytes()[:dims[0]]
+        assert op.decode() in shapes, op
+        quanta, row = np.zeros(shapes[op.decode()], np.float32), np.zeros(shapes[op.decode()][0], np.float32)
+        st = lib.rf_plan_int8_gemm(d, s, None, op, quanta.ctypes.data_as(F), quanta.size, None, 0, row.ctypes.data_as(F), None, row.size, dims)
+        assert st == 0 and (dims[0], dims[1]) == quanta.shape, (op, lib.rf_last_error(None), list(dims))
+        out[op.decode()] = (quanta, row)
+    return out
+
+
+@pytest.mark.parametrize("name", drv.ALL)
+@pytest.mark.parametrize("stem", STEMS)
+def test_host_packer_equals_the_oracle_on_derived_sets(built_lib, nets, tmp_path, stem, name):
+    """Every derived set, packed as the GPU test packs it (write_rfw; tables also through rf_attach_calibration from their text form): the
+    container reads back with the same scales and no calibrated weights, and for every fused dense conv the C++ packer (weights.h put_gemm)
+    has the oracle's weight grid `s_w` BIT for bit and the oracle's integers `wq` -- the zero rows of `degenerate` included, where the row
+    scale must be 1 and the integers all 0 (the `amax > 0 ? amax / 127 : 1` branch no shipped model reaches)."""
+    from oracle.caffe_io import read_int8_table, read_rfw, write_rfw
+    net = drv.derive(nets[stem], name)
+    assert net.int8_qweights == {}
+    dirs = [tmp_path / "py"]
+    dirs[0].mkdir()
+    write_rfw(net, str(dirs[0] / (stem + ".rfw")))
+    if name in drv.TABLES:
+        table = str(tmp_path / "derived.table.int8")
+        drv.write_table(net.int8_scales, table)
+        assert read_int8_table(table) == net.int8_scales
+        dirs.append(tmp_path / "capi")
+        dirs[1].mkdir()
+        st = built_lib.rf_attach_calibration(ASSETS.encode(), stem.encode(), table.encode(), None, str(dirs[1] / (stem + ".rfw")).encode())
+        assert st == 0, built_lib.rf_last_error(None)
+        shipped = nets[stem].int8_scales
+        if name.startswith("pt_"):
+            assert set(net.int8_scales) == {k for k in shipped if "#" not in k}
+        else:
+            assert list(net.int8_scales) == list(shipped)
+        ratios = {net.int8_scales[k] / shipped[k] for k in net.int8_scales}
+        assert ratios == (set(drv.RAGGED_FACTORS) if name == "pc_ragged" else {drv._FACTOR[name]}), ratios
+    for d in dirs:
+        back = read_rfw(str(d / (stem + ".rfw")))
+        assert back.int8_qweights == {} and back.int8_scales == net.int8_scales and list(back.int8_scales) == list(net.int8_scales)
+    q = i8.Int8Net(net)
+    want = _oracle_gemms(q)
+    got = _packer_gemms(built_lib, dirs[-1], stem, {op: (g.cout, g.k * g.k * g.cin) for op, g in want.items()})
+    assert set(got) == set(want) and len(got) == 29, sorted(set(got) ^ set(want))
+    zero_rows = 0
+    for op, g in want.items():
+        quanta, row = got[op]
+        assert np.array_equal(row.view(np.uint32), g.s_w.view(np.uint32)), op
+        wq = np.clip(np.rint(quanta), -127, 127).astype(np.int32)               # put_gemm's own rounding of what it records: nearbyintf, then the clamp
+        assert np.array_equal(wq, g.wq.reshape(g.cout, -1)), op
+        dead = ~wq.any(axis=1)
+        assert np.all(row[dead] == 1.0) and not quanta[dead].any(), op       # a live row has a +-127 somewhere: all-zero integers = a zero row
+        zero_rows += int(dead.sum())
+    if name == "degenerate":
+        ed = drv.degenerate_edits(nets[stem])
+        for layer, _ in drv.ZERO_ROWS:
+            op = next(o for o in want if layer in o.split("+"))
+            off = 0
+            for part in op.split("+"):                       # merged siblings: the layer's rows sit behind those of the layers named before it
+                if part == layer:
+                    break
+                off += nets[stem].layer(part).blobs[0].shape[0]
+            rows = ed[layer + ":zero"] + off
+            assert np.all(got[op][1][rows] == 1.0) and not got[op][0][rows].any(), (op, rows)
+            assert np.all(want[op].s_w[rows] == 1.0) and not want[op].wq[rows].any(), (op, rows)
+        assert zero_rows == sum(n for _, n in drv.ZERO_ROWS)
+        # the depthwise counterpart (weights.h put_dw / the oracle's QDw): zero taps -> tap scale 1, integers 0
+        dw = q.dw[(int(drv.ZERO_TAPS[0][len("mobilenet0_conv"):].split("_")[0]) - 1) // 2]
+        ch = ed[drv.ZERO_TAPS[0] + ":zero"]
+        assert np.all(dw.mult[ch] == 1.0) and not dw.wq[ch].any()
+    else:
+        assert zero_rows == 0
+
+
+def test_degenerate_weight_set_is_what_it_says(nets):
+    """`degenerate` leaves everything before mobilenet0_conv5_fwd alone (the engine's float front end may run through relu4), and its dead
+    and saturated channels behave as intended in the oracle: a zero-row pointwise channel is one constant code, a zero-tap depthwise channel
+    is one constant code, a beta = 1e4 channel is 127 everywhere."""
+    rng = np.random.default_rng(31)
+    x = rng.integers(0, 128, (32, 48, 16)).astype(np.int8)
+    for stem in STEMS:
+        net = drv.derive(nets[stem], "degenerate")
+        names = [l.name for l in net.layers]
+        cut = names.index("mobilenet0_conv5_fwd")
+        for a, b in zip(net.layers[:cut], nets[stem].layers[:cut]):
+            assert len(a.blobs) == len(b.blobs) and all(np.array_equal(u, v) for u, v in zip(a.blobs, b.blobs)), a.name
+        assert net.int8_scales == nets[stem].int8_scales
+        ed = drv.degenerate_edits(nets[stem])
+        acts = i8.Int8Net(net).forward_from(START, x)
+        for blob, key in (("mobilenet0_relu8_fwd", "mobilenet0_conv8_fwd:zero"), ("mobilenet0_relu9_fwd", "mobilenet0_conv9_fwd:zero"),
+                          ("rf_c2_lateral_relu", "rf_c2_lateral:zero"), ("rf_c1_aggr_relu", "rf_c1_aggr:zero")):
+            for c in ed[key]:
+                assert len(np.unique(acts[blob][:, :, c])) == 1, (stem, blob, c)
+        for c in ed["mobilenet0_conv12_fwd:beta"]:
+            assert np.all(acts["mobilenet0_relu12_fwd"][:, :, c] == 127), (stem, c)
+        live = np.setdiff1d(np.arange(64), ed["mobilenet0_conv8_fwd:zero"])
+        assert all(len(np.unique(acts["mobilenet0_relu8_fwd"][:, :, c])) > 1 for c in live[:8])
+
+
+BAD_SCALES = (0.0, -0.03125, float("nan"), float("inf"))
+
+
+@pytest.mark.parametrize("bad", BAD_SCALES)
+def test_unusable_calibration_scales_are_refused(built_lib, nets, tmp_path, bad):
+    """A calibration scale is a quantum size the int8 packer divides by: zero, negative, NaN and inf are refused with RF_ERR_MODEL and a
+    message naming the blob -- by rf_attach_calibration for a line of a text table, by rf_create (int8) for a scale entry of an RFW1
+    container.  The same container still gives an fp16 engine, which never reads the scales."""
+    import copy
+    from oracle.caffe_io import write_rfw
+    from retinaface_amd import _lib
+    stem, blob = "mnet25", "rf_c2_aggr_relu#17"
+    scales = dict(nets[stem].int8_scales)
+    assert blob in scales
+    scales[blob] = bad
+    table = str(tmp_path / "bad.table.int8")
+    drv.write_table(scales, table)
+    st = built_lib.rf_attach_calibration(ASSETS.encode(), stem.encode(), table.encode(), None, str(tmp_path / "out.rfw").encode())
+    msg = built_lib.rf_last_error(None).decode()
+    assert st == _lib.RF_ERR_MODEL and blob in msg, (st, msg)
+    assert not os.path.exists(tmp_path / "out.rfw")
+    net = copy.copy(nets[stem])
+    net.int8_scales, net.int8_qweights = scales, {}
+    write_rfw(net, str(tmp_path / (stem + ".rfw")))
+
+    def create(precision):
+        o = _lib.rf_options()
+        o.struct_size = C.sizeof(_lib.rf_options)
+        o.model_stem, o.precision, o.plan_cache = stem.encode(), precision, 2      # 2: no plan cache
+        h = C.c_void_p()
+        st = built_lib.rf_create(str(tmp_path).encode(), b"net3", 0.4, C.byref(o), C.byref(h))
+        msg = built_lib.rf_last_error(None).decode()
+        if h.value:
+            built_lib.rf_destroy(h)
+        return st, msg
+    st, msg = create(2)
+    assert st == _lib.RF_ERR_MODEL and blob in msg, (st, msg)
+    st, msg = create(1)
+    assert st in (0, _lib.RF_ERR_HIP), (st, msg)                  # parsed and packed; fails only for want of a GPU
+    # ... and re-packing that container without a new table is refused as well
+    st = built_lib.rf_attach_calibration(str(tmp_path).encode(), stem.encode(), None, None, str(tmp_path / "out2.rfw").encode())
+    assert st == _lib.RF_ERR_MODEL and blob in built_lib.rf_last_error(None).decode()
