@@ -72,7 +72,9 @@ public:
     /* additive: detectBatchImages() + the faces it finds as ONE dense, packed, normalised tensor (rf_detect_face_batch): the bytes of
        min(total, spec.capacity) faces of 3 x S x S elements each in the spec's format; face k of image i is packed face
        faceBatchOffsets()[i] + k, faceBatchMatrices() holds 6 doubles per packed face.  Fills lastBatchResult().
-       faceBatchTruncated(): more faces than spec.capacity (the first `capacity` are returned). */
+       faceBatchTruncated(): more faces than spec.capacity (the first `capacity` are returned).
+       spec.antialias = 1 supersamples faces that are larger in the frame than their crop (up to spec.aa_max sub-samples per axis);
+       under detectFaceBatchGated() the luma numbers of the quality records are then those of the antialiased crop. */
     vector<uint8_t> detectFaceBatch(const vector<cv::Mat> &imgs, float threshold, const rf_face_batch_spec &spec);
     const vector<int> &faceBatchOffsets() const { return faceOffsets_; }
     const vector<double> &faceBatchMatrices() const { return faceMats_; }

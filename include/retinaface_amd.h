@@ -204,6 +204,12 @@ int rf_detect_align_batch(rf_handle h, const uint8_t *const *bgr, const int *row
  *                 (A detect call holds at most max_detections records per image: m_i is clamped to that as well.)
  *   value         q = the u8 value of crop pixel (u, v), source channel b of B, G, R, exactly as the crops above (0 everywhere
  *                 for an invalid face).  Output channel c takes source channel c (rgb == 0) or 2 - c (rgb == 1).
+ *                 With spec.antialias == 1 (DESIGN.md "Antialiased face crops"; tests/face_aa_ref.py) q is supersampled instead:
+ *                 with ia, ib the inverse similarity, R = ia * ia + ib * ib (source pixels per crop pixel, squared; IEEE double),
+ *                 k = 1; while (k < aa_max && (double)(k * k) * 2.0 < R) k *= 2;  -- per face; rf_face_aa_factor returns it.
+ *                 Sub-sample (i, j), i, j < k, sits at (u + (2i + 1 - k) / 2k, v + (2j + 1 - k) / 2k) and is sampled exactly as
+ *                 the crop pixel above up to its unshifted sum a = sum w * pix (0 when out of range); with k = 2^m,
+ *                 q = (sum over the k * k sub-samples of a + 2^(19 + 2m)) >> (20 + 2m).  k = 1 is the plain crop bit for bit.
  *                 RF_FACES_U8_HWC: q itself, layout [j][v][u][c]; mean / scale unused.
  *                 RF_FACES_F32_CHW: ((float)q - mean[c]) * scale[c], one fp32 subtract then one fp32 multiply, layout [j][c][v][u].
  *                 RF_FACES_F16_CHW: the same value converted to IEEE half, round to nearest even.
@@ -211,23 +217,30 @@ int rf_detect_align_batch(rf_handle h, const uint8_t *const *bgr, const int *row
  *   matrices      packed the same way: matrices[j*6 .. j*6+5] holds the doubles rf_align_matrix gives for that face. */
 typedef enum rf_face_format { RF_FACES_U8_HWC = 0, RF_FACES_F16_CHW = 1, RF_FACES_F32_CHW = 2 } rf_face_format;
 typedef struct rf_face_batch_spec {
-    uint32_t struct_size;   /* sizeof(rf_face_batch_spec) */
+    uint32_t struct_size;   /* sizeof(rf_face_batch_spec), or 48: the struct up to and including capacity (antialias = 0) */
     int32_t crop_size;      /* 16..512, 0 = 112 */
     int32_t format;         /* rf_face_format */
     int32_t rgb;            /* 0 = frame order (BGR), 1 = RGB */
     float mean[3], scale[3];/* per OUTPUT channel */
     int32_t max_faces;      /* per image, 1..4096; 0 = the engine's max_detections */
     int32_t capacity;       /* packed faces the tensor holds, >= 1 */
+    int32_t antialias;      /* 0 = off: the plain sampling and its bytes.  1 = supersampled sampling (value, above) */
+    int32_t aa_max;         /* largest supersampling factor per axis: 1, 2, 4 or 8; 0 = 4.  Ignored (but still validated) when antialias == 0 */
 } rf_face_batch_spec;
 
 /* Host only, no GPU, no handle.  rf_face_batch_plan: what a call with these per-image counts packs -- fills offsets (n + 1 ints, may
  * be NULL) and bytes_per_face (may be NULL) and returns total (NOT clamped to capacity), or RF_ERR_INVALID_ARG for a bad
- * struct_size / crop_size / format / max_faces / capacity, a non-finite mean or scale, or a negative count.  max_faces == 0
- * stands for the default max_detections (256) here.
+ * struct_size / crop_size / format / max_faces / capacity / antialias / aa_max, a non-finite mean or scale, or a negative count.
+ * max_faces == 0 stands for the default max_detections (256) here.
  * rf_face_value_table: the 256 output values (q = 0..255) of output channel `channel` (0..2) in the spec's element type (u8, half
  * or float) -- the same code the kernel runs, compiled for the host. */
 long rf_face_batch_plan(const rf_face_batch_spec *spec, const int *counts, int n, int *offsets, size_t *bytes_per_face);
 int rf_face_value_table(const rf_face_batch_spec *spec, int channel, void *out256);
+
+/* Host only, no GPU, no handle.  The supersampling factor k (1, 2, 4 or 8; 1 for an invalid face) a face gets under antialias == 1
+ * with this aa_max -- the same code the kernel runs, compiled for the host.  crop_size 0 = 112, aa_max 0 = 4.  RF_ERR_INVALID_ARG for
+ * a NULL face, a crop_size outside 16..512 or an aa_max other than 0, 1, 2, 4, 8. */
+int rf_face_aa_factor(const rf_face *face, float coord_scale, int crop_size, int aa_max);
 
 /* rf_detect_batch_device + the face batch of what it finds, in one call.  Detection runs exactly as in rf_detect_batch_device (out /
  * counts / rf_last_anchor_indices are the same bytes); the packing and the tensor launches follow each detection launch on its
@@ -289,7 +302,9 @@ int rf_face_gate_eval(const rf_face_gate *gate, const rf_face_quality *q, int cr
 
 /* The quality records of faces the CALLER supplies (arguments as rf_align_batch_device); no tensor is written.  quality: host,
  * n * max_faces records; face k < min(counts[i], max_faces) of image i is record i * max_faces + k, the other records are
- * unspecified.  gate may be NULL (flags 0).  A bad gate is refused before any state changes. */
+ * unspecified.  gate may be NULL (flags 0).  A bad gate is refused before any state changes.
+ * This call takes no spec: its records are always those of the PLAIN crop.  The records of the antialiased crop come from
+ * rf_face_batch_gated_device with spec.antialias == 1 and d_tensor = tensor = NULL. */
 int rf_face_quality_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
                            const rf_face *faces, int cap_per_image, const int *counts, const float *coord_scale, int crop_size,
                            int max_faces, const rf_face_gate *gate, rf_face_quality *quality);
@@ -298,7 +313,9 @@ int rf_face_quality_device(rf_handle h, const void *const *d_bgr, const int *row
  * offsets[i+1] = offsets[i] + kept_i, the kept faces of an image stay in score order; tensor, matrices, total, capacity and
  * RF_ERR_TRUNCATED behave as above, counted over kept faces.  quality (host, n * max_faces records with the spec's max_faces, may
  * be NULL) receives the record of every considered face, kept or dropped, at i * max_faces + k.  A NULL gate keeps every face: the
- * tensor, matrices and offsets are the bytes of the ungated call.  Gating never changes out / counts / rf_last_anchor_indices. */
+ * tensor, matrices and offsets are the bytes of the ungated call.  Gating never changes out / counts / rf_last_anchor_indices.
+ * With spec.antialias == 1 luma, sum_luma, sum_lap, sum_lap2 and sharpness are taken from the antialiased crop value; covered (still
+ * the pixel centre's), iod2, yaw and sin2_roll are unchanged. */
 int rf_face_batch_gated_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
                                const rf_face *faces, int cap_per_image, const int *counts, const float *coord_scale,
                                const rf_face_batch_spec *spec, void *d_tensor, void *tensor, double *matrices, int *offsets,

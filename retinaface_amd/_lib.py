@@ -36,7 +36,8 @@ class rf_options(C.Structure):
 
 class rf_face_batch_spec(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("crop_size", C.c_int32), ("format", C.c_int32), ("rgb", C.c_int32),
-                ("mean", C.c_float * 3), ("scale", C.c_float * 3), ("max_faces", C.c_int32), ("capacity", C.c_int32)]
+                ("mean", C.c_float * 3), ("scale", C.c_float * 3), ("max_faces", C.c_int32), ("capacity", C.c_int32),
+                ("antialias", C.c_int32), ("aa_max", C.c_int32)]
 
 
 RF_FACES_U8_HWC, RF_FACES_F16_CHW, RF_FACES_F32_CHW = 0, 1, 2
@@ -83,6 +84,7 @@ SYMBOLS = {
                                         C.c_void_p, C.c_void_p, _PP(C.c_double)]),
     "rf_face_batch_plan": (C.c_long, [_PP(rf_face_batch_spec), _PP(C.c_int), C.c_int, _PP(C.c_int), _PP(C.c_size_t)]),
     "rf_face_value_table": (C.c_int, [_PP(rf_face_batch_spec), C.c_int, C.c_void_p]),
+    "rf_face_aa_factor": (C.c_int, [_PP(rf_face), C.c_float, C.c_int, C.c_int]),
     "rf_detect_face_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
                                               C.c_float, _PP(rf_face), C.c_int, _PP(C.c_int), _PP(rf_face_batch_spec),
                                               C.c_void_p, C.c_void_p, _PP(C.c_double), _PP(C.c_int)]),

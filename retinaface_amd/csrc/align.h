@@ -55,4 +55,17 @@ __host__ __device__ inline int align_estimate(const float *px, const float *py, 
     return 1;
 }
 
+// The supersampling factor per axis of an antialiased crop (DESIGN.md "Antialiased face crops"): R = source pixels per crop pixel,
+// squared; the smallest power of two k <= aa_max (1, 2, 4 or 8) with sub-sample spacing sqrt(R) / k <= sqrt(2) source pixels.
+// An invalid face has k = 1.
+__host__ __device__ inline int align_aa_factor(const AlignXform &t, int aa_max) {
+#pragma clang fp contract(off)
+    if (!t.valid) return 1;
+    const double a2 = t.ia * t.ia, b2 = t.ib * t.ib;
+    const double R = a2 + b2;
+    int k = 1;
+    while (k < aa_max && (double)(k * k) * 2.0 < R) k *= 2;
+    return k;
+}
+
 }  // namespace rf

@@ -316,8 +316,10 @@ int rf_face_value_table(const rf_face_batch_spec *spec, int channel, void *out25
     rf::FaceBatchSpec sp;
     rf_face_batch_spec any;
     if (!spec || !out256 || channel < 0 || channel > 2) return RF_ERR_INVALID_ARG;
-    any = *spec;
-    if (any.struct_size == sizeof(any) && any.capacity == 0) any.capacity = 1;      // the table does not depend on it
+    if (spec->struct_size != sizeof(any) && spec->struct_size != rf::kFaceSpecSizeV1) return RF_ERR_INVALID_ARG;
+    memset(&any, 0, sizeof(any));
+    memcpy(&any, spec, spec->struct_size);                       // only the bytes the caller's struct has
+    if (any.capacity == 0) any.capacity = 1;                     // the table does not depend on it
     if (rf::face_batch_resolve(&any, 256, &sp)) return RF_ERR_INVALID_ARG;
     const float m = sp.mean[channel], k = sp.scale[channel];
     for (unsigned q = 0; q < 256; q++) {
@@ -326,6 +328,15 @@ int rf_face_value_table(const rf_face_batch_spec *spec, int channel, void *out25
         else ((float *)out256)[q] = rf::face_value<float>(q, m, k);
     }
     return RF_OK;
+}
+
+int rf_face_aa_factor(const rf_face *face, float coord_scale, int crop_size, int aa_max) {
+    if (!face) return RF_ERR_INVALID_ARG;
+    const int S = crop_size ? crop_size : rf::kFaceBatchDefaultCrop, kmax = rf::face_aa_max_resolve(aa_max);
+    if (S < rf::kAlignMinCrop || S > rf::kAlignMaxCrop || !kmax) return RF_ERR_INVALID_ARG;
+    rf::AlignXform t;
+    rf::align_estimate(face->px, face->py, coord_scale, S, &t);
+    return rf::align_aa_factor(t, kmax);
 }
 
 int rf_detect_face_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,

@@ -515,6 +515,7 @@ public:
                     qp.counts = (const int *)(d_tab + o_cnt) + base;
                     qp.scale = (const float *)(d_tab + o_sc) + base;
                     qp.n = std::min(per, n - base); qp.max_faces = rq.spec.max_faces; qp.crop = rq.spec.crop;
+                    qp.aa_max = rq.spec.antialias ? rq.spec.aa_max : 0;
                     qp.has_gate = rq.has_gate ? 1 : 0; qp.gate = rq.gate;
                     qp.records = (rf_face_quality *)fq_records_.ptr + (size_t)base * rq.spec.max_faces;
                     launch_face_quality(align_stream_, qp);
@@ -1155,6 +1156,7 @@ private:
             qp.counts = s.h_counts;
             qp.scale = s.h_align_scale;
             qp.n = n; qp.max_faces = spec.max_faces; qp.crop = spec.crop;
+            qp.aa_max = spec.antialias ? spec.aa_max : 0;
             qp.has_gate = fb_.rq.has_gate ? 1 : 0; qp.gate = fb_.rq.gate;
             qp.records = (rf_face_quality *)fq_records_.ptr + slot0;
             launch_face_quality(s.stream, qp);

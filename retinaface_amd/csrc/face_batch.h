@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "../../include/retinaface_amd.h"
 #include "align.h"
@@ -14,12 +15,22 @@
 namespace rf {
 
 constexpr int kFaceBatchDefaultCrop = 112;
+constexpr int kFaceDefaultAaMax = 4;
+constexpr size_t kFaceSpecSizeV1 = 48;                                 // rf_face_batch_spec up to and including capacity: antialias = 0
+static_assert(sizeof(rf_face_batch_spec) == 56, "rf_face_batch_spec is 56 bytes");
+
+// aa_max as a caller gives it (0 = the default) -> 1, 2, 4 or 8; 0 for anything else
+inline int face_aa_max_resolve(int aa_max) {
+    if (aa_max == 0) return kFaceDefaultAaMax;
+    return (aa_max == 1 || aa_max == 2 || aa_max == 4 || aa_max == 8) ? aa_max : 0;
+}
 
 // a validated rf_face_batch_spec with its defaults applied
 struct FaceBatchSpec {
     int crop = kFaceBatchDefaultCrop, format = RF_FACES_U8_HWC, rgb = 0;
     float mean[3] = {127.5f, 127.5f, 127.5f}, scale[3] = {1.f / 128.f, 1.f / 128.f, 1.f / 128.f};      // per OUTPUT channel
     int max_faces = 0, capacity = 0;
+    int antialias = 0, aa_max = 4;                                     // supersampled sampling (align_aa_factor) and its largest factor
     __host__ __device__ int elem_bytes() const { return format == RF_FACES_F32_CHW ? 4 : format == RF_FACES_F16_CHW ? 2 : 1; }
     size_t bytes_per_face() const { return (size_t)3 * crop * crop * elem_bytes(); }
 };
@@ -40,10 +51,17 @@ template <> __host__ __device__ inline _Float16 face_value<_Float16>(unsigned q,
 inline bool face_batch_finite(float v) { return v == v && v - v == 0.f; }
 
 // Host: check a caller's spec and apply its defaults (crop 0 = 112, all-zero scale = (v - 127.5) / 128, max_faces 0 =
-// default_max_faces).  Returns nullptr, or what is wrong with it.
-inline const char *face_batch_resolve(const rf_face_batch_spec *s, int default_max_faces, FaceBatchSpec *out) {
-    if (!s) return "face batch spec is null";
-    if (s->struct_size != sizeof(rf_face_batch_spec)) return "rf_face_batch_spec.struct_size mismatch";
+// default_max_faces, aa_max 0 = 4).  struct_size is the current size or the one before antialias / aa_max were appended (they are 0
+// then): only that many bytes of the caller's struct are read.  Returns nullptr, or what is wrong with it.
+inline const char *face_batch_resolve(const rf_face_batch_spec *in, int default_max_faces, FaceBatchSpec *out) {
+    if (!in) return "face batch spec is null";
+    if (in->struct_size != sizeof(rf_face_batch_spec) && in->struct_size != kFaceSpecSizeV1) return "rf_face_batch_spec.struct_size mismatch";
+    rf_face_batch_spec local;
+    memset(&local, 0, sizeof(local));
+    memcpy(&local, in, in->struct_size);
+    const rf_face_batch_spec *s = &local;
+    if (s->antialias != 0 && s->antialias != 1) return "antialias must be 0 or 1";
+    if (!face_aa_max_resolve(s->aa_max)) return "aa_max must be 0, 1, 2, 4 or 8";
     if (s->crop_size != 0 && (s->crop_size < kAlignMinCrop || s->crop_size > kAlignMaxCrop)) return "crop_size must be 0 or in [16, 512]";
     if (s->format != RF_FACES_U8_HWC && s->format != RF_FACES_F16_CHW && s->format != RF_FACES_F32_CHW) return "unknown face format";
     if (s->max_faces < 0 || s->max_faces > kAlignMaxFaces) return "max_faces must be 0 or in [1, 4096]";
@@ -59,6 +77,8 @@ inline const char *face_batch_resolve(const rf_face_batch_spec *s, int default_m
     r.max_faces = s->max_faces ? s->max_faces : default_max_faces;
     if (r.max_faces < 1 || r.max_faces > kAlignMaxFaces) return "max_faces must be in [1, 4096]";
     r.capacity = s->capacity;
+    r.antialias = s->antialias;
+    r.aa_max = face_aa_max_resolve(s->aa_max);
     *out = r;
     return nullptr;
 }

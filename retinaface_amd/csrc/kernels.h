@@ -217,7 +217,7 @@ struct FaceBatchParams {
     const float *scale;
     const int *offsets;                   // [n + 1], what launch_face_scan wrote (not read when packed is set)
     int n, max_faces;
-    FaceBatchSpec spec;                   // crop edge, format, channel order, mean / scale, capacity
+    FaceBatchSpec spec;                   // crop edge, format, channel order, mean / scale, capacity, antialias
     void *tensor;                         // [capacity] faces of 3 * S * S elements, aligned to the element size, or nullptr
     double *mats;                         // [capacity][6], or nullptr
     const int *packed = nullptr;          // gated: packed index of (image i, face k) at packed[i * max_faces + k], -1 = not packed
@@ -236,6 +236,7 @@ struct FaceQualityParams {
     const int *counts;                    // [n] faces of each image (clamped to faces_per_image and max_faces here)
     const float *scale;
     int n, max_faces, crop;
+    int aa_max = 0;                       // 0: the plain crop; 1, 2, 4, 8: the antialiased crop with this largest factor (align_aa_factor)
     int has_gate;                         // 0: flags stay 0
     FaceGate gate;
     rf_face_quality *records;             // [n * max_faces] out: (image i, face k) at i * max_faces + k; considered faces only

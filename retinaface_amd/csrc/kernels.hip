@@ -11,6 +11,7 @@
 #include "kernels.h"
 
 #include <atomic>
+#include <type_traits>
 
 #include "pack.h"
 
@@ -4040,6 +4041,17 @@ struct AlignSampler {
           ymax((double)(fd.rows + 1)) {}
 };
 
+// what thread 0 leaves in LDS for its workgroup: the transform, and for the antialiased instances the supersampling factor next to it
+struct AlignXformAA : AlignXform { int k; };
+template <bool AA> using AlignShared = typename std::conditional<AA, AlignXformAA, AlignXform>::type;
+template <bool AA> __device__ __forceinline__ void align_shared_set_factor(AlignShared<AA> &x, int aa_max) {
+    if constexpr (AA) x.k = align_aa_factor(x, aa_max);
+}
+template <bool AA> __device__ __forceinline__ int align_shared_factor(const AlignShared<AA> &x) {
+    if constexpr (AA) return x.k;
+    else return 1;
+}
+
 __device__ __forceinline__ void align_sample(const FrameDesc &fd, const AlignSampler &sm, int u, int v, unsigned acc[3]) {
 #pragma clang fp contract(off)
     acc[0] = acc[1] = acc[2] = 0u;
@@ -4061,6 +4073,43 @@ __device__ __forceinline__ void align_sample(const FrameDesc &fd, const AlignSam
 #pragma unroll
         for (int c = 0; c < 3; c++) acc[c] = (acc[c] + (1u << 19)) >> 20;
     }
+}
+
+// The antialiased counterpart (DESIGN.md "Antialiased face crops"): k x k sub-samples per crop pixel (k = 1, 2, 4, 8:
+// align_aa_factor), each at its own position -- ((double)u + ou) - mqx with ou = (2i + 1 - k) / 2k, an exact double -- and from there
+// on align_sample's arithmetic up to the unshifted sum; the sums of all sub-samples are added in 64 bits and shifted once.  k = 1:
+// ou = 0, one sub-sample, the shift is 20 -- align_sample's value bit for bit.
+__device__ __forceinline__ void align_sample_aa(const FrameDesc &fd, const AlignSampler &sm, int k, int u, int v, unsigned acc[3]) {
+#pragma clang fp contract(off)
+    unsigned long long sum[3] = {0ull, 0ull, 0ull};
+    const double inv2k = 1.0 / (double)(2 * k);                   // a power of two: (2i + 1 - k) * inv2k = (2i + 1 - k) / 2k exactly
+    if (sm.valid) {
+        for (int j = 0; j < k; j++) {
+            const double dv = ((double)v + (double)(2 * j + 1 - k) * inv2k) - sm.mqy;
+            for (int i = 0; i < k; i++) {
+                const double du = ((double)u + (double)(2 * i + 1 - k) * inv2k) - sm.mqx;
+                const double x = (sm.ia * du - sm.ib * dv) + sm.mpx;
+                const double y = (sm.ib * du + sm.ia * dv) + sm.mpy;
+                if (!(x > -2.0 && x < sm.xmax && y > -2.0 && y < sm.ymax)) continue;
+                const long long X = (long long)floor(x * 1024.0 + 0.5), Y = (long long)floor(y * 1024.0 + 0.5);
+                const int x0 = (int)(X >> 10), y0 = (int)(Y >> 10);
+                const unsigned fx = (unsigned)(X & 1023), fy = (unsigned)(Y & 1023);
+                unsigned part[3] = {0u, 0u, 0u};                  // <= 255 * 2^20
+#pragma unroll
+                for (int t = 0; t < 4; t++) {
+                    const int xx = x0 + (t & 1), yy = y0 + (t >> 1);
+                    if (xx < 0 || xx >= fd.cols || yy < 0 || yy >= fd.rows) continue;
+                    const unsigned w = ((t & 1) ? fx : 1024u - fx) * ((t >> 1) ? fy : 1024u - fy);
+                    const uint8_t *sp = fd.ptr + (size_t)yy * fd.step + (size_t)xx * 3;
+                    part[0] += w * sp[0]; part[1] += w * sp[1]; part[2] += w * sp[2];
+                }
+                sum[0] += part[0]; sum[1] += part[1]; sum[2] += part[2];
+            }
+        }
+    }
+    const int shift = 20 + 2 * (31 - __builtin_clz((unsigned)k));   // k = 2^m: 20 + 2m
+#pragma unroll
+    for (int c = 0; c < 3; c++) acc[c] = (unsigned)((sum[c] + (1ull << (shift - 1))) >> shift);
 }
 
 __global__ __launch_bounds__(kThreads) void align_kernel(AlignParams a) {
@@ -4129,6 +4178,8 @@ void launch_align(hipStream_t s, const AlignParams &p) {
 //      align_sample).  A band is one contiguous run of the destination for HWC and three for CHW, one per plane; each run is
 //      assembled in LDS at its destination's 16-byte phase and leaves as whole 16-byte vectors per lane, its unaligned head and
 //      tail as elements.  The band height shrinks with the element size so that the three runs of S = 512 fp32 fit 12 KB of LDS.
+//      AA = true (spec.antialias): thread 0 also puts the face's supersampling factor (align_aa_factor) into LDS and the pixel loop
+//      calls align_sample_aa; everything else is shared.  The AA = false instances are the kernel as it was.
 // =============================================================================================
 constexpr int kFaceRunBytes = 4096;                              // LDS bytes of one CHW run (a band of one plane)
 constexpr int kFaceLdsVecs = 3 * (kFaceRunBytes / 16 + 1);       // three runs + 16 bytes of phase each; one HWC run of 8 x 512 x 3 fits too
@@ -4181,10 +4232,10 @@ __device__ __forceinline__ void face_store_run(uint8_t *dst, const uint8_t *lds,
     if (t < nbytes - tail0) *(E *)(dst + tail0 + t) = *(const E *)(lds + tail0 + t);
 }
 
-template <typename E, bool CHW>
+template <typename E, bool CHW, bool AA>
 __global__ __launch_bounds__(kThreads) void face_batch_kernel(FaceBatchParams a, int band_rows) {
 #pragma clang fp contract(off)
-    __shared__ AlignXform xf;
+    __shared__ AlignShared<AA> xf;                               // AA: with the face's supersampling factor next to the transform
     __shared__ uint4 band_buf[kFaceLdsVecs];
     const int band = blockIdx.x, k = blockIdx.y, img = blockIdx.z;
     int j;
@@ -4205,6 +4256,7 @@ __global__ __launch_bounds__(kThreads) void face_batch_kernel(FaceBatchParams a,
         float px[5], py[5];
         for (int i = 0; i < 5; i++) { px[i] = f[5 + i]; py[i] = f[10 + i]; }
         align_estimate(px, py, a.scale ? a.scale[img] : 1.f, S, &xf);
+        align_shared_set_factor<AA>(xf, a.spec.aa_max);
         if (band == 0 && a.mats)
             for (int i = 0; i < 6; i++) a.mats[(size_t)j * 6 + i] = xf.fwd[i];
     }
@@ -4224,9 +4276,11 @@ __global__ __launch_bounds__(kThreads) void face_batch_kernel(FaceBatchParams a,
     }
     const int flip = a.spec.rgb ? 2 : 0;
     const AlignSampler sm(xf, fd);
+    const int aak = align_shared_factor<AA>(xf);
     for (int p = threadIdx.x; p < npix; p += kThreads) {
         unsigned acc[3];
-        align_sample(fd, sm, p % S, r0 + p / S, acc);
+        if (AA) align_sample_aa(fd, sm, aak, p % S, r0 + p / S, acc);
+        else align_sample(fd, sm, p % S, r0 + p / S, acc);
 #pragma unroll
         for (int c = 0; c < 3; c++) {
             const E val = face_value<E>(acc[flip ? 2 - c : c], a.spec.mean[c], a.spec.scale[c]);
@@ -4250,10 +4304,16 @@ void launch_face_batch(hipStream_t s, const FaceBatchParams &p) {
     const int rows = face_batch_band_rows(sp.crop, sp.format);
     // matrices only: one band per face is enough
     dim3 grid(p.tensor ? (sp.crop + rows - 1) / rows : 1, slots, p.n);
-    if (sp.format == RF_FACES_U8_HWC) hipLaunchKernelGGL((face_batch_kernel<uint8_t, false>), grid, dim3(kThreads), 0, s, p, rows);
-    else if (sp.format == RF_FACES_F16_CHW) hipLaunchKernelGGL((face_batch_kernel<half_t, true>), grid, dim3(kThreads), 0, s, p, rows);
-    else if (sp.format == RF_FACES_F32_CHW) hipLaunchKernelGGL((face_batch_kernel<float, true>), grid, dim3(kThreads), 0, s, p, rows);
-    else throw Unsupported("face batch: unknown format");
+    if (sp.format != RF_FACES_U8_HWC && sp.format != RF_FACES_F16_CHW && sp.format != RF_FACES_F32_CHW) throw Unsupported("face batch: unknown format");
+    if (sp.antialias) {                                          // the supersampled instances; the plain ones below are untouched by it
+        if (sp.aa_max != 1 && sp.aa_max != 2 && sp.aa_max != 4 && sp.aa_max != 8) throw Unsupported("face batch: aa_max must be 1, 2, 4 or 8");
+        if (sp.format == RF_FACES_U8_HWC) hipLaunchKernelGGL((face_batch_kernel<uint8_t, false, true>), grid, dim3(kThreads), 0, s, p, rows);
+        else if (sp.format == RF_FACES_F16_CHW) hipLaunchKernelGGL((face_batch_kernel<half_t, true, true>), grid, dim3(kThreads), 0, s, p, rows);
+        else hipLaunchKernelGGL((face_batch_kernel<float, true, true>), grid, dim3(kThreads), 0, s, p, rows);
+    }
+    else if (sp.format == RF_FACES_U8_HWC) hipLaunchKernelGGL((face_batch_kernel<uint8_t, false, false>), grid, dim3(kThreads), 0, s, p, rows);
+    else if (sp.format == RF_FACES_F16_CHW) hipLaunchKernelGGL((face_batch_kernel<half_t, true, false>), grid, dim3(kThreads), 0, s, p, rows);
+    else hipLaunchKernelGGL((face_batch_kernel<float, true, false>), grid, dim3(kThreads), 0, s, p, rows);
 }
 
 // =============================================================================================
@@ -4263,6 +4323,7 @@ void launch_face_batch(hipStream_t s, const FaceBatchParams &p) {
 //      band are still in the ring, so no row is sampled twice.  Every statistic is an integer sum: 64-bit per thread where a
 //      thread's share can pass 2^31, reduced with wave shuffles and one LDS step -- the same integers whatever the order, no
 //      atomics, nothing to zero beforehand.  Thread 0 finishes the record, evaluates the gate and stores the 64 bytes.
+//      AA = true (FaceQualityParams.aa_max != 0): the luma is that of align_sample_aa's value; covered stays the pixel centre's.
 //      face_gate_scan_kernel (one workgroup): kept faces per image from the records' flags, their prefix sum on top of the call's
 //      running base (the protocol of face_scan_kernel), and the packed index of every face slot for face_batch_kernel.
 // =============================================================================================
@@ -4293,9 +4354,10 @@ __device__ __forceinline__ long long wave_sum(long long v) {
     return v;
 }
 
+template <bool AA>
 __global__ __launch_bounds__(kThreads) void face_quality_kernel(FaceQualityParams a, int ring_rows) {
 #pragma clang fp contract(off)
-    __shared__ AlignXform xf;
+    __shared__ AlignShared<AA> xf;                               // AA: with the face's supersampling factor next to the transform
     __shared__ rf_face_quality rec;
     __shared__ uint8_t ring[kQualityRingBytes];
     __shared__ long long part[4][kThreads / 64];
@@ -4313,10 +4375,12 @@ __global__ __launch_bounds__(kThreads) void face_quality_kernel(FaceQualityParam
         for (int i = 0; i < 5; i++) { px[i] = f[5 + i]; py[i] = f[10 + i]; }
         const float cs = a.scale ? a.scale[img] : 1.f;
         align_estimate(px, py, cs, S, &xf);
+        align_shared_set_factor<AA>(xf, a.aa_max);
         face_pose(px, py, cs, xf, &rec);
     }
     __syncthreads();
     const AlignSampler sm(xf, fd);
+    const int aak = align_shared_factor<AA>(xf);
     const int R = ring_rows - 2, W = S - 2;                       // new rows per band; interior columns
     long long s_luma = 0, s_lap = 0, s_lap2 = 0, s_cov = 0;
     if (xf.valid) {                                               // uniform: an invalid face has every sum 0
@@ -4326,7 +4390,8 @@ __global__ __launch_bounds__(kThreads) void face_quality_kernel(FaceQualityParam
             for (int p = threadIdx.x; p < npix; p += kThreads) {
                 const int v = v0 + p / S, u = p % S;
                 unsigned acc[3];
-                align_sample(fd, sm, u, v, acc);
+                if (AA) align_sample_aa(fd, sm, aak, u, v, acc);
+                else align_sample(fd, sm, u, v, acc);
                 const int cov = align_covered(fd, sm, u, v);
                 const unsigned y = face_luma(acc[0], acc[1], acc[2]);
                 ring[(v % ring_rows) * S + u] = (uint8_t)y;
@@ -4372,7 +4437,9 @@ void launch_face_quality(hipStream_t s, const FaceQualityParams &p) {
     if (!p.records) throw Unsupported("face quality: no record buffer");
     const int slots = p.max_faces < p.faces_per_image ? p.max_faces : p.faces_per_image;
     if (slots <= 0) return;
-    hipLaunchKernelGGL(face_quality_kernel, dim3(slots, p.n), dim3(kThreads), 0, s, p, face_quality_ring_rows(p.crop));
+    if (p.aa_max != 0 && p.aa_max != 1 && p.aa_max != 2 && p.aa_max != 4 && p.aa_max != 8) throw Unsupported("face quality: aa_max must be 0, 1, 2, 4 or 8");
+    if (p.aa_max) hipLaunchKernelGGL(face_quality_kernel<true>, dim3(slots, p.n), dim3(kThreads), 0, s, p, face_quality_ring_rows(p.crop));
+    else hipLaunchKernelGGL(face_quality_kernel<false>, dim3(slots, p.n), dim3(kThreads), 0, s, p, face_quality_ring_rows(p.crop));
 }
 
 __global__ __launch_bounds__(kThreads) void face_gate_scan_kernel(FaceGateScanParams a) {

@@ -59,9 +59,10 @@ _FACE_FORMATS = {"u8": (_lib.RF_FACES_U8_HWC, np.uint8), "f16": (_lib.RF_FACES_F
 
 
 def face_batch_spec(crop_size: int = 112, dtype: str = "f16", rgb: bool = True, mean=None, scale=None, max_faces: int = 0,
-                    capacity: int = 1) -> rf_face_batch_spec:
+                    capacity: int = 1, antialias: bool = False, aa_max: int = 0) -> rf_face_batch_spec:
     """An rf_face_batch_spec: dtype "u8" (HWC), "f16" or "f32" (CHW); mean / scale: one number or three, per OUTPUT channel
-    (both None = (v - 127.5) / 128); max_faces 0 = the engine's max_detections."""
+    (both None = (v - 127.5) / 128); max_faces 0 = the engine's max_detections; antialias: supersample faces larger than their crop
+    with up to aa_max (1, 2, 4, 8; 0 = 4) sub-samples per axis (face_aa_factor gives a face's factor)."""
     if dtype not in _FACE_FORMATS:
         raise ValueError('dtype must be "u8", "f16" or "f32"')
     sp = rf_face_batch_spec()
@@ -74,7 +75,19 @@ def face_batch_spec(crop_size: int = 112, dtype: str = "f16", rgb: bool = True, 
     elif mean is not None:
         raise ValueError("mean without scale")
     sp.max_faces, sp.capacity = int(max_faces), int(capacity)
+    sp.antialias, sp.aa_max = 1 if antialias else 0, int(aa_max)
     return sp
+
+
+def face_aa_factor(face, coord_scale: float = 1.0, crop_size: int = 112, aa_max: int = 0) -> int:
+    """rf_face_aa_factor (host only, no GPU): the supersampling factor per axis (1, 2, 4 or 8; 1 for an invalid face) an antialiased
+    face batch gives this face -- a Detection or 15 floats -- with this aa_max (0 = 4)."""
+    lib = _lib.load_library()
+    f = rf_face.from_buffer_copy(_face_rows([face])[0].tobytes())
+    k = lib.rf_face_aa_factor(C.byref(f), float(coord_scale), int(crop_size), int(aa_max))
+    if k < 0:
+        raise _lib.RFError(k, "rf_face_aa_factor: bad argument (crop_size must be 0 or in [16, 512], aa_max 0, 1, 2, 4 or 8)")
+    return int(k)
 
 
 def face_batch_plan(counts: Sequence[int], *, crop_size: int = 112, dtype: str = "f16", max_faces: int = 0, capacity: int = 1):
@@ -371,7 +384,9 @@ class RetinaFace:
         whether total exceeded the capacity.
         gate= (an rf_face_gate from face_gate(), or a dict of its keywords) packs only the faces that pass it;
         return_quality=True appends a fifth result: per image a QUALITY_DTYPE array with the record of every considered face
-        (k < min(faces, max_faces)), kept or dropped.  With neither, the ungated C entry point is called."""
+        (k < min(faces, max_faces)), kept or dropped.  With neither, the ungated C entry point is called.
+        antialias=True supersamples faces that are larger in the frame than their crop, with up to aa_max (1, 2, 4, 8; 0 = 4)
+        sub-samples per axis (face_aa_factor gives a face's factor); the records' luma numbers are then the antialiased crop's."""
         n = len(imgs)
         ptrs = (C.c_void_p * max(n, 1))()
         rows, cols, steps = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
@@ -473,10 +488,10 @@ class RetinaFace:
 
     def _face_batch_call(self, call, n, crop_size: int = 112, dtype: str = "f16", rgb: bool = True, mean=None, scale=None,
                          max_faces: Optional[int] = None, capacity: Optional[int] = None, d_out: Optional[int] = None, host: bool = True,
-                         gate=None, return_quality: bool = False):
+                         gate=None, return_quality: bool = False, antialias: bool = False, aa_max: int = 0):
         mf = int(max_faces) if max_faces else self.max_detections
         capacity = int(capacity) if capacity is not None else max(1, n * mf)
-        sp = face_batch_spec(crop_size, dtype, rgb, mean, scale, mf, capacity)
+        sp = face_batch_spec(crop_size, dtype, rgb, mean, scale, mf, capacity, antialias, aa_max)
         S = int(crop_size) if crop_size else 112
         shape = (S, S, 3) if dtype == "u8" else (3, S, S)
         tensor = np.zeros((max(capacity, 0),) + shape, _FACE_FORMATS[dtype][1]) if host else None
