@@ -89,6 +89,13 @@ public:
     const vector<rf_face_quality> &faceBatchQuality() const { return faceQuality_; }
     int faceBatchQualityStride() const { return faceQualityStride_; }
 
+    /* additive: tiled detection (rf_detect_tiled_batch): frames larger than the net are cut into overlapping net-sized tiles that are
+       detected at 1:1 and merged on the device, so small faces in large frames are not shrunk away.  Fills lastBatchResult() with the
+       merged faces in SOURCE-FRAME pixels (at most spec->max_faces per frame); tileSources() holds, per frame, the pass of the frame's
+       plan (rf_tile_plan) each face came from.  spec may be nullptr (the defaults). */
+    void detectTiled(const vector<cv::Mat> &imgs, float threshold = 0.5, const rf_tile_spec *spec = nullptr);
+    const vector<vector<int>> &tileSources() const { return tileSrc_; }
+
     /* `scale` of RetinaFace.cpp:585-589: multiply lastResult() coordinates by it for source-frame pixels (:732-739, commented) */
     float frameScale(const Mat &img) const { return rf_frame_scale(h_, img.rows, img.cols); }
 
@@ -113,6 +120,7 @@ private:
     bool faceTruncated_ = false;
     vector<rf_face_quality> faceQuality_;
     int faceQualityStride_ = 0;
+    vector<vector<int>> tileSrc_;
     vector<uint8_t> faceBatchCall(const vector<cv::Mat> &imgs, float threshold, const rf_face_batch_spec &spec, bool gated,
                                   const rf_face_gate *gate);
 };

@@ -329,6 +329,80 @@ int rf_detect_face_batch_gated(rf_handle h, const uint8_t *const *bgr, const int
                                void *d_tensor, void *tensor, double *matrices, int *offsets, const rf_face_gate *gate,
                                rf_face_quality *quality);
 
+/* ---- Tiled detection: a frame LARGER than the net is cut into net-sized tiles that overlap, every tile is detected at 1:1, and the
+ * faces of all tiles are moved into source-frame pixels and merged on the device (DESIGN.md "Tiled detection" holds the definition;
+ * tests/tile_ref.py restates it in numpy; every result is byte-exact against it):
+ *   plan     per axis, length L, net size N, overlap ov: L <= N: one tile (0, L); else n = ceil((L - ov) / (N - ov)) tiles of size N at
+ *            o_i = floor(i * (L - N) / (n - 1)).  Tiles are row-major, t = ty * nx + tx, T = nx * ny; with full_frame on and a frame larger
+ *            than the net in some dimension the whole frame, shrunk as rf_detect_batch_device shrinks it, is pass T.  A frame that fits
+ *            the net has the plan "one tile, no extra pass".  More than 1024 passes: RF_ERR_INVALID_ARG.
+ *   pass     the result of pass t is exactly what rf_detect_batch_device returns for the view {ptr + y0 * step + 3 * x0, th, tw, step}
+ *            (the full-frame pass: for the whole frame) at the call's threshold: up to max_detections faces in score order -- to
+ *            the byte when that call holds the passes of ALL frames of the tiled call in plan order, which is the call the engine
+ *            makes.  (As with rf_detect_batch_device itself, the last bits of a view's result can depend on what shares its launch:
+ *            conv0 sums an aligned dense frame in another order than a view with a row pitch, and a launch that holds an oversize
+ *            frame reads every image through the dense canvas.)
+ *   edge     in tile coordinates, fp32: face (x1, y1, x2, y2) of tile (x0, y0, tw, th) is dropped when  x0 > 0 && x1 < (float)edge,
+ *            y0 > 0 && y1 < (float)edge,  x0 + tw < cols && x2 > (float)(tw - 1 - edge)  or  y0 + th < rows && y2 > (float)(th - 1 - edge):
+ *            boxes that reach a tile side which is not a frame side.  The full-frame pass drops nothing.
+ *   mapping  tile: one fp32 add of (float)x0 to every x coordinate (box and landmarks), of (float)y0 to every y coordinate;
+ *            full-frame pass: one fp32 multiply of all 14 coordinates by rf_frame_scale(rows, cols).  Scores are unchanged.  Results are
+ *            in SOURCE-FRAME pixels: their coord_scale for the alignment and face-batch calls is 1.
+ *   merge    per frame, over the surviving faces of all passes: order by score descending (bit order), then g = t * max_detections + k
+ *            ascending (k: the rank in the pass's result); greedy suppression exactly as the detector's NMS (+1-pixel areas, strict
+ *            > nms_threshold of the handle).  counts[i] is the true number kept; out[i * cap_per_image + k] holds the first
+ *            min(counts[i], cap_per_image, max_faces) in merge order; src_tile (may be NULL; same indexing) the pass each came from.
+ *   caps     a pass whose own result was truncated contributes what it holds and the call returns RF_ERR_TRUNCATED; so does a frame
+ *            with more than 4096 surviving candidates, whose faces are then unspecified (the other frames are valid); so does a
+ *            merged list that max_faces or cap_per_image cut (counts[i] > min(max_faces, cap_per_image)), as rf_detect_batch reports
+ *            a cut list: counts stay true and the faces returned are the first of the merge order.
+ * A frame that fits the net gives the faces and counts of rf_detect_batch_device, byte for byte. */
+typedef struct rf_tile_spec {
+    uint32_t struct_size;   /* sizeof(rf_tile_spec) */
+    int32_t overlap;        /* minimum overlap of neighbouring tiles in pixels, < min(net_h, net_w); 0 = min(net_h, net_w) / 4; negative = 0 px */
+    int32_t edge;           /* width of the border band of the edge rule in pixels, < min(net_h, net_w) / 2; 0 = 8; negative = 0 */
+    int32_t full_frame;     /* 0 / 1 = also run the whole frame shrunk as one more pass; 2 = off */
+    int32_t max_faces;      /* merged faces kept per frame on the device, 1..4096; 0 = the engine's max_detections */
+} rf_tile_spec;
+
+/* Host only, no GPU, no handle -- the same code the kernel runs, compiled for the host.  spec may be NULL (all defaults; max_faces 0
+ * stands for 256 here).
+ * rf_tile_plan: the number of passes of a rows x cols frame at a net_h x net_w net, the full-frame pass included, or RF_ERR_INVALID_ARG
+ * (bad spec, non-positive net size, negative or over-size frame, more than 1024 passes).  xywh (may be NULL) receives x0, y0, tw, th
+ * of the first min(passes, cap_tiles) passes; the full-frame pass is reported as 0, 0, cols, rows.
+ * rf_tile_map_face: edge rule and mapping of one face of pass t: 1 = kept, *out is the mapped face (out may equal in); 0 = dropped by the
+ * edge rule; RF_ERR_INVALID_ARG as above or for t outside the plan. */
+int rf_tile_plan(const rf_tile_spec *spec, int rows, int cols, int net_h, int net_w, int *xywh, int cap_tiles);
+int rf_tile_map_face(const rf_tile_spec *spec, int rows, int cols, int net_h, int net_w, int t, const rf_face *in, rf_face *out);
+
+/* Tiled detection of frames resident on the engine's device (frame limits as rf_detect_batch_device; a NULL / 0 x 0 frame yields count
+ * 0).  The passes of all frames go through the engine's ordinary launches (chunked by max_batch, coalesced, spread over the lanes; the
+ * shrunk full-frame passes share launches with the 1:1 tiles); a gather kernel behind each launch applies the edge rule and the
+ * mapping, and one merge launch behind the call's last launch waits for them on the device -- no host synchronisation in between.
+ * spec may be NULL.  A bad spec is refused before any state changes.  Multi-device handles return RF_ERR_UNSUPPORTED from this and
+ * the next three calls.  rf_last_anchor_indices / rf_last_candidate_counts afterwards describe the call's PASSES, in plan order. */
+int rf_detect_tiled_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                 float threshold, const rf_tile_spec *spec, rf_face *out, int cap_per_image, int *counts, int *src_tile);
+
+/* The same with frames in HOST memory (rf_detect_batch's convention): each frame is uploaded once, the tiles are views of that copy. */
+int rf_detect_tiled_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                          float threshold, const rf_tile_spec *spec, rf_face *out, int cap_per_image, int *counts, int *src_tile);
+
+/* Edge rule, mapping and merge of per-pass faces the CALLER supplies (host memory; the counterpart of rf_face_batch_device for this
+ * stage): with first_pass[i] the running sum of the frames' plan sizes, pass t of frame i holds pass_counts[first_pass[i] + t] faces
+ * (clamped to max_detections) at faces[(first_pass[i] + t) * max_detections + k].  No forward pass runs. */
+int rf_tile_merge_device(rf_handle h, const int *rows, const int *cols, int n, const rf_tile_spec *spec, const rf_face *faces,
+                         const int *pass_counts, rf_face *out, int cap_per_image, int *counts, int *src_tile);
+
+/* rf_detect_tiled_batch_device followed ON THE DEVICE by the face batch of the merged faces (rf_face_batch_gated_device's launches,
+ * reading the merged faces and counts from device memory with coordinate scale 1): m_i = min(counts[i], fb_spec max_faces, tile_spec
+ * max_faces).  tensor, matrices, offsets and quality are the bytes rf_face_batch_gated_device gives for the tiled call's out / counts
+ * with coord_scale = NULL; gate = NULL and quality = NULL: those of rf_face_batch_device.  RF_ERR_TRUNCATED as in both calls. */
+int rf_detect_tiled_face_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                      float threshold, const rf_tile_spec *tile_spec, rf_face *out, int cap_per_image, int *counts,
+                                      int *src_tile, const rf_face_batch_spec *fb_spec, void *d_tensor, void *tensor, double *matrices,
+                                      int *offsets, const rf_face_gate *gate, rf_face_quality *quality);
+
 /* Asynchronous form of rf_detect_batch_device for serving loops: enqueue returns as soon as the
  * batch is queued on the engine's stream (n <= max_batch); `ticket` identifies one of
  * rf_num_slots() result slots.  rf_wait blocks until that batch has finished and copies its results.

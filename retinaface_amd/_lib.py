@@ -53,6 +53,11 @@ class rf_face_gate(C.Structure):
                 ("max_sin2_roll", C.c_float), ("min_covered", C.c_float), ("min_luma", C.c_float), ("max_luma", C.c_float)]
 
 
+class rf_tile_spec(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("overlap", C.c_int32), ("edge", C.c_int32), ("full_frame", C.c_int32),
+                ("max_faces", C.c_int32)]
+
+
 RF_GATE_INVALID, RF_GATE_SHARPNESS, RF_GATE_IOD, RF_GATE_YAW, RF_GATE_ROLL, RF_GATE_COVERED, RF_GATE_DARK, RF_GATE_BRIGHT = (
     1, 2, 4, 8, 16, 32, 64, 128)
 
@@ -111,6 +116,18 @@ SYMBOLS = {
                                              C.c_float, _PP(rf_face), C.c_int, _PP(C.c_int), _PP(rf_face_batch_spec),
                                              C.c_void_p, C.c_void_p, _PP(C.c_double), _PP(C.c_int), _PP(rf_face_gate),
                                              _PP(rf_face_quality)]),
+    "rf_tile_plan": (C.c_int, [_PP(rf_tile_spec), C.c_int, C.c_int, C.c_int, C.c_int, _PP(C.c_int), C.c_int]),
+    "rf_tile_map_face": (C.c_int, [_PP(rf_tile_spec), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _PP(rf_face), _PP(rf_face)]),
+    "rf_detect_tiled_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                               C.c_float, _PP(rf_tile_spec), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int)]),
+    "rf_detect_tiled_batch": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                        C.c_float, _PP(rf_tile_spec), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int)]),
+    "rf_tile_merge_device": (C.c_int, [C.c_void_p, _PP(C.c_int), _PP(C.c_int), C.c_int, _PP(rf_tile_spec), _PP(rf_face), _PP(C.c_int),
+                                       _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int)]),
+    "rf_detect_tiled_face_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                                    C.c_float, _PP(rf_tile_spec), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int),
+                                                    _PP(rf_face_batch_spec), C.c_void_p, C.c_void_p, _PP(C.c_double), _PP(C.c_int),
+                                                    _PP(rf_face_gate), _PP(rf_face_quality)]),
     "rf_num_slots": (C.c_int, [C.c_void_p]),
     "rf_enqueue_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int),
                                           C.c_int, C.c_float, _PP(C.c_int)]),

@@ -467,6 +467,102 @@ int rf_detect_face_batch_gated(rf_handle h, const uint8_t *const *bgr, const int
                                           tensor, matrices, offsets, gate, quality);
 }
 
+// ---- tiled detection (tile.h)
+int rf_tile_plan(const rf_tile_spec *spec, int rows, int cols, int net_h, int net_w, int *xywh, int cap_tiles) {
+    rf::TileSpec sp;
+    if (rf::tile_spec_resolve(spec, net_h, net_w, 256, &sp) || rows < 0 || cols < 0 || cap_tiles < 0) return RF_ERR_INVALID_ARG;
+    if (cols > 0 && rows > 4096 * 3072 / cols) return RF_ERR_INVALID_ARG;
+    int nx = 0, ny = 0, full = 0;
+    const int passes = rf::tile_plan_shape(sp, rows, cols, net_h, net_w, &nx, &ny, &full);
+    if (passes < 0) return RF_ERR_INVALID_ARG;
+    for (int t = 0; xywh && t < passes && t < cap_tiles; t++) {
+        const rf::TileEntry e = rf::tile_plan_entry(rows, cols, net_h, net_w, nx, ny, t, 0);
+        xywh[4 * t] = e.x0; xywh[4 * t + 1] = e.y0; xywh[4 * t + 2] = e.tw; xywh[4 * t + 3] = e.th;
+    }
+    return passes;
+}
+
+int rf_tile_map_face(const rf_tile_spec *spec, int rows, int cols, int net_h, int net_w, int t, const rf_face *in, rf_face *out) {
+    rf::TileSpec sp;
+    if (!in || !out || rf::tile_spec_resolve(spec, net_h, net_w, 256, &sp) || rows < 0 || cols < 0) return RF_ERR_INVALID_ARG;
+    if (cols > 0 && rows > 4096 * 3072 / cols) return RF_ERR_INVALID_ARG;
+    int nx = 0, ny = 0, full = 0;
+    const int passes = rf::tile_plan_shape(sp, rows, cols, net_h, net_w, &nx, &ny, &full);
+    if (passes < 0 || t < 0 || t >= passes) return RF_ERR_INVALID_ARG;
+    const rf::TileEntry e = rf::tile_plan_entry(rows, cols, net_h, net_w, nx, ny, t, 0);
+    float f[15];
+    memcpy(f, in, sizeof(f));
+    if (!rf::tile_map_face(e, sp.edge, f, f)) return 0;
+    memcpy(out, f, sizeof(f));
+    return 1;
+}
+
+namespace {
+// a caller's tile spec, checked against the handle's net size and with its defaults applied; refused before the engine is touched
+void tile_request(rf_handle h, const rf_tile_spec *spec, int *src_tile, rf::TileRequest *rq) {
+    if (const char *bad = rf::tile_spec_resolve(spec, h->eng->net_h(), h->eng->net_w(), h->eng->default_max_faces(), &rq->spec))
+        throw rf::ArgError(bad);
+    rq->src_tile = src_tile;
+}
+
+int detect_tiled_common(rf_handle h, const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,
+                        float thr, const rf_tile_spec *spec, rf_face *out, int cap, int *counts, int *src_tile) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        rf::TileRequest rq;
+        tile_request(h, spec, src_tile, &rq);
+        bool tr = false, over = false;
+        h->eng->detect_tiled(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, rq, &over);
+        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+}  // namespace
+
+int rf_detect_tiled_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                 float threshold, const rf_tile_spec *spec, rf_face *out, int cap_per_image, int *counts, int *src_tile) {
+    return detect_tiled_common(h, (const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, spec, out, cap_per_image, counts,
+                               src_tile);
+}
+
+int rf_detect_tiled_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                          float threshold, const rf_tile_spec *spec, rf_face *out, int cap_per_image, int *counts, int *src_tile) {
+    return detect_tiled_common(h, bgr, rows, cols, steps, n, false, threshold, spec, out, cap_per_image, counts, src_tile);
+}
+
+int rf_tile_merge_device(rf_handle h, const int *rows, const int *cols, int n, const rf_tile_spec *spec, const rf_face *faces,
+                         const int *pass_counts, rf_face *out, int cap_per_image, int *counts, int *src_tile) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        rf::TileRequest rq;
+        tile_request(h, spec, src_tile, &rq);
+        bool tr = false;
+        h->eng->tile_merge(rows, cols, n, rq, faces, pass_counts, out, cap_per_image, counts, &tr);
+        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+
+int rf_detect_tiled_face_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                      float threshold, const rf_tile_spec *tile_spec, rf_face *out, int cap_per_image, int *counts,
+                                      int *src_tile, const rf_face_batch_spec *fb_spec, void *d_tensor, void *tensor, double *matrices,
+                                      int *offsets, const rf_face_gate *gate, rf_face_quality *quality) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        rf::TileRequest rq;
+        tile_request(h, tile_spec, src_tile, &rq);
+        rf::FaceBatchRequest fb;
+        face_batch_request(fb_spec, h->eng->default_max_faces(), d_tensor, tensor, matrices, offsets, &fb);
+        if (gate || quality) face_gate_request(gate, quality, &fb);
+        rq.fb = &fb;
+        bool tr = false, over = false;
+        h->eng->detect_tiled((const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, out, cap_per_image, counts, &tr, rq, &over);
+        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        if (over) { h->error = kFaceOverflow; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+
 int rf_num_slots(rf_handle h) { return h ? h->eng->num_slots() : RF_ERR_INVALID_ARG; }
 
 int rf_enqueue_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps,

@@ -207,7 +207,8 @@ public:
         for (void *p : dev_allocs_) (void)hipFree(p);
         for (void *p : host_allocs_) (void)hipHostFree(p);
         if (align_stream_) { (void)hipStreamSynchronize(align_stream_); (void)hipStreamDestroy(align_stream_); }
-        for (DeviceScratch *b : {&align_crops_, &align_mats_, &align_tab_, &fb_state_, &fq_records_, &fq_packed_, &fq_offsets_}) b->release();
+        for (DeviceScratch *b : {&align_crops_, &align_mats_, &align_tab_, &fb_state_, &fq_records_, &fq_packed_, &fq_offsets_, &tile_cand_, &tile_count_, &tile_out_,
+                                 &tile_outcount_, &tile_tab_, &tile_frames_}) b->release();
         kind_.arena->release();
         for (auto &e : prof_ev_) (void)hipEventDestroy(e);
     }
@@ -463,6 +464,69 @@ public:
         else face_batch_copy_out(rq, d_tensor, d_mats, counts, n, std::min(rq.spec.max_faces, opt_.max_detections), overflow);
     }
 
+    // The face-batch launches over n images of ONE table of faces, in stream order: (gated: the quality kernel,) the scan that packs
+    // the counts and advances the call's running base, the tensor kernel.  Shared by the standalone call, the launches behind a
+    // detection launch and the fused tiled call: they differ only in where frames, faces, counts and scales live.
+    struct FaceSeq {
+        const FrameDesc *frames; const uint8_t *faces; int face_stride, faces_per_image;
+        const int *counts; const float *scale;           // scale: nullptr = 1
+        int n, image0;                                   // images of this launch; index of its first image in the call (records / packed / gated offsets)
+        bool first;                                      // the call's first launch
+        int *offsets;                                    // [n + 1] device ints the scan writes
+        hipEvent_t wait_before_scan = nullptr;           // the scan of the call's previous launch, on another stream
+        hipEvent_t record_after_scan = nullptr;
+    };
+    void launch_face_seq(hipStream_t st, const FaceBatchRequest &rq, const FaceSeq &q, uint8_t *d_tensor, double *d_mats) {
+        const FaceBatchSpec &spec = rq.spec;
+        const int *packed = nullptr;
+        if (rq.gated) {
+            // quality kernel first: it needs nothing of the call's earlier launches and runs while their scans finish
+            const size_t slot0 = (size_t)q.image0 * spec.max_faces;
+            FaceQualityParams qp;
+            qp.frames = q.frames;
+            qp.faces = q.faces;
+            qp.face_stride = q.face_stride; qp.faces_per_image = q.faces_per_image;
+            qp.counts = q.counts;
+            qp.scale = q.scale;
+            qp.n = q.n; qp.max_faces = spec.max_faces; qp.crop = spec.crop;
+            qp.aa_max = spec.antialias ? spec.aa_max : 0;
+            qp.has_gate = rq.has_gate ? 1 : 0; qp.gate = rq.gate;
+            qp.records = (rf_face_quality *)fq_records_.ptr + slot0;
+            launch_face_quality(st, qp);
+            if (q.wait_before_scan) RF_HIP(hipStreamWaitEvent(st, q.wait_before_scan, 0));
+            FaceGateScanParams gp;
+            gp.frames = q.frames; gp.counts = q.counts;
+            gp.n = q.n; gp.faces_per_image = q.faces_per_image; gp.max_faces = spec.max_faces;
+            gp.records = qp.records;
+            gp.running = (int *)fb_state_.ptr; gp.first = q.first;
+            gp.offsets = q.offsets;
+            gp.packed = (int *)fq_packed_.ptr + slot0;
+            launch_face_gate_scan(st, gp);
+            packed = gp.packed;
+        } else {
+            if (q.wait_before_scan) RF_HIP(hipStreamWaitEvent(st, q.wait_before_scan, 0));
+            FaceScanParams sp;
+            sp.frames = q.frames;
+            sp.counts = q.counts;
+            sp.n = q.n; sp.faces_per_image = q.faces_per_image; sp.max_faces = spec.max_faces;
+            sp.running = (int *)fb_state_.ptr; sp.first = q.first;
+            sp.offsets = q.offsets;
+            launch_face_scan(st, sp);
+        }
+        if (q.record_after_scan) RF_HIP(hipEventRecord(q.record_after_scan, st));
+        if (!d_tensor && !d_mats) return;
+        FaceBatchParams bp;
+        bp.frames = q.frames;
+        bp.faces = q.faces;
+        bp.face_stride = q.face_stride; bp.faces_per_image = q.faces_per_image;
+        bp.scale = q.scale;
+        bp.offsets = q.offsets; bp.packed = packed;
+        bp.n = q.n; bp.max_faces = spec.max_faces;
+        bp.spec = spec;
+        bp.tensor = d_tensor; bp.mats = d_mats;
+        launch_face_batch(st, bp);
+    }
+
     void face_batch(const void *const *frames, const int *rows, const int *cols, const int *steps, int n, const rf_face *faces,
                     int cap_per_image, const int *counts, const float *coord_scale, const FaceBatchRequest &rq, bool *overflow) override {
         check_face_batch_request(rq);
@@ -507,62 +571,246 @@ public:
             if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
             RF_HIP(hipMemcpyAsync(d_tab, align_host_.data(), total, hipMemcpyHostToDevice, align_stream_));
             for (int base = 0; base < n; base += per) {          // one stream: the scans and the tensor launches run in order
-                if (rq.gated) {
-                    FaceQualityParams qp;
-                    qp.frames = (const FrameDesc *)d_tab + base;
-                    qp.faces = d_tab + o_face + (size_t)base * fpi * sizeof(rf_face);
-                    qp.face_stride = (int)sizeof(rf_face); qp.faces_per_image = fpi;
-                    qp.counts = (const int *)(d_tab + o_cnt) + base;
-                    qp.scale = (const float *)(d_tab + o_sc) + base;
-                    qp.n = std::min(per, n - base); qp.max_faces = rq.spec.max_faces; qp.crop = rq.spec.crop;
-                    qp.aa_max = rq.spec.antialias ? rq.spec.aa_max : 0;
-                    qp.has_gate = rq.has_gate ? 1 : 0; qp.gate = rq.gate;
-                    qp.records = (rf_face_quality *)fq_records_.ptr + (size_t)base * rq.spec.max_faces;
-                    launch_face_quality(align_stream_, qp);
-                    FaceGateScanParams gp;
-                    gp.frames = qp.frames; gp.counts = qp.counts;
-                    gp.n = qp.n; gp.faces_per_image = fpi; gp.max_faces = rq.spec.max_faces;
-                    gp.records = qp.records;
-                    gp.running = (int *)fb_state_.ptr; gp.first = base == 0;
-                    gp.offsets = (int *)fq_offsets_.ptr + base;
-                    gp.packed = (int *)fq_packed_.ptr + (size_t)base * rq.spec.max_faces;
-                    launch_face_gate_scan(align_stream_, gp);
-                    if (d_tensor || d_mats) {
-                        FaceBatchParams bp;
-                        bp.frames = qp.frames; bp.faces = qp.faces;
-                        bp.face_stride = qp.face_stride; bp.faces_per_image = fpi;
-                        bp.scale = qp.scale;
-                        bp.offsets = gp.offsets; bp.packed = gp.packed;
-                        bp.n = qp.n; bp.max_faces = rq.spec.max_faces;
-                        bp.spec = rq.spec;
-                        bp.tensor = d_tensor; bp.mats = d_mats;
-                        launch_face_batch(align_stream_, bp);
-                    }
-                    continue;
-                }
-                FaceScanParams sp;
-                sp.frames = (const FrameDesc *)d_tab + base;
-                sp.counts = (const int *)(d_tab + o_cnt) + base;
-                sp.n = std::min(per, n - base); sp.faces_per_image = fpi; sp.max_faces = rq.spec.max_faces;
-                sp.running = (int *)fb_state_.ptr; sp.first = base == 0;
-                sp.offsets = (int *)(d_tab + o_off);
-                launch_face_scan(align_stream_, sp);
-                FaceBatchParams bp;
-                bp.frames = sp.frames;
-                bp.faces = d_tab + o_face + (size_t)base * fpi * sizeof(rf_face);
-                bp.face_stride = (int)sizeof(rf_face); bp.faces_per_image = fpi;
-                bp.scale = (const float *)(d_tab + o_sc) + base;
-                bp.offsets = sp.offsets;
-                bp.n = sp.n; bp.max_faces = rq.spec.max_faces;
-                bp.spec = rq.spec;
-                bp.tensor = d_tensor; bp.mats = d_mats;
-                launch_face_batch(align_stream_, bp);
+                FaceSeq q;
+                q.frames = (const FrameDesc *)d_tab + base;
+                q.faces = d_tab + o_face + (size_t)base * fpi * sizeof(rf_face);
+                q.face_stride = (int)sizeof(rf_face); q.faces_per_image = fpi;
+                q.counts = (const int *)(d_tab + o_cnt) + base;
+                q.scale = (const float *)(d_tab + o_sc) + base;
+                q.n = std::min(per, n - base); q.image0 = base;
+                q.first = base == 0;
+                q.offsets = rq.gated ? (int *)fq_offsets_.ptr + base : (int *)(d_tab + o_off);
+                launch_face_seq(align_stream_, rq, q, d_tensor, d_mats);
             }
             RF_HIP(hipGetLastError());
             RF_HIP(hipStreamSynchronize(align_stream_));
         }
         if (rq.gated) face_gated_copy_out(rq, d_tensor, d_mats, cnt, n, rq.spec.max_faces, overflow);
         else face_batch_copy_out(rq, d_tensor, d_mats, cnt, n, rq.spec.max_faces, overflow);
+    }
+
+    // -------------------------------------------------------------------------------- tiled detection
+    // The plans of a call's frames as one pass table (frames in call order, passes in plan order); first[i]: frame i's first pass.
+    // A NULL / empty frame is one pass that gathers nothing (frame = -1).  `have_ptrs` false: tile_merge(), which has no pixels.
+    void tile_build_passes(const TileSpec &sp, const uint8_t *const *frames, bool have_ptrs, const int *rows, const int *cols, int n,
+                           std::vector<TileEntry> *entries, std::vector<int> *first) const {
+        entries->clear();
+        first->assign((size_t)n + 1, 0);
+        for (int i = 0; i < n; i++) {
+            (*first)[i] = (int)entries->size();
+            const bool empty = (have_ptrs && !frames[i]) || rows[i] <= 0 || cols[i] <= 0;
+            if (empty) {
+                TileEntry e;
+                memset(&e, 0, sizeof(e));
+                e.frame = -1; e.scale = 1.f;
+                entries->push_back(e);
+                continue;
+            }
+            if (rows[i] > 4096 * 3072 / cols[i]) throw ArgError("frame larger than 4096x3072 (RetinaFace.cpp:325)");
+            int nx = 0, ny = 0, full = 0;
+            const int passes = tile_plan_shape(sp, rows[i], cols[i], net_h_, net_w_, &nx, &ny, &full);
+            if (passes < 0) throw ArgError("tiled detection: a frame's plan has more than 1024 passes");
+            for (int t = 0; t < passes; t++) entries->push_back(tile_plan_entry(rows[i], cols[i], net_h_, net_w_, nx, ny, t, i));
+        }
+        (*first)[n] = (int)entries->size();
+    }
+
+    // device blocks of a tiled call, sized once and reused: per frame kTileMergeCap candidate records and their counter, max_faces
+    // merged records, kept / candidate counts.  The counters are zero between calls (the merge re-arms them as the NMS kernel re-arms
+    // the heads'); a new block, or a call that ended in an error, is zeroed here.
+    void tile_open(int n, const TileSpec &sp) {
+        const size_t nf = (size_t)std::max(n, 1);
+        tile_cand_.reserve(nf * kTileMergeCap * sizeof(Candidate));
+        const uint8_t *before = tile_count_.ptr;
+        tile_count_.reserve(nf * sizeof(int));
+        if (tile_count_.ptr != before) tile_dirty_ = true;
+        tile_out_.reserve(nf * sp.max_faces * sizeof(Candidate));
+        tile_outcount_.reserve(2 * nf * sizeof(int));
+        if (tile_dirty_) {
+            RF_HIP(hipDeviceSynchronize());
+            RF_HIP(hipMemset(tile_count_.ptr, 0, tile_count_.cap));
+            RF_HIP(hipDeviceSynchronize());
+            tile_dirty_ = false;
+        }
+    }
+
+    void tile_launch_gather(hipStream_t st, const uint8_t *faces, int face_stride, const int *counts, const TileEntry *table, int passes,
+                            const TileSpec &sp) {
+        TileGatherParams gp;
+        gp.faces = faces; gp.face_stride = face_stride; gp.faces_per_pass = opt_.max_detections;
+        gp.counts = counts; gp.table = table;
+        gp.n = passes; gp.edge = sp.edge; gp.rank_stride = opt_.max_detections;
+        gp.cand = (Candidate *)tile_cand_.ptr; gp.cand_count = (int *)tile_count_.ptr; gp.cap = kTileMergeCap;
+        launch_tile_gather(st, gp);
+    }
+
+    // the merge: the detector's own NMS kernel over the gathered candidates, one workgroup per frame (`anchor` holds g)
+    void tile_launch_merge(hipStream_t st, int n, const TileSpec &sp, const RunParams *d_params) {
+        NmsParams np;
+        np.cand = (const Candidate *)tile_cand_.ptr; np.cand_count = (int *)tile_count_.ptr; np.cap = kTileMergeCap;
+        np.params = d_params;
+        np.out = (Candidate *)tile_out_.ptr; np.out_count = (int *)tile_outcount_.ptr; np.out_cand_count = (int *)tile_outcount_.ptr + n;
+        np.max_det = sp.max_faces;
+        np.n = n;
+        launch_nms(st, np);
+    }
+
+    // results of a finished tiled call (the host has waited for its last launch): true counts, the first min(count, max_faces,
+    // cap_per_image) faces of each frame, the pass each came from
+    void tile_copy_out(int n, const TileRequest &rq, rf_face *out, int cap_per_image, int *counts, bool *truncated) {
+        if (n == 0) return;
+        std::vector<int> hc(2 * (size_t)n);
+        RF_HIP(hipMemcpy(hc.data(), tile_outcount_.ptr, hc.size() * sizeof(int), hipMemcpyDeviceToHost));
+        const int mf = rq.spec.max_faces;
+        const size_t block = (size_t)n * mf;
+        size_t used = 0;
+        for (int i = 0; i < n; i++) {
+            counts[i] = hc[i];
+            if (hc[n + i] > kTileMergeCap || hc[i] > mf) *truncated = true;
+            if (out && std::min(hc[i], mf) > cap_per_image) *truncated = true;
+            used += (size_t)std::min(std::min(hc[i], mf), out ? cap_per_image : 0);
+        }
+        if (!used) return;
+        const Candidate *d_out = (const Candidate *)tile_out_.ptr;
+        const bool whole = block * sizeof(Candidate) <= (1u << 20) || 2 * used >= block;
+        tile_host_.resize(block);
+        if (whole) RF_HIP(hipMemcpy(tile_host_.data(), d_out, block * sizeof(Candidate), hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; i++) {
+            const int k = std::min(std::min(hc[i], mf), cap_per_image);
+            if (k <= 0) continue;
+            Candidate *src = tile_host_.data() + (size_t)i * mf;
+            if (!whole) RF_HIP(hipMemcpy(src, d_out + (size_t)i * mf, (size_t)k * sizeof(Candidate), hipMemcpyDeviceToHost));
+            for (int j = 0; j < k; j++) {
+                memcpy(&out[(size_t)i * cap_per_image + j], &src[j], sizeof(rf_face));
+                if (rq.src_tile) rq.src_tile[(size_t)i * cap_per_image + j] = src[j].anchor / opt_.max_detections;
+            }
+        }
+    }
+
+    void detect_tiled(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,
+                      float threshold, rf_face *out, int cap_per_image, int *counts, bool *truncated, const TileRequest &rq,
+                      bool *overflow) override {
+        *truncated = false;
+        *overflow = false;
+        if (n < 0 || (n > 0 && (!frames || !rows || !cols || !counts))) throw ArgError("null argument");
+        if (cap_per_image < 0 || (cap_per_image > 0 && !out)) throw ArgError("out is null");
+        if (rq.spec.max_faces < 1 || rq.spec.max_faces > kTileMaxFaces) throw ArgError("max_faces must be in [1, 4096]");
+        if (rq.fb) {
+            check_face_batch_request(*rq.fb);
+            if ((long)n * rq.fb->spec.max_faces > (1L << 24)) throw ArgError("n x max_faces: more than 2^24 faces in one call");
+        }
+        std::vector<int> st((size_t)std::max(n, 1));
+        for (int i = 0; i < n; i++) {
+            st[i] = steps ? steps[i] : cols[i] * 3;
+            check_frame(frames[i], rows[i], cols[i], st[i]);
+        }
+        std::vector<TileEntry> entries;
+        std::vector<int> first;
+        tile_build_passes(rq.spec, frames, true, rows, cols, n, &entries, &first);
+        if (n == 0) { if (rq.fb && rq.fb->offsets) rq.fb->offsets[0] = 0; return; }
+        DeviceGuard guard(device_);
+        // host frames are uploaded once, densely; the passes are views of that copy
+        std::vector<const uint8_t *> base((size_t)n, nullptr);
+        if (!on_device) {
+            size_t bytes = 0;
+            std::vector<size_t> off((size_t)n, 0);
+            for (int i = 0; i < n; i++)
+                if (entries[first[i]].frame >= 0) { off[i] = bytes; bytes += align256((size_t)rows[i] * cols[i] * 3); }
+            uint8_t *d = tile_frames_.reserve(bytes);
+            for (int i = 0; i < n; i++) {
+                if (entries[first[i]].frame < 0) continue;
+                RF_HIP(hipMemcpy2D(d + off[i], (size_t)cols[i] * 3, frames[i], (size_t)st[i], (size_t)cols[i] * 3, (size_t)rows[i], hipMemcpyHostToDevice));
+                base[i] = d + off[i];
+                st[i] = cols[i] * 3;
+            }
+        } else {
+            for (int i = 0; i < n; i++) base[i] = entries[first[i]].frame >= 0 ? frames[i] : nullptr;
+        }
+        const int P = (int)entries.size();
+        std::vector<const uint8_t *> vp((size_t)P);
+        std::vector<int> vr((size_t)P), vc((size_t)P), vs((size_t)P), pass_counts((size_t)P);
+        tile_fd_.assign((size_t)n, FrameDesc{nullptr, 0, 0, 0, 0});
+        for (int i = 0; i < n; i++) {
+            if (base[i]) tile_fd_[i] = FrameDesc{base[i], rows[i], cols[i], st[i], 0};
+            for (int p = first[i]; p < first[i + 1]; p++) {
+                const TileEntry &e = entries[p];
+                if (e.frame < 0) { vp[p] = nullptr; vr[p] = vc[p] = vs[p] = 0; continue; }
+                vp[p] = base[i] + (size_t)e.y0 * st[i] + (size_t)3 * e.x0;
+                vr[p] = e.th; vc[p] = e.tw; vs[p] = st[i];
+            }
+        }
+        // as in detect_align(): a super-batch of earlier enqueues starts now, every later launch carries passes of this call only,
+        // in call order, so image i of a launch is pass tile_.next_pass + i
+        launch_pending();
+        tile_open(n, rq.spec);
+        uint8_t *d_tensor = nullptr;
+        double *d_mats = nullptr;
+        if (rq.fb) {
+            face_batch_open(*rq.fb, &d_tensor, &d_mats);
+            if (rq.fb->gated) face_gate_open(*rq.fb, n);
+            fq_offsets_.reserve(((size_t)n + 1) * sizeof(int));
+            // the frame table of those launches is known now: it is on the device before the call's first launch
+            RF_HIP(hipMemcpy(tile_tab_.reserve((size_t)n * sizeof(FrameDesc)), tile_fd_.data(), (size_t)n * sizeof(FrameDesc), hipMemcpyHostToDevice));
+        }
+        tile_.rq = rq; tile_.entries.swap(entries);
+        tile_.n_frames = n; tile_.next_pass = 0;
+        tile_.lanes_used.clear();
+        tile_.d_tensor = d_tensor; tile_.d_mats = d_mats;
+        tile_.on = true;
+        tile_dirty_ = true;                      // until the call has ended well
+        struct Off { bool &on; ~Off() { on = false; } } off_guard{tile_.on};
+        bool tr = false;
+        detect(vp.data(), vr.data(), vc.data(), vs.data(), P, true, threshold, nullptr, 0, pass_counts.data(), &tr);
+        tile_.on = false;
+        if (tile_.next_pass != P) throw HipError("tiled detection: the merge was not launched");
+        // every launch of the call has been waited for; the merge (and rq.fb's launches) ran in front of the last one's `done`
+        tile_dirty_ = false;
+        *truncated = tr;
+        tile_copy_out(n, rq, out, cap_per_image, counts, truncated);
+        if (rq.fb) {
+            const int limit = std::min(rq.fb->spec.max_faces, rq.spec.max_faces);
+            if (rq.fb->gated) face_gated_copy_out(*rq.fb, d_tensor, d_mats, counts, n, limit, overflow);
+            else face_batch_copy_out(*rq.fb, d_tensor, d_mats, counts, n, limit, overflow);
+        }
+    }
+
+    void tile_merge(const int *rows, const int *cols, int n, const TileRequest &rq, const rf_face *faces, const int *pass_counts,
+                    rf_face *out, int cap_per_image, int *counts, bool *truncated) override {
+        *truncated = false;
+        if (n < 0 || (n > 0 && (!rows || !cols || !counts || !faces || !pass_counts))) throw ArgError("null argument");
+        if (cap_per_image < 0 || (cap_per_image > 0 && !out)) throw ArgError("out is null");
+        if (rq.spec.max_faces < 1 || rq.spec.max_faces > kTileMaxFaces) throw ArgError("max_faces must be in [1, 4096]");
+        std::vector<TileEntry> entries;
+        std::vector<int> first;
+        tile_build_passes(rq.spec, nullptr, false, rows, cols, n, &entries, &first);
+        if (n == 0) return;
+        const int P = (int)entries.size(), md = opt_.max_detections;
+        for (int p = 0; p < P; p++)
+            if (pass_counts[p] < 0) throw ArgError("negative face count");
+        DeviceGuard guard(device_);
+        // one table: run parameters | pass table | counts | faces (60-byte records, max_detections per pass)
+        const size_t o_tab = 256, o_cnt = o_tab + align256((size_t)P * sizeof(TileEntry)), o_face = o_cnt + align256((size_t)P * sizeof(int)),
+                     total = o_face + (size_t)P * md * sizeof(rf_face);
+        align_host_.assign(total, 0);
+        *(RunParams *)align_host_.data() = RunParams{0.f, nms_threshold_, n, 0};
+        memcpy(align_host_.data() + o_tab, entries.data(), (size_t)P * sizeof(TileEntry));
+        int *cnt = (int *)(align_host_.data() + o_cnt);
+        for (int p = 0; p < P; p++) {
+            cnt[p] = std::min(pass_counts[p], md);
+            if (pass_counts[p] > md) *truncated = true;
+            if (cnt[p]) memcpy(align_host_.data() + o_face + (size_t)p * md * sizeof(rf_face), faces + (size_t)p * md, (size_t)cnt[p] * sizeof(rf_face));
+        }
+        uint8_t *d_tab = align_tab_.reserve(total);
+        tile_open(n, rq.spec);
+        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+        tile_dirty_ = true;
+        RF_HIP(hipMemcpyAsync(d_tab, align_host_.data(), total, hipMemcpyHostToDevice, align_stream_));
+        tile_launch_gather(align_stream_, d_tab + o_face, (int)sizeof(rf_face), (const int *)(d_tab + o_cnt), (const TileEntry *)(d_tab + o_tab), P, rq.spec);
+        tile_launch_merge(align_stream_, n, rq.spec, (const RunParams *)d_tab);
+        RF_HIP(hipGetLastError());
+        RF_HIP(hipStreamSynchronize(align_stream_));
+        tile_dirty_ = false;
+        tile_copy_out(n, rq, out, cap_per_image, counts, truncated);
     }
 
     void host_register(const void *ptr, size_t bytes) override {
@@ -767,6 +1015,8 @@ private:
         float *h_align_scale = nullptr;       // detect_align(): pinned, per image of the launch its frame_scale (allocated on first use)
         int *d_face_off = nullptr;            // detect_face_batch(): packed offsets of the launch's images, written by its scan kernel (first use)
         hipEvent_t face_scan_done = nullptr;  // ... recorded behind that scan: the call's next launch (another lane) waits for it on the device
+        TileEntry *h_tile_tab = nullptr;      // detect_tiled(): pinned, per image of the launch the pass it is (allocated on first use)
+        hipEvent_t tile_done = nullptr;       // ... recorded behind the launch's gather: the call's merge (another lane) waits for it on the device
         bool busy = false;                    // a launched super-batch whose results have not been harvested yet
         int n_images = 0;                     // images of the super-batch being assembled / in flight on this lane
         float threshold = 0.f;
@@ -808,6 +1058,7 @@ private:
         if (l.done) (void)hipEventDestroy(l.done);
         if (l.copy2_done) (void)hipEventDestroy(l.copy2_done);
         if (l.face_scan_done) (void)hipEventDestroy(l.face_scan_done);
+        if (l.tile_done) (void)hipEventDestroy(l.tile_done);
         if (l.copy2) { (void)hipStreamSynchronize(l.copy2); (void)hipStreamDestroy(l.copy2); }
         if (l.d_stage) (void)hipFree(l.d_stage);
         if (l.h_stage) (void)hipHostFree(l.h_stage);
@@ -1092,6 +1343,7 @@ private:
         if (eager_timed) RF_HIP(hipEventRecord(s.time_ev[3], s.stream));
         if (align_.on) launch_lane_align(s, n);      // ordinary launches behind the graph, before `done`: nothing waits in between
         if (fb_.on) launch_lane_face_batch(s, n);
+        if (tile_.on) launch_lane_tile(s, n);
         RF_HIP(hipEventRecord(s.done, s.stream));
         trace_.add(4, tt);
         s.busy = true;
@@ -1145,71 +1397,76 @@ private:
             s.d_face_off = (int *)p;
             RF_HIP(hipEventCreateWithFlags(&s.face_scan_done, hipEventDisableTiming));
         }
-        const FaceBatchSpec &spec = fb_.rq.spec;
-        if (fb_.rq.gated) {
-            // quality kernel first: it needs nothing of the call's earlier launches and runs while their scans finish
-            const size_t slot0 = (size_t)fb_.next_image * spec.max_faces;
-            FaceQualityParams qp;
-            qp.frames = s.d_frames;
-            qp.faces = (const uint8_t *)s.h_out;
-            qp.face_stride = (int)sizeof(Candidate); qp.faces_per_image = opt_.max_detections;
-            qp.counts = s.h_counts;
-            qp.scale = s.h_align_scale;
-            qp.n = n; qp.max_faces = spec.max_faces; qp.crop = spec.crop;
-            qp.aa_max = spec.antialias ? spec.aa_max : 0;
-            qp.has_gate = fb_.rq.has_gate ? 1 : 0; qp.gate = fb_.rq.gate;
-            qp.records = (rf_face_quality *)fq_records_.ptr + slot0;
-            launch_face_quality(s.stream, qp);
-            if (fb_.prev_scan && fb_.prev_scan != s.face_scan_done) RF_HIP(hipStreamWaitEvent(s.stream, fb_.prev_scan, 0));
-            FaceGateScanParams gp;
-            gp.frames = s.d_frames; gp.counts = s.h_counts;
-            gp.n = n; gp.faces_per_image = opt_.max_detections; gp.max_faces = spec.max_faces;
-            gp.records = qp.records;
-            gp.running = (int *)fb_state_.ptr; gp.first = fb_.first;
-            gp.offsets = (int *)fq_offsets_.ptr + fb_.next_image;
-            gp.packed = (int *)fq_packed_.ptr + slot0;
-            launch_face_gate_scan(s.stream, gp);
-            RF_HIP(hipEventRecord(s.face_scan_done, s.stream));
-            fb_.prev_scan = s.face_scan_done;
-            fb_.first = false;
-            fb_.next_image += n;
-            if (fb_.d_tensor || fb_.d_mats) {
-                FaceBatchParams bp;
-                bp.frames = s.d_frames;
-                bp.faces = (const uint8_t *)s.h_out;
-                bp.face_stride = (int)sizeof(Candidate); bp.faces_per_image = opt_.max_detections;
-                bp.scale = s.h_align_scale;
-                bp.offsets = gp.offsets; bp.packed = gp.packed;
-                bp.n = n; bp.max_faces = spec.max_faces;
-                bp.spec = spec;
-                bp.tensor = fb_.d_tensor; bp.mats = fb_.d_mats;
-                launch_face_batch(s.stream, bp);
-            }
-            RF_HIP(hipGetLastError());
-            return;
-        }
-        if (fb_.prev_scan && fb_.prev_scan != s.face_scan_done) RF_HIP(hipStreamWaitEvent(s.stream, fb_.prev_scan, 0));
-        FaceScanParams sp;
-        sp.frames = s.d_frames;
-        sp.counts = s.h_counts;
-        sp.n = n; sp.faces_per_image = opt_.max_detections; sp.max_faces = spec.max_faces;
-        sp.running = (int *)fb_state_.ptr; sp.first = fb_.first;
-        sp.offsets = s.d_face_off;
-        launch_face_scan(s.stream, sp);
-        RF_HIP(hipEventRecord(s.face_scan_done, s.stream));
+        FaceSeq q;
+        q.frames = s.d_frames;
+        q.faces = (const uint8_t *)s.h_out;
+        q.face_stride = (int)sizeof(Candidate); q.faces_per_image = opt_.max_detections;
+        q.counts = s.h_counts;
+        q.scale = s.h_align_scale;
+        q.n = n; q.image0 = fb_.next_image;
+        q.first = fb_.first;
+        q.offsets = fb_.rq.gated ? (int *)fq_offsets_.ptr + fb_.next_image : s.d_face_off;
+        q.wait_before_scan = (fb_.prev_scan && fb_.prev_scan != s.face_scan_done) ? fb_.prev_scan : nullptr;
+        q.record_after_scan = s.face_scan_done;
+        launch_face_seq(s.stream, fb_.rq, q, fb_.d_tensor, fb_.d_mats);
         fb_.prev_scan = s.face_scan_done;
         fb_.first = false;
-        FaceBatchParams bp;
-        bp.frames = s.d_frames;
-        bp.faces = (const uint8_t *)s.h_out;
-        bp.face_stride = (int)sizeof(Candidate); bp.faces_per_image = opt_.max_detections;
-        bp.scale = s.h_align_scale;
-        bp.offsets = s.d_face_off;
-        bp.n = n; bp.max_faces = spec.max_faces;
-        bp.spec = spec;
-        bp.tensor = fb_.d_tensor; bp.mats = fb_.d_mats;
-        launch_face_batch(s.stream, bp);
+        fb_.next_image += n;
         RF_HIP(hipGetLastError());
+    }
+
+    // The tiled-detection launches of a super-batch of detect_tiled(): the gather reads the launch's faces and counts from the
+    // pinned result block the NMS kernel of the same stream has just written, and what each image of the launch is from a pinned
+    // per-lane pass table.  Behind the call's LAST launch this stream waits (on the device: hipStreamWaitEvent) for the gathers of
+    // the call's other lanes, then runs the merge and, for the fused call, the face-batch launches over the merged faces.  The
+    // lane's `done` event follows, so the host's ordinary wait for the last launch covers all of it.  No host wait anywhere.
+    void launch_lane_tile(Lane &s, int n) {
+        if (!s.h_tile_tab) {
+            void *p = nullptr;
+            RF_HIP(hipHostMalloc(&p, std::max<size_t>((size_t)cap_images_ * sizeof(TileEntry), 256), hipHostMallocDefault));
+            s.host_allocs.push_back(p);
+            s.h_tile_tab = (TileEntry *)p;
+            RF_HIP(hipEventCreateWithFlags(&s.tile_done, hipEventDisableTiming));
+        }
+        const int total = (int)tile_.entries.size();
+        if (n > cap_images_ || tile_.next_pass + n > total) throw HipError("tiled detection: a launch carries images of another call");
+        for (int i = 0; i < n; i++) s.h_tile_tab[i] = tile_.entries[tile_.next_pass + i];
+        const TileSpec &sp = tile_.rq.spec;
+        tile_launch_gather(s.stream, (const uint8_t *)s.h_out, (int)sizeof(Candidate), s.h_counts, s.h_tile_tab, n, sp);
+        RF_HIP(hipGetLastError());
+        tile_.next_pass += n;
+        const int me = (int)(&s - lanes_.data());
+        if (tile_.next_pass < total) {
+            RF_HIP(hipEventRecord(s.tile_done, s.stream));
+            if (std::find(tile_.lanes_used.begin(), tile_.lanes_used.end(), me) == tile_.lanes_used.end()) tile_.lanes_used.push_back(me);
+            return;
+        }
+        for (int l : tile_.lanes_used)
+            if (l != me && l < (int)lanes_.size() && lanes_[l].tile_done) RF_HIP(hipStreamWaitEvent(s.stream, lanes_[l].tile_done, 0));
+        const int nf = tile_.n_frames;
+        tile_launch_merge(s.stream, nf, sp, s.d_params);
+        if (tile_.rq.fb) launch_tiled_face_batch(s.stream, nf);
+        RF_HIP(hipGetLastError());
+    }
+
+    // the face-batch launches of the fused tiled call: face_batch()'s launches over the merged faces and counts in device memory
+    // (Candidate records, max_faces per frame, coordinate scale 1), on the stream that has just run the merge
+    void launch_tiled_face_batch(hipStream_t st, int n) {
+        const FaceBatchRequest &rq = *tile_.rq.fb;
+        if (!(tile_.d_tensor || tile_.d_mats || rq.gated)) return;
+        const int fpi = tile_.rq.spec.max_faces;
+        for (int base = 0; base < n; base += kAlignImagesPerLaunch) {
+            FaceSeq q;
+            q.frames = (const FrameDesc *)tile_tab_.ptr + base;      // uploaded by detect_tiled() before the call's first launch
+            q.faces = tile_out_.ptr + (size_t)base * fpi * sizeof(Candidate);
+            q.face_stride = (int)sizeof(Candidate); q.faces_per_image = fpi;
+            q.counts = (const int *)tile_outcount_.ptr + base;
+            q.scale = nullptr;
+            q.n = std::min(kAlignImagesPerLaunch, n - base); q.image0 = base;
+            q.first = base == 0;
+            q.offsets = (int *)fq_offsets_.ptr + base;
+            launch_face_seq(st, rq, q, tile_.d_tensor, tile_.d_mats);
+        }
     }
 
     // results of an alignment call to the caller's host buffers: per image the slots that hold faces (the others are unspecified)
@@ -1462,6 +1719,14 @@ private:
              int next_image = 0; } fb_;
     // gated face batches: quality records and packed indices per face slot of the call, the call's packed offsets
     DeviceScratch fq_records_, fq_packed_, fq_offsets_;
+    // tiled detection: per frame the gathered candidates and their counter, the merged records and counts, the frame table of the
+    // fused face batch, the device copy of host frames; the request detect_tiled() has open and its pass table
+    DeviceScratch tile_cand_, tile_count_, tile_out_, tile_outcount_, tile_tab_, tile_frames_;
+    bool tile_dirty_ = true;                  // the counters are not known to be zero (new block, or a call that ended in an error)
+    std::vector<Candidate> tile_host_;
+    std::vector<FrameDesc> tile_fd_;
+    struct { bool on = false; TileRequest rq; std::vector<TileEntry> entries; int n_frames = 0, next_pass = 0; std::vector<int> lanes_used;
+             uint8_t *d_tensor = nullptr; double *d_mats = nullptr; } tile_;
 
     int last_n_ = 0;
     std::vector<int> last_cand_counts_;

@@ -94,6 +94,14 @@ struct FaceBatchRequest {
     rf_face_quality *quality = nullptr;         // host, n * spec.max_faces records, or nullptr
 };
 
+// A tiled-detection call (tile.h; rf_detect_tiled_batch* / rf_tile_merge_device / rf_detect_tiled_face_batch_device): the validated
+// spec, where the pass of each merged face goes, and the face batch that follows the merge on the device (nullptr = none)
+struct TileRequest {
+    TileSpec spec;
+    int *src_tile = nullptr;                    // host, indexed like out, or nullptr
+    const FaceBatchRequest *fb = nullptr;
+};
+
 class Engine {
 public:
     // opt.devices.size() > 1 gives the image-sharding multi-device engine (multi.cpp), otherwise one single-device engine
@@ -131,6 +139,19 @@ public:
     virtual void face_batch(const void *const *, const int *, const int *, const int *, int, const rf_face *, int, const int *,
                             const float *, const FaceBatchRequest &, bool * /*overflow*/) {
         throw Unsupported("face batches are not available on a multi-device handle");
+    }
+    // Tiled detection: the frames are expanded into passes (ROI views + the shrunk full-frame pass) that go through detect()'s
+    // ordinary launches; a gather launch behind each of them and one merge launch behind the last (ordered by events on the
+    // device, no host wait) leave the merged faces in device memory, where rq.fb's face-batch launches read them.  *truncated: a
+    // pass or the merge hit a cap; *overflow: rq.fb's capacity.  Single-device engines only.
+    virtual void detect_tiled(const uint8_t *const *, const int *, const int *, const int *, int, bool, float, rf_face *, int, int *,
+                              bool *, const TileRequest &, bool * /*overflow*/) {
+        throw Unsupported("tiled detection is not available on a multi-device handle");
+    }
+    // edge rule, mapping and merge of per-pass faces the caller supplies (faces[(first_pass[i] + t) * max_detections + k])
+    virtual void tile_merge(const int *, const int *, int, const TileRequest &, const rf_face *, const int *, rf_face *, int, int *,
+                            bool *) {
+        throw Unsupported("tiled detection is not available on a multi-device handle");
     }
     int default_max_faces() const { return opt_.max_detections; }
     // asynchronous: frames on host (staged through pinned memory before the call returns, unless the caller registered

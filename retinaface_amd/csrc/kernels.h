@@ -10,6 +10,7 @@
 #include "align.h"
 #include "face_batch.h"
 #include "face_quality.h"
+#include "tile.h"
 
 namespace rf {
 
@@ -255,6 +256,21 @@ struct FaceGateScanParams {
 };
 void launch_face_gate_scan(hipStream_t s, const FaceGateScanParams &p);
 int face_quality_ring_rows(int crop);                // luma rows the quality kernel holds in LDS (exposed for tests and DESIGN.md)
+
+// ---- K_i: tiled detection (tile.h) -- the gather behind each detection launch of a tiled call: one workgroup per pass (image of the
+//      launch) applies the edge rule and the mapping to the faces the NMS kernel kept and appends them, as Candidate records whose
+//      `anchor` is the tie-break index g = t * rank_stride + k, to the candidate array of the pass's frame (an atomic counter per
+//      frame; the append order does not matter: the merge sorts on a total order).  The merge itself is launch_nms on those arrays.
+struct TileGatherParams {
+    const uint8_t *faces;                 // pass p, rank k: 15 floats at faces + (p * faces_per_pass + k) * face_stride
+    int face_stride, faces_per_pass;      // bytes per record (rf_face 60, Candidate 64); records per pass
+    const int *counts;                    // [n] faces of each pass (clamped to faces_per_pass here)
+    const TileEntry *table;               // [n] what each pass is (frame < 0: skipped)
+    int n, edge, rank_stride;             // passes of this launch; the spec's edge; max_detections
+    Candidate *cand; int *cand_count;     // per frame f: cand[f * cap + pos], pos from atomicAdd(cand_count + f); the counter keeps
+    int cap;                              // counting past cap (the merge reports it), records at or beyond cap are not written
+};
+void launch_tile_gather(hipStream_t s, const TileGatherParams &p);
 
 // LDS bytes / tile geometry chosen for a layer (exposed for tests and DESIGN.md tables)
 struct TileInfo { int th, tw; size_t lds_bytes; int blocks_per_image; };

@@ -4478,6 +4478,53 @@ void launch_face_gate_scan(hipStream_t s, const FaceGateScanParams &p) {
     hipLaunchKernelGGL(face_gate_scan_kernel, dim3(1), dim3(kThreads), 0, s, p);
 }
 
+// =============================================================================================
+// K_i: tiled detection (tile.h).  tile_gather_kernel: one workgroup per pass of the launch.  Each thread takes one face of the pass's
+//      result, applies the edge rule and the mapping (tile_map_face, the code rf_tile_map_face runs on the host) and the survivors are
+//      appended to the candidate array of the pass's frame: one atomic add per wavefront (ballot + popcount of the lanes below) on the
+//      frame's counter in device memory.  Passes of one frame arrive from different launches on different streams in any order; the
+//      merge (nms_kernel on these arrays) sorts on the total order (score, g), so the append order never shows.
+// =============================================================================================
+__global__ __launch_bounds__(kThreads) void tile_gather_kernel(TileGatherParams a) {
+    const int p = blockIdx.x;
+    const TileEntry e = a.table[p];
+    if (e.frame < 0) return;
+    int cnt = a.counts[p];
+    cnt = cnt < 0 ? 0 : cnt < a.faces_per_pass ? cnt : a.faces_per_pass;
+    const int lane = (int)threadIdx.x & 63;
+    Candidate *dst = a.cand + (size_t)e.frame * a.cap;
+    for (int k0 = 0; k0 < cnt; k0 += kThreads) {
+        const int k = k0 + (int)threadIdx.x;
+        float f[15];
+        bool keep = false;
+        if (k < cnt) {
+            const float *src = (const float *)(a.faces + ((size_t)p * a.faces_per_pass + k) * a.face_stride);
+            for (int i = 0; i < 15; i++) f[i] = src[i];
+            keep = tile_map_face(e, a.edge, f, f);
+        }
+        const unsigned long long mask = __ballot(keep);
+        if (!mask) continue;                                     // wave-uniform
+        const int leader = __ffsll((long long)mask) - 1;
+        int base = 0;
+        if (lane == leader) base = atomicAdd(a.cand_count + e.frame, __popcll(mask));
+        base = __shfl(base, leader);
+        if (!keep) continue;
+        const int pos = base + __popcll(mask & ((1ull << lane) - 1ull));
+        if (pos >= a.cap) continue;                              // the counter keeps the true number: the merge reports the overflow
+        Candidate c;
+        c.score = f[0];
+        c.x1 = f[1]; c.y1 = f[2]; c.x2 = f[3]; c.y2 = f[4];
+        for (int i = 0; i < 5; i++) { c.px[i] = f[5 + i]; c.py[i] = f[10 + i]; }
+        c.anchor = e.t * a.rank_stride + k;
+        dst[pos] = c;
+    }
+}
+
+void launch_tile_gather(hipStream_t s, const TileGatherParams &p) {
+    if (p.n <= 0) return;
+    hipLaunchKernelGGL(tile_gather_kernel, dim3(p.n), dim3(kThreads), 0, s, p);
+}
+
 #ifdef RF_KERNEL_TRACE
 extern "C" int rf_trace_select(int kernel_id, unsigned grid) {
     static unsigned long long zeros[kTraceBlocks * kTraceSlots];

@@ -14,7 +14,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import rf_face, rf_face_batch_spec, rf_face_gate, rf_face_quality, rf_options
+from ._lib import rf_face, rf_face_batch_spec, rf_face_gate, rf_face_quality, rf_options, rf_tile_spec
 
 PRECISION_FP32, PRECISION_FP16, PRECISION_INT8 = 0, 1, 2
 
@@ -163,6 +163,42 @@ def face_gate_eval(gate, q, crop_size: int = 112) -> int:
     if st < 0:
         raise _lib.RFError(st, "rf_face_gate_eval: bad gate or crop_size")
     return int(st)
+
+
+def tile_spec(overlap: int = 0, edge: int = 0, full_frame: bool = True, max_faces: int = 0) -> rf_tile_spec:
+    """An rf_tile_spec: overlap (minimum overlap of neighbouring tiles in pixels; 0 = a quarter of the net's smaller side, negative =
+    none), edge (width of the border band of the edge rule; 0 = 8, negative = 0), full_frame (also run the whole frame shrunk as one
+    more pass), max_faces (merged faces kept per frame; 0 = the engine's max_detections)."""
+    sp = rf_tile_spec()
+    sp.struct_size = C.sizeof(rf_tile_spec)
+    sp.overlap, sp.edge, sp.full_frame, sp.max_faces = int(overlap), int(edge), 1 if full_frame else 2, int(max_faces)
+    return sp
+
+
+def tile_plan(rows: int, cols: int, net_h: int, net_w: int, overlap: int = 0, full_frame: bool = True) -> np.ndarray:
+    """rf_tile_plan (host only, no GPU): the passes of a rows x cols frame at a net_h x net_w net as a (passes, 4) int32 array of
+    x0, y0, tw, th -- the tiles row-major, then the full-frame pass (0, 0, cols, rows) when the plan has one."""
+    lib = _lib.load_library()
+    sp = tile_spec(overlap, 0, full_frame)
+    n = lib.rf_tile_plan(C.byref(sp), int(rows), int(cols), int(net_h), int(net_w), None, 0)
+    if n < 0:
+        raise _lib.RFError(n, "rf_tile_plan: bad spec, frame or net size, or more than 1024 passes")
+    out = np.zeros((n, 4), np.int32)
+    lib.rf_tile_plan(C.byref(sp), int(rows), int(cols), int(net_h), int(net_w), out.ctypes.data_as(C.POINTER(C.c_int)), n)
+    return out
+
+
+def tile_map_face(face, t: int, rows: int, cols: int, net_h: int, net_w: int, overlap: int = 0, edge: int = 0, full_frame: bool = True):
+    """rf_tile_map_face (host only, no GPU): the face (a Detection or 15 floats) of pass t moved into source-frame pixels as 15
+    float32, or None when the edge rule drops it."""
+    lib = _lib.load_library()
+    sp = tile_spec(overlap, edge, full_frame)
+    f = rf_face.from_buffer_copy(_face_rows([face])[0].tobytes())
+    g = rf_face()
+    st = lib.rf_tile_map_face(C.byref(sp), int(rows), int(cols), int(net_h), int(net_w), int(t), C.byref(f), C.byref(g))
+    if st < 0:
+        raise _lib.RFError(st, "rf_tile_map_face: bad spec, frame, net size or pass index")
+    return _faces_to_array(C.pointer(g), 1)[0] if st else None
 
 
 def _faces_to_array(buf, n: int) -> np.ndarray:
@@ -512,6 +548,111 @@ class RetinaFace:
         self.faces_truncated = int(offsets[n]) > capacity
         res = (tensor[:got] if host else None), mats[:got], offsets
         return res + (quality,) if return_quality else res
+
+    # ------------------------------------------------------------------ tiled detection
+    def detect_tiled(self, imgs: Sequence[np.ndarray], threshold: float = 0.5, overlap: int = 0, edge: int = 0, full_frame: bool = True,
+                     max_faces: int = 0, return_tiles: bool = False):
+        """rf_detect_tiled_batch: frames larger than the net are cut into overlapping net-sized tiles, every tile is detected at 1:1
+        (plus the whole frame shrunk, with full_frame), and the faces are merged on the device.  Returns per frame the merged
+        detections in SOURCE-FRAME pixels (anchor_index is -1); with return_tiles also, per frame, the pass each came from (tile_plan
+        gives the passes).  Keywords as tile_spec()."""
+        n = len(imgs)
+        ptrs = (C.c_void_p * max(n, 1))()
+        rows, cols, steps = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
+        keep = []
+        for i, im in enumerate(imgs):
+            if im is None or im.size == 0:
+                ptrs[i], rows[i], cols[i], steps[i] = None, 0, 0, 0
+                continue
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
+            if im.strides[2] != 1 or im.strides[1] != 3:
+                im = np.ascontiguousarray(im)
+            keep.append(im)
+            ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
+        return self._run_tiled(self._lib.rf_detect_tiled_batch, ptrs, rows, cols, steps, n, threshold,
+                               tile_spec(overlap, edge, full_frame, max_faces), return_tiles)
+
+    def detect_tiled_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], threshold: float = 0.5,
+                            steps: Optional[Sequence[int]] = None, overlap: int = 0, edge: int = 0, full_frame: bool = True,
+                            max_faces: int = 0, return_tiles: bool = False):
+        """rf_detect_tiled_batch_device: detect_tiled for frames resident in device memory."""
+        n = len(ptrs)
+        p = (C.c_void_p * max(n, 1))(*ptrs)
+        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
+        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        return self._run_tiled(self._lib.rf_detect_tiled_batch_device, p, r, c, s, n, threshold,
+                               tile_spec(overlap, edge, full_frame, max_faces), return_tiles)
+
+    def _tiled_cap(self, sp) -> int:
+        return sp.max_faces or self.max_detections
+
+    def _collect_tiled(self, out, counts, src, n, cap, return_tiles):
+        rows = _faces_to_array(out, max(n * cap, 1))
+        dets, tiles = [], []
+        for i in range(n):
+            k = min(counts[i], cap)
+            dets.append([Detection(float(r[0]), tuple(float(v) for v in r[1:5]), tuple(float(v) for v in r[5:10]),
+                                   tuple(float(v) for v in r[10:15]), -1) for r in rows[i * cap:i * cap + k]])
+            tiles.append(np.array(src[i * cap:i * cap + k], np.int32))
+        self.tiled_counts = [int(counts[i]) for i in range(n)]
+        return (dets, tiles) if return_tiles else dets
+
+    def _run_tiled(self, fn, ptrs, rows, cols, steps, n, threshold, sp, return_tiles):
+        cap = self._tiled_cap(sp)
+        out = (rf_face * max(n * cap, 1))()
+        counts = (C.c_int * max(n, 1))()
+        src = (C.c_int * max(n * cap, 1))()
+        st = _lib.check(fn(self._h, ptrs, rows, cols, steps, n, float(threshold), C.byref(sp), out, cap, counts, src), self._h)
+        self.truncated = st == _lib.RF_ERR_TRUNCATED
+        return self._collect_tiled(out, counts, src, n, cap, return_tiles)
+
+    def tile_merge(self, rows: Sequence[int], cols: Sequence[int], per_pass_faces, overlap: int = 0, edge: int = 0, full_frame: bool = True,
+                   max_faces: int = 0, cap_per_image: Optional[int] = None, return_tiles: bool = False):
+        """rf_tile_merge_device: edge rule, mapping and merge of per-pass faces the caller supplies -- per_pass_faces[i][t]: the faces
+        of pass t of frame i (a (k, 15) array, rows of 15 floats or Detections, at most max_detections), passes as tile_plan gives
+        them.  No forward pass runs.  Returns as detect_tiled; self.tiled_counts holds the true merged counts."""
+        n = len(rows)
+        sp = tile_spec(overlap, edge, full_frame, max_faces)
+        md = self.max_detections
+        passes = [_face_rows(f) for frame in per_pass_faces for f in frame]
+        flat = np.zeros((max(len(passes), 1), md, 15), np.float32)
+        pc = (C.c_int * max(len(passes), 1))()
+        for p, r in enumerate(passes):
+            flat[p, :min(len(r), md)] = r[:md]
+            pc[p] = len(r)
+        cap = int(cap_per_image) if cap_per_image is not None else self._tiled_cap(sp)
+        out = (rf_face * max(n * cap, 1))()
+        counts = (C.c_int * max(n, 1))()
+        src = (C.c_int * max(n * cap, 1))()
+        st = _lib.check(self._lib.rf_tile_merge_device(self._h, (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols), n, C.byref(sp),
+                                                       flat.ctypes.data_as(C.POINTER(rf_face)), pc, out, cap, counts, src), self._h)
+        self.truncated = st == _lib.RF_ERR_TRUNCATED
+        return self._collect_tiled(out, counts, src, n, cap, return_tiles)
+
+    def detect_tiled_face_batch_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], threshold: float = 0.5,
+                                       steps: Optional[Sequence[int]] = None, overlap: int = 0, edge: int = 0, full_frame: bool = True,
+                                       tile_max_faces: int = 0, **kw):
+        """rf_detect_tiled_face_batch_device: detect_tiled_device followed on the device by the face batch of the merged faces.
+        Keywords as detect_face_batch_device (gate= / return_quality= select the gated launches); returns (detections, tensor,
+        matrices, offsets[, quality]) with the detections in source-frame pixels."""
+        n = len(ptrs)
+        p = (C.c_void_p * max(n, 1))(*ptrs)
+        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
+        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        tsp = tile_spec(overlap, edge, full_frame, tile_max_faces)
+        cap = self._tiled_cap(tsp)
+        out = (rf_face * max(n * cap, 1))()
+        counts = (C.c_int * max(n, 1))()
+        src = (C.c_int * max(n * cap, 1))()
+
+        def call(h, spec, d_out, tensor, mats, offsets, gate=None, quality=None):
+            return self._lib.rf_detect_tiled_face_batch_device(h, p, r, c, s, n, float(threshold), C.byref(tsp), out, cap, counts, src,
+                                                               spec, d_out, tensor, mats, offsets, gate, quality)
+        res = self._face_batch_call(call, n, **kw)
+        if len(res) == 4:
+            res = res[:3] + ([res[3][i, :min(counts[i], res[3].shape[1], cap)] for i in range(n)],)
+        return (self._collect_tiled(out, counts, src, n, cap, False),) + res
 
     def enqueue_device(self, ptrs, rows, cols, threshold: float = 0.5) -> int:
         n = len(ptrs)

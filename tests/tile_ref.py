@@ -1,0 +1,158 @@
+"""numpy restatement of tiled detection ("Tiled detection"): a helper, not a test.
+
+A frame larger than the net is cut into net-sized tiles that overlap; every tile is detected at 1:1, optionally the whole frame
+shrunk as one more pass; faces that reach a tile side which is not a frame side are dropped (the neighbour tile sees them whole), the
+rest are moved into source-frame pixels with ONE fp32 operation per coordinate and merged by the detector's own greedy NMS on a total
+order.  The plan is integer arithmetic; everything else is float32, one rounding per operation, in the order written below.  The kernel
+(retinaface_amd/csrc/kernels.hip tile_gather_kernel + nms_kernel as the merge), retinaface_amd/csrc/tile.h and the host entry points
+rf_tile_plan / rf_tile_map_face are checked byte for byte against this file.
+"""
+import numpy as np
+
+f32 = np.float32
+MERGE_CAP = 4096          # surviving candidates per frame the device merge holds
+MAX_PASSES = 1024
+
+
+def resolve(net_h, net_w, overlap=0, edge=0):
+    """the spec's defaults: overlap 0 = min(net) / 4, negative = 0 px; edge 0 = 8, negative = 0"""
+    nmin = min(net_h, net_w)
+    if overlap >= nmin:
+        raise ValueError("overlap must be smaller than min(net_h, net_w)")
+    if edge >= nmin // 2:
+        raise ValueError("edge must be smaller than min(net_h, net_w) / 2")
+    ov = nmin // 4 if overlap == 0 else max(overlap, 0)
+    ed = 8 if edge == 0 else max(edge, 0)
+    return ov, ed
+
+
+def axis(L, N, ov):
+    """(origin, size) of the tiles of one axis: length L, net size N, overlap ov"""
+    if L <= N:
+        return [(0, L)]
+    n = -((L - ov) // -(N - ov))
+    return [(i * (L - N) // (n - 1), N) for i in range(n)]
+
+
+def has_full(rows, cols, net_h, net_w, full_frame=True):
+    return bool(full_frame) and (rows > net_h or cols > net_w)
+
+
+def plan(rows, cols, net_h, net_w, overlap=0, full_frame=True):
+    """(passes, 4) int32 of x0, y0, tw, th: the tiles row-major, then the full-frame pass as (0, 0, cols, rows) when it exists"""
+    ov, _ = resolve(net_h, net_w, overlap)
+    xs, ys = axis(cols, net_w, ov), axis(rows, net_h, ov)
+    out = [(x0, y0, tw, th) for (y0, th) in ys for (x0, tw) in xs]
+    if has_full(rows, cols, net_h, net_w, full_frame):
+        out.append((0, 0, cols, rows))
+    if len(out) > MAX_PASSES:
+        raise ValueError("more than 1024 passes")
+    return np.array(out, np.int32).reshape(-1, 4)
+
+
+def frame_scale(rows, cols, net_h, net_w):
+    """rf_frame_scale: max(cols / net_w, rows / net_h, 1) in float32"""
+    sw, sh = f32(cols) / f32(net_w), f32(rows) / f32(net_h)
+    sc = sw if sw > sh else sh
+    return sc if sc > f32(1) else f32(1)
+
+
+def map_face(face, t, rows, cols, net_h, net_w, overlap=0, edge=0, full_frame=True):
+    """edge rule and mapping of one face (15 float32: score, box, 5 x, 5 y) of pass t: the mapped row, or None when dropped"""
+    _, ed = resolve(net_h, net_w, overlap, edge)
+    tiles = plan(rows, cols, net_h, net_w, overlap, full_frame)
+    f = np.asarray(face, np.float32).copy()
+    if has_full(rows, cols, net_h, net_w, full_frame) and t == len(tiles) - 1:
+        f[1:] = f[1:] * frame_scale(rows, cols, net_h, net_w)
+        return f
+    x0, y0, tw, th = (int(v) for v in tiles[t])
+    x1, y1, x2, y2 = f[1:5]
+    if x0 > 0 and x1 < f32(ed):
+        return None
+    if y0 > 0 and y1 < f32(ed):
+        return None
+    if x0 + tw < cols and x2 > f32(tw - 1 - ed):
+        return None
+    if y0 + th < rows and y2 > f32(th - 1 - ed):
+        return None
+    fx, fy = f32(x0), f32(y0)
+    f[[1, 3]] = f[[1, 3]] + fx
+    f[[2, 4]] = f[[2, 4]] + fy
+    f[5:10] = f[5:10] + fx
+    f[10:15] = f[10:15] + fy
+    return f
+
+
+def candidates(rows, cols, passes, net_h, net_w, max_det, overlap=0, edge=0, full_frame=True):
+    """the surviving faces of all passes of one frame, mapped: (rows (c, 15) float32, g (c,) int64) with g = t * max_det + k"""
+    out, gs = [], []
+    for t, faces in enumerate(passes):
+        faces = np.asarray(faces, np.float32).reshape(-1, 15)[:max_det]
+        for k, f in enumerate(faces):
+            m = map_face(f, t, rows, cols, net_h, net_w, overlap, edge, full_frame)
+            if m is not None:
+                out.append(m)
+                gs.append(t * max_det + k)
+    return (np.stack(out) if out else np.zeros((0, 15), np.float32)), np.array(gs, np.int64)
+
+
+def nms(cand, g, nms_threshold):
+    """greedy NMS on the total order (score descending by bit order, g ascending) with the reference's rule: +1-pixel areas and
+    intersections, skipped when w <= 0 or h <= 0, strict > threshold; float32, one rounding per operation.  Returns indices kept."""
+    thr = f32(nms_threshold)
+    bits = cand[:, 0].view(np.uint32).astype(np.int64)
+    order = np.lexsort((g, -bits))
+    b = cand[order, 1:5]
+    n = len(order)
+    alive = np.ones(n, bool)
+    one = f32(1)
+    area = (b[:, 2] - b[:, 0] + one) * (b[:, 3] - b[:, 1] + one)
+    keep = []
+    for i in range(n):
+        if not alive[i]:
+            continue
+        keep.append(order[i])
+        rest = np.nonzero(alive[i + 1:])[0] + i + 1
+        if len(rest) == 0:
+            continue
+        r = b[rest]
+        x = np.maximum(b[i, 0], r[:, 0])
+        y = np.maximum(b[i, 1], r[:, 1])
+        w = np.minimum(b[i, 2], r[:, 2]) - x + one
+        h = np.minimum(b[i, 3], r[:, 3]) - y + one
+        ok = ~((w <= 0) | (h <= 0))
+        inter = w * h
+        with np.errstate(all="ignore"):
+            iou = inter / (area[i] + area[rest] - inter)
+        alive[rest[ok & (iou > thr)]] = False
+    return np.array(keep, np.int64)
+
+
+def merge(rows, cols, passes, net_h, net_w, nms_threshold, max_det, overlap=0, edge=0, full_frame=True, max_faces=0):
+    """one frame: (faces (k, 15) float32 in merge order, k = min(count, max_faces); count: the true number kept; src_tile (k,) int32;
+    the number of surviving candidates).  passes[t]: the result of pass t (plan order), at most max_det faces in score order."""
+    mf = max_faces or max_det
+    cand, g = candidates(rows, cols, passes, net_h, net_w, max_det, overlap, edge, full_frame)
+    keep = nms(cand, g, nms_threshold) if len(cand) else np.zeros(0, np.int64)
+    return cand[keep[:mf]], len(keep), (g[keep[:mf]] // max_det).astype(np.int32), len(cand)
+
+
+def views(frame, tiles):
+    """the ROI views of a frame for a plan (the full-frame pass is the whole frame)"""
+    return [frame[y0:y0 + th, x0:x0 + tw] for x0, y0, tw, th in (tuple(int(v) for v in t) for t in tiles)]
+
+
+def mosaic(base):
+    """the test frame: the padded base frame averaged over 2 x 2 blocks, (a + b + c + d + 2) >> 2, placed four times as a 2 x 2 mosaic"""
+    b = base.astype(np.uint16)
+    half = ((b[0::2, 0::2] + b[0::2, 1::2] + b[1::2, 0::2] + b[1::2, 1::2] + 2) >> 2).astype(np.uint8)
+    return np.ascontiguousarray(np.tile(half, (2, 2, 1)))
+
+
+def iou_plus1(a, b):
+    w = min(a[2], b[2]) - max(a[0], b[0]) + 1
+    h = min(a[3], b[3]) - max(a[1], b[1]) + 1
+    if w <= 0 or h <= 0:
+        return 0.0
+    inter = float(w) * float(h)
+    return inter / ((float(a[2]) - float(a[0]) + 1) * (float(a[3]) - float(a[1]) + 1) + (float(b[2]) - float(b[0]) + 1) * (float(b[3]) - float(b[1]) + 1) - inter)
