@@ -96,6 +96,15 @@ public:
     void detectTiled(const vector<cv::Mat> &imgs, float threshold = 0.5, const rf_tile_spec *spec = nullptr);
     const vector<vector<int>> &tileSources() const { return tileSrc_; }
 
+    /* additive: face tracks (rf_tracker_create / rf_detect_track_batch): createTracker() makes a tracker on this handle (spec may be
+       nullptr: the defaults; the destructor frees it); detectTracked() is detectBatchImages() plus one frame step per image of stream
+       streams[i] (-1: not tracked), with the tracks in source-frame pixels.  lastTrackTags()[i][k] is the tag of face k of
+       lastBatchResult()[i]; lastEndedTracks()[i] the tracks that ended in image i's step. */
+    rf_tracker createTracker(int nStreams = 1, const rf_track_spec *spec = nullptr);
+    void detectTracked(const vector<cv::Mat> &imgs, rf_tracker tracker, const vector<int> &streams, float threshold = 0.5);
+    const vector<vector<rf_track_tag>> &lastTrackTags() const { return trackTags_; }
+    const vector<vector<rf_track>> &lastEndedTracks() const { return trackEnded_; }
+
     /* `scale` of RetinaFace.cpp:585-589: multiply lastResult() coordinates by it for source-frame pixels (:732-739, commented) */
     float frameScale(const Mat &img) const { return rf_frame_scale(h_, img.rows, img.cols); }
 
@@ -121,6 +130,8 @@ private:
     vector<rf_face_quality> faceQuality_;
     int faceQualityStride_ = 0;
     vector<vector<int>> tileSrc_;
+    vector<vector<rf_track_tag>> trackTags_;
+    vector<vector<rf_track>> trackEnded_;
     vector<uint8_t> faceBatchCall(const vector<cv::Mat> &imgs, float threshold, const rf_face_batch_spec &spec, bool gated,
                                   const rf_face_gate *gate);
 };

@@ -403,6 +403,109 @@ int rf_detect_tiled_face_batch_device(rf_handle h, const void *const *d_bgr, con
                                       int *src_tile, const rf_face_batch_spec *fb_spec, void *d_tensor, void *tensor, double *matrices,
                                       int *offsets, const rf_face_gate *gate, rf_face_quality *quality);
 
+/* ---- Face tracks: stable ids and best shots across calls, kept in device memory (DESIGN.md "Face tracks" holds the definition;
+ * tests/track_ref.py restates it in numpy; every result is byte-exact against it).  A tracker holds, per stream, a table of max_tracks
+ * slots, a frame counter f (from 0) and a next id (from 1; ids never repeat until the stream is reset).  One FRAME STEP of a stream takes
+ * the faces d_0 .. d_(m-1) of one image in score order, m = min(count, max_detections, max_faces, 256); faces at or beyond m get the tag
+ * {0, -1, 0, 0, RF_TRACK_UNTRACKED}:
+ *   map      all 14 coordinates times coord_scale (one fp32 multiply, also for a scale of 1); f = the counter, which then grows by one
+ *   match    for k = 0 .. m-1 in order, over the live tracks no earlier face of this frame has claimed: the overlap of d_k's box with the
+ *            track's `last` box, exactly the detector's NMS expression (w = min(x2) - max(x1) + 1, h likewise, 0 when w <= 0 || h <= 0,
+ *            else inter / (area1 + area2 - inter) with +1-pixel areas; fp32, never contracted).  Eligible: iou >= min_iou (NaN fails).
+ *            The face takes the eligible track with the largest overlap, ties to the lowest slot; that track gets last = d_k,
+ *            last_frame = f, hits += 1, missed = 0
+ *   best     of a matched or new track: with quality records the face is eligible when its record's flags == 0 and its value is the
+ *            record's sharpness; without, every face is eligible with value (double)score.  It replaces the best shot when
+ *            best_frame < 0 || value > best_value (strict: the earlier shot wins a tie); its tag then carries RF_TRACK_BEST
+ *   age      live tracks nobody claimed: missed += 1; a track with missed > max_missed ENDS: its record goes to the image's ended list
+ *            (ascending slot order) and its slot is freed (the whole record becomes zero; id 0 = free)
+ *   open     the unmatched faces with score >= new_score, in score order, each take the lowest free slot (slots freed by `age` in this
+ *            frame included): id = next_id++, hits = 1, missed = 0, first_frame = last_frame = f, best_frame = -1 and then `best`.
+ *            A face below new_score is tagged RF_TRACK_UNTRACKED; with no free slot RF_TRACK_UNTRACKED | RF_TRACK_OVERFLOW and the
+ *            call returns RF_ERR_TRUNCATED (everything else stays valid)
+ *   tag      of a tracked face: the track's id and slot, its hits after this frame, age = (int32)min(f - first_frame + 1, INT32_MAX),
+ *            flags = RF_TRACK_NEW | RF_TRACK_CONFIRMED (hits >= min_hits) | RF_TRACK_BEST as they apply.  rf_track.flags holds
+ *            RF_TRACK_CONFIRMED once it applies, nothing else. */
+typedef struct rf_track_spec {
+    uint32_t struct_size;   /* sizeof(rf_track_spec) */
+    int32_t max_tracks;     /* slots per stream, 1..256; 0 = 64 */
+    float min_iou;          /* association threshold, finite and in (0, 1]; 0 = 0.3 */
+    int32_t max_missed;     /* a track ends in the frame where missed > max_missed; 0 = 10; negative = 0 */
+    int32_t min_hits;       /* matched frames before RF_TRACK_CONFIRMED is set; 0 = 3; negative = 1 */
+    float new_score;        /* an unmatched face opens a track only if score >= new_score; finite and >= 0; 0 = every face */
+} rf_track_spec;
+typedef struct rf_track {   /* 176 bytes, no padding */
+    int64_t id;             /* 0 = free slot */
+    int64_t first_frame, last_frame, best_frame;    /* best_frame -1: no best shot yet */
+    double best_value;
+    int32_t hits, missed, flags, reserved;
+    rf_face last, best;     /* in source-frame pixels (mapped) */
+} rf_track;
+typedef struct rf_track_tag { int64_t id; int32_t slot, hits, age, flags; } rf_track_tag;   /* 24 bytes */
+enum { RF_TRACK_NEW = 1, RF_TRACK_CONFIRMED = 2, RF_TRACK_BEST = 4, RF_TRACK_UNTRACKED = 8, RF_TRACK_OVERFLOW = 16 };
+
+/* Host only, no GPU, no handle -- the same code the kernel runs, compiled for the host.  One frame step on a caller-held table of
+ * max_tracks records (all zero = empty) with its frame counter and next id (0 and 1 to start).  faces: count records in score order;
+ * quality: NULL or one record per face k < min(count, max_faces); max_faces >= 1.  tags: count records.  ended (may be NULL with
+ * cap_ended 0): the first min(*ended_count, cap_ended) ended tracks; *ended_count: the true number.  Returns 0, RF_ERR_TRUNCATED (a
+ * full table or a cut ended list) or RF_ERR_INVALID_ARG (bad spec, NULL argument, negative count), which changes nothing. */
+int rf_track_step(const rf_track_spec *spec, rf_track *table, int64_t *frames, int64_t *next_id, const rf_face *faces, int count,
+                  float coord_scale, const rf_face_quality *quality, int max_faces, rf_track_tag *tags, rf_track *ended, int cap_ended,
+                  int *ended_count);
+
+/* A tracker lives on a handle; its state (n_streams tables) stays in device memory between calls.  n_streams is 1..1024.  A bad spec or
+ * argument is refused before any state changes.  Multi-device handles return RF_ERR_UNSUPPORTED.  rf_destroy frees the trackers that are
+ * left.  A tracked call that ends in an error (RF_ERR_TRUNCATED is not one) leaves the tracker's state unspecified: every later tracked
+ * call returns RF_ERR_INVALID_ARG until rf_tracker_reset(tracker, -1). */
+typedef struct rf_tracker_s *rf_tracker;
+int rf_tracker_create(rf_handle h, const rf_track_spec *spec, int n_streams, rf_tracker *out_tracker);
+void rf_tracker_destroy(rf_tracker tracker);
+/* forget a stream's tracks, frame counter and ids (stream -1: all streams) */
+int rf_tracker_reset(rf_tracker tracker, int stream);
+/* Host copy of a stream's table (the first min(cap, max_tracks) slots; table may be NULL), frame counter and next id (may be NULL).
+ * Returns max_tracks. */
+int rf_tracker_read(rf_tracker tracker, int stream, rf_track *table, int cap, int64_t *frames, int64_t *next_id);
+/* Ends every live track of the stream: they are returned slot-ascending (the first min(count, cap)) and their slots freed; the frame
+ * counter and the next id stay.  Returns the number of tracks ended. */
+int rf_tracker_flush(rf_tracker tracker, int stream, rf_track *ended, int cap, int64_t *frames, int64_t *next_id);
+
+/* Frame steps over faces the CALLER supplies in host memory (faces[i * cap_per_image + k], k < counts[i]; the counterpart of
+ * rf_tile_merge_device for this stage: no forward pass runs, no frames are needed).  stream_of_image[i] is 0 .. n_streams-1, or -1: that
+ * image is not tracked (all-zero tags, empty ended list, no frame step).  Images of one stream are stepped in call order; streams are
+ * independent.  coord_scale: per image, NULL = 1.  quality: NULL, or n * max_faces records (image i, face k at i * max_faces + k).
+ * tags: n * cap_per_image records, tags[i * cap_per_image + k]; records at or beyond counts[i] are zero.  ended: n * cap_ended records,
+ * image i's at ended + i * cap_ended (the first min(ended_counts[i], cap_ended)); a cut list returns RF_ERR_TRUNCATED. */
+int rf_track_update_device(rf_handle h, rf_tracker tracker, const int *stream_of_image, int n, const rf_face *faces, int cap_per_image,
+                           const int *counts, const float *coord_scale, const rf_face_quality *quality, int max_faces,
+                           rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_counts);
+
+/* Measurement hook: the time of the track launch of the handle's most recent rf_track_update_device call, between two HIP events on its
+ * stream (the upload and the copy-out are outside).  RF_ERR_INVALID_ARG before the first such call. */
+int rf_track_last_launch_ms(rf_handle h, float *ms);
+
+/* rf_detect_batch_device / rf_detect_batch + the frame step of every image, in one call: detection runs exactly as there (out / counts /
+ * rf_last_anchor_indices are the same bytes); one track launch follows each detection launch on its stream and reads the faces from the
+ * device-visible result block, the track launches of a call wait for each other on the device (a stream's images may sit in several
+ * launches) -- no host synchronisation in between.  coord_scale is each frame's rf_frame_scale, so tracks live in source pixels; the
+ * best shot goes by score.  A NULL / 0 x 0 frame is a frame with no faces: it ages its stream's tracks.  n may exceed max_batch.
+ * There is no tracked form of the asynchronous tickets, of rf_detect_batch_pad32, of the tiled calls or of the alignment slot-array
+ * calls: a tiled caller follows rf_detect_tiled_batch* with rf_track_update_device. */
+int rf_detect_track_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                 float threshold, rf_face *out, int cap_per_image, int *counts, rf_tracker tracker,
+                                 const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_counts);
+int rf_detect_track_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                          float threshold, rf_face *out, int cap_per_image, int *counts, rf_tracker tracker,
+                          const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_counts);
+
+/* rf_detect_face_batch_gated_device + the frame steps: tensor, matrices, offsets and quality are that call's bytes.  With a gate or a
+ * quality buffer the track launch reads the call's quality records from device memory and the best shot goes by sharpness among the
+ * faces whose flags are 0; otherwise by score.  max_faces is the spec's. */
+int rf_detect_track_face_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                      float threshold, rf_face *out, int cap_per_image, int *counts, const rf_face_batch_spec *spec,
+                                      void *d_tensor, void *tensor, double *matrices, int *offsets, const rf_face_gate *gate,
+                                      rf_face_quality *quality, rf_tracker tracker, const int *stream_of_image, rf_track_tag *tags,
+                                      rf_track *ended, int cap_ended, int *ended_counts);
+
 /* Asynchronous form of rf_detect_batch_device for serving loops: enqueue returns as soon as the
  * batch is queued on the engine's stream (n <= max_batch); `ticket` identifies one of
  * rf_num_slots() result slots.  rf_wait blocks until that batch has finished and copies its results.

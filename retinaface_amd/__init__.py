@@ -11,3 +11,5 @@ from ._lib import RFError, abi_version, lib_path, load_library  # noqa: F401
 from .detector import (PRECISION_FP16, PRECISION_FP32, PRECISION_INT8, QUALITY_DTYPE, Detection, RetinaFace, align_matrix,  # noqa: F401
                        face_aa_factor, face_batch_plan, face_batch_spec, face_gate, face_gate_eval, face_pose, face_value_table, tile_map_face,
                        tile_plan, tile_spec)
+from .detector import (FACE_DTYPE, TRACK_BEST, TRACK_CONFIRMED, TRACK_DTYPE, TRACK_NEW, TRACK_OVERFLOW, TRACK_TAG_DTYPE, TRACK_UNTRACKED,  # noqa: F401
+                       Tracker, track_spec, track_step)

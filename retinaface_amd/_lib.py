@@ -58,6 +58,23 @@ class rf_tile_spec(C.Structure):
                 ("max_faces", C.c_int32)]
 
 
+class rf_track_spec(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_tracks", C.c_int32), ("min_iou", C.c_float), ("max_missed", C.c_int32),
+                ("min_hits", C.c_int32), ("new_score", C.c_float)]
+
+
+class rf_track(C.Structure):
+    _fields_ = [("id", C.c_int64), ("first_frame", C.c_int64), ("last_frame", C.c_int64), ("best_frame", C.c_int64),
+                ("best_value", C.c_double), ("hits", C.c_int32), ("missed", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32),
+                ("last", rf_face), ("best", rf_face)]
+
+
+class rf_track_tag(C.Structure):
+    _fields_ = [("id", C.c_int64), ("slot", C.c_int32), ("hits", C.c_int32), ("age", C.c_int32), ("flags", C.c_int32)]
+
+
+RF_TRACK_NEW, RF_TRACK_CONFIRMED, RF_TRACK_BEST, RF_TRACK_UNTRACKED, RF_TRACK_OVERFLOW = 1, 2, 4, 8, 16
+
 RF_GATE_INVALID, RF_GATE_SHARPNESS, RF_GATE_IOD, RF_GATE_YAW, RF_GATE_ROLL, RF_GATE_COVERED, RF_GATE_DARK, RF_GATE_BRIGHT = (
     1, 2, 4, 8, 16, 32, 64, 128)
 
@@ -128,6 +145,27 @@ SYMBOLS = {
                                                     C.c_float, _PP(rf_tile_spec), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int),
                                                     _PP(rf_face_batch_spec), C.c_void_p, C.c_void_p, _PP(C.c_double), _PP(C.c_int),
                                                     _PP(rf_face_gate), _PP(rf_face_quality)]),
+    "rf_track_step": (C.c_int, [_PP(rf_track_spec), _PP(rf_track), _PP(C.c_int64), _PP(C.c_int64), _PP(rf_face), C.c_int, C.c_float,
+                                _PP(rf_face_quality), C.c_int, _PP(rf_track_tag), _PP(rf_track), C.c_int, _PP(C.c_int)]),
+    "rf_tracker_create": (C.c_int, [C.c_void_p, _PP(rf_track_spec), C.c_int, _PP(C.c_void_p)]),
+    "rf_tracker_destroy": (None, [C.c_void_p]),
+    "rf_tracker_reset": (C.c_int, [C.c_void_p, C.c_int]),
+    "rf_tracker_read": (C.c_int, [C.c_void_p, C.c_int, _PP(rf_track), C.c_int, _PP(C.c_int64), _PP(C.c_int64)]),
+    "rf_tracker_flush": (C.c_int, [C.c_void_p, C.c_int, _PP(rf_track), C.c_int, _PP(C.c_int64), _PP(C.c_int64)]),
+    "rf_track_update_device": (C.c_int, [C.c_void_p, C.c_void_p, _PP(C.c_int), C.c_int, _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_float),
+                                         _PP(rf_face_quality), C.c_int, _PP(rf_track_tag), _PP(rf_track), C.c_int, _PP(C.c_int)]),
+    "rf_track_last_launch_ms": (C.c_int, [C.c_void_p, _PP(C.c_float)]),
+    "rf_detect_track_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int, C.c_float,
+                                               _PP(rf_face), C.c_int, _PP(C.c_int), C.c_void_p, _PP(C.c_int), _PP(rf_track_tag),
+                                               _PP(rf_track), C.c_int, _PP(C.c_int)]),
+    "rf_detect_track_batch": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int, C.c_float,
+                                        _PP(rf_face), C.c_int, _PP(C.c_int), C.c_void_p, _PP(C.c_int), _PP(rf_track_tag),
+                                        _PP(rf_track), C.c_int, _PP(C.c_int)]),
+    "rf_detect_track_face_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                                    C.c_float, _PP(rf_face), C.c_int, _PP(C.c_int), _PP(rf_face_batch_spec),
+                                                    C.c_void_p, C.c_void_p, _PP(C.c_double), _PP(C.c_int), _PP(rf_face_gate),
+                                                    _PP(rf_face_quality), C.c_void_p, _PP(C.c_int), _PP(rf_track_tag), _PP(rf_track),
+                                                    C.c_int, _PP(C.c_int)]),
     "rf_num_slots": (C.c_int, [C.c_void_p]),
     "rf_enqueue_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int),
                                           C.c_int, C.c_float, _PP(C.c_int)]),

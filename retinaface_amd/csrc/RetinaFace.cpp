@@ -71,6 +71,42 @@ void RetinaFace::detectTiled(const vector<cv::Mat> &imgs, float threshold, const
     }
 }
 
+rf_tracker RetinaFace::createTracker(int nStreams, const rf_track_spec *spec) {
+    rf_tracker t = nullptr;
+    check(rf_tracker_create(h_, spec, nStreams, &t), h_, "RetinaFace::createTracker");
+    return t;
+}
+
+void RetinaFace::detectTracked(const vector<cv::Mat> &imgs, rf_tracker tracker, const vector<int> &streams, float threshold) {
+    const int n = (int)imgs.size();
+    if ((int)streams.size() != n) throw std::runtime_error("RetinaFace::detectTracked: one stream per image");
+    lastBatch_.assign(n, vector<FaceDetectInfo>());
+    trackTags_.assign(n, vector<rf_track_tag>());
+    trackEnded_.assign(n, vector<rf_track>());
+    if (n == 0) return;
+    const int capEnded = 256;                          // a table holds at most 256 tracks: no list is ever cut
+    vector<const uint8_t *> ptrs(n);
+    vector<int> rows(n), cols(n), steps(n), counts(n, 0), endedCounts(n, 0);
+    for (int i = 0; i < n; i++) {
+        ptrs[i] = imgs[i].empty() ? nullptr : imgs[i].data;
+        rows[i] = imgs[i].rows; cols[i] = imgs[i].cols; steps[i] = (int)(size_t)imgs[i].step;
+    }
+    vector<rf_face> faces((size_t)n * maxDet_);
+    vector<rf_track_tag> tags((size_t)n * maxDet_);
+    vector<rf_track> ended((size_t)n * capEnded);
+    check(rf_detect_track_batch(h_, ptrs.data(), rows.data(), cols.data(), steps.data(), n, threshold, faces.data(), maxDet_, counts.data(),
+                                tracker, streams.data(), tags.data(), ended.data(), capEnded, endedCounts.data()), h_,
+          "RetinaFace::detectTracked");
+    for (int i = 0; i < n; i++) {
+        const int k = counts[i] < maxDet_ ? counts[i] : maxDet_;
+        lastBatch_[i].resize(k);
+        if (k) memcpy(lastBatch_[i].data(), &faces[(size_t)i * maxDet_], (size_t)k * sizeof(rf_face));
+        trackTags_[i].assign(tags.begin() + (size_t)i * maxDet_, tags.begin() + (size_t)i * maxDet_ + k);
+        const int e = endedCounts[i] < capEnded ? endedCounts[i] : capEnded;
+        trackEnded_[i].assign(ended.begin() + (size_t)i * capEnded, ended.begin() + (size_t)i * capEnded + e);
+    }
+}
+
 void RetinaFace::detectPad32(const Mat &img, float threshold) {
     last_.clear();
     if (img.empty()) return;                       // RetinaFace.cpp:945-947

@@ -27,7 +27,19 @@ struct rf_engine {
     float nms = 0.4f;
     rf::EngineOptions opt;
     std::list<std::pair<std::pair<int, int>, std::unique_ptr<rf::Engine>>> pool;
+    std::vector<rf_tracker_s *> trackers;              // rf_tracker_create: what rf_destroy still has to free
+    ~rf_engine();
 };
+
+// a tracker: the handle it lives on and the engine's object
+struct rf_tracker_s {
+    rf_engine *h;
+    void *impl;
+};
+
+rf_engine::~rf_engine() {
+    for (rf_tracker_s *t : trackers) delete t;         // the engine frees the device state with itself
+}
 
 namespace {
 
@@ -559,6 +571,154 @@ int rf_detect_tiled_face_batch_device(rf_handle h, const void *const *d_bgr, con
         h->eng->detect_tiled((const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, out, cap_per_image, counts, &tr, rq, &over);
         if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
         if (over) { h->error = kFaceOverflow; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+
+// ---- face tracks (track.h)
+int rf_track_step(const rf_track_spec *spec, rf_track *table, int64_t *frames, int64_t *next_id, const rf_face *faces, int count,
+                  float coord_scale, const rf_face_quality *quality, int max_faces, rf_track_tag *tags, rf_track *ended, int cap_ended,
+                  int *ended_count) {
+    rf::TrackSpec sp;
+    if (rf::track_spec_resolve(spec, &sp)) return RF_ERR_INVALID_ARG;
+    if (!table || !frames || !next_id || !ended_count || count < 0 || max_faces < 1 || cap_ended < 0) return RF_ERR_INVALID_ARG;
+    if (count > 0 && (!faces || !tags)) return RF_ERR_INVALID_ARG;
+    if (cap_ended > 0 && !ended) return RF_ERR_INVALID_ARG;
+    const int m = std::min(std::min(count, max_faces), rf::kTrackMaxFaces);
+    const int st = rf::track_step(sp, table, frames, next_id, (const float *)faces, (int)(sizeof(rf_face) / sizeof(float)), m, coord_scale,
+                                  quality, tags, ended, cap_ended, ended_count);
+    for (int k = m; k < count; k++) tags[k] = rf::track_tag_untracked(0);
+    return st ? RF_ERR_TRUNCATED : RF_OK;
+}
+
+namespace {
+const char kTrackCut[] = "a track table is full or an ended list was cut";
+
+void track_request(rf_handle h, rf_tracker tracker, const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended,
+                   int *ended_counts, rf::TrackRequest *rq) {
+    if (!tracker || tracker->h != h) throw rf::ArgError("not a tracker of this handle");
+    rq->tracker = tracker->impl;
+    rq->stream_of_image = stream_of_image;
+    rq->tags = tags; rq->ended = ended; rq->cap_ended = cap_ended; rq->ended_counts = ended_counts;
+}
+
+int detect_track_common(rf_handle h, const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,
+                        float thr, rf_face *out, int cap, int *counts, rf_tracker tracker, const int *stream_of_image, rf_track_tag *tags,
+                        rf_track *ended, int cap_ended, int *ended_counts) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        if (h->eng->num_devices() > 1) throw rf::Unsupported("face tracks are not available on a multi-device handle");
+        rf::TrackRequest rq;
+        track_request(h, tracker, stream_of_image, tags, ended, cap_ended, ended_counts, &rq);
+        bool tr = false, cut = false;
+        h->eng->detect_track(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, rq, &cut);
+        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        if (cut) { h->error = kTrackCut; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+}  // namespace
+
+int rf_tracker_create(rf_handle h, const rf_track_spec *spec, int n_streams, rf_tracker *out_tracker) {
+    rf::TrackSpec sp;
+    if (out_tracker) *out_tracker = nullptr;
+    const char *bad = rf::track_spec_resolve(spec, &sp);               // spec and range first: refused without a GPU
+    if (!bad && (n_streams < 1 || n_streams > rf::kTrackMaxStreams)) bad = "n_streams must be in [1, 1024]";
+    if (!h || !out_tracker) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        if (bad) throw rf::ArgError(bad);
+        void *impl = h->eng->tracker_create(sp, n_streams);
+        rf_tracker_s *t = new rf_tracker_s{h, impl};
+        h->trackers.push_back(t);
+        *out_tracker = t;
+        return RF_OK;
+    });
+}
+
+void rf_tracker_destroy(rf_tracker tracker) {
+    if (!tracker) return;
+    rf_engine *h = tracker->h;
+    (void)guarded(h, [&]() -> int {
+        h->eng->tracker_destroy(tracker->impl);
+        h->trackers.erase(std::remove(h->trackers.begin(), h->trackers.end(), tracker), h->trackers.end());
+        delete tracker;
+        return RF_OK;
+    });
+}
+
+int rf_tracker_reset(rf_tracker tracker, int stream) {
+    if (!tracker) return RF_ERR_INVALID_ARG;
+    return guarded(tracker->h, [&]() -> int { tracker->h->eng->tracker_reset(tracker->impl, stream); return RF_OK; });
+}
+
+int rf_tracker_read(rf_tracker tracker, int stream, rf_track *table, int cap, int64_t *frames, int64_t *next_id) {
+    if (!tracker) return RF_ERR_INVALID_ARG;
+    return guarded(tracker->h, [&]() -> int { return tracker->h->eng->tracker_read(tracker->impl, stream, table, cap, frames, next_id, false); });
+}
+
+int rf_tracker_flush(rf_tracker tracker, int stream, rf_track *ended, int cap, int64_t *frames, int64_t *next_id) {
+    if (!tracker) return RF_ERR_INVALID_ARG;
+    return guarded(tracker->h, [&]() -> int { return tracker->h->eng->tracker_read(tracker->impl, stream, ended, cap, frames, next_id, true); });
+}
+
+int rf_track_update_device(rf_handle h, rf_tracker tracker, const int *stream_of_image, int n, const rf_face *faces, int cap_per_image,
+                           const int *counts, const float *coord_scale, const rf_face_quality *quality, int max_faces,
+                           rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_counts) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        if (h->eng->num_devices() > 1) throw rf::Unsupported("face tracks are not available on a multi-device handle");
+        rf::TrackRequest rq;
+        track_request(h, tracker, stream_of_image, tags, ended, cap_ended, ended_counts, &rq);
+        bool cut = false;
+        h->eng->track_update(rq, n, faces, cap_per_image, counts, coord_scale, quality, max_faces ? max_faces : h->eng->default_max_faces(), &cut);
+        if (cut) { h->error = kTrackCut; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+
+int rf_track_last_launch_ms(rf_handle h, float *ms) {
+    if (!h || !ms) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        const float v = h->eng->track_last_launch_ms();
+        if (v < 0.f) throw rf::ArgError("no rf_track_update_device call has been timed on this handle");
+        *ms = v;
+        return RF_OK;
+    });
+}
+
+int rf_detect_track_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                 float threshold, rf_face *out, int cap_per_image, int *counts, rf_tracker tracker,
+                                 const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_counts) {
+    return detect_track_common(h, (const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, out, cap_per_image, counts, tracker,
+                               stream_of_image, tags, ended, cap_ended, ended_counts);
+}
+
+int rf_detect_track_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                          float threshold, rf_face *out, int cap_per_image, int *counts, rf_tracker tracker,
+                          const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_counts) {
+    return detect_track_common(h, bgr, rows, cols, steps, n, false, threshold, out, cap_per_image, counts, tracker, stream_of_image, tags,
+                               ended, cap_ended, ended_counts);
+}
+
+int rf_detect_track_face_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                      float threshold, rf_face *out, int cap_per_image, int *counts, const rf_face_batch_spec *spec,
+                                      void *d_tensor, void *tensor, double *matrices, int *offsets, const rf_face_gate *gate,
+                                      rf_face_quality *quality, rf_tracker tracker, const int *stream_of_image, rf_track_tag *tags,
+                                      rf_track *ended, int cap_ended, int *ended_counts) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        if (h->eng->num_devices() > 1) throw rf::Unsupported("face tracks are not available on a multi-device handle");
+        rf::FaceBatchRequest fb;
+        face_batch_request(spec, h->eng->default_max_faces(), d_tensor, tensor, matrices, offsets, &fb);
+        if (gate || quality) face_gate_request(gate, quality, &fb);
+        rf::TrackRequest rq;
+        track_request(h, tracker, stream_of_image, tags, ended, cap_ended, ended_counts, &rq);
+        bool tr = false, over = false, cut = false;
+        h->eng->detect_track_face_batch((const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, out, cap_per_image, counts, &tr,
+                                        fb, &over, rq, &cut);
+        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        if (over) { h->error = kFaceOverflow; return RF_ERR_TRUNCATED; }
+        if (cut) { h->error = kTrackCut; return RF_ERR_TRUNCATED; }
         return RF_OK;
     });
 }

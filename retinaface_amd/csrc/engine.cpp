@@ -209,6 +209,9 @@ public:
         if (align_stream_) { (void)hipStreamSynchronize(align_stream_); (void)hipStreamDestroy(align_stream_); }
         for (DeviceScratch *b : {&align_crops_, &align_mats_, &align_tab_, &fb_state_, &fq_records_, &fq_packed_, &fq_offsets_, &tile_cand_, &tile_count_, &tile_out_,
                                  &tile_outcount_, &tile_tab_, &tile_frames_}) b->release();
+        for (HostScratch *b : {&trk_tags_, &trk_ended_, &trk_counts_}) b->release();
+        for (auto &t : trackers_) t->state.release();
+        for (hipEvent_t e : trk_ev_) if (e) (void)hipEventDestroy(e);
         kind_.arena->release();
         for (auto &e : prof_ev_) (void)hipEventDestroy(e);
     }
@@ -813,6 +816,159 @@ public:
         tile_copy_out(n, rq, out, cap_per_image, counts, truncated);
     }
 
+    // -------------------------------------------------------------------------------- face tracks
+    void *tracker_create(const TrackSpec &spec, int n_streams) override {
+        if (n_streams < 1 || n_streams > kTrackMaxStreams) throw ArgError("n_streams must be in [1, 1024]");
+        if (spec.max_tracks < 1 || spec.max_tracks > kTrackMaxTracks) throw ArgError("max_tracks must be in [1, 256]");
+        DeviceGuard guard(device_);
+        std::unique_ptr<Tracker> t(new Tracker);
+        t->spec = spec; t->n_streams = n_streams;
+        t->state.reserve((size_t)n_streams * t->stream_bytes());
+        try { tracker_reset_impl(*t, -1); } catch (...) { t->state.release(); throw; }
+        trackers_.push_back(std::move(t));
+        return trackers_.back().get();
+    }
+    void tracker_destroy(void *p) override {
+        for (size_t i = 0; i < trackers_.size(); i++)
+            if (trackers_[i].get() == p) {
+                DeviceGuard guard(device_);
+                trackers_[i]->state.release();
+                trackers_.erase(trackers_.begin() + i);
+                return;
+            }
+    }
+    void tracker_reset(void *p, int stream) override {
+        Tracker &t = tracker_of(p);
+        if (stream < -1 || stream >= t.n_streams) throw ArgError("stream out of range");
+        DeviceGuard guard(device_);
+        tracker_reset_impl(t, stream);
+        if (stream < 0) t.dirty = false;
+    }
+    int tracker_read(void *p, int stream, rf_track *table, int cap, int64_t *frames, int64_t *next_id, bool flush) override {
+        Tracker &t = tracker_of(p);
+        if (stream < 0 || stream >= t.n_streams) throw ArgError("stream out of range");
+        if (cap < 0 || (cap > 0 && !table)) throw ArgError("table is null");
+        if (t.dirty) throw ArgError("the tracker's last call failed: reset it first");
+        DeviceGuard guard(device_);
+        std::vector<uint8_t> img(t.stream_bytes());
+        uint8_t *d = t.state.ptr + (size_t)stream * t.stream_bytes();
+        RF_HIP(hipMemcpy(img.data(), d, img.size(), hipMemcpyDeviceToHost));
+        const TrackHeader *hd = (const TrackHeader *)img.data();
+        rf_track *tr = (rf_track *)(img.data() + sizeof(TrackHeader));
+        if (frames) *frames = hd->frames;
+        if (next_id) *next_id = hd->next_id;
+        if (!flush) {
+            if (cap > 0) memcpy(table, tr, (size_t)std::min(cap, t.spec.max_tracks) * sizeof(rf_track));
+            return t.spec.max_tracks;
+        }
+        int ended = 0;
+        for (int s = 0; s < t.spec.max_tracks; s++) {
+            if (tr[s].id == 0) continue;
+            if (ended < cap) table[ended] = tr[s];
+            ended++;
+            memset(&tr[s], 0, sizeof(rf_track));
+        }
+        if (ended) RF_HIP(hipMemcpy(d, img.data(), img.size(), hipMemcpyHostToDevice));
+        return ended;
+    }
+
+    void track_update(const TrackRequest &rq, int n, const rf_face *faces, int cap_per_image, const int *counts, const float *coord_scale,
+                      const rf_face_quality *quality, int max_faces, bool *cut) override {
+        *cut = false;
+        if (n < 0 || (n > 0 && (!faces || !counts))) throw ArgError("null argument");
+        if (cap_per_image < 1) throw ArgError("cap_per_image must be >= 1");
+        if (max_faces < 1 || max_faces > kAlignMaxFaces) throw ArgError("max_faces must be in [1, 4096]");
+        for (int i = 0; i < n; i++)
+            if (counts[i] < 0) throw ArgError("negative face count");
+        Tracker &t = track_check(rq, n);
+        if (n == 0) return;
+        DeviceGuard guard(device_);
+        const int fpi = std::min(std::min(cap_per_image, max_faces), kTrackMaxFaces);      // records per image that travel to the device
+        const int mq = std::min(max_faces, kTrackMaxFaces);                                 // quality records per image that do
+        // one table: streams | images | counts | quality records | faces (60-byte records)
+        const size_t o_img = align256((size_t)n * sizeof(TrackStreamEntry)), o_cnt = o_img + align256((size_t)n * sizeof(TrackImageEntry)),
+                     o_q = o_cnt + align256((size_t)n * sizeof(int)), o_face = o_q + align256(quality ? (size_t)n * mq * sizeof(rf_face_quality) : 0),
+                     total = o_face + (size_t)n * fpi * sizeof(rf_face);
+        align_host_.assign(total, 0);
+        int *cnt = (int *)(align_host_.data() + o_cnt);
+        std::vector<float> scale(n);
+        std::vector<char> empty(n, 0);
+        for (int i = 0; i < n; i++) {
+            cnt[i] = counts[i];            // the true count: the kernel clamps it, and tags the faces beyond the clamp
+            scale[i] = coord_scale ? coord_scale[i] : 1.f;
+            const int c = std::min(counts[i], fpi);
+            if (c) memcpy(align_host_.data() + o_face + (size_t)i * fpi * sizeof(rf_face), faces + (size_t)i * cap_per_image, (size_t)c * sizeof(rf_face));
+            if (quality && c) memcpy(align_host_.data() + o_q + (size_t)i * mq * sizeof(rf_face_quality), quality + (size_t)i * max_faces,
+                                     (size_t)std::min(c, mq) * sizeof(rf_face_quality));
+        }
+        const int ns = track_build_table(rq.stream_of_image, 0, n, scale.data(), empty.data(), (TrackStreamEntry *)align_host_.data(),
+                                         (TrackImageEntry *)(align_host_.data() + o_img));
+        uint8_t *d_tab = align_tab_.reserve(total);
+        track_open_call(t, rq, n, cap_per_image);
+        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+        t.dirty = true;
+        RF_HIP(hipMemcpyAsync(d_tab, align_host_.data(), total, hipMemcpyHostToDevice, align_stream_));
+        TrackParams tp = track_params(t);
+        tp.streams = (const TrackStreamEntry *)d_tab; tp.n_streams = ns;
+        tp.images = (const TrackImageEntry *)(d_tab + o_img);
+        tp.faces = d_tab + o_face; tp.face_stride = (int)sizeof(rf_face); tp.faces_per_image = fpi;
+        tp.counts = (const int *)(d_tab + o_cnt);
+        tp.records = quality ? (const rf_face_quality *)(d_tab + o_q) : nullptr;
+        tp.max_faces = mq;
+        if (!trk_ev_[0]) { RF_HIP(hipEventCreate(&trk_ev_[0])); RF_HIP(hipEventCreate(&trk_ev_[1])); }
+        RF_HIP(hipEventRecord(trk_ev_[0], align_stream_));
+        launch_track(align_stream_, tp);
+        RF_HIP(hipGetLastError());
+        RF_HIP(hipEventRecord(trk_ev_[1], align_stream_));
+        RF_HIP(hipStreamSynchronize(align_stream_));
+        if (hipEventElapsedTime(&trk_launch_ms_, trk_ev_[0], trk_ev_[1]) != hipSuccess) trk_launch_ms_ = -1.f;
+        track_copy_out(t, rq, n, cap_per_image, counts, cut);
+    }
+    float track_last_launch_ms() const override { return trk_launch_ms_; }
+
+    void detect_track(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device, float threshold,
+                      rf_face *out, int cap_per_image, int *counts, bool *truncated, const TrackRequest &rq, bool *cut) override {
+        *cut = false;
+        if (n < 0 || (n > 0 && (!frames || !rows || !cols || !counts))) throw ArgError("null argument");
+        if (cap_per_image < 0 || (cap_per_image > 0 && !out)) throw ArgError("out is null");
+        Tracker &t = track_check(rq, n);
+        DeviceGuard guard(device_);
+        // as in detect_align(): a super-batch of earlier enqueues starts now, every later launch carries images of this call only
+        launch_pending();
+        track_open_call(t, rq, n, cap_per_image);
+        trk_.records = nullptr; trk_.max_faces = kTrackMaxFaces;
+        t.dirty = true;
+        trk_.on = n > 0;
+        struct Off { bool &on; ~Off() { on = false; } } off{trk_.on};
+        detect(frames, rows, cols, steps, n, on_device, threshold, out, cap_per_image, counts, truncated);
+        trk_.on = false;
+        // every launch of the call has been waited for (its `done` event follows the track launch)
+        track_copy_out(t, rq, n, cap_per_image, counts, cut);
+    }
+
+    void detect_track_face_batch(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,
+                                 float threshold, rf_face *out, int cap_per_image, int *counts, bool *truncated, const FaceBatchRequest &fb,
+                                 bool *overflow, const TrackRequest &rq, bool *cut) override {
+        *cut = false;
+        check_face_batch_request(fb);
+        if (n < 0 || (n > 0 && (!frames || !rows || !cols || !counts))) throw ArgError("null argument");
+        if (cap_per_image < 0 || (cap_per_image > 0 && !out)) throw ArgError("out is null");
+        if ((long)n * fb.spec.max_faces > (1L << 24)) throw ArgError("n x max_faces: more than 2^24 faces in one call");
+        Tracker &t = track_check(rq, n);
+        DeviceGuard guard(device_);
+        launch_pending();
+        track_open_call(t, rq, n, cap_per_image);
+        if (fb.gated) face_gate_open(fb, n);
+        trk_.records = fb.gated ? (const rf_face_quality *)fq_records_.ptr : nullptr;
+        trk_.max_faces = fb.spec.max_faces;
+        t.dirty = true;
+        trk_.on = n > 0;
+        struct Off { bool &on; ~Off() { on = false; } } off{trk_.on};
+        detect_face_batch(frames, rows, cols, steps, n, on_device, threshold, out, cap_per_image, counts, truncated, fb, overflow);
+        trk_.on = false;
+        track_copy_out(t, rq, n, cap_per_image, counts, cut);
+    }
+
     void host_register(const void *ptr, size_t bytes) override {
         if (!ptr || !bytes) throw ArgError("host_register: null / empty range");
         DeviceGuard guard(device_);
@@ -1017,6 +1173,8 @@ private:
         hipEvent_t face_scan_done = nullptr;  // ... recorded behind that scan: the call's next launch (another lane) waits for it on the device
         TileEntry *h_tile_tab = nullptr;      // detect_tiled(): pinned, per image of the launch the pass it is (allocated on first use)
         hipEvent_t tile_done = nullptr;       // ... recorded behind the launch's gather: the call's merge (another lane) waits for it on the device
+        uint8_t *h_track_tab = nullptr;       // detect_track(): pinned, the launch's stream table and image table (allocated on first use)
+        hipEvent_t track_done = nullptr;      // ... recorded behind the launch's track kernel: the call's next track launch (another lane) waits for it
         bool busy = false;                    // a launched super-batch whose results have not been harvested yet
         int n_images = 0;                     // images of the super-batch being assembled / in flight on this lane
         float threshold = 0.f;
@@ -1059,6 +1217,7 @@ private:
         if (l.copy2_done) (void)hipEventDestroy(l.copy2_done);
         if (l.face_scan_done) (void)hipEventDestroy(l.face_scan_done);
         if (l.tile_done) (void)hipEventDestroy(l.tile_done);
+        if (l.track_done) (void)hipEventDestroy(l.track_done);
         if (l.copy2) { (void)hipStreamSynchronize(l.copy2); (void)hipStreamDestroy(l.copy2); }
         if (l.d_stage) (void)hipFree(l.d_stage);
         if (l.h_stage) (void)hipHostFree(l.h_stage);
@@ -1344,6 +1503,7 @@ private:
         if (align_.on) launch_lane_align(s, n);      // ordinary launches behind the graph, before `done`: nothing waits in between
         if (fb_.on) launch_lane_face_batch(s, n);
         if (tile_.on) launch_lane_tile(s, n);
+        if (trk_.on) launch_lane_track(s, n);
         RF_HIP(hipEventRecord(s.done, s.stream));
         trace_.add(4, tt);
         s.busy = true;
@@ -1467,6 +1627,139 @@ private:
             q.offsets = (int *)fq_offsets_.ptr + base;
             launch_face_seq(st, rq, q, tile_.d_tensor, tile_.d_mats);
         }
+    }
+
+    // The track launch of a super-batch of detect_track(): faces and counts from the pinned result block the NMS kernel of the same
+    // stream has just written (and, for the fused face batch, the quality records its quality kernel has just written), which images
+    // belong to which stream from a pinned per-lane table.  A stream's images may sit in several launches on different lanes, and the
+    // state is one block in device memory, so the track launches of a call form a chain: each waits (on the device: hipStreamWaitEvent)
+    // for the track launch of the call's previous launch and records its own event.  The detection launches in front do not wait and
+    // keep overlapping.  The lane's `done` event follows, so the host's ordinary wait covers it.  No host wait anywhere.
+    void launch_lane_track(Lane &s, int n) {
+        if (!s.h_track_tab) {
+            void *p = nullptr;
+            RF_HIP(hipHostMalloc(&p, std::max<size_t>((size_t)cap_images_ * (sizeof(TrackStreamEntry) + sizeof(TrackImageEntry)), 256), hipHostMallocDefault));
+            s.host_allocs.push_back(p);
+            s.h_track_tab = (uint8_t *)p;
+            RF_HIP(hipEventCreateWithFlags(&s.track_done, hipEventDisableTiming));
+        }
+        if (n > cap_images_ || trk_.next_image + n > trk_.n) throw HipError("face tracks: a launch carries images of another call");
+        std::vector<float> scale(n);
+        std::vector<char> empty(n);
+        for (int i = 0; i < n; i++) {
+            const FrameDesc &f = s.h_frames[i];
+            empty[i] = f.ptr ? 0 : 1;
+            scale[i] = f.ptr ? frame_scale(f.rows, f.cols, net_h_, net_w_) : 1.f;
+        }
+        TrackStreamEntry *se = (TrackStreamEntry *)s.h_track_tab;
+        TrackImageEntry *ie = (TrackImageEntry *)(se + cap_images_);
+        const int ns = track_build_table(trk_.stream_of_image, trk_.next_image, n, scale.data(), empty.data(), se, ie);
+        trk_.next_image += n;
+        if (ns == 0) return;
+        if (trk_.prev && trk_.prev != s.track_done) RF_HIP(hipStreamWaitEvent(s.stream, trk_.prev, 0));
+        TrackParams tp = track_params(*trk_.tr);
+        tp.streams = se; tp.n_streams = ns;
+        tp.images = ie;
+        tp.faces = (const uint8_t *)s.h_out; tp.face_stride = (int)sizeof(Candidate); tp.faces_per_image = opt_.max_detections;
+        tp.counts = s.h_counts;
+        tp.records = trk_.records;
+        tp.max_faces = trk_.max_faces;
+        launch_track(s.stream, tp);
+        RF_HIP(hipGetLastError());
+        RF_HIP(hipEventRecord(s.track_done, s.stream));
+        trk_.prev = s.track_done;
+    }
+
+    // The stream table of images [image0, image0 + n) of a call: the streams present in order of first appearance, each with its
+    // images in call order.  Returns the number of streams present (images of stream -1 appear nowhere).
+    static int track_build_table(const int *stream_of_image, int image0, int n, const float *scale, const char *empty, TrackStreamEntry *se,
+                                 TrackImageEntry *ie) {
+        std::vector<int> order;
+        for (int i = 0; i < n; i++)
+            if (stream_of_image[image0 + i] >= 0) order.push_back(i);
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return stream_of_image[image0 + a] < stream_of_image[image0 + b]; });
+        int ns = 0;
+        for (size_t j = 0; j < order.size(); j++) {
+            const int i = order[j], st = stream_of_image[image0 + i];
+            if (j == 0 || st != se[ns - 1].stream) se[ns++] = TrackStreamEntry{st, (int)j, 0, 0};
+            se[ns - 1].n++;
+            ie[j] = TrackImageEntry{i, image0 + i, scale[i], empty[i]};
+        }
+        return ns;
+    }
+
+    struct Tracker;
+    Tracker &tracker_of(void *p) {
+        for (auto &t : trackers_)
+            if (t.get() == p) return *t;
+        throw ArgError("not a tracker of this handle");
+    }
+    // a stream's (or every stream's) empty state: no tracks, frame counter 0, next id 1
+    void tracker_reset_impl(Tracker &t, int stream) {
+        const size_t sb = t.stream_bytes();
+        const int first = stream < 0 ? 0 : stream, count = stream < 0 ? t.n_streams : 1;
+        std::vector<uint8_t> img((size_t)count * sb, 0);
+        for (int i = 0; i < count; i++) *(TrackHeader *)(img.data() + (size_t)i * sb) = TrackHeader{0, 1};
+        RF_HIP(hipMemcpy(t.state.ptr + (size_t)first * sb, img.data(), img.size(), hipMemcpyHostToDevice));
+    }
+    // the arguments of a tracked call, checked before any state changes
+    Tracker &track_check(const TrackRequest &rq, int n) {
+        Tracker &t = tracker_of(rq.tracker);
+        if (t.dirty) throw ArgError("the tracker's last call failed: reset it first");
+        if (n > 0 && !rq.stream_of_image) throw ArgError("stream_of_image is null");
+        if (rq.cap_ended < 0 || (rq.cap_ended > 0 && !rq.ended)) throw ArgError("ended is null");
+        if ((long)n * std::max(rq.cap_ended, 1) > (1L << 24)) throw ArgError("n x cap_ended: more than 2^24 records in one call");
+        for (int i = 0; i < n; i++)
+            if (rq.stream_of_image[i] < -1 || rq.stream_of_image[i] >= t.n_streams) throw ArgError("stream_of_image: stream out of range");
+        return t;
+    }
+    // call-level result blocks (pinned host memory): tags (tag_stride per image), ended lists, ended counts | status
+    void track_open_call(Tracker &t, const TrackRequest &rq, int n, int cap_per_image) {
+        trk_.tr = &t;
+        trk_.stream_of_image = rq.stream_of_image;
+        trk_.n = n; trk_.next_image = 0; trk_.prev = nullptr;
+        trk_.tag_stride = std::max(0, std::min(cap_per_image, kTrackMaxFaces));
+        trk_.cap_ended = rq.cap_ended;
+        trk_tags_.reserve((size_t)std::max(n, 1) * std::max(trk_.tag_stride, 1) * sizeof(rf_track_tag));
+        trk_ended_.reserve((size_t)std::max(n, 1) * std::max(rq.cap_ended, 1) * sizeof(rf_track));
+        trk_counts_.reserve((size_t)std::max(n, 1) * 2 * sizeof(int));
+    }
+    TrackParams track_params(const Tracker &t) const {
+        TrackParams tp;
+        memset(&tp, 0, sizeof(tp));
+        tp.spec = t.spec;
+        tp.state = t.state.ptr;
+        tp.tags = (rf_track_tag *)trk_tags_.ptr; tp.tag_stride = trk_.tag_stride;
+        tp.ended = (rf_track *)trk_ended_.ptr; tp.cap_ended = trk_.cap_ended;
+        tp.ended_counts = (int *)trk_counts_.ptr;
+        tp.status = (int *)trk_counts_.ptr + std::max(trk_.n, 1);
+        return tp;
+    }
+    // Results of a finished tracked call, from the pinned blocks the kernel wrote; the host fills what the device never writes -- the
+    // images of stream -1, the tags at or beyond the image's count and whatever lies behind an ended list.
+    void track_copy_out(Tracker &t, const TrackRequest &rq, int n, int cap_per_image, const int *counts, bool *cut) {
+        const int ts = trk_.tag_stride;
+        const int *cs = (const int *)trk_counts_.ptr;
+        const rf_track_tag *tags = (const rf_track_tag *)trk_tags_.ptr;
+        const rf_track *ended = (const rf_track *)trk_ended_.ptr;
+        for (int i = 0; i < n; i++) {
+            const bool tracked = rq.stream_of_image[i] >= 0;
+            const int ec = tracked ? cs[i] : 0;
+            if (rq.ended_counts) rq.ended_counts[i] = ec;
+            if (ec > rq.cap_ended || (tracked && cs[n + i])) *cut = true;
+            if (rq.ended && rq.cap_ended > 0) {
+                const int have = std::min(ec, rq.cap_ended);
+                rf_track *dst = rq.ended + (size_t)i * rq.cap_ended;
+                if (have) memcpy((void *)dst, ended + (size_t)i * rq.cap_ended, (size_t)have * sizeof(rf_track));
+                memset((void *)(dst + have), 0, (size_t)(rq.cap_ended - have) * sizeof(rf_track));
+            }
+            if (!rq.tags) continue;
+            rf_track_tag *dst = rq.tags + (size_t)i * cap_per_image;
+            const int have = tracked ? std::max(0, std::min(std::min(counts[i], ts), cap_per_image)) : 0;      // what the kernel wrote
+            if (have) memcpy((void *)dst, tags + (size_t)i * ts, (size_t)have * sizeof(rf_track_tag));
+            for (int k = have; k < cap_per_image; k++) dst[k] = tracked && k < counts[i] ? track_tag_untracked(0) : track_tag_zero();
+        }
+        t.dirty = false;
     }
 
     // results of an alignment call to the caller's host buffers: per image the slots that hold faces (the others are unspecified)
@@ -1727,6 +2020,36 @@ private:
     std::vector<FrameDesc> tile_fd_;
     struct { bool on = false; TileRequest rq; std::vector<TileEntry> entries; int n_frames = 0, next_pass = 0; std::vector<int> lanes_used;
              uint8_t *d_tensor = nullptr; double *d_mats = nullptr; } tile_;
+
+    // face tracks: the trackers of this handle, the call-level result buffers and the request a tracked call has open
+    struct Tracker {
+        TrackSpec spec;
+        int n_streams = 0;
+        DeviceScratch state;                  // n_streams x (TrackHeader + max_tracks records)
+        bool dirty = false;                   // a call on it ended in an error: refused until it is reset
+        size_t stream_bytes() const { return sizeof(TrackHeader) + (size_t)spec.max_tracks * sizeof(rf_track); }
+    };
+    std::vector<std::unique_ptr<Tracker>> trackers_;
+    // (pinned host memory the kernel writes straight into, as the NMS kernel writes its result block: no copy after the call)
+    struct HostScratch {
+        uint8_t *ptr = nullptr; size_t cap = 0;
+        uint8_t *reserve(size_t bytes) {
+            if (bytes > cap) {
+                if (ptr) (void)hipHostFree(ptr);
+                ptr = nullptr; cap = 0;
+                const size_t want = (std::max<size_t>(bytes, 4096) + 4095) / 4096 * 4096;
+                RF_HIP(hipHostMalloc((void **)&ptr, want, hipHostMallocDefault));
+                cap = want;
+            }
+            return ptr;
+        }
+        void release() { if (ptr) (void)hipHostFree(ptr); ptr = nullptr; cap = 0; }
+    };
+    HostScratch trk_tags_, trk_ended_, trk_counts_;
+    hipEvent_t trk_ev_[2] = {nullptr, nullptr};   // around the track launch of track_update() (tools/track_bench.py reads the time)
+    float trk_launch_ms_ = -1.f;
+    struct { bool on = false; Tracker *tr = nullptr; const int *stream_of_image = nullptr; int n = 0, next_image = 0, tag_stride = 0, cap_ended = 0,
+             max_faces = 0; const rf_face_quality *records = nullptr; hipEvent_t prev = nullptr; } trk_;
 
     int last_n_ = 0;
     std::vector<int> last_cand_counts_;

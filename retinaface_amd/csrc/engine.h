@@ -102,6 +102,17 @@ struct TileRequest {
     const FaceBatchRequest *fb = nullptr;
 };
 
+// A tracked call (track.h; rf_track_update_device / rf_detect_track_*): the tracker (what tracker_create returned), the stream of every
+// image (-1 = not tracked) and where tags, ended lists and their counts go (host; each may be nullptr)
+struct TrackRequest {
+    void *tracker = nullptr;
+    const int *stream_of_image = nullptr;
+    rf_track_tag *tags = nullptr;               // n * cap_per_image
+    rf_track *ended = nullptr;                  // n * cap_ended
+    int cap_ended = 0;
+    int *ended_counts = nullptr;                // n
+};
+
 class Engine {
 public:
     // opt.devices.size() > 1 gives the image-sharding multi-device engine (multi.cpp), otherwise one single-device engine
@@ -152,6 +163,34 @@ public:
     virtual void tile_merge(const int *, const int *, int, const TileRequest &, const rf_face *, const int *, rf_face *, int, int *,
                             bool *) {
         throw Unsupported("tiled detection is not available on a multi-device handle");
+    }
+    // Face tracks: a tracker's state (n_streams tables) lives in device memory between calls; the track launch of a detection launch
+    // follows it on its stream, the track launches of a call wait for each other on the device.  *cut: a full table or a cut ended
+    // list.  Single-device engines only.
+    virtual void *tracker_create(const TrackSpec &, int /*n_streams*/) { throw Unsupported("face tracks are not available on a multi-device handle"); }
+    virtual void tracker_destroy(void *) {}
+    virtual void tracker_reset(void *, int /*stream*/) { throw Unsupported("face tracks are not available on a multi-device handle"); }
+    // host copy of a stream's table, frame counter and next id; flush: end its live tracks (returned instead of the table).  Returns
+    // max_tracks, or the number of tracks ended.
+    virtual int tracker_read(void *, int /*stream*/, rf_track *, int /*cap*/, int64_t *, int64_t *, bool /*flush*/) {
+        throw Unsupported("face tracks are not available on a multi-device handle");
+    }
+    // frame steps over faces the caller supplies (host memory)
+    virtual void track_update(const TrackRequest &, int /*n*/, const rf_face *, int /*cap_per_image*/, const int * /*counts*/,
+                              const float * /*coord_scale*/, const rf_face_quality *, int /*max_faces*/, bool * /*cut*/) {
+        throw Unsupported("face tracks are not available on a multi-device handle");
+    }
+    // hipEvent time of the track launch of the most recent track_update() (negative: none yet)
+    virtual float track_last_launch_ms() const { return -1.f; }
+    // detect() + the frame step of every image
+    virtual void detect_track(const uint8_t *const *, const int *, const int *, const int *, int, bool, float, rf_face *, int, int *, bool *,
+                              const TrackRequest &, bool * /*cut*/) {
+        throw Unsupported("face tracks are not available on a multi-device handle");
+    }
+    // detect_face_batch() + the frame steps, which read the call's quality records when the request is gated
+    virtual void detect_track_face_batch(const uint8_t *const *, const int *, const int *, const int *, int, bool, float, rf_face *, int,
+                                         int *, bool *, const FaceBatchRequest &, bool * /*overflow*/, const TrackRequest &, bool * /*cut*/) {
+        throw Unsupported("face tracks are not available on a multi-device handle");
     }
     int default_max_faces() const { return opt_.max_detections; }
     // asynchronous: frames on host (staged through pinned memory before the call returns, unless the caller registered

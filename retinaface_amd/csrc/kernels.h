@@ -11,6 +11,7 @@
 #include "face_batch.h"
 #include "face_quality.h"
 #include "tile.h"
+#include "track.h"
 
 namespace rf {
 
@@ -271,6 +272,33 @@ struct TileGatherParams {
     int cap;                              // counting past cap (the merge reports it), records at or beyond cap are not written
 };
 void launch_tile_gather(hipStream_t s, const TileGatherParams &p);
+
+// ---- K_j: face tracks (track.h) -- the frame steps of a launch's images: one workgroup per stream present in the launch walks that
+//      stream's images in order, its table in LDS, one thread per slot.  Every pointer is device-visible memory (the fused calls read
+//      faces and counts from the pinned result block the NMS kernel wrote, and the two tables below from pinned memory).
+struct TrackStreamEntry { int32_t stream, first, n, pad_; };          // images[first .. first + n) are this stream's, in call order
+struct TrackImageEntry {
+    int32_t local;                        // index of the image among the launch's faces / counts
+    int32_t image;                        // index of the image in the call (tags, ended lists, quality records)
+    float scale;                          // coord_scale
+    int32_t empty;                        // != 0: a frame without pixels, it has no faces whatever counts says
+};
+struct TrackParams {
+    const TrackStreamEntry *streams; int n_streams;      // the grid
+    const TrackImageEntry *images;
+    const uint8_t *faces;                 // image i, face k: 15 floats at faces + (i * faces_per_image + k) * face_stride
+    int face_stride, faces_per_image;
+    const int *counts;                    // [launch images]
+    const rf_face_quality *records;       // call image c, face k at records[c * max_faces + k], or nullptr: best shots by score
+    int max_faces;                        // m = min(count, faces_per_image, max_faces, kTrackMaxFaces)
+    TrackSpec spec;
+    uint8_t *state;                       // stream s: TrackHeader + max_tracks rf_track at s * (16 + max_tracks * 176)
+    rf_track_tag *tags; int tag_stride;   // call image c, face k < min(count, tag_stride) at tags[c * tag_stride + k]
+    rf_track *ended; int cap_ended;       // call image c: ended[c * cap_ended + j]
+    int *ended_counts;                    // [call images] the true number
+    int *status;                          // [call images] kTrackOverflow or 0
+};
+void launch_track(hipStream_t s, const TrackParams &p);
 
 // LDS bytes / tile geometry chosen for a layer (exposed for tests and DESIGN.md tables)
 struct TileInfo { int th, tw; size_t lds_bytes; int blocks_per_image; };

@@ -4525,6 +4525,177 @@ void launch_tile_gather(hipStream_t s, const TileGatherParams &p) {
     hipLaunchKernelGGL(tile_gather_kernel, dim3(p.n), dim3(kThreads), 0, s, p);
 }
 
+// =============================================================================================
+// K_j: face tracks (track.h).  track_kernel: one workgroup per stream present in the launch, one thread per slot (64 threads per 64
+//      slots).  The stream's table is loaded into LDS once, the stream's images of the launch are stepped in order, the table is written
+//      back once.  Match: every thread keeps its track's last box in registers, face k is broadcast from LDS, each thread forms the
+//      64-bit key of track_match_key and ONE max-reduction (wave64 shuffles, then LDS across wavefronts, double-buffered: one barrier
+//      per face; none at all when the table fits one wavefront) names the winner, which updates its own record.  Ended-list positions,
+//      free-slot ranks and the ranks of the faces that open tracks are prefix counts by ballot + popcount (the gather kernel's idiom),
+//      so slot order and score order come out without atomics.  Every loop is bounded by 256 faces, 256 slots and the launch's images.
+// =============================================================================================
+__device__ inline unsigned long long track_wave_max(unsigned long long v) {
+    for (int d = 32; d >= 1; d >>= 1) {
+        const unsigned long long o = __shfl_xor(v, d, 64);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+// exclusive prefix count of `flag` over the workgroup's threads in thread order, and the total; every thread calls it
+__device__ inline int track_prefix_count(bool flag, int nw, int *s_cnt, int *total) {
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const unsigned long long mask = __ballot(flag);
+    int pos = __popcll(mask & ((1ull << lane) - 1ull));
+    if (nw == 1) { *total = __popcll(mask); return pos; }
+    __syncthreads();                                             // the readers of the previous count are done
+    if (lane == 0) s_cnt[wave] = __popcll(mask);
+    __syncthreads();
+    int t = 0;
+    for (int w = 0; w < nw; w++) { const int c = s_cnt[w]; if (w < wave) pos += c; t += c; }
+    *total = t;
+    return pos;
+}
+
+__global__ __launch_bounds__(kThreads) void track_kernel(TrackParams a) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    rf_track *s_trk = (rf_track *)smem;                          // [max_tracks]
+    __shared__ float s_face[kTrackMaxFaces][15];                 // the image's mapped faces
+    __shared__ short s_fslot[kTrackMaxFaces];                    // the slot face k matched, -1 = none
+    __shared__ short s_new[kTrackMaxFaces];                      // the faces that open tracks, in score order
+    __shared__ unsigned long long s_key[2][kThreads / 64];
+    __shared__ int s_cnt[kThreads / 64];
+    constexpr int kWords = (int)(sizeof(rf_track) / 4);
+
+    const int tid = (int)threadIdx.x, nthr = (int)blockDim.x, nw = nthr >> 6, lane = tid & 63, wave = tid >> 6;
+    const TrackStreamEntry se = a.streams[blockIdx.x];
+    const TrackSpec sp = a.spec;
+    const int T = sp.max_tracks;
+    uint8_t *st = a.state + (size_t)se.stream * (sizeof(TrackHeader) + (size_t)T * sizeof(rf_track));
+    TrackHeader *hdr = (TrackHeader *)st;
+    uint32_t *g_trk = (uint32_t *)(st + sizeof(TrackHeader));
+    for (int i = tid; i < T * kWords; i += nthr) ((uint32_t *)s_trk)[i] = g_trk[i];
+    long long f = hdr->frames, next_id = hdr->next_id;
+    __syncthreads();
+    const bool has_slot = tid < T;
+    bool live = has_slot && s_trk[has_slot ? tid : 0].id != 0;
+    float box[4] = {0.f, 0.f, 0.f, 0.f};
+    if (live) { box[0] = s_trk[tid].last.x1; box[1] = s_trk[tid].last.y1; box[2] = s_trk[tid].last.x2; box[3] = s_trk[tid].last.y2; }
+
+    for (int ii = 0; ii < se.n; ii++) {
+        const TrackImageEntry im = a.images[se.first + ii];
+        int count = im.empty ? 0 : a.counts[im.local];
+        if (count < 0) count = 0;
+        int m = count < a.faces_per_image ? count : a.faces_per_image;
+        if (m > a.max_faces) m = a.max_faces;
+        if (m > kTrackMaxFaces) m = kTrackMaxFaces;
+        const uint8_t *src = a.faces + (size_t)im.local * a.faces_per_image * a.face_stride;
+        __syncthreads();                                         // the previous image's readers of s_face / s_fslot / s_new are done
+        for (int i = tid; i < m * 15; i += nthr) {
+            const int k = i / 15, j = i - k * 15;
+            const float v = ((const float *)(src + (size_t)k * a.face_stride))[j];
+            s_face[k][j] = j ? v * im.scale : v;                 // track_map_face
+        }
+        __syncthreads();
+        rf_track_tag *tags = a.tags + (size_t)im.image * a.tag_stride;
+        const rf_face_quality *rec = a.records ? a.records + (size_t)im.image * a.max_faces : nullptr;
+
+        // match
+        bool claimed = false;
+        for (int k = 0; k < m; k++) {
+            const float *fk = s_face[k];
+            const bool avail = live && !claimed;
+            const float iou = avail ? track_iou(fk + 1, box) : 0.f;
+            unsigned long long key = track_wave_max(track_match_key(avail, iou, sp.min_iou, tid));
+            if (nw > 1) {
+                if (lane == 0) s_key[k & 1][wave] = key;
+                __syncthreads();
+                for (int w = 0; w < nw; w++) { const unsigned long long o = s_key[k & 1][w]; key = o > key ? o : key; }
+            }
+            const int win = key ? track_key_slot(key) : -1;
+            if (tid == 0) s_fslot[k] = (short)win;
+            if (tid == win) {
+                claimed = true;
+                rf_track *t = &s_trk[tid];
+                track_match_update(t, fk, f, sp.min_hits);
+                box[0] = fk[1]; box[1] = fk[2]; box[2] = fk[3]; box[3] = fk[4];
+                const int b = track_best_update(t, fk, f, rec ? rec + k : nullptr);
+                if (k < a.tag_stride) tags[k] = track_tag(t, tid, f, sp.min_hits, b);
+            }
+        }
+        __syncthreads();
+
+        // age: the ended tracks leave in slot order
+        bool ends = false;
+        if (live && !claimed) ends = track_age(&s_trk[tid], sp.max_missed);
+        int n_ended = 0;
+        const int epos = track_prefix_count(ends, nw, s_cnt, &n_ended);
+        if (ends) {
+            uint32_t *rec32 = (uint32_t *)&s_trk[tid];
+            if (epos < a.cap_ended) {
+                uint32_t *dst = (uint32_t *)(a.ended + (size_t)im.image * a.cap_ended + epos);
+                for (int i = 0; i < kWords; i++) dst[i] = rec32[i];
+            }
+            for (int i = 0; i < kWords; i++) rec32[i] = 0u;
+            live = false;
+        }
+
+        // open: the j-th face that wants a track takes the j-th free slot
+        int n_new = 0;
+        for (int k0 = 0; k0 < m; k0 += nthr) {
+            const int k = k0 + tid;
+            bool wants = false;
+            if (k < m && s_fslot[k] < 0) {
+                if (s_face[k][0] >= sp.new_score) wants = true;
+                else if (k < a.tag_stride) tags[k] = track_tag_untracked(0);
+            }
+            int tot = 0;
+            const int pos = track_prefix_count(wants, nw, s_cnt, &tot);
+            if (wants) s_new[n_new + pos] = (short)k;
+            n_new += tot;
+        }
+        const bool is_free = has_slot && !live;
+        int n_free = 0;
+        const int fpos = track_prefix_count(is_free, nw, s_cnt, &n_free);
+        __syncthreads();                                         // s_new is complete
+        const int n_open = n_new < n_free ? n_new : n_free;
+        if (is_free && fpos < n_open) {
+            const int k = s_new[fpos];
+            const float *fk = s_face[k];
+            rf_track *t = &s_trk[tid];
+            track_open(t, next_id + fpos, fk, f, sp.min_hits);
+            box[0] = fk[1]; box[1] = fk[2]; box[2] = fk[3]; box[3] = fk[4];
+            live = true;
+            const int b = track_best_update(t, fk, f, rec ? rec + k : nullptr);
+            if (k < a.tag_stride) tags[k] = track_tag(t, tid, f, sp.min_hits, RF_TRACK_NEW | b);
+        }
+        for (int j = n_open + tid; j < n_new; j += nthr) {
+            const int k = s_new[j];
+            if (k < a.tag_stride) tags[k] = track_tag_untracked(RF_TRACK_OVERFLOW);
+        }
+        const int n_tags = count < a.tag_stride ? count : a.tag_stride;            // the host fills the tags behind the image's count
+        for (int k = m + tid; k < n_tags; k += nthr) tags[k] = track_tag_untracked(0);
+        if (tid == 0) {
+            a.ended_counts[im.image] = n_ended;
+            a.status[im.image] = n_new > n_free ? kTrackOverflow : 0;
+        }
+        next_id += n_open;
+        f += 1;
+    }
+    __syncthreads();
+    for (int i = tid; i < T * kWords; i += nthr) g_trk[i] = ((const uint32_t *)s_trk)[i];
+    if (tid == 0) { hdr->frames = f; hdr->next_id = next_id; }
+}
+
+void launch_track(hipStream_t s, const TrackParams &p) {
+    if (p.n_streams <= 0) return;
+    const int T = p.spec.max_tracks;
+    if (T < 1 || T > kTrackMaxTracks) throw LaunchUnsupported("track: max_tracks must be in [1, 256]");
+    const int threads = (T + 63) / 64 * 64;
+    hipLaunchKernelGGL(track_kernel, dim3(p.n_streams), dim3(threads), (size_t)T * sizeof(rf_track), s, p);
+}
+
 #ifdef RF_KERNEL_TRACE
 extern "C" int rf_trace_select(int kernel_id, unsigned grid) {
     static unsigned long long zeros[kTraceBlocks * kTraceSlots];

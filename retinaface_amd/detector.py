@@ -14,7 +14,8 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import rf_face, rf_face_batch_spec, rf_face_gate, rf_face_quality, rf_options, rf_tile_spec
+from ._lib import (rf_face, rf_face_batch_spec, rf_face_gate, rf_face_quality, rf_options, rf_tile_spec, rf_track, rf_track_spec,
+                   rf_track_tag)
 
 PRECISION_FP32, PRECISION_FP16, PRECISION_INT8 = 0, 1, 2
 
@@ -35,6 +36,8 @@ class Detection:
 def _face_rows(faces) -> np.ndarray:
     """(k, 15) float32 rows from an array, a list of rows or a list of Detection."""
     if isinstance(faces, np.ndarray):
+        if faces.dtype.names:                          # rf_face records (FACE_DTYPE)
+            return np.ascontiguousarray(faces).view(np.float32).reshape(-1, 15)
         return np.ascontiguousarray(faces, np.float32).reshape(-1, 15)
     rows = [f.as_row() if isinstance(f, Detection) else np.asarray(f, np.float32) for f in faces]
     return np.stack(rows).astype(np.float32).reshape(-1, 15) if rows else np.zeros((0, 15), np.float32)
@@ -199,6 +202,123 @@ def tile_map_face(face, t: int, rows: int, cols: int, net_h: int, net_w: int, ov
     if st < 0:
         raise _lib.RFError(st, "rf_tile_map_face: bad spec, frame, net size or pass index")
     return _faces_to_array(C.pointer(g), 1)[0] if st else None
+
+
+FACE_DTYPE = np.dtype([("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4"), ("px", "<f4", 5), ("py", "<f4", 5)])
+TRACK_DTYPE = np.dtype([("id", "<i8"), ("first_frame", "<i8"), ("last_frame", "<i8"), ("best_frame", "<i8"), ("best_value", "<f8"),
+                        ("hits", "<i4"), ("missed", "<i4"), ("flags", "<i4"), ("reserved", "<i4"), ("last", FACE_DTYPE), ("best", FACE_DTYPE)])
+TRACK_TAG_DTYPE = np.dtype([("id", "<i8"), ("slot", "<i4"), ("hits", "<i4"), ("age", "<i4"), ("flags", "<i4")])
+TRACK_NEW, TRACK_CONFIRMED, TRACK_BEST, TRACK_UNTRACKED, TRACK_OVERFLOW = 1, 2, 4, 8, 16
+
+
+def track_spec(max_tracks: int = 0, min_iou: float = 0.0, max_missed: int = 0, min_hits: int = 0, new_score: float = 0.0) -> rf_track_spec:
+    """rf_track_spec; 0 = the default (64 slots, IoU 0.3, 10 missed frames, 3 hits, every face opens a track)"""
+    s = rf_track_spec()
+    s.struct_size = C.sizeof(rf_track_spec)
+    s.max_tracks, s.min_iou, s.max_missed, s.min_hits, s.new_score = int(max_tracks), float(min_iou), int(max_missed), int(min_hits), float(new_score)
+    return s
+
+
+def track_step(table: np.ndarray, frames: int, next_id: int, faces, coord_scale: float = 1.0, quality=None, max_faces: int = 256,
+               cap_ended: Optional[int] = None, **spec):
+    """rf_track_step (host only, no GPU): one frame step on a caller-held table (TRACK_DTYPE records, updated in place).  Returns
+    (tags, ended, frames, next_id, truncated); keywords as track_spec()."""
+    lib = _lib.load_library()
+    sp = track_spec(**spec)
+    rows = _face_rows(faces)
+    count = len(rows)
+    cap_ended = len(table) if cap_ended is None else int(cap_ended)
+    tags = np.zeros(max(count, 1), TRACK_TAG_DTYPE)
+    ended = np.zeros(max(cap_ended, 1), TRACK_DTYPE)
+    f, nid, ne = C.c_int64(frames), C.c_int64(next_id), C.c_int(0)
+    q = np.ascontiguousarray(quality, QUALITY_DTYPE) if quality is not None else None
+    st = lib.rf_track_step(C.byref(sp), table.ctypes.data_as(C.POINTER(rf_track)), C.byref(f), C.byref(nid),
+                           rows.ctypes.data_as(C.POINTER(rf_face)), count, float(coord_scale),
+                           q.ctypes.data_as(C.POINTER(rf_face_quality)) if q is not None else None, int(max_faces),
+                           tags.ctypes.data_as(C.POINTER(rf_track_tag)), ended.ctypes.data_as(C.POINTER(rf_track)), cap_ended, C.byref(ne))
+    if st < 0 and st != _lib.RF_ERR_TRUNCATED:
+        raise _lib.RFError(st, "rf_track_step: bad spec or argument")
+    return tags[:count], ended[:min(ne.value, cap_ended)], f.value, nid.value, st == _lib.RF_ERR_TRUNCATED
+
+
+class Tracker:
+    """rf_tracker: per-stream track tables that live in device memory between calls (RetinaFace.tracker() creates one).  After every
+    tracked call last_tags ((n, cap) TRACK_TAG_DTYPE), last_ended ((n, cap_ended) TRACK_DTYPE) and last_ended_counts hold the call's
+    whole buffers and truncated says whether a table was full or an ended list was cut."""
+
+    def __init__(self, det: "RetinaFace", n_streams: int, **spec):
+        self._det, self._lib = det, det._lib
+        self.spec = track_spec(**spec)
+        self.max_tracks = self.spec.max_tracks or 64
+        self.n_streams = int(n_streams)
+        t = C.c_void_p()
+        _lib.check(self._lib.rf_tracker_create(det._h, C.byref(self.spec), self.n_streams, C.byref(t)), det._h)
+        self._t = t
+        self.truncated = False
+        self.last_tags = self.last_ended = self.last_ended_counts = None
+
+    def close(self):
+        if getattr(self, "_t", None) and getattr(self._det, "_h", None):
+            self._lib.rf_tracker_destroy(self._t)
+        self._t = None
+
+    def _buffers(self, n, cap, cap_ended):
+        cap_ended = self.max_tracks if cap_ended is None else int(cap_ended)
+        self.last_tags = np.full((max(n, 1), max(cap, 1)), 0x55, np.uint8).repeat(24, 1).view(TRACK_TAG_DTYPE)
+        self.last_ended = np.zeros((max(n, 1), max(cap_ended, 1)), TRACK_DTYPE)
+        self.last_ended_counts = np.zeros(max(n, 1), np.int32)
+        return (self._t, None, self.last_tags.ctypes.data_as(C.POINTER(rf_track_tag)), self.last_ended.ctypes.data_as(C.POINTER(rf_track)),
+                cap_ended, self.last_ended_counts.ctypes.data_as(C.POINTER(C.c_int)))
+
+    def _results(self, n, counts, cap):
+        tags = [self.last_tags[i, :min(int(counts[i]), cap)].copy() for i in range(n)]
+        ended = [self.last_ended[i, :min(int(self.last_ended_counts[i]), self.last_ended.shape[1])].copy() for i in range(n)]
+        return tags, ended
+
+    def update(self, streams: Sequence[int], faces, *, coord_scale: Optional[Sequence[float]] = None, quality=None,
+               max_faces: Optional[int] = None, cap_per_image: Optional[int] = None, cap_ended: Optional[int] = None):
+        """rf_track_update_device: frame steps over faces the caller supplies -- faces[i]: the faces of image i in score order (a
+        (k, 15) array, rows or Detections), streams[i]: its stream or -1; quality[i]: None or its QUALITY_DTYPE records.  Returns
+        (tags per image, ended tracks per image)."""
+        n = len(streams)
+        per = [_face_rows(f) for f in faces]
+        mf = int(max_faces) if max_faces else self._det.max_detections
+        cap = int(cap_per_image) if cap_per_image is not None else max([len(r) for r in per] + [1])
+        flat = np.zeros((max(n, 1), cap, 15), np.float32)
+        counts = (C.c_int * max(n, 1))()
+        for i, r in enumerate(per):
+            flat[i, :min(len(r), cap)] = r[:cap]
+            counts[i] = len(r)
+        q = None
+        if quality is not None:
+            q = np.zeros((max(n, 1), mf), QUALITY_DTYPE)
+            for i, rec in enumerate(quality):
+                if rec is not None and len(rec):
+                    q[i, :min(len(rec), mf)] = np.asarray(rec, QUALITY_DTYPE)[:mf]
+        cs = (C.c_float * max(n, 1))(*coord_scale) if coord_scale is not None else None
+        t, _, tags, ended, ce, ec = self._buffers(n, cap, cap_ended)
+        st = _lib.check(self._lib.rf_track_update_device(self._det._h, t, (C.c_int * max(n, 1))(*streams), n, flat.ctypes.data_as(C.POINTER(rf_face)),
+                                                         cap, counts, cs, q.ctypes.data_as(C.POINTER(rf_face_quality)) if q is not None else None,
+                                                         mf, tags, ended, ce, ec), self._det._h)
+        self.truncated = st == _lib.RF_ERR_TRUNCATED
+        return self._results(n, counts, cap)
+
+    def read(self, stream: int):
+        """rf_tracker_read: (table, frames, next_id) of a stream"""
+        table = np.zeros(self.max_tracks, TRACK_DTYPE)
+        f, nid = C.c_int64(), C.c_int64()
+        _lib.check(self._lib.rf_tracker_read(self._t, int(stream), table.ctypes.data_as(C.POINTER(rf_track)), len(table), C.byref(f), C.byref(nid)),
+                   self._det._h)
+        return table, f.value, nid.value
+
+    def flush(self, stream: int) -> np.ndarray:
+        """rf_tracker_flush: ends every live track of the stream and returns them slot-ascending"""
+        ended = np.zeros(self.max_tracks, TRACK_DTYPE)
+        k = _lib.check(self._lib.rf_tracker_flush(self._t, int(stream), ended.ctypes.data_as(C.POINTER(rf_track)), len(ended), None, None), self._det._h)
+        return ended[:k]
+
+    def reset(self, stream: int = -1) -> None:
+        _lib.check(self._lib.rf_tracker_reset(self._t, int(stream)), self._det._h)
 
 
 def _faces_to_array(buf, n: int) -> np.ndarray:
@@ -653,6 +773,76 @@ class RetinaFace:
         if len(res) == 4:
             res = res[:3] + ([res[3][i, :min(counts[i], res[3].shape[1], cap)] for i in range(n)],)
         return (self._collect_tiled(out, counts, src, n, cap, False),) + res
+
+    # ------------------------------------------------------------------ face tracks
+    def tracker(self, n_streams: int = 1, **spec) -> Tracker:
+        """rf_tracker_create: a tracker on this handle; keywords as track_spec()"""
+        return Tracker(self, n_streams, **spec)
+
+    def _run_tracked(self, fn, ptrs, rows, cols, steps, n, threshold, tracker, streams, cap_ended):
+        cap = self.max_detections
+        out = (rf_face * max(n * cap, 1))()
+        counts = (C.c_int * max(n, 1))()
+        t, _, tags, ended, ce, ec = tracker._buffers(n, cap, cap_ended)
+        st = _lib.check(fn(self._h, ptrs, rows, cols, steps, n, float(threshold), out, cap, counts, t, (C.c_int * max(n, 1))(*streams),
+                           tags, ended, ce, ec), self._h)
+        self.truncated = tracker.truncated = st == _lib.RF_ERR_TRUNCATED
+        self.last_out = _faces_to_array(out, max(n * cap, 1)).reshape(max(n, 1), cap, 15)
+        self.last_counts = [int(counts[i]) for i in range(n)]
+        return (self._collect(out, counts, n, cap),) + tracker._results(n, counts, cap)
+
+    def detect_tracked(self, imgs: Sequence[np.ndarray], tracker: Tracker, streams: Sequence[int], threshold: float = 0.5,
+                       cap_ended: Optional[int] = None):
+        """rf_detect_track_batch: detectBatchImages + the frame step of every image (streams[i]: its stream, -1 = not tracked).
+        Returns (detections, tags per image, ended tracks per image); tracks live in source-frame pixels."""
+        n = len(imgs)
+        ptrs = (C.c_void_p * max(n, 1))()
+        rows, cols, steps = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
+        keep = []
+        for i, im in enumerate(imgs):
+            if im is None or im.size == 0:
+                ptrs[i], rows[i], cols[i], steps[i] = None, 0, 0, 0
+                continue
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
+            if im.strides[2] != 1 or im.strides[1] != 3:
+                im = np.ascontiguousarray(im)
+            keep.append(im)
+            ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
+        return self._run_tracked(self._lib.rf_detect_track_batch, ptrs, rows, cols, steps, n, threshold, tracker, streams, cap_ended)
+
+    def detect_tracked_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], tracker: Tracker, streams: Sequence[int],
+                              threshold: float = 0.5, steps: Optional[Sequence[int]] = None, cap_ended: Optional[int] = None):
+        """rf_detect_track_batch_device: detect_tracked for frames resident in device memory (a 0 pointer is a frame with no faces)."""
+        n = len(ptrs)
+        p = (C.c_void_p * max(n, 1))(*ptrs)
+        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
+        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        return self._run_tracked(self._lib.rf_detect_track_batch_device, p, r, c, s, n, threshold, tracker, streams, cap_ended)
+
+    def detect_track_face_batch_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], tracker: Tracker,
+                                       streams: Sequence[int], threshold: float = 0.5, steps: Optional[Sequence[int]] = None,
+                                       cap_ended: Optional[int] = None, **kw):
+        """rf_detect_track_face_batch_device: detect_face_batch_device + the frame steps; with gate= / return_quality= the best shots go
+        by sharpness.  Returns (detections, tensor, matrices, offsets[, quality], tags, ended)."""
+        n = len(ptrs)
+        p = (C.c_void_p * max(n, 1))(*ptrs)
+        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
+        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        cap = self.max_detections
+        out = (rf_face * max(n * cap, 1))()
+        counts = (C.c_int * max(n, 1))()
+        t, _, tags, ended, ce, ec = tracker._buffers(n, cap, cap_ended)
+        sv = (C.c_int * max(n, 1))(*streams)
+
+        def call(h, spec, d_out, tensor, mats, offsets, gate=None, quality=None):
+            return self._lib.rf_detect_track_face_batch_device(h, p, r, c, s, n, float(threshold), out, cap, counts, spec, d_out, tensor, mats,
+                                                               offsets, gate, quality, t, sv, tags, ended, ce, ec)
+        res = self._face_batch_call(call, n, **kw)
+        tracker.truncated = self.truncated
+        if len(res) == 4:
+            res = res[:3] + ([res[3][i, :min(counts[i], res[3].shape[1], cap)] for i in range(n)],)
+        return (self._collect(out, counts, n, cap),) + res + tracker._results(n, counts, cap)
 
     def enqueue_device(self, ptrs, rows, cols, threshold: float = 0.5) -> int:
         n = len(ptrs)
