@@ -105,6 +105,12 @@ public:
     const vector<vector<rf_track_tag>> &lastTrackTags() const { return trackTags_; }
     const vector<vector<rf_track>> &lastEndedTracks() const { return trackEnded_; }
 
+    /* additive: face redaction (rf_detect_redact_batch): detectBatchImages() plus redaction of the faces it finds, IN PLACE in the Mats'
+       pixels (pixelate or fill, rectangle or ellipse: rf_redact_spec; nullptr = the defaults).  Fills lastBatchResult();
+       redactedPixels()[i][k] is the number of pixels face k of image i owns. */
+    void detectRedacted(vector<cv::Mat> &imgs, float threshold = 0.5, const rf_redact_spec *spec = nullptr);
+    const vector<vector<int32_t>> &redactedPixels() const { return redactPixels_; }
+
     /* `scale` of RetinaFace.cpp:585-589: multiply lastResult() coordinates by it for source-frame pixels (:732-739, commented) */
     float frameScale(const Mat &img) const { return rf_frame_scale(h_, img.rows, img.cols); }
 
@@ -132,6 +138,7 @@ private:
     vector<vector<int>> tileSrc_;
     vector<vector<rf_track_tag>> trackTags_;
     vector<vector<rf_track>> trackEnded_;
+    vector<vector<int32_t>> redactPixels_;
     vector<uint8_t> faceBatchCall(const vector<cv::Mat> &imgs, float threshold, const rf_face_batch_spec &spec, bool gated,
                                   const rf_face_gate *gate);
 };

@@ -506,6 +506,85 @@ int rf_detect_track_face_batch_device(rf_handle h, const void *const *d_bgr, con
                                       rf_face_quality *quality, rf_tracker tracker, const int *stream_of_image, rf_track_tag *tags,
                                       rf_track *ended, int cap_ended, int *ended_counts);
 
+/* ---- Face redaction: pixelate or fill the faces of a frame IN PLACE, on the device (DESIGN.md "Face redaction" holds the definition;
+ * tests/redact_ref.py restates it in numpy; every result is byte-exact against it).  Frames are CV_8UC3 BGR with any pointer and row step.
+ *   region   of a face with box x1, y1, x2, y2 in a rows x cols frame, coord_scale s (fp32, one rounding per operation, never contracted):
+ *            b = box * s (also for s = 1); w = bx2 - bx1, h = by2 - by1.  INVALID (owns no pixel) unless bx1, by1, bx2, by2, w, h are all
+ *            finite and w >= 0, h >= 0.  ex1 = bx1 - margin * w, ex2 = bx2 + margin * w, ey likewise; each clamped to [-4096, 8192];
+ *            ux0 = floor(ex1), ux1 = floor(ex2) + 1, uy likewise; W = ux1 - ux0, H = uy1 - uy0.  The clipped rectangle is its
+ *            intersection with [0, cols) x [0, rows), which may be empty.
+ *   mask     RECT: the clipped rectangle.  ELLIPSE: its pixels with a*a*H*H + b*b*W*W <= W*W*H*H, a = 2x + 1 - (ux0 + ux1),
+ *            b = 2y + 1 - (uy0 + uy1), in int64: the ellipse inscribed in the UNCLIPPED rectangle, at pixel centres, exact.
+ *   cells    c = (max(W, H) + cells - 1) / cells; pixel (x, y) lies in cell ((x - ux0) / c, (y - uy0) / c).  A cell's pixel set is its
+ *            c x c square cut by the unclipped rectangle and the frame (not by the mask, not by ownership); its value per channel is
+ *            (sum + n / 2) / n over that set, of the ORIGINAL bytes.  With c == 1 pixelation is the identity.
+ *   list     of image i: its faces k < min(counts[i], max_regions) in score order; with a tracker, then the `last` boxes (scale 1) of
+ *            its stream's live tracks with 1 <= missed <= coast in ascending slot order; cut at max_regions.  A pixel is OWNED by the
+ *            lowest-indexed region whose mask covers it.  The output equals the input except at owned pixels, which take their owner's
+ *            cell value (PIXELATE) or fill (FILL).  Every read is of the original frame.
+ *   results  pixels[i * max_regions + r] (may be NULL): the pixels region r owns; region_counts[i] (may be NULL): the length of the list
+ *            before the cut (counts[i] + coasting tracks); a cut list returns RF_ERR_TRUNCATED. */
+enum { RF_REDACT_PIXELATE = 0, RF_REDACT_FILL = 1 };
+enum { RF_REDACT_RECT = 0, RF_REDACT_ELLIPSE = 1 };
+typedef struct rf_redact_spec {   /* 32 bytes; a field of 0 means its default, a NULL spec all defaults */
+    uint32_t struct_size;   /* sizeof(rf_redact_spec) */
+    int32_t mode;           /* RF_REDACT_PIXELATE / RF_REDACT_FILL */
+    int32_t shape;          /* RF_REDACT_RECT / RF_REDACT_ELLIPSE */
+    int32_t cells;          /* cells across the longer side of a region, 1..64; 0 = 8 */
+    float margin;           /* the box grows by this fraction of its width / height on each side; finite and <= 1; 0 = 0.2; negative = 0 */
+    uint8_t fill[3];        /* B, G, R of RF_REDACT_FILL */
+    uint8_t reserved;
+    int32_t max_regions;    /* regions per image, 1..1024; 0 = the engine's max_detections clamped to 1024 (256 without a handle) */
+    int32_t coast;          /* with a tracker: also redact live tracks with 1 <= missed <= coast; 0 = the tracker's max_missed; negative = none */
+} rf_redact_spec;
+
+/* Host only, no GPU, no handle -- the same code the kernels run, compiled for the host.  rf_redact_region: out = ux0, uy0, ux1, uy1, the
+ * clipped rectangle cx0, cy0, cx1, cy1 (cx1 <= cx0 or cy1 <= cy0: empty) and c; returns 1 (valid), 0 (invalid region: out is all zero)
+ * or RF_ERR_INVALID_ARG (bad spec, NULL argument, rows or cols < 0). */
+int rf_redact_region(const rf_redact_spec *spec, const rf_face *face, float coord_scale, int rows, int cols, int out[9]);
+/* Redacts a whole frame in place in HOST memory (the CPU counterpart of rf_redact_device for one image without a tracker; a usable
+ * fallback).  pixels: min(count, max_regions) counts, may be NULL.  Returns 0, RF_ERR_TRUNCATED (count > max_regions: the first
+ * max_regions faces were redacted) or RF_ERR_INVALID_ARG, which changes nothing. */
+int rf_redact_host(const rf_redact_spec *spec, uint8_t *bgr, int rows, int cols, int step, const rf_face *faces, int count,
+                   float coord_scale, int32_t *pixels);
+
+/* Redacts faces the CALLER supplies (host memory: faces[i * cap_per_image + k], k < counts[i] <= cap_per_image) in place in
+ * device-resident frames; no forward pass runs.  coord_scale: per image, NULL = 1 -- a tiled caller follows rf_detect_tiled_batch_device
+ * with this call and coord_scale NULL (the tiled calls, the asynchronous tickets and rf_detect_batch_pad32 have no redacting form).
+ * tracker may be NULL; with one, stream_of_image[i] names the stream whose coasting tracks (the tracker's CURRENT table) are redacted in
+ * image i, -1 = faces only; a stream may appear at most once per call.  A NULL / 0 x 0 frame is skipped (no regions).  Refused before
+ * any state changes: a bad spec, a NULL frame array, two frames of the call whose byte ranges overlap (RF_ERR_INVALID_ARG), a frame
+ * resident on another GPU (RF_ERR_UNSUPPORTED: its staged copy would be redacted, not the frame), a multi-device handle
+ * (RF_ERR_UNSUPPORTED). */
+int rf_redact_device(rf_handle h, void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n, const rf_face *faces,
+                     int cap_per_image, const int *counts, const float *coord_scale, const rf_redact_spec *spec, rf_tracker tracker,
+                     const int *stream_of_image, int32_t *pixels, int *region_counts);
+
+/* Measurement hook: the time of the redaction launches of the handle's most recent rf_redact_device call, between two HIP events on its
+ * stream (the upload and the copy-out are outside).  RF_ERR_INVALID_ARG before the first such call. */
+int rf_redact_last_launch_ms(rf_handle h, float *ms);
+
+/* rf_detect_batch_device + redaction of what it finds, in one call: detection runs exactly as there (out / counts /
+ * rf_last_anchor_indices are the same bytes); the redaction launches follow each detection launch on its stream and read the faces from
+ * the device-visible result block -- no host synchronisation in between.  coord_scale is each frame's rf_frame_scale, so an oversize
+ * frame is redacted at its full source resolution.  n may exceed max_batch.  pixels: n * max_regions, may be NULL.  Refusals as above. */
+int rf_detect_redact_batch_device(rf_handle h, void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                  float threshold, rf_face *out, int cap_per_image, int *counts, const rf_redact_spec *spec,
+                                  int32_t *pixels);
+/* Frames in host memory: uploaded once, detected and redacted on that copy; the redacted frames go to out_bgr[i] with rows of
+ * out_steps[i] bytes (NULL = cols * 3), which may be the input buffers. */
+int rf_detect_redact_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                           float threshold, rf_face *out, int cap_per_image, int *counts, const rf_redact_spec *spec,
+                           uint8_t *const *out_bgr, const int *out_steps, int32_t *pixels);
+/* rf_detect_track_batch_device + redaction: the redaction launches sit behind each track launch, so the coasting regions are those of
+ * the table AFTER this call's frame step -- a face the detector misses in this frame stays covered where it was last seen.  Each stream
+ * may appear at most once per call (RF_ERR_INVALID_ARG otherwise).  Tags, ended lists and the tracker's state are the bytes of the
+ * unredacted tracked call. */
+int rf_detect_track_redact_batch_device(rf_handle h, void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                        float threshold, rf_face *out, int cap_per_image, int *counts, rf_tracker tracker,
+                                        const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_counts,
+                                        const rf_redact_spec *spec, int32_t *pixels, int *region_counts);
+
 /* Asynchronous form of rf_detect_batch_device for serving loops: enqueue returns as soon as the
  * batch is queued on the engine's stream (n <= max_batch); `ticket` identifies one of
  * rf_num_slots() result slots.  rf_wait blocks until that batch has finished and copies its results.

@@ -73,6 +73,14 @@ class rf_track_tag(C.Structure):
     _fields_ = [("id", C.c_int64), ("slot", C.c_int32), ("hits", C.c_int32), ("age", C.c_int32), ("flags", C.c_int32)]
 
 
+class rf_redact_spec(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("shape", C.c_int32), ("cells", C.c_int32), ("margin", C.c_float),
+                ("fill", C.c_uint8 * 3), ("reserved", C.c_uint8), ("max_regions", C.c_int32), ("coast", C.c_int32)]
+
+
+RF_REDACT_PIXELATE, RF_REDACT_FILL = 0, 1
+RF_REDACT_RECT, RF_REDACT_ELLIPSE = 0, 1
+
 RF_TRACK_NEW, RF_TRACK_CONFIRMED, RF_TRACK_BEST, RF_TRACK_UNTRACKED, RF_TRACK_OVERFLOW = 1, 2, 4, 8, 16
 
 RF_GATE_INVALID, RF_GATE_SHARPNESS, RF_GATE_IOD, RF_GATE_YAW, RF_GATE_ROLL, RF_GATE_COVERED, RF_GATE_DARK, RF_GATE_BRIGHT = (
@@ -166,6 +174,22 @@ SYMBOLS = {
                                                     C.c_void_p, C.c_void_p, _PP(C.c_double), _PP(C.c_int), _PP(rf_face_gate),
                                                     _PP(rf_face_quality), C.c_void_p, _PP(C.c_int), _PP(rf_track_tag), _PP(rf_track),
                                                     C.c_int, _PP(C.c_int)]),
+    "rf_redact_region": (C.c_int, [_PP(rf_redact_spec), _PP(rf_face), C.c_float, C.c_int, C.c_int, _PP(C.c_int)]),
+    "rf_redact_host": (C.c_int, [_PP(rf_redact_spec), C.c_void_p, C.c_int, C.c_int, C.c_int, _PP(rf_face), C.c_int, C.c_float,
+                                 _PP(C.c_int32)]),
+    "rf_redact_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int, _PP(rf_face), C.c_int,
+                                   _PP(C.c_int), _PP(C.c_float), _PP(rf_redact_spec), C.c_void_p, _PP(C.c_int), _PP(C.c_int32),
+                                   _PP(C.c_int)]),
+    "rf_redact_last_launch_ms": (C.c_int, [C.c_void_p, _PP(C.c_float)]),
+    "rf_detect_redact_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int, C.c_float,
+                                                _PP(rf_face), C.c_int, _PP(C.c_int), _PP(rf_redact_spec), _PP(C.c_int32)]),
+    "rf_detect_redact_batch": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int, C.c_float,
+                                         _PP(rf_face), C.c_int, _PP(C.c_int), _PP(rf_redact_spec), _PP(C.c_void_p), _PP(C.c_int),
+                                         _PP(C.c_int32)]),
+    "rf_detect_track_redact_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                                      C.c_float, _PP(rf_face), C.c_int, _PP(C.c_int), C.c_void_p, _PP(C.c_int),
+                                                      _PP(rf_track_tag), _PP(rf_track), C.c_int, _PP(C.c_int), _PP(rf_redact_spec),
+                                                      _PP(C.c_int32), _PP(C.c_int)]),
     "rf_num_slots": (C.c_int, [C.c_void_p]),
     "rf_enqueue_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int),
                                           C.c_int, C.c_float, _PP(C.c_int)]),

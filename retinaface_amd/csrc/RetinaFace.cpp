@@ -47,6 +47,32 @@ void RetinaFace::detectBatchImages(vector<cv::Mat> imgs, float threshold) {
     }
 }
 
+void RetinaFace::detectRedacted(vector<cv::Mat> &imgs, float threshold, const rf_redact_spec *spec) {
+    const int n = (int)imgs.size();
+    lastBatch_.assign(n, vector<FaceDetectInfo>());
+    redactPixels_.assign(n, vector<int32_t>());
+    if (n == 0) return;
+    const int regions = spec && spec->max_regions > 0 ? spec->max_regions : (maxDet_ < 1024 ? maxDet_ : 1024);
+    vector<const uint8_t *> ptrs(n);
+    vector<uint8_t *> outs(n);
+    vector<int> rows(n), cols(n), steps(n), counts(n, 0);
+    for (int i = 0; i < n; i++) {
+        ptrs[i] = outs[i] = imgs[i].empty() ? nullptr : imgs[i].data;
+        rows[i] = imgs[i].rows; cols[i] = imgs[i].cols; steps[i] = (int)(size_t)imgs[i].step;
+    }
+    vector<rf_face> faces((size_t)n * maxDet_);
+    vector<int32_t> pixels((size_t)n * regions);
+    check(rf_detect_redact_batch(h_, ptrs.data(), rows.data(), cols.data(), steps.data(), n, threshold, faces.data(), maxDet_, counts.data(),
+                                 spec, outs.data(), steps.data(), pixels.data()), h_, "RetinaFace::detectRedacted");
+    for (int i = 0; i < n; i++) {
+        int k = counts[i] < maxDet_ ? counts[i] : maxDet_;
+        lastBatch_[i].resize(k);
+        if (k) memcpy(lastBatch_[i].data(), &faces[(size_t)i * maxDet_], (size_t)k * sizeof(rf_face));
+        const int r = k < regions ? k : regions;
+        redactPixels_[i].assign(pixels.begin() + (size_t)i * regions, pixels.begin() + (size_t)i * regions + r);
+    }
+}
+
 void RetinaFace::detectTiled(const vector<cv::Mat> &imgs, float threshold, const rf_tile_spec *spec) {
     const int n = (int)imgs.size();
     lastBatch_.assign(n, vector<FaceDetectInfo>());

@@ -723,6 +723,119 @@ int rf_detect_track_face_batch_device(rf_handle h, const void *const *d_bgr, con
     });
 }
 
+// ---- face redaction (redact.h)
+int rf_redact_region(const rf_redact_spec *spec, const rf_face *face, float coord_scale, int rows, int cols, int out[9]) {
+    rf::RedactSpec sp;
+    if (rf::redact_spec_resolve(spec, 256, &sp) || !face || !out || rows < 0 || cols < 0) return RF_ERR_INVALID_ARG;
+    const rf::RedactRegion r = rf::redact_region_make(&face->x1, coord_scale, sp.margin, sp.cells, rows, cols);
+    const int v[9] = {r.ux0, r.uy0, r.ux1, r.uy1, r.cx0, r.cy0, r.cx1, r.cy1, r.c};
+    memcpy(out, v, sizeof(v));
+    return r.valid;
+}
+
+int rf_redact_host(const rf_redact_spec *spec, uint8_t *bgr, int rows, int cols, int step, const rf_face *faces, int count,
+                   float coord_scale, int32_t *pixels) {
+    rf::RedactSpec sp;
+    if (rf::redact_spec_resolve(spec, 256, &sp) || count < 0 || (count > 0 && !faces) || rows < 0 || cols < 0) return RF_ERR_INVALID_ARG;
+    const bool empty = !bgr || rows == 0 || cols == 0;
+    if (!empty && (step < cols * 3 || rows > 4096 * 3072 / cols)) return RF_ERR_INVALID_ARG;
+    const int m = empty ? 0 : std::min(count, sp.max_regions);
+    std::vector<rf::RedactRegion> regions((size_t)m);
+    for (int k = 0; k < m; k++) regions[k] = rf::redact_region_make(&faces[k].x1, coord_scale, sp.margin, sp.cells, rows, cols);
+    if (empty) { if (pixels) for (int k = 0; k < std::min(count, sp.max_regions); k++) pixels[k] = 0; }
+    else rf::redact_host_frame(sp, bgr, rows, cols, (size_t)step, regions.data(), m, pixels);
+    return count > sp.max_regions ? RF_ERR_TRUNCATED : RF_OK;
+}
+
+namespace {
+const char kRedactCut[] = "a region list was cut at max_regions";
+
+// the spec, refused before any state changes; the tracker (may be NULL) must live on this handle
+void redact_request(rf_handle h, const rf_redact_spec *spec, rf_tracker tracker, const int *stream_of_image, int32_t *pixels, int *region_counts,
+                    rf::RedactRequest *rq) {
+    if (h->eng->num_devices() > 1) throw rf::Unsupported("face redaction is not available on a multi-device handle");
+    const char *bad = rf::redact_spec_resolve(spec, h->eng->default_max_faces(), &rq->spec);
+    if (bad) throw rf::ArgError(bad);
+    if (tracker && tracker->h != h) throw rf::ArgError("not a tracker of this handle");
+    rq->tracker = tracker ? tracker->impl : nullptr;
+    rq->stream_of_image = tracker ? stream_of_image : nullptr;
+    rq->pixels = pixels; rq->region_counts = region_counts;
+}
+}  // namespace
+
+int rf_redact_device(rf_handle h, void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n, const rf_face *faces,
+                     int cap_per_image, const int *counts, const float *coord_scale, const rf_redact_spec *spec, rf_tracker tracker,
+                     const int *stream_of_image, int32_t *pixels, int *region_counts) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        rf::RedactRequest rq;
+        redact_request(h, spec, tracker, stream_of_image, pixels, region_counts, &rq);
+        bool cut = false;
+        h->eng->redact((const void *const *)d_bgr, rows, cols, steps, n, faces, cap_per_image, counts, coord_scale, rq, &cut);
+        if (cut) { h->error = kRedactCut; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+
+int rf_redact_last_launch_ms(rf_handle h, float *ms) {
+    if (!h || !ms) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        const float v = h->eng->redact_last_launch_ms();
+        if (v < 0.f) throw rf::ArgError("no rf_redact_device call has been timed on this handle");
+        *ms = v;
+        return RF_OK;
+    });
+}
+
+namespace {
+int detect_redact_common(rf_handle h, const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,
+                         float thr, rf_face *out, int cap, int *counts, const rf_redact_spec *spec, uint8_t *const *out_bgr, const int *out_steps,
+                         int32_t *pixels) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        rf::RedactRequest rq;
+        redact_request(h, spec, nullptr, nullptr, pixels, nullptr, &rq);
+        bool tr = false, cut = false;
+        h->eng->detect_redact(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, rq, &cut, out_bgr, out_steps);
+        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        if (cut) { h->error = kRedactCut; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+}  // namespace
+
+int rf_detect_redact_batch_device(rf_handle h, void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n, float threshold,
+                                  rf_face *out, int cap_per_image, int *counts, const rf_redact_spec *spec, int32_t *pixels) {
+    return detect_redact_common(h, (const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, out, cap_per_image, counts, spec,
+                                nullptr, nullptr, pixels);
+}
+
+int rf_detect_redact_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n, float threshold,
+                           rf_face *out, int cap_per_image, int *counts, const rf_redact_spec *spec, uint8_t *const *out_bgr,
+                           const int *out_steps, int32_t *pixels) {
+    return detect_redact_common(h, bgr, rows, cols, steps, n, false, threshold, out, cap_per_image, counts, spec, out_bgr, out_steps, pixels);
+}
+
+int rf_detect_track_redact_batch_device(rf_handle h, void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                        float threshold, rf_face *out, int cap_per_image, int *counts, rf_tracker tracker,
+                                        const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_counts,
+                                        const rf_redact_spec *spec, int32_t *pixels, int *region_counts) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        rf::RedactRequest rq;
+        redact_request(h, spec, tracker, stream_of_image, pixels, region_counts, &rq);
+        rf::TrackRequest trq;
+        track_request(h, tracker, stream_of_image, tags, ended, cap_ended, ended_counts, &trq);
+        bool tr = false, tcut = false, cut = false;
+        h->eng->detect_track_redact((const uint8_t *const *)d_bgr, rows, cols, steps, n, threshold, out, cap_per_image, counts, &tr, trq, &tcut,
+                                    rq, &cut);
+        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        if (tcut) { h->error = kTrackCut; return RF_ERR_TRUNCATED; }
+        if (cut) { h->error = kRedactCut; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+
 int rf_num_slots(rf_handle h) { return h ? h->eng->num_slots() : RF_ERR_INVALID_ARG; }
 
 int rf_enqueue_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps,

@@ -208,10 +208,11 @@ public:
         for (void *p : host_allocs_) (void)hipHostFree(p);
         if (align_stream_) { (void)hipStreamSynchronize(align_stream_); (void)hipStreamDestroy(align_stream_); }
         for (DeviceScratch *b : {&align_crops_, &align_mats_, &align_tab_, &fb_state_, &fq_records_, &fq_packed_, &fq_offsets_, &tile_cand_, &tile_count_, &tile_out_,
-                                 &tile_outcount_, &tile_tab_, &tile_frames_}) b->release();
+                                 &tile_outcount_, &tile_tab_, &tile_frames_, &red_regions_, &red_counts_, &red_cells_, &red_frames_}) b->release();
         for (HostScratch *b : {&trk_tags_, &trk_ended_, &trk_counts_}) b->release();
         for (auto &t : trackers_) t->state.release();
         for (hipEvent_t e : trk_ev_) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : red_ev_) if (e) (void)hipEventDestroy(e);
         kind_.arena->release();
         for (auto &e : prof_ev_) (void)hipEventDestroy(e);
     }
@@ -969,6 +970,215 @@ public:
         track_copy_out(t, rq, n, cap_per_image, counts, cut);
     }
 
+
+    // -------------------------------------------------------------------------------- face redaction
+    // The arguments of a redacting call, checked before any state changes: the tracker and its streams (each at most once per call:
+    // the coasting regions of a stream belong to one frame), the frames (in-place writes: no two frames of a call may share a byte,
+    // and a frame resident on another device would be redacted in its staged copy, not where the caller holds it).
+    void *redact_check(const RedactRequest &rq, const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n,
+                          bool on_device) {
+        if (n < 0 || (n > 0 && (!frames || !rows || !cols))) throw ArgError("null argument");
+        if (rq.spec.max_regions < 1 || rq.spec.max_regions > kRedactMaxRegions) throw ArgError("max_regions must be in [1, 1024]");
+        if ((size_t)std::max(n, 1) * rq.spec.max_regions * rq.spec.cells * rq.spec.cells > ((size_t)1 << 28))
+            throw ArgError("n x max_regions x cells^2: more than 2^28 cells in one call");
+        auto *t = rq.tracker ? &tracker_of(rq.tracker) : nullptr;
+        if (t) {
+            if (t->dirty) throw ArgError("the tracker's last call failed: reset it first");
+            if (n > 0 && !rq.stream_of_image) throw ArgError("stream_of_image is null");
+            std::vector<int> seen;
+            for (int i = 0; i < n; i++) {
+                const int st = rq.stream_of_image[i];
+                if (st < -1 || st >= t->n_streams) throw ArgError("stream_of_image: stream out of range");
+                if (st >= 0) seen.push_back(st);
+            }
+            std::sort(seen.begin(), seen.end());
+            if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) throw ArgError("redaction: a stream appears more than once in the call");
+        }
+        std::vector<std::pair<uintptr_t, uintptr_t>> span;
+        for (int i = 0; i < n; i++) {
+            const int st = steps ? steps[i] : cols[i] * 3;
+            check_frame(frames[i], rows[i], cols[i], st);
+            if (!frames[i] || rows[i] <= 0 || cols[i] <= 0) continue;
+            if (on_device && check_residency_) {
+                const int where = foreign_device_of(frames[i]);
+                if (where >= 0 && where != device_) throw Unsupported("redaction: a frame is resident on another device (its staged copy would be redacted, not the frame)");
+            }
+            span.emplace_back((uintptr_t)frames[i], (uintptr_t)frames[i] + (size_t)(rows[i] - 1) * st + (size_t)cols[i] * 3);
+        }
+        std::sort(span.begin(), span.end());
+        for (size_t j = 1; j < span.size(); j++)
+            if (span[j].first < span[j - 1].second) throw ArgError("redaction: two frames of the call overlap in memory");
+        return t;
+    }
+
+    // device blocks of a redacting call, sized once and reused; the region counts (after | before the cut) and the owned-pixel counts
+    // share one block, so the results of a call come back in one copy
+    void redact_open(const RedactRequest &rq, void *tracker, int n) {
+        const size_t slots = (size_t)std::max(n, 1) * rq.spec.max_regions;
+        red_regions_.reserve(slots * sizeof(RedactRegion));
+        red_counts_.reserve(((size_t)std::max(n, 1) * 2 + slots) * sizeof(int));
+        if (rq.spec.mode == RF_REDACT_PIXELATE) red_cells_.reserve(slots * rq.spec.cells * rq.spec.cells * sizeof(uint32_t));
+        red_.spec = rq.spec; red_.tr = tracker ? &tracker_of(tracker) : nullptr; red_.stream_of_image = rq.stream_of_image;
+        red_.n = n; red_.next_image = 0;
+    }
+    RedactParams redact_params() const {
+        RedactParams rp;
+        memset((void *)&rp, 0, sizeof(rp));
+        rp.spec = red_.spec;
+        if (red_.tr) {
+            rp.track_state = red_.tr->state.ptr;
+            rp.max_tracks = red_.tr->spec.max_tracks;
+            rp.coast = redact_coast(red_.spec.coast, red_.tr->spec.max_missed);
+        }
+        rp.regions = (RedactRegion *)red_regions_.ptr;
+        rp.nreg = (int *)red_counts_.ptr; rp.true_counts = (int *)red_counts_.ptr + std::max(red_.n, 1);
+        rp.cell_values = (uint32_t *)red_cells_.ptr;
+        rp.pixels = (int *)red_counts_.ptr + 2 * std::max(red_.n, 1);
+        return rp;
+    }
+    static void redact_launch(hipStream_t st, const RedactParams &rp) {
+        launch_redact_regions(st, rp);
+        launch_redact_mean(st, rp);
+        launch_redact_write(st, rp);
+    }
+    // results of a finished redacting call (the host has waited for its last launch)
+    void redact_copy_out(const RedactRequest &rq, int n, bool *cut) {
+        if (n == 0) return;
+        const size_t px = rq.pixels ? (size_t)n * rq.spec.max_regions : 0;
+        red_host_.resize(2 * (size_t)n + px);
+        RF_HIP(hipMemcpy(red_host_.data(), red_counts_.ptr, red_host_.size() * sizeof(int), hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; i++) {
+            if (red_host_[n + i] > rq.spec.max_regions) *cut = true;
+            if (rq.region_counts) rq.region_counts[i] = red_host_[n + i];
+        }
+        if (px) memcpy(rq.pixels, red_host_.data() + 2 * (size_t)n, px * sizeof(int));
+    }
+
+    void redact(const void *const *frames, const int *rows, const int *cols, const int *steps, int n, const rf_face *faces, int cap_per_image,
+                const int *counts, const float *coord_scale, const RedactRequest &rq, bool *cut) override {
+        *cut = false;
+        if (n < 0 || (n > 0 && (!counts || (!faces && cap_per_image > 0)))) throw ArgError("null argument");
+        if (cap_per_image < 0) throw ArgError("cap_per_image must be >= 0");
+        for (int i = 0; i < n; i++)
+            if (counts[i] < 0 || counts[i] > cap_per_image) throw ArgError("counts[i] must be in [0, cap_per_image]");
+        void *t = redact_check(rq, (const uint8_t *const *)frames, rows, cols, steps, n, true);
+        if (n == 0) return;
+        DeviceGuard guard(device_);
+        const int fpi = std::max(1, std::min(cap_per_image, rq.spec.max_regions));      // records per image that travel to the device
+        // one table: frames | counts | scales | streams | faces (60-byte records)
+        const size_t o_cnt = align256((size_t)n * sizeof(FrameDesc)), o_sc = o_cnt + align256((size_t)n * sizeof(int)),
+                     o_st = o_sc + align256((size_t)n * sizeof(float)), o_face = o_st + align256((size_t)n * sizeof(int)),
+                     total = o_face + (size_t)n * fpi * sizeof(rf_face);
+        align_host_.assign(total, 0);
+        FrameDesc *fd = (FrameDesc *)align_host_.data();
+        int *cnt = (int *)(align_host_.data() + o_cnt);
+        float *sc = (float *)(align_host_.data() + o_sc);
+        int *strm = (int *)(align_host_.data() + o_st);
+        for (int i = 0; i < n; i++) {
+            const uint8_t *p = (const uint8_t *)frames[i];
+            const bool empty = !p || rows[i] <= 0 || cols[i] <= 0;
+            fd[i] = empty ? FrameDesc{nullptr, 0, 0, 0, 0} : FrameDesc{p, rows[i], cols[i], steps ? steps[i] : cols[i] * 3, 0};
+            cnt[i] = counts[i];             // the true count: the kernel cuts the list and reports its length
+            sc[i] = coord_scale ? coord_scale[i] : 1.f;
+            strm[i] = t ? rq.stream_of_image[i] : -1;
+            const int c = std::min(counts[i], fpi);
+            if (c) memcpy(align_host_.data() + o_face + (size_t)i * fpi * sizeof(rf_face), faces + (size_t)i * cap_per_image, (size_t)c * sizeof(rf_face));
+        }
+        uint8_t *d_tab = align_tab_.reserve(total);
+        redact_open(rq, t, n);
+        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+        RF_HIP(hipMemcpyAsync(d_tab, align_host_.data(), total, hipMemcpyHostToDevice, align_stream_));
+        RedactParams rp = redact_params();
+        rp.frames = (const FrameDesc *)d_tab;
+        rp.faces = d_tab + o_face; rp.face_stride = (int)sizeof(rf_face); rp.faces_per_image = fpi;
+        rp.counts = (const int *)(d_tab + o_cnt); rp.count_cap = 0x7fffffff;
+        rp.scale = (const float *)(d_tab + o_sc);
+        rp.streams = t ? (const int *)(d_tab + o_st) : nullptr;
+        rp.n = n; rp.image0 = 0;
+        if (!red_ev_[0]) { RF_HIP(hipEventCreate(&red_ev_[0])); RF_HIP(hipEventCreate(&red_ev_[1])); }
+        RF_HIP(hipEventRecord(red_ev_[0], align_stream_));
+        redact_launch(align_stream_, rp);
+        RF_HIP(hipGetLastError());
+        RF_HIP(hipEventRecord(red_ev_[1], align_stream_));
+        RF_HIP(hipStreamSynchronize(align_stream_));
+        if (hipEventElapsedTime(&red_launch_ms_, red_ev_[0], red_ev_[1]) != hipSuccess) red_launch_ms_ = -1.f;
+        redact_copy_out(rq, n, cut);
+    }
+    float redact_last_launch_ms() const override { return red_launch_ms_; }
+
+    void detect_redact(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device, float threshold,
+                       rf_face *out, int cap_per_image, int *counts, bool *truncated, const RedactRequest &rq, bool *cut, uint8_t *const *out_bgr,
+                       const int *out_steps) override {
+        *cut = false;
+        if (n < 0 || (n > 0 && (!frames || !rows || !cols || !counts))) throw ArgError("null argument");
+        if (cap_per_image < 0 || (cap_per_image > 0 && !out)) throw ArgError("out is null");
+        if (rq.tracker) throw ArgError("redaction: the tracked form is detect_track_redact");
+        if (!on_device && n > 0 && !out_bgr) throw ArgError("out_bgr is null");
+        redact_check(rq, frames, rows, cols, steps, n, on_device);
+        DeviceGuard guard(device_);
+        // host frames are uploaded once, densely: detection and redaction run on that copy
+        std::vector<const uint8_t *> dev((size_t)n, nullptr);
+        std::vector<int> st((size_t)std::max(n, 1));
+        for (int i = 0; i < n; i++) st[i] = steps ? steps[i] : cols[i] * 3;
+        if (!on_device) {
+            size_t bytes = 0;
+            std::vector<size_t> off((size_t)n, 0);
+            for (int i = 0; i < n; i++) {
+                if (!frames[i] || rows[i] <= 0 || cols[i] <= 0) continue;
+                if (!out_bgr[i]) throw ArgError("out_bgr[i] is null");
+                if (out_steps && out_steps[i] < cols[i] * 3) throw ArgError("out_steps[i] smaller than cols*3");
+                off[i] = bytes; bytes += align256((size_t)rows[i] * cols[i] * 3);
+            }
+            uint8_t *d = red_frames_.reserve(bytes);
+            for (int i = 0; i < n; i++) {
+                if (!frames[i] || rows[i] <= 0 || cols[i] <= 0) continue;
+                RF_HIP(hipMemcpy2D(d + off[i], (size_t)cols[i] * 3, frames[i], (size_t)st[i], (size_t)cols[i] * 3, (size_t)rows[i], hipMemcpyHostToDevice));
+                dev[i] = d + off[i];
+                st[i] = cols[i] * 3;
+            }
+        } else {
+            for (int i = 0; i < n; i++) dev[i] = frames[i];
+        }
+        // as in detect_align(): a super-batch of earlier enqueues starts now, every later launch carries images of this call only
+        launch_pending();
+        redact_open(rq, nullptr, n);
+        red_.on = n > 0;
+        struct Off { bool &on; ~Off() { on = false; } } off_guard{red_.on};
+        detect(dev.data(), rows, cols, st.data(), n, true, threshold, out, cap_per_image, counts, truncated);
+        red_.on = false;
+        if (red_.next_image != n) throw HipError("redaction: a launch of the call was not redacted");
+        // every launch of the call has been waited for (its `done` event follows the redaction launches)
+        redact_copy_out(rq, n, cut);
+        if (!on_device)
+            for (int i = 0; i < n; i++)
+                if (dev[i]) RF_HIP(hipMemcpy2D(out_bgr[i], out_steps ? (size_t)out_steps[i] : (size_t)cols[i] * 3, dev[i], (size_t)cols[i] * 3,
+                                               (size_t)cols[i] * 3, (size_t)rows[i], hipMemcpyDeviceToHost));
+    }
+
+    void detect_track_redact(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, float threshold, rf_face *out,
+                             int cap_per_image, int *counts, bool *truncated, const TrackRequest &trq, bool *track_cut, const RedactRequest &rq,
+                             bool *cut) override {
+        *cut = false; *track_cut = false;
+        if (n < 0 || (n > 0 && (!frames || !rows || !cols || !counts))) throw ArgError("null argument");
+        if (cap_per_image < 0 || (cap_per_image > 0 && !out)) throw ArgError("out is null");
+        if (!rq.tracker || rq.tracker != trq.tracker || rq.stream_of_image != trq.stream_of_image) throw ArgError("redaction: not the tracked call's tracker");
+        Tracker &t = track_check(trq, n);
+        redact_check(rq, frames, rows, cols, steps, n, true);
+        DeviceGuard guard(device_);
+        launch_pending();
+        track_open_call(t, trq, n, cap_per_image);
+        trk_.records = nullptr; trk_.max_faces = kTrackMaxFaces;
+        redact_open(rq, rq.tracker, n);
+        t.dirty = true;
+        trk_.on = n > 0; red_.on = n > 0;
+        struct Off { bool &a, &b; ~Off() { a = false; b = false; } } off{trk_.on, red_.on};
+        detect(frames, rows, cols, steps, n, true, threshold, out, cap_per_image, counts, truncated);
+        trk_.on = false; red_.on = false;
+        if (red_.next_image != n) throw HipError("redaction: a launch of the call was not redacted");
+        track_copy_out(t, trq, n, cap_per_image, counts, track_cut);
+        redact_copy_out(rq, n, cut);
+    }
+
     void host_register(const void *ptr, size_t bytes) override {
         if (!ptr || !bytes) throw ArgError("host_register: null / empty range");
         DeviceGuard guard(device_);
@@ -1175,6 +1385,7 @@ private:
         hipEvent_t tile_done = nullptr;       // ... recorded behind the launch's gather: the call's merge (another lane) waits for it on the device
         uint8_t *h_track_tab = nullptr;       // detect_track(): pinned, the launch's stream table and image table (allocated on first use)
         hipEvent_t track_done = nullptr;      // ... recorded behind the launch's track kernel: the call's next track launch (another lane) waits for it
+        int *h_red_streams = nullptr;         // detect_track_redact(): pinned, per image of the launch its stream (allocated on first use)
         bool busy = false;                    // a launched super-batch whose results have not been harvested yet
         int n_images = 0;                     // images of the super-batch being assembled / in flight on this lane
         float threshold = 0.f;
@@ -1504,6 +1715,7 @@ private:
         if (fb_.on) launch_lane_face_batch(s, n);
         if (tile_.on) launch_lane_tile(s, n);
         if (trk_.on) launch_lane_track(s, n);
+        if (red_.on) launch_lane_redact(s, n);
         RF_HIP(hipEventRecord(s.done, s.stream));
         trace_.add(4, tt);
         s.busy = true;
@@ -1668,6 +1880,36 @@ private:
         RF_HIP(hipGetLastError());
         RF_HIP(hipEventRecord(s.track_done, s.stream));
         trk_.prev = s.track_done;
+    }
+
+    // The redaction launches of a super-batch of detect_redact() / detect_track_redact(): frames from the launch's own frame table (the
+    // first half: the caller's full-resolution frames, which are written in place), faces and counts from the pinned result block the
+    // NMS kernel of the same stream has just written, each frame's coordinate scale from the pinned per-lane array.  With a tracker the
+    // launches sit behind the lane's track launch: every stream appears at most once in the call, so its table is the one after this
+    // frame's step.  Region records, cell values and pixel counts are indexed by the image's place in the call: launches on different
+    // lanes write different slices.  The lane's `done` event follows.  No host wait anywhere.
+    void launch_lane_redact(Lane &s, int n) {
+        if (n > cap_images_ || red_.next_image + n > red_.n) throw HipError("redaction: a launch carries images of another call");
+        fill_lane_align_scale(s, n);
+        RedactParams rp = redact_params();
+        if (red_.tr) {
+            if (!s.h_red_streams) {
+                void *p = nullptr;
+                RF_HIP(hipHostMalloc(&p, std::max<size_t>((size_t)cap_images_ * sizeof(int), 256), hipHostMallocDefault));
+                s.host_allocs.push_back(p);
+                s.h_red_streams = (int *)p;
+            }
+            for (int i = 0; i < n; i++) s.h_red_streams[i] = red_.stream_of_image[red_.next_image + i];
+            rp.streams = s.h_red_streams;
+        }
+        rp.frames = s.d_frames;
+        rp.faces = (const uint8_t *)s.h_out; rp.face_stride = (int)sizeof(Candidate); rp.faces_per_image = opt_.max_detections;
+        rp.counts = s.h_counts; rp.count_cap = opt_.max_detections;
+        rp.scale = s.h_align_scale;
+        rp.n = n; rp.image0 = red_.next_image;
+        redact_launch(s.stream, rp);
+        RF_HIP(hipGetLastError());
+        red_.next_image += n;
     }
 
     // The stream table of images [image0, image0 + n) of a call: the streams present in order of first appearance, each with its
@@ -2048,8 +2290,16 @@ private:
     HostScratch trk_tags_, trk_ended_, trk_counts_;
     hipEvent_t trk_ev_[2] = {nullptr, nullptr};   // around the track launch of track_update() (tools/track_bench.py reads the time)
     float trk_launch_ms_ = -1.f;
+    hipEvent_t red_ev_[2] = {nullptr, nullptr};   // around the redaction launches of redact() (tools/redact_bench.py reads the time)
+    float red_launch_ms_ = -1.f;
     struct { bool on = false; Tracker *tr = nullptr; const int *stream_of_image = nullptr; int n = 0, next_image = 0, tag_stride = 0, cap_ended = 0,
              max_faces = 0; const rf_face_quality *records = nullptr; hipEvent_t prev = nullptr; } trk_;
+
+    // face redaction: region records, region counts (after | before the cut) + owned-pixel counts, and cell values of the call's
+    // images, the device copy of host frames; the request a redacting call has open
+    DeviceScratch red_regions_, red_counts_, red_cells_, red_frames_;
+    std::vector<int> red_host_;
+    struct { bool on = false; RedactSpec spec; Tracker *tr = nullptr; const int *stream_of_image = nullptr; int n = 0, next_image = 0; } red_;
 
     int last_n_ = 0;
     std::vector<int> last_cand_counts_;

@@ -113,6 +113,17 @@ struct TrackRequest {
     int *ended_counts = nullptr;                // n
 };
 
+// A redacting call (redact.h; rf_redact_device / rf_detect_redact_batch* / rf_detect_track_redact_batch_device): the validated spec,
+// the tracker whose coasting tracks are redacted too (nullptr = none) with the stream of every image, and where the per-region pixel
+// counts (n * spec.max_regions) and the true region counts (n) go (host; each may be nullptr)
+struct RedactRequest {
+    RedactSpec spec;
+    void *tracker = nullptr;
+    const int *stream_of_image = nullptr;
+    int32_t *pixels = nullptr;
+    int *region_counts = nullptr;
+};
+
 class Engine {
 public:
     // opt.devices.size() > 1 gives the image-sharding multi-device engine (multi.cpp), otherwise one single-device engine
@@ -192,6 +203,26 @@ public:
                                          int *, bool *, const FaceBatchRequest &, bool * /*overflow*/, const TrackRequest &, bool * /*cut*/) {
         throw Unsupported("face tracks are not available on a multi-device handle");
     }
+    // Face redaction, in place in device-resident frames: regions of faces the caller supplies (host memory) and, with a tracker in
+    // the request, of its streams' coasting tracks.  *cut: a region list was cut at max_regions.  Single-device engines only.
+    virtual void redact(const void *const *, const int *, const int *, const int *, int, const rf_face *, int, const int *, const float *,
+                        const RedactRequest &, bool * /*cut*/) {
+        throw Unsupported("face redaction is not available on a multi-device handle");
+    }
+    // detect() + the redaction of what it finds: the redaction launches follow each detection launch on its stream and read faces and
+    // counts from the device-visible result block.  Host frames are uploaded once, detected and redacted on that copy, and the copy
+    // goes to out_bgr[i] (rows of out_steps[i] bytes; nullptr = dense).
+    virtual void detect_redact(const uint8_t *const *, const int *, const int *, const int *, int, bool, float, rf_face *, int, int *, bool *,
+                               const RedactRequest &, bool * /*cut*/, uint8_t *const * /*out_bgr*/, const int * /*out_steps*/) {
+        throw Unsupported("face redaction is not available on a multi-device handle");
+    }
+    // detect_track() + redaction behind each track launch: the coasting regions are those of the table after this call's frame step
+    virtual void detect_track_redact(const uint8_t *const *, const int *, const int *, const int *, int, float, rf_face *, int, int *, bool *,
+                                     const TrackRequest &, bool * /*track_cut*/, const RedactRequest &, bool * /*cut*/) {
+        throw Unsupported("face redaction is not available on a multi-device handle");
+    }
+    // hipEvent time of the redaction launches of the most recent redact() (negative: none yet)
+    virtual float redact_last_launch_ms() const { return -1.f; }
     int default_max_faces() const { return opt_.max_detections; }
     // asynchronous: frames on host (staged through pinned memory before the call returns, unless the caller registered
     // them with host_register) or on the device

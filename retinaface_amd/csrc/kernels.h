@@ -10,6 +10,7 @@
 #include "align.h"
 #include "face_batch.h"
 #include "face_quality.h"
+#include "redact.h"
 #include "tile.h"
 #include "track.h"
 
@@ -299,6 +300,33 @@ struct TrackParams {
     int *status;                          // [call images] kTrackOverflow or 0
 };
 void launch_track(hipStream_t s, const TrackParams &p);
+
+// ---- K_k: face redaction (redact.h) -- in place in the frames of a launch, in three launches ordered on the stream.
+//      launch_redact_regions: one workgroup per image turns its faces, and with a tracker its stream's coasting tracks, into region
+//      records.  launch_redact_mean (PIXELATE only) reads the frames and writes every region's cell values; launch_redact_write reads
+//      only those, the records and the spec and writes the pixels each region owns.  Every pointer is device-visible memory (the fused
+//      calls read faces and counts from the pinned result block the NMS kernel wrote).
+struct RedactParams {
+    const FrameDesc *frames;              // [n] SOURCE frames (full resolution); they are written
+    const uint8_t *faces;                 // image i, face k: an rf_face at faces + (i * faces_per_image + k) * face_stride
+    int face_stride, faces_per_image;
+    const int *counts;                    // [n] faces of each image, clamped to count_cap here (the faces beyond it do not exist)
+    int count_cap;
+    const float *scale;                   // [n] coordinate scale per image, nullptr = 1
+    int n, image0;                        // images of this launch; call index of its first image
+    RedactSpec spec;
+    const uint8_t *track_state;           // a tracker's state block (TrackParams::state), or nullptr
+    int max_tracks, coast;                // its slots per stream; live tracks with 1 <= missed <= coast are redacted
+    const int *streams;                   // [n] the stream of each image (-1: faces only), or nullptr
+    RedactRegion *regions;                // call image c: regions[c * max_regions + r]
+    int *nreg;                            // [call images] length of the list after the cut
+    int *true_counts;                     // [call images] ... before the cut
+    uint32_t *cell_values;                // region slot q = c * max_regions + r, cell (gx, gy): cell_values[(q * cells + gy) * cells + gx]
+    int *pixels;                          // [call images * max_regions] pixels each region owns (zeroed by launch_redact_regions)
+};
+void launch_redact_regions(hipStream_t s, const RedactParams &p);
+void launch_redact_mean(hipStream_t s, const RedactParams &p);
+void launch_redact_write(hipStream_t s, const RedactParams &p);
 
 // LDS bytes / tile geometry chosen for a layer (exposed for tests and DESIGN.md tables)
 struct TileInfo { int th, tw; size_t lds_bytes; int blocks_per_image; };

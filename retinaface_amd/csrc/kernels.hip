@@ -4696,6 +4696,238 @@ void launch_track(hipStream_t s, const TrackParams &p) {
     hipLaunchKernelGGL(track_kernel, dim3(p.n_streams), dim3(threads), (size_t)T * sizeof(rf_track), s, p);
 }
 
+// =============================================================================================
+// K_k: face redaction (redact.h), in place in the frames of a launch.  Three launches ordered on the stream, race-free by
+//      construction: redact_regions_kernel writes region records, redact_mean_kernel only READS frames and writes cell values,
+//      redact_write_kernel reads only records, cell values and spec constants and writes the pixels each region owns -- every pixel
+//      has at most one owner, so no two threads write the same byte.  The work of the last two is the list of (image, region, cell)
+//      items; a bounded grid of workgroups walks it, so a launch with one huge face is split over cells x cells workgroups and a
+//      launch without faces costs one read of the image's region count per workgroup.  A cell is never split over workgroups, so
+//      there are no atomics on sums.  (One item per ROW of cells was measured too, profiles/redact_variants.json: 3.6 x the time
+//      at 448 x 448, where a face is a few long dependent chains in a few workgroups.)  Everything is bounded: 1024 regions,
+//      64 x 64 cells, the frame's pixels.  Nothing waits on memory.
+// =============================================================================================
+constexpr int kRedactItemsPerImage = 256;      // workgroup slots per image the item list is dealt over
+constexpr int kRedactMaxGrid = 2048;
+
+__global__ __launch_bounds__(kThreads) void redact_regions_kernel(RedactParams a) {
+    __shared__ int s_cnt[kThreads / 64];
+    const int i = blockIdx.x, tid = (int)threadIdx.x;
+    const int M = a.spec.max_regions;
+    const size_t slot0 = (size_t)(a.image0 + i) * M;
+    const FrameDesc fd = a.frames[i];
+    const bool empty = !fd.ptr || fd.rows <= 0 || fd.cols <= 0;
+    for (int r = tid; r < M; r += kThreads) a.pixels[slot0 + r] = 0;
+    int cnt = empty ? 0 : a.counts[i];
+    cnt = cnt < 0 ? 0 : cnt < a.count_cap ? cnt : a.count_cap;
+    int nf = cnt < a.faces_per_image ? cnt : a.faces_per_image;      // cnt stays the true count: the list's length before the cut
+    nf = nf < M ? nf : M;
+    const float scale = a.scale ? a.scale[i] : 1.f;
+    for (int k = tid; k < nf; k += kThreads) {
+        const float *src = (const float *)(a.faces + ((size_t)i * a.faces_per_image + k) * a.face_stride);
+        const float box[4] = {src[1], src[2], src[3], src[4]};
+        a.regions[slot0 + k] = redact_region_make(box, scale, a.spec.margin, a.spec.cells, fd.rows, fd.cols);
+    }
+    // the stream's coasting tracks, in slot order (prefix count by ballot + popcount), behind the faces: where each was last seen
+    int coasting = 0;
+    const int stream = (a.streams && a.track_state && !empty) ? a.streams[i] : -1;
+    if (stream >= 0) {                                            // workgroup-uniform
+        const rf_track *tab = (const rf_track *)(a.track_state + (size_t)stream * (sizeof(TrackHeader) + (size_t)a.max_tracks * sizeof(rf_track)) +
+                                                 sizeof(TrackHeader));
+        bool live = false;
+        float box[4] = {0.f, 0.f, 0.f, 0.f};
+        if (tid < a.max_tracks) {
+            const rf_track *t = tab + tid;
+            live = t->id != 0 && t->missed >= 1 && t->missed <= a.coast;
+            if (live) { box[0] = t->last.x1; box[1] = t->last.y1; box[2] = t->last.x2; box[3] = t->last.y2; }
+        }
+        const int pos = track_prefix_count(live, kThreads / 64, s_cnt, &coasting);
+        if (live && nf + pos < M) a.regions[slot0 + nf + pos] = redact_region_make(box, 1.f, a.spec.margin, a.spec.cells, fd.rows, fd.cols);
+    }
+    if (tid == 0) {
+        const int total = cnt + coasting;
+        a.true_counts[a.image0 + i] = total;
+        a.nreg[a.image0 + i] = total < M ? total : M;
+    }
+}
+
+// the three channel sums of the workgroup's threads; the result is valid in thread 0
+__device__ inline void redact_block_sum(uint32_t &sb, uint32_t &sg, uint32_t &sr, uint32_t (*s_red)[3]) {
+    for (int d = 32; d >= 1; d >>= 1) {
+        sb += __shfl_xor(sb, d, 64); sg += __shfl_xor(sg, d, 64); sr += __shfl_xor(sr, d, 64);
+    }
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    __syncthreads();                                             // the reader of the previous sums is done
+    if (lane == 0) { s_red[wave][0] = sb; s_red[wave][1] = sg; s_red[wave][2] = sr; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        sb = sg = sr = 0;
+        for (int w = 0; w < kThreads / 64; w++) { sb += s_red[w][0]; sg += s_red[w][1]; sr += s_red[w][2]; }
+    }
+}
+
+// One workgroup per item = one cell of one region.  The cell's rows are dealt over
+// the threads as (row, aligned dword of the row's byte span): L = the power of two that holds a row's dwords (at most the workgroup),
+// kThreads / L rows at a time, so a 15 x 15 cell of a small face keeps 16 rows x 13 lanes busy and a 160 x 160 cell of a huge one
+// reads whole rows.  A dword that lies inside the span is one aligned 32-bit load whatever the frame's pointer and pitch are; the
+// dwords at the two ends are read bytewise, so no byte outside the span is touched.  Byte j of the span belongs to channel j % 3.
+__global__ __launch_bounds__(kThreads) void redact_mean_kernel(RedactParams a, int per_image) {
+    __shared__ uint32_t s_red[kThreads / 64][3];
+    const int tid = (int)threadIdx.x;
+    const int M = a.spec.max_regions, C = a.spec.cells;
+    for (int w = blockIdx.x; w < a.n * per_image; w += gridDim.x) {
+        const int i = w / per_image;
+        const int image = a.image0 + i;
+        const int items = a.nreg[image] * C * C;
+        const FrameDesc fd = a.frames[i];
+        for (int item = w - i * per_image; item < items; item += per_image) {
+            const int r = item / (C * C), cell = item - r * C * C, gy = cell / C, gx = cell - gy * C;
+            const RedactRegion reg = a.regions[(size_t)image * M + r];
+            if (redact_clip_empty(reg) || gy >= redact_cells_y(reg) || gx >= redact_cells_x(reg)) continue;
+            int x0, y0, x1, y1;
+            redact_cell_rect(reg, gx, gy, &x0, &y0, &x1, &y1);
+            if (x1 <= x0 || y1 <= y0) continue;               // workgroup-uniform
+            const int nb = 3 * (x1 - x0);
+            const int ndmax = (nb + 3) / 4 + 1;
+            int L = 4;
+            while (L < ndmax && L < kThreads) L <<= 1;
+            const int sub = tid / L, d0 = tid - sub * L, rows_per_pass = kThreads / L;
+            uint32_t sb = 0, sg = 0, sr = 0;
+            for (int y = y0 + sub; y < y1; y += rows_per_pass) {
+                const uint8_t *p = fd.ptr + (size_t)y * fd.step + (size_t)3 * x0;
+                const int head = (int)((uintptr_t)p & 3);     // the span starts `head` bytes into its first aligned dword
+                const int nd = (head + nb + 3) / 4;
+                for (int d = d0; d < nd; d += L) {
+                    const int j = 4 * d - head;               // span offset of the dword's first byte
+                    int ph = (j + 3) % 3;                     // j >= -3
+                    if (j >= 0 && j + 4 <= nb) {
+                        const uint32_t v = *(const uint32_t *)(p + j);
+                        const uint32_t b0 = v & 255u, b1 = (v >> 8) & 255u, b2 = (v >> 16) & 255u, b3 = v >> 24;
+                        // bytes 0 and 3 share a channel
+                        if (ph == 0) { sb += b0 + b3; sg += b1; sr += b2; }
+                        else if (ph == 1) { sg += b0 + b3; sr += b1; sb += b2; }
+                        else { sr += b0 + b3; sb += b1; sg += b2; }
+                    } else {
+                        for (int k = 0; k < 4; k++, ph = ph == 2 ? 0 : ph + 1) {
+                            const int jj = j + k;
+                            if (jj < 0 || jj >= nb) continue;
+                            const uint32_t v = p[jj];
+                            if (ph == 0) sb += v; else if (ph == 1) sg += v; else sr += v;
+                        }
+                    }
+                }
+            }
+            redact_block_sum(sb, sg, sr, s_red);
+            if (tid == 0) a.cell_values[(((size_t)image * M + r) * C + gy) * C + gx] = redact_cell_value(sb, sg, sr, (uint32_t)(x1 - x0) * (uint32_t)(y1 - y0));
+        }
+    }
+}
+
+// One workgroup per item = the part of a region's clipped rectangle that one of its cells covers.  The lower-indexed regions of
+// the image whose clipped rectangles meet that part are gathered into LDS in index order (256 candidates at a time: ballot + popcount
+// prefix, the gather kernel's idiom), then every pixel of it is tested: inside the region's own mask and inside no gathered
+// one = owned.  Owned pixels get their cell's value (or the fill) with three ordinary byte stores; the owned count is reduced over
+// the workgroup and added to the region's counter with one integer atomicAdd.
+__global__ __launch_bounds__(kThreads) void redact_write_kernel(RedactParams a, int per_image) {
+    __shared__ int s_low[kRedactMaxRegions][8];                   // ux0, uy0, ux1, uy1, cx0, cy0, cx1, cy1 of a lower region: 32 KB
+    __shared__ int s_cnt[kThreads / 64];
+    const int tid = (int)threadIdx.x;
+    const int M = a.spec.max_regions, C = a.spec.cells, shape = a.spec.shape;
+    const bool fill_mode = a.spec.mode == RF_REDACT_FILL;
+    const uint32_t fill = (uint32_t)a.spec.fill[0] | ((uint32_t)a.spec.fill[1] << 8) | ((uint32_t)a.spec.fill[2] << 16);
+    for (int w = blockIdx.x; w < a.n * per_image; w += gridDim.x) {
+        const int i = w / per_image;
+        const int image = a.image0 + i;
+        const int items = a.nreg[image] * C * C;
+        const FrameDesc fd = a.frames[i];
+        const RedactRegion *regs = a.regions + (size_t)image * M;
+        for (int item = w - i * per_image; item < items; item += per_image) {
+            const int r = item / (C * C), cell = item - r * C * C, gy = cell / C, gx = cell - gy * C;
+            const RedactRegion reg = regs[r];
+            if (redact_clip_empty(reg) || gy >= redact_cells_y(reg) || gx >= redact_cells_x(reg)) continue;
+            int bx0, by0, bx1, by1;
+            redact_cell_rect(reg, gx, gy, &bx0, &by0, &bx1, &by1);
+            if (bx1 <= bx0 || by1 <= by0) continue;
+            int nlow = 0;
+            for (int q0 = 0; q0 < r; q0 += kThreads) {
+                const int q = q0 + tid;
+                RedactRegion o;
+                bool meets = false;
+                if (q < r) {
+                    o = regs[q];
+                    meets = !redact_clip_empty(o) && o.cx0 < bx1 && o.cx1 > bx0 && o.cy0 < by1 && o.cy1 > by0;
+                }
+                int total = 0;
+                const int pos = track_prefix_count(meets, kThreads / 64, s_cnt, &total);
+                if (meets) {
+                    int *e = s_low[nlow + pos];
+                    e[0] = o.ux0; e[1] = o.uy0; e[2] = o.ux1; e[3] = o.uy1; e[4] = o.cx0; e[5] = o.cy0; e[6] = o.cx1; e[7] = o.cy1;
+                }
+                nlow += total;
+            }
+            __syncthreads();
+            const int bw = bx1 - bx0, npix = bw * (by1 - by0);
+            const uint32_t v = fill_mode ? fill : a.cell_values[(((size_t)image * M + r) * C + gy) * C + gx];
+            int owned = 0;
+            for (int idx = tid; idx < npix; idx += kThreads) {
+                const int yy = idx / bw, x = bx0 + idx - yy * bw, y = by0 + yy;
+                if (!redact_covers(reg, shape, x, y)) continue;
+                bool lower = false;
+                for (int k = 0; k < nlow && !lower; k++) {
+                    const int *e = s_low[k];
+                    RedactRegion o;
+                    o.ux0 = e[0]; o.uy0 = e[1]; o.ux1 = e[2]; o.uy1 = e[3]; o.cx0 = e[4]; o.cy0 = e[5]; o.cx1 = e[6]; o.cy1 = e[7];
+                    o.valid = 1;
+                    lower = redact_covers(o, shape, x, y);
+                }
+                if (lower) continue;
+                uint8_t *p = (uint8_t *)fd.ptr + (size_t)y * fd.step + (size_t)3 * x;
+                p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16);
+                owned++;
+            }
+            for (int d = 32; d >= 1; d >>= 1) owned += __shfl_xor(owned, d, 64);
+            __syncthreads();                                      // every reader of s_low and s_cnt is done
+            if ((tid & 63) == 0) s_cnt[tid >> 6] = owned;
+            __syncthreads();
+            if (tid == 0) {
+                int t = 0;
+                for (int k = 0; k < kThreads / 64; k++) t += s_cnt[k];
+                if (t) atomicAdd(a.pixels + (size_t)image * M + r, t);
+            }
+        }
+    }
+}
+
+static void redact_check(const RedactParams &p) {
+    if (p.spec.max_regions < 1 || p.spec.max_regions > kRedactMaxRegions) throw LaunchUnsupported("redact: max_regions must be in [1, 1024]");
+    if (p.spec.cells < 1 || p.spec.cells > kRedactMaxCells) throw LaunchUnsupported("redact: cells must be in [1, 64]");
+    if (p.track_state && (p.max_tracks < 1 || p.max_tracks > kTrackMaxTracks)) throw LaunchUnsupported("redact: max_tracks must be in [1, 256]");
+}
+static int redact_per_image(const RedactParams &p) {
+    const int items = p.spec.max_regions * p.spec.cells * p.spec.cells;
+    return items < kRedactItemsPerImage ? items : kRedactItemsPerImage;
+}
+static int redact_grid(const RedactParams &p) {
+    const long total = (long)p.n * redact_per_image(p);
+    return (int)(total < kRedactMaxGrid ? total : kRedactMaxGrid);
+}
+
+void launch_redact_regions(hipStream_t s, const RedactParams &p) {
+    if (p.n <= 0) return;
+    redact_check(p);
+    hipLaunchKernelGGL(redact_regions_kernel, dim3(p.n), dim3(kThreads), 0, s, p);
+}
+void launch_redact_mean(hipStream_t s, const RedactParams &p) {
+    if (p.n <= 0 || p.spec.mode != RF_REDACT_PIXELATE) return;
+    redact_check(p);
+    hipLaunchKernelGGL(redact_mean_kernel, dim3(redact_grid(p)), dim3(kThreads), 0, s, p, redact_per_image(p));
+}
+void launch_redact_write(hipStream_t s, const RedactParams &p) {
+    if (p.n <= 0) return;
+    redact_check(p);
+    hipLaunchKernelGGL(redact_write_kernel, dim3(redact_grid(p)), dim3(kThreads), 0, s, p, redact_per_image(p));
+}
+
 #ifdef RF_KERNEL_TRACE
 extern "C" int rf_trace_select(int kernel_id, unsigned grid) {
     static unsigned long long zeros[kTraceBlocks * kTraceSlots];

@@ -14,8 +14,8 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (rf_face, rf_face_batch_spec, rf_face_gate, rf_face_quality, rf_options, rf_tile_spec, rf_track, rf_track_spec,
-                   rf_track_tag)
+from ._lib import (rf_face, rf_face_batch_spec, rf_face_gate, rf_face_quality, rf_options, rf_redact_spec, rf_tile_spec, rf_track,
+                   rf_track_spec, rf_track_tag)
 
 PRECISION_FP32, PRECISION_FP16, PRECISION_INT8 = 0, 1, 2
 
@@ -241,6 +241,58 @@ def track_step(table: np.ndarray, frames: int, next_id: int, faces, coord_scale:
     return tags[:count], ended[:min(ne.value, cap_ended)], f.value, nid.value, st == _lib.RF_ERR_TRUNCATED
 
 
+REDACT_PIXELATE, REDACT_FILL = _lib.RF_REDACT_PIXELATE, _lib.RF_REDACT_FILL
+REDACT_RECT, REDACT_ELLIPSE = _lib.RF_REDACT_RECT, _lib.RF_REDACT_ELLIPSE
+
+
+def redact_spec(mode: int = 0, shape: int = 0, cells: int = 0, margin: float = 0.0, fill=(0, 0, 0), max_regions: int = 0,
+                coast: int = 0) -> rf_redact_spec:
+    """rf_redact_spec; 0 = the default (pixelate, rectangle, 8 cells, margin 0.2 -- negative = none, max_detections regions, coast = the
+    tracker's max_missed -- negative = no coasting regions)"""
+    s = rf_redact_spec()
+    s.struct_size = C.sizeof(rf_redact_spec)
+    s.mode, s.shape, s.cells, s.margin, s.max_regions, s.coast = int(mode), int(shape), int(cells), float(margin), int(max_regions), int(coast)
+    s.fill[0], s.fill[1], s.fill[2] = (int(v) for v in fill)
+    return s
+
+
+def _as_redact_spec(spec):
+    if spec is None or isinstance(spec, rf_redact_spec):
+        return spec
+    return redact_spec(**spec)
+
+
+def redact_region(face, rows: int, cols: int, coord_scale: float = 1.0, **spec):
+    """rf_redact_region (host only, no GPU): (valid, [ux0, uy0, ux1, uy1, cx0, cy0, cx1, cy1, c]) of one face; keywords as redact_spec()"""
+    lib = _lib.load_library()
+    f = rf_face.from_buffer_copy(_face_rows([face])[0].tobytes())
+    out = (C.c_int * 9)()
+    st = lib.rf_redact_region(C.byref(redact_spec(**spec)), C.byref(f), float(coord_scale), int(rows), int(cols), out)
+    if st < 0:
+        raise _lib.RFError(st, "rf_redact_region: bad spec or argument")
+    return bool(st), np.array(out, np.int32)
+
+
+def redact_host(img: np.ndarray, faces, coord_scale: float = 1.0, **spec):
+    """rf_redact_host (host only, no GPU): redacts a uint8 H x W x 3 array (any row stride) in place at the given faces.  Returns
+    (pixels per region, truncated); keywords as redact_spec()."""
+    lib = _lib.load_library()
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3 or (img.size and (img.strides[2] != 1 or img.strides[1] != 3)):
+        raise ValueError("the frame must be uint8 H x W x 3 with dense pixels (CV_8UC3, BGR)")
+    if not img.flags.writeable:
+        raise ValueError("the frame is redacted in place: it must be writeable")
+    rows_f = _face_rows(faces)
+    k = len(rows_f)
+    pixels = np.zeros(max(k, 1), np.int32)
+    flat = np.ascontiguousarray(rows_f) if k else np.zeros((1, 15), np.float32)
+    st = lib.rf_redact_host(C.byref(redact_spec(**spec)), C.c_void_p(img.ctypes.data if img.size else None), img.shape[0], img.shape[1],
+                            img.strides[0] if img.size else 0, flat.ctypes.data_as(C.POINTER(rf_face)), k, float(coord_scale),
+                            pixels.ctypes.data_as(C.POINTER(C.c_int32)))
+    if st < 0 and st != _lib.RF_ERR_TRUNCATED:
+        raise _lib.RFError(st, "rf_redact_host: bad spec or argument")
+    return pixels[:k], st == _lib.RF_ERR_TRUNCATED
+
+
 class Tracker:
     """rf_tracker: per-stream track tables that live in device memory between calls (RetinaFace.tracker() creates one).  After every
     tracked call last_tags ((n, cap) TRACK_TAG_DTYPE), last_ended ((n, cap_ended) TRACK_DTYPE) and last_ended_counts hold the call's
@@ -302,6 +354,33 @@ class Tracker:
                                                          mf, tags, ended, ce, ec), self._det._h)
         self.truncated = st == _lib.RF_ERR_TRUNCATED
         return self._results(n, counts, cap)
+
+    def detect_redacted_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], streams: Sequence[int],
+                               threshold: float = 0.5, steps: Optional[Sequence[int]] = None, cap_ended: Optional[int] = None, spec=None):
+        """rf_detect_track_redact_batch_device: RetinaFace.detect_tracked_device + redaction in place, the coasting tracks of each
+        stream included (each stream at most once per call).  Returns (detections, tags, ended); last_pixels / last_region_counts
+        hold the redaction's results."""
+        det = self._det
+        n = len(ptrs)
+        p = (C.c_void_p * max(n, 1))(*ptrs)
+        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
+        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        sp = _as_redact_spec(spec)
+        mr = det._redact_regions(sp)
+        self.last_pixels = np.zeros((max(n, 1), mr), np.int32)
+        self.last_region_counts = np.zeros(max(n, 1), np.int32)
+        cap = det.max_detections
+        out = (rf_face * max(n * cap, 1))()
+        counts = (C.c_int * max(n, 1))()
+        t, _, tags, ended, ce, ec = self._buffers(n, cap, cap_ended)
+        st = _lib.check(self._lib.rf_detect_track_redact_batch_device(
+            det._h, p, r, c, s, n, float(threshold), out, cap, counts, t, (C.c_int * max(n, 1))(*streams), tags, ended, ce, ec,
+            C.byref(sp) if sp is not None else None, self.last_pixels.ctypes.data_as(C.POINTER(C.c_int32)),
+            self.last_region_counts.ctypes.data_as(C.POINTER(C.c_int))), det._h)
+        det.truncated = self.truncated = st == _lib.RF_ERR_TRUNCATED
+        det.last_out = _faces_to_array(out, max(n * cap, 1)).reshape(max(n, 1), cap, 15)
+        det.last_counts = [int(counts[i]) for i in range(n)]
+        return (det._collect(out, counts, n, cap),) + self._results(n, counts, cap)
 
     def read(self, stream: int):
         """rf_tracker_read: (table, frames, next_id) of a stream"""
@@ -843,6 +922,95 @@ class RetinaFace:
         if len(res) == 4:
             res = res[:3] + ([res[3][i, :min(counts[i], res[3].shape[1], cap)] for i in range(n)],)
         return (self._collect(out, counts, n, cap),) + res + tracker._results(n, counts, cap)
+
+    # ------------------------------------------------------------------ face redaction
+    def _redact_regions(self, sp) -> int:
+        return int(sp.max_regions) if sp is not None and sp.max_regions else min(self.max_detections, 1024)
+
+    def redact_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], faces, *, steps: Optional[Sequence[int]] = None,
+                      coord_scale: Optional[Sequence[float]] = None, spec=None, tracker: Optional[Tracker] = None,
+                      streams: Optional[Sequence[int]] = None, cap_per_image: Optional[int] = None):
+        """rf_redact_device: redacts faces the caller supplies in place in device-resident frames; faces[i]: the faces of image i (a
+        (k, 15) array, rows or Detections).  spec: redact_spec() or its keywords as a dict.  With a tracker, streams[i] names the stream
+        whose coasting tracks are redacted too (-1 = faces only).  Returns (pixels (n, max_regions) int32, region_counts (n,) int32);
+        truncated says whether a region list was cut."""
+        n = len(ptrs)
+        per = [_face_rows(f) for f in faces]
+        if len(per) != n:
+            raise ValueError("faces must hold one entry per frame")
+        cap = int(cap_per_image) if cap_per_image is not None else max([len(r) for r in per] + [1])
+        flat = np.zeros((max(n, 1), cap, 15), np.float32)
+        counts = (C.c_int * max(n, 1))()
+        for i, r in enumerate(per):
+            flat[i, :min(len(r), cap)] = r[:cap]
+            counts[i] = len(r)
+        p = (C.c_void_p * max(n, 1))(*ptrs)
+        r_, c_ = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
+        s_ = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        cs = (C.c_float * max(n, 1))(*[float(v) for v in coord_scale]) if coord_scale is not None else None
+        sp = _as_redact_spec(spec)
+        pixels = np.zeros((max(n, 1), self._redact_regions(sp)), np.int32)
+        rc = np.zeros(max(n, 1), np.int32)
+        sv = (C.c_int * max(n, 1))(*streams) if streams is not None else None
+        st = _lib.check(self._lib.rf_redact_device(
+            self._h, p, r_, c_, s_, n, flat.ctypes.data_as(C.POINTER(rf_face)), cap, counts, cs, C.byref(sp) if sp is not None else None,
+            tracker._t if tracker is not None else None, sv, pixels.ctypes.data_as(C.POINTER(C.c_int32)),
+            rc.ctypes.data_as(C.POINTER(C.c_int))), self._h)
+        self.truncated = st == _lib.RF_ERR_TRUNCATED
+        return pixels[:n], rc[:n]
+
+    def redact_last_launch_ms(self) -> float:
+        """rf_redact_last_launch_ms: HIP-event time of the redaction launches of the last redact_device call"""
+        ms = C.c_float()
+        _lib.check(self._lib.rf_redact_last_launch_ms(self._h, C.byref(ms)), self._h)
+        return float(ms.value)
+
+    def detect_redacted_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], threshold: float = 0.5,
+                               steps: Optional[Sequence[int]] = None, spec=None) -> List[List[Detection]]:
+        """rf_detect_redact_batch_device: detect_device + redaction of what it finds, in place in the device frames.  last_pixels holds
+        the pixels every region owns ((n, max_regions) int32)."""
+        n = len(ptrs)
+        p = (C.c_void_p * max(n, 1))(*ptrs)
+        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
+        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        sp = _as_redact_spec(spec)
+        self.last_pixels = np.zeros((max(n, 1), self._redact_regions(sp)), np.int32)
+        cap = self.max_detections
+        out = (rf_face * max(n * cap, 1))()
+        counts = (C.c_int * max(n, 1))()
+        st = _lib.check(self._lib.rf_detect_redact_batch_device(self._h, p, r, c, s, n, float(threshold), out, cap, counts,
+                                                                C.byref(sp) if sp is not None else None,
+                                                                self.last_pixels.ctypes.data_as(C.POINTER(C.c_int32))), self._h)
+        self.truncated = st == _lib.RF_ERR_TRUNCATED
+        self.last_out = _faces_to_array(out, max(n * cap, 1)).reshape(max(n, 1), cap, 15)
+        self.last_counts = [int(counts[i]) for i in range(n)]
+        return self._collect(out, counts, n, cap)
+
+    def detect_redacted(self, imgs: Sequence[np.ndarray], threshold: float = 0.5, spec=None) -> List[List[Detection]]:
+        """rf_detect_redact_batch: detectBatchImages + redaction; the frames (uint8 H x W x 3, dense pixels, any row stride, writeable)
+        are redacted in place."""
+        n = len(imgs)
+        ptrs = (C.c_void_p * max(n, 1))()
+        rows, cols, steps = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
+        for i, im in enumerate(imgs):
+            if im is None or im.size == 0:
+                ptrs[i], rows[i], cols[i], steps[i] = None, 0, 0, 0
+                continue
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 or im.strides[2] != 1 or im.strides[1] != 3:
+                raise ValueError("frames must be uint8 H x W x 3 with dense pixels (CV_8UC3, BGR)")
+            if not im.flags.writeable:
+                raise ValueError("frames are redacted in place: they must be writeable")
+            ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
+        sp = _as_redact_spec(spec)
+        self.last_pixels = np.zeros((max(n, 1), self._redact_regions(sp)), np.int32)
+        cap = self.max_detections
+        out = (rf_face * max(n * cap, 1))()
+        counts = (C.c_int * max(n, 1))()
+        st = _lib.check(self._lib.rf_detect_redact_batch(self._h, ptrs, rows, cols, steps, n, float(threshold), out, cap, counts,
+                                                         C.byref(sp) if sp is not None else None, ptrs, steps,
+                                                         self.last_pixels.ctypes.data_as(C.POINTER(C.c_int32))), self._h)
+        self.truncated = st == _lib.RF_ERR_TRUNCATED
+        return self._collect(out, counts, n, cap)
 
     def enqueue_device(self, ptrs, rows, cols, threshold: float = 0.5) -> int:
         n = len(ptrs)
