@@ -96,6 +96,14 @@ public:
     void detectTiled(const vector<cv::Mat> &imgs, float threshold = 0.5, const rf_tile_spec *spec = nullptr);
     const vector<vector<int>> &tileSources() const { return tileSrc_; }
 
+    /* additive: flip test-time augmentation (rf_detect_tta_batch): every frame is also detected mirrored left-right, the mirrored faces
+       are moved back and overlapping boxes are merged on the device into a score-weighted mean.  Fills lastBatchResult() with the merged
+       faces in SOURCE-FRAME pixels (at most spec->max_faces per frame); ttaVotes() holds, per frame, how many candidates each face
+       merged, ttaPasses() the pass (0: the frame, 1: mirrored) its head came from.  spec may be nullptr (the defaults). */
+    void detectTta(const vector<cv::Mat> &imgs, float threshold = 0.5, const rf_tta_spec *spec = nullptr);
+    const vector<vector<int>> &ttaVotes() const { return ttaVotes_; }
+    const vector<vector<int>> &ttaPasses() const { return ttaPasses_; }
+
     /* additive: face tracks (rf_tracker_create / rf_detect_track_batch): createTracker() makes a tracker on this handle (spec may be
        nullptr: the defaults; the destructor frees it); detectTracked() is detectBatchImages() plus one frame step per image of stream
        streams[i] (-1: not tracked), with the tracks in source-frame pixels.  lastTrackTags()[i][k] is the tag of face k of
@@ -136,6 +144,7 @@ private:
     vector<rf_face_quality> faceQuality_;
     int faceQualityStride_ = 0;
     vector<vector<int>> tileSrc_;
+    vector<vector<int>> ttaVotes_, ttaPasses_;
     vector<vector<rf_track_tag>> trackTags_;
     vector<vector<rf_track>> trackEnded_;
     vector<vector<int32_t>> redactPixels_;

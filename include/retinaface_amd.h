@@ -585,6 +585,69 @@ int rf_detect_track_redact_batch_device(rf_handle h, void *const *d_bgr, const i
                                         const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_counts,
                                         const rf_redact_spec *spec, int32_t *pixels, int *region_counts);
 
+/* ---- Flip test-time augmentation with box voting: every frame is detected as it is and mirrored left-right, the mirrored faces are
+ * moved back into the frame, and overlapping boxes of both passes are merged on the device into a score-weighted mean (DESIGN.md "Flip
+ * test-time augmentation" holds the definition; tests/tta_ref.py restates it in numpy; every result is byte-exact against it):
+ *   passes   pass 0 is the frame; pass 1 (flip on) the frame mirrored, M[y][x] = F[y][cols - 1 - x].  Over a call the passes are
+ *            frame-major: f0, f0 mirrored, f1, f1 mirrored ...  The result of a pass is exactly what rf_detect_batch_device returns for
+ *            that image at the call's threshold -- to the byte when that ONE call holds all passes of the TTA call in that order, the
+ *            mirrors as dense frames of their own (the caveat of the tiled call's views: the last bits of an image's result can depend on
+ *            what shares its launch).  Frames larger than the net are shrunk as always, in both passes.  A NULL / 0 x 0 frame finds nothing.
+ *   mapping  face k of pass p: all 14 coordinates get one fp32 multiply by rf_frame_scale(rows, cols) (also when it is 1).  For p = 1,
+ *            with c = (float)(cols - 1): x1' = c - x2, x2' = c - x1, px'[i] = c - px[perm[i]], py'[i] = py[perm[i]], perm = {1, 0, 2, 4, 3}
+ *            (left and right eye, left and right mouth corner change places): one fp32 subtract per x coordinate; y and the score are
+ *            untouched.  Results are in SOURCE-FRAME pixels: their coord_scale for the alignment and face-batch calls is 1.
+ *   merge    per frame, over the mapped faces of its passes: order by score descending (bit order), then g = p * max_detections + k
+ *            ascending; greedy suppression exactly as the detector's NMS (+1-pixel areas, skipped when w <= 0 || h <= 0, strict
+ *            > nms_threshold of the handle).  The CLUSTER of a kept head is the head and every candidate it suppresses.  vote off: the
+ *            output is the heads.  vote on: a head keeps its score and g, and each of its 14 coordinates q becomes (float)(acc_q / sw),
+ *            sw = sum (double)s_m, acc_q = sum (double)s_m * (double)v_mq over the members in the total order, head first, one double
+ *            rounding per add (a product of two floats is exact in double).  A head without other members keeps its bytes.
+ *   outputs  counts[i]: the true number of heads; out[i * cap_per_image + k]: the first min(counts[i], cap_per_image, max_faces) in
+ *            merge order; votes (may be NULL; same indexing): the members of each; src_pass (may be NULL): g / max_detections of the head.
+ *   caps     RF_ERR_TRUNCATED as for the tiled call: a pass whose own result was truncated, a frame with more than 4096 candidates
+ *            (its faces are then unspecified, the other frames valid), a list that max_faces or cap_per_image cut.
+ * There is no on-device minimum-votes filter: `votes` lets the caller choose. */
+typedef struct rf_tta_spec {
+    uint32_t struct_size;   /* sizeof(rf_tta_spec) */
+    int32_t flip;           /* 0 / 1 = also detect the frame mirrored; 2 = off (one pass per frame) */
+    int32_t vote;           /* 0 / 1 = kept boxes become the score-weighted mean of their cluster; 2 = off (plain greedy NMS) */
+    int32_t max_faces;      /* merged faces kept per frame on the device, 1..4096; 0 = the engine's max_detections */
+} rf_tta_spec;
+
+/* Host only, no GPU, no handle -- the same code the kernels run, compiled for the host.
+ * rf_tta_map_face: the mapping of one face of pass `pass` (0 or 1) of a rows x cols frame at a net_h x net_w net (out may equal in).
+ * rf_tta_merge_host: mapping and merge of ONE frame: pass p holds pass_counts[p] faces (clamped to max_detections) at
+ * faces[p * max_detections + k]; two passes, one with flip off.  spec may be NULL (max_faces 0 stands for max_detections).  *count is the
+ * true number of heads; out / votes / src_pass (the last two may be NULL) receive the first min(*count, cap, max_faces).  Returns RF_OK,
+ * RF_ERR_TRUNCATED (a pass count above max_detections, or a cut list) or RF_ERR_INVALID_ARG. */
+int rf_tta_map_face(int rows, int cols, int net_h, int net_w, int pass, const rf_face *in, rf_face *out);
+int rf_tta_merge_host(const rf_tta_spec *spec, int rows, int cols, int net_h, int net_w, float nms_threshold, int max_detections,
+                      const rf_face *faces, const int *pass_counts, rf_face *out, int cap, int *count, int *votes, int *src_pass);
+
+/* The mirror kernel on its own: d_dst row y (at d_dst + y * dst_step, cols * 3 bytes; bytes beyond them are untouched) is row y of the
+ * BGR frame d_src (row pitch `step`, any pointer alignment; ROI views are legal) mirrored left-right.  Synchronous. */
+int rf_mirror_device(rf_handle h, const void *d_src, int rows, int cols, int step, void *d_dst, int dst_step);
+
+/* TTA detection of frames resident on the engine's device (frame limits as rf_detect_batch_device).  The mirrored copies are made on
+ * the device in front of the call's first detection launch; the passes of all frames go through the engine's ordinary launches; a
+ * gather kernel behind each launch applies the mapping, and one merge launch behind the call's last launch waits for them on the device
+ * -- no host synchronisation in between.  spec may be NULL.  A bad spec is refused before any state changes.  Multi-device handles
+ * return RF_ERR_UNSUPPORTED from this call, the next two and rf_mirror_device.  rf_last_anchor_indices / rf_last_candidate_counts afterwards describe
+ * the call's PASSES. */
+int rf_detect_tta_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                               float threshold, const rf_tta_spec *spec, rf_face *out, int cap_per_image, int *counts, int *votes,
+                               int *src_pass);
+
+/* The same with frames in HOST memory (rf_detect_batch's convention): each frame is uploaded once, densely. */
+int rf_detect_tta_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                        float threshold, const rf_tta_spec *spec, rf_face *out, int cap_per_image, int *counts, int *votes, int *src_pass);
+
+/* Mapping and merge of per-pass faces the CALLER supplies (host memory): with P = 2 (flip off: 1) passes per frame, pass p of frame i
+ * holds pass_counts[i * P + p] faces (clamped to max_detections) at faces[(i * P + p) * max_detections + k].  No forward pass runs. */
+int rf_tta_merge_device(rf_handle h, const int *rows, const int *cols, int n, const rf_tta_spec *spec, const rf_face *faces,
+                        const int *pass_counts, rf_face *out, int cap_per_image, int *counts, int *votes, int *src_pass);
+
 /* Asynchronous form of rf_detect_batch_device for serving loops: enqueue returns as soon as the
  * batch is queued on the engine's stream (n <= max_batch); `ticket` identifies one of
  * rf_num_slots() result slots.  rf_wait blocks until that batch has finished and copies its results.

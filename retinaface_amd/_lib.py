@@ -83,6 +83,10 @@ RF_REDACT_RECT, RF_REDACT_ELLIPSE = 0, 1
 
 RF_TRACK_NEW, RF_TRACK_CONFIRMED, RF_TRACK_BEST, RF_TRACK_UNTRACKED, RF_TRACK_OVERFLOW = 1, 2, 4, 8, 16
 
+class rf_tta_spec(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flip", C.c_int32), ("vote", C.c_int32), ("max_faces", C.c_int32)]
+
+
 RF_GATE_INVALID, RF_GATE_SHARPNESS, RF_GATE_IOD, RF_GATE_YAW, RF_GATE_ROLL, RF_GATE_COVERED, RF_GATE_DARK, RF_GATE_BRIGHT = (
     1, 2, 4, 8, 16, 32, 64, 128)
 
@@ -190,6 +194,16 @@ SYMBOLS = {
                                                       C.c_float, _PP(rf_face), C.c_int, _PP(C.c_int), C.c_void_p, _PP(C.c_int),
                                                       _PP(rf_track_tag), _PP(rf_track), C.c_int, _PP(C.c_int), _PP(rf_redact_spec),
                                                       _PP(C.c_int32), _PP(C.c_int)]),
+    "rf_tta_map_face": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _PP(rf_face), _PP(rf_face)]),
+    "rf_tta_merge_host": (C.c_int, [_PP(rf_tta_spec), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _PP(rf_face), _PP(C.c_int),
+                                    _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int)]),
+    "rf_mirror_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    "rf_detect_tta_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                             C.c_float, _PP(rf_tta_spec), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int)]),
+    "rf_detect_tta_batch": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                      C.c_float, _PP(rf_tta_spec), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int)]),
+    "rf_tta_merge_device": (C.c_int, [C.c_void_p, _PP(C.c_int), _PP(C.c_int), C.c_int, _PP(rf_tta_spec), _PP(rf_face), _PP(C.c_int),
+                                      _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int)]),
     "rf_num_slots": (C.c_int, [C.c_void_p]),
     "rf_enqueue_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int),
                                           C.c_int, C.c_float, _PP(C.c_int)]),

@@ -836,6 +836,112 @@ int rf_detect_track_redact_batch_device(rf_handle h, void *const *d_bgr, const i
     });
 }
 
+// ---- flip test-time augmentation (tta.h)
+int rf_tta_map_face(int rows, int cols, int net_h, int net_w, int pass, const rf_face *in, rf_face *out) {
+    if (!in || !out || rows <= 0 || cols <= 0 || net_h <= 0 || net_w <= 0 || pass < 0 || pass > 1) return RF_ERR_INVALID_ARG;
+    if (rows > 4096 * 3072 / cols) return RF_ERR_INVALID_ARG;
+    rf::TtaEntry e{0, rows, cols, pass, rf::tile_frame_scale(rows, cols, net_h, net_w)};
+    float f[15];
+    memcpy(f, in, sizeof(f));
+    rf::tta_map_face(e, f, f);
+    memcpy(out, f, sizeof(f));
+    return RF_OK;
+}
+
+int rf_tta_merge_host(const rf_tta_spec *spec, int rows, int cols, int net_h, int net_w, float nms_threshold, int max_detections,
+                      const rf_face *faces, const int *pass_counts, rf_face *out, int cap, int *count, int *votes, int *src_pass) {
+    rf::TtaSpec sp;
+    if (max_detections < 1 || max_detections > rf::kTtaMaxFaces || rf::tta_spec_resolve(spec, max_detections, &sp)) return RF_ERR_INVALID_ARG;
+    if (!faces || !pass_counts || !count || cap < 0 || (cap > 0 && !out) || rows < 0 || cols < 0 || net_h <= 0 || net_w <= 0)
+        return RF_ERR_INVALID_ARG;
+    if (cols > 0 && rows > 4096 * 3072 / cols) return RF_ERR_INVALID_ARG;
+    for (int p = 0; p < sp.passes(); p++)
+        if (pass_counts[p] < 0) return RF_ERR_INVALID_ARG;
+    bool truncated = false;
+    std::vector<float> cand;
+    std::vector<int> g;
+    if (rows > 0 && cols > 0) {
+        for (int p = 0; p < sp.passes(); p++) {
+            const rf::TtaEntry e{0, rows, cols, p, rf::tile_frame_scale(rows, cols, net_h, net_w)};
+            if (pass_counts[p] > max_detections) truncated = true;
+            for (int k = 0; k < pass_counts[p] && k < max_detections; k++) {
+                float f[15];
+                memcpy(f, &faces[(size_t)p * max_detections + k], sizeof(f));
+                rf::tta_map_face(e, f, f);
+                cand.insert(cand.end(), f, f + 15);
+                g.push_back(p * max_detections + k);
+            }
+        }
+    }
+    const int limit = cap < sp.max_faces ? cap : sp.max_faces;
+    std::vector<float> merged((size_t)limit * 15 + 1);
+    std::vector<int> vt((size_t)limit + 1), hg((size_t)limit + 1);
+    const int heads = rf::tta_merge_candidates(cand, g, nms_threshold, sp.vote != 0, limit, merged.data(), vt.data(), hg.data());
+    *count = heads;
+    for (int k = 0; k < heads && k < limit; k++) {
+        memset(&out[k], 0, sizeof(rf_face));
+        memcpy(&out[k], &merged[(size_t)k * 15], 15 * sizeof(float));
+        if (votes) votes[k] = vt[k];
+        if (src_pass) src_pass[k] = hg[k] / max_detections;
+    }
+    return truncated || heads > limit ? RF_ERR_TRUNCATED : RF_OK;
+}
+
+namespace {
+// a caller's TTA spec with its defaults applied; refused before the engine is touched
+void tta_request(rf_handle h, const rf_tta_spec *spec, int *votes, int *src_pass, rf::TtaRequest *rq) {
+    if (const char *bad = rf::tta_spec_resolve(spec, h->eng->default_max_faces(), &rq->spec)) throw rf::ArgError(bad);
+    rq->votes = votes;
+    rq->src_pass = src_pass;
+}
+
+int detect_tta_common(rf_handle h, const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,
+                      float thr, const rf_tta_spec *spec, rf_face *out, int cap, int *counts, int *votes, int *src_pass) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        rf::TtaRequest rq;
+        tta_request(h, spec, votes, src_pass, &rq);
+        bool tr = false;
+        h->eng->detect_tta(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, rq);
+        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+}  // namespace
+
+int rf_mirror_device(rf_handle h, const void *d_src, int rows, int cols, int step, void *d_dst, int dst_step) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        h->eng->mirror(d_src, rows, cols, step, d_dst, dst_step);
+        return RF_OK;
+    });
+}
+
+int rf_detect_tta_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                               float threshold, const rf_tta_spec *spec, rf_face *out, int cap_per_image, int *counts, int *votes,
+                               int *src_pass) {
+    return detect_tta_common(h, (const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, spec, out, cap_per_image, counts, votes,
+                             src_pass);
+}
+
+int rf_detect_tta_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                        float threshold, const rf_tta_spec *spec, rf_face *out, int cap_per_image, int *counts, int *votes, int *src_pass) {
+    return detect_tta_common(h, bgr, rows, cols, steps, n, false, threshold, spec, out, cap_per_image, counts, votes, src_pass);
+}
+
+int rf_tta_merge_device(rf_handle h, const int *rows, const int *cols, int n, const rf_tta_spec *spec, const rf_face *faces,
+                        const int *pass_counts, rf_face *out, int cap_per_image, int *counts, int *votes, int *src_pass) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        rf::TtaRequest rq;
+        tta_request(h, spec, votes, src_pass, &rq);
+        bool tr = false;
+        h->eng->tta_merge(rows, cols, n, rq, faces, pass_counts, out, cap_per_image, counts, &tr);
+        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+
 int rf_num_slots(rf_handle h) { return h ? h->eng->num_slots() : RF_ERR_INVALID_ARG; }
 
 int rf_enqueue_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps,

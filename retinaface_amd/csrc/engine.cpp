@@ -208,11 +208,13 @@ public:
         for (void *p : host_allocs_) (void)hipHostFree(p);
         if (align_stream_) { (void)hipStreamSynchronize(align_stream_); (void)hipStreamDestroy(align_stream_); }
         for (DeviceScratch *b : {&align_crops_, &align_mats_, &align_tab_, &fb_state_, &fq_records_, &fq_packed_, &fq_offsets_, &tile_cand_, &tile_count_, &tile_out_,
-                                 &tile_outcount_, &tile_tab_, &tile_frames_, &red_regions_, &red_counts_, &red_cells_, &red_frames_}) b->release();
-        for (HostScratch *b : {&trk_tags_, &trk_ended_, &trk_counts_}) b->release();
+                                 &tile_outcount_, &tile_tab_, &tile_frames_, &tta_cand_, &tta_count_, &tta_frames_, &tta_mirror_,
+                                 &red_regions_, &red_counts_, &red_cells_, &red_frames_}) b->release();
+        for (HostScratch *b : {&trk_tags_, &trk_ended_, &trk_counts_, &tta_out_, &tta_votes_, &tta_outcount_}) b->release();
         for (auto &t : trackers_) t->state.release();
         for (hipEvent_t e : trk_ev_) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : red_ev_) if (e) (void)hipEventDestroy(e);
+        if (tta_mirror_done_) (void)hipEventDestroy(tta_mirror_done_);
         kind_.arena->release();
         for (auto &e : prof_ev_) (void)hipEventDestroy(e);
     }
@@ -817,6 +819,225 @@ public:
         tile_copy_out(n, rq, out, cap_per_image, counts, truncated);
     }
 
+    // -------------------------------------------------------------------------------- flip test-time augmentation
+    // The passes of a call's frames as one table, frame-major (frame i: pass 0, then with flip on pass 1).  A NULL / empty frame
+    // keeps its passes, which gather nothing (frame = -1).  `have_ptrs` false: tta_merge(), which has no pixels.
+    void tta_build_passes(const TtaSpec &sp, const uint8_t *const *frames, bool have_ptrs, const int *rows, const int *cols, int n,
+                          std::vector<TtaEntry> *entries) const {
+        entries->clear();
+        for (int i = 0; i < n; i++) {
+            const bool empty = (have_ptrs && !frames[i]) || rows[i] <= 0 || cols[i] <= 0;
+            if (!empty && rows[i] > 4096 * 3072 / cols[i]) throw ArgError("frame larger than 4096x3072 (RetinaFace.cpp:325)");
+            for (int p = 0; p < sp.passes(); p++) {
+                TtaEntry e;
+                e.frame = empty ? -1 : i; e.rows = empty ? 0 : rows[i]; e.cols = empty ? 0 : cols[i]; e.pass = p;
+                e.scale = empty ? 1.f : tile_frame_scale(rows[i], cols[i], net_h_, net_w_);
+                entries->push_back(e);
+            }
+        }
+    }
+
+    // blocks of a TTA call, sized once and reused (as tile_open): in device memory, per frame kTtaMergeCap candidate records and
+    // their counter; in pinned host memory, which the merge kernel writes straight into as the NMS kernel writes its result block
+    // (nothing reads the merged faces on the device, so no copy follows the call), max_faces merged records and member counts
+    // and the head / candidate counts.  The counters are zero between calls (the merge re-arms them); a new block, or a call that
+    // ended in an error, is zeroed here.
+    void tta_open(int n, const TtaSpec &sp) {
+        const size_t nf = (size_t)std::max(n, 1);
+        tta_cand_.reserve(nf * kTtaMergeCap * sizeof(Candidate));
+        const uint8_t *before = tta_count_.ptr;
+        tta_count_.reserve(nf * sizeof(int));
+        if (tta_count_.ptr != before) tta_dirty_ = true;
+        tta_out_.reserve(nf * sp.max_faces * sizeof(Candidate));
+        tta_votes_.reserve(nf * sp.max_faces * sizeof(int));
+        tta_outcount_.reserve(2 * nf * sizeof(int));
+        if (tta_dirty_) {
+            RF_HIP(hipDeviceSynchronize());
+            RF_HIP(hipMemset(tta_count_.ptr, 0, tta_count_.cap));
+            RF_HIP(hipDeviceSynchronize());
+            tta_dirty_ = false;
+        }
+    }
+
+    void tta_launch_gather(hipStream_t st, const uint8_t *faces, int face_stride, const int *counts, const TtaEntry *table, int passes) {
+        TtaGatherParams gp;
+        gp.faces = faces; gp.face_stride = face_stride; gp.faces_per_pass = opt_.max_detections;
+        gp.counts = counts; gp.table = table;
+        gp.n = passes; gp.rank_stride = opt_.max_detections;
+        gp.cand = (Candidate *)tta_cand_.ptr; gp.cand_count = (int *)tta_count_.ptr; gp.cap = kTtaMergeCap;
+        launch_tta_gather(st, gp);
+    }
+
+    void tta_launch_merge(hipStream_t st, int n, const TtaSpec &sp, const RunParams *d_params) {
+        VoteMergeParams vp;
+        vp.cand = (const Candidate *)tta_cand_.ptr; vp.cand_count = (int *)tta_count_.ptr; vp.cap = kTtaMergeCap;
+        vp.params = d_params;
+        vp.out = (Candidate *)tta_out_.ptr; vp.out_count = (int *)tta_outcount_.ptr; vp.out_cand_count = (int *)tta_outcount_.ptr + n;
+        vp.votes = (int *)tta_votes_.ptr;
+        vp.max_det = sp.max_faces;
+        vp.n = n;
+        launch_vote_merge(st, vp, sp.vote != 0);
+    }
+
+    // results of a finished TTA call (the host has waited for its last launch, so the pinned blocks hold them): true counts, the
+    // first min(count, max_faces, cap_per_image) faces of each frame, their member counts and passes
+    void tta_copy_out(int n, const TtaRequest &rq, rf_face *out, int cap_per_image, int *counts, bool *truncated) {
+        const int *hc = (const int *)tta_outcount_.ptr;
+        const int mf = rq.spec.max_faces;
+        for (int i = 0; i < n; i++) {
+            counts[i] = hc[i];
+            if (hc[n + i] > kTtaMergeCap || hc[i] > mf) *truncated = true;
+            if (out && std::min(hc[i], mf) > cap_per_image) *truncated = true;
+            const int k = out ? std::min(std::min(hc[i], mf), cap_per_image) : 0;
+            const Candidate *src = (const Candidate *)tta_out_.ptr + (size_t)i * mf;
+            const int *vt = (const int *)tta_votes_.ptr + (size_t)i * mf;
+            for (int j = 0; j < k; j++) {
+                memcpy(&out[(size_t)i * cap_per_image + j], &src[j], sizeof(rf_face));
+                if (rq.votes) rq.votes[(size_t)i * cap_per_image + j] = vt[j];
+                if (rq.src_pass) rq.src_pass[(size_t)i * cap_per_image + j] = src[j].anchor / opt_.max_detections;
+            }
+        }
+    }
+
+    static void tta_check_args(int n, const void *a, const void *b, const void *c, const void *d, rf_face *out, int cap_per_image,
+                               const TtaSpec &sp) {
+        if (n < 0 || (n > 0 && (!a || !b || !c || !d))) throw ArgError("null argument");
+        if (cap_per_image < 0 || (cap_per_image > 0 && !out)) throw ArgError("out is null");
+        if (sp.max_faces < 1 || sp.max_faces > kTtaMaxFaces) throw ArgError("max_faces must be in [1, 4096]");
+    }
+
+    void mirror(const void *d_src, int rows, int cols, int step, void *d_dst, int dst_step) override {
+        if (rows < 0 || cols < 0) throw ArgError("negative frame size");
+        if (rows == 0 || cols == 0) return;
+        if (!d_dst || dst_step < cols * 3) throw ArgError("mirror: null destination or dst_step < cols * 3");
+        check_frame((const uint8_t *)d_src, rows, cols, step);
+        if (!d_src) throw ArgError("null argument");
+        DeviceGuard guard(device_);
+        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+        const MirrorParams mp{(const uint8_t *)d_src, rows, cols, step, (uint8_t *)d_dst, dst_step};
+        launch_mirror_rows(align_stream_, &mp, 1);
+        RF_HIP(hipGetLastError());
+        RF_HIP(hipStreamSynchronize(align_stream_));
+    }
+
+    void detect_tta(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,
+                    float threshold, rf_face *out, int cap_per_image, int *counts, bool *truncated, const TtaRequest &rq) override {
+        *truncated = false;
+        tta_check_args(n, frames, rows, cols, counts, out, cap_per_image, rq.spec);
+        std::vector<int> st((size_t)std::max(n, 1));
+        for (int i = 0; i < n; i++) {
+            st[i] = steps ? steps[i] : cols[i] * 3;
+            check_frame(frames[i], rows[i], cols[i], st[i]);
+        }
+        std::vector<TtaEntry> entries;
+        tta_build_passes(rq.spec, frames, true, rows, cols, n, &entries);
+        if (n == 0) return;
+        DeviceGuard guard(device_);
+        const int PP = rq.spec.passes();
+        auto live = [&](int i) { return entries[(size_t)i * PP].frame >= 0; };
+        // host frames are uploaded once, densely
+        std::vector<const uint8_t *> base((size_t)n, nullptr);
+        if (!on_device) {
+            size_t bytes = 0;
+            std::vector<size_t> off((size_t)n, 0);
+            for (int i = 0; i < n; i++)
+                if (live(i)) { off[i] = bytes; bytes += align256((size_t)rows[i] * cols[i] * 3); }
+            uint8_t *d = tta_frames_.reserve(bytes);
+            for (int i = 0; i < n; i++) {
+                if (!live(i)) continue;
+                RF_HIP(hipMemcpy2D(d + off[i], (size_t)cols[i] * 3, frames[i], (size_t)st[i], (size_t)cols[i] * 3, (size_t)rows[i], hipMemcpyHostToDevice));
+                base[i] = d + off[i];
+                st[i] = cols[i] * 3;
+            }
+        } else {
+            for (int i = 0; i < n; i++) base[i] = live(i) ? frames[i] : nullptr;
+        }
+        // as in detect_tiled(): a super-batch of earlier enqueues starts now, every later launch carries passes of this call only
+        launch_pending();
+        // The mirrored copies: dense, each at a 256-byte-aligned offset of one block (what a freshly allocated dense frame looks
+        // like to conv0's staging), made on the side stream; every lane that launches a pass of the call waits for them on the device.
+        uint8_t *d_mirror = nullptr;
+        std::vector<size_t> moff((size_t)n, 0);
+        if (rq.spec.flip) {
+            size_t bytes = 0;
+            for (int i = 0; i < n; i++)
+                if (live(i)) { moff[i] = bytes; bytes += align256((size_t)rows[i] * cols[i] * 3); }
+            d_mirror = tta_mirror_.reserve(bytes);
+            if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+            if (!tta_mirror_done_) RF_HIP(hipEventCreateWithFlags(&tta_mirror_done_, hipEventDisableTiming));
+            std::vector<MirrorParams> mp;
+            for (int i = 0; i < n; i++)
+                if (live(i)) mp.push_back(MirrorParams{base[i], rows[i], cols[i], st[i], d_mirror + moff[i], cols[i] * 3});
+            launch_mirror_rows(align_stream_, mp.data(), (int)mp.size());
+            RF_HIP(hipGetLastError());
+            RF_HIP(hipEventRecord(tta_mirror_done_, align_stream_));
+        }
+        const int P = (int)entries.size();
+        std::vector<const uint8_t *> vp((size_t)P, nullptr);
+        std::vector<int> vr((size_t)P, 0), vc((size_t)P, 0), vs((size_t)P, 0), pass_counts((size_t)P);
+        for (int i = 0; i < n; i++) {
+            if (!live(i)) continue;
+            for (int p = 0; p < PP; p++) {
+                const size_t q = (size_t)i * PP + p;
+                vp[q] = p ? d_mirror + moff[i] : base[i];
+                vr[q] = rows[i]; vc[q] = cols[i]; vs[q] = p ? cols[i] * 3 : st[i];
+            }
+        }
+        tta_open(n, rq.spec);
+        tta_.rq = rq; tta_.entries.swap(entries);
+        tta_.n_frames = n; tta_.next_pass = 0;
+        tta_.lanes_used.clear();
+        tta_.wait_mirror = rq.spec.flip != 0;
+        tta_.on = true;
+        tta_dirty_ = true;                       // until the call has ended well
+        struct Off { bool &on; ~Off() { on = false; } } off_guard{tta_.on};
+        bool tr = false;
+        detect(vp.data(), vr.data(), vc.data(), vs.data(), P, true, threshold, nullptr, 0, pass_counts.data(), &tr);
+        tta_.on = false;
+        if (tta_.next_pass != P) throw HipError("test-time augmentation: the merge was not launched");
+        // every launch of the call has been waited for; the merge ran in front of the last one's `done`
+        tta_dirty_ = false;
+        *truncated = tr;
+        tta_copy_out(n, rq, out, cap_per_image, counts, truncated);
+    }
+
+    void tta_merge(const int *rows, const int *cols, int n, const TtaRequest &rq, const rf_face *faces, const int *pass_counts,
+                   rf_face *out, int cap_per_image, int *counts, bool *truncated) override {
+        *truncated = false;
+        tta_check_args(n, rows, cols, counts, faces, out, cap_per_image, rq.spec);
+        if (n > 0 && !pass_counts) throw ArgError("null argument");
+        std::vector<TtaEntry> entries;
+        tta_build_passes(rq.spec, nullptr, false, rows, cols, n, &entries);
+        if (n == 0) return;
+        const int P = (int)entries.size(), md = opt_.max_detections;
+        for (int p = 0; p < P; p++)
+            if (pass_counts[p] < 0) throw ArgError("negative face count");
+        DeviceGuard guard(device_);
+        // one table: run parameters | pass table | counts | faces (60-byte records, max_detections per pass)
+        const size_t o_tab = 256, o_cnt = o_tab + align256((size_t)P * sizeof(TtaEntry)), o_face = o_cnt + align256((size_t)P * sizeof(int)),
+                     total = o_face + (size_t)P * md * sizeof(rf_face);
+        align_host_.assign(total, 0);
+        *(RunParams *)align_host_.data() = RunParams{0.f, nms_threshold_, n, 0};
+        memcpy(align_host_.data() + o_tab, entries.data(), (size_t)P * sizeof(TtaEntry));
+        int *cnt = (int *)(align_host_.data() + o_cnt);
+        for (int p = 0; p < P; p++) {
+            cnt[p] = std::min(pass_counts[p], md);
+            if (pass_counts[p] > md) *truncated = true;
+            if (cnt[p]) memcpy(align_host_.data() + o_face + (size_t)p * md * sizeof(rf_face), faces + (size_t)p * md, (size_t)cnt[p] * sizeof(rf_face));
+        }
+        uint8_t *d_tab = align_tab_.reserve(total);
+        tta_open(n, rq.spec);
+        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+        tta_dirty_ = true;
+        RF_HIP(hipMemcpyAsync(d_tab, align_host_.data(), total, hipMemcpyHostToDevice, align_stream_));
+        tta_launch_gather(align_stream_, d_tab + o_face, (int)sizeof(rf_face), (const int *)(d_tab + o_cnt), (const TtaEntry *)(d_tab + o_tab), P);
+        tta_launch_merge(align_stream_, n, rq.spec, (const RunParams *)d_tab);
+        RF_HIP(hipGetLastError());
+        RF_HIP(hipStreamSynchronize(align_stream_));
+        tta_dirty_ = false;
+        tta_copy_out(n, rq, out, cap_per_image, counts, truncated);
+    }
+
     // -------------------------------------------------------------------------------- face tracks
     void *tracker_create(const TrackSpec &spec, int n_streams) override {
         if (n_streams < 1 || n_streams > kTrackMaxStreams) throw ArgError("n_streams must be in [1, 1024]");
@@ -1383,6 +1604,8 @@ private:
         hipEvent_t face_scan_done = nullptr;  // ... recorded behind that scan: the call's next launch (another lane) waits for it on the device
         TileEntry *h_tile_tab = nullptr;      // detect_tiled(): pinned, per image of the launch the pass it is (allocated on first use)
         hipEvent_t tile_done = nullptr;       // ... recorded behind the launch's gather: the call's merge (another lane) waits for it on the device
+        TtaEntry *h_tta_tab = nullptr;        // detect_tta(): pinned, per image of the launch the pass it is (allocated on first use)
+        hipEvent_t tta_done = nullptr;        // ... recorded behind the launch's gather, as tile_done
         uint8_t *h_track_tab = nullptr;       // detect_track(): pinned, the launch's stream table and image table (allocated on first use)
         hipEvent_t track_done = nullptr;      // ... recorded behind the launch's track kernel: the call's next track launch (another lane) waits for it
         int *h_red_streams = nullptr;         // detect_track_redact(): pinned, per image of the launch its stream (allocated on first use)
@@ -1428,6 +1651,7 @@ private:
         if (l.copy2_done) (void)hipEventDestroy(l.copy2_done);
         if (l.face_scan_done) (void)hipEventDestroy(l.face_scan_done);
         if (l.tile_done) (void)hipEventDestroy(l.tile_done);
+        if (l.tta_done) (void)hipEventDestroy(l.tta_done);
         if (l.track_done) (void)hipEventDestroy(l.track_done);
         if (l.copy2) { (void)hipStreamSynchronize(l.copy2); (void)hipStreamDestroy(l.copy2); }
         if (l.d_stage) (void)hipFree(l.d_stage);
@@ -1686,6 +1910,7 @@ private:
             RF_HIP(hipStreamWaitEvent(s.stream, s.copy2_done, 0));
             s.copy2_used = false;
         }
+        if (tta_.on && tta_.wait_mirror) RF_HIP(hipStreamWaitEvent(s.stream, tta_mirror_done_, 0));      // the launch reads mirrored copies
         double tt = trace_.on ? HostTrace::now() : 0.0;
         RF_HIP(hipMemcpyAsync(s.d_frames, s.h_frames, s.table_bytes, hipMemcpyHostToDevice, s.stream));
         trace_.add(2, tt);
@@ -1714,6 +1939,7 @@ private:
         if (align_.on) launch_lane_align(s, n);      // ordinary launches behind the graph, before `done`: nothing waits in between
         if (fb_.on) launch_lane_face_batch(s, n);
         if (tile_.on) launch_lane_tile(s, n);
+        if (tta_.on) launch_lane_tta(s, n);
         if (trk_.on) launch_lane_track(s, n);
         if (red_.on) launch_lane_redact(s, n);
         RF_HIP(hipEventRecord(s.done, s.stream));
@@ -1818,6 +2044,35 @@ private:
         const int nf = tile_.n_frames;
         tile_launch_merge(s.stream, nf, sp, s.d_params);
         if (tile_.rq.fb) launch_tiled_face_batch(s.stream, nf);
+        RF_HIP(hipGetLastError());
+    }
+
+    // The TTA launches of a super-batch of detect_tta(), as launch_lane_tile(): the gather reads the launch's faces and counts from the
+    // pinned result block and what each image of the launch is from a pinned per-lane pass table; behind the call's LAST launch this
+    // stream waits on the device for the gathers of the call's other lanes, then runs the voting merge.  No host wait anywhere.
+    void launch_lane_tta(Lane &s, int n) {
+        if (!s.h_tta_tab) {
+            void *p = nullptr;
+            RF_HIP(hipHostMalloc(&p, std::max<size_t>((size_t)cap_images_ * sizeof(TtaEntry), 256), hipHostMallocDefault));
+            s.host_allocs.push_back(p);
+            s.h_tta_tab = (TtaEntry *)p;
+            RF_HIP(hipEventCreateWithFlags(&s.tta_done, hipEventDisableTiming));
+        }
+        const int total = (int)tta_.entries.size();
+        if (n > cap_images_ || tta_.next_pass + n > total) throw HipError("test-time augmentation: a launch carries images of another call");
+        for (int i = 0; i < n; i++) s.h_tta_tab[i] = tta_.entries[tta_.next_pass + i];
+        tta_launch_gather(s.stream, (const uint8_t *)s.h_out, (int)sizeof(Candidate), s.h_counts, s.h_tta_tab, n);
+        RF_HIP(hipGetLastError());
+        tta_.next_pass += n;
+        const int me = (int)(&s - lanes_.data());
+        if (tta_.next_pass < total) {
+            RF_HIP(hipEventRecord(s.tta_done, s.stream));
+            if (std::find(tta_.lanes_used.begin(), tta_.lanes_used.end(), me) == tta_.lanes_used.end()) tta_.lanes_used.push_back(me);
+            return;
+        }
+        for (int l : tta_.lanes_used)
+            if (l != me && l < (int)lanes_.size() && lanes_[l].tta_done) RF_HIP(hipStreamWaitEvent(s.stream, lanes_[l].tta_done, 0));
+        tta_launch_merge(s.stream, tta_.n_frames, tta_.rq.spec, s.d_params);
         RF_HIP(hipGetLastError());
     }
 
@@ -2263,6 +2518,14 @@ private:
     struct { bool on = false; TileRequest rq; std::vector<TileEntry> entries; int n_frames = 0, next_pass = 0; std::vector<int> lanes_used;
              uint8_t *d_tensor = nullptr; double *d_mats = nullptr; } tile_;
 
+    // flip test-time augmentation: per frame the gathered candidates and their counter, the merged records, member counts and
+    // counts, the device copy of host frames, the mirrored copies and the event behind them; the request detect_tta() has open
+    DeviceScratch tta_cand_, tta_count_, tta_frames_, tta_mirror_;
+    hipEvent_t tta_mirror_done_ = nullptr;
+    bool tta_dirty_ = true;
+    struct { bool on = false, wait_mirror = false; TtaRequest rq; std::vector<TtaEntry> entries; int n_frames = 0, next_pass = 0;
+             std::vector<int> lanes_used; } tta_;
+
     // face tracks: the trackers of this handle, the call-level result buffers and the request a tracked call has open
     struct Tracker {
         TrackSpec spec;
@@ -2288,6 +2551,7 @@ private:
         void release() { if (ptr) (void)hipHostFree(ptr); ptr = nullptr; cap = 0; }
     };
     HostScratch trk_tags_, trk_ended_, trk_counts_;
+    HostScratch tta_out_, tta_votes_, tta_outcount_;      // detect_tta() / tta_merge(): what the voting merge writes (see tta_open)
     hipEvent_t trk_ev_[2] = {nullptr, nullptr};   // around the track launch of track_update() (tools/track_bench.py reads the time)
     float trk_launch_ms_ = -1.f;
     hipEvent_t red_ev_[2] = {nullptr, nullptr};   // around the redaction launches of redact() (tools/redact_bench.py reads the time)

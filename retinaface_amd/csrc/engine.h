@@ -102,6 +102,14 @@ struct TileRequest {
     const FaceBatchRequest *fb = nullptr;
 };
 
+// A flip-TTA call (tta.h; rf_detect_tta_batch* / rf_tta_merge_device): the validated spec and where the member count and the pass of
+// each merged face go
+struct TtaRequest {
+    TtaSpec spec;
+    int *votes = nullptr;                       // host, indexed like out, or nullptr
+    int *src_pass = nullptr;
+};
+
 // A tracked call (track.h; rf_track_update_device / rf_detect_track_*): the tracker (what tracker_create returned), the stream of every
 // image (-1 = not tracked) and where tags, ended lists and their counts go (host; each may be nullptr)
 struct TrackRequest {
@@ -174,6 +182,23 @@ public:
     virtual void tile_merge(const int *, const int *, int, const TileRequest &, const rf_face *, const int *, rf_face *, int, int *,
                             bool *) {
         throw Unsupported("tiled detection is not available on a multi-device handle");
+    }
+    // Flip test-time augmentation: every frame becomes two passes (itself and a mirrored copy made on the device in front of the
+    // call's first launch) that go through detect()'s ordinary launches; a gather launch behind each of them and one voting merge
+    // behind the last (ordered by events on the device, no host wait).  *truncated: a pass or the merge hit a cap.  Single-device
+    // engines only.
+    virtual void detect_tta(const uint8_t *const *, const int *, const int *, const int *, int, bool, float, rf_face *, int, int *,
+                            bool *, const TtaRequest &) {
+        throw Unsupported("test-time augmentation is not available on a multi-device handle");
+    }
+    // mapping and merge of per-pass faces the caller supplies (faces[(i * passes + p) * max_detections + k])
+    virtual void tta_merge(const int *, const int *, int, const TtaRequest &, const rf_face *, const int *, rf_face *, int, int *,
+                           bool *) {
+        throw Unsupported("test-time augmentation is not available on a multi-device handle");
+    }
+    // the mirror kernel on its own: a left-right mirrored copy of a device-resident frame
+    virtual void mirror(const void *, int, int, int, void *, int) {
+        throw Unsupported("test-time augmentation is not available on a multi-device handle");
     }
     // Face tracks: a tracker's state (n_streams tables) lives in device memory between calls; the track launch of a detection launch
     // follows it on its stream, the track launches of a call wait for each other on the device.  *cut: a full table or a cut ended

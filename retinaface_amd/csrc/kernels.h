@@ -12,6 +12,7 @@
 #include "face_quality.h"
 #include "redact.h"
 #include "tile.h"
+#include "tta.h"
 #include "track.h"
 
 namespace rf {
@@ -327,6 +328,40 @@ struct RedactParams {
 void launch_redact_regions(hipStream_t s, const RedactParams &p);
 void launch_redact_mean(hipStream_t s, const RedactParams &p);
 void launch_redact_write(hipStream_t s, const RedactParams &p);
+
+// ---- K_j: flip test-time augmentation (tta.h).
+//      mirror_rows: a dense left-right mirrored copy of a BGR frame (any source pitch and alignment), in front of a TTA call's launches.
+//      tta_gather:  tile_gather's shape with tta_map_face as the mapping: one workgroup per pass of the launch, g = pass * rank_stride + k.
+//      vote_merge:  nms_kernel's sort and greedy walk over the gathered candidates of a frame, which also records the head that
+//                   suppressed each candidate; a second sort groups the members by head and every kept head becomes the
+//                   score-weighted mean of its members.  One workgroup per frame; re-arms the frame counters as launch_nms does.
+struct MirrorParams {
+    const uint8_t *src; int rows, cols, step;     // row y at src + y * step
+    uint8_t *dst; int dst_step;                   // cols * 3 bytes per row are written
+};
+constexpr int kMirrorFramesPerLaunch = 16;       // frames of one launch: their descriptors travel as kernel arguments
+void launch_mirror_rows(hipStream_t s, const MirrorParams *frames, int n);
+
+struct TtaGatherParams {
+    const uint8_t *faces;                 // pass p, rank k: 15 floats at faces + (p * faces_per_pass + k) * face_stride
+    int face_stride, faces_per_pass;
+    const int *counts;                    // [n] faces of each pass (clamped to faces_per_pass here)
+    const TtaEntry *table;                // [n] what each pass is (frame < 0: skipped)
+    int n, rank_stride;                   // passes of this launch; max_detections
+    Candidate *cand; int *cand_count;     // as TileGatherParams
+    int cap;
+};
+void launch_tta_gather(hipStream_t s, const TtaGatherParams &p);
+
+struct VoteMergeParams {
+    const Candidate *cand; int *cand_count; int cap;         // cap <= 4096; the counter is reset to 0 at the end
+    const RunParams *params;                                 // nms_threshold
+    Candidate *out; int *out_count; int *out_cand_count;     // out[img * max_det + k] (anchor: g of the head); true head / candidate counts
+    int *votes;                                              // votes[img * max_det + k]: members of each returned head
+    int max_det;
+    int n;
+};
+void launch_vote_merge(hipStream_t s, const VoteMergeParams &p, bool vote);     // vote false: the heads keep their own coordinates
 
 // LDS bytes / tile geometry chosen for a layer (exposed for tests and DESIGN.md tables)
 struct TileInfo { int th, tw; size_t lds_bytes; int blocks_per_image; };

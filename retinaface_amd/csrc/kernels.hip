@@ -4928,6 +4928,313 @@ void launch_redact_write(hipStream_t s, const RedactParams &p) {
     hipLaunchKernelGGL(redact_write_kernel, dim3(redact_grid(p)), dim3(kThreads), 0, s, p, redact_per_image(p));
 }
 
+// =============================================================================================
+// K_j: flip test-time augmentation (tta.h).
+// mirror_rows_kernel: dst[y][x] = src[y][cols - 1 - x] for BGR pixels.  One thread moves four pixels = 12 bytes = three dwords: the
+//      twelve source bytes are contiguous (pixels cols - 4 - x .. cols - 1 - x), read as three dwords where the pitched source
+//      happens to be dword aligned and bytewise elsewhere; the pixels change places in registers (a dword holds parts of two
+//      pixels, so the bytes are re-packed, not the dwords swapped) and leave as three dword stores where the destination is
+//      aligned -- a dense frame at a 256-byte-aligned base with 12 | 3 * 4 * x always is -- and bytewise elsewhere.  The last
+//      cols % 4 pixels of a row go bytewise.  No byte outside the cols * 3 bytes of a row is read or written.  One launch
+//      carries up to sixteen frames (blockIdx.y), so the mirrors of a call are one or a few launches, not one per frame.
+// =============================================================================================
+struct MirrorBatch { MirrorParams f[kMirrorFramesPerLaunch]; };
+
+__global__ __launch_bounds__(kThreads) void mirror_rows_kernel(MirrorBatch batch) {
+    const MirrorParams a = batch.f[blockIdx.y];
+    const int gpr = (a.cols + 3) >> 2;                               // groups of four pixels per row
+    const long long total = (long long)a.rows * gpr;
+    for (long long item = (long long)blockIdx.x * kThreads + threadIdx.x; item < total; item += (long long)gridDim.x * kThreads) {
+        const int y = (int)(item / gpr), x = (int)(item - (long long)y * gpr) << 2;
+        const int k = a.cols - x < 4 ? a.cols - x : 4;
+        const uint8_t *sp = a.src + (size_t)y * a.step + (size_t)3 * (a.cols - x - k);
+        uint8_t *dp = a.dst + (size_t)y * a.dst_step + (size_t)3 * x;
+        if (k < 4) {
+            for (int j = 0; j < k; j++)
+                for (int c = 0; c < 3; c++) dp[3 * j + c] = sp[3 * (k - 1 - j) + c];
+            continue;
+        }
+        uint32_t w0, w1, w2;
+        if (((uintptr_t)sp & 3) == 0) {
+            const uint32_t *s4 = (const uint32_t *)sp;
+            w0 = s4[0]; w1 = s4[1]; w2 = s4[2];
+        } else {
+            w0 = sp[0] | (uint32_t)sp[1] << 8 | (uint32_t)sp[2] << 16 | (uint32_t)sp[3] << 24;
+            w1 = sp[4] | (uint32_t)sp[5] << 8 | (uint32_t)sp[6] << 16 | (uint32_t)sp[7] << 24;
+            w2 = sp[8] | (uint32_t)sp[9] << 8 | (uint32_t)sp[10] << 16 | (uint32_t)sp[11] << 24;
+        }
+        // source bytes b0 .. b11 = pixels P0 P1 P2 P3; the output is P3 P2 P1 P0 = b9 b10 b11 | b6 b7 b8 | b3 b4 b5 | b0 b1 b2
+        const uint32_t o0 = (w2 >> 8) | (w1 >> 16 << 24);                                      // b9 b10 b11 b6
+        const uint32_t o1 = (w1 >> 24) | ((w2 & 0xffu) << 8) | ((w0 >> 24) << 16) | ((w1 & 0xffu) << 24);   // b7 b8 b3 b4
+        const uint32_t o2 = ((w1 >> 8) & 0xffu) | (w0 << 8);                                   // b5 b0 b1 b2
+        if (((uintptr_t)dp & 3) == 0) {
+            uint32_t *d4 = (uint32_t *)dp;
+            d4[0] = o0; d4[1] = o1; d4[2] = o2;
+        } else {
+            for (int j = 0; j < 4; j++) {
+                dp[j] = (uint8_t)(o0 >> (8 * j)); dp[4 + j] = (uint8_t)(o1 >> (8 * j)); dp[8 + j] = (uint8_t)(o2 >> (8 * j));
+            }
+        }
+    }
+}
+
+// up to kMirrorFramesPerLaunch frames per launch (blockIdx.y), the grid sized for the largest of them: a frame's surplus workgroups
+// find no item and retire
+void launch_mirror_rows(hipStream_t s, const MirrorParams *frames, int n) {
+    for (int f0 = 0; f0 < n; f0 += kMirrorFramesPerLaunch) {
+        MirrorBatch b;
+        memset(&b, 0, sizeof(b));
+        const int m = n - f0 < kMirrorFramesPerLaunch ? n - f0 : kMirrorFramesPerLaunch;
+        long long blocks = 0;
+        for (int i = 0; i < m; i++) {
+            const MirrorParams &p = frames[f0 + i];
+            if (p.rows <= 0 || p.cols <= 0) continue;          // rows = 0: no items
+            b.f[i] = p;
+            const long long total = (long long)p.rows * ((p.cols + 3) >> 2);
+            blocks = std::max(blocks, (total + kThreads - 1) / kThreads);
+        }
+        if (!blocks) continue;
+        hipLaunchKernelGGL(mirror_rows_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536), (unsigned)m), dim3(kThreads), 0, s, b);
+    }
+}
+
+// tta_gather_kernel: tile_gather_kernel's shape -- one workgroup per pass of the launch, one face per thread, one atomic add per
+//      wavefront (ballot + popcount of the lanes below) on the frame's counter -- with tta_map_face, the code rf_tta_map_face runs on
+//      the host, as the mapping.  Nothing is dropped.  The two passes of a frame may arrive from different launches on different
+//      streams; the merge sorts on the total order (score, g), so the append order never shows.
+__global__ __launch_bounds__(kThreads) void tta_gather_kernel(TtaGatherParams a) {
+    const int p = blockIdx.x;
+    const TtaEntry e = a.table[p];
+    if (e.frame < 0) return;
+    int cnt = a.counts[p];
+    cnt = cnt < 0 ? 0 : cnt < a.faces_per_pass ? cnt : a.faces_per_pass;
+    const int lane = (int)threadIdx.x & 63;
+    Candidate *dst = a.cand + (size_t)e.frame * a.cap;
+    for (int k0 = 0; k0 < cnt; k0 += kThreads) {
+        const int k = k0 + (int)threadIdx.x;
+        const bool keep = k < cnt;
+        float f[15];
+        if (keep) {
+            const float *src = (const float *)(a.faces + ((size_t)p * a.faces_per_pass + k) * a.face_stride);
+            for (int i = 0; i < 15; i++) f[i] = src[i];
+            tta_map_face(e, f, f);
+        }
+        const unsigned long long mask = __ballot(keep);
+        if (!mask) continue;                                     // wave-uniform
+        const int leader = __ffsll((long long)mask) - 1;
+        int base = 0;
+        if (lane == leader) base = atomicAdd(a.cand_count + e.frame, __popcll(mask));
+        base = __shfl(base, leader);
+        if (!keep) continue;
+        const int pos = base + __popcll(mask & ((1ull << lane) - 1ull));
+        if (pos >= a.cap) continue;                              // the counter keeps the true number: the merge reports the overflow
+        Candidate c;
+        c.score = f[0];
+        c.x1 = f[1]; c.y1 = f[2]; c.x2 = f[3]; c.y2 = f[4];
+        for (int i = 0; i < 5; i++) { c.px[i] = f[5 + i]; c.py[i] = f[10 + i]; }
+        c.anchor = e.pass * a.rank_stride + k;
+        dst[pos] = c;
+    }
+}
+
+void launch_tta_gather(hipStream_t s, const TtaGatherParams &p) {
+    if (p.n <= 0) return;
+    hipLaunchKernelGGL(tta_gather_kernel, dim3(p.n), dim3(kThreads), 0, s, p);
+}
+
+// vote_merge_kernel: one workgroup per frame.  The first half is nms_kernel, copied (so that kernel's launches cannot change): the
+//      same three sort regimes on the key (score bits descending, g ascending) and the same greedy walk with the same suppression
+//      expression; the walk additionally writes, for every candidate, the rank of the head that kept or suppressed it (s_own, in
+//      the LDS of the sort keys, which are dead once s_slot holds the order).  Then the members are grouped by head: a second sort
+//      on (head rank << 12 | position) -- rank sort up to 256, the bitonic network above -- is stable in the total order, so a head's
+//      members are one contiguous segment with the head first (its position is the smallest).  Sixteen lanes take one head: lane 0
+//      sums the weights, lanes 1..14 one coordinate each, sequentially over the segment in double (tta_vote_add: the product of
+//      two floats is exact in double, so a fused multiply-add and a multiply plus an add give the same bits); lane 15 carries g.
+//      A head costs its own members only: 4096 singletons are 4096 one-step walks, not 4096 scans of 4096 positions.
+//      LDS is launch_nms's: the sorted keys reuse s_key, the segment starts reuse s_box (dead after the walk).
+// =============================================================================================
+__global__ __launch_bounds__(NMS_THREADS) void vote_merge_kernel(VoteMergeParams a, int vote) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int cap = a.cap;
+    unsigned long long *s_key = (unsigned long long *)smem;                 // [cap]
+    float4 *s_box = (float4 *)(s_key + cap);                                 // [cap]
+    int *s_slot = (int *)(s_box + cap);                                      // [cap]
+    int *s_kept = s_slot + cap;                                              // [max_det]
+    unsigned char *s_alive = (unsigned char *)(s_kept + a.max_det);          // [cap]
+    int *s_own = (int *)s_key;                                               // [cap]  after the sort: head rank of each position, then the keys of the second sort
+    int *s_sorted = s_own + cap;                                             // [cap]  the rank sort's destination
+    int *s_start = (int *)s_box;                                             // [cap]  after the walk: first member of each head in the grouped order
+
+    const int tid = threadIdx.x;
+    const int img = blockIdx.x;
+    const Candidate *cand = a.cand + (size_t)img * cap;
+    const float thr = a.params->nms_threshold;
+    const int n_found = a.cand_count[img];
+    int n = n_found;
+    if (n > cap) n = cap;
+    const bool small = n <= 64;
+    if (small && tid >= 64) return;
+    const int nthr = small ? 64 : NMS_THREADS;
+    if (n <= 256) {
+        for (int i = tid; i < n; i += nthr) {
+            const unsigned int sbits = __float_as_uint(cand[i].score);      // scores are positive: bit order = value order
+            s_key[i] = ((unsigned long long)(~sbits) << 32) | (unsigned int)cand[i].anchor;
+        }
+        __syncthreads();
+        for (int i = tid; i < n; i += nthr) {
+            const unsigned long long ki = s_key[i];
+            int rank = 0;
+            for (int j = 0; j < n; j++) { const unsigned long long kj = s_key[j]; rank += (kj < ki || (kj == ki && j < i)) ? 1 : 0; }
+            s_slot[rank] = i;
+        }
+        __syncthreads();
+    } else {
+        int npow = 512;
+        while (npow < n) npow <<= 1;
+        for (int i = tid; i < npow; i += nthr) {
+            unsigned long long key = ~0ull;
+            if (i < n) {
+                const unsigned int sbits = __float_as_uint(cand[i].score);
+                key = ((unsigned long long)(~sbits) << 32) | (unsigned int)cand[i].anchor;
+            }
+            s_key[i] = key;
+            s_slot[i] = i;
+        }
+        __syncthreads();
+        for (int k = 2; k <= npow; k <<= 1) {
+            for (int j = k >> 1; j > 0; j >>= 1) {
+                for (int i = tid; i < npow; i += nthr) {
+                    const int l = i ^ j;
+                    if (l > i) {
+                        const unsigned long long ki = s_key[i], kl = s_key[l];
+                        const bool up = (i & k) == 0;
+                        if ((ki > kl) == up) {
+                            s_key[i] = kl; s_key[l] = ki;
+                            const int t = s_slot[i]; s_slot[i] = s_slot[l]; s_slot[l] = t;
+                        }
+                    }
+                }
+                __syncthreads();
+            }
+        }
+    }
+    for (int i = tid; i < n; i += nthr) {
+        const Candidate *c = cand + s_slot[i];
+        s_box[i] = make_float4(c->x1, c->y1, c->x2, c->y2);
+        s_alive[i] = 1;
+    }
+    __syncthreads();                                     // s_key is dead from here: s_own / s_sorted take its place
+
+    const int lane = tid & 63;
+    int kept = 0;
+    for (int base = 0; base < n; base += 64) {
+        const int idx = base + lane;
+        unsigned long long mask = __ballot(idx < n && s_alive[idx]);
+        while (mask) {
+            const int sel = base + __ffsll((long long)mask) - 1;
+            if (tid == 0) {
+                if (kept < a.max_det) s_kept[kept] = sel;
+                s_own[sel] = kept;
+            }
+            const float4 sb = s_box[sel];
+            const float area1 = (sb.z - sb.x + 1) * (sb.w - sb.y + 1);
+            for (int i = sel + 1 + tid; i < n; i += nthr) {
+                if (!s_alive[i]) continue;
+                const float4 bi = s_box[i];
+                const float x = fmaxf(sb.x, bi.x);
+                const float y = fmaxf(sb.y, bi.y);
+                const float w = fminf(sb.z, bi.z) - x + 1;
+                const float h = fminf(sb.w, bi.w) - y + 1;
+                if (w <= 0 || h <= 0) continue;
+                const float area2 = (bi.z - bi.x + 1) * (bi.w - bi.y + 1);
+                const float inter = w * h;
+                if (inter / (area1 + area2 - inter) > thr) { s_alive[i] = 0; s_own[i] = kept; }
+            }
+            kept++;
+            __syncthreads();
+            const unsigned long long later = (sel - base) >= 63 ? 0ull : (~0ull << (sel - base + 1));
+            mask = __ballot(idx < n && s_alive[idx]) & later;
+        }
+    }
+    __syncthreads();                                     // s_box is dead from here: s_start takes its place
+
+    // group the members by head: keys (head rank << 12 | position), both below 4096
+    const int *srt;
+    if (n <= 256) {
+        for (int i = tid; i < n; i += nthr) {
+            const int ki = (s_own[i] << 12) | i;         // unique
+            int rank = 0;
+            for (int j = 0; j < n; j++) rank += ((s_own[j] << 12) | j) < ki ? 1 : 0;
+            s_sorted[rank] = ki;
+        }
+        srt = s_sorted;
+    } else {
+        int npow = 512;
+        while (npow < n) npow <<= 1;
+        for (int i = tid; i < npow; i += nthr) s_own[i] = i < n ? (s_own[i] << 12) | i : 0x7fffffff;
+        __syncthreads();
+        for (int k = 2; k <= npow; k <<= 1) {
+            for (int j = k >> 1; j > 0; j >>= 1) {
+                for (int i = tid; i < npow; i += nthr) {
+                    const int l = i ^ j;
+                    if (l > i) {
+                        const int ki = s_own[i], kl = s_own[l];
+                        const bool up = (i & k) == 0;
+                        if ((ki > kl) == up) { s_own[i] = kl; s_own[l] = ki; }
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        srt = s_own;
+    }
+    __syncthreads();
+    for (int j = tid; j < n; j += nthr) {
+        const int o = srt[j] >> 12;
+        if (j == 0 || (srt[j - 1] >> 12) != o) s_start[o] = j;
+    }
+    __syncthreads();
+
+    const int nout = kept < a.max_det ? kept : a.max_det;
+    const int f = tid & 15;
+    for (int h = tid >> 4; h < nout; h += nthr >> 4) {
+        const int b = s_start[h], e = h + 1 < kept ? s_start[h + 1] : n;
+        const float *head = (const float *)(cand + s_slot[srt[b] & 4095]);
+        double acc = 0.0;
+        if (vote && f < 15) {
+            const float s0 = head[0];
+            acc = f == 0 ? (double)s0 : tta_vote_first(s0, head[f]);
+#pragma unroll 4
+            for (int m = b + 1; m < e; m++) {
+                const float *c = (const float *)(cand + s_slot[srt[m] & 4095]);
+                const float s = c[0];
+                acc = f == 0 ? acc + (double)s : tta_vote_add(acc, s, c[f]);
+            }
+        }
+        const double sw = __shfl(acc, lane & ~15);       // the 16 lanes of a head are active together
+        uint32_t word = ((const uint32_t *)head)[f];     // score, the head's own coordinates, g
+        if (vote && f >= 1 && f < 15) word = __float_as_uint(tta_vote_result(acc, sw));
+        ((uint32_t *)(a.out + (size_t)img * a.max_det + h))[f] = word;
+        if (f == 0) a.votes[(size_t)img * a.max_det + h] = e - b;
+    }
+    if (tid == 0) {
+        a.out_count[img] = kept;
+        a.out_cand_count[img] = n_found;
+        a.cand_count[img] = 0;        // re-arm the gather's counter for the next call
+    }
+}
+
+void launch_vote_merge(hipStream_t s, const VoteMergeParams &p, bool vote) {
+    if (p.n <= 0) return;
+    if (p.cap > 4096 || (p.cap & (p.cap - 1))) throw LaunchUnsupported("vote merge: cap must be a power of two <= 4096");
+    size_t lds = (size_t)p.cap * (8 + 16 + 4 + 1) + (size_t)p.max_det * 4 + 16;
+    static std::atomic<size_t> attr_bytes[kMaxDevices] = {};
+    const int dev = launch_device();
+    if (lds > attr_bytes[dev].load(std::memory_order_acquire)) { set_max_lds(vote_merge_kernel, lds); attr_bytes[dev].store(lds, std::memory_order_release); }
+    hipLaunchKernelGGL(vote_merge_kernel, dim3(p.n), dim3(NMS_THREADS), lds, s, p, vote ? 1 : 0);
+}
+
 #ifdef RF_KERNEL_TRACE
 extern "C" int rf_trace_select(int kernel_id, unsigned grid) {
     static unsigned long long zeros[kTraceBlocks * kTraceSlots];

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (rf_face, rf_face_batch_spec, rf_face_gate, rf_face_quality, rf_options, rf_redact_spec, rf_tile_spec, rf_track,
-                   rf_track_spec, rf_track_tag)
+                   rf_track_spec, rf_track_tag, rf_tta_spec)
 
 PRECISION_FP32, PRECISION_FP16, PRECISION_INT8 = 0, 1, 2
 
@@ -398,6 +398,58 @@ class Tracker:
 
     def reset(self, stream: int = -1) -> None:
         _lib.check(self._lib.rf_tracker_reset(self._t, int(stream)), self._det._h)
+
+
+def tta_spec(flip: bool = True, vote: bool = True, max_faces: int = 0) -> rf_tta_spec:
+    """An rf_tta_spec: flip (also detect every frame mirrored left-right), vote (a kept box becomes the score-weighted mean of the
+    candidates it suppressed; off: the plain greedy NMS), max_faces (merged faces kept per frame; 0 = the engine's max_detections)."""
+    sp = rf_tta_spec()
+    sp.struct_size = C.sizeof(rf_tta_spec)
+    sp.flip, sp.vote, sp.max_faces = 1 if flip else 2, 1 if vote else 2, int(max_faces)
+    return sp
+
+
+def tta_map_face(face, pass_index: int, rows: int, cols: int, net_h: int, net_w: int) -> np.ndarray:
+    """rf_tta_map_face (host only, no GPU): the face (a Detection or 15 floats) of pass 0 (the frame) or 1 (the frame mirrored) in
+    source-frame pixels, as 15 float32."""
+    lib = _lib.load_library()
+    f = rf_face.from_buffer_copy(_face_rows([face])[0].tobytes())
+    g = rf_face()
+    st = lib.rf_tta_map_face(int(rows), int(cols), int(net_h), int(net_w), int(pass_index), C.byref(f), C.byref(g))
+    if st < 0:
+        raise _lib.RFError(st, "rf_tta_map_face: bad frame, net size or pass index")
+    return _faces_to_array(C.pointer(g), 1)[0]
+
+
+def tta_merge_host(passes, rows: int, cols: int, net_h: int, net_w: int, nms_threshold: float, max_detections: int, flip: bool = True,
+                   vote: bool = True, max_faces: int = 0, cap: Optional[int] = None, spec=None):
+    """rf_tta_merge_host (host only, no GPU): mapping and merge of ONE frame -- passes[p]: the faces of pass p (a (k, 15) array, rows of
+    15 floats or Detections), two passes, one with flip off.  Returns (faces (k, 15) float32 in merge order, count: the true number of
+    heads, votes (k,) int32, src_pass (k,) int32, truncated)."""
+    lib = _lib.load_library()
+    sp = spec if spec is not None else tta_spec(flip, vote, max_faces)
+    md = int(max_detections)
+    if md < 1:
+        raise _lib.RFError(_lib.RF_ERR_INVALID_ARG, "rf_tta_merge_host: max_detections must be positive")
+    rows_ = [_face_rows(p) for p in passes]
+    flat = np.zeros((max(len(rows_), 1), md, 15), np.float32)
+    pc = (C.c_int * max(len(rows_), 2))()
+    for p, r in enumerate(rows_):
+        flat[p, :min(len(r), md)] = r[:md]
+        pc[p] = len(r)
+    cap = int(cap) if cap is not None else (sp.max_faces or md)
+    out = (rf_face * max(cap, 1))()
+    votes, src = (C.c_int * max(cap, 1))(), (C.c_int * max(cap, 1))()
+    count = C.c_int(0)
+    if len(rows_) != (1 if sp.flip == 2 else 2):
+        raise _lib.RFError(_lib.RF_ERR_INVALID_ARG, "rf_tta_merge_host: one pass per frame with flip off, two otherwise")
+    st = lib.rf_tta_merge_host(C.byref(sp), int(rows), int(cols), int(net_h), int(net_w), float(nms_threshold), md,
+                               flat.ctypes.data_as(C.POINTER(rf_face)), pc, out, cap, C.byref(count), votes, src)
+    if st < 0 and st != _lib.RF_ERR_TRUNCATED:
+        raise _lib.RFError(st, "rf_tta_merge_host: bad spec, frame, net size or counts")
+    k = max(0, min(count.value, cap, sp.max_faces or md))
+    return (_faces_to_array(out, max(cap, 1))[:k], int(count.value), np.array(votes[:k], np.int32), np.array(src[:k], np.int32),
+            st == _lib.RF_ERR_TRUNCATED)
 
 
 def _faces_to_array(buf, n: int) -> np.ndarray:
@@ -1011,6 +1063,93 @@ class RetinaFace:
                                                          self.last_pixels.ctypes.data_as(C.POINTER(C.c_int32))), self._h)
         self.truncated = st == _lib.RF_ERR_TRUNCATED
         return self._collect(out, counts, n, cap)
+
+    # ------------------------------------------------------------------ flip test-time augmentation
+    def detect_tta(self, imgs: Sequence[np.ndarray], threshold: float = 0.5, flip: bool = True, vote: bool = True, max_faces: int = 0,
+                   return_votes: bool = False):
+        """rf_detect_tta_batch: every frame is detected as it is and mirrored left-right; the mirrored faces are moved back and
+        overlapping boxes of both passes are merged on the device into a score-weighted mean.  Returns per frame the merged
+        detections in SOURCE-FRAME pixels (anchor_index is -1); with return_votes also, per frame, how many candidates each face
+        merged and the pass (0: the frame, 1: mirrored) its head came from.  self.tta_counts holds the true merged counts."""
+        n = len(imgs)
+        ptrs = (C.c_void_p * max(n, 1))()
+        rows, cols, steps = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
+        keep = []
+        for i, im in enumerate(imgs):
+            if im is None or im.size == 0:
+                ptrs[i], rows[i], cols[i], steps[i] = None, 0, 0, 0
+                continue
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
+            if im.strides[2] != 1 or im.strides[1] != 3:
+                im = np.ascontiguousarray(im)
+            keep.append(im)
+            ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
+        return self._run_tta(self._lib.rf_detect_tta_batch, ptrs, rows, cols, steps, n, threshold, tta_spec(flip, vote, max_faces),
+                             return_votes)
+
+    def detect_tta_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], threshold: float = 0.5,
+                          steps: Optional[Sequence[int]] = None, flip: bool = True, vote: bool = True, max_faces: int = 0,
+                          return_votes: bool = False):
+        """rf_detect_tta_batch_device: detect_tta for frames resident in device memory (0 / None: an empty frame)."""
+        n = len(ptrs)
+        p = (C.c_void_p * max(n, 1))(*ptrs)
+        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
+        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        return self._run_tta(self._lib.rf_detect_tta_batch_device, p, r, c, s, n, threshold, tta_spec(flip, vote, max_faces), return_votes)
+
+    def _collect_tta(self, out, counts, votes, src, n, cap, return_votes):
+        rows = _faces_to_array(out, max(n * cap, 1))
+        dets, vt, ps = [], [], []
+        for i in range(n):
+            k = min(counts[i], cap)
+            dets.append([Detection(float(r[0]), tuple(float(v) for v in r[1:5]), tuple(float(v) for v in r[5:10]),
+                                   tuple(float(v) for v in r[10:15]), -1) for r in rows[i * cap:i * cap + k]])
+            vt.append(np.array(votes[i * cap:i * cap + k], np.int32))
+            ps.append(np.array(src[i * cap:i * cap + k], np.int32))
+        self.tta_counts = [int(counts[i]) for i in range(n)]
+        return (dets, vt, ps) if return_votes else dets
+
+    def _run_tta(self, fn, ptrs, rows, cols, steps, n, threshold, sp, return_votes):
+        cap = sp.max_faces or self.max_detections
+        out = (rf_face * max(n * cap, 1))()
+        counts = (C.c_int * max(n, 1))()
+        votes, src = (C.c_int * max(n * cap, 1))(), (C.c_int * max(n * cap, 1))()
+        st = _lib.check(fn(self._h, ptrs, rows, cols, steps, n, float(threshold), C.byref(sp), out, cap, counts, votes, src), self._h)
+        self.truncated = st == _lib.RF_ERR_TRUNCATED
+        return self._collect_tta(out, counts, votes, src, n, cap, return_votes)
+
+    def tta_merge(self, rows: Sequence[int], cols: Sequence[int], per_pass_faces, flip: bool = True, vote: bool = True, max_faces: int = 0,
+                  cap_per_image: Optional[int] = None, return_votes: bool = False):
+        """rf_tta_merge_device: mapping and merge of per-pass faces the caller supplies -- per_pass_faces[i][p]: the faces of pass p
+        of frame i (a (k, 15) array, rows of 15 floats or Detections, at most max_detections); two passes per frame, one with flip
+        off.  No forward pass runs.  Returns as detect_tta; self.tta_counts holds the true merged counts."""
+        n = len(rows)
+        sp = tta_spec(flip, vote, max_faces)
+        md = self.max_detections
+        per = 2 if flip else 1
+        if any(len(frame) != per for frame in per_pass_faces) or len(per_pass_faces) != n:
+            raise ValueError("per_pass_faces: one list of %d passes per frame" % per)
+        passes = [_face_rows(f) for frame in per_pass_faces for f in frame]
+        flat = np.zeros((max(len(passes), 1), md, 15), np.float32)
+        pc = (C.c_int * max(len(passes), 1))()
+        for p, r in enumerate(passes):
+            flat[p, :min(len(r), md)] = r[:md]
+            pc[p] = len(r)
+        cap = int(cap_per_image) if cap_per_image is not None else (sp.max_faces or md)
+        out = (rf_face * max(n * cap, 1))()
+        counts = (C.c_int * max(n, 1))()
+        votes, src = (C.c_int * max(n * cap, 1))(), (C.c_int * max(n * cap, 1))()
+        st = _lib.check(self._lib.rf_tta_merge_device(self._h, (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols), n, C.byref(sp),
+                                                      flat.ctypes.data_as(C.POINTER(rf_face)), pc, out, cap, counts, votes, src), self._h)
+        self.truncated = st == _lib.RF_ERR_TRUNCATED
+        return self._collect_tta(out, counts, votes, src, n, cap, return_votes)
+
+    def mirror_device(self, src_ptr: int, rows: int, cols: int, dst_ptr: int, step: Optional[int] = None, dst_step: Optional[int] = None):
+        """rf_mirror_device: the mirror kernel on its own -- row y of the destination (dst_step bytes apart, cols * 3 bytes written)
+        is row y of the BGR frame at src_ptr (row pitch `step`, any alignment) mirrored left-right.  Both in device memory."""
+        _lib.check(self._lib.rf_mirror_device(self._h, src_ptr, int(rows), int(cols), int(step if step is not None else 3 * cols), dst_ptr,
+                                              int(dst_step if dst_step is not None else 3 * cols)), self._h)
 
     def enqueue_device(self, ptrs, rows, cols, threshold: float = 0.5) -> int:
         n = len(ptrs)
