@@ -104,6 +104,15 @@ public:
     const vector<vector<int>> &ttaVotes() const { return ttaVotes_; }
     const vector<vector<int>> &ttaPasses() const { return ttaPasses_; }
 
+    /* additive: zoom-pyramid detection (rf_detect_pyramid_batch): every frame is detected at 1x and as net-sized tiles of the frame enlarged
+       2x / 4x on the device, so that faces below the smallest anchor are found; the faces of all passes are moved back and merged as in
+       detectTta().  Fills lastBatchResult() with the merged faces in SOURCE-FRAME pixels (at most spec->max_faces per frame);
+       pyramidVotes() holds, per frame, how many candidates each face merged, pyramidPasses() the pass of the plan (rf_pyramid_plan) its
+       head came from.  spec may be nullptr (the defaults: 1x and 2x). */
+    void detectPyramid(const vector<cv::Mat> &imgs, float threshold = 0.5, const rf_pyramid_spec *spec = nullptr);
+    const vector<vector<int>> &pyramidVotes() const { return pyrVotes_; }
+    const vector<vector<int>> &pyramidPasses() const { return pyrPasses_; }
+
     /* additive: face tracks (rf_tracker_create / rf_detect_track_batch): createTracker() makes a tracker on this handle (spec may be
        nullptr: the defaults; the destructor frees it); detectTracked() is detectBatchImages() plus one frame step per image of stream
        streams[i] (-1: not tracked), with the tracks in source-frame pixels.  lastTrackTags()[i][k] is the tag of face k of
@@ -145,6 +154,7 @@ private:
     int faceQualityStride_ = 0;
     vector<vector<int>> tileSrc_;
     vector<vector<int>> ttaVotes_, ttaPasses_;
+    vector<vector<int>> pyrVotes_, pyrPasses_;
     vector<vector<rf_track_tag>> trackTags_;
     vector<vector<rf_track>> trackEnded_;
     vector<vector<int32_t>> redactPixels_;

@@ -648,6 +648,87 @@ int rf_detect_tta_batch(rf_handle h, const uint8_t *const *bgr, const int *rows,
 int rf_tta_merge_device(rf_handle h, const int *rows, const int *cols, int n, const rf_tta_spec *spec, const rf_face *faces,
                         const int *pass_counts, rf_face *out, int cap_per_image, int *counts, int *votes, int *src_pass);
 
+/* ---- Zoom-pyramid detection: the smallest anchors are 16 px, so faces below about 16 px are not seen in a frame that already fits the
+ * net.  A pyramid call detects every frame at 1x (the passes of its tile plan) and as net-sized tiles of the frame ENLARGED 2x and / or 4x
+ * on the device, moves the faces of all passes back into the frame and merges them with the voting merge of the TTA call (DESIGN.md
+ * "Zoom-pyramid detection" holds the definition; tests/pyramid_ref.py restates it in numpy; every result is byte-exact against it):
+ *   plan     three groups in this order: level 1x (levels bit 0): the passes of rf_tile_plan(rows, cols) in its order, its full-frame
+ *            pass included; level 2x (bit 1): the tiles of the tile plan of a VIRTUAL 2 rows x 2 cols frame with full_frame off,
+ *            row-major; level 4x (bit 2): the same for 4 rows x 4 cols.  overlap and edge are in net pixels at every level.  More than
+ *            1024 passes per frame, or zoom tiles of more than RF_PYRAMID_MAX_ZOOM_BYTES in one call (each tile tw * th * 3 bytes rounded
+ *            up to 256): RF_ERR_INVALID_ARG, before any state changes.  A NULL / 0 x 0 frame is one pass that finds nothing.
+ *   zoom     Z = zoom(F, z), z = 2 or 4: bilinear with half-pixel centres, in integers.  Per axis of length n, output index X:
+ *            D = 2z, num = 2X + 1 - z, i0 = floor(num / D), w = num - i0 * D, i1 = i0 + 1, then i0 and i1 are clamped to [0, n - 1].
+ *            Per channel, a, b on row y0 and c, d on row y1:  acc = ((D - wx) a + wx b)(D - wy) + ((D - wx) c + wx d) wy,
+ *            out = (acc + D * D / 2) >> (2 log2 D).  Zoom tile (X0, Y0, tw, th) is Z[Y0 : Y0 + th, X0 : X0 + tw]: the clamp is at the
+ *            FRAME border, never at the tile border, so neighbouring tiles agree on their overlap.
+ *   pass     the result of a pass is exactly what rf_detect_batch_device returns for that image at the call's threshold -- to the byte
+ *            when that ONE call holds all passes of the pyramid call in plan order, 1x tiles as ROI views, zoom tiles as dense frames of
+ *            their own (the caveat of the tiled call's views: the last bits of an image's result can depend on what shares its launch).
+ *   mapping  a 1x pass: rf_tile_map_face.  A zoom pass: the edge rule of rf_tile_map_face in tile coordinates against the virtual frame
+ *            (z cols, z rows); then every x becomes (x + (float)X0) * inv - off, every y (y + (float)Y0) * inv - off, inv = 1 / z,
+ *            off = (z - 1) / 2z (0.25 at 2x, 0.375 at 4x): the pixel-centre correspondence.  Scores are unchanged.  Results are in
+ *            SOURCE-FRAME pixels: their coord_scale for the alignment and face-batch calls is 1.
+ *   merge    rf_tta_spec's merge over the surviving faces of all passes of a frame, g = p * max_detections + k with p the pass index in
+ *            the plan; outputs and caps as for the TTA call (src_pass = g / max_detections).
+ * With levels = 1 and vote = 2 (off), out, counts and src_pass are the bytes of rf_detect_tiled_batch_device with the same overlap, edge,
+ * full_frame and max_faces. */
+#define RF_PYRAMID_MAX_ZOOM_BYTES (1u << 30)
+typedef struct rf_pyramid_spec {
+    uint32_t struct_size;   /* sizeof(rf_pyramid_spec) */
+    int32_t levels;         /* bit 0: the 1x passes; bit 1: 2x zoom tiles; bit 2: 4x zoom tiles; 1..7; 0 = 3 (1x and 2x) */
+    int32_t overlap;        /* as rf_tile_spec, in net pixels at every level */
+    int32_t edge;           /* as rf_tile_spec, in net pixels at every level */
+    int32_t full_frame;     /* as rf_tile_spec (level 1x only) */
+    int32_t max_faces;      /* as rf_tile_spec */
+    int32_t vote;           /* as rf_tta_spec.vote */
+} rf_pyramid_spec;
+
+/* Host only, no GPU, no handle -- the same code the kernels run, compiled for the host.  spec may be NULL (all defaults; max_faces 0
+ * stands for 256 in the first two, for max_detections in the third).
+ * rf_pyramid_plan: the number of passes of a rows x cols frame at a net_h x net_w net, or RF_ERR_INVALID_ARG (bad spec, non-positive net
+ * size, negative or over-size frame, more than 1024 passes, zoom tiles above RF_PYRAMID_MAX_ZOOM_BYTES).  zxywh (may be NULL) receives z, x0,
+ * y0, tw, th of the first min(passes, cap_passes) passes, in the level's virtual pixels; a full-frame pass is 1, 0, 0, cols, rows.
+ * rf_pyramid_map_face: edge rule and mapping of one face of pass p: 1 = kept, *out is the mapped face (out may equal in); 0 = dropped by
+ * the edge rule; RF_ERR_INVALID_ARG as above or for p outside the plan.
+ * rf_pyramid_merge_host: edge rule, mapping and merge of ONE frame: pass p holds pass_counts[p] faces (clamped to max_detections) at
+ * faces[p * max_detections + k].  *count is the true number of heads; out / votes / src_pass (the last two may be NULL) receive the first
+ * min(*count, cap, max_faces).  Returns RF_OK, RF_ERR_TRUNCATED (a pass count above max_detections, or a cut list) or RF_ERR_INVALID_ARG.
+ * rf_zoom_host: the window [x0, x0 + tw) x [y0, y0 + th) of the rows x cols BGR frame src (row pitch step) enlarged z (2 or 4) times,
+ * written as tw * 3 bytes per row at dst + y * dst_step (bytes beyond them are untouched).  The window lies inside the z rows x z cols
+ * frame. */
+int rf_pyramid_plan(const rf_pyramid_spec *spec, int rows, int cols, int net_h, int net_w, int *zxywh, int cap_passes);
+int rf_pyramid_map_face(const rf_pyramid_spec *spec, int rows, int cols, int net_h, int net_w, int p, const rf_face *in, rf_face *out);
+int rf_pyramid_merge_host(const rf_pyramid_spec *spec, int rows, int cols, int net_h, int net_w, float nms_threshold, int max_detections,
+                          const rf_face *faces, const int *pass_counts, rf_face *out, int cap, int *count, int *votes, int *src_pass);
+int rf_zoom_host(const uint8_t *src, int rows, int cols, int step, int z, int x0, int y0, int tw, int th, uint8_t *dst, int dst_step);
+
+/* The zoom kernel on its own: rf_zoom_host for a frame and a destination in device memory (any source pitch and pointer alignment; ROI
+ * views are legal).  Synchronous. */
+int rf_zoom_device(rf_handle h, const void *d_src, int rows, int cols, int step, int z, int x0, int y0, int tw, int th, void *d_dst,
+                   int dst_step);
+
+/* Pyramid detection of frames resident on the engine's device (frame limits as rf_detect_batch_device).  The zoom tiles are made on the
+ * device in front of the call's first detection launch; the passes of all frames go through the engine's ordinary launches; a gather
+ * kernel behind each launch applies the edge rule and the mapping, and one merge launch behind the call's last launch waits for them
+ * on the device -- no host synchronisation in between.  spec may be NULL.  A bad spec is refused before any state changes.
+ * Multi-device handles return RF_ERR_UNSUPPORTED from this call, the next two and rf_zoom_device.  rf_last_anchor_indices /
+ * rf_last_candidate_counts afterwards describe the call's PASSES, in plan order. */
+int rf_detect_pyramid_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                   float threshold, const rf_pyramid_spec *spec, rf_face *out, int cap_per_image, int *counts, int *votes,
+                                   int *src_pass);
+
+/* The same with frames in HOST memory (rf_detect_batch's convention): each frame is uploaded once, densely. */
+int rf_detect_pyramid_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                            float threshold, const rf_pyramid_spec *spec, rf_face *out, int cap_per_image, int *counts, int *votes,
+                            int *src_pass);
+
+/* Edge rule, mapping and merge of per-pass faces the CALLER supplies (host memory): with first_pass[i] the running sum of the frames'
+ * plan sizes, pass p of frame i holds pass_counts[first_pass[i] + p] faces (clamped to max_detections) at
+ * faces[(first_pass[i] + p) * max_detections + k].  No forward pass runs. */
+int rf_pyramid_merge_device(rf_handle h, const int *rows, const int *cols, int n, const rf_pyramid_spec *spec, const rf_face *faces,
+                            const int *pass_counts, rf_face *out, int cap_per_image, int *counts, int *votes, int *src_pass);
+
 /* Asynchronous form of rf_detect_batch_device for serving loops: enqueue returns as soon as the
  * batch is queued on the engine's stream (n <= max_batch); `ticket` identifies one of
  * rf_num_slots() result slots.  rf_wait blocks until that batch has finished and copies its results.

@@ -87,6 +87,11 @@ class rf_tta_spec(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flip", C.c_int32), ("vote", C.c_int32), ("max_faces", C.c_int32)]
 
 
+class rf_pyramid_spec(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("levels", C.c_int32), ("overlap", C.c_int32), ("edge", C.c_int32),
+                ("full_frame", C.c_int32), ("max_faces", C.c_int32), ("vote", C.c_int32)]
+
+
 RF_GATE_INVALID, RF_GATE_SHARPNESS, RF_GATE_IOD, RF_GATE_YAW, RF_GATE_ROLL, RF_GATE_COVERED, RF_GATE_DARK, RF_GATE_BRIGHT = (
     1, 2, 4, 8, 16, 32, 64, 128)
 
@@ -204,6 +209,20 @@ SYMBOLS = {
                                       C.c_float, _PP(rf_tta_spec), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int)]),
     "rf_tta_merge_device": (C.c_int, [C.c_void_p, _PP(C.c_int), _PP(C.c_int), C.c_int, _PP(rf_tta_spec), _PP(rf_face), _PP(C.c_int),
                                       _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int)]),
+    "rf_pyramid_plan": (C.c_int, [_PP(rf_pyramid_spec), C.c_int, C.c_int, C.c_int, C.c_int, _PP(C.c_int), C.c_int]),
+    "rf_pyramid_map_face": (C.c_int, [_PP(rf_pyramid_spec), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _PP(rf_face), _PP(rf_face)]),
+    "rf_pyramid_merge_host": (C.c_int, [_PP(rf_pyramid_spec), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _PP(rf_face),
+                                        _PP(C.c_int), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int)]),
+    "rf_zoom_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    "rf_zoom_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                 C.c_void_p, C.c_int]),
+    "rf_detect_pyramid_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                                 C.c_float, _PP(rf_pyramid_spec), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int),
+                                                 _PP(C.c_int)]),
+    "rf_detect_pyramid_batch": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                          C.c_float, _PP(rf_pyramid_spec), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int)]),
+    "rf_pyramid_merge_device": (C.c_int, [C.c_void_p, _PP(C.c_int), _PP(C.c_int), C.c_int, _PP(rf_pyramid_spec), _PP(rf_face),
+                                          _PP(C.c_int), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int)]),
     "rf_num_slots": (C.c_int, [C.c_void_p]),
     "rf_enqueue_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int),
                                           C.c_int, C.c_float, _PP(C.c_int)]),

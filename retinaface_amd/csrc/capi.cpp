@@ -942,6 +942,159 @@ int rf_tta_merge_device(rf_handle h, const int *rows, const int *cols, int n, co
     });
 }
 
+// ---- zoom-pyramid detection (pyramid.h)
+namespace {
+// the plan of one frame for the host-only entry points: false = refused
+bool pyr_host_plan(const rf_pyramid_spec *spec, int rows, int cols, int net_h, int net_w, int default_max_faces, rf::PyrSpec *sp,
+                   std::vector<rf::PyrEntry> *entries) {
+    if (net_h <= 0 || net_w <= 0 || rows < 0 || cols < 0 || rf::pyr_spec_resolve(spec, net_h, net_w, default_max_faces, sp)) return false;
+    if (cols > 0 && rows > 4096 * 3072 / cols) return false;
+    entries->clear();
+    if (rows == 0 || cols == 0) {                      // an empty frame: one pass that finds nothing
+        rf::PyrEntry e;
+        memset(&e, 0, sizeof(e));
+        e.frame = -1; e.z = 1; e.scale = 1.f;
+        entries->push_back(e);
+        return true;
+    }
+    size_t zoom_bytes = 0;
+    if (rf::pyr_plan(*sp, rows, cols, net_h, net_w, 0, entries, &zoom_bytes) < 0) return false;
+    return zoom_bytes <= rf::kPyrMaxZoomBytes;
+}
+}  // namespace
+
+int rf_pyramid_plan(const rf_pyramid_spec *spec, int rows, int cols, int net_h, int net_w, int *zxywh, int cap_passes) {
+    rf::PyrSpec sp;
+    std::vector<rf::PyrEntry> entries;
+    if (cap_passes < 0 || !pyr_host_plan(spec, rows, cols, net_h, net_w, 256, &sp, &entries)) return RF_ERR_INVALID_ARG;
+    const int passes = (int)entries.size();
+    for (int p = 0; zxywh && p < passes && p < cap_passes; p++) {
+        const rf::PyrEntry &e = entries[p];
+        zxywh[5 * p] = e.z; zxywh[5 * p + 1] = e.x0; zxywh[5 * p + 2] = e.y0; zxywh[5 * p + 3] = e.tw; zxywh[5 * p + 4] = e.th;
+    }
+    return passes;
+}
+
+int rf_pyramid_map_face(const rf_pyramid_spec *spec, int rows, int cols, int net_h, int net_w, int p, const rf_face *in, rf_face *out) {
+    rf::PyrSpec sp;
+    std::vector<rf::PyrEntry> entries;
+    if (!in || !out || !pyr_host_plan(spec, rows, cols, net_h, net_w, 256, &sp, &entries)) return RF_ERR_INVALID_ARG;
+    if (p < 0 || p >= (int)entries.size() || entries[p].frame < 0) return RF_ERR_INVALID_ARG;
+    float f[15];
+    memcpy(f, in, sizeof(f));
+    if (!rf::pyr_map_face(entries[p], sp.tile.edge, f, f)) return 0;
+    memcpy(out, f, sizeof(f));
+    return 1;
+}
+
+int rf_pyramid_merge_host(const rf_pyramid_spec *spec, int rows, int cols, int net_h, int net_w, float nms_threshold, int max_detections,
+                          const rf_face *faces, const int *pass_counts, rf_face *out, int cap, int *count, int *votes, int *src_pass) {
+    rf::PyrSpec sp;
+    std::vector<rf::PyrEntry> entries;
+    if (max_detections < 1 || max_detections > rf::kTtaMaxFaces) return RF_ERR_INVALID_ARG;
+    if (!pyr_host_plan(spec, rows, cols, net_h, net_w, max_detections, &sp, &entries)) return RF_ERR_INVALID_ARG;
+    if (!faces || !pass_counts || !count || cap < 0 || (cap > 0 && !out)) return RF_ERR_INVALID_ARG;
+    const int P = (int)entries.size();
+    for (int p = 0; p < P; p++)
+        if (pass_counts[p] < 0) return RF_ERR_INVALID_ARG;
+    bool truncated = false;
+    std::vector<float> cand;
+    std::vector<int> g;
+    for (int p = 0; p < P; p++) {
+        if (pass_counts[p] > max_detections) truncated = true;
+        if (entries[p].frame < 0) continue;
+        for (int k = 0; k < pass_counts[p] && k < max_detections; k++) {
+            float f[15];
+            memcpy(f, &faces[(size_t)p * max_detections + k], sizeof(f));
+            if (!rf::pyr_map_face(entries[p], sp.tile.edge, f, f)) continue;
+            cand.insert(cand.end(), f, f + 15);
+            g.push_back(p * max_detections + k);
+        }
+    }
+    const int limit = cap < sp.tile.max_faces ? cap : sp.tile.max_faces;
+    std::vector<float> merged((size_t)limit * 15 + 1);
+    std::vector<int> vt((size_t)limit + 1), hg((size_t)limit + 1);
+    const int heads = rf::tta_merge_candidates(cand, g, nms_threshold, sp.vote != 0, limit, merged.data(), vt.data(), hg.data());
+    *count = heads;
+    for (int k = 0; k < heads && k < limit; k++) {
+        memset(&out[k], 0, sizeof(rf_face));
+        memcpy(&out[k], &merged[(size_t)k * 15], 15 * sizeof(float));
+        if (votes) votes[k] = vt[k];
+        if (src_pass) src_pass[k] = hg[k] / max_detections;
+    }
+    return truncated || heads > limit ? RF_ERR_TRUNCATED : RF_OK;
+}
+
+int rf_zoom_host(const uint8_t *src, int rows, int cols, int step, int z, int x0, int y0, int tw, int th, uint8_t *dst, int dst_step) {
+    if (rows < 0 || cols < 0 || tw < 0 || th < 0 || (z != 2 && z != 4)) return RF_ERR_INVALID_ARG;
+    if (rows == 0 || cols == 0 || tw == 0 || th == 0) return RF_OK;
+    if (!src || !dst || rows > 4096 * 3072 / cols || step < cols * 3 || dst_step < tw * 3) return RF_ERR_INVALID_ARG;
+    if (x0 < 0 || y0 < 0 || x0 > z * cols - tw || y0 > z * rows - th) return RF_ERR_INVALID_ARG;
+    for (int y = 0; y < th; y++)
+        for (int x = 0; x < tw; x++)
+            rf::pyr_zoom_pixel(src, rows, cols, (size_t)step, z, x0 + x, y0 + y, dst + (size_t)y * dst_step + (size_t)3 * x);
+    return RF_OK;
+}
+
+namespace {
+// a caller's pyramid spec with its defaults applied; refused before the engine is touched
+void pyr_request(rf_handle h, const rf_pyramid_spec *spec, int *votes, int *src_pass, rf::PyrRequest *rq) {
+    if (const char *bad = rf::pyr_spec_resolve(spec, h->eng->net_h(), h->eng->net_w(), h->eng->default_max_faces(), &rq->spec))
+        throw rf::ArgError(bad);
+    rq->votes = votes;
+    rq->src_pass = src_pass;
+}
+
+int detect_pyramid_common(rf_handle h, const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n,
+                          bool on_device, float thr, const rf_pyramid_spec *spec, rf_face *out, int cap, int *counts, int *votes,
+                          int *src_pass) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        rf::PyrRequest rq;
+        pyr_request(h, spec, votes, src_pass, &rq);
+        bool tr = false;
+        h->eng->detect_pyramid(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, rq);
+        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+}  // namespace
+
+int rf_zoom_device(rf_handle h, const void *d_src, int rows, int cols, int step, int z, int x0, int y0, int tw, int th, void *d_dst,
+                   int dst_step) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        h->eng->zoom(d_src, rows, cols, step, z, x0, y0, tw, th, d_dst, dst_step);
+        return RF_OK;
+    });
+}
+
+int rf_detect_pyramid_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                   float threshold, const rf_pyramid_spec *spec, rf_face *out, int cap_per_image, int *counts, int *votes,
+                                   int *src_pass) {
+    return detect_pyramid_common(h, (const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, spec, out, cap_per_image, counts,
+                                 votes, src_pass);
+}
+
+int rf_detect_pyramid_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                            float threshold, const rf_pyramid_spec *spec, rf_face *out, int cap_per_image, int *counts, int *votes,
+                            int *src_pass) {
+    return detect_pyramid_common(h, bgr, rows, cols, steps, n, false, threshold, spec, out, cap_per_image, counts, votes, src_pass);
+}
+
+int rf_pyramid_merge_device(rf_handle h, const int *rows, const int *cols, int n, const rf_pyramid_spec *spec, const rf_face *faces,
+                            const int *pass_counts, rf_face *out, int cap_per_image, int *counts, int *votes, int *src_pass) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        rf::PyrRequest rq;
+        pyr_request(h, spec, votes, src_pass, &rq);
+        bool tr = false;
+        h->eng->pyramid_merge(rows, cols, n, rq, faces, pass_counts, out, cap_per_image, counts, &tr);
+        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+
 int rf_num_slots(rf_handle h) { return h ? h->eng->num_slots() : RF_ERR_INVALID_ARG; }
 
 int rf_enqueue_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps,

@@ -208,13 +208,14 @@ public:
         for (void *p : host_allocs_) (void)hipHostFree(p);
         if (align_stream_) { (void)hipStreamSynchronize(align_stream_); (void)hipStreamDestroy(align_stream_); }
         for (DeviceScratch *b : {&align_crops_, &align_mats_, &align_tab_, &fb_state_, &fq_records_, &fq_packed_, &fq_offsets_, &tile_cand_, &tile_count_, &tile_out_,
-                                 &tile_outcount_, &tile_tab_, &tile_frames_, &tta_cand_, &tta_count_, &tta_frames_, &tta_mirror_,
+                                 &tile_outcount_, &tile_tab_, &tile_frames_, &tta_cand_, &tta_count_, &tta_frames_, &tta_mirror_, &pyr_frames_, &pyr_zoom_,
                                  &red_regions_, &red_counts_, &red_cells_, &red_frames_}) b->release();
         for (HostScratch *b : {&trk_tags_, &trk_ended_, &trk_counts_, &tta_out_, &tta_votes_, &tta_outcount_}) b->release();
         for (auto &t : trackers_) t->state.release();
         for (hipEvent_t e : trk_ev_) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : red_ev_) if (e) (void)hipEventDestroy(e);
         if (tta_mirror_done_) (void)hipEventDestroy(tta_mirror_done_);
+        if (pyr_zoom_done_) (void)hipEventDestroy(pyr_zoom_done_);
         kind_.arena->release();
         for (auto &e : prof_ev_) (void)hipEventDestroy(e);
     }
@@ -1038,6 +1039,195 @@ public:
         tta_copy_out(n, rq, out, cap_per_image, counts, truncated);
     }
 
+    // -------------------------------------------------------------------------------- zoom-pyramid detection
+    // The pyramid plans of a call's frames as one pass table (frames in call order, passes in plan order); first[i]: frame i's first
+    // pass; *zoom_bytes: what the zoom tiles of the call take.  A NULL / empty frame is one pass that gathers nothing (frame = -1).
+    // `have_ptrs` false: pyramid_merge(), which has no pixels.  Throws before any state has changed.
+    void pyr_build_passes(const PyrSpec &sp, const uint8_t *const *frames, bool have_ptrs, const int *rows, const int *cols, int n,
+                          std::vector<PyrEntry> *entries, std::vector<int> *first, size_t *zoom_bytes) const {
+        entries->clear();
+        first->assign((size_t)n + 1, 0);
+        *zoom_bytes = 0;
+        for (int i = 0; i < n; i++) {
+            (*first)[i] = (int)entries->size();
+            const bool empty = (have_ptrs && !frames[i]) || rows[i] <= 0 || cols[i] <= 0;
+            if (empty) {
+                PyrEntry e;
+                memset(&e, 0, sizeof(e));
+                e.frame = -1; e.z = 1; e.scale = 1.f;
+                entries->push_back(e);
+                continue;
+            }
+            if (rows[i] > 4096 * 3072 / cols[i]) throw ArgError("frame larger than 4096x3072 (RetinaFace.cpp:325)");
+            if (pyr_plan(sp, rows[i], cols[i], net_h_, net_w_, i, entries, zoom_bytes) < 0)
+                throw ArgError("pyramid detection: a frame's plan has more than 1024 passes");
+            if (*zoom_bytes > kPyrMaxZoomBytes) throw ArgError("pyramid detection: the zoom tiles of the call need more than 1 GiB");
+        }
+        (*first)[n] = (int)entries->size();
+    }
+
+    // the blocks of a pyramid call are those of a TTA call (tta_open): the two calls never overlap, and the merge is the same launch
+    static TtaSpec pyr_merge_spec(const PyrSpec &sp) {
+        TtaSpec t;
+        t.flip = 0; t.vote = sp.vote; t.max_faces = sp.tile.max_faces;
+        return t;
+    }
+    static TtaRequest pyr_merge_request(const PyrRequest &rq) {
+        TtaRequest t;
+        t.spec = pyr_merge_spec(rq.spec); t.votes = rq.votes; t.src_pass = rq.src_pass;
+        return t;
+    }
+
+    void pyr_launch_gather(hipStream_t st, const uint8_t *faces, int face_stride, const int *counts, const PyrEntry *table, int passes,
+                           const PyrSpec &sp) {
+        PyrGatherParams gp;
+        gp.faces = faces; gp.face_stride = face_stride; gp.faces_per_pass = opt_.max_detections;
+        gp.counts = counts; gp.table = table;
+        gp.n = passes; gp.edge = sp.tile.edge; gp.rank_stride = opt_.max_detections;
+        gp.cand = (Candidate *)tta_cand_.ptr; gp.cand_count = (int *)tta_count_.ptr; gp.cap = kTtaMergeCap;
+        launch_pyr_gather(st, gp);
+    }
+
+    void zoom(const void *d_src, int rows, int cols, int step, int z, int x0, int y0, int tw, int th, void *d_dst, int dst_step) override {
+        if (rows < 0 || cols < 0 || tw < 0 || th < 0) throw ArgError("negative frame or window size");
+        if (z != 2 && z != 4) throw ArgError("zoom: z must be 2 or 4");
+        if (rows == 0 || cols == 0 || tw == 0 || th == 0) return;
+        check_frame((const uint8_t *)d_src, rows, cols, step);
+        if (!d_src) throw ArgError("null argument");
+        if (x0 < 0 || y0 < 0 || x0 > z * cols - tw || y0 > z * rows - th) throw ArgError("zoom: the window leaves the enlarged frame");
+        if (!d_dst || dst_step < tw * 3) throw ArgError("zoom: null destination or dst_step < tw * 3");
+        DeviceGuard guard(device_);
+        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+        const ZoomParams zp{(const uint8_t *)d_src, rows, cols, step, z, x0, y0, tw, th, (uint8_t *)d_dst, dst_step};
+        launch_zoom_tiles(align_stream_, &zp, 1);
+        RF_HIP(hipGetLastError());
+        RF_HIP(hipStreamSynchronize(align_stream_));
+    }
+
+    void detect_pyramid(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,
+                        float threshold, rf_face *out, int cap_per_image, int *counts, bool *truncated, const PyrRequest &rq) override {
+        *truncated = false;
+        const TtaRequest mrq = pyr_merge_request(rq);
+        tta_check_args(n, frames, rows, cols, counts, out, cap_per_image, mrq.spec);
+        std::vector<int> st((size_t)std::max(n, 1));
+        for (int i = 0; i < n; i++) {
+            st[i] = steps ? steps[i] : cols[i] * 3;
+            check_frame(frames[i], rows[i], cols[i], st[i]);
+        }
+        std::vector<PyrEntry> entries;
+        std::vector<int> first;
+        size_t zoom_bytes = 0;
+        pyr_build_passes(rq.spec, frames, true, rows, cols, n, &entries, &first, &zoom_bytes);
+        if (n == 0) return;
+        DeviceGuard guard(device_);
+        auto live = [&](int i) { return entries[first[i]].frame >= 0; };
+        // host frames are uploaded once, densely; the 1x passes are views of that copy, the zoom kernel reads it
+        std::vector<const uint8_t *> base((size_t)n, nullptr);
+        if (!on_device) {
+            size_t bytes = 0;
+            std::vector<size_t> off((size_t)n, 0);
+            for (int i = 0; i < n; i++)
+                if (live(i)) { off[i] = bytes; bytes += align256((size_t)rows[i] * cols[i] * 3); }
+            uint8_t *d = pyr_frames_.reserve(bytes);
+            for (int i = 0; i < n; i++) {
+                if (!live(i)) continue;
+                RF_HIP(hipMemcpy2D(d + off[i], (size_t)cols[i] * 3, frames[i], (size_t)st[i], (size_t)cols[i] * 3, (size_t)rows[i], hipMemcpyHostToDevice));
+                base[i] = d + off[i];
+                st[i] = cols[i] * 3;
+            }
+        } else {
+            for (int i = 0; i < n; i++) base[i] = live(i) ? frames[i] : nullptr;
+        }
+        // as in detect_tiled(): a super-batch of earlier enqueues starts now, every later launch carries passes of this call only
+        launch_pending();
+        // The zoom tiles: dense, each at a 256-byte-aligned offset of one growing block (what a freshly allocated dense frame looks
+        // like to conv0's staging), made on the side stream; every lane that launches a pass of the call waits for them on the device.
+        const int P = (int)entries.size();
+        std::vector<const uint8_t *> vp((size_t)P, nullptr);
+        std::vector<int> vr((size_t)P, 0), vc((size_t)P, 0), vs((size_t)P, 0), pass_counts((size_t)P);
+        uint8_t *d_zoom = zoom_bytes ? pyr_zoom_.reserve(zoom_bytes) : nullptr;
+        std::vector<ZoomParams> zp;
+        size_t zoff = 0;
+        for (int q = 0; q < P; q++) {
+            const PyrEntry &e = entries[q];
+            if (e.frame < 0) continue;
+            const int i = e.frame;
+            vr[q] = e.th; vc[q] = e.tw;
+            if (e.z == 1) {
+                vp[q] = base[i] + (size_t)e.y0 * st[i] + (size_t)3 * e.x0;
+                vs[q] = st[i];
+                continue;
+            }
+            uint8_t *dst = d_zoom + zoff;
+            zoff += align256((size_t)e.tw * e.th * 3);
+            zp.push_back(ZoomParams{base[i], rows[i], cols[i], st[i], e.z, e.x0, e.y0, e.tw, e.th, dst, e.tw * 3});
+            vp[q] = dst; vs[q] = e.tw * 3;
+        }
+        if (!zp.empty()) {
+            if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+            if (!pyr_zoom_done_) RF_HIP(hipEventCreateWithFlags(&pyr_zoom_done_, hipEventDisableTiming));
+            launch_zoom_tiles(align_stream_, zp.data(), (int)zp.size());
+            RF_HIP(hipGetLastError());
+            RF_HIP(hipEventRecord(pyr_zoom_done_, align_stream_));
+        }
+        tta_open(n, mrq.spec);
+        pyr_.rq = rq; pyr_.entries.swap(entries);
+        pyr_.n_frames = n; pyr_.next_pass = 0;
+        pyr_.lanes_used.clear();
+        pyr_.wait_zoom = !zp.empty();
+        pyr_.on = true;
+        tta_dirty_ = true;                       // until the call has ended well
+        struct Off { bool &on; ~Off() { on = false; } } off_guard{pyr_.on};
+        bool tr = false;
+        detect(vp.data(), vr.data(), vc.data(), vs.data(), P, true, threshold, nullptr, 0, pass_counts.data(), &tr);
+        pyr_.on = false;
+        if (pyr_.next_pass != P) throw HipError("pyramid detection: the merge was not launched");
+        // every launch of the call has been waited for; the merge ran in front of the last one's `done`
+        tta_dirty_ = false;
+        *truncated = tr;
+        tta_copy_out(n, mrq, out, cap_per_image, counts, truncated);
+    }
+
+    void pyramid_merge(const int *rows, const int *cols, int n, const PyrRequest &rq, const rf_face *faces, const int *pass_counts,
+                       rf_face *out, int cap_per_image, int *counts, bool *truncated) override {
+        *truncated = false;
+        const TtaRequest mrq = pyr_merge_request(rq);
+        tta_check_args(n, rows, cols, counts, faces, out, cap_per_image, mrq.spec);
+        if (n > 0 && !pass_counts) throw ArgError("null argument");
+        std::vector<PyrEntry> entries;
+        std::vector<int> first;
+        size_t zoom_bytes = 0;
+        pyr_build_passes(rq.spec, nullptr, false, rows, cols, n, &entries, &first, &zoom_bytes);
+        if (n == 0) return;
+        const int P = (int)entries.size(), md = opt_.max_detections;
+        for (int p = 0; p < P; p++)
+            if (pass_counts[p] < 0) throw ArgError("negative face count");
+        DeviceGuard guard(device_);
+        // one table: run parameters | pass table | counts | faces (60-byte records, max_detections per pass)
+        const size_t o_tab = 256, o_cnt = o_tab + align256((size_t)P * sizeof(PyrEntry)), o_face = o_cnt + align256((size_t)P * sizeof(int)),
+                     total = o_face + (size_t)P * md * sizeof(rf_face);
+        align_host_.assign(total, 0);
+        *(RunParams *)align_host_.data() = RunParams{0.f, nms_threshold_, n, 0};
+        memcpy(align_host_.data() + o_tab, entries.data(), (size_t)P * sizeof(PyrEntry));
+        int *cnt = (int *)(align_host_.data() + o_cnt);
+        for (int p = 0; p < P; p++) {
+            cnt[p] = std::min(pass_counts[p], md);
+            if (pass_counts[p] > md) *truncated = true;
+            if (cnt[p]) memcpy(align_host_.data() + o_face + (size_t)p * md * sizeof(rf_face), faces + (size_t)p * md, (size_t)cnt[p] * sizeof(rf_face));
+        }
+        uint8_t *d_tab = align_tab_.reserve(total);
+        tta_open(n, mrq.spec);
+        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+        tta_dirty_ = true;
+        RF_HIP(hipMemcpyAsync(d_tab, align_host_.data(), total, hipMemcpyHostToDevice, align_stream_));
+        pyr_launch_gather(align_stream_, d_tab + o_face, (int)sizeof(rf_face), (const int *)(d_tab + o_cnt), (const PyrEntry *)(d_tab + o_tab), P, rq.spec);
+        tta_launch_merge(align_stream_, n, mrq.spec, (const RunParams *)d_tab);
+        RF_HIP(hipGetLastError());
+        RF_HIP(hipStreamSynchronize(align_stream_));
+        tta_dirty_ = false;
+        tta_copy_out(n, mrq, out, cap_per_image, counts, truncated);
+    }
+
     // -------------------------------------------------------------------------------- face tracks
     void *tracker_create(const TrackSpec &spec, int n_streams) override {
         if (n_streams < 1 || n_streams > kTrackMaxStreams) throw ArgError("n_streams must be in [1, 1024]");
@@ -1606,6 +1796,8 @@ private:
         hipEvent_t tile_done = nullptr;       // ... recorded behind the launch's gather: the call's merge (another lane) waits for it on the device
         TtaEntry *h_tta_tab = nullptr;        // detect_tta(): pinned, per image of the launch the pass it is (allocated on first use)
         hipEvent_t tta_done = nullptr;        // ... recorded behind the launch's gather, as tile_done
+        PyrEntry *h_pyr_tab = nullptr;        // detect_pyramid(): pinned, per image of the launch the pass it is (allocated on first use)
+        hipEvent_t pyr_done = nullptr;        // ... recorded behind the launch's gather, as tile_done
         uint8_t *h_track_tab = nullptr;       // detect_track(): pinned, the launch's stream table and image table (allocated on first use)
         hipEvent_t track_done = nullptr;      // ... recorded behind the launch's track kernel: the call's next track launch (another lane) waits for it
         int *h_red_streams = nullptr;         // detect_track_redact(): pinned, per image of the launch its stream (allocated on first use)
@@ -1652,6 +1844,7 @@ private:
         if (l.face_scan_done) (void)hipEventDestroy(l.face_scan_done);
         if (l.tile_done) (void)hipEventDestroy(l.tile_done);
         if (l.tta_done) (void)hipEventDestroy(l.tta_done);
+        if (l.pyr_done) (void)hipEventDestroy(l.pyr_done);
         if (l.track_done) (void)hipEventDestroy(l.track_done);
         if (l.copy2) { (void)hipStreamSynchronize(l.copy2); (void)hipStreamDestroy(l.copy2); }
         if (l.d_stage) (void)hipFree(l.d_stage);
@@ -1911,6 +2104,7 @@ private:
             s.copy2_used = false;
         }
         if (tta_.on && tta_.wait_mirror) RF_HIP(hipStreamWaitEvent(s.stream, tta_mirror_done_, 0));      // the launch reads mirrored copies
+        if (pyr_.on && pyr_.wait_zoom) RF_HIP(hipStreamWaitEvent(s.stream, pyr_zoom_done_, 0));          // the launch reads zoom tiles
         double tt = trace_.on ? HostTrace::now() : 0.0;
         RF_HIP(hipMemcpyAsync(s.d_frames, s.h_frames, s.table_bytes, hipMemcpyHostToDevice, s.stream));
         trace_.add(2, tt);
@@ -1940,6 +2134,7 @@ private:
         if (fb_.on) launch_lane_face_batch(s, n);
         if (tile_.on) launch_lane_tile(s, n);
         if (tta_.on) launch_lane_tta(s, n);
+        if (pyr_.on) launch_lane_pyr(s, n);
         if (trk_.on) launch_lane_track(s, n);
         if (red_.on) launch_lane_redact(s, n);
         RF_HIP(hipEventRecord(s.done, s.stream));
@@ -2073,6 +2268,34 @@ private:
         for (int l : tta_.lanes_used)
             if (l != me && l < (int)lanes_.size() && lanes_[l].tta_done) RF_HIP(hipStreamWaitEvent(s.stream, lanes_[l].tta_done, 0));
         tta_launch_merge(s.stream, tta_.n_frames, tta_.rq.spec, s.d_params);
+        RF_HIP(hipGetLastError());
+    }
+
+    // The pyramid launches of a super-batch of detect_pyramid(), as launch_lane_tta(): the gather behind each launch, and behind the
+    // call's LAST launch the wait for the gathers of the call's other lanes and the voting merge.  No host wait anywhere.
+    void launch_lane_pyr(Lane &s, int n) {
+        if (!s.h_pyr_tab) {
+            void *p = nullptr;
+            RF_HIP(hipHostMalloc(&p, std::max<size_t>((size_t)cap_images_ * sizeof(PyrEntry), 256), hipHostMallocDefault));
+            s.host_allocs.push_back(p);
+            s.h_pyr_tab = (PyrEntry *)p;
+            RF_HIP(hipEventCreateWithFlags(&s.pyr_done, hipEventDisableTiming));
+        }
+        const int total = (int)pyr_.entries.size();
+        if (n > cap_images_ || pyr_.next_pass + n > total) throw HipError("pyramid detection: a launch carries images of another call");
+        for (int i = 0; i < n; i++) s.h_pyr_tab[i] = pyr_.entries[pyr_.next_pass + i];
+        pyr_launch_gather(s.stream, (const uint8_t *)s.h_out, (int)sizeof(Candidate), s.h_counts, s.h_pyr_tab, n, pyr_.rq.spec);
+        RF_HIP(hipGetLastError());
+        pyr_.next_pass += n;
+        const int me = (int)(&s - lanes_.data());
+        if (pyr_.next_pass < total) {
+            RF_HIP(hipEventRecord(s.pyr_done, s.stream));
+            if (std::find(pyr_.lanes_used.begin(), pyr_.lanes_used.end(), me) == pyr_.lanes_used.end()) pyr_.lanes_used.push_back(me);
+            return;
+        }
+        for (int l : pyr_.lanes_used)
+            if (l != me && l < (int)lanes_.size() && lanes_[l].pyr_done) RF_HIP(hipStreamWaitEvent(s.stream, lanes_[l].pyr_done, 0));
+        tta_launch_merge(s.stream, pyr_.n_frames, pyr_merge_spec(pyr_.rq.spec), s.d_params);
         RF_HIP(hipGetLastError());
     }
 
@@ -2525,6 +2748,13 @@ private:
     bool tta_dirty_ = true;
     struct { bool on = false, wait_mirror = false; TtaRequest rq; std::vector<TtaEntry> entries; int n_frames = 0, next_pass = 0;
              std::vector<int> lanes_used; } tta_;
+
+    // zoom-pyramid detection: the device copy of host frames, the zoom tiles and the event behind them; the request
+    // detect_pyramid() has open.  Candidates, counters and merged records are the TTA call's blocks (pyr_merge_spec).
+    DeviceScratch pyr_frames_, pyr_zoom_;
+    hipEvent_t pyr_zoom_done_ = nullptr;
+    struct { bool on = false, wait_zoom = false; PyrRequest rq; std::vector<PyrEntry> entries; int n_frames = 0, next_pass = 0;
+             std::vector<int> lanes_used; } pyr_;
 
     // face tracks: the trackers of this handle, the call-level result buffers and the request a tracked call has open
     struct Tracker {

@@ -110,6 +110,14 @@ struct TtaRequest {
     int *src_pass = nullptr;
 };
 
+// A zoom-pyramid call (pyramid.h; rf_detect_pyramid_batch* / rf_pyramid_merge_device): the validated spec and where the member count
+// and the pass of each merged face go
+struct PyrRequest {
+    PyrSpec spec;
+    int *votes = nullptr;                       // host, indexed like out, or nullptr
+    int *src_pass = nullptr;
+};
+
 // A tracked call (track.h; rf_track_update_device / rf_detect_track_*): the tracker (what tracker_create returned), the stream of every
 // image (-1 = not tracked) and where tags, ended lists and their counts go (host; each may be nullptr)
 struct TrackRequest {
@@ -199,6 +207,23 @@ public:
     // the mirror kernel on its own: a left-right mirrored copy of a device-resident frame
     virtual void mirror(const void *, int, int, int, void *, int) {
         throw Unsupported("test-time augmentation is not available on a multi-device handle");
+    }
+    // Zoom-pyramid detection: every frame becomes the passes of its pyramid plan -- 1x views, and tiles of the frame enlarged 2x / 4x
+    // that a zoom kernel writes on the device in front of the call's first launch -- which go through detect()'s ordinary launches; a
+    // gather launch behind each of them and one voting merge behind the last (ordered by events on the device, no host wait).
+    // *truncated: a pass or the merge hit a cap.  Single-device engines only.
+    virtual void detect_pyramid(const uint8_t *const *, const int *, const int *, const int *, int, bool, float, rf_face *, int, int *,
+                                bool *, const PyrRequest &) {
+        throw Unsupported("pyramid detection is not available on a multi-device handle");
+    }
+    // edge rule, mapping and merge of per-pass faces the caller supplies (faces[(first_pass[i] + p) * max_detections + k])
+    virtual void pyramid_merge(const int *, const int *, int, const PyrRequest &, const rf_face *, const int *, rf_face *, int, int *,
+                               bool *) {
+        throw Unsupported("pyramid detection is not available on a multi-device handle");
+    }
+    // the zoom kernel on its own: a window of a device-resident frame enlarged 2x or 4x
+    virtual void zoom(const void *, int, int, int, int, int, int, int, int, void *, int) {
+        throw Unsupported("pyramid detection is not available on a multi-device handle");
     }
     // Face tracks: a tracker's state (n_streams tables) lives in device memory between calls; the track launch of a detection launch
     // follows it on its stream, the track launches of a call wait for each other on the device.  *cut: a full table or a cut ended

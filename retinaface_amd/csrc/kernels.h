@@ -11,6 +11,7 @@
 #include "face_batch.h"
 #include "face_quality.h"
 #include "redact.h"
+#include "pyramid.h"
 #include "tile.h"
 #include "tta.h"
 #include "track.h"
@@ -362,6 +363,30 @@ struct VoteMergeParams {
     int n;
 };
 void launch_vote_merge(hipStream_t s, const VoteMergeParams &p, bool vote);     // vote false: the heads keep their own coordinates
+
+// ---- K_k: zoom-pyramid detection (pyramid.h).
+//      zoom_tile:  windows of frames enlarged 2x / 4x (integer bilinear, pyr_zoom_pixel) written as dense frames, in front of a
+//                  pyramid call's launches; mirror_rows' store discipline.
+//      pyr_gather: tta_gather's shape with pyr_map_face (edge rule and mapping) as the mapping, g = p * rank_stride + k.
+//      The merge is launch_vote_merge.
+struct ZoomParams {
+    const uint8_t *src; int rows, cols, step;     // the source frame: row y at src + y * step
+    int z, x0, y0, tw, th;                        // the window of the z rows x z cols frame
+    uint8_t *dst; int dst_step;                   // tw * 3 bytes per row are written
+};
+constexpr int kZoomTilesPerLaunch = 16;          // tiles of one launch: their descriptors travel as kernel arguments
+void launch_zoom_tiles(hipStream_t s, const ZoomParams *tiles, int n);
+
+struct PyrGatherParams {
+    const uint8_t *faces;                 // pass p, rank k: 15 floats at faces + (p * faces_per_pass + k) * face_stride
+    int face_stride, faces_per_pass;
+    const int *counts;                    // [n] faces of each pass (clamped to faces_per_pass here)
+    const PyrEntry *table;                // [n] what each pass is (frame < 0: skipped)
+    int n, edge, rank_stride;             // passes of this launch; the spec's edge; max_detections
+    Candidate *cand; int *cand_count;     // as TileGatherParams
+    int cap;
+};
+void launch_pyr_gather(hipStream_t s, const PyrGatherParams &p);
 
 // LDS bytes / tile geometry chosen for a layer (exposed for tests and DESIGN.md tables)
 struct TileInfo { int th, tw; size_t lds_bytes; int blocks_per_image; };

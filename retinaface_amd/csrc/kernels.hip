@@ -5235,6 +5235,115 @@ void launch_vote_merge(hipStream_t s, const VoteMergeParams &p, bool vote) {
     hipLaunchKernelGGL(vote_merge_kernel, dim3(p.n), dim3(NMS_THREADS), lds, s, p, vote ? 1 : 0);
 }
 
+// =============================================================================================
+// K_k: zoom-pyramid detection (pyramid.h).
+// zoom_tile_kernel: dst[y][x] = Z[y0 + y][x0 + x], Z the source frame enlarged z times (pyr_zoom_pixel, the code rf_zoom_host runs on
+//      the host: integer bilinear, clamped at the frame border).  One thread produces four output pixels = 12 bytes, which leave as
+//      three dword stores where the destination is aligned -- a dense tile at a 256-byte-aligned base with 12 | 3 * 4 * x always
+//      is -- and bytewise elsewhere; the last tw % 4 pixels of a row go bytewise.  No byte outside the tw * 3 bytes of a row is
+//      written, none outside the source frame is read (bytewise loads: ROI views at odd pointers are legal).  The source is read
+//      straight from global memory: at 2x every source pixel serves about four output pixels of neighbouring threads and rows, which
+//      L2 holds; the kernel is bound by its tw * th * 3 bytes of stores.  One launch carries up to sixteen tiles (blockIdx.y).
+// =============================================================================================
+struct ZoomBatch { ZoomParams f[kZoomTilesPerLaunch]; };
+
+__global__ __launch_bounds__(kThreads) void zoom_tile_kernel(ZoomBatch batch) {
+    const ZoomParams a = batch.f[blockIdx.y];
+    const int gpr = (a.tw + 3) >> 2;                                 // groups of four pixels per row
+    const long long total = (long long)a.th * gpr;
+    for (long long item = (long long)blockIdx.x * kThreads + threadIdx.x; item < total; item += (long long)gridDim.x * kThreads) {
+        const int y = (int)(item / gpr), x = (int)(item - (long long)y * gpr) << 2;
+        const int k = a.tw - x < 4 ? a.tw - x : 4;
+        uint8_t *dp = a.dst + (size_t)y * a.dst_step + (size_t)3 * x;
+        // the twelve bytes b0 .. b11 of pixels P0 .. P3 as three dwords, kept in registers (every index below is a constant)
+        unsigned long long lo = 0;                                   // b0 .. b7
+        uint32_t hi = 0;                                             // b8 .. b11
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (j >= k) continue;
+            uint8_t px[3];
+            pyr_zoom_pixel(a.src, a.rows, a.cols, (size_t)a.step, a.z, a.x0 + x + j, a.y0 + y, px);
+            const uint32_t p24 = px[0] | (uint32_t)px[1] << 8 | (uint32_t)px[2] << 16;
+            if (j < 2) lo |= (unsigned long long)p24 << (24 * j);
+            else if (j == 2) { lo |= (unsigned long long)(p24 & 0xffffu) << 48; hi |= p24 >> 16; }
+            else hi |= p24 << 8;
+        }
+        const uint32_t w0 = (uint32_t)lo, w1 = (uint32_t)(lo >> 32), w2 = hi;
+        if (k == 4 && ((uintptr_t)dp & 3) == 0) {
+            uint32_t *d4 = (uint32_t *)dp;
+            d4[0] = w0; d4[1] = w1; d4[2] = w2;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 12; j++) {
+                if (j < 3 * k) dp[j] = (uint8_t)((j < 4 ? w0 : j < 8 ? w1 : w2) >> (8 * (j & 3)));
+            }
+        }
+    }
+}
+
+// up to kZoomTilesPerLaunch tiles per launch (blockIdx.y), the grid sized for the largest of them: a tile's surplus workgroups find
+// no item and retire
+void launch_zoom_tiles(hipStream_t s, const ZoomParams *tiles, int n) {
+    for (int f0 = 0; f0 < n; f0 += kZoomTilesPerLaunch) {
+        ZoomBatch b;
+        memset(&b, 0, sizeof(b));
+        const int m = n - f0 < kZoomTilesPerLaunch ? n - f0 : kZoomTilesPerLaunch;
+        long long blocks = 0;
+        for (int i = 0; i < m; i++) {
+            const ZoomParams &p = tiles[f0 + i];
+            if (p.tw <= 0 || p.th <= 0) continue;              // th = 0: no items
+            b.f[i] = p;
+            const long long total = (long long)p.th * ((p.tw + 3) >> 2);
+            blocks = std::max(blocks, (total + kThreads - 1) / kThreads);
+        }
+        if (!blocks) continue;
+        hipLaunchKernelGGL(zoom_tile_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536), (unsigned)m), dim3(kThreads), 0, s, b);
+    }
+}
+
+// pyr_gather_kernel: tta_gather_kernel's shape -- one workgroup per pass of the launch, one face per thread, one atomic add per
+//      wavefront (ballot + popcount of the lanes below) on the frame's counter -- with pyr_map_face, the code rf_pyramid_map_face runs
+//      on the host, as edge rule and mapping.  A kernel of its own, so the tiled and TTA gathers cannot change.
+__global__ __launch_bounds__(kThreads) void pyr_gather_kernel(PyrGatherParams a) {
+    const int p = blockIdx.x;
+    const PyrEntry e = a.table[p];
+    if (e.frame < 0) return;
+    int cnt = a.counts[p];
+    cnt = cnt < 0 ? 0 : cnt < a.faces_per_pass ? cnt : a.faces_per_pass;
+    const int lane = (int)threadIdx.x & 63;
+    Candidate *dst = a.cand + (size_t)e.frame * a.cap;
+    for (int k0 = 0; k0 < cnt; k0 += kThreads) {
+        const int k = k0 + (int)threadIdx.x;
+        float f[15];
+        bool keep = false;
+        if (k < cnt) {
+            const float *src = (const float *)(a.faces + ((size_t)p * a.faces_per_pass + k) * a.face_stride);
+            for (int i = 0; i < 15; i++) f[i] = src[i];
+            keep = pyr_map_face(e, a.edge, f, f);
+        }
+        const unsigned long long mask = __ballot(keep);
+        if (!mask) continue;                                     // wave-uniform
+        const int leader = __ffsll((long long)mask) - 1;
+        int base = 0;
+        if (lane == leader) base = atomicAdd(a.cand_count + e.frame, __popcll(mask));
+        base = __shfl(base, leader);
+        if (!keep) continue;
+        const int pos = base + __popcll(mask & ((1ull << lane) - 1ull));
+        if (pos >= a.cap) continue;                              // the counter keeps the true number: the merge reports the overflow
+        Candidate c;
+        c.score = f[0];
+        c.x1 = f[1]; c.y1 = f[2]; c.x2 = f[3]; c.y2 = f[4];
+        for (int i = 0; i < 5; i++) { c.px[i] = f[5 + i]; c.py[i] = f[10 + i]; }
+        c.anchor = e.p * a.rank_stride + k;
+        dst[pos] = c;
+    }
+}
+
+void launch_pyr_gather(hipStream_t s, const PyrGatherParams &p) {
+    if (p.n <= 0) return;
+    hipLaunchKernelGGL(pyr_gather_kernel, dim3(p.n), dim3(kThreads), 0, s, p);
+}
+
 #ifdef RF_KERNEL_TRACE
 extern "C" int rf_trace_select(int kernel_id, unsigned grid) {
     static unsigned long long zeros[kTraceBlocks * kTraceSlots];

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (rf_face, rf_face_batch_spec, rf_face_gate, rf_face_quality, rf_options, rf_redact_spec, rf_tile_spec, rf_track,
-                   rf_track_spec, rf_track_tag, rf_tta_spec)
+                   rf_pyramid_spec, rf_track_spec, rf_track_tag, rf_tta_spec)
 
 PRECISION_FP32, PRECISION_FP16, PRECISION_INT8 = 0, 1, 2
 
@@ -450,6 +450,102 @@ def tta_merge_host(passes, rows: int, cols: int, net_h: int, net_w: int, nms_thr
     k = max(0, min(count.value, cap, sp.max_faces or md))
     return (_faces_to_array(out, max(cap, 1))[:k], int(count.value), np.array(votes[:k], np.int32), np.array(src[:k], np.int32),
             st == _lib.RF_ERR_TRUNCATED)
+
+
+def pyramid_spec(levels: int = 0, overlap: int = 0, edge: int = 0, full_frame: bool = True, max_faces: int = 0,
+                 vote: bool = True) -> rf_pyramid_spec:
+    """An rf_pyramid_spec: levels (bit 0: the 1x passes, bit 1: 2x zoom tiles, bit 2: 4x zoom tiles; 0 = 3), overlap / edge /
+    full_frame / max_faces as tile_spec (overlap and edge in net pixels at every level), vote as tta_spec."""
+    sp = rf_pyramid_spec()
+    sp.struct_size = C.sizeof(rf_pyramid_spec)
+    sp.levels, sp.overlap, sp.edge, sp.full_frame, sp.max_faces, sp.vote = (int(levels), int(overlap), int(edge), 1 if full_frame else 2,
+                                                                            int(max_faces), 1 if vote else 2)
+    return sp
+
+
+def pyramid_plan(rows: int, cols: int, net_h: int, net_w: int, levels: int = 0, overlap: int = 0, full_frame: bool = True,
+                 spec=None) -> np.ndarray:
+    """rf_pyramid_plan (host only, no GPU): the passes of a rows x cols frame at a net_h x net_w net as a (passes, 5) int32 array of
+    z, x0, y0, tw, th in the level's virtual pixels -- the 1x passes of tile_plan, then the 2x tiles, then the 4x tiles."""
+    lib = _lib.load_library()
+    sp = spec if spec is not None else pyramid_spec(levels, overlap, 0, full_frame)
+    n = lib.rf_pyramid_plan(C.byref(sp), int(rows), int(cols), int(net_h), int(net_w), None, 0)
+    if n < 0:
+        raise _lib.RFError(n, "rf_pyramid_plan: bad spec, frame or net size, more than 1024 passes or zoom tiles above 1 GiB")
+    out = np.zeros((n, 5), np.int32)
+    lib.rf_pyramid_plan(C.byref(sp), int(rows), int(cols), int(net_h), int(net_w), out.ctypes.data_as(C.POINTER(C.c_int)), n)
+    return out
+
+
+def pyramid_map_face(face, p: int, rows: int, cols: int, net_h: int, net_w: int, levels: int = 0, overlap: int = 0, edge: int = 0,
+                     full_frame: bool = True):
+    """rf_pyramid_map_face (host only, no GPU): the face (a Detection or 15 floats) of pass p of the pyramid plan moved into
+    source-frame pixels as 15 float32, or None when the edge rule drops it."""
+    lib = _lib.load_library()
+    sp = pyramid_spec(levels, overlap, edge, full_frame)
+    f = rf_face.from_buffer_copy(_face_rows([face])[0].tobytes())
+    g = rf_face()
+    st = lib.rf_pyramid_map_face(C.byref(sp), int(rows), int(cols), int(net_h), int(net_w), int(p), C.byref(f), C.byref(g))
+    if st < 0:
+        raise _lib.RFError(st, "rf_pyramid_map_face: bad spec, frame, net size or pass index")
+    return _faces_to_array(C.pointer(g), 1)[0] if st else None
+
+
+def pyramid_merge_host(passes, rows: int, cols: int, net_h: int, net_w: int, nms_threshold: float, max_detections: int, levels: int = 0,
+                       overlap: int = 0, edge: int = 0, full_frame: bool = True, max_faces: int = 0, vote: bool = True,
+                       cap: Optional[int] = None, spec=None):
+    """rf_pyramid_merge_host (host only, no GPU): edge rule, mapping and merge of ONE frame -- passes[p]: the faces of pass p of the
+    pyramid plan (a (k, 15) array, rows of 15 floats or Detections).  Returns (faces (k, 15) float32 in merge order, count: the true
+    number of heads, votes (k,) int32, src_pass (k,) int32, truncated)."""
+    lib = _lib.load_library()
+    sp = spec if spec is not None else pyramid_spec(levels, overlap, edge, full_frame, max_faces, vote)
+    md = int(max_detections)
+    if md < 1:
+        raise _lib.RFError(_lib.RF_ERR_INVALID_ARG, "rf_pyramid_merge_host: max_detections must be positive")
+    want = lib.rf_pyramid_plan(C.byref(sp), int(rows), int(cols), int(net_h), int(net_w), None, 0)
+    if want < 0 or len(passes) != want:
+        raise _lib.RFError(_lib.RF_ERR_INVALID_ARG, "rf_pyramid_merge_host: bad spec or frame, or not one list of faces per pass of the plan")
+    rows_ = [_face_rows(p) for p in passes]
+    flat = np.zeros((max(len(rows_), 1), md, 15), np.float32)
+    pc = (C.c_int * max(len(rows_), 1))()
+    for p, r in enumerate(rows_):
+        flat[p, :min(len(r), md)] = r[:md]
+        pc[p] = len(r)
+    cap = int(cap) if cap is not None else (sp.max_faces or md)
+    out = (rf_face * max(cap, 1))()
+    votes, src = (C.c_int * max(cap, 1))(), (C.c_int * max(cap, 1))()
+    count = C.c_int(0)
+    st = lib.rf_pyramid_merge_host(C.byref(sp), int(rows), int(cols), int(net_h), int(net_w), float(nms_threshold), md,
+                                   flat.ctypes.data_as(C.POINTER(rf_face)), pc, out, cap, C.byref(count), votes, src)
+    if st < 0 and st != _lib.RF_ERR_TRUNCATED:
+        raise _lib.RFError(st, "rf_pyramid_merge_host: bad spec, frame, net size or counts")
+    k = max(0, min(count.value, cap, sp.max_faces or md))
+    return (_faces_to_array(out, max(cap, 1))[:k], int(count.value), np.array(votes[:k], np.int32), np.array(src[:k], np.int32),
+            st == _lib.RF_ERR_TRUNCATED)
+
+
+def zoom_host(frame: np.ndarray, z: int, x0: int = 0, y0: int = 0, tw: Optional[int] = None, th: Optional[int] = None,
+              out: Optional[np.ndarray] = None) -> np.ndarray:
+    """rf_zoom_host (host only, no GPU): the window [x0, x0 + tw) x [y0, y0 + th) of the BGR frame enlarged z (2 or 4) times (integer
+    bilinear, half-pixel centres; default: the whole enlarged frame).  `out`: a uint8 (th, >= tw, 3) view to write into (its row
+    pitch is kept); returned either way."""
+    lib = _lib.load_library()
+    if frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3:
+        raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
+    if frame.strides[2] != 1 or frame.strides[1] != 3:
+        frame = np.ascontiguousarray(frame)
+    rows, cols = frame.shape[:2]
+    tw = int(z) * cols - int(x0) if tw is None else int(tw)
+    th = int(z) * rows - int(y0) if th is None else int(th)
+    if out is None:
+        out = np.zeros((max(th, 0), max(tw, 0), 3), np.uint8)
+    if out.dtype != np.uint8 or out.ndim != 3 or out.shape[2] != 3 or out.strides[2] != 1 or out.strides[1] != 3 or out.shape[0] < th:
+        raise ValueError("out must be a uint8 (th, tw, 3) array or row-pitched view")
+    st = lib.rf_zoom_host(frame.ctypes.data, rows, cols, frame.strides[0] if rows else 3 * cols, int(z), int(x0), int(y0), tw, th,
+                          out.ctypes.data, out.strides[0] if out.shape[0] else 3 * max(tw, 0))
+    if st < 0:
+        raise _lib.RFError(st, "rf_zoom_host: z must be 2 or 4 and the window must lie inside the enlarged frame")
+    return out
 
 
 def _faces_to_array(buf, n: int) -> np.ndarray:
@@ -1150,6 +1246,98 @@ class RetinaFace:
         is row y of the BGR frame at src_ptr (row pitch `step`, any alignment) mirrored left-right.  Both in device memory."""
         _lib.check(self._lib.rf_mirror_device(self._h, src_ptr, int(rows), int(cols), int(step if step is not None else 3 * cols), dst_ptr,
                                               int(dst_step if dst_step is not None else 3 * cols)), self._h)
+
+    # ------------------------------------------------------------------ zoom-pyramid detection
+    def detect_pyramid(self, imgs: Sequence[np.ndarray], threshold: float = 0.5, levels: int = 0, overlap: int = 0, edge: int = 0,
+                       full_frame: bool = True, max_faces: int = 0, vote: bool = True, return_votes: bool = False):
+        """rf_detect_pyramid_batch: every frame is detected at 1x (its tile plan) and as net-sized tiles of the frame enlarged 2x / 4x
+        on the device (levels: bit 0 1x, bit 1 2x, bit 2 4x; 0 = 1x and 2x), so that faces below the smallest anchor are found; the
+        faces of all passes are moved back and merged as in detect_tta.  Returns per frame the merged detections in SOURCE-FRAME
+        pixels (anchor_index is -1); with return_votes also, per frame, how many candidates each face merged and the pass of the
+        plan (pyramid_plan) its head came from.  self.pyramid_counts holds the true merged counts."""
+        n = len(imgs)
+        ptrs = (C.c_void_p * max(n, 1))()
+        rows, cols, steps = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
+        keep = []
+        for i, im in enumerate(imgs):
+            if im is None or im.size == 0:
+                ptrs[i], rows[i], cols[i], steps[i] = None, 0, 0, 0
+                continue
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
+            if im.strides[2] != 1 or im.strides[1] != 3:
+                im = np.ascontiguousarray(im)
+            keep.append(im)
+            ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
+        return self._run_pyramid(self._lib.rf_detect_pyramid_batch, ptrs, rows, cols, steps, n, threshold,
+                                 pyramid_spec(levels, overlap, edge, full_frame, max_faces, vote), return_votes)
+
+    def detect_pyramid_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], threshold: float = 0.5,
+                              steps: Optional[Sequence[int]] = None, levels: int = 0, overlap: int = 0, edge: int = 0,
+                              full_frame: bool = True, max_faces: int = 0, vote: bool = True, return_votes: bool = False):
+        """rf_detect_pyramid_batch_device: detect_pyramid for frames resident in device memory (0 / None: an empty frame)."""
+        n = len(ptrs)
+        p = (C.c_void_p * max(n, 1))(*ptrs)
+        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
+        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        return self._run_pyramid(self._lib.rf_detect_pyramid_batch_device, p, r, c, s, n, threshold,
+                                 pyramid_spec(levels, overlap, edge, full_frame, max_faces, vote), return_votes)
+
+    def _collect_pyramid(self, out, counts, votes, src, n, cap, return_votes):
+        kept = getattr(self, "tta_counts", None)             # _collect_tta's layout is this call's too; its counts are not
+        res = self._collect_tta(out, counts, votes, src, n, cap, return_votes)
+        self.pyramid_counts, self.tta_counts = self.tta_counts, kept
+        return res
+
+    def _run_pyramid(self, fn, ptrs, rows, cols, steps, n, threshold, sp, return_votes):
+        cap = sp.max_faces or self.max_detections
+        out = (rf_face * max(n * cap, 1))()
+        counts = (C.c_int * max(n, 1))()
+        votes, src = (C.c_int * max(n * cap, 1))(), (C.c_int * max(n * cap, 1))()
+        st = _lib.check(fn(self._h, ptrs, rows, cols, steps, n, float(threshold), C.byref(sp), out, cap, counts, votes, src), self._h)
+        self.truncated = st == _lib.RF_ERR_TRUNCATED
+        return self._collect_pyramid(out, counts, votes, src, n, cap, return_votes)
+
+    def pyramid_merge(self, rows: Sequence[int], cols: Sequence[int], per_pass_faces, levels: int = 0, overlap: int = 0, edge: int = 0,
+                      full_frame: bool = True, max_faces: int = 0, vote: bool = True, cap_per_image: Optional[int] = None,
+                      return_votes: bool = False):
+        """rf_pyramid_merge_device: edge rule, mapping and merge of per-pass faces the caller supplies -- per_pass_faces[i][p]: the
+        faces of pass p of frame i's pyramid plan (a (k, 15) array, rows of 15 floats or Detections, at most max_detections).  No
+        forward pass runs.  Returns as detect_pyramid; self.pyramid_counts holds the true merged counts."""
+        n = len(rows)
+        sp = pyramid_spec(levels, overlap, edge, full_frame, max_faces, vote)
+        md = self.max_detections
+        if len(per_pass_faces) != n:
+            raise ValueError("per_pass_faces: one list of passes per frame")
+        for i in range(n):
+            want = 1 if rows[i] <= 0 or cols[i] <= 0 else self._lib.rf_pyramid_plan(C.byref(sp), int(rows[i]), int(cols[i]), self.net_h,
+                                                                                    self.net_w, None, 0)
+            if want >= 0 and len(per_pass_faces[i]) != want:
+                raise ValueError("per_pass_faces[%d]: %d passes, the plan has %d" % (i, len(per_pass_faces[i]), want))
+        passes = [_face_rows(f) for frame in per_pass_faces for f in frame]
+        flat = np.zeros((max(len(passes), 1), md, 15), np.float32)
+        pc = (C.c_int * max(len(passes), 1))()
+        for p, r in enumerate(passes):
+            flat[p, :min(len(r), md)] = r[:md]
+            pc[p] = len(r)
+        cap = int(cap_per_image) if cap_per_image is not None else (sp.max_faces or md)
+        out = (rf_face * max(n * cap, 1))()
+        counts = (C.c_int * max(n, 1))()
+        votes, src = (C.c_int * max(n * cap, 1))(), (C.c_int * max(n * cap, 1))()
+        st = _lib.check(self._lib.rf_pyramid_merge_device(self._h, (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols), n,
+                                                          C.byref(sp), flat.ctypes.data_as(C.POINTER(rf_face)), pc, out, cap, counts, votes,
+                                                          src), self._h)
+        self.truncated = st == _lib.RF_ERR_TRUNCATED
+        return self._collect_pyramid(out, counts, votes, src, n, cap, return_votes)
+
+    def zoom_device(self, src_ptr: int, rows: int, cols: int, z: int, x0: int, y0: int, tw: int, th: int, dst_ptr: int,
+                    step: Optional[int] = None, dst_step: Optional[int] = None):
+        """rf_zoom_device: the zoom kernel on its own -- the window [x0, x0 + tw) x [y0, y0 + th) of the BGR frame at src_ptr (row
+        pitch `step`, any alignment) enlarged z (2 or 4) times, written as tw * 3 bytes per row, dst_step bytes apart.  Both in
+        device memory."""
+        _lib.check(self._lib.rf_zoom_device(self._h, src_ptr, int(rows), int(cols), int(step if step is not None else 3 * cols), int(z),
+                                            int(x0), int(y0), int(tw), int(th), dst_ptr,
+                                            int(dst_step if dst_step is not None else 3 * tw)), self._h)
 
     def enqueue_device(self, ptrs, rows, cols, threshold: float = 0.5) -> int:
         n = len(ptrs)
