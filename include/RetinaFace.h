@@ -122,6 +122,19 @@ public:
     const vector<vector<rf_track_tag>> &lastTrackTags() const { return trackTags_; }
     const vector<vector<rf_track>> &lastEndedTracks() const { return trackEnded_; }
 
+    /* additive: best-shot gallery (rf_tracker_enable_shots / rf_detect_track_shots_batch): enableShots() gives a tracker a gallery of
+       face-batch crops (spec as detectFaceBatch(); capacity is not used) and returns the bytes of one shot; from then on the tracker is
+       stepped with detectTrackShots(), which is detectTracked() plus the shots of the tracks that end: lastShots()[i] holds
+       lastEndedTracks()[i].size() shots back to back, lastShotInfo()[i] their records.  With a gate the best shot goes by sharpness among
+       the faces the gate keeps, otherwise by score.  capEnded: ended tracks reported per image (more than that throws).  flushShots()
+       ends a stream's live tracks and returns them with their shots. */
+    size_t enableShots(rf_tracker tracker, const rf_face_batch_spec &spec);
+    void detectTrackShots(const vector<cv::Mat> &imgs, rf_tracker tracker, const vector<int> &streams, float threshold = 0.5,
+                          const rf_face_gate *gate = nullptr, int capEnded = 64);
+    const vector<vector<uint8_t>> &lastShots() const { return shots_; }
+    const vector<vector<rf_shot>> &lastShotInfo() const { return shotInfo_; }
+    vector<rf_track> flushShots(rf_tracker tracker, int stream, vector<uint8_t> *shots, vector<rf_shot> *info);
+
     /* additive: face redaction (rf_detect_redact_batch): detectBatchImages() plus redaction of the faces it finds, IN PLACE in the Mats'
        pixels (pixelate or fill, rectangle or ellipse: rf_redact_spec; nullptr = the defaults).  Fills lastBatchResult();
        redactedPixels()[i][k] is the number of pixels face k of image i owns. */
@@ -158,6 +171,9 @@ private:
     vector<vector<rf_track_tag>> trackTags_;
     vector<vector<rf_track>> trackEnded_;
     vector<vector<int32_t>> redactPixels_;
+    map<rf_tracker, size_t> shotBytes_;
+    vector<vector<uint8_t>> shots_;
+    vector<vector<rf_shot>> shotInfo_;
     vector<uint8_t> faceBatchCall(const vector<cv::Mat> &imgs, float threshold, const rf_face_batch_spec &spec, bool gated,
                                   const rf_face_gate *gate);
 };

@@ -506,6 +506,82 @@ int rf_detect_track_face_batch_device(rf_handle h, const void *const *d_bgr, con
                                       rf_face_quality *quality, rf_tracker tracker, const int *stream_of_image, rf_track_tag *tags,
                                       rf_track *ended, int cap_ended, int *ended_counts);
 
+/* ---- Best-shot gallery: every track slot keeps the pixels of its best shot in device memory, and a track hands them over when it ends
+ * (DESIGN.md "Best-shot gallery" holds the definition; tests/shot_ref.py restates it in numpy; every result is byte-exact against it).
+ * A tracker may own a gallery: n_streams x max_tracks entries of bytes_per_face (one face's tensor of rf_face_batch_device for the
+ * gallery spec) and one rf_shot record per slot.  The frame step is rf_track_step's, tags / ended lists / counts / table are the bytes of
+ * the plain tracked call, and two rules are added:
+ *   keep     a face whose tag carries RF_TRACK_BEST sets its track's slot: the entry becomes exactly the bytes rf_face_batch_device
+ *            writes for that face of that image (its own coordinates and coord_scale, not the mapped rf_track.best) with the gallery
+ *            spec, the record becomes {id, f, matrix}
+ *   deliver  every ended track that makes it into the image's ended list (the first min(ended_counts[i], cap_ended)) gets its shot at
+ *            shots + (i * cap_ended + e) * bytes_per_face and its record at shot_info[i * cap_ended + e], the index of its rf_track in
+ *            `ended`.  A track with best_frame < 0 (every face it had was gated) gets an all-zero shot and record.  Tracks cut from the
+ *            list deliver nothing; shots and records beyond the delivered ones are not written.
+ * Order within a frame is the tracker's: age (which ends tracks), then open -- a track that ends and one that opens in the same slot in
+ * the same frame are both well defined: the ended track delivers the old entry, the slot then holds the new track's crop.  The entry of
+ * a free slot, and of a live track with best_frame < 0, is unspecified in device memory; rf_tracker_read_shots / rf_tracker_flush_shots
+ * return zeros for them. */
+#define RF_SHOT_MAX_BYTES (1u << 30)
+typedef struct rf_shot {    /* 64 bytes, no padding */
+    int64_t id;             /* the track's id; 0 = no shot, the whole record is zero */
+    int64_t frame;          /* the track's best_frame */
+    double matrix[6];       /* rf_align_matrix of that face: the bytes the face-batch call writes to `matrices` */
+} rf_shot;
+
+/* Host only, no GPU, no handle -- the decisions of the two shot kernels, from the same code, for ONE stream's n images of one launch in
+ * call order.  tags: n * cap_per_image (what the frame steps wrote), counts: n; ended / ended_counts: n * cap_ended / n; first_frame:
+ * the stream's frame index of image 0; records: max_tracks shot records, before the launch on entry, after it on return (faces /
+ * coord_scale / crop_size feed the matrix: faces n * cap_per_image or NULL = zero matrices, coord_scale n or NULL = 1).
+ * source (may be NULL): 3 ints per ended-list entry (i * cap_ended + e): kind RF_SHOT_NONE (zero shot) / RF_SHOT_STORED (a = slot, b = 0)
+ * / RF_SHOT_LAUNCH (a = image, b = face of this launch); entries beyond the delivered ones are {-1, -1, -1}.  owner (may be NULL):
+ * 2 ints per slot, the (image, face) of this launch whose crop the slot holds afterwards, or {-1, -1}: the launch leaves it alone.  The
+ * record of a delivered track is zeroed (its slot is free).  Returns the number of delivered shots, or RF_ERR_INVALID_ARG. */
+enum { RF_SHOT_NONE = 0, RF_SHOT_STORED = 1, RF_SHOT_LAUNCH = 2 };
+int rf_shot_resolve(int max_tracks, int n, const rf_track_tag *tags, int cap_per_image, const int *counts, const rf_track *ended,
+                    int cap_ended, const int *ended_counts, int64_t first_frame, const rf_face *faces, const float *coord_scale,
+                    int crop_size, rf_shot *records, int32_t *source, int32_t *owner);
+
+/* Fixes the tracker's gallery for its lifetime: crop_size, format, rgb, mean, scale, antialias, aa_max and max_faces mean what they mean
+ * in rf_face_batch_device; capacity is validated as there (>= 1) and otherwise unused.  RF_ERR_INVALID_ARG, before any state changes,
+ * for a bad spec, a gallery above RF_SHOT_MAX_BYTES, a tracker that has stepped a frame (any stream's frame counter non-zero) or one
+ * that has a gallery already.  Every tracked call without "shots" in its name then refuses the tracker (RF_ERR_INVALID_ARG, nothing
+ * changes), so a gallery never goes stale; rf_tracker_read / rf_tracker_flush / rf_tracker_reset keep working (reset also zeroes the
+ * stream's shot records). */
+int rf_tracker_enable_shots(rf_tracker tracker, const rf_face_batch_spec *spec);
+/* Host copy of the first min(cap, max_tracks) slots of a stream: entries (bytes_per_face each; may be NULL) and records (may be NULL).
+ * A slot that is free, whose track has best_frame < 0 or whose record is not its track's reads as zeros.  Returns max_tracks. */
+int rf_tracker_read_shots(rf_tracker tracker, int stream, void *shots, rf_shot *shot_info, int cap);
+/* rf_tracker_flush + the shots of the tracks it ends, in the same order (the first min(count, cap); shots / shot_info may be NULL). */
+int rf_tracker_flush_shots(rf_tracker tracker, int stream, rf_track *ended, int cap, int64_t *frames, int64_t *next_id, void *shots,
+                           rf_shot *shot_info);
+
+/* rf_track_update_device against frames resident on the device (those of rf_face_batch_device: any pointer and row step, NULL / 0 x 0 =
+ * a frame with no faces), plus the gallery rules.  max_faces is the gallery spec's; quality: NULL (best by score) or n * max_faces
+ * records.  d_shots (device) and shots (host) are n * cap_ended faces each, shot_info n * cap_ended records; each may be NULL.  A shots
+ * block above RF_SHOT_MAX_BYTES is refused.  The tracker must have a gallery.  Dirty-tracker rules as above. */
+int rf_track_shots_device(rf_handle h, rf_tracker tracker, const void *const *d_bgr, const int *rows, const int *cols, const int *steps,
+                          int n, const int *stream_of_image, const rf_face *faces, int cap_per_image, const int *counts,
+                          const float *coord_scale, const rf_face_quality *quality, rf_track_tag *tags, rf_track *ended, int cap_ended,
+                          int *ended_counts, void *d_shots, void *shots, rf_shot *shot_info);
+/* Measurement hook: the time of the two shot launches of the handle's most recent rf_track_shots_device call, between two HIP events. */
+int rf_shot_last_launch_ms(rf_handle h, float *ms);
+
+/* rf_detect_batch_device / rf_detect_batch + the frame steps + the gallery rules in one call; detection runs exactly as there.  With a
+ * gate or a quality buffer the quality launch of the gated face-batch path runs for the gallery spec with no tensor (the records are
+ * the bytes of rf_face_quality_device for that spec) and the best shot goes by sharpness among the faces whose flags are 0; otherwise
+ * by score.  The shot launches follow each track launch on its stream and join the chain the track launches form; frames larger than
+ * the net are sampled at full resolution with rf_frame_scale.  The call produces no per-frame tensor.  There is no shot form of the
+ * asynchronous tickets, of pad32, of the tiled, TTA and pyramid calls or of redaction, and none on multi-device handles. */
+int rf_detect_track_shots_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                       float threshold, rf_face *out, int cap_per_image, int *counts, rf_tracker tracker,
+                                       const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_counts,
+                                       const rf_face_gate *gate, rf_face_quality *quality, void *d_shots, void *shots, rf_shot *shot_info);
+int rf_detect_track_shots_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                                float threshold, rf_face *out, int cap_per_image, int *counts, rf_tracker tracker,
+                                const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_counts,
+                                const rf_face_gate *gate, rf_face_quality *quality, void *d_shots, void *shots, rf_shot *shot_info);
+
 /* ---- Face redaction: pixelate or fill the faces of a frame IN PLACE, on the device (DESIGN.md "Face redaction" holds the definition;
  * tests/redact_ref.py restates it in numpy; every result is byte-exact against it).  Frames are CV_8UC3 BGR with any pointer and row step.
  *   region   of a face with box x1, y1, x2, y2 in a rows x cols frame, coord_scale s (fp32, one rounding per operation, never contracted):

@@ -73,6 +73,14 @@ class rf_track_tag(C.Structure):
     _fields_ = [("id", C.c_int64), ("slot", C.c_int32), ("hits", C.c_int32), ("age", C.c_int32), ("flags", C.c_int32)]
 
 
+class rf_shot(C.Structure):
+    _fields_ = [("id", C.c_int64), ("frame", C.c_int64), ("matrix", C.c_double * 6)]
+
+
+RF_SHOT_NONE, RF_SHOT_STORED, RF_SHOT_LAUNCH = 0, 1, 2
+RF_SHOT_MAX_BYTES = 1 << 30
+
+
 class rf_redact_spec(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("shape", C.c_int32), ("cells", C.c_int32), ("margin", C.c_float),
                 ("fill", C.c_uint8 * 3), ("reserved", C.c_uint8), ("max_regions", C.c_int32), ("coast", C.c_int32)]
@@ -183,6 +191,24 @@ SYMBOLS = {
                                                     C.c_void_p, C.c_void_p, _PP(C.c_double), _PP(C.c_int), _PP(rf_face_gate),
                                                     _PP(rf_face_quality), C.c_void_p, _PP(C.c_int), _PP(rf_track_tag), _PP(rf_track),
                                                     C.c_int, _PP(C.c_int)]),
+    "rf_shot_resolve": (C.c_int, [C.c_int, C.c_int, _PP(rf_track_tag), C.c_int, _PP(C.c_int), _PP(rf_track), C.c_int, _PP(C.c_int), C.c_int64,
+                                  _PP(rf_face), _PP(C.c_float), C.c_int, _PP(rf_shot), _PP(C.c_int32), _PP(C.c_int32)]),
+    "rf_tracker_enable_shots": (C.c_int, [C.c_void_p, _PP(rf_face_batch_spec)]),
+    "rf_tracker_read_shots": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, _PP(rf_shot), C.c_int]),
+    "rf_tracker_flush_shots": (C.c_int, [C.c_void_p, C.c_int, _PP(rf_track), C.c_int, _PP(C.c_int64), _PP(C.c_int64), C.c_void_p,
+                                         _PP(rf_shot)]),
+    "rf_track_shots_device": (C.c_int, [C.c_void_p, C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                        _PP(C.c_int), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_float), _PP(rf_face_quality),
+                                        _PP(rf_track_tag), _PP(rf_track), C.c_int, _PP(C.c_int), C.c_void_p, C.c_void_p, _PP(rf_shot)]),
+    "rf_shot_last_launch_ms": (C.c_int, [C.c_void_p, _PP(C.c_float)]),
+    "rf_detect_track_shots_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                                     C.c_float, _PP(rf_face), C.c_int, _PP(C.c_int), C.c_void_p, _PP(C.c_int),
+                                                     _PP(rf_track_tag), _PP(rf_track), C.c_int, _PP(C.c_int), _PP(rf_face_gate),
+                                                     _PP(rf_face_quality), C.c_void_p, C.c_void_p, _PP(rf_shot)]),
+    "rf_detect_track_shots_batch": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                              C.c_float, _PP(rf_face), C.c_int, _PP(C.c_int), C.c_void_p, _PP(C.c_int),
+                                              _PP(rf_track_tag), _PP(rf_track), C.c_int, _PP(C.c_int), _PP(rf_face_gate),
+                                              _PP(rf_face_quality), C.c_void_p, C.c_void_p, _PP(rf_shot)]),
     "rf_redact_region": (C.c_int, [_PP(rf_redact_spec), _PP(rf_face), C.c_float, C.c_int, C.c_int, _PP(C.c_int)]),
     "rf_redact_host": (C.c_int, [_PP(rf_redact_spec), C.c_void_p, C.c_int, C.c_int, C.c_int, _PP(rf_face), C.c_int, C.c_float,
                                  _PP(C.c_int32)]),

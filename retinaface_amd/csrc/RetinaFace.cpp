@@ -133,6 +133,69 @@ void RetinaFace::detectTracked(const vector<cv::Mat> &imgs, rf_tracker tracker, 
     }
 }
 
+size_t RetinaFace::enableShots(rf_tracker tracker, const rf_face_batch_spec &spec) {
+    check(rf_tracker_enable_shots(tracker, &spec), h_, "RetinaFace::enableShots");
+    const size_t S = spec.crop_size ? (size_t)spec.crop_size : 112;
+    const size_t bytes = 3 * S * S * (spec.format == RF_FACES_F32_CHW ? 4 : spec.format == RF_FACES_F16_CHW ? 2 : 1);
+    shotBytes_[tracker] = bytes;
+    return bytes;
+}
+
+void RetinaFace::detectTrackShots(const vector<cv::Mat> &imgs, rf_tracker tracker, const vector<int> &streams, float threshold,
+                                  const rf_face_gate *gate, int capEnded) {
+    const int n = (int)imgs.size();
+    if ((int)streams.size() != n) throw std::runtime_error("RetinaFace::detectTrackShots: one stream per image");
+    if (!shotBytes_.count(tracker) || capEnded < 1) throw std::runtime_error("RetinaFace::detectTrackShots: enableShots() first, capEnded >= 1");
+    const size_t bpf = shotBytes_[tracker];
+    lastBatch_.assign(n, vector<FaceDetectInfo>());
+    trackTags_.assign(n, vector<rf_track_tag>());
+    trackEnded_.assign(n, vector<rf_track>());
+    shots_.assign(n, vector<uint8_t>());
+    shotInfo_.assign(n, vector<rf_shot>());
+    if (n == 0) return;
+    vector<const uint8_t *> ptrs(n);
+    vector<int> rows(n), cols(n), steps(n), counts(n, 0), endedCounts(n, 0);
+    for (int i = 0; i < n; i++) {
+        ptrs[i] = imgs[i].empty() ? nullptr : imgs[i].data;
+        rows[i] = imgs[i].rows; cols[i] = imgs[i].cols; steps[i] = (int)(size_t)imgs[i].step;
+    }
+    vector<rf_face> faces((size_t)n * maxDet_);
+    vector<rf_track_tag> tags((size_t)n * maxDet_);
+    vector<rf_track> ended((size_t)n * capEnded);
+    vector<uint8_t> shots((size_t)n * capEnded * bpf);
+    vector<rf_shot> info((size_t)n * capEnded);
+    const int st = rf_detect_track_shots_batch(h_, ptrs.data(), rows.data(), cols.data(), steps.data(), n, threshold, faces.data(), maxDet_,
+                                               counts.data(), tracker, streams.data(), tags.data(), ended.data(), capEnded, endedCounts.data(),
+                                               gate, nullptr, nullptr, shots.data(), info.data());
+    check(st, h_, "RetinaFace::detectTrackShots");
+    for (int i = 0; i < n; i++) {
+        const int k = counts[i] < maxDet_ ? counts[i] : maxDet_;
+        lastBatch_[i].resize(k);
+        if (k) memcpy(lastBatch_[i].data(), &faces[(size_t)i * maxDet_], (size_t)k * sizeof(rf_face));
+        trackTags_[i].assign(tags.begin() + (size_t)i * maxDet_, tags.begin() + (size_t)i * maxDet_ + k);
+        if (endedCounts[i] > capEnded) throw std::runtime_error("RetinaFace::detectTrackShots: more tracks ended in one frame than capEnded");
+        const size_t e = (size_t)endedCounts[i], at = (size_t)i * capEnded;
+        trackEnded_[i].assign(ended.begin() + at, ended.begin() + at + e);
+        shots_[i].assign(shots.begin() + at * bpf, shots.begin() + (at + e) * bpf);
+        shotInfo_[i].assign(info.begin() + at, info.begin() + at + e);
+    }
+}
+
+vector<rf_track> RetinaFace::flushShots(rf_tracker tracker, int stream, vector<uint8_t> *shots, vector<rf_shot> *info) {
+    if (!shotBytes_.count(tracker)) throw std::runtime_error("RetinaFace::flushShots: enableShots() first");
+    const size_t bpf = shotBytes_[tracker];
+    const int cap = 256;                               // a table holds at most 256 tracks
+    vector<rf_track> ended(cap);
+    vector<uint8_t> px((size_t)cap * bpf);
+    vector<rf_shot> rec(cap);
+    const int k = rf_tracker_flush_shots(tracker, stream, ended.data(), cap, nullptr, nullptr, px.data(), rec.data());
+    if (k < 0) check(k, h_, "RetinaFace::flushShots");
+    ended.resize(k);
+    if (shots) shots->assign(px.begin(), px.begin() + (size_t)k * bpf);
+    if (info) info->assign(rec.begin(), rec.begin() + k);
+    return ended;
+}
+
 void RetinaFace::detectTta(const vector<cv::Mat> &imgs, float threshold, const rf_tta_spec *spec) {
     const int n = (int)imgs.size();
     lastBatch_.assign(n, vector<FaceDetectInfo>());

@@ -723,6 +723,120 @@ int rf_detect_track_face_batch_device(rf_handle h, const void *const *d_bgr, con
     });
 }
 
+// ---- best-shot gallery (shot.h)
+int rf_shot_resolve(int max_tracks, int n, const rf_track_tag *tags, int cap_per_image, const int *counts, const rf_track *ended,
+                    int cap_ended, const int *ended_counts, int64_t first_frame, const rf_face *faces, const float *coord_scale,
+                    int crop_size, rf_shot *records, int32_t *source, int32_t *owner) {
+    if (max_tracks < 1 || max_tracks > rf::kTrackMaxTracks || n < 0 || cap_per_image < 1 || cap_ended < 0 || first_frame < 0 || !records)
+        return RF_ERR_INVALID_ARG;
+    if (n > 0 && (!tags || !counts || !ended_counts)) return RF_ERR_INVALID_ARG;
+    if (cap_ended > 0 && n > 0 && !ended) return RF_ERR_INVALID_ARG;
+    if (faces && (crop_size < rf::kAlignMinCrop || crop_size > rf::kAlignMaxCrop)) return RF_ERR_INVALID_ARG;
+    for (int i = 0; i < n; i++)
+        if (counts[i] < 0 || ended_counts[i] < 0) return RF_ERR_INVALID_ARG;
+    return rf::shot_resolve(max_tracks, n, tags, cap_per_image, counts, ended, cap_ended, ended_counts, first_frame, faces, coord_scale,
+                            crop_size, records, source, owner);
+}
+
+namespace {
+void shot_request(const rf_face_gate *gate, rf_face_quality *quality, void *d_shots, void *shots, rf_shot *shot_info, rf::ShotRequest *sq) {
+    sq->d_shots = (uint8_t *)d_shots; sq->shots = (uint8_t *)shots; sq->info = shot_info;
+    sq->gated = gate || quality;
+    sq->has_gate = gate != nullptr;
+    if (gate)
+        if (const char *bad = rf::face_gate_resolve(gate, &sq->gate)) throw rf::ArgError(bad);
+    sq->quality = quality;
+}
+
+int detect_track_shots_common(rf_handle h, const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,
+                              float thr, rf_face *out, int cap, int *counts, rf_tracker tracker, const int *stream_of_image, rf_track_tag *tags,
+                              rf_track *ended, int cap_ended, int *ended_counts, const rf_face_gate *gate, rf_face_quality *quality,
+                              void *d_shots, void *shots, rf_shot *shot_info) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        if (h->eng->num_devices() > 1) throw rf::Unsupported("face tracks are not available on a multi-device handle");
+        rf::TrackRequest rq;
+        track_request(h, tracker, stream_of_image, tags, ended, cap_ended, ended_counts, &rq);
+        rf::ShotRequest sq;
+        shot_request(gate, quality, d_shots, shots, shot_info, &sq);
+        bool tr = false, cut = false;
+        h->eng->detect_track_shots(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, rq, sq, &cut);
+        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        if (cut) { h->error = kTrackCut; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+}  // namespace
+
+int rf_tracker_enable_shots(rf_tracker tracker, const rf_face_batch_spec *spec) {
+    if (!tracker) return RF_ERR_INVALID_ARG;
+    rf_engine *h = tracker->h;
+    return guarded(h, [&]() -> int {
+        if (h->eng->num_devices() > 1) throw rf::Unsupported("face tracks are not available on a multi-device handle");
+        rf::FaceBatchSpec sp;
+        if (const char *bad = rf::face_batch_resolve(spec, h->eng->default_max_faces(), &sp)) throw rf::ArgError(bad);
+        h->eng->tracker_enable_shots(tracker->impl, sp);
+        return RF_OK;
+    });
+}
+
+int rf_tracker_read_shots(rf_tracker tracker, int stream, void *shots, rf_shot *shot_info, int cap) {
+    if (!tracker) return RF_ERR_INVALID_ARG;
+    return guarded(tracker->h, [&]() -> int { return tracker->h->eng->tracker_read_shots(tracker->impl, stream, (uint8_t *)shots, shot_info, cap); });
+}
+
+int rf_tracker_flush_shots(rf_tracker tracker, int stream, rf_track *ended, int cap, int64_t *frames, int64_t *next_id, void *shots,
+                           rf_shot *shot_info) {
+    if (!tracker) return RF_ERR_INVALID_ARG;
+    return guarded(tracker->h, [&]() -> int {
+        return tracker->h->eng->tracker_flush_shots(tracker->impl, stream, ended, cap, frames, next_id, (uint8_t *)shots, shot_info);
+    });
+}
+
+int rf_track_shots_device(rf_handle h, rf_tracker tracker, const void *const *d_bgr, const int *rows, const int *cols, const int *steps,
+                          int n, const int *stream_of_image, const rf_face *faces, int cap_per_image, const int *counts,
+                          const float *coord_scale, const rf_face_quality *quality, rf_track_tag *tags, rf_track *ended, int cap_ended,
+                          int *ended_counts, void *d_shots, void *shots, rf_shot *shot_info) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        if (h->eng->num_devices() > 1) throw rf::Unsupported("face tracks are not available on a multi-device handle");
+        rf::TrackRequest rq;
+        track_request(h, tracker, stream_of_image, tags, ended, cap_ended, ended_counts, &rq);
+        rf::ShotRequest sq;
+        shot_request(nullptr, nullptr, d_shots, shots, shot_info, &sq);
+        bool cut = false;
+        h->eng->track_shots(rq, sq, d_bgr, rows, cols, steps, n, faces, cap_per_image, counts, coord_scale, quality, &cut);
+        if (cut) { h->error = kTrackCut; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+
+int rf_shot_last_launch_ms(rf_handle h, float *ms) {
+    if (!h || !ms) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        const float v = h->eng->shot_last_launch_ms();
+        if (v < 0.f) throw rf::ArgError("no rf_track_shots_device call has been timed on this handle");
+        *ms = v;
+        return RF_OK;
+    });
+}
+
+int rf_detect_track_shots_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                       float threshold, rf_face *out, int cap_per_image, int *counts, rf_tracker tracker,
+                                       const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_counts,
+                                       const rf_face_gate *gate, rf_face_quality *quality, void *d_shots, void *shots, rf_shot *shot_info) {
+    return detect_track_shots_common(h, (const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, out, cap_per_image, counts, tracker,
+                                     stream_of_image, tags, ended, cap_ended, ended_counts, gate, quality, d_shots, shots, shot_info);
+}
+
+int rf_detect_track_shots_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                                float threshold, rf_face *out, int cap_per_image, int *counts, rf_tracker tracker,
+                                const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_counts,
+                                const rf_face_gate *gate, rf_face_quality *quality, void *d_shots, void *shots, rf_shot *shot_info) {
+    return detect_track_shots_common(h, bgr, rows, cols, steps, n, false, threshold, out, cap_per_image, counts, tracker, stream_of_image, tags,
+                                     ended, cap_ended, ended_counts, gate, quality, d_shots, shots, shot_info);
+}
+
 // ---- face redaction (redact.h)
 int rf_redact_region(const rf_redact_spec *spec, const rf_face *face, float coord_scale, int rows, int cols, int out[9]) {
     rf::RedactSpec sp;

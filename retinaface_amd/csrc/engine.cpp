@@ -210,9 +210,10 @@ public:
         for (DeviceScratch *b : {&align_crops_, &align_mats_, &align_tab_, &fb_state_, &fq_records_, &fq_packed_, &fq_offsets_, &tile_cand_, &tile_count_, &tile_out_,
                                  &tile_outcount_, &tile_tab_, &tile_frames_, &tta_cand_, &tta_count_, &tta_frames_, &tta_mirror_, &pyr_frames_, &pyr_zoom_,
                                  &red_regions_, &red_counts_, &red_cells_, &red_frames_}) b->release();
-        for (HostScratch *b : {&trk_tags_, &trk_ended_, &trk_counts_, &tta_out_, &tta_votes_, &tta_outcount_}) b->release();
-        for (auto &t : trackers_) t->state.release();
+        for (HostScratch *b : {&trk_tags_, &trk_ended_, &trk_counts_, &tta_out_, &tta_votes_, &tta_outcount_, &shot_out_, &shot_info_}) b->release();
+        for (auto &t : trackers_) t->release();
         for (hipEvent_t e : trk_ev_) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : shot_ev_) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : red_ev_) if (e) (void)hipEventDestroy(e);
         if (tta_mirror_done_) (void)hipEventDestroy(tta_mirror_done_);
         if (pyr_zoom_done_) (void)hipEventDestroy(pyr_zoom_done_);
@@ -1236,7 +1237,7 @@ public:
         std::unique_ptr<Tracker> t(new Tracker);
         t->spec = spec; t->n_streams = n_streams;
         t->state.reserve((size_t)n_streams * t->stream_bytes());
-        try { tracker_reset_impl(*t, -1); } catch (...) { t->state.release(); throw; }
+        try { tracker_reset_impl(*t, -1); } catch (...) { t->release(); throw; }
         trackers_.push_back(std::move(t));
         return trackers_.back().get();
     }
@@ -1244,7 +1245,7 @@ public:
         for (size_t i = 0; i < trackers_.size(); i++)
             if (trackers_[i].get() == p) {
                 DeviceGuard guard(device_);
-                trackers_[i]->state.release();
+                trackers_[i]->release();
                 trackers_.erase(trackers_.begin() + i);
                 return;
             }
@@ -1381,6 +1382,263 @@ public:
         track_copy_out(t, rq, n, cap_per_image, counts, cut);
     }
 
+    // -------------------------------------------------------------------------------- best-shot gallery
+private:
+    struct Tracker;
+public:
+    void tracker_enable_shots(void *p, const FaceBatchSpec &spec) override {
+        Tracker &t = tracker_of(p);
+        FaceBatchRequest probe;
+        probe.spec = spec;
+        check_face_batch_request(probe);
+        if (t.dirty) throw ArgError("the tracker's last call failed: reset it first");
+        if (t.has_shots) throw ArgError("the tracker has a shot gallery already");
+        const size_t entries = (size_t)t.n_streams * t.spec.max_tracks;
+        if (entries * spec.bytes_per_face() > (size_t)RF_SHOT_MAX_BYTES) throw ArgError("shot gallery: more than RF_SHOT_MAX_BYTES");
+        DeviceGuard guard(device_);
+        std::vector<TrackHeader> hd((size_t)t.n_streams);
+        RF_HIP(hipMemcpy2D(hd.data(), sizeof(TrackHeader), t.state.ptr, t.stream_bytes(), sizeof(TrackHeader), (size_t)t.n_streams, hipMemcpyDeviceToHost));
+        for (const TrackHeader &h : hd)
+            if (h.frames != 0) throw ArgError("shot gallery: the tracker has stepped a frame already");
+        try {
+            t.gallery.reserve(entries * spec.bytes_per_face());
+            RF_HIP(hipMemset(t.shot_records.reserve(entries * sizeof(rf_shot)), 0, entries * sizeof(rf_shot)));
+            RF_HIP(hipDeviceSynchronize());
+        } catch (...) { t.gallery.release(); t.shot_records.release(); throw; }
+        t.shot_spec = spec;
+        t.has_shots = true;
+    }
+
+    // a stream's table and shot records on the host
+    void shot_read_state(Tracker &t, int stream, std::vector<uint8_t> *img, std::vector<rf_shot> *rec) {
+        const int T = t.spec.max_tracks;
+        img->resize(t.stream_bytes());
+        rec->resize((size_t)T);
+        RF_HIP(hipMemcpy(img->data(), t.state.ptr + (size_t)stream * t.stream_bytes(), img->size(), hipMemcpyDeviceToHost));
+        RF_HIP(hipMemcpy(rec->data(), t.shot_records.ptr + (size_t)stream * T * sizeof(rf_shot), (size_t)T * sizeof(rf_shot), hipMemcpyDeviceToHost));
+    }
+    // the shot of slot `slot` of a stream to the host: zeros unless the slot's track has a best shot and the record is that shot's
+    void shot_fetch(Tracker &t, int stream, int slot, const rf_track &tr, const rf_shot &rec, uint8_t *shot, rf_shot *info) {
+        const size_t bpf = t.shot_spec.bytes_per_face();
+        const bool ok = tr.id != 0 && tr.best_frame >= 0 && shot_record_is(&rec, tr.id, tr.best_frame);
+        if (info) { if (ok) *info = rec; else memset((void *)info, 0, sizeof(rf_shot)); }
+        if (!shot) return;
+        if (ok) RF_HIP(hipMemcpy(shot, t.gallery.ptr + ((size_t)stream * t.spec.max_tracks + slot) * bpf, bpf, hipMemcpyDeviceToHost));
+        else memset(shot, 0, bpf);
+    }
+    Tracker &shot_tracker(void *p, int stream) {
+        Tracker &t = tracker_of(p);
+        if (!t.has_shots) throw ArgError("the tracker has no shot gallery (rf_tracker_enable_shots)");
+        if (stream < 0 || stream >= t.n_streams) throw ArgError("stream out of range");
+        if (t.dirty) throw ArgError("the tracker's last call failed: reset it first");
+        return t;
+    }
+
+    int tracker_read_shots(void *p, int stream, uint8_t *shots, rf_shot *info, int cap) override {
+        Tracker &t = shot_tracker(p, stream);
+        if (cap < 0) throw ArgError("cap is negative");
+        const int T = t.spec.max_tracks, m = std::min(cap, T);
+        if (m == 0 || (!shots && !info)) return T;
+        DeviceGuard guard(device_);
+        std::vector<uint8_t> img;
+        std::vector<rf_shot> rec;
+        shot_read_state(t, stream, &img, &rec);
+        const rf_track *tr = (const rf_track *)(img.data() + sizeof(TrackHeader));
+        const size_t bpf = t.shot_spec.bytes_per_face();
+        for (int s = 0; s < m; s++) shot_fetch(t, stream, s, tr[s], rec[s], shots ? shots + (size_t)s * bpf : nullptr, info ? info + s : nullptr);
+        return T;
+    }
+
+    int tracker_flush_shots(void *p, int stream, rf_track *ended, int cap, int64_t *frames, int64_t *next_id, uint8_t *shots, rf_shot *info) override {
+        Tracker &t = shot_tracker(p, stream);
+        if (cap < 0 || (cap > 0 && !ended)) throw ArgError("table is null");
+        DeviceGuard guard(device_);
+        std::vector<uint8_t> img;
+        std::vector<rf_shot> rec;
+        shot_read_state(t, stream, &img, &rec);
+        const rf_track *tr = (const rf_track *)(img.data() + sizeof(TrackHeader));
+        const size_t bpf = t.shot_spec.bytes_per_face();
+        int e = 0;
+        for (int s = 0; s < t.spec.max_tracks; s++) {                  // the order of tracker_read(flush): slot ascending
+            if (tr[s].id == 0) continue;
+            if (e < cap) shot_fetch(t, stream, s, tr[s], rec[s], shots ? shots + (size_t)e * bpf : nullptr, info ? info + e : nullptr);
+            e++;
+        }
+        const int count = tracker_read(p, stream, ended, cap, frames, next_id, true);
+        const size_t rb = (size_t)t.spec.max_tracks * sizeof(rf_shot);
+        RF_HIP(hipMemset(t.shot_records.ptr + (size_t)stream * rb, 0, rb));
+        RF_HIP(hipDeviceSynchronize());
+        return count;
+    }
+
+    // the arguments of a shot call, checked before any state changes; opens the call-level blocks
+    void shot_check(const Tracker &t, const ShotRequest &sq, int n, int cap_ended) {
+        if (sq.d_shots && ((uintptr_t)sq.d_shots & (uintptr_t)(t.shot_spec.elem_bytes() - 1))) throw ArgError("d_shots is not aligned to its element size");
+        if ((sq.d_shots || sq.shots) && (size_t)std::max(n, 0) * std::max(cap_ended, 0) * t.shot_spec.bytes_per_face() > (size_t)RF_SHOT_MAX_BYTES)
+            throw ArgError("n x cap_ended shots: more than RF_SHOT_MAX_BYTES");
+    }
+    void shot_open_call(const Tracker &t, const ShotRequest &sq, int n, int cap_ended) {
+        const size_t slots = (size_t)std::max(n, 1) * std::max(cap_ended, 1);
+        shot_.d_out = sq.d_shots;
+        shot_.host = sq.shots != nullptr; shot_.info = sq.info != nullptr;
+        if (shot_.host) shot_out_.reserve(slots * t.shot_spec.bytes_per_face());
+        if (shot_.info) shot_info_.reserve(slots * sizeof(rf_shot));
+        shot_.last_streams = 0;
+    }
+    // The two shot launches behind a track launch on stream st (what is common to both is in sp): deliver to the caller's device block
+    // and / or the pinned call-level block the kernel writes straight into, then keep.
+    void shot_launches(hipStream_t st, ShotParams sp) {
+        const Tracker &t = *trk_.tr;
+        sp.max_tracks = t.spec.max_tracks;
+        sp.state = t.state.ptr;
+        sp.tags = (const rf_track_tag *)trk_tags_.ptr; sp.tag_stride = trk_.tag_stride;
+        sp.ended = (const rf_track *)trk_ended_.ptr; sp.cap_ended = trk_.cap_ended;
+        sp.ended_counts = (const int *)trk_counts_.ptr;
+        sp.spec = t.shot_spec;
+        sp.max_faces = trk_.max_faces;
+        sp.gallery = t.gallery.ptr; sp.records = (rf_shot *)t.shot_records.ptr;
+        sp.out_info = shot_.info ? (rf_shot *)shot_info_.ptr : nullptr;
+        if (shot_.host || !shot_.d_out) {
+            sp.out = shot_.host ? shot_out_.ptr : nullptr;
+            launch_shot_deliver(st, sp);
+            sp.out_info = nullptr;
+        }
+        if (shot_.d_out) {
+            sp.out = shot_.d_out;
+            launch_shot_deliver(st, sp);
+        }
+        launch_shot_keep(st, sp);
+        RF_HIP(hipGetLastError());
+    }
+    // the delivered shots of a finished call, from the pinned blocks the deliver kernel wrote, to the caller's host buffers
+    void shot_copy_out(const Tracker &t, const TrackRequest &rq, const ShotRequest &sq, int n) {
+        if (!sq.shots && !sq.info) return;
+        const size_t bpf = t.shot_spec.bytes_per_face();
+        const int *cs = (const int *)trk_counts_.ptr;
+        for (int i = 0; i < n; i++) {
+            if (rq.stream_of_image[i] < 0) continue;
+            const size_t have = (size_t)std::max(0, std::min(cs[i], rq.cap_ended)), at = (size_t)i * rq.cap_ended;
+            if (!have) continue;
+            if (sq.shots) memcpy(sq.shots + at * bpf, shot_out_.ptr + at * bpf, have * bpf);
+            if (sq.info) memcpy((void *)(sq.info + at), shot_info_.ptr + at * sizeof(rf_shot), have * sizeof(rf_shot));
+        }
+    }
+
+    void track_shots(const TrackRequest &rq, const ShotRequest &sq, const void *const *frames, const int *rows, const int *cols, const int *steps,
+                     int n, const rf_face *faces, int cap_per_image, const int *counts, const float *coord_scale, const rf_face_quality *quality,
+                     bool *cut) override {
+        *cut = false;
+        if (n < 0 || (n > 0 && (!frames || !rows || !cols || !faces || !counts))) throw ArgError("null argument");
+        if (cap_per_image < 1) throw ArgError("cap_per_image must be >= 1");
+        for (int i = 0; i < n; i++)
+            if (counts[i] < 0) throw ArgError("negative face count");
+        Tracker &t = track_check(rq, n, true);
+        shot_check(t, sq, n, rq.cap_ended);
+        const int max_faces = t.shot_spec.max_faces;
+        const int fpi = std::min(std::min(cap_per_image, max_faces), kTrackMaxFaces);      // records per image that travel to the device
+        const int mq = std::min(max_faces, kTrackMaxFaces);                                 // quality records per image that do
+        // one table: streams | images | counts | stream entry of each image | frames | quality records | faces (60-byte records)
+        const size_t o_img = align256((size_t)n * sizeof(TrackStreamEntry)), o_cnt = o_img + align256((size_t)n * sizeof(TrackImageEntry)),
+                     o_ent = o_cnt + align256((size_t)n * sizeof(int)), o_fd = o_ent + align256((size_t)n * sizeof(int32_t)),
+                     o_q = o_fd + align256((size_t)n * sizeof(FrameDesc)), o_face = o_q + align256(quality ? (size_t)n * mq * sizeof(rf_face_quality) : 0),
+                     total = o_face + (size_t)n * fpi * sizeof(rf_face);
+        std::vector<uint8_t> tab(total, 0);
+        int *cnt = (int *)(tab.data() + o_cnt);
+        FrameDesc *fd = (FrameDesc *)(tab.data() + o_fd);
+        std::vector<float> scale((size_t)n);
+        std::vector<char> empty((size_t)n, 0);
+        for (int i = 0; i < n; i++) {
+            const int st = steps ? steps[i] : cols[i] * 3;
+            const uint8_t *p = (const uint8_t *)frames[i];
+            check_frame(p, rows[i], cols[i], st);
+            empty[i] = !p || rows[i] <= 0 || cols[i] <= 0;
+            if (!empty[i] && check_residency_) {
+                const int where = foreign_device_of(p);
+                if (where >= 0 && where != device_) throw ArgError("shots: frame is resident on another device");
+            }
+            fd[i] = empty[i] ? FrameDesc{nullptr, 0, 0, 0, 0} : FrameDesc{p, rows[i], cols[i], st, 0};
+            cnt[i] = empty[i] ? 0 : counts[i];      // the true count: the kernel clamps it, and tags the faces beyond the clamp; a frame
+            scale[i] = coord_scale ? coord_scale[i] : 1.f;      // without pixels has no faces
+            const int c = std::min(cnt[i], fpi);
+            if (c) memcpy(tab.data() + o_face + (size_t)i * fpi * sizeof(rf_face), faces + (size_t)i * cap_per_image, (size_t)c * sizeof(rf_face));
+            if (quality && c) memcpy(tab.data() + o_q + (size_t)i * mq * sizeof(rf_face_quality), quality + (size_t)i * max_faces,
+                                     (size_t)std::min(c, mq) * sizeof(rf_face_quality));
+        }
+        if (n == 0) return;
+        DeviceGuard guard(device_);
+        TrackStreamEntry *se = (TrackStreamEntry *)tab.data();
+        const int ns = track_build_table(rq.stream_of_image, 0, n, scale.data(), empty.data(), se, (TrackImageEntry *)(tab.data() + o_img));
+        int32_t *ent = (int32_t *)(tab.data() + o_ent);
+        int n_img = 0;
+        for (int z = 0; z < ns; z++)
+            for (int j = 0; j < se[z].n; j++) ent[n_img++] = z;
+        uint8_t *d_tab = align_tab_.reserve(total);
+        track_open_call(t, rq, n, cap_per_image);
+        shot_open_call(t, sq, n, rq.cap_ended);
+        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+        t.dirty = true;
+        RF_HIP(hipMemcpyAsync(d_tab, tab.data(), total, hipMemcpyHostToDevice, align_stream_));
+        TrackParams tp = track_params(t);
+        tp.streams = (const TrackStreamEntry *)d_tab; tp.n_streams = ns;
+        tp.images = (const TrackImageEntry *)(d_tab + o_img);
+        tp.faces = d_tab + o_face; tp.face_stride = (int)sizeof(rf_face); tp.faces_per_image = fpi;
+        tp.counts = (const int *)(d_tab + o_cnt);
+        tp.records = quality ? (const rf_face_quality *)(d_tab + o_q) : nullptr;
+        tp.max_faces = mq;
+        trk_.max_faces = mq;
+        launch_track(align_stream_, tp);
+        RF_HIP(hipGetLastError());
+        ShotParams sp;
+        memset((void *)&sp, 0, sizeof(sp));
+        sp.streams = tp.streams; sp.n_streams = ns;
+        sp.images = tp.images; sp.n_images = n_img;
+        sp.entry_of = (const int32_t *)(d_tab + o_ent);
+        sp.frames = (const FrameDesc *)(d_tab + o_fd);
+        sp.faces = tp.faces; sp.face_stride = tp.face_stride; sp.faces_per_image = fpi;
+        sp.counts = tp.counts;
+        if (!shot_ev_[0]) { RF_HIP(hipEventCreate(&shot_ev_[0])); RF_HIP(hipEventCreate(&shot_ev_[1])); }
+        RF_HIP(hipEventRecord(shot_ev_[0], align_stream_));
+        if (ns > 0) shot_launches(align_stream_, sp);
+        RF_HIP(hipEventRecord(shot_ev_[1], align_stream_));
+        RF_HIP(hipStreamSynchronize(align_stream_));
+        if (hipEventElapsedTime(&shot_launch_ms_, shot_ev_[0], shot_ev_[1]) != hipSuccess) shot_launch_ms_ = -1.f;
+        track_copy_out(t, rq, n, cap_per_image, cnt, cut);
+        shot_copy_out(t, rq, sq, n);
+    }
+    float shot_last_launch_ms() const override { return shot_launch_ms_; }
+
+    void detect_track_shots(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device, float threshold,
+                            rf_face *out, int cap_per_image, int *counts, bool *truncated, const TrackRequest &rq, const ShotRequest &sq,
+                            bool *cut) override {
+        *cut = false;
+        if (n < 0 || (n > 0 && (!frames || !rows || !cols || !counts))) throw ArgError("null argument");
+        if (cap_per_image < 0 || (cap_per_image > 0 && !out)) throw ArgError("out is null");
+        Tracker &t = track_check(rq, n, true);
+        shot_check(t, sq, n, rq.cap_ended);
+        FaceBatchRequest fb;                          // the quality launch of the gated face-batch path, for the gallery spec, no tensor
+        fb.spec = t.shot_spec;
+        fb.spec.capacity = std::max(1, n) * fb.spec.max_faces;
+        fb.gated = sq.gated; fb.has_gate = sq.has_gate; fb.gate = sq.gate; fb.quality = sq.quality;
+        if ((long)n * fb.spec.max_faces > (1L << 24)) throw ArgError("n x max_faces: more than 2^24 faces in one call");
+        DeviceGuard guard(device_);
+        launch_pending();
+        track_open_call(t, rq, n, cap_per_image, true);
+        shot_open_call(t, sq, n, rq.cap_ended);
+        if (fb.gated) face_gate_open(fb, n);
+        trk_.records = fb.gated ? (const rf_face_quality *)fq_records_.ptr : nullptr;
+        trk_.max_faces = fb.spec.max_faces;
+        t.dirty = true;
+        trk_.on = n > 0; shot_.on = n > 0;
+        struct Off { bool &a, &b; ~Off() { a = false; b = false; } } off{trk_.on, shot_.on};
+        if (fb.gated) {
+            bool overflow = false;
+            detect_face_batch(frames, rows, cols, steps, n, on_device, threshold, out, cap_per_image, counts, truncated, fb, &overflow);
+        } else detect(frames, rows, cols, steps, n, on_device, threshold, out, cap_per_image, counts, truncated);
+        trk_.on = false; shot_.on = false;
+        // every launch of the call has been waited for (its `done` event follows the keep launch)
+        track_copy_out(t, rq, n, cap_per_image, counts, cut);
+        shot_copy_out(t, rq, sq, n);
+    }
 
     // -------------------------------------------------------------------------------- face redaction
     // The arguments of a redacting call, checked before any state changes: the tracker and its streams (each at most once per call:
@@ -1394,8 +1652,7 @@ public:
             throw ArgError("n x max_regions x cells^2: more than 2^28 cells in one call");
         auto *t = rq.tracker ? &tracker_of(rq.tracker) : nullptr;
         if (t) {
-            if (t->dirty) throw ArgError("the tracker's last call failed: reset it first");
-            if (n > 0 && !rq.stream_of_image) throw ArgError("stream_of_image is null");
+            if (t->dirty) throw ArgError("the tracker's last call failed: reset it first");            if (n > 0 && !rq.stream_of_image) throw ArgError("stream_of_image is null");
             std::vector<int> seen;
             for (int i = 0; i < n; i++) {
                 const int st = rq.stream_of_image[i];
@@ -1800,6 +2057,8 @@ private:
         hipEvent_t pyr_done = nullptr;        // ... recorded behind the launch's gather, as tile_done
         uint8_t *h_track_tab = nullptr;       // detect_track(): pinned, the launch's stream table and image table (allocated on first use)
         hipEvent_t track_done = nullptr;      // ... recorded behind the launch's track kernel: the call's next track launch (another lane) waits for it
+        int32_t *h_shot_tab = nullptr;        // detect_track_shots(): pinned, per tracked image of the launch its stream entry (allocated on first use)
+        hipEvent_t shot_done = nullptr;       // ... recorded behind the launch's keep kernel: with a gallery the call's next track launch waits for this one
         int *h_red_streams = nullptr;         // detect_track_redact(): pinned, per image of the launch its stream (allocated on first use)
         bool busy = false;                    // a launched super-batch whose results have not been harvested yet
         int n_images = 0;                     // images of the super-batch being assembled / in flight on this lane
@@ -1846,6 +2105,7 @@ private:
         if (l.tta_done) (void)hipEventDestroy(l.tta_done);
         if (l.pyr_done) (void)hipEventDestroy(l.pyr_done);
         if (l.track_done) (void)hipEventDestroy(l.track_done);
+        if (l.shot_done) (void)hipEventDestroy(l.shot_done);
         if (l.copy2) { (void)hipStreamSynchronize(l.copy2); (void)hipStreamDestroy(l.copy2); }
         if (l.d_stage) (void)hipFree(l.d_stage);
         if (l.h_stage) (void)hipHostFree(l.h_stage);
@@ -2136,6 +2396,7 @@ private:
         if (tta_.on) launch_lane_tta(s, n);
         if (pyr_.on) launch_lane_pyr(s, n);
         if (trk_.on) launch_lane_track(s, n);
+        if (shot_.on) launch_lane_shots(s);
         if (red_.on) launch_lane_redact(s, n);
         RF_HIP(hipEventRecord(s.done, s.stream));
         trace_.add(4, tt);
@@ -2345,6 +2606,7 @@ private:
         TrackImageEntry *ie = (TrackImageEntry *)(se + cap_images_);
         const int ns = track_build_table(trk_.stream_of_image, trk_.next_image, n, scale.data(), empty.data(), se, ie);
         trk_.next_image += n;
+        shot_.last_streams = ns;
         if (ns == 0) return;
         if (trk_.prev && trk_.prev != s.track_done) RF_HIP(hipStreamWaitEvent(s.stream, trk_.prev, 0));
         TrackParams tp = track_params(*trk_.tr);
@@ -2358,6 +2620,38 @@ private:
         RF_HIP(hipGetLastError());
         RF_HIP(hipEventRecord(s.track_done, s.stream));
         trk_.prev = s.track_done;
+    }
+
+    // The shot launches of a super-batch of detect_track_shots(), behind its track launch: the tables launch_lane_track() has just
+    // filled, frames from the launch's own frame table (the first half: full-resolution frames), faces and counts from the pinned
+    // result block.  The keep launch reads the table the NEXT track launch of the call rewrites, and that launch's deliver reads the
+    // entries this keep writes, so with a gallery the chain runs through the event recorded here: the call's next track launch waits
+    // for this keep launch, not only for the track launch in front of it.  The lane's `done` event follows.  No host wait anywhere.
+    void launch_lane_shots(Lane &s) {
+        const int ns = shot_.last_streams;
+        if (ns == 0) return;                          // no tracked image in this launch: launch_lane_track() launched nothing either
+        if (!s.h_shot_tab) {
+            void *p = nullptr;
+            RF_HIP(hipHostMalloc(&p, std::max<size_t>((size_t)cap_images_ * sizeof(int32_t), 256), hipHostMallocDefault));
+            s.host_allocs.push_back(p);
+            s.h_shot_tab = (int32_t *)p;
+            RF_HIP(hipEventCreateWithFlags(&s.shot_done, hipEventDisableTiming));
+        }
+        const TrackStreamEntry *se = (const TrackStreamEntry *)s.h_track_tab;
+        int n_img = 0;
+        for (int z = 0; z < ns; z++)
+            for (int j = 0; j < se[z].n && n_img < cap_images_; j++) s.h_shot_tab[n_img++] = z;
+        ShotParams sp;
+        memset((void *)&sp, 0, sizeof(sp));
+        sp.streams = se; sp.n_streams = ns;
+        sp.images = (const TrackImageEntry *)(se + cap_images_); sp.n_images = n_img;
+        sp.entry_of = s.h_shot_tab;
+        sp.frames = s.d_frames;
+        sp.faces = (const uint8_t *)s.h_out; sp.face_stride = (int)sizeof(Candidate); sp.faces_per_image = opt_.max_detections;
+        sp.counts = s.h_counts;
+        shot_launches(s.stream, sp);
+        RF_HIP(hipEventRecord(s.shot_done, s.stream));
+        trk_.prev = s.shot_done;
     }
 
     // The redaction launches of a super-batch of detect_redact() / detect_track_redact(): frames from the launch's own frame table (the
@@ -2408,7 +2702,6 @@ private:
         return ns;
     }
 
-    struct Tracker;
     Tracker &tracker_of(void *p) {
         for (auto &t : trackers_)
             if (t.get() == p) return *t;
@@ -2421,11 +2714,18 @@ private:
         std::vector<uint8_t> img((size_t)count * sb, 0);
         for (int i = 0; i < count; i++) *(TrackHeader *)(img.data() + (size_t)i * sb) = TrackHeader{0, 1};
         RF_HIP(hipMemcpy(t.state.ptr + (size_t)first * sb, img.data(), img.size(), hipMemcpyHostToDevice));
+        if (t.has_shots) {
+            const size_t rb = (size_t)t.spec.max_tracks * sizeof(rf_shot);
+            RF_HIP(hipMemset(t.shot_records.ptr + (size_t)first * rb, 0, (size_t)count * rb));
+            RF_HIP(hipDeviceSynchronize());
+        }
     }
     // the arguments of a tracked call, checked before any state changes
-    Tracker &track_check(const TrackRequest &rq, int n) {
+    Tracker &track_check(const TrackRequest &rq, int n, bool shots = false) {
         Tracker &t = tracker_of(rq.tracker);
         if (t.dirty) throw ArgError("the tracker's last call failed: reset it first");
+        if (t.has_shots && !shots) throw ArgError("the tracker has a shot gallery: use the shot calls, this one would leave it stale");
+        if (!t.has_shots && shots) throw ArgError("the tracker has no shot gallery (rf_tracker_enable_shots)");
         if (n > 0 && !rq.stream_of_image) throw ArgError("stream_of_image is null");
         if (rq.cap_ended < 0 || (rq.cap_ended > 0 && !rq.ended)) throw ArgError("ended is null");
         if ((long)n * std::max(rq.cap_ended, 1) > (1L << 24)) throw ArgError("n x cap_ended: more than 2^24 records in one call");
@@ -2434,11 +2734,12 @@ private:
         return t;
     }
     // call-level result blocks (pinned host memory): tags (tag_stride per image), ended lists, ended counts | status
-    void track_open_call(Tracker &t, const TrackRequest &rq, int n, int cap_per_image) {
+    // (full_tags: the shot kernels find faces by their tags, so every face the step looks at gets one whatever the caller's cap is)
+    void track_open_call(Tracker &t, const TrackRequest &rq, int n, int cap_per_image, bool full_tags = false) {
         trk_.tr = &t;
         trk_.stream_of_image = rq.stream_of_image;
         trk_.n = n; trk_.next_image = 0; trk_.prev = nullptr;
-        trk_.tag_stride = std::max(0, std::min(cap_per_image, kTrackMaxFaces));
+        trk_.tag_stride = full_tags ? kTrackMaxFaces : std::max(0, std::min(cap_per_image, kTrackMaxFaces));
         trk_.cap_ended = rq.cap_ended;
         trk_tags_.reserve((size_t)std::max(n, 1) * std::max(trk_.tag_stride, 1) * sizeof(rf_track_tag));
         trk_ended_.reserve((size_t)std::max(n, 1) * std::max(rq.cap_ended, 1) * sizeof(rf_track));
@@ -2762,7 +3063,13 @@ private:
         int n_streams = 0;
         DeviceScratch state;                  // n_streams x (TrackHeader + max_tracks records)
         bool dirty = false;                   // a call on it ended in an error: refused until it is reset
+        // the best-shot gallery (shot.h), fixed by tracker_enable_shots(): n_streams x max_tracks entries of the resolved spec's
+        // bytes_per_face, and as many rf_shot records
+        bool has_shots = false;
+        FaceBatchSpec shot_spec;
+        DeviceScratch gallery, shot_records;
         size_t stream_bytes() const { return sizeof(TrackHeader) + (size_t)spec.max_tracks * sizeof(rf_track); }
+        void release() { state.release(); gallery.release(); shot_records.release(); }
     };
     std::vector<std::unique_ptr<Tracker>> trackers_;
     // (pinned host memory the kernel writes straight into, as the NMS kernel writes its result block: no copy after the call)
@@ -2781,6 +3088,12 @@ private:
         void release() { if (ptr) (void)hipHostFree(ptr); ptr = nullptr; cap = 0; }
     };
     HostScratch trk_tags_, trk_ended_, trk_counts_;
+    // best-shot gallery: the call-level blocks the deliver kernel writes (shots, records; indexed image * cap_ended + e), the events
+    // around the shot launches of track_shots() (tools/shot_bench.py reads the time) and the request a shot call has open
+    HostScratch shot_out_, shot_info_;
+    hipEvent_t shot_ev_[2] = {nullptr, nullptr};
+    float shot_launch_ms_ = -1.f;
+    struct { bool on = false; uint8_t *d_out = nullptr; bool host = false, info = false; int last_streams = 0; } shot_;
     HostScratch tta_out_, tta_votes_, tta_outcount_;      // detect_tta() / tta_merge(): what the voting merge writes (see tta_open)
     hipEvent_t trk_ev_[2] = {nullptr, nullptr};   // around the track launch of track_update() (tools/track_bench.py reads the time)
     float trk_launch_ms_ = -1.f;

@@ -129,6 +129,16 @@ struct TrackRequest {
     int *ended_counts = nullptr;                // n
 };
 
+// The gallery half of a shot call (shot.h; rf_track_shots_device / rf_detect_track_shots_batch*): where the delivered shots (n * cap_ended
+// faces of the gallery spec, device and / or host) and their records go; for the fused call the gate and the quality records
+struct ShotRequest {
+    uint8_t *d_shots = nullptr, *shots = nullptr;
+    rf_shot *info = nullptr;
+    bool gated = false, has_gate = false;       // gated: a gate or a quality buffer was given, the best shot goes by sharpness
+    FaceGate gate;
+    rf_face_quality *quality = nullptr;         // host, n * max_faces records (the gallery spec's max_faces), or nullptr
+};
+
 // A redacting call (redact.h; rf_redact_device / rf_detect_redact_batch* / rf_detect_track_redact_batch_device): the validated spec,
 // the tracker whose coasting tracks are redacted too (nullptr = none) with the stream of every image, and where the per-region pixel
 // counts (n * spec.max_regions) and the true region counts (n) go (host; each may be nullptr)
@@ -253,6 +263,30 @@ public:
                                          int *, bool *, const FaceBatchRequest &, bool * /*overflow*/, const TrackRequest &, bool * /*cut*/) {
         throw Unsupported("face tracks are not available on a multi-device handle");
     }
+    // Best-shot gallery (shot.h): a tracker may own n_streams x max_tracks face-batch crops and shot records in device memory; the two
+    // shot launches follow each track launch on its stream and join the chain the track launches form.  Single-device engines only.
+    virtual void tracker_enable_shots(void *, const FaceBatchSpec &) { throw Unsupported("face tracks are not available on a multi-device handle"); }
+    // host copy of a stream's entries and records (zeros where the slot holds no shot); returns max_tracks
+    virtual int tracker_read_shots(void *, int /*stream*/, uint8_t *, rf_shot *, int /*cap*/) {
+        throw Unsupported("face tracks are not available on a multi-device handle");
+    }
+    // tracker_read(flush) + the shots of the tracks it ends
+    virtual int tracker_flush_shots(void *, int /*stream*/, rf_track *, int /*cap*/, int64_t *, int64_t *, uint8_t *, rf_shot *) {
+        throw Unsupported("face tracks are not available on a multi-device handle");
+    }
+    // track_update() against device-resident frames + the gallery rules; max_faces is the gallery spec's
+    virtual void track_shots(const TrackRequest &, const ShotRequest &, const void *const *, const int *, const int *, const int *, int /*n*/,
+                             const rf_face *, int /*cap_per_image*/, const int * /*counts*/, const float * /*coord_scale*/,
+                             const rf_face_quality *, bool * /*cut*/) {
+        throw Unsupported("face tracks are not available on a multi-device handle");
+    }
+    // detect_track() + the gallery rules; with rq.gated the quality launch of the gated face-batch path runs for the gallery spec
+    virtual void detect_track_shots(const uint8_t *const *, const int *, const int *, const int *, int, bool, float, rf_face *, int, int *, bool *,
+                                    const TrackRequest &, const ShotRequest &, bool * /*cut*/) {
+        throw Unsupported("face tracks are not available on a multi-device handle");
+    }
+    // hipEvent time of the two shot launches of the most recent track_shots() (negative: none yet)
+    virtual float shot_last_launch_ms() const { return -1.f; }
     // Face redaction, in place in device-resident frames: regions of faces the caller supplies (host memory) and, with a tracker in
     // the request, of its streams' coasting tracks.  *cut: a region list was cut at max_regions.  Single-device engines only.
     virtual void redact(const void *const *, const int *, const int *, const int *, int, const rf_face *, int, const int *, const float *,

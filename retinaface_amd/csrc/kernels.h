@@ -15,6 +15,7 @@
 #include "tile.h"
 #include "tta.h"
 #include "track.h"
+#include "shot.h"
 
 namespace rf {
 
@@ -302,6 +303,31 @@ struct TrackParams {
     int *status;                          // [call images] kTrackOverflow or 0
 };
 void launch_track(hipStream_t s, const TrackParams &p);
+
+// ---- K_l: best-shot gallery (shot.h) -- two launches behind launch_track on its stream, which read tags, ended lists, counts and the
+//      table after the step from where the track kernel has just written them.  launch_shot_deliver: one workgroup per (delivered
+//      shot, band of crop rows) copies the slot's stored entry, or samples the frame of this launch the shot was taken in, into the
+//      call's shot block.  launch_shot_keep: one workgroup per (slot, band) whose final owner is a face of this launch samples that
+//      face into the slot's entry.  Stream order between the two is what makes "deliver the old entry, then keep the new one" safe.
+struct ShotParams {
+    const TrackStreamEntry *streams; int n_streams;      // as TrackParams, the same tables
+    const TrackImageEntry *images; int n_images;         // the tracked images of the launch: the sum of streams[].n
+    const int32_t *entry_of;              // [n_images] index into streams of images[j]'s stream
+    const FrameDesc *frames;              // [launch images] SOURCE frames, indexed by images[j].local
+    const uint8_t *faces;                 // as TrackParams
+    int face_stride, faces_per_image;
+    const int *counts;
+    int max_faces, max_tracks;
+    const uint8_t *state;                 // the tables AFTER the launch's frame steps
+    const rf_track_tag *tags; int tag_stride;
+    const rf_track *ended; int cap_ended;
+    const int *ended_counts;
+    FaceBatchSpec spec;                   // the gallery's
+    uint8_t *gallery; rf_shot *records;   // stream s, slot t: entry (s * max_tracks + t) of bytes_per_face, record likewise
+    uint8_t *out; rf_shot *out_info;      // deliver: call image c, ended entry e at c * cap_ended + e; each may be nullptr
+};
+void launch_shot_deliver(hipStream_t s, const ShotParams &p);
+void launch_shot_keep(hipStream_t s, const ShotParams &p);
 
 // ---- K_k: face redaction (redact.h) -- in place in the frames of a launch, in three launches ordered on the stream.
 //      launch_redact_regions: one workgroup per image turns its faces, and with a tracker its stream's coasting tracks, into region

@@ -4697,6 +4697,247 @@ void launch_track(hipStream_t s, const TrackParams &p) {
 }
 
 // =============================================================================================
+// K_l: best-shot gallery (shot.h).  Two launches behind track_kernel on its stream; both read what it has just written (tags, ended
+//      records, counts, the table after the step) and decide with the pieces of shot.h.
+//      shot_deliver_kernel: one workgroup = one (tracked image of the launch, ended-list entry, band of crop rows).  The source of
+//      the shot is shot_source_kind(): a stored entry -- the workgroup searches the stream's <= 256 shot records for the ended id, one
+//      thread per record (ids are unique per stream, so at most one thread answers; rf_track has no slot field) and copies the band in
+//      16-byte vectors -- or a face of one of this launch's own images, found by the same kind of search over that image's tags and
+//      sampled from its frame, or nothing: zeros.
+//      shot_keep_kernel: one workgroup = one (stream of the launch, slot, band).  It works only when the slot's final owner after the
+//      launch is a face of this launch (shot_owner_ordinal on the table after the step), so every gallery byte is written at most once
+//      per launch and nothing written is overwritten; the stored entries shot_deliver_kernel reads are older than the launch and the
+//      stream orders the two kernels.  Sampling is K_g's: align_estimate, AlignSampler, align_sample / align_sample_aa, face_value, the
+//      band assembled in LDS at the destination's 16-byte phase, face_store_run.  No atomics, nothing spins, nothing outside a frame
+//      is read (the sampler's range test is part of the arithmetic).
+// =============================================================================================
+template <typename E, bool CHW> struct ShotBand {
+    static constexpr int ES = (int)sizeof(E), RUNS = CHW ? 3 : 1;
+    uint8_t *dst[RUNS], *lds[RUNS];
+    size_t off[RUNS];                                            // byte offset of each run inside a face
+    int r0, npix, run_bytes;
+    __device__ ShotBand(uint8_t *face, uint4 *band_buf, int S, int band, int band_rows) {
+        r0 = band * band_rows;
+        const int nrows = S - r0 < band_rows ? S - r0 : band_rows;
+        npix = nrows * S;
+        run_bytes = npix * ES * (CHW ? 1 : 3);
+#pragma unroll
+        for (int r = 0; r < RUNS; r++) {
+            off[r] = CHW ? ((size_t)r * S * S + (size_t)r0 * S) * ES : (size_t)r0 * S * 3 * ES;
+            dst[r] = face + off[r];
+            lds[r] = (uint8_t *)band_buf + r * (kFaceRunBytes + 16) + ((uintptr_t)dst[r] & 15);
+        }
+    }
+    // the band of face `f` (15 floats) of frame fd, as face_batch_kernel fills it
+    template <bool AA>
+    __device__ void sample(const FrameDesc &fd, const AlignShared<AA> &xf, const FaceBatchSpec &spec) const {
+#pragma clang fp contract(off)
+        const int S = spec.crop, flip = spec.rgb ? 2 : 0;
+        const AlignSampler sm(xf, fd);
+        const int aak = align_shared_factor<AA>(xf);
+        for (int p = threadIdx.x; p < npix; p += kThreads) {
+            unsigned acc[3];
+            if (AA) align_sample_aa(fd, sm, aak, p % S, r0 + p / S, acc);
+            else align_sample(fd, sm, p % S, r0 + p / S, acc);
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const E val = face_value<E>(acc[flip ? 2 - c : c], spec.mean[c], spec.scale[c]);
+                if (CHW) ((E *)lds[CHW ? c : 0])[p] = val;
+                else ((E *)lds[0])[3 * p + c] = val;
+            }
+        }
+    }
+    // the band of a stored face (src = its first byte), or zeros (src = nullptr)
+    __device__ void load(const uint8_t *src) const {
+#pragma unroll
+        for (int r = 0; r < RUNS; r++) {
+            const int ne = run_bytes / ES;
+            const E *sv = src ? (const E *)(src + off[r]) : nullptr;
+            for (int i = threadIdx.x; i < ne; i += kThreads) ((E *)lds[r])[i] = sv ? sv[i] : (E)0;
+        }
+    }
+    __device__ void store() const {
+#pragma unroll
+        for (int r = 0; r < RUNS; r++) face_store_run<E>(dst[r], lds[r], run_bytes);
+    }
+    // a stored band whose source and destination runs are both whole aligned 16-byte vectors leaves without touching LDS
+    __device__ bool copy_vectors(const uint8_t *src) const {
+        unsigned bits = (unsigned)run_bytes;
+#pragma unroll
+        for (int r = 0; r < RUNS; r++) bits |= (unsigned)((uintptr_t)dst[r] | (uintptr_t)(src + off[r]));
+        if (bits & 15u) return false;
+#pragma unroll
+        for (int r = 0; r < RUNS; r++) {
+            const uint4 *sv = (const uint4 *)(src + off[r]);
+            uint4 *dv = (uint4 *)dst[r];
+            for (int i = threadIdx.x; i < run_bytes / 16; i += kThreads) dv[i] = sv[i];
+        }
+        return true;
+    }
+};
+
+// thread 0: the transform of face k of launch image `local` into LDS (the caller synchronises)
+template <bool AA>
+__device__ __forceinline__ void shot_estimate(const ShotParams &a, int local, int k, float scale, AlignShared<AA> *xf) {
+#pragma clang fp contract(off)
+    const float *f = (const float *)(a.faces + ((size_t)local * a.faces_per_image + k) * a.face_stride);
+    float px[5], py[5];
+    for (int i = 0; i < 5; i++) { px[i] = f[5 + i]; py[i] = f[10 + i]; }
+    align_estimate(px, py, scale, a.spec.crop, xf);
+    align_shared_set_factor<AA>(*xf, a.spec.aa_max);
+}
+
+// The face of image entry `im` whose tag says it is the best shot of track `id`: one thread per tag, at most one answers.  Every thread
+// of the workgroup calls it; *s_hit must be -1 and visible on entry; the answer is *s_hit after the barrier inside.
+__device__ __forceinline__ void shot_find_face(const ShotParams &a, const TrackImageEntry &im, long long id, int *s_hit) {
+    int m = shot_tagged(im.empty ? 0 : a.counts[im.local], a.faces_per_image, a.max_faces);
+    m = m < a.tag_stride ? m : a.tag_stride;
+    const int k = (int)threadIdx.x;
+    if (k < m && shot_tag_is(a.tags + (size_t)im.image * a.tag_stride + k, id)) *s_hit = k;
+    __syncthreads();
+}
+
+template <typename E, bool CHW, bool AA>
+__global__ __launch_bounds__(kThreads) void shot_deliver_kernel(ShotParams a, int band_rows) {
+#pragma clang fp contract(off)
+    __shared__ AlignShared<AA> xf;
+    __shared__ uint4 band_buf[kFaceLdsVecs];
+    __shared__ int s_hit;
+    const int j = blockIdx.x, e = blockIdx.y, band = blockIdx.z;
+    const TrackImageEntry im = a.images[j];
+    int ne = a.ended_counts[im.image];
+    ne = ne < a.cap_ended ? ne : a.cap_ended;
+    if (e >= ne) return;
+    const TrackStreamEntry se = a.streams[a.entry_of[j]];
+    const int T = a.max_tracks, S = a.spec.crop;
+    const size_t idx = (size_t)im.image * a.cap_ended + e, bpf = (size_t)3 * S * S * sizeof(E);
+    const rf_track *t = a.ended + idx;
+    const long long id = t->id, bf = t->best_frame;
+    const TrackHeader *hdr = (const TrackHeader *)(a.state + (size_t)se.stream * (sizeof(TrackHeader) + (size_t)T * sizeof(rf_track)));
+    const long long f0 = shot_first_frame(hdr->frames, se.n);
+    int kind = shot_source_kind(bf, f0);
+    if (threadIdx.x == 0) s_hit = -1;
+    __syncthreads();
+    const rf_shot *recs = a.records + (size_t)se.stream * T;
+    TrackImageEntry src_im = im;
+    if (kind == RF_SHOT_STORED) {
+        if ((int)threadIdx.x < T && shot_record_is(recs + threadIdx.x, id, bf)) s_hit = (int)threadIdx.x;
+        __syncthreads();
+    } else if (kind == RF_SHOT_LAUNCH) {
+        const long long o = bf - f0;
+        if (o < (long long)se.n) {
+            src_im = a.images[se.first + (int)o];
+            shot_find_face(a, src_im, id, &s_hit);
+        } else __syncthreads();
+    }
+    const int hit = s_hit;
+    if (kind != RF_SHOT_NONE && hit < 0) kind = RF_SHOT_NONE;
+    FrameDesc fd = FrameDesc{nullptr, 0, 0, 0, 0};
+    if (kind == RF_SHOT_LAUNCH) {
+        fd = a.frames[src_im.local];
+        if (fd.ptr == nullptr || fd.rows <= 0 || fd.cols <= 0) kind = RF_SHOT_NONE;
+    }
+    if (kind == RF_SHOT_LAUNCH) {
+        if (threadIdx.x == 0) shot_estimate<AA>(a, src_im.local, hit, src_im.scale, &xf);
+        __syncthreads();
+    }
+    if (band == 0 && threadIdx.x == 0 && a.out_info) {
+        rf_shot r;
+        if (kind == RF_SHOT_STORED) r = recs[hit];
+        else if (kind == RF_SHOT_LAUNCH) shot_record_set(&r, id, bf, xf.fwd);
+        else shot_record_set(&r, 0, 0, nullptr);
+        a.out_info[idx] = r;
+    }
+    if (a.out == nullptr) return;
+    const ShotBand<E, CHW> b(a.out + idx * bpf, band_buf, S, band, band_rows);
+    const uint8_t *stored = kind == RF_SHOT_STORED ? a.gallery + ((size_t)se.stream * T + hit) * bpf : nullptr;
+    if (kind == RF_SHOT_LAUNCH) b.template sample<AA>(fd, xf, a.spec);
+    else if (stored && b.copy_vectors(stored)) return;
+    else b.load(stored);
+    __syncthreads();
+    b.store();
+}
+
+template <typename E, bool CHW, bool AA>
+__global__ __launch_bounds__(kThreads) void shot_keep_kernel(ShotParams a, int band_rows) {
+#pragma clang fp contract(off)
+    __shared__ AlignShared<AA> xf;
+    __shared__ uint4 band_buf[kFaceLdsVecs];
+    __shared__ int s_hit;
+    const int slot = blockIdx.y, band = blockIdx.z;
+    const TrackStreamEntry se = a.streams[blockIdx.x];
+    const int T = a.max_tracks, S = a.spec.crop;
+    const uint8_t *st = a.state + (size_t)se.stream * (sizeof(TrackHeader) + (size_t)T * sizeof(rf_track));
+    const rf_track *t = (const rf_track *)(st + sizeof(TrackHeader)) + slot;
+    const long long id = t->id, bf = t->best_frame;
+    const long long f0 = shot_first_frame(((const TrackHeader *)st)->frames, se.n);
+    rf_track key;
+    key.id = id; key.best_frame = bf;
+    const int o = shot_owner_ordinal(&key, f0, se.n);
+    if (o < 0) return;
+    const TrackImageEntry im = a.images[se.first + o];
+    if (threadIdx.x == 0) s_hit = -1;
+    __syncthreads();
+    shot_find_face(a, im, id, &s_hit);
+    const int k = s_hit;
+    if (k < 0) return;
+    const FrameDesc fd = a.frames[im.local];
+    if (fd.ptr == nullptr || fd.rows <= 0 || fd.cols <= 0) return;
+    if (threadIdx.x == 0) shot_estimate<AA>(a, im.local, k, im.scale, &xf);
+    __syncthreads();
+    const size_t entry = (size_t)se.stream * T + slot;
+    if (band == 0 && threadIdx.x == 0) {
+        rf_shot r;
+        shot_record_set(&r, id, bf, xf.fwd);
+        a.records[entry] = r;
+    }
+    const ShotBand<E, CHW> b(a.gallery + entry * (size_t)3 * S * S * sizeof(E), band_buf, S, band, band_rows);
+    b.template sample<AA>(fd, xf, a.spec);
+    __syncthreads();
+    b.store();
+}
+
+static void shot_check(const ShotParams &p) {
+    const FaceBatchSpec &sp = p.spec;
+    if (sp.crop < kAlignMinCrop || sp.crop > kAlignMaxCrop || p.max_tracks < 1 || p.max_tracks > kTrackMaxTracks || p.max_faces < 1)
+        throw Unsupported("shots: crop size, tracks per stream or faces per image out of range");
+    if (sp.format != RF_FACES_U8_HWC && sp.format != RF_FACES_F16_CHW && sp.format != RF_FACES_F32_CHW) throw Unsupported("shots: unknown format");
+    if (sp.antialias && sp.aa_max != 1 && sp.aa_max != 2 && sp.aa_max != 4 && sp.aa_max != 8) throw Unsupported("shots: aa_max must be 1, 2, 4 or 8");
+    if (p.out && ((uintptr_t)p.out & (uintptr_t)(sp.elem_bytes() - 1))) throw Unsupported("shots: the shot block is not aligned to its element size");
+}
+
+#define RF_SHOT_DISPATCH(KERNEL, GRID)                                                                                                  \
+    do {                                                                                                                                \
+        if (sp.antialias) {                                                                                                             \
+            if (sp.format == RF_FACES_U8_HWC) hipLaunchKernelGGL((KERNEL<uint8_t, false, true>), GRID, dim3(kThreads), 0, s, p, rows);   \
+            else if (sp.format == RF_FACES_F16_CHW) hipLaunchKernelGGL((KERNEL<half_t, true, true>), GRID, dim3(kThreads), 0, s, p, rows); \
+            else hipLaunchKernelGGL((KERNEL<float, true, true>), GRID, dim3(kThreads), 0, s, p, rows);                                   \
+        } else if (sp.format == RF_FACES_U8_HWC) hipLaunchKernelGGL((KERNEL<uint8_t, false, false>), GRID, dim3(kThreads), 0, s, p, rows); \
+        else if (sp.format == RF_FACES_F16_CHW) hipLaunchKernelGGL((KERNEL<half_t, true, false>), GRID, dim3(kThreads), 0, s, p, rows);  \
+        else hipLaunchKernelGGL((KERNEL<float, true, false>), GRID, dim3(kThreads), 0, s, p, rows);                                      \
+    } while (0)
+
+void launch_shot_deliver(hipStream_t s, const ShotParams &p) {
+    if (p.n_images <= 0 || p.cap_ended <= 0 || (!p.out && !p.out_info)) return;
+    shot_check(p);
+    const FaceBatchSpec &sp = p.spec;
+    const int rows = face_batch_band_rows(sp.crop, sp.format);
+    // at most max_tracks tracks end in one frame step; records only: one band per shot is enough
+    const dim3 grid(p.n_images, p.cap_ended < p.max_tracks ? p.cap_ended : p.max_tracks, p.out ? (sp.crop + rows - 1) / rows : 1);
+    RF_SHOT_DISPATCH(shot_deliver_kernel, grid);
+}
+
+void launch_shot_keep(hipStream_t s, const ShotParams &p) {
+    if (p.n_streams <= 0) return;
+    shot_check(p);
+    const FaceBatchSpec &sp = p.spec;
+    const int rows = face_batch_band_rows(sp.crop, sp.format);
+    const dim3 grid(p.n_streams, p.max_tracks, (sp.crop + rows - 1) / rows);
+    RF_SHOT_DISPATCH(shot_keep_kernel, grid);
+}
+#undef RF_SHOT_DISPATCH
+
+// =============================================================================================
 // K_k: face redaction (redact.h), in place in the frames of a launch.  Three launches ordered on the stream, race-free by
 //      construction: redact_regions_kernel writes region records, redact_mean_kernel only READS frames and writes cell values,
 //      redact_write_kernel reads only records, cell values and spec constants and writes the pixels each region owns -- every pixel

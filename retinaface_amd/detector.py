@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (rf_face, rf_face_batch_spec, rf_face_gate, rf_face_quality, rf_options, rf_redact_spec, rf_tile_spec, rf_track,
-                   rf_pyramid_spec, rf_track_spec, rf_track_tag, rf_tta_spec)
+                   rf_pyramid_spec, rf_shot, rf_track_spec, rf_track_tag, rf_tta_spec)
 
 PRECISION_FP32, PRECISION_FP16, PRECISION_INT8 = 0, 1, 2
 
@@ -208,6 +208,34 @@ FACE_DTYPE = np.dtype([("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<
 TRACK_DTYPE = np.dtype([("id", "<i8"), ("first_frame", "<i8"), ("last_frame", "<i8"), ("best_frame", "<i8"), ("best_value", "<f8"),
                         ("hits", "<i4"), ("missed", "<i4"), ("flags", "<i4"), ("reserved", "<i4"), ("last", FACE_DTYPE), ("best", FACE_DTYPE)])
 TRACK_TAG_DTYPE = np.dtype([("id", "<i8"), ("slot", "<i4"), ("hits", "<i4"), ("age", "<i4"), ("flags", "<i4")])
+# one rf_shot record (64 bytes)
+SHOT_DTYPE = np.dtype([("id", "<i8"), ("frame", "<i8"), ("matrix", "<f8", 6)])
+
+
+def shot_resolve(max_tracks: int, tags, counts, ended, ended_counts, first_frame: int, records, faces=None, coord_scale=None,
+                 crop_size: int = 112):
+    """rf_shot_resolve (host only, no GPU): the decisions of the two shot kernels for one stream's n images of one launch.  tags:
+    (n, cap_per_image) TRACK_TAG_DTYPE, ended: (n, cap_ended) TRACK_DTYPE, records: (max_tracks,) SHOT_DTYPE before the launch, faces:
+    None or (n, cap_per_image, 15) float32.  Returns (delivered, source (n, cap_ended, 3), owner (max_tracks, 2), records after)."""
+    lib = _lib.load_library()
+    tags = np.ascontiguousarray(tags, TRACK_TAG_DTYPE)
+    ended = np.ascontiguousarray(ended, TRACK_DTYPE)
+    n, cap = tags.shape
+    cap_ended = ended.shape[1]
+    rec = np.ascontiguousarray(records, SHOT_DTYPE).copy()
+    cnt = (C.c_int * max(n, 1))(*[int(c) for c in counts])
+    ec = (C.c_int * max(n, 1))(*[int(c) for c in ended_counts])
+    source = np.zeros((max(n, 1), max(cap_ended, 1), 3), np.int32)
+    owner = np.zeros((max_tracks, 2), np.int32)
+    fr = np.ascontiguousarray(faces, np.float32) if faces is not None else None
+    cs = (C.c_float * max(n, 1))(*coord_scale) if coord_scale is not None else None
+    st = lib.rf_shot_resolve(int(max_tracks), n, tags.ctypes.data_as(C.POINTER(rf_track_tag)), cap, cnt, ended.ctypes.data_as(C.POINTER(rf_track)),
+                             cap_ended, ec, int(first_frame), fr.ctypes.data_as(C.POINTER(rf_face)) if fr is not None else None, cs,
+                             int(crop_size), rec.ctypes.data_as(C.POINTER(rf_shot)), source.ctypes.data_as(C.POINTER(C.c_int32)),
+                             owner.ctypes.data_as(C.POINTER(C.c_int32)))
+    if st < 0:
+        raise _lib.RFError(st, "rf_shot_resolve: bad argument")
+    return int(st), source[:n, :cap_ended], owner, rec
 TRACK_NEW, TRACK_CONFIRMED, TRACK_BEST, TRACK_UNTRACKED, TRACK_OVERFLOW = 1, 2, 4, 8, 16
 
 
@@ -354,6 +382,87 @@ class Tracker:
                                                          mf, tags, ended, ce, ec), self._det._h)
         self.truncated = st == _lib.RF_ERR_TRUNCATED
         return self._results(n, counts, cap)
+
+    # ------------------------------------------------------------------ best-shot gallery
+    def enable_shots(self, **spec):
+        """rf_tracker_enable_shots: give the tracker a gallery; keywords as face_batch_spec().  From then on only the shot calls take it."""
+        sp = face_batch_spec(**spec)
+        _lib.check(self._lib.rf_tracker_enable_shots(self._t, C.byref(sp)), self._det._h)
+        self.shot_spec = sp
+        self.shot_dtype = np.dtype(_FACE_FORMATS[spec.get("dtype", "f16")][1])
+        self.bytes_per_face = 3 * (sp.crop_size or 112) ** 2 * self.shot_dtype.itemsize
+        self.shot_max_faces = sp.max_faces or self._det.max_detections
+        self.last_shots = self.last_shot_info = None
+        return self
+
+    def _shot_buffers(self, n, cap_ended, host=True):
+        cap_ended = self.max_tracks if cap_ended is None else int(cap_ended)
+        self.last_shots = np.full((max(n, 1), max(cap_ended, 1), self.bytes_per_face), 0xA5, np.uint8) if host else None
+        self.last_shot_info = np.full((max(n, 1), max(cap_ended, 1)), 0xA5, np.uint8).repeat(64, 1).view(SHOT_DTYPE)
+        return (self.last_shots.ctypes.data if host else None), self.last_shot_info.ctypes.data_as(C.POINTER(rf_shot))
+
+    def _shot_results(self, n):
+        ce = self.last_ended.shape[1]
+        k = [min(int(self.last_ended_counts[i]), ce) for i in range(n)]
+        shots = [self.last_shots[i, :k[i]].copy() for i in range(n)] if self.last_shots is not None else None
+        return shots, [self.last_shot_info[i, :k[i]].copy() for i in range(n)]
+
+    def read_shots(self, stream: int):
+        """rf_tracker_read_shots: (entries (max_tracks, bytes_per_face) u8, records (max_tracks,) SHOT_DTYPE) of a stream"""
+        ent = np.zeros((self.max_tracks, self.bytes_per_face), np.uint8)
+        rec = np.zeros(self.max_tracks, SHOT_DTYPE)
+        _lib.check(self._lib.rf_tracker_read_shots(self._t, int(stream), ent.ctypes.data, rec.ctypes.data_as(C.POINTER(rf_shot)), self.max_tracks),
+                   self._det._h)
+        return ent, rec
+
+    def flush_shots(self, stream: int):
+        """rf_tracker_flush_shots: (ended tracks, their shots (k, bytes_per_face) u8, their records), slot-ascending"""
+        ended = np.zeros(self.max_tracks, TRACK_DTYPE)
+        ent = np.zeros((self.max_tracks, self.bytes_per_face), np.uint8)
+        rec = np.zeros(self.max_tracks, SHOT_DTYPE)
+        k = _lib.check(self._lib.rf_tracker_flush_shots(self._t, int(stream), ended.ctypes.data_as(C.POINTER(rf_track)), self.max_tracks, None, None,
+                                                        ent.ctypes.data, rec.ctypes.data_as(C.POINTER(rf_shot))), self._det._h)
+        return ended[:k], ent[:k], rec[:k]
+
+    def update_shots(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], streams: Sequence[int], faces, *,
+                     steps: Optional[Sequence[int]] = None, coord_scale: Optional[Sequence[float]] = None, quality=None,
+                     cap_per_image: Optional[int] = None, cap_ended: Optional[int] = None, d_shots: int = 0, host_shots: bool = True):
+        """rf_track_shots_device: update() against frames resident in device memory + the gallery rules.  Returns (tags per image,
+        ended tracks per image, shots per image (None without host_shots), shot records per image)."""
+        n = len(streams)
+        per = [_face_rows(f) for f in faces]
+        mf = self.shot_max_faces
+        cap = int(cap_per_image) if cap_per_image is not None else max([len(r) for r in per] + [1])
+        flat = np.zeros((max(n, 1), cap, 15), np.float32)
+        counts = (C.c_int * max(n, 1))()
+        for i, r in enumerate(per):
+            flat[i, :min(len(r), cap)] = r[:cap]
+            counts[i] = len(r)
+        q = None
+        if quality is not None:
+            q = np.zeros((max(n, 1), mf), QUALITY_DTYPE)
+            for i, rec in enumerate(quality):
+                if rec is not None and len(rec):
+                    q[i, :min(len(rec), mf)] = np.asarray(rec, QUALITY_DTYPE)[:mf]
+        cs = (C.c_float * max(n, 1))(*coord_scale) if coord_scale is not None else None
+        p = (C.c_void_p * max(n, 1))(*ptrs)
+        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
+        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        t, _, tags, ended, ce, ec = self._buffers(n, cap, cap_ended)
+        shots, info = self._shot_buffers(n, cap_ended, host_shots)
+        st = _lib.check(self._lib.rf_track_shots_device(self._det._h, t, p, r, c, s, n, (C.c_int * max(n, 1))(*streams),
+                                                        flat.ctypes.data_as(C.POINTER(rf_face)), cap, counts, cs,
+                                                        q.ctypes.data_as(C.POINTER(rf_face_quality)) if q is not None else None, tags, ended, ce,
+                                                        ec, d_shots or None, shots, info), self._det._h)
+        self.truncated = st == _lib.RF_ERR_TRUNCATED
+        self.last_counts = [0 if not ptrs[i] else int(counts[i]) for i in range(n)]
+        return self._results(n, self.last_counts, cap) + self._shot_results(n)
+
+    def shot_last_launch_ms(self) -> float:
+        """rf_shot_last_launch_ms: HIP-event time of the two shot launches of the most recent update_shots()"""
+        ms = C.c_float()
+        _lib.check(self._lib.rf_shot_last_launch_ms(self._det._h, C.byref(ms)), self._det._h)
+        return float(ms.value)
 
     def detect_redacted_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], streams: Sequence[int],
                                threshold: float = 0.5, steps: Optional[Sequence[int]] = None, cap_ended: Optional[int] = None, spec=None):
@@ -1070,6 +1179,58 @@ class RetinaFace:
         if len(res) == 4:
             res = res[:3] + ([res[3][i, :min(counts[i], res[3].shape[1], cap)] for i in range(n)],)
         return (self._collect(out, counts, n, cap),) + res + tracker._results(n, counts, cap)
+
+    # ------------------------------------------------------------------ best-shot gallery
+    def _run_shots(self, fn, ptrs, rows, cols, steps, n, threshold, tracker, streams, cap_ended, gate, return_quality, d_shots, host_shots):
+        cap = self.max_detections
+        out = (rf_face * max(n * cap, 1))()
+        counts = (C.c_int * max(n, 1))()
+        t, _, tags, ended, ce, ec = tracker._buffers(n, cap, cap_ended)
+        shots, info = tracker._shot_buffers(n, cap_ended, host_shots)
+        g = _as_gate(gate)
+        q = np.zeros((max(n, 1), tracker.shot_max_faces), QUALITY_DTYPE) if return_quality else None
+        st = _lib.check(fn(self._h, ptrs, rows, cols, steps, n, float(threshold), out, cap, counts, t, (C.c_int * max(n, 1))(*streams), tags,
+                           ended, ce, ec, C.byref(g) if g is not None else None,
+                           q.ctypes.data_as(C.POINTER(rf_face_quality)) if q is not None else None, d_shots or None, shots, info), self._h)
+        self.truncated = tracker.truncated = st == _lib.RF_ERR_TRUNCATED
+        self.last_out = _faces_to_array(out, max(n * cap, 1)).reshape(max(n, 1), cap, 15)
+        self.last_counts = [int(counts[i]) for i in range(n)]
+        res = (self._collect(out, counts, n, cap),) + tracker._results(n, counts, cap) + tracker._shot_results(n)
+        if q is not None:
+            res += ([q[i, :min(counts[i], q.shape[1], cap)] for i in range(n)],)
+        return res
+
+    def detect_track_shots_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], tracker: Tracker, streams: Sequence[int],
+                                  threshold: float = 0.5, steps: Optional[Sequence[int]] = None, cap_ended: Optional[int] = None, gate=None,
+                                  return_quality: bool = False, d_shots: int = 0, host_shots: bool = True):
+        """rf_detect_track_shots_batch_device: detect_tracked_device on a tracker with a gallery (Tracker.enable_shots); the tracks that
+        end hand over their best shots.  Returns (detections, tags, ended, shots, shot records[, quality])."""
+        n = len(ptrs)
+        p = (C.c_void_p * max(n, 1))(*ptrs)
+        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
+        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        return self._run_shots(self._lib.rf_detect_track_shots_batch_device, p, r, c, s, n, threshold, tracker, streams, cap_ended, gate,
+                               return_quality, d_shots, host_shots)
+
+    def detect_track_shots(self, imgs: Sequence[np.ndarray], tracker: Tracker, streams: Sequence[int], threshold: float = 0.5,
+                           cap_ended: Optional[int] = None, gate=None, return_quality: bool = False):
+        """rf_detect_track_shots_batch: detect_track_shots_device for frames in host memory"""
+        n = len(imgs)
+        ptrs = (C.c_void_p * max(n, 1))()
+        rows, cols, steps = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
+        keep = []
+        for i, im in enumerate(imgs):
+            if im is None or im.size == 0:
+                ptrs[i], rows[i], cols[i], steps[i] = None, 0, 0, 0
+                continue
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
+            if im.strides[2] != 1 or im.strides[1] != 3:
+                im = np.ascontiguousarray(im)
+            keep.append(im)
+            ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
+        return self._run_shots(self._lib.rf_detect_track_shots_batch, ptrs, rows, cols, steps, n, threshold, tracker, streams, cap_ended, gate,
+                               return_quality, 0, True)
 
     # ------------------------------------------------------------------ face redaction
     def _redact_regions(self, sp) -> int:
