@@ -122,6 +122,14 @@ public:
     const vector<vector<rf_track_tag>> &lastTrackTags() const { return trackTags_; }
     const vector<vector<rf_track>> &lastEndedTracks() const { return trackEnded_; }
 
+    /* additive: motion-predicted tracks (rf_tracker_enable_motion): enableMotion() gives a tracker a velocity per track (spec may be
+       nullptr: the defaults) before its first frame step; every tracked call then matches and coasts at the predicted boxes.
+       readMotion() returns a stream's records, one per slot; predictTrack() is rf_track_predict: the face a live track is expected
+       at, ahead = 0 (where redaction coasts) or 1 (where the next frame step matches). */
+    void enableMotion(rf_tracker tracker, const rf_motion_spec *spec = nullptr);
+    vector<rf_track_motion> readMotion(rf_tracker tracker, int stream);
+    static rf_face predictTrack(const rf_track &track, const rf_track_motion &motion, int ahead = 1, const rf_motion_spec *spec = nullptr);
+
     /* additive: best-shot gallery (rf_tracker_enable_shots / rf_detect_track_shots_batch): enableShots() gives a tracker a gallery of
        face-batch crops (spec as detectFaceBatch(); capacity is not used) and returns the bytes of one shot; from then on the tracker is
        stepped with detectTrackShots(), which is detectTracked() plus the shots of the tracks that end: lastShots()[i] holds

@@ -595,7 +595,8 @@ int rf_detect_track_shots_batch(rf_handle h, const uint8_t *const *bgr, const in
  *            c x c square cut by the unclipped rectangle and the frame (not by the mask, not by ownership); its value per channel is
  *            (sum + n / 2) / n over that set, of the ORIGINAL bytes.  With c == 1 pixelation is the identity.
  *   list     of image i: its faces k < min(counts[i], max_regions) in score order; with a tracker, then the `last` boxes (scale 1) of
- *            its stream's live tracks with 1 <= missed <= coast in ascending slot order; cut at max_regions.  A pixel is OWNED by the
+ *            its stream's live tracks with 1 <= missed <= coast in ascending slot order (with a motion tracker, rf_tracker_enable_motion,
+ *            their predicted boxes instead); cut at max_regions.  A pixel is OWNED by the
  *            lowest-indexed region whose mask covers it.  The output equals the input except at owned pixels, which take their owner's
  *            cell value (PIXELATE) or fill (FILL).  Every read is of the original frame.
  *   results  pixels[i * max_regions + r] (may be NULL): the pixels region r owns; region_counts[i] (may be NULL): the length of the list
@@ -660,6 +661,50 @@ int rf_detect_track_redact_batch_device(rf_handle h, void *const *d_bgr, const i
                                         float threshold, rf_face *out, int cap_per_image, int *counts, rf_tracker tracker,
                                         const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_counts,
                                         const rf_redact_spec *spec, int32_t *pixels, int *region_counts);
+
+/* ---- Motion-predicted face tracks: a tracker may keep a velocity per track slot and match and coast at the PREDICTED box, so a face
+ * that moves while the detector drops it keeps its id and stays covered (DESIGN.md "Motion-predicted tracks" holds the definition;
+ * tests/motion_ref.py restates it in numpy; every result is byte-exact against it).  All arithmetic is fp32 with one rounding per
+ * operation, never contracted.  rf_track, rf_track_tag and rf_track.last (the last OBSERVED face) are what they were.
+ *   record     one rf_track_motion per slot; a free slot and a newly opened track have the all-zero record
+ *   predicted  face of a live track h frames ahead: samples == 0 or h == 0: `last`, the same bytes, no arithmetic.  Otherwise
+ *              dx = vx * (float)h, dy = vy * (float)h; every x coordinate (x1, x2, px[0..4]) becomes x + dx, every y coordinate y + dy; the
+ *              score is copied.  The box keeps its observed size.
+ *   frame step rf_track_step's with two changes.  `match` compares d_k with the track's predicted box for h = min(missed + 1, horizon)
+ *              (h = 0 with a negative horizon), taken once at the start of the image's step; expression, eligibility, tie rule and greedy
+ *              order are unchanged.  A matched track updates its velocity before `last` is overwritten: dt = (float)(missed + 1) with
+ *              missed from before the match; rx = ((nx1 + nx2) * 0.5f - (lx1 + lx2) * 0.5f) / dt, n the new mapped box, l the old `last`;
+ *              ry likewise; samples == 0: v = r, else v = v + alpha * (r - v) (a subtract, a multiply, an add).  vx or vy not finite: the
+ *              record becomes all zero; else samples = min(samples + 1, 1 << 30).  A slot that ends or is opened gets the zero record.
+ *   redaction  the coasting entries of the region list (1 <= missed <= coast) use the predicted box for h = min(missed, horizon).
+ * With a negative horizon tags, ended lists, counts and tables are the bytes of the plain tracker; only the records differ. */
+typedef struct rf_motion_spec {
+    uint32_t struct_size;   /* sizeof(rf_motion_spec) */
+    float alpha;            /* weight of the newest velocity sample, finite and in (0, 1]; 0 = 0.5 */
+    int32_t horizon;        /* most frames a box is extrapolated, 1..65536; 0 = 8; negative = never extrapolate */
+    int32_t reserved;       /* must be 0 */
+} rf_motion_spec;
+typedef struct rf_track_motion { float vx, vy; int32_t samples; int32_t reserved; } rf_track_motion;   /* 16 bytes, no padding */
+
+/* Host only, no GPU, no handle.  rf_track_step_motion: rf_track_step plus a caller-held array of max_tracks motion records (all zero to
+ * start); mspec NULL = all defaults.  A bad mspec (wrong size, non-zero reserved, a field out of range) is RF_ERR_INVALID_ARG like any
+ * other bad argument and changes nothing.
+ * rf_track_predict: the predicted face of a live track for h = min(missed + ahead, horizon), ahead 0 (where redaction coasts) or 1 (where
+ * the next frame step matches).  RF_ERR_INVALID_ARG for a free slot (id 0), a bad spec, another `ahead` or a NULL argument. */
+int rf_track_step_motion(const rf_track_spec *spec, const rf_motion_spec *mspec, rf_track *table, rf_track_motion *motion, int64_t *frames,
+                         int64_t *next_id, const rf_face *faces, int count, float coord_scale, const rf_face_quality *quality,
+                         int max_faces, rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_count);
+int rf_track_predict(const rf_motion_spec *mspec, const rf_track *track, const rf_track_motion *motion, int ahead, rf_face *out);
+
+/* Gives the tracker motion for its lifetime: every tracked call (rf_track_update_device, rf_detect_track_batch*,
+ * rf_detect_track_face_batch_device, rf_track_shots_device, rf_detect_track_shots_batch*, rf_detect_track_redact_batch_device) then runs
+ * the motion frame step, and rf_redact_device / rf_detect_track_redact_batch_device coast at the predicted boxes; their other outputs are
+ * defined as before, from the tags the step produced.  Refused with RF_ERR_INVALID_ARG, changing nothing, for a bad spec, a tracker that
+ * has stepped a frame (any stream's frame counter non-zero) or one that has motion already.  Composes with rf_tracker_enable_shots in
+ * either order.  rf_tracker_reset, rf_tracker_flush and rf_tracker_flush_shots zero the records of the slots they free. */
+int rf_tracker_enable_motion(rf_tracker tracker, const rf_motion_spec *mspec);
+/* Host copy of the first min(cap, max_tracks) motion records of a stream.  Returns max_tracks; RF_ERR_INVALID_ARG without motion. */
+int rf_tracker_read_motion(rf_tracker tracker, int stream, rf_track_motion *out, int cap);
 
 /* ---- Flip test-time augmentation with box voting: every frame is detected as it is and mirrored left-right, the mirrored faces are
  * moved back into the frame, and overlapping boxes of both passes are merged on the device into a score-weighted mean (DESIGN.md "Flip

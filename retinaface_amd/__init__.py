@@ -14,6 +14,7 @@ from .detector import (PRECISION_FP16, PRECISION_FP32, PRECISION_INT8, QUALITY_D
 from .detector import (FACE_DTYPE, TRACK_BEST, TRACK_CONFIRMED, TRACK_DTYPE, TRACK_NEW, TRACK_OVERFLOW, TRACK_TAG_DTYPE, TRACK_UNTRACKED,  # noqa: F401
                        Tracker, track_spec, track_step)
 from .detector import SHOT_DTYPE, shot_resolve  # noqa: F401
+from .detector import MOTION_DTYPE, motion_spec, track_predict  # noqa: F401
 from .detector import tta_map_face, tta_merge_host, tta_spec  # noqa: F401
 from .detector import pyramid_map_face, pyramid_merge_host, pyramid_plan, pyramid_spec, zoom_host  # noqa: F401
 from .detector import REDACT_ELLIPSE, REDACT_FILL, REDACT_PIXELATE, REDACT_RECT, redact_host, redact_region, redact_spec  # noqa: F401

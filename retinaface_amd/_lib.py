@@ -77,6 +77,14 @@ class rf_shot(C.Structure):
     _fields_ = [("id", C.c_int64), ("frame", C.c_int64), ("matrix", C.c_double * 6)]
 
 
+class rf_motion_spec(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("alpha", C.c_float), ("horizon", C.c_int32), ("reserved", C.c_int32)]
+
+
+class rf_track_motion(C.Structure):
+    _fields_ = [("vx", C.c_float), ("vy", C.c_float), ("samples", C.c_int32), ("reserved", C.c_int32)]
+
+
 RF_SHOT_NONE, RF_SHOT_STORED, RF_SHOT_LAUNCH = 0, 1, 2
 RF_SHOT_MAX_BYTES = 1 << 30
 
@@ -201,6 +209,12 @@ SYMBOLS = {
                                         _PP(C.c_int), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_float), _PP(rf_face_quality),
                                         _PP(rf_track_tag), _PP(rf_track), C.c_int, _PP(C.c_int), C.c_void_p, C.c_void_p, _PP(rf_shot)]),
     "rf_shot_last_launch_ms": (C.c_int, [C.c_void_p, _PP(C.c_float)]),
+    "rf_track_step_motion": (C.c_int, [_PP(rf_track_spec), _PP(rf_motion_spec), _PP(rf_track), _PP(rf_track_motion), _PP(C.c_int64),
+                                       _PP(C.c_int64), _PP(rf_face), C.c_int, C.c_float, _PP(rf_face_quality), C.c_int, _PP(rf_track_tag),
+                                       _PP(rf_track), C.c_int, _PP(C.c_int)]),
+    "rf_track_predict": (C.c_int, [_PP(rf_motion_spec), _PP(rf_track), _PP(rf_track_motion), C.c_int, _PP(rf_face)]),
+    "rf_tracker_enable_motion": (C.c_int, [C.c_void_p, _PP(rf_motion_spec)]),
+    "rf_tracker_read_motion": (C.c_int, [C.c_void_p, C.c_int, _PP(rf_track_motion), C.c_int]),
     "rf_detect_track_shots_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
                                                      C.c_float, _PP(rf_face), C.c_int, _PP(C.c_int), C.c_void_p, _PP(C.c_int),
                                                      _PP(rf_track_tag), _PP(rf_track), C.c_int, _PP(C.c_int), _PP(rf_face_gate),

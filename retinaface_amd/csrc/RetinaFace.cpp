@@ -133,6 +133,25 @@ void RetinaFace::detectTracked(const vector<cv::Mat> &imgs, rf_tracker tracker, 
     }
 }
 
+void RetinaFace::enableMotion(rf_tracker tracker, const rf_motion_spec *spec) {
+    check(rf_tracker_enable_motion(tracker, spec), h_, "RetinaFace::enableMotion");
+}
+
+vector<rf_track_motion> RetinaFace::readMotion(rf_tracker tracker, int stream) {
+    vector<rf_track_motion> rec(256);                  // a table holds at most 256 tracks
+    const int k = rf_tracker_read_motion(tracker, stream, rec.data(), (int)rec.size());
+    if (k < 0) check(k, h_, "RetinaFace::readMotion");
+    rec.resize(k);
+    return rec;
+}
+
+rf_face RetinaFace::predictTrack(const rf_track &track, const rf_track_motion &motion, int ahead, const rf_motion_spec *spec) {
+    rf_face f;
+    if (rf_track_predict(spec, &track, &motion, ahead, &f) != RF_OK)
+        throw std::runtime_error("RetinaFace::predictTrack: a free slot, a bad spec or an ahead other than 0 or 1");
+    return f;
+}
+
 size_t RetinaFace::enableShots(rf_tracker tracker, const rf_face_batch_spec &spec) {
     check(rf_tracker_enable_shots(tracker, &spec), h_, "RetinaFace::enableShots");
     const size_t S = spec.crop_size ? (size_t)spec.crop_size : 112;

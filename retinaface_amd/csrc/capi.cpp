@@ -780,6 +780,50 @@ int rf_tracker_enable_shots(rf_tracker tracker, const rf_face_batch_spec *spec) 
     });
 }
 
+// ---- motion-predicted tracks (motion.h)
+int rf_track_step_motion(const rf_track_spec *spec, const rf_motion_spec *mspec, rf_track *table, rf_track_motion *motion, int64_t *frames,
+                         int64_t *next_id, const rf_face *faces, int count, float coord_scale, const rf_face_quality *quality,
+                         int max_faces, rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_count) {
+    rf::TrackSpec sp;
+    rf::MotionSpec ms;
+    if (rf::track_spec_resolve(spec, &sp) || rf::motion_spec_resolve(mspec, &ms)) return RF_ERR_INVALID_ARG;
+    if (!table || !motion || !frames || !next_id || !ended_count || count < 0 || max_faces < 1 || cap_ended < 0) return RF_ERR_INVALID_ARG;
+    if (count > 0 && (!faces || !tags)) return RF_ERR_INVALID_ARG;
+    if (cap_ended > 0 && !ended) return RF_ERR_INVALID_ARG;
+    const int m = std::min(std::min(count, max_faces), rf::kTrackMaxFaces);
+    const int st = rf::track_step_motion(sp, ms, table, motion, frames, next_id, (const float *)faces, (int)(sizeof(rf_face) / sizeof(float)), m,
+                                         coord_scale, quality, tags, ended, cap_ended, ended_count);
+    for (int k = m; k < count; k++) tags[k] = rf::track_tag_untracked(0);
+    return st ? RF_ERR_TRUNCATED : RF_OK;
+}
+
+int rf_track_predict(const rf_motion_spec *mspec, const rf_track *track, const rf_track_motion *motion, int ahead, rf_face *out) {
+    rf::MotionSpec ms;
+    if (rf::motion_spec_resolve(mspec, &ms)) return RF_ERR_INVALID_ARG;
+    if (!track || !motion || !out || (ahead != 0 && ahead != 1) || track->id == 0 || track->missed < 0) return RF_ERR_INVALID_ARG;
+    rf_face f;
+    rf::motion_predict_face(&track->last, motion, rf::motion_frames_ahead(track->missed, ahead, ms.horizon), &f);
+    *out = f;
+    return RF_OK;
+}
+
+int rf_tracker_enable_motion(rf_tracker tracker, const rf_motion_spec *mspec) {
+    if (!tracker) return RF_ERR_INVALID_ARG;
+    rf_engine *h = tracker->h;
+    return guarded(h, [&]() -> int {
+        if (h->eng->num_devices() > 1) throw rf::Unsupported("face tracks are not available on a multi-device handle");
+        rf::MotionSpec ms;
+        if (const char *bad = rf::motion_spec_resolve(mspec, &ms)) throw rf::ArgError(bad);
+        h->eng->tracker_enable_motion(tracker->impl, ms);
+        return RF_OK;
+    });
+}
+
+int rf_tracker_read_motion(rf_tracker tracker, int stream, rf_track_motion *out, int cap) {
+    if (!tracker) return RF_ERR_INVALID_ARG;
+    return guarded(tracker->h, [&]() -> int { return tracker->h->eng->tracker_read_motion(tracker->impl, stream, out, cap); });
+}
+
 int rf_tracker_read_shots(rf_tracker tracker, int stream, void *shots, rf_shot *shot_info, int cap) {
     if (!tracker) return RF_ERR_INVALID_ARG;
     return guarded(tracker->h, [&]() -> int { return tracker->h->eng->tracker_read_shots(tracker->impl, stream, (uint8_t *)shots, shot_info, cap); });

@@ -1282,6 +1282,10 @@ public:
             memset(&tr[s], 0, sizeof(rf_track));
         }
         if (ended) RF_HIP(hipMemcpy(d, img.data(), img.size(), hipMemcpyHostToDevice));
+        if (ended && t.has_motion) {                                   // every live slot was freed: the stream's records are all zero now
+            RF_HIP(hipMemset(t.motion.ptr + (size_t)stream * t.motion_bytes(), 0, t.motion_bytes()));
+            RF_HIP(hipDeviceSynchronize());
+        }
         return ended;
     }
 
@@ -1407,6 +1411,36 @@ public:
         } catch (...) { t.gallery.release(); t.shot_records.release(); throw; }
         t.shot_spec = spec;
         t.has_shots = true;
+    }
+
+    // -------------------------------------------------------------------------------- motion-predicted tracks
+    void tracker_enable_motion(void *p, const MotionSpec &spec) override {
+        Tracker &t = tracker_of(p);
+        if (t.dirty) throw ArgError("the tracker's last call failed: reset it first");
+        if (t.has_motion) throw ArgError("the tracker has motion already");
+        DeviceGuard guard(device_);
+        std::vector<TrackHeader> hd((size_t)t.n_streams);
+        RF_HIP(hipMemcpy2D(hd.data(), sizeof(TrackHeader), t.state.ptr, t.stream_bytes(), sizeof(TrackHeader), (size_t)t.n_streams, hipMemcpyDeviceToHost));
+        for (const TrackHeader &h : hd)
+            if (h.frames != 0) throw ArgError("motion: the tracker has stepped a frame already");
+        const size_t bytes = (size_t)t.n_streams * t.motion_bytes();
+        try {
+            RF_HIP(hipMemset(t.motion.reserve(bytes), 0, bytes));
+            RF_HIP(hipDeviceSynchronize());
+        } catch (...) { t.motion.release(); throw; }
+        t.motion_spec = spec;
+        t.has_motion = true;
+    }
+    int tracker_read_motion(void *p, int stream, rf_track_motion *out, int cap) override {
+        Tracker &t = tracker_of(p);
+        if (!t.has_motion) throw ArgError("the tracker has no motion (rf_tracker_enable_motion)");
+        if (stream < 0 || stream >= t.n_streams) throw ArgError("stream out of range");
+        if (cap < 0 || (cap > 0 && !out)) throw ArgError("out is null");
+        if (t.dirty) throw ArgError("the tracker's last call failed: reset it first");
+        DeviceGuard guard(device_);
+        const int m = std::min(cap, t.spec.max_tracks);
+        if (m > 0) RF_HIP(hipMemcpy(out, t.motion.ptr + (size_t)stream * t.motion_bytes(), (size_t)m * sizeof(rf_track_motion), hipMemcpyDeviceToHost));
+        return t.spec.max_tracks;
     }
 
     // a stream's table and shot records on the host
@@ -1697,6 +1731,7 @@ public:
             rp.track_state = red_.tr->state.ptr;
             rp.max_tracks = red_.tr->spec.max_tracks;
             rp.coast = redact_coast(red_.spec.coast, red_.tr->spec.max_missed);
+            if (red_.tr->has_motion) { rp.motion = (const rf_track_motion *)red_.tr->motion.ptr; rp.horizon = red_.tr->motion_spec.horizon; }
         }
         rp.regions = (RedactRegion *)red_regions_.ptr;
         rp.nreg = (int *)red_counts_.ptr; rp.true_counts = (int *)red_counts_.ptr + std::max(red_.n, 1);
@@ -2719,6 +2754,10 @@ private:
             RF_HIP(hipMemset(t.shot_records.ptr + (size_t)first * rb, 0, (size_t)count * rb));
             RF_HIP(hipDeviceSynchronize());
         }
+        if (t.has_motion) {
+            RF_HIP(hipMemset(t.motion.ptr + (size_t)first * t.motion_bytes(), 0, (size_t)count * t.motion_bytes()));
+            RF_HIP(hipDeviceSynchronize());
+        }
     }
     // the arguments of a tracked call, checked before any state changes
     Tracker &track_check(const TrackRequest &rq, int n, bool shots = false) {
@@ -2754,6 +2793,7 @@ private:
         tp.ended = (rf_track *)trk_ended_.ptr; tp.cap_ended = trk_.cap_ended;
         tp.ended_counts = (int *)trk_counts_.ptr;
         tp.status = (int *)trk_counts_.ptr + std::max(trk_.n, 1);
+        if (t.has_motion) { tp.motion = (rf_track_motion *)t.motion.ptr; tp.mspec = t.motion_spec; }
         return tp;
     }
     // Results of a finished tracked call, from the pinned blocks the kernel wrote; the host fills what the device never writes -- the
@@ -3068,8 +3108,13 @@ private:
         bool has_shots = false;
         FaceBatchSpec shot_spec;
         DeviceScratch gallery, shot_records;
+        // motion (motion.h), fixed by tracker_enable_motion(): n_streams x max_tracks rf_track_motion records
+        bool has_motion = false;
+        MotionSpec motion_spec;
+        DeviceScratch motion;
         size_t stream_bytes() const { return sizeof(TrackHeader) + (size_t)spec.max_tracks * sizeof(rf_track); }
-        void release() { state.release(); gallery.release(); shot_records.release(); }
+        size_t motion_bytes() const { return (size_t)spec.max_tracks * sizeof(rf_track_motion); }
+        void release() { state.release(); gallery.release(); shot_records.release(); motion.release(); }
     };
     std::vector<std::unique_ptr<Tracker>> trackers_;
     // (pinned host memory the kernel writes straight into, as the NMS kernel writes its result block: no copy after the call)

@@ -274,6 +274,13 @@ public:
     virtual int tracker_flush_shots(void *, int /*stream*/, rf_track *, int /*cap*/, int64_t *, int64_t *, uint8_t *, rf_shot *) {
         throw Unsupported("face tracks are not available on a multi-device handle");
     }
+    // Motion-predicted tracks (motion.h): a tracker may own n_streams x max_tracks motion records in device memory; every track launch
+    // of such a tracker is the motion kernel's, and redaction coasts at the predicted boxes.  Single-device engines only.
+    virtual void tracker_enable_motion(void *, const MotionSpec &) { throw Unsupported("face tracks are not available on a multi-device handle"); }
+    // host copy of a stream's motion records; returns max_tracks
+    virtual int tracker_read_motion(void *, int /*stream*/, rf_track_motion *, int /*cap*/) {
+        throw Unsupported("face tracks are not available on a multi-device handle");
+    }
     // track_update() against device-resident frames + the gallery rules; max_faces is the gallery spec's
     virtual void track_shots(const TrackRequest &, const ShotRequest &, const void *const *, const int *, const int *, const int *, int /*n*/,
                              const rf_face *, int /*cap_per_image*/, const int * /*counts*/, const float * /*coord_scale*/,

@@ -15,6 +15,7 @@
 #include "tile.h"
 #include "tta.h"
 #include "track.h"
+#include "motion.h"
 #include "shot.h"
 
 namespace rf {
@@ -287,7 +288,7 @@ struct TrackImageEntry {
     float scale;                          // coord_scale
     int32_t empty;                        // != 0: a frame without pixels, it has no faces whatever counts says
 };
-struct TrackParams {
+struct TrackArgs {                        // what track_kernel takes
     const TrackStreamEntry *streams; int n_streams;      // the grid
     const TrackImageEntry *images;
     const uint8_t *faces;                 // image i, face k: 15 floats at faces + (i * faces_per_image + k) * face_stride
@@ -301,6 +302,12 @@ struct TrackParams {
     rf_track *ended; int cap_ended;       // call image c: ended[c * cap_ended + j]
     int *ended_counts;                    // [call images] the true number
     int *status;                          // [call images] kTrackOverflow or 0
+};
+// With a motion pointer (motion.h) launch_track runs track_motion_kernel, the same layout with each slot's velocity in registers;
+// without one it runs track_kernel on the TrackArgs part alone.
+struct TrackParams : TrackArgs {
+    rf_track_motion *motion;              // stream s, slot t: motion[s * max_tracks + t], or nullptr: the plain frame step
+    MotionSpec mspec;
 };
 void launch_track(hipStream_t s, const TrackParams &p);
 
@@ -334,7 +341,7 @@ void launch_shot_keep(hipStream_t s, const ShotParams &p);
 //      records.  launch_redact_mean (PIXELATE only) reads the frames and writes every region's cell values; launch_redact_write reads
 //      only those, the records and the spec and writes the pixels each region owns.  Every pointer is device-visible memory (the fused
 //      calls read faces and counts from the pinned result block the NMS kernel wrote).
-struct RedactParams {
+struct RedactArgs {                       // what the three kernels take
     const FrameDesc *frames;              // [n] SOURCE frames (full resolution); they are written
     const uint8_t *faces;                 // image i, face k: an rf_face at faces + (i * faces_per_image + k) * face_stride
     int face_stride, faces_per_image;
@@ -351,6 +358,12 @@ struct RedactParams {
     int *true_counts;                     // [call images] ... before the cut
     uint32_t *cell_values;                // region slot q = c * max_regions + r, cell (gx, gy): cell_values[(q * cells + gy) * cells + gx]
     int *pixels;                          // [call images * max_regions] pixels each region owns (zeroed by launch_redact_regions)
+};
+// With a motion pointer launch_redact_regions runs the coasting-box variant of its kernel: a coasting track is redacted at its predicted
+// box for h = min(missed, horizon) (motion.h) instead of where it was last seen.
+struct RedactParams : RedactArgs {
+    const rf_track_motion *motion;        // the tracker's motion records (TrackParams::motion), or nullptr
+    int horizon;                          // MotionSpec::horizon
 };
 void launch_redact_regions(hipStream_t s, const RedactParams &p);
 void launch_redact_mean(hipStream_t s, const RedactParams &p);

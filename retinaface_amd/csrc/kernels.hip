@@ -4557,7 +4557,7 @@ __device__ inline int track_prefix_count(bool flag, int nw, int *s_cnt, int *tot
     return pos;
 }
 
-__global__ __launch_bounds__(kThreads) void track_kernel(TrackParams a) {
+__global__ __launch_bounds__(kThreads) void track_kernel(TrackArgs a) {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     rf_track *s_trk = (rf_track *)smem;                          // [max_tracks]
@@ -4688,12 +4688,170 @@ __global__ __launch_bounds__(kThreads) void track_kernel(TrackParams a) {
     if (tid == 0) { hdr->frames = f; hdr->next_id = next_id; }
 }
 
+// track_motion_kernel: track_kernel with motion (motion.h), a kernel of its own so that a tracker without motion runs exactly what it
+//      ran.  Same layout, barriers and LDS.  The slot's velocity and sample count live in registers: one 16-byte load per thread in
+//      front of the first image, one 16-byte store behind the last.  A stream may have several images in the launch, so the predicted
+//      box is recomputed in registers at the top of every image step from the thread's own last box, missed count (a register copy of
+//      the record's field, kept in step with it) and velocity; the
+//      winner of the max-reduction updates its velocity from the old last box right where it takes the face.
+__global__ __launch_bounds__(kThreads) void track_motion_kernel(TrackParams a) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    rf_track *s_trk = (rf_track *)smem;                          // [max_tracks]
+    __shared__ float s_face[kTrackMaxFaces][15];                 // the image's mapped faces
+    __shared__ short s_fslot[kTrackMaxFaces];                    // the slot face k matched, -1 = none
+    __shared__ short s_new[kTrackMaxFaces];                      // the faces that open tracks, in score order
+    __shared__ unsigned long long s_key[2][kThreads / 64];
+    __shared__ int s_cnt[kThreads / 64];
+    constexpr int kWords = (int)(sizeof(rf_track) / 4);
+
+    const int tid = (int)threadIdx.x, nthr = (int)blockDim.x, nw = nthr >> 6, lane = tid & 63, wave = tid >> 6;
+    const TrackStreamEntry se = a.streams[blockIdx.x];
+    const TrackSpec sp = a.spec;
+    const MotionSpec ms = a.mspec;
+    const int T = sp.max_tracks;
+    uint8_t *st = a.state + (size_t)se.stream * (sizeof(TrackHeader) + (size_t)T * sizeof(rf_track));
+    TrackHeader *hdr = (TrackHeader *)st;
+    uint32_t *g_trk = (uint32_t *)(st + sizeof(TrackHeader));
+    int4 *g_mot = (int4 *)(a.motion + (size_t)se.stream * T);   // hipMalloc'ed block, 16-byte records: aligned
+    for (int i = tid; i < T * kWords; i += nthr) ((uint32_t *)s_trk)[i] = g_trk[i];
+    long long f = hdr->frames, next_id = hdr->next_id;
+    const bool has_slot = tid < T;
+    float vx = 0.f, vy = 0.f;
+    int samples = 0;
+    if (has_slot) {
+        const int4 r = g_mot[tid];
+        vx = __int_as_float(r.x); vy = __int_as_float(r.y); samples = r.z;
+    }
+    __syncthreads();
+    bool live = has_slot && s_trk[has_slot ? tid : 0].id != 0;
+    float box[4] = {0.f, 0.f, 0.f, 0.f};                         // the track's last (observed) box
+    int missed = 0;                                              // its missed count: a register copy, so the winner does not wait for LDS
+    if (live) {
+        box[0] = s_trk[tid].last.x1; box[1] = s_trk[tid].last.y1; box[2] = s_trk[tid].last.x2; box[3] = s_trk[tid].last.y2;
+        missed = s_trk[tid].missed;
+    }
+
+    for (int ii = 0; ii < se.n; ii++) {
+        const TrackImageEntry im = a.images[se.first + ii];
+        int count = im.empty ? 0 : a.counts[im.local];
+        if (count < 0) count = 0;
+        int m = count < a.faces_per_image ? count : a.faces_per_image;
+        if (m > a.max_faces) m = a.max_faces;
+        if (m > kTrackMaxFaces) m = kTrackMaxFaces;
+        const uint8_t *src = a.faces + (size_t)im.local * a.faces_per_image * a.face_stride;
+        __syncthreads();                                         // the previous image's readers of s_face / s_fslot / s_new are done
+        for (int i = tid; i < m * 15; i += nthr) {
+            const int k = i / 15, j = i - k * 15;
+            const float v = ((const float *)(src + (size_t)k * a.face_stride))[j];
+            s_face[k][j] = j ? v * im.scale : v;                 // track_map_face
+        }
+        // where the track is expected in this frame
+        float pbox[4] = {0.f, 0.f, 0.f, 0.f};
+        if (live) motion_predict_box(box, vx, vy, samples, motion_frames_ahead(missed, 1, ms.horizon), pbox);
+        __syncthreads();
+        rf_track_tag *tags = a.tags + (size_t)im.image * a.tag_stride;
+        const rf_face_quality *rec = a.records ? a.records + (size_t)im.image * a.max_faces : nullptr;
+
+        // match
+        bool claimed = false;
+        for (int k = 0; k < m; k++) {
+            const float *fk = s_face[k];
+            const bool avail = live && !claimed;
+            const float iou = avail ? track_iou(fk + 1, pbox) : 0.f;
+            unsigned long long key = track_wave_max(track_match_key(avail, iou, sp.min_iou, tid));
+            if (nw > 1) {
+                if (lane == 0) s_key[k & 1][wave] = key;
+                __syncthreads();
+                for (int w = 0; w < nw; w++) { const unsigned long long o = s_key[k & 1][w]; key = o > key ? o : key; }
+            }
+            const int win = key ? track_key_slot(key) : -1;
+            if (tid == 0) s_fslot[k] = (short)win;
+            if (tid == win) {
+                claimed = true;
+                rf_track *t = &s_trk[tid];
+                motion_update(&vx, &vy, &samples, fk + 1, box, missed, ms.alpha);
+                missed = 0;
+                track_match_update(t, fk, f, sp.min_hits);
+                box[0] = fk[1]; box[1] = fk[2]; box[2] = fk[3]; box[3] = fk[4];
+                const int b = track_best_update(t, fk, f, rec ? rec + k : nullptr);
+                if (k < a.tag_stride) tags[k] = track_tag(t, tid, f, sp.min_hits, b);
+            }
+        }
+        __syncthreads();
+
+        // age: the ended tracks leave in slot order
+        bool ends = false;
+        if (live && !claimed) { ends = track_age(&s_trk[tid], sp.max_missed); missed += 1; }
+        int n_ended = 0;
+        const int epos = track_prefix_count(ends, nw, s_cnt, &n_ended);
+        if (ends) {
+            uint32_t *rec32 = (uint32_t *)&s_trk[tid];
+            if (epos < a.cap_ended) {
+                uint32_t *dst = (uint32_t *)(a.ended + (size_t)im.image * a.cap_ended + epos);
+                for (int i = 0; i < kWords; i++) dst[i] = rec32[i];
+            }
+            for (int i = 0; i < kWords; i++) rec32[i] = 0u;
+            live = false;
+            vx = 0.f; vy = 0.f; samples = 0; missed = 0;
+        }
+
+        // open: the j-th face that wants a track takes the j-th free slot
+        int n_new = 0;
+        for (int k0 = 0; k0 < m; k0 += nthr) {
+            const int k = k0 + tid;
+            bool wants = false;
+            if (k < m && s_fslot[k] < 0) {
+                if (s_face[k][0] >= sp.new_score) wants = true;
+                else if (k < a.tag_stride) tags[k] = track_tag_untracked(0);
+            }
+            int tot = 0;
+            const int pos = track_prefix_count(wants, nw, s_cnt, &tot);
+            if (wants) s_new[n_new + pos] = (short)k;
+            n_new += tot;
+        }
+        const bool is_free = has_slot && !live;
+        int n_free = 0;
+        const int fpos = track_prefix_count(is_free, nw, s_cnt, &n_free);
+        __syncthreads();                                         // s_new is complete
+        const int n_open = n_new < n_free ? n_new : n_free;
+        if (is_free && fpos < n_open) {
+            const int k = s_new[fpos];
+            const float *fk = s_face[k];
+            rf_track *t = &s_trk[tid];
+            track_open(t, next_id + fpos, fk, f, sp.min_hits);
+            box[0] = fk[1]; box[1] = fk[2]; box[2] = fk[3]; box[3] = fk[4];
+            live = true;
+            vx = 0.f; vy = 0.f; samples = 0; missed = 0;
+            const int b = track_best_update(t, fk, f, rec ? rec + k : nullptr);
+            if (k < a.tag_stride) tags[k] = track_tag(t, tid, f, sp.min_hits, RF_TRACK_NEW | b);
+        }
+        for (int j = n_open + tid; j < n_new; j += nthr) {
+            const int k = s_new[j];
+            if (k < a.tag_stride) tags[k] = track_tag_untracked(RF_TRACK_OVERFLOW);
+        }
+        const int n_tags = count < a.tag_stride ? count : a.tag_stride;            // the host fills the tags behind the image's count
+        for (int k = m + tid; k < n_tags; k += nthr) tags[k] = track_tag_untracked(0);
+        if (tid == 0) {
+            a.ended_counts[im.image] = n_ended;
+            a.status[im.image] = n_new > n_free ? kTrackOverflow : 0;
+        }
+        next_id += n_open;
+        f += 1;
+    }
+    __syncthreads();
+    for (int i = tid; i < T * kWords; i += nthr) g_trk[i] = ((const uint32_t *)s_trk)[i];
+    if (has_slot) g_mot[tid] = make_int4(__float_as_int(vx), __float_as_int(vy), samples, 0);
+    if (tid == 0) { hdr->frames = f; hdr->next_id = next_id; }
+}
+
 void launch_track(hipStream_t s, const TrackParams &p) {
     if (p.n_streams <= 0) return;
     const int T = p.spec.max_tracks;
     if (T < 1 || T > kTrackMaxTracks) throw LaunchUnsupported("track: max_tracks must be in [1, 256]");
     const int threads = (T + 63) / 64 * 64;
-    hipLaunchKernelGGL(track_kernel, dim3(p.n_streams), dim3(threads), (size_t)T * sizeof(rf_track), s, p);
+    if (p.motion) hipLaunchKernelGGL(track_motion_kernel, dim3(p.n_streams), dim3(threads), (size_t)T * sizeof(rf_track), s, p);
+    else hipLaunchKernelGGL(track_kernel, dim3(p.n_streams), dim3(threads), (size_t)T * sizeof(rf_track), s, (const TrackArgs &)p);
 }
 
 // =============================================================================================
@@ -4951,7 +5109,10 @@ void launch_shot_keep(hipStream_t s, const ShotParams &p) {
 constexpr int kRedactItemsPerImage = 256;      // workgroup slots per image the item list is dealt over
 constexpr int kRedactMaxGrid = 2048;
 
-__global__ __launch_bounds__(kThreads) void redact_regions_kernel(RedactParams a) {
+// kMotion: the coasting-box variant -- a coasting track is redacted at its predicted box (motion.h) instead of where it was last seen.
+// The plain instantiation takes the RedactArgs part alone and reads what it always read.
+template <bool kMotion>
+__global__ __launch_bounds__(kThreads) void redact_regions_kernel(typename std::conditional<kMotion, RedactParams, RedactArgs>::type a) {
     __shared__ int s_cnt[kThreads / 64];
     const int i = blockIdx.x, tid = (int)threadIdx.x;
     const int M = a.spec.max_regions;
@@ -4981,6 +5142,13 @@ __global__ __launch_bounds__(kThreads) void redact_regions_kernel(RedactParams a
             const rf_track *t = tab + tid;
             live = t->id != 0 && t->missed >= 1 && t->missed <= a.coast;
             if (live) { box[0] = t->last.x1; box[1] = t->last.y1; box[2] = t->last.x2; box[3] = t->last.y2; }
+            if constexpr (kMotion) {
+                if (live) {
+                    const int4 r = ((const int4 *)(a.motion + (size_t)stream * a.max_tracks))[tid];
+                    const float last[4] = {box[0], box[1], box[2], box[3]};
+                    motion_predict_box(last, __int_as_float(r.x), __int_as_float(r.y), r.z, motion_frames_ahead(t->missed, 0, a.horizon), box);
+                }
+            }
         }
         const int pos = track_prefix_count(live, kThreads / 64, s_cnt, &coasting);
         if (live && nf + pos < M) a.regions[slot0 + nf + pos] = redact_region_make(box, 1.f, a.spec.margin, a.spec.cells, fd.rows, fd.cols);
@@ -5012,7 +5180,7 @@ __device__ inline void redact_block_sum(uint32_t &sb, uint32_t &sg, uint32_t &sr
 // kThreads / L rows at a time, so a 15 x 15 cell of a small face keeps 16 rows x 13 lanes busy and a 160 x 160 cell of a huge one
 // reads whole rows.  A dword that lies inside the span is one aligned 32-bit load whatever the frame's pointer and pitch are; the
 // dwords at the two ends are read bytewise, so no byte outside the span is touched.  Byte j of the span belongs to channel j % 3.
-__global__ __launch_bounds__(kThreads) void redact_mean_kernel(RedactParams a, int per_image) {
+__global__ __launch_bounds__(kThreads) void redact_mean_kernel(RedactArgs a, int per_image) {
     __shared__ uint32_t s_red[kThreads / 64][3];
     const int tid = (int)threadIdx.x;
     const int M = a.spec.max_regions, C = a.spec.cells;
@@ -5069,7 +5237,7 @@ __global__ __launch_bounds__(kThreads) void redact_mean_kernel(RedactParams a, i
 // prefix, the gather kernel's idiom), then every pixel of it is tested: inside the region's own mask and inside no gathered
 // one = owned.  Owned pixels get their cell's value (or the fill) with three ordinary byte stores; the owned count is reduced over
 // the workgroup and added to the region's counter with one integer atomicAdd.
-__global__ __launch_bounds__(kThreads) void redact_write_kernel(RedactParams a, int per_image) {
+__global__ __launch_bounds__(kThreads) void redact_write_kernel(RedactArgs a, int per_image) {
     __shared__ int s_low[kRedactMaxRegions][8];                   // ux0, uy0, ux1, uy1, cx0, cy0, cx1, cy1 of a lower region: 32 KB
     __shared__ int s_cnt[kThreads / 64];
     const int tid = (int)threadIdx.x;
@@ -5156,17 +5324,18 @@ static int redact_grid(const RedactParams &p) {
 void launch_redact_regions(hipStream_t s, const RedactParams &p) {
     if (p.n <= 0) return;
     redact_check(p);
-    hipLaunchKernelGGL(redact_regions_kernel, dim3(p.n), dim3(kThreads), 0, s, p);
+    if (p.motion && p.track_state) hipLaunchKernelGGL(redact_regions_kernel<true>, dim3(p.n), dim3(kThreads), 0, s, p);
+    else hipLaunchKernelGGL(redact_regions_kernel<false>, dim3(p.n), dim3(kThreads), 0, s, (const RedactArgs &)p);
 }
 void launch_redact_mean(hipStream_t s, const RedactParams &p) {
     if (p.n <= 0 || p.spec.mode != RF_REDACT_PIXELATE) return;
     redact_check(p);
-    hipLaunchKernelGGL(redact_mean_kernel, dim3(redact_grid(p)), dim3(kThreads), 0, s, p, redact_per_image(p));
+    hipLaunchKernelGGL(redact_mean_kernel, dim3(redact_grid(p)), dim3(kThreads), 0, s, (const RedactArgs &)p, redact_per_image(p));
 }
 void launch_redact_write(hipStream_t s, const RedactParams &p) {
     if (p.n <= 0) return;
     redact_check(p);
-    hipLaunchKernelGGL(redact_write_kernel, dim3(redact_grid(p)), dim3(kThreads), 0, s, p, redact_per_image(p));
+    hipLaunchKernelGGL(redact_write_kernel, dim3(redact_grid(p)), dim3(kThreads), 0, s, (const RedactArgs &)p, redact_per_image(p));
 }
 
 // =============================================================================================

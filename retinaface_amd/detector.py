@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (rf_face, rf_face_batch_spec, rf_face_gate, rf_face_quality, rf_options, rf_redact_spec, rf_tile_spec, rf_track,
-                   rf_pyramid_spec, rf_shot, rf_track_spec, rf_track_tag, rf_tta_spec)
+                   rf_motion_spec, rf_pyramid_spec, rf_shot, rf_track_motion, rf_track_spec, rf_track_tag, rf_tta_spec)
 
 PRECISION_FP32, PRECISION_FP16, PRECISION_INT8 = 0, 1, 2
 
@@ -247,12 +247,48 @@ def track_spec(max_tracks: int = 0, min_iou: float = 0.0, max_missed: int = 0, m
     return s
 
 
+# one rf_track_motion record (16 bytes)
+MOTION_DTYPE = np.dtype([("vx", "<f4"), ("vy", "<f4"), ("samples", "<i4"), ("reserved", "<i4")])
+
+
+def motion_spec(alpha: float = 0.0, horizon: int = 0) -> rf_motion_spec:
+    """rf_motion_spec; 0 = the default (alpha 0.5, horizon 8 frames; a negative horizon never extrapolates)"""
+    s = rf_motion_spec()
+    s.struct_size = C.sizeof(rf_motion_spec)
+    s.alpha, s.horizon, s.reserved = float(alpha), int(horizon), 0
+    return s
+
+
+def _as_motion_spec(spec):
+    if spec is None or isinstance(spec, rf_motion_spec):
+        return spec
+    return motion_spec(**spec)
+
+
+def track_predict(track, motion, ahead: int = 1, spec=None) -> np.ndarray:
+    """rf_track_predict (host only, no GPU): the predicted face (15 float32) of one live track (a TRACK_DTYPE record) with its
+    MOTION_DTYPE record, ahead = 0 (where redaction coasts) or 1 (where the next frame step matches); spec: motion_spec() or its
+    keywords as a dict."""
+    lib = _lib.load_library()
+    sp = _as_motion_spec(spec)
+    t = rf_track.from_buffer_copy(np.asarray(track, TRACK_DTYPE).tobytes())
+    m = rf_track_motion.from_buffer_copy(np.asarray(motion, MOTION_DTYPE).tobytes())
+    out = rf_face()
+    st = lib.rf_track_predict(C.byref(sp) if sp is not None else None, C.byref(t), C.byref(m), int(ahead), C.byref(out))
+    if st < 0:
+        raise _lib.RFError(st, "rf_track_predict: free slot, bad spec or argument")
+    return np.frombuffer(bytes(out), np.float32).copy()
+
+
 def track_step(table: np.ndarray, frames: int, next_id: int, faces, coord_scale: float = 1.0, quality=None, max_faces: int = 256,
-               cap_ended: Optional[int] = None, **spec):
+               cap_ended: Optional[int] = None, motion: Optional[np.ndarray] = None, mspec=None, **spec):
     """rf_track_step (host only, no GPU): one frame step on a caller-held table (TRACK_DTYPE records, updated in place).  Returns
-    (tags, ended, frames, next_id, truncated); keywords as track_spec()."""
+    (tags, ended, frames, next_id, truncated); keywords as track_spec().  motion: a MOTION_DTYPE array of len(table) records (updated
+    in place) makes it rf_track_step_motion; mspec: motion_spec() or its keywords as a dict."""
     lib = _lib.load_library()
     sp = track_spec(**spec)
+    if motion is not None and (motion.dtype != MOTION_DTYPE or len(motion) != len(table) or not motion.flags.c_contiguous):
+        raise ValueError("motion must be a contiguous MOTION_DTYPE array with one record per slot")
     rows = _face_rows(faces)
     count = len(rows)
     cap_ended = len(table) if cap_ended is None else int(cap_ended)
@@ -260,12 +296,18 @@ def track_step(table: np.ndarray, frames: int, next_id: int, faces, coord_scale:
     ended = np.zeros(max(cap_ended, 1), TRACK_DTYPE)
     f, nid, ne = C.c_int64(frames), C.c_int64(next_id), C.c_int(0)
     q = np.ascontiguousarray(quality, QUALITY_DTYPE) if quality is not None else None
-    st = lib.rf_track_step(C.byref(sp), table.ctypes.data_as(C.POINTER(rf_track)), C.byref(f), C.byref(nid),
-                           rows.ctypes.data_as(C.POINTER(rf_face)), count, float(coord_scale),
-                           q.ctypes.data_as(C.POINTER(rf_face_quality)) if q is not None else None, int(max_faces),
-                           tags.ctypes.data_as(C.POINTER(rf_track_tag)), ended.ctypes.data_as(C.POINTER(rf_track)), cap_ended, C.byref(ne))
+    head = (C.byref(sp), table.ctypes.data_as(C.POINTER(rf_track)))
+    tail = (C.byref(f), C.byref(nid), rows.ctypes.data_as(C.POINTER(rf_face)), count, float(coord_scale),
+            q.ctypes.data_as(C.POINTER(rf_face_quality)) if q is not None else None, int(max_faces),
+            tags.ctypes.data_as(C.POINTER(rf_track_tag)), ended.ctypes.data_as(C.POINTER(rf_track)), cap_ended, C.byref(ne))
+    if motion is None:
+        name, st = "rf_track_step", lib.rf_track_step(*head, *tail)
+    else:
+        msp = _as_motion_spec(mspec)
+        name, st = "rf_track_step_motion", lib.rf_track_step_motion(head[0], C.byref(msp) if msp is not None else None, head[1],
+                                                                    motion.ctypes.data_as(C.POINTER(rf_track_motion)), *tail)
     if st < 0 and st != _lib.RF_ERR_TRUNCATED:
-        raise _lib.RFError(st, "rf_track_step: bad spec or argument")
+        raise _lib.RFError(st, name + ": bad spec or argument")
     return tags[:count], ended[:min(ne.value, cap_ended)], f.value, nid.value, st == _lib.RF_ERR_TRUNCATED
 
 
@@ -326,8 +368,9 @@ class Tracker:
     tracked call last_tags ((n, cap) TRACK_TAG_DTYPE), last_ended ((n, cap_ended) TRACK_DTYPE) and last_ended_counts hold the call's
     whole buffers and truncated says whether a table was full or an ended list was cut."""
 
-    def __init__(self, det: "RetinaFace", n_streams: int, **spec):
+    def __init__(self, det: "RetinaFace", n_streams: int, motion=None, **spec):
         self._det, self._lib = det, det._lib
+        self.motion_spec = None
         self.spec = track_spec(**spec)
         self.max_tracks = self.spec.max_tracks or 64
         self.n_streams = int(n_streams)
@@ -336,6 +379,12 @@ class Tracker:
         self._t = t
         self.truncated = False
         self.last_tags = self.last_ended = self.last_ended_counts = None
+        if motion is not None:
+            try:
+                self.enable_motion(**({} if motion is True else motion))
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "_t", None) and getattr(self._det, "_h", None):
@@ -382,6 +431,21 @@ class Tracker:
                                                          mf, tags, ended, ce, ec), self._det._h)
         self.truncated = st == _lib.RF_ERR_TRUNCATED
         return self._results(n, counts, cap)
+
+    # ------------------------------------------------------------------ motion-predicted tracks
+    def enable_motion(self, **spec):
+        """rf_tracker_enable_motion: every tracked call then matches and coasts at the predicted boxes; keywords as motion_spec()"""
+        sp = motion_spec(**spec)
+        _lib.check(self._lib.rf_tracker_enable_motion(self._t, C.byref(sp)), self._det._h)
+        self.motion_spec = sp
+        return self
+
+    def read_motion(self, stream: int) -> np.ndarray:
+        """rf_tracker_read_motion: the (max_tracks,) MOTION_DTYPE records of a stream"""
+        rec = np.zeros(self.max_tracks, MOTION_DTYPE)
+        _lib.check(self._lib.rf_tracker_read_motion(self._t, int(stream), rec.ctypes.data_as(C.POINTER(rf_track_motion)), self.max_tracks),
+                   self._det._h)
+        return rec
 
     # ------------------------------------------------------------------ best-shot gallery
     def enable_shots(self, **spec):
@@ -1111,9 +1175,10 @@ class RetinaFace:
         return (self._collect_tiled(out, counts, src, n, cap, False),) + res
 
     # ------------------------------------------------------------------ face tracks
-    def tracker(self, n_streams: int = 1, **spec) -> Tracker:
-        """rf_tracker_create: a tracker on this handle; keywords as track_spec()"""
-        return Tracker(self, n_streams, **spec)
+    def tracker(self, n_streams: int = 1, motion=None, **spec) -> Tracker:
+        """rf_tracker_create: a tracker on this handle; keywords as track_spec().  motion: True or motion_spec()'s keywords as a dict
+        also gives it motion (Tracker.enable_motion)."""
+        return Tracker(self, n_streams, motion=motion, **spec)
 
     def _run_tracked(self, fn, ptrs, rows, cols, steps, n, threshold, tracker, streams, cap_ended):
         cap = self.max_detections
