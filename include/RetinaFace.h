@@ -144,7 +144,8 @@ public:
     vector<rf_track> flushShots(rf_tracker tracker, int stream, vector<uint8_t> *shots, vector<rf_shot> *info);
 
     /* additive: face redaction (rf_detect_redact_batch): detectBatchImages() plus redaction of the faces it finds, IN PLACE in the Mats'
-       pixels (pixelate or fill, rectangle or ellipse: rf_redact_spec; nullptr = the defaults).  Fills lastBatchResult();
+       pixels (pixelate, blur -- rf_redact_spec.blur -- or fill, rectangle or ellipse: rf_redact_spec; nullptr = the defaults).  Fills
+       lastBatchResult();
        redactedPixels()[i][k] is the number of pixels face k of image i owns. */
     void detectRedacted(vector<cv::Mat> &imgs, float threshold = 0.5, const rf_redact_spec *spec = nullptr);
     const vector<vector<int32_t>> &redactedPixels() const { return redactPixels_; }

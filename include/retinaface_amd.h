@@ -582,7 +582,7 @@ int rf_detect_track_shots_batch(rf_handle h, const uint8_t *const *bgr, const in
                                 const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_counts,
                                 const rf_face_gate *gate, rf_face_quality *quality, void *d_shots, void *shots, rf_shot *shot_info);
 
-/* ---- Face redaction: pixelate or fill the faces of a frame IN PLACE, on the device (DESIGN.md "Face redaction" holds the definition;
+/* ---- Face redaction: pixelate, blur or fill the faces of a frame IN PLACE, on the device (DESIGN.md "Face redaction" holds the definition;
  * tests/redact_ref.py restates it in numpy; every result is byte-exact against it).  Frames are CV_8UC3 BGR with any pointer and row step.
  *   region   of a face with box x1, y1, x2, y2 in a rows x cols frame, coord_scale s (fp32, one rounding per operation, never contracted):
  *            b = box * s (also for s = 1); w = bx2 - bx1, h = by2 - by1.  INVALID (owns no pixel) unless bx1, by1, bx2, by2, w, h are all
@@ -599,6 +599,15 @@ int rf_detect_track_shots_batch(rf_handle h, const uint8_t *const *bgr, const in
  *            their predicted boxes instead); cut at max_regions.  A pixel is OWNED by the
  *            lowest-indexed region whose mask covers it.  The output equals the input except at owned pixels, which take their owner's
  *            cell value (PIXELATE) or fill (FILL).  Every read is of the original frame.
+ *   blur     rf_redact_spec.blur = 1, 2 or 3 (PIXELATE only): an owned pixel takes the frame BLURRED instead of its cell's mean
+ *            (DESIGN.md "Blur redaction"; tests/redact_blur_ref.py).  The radius of a region is rho = min(c, 64).  One 1-D pass of
+ *            radius rho along an axis of length L maps u8 to u8 per channel: out[i] = (sum over d in [-rho, rho] of
+ *            in[clamp(i + d, 0, L - 1)] + rho) / (2 rho + 1), integer division: the rounded mean with the border replicated.  The
+ *            blurred frame is `blur` such passes along x on every row, then `blur` passes along y on every column (1: a box, 2: a
+ *            triangle, 3: close to a Gaussian of sigma rho), every intermediate u8, of the ORIGINAL frame (of a view: the view --
+ *            no byte outside cols * 3 of each row is read).  Region, mask, list, ownership and results are those above.  The blur
+ *            is selected by this byte and not by a third `mode` because mode = 2 has always been refused and callers rely on that;
+ *            blur > 3, or blur != 0 with RF_REDACT_FILL, is RF_ERR_INVALID_ARG like any bad spec.  blur = 0: exactly the above.
  *   results  pixels[i * max_regions + r] (may be NULL): the pixels region r owns; region_counts[i] (may be NULL): the length of the list
  *            before the cut (counts[i] + coasting tracks); a cut list returns RF_ERR_TRUNCATED. */
 enum { RF_REDACT_PIXELATE = 0, RF_REDACT_FILL = 1 };
@@ -610,23 +619,24 @@ typedef struct rf_redact_spec {   /* 32 bytes; a field of 0 means its default, a
     int32_t cells;          /* cells across the longer side of a region, 1..64; 0 = 8 */
     float margin;           /* the box grows by this fraction of its width / height on each side; finite and <= 1; 0 = 0.2; negative = 0 */
     uint8_t fill[3];        /* B, G, R of RF_REDACT_FILL */
-    uint8_t reserved;
+    uint8_t blur;           /* 0 = cell means; 1..3 (RF_REDACT_PIXELATE only) = box-blur passes per axis, radius min(c, 64) per region */
     int32_t max_regions;    /* regions per image, 1..1024; 0 = the engine's max_detections clamped to 1024 (256 without a handle) */
     int32_t coast;          /* with a tracker: also redact live tracks with 1 <= missed <= coast; 0 = the tracker's max_missed; negative = none */
 } rf_redact_spec;
 
 /* Host only, no GPU, no handle -- the same code the kernels run, compiled for the host.  rf_redact_region: out = ux0, uy0, ux1, uy1, the
  * clipped rectangle cx0, cy0, cx1, cy1 (cx1 <= cx0 or cy1 <= cy0: empty) and c; returns 1 (valid), 0 (invalid region: out is all zero)
- * or RF_ERR_INVALID_ARG (bad spec, NULL argument, rows or cols < 0). */
+ * or RF_ERR_INVALID_ARG (bad spec -- a bad spec->blur included --, NULL argument, rows or cols < 0).  With spec->blur set the region is
+ * the same; its blur radius is min(c, 64). */
 int rf_redact_region(const rf_redact_spec *spec, const rf_face *face, float coord_scale, int rows, int cols, int out[9]);
 /* Redacts a whole frame in place in HOST memory (the CPU counterpart of rf_redact_device for one image without a tracker; a usable
- * fallback).  pixels: min(count, max_regions) counts, may be NULL.  Returns 0, RF_ERR_TRUNCATED (count > max_regions: the first
+ * fallback; spec->blur as on the device, same bytes).  pixels: min(count, max_regions) counts, may be NULL.  Returns 0, RF_ERR_TRUNCATED (count > max_regions: the first
  * max_regions faces were redacted) or RF_ERR_INVALID_ARG, which changes nothing. */
 int rf_redact_host(const rf_redact_spec *spec, uint8_t *bgr, int rows, int cols, int step, const rf_face *faces, int count,
                    float coord_scale, int32_t *pixels);
 
 /* Redacts faces the CALLER supplies (host memory: faces[i * cap_per_image + k], k < counts[i] <= cap_per_image) in place in
- * device-resident frames; no forward pass runs.  coord_scale: per image, NULL = 1 -- a tiled caller follows rf_detect_tiled_batch_device
+ * device-resident frames (pixelated, blurred with spec->blur, or filled); no forward pass runs.  coord_scale: per image, NULL = 1 -- a tiled caller follows rf_detect_tiled_batch_device
  * with this call and coord_scale NULL (the tiled calls, the asynchronous tickets and rf_detect_batch_pad32 have no redacting form).
  * tracker may be NULL; with one, stream_of_image[i] names the stream whose coasting tracks (the tracker's CURRENT table) are redacted in
  * image i, -1 = faces only; a stream may appear at most once per call.  A NULL / 0 x 0 frame is skipped (no regions).  Refused before
@@ -644,7 +654,8 @@ int rf_redact_last_launch_ms(rf_handle h, float *ms);
 /* rf_detect_batch_device + redaction of what it finds, in one call: detection runs exactly as there (out / counts /
  * rf_last_anchor_indices are the same bytes); the redaction launches follow each detection launch on its stream and read the faces from
  * the device-visible result block -- no host synchronisation in between.  coord_scale is each frame's rf_frame_scale, so an oversize
- * frame is redacted at its full source resolution.  n may exceed max_batch.  pixels: n * max_regions, may be NULL.  Refusals as above. */
+ * frame is redacted at its full source resolution.  n may exceed max_batch.  pixels: n * max_regions, may be NULL.  Refusals as above.
+ * spec->blur selects the blur here and in the two calls below as in rf_redact_device. */
 int rf_detect_redact_batch_device(rf_handle h, void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
                                   float threshold, rf_face *out, int cap_per_image, int *counts, const rf_redact_spec *spec,
                                   int32_t *pixels);

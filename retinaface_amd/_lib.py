@@ -91,7 +91,7 @@ RF_SHOT_MAX_BYTES = 1 << 30
 
 class rf_redact_spec(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("shape", C.c_int32), ("cells", C.c_int32), ("margin", C.c_float),
-                ("fill", C.c_uint8 * 3), ("reserved", C.c_uint8), ("max_regions", C.c_int32), ("coast", C.c_int32)]
+                ("fill", C.c_uint8 * 3), ("blur", C.c_uint8), ("max_regions", C.c_int32), ("coast", C.c_int32)]
 
 
 RF_REDACT_PIXELATE, RF_REDACT_FILL = 0, 1

@@ -209,7 +209,7 @@ public:
         if (align_stream_) { (void)hipStreamSynchronize(align_stream_); (void)hipStreamDestroy(align_stream_); }
         for (DeviceScratch *b : {&align_crops_, &align_mats_, &align_tab_, &fb_state_, &fq_records_, &fq_packed_, &fq_offsets_, &tile_cand_, &tile_count_, &tile_out_,
                                  &tile_outcount_, &tile_tab_, &tile_frames_, &tta_cand_, &tta_count_, &tta_frames_, &tta_mirror_, &pyr_frames_, &pyr_zoom_,
-                                 &red_regions_, &red_counts_, &red_cells_, &red_frames_}) b->release();
+                                 &red_regions_, &red_counts_, &red_cells_, &red_frames_, &red_shadow_}) b->release();
         for (HostScratch *b : {&trk_tags_, &trk_ended_, &trk_counts_, &tta_out_, &tta_votes_, &tta_outcount_, &shot_out_, &shot_info_}) b->release();
         for (auto &t : trackers_) t->release();
         for (hipEvent_t e : trk_ev_) if (e) (void)hipEventDestroy(e);
@@ -1714,12 +1714,25 @@ public:
     }
 
     // device blocks of a redacting call, sized once and reused; the region counts (after | before the cut) and the owned-pixel counts
-    // share one block, so the results of a call come back in one copy
-    void redact_open(const RedactRequest &rq, void *tracker, int n) {
+    // share one block, so the results of a call come back in one copy.  A blurring call also gets its shadow: behind a table of one
+    // offset per call image, rows x cols x 3 bytes for every frame of the call -- sized from what the host knows, whatever the faces
+    // turn out to be; the block grows to the largest call seen.  (No launch of an earlier call is in flight: every redacting call
+    // waits for its last launch before it returns.)
+    void redact_open(const RedactRequest &rq, void *tracker, int n, const uint8_t *const *frames, const int *rows, const int *cols) {
         const size_t slots = (size_t)std::max(n, 1) * rq.spec.max_regions;
         red_regions_.reserve(slots * sizeof(RedactRegion));
         red_counts_.reserve(((size_t)std::max(n, 1) * 2 + slots) * sizeof(int));
-        if (rq.spec.mode == RF_REDACT_PIXELATE) red_cells_.reserve(slots * rq.spec.cells * rq.spec.cells * sizeof(uint32_t));
+        if (rq.spec.mode == RF_REDACT_PIXELATE && !rq.spec.blur) red_cells_.reserve(slots * rq.spec.cells * rq.spec.cells * sizeof(uint32_t));
+        if (rq.spec.blur && n > 0) {
+            red_shadow_off_.assign((size_t)n, 0);
+            size_t bytes = align256((size_t)n * sizeof(unsigned long long));
+            for (int i = 0; i < n; i++) {
+                red_shadow_off_[i] = bytes;
+                if (frames[i] && rows[i] > 0 && cols[i] > 0) bytes += align256((size_t)rows[i] * cols[i] * 3);
+            }
+            uint8_t *d = red_shadow_.reserve(bytes);
+            RF_HIP(hipMemcpy(d, red_shadow_off_.data(), (size_t)n * sizeof(unsigned long long), hipMemcpyHostToDevice));
+        }
         red_.spec = rq.spec; red_.tr = tracker ? &tracker_of(tracker) : nullptr; red_.stream_of_image = rq.stream_of_image;
         red_.n = n; red_.next_image = 0;
     }
@@ -1737,11 +1750,13 @@ public:
         rp.nreg = (int *)red_counts_.ptr; rp.true_counts = (int *)red_counts_.ptr + std::max(red_.n, 1);
         rp.cell_values = (uint32_t *)red_cells_.ptr;
         rp.pixels = (int *)red_counts_.ptr + 2 * std::max(red_.n, 1);
+        if (red_.spec.blur) { rp.shadow = red_shadow_.ptr; rp.shadow_off = (const unsigned long long *)red_shadow_.ptr; }
         return rp;
     }
     static void redact_launch(hipStream_t st, const RedactParams &rp) {
         launch_redact_regions(st, rp);
-        launch_redact_mean(st, rp);
+        if (rp.spec.blur) launch_redact_blur(st, rp);
+        else launch_redact_mean(st, rp);
         launch_redact_write(st, rp);
     }
     // results of a finished redacting call (the host has waited for its last launch)
@@ -1788,7 +1803,7 @@ public:
             if (c) memcpy(align_host_.data() + o_face + (size_t)i * fpi * sizeof(rf_face), faces + (size_t)i * cap_per_image, (size_t)c * sizeof(rf_face));
         }
         uint8_t *d_tab = align_tab_.reserve(total);
-        redact_open(rq, t, n);
+        redact_open(rq, t, n, (const uint8_t *const *)frames, rows, cols);
         if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
         RF_HIP(hipMemcpyAsync(d_tab, align_host_.data(), total, hipMemcpyHostToDevice, align_stream_));
         RedactParams rp = redact_params();
@@ -1844,7 +1859,7 @@ public:
         }
         // as in detect_align(): a super-batch of earlier enqueues starts now, every later launch carries images of this call only
         launch_pending();
-        redact_open(rq, nullptr, n);
+        redact_open(rq, nullptr, n, dev.data(), rows, cols);
         red_.on = n > 0;
         struct Off { bool &on; ~Off() { on = false; } } off_guard{red_.on};
         detect(dev.data(), rows, cols, st.data(), n, true, threshold, out, cap_per_image, counts, truncated);
@@ -1871,7 +1886,7 @@ public:
         launch_pending();
         track_open_call(t, trq, n, cap_per_image);
         trk_.records = nullptr; trk_.max_faces = kTrackMaxFaces;
-        redact_open(rq, rq.tracker, n);
+        redact_open(rq, rq.tracker, n, frames, rows, cols);
         t.dirty = true;
         trk_.on = n > 0; red_.on = n > 0;
         struct Off { bool &a, &b; ~Off() { a = false; b = false; } } off{trk_.on, red_.on};
@@ -3150,6 +3165,8 @@ private:
     // face redaction: region records, region counts (after | before the cut) + owned-pixel counts, and cell values of the call's
     // images, the device copy of host frames; the request a redacting call has open
     DeviceScratch red_regions_, red_counts_, red_cells_, red_frames_;
+    DeviceScratch red_shadow_;                    // a blurring call: offset table | the blurred owned pixels of every frame of the call
+    std::vector<unsigned long long> red_shadow_off_;
     std::vector<int> red_host_;
     struct { bool on = false; RedactSpec spec; Tracker *tr = nullptr; const int *stream_of_image = nullptr; int n = 0, next_image = 0; } red_;
 

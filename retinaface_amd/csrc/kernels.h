@@ -338,7 +338,7 @@ void launch_shot_keep(hipStream_t s, const ShotParams &p);
 
 // ---- K_k: face redaction (redact.h) -- in place in the frames of a launch, in three launches ordered on the stream.
 //      launch_redact_regions: one workgroup per image turns its faces, and with a tracker its stream's coasting tracks, into region
-//      records.  launch_redact_mean (PIXELATE only) reads the frames and writes every region's cell values; launch_redact_write reads
+//      records.  launch_redact_mean (PIXELATE without blur) reads the frames and writes every region's cell values; launch_redact_write reads
 //      only those, the records and the spec and writes the pixels each region owns.  Every pointer is device-visible memory (the fused
 //      calls read faces and counts from the pinned result block the NMS kernel wrote).
 struct RedactArgs {                       // what the three kernels take
@@ -358,6 +358,8 @@ struct RedactArgs {                       // what the three kernels take
     int *true_counts;                     // [call images] ... before the cut
     uint32_t *cell_values;                // region slot q = c * max_regions + r, cell (gx, gy): cell_values[(q * cells + gy) * cells + gx]
     int *pixels;                          // [call images * max_regions] pixels each region owns (zeroed by launch_redact_regions)
+    uint8_t *shadow;                      // spec.blur only: call image c's blurred owned pixels, dense cols * 3 bytes per row, at
+    const unsigned long long *shadow_off; //   shadow + shadow_off[c]; every byte has one writer (its pixel's owner)
 };
 // With a motion pointer launch_redact_regions runs the coasting-box variant of its kernel: a coasting track is redacted at its predicted
 // box for h = min(missed, horizon) (motion.h) instead of where it was last seen.
@@ -367,6 +369,9 @@ struct RedactParams : RedactArgs {
 };
 void launch_redact_regions(hipStream_t s, const RedactParams &p);
 void launch_redact_mean(hipStream_t s, const RedactParams &p);
+// spec.blur: takes the place of launch_redact_mean -- reads the frames and writes the blurred value of every owned pixel into the
+// shadow; launch_redact_write then copies owned pixels from the shadow into the frame
+void launch_redact_blur(hipStream_t s, const RedactParams &p);
 void launch_redact_write(hipStream_t s, const RedactParams &p);
 
 // ---- K_j: flip test-time augmentation (tta.h).

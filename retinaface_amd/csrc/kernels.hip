@@ -5237,6 +5237,9 @@ __global__ __launch_bounds__(kThreads) void redact_mean_kernel(RedactArgs a, int
 // prefix, the gather kernel's idiom), then every pixel of it is tested: inside the region's own mask and inside no gathered
 // one = owned.  Owned pixels get their cell's value (or the fill) with three ordinary byte stores; the owned count is reduced over
 // the workgroup and added to the region's counter with one integer atomicAdd.
+// kBlur: the value of an owned pixel is the one redact_blur_kernel left for it in the shadow; the plain instantiation is the kernel
+// as it always was.
+template <bool kBlur>
 __global__ __launch_bounds__(kThreads) void redact_write_kernel(RedactArgs a, int per_image) {
     __shared__ int s_low[kRedactMaxRegions][8];                   // ux0, uy0, ux1, uy1, cx0, cy0, cx1, cy1 of a lower region: 32 KB
     __shared__ int s_cnt[kThreads / 64];
@@ -5276,7 +5279,10 @@ __global__ __launch_bounds__(kThreads) void redact_write_kernel(RedactArgs a, in
             }
             __syncthreads();
             const int bw = bx1 - bx0, npix = bw * (by1 - by0);
-            const uint32_t v = fill_mode ? fill : a.cell_values[(((size_t)image * M + r) * C + gy) * C + gx];
+            uint32_t v = fill;
+            if constexpr (!kBlur) v = fill_mode ? fill : a.cell_values[(((size_t)image * M + r) * C + gy) * C + gx];
+            const uint8_t *shadow = nullptr;
+            if constexpr (kBlur) shadow = a.shadow + a.shadow_off[image];
             int owned = 0;
             for (int idx = tid; idx < npix; idx += kThreads) {
                 const int yy = idx / bw, x = bx0 + idx - yy * bw, y = by0 + yy;
@@ -5291,7 +5297,12 @@ __global__ __launch_bounds__(kThreads) void redact_write_kernel(RedactArgs a, in
                 }
                 if (lower) continue;
                 uint8_t *p = (uint8_t *)fd.ptr + (size_t)y * fd.step + (size_t)3 * x;
-                p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16);
+                if constexpr (kBlur) {
+                    const uint8_t *b = shadow + ((size_t)y * fd.cols + x) * 3;
+                    p[0] = b[0]; p[1] = b[1]; p[2] = b[2];
+                } else {
+                    p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16);
+                }
                 owned++;
             }
             for (int d = 32; d >= 1; d >>= 1) owned += __shfl_xor(owned, d, 64);
@@ -5307,10 +5318,213 @@ __global__ __launch_bounds__(kThreads) void redact_write_kernel(RedactArgs a, in
     }
 }
 
+// ---- the blur (RedactSpec::blur = P box passes per axis, radius rho = min(c, 64) per region; redact.h).  redact_blur_kernel takes the
+// place of the mean kernel: it only READS frames and writes the blurred value of every OWNED pixel into the call's shadow (one byte,
+// one writer); redact_write_kernel<true> then copies owned pixels from the shadow into the frame.
+//   Item = a tile of kBlurTileW x kBlurTileH pixels of a region's clipped rectangle.  A tile's values depend on originals up to
+//   halo = P * rho away.  The x passes need the horizontal halo only, so they run on batches of rows staged in s_row (tw + 2 halo
+//   pixels each; as many rows as fit), and what they leave -- tw pixels of each of th + 2 halo rows -- is collected in s_col, where
+//   the y passes run.  Rows and columns outside the frame are replicas of its border rows and columns, as the definition's clamp
+//   makes them, before the first pass and after every pass but the last.
+//   A pass is a running sum, serial along its axis and O(1) per element, one chain per (row, channel) resp. (column, channel) dealt
+//   over the threads.  It runs in place: out[i] needs in[i - rho .. i + rho], the step to out[i + 1] adds in[i + rho + 1] and drops
+//   in[i - rho], and in[i - rho - 1] is dead by then, so out[i] goes where in[i - rho - 1] was.  Each pass therefore moves the line
+//   rho + 1 slots down and loses rho elements at either end; a line starts P slots into its buffer and the tile's own elements end
+//   at slot 0.  Sums are at most 255 * 129 (redact_blur_mean); the division is the exact multiply of redact.h.
+//   LDS: s_col (64 + 2 * 192 + 3) rows x 96 bytes = 43 296, s_row 20 096, the gathered lower regions as 16-bit indices 2 048:
+//   65 456 bytes with s_cnt, under the 64 KB that need no launch attribute, one workgroup per CU at a time.  At rho = 64, P = 3 a
+//   batch is 15 rows (45 chains); at the default cells a 140-pixel face has rho = 18 and a batch of 47 rows (141 chains).
+constexpr int kBlurTileW = 32, kBlurTileH = 64;
+constexpr int kBlurMaxHalo = kRedactMaxBlurPasses * kRedactMaxBlurRadius;
+constexpr int kBlurColPitch = kBlurTileW * 3;
+constexpr int kBlurColRows = kBlurTileH + 2 * kBlurMaxHalo + kRedactMaxBlurPasses;
+constexpr int kBlurRowBytes = 20096;
+static_assert(kBlurColRows * kBlurColPitch + kBlurRowBytes + kRedactMaxRegions * 2 + (kThreads / 64) * 4 <= 65536, "static LDS of redact_blur_kernel");
+static_assert(kBlurRowBytes >= 3 * (kBlurTileW + 2 * kBlurMaxHalo + kRedactMaxBlurPasses) + 8, "s_row holds at least one row");
+
+// The P passes of one chain.  e: the chain's slot 0; slot s is e[s * stride].  The line has n elements; element i is coordinate v0 + i
+// of an axis of length L and sits in slot i + P.  Elements outside [0, L) hold their clamped neighbour's value on entry.  On return
+// element i of [P * rho, n - P * rho) is in slot i - P * rho.
+__device__ inline void redact_blur_chain(uint8_t *e, int stride, int n, int v0, int L, int P, int rho, uint32_t magic) {
+    int off = P, lo = 0, hi = n;
+    const int i0 = -v0, i1 = L - 1 - v0;                         // the elements that are coordinates 0 and L - 1
+    for (int k = 0; k < P; k++) {
+        uint32_t s = 0;
+#pragma unroll 8
+        for (int i = lo; i <= lo + 2 * rho; i++) s += e[(i + off) * stride];
+        const int end = hi - rho, noff = off - rho - 1;
+        int i = lo + rho;
+        // Eight steps at a time: the sixteen taps they add and drop are read before the first of their eight writes.  A write goes to
+        // the slot whose tap was dropped one step earlier, below every tap still to be read, so the order changes no value -- but as
+        // one loop of read, read, write the compiler must keep every LDS round trip in order, and a step costs three of them.
+        while (i + 8 < end) {
+            uint32_t add[8], drop[8];
+#pragma unroll
+            for (int j = 0; j < 8; j++) { add[j] = e[(i + 1 + j + rho + off) * stride]; drop[j] = e[(i + j - rho + off) * stride]; }
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                e[(i + j + noff) * stride] = (uint8_t)redact_blur_mean(s, rho, magic);
+                s += add[j];
+                s -= drop[j];
+            }
+            i += 8;
+        }
+        for (;;) {
+            e[(i + noff) * stride] = (uint8_t)redact_blur_mean(s, rho, magic);
+            if (++i >= end) break;
+            s += e[(i + rho + off) * stride];
+            s -= e[(i - rho - 1 + off) * stride];
+        }
+        lo += rho; hi -= rho; off = noff;
+        if (k + 1 < P) {                                          // outside the axis: the clamped neighbour's value
+            if (lo < i0) { const uint8_t v = e[(i0 + off) * stride]; for (int i = lo; i < i0; i++) e[(i + off) * stride] = v; }
+            if (hi - 1 > i1) { const uint8_t v = e[(i1 + off) * stride]; for (int i = i1 + 1; i < hi; i++) e[(i + off) * stride] = v; }
+        }
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void redact_blur_kernel(RedactArgs a, int per_image) {
+    __shared__ __attribute__((aligned(16))) uint8_t s_col[kBlurColRows * kBlurColPitch];
+    __shared__ __attribute__((aligned(16))) uint8_t s_row[kBlurRowBytes];
+    __shared__ uint16_t s_low[kRedactMaxRegions];                 // the lower regions that meet the tile, in index order
+    __shared__ int s_cnt[kThreads / 64];
+    const int tid = (int)threadIdx.x;
+    const int M = a.spec.max_regions, shape = a.spec.shape, P = a.spec.blur;
+    for (int w = blockIdx.x; w < a.n * per_image; w += gridDim.x) {
+        const int i = w / per_image, slot = w - i * per_image;
+        const int image = a.image0 + i;
+        const int nreg = a.nreg[image];
+        if (nreg <= 0) continue;                                  // nothing to do: one read
+        const FrameDesc fd = a.frames[i];
+        const RedactRegion *regs = a.regions + (size_t)image * M;
+        uint8_t *shadow = a.shadow + a.shadow_off[image];
+        int base = 0;                                             // tiles of the regions before r, modulo per_image
+        for (int r = 0; r < nreg; r++) {
+            const RedactRegion reg = regs[r];
+            if (redact_clip_empty(reg)) continue;
+            const int ntx = (reg.cx1 - reg.cx0 + kBlurTileW - 1) / kBlurTileW, nty = (reg.cy1 - reg.cy0 + kBlurTileH - 1) / kBlurTileH;
+            const int nt = ntx * nty;                             // at most 128 * 48
+            int first = slot - base;
+            if (first < 0) first += per_image;
+            base = (base + nt) % per_image;
+            const int rho = redact_blur_radius(reg), halo = P * rho;
+            const uint32_t magic = redact_blur_magic(rho);
+            for (int t = first; t < nt; t += per_image) {         // workgroup-uniform
+                const int ty = t / ntx, tx = t - ty * ntx;
+                const int x0 = reg.cx0 + tx * kBlurTileW, y0 = reg.cy0 + ty * kBlurTileH;
+                const int x1 = x0 + kBlurTileW < reg.cx1 ? x0 + kBlurTileW : reg.cx1, y1 = y0 + kBlurTileH < reg.cy1 ? y0 + kBlurTileH : reg.cy1;
+                const int tw = x1 - x0, th = y1 - y0;
+                // the lower regions whose clipped rectangles meet the tile
+                int nlow = 0;
+                for (int q0 = 0; q0 < r; q0 += kThreads) {
+                    const int q = q0 + tid;
+                    bool meets = false;
+                    if (q < r) {
+                        const RedactRegion o = regs[q];
+                        meets = !redact_clip_empty(o) && o.cx0 < x1 && o.cx1 > x0 && o.cy0 < y1 && o.cy1 > y0;
+                    }
+                    int total = 0;
+                    const int pos = track_prefix_count(meets, kThreads / 64, s_cnt, &total);
+                    if (meets) s_low[nlow + pos] = (uint16_t)q;
+                    nlow += total;
+                }
+                // ---- x passes, a batch of rows at a time
+                const int X0 = x0 - halo, Y0 = y0 - halo;         // coordinates of element 0 of a row / a column
+                const int nx = tw + 2 * halo, ny = th + 2 * halo;
+                int pitch = (3 * (nx + P) + 3) & ~3;
+                if (!(pitch & 4)) pitch += 4;                     // an odd number of dwords: the chains of a batch spread over the banks
+                const int batch = kBlurRowBytes / pitch;
+                const int fx0 = X0 > 0 ? X0 : 0, fx1 = X0 + nx < fd.cols ? X0 + nx : fd.cols;      // the part of a row inside the frame
+                const int nb = 3 * (fx1 - fx0);                   // >= 3 * tw
+                const int ndmax = (nb + 3) / 4 + 1;
+                const int lead = 3 * (fx0 - X0 + P);              // byte of a row buffer where the frame's part starts
+                const int nl = fx0 - X0, nr = X0 + nx - fx1;      // replicated columns left and right
+                for (int rb = 0; rb < ny; rb += batch) {
+                    const int rows_here = ny - rb < batch ? ny - rb : batch;
+                    __syncthreads();                              // the previous batch has left s_row; s_low is complete
+                    // four dwords per thread at a time, their loads issued before the first of them is stored
+                    for (int idx0 = tid; idx0 < rows_here * ndmax; idx0 += 4 * kThreads) {
+                        const uint8_t *src[4];
+                        uint8_t *dst[4];
+                        uint32_t v[4];
+                        int off4[4];
+                        bool live[4], whole[4];
+#pragma unroll
+                        for (int u = 0; u < 4; u++) {
+                            const int idx = idx0 + u * kThreads;
+                            live[u] = idx < rows_here * ndmax;
+                            const int j = live[u] ? idx / ndmax : 0, d = live[u] ? idx - j * ndmax : 0;
+                            const int y = redact_blur_clamp(Y0 + rb + j, fd.rows);
+                            const uint8_t *p = fd.ptr + (size_t)y * fd.step + (size_t)3 * fx0;
+                            const int jj = 4 * d - (int)((uintptr_t)p & 3);   // span offset of the aligned dword's first byte
+                            src[u] = p + jj; dst[u] = s_row + j * pitch + lead + jj; off4[u] = jj;
+                            whole[u] = live[u] && jj >= 0 && jj + 4 <= nb;
+                            v[u] = whole[u] ? *(const uint32_t *)src[u] : 0u;
+                            if (live[u] && !whole[u])             // an end of the span: bytewise, nothing outside it is touched
+                                for (int k = 0; k < 4; k++)
+                                    if (jj + k >= 0 && jj + k < nb) v[u] |= (uint32_t)src[u][k] << (8 * k);
+                            live[u] = live[u] && jj + 4 > 0 && jj < nb;
+                        }
+#pragma unroll
+                        for (int u = 0; u < 4; u++) {
+                            if (whole[u]) {
+                                dst[u][0] = (uint8_t)v[u]; dst[u][1] = (uint8_t)(v[u] >> 8); dst[u][2] = (uint8_t)(v[u] >> 16); dst[u][3] = (uint8_t)(v[u] >> 24);
+                            } else if (live[u]) {
+                                for (int k = 0; k < 4; k++)
+                                    if (off4[u] + k >= 0 && off4[u] + k < nb) dst[u][k] = (uint8_t)(v[u] >> (8 * k));
+                            }
+                        }
+                    }
+                    if (nl + nr > 0) {
+                        __syncthreads();
+                        for (int idx = tid; idx < rows_here * (nl + nr) * 3; idx += kThreads) {
+                            const int j = idx / ((nl + nr) * 3), rest = idx - j * (nl + nr) * 3, c = rest / 3, ch = rest - c * 3;
+                            uint8_t *row = s_row + j * pitch;
+                            if (c < nl) row[3 * (c + P) + ch] = row[lead + ch];
+                            else row[lead + nb + 3 * (c - nl) + ch] = row[lead + nb - 3 + ch];
+                        }
+                    }
+                    __syncthreads();
+                    for (int chain = tid; chain < rows_here * 3; chain += kThreads) {
+                        const int j = chain / 3, ch = chain - j * 3;
+                        redact_blur_chain(s_row + j * pitch + ch, 3, nx, X0, fd.cols, P, rho, magic);
+                    }
+                    __syncthreads();
+                    const int cw = (tw * 3 + 3) / 4;              // dwords of a finished row (both pitches are multiples of 4; what a
+#pragma unroll 4                                                  // last dword carries beyond 3 tw bytes lands in columns no chain reads)
+                    for (int idx = tid; idx < rows_here * cw; idx += kThreads) {
+                        const int j = idx / cw, b = idx - j * cw;
+                        ((uint32_t *)(s_col + (rb + j + P) * kBlurColPitch))[b] = ((const uint32_t *)(s_row + j * pitch))[b];
+                    }
+                }
+                __syncthreads();
+                // ---- y passes: one chain per byte of a tile row
+                if (tid < tw * 3) redact_blur_chain(s_col + tid, kBlurColPitch, ny, Y0, fd.rows, P, rho, magic);
+                __syncthreads();
+                // ---- the owned pixels of the tile go to the shadow
+                for (int idx = tid; idx < tw * th; idx += kThreads) {
+                    const int yy = idx / tw, xx = idx - yy * tw, x = x0 + xx, y = y0 + yy;
+                    if (!redact_covers(reg, shape, x, y)) continue;
+                    bool lower = false;
+                    for (int k = 0; k < nlow && !lower; k++) lower = redact_covers(regs[s_low[k]], shape, x, y);
+                    if (lower) continue;
+                    const uint8_t *v = s_col + yy * kBlurColPitch + 3 * xx;
+                    uint8_t *o = shadow + ((size_t)y * fd.cols + x) * 3;
+                    o[0] = v[0]; o[1] = v[1]; o[2] = v[2];
+                }
+                __syncthreads();                                  // s_col and s_low are free for the next tile
+            }
+        }
+    }
+}
+
 static void redact_check(const RedactParams &p) {
     if (p.spec.max_regions < 1 || p.spec.max_regions > kRedactMaxRegions) throw LaunchUnsupported("redact: max_regions must be in [1, 1024]");
     if (p.spec.cells < 1 || p.spec.cells > kRedactMaxCells) throw LaunchUnsupported("redact: cells must be in [1, 64]");
     if (p.track_state && (p.max_tracks < 1 || p.max_tracks > kTrackMaxTracks)) throw LaunchUnsupported("redact: max_tracks must be in [1, 256]");
+    if (p.spec.blur < 0 || p.spec.blur > kRedactMaxBlurPasses || (p.spec.blur && p.spec.mode != RF_REDACT_PIXELATE))
+        throw LaunchUnsupported("redact: blur must be in [0, 3] and needs PIXELATE");
+    if (p.spec.blur && (!p.shadow || !p.shadow_off)) throw LaunchUnsupported("redact: a blurring launch needs its shadow");
 }
 static int redact_per_image(const RedactParams &p) {
     const int items = p.spec.max_regions * p.spec.cells * p.spec.cells;
@@ -5328,14 +5542,22 @@ void launch_redact_regions(hipStream_t s, const RedactParams &p) {
     else hipLaunchKernelGGL(redact_regions_kernel<false>, dim3(p.n), dim3(kThreads), 0, s, (const RedactArgs &)p);
 }
 void launch_redact_mean(hipStream_t s, const RedactParams &p) {
-    if (p.n <= 0 || p.spec.mode != RF_REDACT_PIXELATE) return;
+    if (p.n <= 0 || p.spec.mode != RF_REDACT_PIXELATE || p.spec.blur) return;
     redact_check(p);
     hipLaunchKernelGGL(redact_mean_kernel, dim3(redact_grid(p)), dim3(kThreads), 0, s, (const RedactArgs &)p, redact_per_image(p));
+}
+void launch_redact_blur(hipStream_t s, const RedactParams &p) {
+    if (p.n <= 0 || !p.spec.blur) return;
+    redact_check(p);
+    const long total = (long)p.n * kRedactItemsPerImage;
+    hipLaunchKernelGGL(redact_blur_kernel, dim3((int)(total < kRedactMaxGrid ? total : kRedactMaxGrid)), dim3(kThreads), 0, s, (const RedactArgs &)p,
+                       kRedactItemsPerImage);
 }
 void launch_redact_write(hipStream_t s, const RedactParams &p) {
     if (p.n <= 0) return;
     redact_check(p);
-    hipLaunchKernelGGL(redact_write_kernel, dim3(redact_grid(p)), dim3(kThreads), 0, s, (const RedactArgs &)p, redact_per_image(p));
+    if (p.spec.blur) hipLaunchKernelGGL(redact_write_kernel<true>, dim3(redact_grid(p)), dim3(kThreads), 0, s, (const RedactArgs &)p, redact_per_image(p));
+    else hipLaunchKernelGGL(redact_write_kernel<false>, dim3(redact_grid(p)), dim3(kThreads), 0, s, (const RedactArgs &)p, redact_per_image(p));
 }
 
 // =============================================================================================

@@ -1,9 +1,10 @@
 // redact.h -- face redaction, shared by the kernels (kernels.hip redact_*_kernel), the host entry points rf_redact_region /
 // rf_redact_host (capi.cpp) and the engine.  A face's box grows by a margin and becomes an integer REGION; a region's MASK is its
 // rectangle or the ellipse inscribed in it; PIXELATE replaces every pixel a region owns by the rounded mean of its CELL, FILL by a
-// constant (DESIGN.md "Face redaction").  The floating-point part (redact_region_make) is fp32 with one rounding per operation (never
+// constant (DESIGN.md "Face redaction"); with RedactSpec::blur a PIXELATE region's pixels take the box-BLURRED frame instead (DESIGN.md
+// "Blur redaction").  The floating-point part (redact_region_make) is fp32 with one rounding per operation (never
 // contracted); everything after it is integer arithmetic, so host and device agree bit for bit with each other and with
-// tests/redact_ref.py.  The host runs the pieces below in sequential loops (redact_host_frame); the kernels run the same pieces one
+// tests/redact_ref.py / tests/redact_blur_ref.py.  The host runs the pieces below in sequential loops (redact_host_frame); the kernels run the same pieces one
 // thread per pixel or per span of bytes.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -19,6 +20,8 @@ namespace rf {
 
 constexpr int kRedactMaxRegions = 1024;    // regions per image
 constexpr int kRedactMaxCells = 64;        // cells across the longer side of a region
+constexpr int kRedactMaxBlurRadius = 64;   // box radius of a blurred region, min(c, 64)
+constexpr int kRedactMaxBlurPasses = 3;    // box passes per axis
 static_assert(sizeof(rf_redact_spec) == 32, "rf_redact_spec is 32 bytes");
 
 // a validated rf_redact_spec with its defaults applied
@@ -29,6 +32,7 @@ struct RedactSpec {
     uint8_t fill[4] = {0, 0, 0, 0};        // B, G, R, unused
     int max_regions = 256;
     int coast = 0;                         // as the caller gave it: 0 = the tracker's max_missed, negative = none (redact_coast)
+    int blur = 0;                          // 0 = cell means; 1..3 = box passes per axis of the blur (PIXELATE only)
 };
 
 // A region: the unclipped rectangle [ux0, ux1) x [uy0, uy1), its intersection with the frame [cx0, cx1) x [cy0, cy1) (empty when
@@ -50,12 +54,15 @@ inline const char *redact_spec_resolve(const rf_redact_spec *in, int default_reg
         if (in->cells < 0 || in->cells > kRedactMaxCells) return "cells must be 0 or in [1, 64]";
         if (!redact_finite(in->margin) || in->margin > 1.f) return "margin must be finite and <= 1 (0 = 0.2, negative = 0)";
         if (in->max_regions < 0 || in->max_regions > kRedactMaxRegions) return "max_regions must be 0 or in [1, 1024]";
+        if (in->blur > kRedactMaxBlurPasses) return "blur must be 0 (cell means) or 1, 2, 3 (box passes per axis)";
+        if (in->blur && in->mode != RF_REDACT_PIXELATE) return "blur needs RF_REDACT_PIXELATE";
         r.mode = in->mode; r.shape = in->shape;
         if (in->cells) r.cells = in->cells;
         if (in->margin != 0.f) r.margin = in->margin < 0.f ? 0.f : in->margin;
         r.fill[0] = in->fill[0]; r.fill[1] = in->fill[1]; r.fill[2] = in->fill[2];
         if (in->max_regions) r.max_regions = in->max_regions;
         r.coast = in->coast;
+        r.blur = in->blur;
     }
     *out = r;
     return nullptr;
@@ -123,12 +130,74 @@ __host__ __device__ inline uint32_t redact_cell_value(uint32_t sb, uint32_t sg, 
     return ((sb + h) / n) | (((sg + h) / n) << 8) | (((sr + h) / n) << 16);
 }
 
+// ---- blur (RedactSpec::blur passes per axis).  A region's box radius; c >= 1 for every valid region, so rho >= 1.
+__host__ __device__ inline int redact_blur_radius(const RedactRegion &r) { return r.c < kRedactMaxBlurRadius ? r.c : kRedactMaxBlurRadius; }
+// the index a tap reads on an axis of length L >= 1: the border is replicated
+__host__ __device__ inline int redact_blur_clamp(int i, int L) { return i < 0 ? 0 : i >= L ? L - 1 : i; }
+// The rounded mean of the 2 rho + 1 taps of a pass.  sum <= 255 * 129 = 32 895, sum + rho <= 32 959 < 2^15: 16 bits hold every sum.
+// The division is a multiplication by magic = redact_blur_magic(rho) = 2^24 / n + 1, n = 2 rho + 1 <= 129: with e = magic * n - 2^24
+// (0 < e <= n) the product's quotient is exact while v * e < 2^24, and v * e <= 32 959 * 129 < 2^23.  (tests/csrc/test_redact_blur_host.cpp
+// compares it with `/` for every rho and every v.)
+__host__ __device__ inline uint32_t redact_blur_magic(int rho) { return (1u << 24) / (uint32_t)(2 * rho + 1) + 1u; }
+__host__ __device__ inline uint32_t redact_blur_mean(uint32_t sum, int rho, uint32_t magic) { return ((sum + (uint32_t)rho) * magic) >> 24; }
+
+// Host: one 1-D pass of radius rho over `count` lines of length L; element i of line k is at in[k * line + i * stride] (out likewise;
+// out != in).  A running sum: O(1) per element.
+inline void redact_blur_pass_host(const uint8_t *in, uint8_t *out, int count, size_t line, int L, size_t stride, int rho) {
+    const uint32_t magic = redact_blur_magic(rho);
+    for (int k = 0; k < count; k++) {
+        const uint8_t *a = in + (size_t)k * line;
+        uint8_t *o = out + (size_t)k * line;
+        uint32_t s = 0;
+        for (int d = -rho; d <= rho; d++) s += a[(size_t)redact_blur_clamp(d, L) * stride];
+        for (int i = 0; i < L; i++) {
+            o[(size_t)i * stride] = (uint8_t)redact_blur_mean(s, rho, magic);
+            s += a[(size_t)redact_blur_clamp(i + rho + 1, L) * stride];
+            s -= a[(size_t)redact_blur_clamp(i - rho, L) * stride];
+        }
+    }
+}
+
+// Host: B(orig, rho, passes) on the clipped rectangle of region r, dense (cx1 - cx0) * 3 bytes per row, into `out`.  A value depends on
+// originals at most passes * rho away, so the window blurred is the rectangle grown by that halo and cut by the frame: a pass
+// replicates the window's border, which is the frame's wherever the rectangle is nearer than the halo to it, and what a cut elsewhere
+// spoils stays outside the rectangle (pass k spoils k * rho pixels from such a cut).
+inline void redact_blur_host_region(const RedactRegion &r, int passes, const uint8_t *orig, int rows, int cols, size_t step,
+                                    std::vector<uint8_t> &w0, std::vector<uint8_t> &w1, std::vector<uint8_t> &out) {
+    const int rho = redact_blur_radius(r), halo = passes * rho;
+    const int wx0 = r.cx0 - halo > 0 ? r.cx0 - halo : 0, wx1 = r.cx1 + halo < cols ? r.cx1 + halo : cols;
+    const int wy0 = r.cy0 - halo > 0 ? r.cy0 - halo : 0, wy1 = r.cy1 + halo < rows ? r.cy1 + halo : rows;
+    const int ww = wx1 - wx0, wh = wy1 - wy0;
+    const size_t pitch = (size_t)ww * 3;
+    w0.resize(pitch * wh); w1.resize(pitch * wh);
+    for (int y = 0; y < wh; y++) memcpy(w0.data() + (size_t)y * pitch, orig + (size_t)(wy0 + y) * step + (size_t)3 * wx0, pitch);
+    uint8_t *a = w0.data(), *b = w1.data();
+    for (int p = 0; p < passes; p++) {                            // along x: 3 * wh lines (row, channel) of length ww
+        for (int ch = 0; ch < 3; ch++) redact_blur_pass_host(a + ch, b + ch, wh, pitch, ww, 3, rho);
+        uint8_t *t = a; a = b; b = t;
+    }
+    for (int p = 0; p < passes; p++) {                            // along y: 3 * ww lines (one per byte of a row) of length wh
+        redact_blur_pass_host(a, b, (int)pitch, 1, wh, pitch, rho);
+        uint8_t *t = a; a = b; b = t;
+    }
+    const size_t op = (size_t)(r.cx1 - r.cx0) * 3;
+    out.resize(op * (r.cy1 - r.cy0));
+    for (int y = r.cy0; y < r.cy1; y++) memcpy(out.data() + (size_t)(y - r.cy0) * op, a + (size_t)(y - wy0) * pitch + (size_t)3 * (r.cx0 - wx0), op);
+}
+
 // Host: a whole frame in place.  regions: the image's list, already cut at max_regions.  pixels: one count per region, or nullptr.
-// Every read is of the original bytes: the cell values are formed before the first write.
+// Every read is of the original bytes: the cell values are formed before the first write, and a blur reads a copy of the frame made
+// before the first write.
 inline void redact_host_frame(const RedactSpec &sp, uint8_t *bgr, int rows, int cols, size_t step, const RedactRegion *regions, int nreg,
                               int32_t *pixels) {
     std::vector<std::vector<uint32_t>> value((size_t)nreg);
-    if (sp.mode == RF_REDACT_PIXELATE)
+    const bool blur = sp.mode == RF_REDACT_PIXELATE && sp.blur > 0;
+    std::vector<uint8_t> orig, w0, w1, blurred;
+    if (blur && nreg > 0 && rows > 0 && cols > 0) {
+        orig.resize((size_t)rows * cols * 3);
+        for (int y = 0; y < rows; y++) memcpy(orig.data() + (size_t)y * cols * 3, bgr + (size_t)y * step, (size_t)cols * 3);
+    }
+    if (sp.mode == RF_REDACT_PIXELATE && !blur)
         for (int q = 0; q < nreg; q++) {
             const RedactRegion &r = regions[q];
             if (redact_clip_empty(r)) continue;
@@ -153,13 +222,20 @@ inline void redact_host_frame(const RedactSpec &sp, uint8_t *bgr, int rows, int 
         int32_t owned = 0;
         if (!redact_clip_empty(r)) {
             const int gw = redact_cells_x(r);
+            if (blur) redact_blur_host_region(r, sp.blur, orig.data(), rows, cols, (size_t)cols * 3, w0, w1, blurred);
             for (int y = r.cy0; y < r.cy1; y++)
                 for (int x = r.cx0; x < r.cx1; x++) {
                     if (!redact_covers(r, sp.shape, x, y)) continue;
                     bool lower = false;
                     for (int o = 0; o < q && !lower; o++) lower = redact_covers(regions[o], sp.shape, x, y);
                     if (lower) continue;
-                    const uint32_t v = sp.mode == RF_REDACT_FILL ? fill : value[q][(size_t)((y - r.uy0) / r.c) * gw + (x - r.ux0) / r.c];
+                    uint32_t v;
+                    if (blur) {
+                        const uint8_t *b = blurred.data() + ((size_t)(y - r.cy0) * (r.cx1 - r.cx0) + (x - r.cx0)) * 3;
+                        v = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16);
+                    } else {
+                        v = sp.mode == RF_REDACT_FILL ? fill : value[q][(size_t)((y - r.uy0) / r.c) * gw + (x - r.ux0) / r.c];
+                    }
                     uint8_t *p = bgr + (size_t)y * step + (size_t)3 * x;
                     p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16);
                     owned++;

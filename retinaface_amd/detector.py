@@ -316,13 +316,17 @@ REDACT_RECT, REDACT_ELLIPSE = _lib.RF_REDACT_RECT, _lib.RF_REDACT_ELLIPSE
 
 
 def redact_spec(mode: int = 0, shape: int = 0, cells: int = 0, margin: float = 0.0, fill=(0, 0, 0), max_regions: int = 0,
-                coast: int = 0) -> rf_redact_spec:
+                coast: int = 0, blur: int = 0) -> rf_redact_spec:
     """rf_redact_spec; 0 = the default (pixelate, rectangle, 8 cells, margin 0.2 -- negative = none, max_detections regions, coast = the
-    tracker's max_missed -- negative = no coasting regions)"""
+    tracker's max_missed -- negative = no coasting regions).  blur = 1, 2, 3 (pixelate only): the faces are box-blurred with that many
+    passes per axis, radius min(cell edge, 64) per region, instead of pixelated."""
     s = rf_redact_spec()
     s.struct_size = C.sizeof(rf_redact_spec)
     s.mode, s.shape, s.cells, s.margin, s.max_regions, s.coast = int(mode), int(shape), int(cells), float(margin), int(max_regions), int(coast)
     s.fill[0], s.fill[1], s.fill[2] = (int(v) for v in fill)
+    if not 0 <= int(blur) <= 255:
+        raise ValueError("blur must fit a byte (0 = none; 1, 2, 3 = box passes per axis)")
+    s.blur = int(blur)
     return s
 
 
