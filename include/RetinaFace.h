@@ -104,6 +104,17 @@ public:
     const vector<vector<int>> &ttaVotes() const { return ttaVotes_; }
     const vector<vector<int>> &ttaPasses() const { return ttaPasses_; }
 
+    /* additive: rotation-robust detection (rf_detect_rot_batch): every frame is also detected turned by one, two and three quarter turns
+       (the copies are made on the device), the faces of all passes are moved back and merged on the device.  Fills lastBatchResult()
+       with the merged faces in SOURCE-FRAME pixels (at most spec->max_faces per frame); rotVotes() holds, per frame, how many
+       candidates each face merged, rotSources() the rotation (0..3) its head came from, frameRotations() per frame the quarter turns
+       counter-clockwise that make it upright (-1: no face), rotScores() per frame the four score sums.  spec may be nullptr. */
+    void detectRotated(const vector<cv::Mat> &imgs, float threshold = 0.5, const rf_rot_spec *spec = nullptr);
+    const vector<vector<int>> &rotVotes() const { return rotVotes_; }
+    const vector<vector<int>> &rotSources() const { return rotSrc_; }
+    const vector<int> &frameRotations() const { return frameRot_; }
+    const vector<float> &rotScores() const { return rotScore_; }
+
     /* additive: zoom-pyramid detection (rf_detect_pyramid_batch): every frame is detected at 1x and as net-sized tiles of the frame enlarged
        2x / 4x on the device, so that faces below the smallest anchor are found; the faces of all passes are moved back and merged as in
        detectTta().  Fills lastBatchResult() with the merged faces in SOURCE-FRAME pixels (at most spec->max_faces per frame);
@@ -177,6 +188,9 @@ private:
     vector<vector<int>> tileSrc_;
     vector<vector<int>> ttaVotes_, ttaPasses_;
     vector<vector<int>> pyrVotes_, pyrPasses_;
+    vector<vector<int>> rotVotes_, rotSrc_;
+    vector<int> frameRot_;
+    vector<float> rotScore_;
     vector<vector<rf_track_tag>> trackTags_;
     vector<vector<rf_track>> trackEnded_;
     vector<vector<int32_t>> redactPixels_;

@@ -780,6 +780,83 @@ int rf_detect_tta_batch(rf_handle h, const uint8_t *const *bgr, const int *rows,
 int rf_tta_merge_device(rf_handle h, const int *rows, const int *cols, int n, const rf_tta_spec *spec, const rf_face *faces,
                         const int *pass_counts, rf_face *out, int cap_per_image, int *counts, int *votes, int *src_pass);
 
+/* ---- Rotation-robust detection: the detector finds upright faces; a frame that arrives turned by a quarter, a half or three quarters
+ * of a turn (phone video without its orientation tag, scans, ceiling cameras) loses faces and score.  A rotation call detects every
+ * frame in up to four orientations, the rotated copies made on the device, moves the faces of all passes back into the frame and merges
+ * them on the device with the merge of the TTA call; the same call tells which way is up (DESIGN.md "Rotation-robust detection" holds the
+ * definition; tests/rot_ref.py restates it in numpy; every result is byte-exact against it):
+ *   passes   pass k (k = 0..3) of a rows x cols frame F is F turned by k quarter turns counter-clockwise, np.rot90(F, k):
+ *              k = 0: F itself;                       k = 1: D is cols x rows, D[y][x] = F[x][cols - 1 - y];
+ *              k = 2: D[y][x] = F[rows - 1 - y][cols - 1 - x];     k = 3: D is cols x rows, D[y][x] = F[rows - 1 - x][y].
+ *            rots is a bit mask of the k to run (0 = all four).  Over a call the passes are frame-major, ascending k.  A pass is an
+ *            ordinary image of the call: a rotated pass larger than the net is shrunk as always, and its result is exactly what
+ *            rf_detect_batch_device returns for that image at the call's threshold -- to the byte when that ONE call holds all passes of
+ *            the rotation call in that order, the rotated copies as dense frames of their own (the caveat of the TTA call: the last
+ *            bits of an image's result can depend on what shares its launch).  A NULL / 0 x 0 frame finds nothing.  A pass that breaks a
+ *            frame limit of rf_detect_batch_device: RF_ERR_INVALID_ARG, before any state changes.
+ *   mapping  face j of pass k: all 14 coordinates get one fp32 multiply by rf_frame_scale(rows_k, cols_k), the PASS's own shape
+ *            ((cols, rows) for odd k), also when it is 1.  Then, with c = (float)(cols - 1) and r = (float)(rows - 1) of the source
+ *            frame, a point (x', y') of the pass becomes  k = 1: (c - y', x');  k = 2: (c - x', r - y');  k = 3: (y', r - x')  -- one fp32
+ *            subtract where a coordinate flips.  Boxes: k = 1: x1 = c - y2', x2 = c - y1', y1 = x1', y2 = x2'; k = 2: x1 = c - x2',
+ *            x2 = c - x1', y1 = r - y2', y2 = r - y1'; k = 3: x1 = y1', x2 = y2', y1 = r - x2', y2 = r - x1'.  The landmarks keep their
+ *            index (a rotation keeps handedness: no left / right swap); the score is untouched.  Results are in SOURCE-FRAME pixels:
+ *            their coord_scale for the alignment and face-batch calls is 1.
+ *   merge    rf_tta_spec's merge over the mapped faces of a frame's passes, g = k * max_detections + j with k the ROTATION (not the
+ *            ordinal of the pass); src_rot = g / max_detections is the rotation the head came from.  vote: 0 / 2 = off (the default: a
+ *            sideways pass gives a poorer box and unreliable landmarks for the same face; the head, almost always from the upright
+ *            pass, wins unaveraged), 1 = on.  max_faces, outputs and caps (RF_ERR_TRUNCATED) as for the TTA call.  With rots = 1 and
+ *            vote off, out and counts are the bytes of the TTA call with flip off.
+ *   orientation  two optional outputs: rot_score[i * 4 + k] = (float) of the double sum, in merge order, of the scores of frame i's
+ *            emitted heads with src_rot == k; frame_rot[i] = the k with the largest sum (ties: the lowest k), -1 for a frame without a
+ *            head.  Turning the frame by frame_rot quarter turns counter-clockwise makes it upright. */
+typedef struct rf_rot_spec {
+    uint32_t struct_size;   /* sizeof(rf_rot_spec) */
+    int32_t rots;           /* bit k: run pass k; 1..15; 0 = 15 (all four) */
+    int32_t vote;           /* 0 / 2 = off (plain greedy NMS over all passes); 1 = kept boxes become the score-weighted mean of their cluster */
+    int32_t max_faces;      /* merged faces kept per frame on the device, 1..4096; 0 = the engine's max_detections */
+} rf_rot_spec;
+
+/* Host only, no GPU, no handle -- the same code the kernels run, compiled for the host.
+ * rf_rot_map_face: the mapping of one face of pass k (0..3) of a rows x cols frame at a net_h x net_w net (out may equal in).
+ * rf_rot_merge_host: mapping and merge of ONE frame: with P = popcount(rots) passes in ascending k, the p-th of them holds pass_counts[p]
+ * faces (clamped to max_detections) at faces[p * max_detections + j].  spec may be NULL (max_faces 0 stands for max_detections).  *count is
+ * the true number of heads; out / votes / src_rot (the last two may be NULL) receive the first min(*count, cap, max_faces); frame_rot (one
+ * int) and rot_score (four floats) may be NULL.  Returns RF_OK, RF_ERR_TRUNCATED (a pass count above max_detections, or a cut list) or
+ * RF_ERR_INVALID_ARG.
+ * rf_rotate_host: pass k (0..3; 0 is a row copy) of the rows x cols BGR frame src (row pitch step), written as cols_k * 3 bytes per row
+ * at dst + y * dst_step (bytes beyond them are untouched). */
+int rf_rot_map_face(int rows, int cols, int net_h, int net_w, int k, const rf_face *in, rf_face *out);
+int rf_rot_merge_host(const rf_rot_spec *spec, int rows, int cols, int net_h, int net_w, float nms_threshold, int max_detections,
+                      const rf_face *faces, const int *pass_counts, rf_face *out, int cap, int *count, int *votes, int *src_rot,
+                      int *frame_rot, float *rot_score);
+int rf_rotate_host(const uint8_t *src, int rows, int cols, int step, int k, uint8_t *dst, int dst_step);
+
+/* The rotate kernel on its own: rf_rotate_host for a frame and a destination in device memory (any source pitch and pointer alignment;
+ * ROI views are legal).  Synchronous. */
+int rf_rotate_device(rf_handle h, const void *d_src, int rows, int cols, int step, int k, void *d_dst, int dst_step);
+
+/* Rotation detection of frames resident on the engine's device (frame limits as rf_detect_batch_device).  The rotated copies are made
+ * on the device in front of the call's first detection launch; the passes of all frames go through the engine's ordinary launches; a
+ * gather kernel behind each launch applies the mapping, and one merge launch behind the call's last launch waits for them on the device
+ * -- no host synchronisation in between.  spec may be NULL; votes, src_rot (indexed like out), frame_rot (n ints) and rot_score (n * 4
+ * floats) may be NULL.  A bad spec is refused before any state changes.  Multi-device handles return RF_ERR_UNSUPPORTED from this call,
+ * the next two and rf_rotate_device.  rf_last_anchor_indices / rf_last_candidate_counts afterwards describe the call's PASSES. */
+int rf_detect_rot_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                               float threshold, const rf_rot_spec *spec, rf_face *out, int cap_per_image, int *counts, int *votes,
+                               int *src_rot, int *frame_rot, float *rot_score);
+
+/* The same with frames in HOST memory (rf_detect_batch's convention): each frame is uploaded once, densely. */
+int rf_detect_rot_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                        float threshold, const rf_rot_spec *spec, rf_face *out, int cap_per_image, int *counts, int *votes, int *src_rot,
+                        int *frame_rot, float *rot_score);
+
+/* Mapping and merge of per-pass faces the CALLER supplies (host memory): with P = popcount(rots) passes per frame in ascending k, the
+ * p-th pass of frame i holds pass_counts[i * P + p] faces (clamped to max_detections) at faces[(i * P + p) * max_detections + j].  No
+ * forward pass runs. */
+int rf_rot_merge_device(rf_handle h, const int *rows, const int *cols, int n, const rf_rot_spec *spec, const rf_face *faces,
+                        const int *pass_counts, rf_face *out, int cap_per_image, int *counts, int *votes, int *src_rot, int *frame_rot,
+                        float *rot_score);
+
 /* ---- Zoom-pyramid detection: the smallest anchors are 16 px, so faces below about 16 px are not seen in a frame that already fits the
  * net.  A pyramid call detects every frame at 1x (the passes of its tile plan) and as net-sized tiles of the frame ENLARGED 2x and / or 4x
  * on the device, moves the faces of all passes back into the frame and merges them with the voting merge of the TTA call (DESIGN.md

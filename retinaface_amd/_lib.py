@@ -103,6 +103,10 @@ class rf_tta_spec(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flip", C.c_int32), ("vote", C.c_int32), ("max_faces", C.c_int32)]
 
 
+class rf_rot_spec(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("rots", C.c_int32), ("vote", C.c_int32), ("max_faces", C.c_int32)]
+
+
 class rf_pyramid_spec(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("levels", C.c_int32), ("overlap", C.c_int32), ("edge", C.c_int32),
                 ("full_frame", C.c_int32), ("max_faces", C.c_int32), ("vote", C.c_int32)]
@@ -249,6 +253,19 @@ SYMBOLS = {
                                       C.c_float, _PP(rf_tta_spec), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int)]),
     "rf_tta_merge_device": (C.c_int, [C.c_void_p, _PP(C.c_int), _PP(C.c_int), C.c_int, _PP(rf_tta_spec), _PP(rf_face), _PP(C.c_int),
                                       _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int)]),
+    "rf_rot_map_face": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _PP(rf_face), _PP(rf_face)]),
+    "rf_rot_merge_host": (C.c_int, [_PP(rf_rot_spec), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _PP(rf_face), _PP(C.c_int),
+                                    _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), _PP(C.c_float)]),
+    "rf_rotate_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    "rf_rotate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    "rf_detect_rot_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                             C.c_float, _PP(rf_rot_spec), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int),
+                                             _PP(C.c_int), _PP(C.c_float)]),
+    "rf_detect_rot_batch": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                      C.c_float, _PP(rf_rot_spec), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int),
+                                      _PP(C.c_int), _PP(C.c_float)]),
+    "rf_rot_merge_device": (C.c_int, [C.c_void_p, _PP(C.c_int), _PP(C.c_int), C.c_int, _PP(rf_rot_spec), _PP(rf_face), _PP(C.c_int),
+                                      _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), _PP(C.c_float)]),
     "rf_pyramid_plan": (C.c_int, [_PP(rf_pyramid_spec), C.c_int, C.c_int, C.c_int, C.c_int, _PP(C.c_int), C.c_int]),
     "rf_pyramid_map_face": (C.c_int, [_PP(rf_pyramid_spec), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _PP(rf_face), _PP(rf_face)]),
     "rf_pyramid_merge_host": (C.c_int, [_PP(rf_pyramid_spec), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _PP(rf_face),

@@ -241,6 +241,34 @@ void RetinaFace::detectTta(const vector<cv::Mat> &imgs, float threshold, const r
     }
 }
 
+void RetinaFace::detectRotated(const vector<cv::Mat> &imgs, float threshold, const rf_rot_spec *spec) {
+    const int n = (int)imgs.size();
+    lastBatch_.assign(n, vector<FaceDetectInfo>());
+    rotVotes_.assign(n, vector<int>());
+    rotSrc_.assign(n, vector<int>());
+    frameRot_.assign(n, -1);
+    rotScore_.assign((size_t)n * 4, 0.f);
+    if (n == 0) return;
+    const int cap = spec && spec->max_faces > 0 ? spec->max_faces : maxDet_;
+    vector<const uint8_t *> ptrs(n);
+    vector<int> rows(n), cols(n), steps(n), counts(n, 0);
+    for (int i = 0; i < n; i++) {
+        ptrs[i] = imgs[i].empty() ? nullptr : imgs[i].data;
+        rows[i] = imgs[i].rows; cols[i] = imgs[i].cols; steps[i] = (int)(size_t)imgs[i].step;
+    }
+    vector<rf_face> faces((size_t)n * cap);
+    vector<int> votes((size_t)n * cap, 0), src((size_t)n * cap, 0);
+    check(rf_detect_rot_batch(h_, ptrs.data(), rows.data(), cols.data(), steps.data(), n, threshold, spec, faces.data(), cap, counts.data(),
+                              votes.data(), src.data(), frameRot_.data(), rotScore_.data()), h_, "RetinaFace::detectRotated");
+    for (int i = 0; i < n; i++) {
+        const int k = counts[i] < cap ? counts[i] : cap;
+        lastBatch_[i].resize(k);
+        if (k) memcpy(lastBatch_[i].data(), &faces[(size_t)i * cap], (size_t)k * sizeof(rf_face));
+        rotVotes_[i].assign(votes.begin() + (size_t)i * cap, votes.begin() + (size_t)i * cap + k);
+        rotSrc_[i].assign(src.begin() + (size_t)i * cap, src.begin() + (size_t)i * cap + k);
+    }
+}
+
 void RetinaFace::detectPyramid(const vector<cv::Mat> &imgs, float threshold, const rf_pyramid_spec *spec) {
     const int n = (int)imgs.size();
     lastBatch_.assign(n, vector<FaceDetectInfo>());

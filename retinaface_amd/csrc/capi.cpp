@@ -1100,6 +1100,172 @@ int rf_tta_merge_device(rf_handle h, const int *rows, const int *cols, int n, co
     });
 }
 
+// ---- rotation-robust detection (rot.h)
+namespace {
+// the orientation outputs of one frame from its emitted heads (merge order): the double sum of the scores per rotation, the rotation
+// with the largest sum (ties: the lowest), -1 without a head
+void rot_orientation(const rf_face *faces, const int *src_rot, int emitted, int *frame_rot, float *rot_score) {
+    double sum[4] = {0, 0, 0, 0};
+    int seen[4] = {0, 0, 0, 0};
+    for (int j = 0; j < emitted; j++) {
+        const int k = src_rot[j];
+        if (k < 0 || k > 3) continue;
+        sum[k] = sum[k] + (double)faces[j].score;
+        seen[k] = 1;
+    }
+    int best = -1;
+    for (int k = 0; k < 4; k++)
+        if (seen[k] && (best < 0 || sum[k] > sum[best])) best = k;
+    if (frame_rot) *frame_rot = best;
+    if (rot_score)
+        for (int k = 0; k < 4; k++) rot_score[k] = (float)sum[k];
+}
+}  // namespace
+
+int rf_rot_map_face(int rows, int cols, int net_h, int net_w, int k, const rf_face *in, rf_face *out) {
+    if (!in || !out || rows <= 0 || cols <= 0 || net_h <= 0 || net_w <= 0 || k < 0 || k > 3) return RF_ERR_INVALID_ARG;
+    if (rows > 4096 * 3072 / cols) return RF_ERR_INVALID_ARG;
+    rf::RotEntry e{0, rows, cols, k, rf::tile_frame_scale(rf::rot_rows(k, rows, cols), rf::rot_cols(k, rows, cols), net_h, net_w)};
+    float f[15];
+    memcpy(f, in, sizeof(f));
+    rf::rot_map_face(e, f, f);
+    memcpy(out, f, sizeof(f));
+    return RF_OK;
+}
+
+int rf_rot_merge_host(const rf_rot_spec *spec, int rows, int cols, int net_h, int net_w, float nms_threshold, int max_detections,
+                      const rf_face *faces, const int *pass_counts, rf_face *out, int cap, int *count, int *votes, int *src_rot,
+                      int *frame_rot, float *rot_score) {
+    rf::RotSpec sp;
+    if (max_detections < 1 || max_detections > rf::kTtaMaxFaces || rf::rot_spec_resolve(spec, max_detections, &sp)) return RF_ERR_INVALID_ARG;
+    if (!faces || !pass_counts || !count || cap < 0 || (cap > 0 && !out) || rows < 0 || cols < 0 || net_h <= 0 || net_w <= 0)
+        return RF_ERR_INVALID_ARG;
+    if (cols > 0 && rows > 4096 * 3072 / cols) return RF_ERR_INVALID_ARG;
+    for (int p = 0; p < sp.passes(); p++)
+        if (pass_counts[p] < 0) return RF_ERR_INVALID_ARG;
+    bool truncated = false;
+    std::vector<float> cand;
+    std::vector<int> g;
+    if (rows > 0 && cols > 0) {
+        int p = 0;
+        for (int k = 0; k < 4; k++) {
+            if (!(sp.rots >> k & 1)) continue;
+            const rf::RotEntry e{0, rows, cols, k, rf::tile_frame_scale(rf::rot_rows(k, rows, cols), rf::rot_cols(k, rows, cols), net_h, net_w)};
+            if (pass_counts[p] > max_detections) truncated = true;
+            for (int j = 0; j < pass_counts[p] && j < max_detections; j++) {
+                float f[15];
+                memcpy(f, &faces[(size_t)p * max_detections + j], sizeof(f));
+                rf::rot_map_face(e, f, f);
+                cand.insert(cand.end(), f, f + 15);
+                g.push_back(k * max_detections + j);
+            }
+            p++;
+        }
+    }
+    const int limit = cap < sp.max_faces ? cap : sp.max_faces;
+    std::vector<float> merged((size_t)limit * 15 + 1);
+    std::vector<int> vt((size_t)limit + 1), hg((size_t)limit + 1);
+    std::vector<rf_face> heads_out((size_t)limit + 1);
+    const int heads = rf::tta_merge_candidates(cand, g, nms_threshold, sp.vote != 0, limit, merged.data(), vt.data(), hg.data());
+    *count = heads;
+    const int emitted = heads < limit ? heads : limit;
+    for (int j = 0; j < emitted; j++) {
+        memset(&heads_out[j], 0, sizeof(rf_face));
+        memcpy(&heads_out[j], &merged[(size_t)j * 15], 15 * sizeof(float));
+        out[j] = heads_out[j];
+        hg[j] /= max_detections;
+        if (votes) votes[j] = vt[j];
+        if (src_rot) src_rot[j] = hg[j];
+    }
+    rot_orientation(heads_out.data(), hg.data(), emitted, frame_rot, rot_score);
+    return truncated || heads > limit ? RF_ERR_TRUNCATED : RF_OK;
+}
+
+int rf_rotate_host(const uint8_t *src, int rows, int cols, int step, int k, uint8_t *dst, int dst_step) {
+    if (rows < 0 || cols < 0 || k < 0 || k > 3) return RF_ERR_INVALID_ARG;
+    if (rows == 0 || cols == 0) return RF_OK;
+    if (!src || !dst || rows > 4096 * 3072 / cols || step < cols * 3 || dst_step < rf::rot_cols(k, rows, cols) * 3) return RF_ERR_INVALID_ARG;
+    rf::rot_rotate_host(src, rows, cols, step, k, dst, dst_step);
+    return RF_OK;
+}
+
+namespace {
+// a caller's rotation spec with its defaults applied; refused before the engine is touched
+void rot_request(rf_handle h, const rf_rot_spec *spec, int *votes, int *src_rot, rf::RotRequest *rq) {
+    if (const char *bad = rf::rot_spec_resolve(spec, h->eng->default_max_faces(), &rq->spec)) throw rf::ArgError(bad);
+    rq->votes = votes;
+    rq->src_rot = src_rot;
+}
+
+// the orientation outputs of a finished call, from what it wrote for the caller
+void rot_orient_call(const rf::RotRequest &rq, int n, const rf_face *out, int cap, const int *counts, const int *src_rot, int *frame_rot,
+                     float *rot_score) {
+    if (!frame_rot && !rot_score) return;
+    for (int i = 0; i < n; i++) {
+        const bool have = out && src_rot;
+        const int emitted = have ? std::min(std::min(counts[i], rq.spec.max_faces), cap) : 0;
+        rot_orientation(have ? out + (size_t)i * cap : nullptr, have ? src_rot + (size_t)i * cap : nullptr, emitted,
+                        frame_rot ? frame_rot + i : nullptr, rot_score ? rot_score + (size_t)i * 4 : nullptr);
+    }
+}
+
+int detect_rot_common(rf_handle h, const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,
+                      float thr, const rf_rot_spec *spec, rf_face *out, int cap, int *counts, int *votes, int *src_rot, int *frame_rot,
+                      float *rot_score) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        rf::RotRequest rq;
+        std::vector<int> own;                    // the orientation outputs need the rotation of every head
+        if (!src_rot && (frame_rot || rot_score) && n > 0 && cap > 0) { own.assign((size_t)n * cap, 0); src_rot = own.data(); }
+        rot_request(h, spec, votes, src_rot, &rq);
+        bool tr = false;
+        h->eng->detect_rot(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, rq);
+        rot_orient_call(rq, n, src_rot ? out : nullptr, cap, counts, src_rot, frame_rot, rot_score);
+        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+}  // namespace
+
+int rf_rotate_device(rf_handle h, const void *d_src, int rows, int cols, int step, int k, void *d_dst, int dst_step) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        h->eng->rotate(d_src, rows, cols, step, k, d_dst, dst_step);
+        return RF_OK;
+    });
+}
+
+int rf_detect_rot_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                               float threshold, const rf_rot_spec *spec, rf_face *out, int cap_per_image, int *counts, int *votes,
+                               int *src_rot, int *frame_rot, float *rot_score) {
+    return detect_rot_common(h, (const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, spec, out, cap_per_image, counts, votes,
+                             src_rot, frame_rot, rot_score);
+}
+
+int rf_detect_rot_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                        float threshold, const rf_rot_spec *spec, rf_face *out, int cap_per_image, int *counts, int *votes, int *src_rot,
+                        int *frame_rot, float *rot_score) {
+    return detect_rot_common(h, bgr, rows, cols, steps, n, false, threshold, spec, out, cap_per_image, counts, votes, src_rot, frame_rot,
+                             rot_score);
+}
+
+int rf_rot_merge_device(rf_handle h, const int *rows, const int *cols, int n, const rf_rot_spec *spec, const rf_face *faces,
+                        const int *pass_counts, rf_face *out, int cap_per_image, int *counts, int *votes, int *src_rot, int *frame_rot,
+                        float *rot_score) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        rf::RotRequest rq;
+        std::vector<int> own;
+        if (!src_rot && (frame_rot || rot_score) && n > 0 && cap_per_image > 0) { own.assign((size_t)n * cap_per_image, 0); src_rot = own.data(); }
+        rot_request(h, spec, votes, src_rot, &rq);
+        bool tr = false;
+        h->eng->rot_merge(rows, cols, n, rq, faces, pass_counts, out, cap_per_image, counts, &tr);
+        rot_orient_call(rq, n, src_rot ? out : nullptr, cap_per_image, counts, src_rot, frame_rot, rot_score);
+        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+
 // ---- zoom-pyramid detection (pyramid.h)
 namespace {
 // the plan of one frame for the host-only entry points: false = refused

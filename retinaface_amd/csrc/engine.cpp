@@ -208,7 +208,7 @@ public:
         for (void *p : host_allocs_) (void)hipHostFree(p);
         if (align_stream_) { (void)hipStreamSynchronize(align_stream_); (void)hipStreamDestroy(align_stream_); }
         for (DeviceScratch *b : {&align_crops_, &align_mats_, &align_tab_, &fb_state_, &fq_records_, &fq_packed_, &fq_offsets_, &tile_cand_, &tile_count_, &tile_out_,
-                                 &tile_outcount_, &tile_tab_, &tile_frames_, &tta_cand_, &tta_count_, &tta_frames_, &tta_mirror_, &pyr_frames_, &pyr_zoom_,
+                                 &tile_outcount_, &tile_tab_, &tile_frames_, &tta_cand_, &tta_count_, &tta_frames_, &tta_mirror_, &pyr_frames_, &pyr_zoom_, &rot_frames_, &rot_copies_,
                                  &red_regions_, &red_counts_, &red_cells_, &red_frames_, &red_shadow_}) b->release();
         for (HostScratch *b : {&trk_tags_, &trk_ended_, &trk_counts_, &tta_out_, &tta_votes_, &tta_outcount_, &shot_out_, &shot_info_}) b->release();
         for (auto &t : trackers_) t->release();
@@ -217,6 +217,7 @@ public:
         for (hipEvent_t e : red_ev_) if (e) (void)hipEventDestroy(e);
         if (tta_mirror_done_) (void)hipEventDestroy(tta_mirror_done_);
         if (pyr_zoom_done_) (void)hipEventDestroy(pyr_zoom_done_);
+        if (rot_copies_done_) (void)hipEventDestroy(rot_copies_done_);
         kind_.arena->release();
         for (auto &e : prof_ev_) (void)hipEventDestroy(e);
     }
@@ -1229,6 +1230,190 @@ public:
         tta_copy_out(n, mrq, out, cap_per_image, counts, truncated);
     }
 
+    // -------------------------------------------------------------------------------- rotation-robust detection
+    // The passes of a call's frames as one table, frame-major, ascending k over the rotations of the spec.  A NULL / empty frame keeps
+    // its passes, which gather nothing (frame = -1).  `have_ptrs` false: rot_merge(), which has no pixels.  Throws before any state
+    // has changed.
+    void rot_build_passes(const RotSpec &sp, const uint8_t *const *frames, bool have_ptrs, const int *rows, const int *cols, int n,
+                          std::vector<RotEntry> *entries) const {
+        entries->clear();
+        for (int i = 0; i < n; i++) {
+            const bool empty = (have_ptrs && !frames[i]) || rows[i] <= 0 || cols[i] <= 0;
+            if (!empty && rows[i] > 4096 * 3072 / cols[i]) throw ArgError("frame larger than 4096x3072 (RetinaFace.cpp:325)");
+            for (int k = 0; k < 4; k++) {
+                if (!(sp.rots >> k & 1)) continue;
+                RotEntry e;
+                e.frame = empty ? -1 : i; e.rows = empty ? 0 : rows[i]; e.cols = empty ? 0 : cols[i]; e.k = k;
+                e.scale = 1.f;
+                if (!empty) {
+                    const int rk = rot_rows(k, rows[i], cols[i]), ck = rot_cols(k, rows[i], cols[i]);
+                    if (rk > 4096 * 3072 / ck) throw ArgError("a rotated pass is larger than 4096x3072 (RetinaFace.cpp:325)");
+                    e.scale = tile_frame_scale(rk, ck, net_h_, net_w_);
+                }
+                entries->push_back(e);
+            }
+        }
+    }
+
+    // the blocks of a rotation call are those of a TTA call (tta_open): the two calls never overlap, and the merge is the same launch
+    static TtaSpec rot_merge_spec(const RotSpec &sp) {
+        TtaSpec t;
+        t.flip = 0; t.vote = sp.vote; t.max_faces = sp.max_faces;
+        return t;
+    }
+    static TtaRequest rot_merge_request(const RotRequest &rq) {
+        TtaRequest t;
+        t.spec = rot_merge_spec(rq.spec); t.votes = rq.votes; t.src_pass = rq.src_rot;
+        return t;
+    }
+
+    void rot_launch_gather(hipStream_t st, const uint8_t *faces, int face_stride, const int *counts, const RotEntry *table, int passes) {
+        RotGatherParams gp;
+        gp.faces = faces; gp.face_stride = face_stride; gp.faces_per_pass = opt_.max_detections;
+        gp.counts = counts; gp.table = table;
+        gp.n = passes; gp.rank_stride = opt_.max_detections;
+        gp.cand = (Candidate *)tta_cand_.ptr; gp.cand_count = (int *)tta_count_.ptr; gp.cap = kTtaMergeCap;
+        launch_rot_gather(st, gp);
+    }
+
+    void rotate(const void *d_src, int rows, int cols, int step, int k, void *d_dst, int dst_step) override {
+        if (rows < 0 || cols < 0) throw ArgError("negative frame size");
+        if (k < 0 || k > 3) throw ArgError("rotate: k must be in [0, 3]");
+        if (rows == 0 || cols == 0) return;
+        if (!d_dst || dst_step < rot_cols(k, rows, cols) * 3) throw ArgError("rotate: null destination or dst_step < cols_k * 3");
+        check_frame((const uint8_t *)d_src, rows, cols, step);
+        if (!d_src) throw ArgError("null argument");
+        DeviceGuard guard(device_);
+        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+        const RotateParams rp{(const uint8_t *)d_src, rows, cols, step, k, (uint8_t *)d_dst, dst_step};
+        launch_rotate_frames(align_stream_, &rp, 1);
+        RF_HIP(hipGetLastError());
+        RF_HIP(hipStreamSynchronize(align_stream_));
+    }
+
+    void detect_rot(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,
+                    float threshold, rf_face *out, int cap_per_image, int *counts, bool *truncated, const RotRequest &rq) override {
+        *truncated = false;
+        const TtaRequest mrq = rot_merge_request(rq);
+        tta_check_args(n, frames, rows, cols, counts, out, cap_per_image, mrq.spec);
+        std::vector<int> st((size_t)std::max(n, 1));
+        for (int i = 0; i < n; i++) {
+            st[i] = steps ? steps[i] : cols[i] * 3;
+            check_frame(frames[i], rows[i], cols[i], st[i]);
+        }
+        std::vector<RotEntry> entries;
+        rot_build_passes(rq.spec, frames, true, rows, cols, n, &entries);
+        if (n == 0) return;
+        DeviceGuard guard(device_);
+        const int PP = rq.spec.passes();
+        auto live = [&](int i) { return entries[(size_t)i * PP].frame >= 0; };
+        // host frames are uploaded once, densely
+        std::vector<const uint8_t *> base((size_t)n, nullptr);
+        if (!on_device) {
+            size_t bytes = 0;
+            std::vector<size_t> off((size_t)n, 0);
+            for (int i = 0; i < n; i++)
+                if (live(i)) { off[i] = bytes; bytes += align256((size_t)rows[i] * cols[i] * 3); }
+            uint8_t *d = rot_frames_.reserve(bytes);
+            for (int i = 0; i < n; i++) {
+                if (!live(i)) continue;
+                RF_HIP(hipMemcpy2D(d + off[i], (size_t)cols[i] * 3, frames[i], (size_t)st[i], (size_t)cols[i] * 3, (size_t)rows[i], hipMemcpyHostToDevice));
+                base[i] = d + off[i];
+                st[i] = cols[i] * 3;
+            }
+        } else {
+            for (int i = 0; i < n; i++) base[i] = live(i) ? frames[i] : nullptr;
+        }
+        // as in detect_tiled(): a super-batch of earlier enqueues starts now, every later launch carries passes of this call only
+        launch_pending();
+        // The rotated copies: dense, each at a 256-byte-aligned offset of one block (what a freshly allocated dense frame looks like to
+        // conv0's staging), made on the side stream; every lane that launches a pass of the call waits for them on the device.
+        const int P = (int)entries.size();
+        size_t copy_bytes = 0;
+        for (int i = 0; i < n; i++)
+            if (live(i)) copy_bytes += align256((size_t)rows[i] * cols[i] * 3) * (size_t)__builtin_popcount((unsigned)rq.spec.rots & 14u);
+        uint8_t *d_copies = copy_bytes ? rot_copies_.reserve(copy_bytes) : nullptr;
+        std::vector<const uint8_t *> vp((size_t)P, nullptr);
+        std::vector<int> vr((size_t)P, 0), vc((size_t)P, 0), vs((size_t)P, 0), pass_counts((size_t)P);
+        std::vector<RotateParams> rp;
+        size_t coff = 0;
+        for (int q = 0; q < P; q++) {
+            const RotEntry &e = entries[q];
+            if (e.frame < 0) continue;
+            const int i = e.frame;
+            vr[q] = rot_rows(e.k, rows[i], cols[i]); vc[q] = rot_cols(e.k, rows[i], cols[i]);
+            if (e.k == 0) {
+                vp[q] = base[i]; vs[q] = st[i];
+                continue;
+            }
+            uint8_t *dst = d_copies + coff;
+            coff += align256((size_t)rows[i] * cols[i] * 3);
+            rp.push_back(RotateParams{base[i], rows[i], cols[i], st[i], e.k, dst, vc[q] * 3});
+            vp[q] = dst; vs[q] = vc[q] * 3;
+        }
+        if (!rp.empty()) {
+            if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+            if (!rot_copies_done_) RF_HIP(hipEventCreateWithFlags(&rot_copies_done_, hipEventDisableTiming));
+            launch_rotate_frames(align_stream_, rp.data(), (int)rp.size());
+            RF_HIP(hipGetLastError());
+            RF_HIP(hipEventRecord(rot_copies_done_, align_stream_));
+        }
+        tta_open(n, mrq.spec);
+        rot_.rq = rq; rot_.entries.swap(entries);
+        rot_.n_frames = n; rot_.next_pass = 0;
+        rot_.lanes_used.clear();
+        rot_.wait_copies = !rp.empty();
+        rot_.on = true;
+        tta_dirty_ = true;                       // until the call has ended well
+        struct Off { bool &on; ~Off() { on = false; } } off_guard{rot_.on};
+        bool tr = false;
+        detect(vp.data(), vr.data(), vc.data(), vs.data(), P, true, threshold, nullptr, 0, pass_counts.data(), &tr);
+        rot_.on = false;
+        if (rot_.next_pass != P) throw HipError("rotation detection: the merge was not launched");
+        // every launch of the call has been waited for; the merge ran in front of the last one's `done`
+        tta_dirty_ = false;
+        *truncated = tr;
+        tta_copy_out(n, mrq, out, cap_per_image, counts, truncated);
+    }
+
+    void rot_merge(const int *rows, const int *cols, int n, const RotRequest &rq, const rf_face *faces, const int *pass_counts,
+                   rf_face *out, int cap_per_image, int *counts, bool *truncated) override {
+        *truncated = false;
+        const TtaRequest mrq = rot_merge_request(rq);
+        tta_check_args(n, rows, cols, counts, faces, out, cap_per_image, mrq.spec);
+        if (n > 0 && !pass_counts) throw ArgError("null argument");
+        std::vector<RotEntry> entries;
+        rot_build_passes(rq.spec, nullptr, false, rows, cols, n, &entries);
+        if (n == 0) return;
+        const int P = (int)entries.size(), md = opt_.max_detections;
+        for (int p = 0; p < P; p++)
+            if (pass_counts[p] < 0) throw ArgError("negative face count");
+        DeviceGuard guard(device_);
+        // one table: run parameters | pass table | counts | faces (60-byte records, max_detections per pass)
+        const size_t o_tab = 256, o_cnt = o_tab + align256((size_t)P * sizeof(RotEntry)), o_face = o_cnt + align256((size_t)P * sizeof(int)),
+                     total = o_face + (size_t)P * md * sizeof(rf_face);
+        align_host_.assign(total, 0);
+        *(RunParams *)align_host_.data() = RunParams{0.f, nms_threshold_, n, 0};
+        memcpy(align_host_.data() + o_tab, entries.data(), (size_t)P * sizeof(RotEntry));
+        int *cnt = (int *)(align_host_.data() + o_cnt);
+        for (int p = 0; p < P; p++) {
+            cnt[p] = std::min(pass_counts[p], md);
+            if (pass_counts[p] > md) *truncated = true;
+            if (cnt[p]) memcpy(align_host_.data() + o_face + (size_t)p * md * sizeof(rf_face), faces + (size_t)p * md, (size_t)cnt[p] * sizeof(rf_face));
+        }
+        uint8_t *d_tab = align_tab_.reserve(total);
+        tta_open(n, mrq.spec);
+        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+        tta_dirty_ = true;
+        RF_HIP(hipMemcpyAsync(d_tab, align_host_.data(), total, hipMemcpyHostToDevice, align_stream_));
+        rot_launch_gather(align_stream_, d_tab + o_face, (int)sizeof(rf_face), (const int *)(d_tab + o_cnt), (const RotEntry *)(d_tab + o_tab), P);
+        tta_launch_merge(align_stream_, n, mrq.spec, (const RunParams *)d_tab);
+        RF_HIP(hipGetLastError());
+        RF_HIP(hipStreamSynchronize(align_stream_));
+        tta_dirty_ = false;
+        tta_copy_out(n, mrq, out, cap_per_image, counts, truncated);
+    }
+
     // -------------------------------------------------------------------------------- face tracks
     void *tracker_create(const TrackSpec &spec, int n_streams) override {
         if (n_streams < 1 || n_streams > kTrackMaxStreams) throw ArgError("n_streams must be in [1, 1024]");
@@ -2105,6 +2290,8 @@ private:
         hipEvent_t tta_done = nullptr;        // ... recorded behind the launch's gather, as tile_done
         PyrEntry *h_pyr_tab = nullptr;        // detect_pyramid(): pinned, per image of the launch the pass it is (allocated on first use)
         hipEvent_t pyr_done = nullptr;        // ... recorded behind the launch's gather, as tile_done
+        RotEntry *h_rot_tab = nullptr;        // detect_rot(): pinned, per image of the launch the pass it is (allocated on first use)
+        hipEvent_t rot_done = nullptr;        // ... recorded behind the launch's gather, as tile_done
         uint8_t *h_track_tab = nullptr;       // detect_track(): pinned, the launch's stream table and image table (allocated on first use)
         hipEvent_t track_done = nullptr;      // ... recorded behind the launch's track kernel: the call's next track launch (another lane) waits for it
         int32_t *h_shot_tab = nullptr;        // detect_track_shots(): pinned, per tracked image of the launch its stream entry (allocated on first use)
@@ -2154,6 +2341,7 @@ private:
         if (l.tile_done) (void)hipEventDestroy(l.tile_done);
         if (l.tta_done) (void)hipEventDestroy(l.tta_done);
         if (l.pyr_done) (void)hipEventDestroy(l.pyr_done);
+        if (l.rot_done) (void)hipEventDestroy(l.rot_done);
         if (l.track_done) (void)hipEventDestroy(l.track_done);
         if (l.shot_done) (void)hipEventDestroy(l.shot_done);
         if (l.copy2) { (void)hipStreamSynchronize(l.copy2); (void)hipStreamDestroy(l.copy2); }
@@ -2415,6 +2603,7 @@ private:
         }
         if (tta_.on && tta_.wait_mirror) RF_HIP(hipStreamWaitEvent(s.stream, tta_mirror_done_, 0));      // the launch reads mirrored copies
         if (pyr_.on && pyr_.wait_zoom) RF_HIP(hipStreamWaitEvent(s.stream, pyr_zoom_done_, 0));          // the launch reads zoom tiles
+        if (rot_.on && rot_.wait_copies) RF_HIP(hipStreamWaitEvent(s.stream, rot_copies_done_, 0));      // the launch reads rotated copies
         double tt = trace_.on ? HostTrace::now() : 0.0;
         RF_HIP(hipMemcpyAsync(s.d_frames, s.h_frames, s.table_bytes, hipMemcpyHostToDevice, s.stream));
         trace_.add(2, tt);
@@ -2445,6 +2634,7 @@ private:
         if (tile_.on) launch_lane_tile(s, n);
         if (tta_.on) launch_lane_tta(s, n);
         if (pyr_.on) launch_lane_pyr(s, n);
+        if (rot_.on) launch_lane_rot(s, n);
         if (trk_.on) launch_lane_track(s, n);
         if (shot_.on) launch_lane_shots(s);
         if (red_.on) launch_lane_redact(s, n);
@@ -2607,6 +2797,34 @@ private:
         for (int l : pyr_.lanes_used)
             if (l != me && l < (int)lanes_.size() && lanes_[l].pyr_done) RF_HIP(hipStreamWaitEvent(s.stream, lanes_[l].pyr_done, 0));
         tta_launch_merge(s.stream, pyr_.n_frames, pyr_merge_spec(pyr_.rq.spec), s.d_params);
+        RF_HIP(hipGetLastError());
+    }
+
+    // The rotation launches of a super-batch of detect_rot(), as launch_lane_tta(): the gather behind each launch, and behind the
+    // call's LAST launch the wait for the gathers of the call's other lanes and the voting merge.  No host wait anywhere.
+    void launch_lane_rot(Lane &s, int n) {
+        if (!s.h_rot_tab) {
+            void *p = nullptr;
+            RF_HIP(hipHostMalloc(&p, std::max<size_t>((size_t)cap_images_ * sizeof(RotEntry), 256), hipHostMallocDefault));
+            s.host_allocs.push_back(p);
+            s.h_rot_tab = (RotEntry *)p;
+            RF_HIP(hipEventCreateWithFlags(&s.rot_done, hipEventDisableTiming));
+        }
+        const int total = (int)rot_.entries.size();
+        if (n > cap_images_ || rot_.next_pass + n > total) throw HipError("rotation detection: a launch carries images of another call");
+        for (int i = 0; i < n; i++) s.h_rot_tab[i] = rot_.entries[rot_.next_pass + i];
+        rot_launch_gather(s.stream, (const uint8_t *)s.h_out, (int)sizeof(Candidate), s.h_counts, s.h_rot_tab, n);
+        RF_HIP(hipGetLastError());
+        rot_.next_pass += n;
+        const int me = (int)(&s - lanes_.data());
+        if (rot_.next_pass < total) {
+            RF_HIP(hipEventRecord(s.rot_done, s.stream));
+            if (std::find(rot_.lanes_used.begin(), rot_.lanes_used.end(), me) == rot_.lanes_used.end()) rot_.lanes_used.push_back(me);
+            return;
+        }
+        for (int l : rot_.lanes_used)
+            if (l != me && l < (int)lanes_.size() && lanes_[l].rot_done) RF_HIP(hipStreamWaitEvent(s.stream, lanes_[l].rot_done, 0));
+        tta_launch_merge(s.stream, rot_.n_frames, rot_merge_spec(rot_.rq.spec), s.d_params);
         RF_HIP(hipGetLastError());
     }
 
@@ -3111,6 +3329,13 @@ private:
     hipEvent_t pyr_zoom_done_ = nullptr;
     struct { bool on = false, wait_zoom = false; PyrRequest rq; std::vector<PyrEntry> entries; int n_frames = 0, next_pass = 0;
              std::vector<int> lanes_used; } pyr_;
+
+    // rotation detection (rot.h): the device copy of host frames, the rotated copies and the event behind them; the request detect_rot()
+    // has open.  Candidates, counters and merged records are the TTA call's blocks (rot_merge_spec).
+    DeviceScratch rot_frames_, rot_copies_;
+    hipEvent_t rot_copies_done_ = nullptr;
+    struct { bool on = false, wait_copies = false; RotRequest rq; std::vector<RotEntry> entries; int n_frames = 0, next_pass = 0;
+             std::vector<int> lanes_used; } rot_;
 
     // face tracks: the trackers of this handle, the call-level result buffers and the request a tracked call has open
     struct Tracker {

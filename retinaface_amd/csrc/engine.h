@@ -118,6 +118,14 @@ struct PyrRequest {
     int *src_pass = nullptr;
 };
 
+// A rotation call (rot.h; rf_detect_rot_batch* / rf_rot_merge_device): the validated spec and where the member count and the rotation
+// of each merged face go
+struct RotRequest {
+    RotSpec spec;
+    int *votes = nullptr;                       // host, indexed like out, or nullptr
+    int *src_rot = nullptr;
+};
+
 // A tracked call (track.h; rf_track_update_device / rf_detect_track_*): the tracker (what tracker_create returned), the stream of every
 // image (-1 = not tracked) and where tags, ended lists and their counts go (host; each may be nullptr)
 struct TrackRequest {
@@ -217,6 +225,23 @@ public:
     // the mirror kernel on its own: a left-right mirrored copy of a device-resident frame
     virtual void mirror(const void *, int, int, int, void *, int) {
         throw Unsupported("test-time augmentation is not available on a multi-device handle");
+    }
+    // Rotation-robust detection: every frame becomes up to four passes (itself and copies turned by quarter turns, made on the device in
+    // front of the call's first launch) that go through detect()'s ordinary launches; a gather launch behind each of them and one
+    // voting merge behind the last (ordered by events on the device, no host wait).  *truncated: a pass or the merge hit a cap.
+    // Single-device engines only.
+    virtual void detect_rot(const uint8_t *const *, const int *, const int *, const int *, int, bool, float, rf_face *, int, int *,
+                            bool *, const RotRequest &) {
+        throw Unsupported("rotation detection is not available on a multi-device handle");
+    }
+    // mapping and merge of per-pass faces the caller supplies (faces[(i * passes + p) * max_detections + j])
+    virtual void rot_merge(const int *, const int *, int, const RotRequest &, const rf_face *, const int *, rf_face *, int, int *,
+                           bool *) {
+        throw Unsupported("rotation detection is not available on a multi-device handle");
+    }
+    // the rotate kernel on its own: a device-resident frame turned by k quarter turns counter-clockwise
+    virtual void rotate(const void *, int, int, int, int, void *, int) {
+        throw Unsupported("rotation detection is not available on a multi-device handle");
     }
     // Zoom-pyramid detection: every frame becomes the passes of its pyramid plan -- 1x views, and tiles of the frame enlarged 2x / 4x
     // that a zoom kernel writes on the device in front of the call's first launch -- which go through detect()'s ordinary launches; a

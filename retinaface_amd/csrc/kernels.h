@@ -12,6 +12,7 @@
 #include "face_quality.h"
 #include "redact.h"
 #include "pyramid.h"
+#include "rot.h"
 #include "tile.h"
 #include "tta.h"
 #include "track.h"
@@ -407,6 +408,30 @@ struct VoteMergeParams {
     int n;
 };
 void launch_vote_merge(hipStream_t s, const VoteMergeParams &p, bool vote);     // vote false: the heads keep their own coordinates
+
+// ---- K_m: rotation-robust detection (rot.h).
+//      rotate_frames: dense or pitched quarter-turn rotations (np.rot90(F, k)) of BGR frames (any source pitch and alignment), in
+//                     front of a rotation call's launches.  k = 0 / 2: mirror_rows' 12-byte path; k = 1 / 3: an LDS-tiled transpose.
+//      rot_gather:    tta_gather's shape with rot_map_face as the mapping, g = k * rank_stride + j.
+//      The merge is launch_vote_merge.
+struct RotateParams {
+    const uint8_t *src; int rows, cols, step;     // the SOURCE frame: row y at src + y * step
+    int k;                                        // quarter turns counter-clockwise, 0..3
+    uint8_t *dst; int dst_step;                   // rot_cols(k) * 3 bytes per row are written, rot_rows(k) rows
+};
+constexpr int kRotateFramesPerLaunch = 16;       // rotations of one launch: their descriptors travel as kernel arguments
+void launch_rotate_frames(hipStream_t s, const RotateParams *frames, int n);
+
+struct RotGatherParams {
+    const uint8_t *faces;                 // pass p, rank j: 15 floats at faces + (p * faces_per_pass + j) * face_stride
+    int face_stride, faces_per_pass;
+    const int *counts;                    // [n] faces of each pass (clamped to faces_per_pass here)
+    const RotEntry *table;                // [n] what each pass is (frame < 0: skipped)
+    int n, rank_stride;                   // passes of this launch; max_detections
+    Candidate *cand; int *cand_count;     // as TileGatherParams
+    int cap;
+};
+void launch_rot_gather(hipStream_t s, const RotGatherParams &p);
 
 // ---- K_k: zoom-pyramid detection (pyramid.h).
 //      zoom_tile:  windows of frames enlarged 2x / 4x (integer bilinear, pyr_zoom_pixel) written as dense frames, in front of a

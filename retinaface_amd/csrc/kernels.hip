@@ -5976,6 +5976,206 @@ void launch_pyr_gather(hipStream_t s, const PyrGatherParams &p) {
     hipLaunchKernelGGL(pyr_gather_kernel, dim3(p.n), dim3(kThreads), 0, s, p);
 }
 
+// =============================================================================================
+// K_m: rotation-robust detection (rot.h).
+// rotate_frames_kernel: pass k of a frame, np.rot90(F, k).  One launch carries up to sixteen frame-rotations (blockIdx.y).
+//      k = 0 / 2: a row copy / a reversal of both axes: mirror_rows_kernel's path -- one thread moves four pixels = 12 contiguous
+//      bytes, read as three dwords where the pitched source happens to be dword aligned and bytewise elsewhere, re-packed in
+//      registers (k = 2), stored as three dwords where the destination is aligned and bytewise elsewhere; both directions coalesced.
+//      k = 1 / 3: a transpose of 3-byte pixels through LDS.  A workgroup takes a 64 x 64 pixel tile: it reads the tile row-wise
+//      (16 threads per row, 12 bytes each, as above), unpacks every pixel into ONE dword and writes it to LDS at row pitch 65
+//      dwords; after the barrier it reads the tile column-wise -- lane l of a wave takes column 4 w + (l & 3) and source rows
+//      4 (l >> 2) .. + 3 -- packs the four pixels into three dwords and stores them into the destination row that column became
+//      (three dword stores where that address is aligned, bytewise elsewhere; k = 3 reverses the four pixels).  LDS banks
+//      (ds_read_b32 / ds_write_b32: 32 banks, lanes 0-31 and 32-63 are the two groups): a column-wise read of lane l addresses dword
+//      (4 g + j) * 65 + c, bank (4 g + j + c) mod 32 with g = 0..7 and c = c0..c0 + 3 inside a group: 32 lanes, 32 banks, no conflict.
+//      The row-wise write of a group covers two tile rows, dwords r * 65 + 4 q + j, q = 0..15: bank (r + 4 q + j) mod 32, two
+//      addresses per bank, which a ds_write_b32 absorbs (its issue cost covers two array cycles).  16,640 bytes of LDS per workgroup:
+//      nine workgroups fit a CU's 160 KiB, eight of them are the CU's 32 wave slots.  The tile's last pixels of a row or a column
+//      (th, tw not multiples of 4) go bytewise.  No byte outside the cols_k * 3 bytes of a row is read or written.
+// =============================================================================================
+constexpr int kRotTile = 64;
+constexpr int kRotPitch = kRotTile + 1;
+struct RotateBatch { RotateParams f[kRotateFramesPerLaunch]; };
+
+// twelve contiguous bytes = four pixels, as three dwords
+__device__ __forceinline__ void rot_load12(const uint8_t *sp, uint32_t &w0, uint32_t &w1, uint32_t &w2) {
+    if (((uintptr_t)sp & 3) == 0) {
+        const uint32_t *s4 = (const uint32_t *)sp;
+        w0 = s4[0]; w1 = s4[1]; w2 = s4[2];
+    } else {
+        w0 = sp[0] | (uint32_t)sp[1] << 8 | (uint32_t)sp[2] << 16 | (uint32_t)sp[3] << 24;
+        w1 = sp[4] | (uint32_t)sp[5] << 8 | (uint32_t)sp[6] << 16 | (uint32_t)sp[7] << 24;
+        w2 = sp[8] | (uint32_t)sp[9] << 8 | (uint32_t)sp[10] << 16 | (uint32_t)sp[11] << 24;
+    }
+}
+__device__ __forceinline__ void rot_store12(uint8_t *dp, uint32_t o0, uint32_t o1, uint32_t o2) {
+    if (((uintptr_t)dp & 3) == 0) {
+        uint32_t *d4 = (uint32_t *)dp;
+        d4[0] = o0; d4[1] = o1; d4[2] = o2;
+    } else {
+        for (int j = 0; j < 4; j++) {
+            dp[j] = (uint8_t)(o0 >> (8 * j)); dp[4 + j] = (uint8_t)(o1 >> (8 * j)); dp[8 + j] = (uint8_t)(o2 >> (8 * j));
+        }
+    }
+}
+// pixels P0 .. P3 (24 bits each, B in the low byte) as the twelve bytes P0 P1 P2 P3
+__device__ __forceinline__ void rot_pack(uint32_t p0, uint32_t p1, uint32_t p2, uint32_t p3, uint32_t &o0, uint32_t &o1, uint32_t &o2) {
+    o0 = p0 | p1 << 24;
+    o1 = p1 >> 8 | p2 << 16;
+    o2 = p2 >> 16 | p3 << 8;
+}
+
+__global__ __launch_bounds__(kThreads) void rotate_frames_kernel(RotateBatch batch) {
+    __shared__ uint32_t s_tile[kRotTile * kRotPitch];
+    const RotateParams a = batch.f[blockIdx.y];
+    if (a.rows <= 0 || a.cols <= 0) return;
+    if (!(a.k & 1)) {
+        const int gpr = (a.cols + 3) >> 2;                               // groups of four pixels per row
+        const long long total = (long long)a.rows * gpr;
+        for (long long item = (long long)blockIdx.x * kThreads + threadIdx.x; item < total; item += (long long)gridDim.x * kThreads) {
+            const int y = (int)(item / gpr), x = (int)(item - (long long)y * gpr) << 2;
+            const int n = a.cols - x < 4 ? a.cols - x : 4;
+            uint8_t *dp = a.dst + (size_t)y * a.dst_step + (size_t)3 * x;
+            const uint8_t *sp = a.k ? a.src + (size_t)(a.rows - 1 - y) * a.step + (size_t)3 * (a.cols - x - n)
+                                    : a.src + (size_t)y * a.step + (size_t)3 * x;
+            if (n < 4) {
+                for (int j = 0; j < n; j++)
+                    for (int c = 0; c < 3; c++) dp[3 * j + c] = sp[3 * (a.k ? n - 1 - j : j) + c];
+                continue;
+            }
+            uint32_t w0, w1, w2;
+            rot_load12(sp, w0, w1, w2);
+            if (a.k) {
+                // source bytes b0 .. b11 = pixels P0 P1 P2 P3; the output is P3 P2 P1 P0 (mirror_rows_kernel)
+                const uint32_t o0 = (w2 >> 8) | (w1 >> 16 << 24);
+                const uint32_t o1 = (w1 >> 24) | ((w2 & 0xffu) << 8) | ((w0 >> 24) << 16) | ((w1 & 0xffu) << 24);
+                const uint32_t o2 = ((w1 >> 8) & 0xffu) | (w0 << 8);
+                w0 = o0; w1 = o1; w2 = o2;
+            }
+            rot_store12(dp, w0, w1, w2);
+        }
+        return;
+    }
+    const int tiles_x = (a.cols + kRotTile - 1) / kRotTile, tiles_y = (a.rows + kRotTile - 1) / kRotTile;
+    const int tiles = tiles_x * tiles_y;                                 // rows * cols <= 4096 * 3072: fits an int
+    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {       // uniform over the workgroup
+        const int y0 = tile / tiles_x * kRotTile, x0 = tile % tiles_x * kRotTile;
+        const int th = a.rows - y0 < kRotTile ? a.rows - y0 : kRotTile, tw = a.cols - x0 < kRotTile ? a.cols - x0 : kRotTile;
+        for (int item = threadIdx.x; item < kRotTile * (kRotTile / 4); item += kThreads) {
+            const int r = item >> 4, q = (item & 15) << 2;
+            if (r >= th || q >= tw) continue;
+            const int n = tw - q < 4 ? tw - q : 4;
+            const uint8_t *sp = a.src + (size_t)(y0 + r) * a.step + (size_t)3 * (x0 + q);
+            uint32_t *lp = s_tile + r * kRotPitch + q;
+            if (n < 4) {
+                for (int j = 0; j < n; j++) lp[j] = sp[3 * j] | (uint32_t)sp[3 * j + 1] << 8 | (uint32_t)sp[3 * j + 2] << 16;
+                continue;
+            }
+            uint32_t w0, w1, w2;
+            rot_load12(sp, w0, w1, w2);
+            lp[0] = w0 & 0xffffffu;
+            lp[1] = (w0 >> 24 | w1 << 8) & 0xffffffu;
+            lp[2] = (w1 >> 16 | w2 << 16) & 0xffffffu;
+            lp[3] = w2 >> 8;
+        }
+        __syncthreads();
+        for (int item = threadIdx.x; item < kRotTile * (kRotTile / 4); item += kThreads) {
+            const int c = ((item >> 6) << 2) | (item & 3), g = ((item >> 2) & 15) << 2;      // source column, first source row of the tile
+            if (c >= tw || g >= th) continue;
+            const int n = th - g < 4 ? th - g : 4;
+            uint32_t p[4];
+            for (int j = 0; j < 4; j++) p[j] = j < n ? s_tile[(g + j) * kRotPitch + c] : 0u;
+            // k = 1: D[cols - 1 - sx][sy]: the source rows ascend along the destination row.  k = 3: D[sx][rows - 1 - sy]: they descend.
+            uint8_t *dp;
+            if (a.k == 1) {
+                dp = a.dst + (size_t)(a.cols - 1 - (x0 + c)) * a.dst_step + (size_t)3 * (y0 + g);
+            } else {
+                dp = a.dst + (size_t)(x0 + c) * a.dst_step + (size_t)3 * (a.rows - (y0 + g) - n);
+                uint32_t t[4];
+                for (int j = 0; j < 4; j++) t[j] = p[j];
+                for (int j = 0; j < 4; j++) p[j] = j < n ? t[n - 1 - j] : 0u;
+            }
+            if (n < 4) {
+                for (int j = 0; j < n; j++) {
+                    dp[3 * j] = (uint8_t)p[j]; dp[3 * j + 1] = (uint8_t)(p[j] >> 8); dp[3 * j + 2] = (uint8_t)(p[j] >> 16);
+                }
+                continue;
+            }
+            uint32_t o0, o1, o2;
+            rot_pack(p[0], p[1], p[2], p[3], o0, o1, o2);
+            rot_store12(dp, o0, o1, o2);
+        }
+        __syncthreads();                                                 // the next tile overwrites s_tile
+    }
+}
+
+// up to kRotateFramesPerLaunch rotations per launch (blockIdx.y), the grid sized for the largest of them: a rotation's surplus
+// workgroups find no item and retire
+void launch_rotate_frames(hipStream_t s, const RotateParams *frames, int n) {
+    for (int f0 = 0; f0 < n; f0 += kRotateFramesPerLaunch) {
+        RotateBatch b;
+        memset(&b, 0, sizeof(b));
+        const int m = n - f0 < kRotateFramesPerLaunch ? n - f0 : kRotateFramesPerLaunch;
+        long long blocks = 0;
+        for (int i = 0; i < m; i++) {
+            const RotateParams &p = frames[f0 + i];
+            if (p.rows <= 0 || p.cols <= 0) continue;          // rows = 0: no items
+            if (p.k < 0 || p.k > 3) throw std::invalid_argument("launch_rotate_frames: k outside 0..3");
+            b.f[i] = p;
+            const long long total = (p.k & 1) ? (long long)((p.rows + kRotTile - 1) / kRotTile) * ((p.cols + kRotTile - 1) / kRotTile)
+                                              : ((long long)p.rows * ((p.cols + 3) >> 2) + kThreads - 1) / kThreads;
+            blocks = std::max(blocks, total);
+        }
+        if (!blocks) continue;
+        hipLaunchKernelGGL(rotate_frames_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536), (unsigned)m), dim3(kThreads), 0, s, b);
+    }
+}
+
+// rot_gather_kernel: tta_gather_kernel's shape -- one workgroup per pass of the launch, one face per thread, one atomic add per
+//      wavefront on the frame's counter -- with rot_map_face, the code rf_rot_map_face runs on the host, as the mapping.  Nothing is
+//      dropped.  The passes of a frame may arrive from different launches on different streams; the merge sorts on the total order
+//      (score, g), so the append order never shows.
+__global__ __launch_bounds__(kThreads) void rot_gather_kernel(RotGatherParams a) {
+    const int p = blockIdx.x;
+    const RotEntry e = a.table[p];
+    if (e.frame < 0) return;
+    int cnt = a.counts[p];
+    cnt = cnt < 0 ? 0 : cnt < a.faces_per_pass ? cnt : a.faces_per_pass;
+    const int lane = (int)threadIdx.x & 63;
+    Candidate *dst = a.cand + (size_t)e.frame * a.cap;
+    for (int j0 = 0; j0 < cnt; j0 += kThreads) {
+        const int j = j0 + (int)threadIdx.x;
+        const bool keep = j < cnt;
+        float f[15];
+        if (keep) {
+            const float *src = (const float *)(a.faces + ((size_t)p * a.faces_per_pass + j) * a.face_stride);
+            for (int i = 0; i < 15; i++) f[i] = src[i];
+            rot_map_face(e, f, f);
+        }
+        const unsigned long long mask = __ballot(keep);
+        if (!mask) continue;                                     // wave-uniform
+        const int leader = __ffsll((long long)mask) - 1;
+        int base = 0;
+        if (lane == leader) base = atomicAdd(a.cand_count + e.frame, __popcll(mask));
+        base = __shfl(base, leader);
+        if (!keep) continue;
+        const int pos = base + __popcll(mask & ((1ull << lane) - 1ull));
+        if (pos >= a.cap) continue;                              // the counter keeps the true number: the merge reports the overflow
+        Candidate c;
+        c.score = f[0];
+        c.x1 = f[1]; c.y1 = f[2]; c.x2 = f[3]; c.y2 = f[4];
+        for (int i = 0; i < 5; i++) { c.px[i] = f[5 + i]; c.py[i] = f[10 + i]; }
+        c.anchor = e.k * a.rank_stride + j;
+        dst[pos] = c;
+    }
+}
+
+void launch_rot_gather(hipStream_t s, const RotGatherParams &p) {
+    if (p.n <= 0) return;
+    hipLaunchKernelGGL(rot_gather_kernel, dim3(p.n), dim3(kThreads), 0, s, p);
+}
+
 #ifdef RF_KERNEL_TRACE
 extern "C" int rf_trace_select(int kernel_id, unsigned grid) {
     static unsigned long long zeros[kTraceBlocks * kTraceSlots];

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (rf_face, rf_face_batch_spec, rf_face_gate, rf_face_quality, rf_options, rf_redact_spec, rf_tile_spec, rf_track,
-                   rf_motion_spec, rf_pyramid_spec, rf_shot, rf_track_motion, rf_track_spec, rf_track_tag, rf_tta_spec)
+                   rf_motion_spec, rf_pyramid_spec, rf_rot_spec, rf_shot, rf_track_motion, rf_track_spec, rf_track_tag, rf_tta_spec)
 
 PRECISION_FP32, PRECISION_FP16, PRECISION_INT8 = 0, 1, 2
 
@@ -627,6 +627,85 @@ def tta_merge_host(passes, rows: int, cols: int, net_h: int, net_w: int, nms_thr
     k = max(0, min(count.value, cap, sp.max_faces or md))
     return (_faces_to_array(out, max(cap, 1))[:k], int(count.value), np.array(votes[:k], np.int32), np.array(src[:k], np.int32),
             st == _lib.RF_ERR_TRUNCATED)
+
+
+def rot_spec(rots: int = 0, vote: bool = False, max_faces: int = 0) -> rf_rot_spec:
+    """An rf_rot_spec: rots (bit k: also detect every frame turned by k quarter turns counter-clockwise; 0 = all four), vote (a kept
+    box becomes the score-weighted mean of the candidates it suppressed; off, the default: the plain greedy NMS over all passes),
+    max_faces (merged faces kept per frame; 0 = the engine's max_detections)."""
+    sp = rf_rot_spec()
+    sp.struct_size = C.sizeof(rf_rot_spec)
+    sp.rots, sp.vote, sp.max_faces = int(rots), 1 if vote else 2, int(max_faces)
+    return sp
+
+
+def _rot_list(rots: int):
+    return [k for k in range(4) if (int(rots) or 15) >> k & 1]
+
+
+def rot_map_face(face, k: int, rows: int, cols: int, net_h: int, net_w: int) -> np.ndarray:
+    """rf_rot_map_face (host only, no GPU): the face (a Detection or 15 floats) of pass k (the rows x cols frame turned by k quarter
+    turns counter-clockwise) in source-frame pixels, as 15 float32."""
+    lib = _lib.load_library()
+    f = rf_face.from_buffer_copy(_face_rows([face])[0].tobytes())
+    g = rf_face()
+    st = lib.rf_rot_map_face(int(rows), int(cols), int(net_h), int(net_w), int(k), C.byref(f), C.byref(g))
+    if st < 0:
+        raise _lib.RFError(st, "rf_rot_map_face: bad frame, net size or rotation")
+    return _faces_to_array(C.pointer(g), 1)[0]
+
+
+def rot_merge_host(passes, rows: int, cols: int, net_h: int, net_w: int, nms_threshold: float, max_detections: int, rots: int = 0,
+                   vote: bool = False, max_faces: int = 0, cap: Optional[int] = None, spec=None):
+    """rf_rot_merge_host (host only, no GPU): mapping and merge of ONE frame -- passes[p]: the faces of the p-th rotation of `rots` in
+    ascending k (a (j, 15) array, rows of 15 floats or Detections).  Returns (faces (j, 15) float32 in merge order, count: the true
+    number of heads, votes (j,) int32, src_rot (j,) int32, truncated, frame_rot, rot_score (4,) float32)."""
+    lib = _lib.load_library()
+    sp = spec if spec is not None else rot_spec(rots, vote, max_faces)
+    md = int(max_detections)
+    if md < 1:
+        raise _lib.RFError(_lib.RF_ERR_INVALID_ARG, "rf_rot_merge_host: max_detections must be positive")
+    rows_ = [_face_rows(p) for p in passes]
+    flat = np.zeros((max(len(rows_), 1), md, 15), np.float32)
+    pc = (C.c_int * max(len(rows_), 4))()
+    for p, r in enumerate(rows_):
+        flat[p, :min(len(r), md)] = r[:md]
+        pc[p] = len(r)
+    cap = int(cap) if cap is not None else (sp.max_faces or md)
+    out = (rf_face * max(cap, 1))()
+    votes, src = (C.c_int * max(cap, 1))(), (C.c_int * max(cap, 1))()
+    count, frame_rot = C.c_int(0), C.c_int(-1)
+    score = (C.c_float * 4)()
+    if 0 <= sp.rots <= 15 and len(rows_) != len(_rot_list(sp.rots)):
+        raise _lib.RFError(_lib.RF_ERR_INVALID_ARG, "rf_rot_merge_host: one pass per rotation of rots")
+    st = lib.rf_rot_merge_host(C.byref(sp), int(rows), int(cols), int(net_h), int(net_w), float(nms_threshold), md,
+                               flat.ctypes.data_as(C.POINTER(rf_face)), pc, out, cap, C.byref(count), votes, src, C.byref(frame_rot), score)
+    if st < 0 and st != _lib.RF_ERR_TRUNCATED:
+        raise _lib.RFError(st, "rf_rot_merge_host: bad spec, frame, net size or counts")
+    k = max(0, min(count.value, cap, sp.max_faces or md))
+    return (_faces_to_array(out, max(cap, 1))[:k], int(count.value), np.array(votes[:k], np.int32), np.array(src[:k], np.int32),
+            st == _lib.RF_ERR_TRUNCATED, int(frame_rot.value), np.array(score[:], np.float32))
+
+
+def rotate_host(frame: np.ndarray, k: int, out: Optional[np.ndarray] = None) -> np.ndarray:
+    """rf_rotate_host (host only, no GPU): the BGR frame turned by k (0..3) quarter turns counter-clockwise, np.rot90(frame, k).
+    `out`: a uint8 (rows_k, >= cols_k, 3) view to write into (its row pitch is kept); returned either way."""
+    lib = _lib.load_library()
+    if frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3:
+        raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
+    if frame.strides[2] != 1 or frame.strides[1] != 3:
+        frame = np.ascontiguousarray(frame)
+    rows, cols = frame.shape[:2]
+    dr, dc = (cols, rows) if int(k) & 1 else (rows, cols)
+    if out is None:
+        out = np.zeros((dr, dc, 3), np.uint8)
+    if out.dtype != np.uint8 or out.ndim != 3 or out.shape[2] != 3 or out.strides[2] != 1 or out.strides[1] != 3 or out.shape[0] < dr:
+        raise ValueError("out must be a uint8 (rows_k, cols_k, 3) array or row-pitched view")
+    st = lib.rf_rotate_host(frame.ctypes.data, rows, cols, frame.strides[0] if rows else 3 * cols, int(k), out.ctypes.data,
+                            out.strides[0] if out.shape[0] else 3 * dc)
+    if st < 0:
+        raise _lib.RFError(st, "rf_rotate_host: k must be in 0..3 and the destination pitch at least cols_k * 3")
+    return out
 
 
 def pyramid_spec(levels: int = 0, overlap: int = 0, edge: int = 0, full_frame: bool = True, max_faces: int = 0,
@@ -1476,6 +1555,97 @@ class RetinaFace:
         is row y of the BGR frame at src_ptr (row pitch `step`, any alignment) mirrored left-right.  Both in device memory."""
         _lib.check(self._lib.rf_mirror_device(self._h, src_ptr, int(rows), int(cols), int(step if step is not None else 3 * cols), dst_ptr,
                                               int(dst_step if dst_step is not None else 3 * cols)), self._h)
+
+    # ------------------------------------------------------------------ rotation-robust detection
+    def detect_rotated(self, imgs: Sequence[np.ndarray], threshold: float = 0.5, rots: int = 0, vote: bool = False, max_faces: int = 0,
+                       return_votes: bool = False):
+        """rf_detect_rot_batch: every frame is detected as it is and turned by one, two and three quarter turns counter-clockwise
+        (rots: a bit mask of the turns to run, 0 = all four; the copies are made on the device); the faces of all passes are moved
+        back and merged on the device.  Returns per frame the merged detections in SOURCE-FRAME pixels (anchor_index is -1); with
+        return_votes also, per frame, how many candidates each face merged and the rotation (0..3) its head came from.
+        self.rot_counts holds the true merged counts, self.frame_rot per frame the quarter turns counter-clockwise that make it
+        upright (-1: no face), self.rot_score the (n, 4) score sums behind that."""
+        n = len(imgs)
+        ptrs = (C.c_void_p * max(n, 1))()
+        rows, cols, steps = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
+        keep = []
+        for i, im in enumerate(imgs):
+            if im is None or im.size == 0:
+                ptrs[i], rows[i], cols[i], steps[i] = None, 0, 0, 0
+                continue
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
+            if im.strides[2] != 1 or im.strides[1] != 3:
+                im = np.ascontiguousarray(im)
+            keep.append(im)
+            ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
+        return self._run_rot(self._lib.rf_detect_rot_batch, ptrs, rows, cols, steps, n, threshold, rot_spec(rots, vote, max_faces),
+                             return_votes)
+
+    def detect_rotated_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], threshold: float = 0.5,
+                              steps: Optional[Sequence[int]] = None, rots: int = 0, vote: bool = False, max_faces: int = 0,
+                              return_votes: bool = False):
+        """rf_detect_rot_batch_device: detect_rotated for frames resident in device memory (0 / None: an empty frame)."""
+        n = len(ptrs)
+        p = (C.c_void_p * max(n, 1))(*ptrs)
+        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
+        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        return self._run_rot(self._lib.rf_detect_rot_batch_device, p, r, c, s, n, threshold, rot_spec(rots, vote, max_faces), return_votes)
+
+    def _collect_rot(self, out, counts, votes, src, frame_rot, score, n, cap, return_votes):
+        kept = getattr(self, "tta_counts", None)             # _collect_tta's layout is this call's too; its counts are not
+        res = self._collect_tta(out, counts, votes, src, n, cap, return_votes)
+        self.rot_counts, self.tta_counts = self.tta_counts, kept
+        self.frame_rot = [int(frame_rot[i]) for i in range(n)]
+        self.rot_score = np.array(score[:4 * n], np.float32).reshape(n, 4)
+        return res
+
+    def _run_rot(self, fn, ptrs, rows, cols, steps, n, threshold, sp, return_votes):
+        cap = sp.max_faces or self.max_detections
+        out = (rf_face * max(n * cap, 1))()
+        counts, frame_rot = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
+        score = (C.c_float * max(4 * n, 1))()
+        votes, src = (C.c_int * max(n * cap, 1))(), (C.c_int * max(n * cap, 1))()
+        st = _lib.check(fn(self._h, ptrs, rows, cols, steps, n, float(threshold), C.byref(sp), out, cap, counts, votes, src, frame_rot,
+                           score), self._h)
+        self.truncated = st == _lib.RF_ERR_TRUNCATED
+        return self._collect_rot(out, counts, votes, src, frame_rot, score, n, cap, return_votes)
+
+    def rot_merge(self, rows: Sequence[int], cols: Sequence[int], per_pass_faces, rots: int = 0, vote: bool = False, max_faces: int = 0,
+                  cap_per_image: Optional[int] = None, return_votes: bool = False):
+        """rf_rot_merge_device: mapping and merge of per-pass faces the caller supplies -- per_pass_faces[i][p]: the faces of the p-th
+        rotation of `rots` (ascending k) of frame i (a (j, 15) array, rows of 15 floats or Detections, at most max_detections).  No
+        forward pass runs.  Returns as detect_rotated; self.rot_counts, self.frame_rot and self.rot_score as there."""
+        n = len(rows)
+        sp = rot_spec(rots, vote, max_faces)
+        md = self.max_detections
+        per = len(_rot_list(rots)) if 0 <= int(rots) <= 15 else 4
+        if any(len(frame) != per for frame in per_pass_faces) or len(per_pass_faces) != n:
+            raise ValueError("per_pass_faces: one list of %d passes per frame" % per)
+        passes = [_face_rows(f) for frame in per_pass_faces for f in frame]
+        flat = np.zeros((max(len(passes), 1), md, 15), np.float32)
+        pc = (C.c_int * max(len(passes), 1))()
+        for p, r in enumerate(passes):
+            flat[p, :min(len(r), md)] = r[:md]
+            pc[p] = len(r)
+        cap = int(cap_per_image) if cap_per_image is not None else (sp.max_faces or md)
+        out = (rf_face * max(n * cap, 1))()
+        counts, frame_rot = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
+        score = (C.c_float * max(4 * n, 1))()
+        votes, src = (C.c_int * max(n * cap, 1))(), (C.c_int * max(n * cap, 1))()
+        st = _lib.check(self._lib.rf_rot_merge_device(self._h, (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols), n, C.byref(sp),
+                                                      flat.ctypes.data_as(C.POINTER(rf_face)), pc, out, cap, counts, votes, src, frame_rot,
+                                                      score), self._h)
+        self.truncated = st == _lib.RF_ERR_TRUNCATED
+        return self._collect_rot(out, counts, votes, src, frame_rot, score, n, cap, return_votes)
+
+    def rotate_device(self, src_ptr: int, rows: int, cols: int, k: int, dst_ptr: int, step: Optional[int] = None,
+                      dst_step: Optional[int] = None):
+        """rf_rotate_device: the rotate kernel on its own -- the destination (rows dst_step bytes apart, cols_k * 3 bytes written) is
+        the BGR frame at src_ptr (row pitch `step`, any alignment) turned by k quarter turns counter-clockwise.  Both in device memory."""
+        dc = rows if int(k) & 1 else cols
+        _lib.check(self._lib.rf_rotate_device(self._h, src_ptr, int(rows), int(cols), int(step if step is not None else 3 * cols), int(k),
+                                              dst_ptr, int(dst_step if dst_step is not None else 3 * dc)), self._h)
 
     # ------------------------------------------------------------------ zoom-pyramid detection
     def detect_pyramid(self, imgs: Sequence[np.ndarray], threshold: float = 0.5, levels: int = 0, overlap: int = 0, edge: int = 0,
