@@ -337,11 +337,10 @@ int rf_detect_face_batch_gated(rf_handle h, const uint8_t *const *bgr, const int
  *            than the net in some dimension the whole frame, shrunk as rf_detect_batch_device shrinks it, is pass T.  A frame that fits
  *            the net has the plan "one tile, no extra pass".  More than 1024 passes: RF_ERR_INVALID_ARG.
  *   pass     the result of pass t is exactly what rf_detect_batch_device returns for the view {ptr + y0 * step + 3 * x0, th, tw, step}
- *            (the full-frame pass: for the whole frame) at the call's threshold: up to max_detections faces in score order -- to
- *            the byte when that call holds the passes of ALL frames of the tiled call in plan order, which is the call the engine
- *            makes.  (As with rf_detect_batch_device itself, the last bits of a view's result can depend on what shares its launch:
- *            conv0 sums an aligned dense frame in another order than a view with a row pitch, and a launch that holds an oversize
- *            frame reads every image through the dense canvas.)
+ *            (the full-frame pass: for the whole frame) at the call's threshold: up to max_detections faces in score order, to
+ *            the byte.  (As with rf_detect_batch_device itself, the last bits of a view's result depend on how it lies in memory --
+ *            conv0 sums an aligned dense frame in another order than a view with a row pitch -- but not on what shares its launch:
+ *            only a frame larger than the net is read from the resize canvas, a view that fits is read where it lies.)
  *   edge     in tile coordinates, fp32: face (x1, y1, x2, y2) of tile (x0, y0, tw, th) is dropped when  x0 > 0 && x1 < (float)edge,
  *            y0 > 0 && y1 < (float)edge,  x0 + tw < cols && x2 > (float)(tw - 1 - edge)  or  y0 + th < rows && y2 > (float)(th - 1 - edge):
  *            boxes that reach a tile side which is not a frame side.  The full-frame pass drops nothing.
@@ -723,8 +722,8 @@ int rf_tracker_read_motion(rf_tracker tracker, int stream, rf_track_motion *out,
  *   passes   pass 0 is the frame; pass 1 (flip on) the frame mirrored, M[y][x] = F[y][cols - 1 - x].  Over a call the passes are
  *            frame-major: f0, f0 mirrored, f1, f1 mirrored ...  The result of a pass is exactly what rf_detect_batch_device returns for
  *            that image at the call's threshold -- to the byte when that ONE call holds all passes of the TTA call in that order, the
- *            mirrors as dense frames of their own (the caveat of the tiled call's views: the last bits of an image's result can depend on
- *            what shares its launch).  Frames larger than the net are shrunk as always, in both passes.  A NULL / 0 x 0 frame finds nothing.
+ *            mirrors as dense frames of their own (the caveat of the tiled call's views: the last bits of an image's result depend on
+ *            how it lies in memory, not on what shares its launch).  Frames larger than the net are shrunk as always, in both passes.  A NULL / 0 x 0 frame finds nothing.
  *   mapping  face k of pass p: all 14 coordinates get one fp32 multiply by rf_frame_scale(rows, cols) (also when it is 1).  For p = 1,
  *            with c = (float)(cols - 1): x1' = c - x2, x2' = c - x1, px'[i] = c - px[perm[i]], py'[i] = py[perm[i]], perm = {1, 0, 2, 4, 3}
  *            (left and right eye, left and right mouth corner change places): one fp32 subtract per x coordinate; y and the score are
@@ -792,7 +791,7 @@ int rf_tta_merge_device(rf_handle h, const int *rows, const int *cols, int n, co
  *            ordinary image of the call: a rotated pass larger than the net is shrunk as always, and its result is exactly what
  *            rf_detect_batch_device returns for that image at the call's threshold -- to the byte when that ONE call holds all passes of
  *            the rotation call in that order, the rotated copies as dense frames of their own (the caveat of the TTA call: the last
- *            bits of an image's result can depend on what shares its launch).  A NULL / 0 x 0 frame finds nothing.  A pass that breaks a
+ *            bits of an image's result depend on how it lies in memory, not on what shares its launch).  A NULL / 0 x 0 frame finds nothing.  A pass that breaks a
  *            frame limit of rf_detect_batch_device: RF_ERR_INVALID_ARG, before any state changes.
  *   mapping  face j of pass k: all 14 coordinates get one fp32 multiply by rf_frame_scale(rows_k, cols_k), the PASS's own shape
  *            ((cols, rows) for odd k), also when it is 1.  Then, with c = (float)(cols - 1) and r = (float)(rows - 1) of the source
@@ -873,7 +872,7 @@ int rf_rot_merge_device(rf_handle h, const int *rows, const int *cols, int n, co
  *            FRAME border, never at the tile border, so neighbouring tiles agree on their overlap.
  *   pass     the result of a pass is exactly what rf_detect_batch_device returns for that image at the call's threshold -- to the byte
  *            when that ONE call holds all passes of the pyramid call in plan order, 1x tiles as ROI views, zoom tiles as dense frames of
- *            their own (the caveat of the tiled call's views: the last bits of an image's result can depend on what shares its launch).
+ *            their own (the caveat of the tiled call's views: the last bits of an image's result depend on how it lies in memory, not on what shares its launch).
  *   mapping  a 1x pass: rf_tile_map_face.  A zoom pass: the edge rule of rf_tile_map_face in tile coordinates against the virtual frame
  *            (z cols, z rows); then every x becomes (x + (float)X0) * inv - off, every y (y + (float)Y0) * inv - off, inv = 1 / z,
  *            off = (z - 1) / 2z (0.25 at 2x, 0.375 at 4x): the pixel-centre correspondence.  Scores are unchanged.  Results are in
@@ -939,10 +938,17 @@ int rf_pyramid_merge_device(rf_handle h, const int *rows, const int *cols, int n
                             const int *pass_counts, rf_face *out, int cap_per_image, int *counts, int *votes, int *src_pass);
 
 /* Asynchronous form of rf_detect_batch_device for serving loops: enqueue returns as soon as the
- * batch is queued on the engine's stream (n <= max_batch); `ticket` identifies one of
- * rf_num_slots() result slots.  rf_wait blocks until that batch has finished and copies its results.
- * Up to rf_num_slots() tickets may be outstanding; the engine merges consecutive enqueues into one launch
- * (options.coalesce) and overlaps launches on options.lanes streams. */
+ * batch is queued on the engine's stream (n <= max_batch); `ticket` identifies that batch until it has been
+ * waited for.  rf_wait blocks until the batch has finished and copies its results; a ticket is waited for once
+ * (a second rf_wait on it is RF_ERR_INVALID_ARG), in any order.  The engine merges consecutive enqueues into one
+ * launch (options.coalesce; INTEGRATION.md states when a launch is closed) and overlaps launches on options.lanes
+ * streams.
+ * rf_num_slots() = lanes * coalesce is the number of outstanding tickets that keeps every lane busy with a full
+ * launch, and the number a caller may always keep outstanding.  The ticket pool behind it holds
+ * 4 * options.lanes * coalesce + 8 tickets: more than rf_num_slots() outstanding tickets are accepted up to that
+ * pool size (a launch whose lane is needed again is collected into its tickets, which keep their results until they
+ * are waited for), then rf_enqueue_batch* returns RF_ERR_INVALID_ARG ("too many outstanding tickets") and changes
+ * nothing: every outstanding ticket still delivers its result. */
 int rf_num_slots(rf_handle h);
 int rf_enqueue_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols,
                             const int *steps, int n, float threshold, int *ticket);
@@ -977,6 +983,10 @@ int rf_num_devices(rf_handle h);
  * GPU and pulled over xGMI before their launch, and the hipMemcpyPeerAsync calls that carried them (frames that follow each other in
  * memory travel as one copy: a contiguous slice of a sharded batch = 1 copy; RF_SCATTER_PER_FRAME=1 in the environment = 1 per frame). */
 int rf_scatter_stats(rf_handle h, long long *frames, long long *copies);
+
+/* The coalescing scheduler in numbers (since rf_create, summed over the handle's engines): launches (super-batches) started by
+ * synchronous calls, enqueues and waits, and the images in them.  Read-only. */
+int rf_launch_stats(rf_handle h, long long *launches, long long *images);
 
 /* Global anchor index (offset(stride) + a*h*w + iy*w + ix, strides 32,16,8) of each
  * detection of image `image` of the most recent completed batch, in the same order as out[]. */

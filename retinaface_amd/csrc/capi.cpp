@@ -1458,6 +1458,11 @@ int rf_scatter_stats(rf_handle h, long long *frames, long long *copies) {
     return guarded(h, [&]() -> int { *frames = 0; *copies = 0; h->eng->scatter_stats(frames, copies); return RF_OK; });
 }
 
+int rf_launch_stats(rf_handle h, long long *launches, long long *images) {
+    if (!h || !launches || !images) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int { *launches = 0; *images = 0; h->eng->launch_stats(launches, images); return RF_OK; });
+}
+
 int rf_wait(rf_handle h, int ticket, rf_face *out, int cap_per_image, int *counts) {
     if (!h) return RF_ERR_INVALID_ARG;
     return guarded(h, [&]() -> int {

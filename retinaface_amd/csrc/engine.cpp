@@ -2096,6 +2096,7 @@ public:
     void host_forget(const void *ptr) override { drop_range(ptr, false); }
     void invalidate_residency() override { residency_.clear(); }
     void scatter_stats(long long *frames, long long *copies) const override { *frames += scattered_frames_; *copies += peer_copies_; }
+    void launch_stats(long long *launches, long long *images) const override { *launches += launches_; *images += launched_images_; }
 
     // tickets the caller may keep outstanding before it has to wait: every lane can hold a full super-batch
     int num_slots() const override { return (int)lanes_.size() * opt_.coalesce; }
@@ -2590,11 +2591,18 @@ private:
         pending_lane_ = -1;
         const int n = s.n_images;
         if (n == 0) return;
+        launches_++;
+        launched_images_ += n;
         *s.h_params = RunParams{s.threshold, nms_threshold_, n, 0};
         if (s.need_resize) {
+            // Only the frames that are larger than the net are read from the canvas.  A frame that fits keeps its own descriptor, as in a
+            // launch without a resize: the stems choose their staging path (raw rows / general, different conv0 K order) from a frame's
+            // pointer, pitch and width, so a fitting frame read from the canvas instead could differ in the last bits from the same frame in
+            // a launch that holds no oversize frame -- an image's result must not depend on what it shares a launch with.
             const int mb = cap_images_;
             for (int i = 0; i < n; i++)
-                s.h_frames[mb + i] = FrameDesc{s.d_canvas + (size_t)i * net_h_ * net_w_ * 3, net_h_, net_w_, net_w_ * 3, 0};
+                if (s.h_frames[i].rows > net_h_ || s.h_frames[i].cols > net_w_)
+                    s.h_frames[mb + i] = FrameDesc{s.d_canvas + (size_t)i * net_h_ * net_w_ * 3, net_h_, net_w_, net_w_ * 3, 0};
         }
         if (s.copy2_used) {             // uploads that went through the second copy stream: the launch waits for them
             RF_HIP(hipEventRecord(s.copy2_done, s.copy2));
@@ -3259,6 +3267,8 @@ private:
     long staged_pieces_ = 0;
     long scattered_frames_ = 0;               // device frames that arrived from another device
     long peer_copies_ = 0;                    // ... in this many hipMemcpyPeerAsync calls (one per contiguous run of frames)
+    long long launches_ = 0;                  // super-batches launched (launch_pending()) ...
+    long long launched_images_ = 0;           // ... and the images in them
     std::vector<float> ratios_;                // the network preset's anchor ratios (empty: a preset without anchors)
     int na_ = 2;                               // anchors per cell the preset decodes (head_a_: what the model's heads carry)
     std::unique_ptr<ParallelCopier> copier_;

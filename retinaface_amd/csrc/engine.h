@@ -356,6 +356,8 @@ public:
     virtual void invalidate_residency() = 0;
     // device frames that arrived from another device since the handle was built, and the peer copies that carried them
     virtual void scatter_stats(long long *frames, long long *copies) const = 0;
+    // super-batches launched since the handle was built and the images in them (added to what the arguments hold)
+    virtual void launch_stats(long long *launches, long long *images) const = 0;
 
     virtual int last_anchor_indices(int image, int32_t *out, int cap) const = 0;
     virtual int last_candidate_counts(int *counts, int n) const = 0;

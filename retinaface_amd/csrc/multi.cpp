@@ -199,6 +199,9 @@ public:
     void scatter_stats(long long *frames, long long *copies) const override {
         for (auto &e : eng_) e->scatter_stats(frames, copies);
     }
+    void launch_stats(long long *launches, long long *images) const override {
+        for (auto &e : eng_) e->launch_stats(launches, images);
+    }
 
     int last_anchor_indices(int image, int32_t *out, int cap) const override {
         if (last_from_wait_ >= 0) return eng_[last_from_wait_]->last_anchor_indices(image, out, cap);

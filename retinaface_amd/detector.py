@@ -1739,11 +1739,11 @@ class RetinaFace:
                                             int(x0), int(y0), int(tw), int(th), dst_ptr,
                                             int(dst_step if dst_step is not None else 3 * tw)), self._h)
 
-    def enqueue_device(self, ptrs, rows, cols, threshold: float = 0.5) -> int:
+    def enqueue_device(self, ptrs, rows, cols, threshold: float = 0.5, steps: Optional[Sequence[int]] = None) -> int:
         n = len(ptrs)
         p = (C.c_void_p * n)(*ptrs)
         r, c = (C.c_int * n)(*rows), (C.c_int * n)(*cols)
-        s = (C.c_int * n)(*[3 * x for x in cols])
+        s = (C.c_int * n)(*(steps if steps is not None else [3 * x for x in cols]))
         t = C.c_int()
         _lib.check(self._lib.rf_enqueue_batch_device(self._h, p, r, c, s, n, float(threshold), C.byref(t)), self._h)
         return t.value
@@ -1783,6 +1783,12 @@ class RetinaFace:
         f, c = C.c_longlong(), C.c_longlong()
         _lib.check(self._lib.rf_scatter_stats(self._h, C.byref(f), C.byref(c)), self._h)
         return {"frames": f.value, "peer_copies": c.value}
+
+    def launch_stats(self) -> dict:
+        """rf_launch_stats: super-batches launched since the handle was built, and the images in them."""
+        l, i = C.c_longlong(), C.c_longlong()
+        _lib.check(self._lib.rf_launch_stats(self._h, C.byref(l), C.byref(i)), self._h)
+        return {"launches": l.value, "images": i.value}
 
     def prepare_device_batch(self, ptrs, rows, cols, steps=None):
         """Build the C argument arrays of rf_enqueue_batch_device once for a batch of device frames that is submitted

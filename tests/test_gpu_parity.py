@@ -1660,13 +1660,7 @@ def test_every_fused_op_on_photometric_variants(rfa, oracles, stem, prec):
 EDGE_SIZES = ((32, 32), (32, 1280), (1280, 32), (64, 96), (352, 608))
 
 
-def _edge_frame(base_frame, hw, k=0):
-    """A net-sized frame cut from the fixture photo (the photo with its mirror image below it, for heights over 896), centred on face 0 and
-    shifted by k for the batch of distinct frames."""
-    tall = np.concatenate([base_frame, base_frame[::-1]], axis=0)
-    y0 = int(np.clip(342 - hw[0] // 2 + 5 * k, 0, tall.shape[0] - hw[0]))
-    x0 = int(np.clip(517 - hw[1] // 2 + 11 * k, 0, tall.shape[1] - hw[1]))
-    return np.ascontiguousarray(tall[y0:y0 + hw[0], x0:x0 + hw[1]])
+from schedule_ref import edge_frame as _edge_frame      # noqa: E402  (the frame recipe lives with the scheduler tests' pool: one copy)
 
 
 def _float_engine_against_the_oracle(det, od, stem, frame, prec, label):

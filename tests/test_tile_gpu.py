@@ -184,10 +184,9 @@ def mosaic(base_frame):
 
 def parts_of_call(det, frames, full=True, overlap=OV, edge=EDGE, thr=0.5):
     """frames: (ptr, rows, cols, step) of one tiled call.  tile_ref.merge, per frame, over what ONE rf_detect_batch_device call returns
-    for the views of all frames in plan order -- the call the engine itself makes.  One call, because the last bits of a view's
-    result depend on what shares its launch (conv0 sums an aligned dense frame in another order than a view with a row pitch, and a
-    launch that holds an oversize frame reads every image through the dense canvas): per-frame calls are chunked differently once a
-    call spans several launches."""
+    for the views of all frames in plan order -- the call the engine itself makes.  (One call for brevity: a view's result does not
+    depend on what shares its launch -- a view that fits the net is read where it lies even when the oversize full-frame pass puts the
+    resize kernel into the launch -- which test_fused_call_equals_the_merge_of_its_own_passes checks pass by pass.)"""
     plans = [tr.plan(r, c, det.net_h, det.net_w, overlap, full) for _, r, c, _ in frames]
     ptrs = [p + int(t[1]) * st + 3 * int(t[0]) for (p, _, _, st), tiles in zip(frames, plans) for t in tiles]
     res = det.detect_device(ptrs, [int(t[3]) for tiles in plans for t in tiles], [int(t[2]) for tiles in plans for t in tiles], thr,
@@ -247,11 +246,17 @@ def test_fused_call_equals_the_merge_of_its_own_passes(rfa, mosaic, crop448, pre
         return
     # the frame as an odd-pointer, odd-step ROI
     keep, rptr, rstep = roi_view(mosaic)
-    want_roi, _ = parts(det, rptr, 896, 1280, rstep)
+    want_roi, passes_roi = parts(det, rptr, 896, 1280, rstep)
     got_roi, tiles_roi = det.detect_tiled_device([rptr], [896], [1280], 0.5, steps=[rstep], overlap=OV, edge=EDGE, return_tiles=True)
     check_tiled(got_roi, tiles_roi, det.tiled_counts, 0, want_roi)
-    if not kw:                 # one launch: every image is read through the dense canvas, so the same pixels give the same bytes wherever
-        assert rows_of(got_roi[0]).tobytes() == want[0].tobytes()          # they lie; split, the 1:1 launch reads aligned and odd views differently
+    # Every pass detected ALONE gives the bytes it gives inside the call's launches, whatever shares them and however the call is split:
+    # only the oversize full-frame pass is read from the resize canvas, a view that fits is read where it lies.  (Until the scheduler
+    # tests, a launch that held an oversize frame read every image from the canvas: the one-launch call then gave the aligned frame and
+    # the odd view the same bytes, and each of them other bytes than the same view in a launch without the full-frame pass.)
+    for p0, st, ps in ((ptr, 3 * 1280, passes), (rptr, rstep, passes_roi)):
+        for t, rows_in_call in zip(tr.plan(896, 1280, det.net_h, det.net_w, OV, True), ps):
+            alone = det.detect_device([p0 + int(t[1]) * st + 3 * int(t[0])], [int(t[3])], [int(t[2])], 0.5, steps=[st])[0]
+            assert rows_of(alone).tobytes() == rows_in_call.tobytes(), (st, list(t))
     assert len(got_roi[0]) == want[1]
     # host frames: uploaded once, the tiles are views of the copy; an empty frame in between
     hgot, htiles = det.detect_tiled([mosaic, None, crop448], 0.5, overlap=OV, edge=EDGE, return_tiles=True)
