@@ -161,6 +161,17 @@ public:
     void detectRedacted(vector<cv::Mat> &imgs, float threshold = 0.5, const rf_redact_spec *spec = nullptr);
     const vector<vector<int32_t>> &redactedPixels() const { return redactPixels_; }
 
+    /* additive: overlays (rf_detect_overlay_batch / rf_detect_track_overlay_batch_device): what the reference's detect() ends with,
+       cv::rectangle + cv::circle per face, on the device.  detectOverlay() is detectBatchImages() plus boxes, landmark discs and
+       optional score labels drawn IN PLACE into the Mats' pixels (rf_overlay_spec; nullptr = the reference's look).
+       detectTrackedOverlay() is the tracked call on frames that already live in device memory (pointer, rows, cols and row step per
+       frame): ids as labels or colours, coasting tracks dashed; it fills lastBatchResult(), lastTrackTags() and lastEndedTracks().
+       overlayPixels()[i][r] is the number of pixels region r of image i painted. */
+    void detectOverlay(vector<cv::Mat> &imgs, float threshold = 0.5, const rf_overlay_spec *spec = nullptr);
+    void detectTrackedOverlay(const vector<void *> &deviceFrames, const vector<int> &rows, const vector<int> &cols, const vector<int> &steps,
+                              rf_tracker tracker, const vector<int> &streams, float threshold = 0.5, const rf_overlay_spec *spec = nullptr);
+    const vector<vector<int32_t>> &overlayPixels() const { return overlayPixels_; }
+
     /* `scale` of RetinaFace.cpp:585-589: multiply lastResult() coordinates by it for source-frame pixels (:732-739, commented) */
     float frameScale(const Mat &img) const { return rf_frame_scale(h_, img.rows, img.cols); }
 
@@ -194,6 +205,7 @@ private:
     vector<vector<rf_track_tag>> trackTags_;
     vector<vector<rf_track>> trackEnded_;
     vector<vector<int32_t>> redactPixels_;
+    vector<vector<int32_t>> overlayPixels_;
     map<rf_tracker, size_t> shotBytes_;
     vector<vector<uint8_t>> shots_;
     vector<vector<rf_shot>> shotInfo_;

@@ -672,6 +672,105 @@ int rf_detect_track_redact_batch_device(rf_handle h, void *const *d_bgr, const i
                                         const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_counts,
                                         const rf_redact_spec *spec, int32_t *pixels, int *region_counts);
 
+/* ---- Overlays: draw the boxes, landmarks and labels of faces and tracks into frames IN PLACE, on the device -- what the reference's
+ * detect() ends with (cv::rectangle(src, rect, Scalar(0,0,255), 2) and cv::circle(src, pt, 1, Scalar(0,255,0), 2) per face,
+ * RetinaFace.cpp:1083-1091).  DESIGN.md "Overlays" holds the definition; tests/overlay_ref.py restates it in numpy; every result is
+ * byte-exact against it.  Frames are CV_8UC3 BGR with any pointer and row step.  Integer-exact apart from the fp32 scaling (one
+ * rounding per operation, never contracted).  With t = thickness, r = radius, f = font_scale, a = alpha:
+ *   region   of a face with box x1, y1, x2, y2 at coord_scale s: b = box * s (also for s = 1); w = bx2 - bx1, h = by2 - by1.  INVALID (paints
+ *            nothing) unless bx1, by1, bx2, by2, w, h are all finite and w >= 0, h >= 0.  Each coordinate is clamped to [-4096, 8192];
+ *            x0 = floor(bx1), y0 = floor(by1), x1 = floor(bx2), y1 = floor(by2); o = t / 2 (integer division).  The outer rectangle is
+ *            O = [x0 - o, x1 + o] x [y0 - o, y1 + o], inclusive.
+ *   outline  the pixels of O that are not in [x0 - o + t, x1 + o - t] x [y0 - o + t, y1 + o - t] (when that inner rectangle is empty the
+ *            outline is all of O).  The region of a COASTING track is dashed: only the pixels with
+ *            ((x - (x0 - o)) + (y - (y0 - o))) / (2 t) even.
+ *   discs    detected faces only (a coasting track has none; radius < 0: nobody has any).  Point k has the centre
+ *            (floor(clamp(px[k] * s)), floor(clamp(py[k] * s))); a point with a non-finite product is skipped.  Its disc is the pixels
+ *            with dx * dx + dy * dy <= r * r.
+ *   label    n digits.  RF_OVERLAY_LABEL_SCORE: v = (int)(score * 100.f) clamped to 0..99, NaN -> 0, always two digits (of a coasting
+ *            track: the score of its box).  RF_OVERLAY_LABEL_ID: the decimal digits of id mod 1 000 000 without leading zeros; no label
+ *            when id <= 0 (faces tagged RF_TRACK_UNTRACKED and faces without ids included).  The plate is PW = f + 6 f n wide and
+ *            PH = 9 f tall; its left edge is x0 - o, its rows are [y0 - o - PH, y0 - o - 1], or [y0 - o, y0 - o + PH - 1] when that top
+ *            row is < 0.  Digit j, glyph bit (gx, gy) (gx 0..4 from the left, gy 0..6 from the top) covers the f x f square at
+ *            plate-relative (f + 6 f j + f gx, f + f gy).  The glyphs are 5 x 7, rows top to bottom, most significant bit on the left:
+ *              0: 0E 11 13 15 19 11 0E   1: 04 0C 04 04 04 04 0E   2: 0E 11 01 02 04 08 1F   3: 1F 02 04 02 01 11 0E   4: 02 06 0A 12 1F 02 02
+ *              5: 1F 10 1E 01 01 11 0E   6: 06 08 10 1E 11 11 0E   7: 1F 01 02 04 08 08 08   8: 0E 11 11 0E 11 11 0E   9: 0E 11 11 0F 01 02 0C
+ *   colour   of a region: `box`; with color_by_id and id > 0 the palette entry id & 7 of (0,0,255) (0,255,0) (255,0,0) (0,255,255)
+ *            (255,0,255) (255,255,0) (0,128,255) (255,128,0) (B, G, R).  Plate and outline take the region's colour, glyph pixels `text`,
+ *            discs `point`.
+ *   list     of image i: exactly redaction's -- its faces k < min(counts[i], max_regions) in score order, then with a tracker its
+ *            stream's live tracks with 1 <= missed <= coast in ascending slot order at `last` (with a motion tracker at the predicted
+ *            box), their ids the tracks'; cut at max_regions.
+ *   owner    within a region the priority is glyph > plate > disc (lower k first) > outline.  A pixel is painted by the lowest-indexed
+ *            region that has any primitive covering it, and takes that region's highest-priority primitive there.
+ *   value    out = (orig * (255 - a) + colour * a + 127) / 255 per channel, of the ORIGINAL byte.  Every painted pixel is painted once;
+ *            every other byte of the frame and of its row padding is untouched.  Everything is clipped to [0, cols) x [0, rows).
+ *   results  pixels[i * max_regions + r] (may be NULL): the pixels region r painted; region_counts[i] (may be NULL): the length of the
+ *            list before the cut; a cut list returns RF_ERR_TRUNCATED.
+ * There is no fused redact-plus-overlay call: a caller follows a redacting call with rf_overlay_device on the faces it returned. */
+enum { RF_OVERLAY_LABEL_NONE = 0, RF_OVERLAY_LABEL_SCORE = 1, RF_OVERLAY_LABEL_ID = 2 };
+typedef struct rf_overlay_spec {   /* 40 bytes; a field of 0 means its default, a NULL spec all defaults */
+    uint32_t struct_size;   /* sizeof(rf_overlay_spec) */
+    int32_t thickness;      /* of the outline, 1..16; 0 = 2 (the reference's) */
+    int32_t radius;         /* of a landmark disc, 1..16; 0 = 2; negative = no landmarks */
+    uint8_t box[3];         /* B, G, R of outline and plate; all zero (and colors_set 0) = (0, 0, 255), the reference's */
+    uint8_t colors_set;     /* 1: box, point and text are taken as they are, so that all zero is black; 0 or 1 */
+    uint8_t point[3];       /* of the discs; all zero = (0, 255, 0), the reference's */
+    uint8_t alpha;          /* 1..255; 0 = 255 (opaque) */
+    uint8_t text[3];        /* of the glyphs; all zero = (255, 255, 255) */
+    uint8_t color_by_id;    /* 0 / 1: a region with id > 0 takes its colour from the palette */
+    int32_t label;          /* RF_OVERLAY_LABEL_NONE / _SCORE / _ID */
+    int32_t font_scale;     /* pixels per glyph bit, 1..8; 0 = 2 */
+    int32_t max_regions;    /* as rf_redact_spec.max_regions */
+    int32_t coast;          /* as rf_redact_spec.coast */
+} rf_overlay_spec;
+
+/* Host only, no GPU, no handle -- the same code the kernels run, compiled for the host.  rf_overlay_region: the record of one face with
+ * track id `id` (0 = none): out = x0, y0, x1, y1, the bounding rectangle of everything it paints bx0, by0, bx1, by1 (inclusive,
+ * unclipped), digit count n, the digits (digit j in bits 4 j .. 4 j + 3), plate left, plate top, colour (B | G << 8 | R << 16), a mask of the
+ * points that have a disc, the five centres cx[5], cy[5]: 24 values.  Returns 1 (valid), 0 (invalid region: out is all zero) or
+ * RF_ERR_INVALID_ARG (bad spec, NULL argument, rows or cols < 0). */
+int rf_overlay_region(const rf_overlay_spec *spec, const rf_face *face, int64_t id, float coord_scale, int rows, int cols, int32_t out[24]);
+/* Draws into a whole frame in place in HOST memory (the CPU counterpart of rf_overlay_device for one image without a tracker; a usable
+ * fallback).  ids: one per face, or NULL = none.  pixels: min(count, max_regions) counts, may be NULL.  Returns 0, RF_ERR_TRUNCATED
+ * (count > max_regions: the first max_regions faces were drawn) or RF_ERR_INVALID_ARG, which changes nothing. */
+int rf_overlay_host(const rf_overlay_spec *spec, uint8_t *bgr, int rows, int cols, int step, const rf_face *faces, const int64_t *ids,
+                    int count, float coord_scale, int32_t *pixels);
+
+/* Draws faces the CALLER supplies (host memory, as rf_redact_device; ids: NULL or ids[i * cap_per_image + k]) in place in
+ * device-resident frames; no forward pass runs.  coord_scale: per image, NULL = 1.  tracker may be NULL; with one, stream_of_image[i]
+ * names the stream whose coasting tracks (the tracker's CURRENT table) are drawn dashed in image i, -1 = faces only; a stream may appear
+ * at most once per call.  A NULL / 0 x 0 frame is skipped.  Refused before any state changes, as by rf_redact_device: a bad spec, a
+ * NULL frame array, two frames of the call whose byte ranges overlap (RF_ERR_INVALID_ARG), a frame resident on another GPU, a
+ * multi-device handle (RF_ERR_UNSUPPORTED). */
+int rf_overlay_device(rf_handle h, void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n, const rf_face *faces,
+                      const int64_t *ids, int cap_per_image, const int *counts, const float *coord_scale, const rf_overlay_spec *spec,
+                      rf_tracker tracker, const int *stream_of_image, int32_t *pixels, int *region_counts);
+/* Measurement hook: the time of the two overlay launches of the handle's most recent rf_overlay_device call, between two HIP events on
+ * its stream (the upload and the copy-out are outside).  RF_ERR_INVALID_ARG before the first such call. */
+int rf_overlay_last_launch_ms(rf_handle h, float *ms);
+
+/* rf_detect_batch_device + the overlay of what it finds, in one call: detection runs exactly as there (out / counts /
+ * rf_last_anchor_indices are the same bytes); the two overlay launches follow each detection launch on its stream and read the faces
+ * from the device-visible result block -- no host synchronisation in between.  coord_scale is each frame's rf_frame_scale; faces have
+ * no ids.  n may exceed max_batch.  pixels: n * max_regions, may be NULL.  Refusals as above. */
+int rf_detect_overlay_batch_device(rf_handle h, void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                   float threshold, rf_face *out, int cap_per_image, int *counts, const rf_overlay_spec *spec,
+                                   int32_t *pixels);
+/* Frames in host memory: uploaded once, detected and drawn into on that copy; the annotated frames go to out_bgr[i] with rows of
+ * out_steps[i] bytes (NULL = cols * 3), which may be the input buffers. */
+int rf_detect_overlay_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                            float threshold, rf_face *out, int cap_per_image, int *counts, const rf_overlay_spec *spec,
+                            uint8_t *const *out_bgr, const int *out_steps, int32_t *pixels);
+/* rf_detect_track_batch_device + overlay: the overlay launches sit behind each track launch; the id of a face is the one in the tag the
+ * track launch wrote for it (an image of stream -1 has no ids), and the coasting tracks are those of the table AFTER this call's frame
+ * step.  Each stream may appear at most once per call (RF_ERR_INVALID_ARG otherwise).  Tags, ended lists and the tracker's state are
+ * the bytes of the tracked call without overlay. */
+int rf_detect_track_overlay_batch_device(rf_handle h, void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                         float threshold, rf_face *out, int cap_per_image, int *counts, rf_tracker tracker,
+                                         const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_counts,
+                                         const rf_overlay_spec *spec, int32_t *pixels, int *region_counts);
+
 /* ---- Motion-predicted face tracks: a tracker may keep a velocity per track slot and match and coast at the PREDICTED box, so a face
  * that moves while the detector drops it keeps its id and stays covered (DESIGN.md "Motion-predicted tracks" holds the definition;
  * tests/motion_ref.py restates it in numpy; every result is byte-exact against it).  All arithmetic is fp32 with one rounding per

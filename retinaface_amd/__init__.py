@@ -18,4 +18,6 @@ from .detector import MOTION_DTYPE, motion_spec, track_predict  # noqa: F401
 from .detector import tta_map_face, tta_merge_host, tta_spec  # noqa: F401
 from .detector import rot_map_face, rot_merge_host, rot_spec, rotate_host  # noqa: F401
 from .detector import pyramid_map_face, pyramid_merge_host, pyramid_plan, pyramid_spec, zoom_host  # noqa: F401
+from .detector import (OVERLAY_LABEL_ID, OVERLAY_LABEL_NONE, OVERLAY_LABEL_SCORE, overlay_host, overlay_region,  # noqa: F401
+                       overlay_spec)
 from .detector import REDACT_ELLIPSE, REDACT_FILL, REDACT_PIXELATE, REDACT_RECT, redact_host, redact_region, redact_spec  # noqa: F401

@@ -94,6 +94,14 @@ class rf_redact_spec(C.Structure):
                 ("fill", C.c_uint8 * 3), ("blur", C.c_uint8), ("max_regions", C.c_int32), ("coast", C.c_int32)]
 
 
+class rf_overlay_spec(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("thickness", C.c_int32), ("radius", C.c_int32), ("box", C.c_uint8 * 3),
+                ("colors_set", C.c_uint8), ("point", C.c_uint8 * 3), ("alpha", C.c_uint8), ("text", C.c_uint8 * 3),
+                ("color_by_id", C.c_uint8), ("label", C.c_int32), ("font_scale", C.c_int32), ("max_regions", C.c_int32),
+                ("coast", C.c_int32)]
+
+
+RF_OVERLAY_LABEL_NONE, RF_OVERLAY_LABEL_SCORE, RF_OVERLAY_LABEL_ID = 0, 1, 2
 RF_REDACT_PIXELATE, RF_REDACT_FILL = 0, 1
 RF_REDACT_RECT, RF_REDACT_ELLIPSE = 0, 1
 
@@ -243,6 +251,22 @@ SYMBOLS = {
                                                       C.c_float, _PP(rf_face), C.c_int, _PP(C.c_int), C.c_void_p, _PP(C.c_int),
                                                       _PP(rf_track_tag), _PP(rf_track), C.c_int, _PP(C.c_int), _PP(rf_redact_spec),
                                                       _PP(C.c_int32), _PP(C.c_int)]),
+    "rf_overlay_region": (C.c_int, [_PP(rf_overlay_spec), _PP(rf_face), C.c_int64, C.c_float, C.c_int, C.c_int, _PP(C.c_int32)]),
+    "rf_overlay_host": (C.c_int, [_PP(rf_overlay_spec), C.c_void_p, C.c_int, C.c_int, C.c_int, _PP(rf_face), _PP(C.c_int64), C.c_int,
+                                  C.c_float, _PP(C.c_int32)]),
+    "rf_overlay_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int, _PP(rf_face),
+                                    _PP(C.c_int64), C.c_int, _PP(C.c_int), _PP(C.c_float), _PP(rf_overlay_spec), C.c_void_p, _PP(C.c_int),
+                                    _PP(C.c_int32), _PP(C.c_int)]),
+    "rf_overlay_last_launch_ms": (C.c_int, [C.c_void_p, _PP(C.c_float)]),
+    "rf_detect_overlay_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int, C.c_float,
+                                                 _PP(rf_face), C.c_int, _PP(C.c_int), _PP(rf_overlay_spec), _PP(C.c_int32)]),
+    "rf_detect_overlay_batch": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int, C.c_float,
+                                          _PP(rf_face), C.c_int, _PP(C.c_int), _PP(rf_overlay_spec), _PP(C.c_void_p), _PP(C.c_int),
+                                          _PP(C.c_int32)]),
+    "rf_detect_track_overlay_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                                       C.c_float, _PP(rf_face), C.c_int, _PP(C.c_int), C.c_void_p, _PP(C.c_int),
+                                                       _PP(rf_track_tag), _PP(rf_track), C.c_int, _PP(C.c_int), _PP(rf_overlay_spec),
+                                                       _PP(C.c_int32), _PP(C.c_int)]),
     "rf_tta_map_face": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _PP(rf_face), _PP(rf_face)]),
     "rf_tta_merge_host": (C.c_int, [_PP(rf_tta_spec), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _PP(rf_face), _PP(C.c_int),
                                     _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int)]),

@@ -73,6 +73,66 @@ void RetinaFace::detectRedacted(vector<cv::Mat> &imgs, float threshold, const rf
     }
 }
 
+void RetinaFace::detectOverlay(vector<cv::Mat> &imgs, float threshold, const rf_overlay_spec *spec) {
+    const int n = (int)imgs.size();
+    lastBatch_.assign(n, vector<FaceDetectInfo>());
+    overlayPixels_.assign(n, vector<int32_t>());
+    if (n == 0) return;
+    const int regions = spec && spec->max_regions > 0 ? spec->max_regions : (maxDet_ < 1024 ? maxDet_ : 1024);
+    vector<const uint8_t *> ptrs(n);
+    vector<uint8_t *> outs(n);
+    vector<int> rows(n), cols(n), steps(n), counts(n, 0);
+    for (int i = 0; i < n; i++) {
+        ptrs[i] = outs[i] = imgs[i].empty() ? nullptr : imgs[i].data;
+        rows[i] = imgs[i].rows; cols[i] = imgs[i].cols; steps[i] = (int)(size_t)imgs[i].step;
+    }
+    vector<rf_face> faces((size_t)n * maxDet_);
+    vector<int32_t> pixels((size_t)n * regions);
+    check(rf_detect_overlay_batch(h_, ptrs.data(), rows.data(), cols.data(), steps.data(), n, threshold, faces.data(), maxDet_, counts.data(),
+                                  spec, outs.data(), steps.data(), pixels.data()), h_, "RetinaFace::detectOverlay");
+    for (int i = 0; i < n; i++) {
+        int k = counts[i] < maxDet_ ? counts[i] : maxDet_;
+        lastBatch_[i].resize(k);
+        if (k) memcpy(lastBatch_[i].data(), &faces[(size_t)i * maxDet_], (size_t)k * sizeof(rf_face));
+        const int r = k < regions ? k : regions;
+        overlayPixels_[i].assign(pixels.begin() + (size_t)i * regions, pixels.begin() + (size_t)i * regions + r);
+    }
+}
+
+void RetinaFace::detectTrackedOverlay(const vector<void *> &deviceFrames, const vector<int> &rows, const vector<int> &cols,
+                                      const vector<int> &steps, rf_tracker tracker, const vector<int> &streams, float threshold,
+                                      const rf_overlay_spec *spec) {
+    const int n = (int)deviceFrames.size();
+    if ((int)rows.size() != n || (int)cols.size() != n || (int)steps.size() != n || (int)streams.size() != n)
+        throw std::runtime_error("RetinaFace::detectTrackedOverlay: rows, cols, steps and one stream per frame");
+    lastBatch_.assign(n, vector<FaceDetectInfo>());
+    trackTags_.assign(n, vector<rf_track_tag>());
+    trackEnded_.assign(n, vector<rf_track>());
+    overlayPixels_.assign(n, vector<int32_t>());
+    if (n == 0) return;
+    const int capEnded = 256;                          // a table holds at most 256 tracks: no list is ever cut
+    const int regions = spec && spec->max_regions > 0 ? spec->max_regions : (maxDet_ < 1024 ? maxDet_ : 1024);
+    vector<int> counts(n, 0), endedCounts(n, 0), regionCounts(n, 0);
+    vector<rf_face> faces((size_t)n * maxDet_);
+    vector<rf_track_tag> tags((size_t)n * maxDet_);
+    vector<rf_track> ended((size_t)n * capEnded);
+    vector<int32_t> pixels((size_t)n * regions);
+    check(rf_detect_track_overlay_batch_device(h_, deviceFrames.data(), rows.data(), cols.data(), steps.data(), n, threshold, faces.data(),
+                                               maxDet_, counts.data(), tracker, streams.data(), tags.data(), ended.data(), capEnded,
+                                               endedCounts.data(), spec, pixels.data(), regionCounts.data()), h_,
+          "RetinaFace::detectTrackedOverlay");
+    for (int i = 0; i < n; i++) {
+        const int k = counts[i] < maxDet_ ? counts[i] : maxDet_;
+        lastBatch_[i].resize(k);
+        if (k) memcpy(lastBatch_[i].data(), &faces[(size_t)i * maxDet_], (size_t)k * sizeof(rf_face));
+        trackTags_[i].assign(tags.begin() + (size_t)i * maxDet_, tags.begin() + (size_t)i * maxDet_ + k);
+        const int e = endedCounts[i] < capEnded ? endedCounts[i] : capEnded;
+        trackEnded_[i].assign(ended.begin() + (size_t)i * capEnded, ended.begin() + (size_t)i * capEnded + e);
+        const int r = regionCounts[i] < regions ? regionCounts[i] : regions;
+        overlayPixels_[i].assign(pixels.begin() + (size_t)i * regions, pixels.begin() + (size_t)i * regions + r);
+    }
+}
+
 void RetinaFace::detectTiled(const vector<cv::Mat> &imgs, float threshold, const rf_tile_spec *spec) {
     const int n = (int)imgs.size();
     lastBatch_.assign(n, vector<FaceDetectInfo>());

@@ -994,6 +994,121 @@ int rf_detect_track_redact_batch_device(rf_handle h, void *const *d_bgr, const i
     });
 }
 
+// ---- overlays (overlay.h)
+int rf_overlay_region(const rf_overlay_spec *spec, const rf_face *face, int64_t id, float coord_scale, int rows, int cols, int32_t out[24]) {
+    rf::OverlaySpec sp;
+    if (rf::overlay_spec_resolve(spec, 256, &sp) || !face || !out || rows < 0 || cols < 0) return RF_ERR_INVALID_ARG;
+    const rf::OverlayRegion r = rf::overlay_region_make(sp, &face->score, id, coord_scale, false);
+    const int32_t v[24] = {r.x0, r.y0, r.x1, r.y1, r.bx0, r.by0, r.bx1, r.by1, r.ndig, (int32_t)r.digits, r.plx, r.ply, (int32_t)r.colour,
+                           (r.flags >> 8) & 31, r.cx[0], r.cx[1], r.cx[2], r.cx[3], r.cx[4], r.cy[0], r.cy[1], r.cy[2], r.cy[3], r.cy[4]};
+    memcpy(out, v, sizeof(v));
+    return r.flags & rf::kOverlayValid;
+}
+
+int rf_overlay_host(const rf_overlay_spec *spec, uint8_t *bgr, int rows, int cols, int step, const rf_face *faces, const int64_t *ids,
+                    int count, float coord_scale, int32_t *pixels) {
+    rf::OverlaySpec sp;
+    if (rf::overlay_spec_resolve(spec, 256, &sp) || count < 0 || (count > 0 && !faces) || rows < 0 || cols < 0) return RF_ERR_INVALID_ARG;
+    const bool empty = !bgr || rows == 0 || cols == 0;
+    if (!empty && (step < cols * 3 || rows > 4096 * 3072 / cols)) return RF_ERR_INVALID_ARG;
+    const int m = std::min(count, sp.max_regions);
+    if (empty) { if (pixels) for (int k = 0; k < m; k++) pixels[k] = 0; }
+    else {
+        std::vector<rf::OverlayRegion> regions((size_t)m);
+        for (int k = 0; k < m; k++) regions[k] = rf::overlay_region_make(sp, &faces[k].score, ids ? ids[k] : 0, coord_scale, false);
+        rf::overlay_host_frame(sp, bgr, rows, cols, (size_t)step, regions.data(), m, pixels);
+    }
+    return count > sp.max_regions ? RF_ERR_TRUNCATED : RF_OK;
+}
+
+namespace {
+// the spec, refused before any state changes; an overlay call travels as a redaction request with `overlay` set (engine.h)
+void overlay_request(rf_handle h, const rf_overlay_spec *spec, rf_tracker tracker, const int *stream_of_image, int32_t *pixels, int *region_counts,
+                     rf::RedactRequest *rq) {
+    if (h->eng->num_devices() > 1) throw rf::Unsupported("overlays are not available on a multi-device handle");
+    const char *bad = rf::overlay_spec_resolve(spec, h->eng->default_max_faces(), &rq->ospec);
+    if (bad) throw rf::ArgError(bad);
+    if (tracker && tracker->h != h) throw rf::ArgError("not a tracker of this handle");
+    rq->overlay = true;
+    rq->spec.max_regions = rq->ospec.max_regions; rq->spec.coast = rq->ospec.coast;
+    rq->tracker = tracker ? tracker->impl : nullptr;
+    rq->stream_of_image = tracker ? stream_of_image : nullptr;
+    rq->pixels = pixels; rq->region_counts = region_counts;
+}
+
+int detect_overlay_common(rf_handle h, const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,
+                          float thr, rf_face *out, int cap, int *counts, const rf_overlay_spec *spec, uint8_t *const *out_bgr, const int *out_steps,
+                          int32_t *pixels) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        rf::RedactRequest rq;
+        overlay_request(h, spec, nullptr, nullptr, pixels, nullptr, &rq);
+        bool tr = false, cut = false;
+        h->eng->detect_redact(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, rq, &cut, out_bgr, out_steps);
+        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        if (cut) { h->error = kRedactCut; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+}  // namespace
+
+int rf_overlay_device(rf_handle h, void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n, const rf_face *faces,
+                      const int64_t *ids, int cap_per_image, const int *counts, const float *coord_scale, const rf_overlay_spec *spec,
+                      rf_tracker tracker, const int *stream_of_image, int32_t *pixels, int *region_counts) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        rf::RedactRequest rq;
+        overlay_request(h, spec, tracker, stream_of_image, pixels, region_counts, &rq);
+        rq.ids = ids;
+        bool cut = false;
+        h->eng->redact((const void *const *)d_bgr, rows, cols, steps, n, faces, cap_per_image, counts, coord_scale, rq, &cut);
+        if (cut) { h->error = kRedactCut; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+
+int rf_overlay_last_launch_ms(rf_handle h, float *ms) {
+    if (!h || !ms) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        const float v = h->eng->overlay_last_launch_ms();
+        if (v < 0.f) throw rf::ArgError("no rf_overlay_device call has been timed on this handle");
+        *ms = v;
+        return RF_OK;
+    });
+}
+
+int rf_detect_overlay_batch_device(rf_handle h, void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n, float threshold,
+                                   rf_face *out, int cap_per_image, int *counts, const rf_overlay_spec *spec, int32_t *pixels) {
+    return detect_overlay_common(h, (const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, out, cap_per_image, counts, spec,
+                                 nullptr, nullptr, pixels);
+}
+
+int rf_detect_overlay_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n, float threshold,
+                            rf_face *out, int cap_per_image, int *counts, const rf_overlay_spec *spec, uint8_t *const *out_bgr,
+                            const int *out_steps, int32_t *pixels) {
+    return detect_overlay_common(h, bgr, rows, cols, steps, n, false, threshold, out, cap_per_image, counts, spec, out_bgr, out_steps, pixels);
+}
+
+int rf_detect_track_overlay_batch_device(rf_handle h, void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                         float threshold, rf_face *out, int cap_per_image, int *counts, rf_tracker tracker,
+                                         const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_counts,
+                                         const rf_overlay_spec *spec, int32_t *pixels, int *region_counts) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        rf::RedactRequest rq;
+        overlay_request(h, spec, tracker, stream_of_image, pixels, region_counts, &rq);
+        rf::TrackRequest trq;
+        track_request(h, tracker, stream_of_image, tags, ended, cap_ended, ended_counts, &trq);
+        bool tr = false, tcut = false, cut = false;
+        h->eng->detect_track_redact((const uint8_t *const *)d_bgr, rows, cols, steps, n, threshold, out, cap_per_image, counts, &tr, trq, &tcut,
+                                    rq, &cut);
+        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        if (tcut) { h->error = kTrackCut; return RF_ERR_TRUNCATED; }
+        if (cut) { h->error = kRedactCut; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+
 // ---- flip test-time augmentation (tta.h)
 int rf_tta_map_face(int rows, int cols, int net_h, int net_w, int pass, const rf_face *in, rf_face *out) {
     if (!in || !out || rows <= 0 || cols <= 0 || net_h <= 0 || net_w <= 0 || pass < 0 || pass > 1) return RF_ERR_INVALID_ARG;

@@ -1869,6 +1869,7 @@ public:
         if (rq.spec.max_regions < 1 || rq.spec.max_regions > kRedactMaxRegions) throw ArgError("max_regions must be in [1, 1024]");
         if ((size_t)std::max(n, 1) * rq.spec.max_regions * rq.spec.cells * rq.spec.cells > ((size_t)1 << 28))
             throw ArgError("n x max_regions x cells^2: more than 2^28 cells in one call");
+        const std::string who = rq.overlay ? "overlay" : "redaction", verb = rq.overlay ? "drawn into" : "redacted";
         auto *t = rq.tracker ? &tracker_of(rq.tracker) : nullptr;
         if (t) {
             if (t->dirty) throw ArgError("the tracker's last call failed: reset it first");            if (n > 0 && !rq.stream_of_image) throw ArgError("stream_of_image is null");
@@ -1879,7 +1880,7 @@ public:
                 if (st >= 0) seen.push_back(st);
             }
             std::sort(seen.begin(), seen.end());
-            if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) throw ArgError("redaction: a stream appears more than once in the call");
+            if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) throw ArgError(who + ": a stream appears more than once in the call");
         }
         std::vector<std::pair<uintptr_t, uintptr_t>> span;
         for (int i = 0; i < n; i++) {
@@ -1888,13 +1889,13 @@ public:
             if (!frames[i] || rows[i] <= 0 || cols[i] <= 0) continue;
             if (on_device && check_residency_) {
                 const int where = foreign_device_of(frames[i]);
-                if (where >= 0 && where != device_) throw Unsupported("redaction: a frame is resident on another device (its staged copy would be redacted, not the frame)");
+                if (where >= 0 && where != device_) throw Unsupported(who + ": a frame is resident on another device (its staged copy would be " + verb + ", not the frame)");
             }
             span.emplace_back((uintptr_t)frames[i], (uintptr_t)frames[i] + (size_t)(rows[i] - 1) * st + (size_t)cols[i] * 3);
         }
         std::sort(span.begin(), span.end());
         for (size_t j = 1; j < span.size(); j++)
-            if (span[j].first < span[j - 1].second) throw ArgError("redaction: two frames of the call overlap in memory");
+            if (span[j].first < span[j - 1].second) throw ArgError(who + ": two frames of the call overlap in memory");
         return t;
     }
 
@@ -1905,9 +1906,10 @@ public:
     // waits for its last launch before it returns.)
     void redact_open(const RedactRequest &rq, void *tracker, int n, const uint8_t *const *frames, const int *rows, const int *cols) {
         const size_t slots = (size_t)std::max(n, 1) * rq.spec.max_regions;
-        red_regions_.reserve(slots * sizeof(RedactRegion));
+        if (rq.overlay) ov_regions_.reserve(slots * sizeof(OverlayRegion));
+        else red_regions_.reserve(slots * sizeof(RedactRegion));
         red_counts_.reserve(((size_t)std::max(n, 1) * 2 + slots) * sizeof(int));
-        if (rq.spec.mode == RF_REDACT_PIXELATE && !rq.spec.blur) red_cells_.reserve(slots * rq.spec.cells * rq.spec.cells * sizeof(uint32_t));
+        if (!rq.overlay && rq.spec.mode == RF_REDACT_PIXELATE && !rq.spec.blur) red_cells_.reserve(slots * rq.spec.cells * rq.spec.cells * sizeof(uint32_t));
         if (rq.spec.blur && n > 0) {
             red_shadow_off_.assign((size_t)n, 0);
             size_t bytes = align256((size_t)n * sizeof(unsigned long long));
@@ -1920,11 +1922,14 @@ public:
         }
         red_.spec = rq.spec; red_.tr = tracker ? &tracker_of(tracker) : nullptr; red_.stream_of_image = rq.stream_of_image;
         red_.n = n; red_.next_image = 0;
+        red_.overlay = rq.overlay; red_.ospec = rq.ospec;
     }
-    RedactParams redact_params() const {
-        RedactParams rp;
+    // (the overlay part stays zero in a redacting call, whose launches take the RedactParams part alone)
+    OverlayParams redact_params() const {
+        OverlayParams rp;
         memset((void *)&rp, 0, sizeof(rp));
         rp.spec = red_.spec;
+        if (red_.overlay) { rp.ospec = red_.ospec; rp.oregions = (OverlayRegion *)ov_regions_.ptr; }
         if (red_.tr) {
             rp.track_state = red_.tr->state.ptr;
             rp.max_tracks = red_.tr->spec.max_tracks;
@@ -1938,7 +1943,12 @@ public:
         if (red_.spec.blur) { rp.shadow = red_shadow_.ptr; rp.shadow_off = (const unsigned long long *)red_shadow_.ptr; }
         return rp;
     }
-    static void redact_launch(hipStream_t st, const RedactParams &rp) {
+    void redact_launch(hipStream_t st, const OverlayParams &rp) const {
+        if (red_.overlay) {
+            launch_overlay_regions(st, rp);
+            launch_overlay_draw(st, rp);
+            return;
+        }
         launch_redact_regions(st, rp);
         if (rp.spec.blur) launch_redact_blur(st, rp);
         else launch_redact_mean(st, rp);
@@ -1968,10 +1978,12 @@ public:
         if (n == 0) return;
         DeviceGuard guard(device_);
         const int fpi = std::max(1, std::min(cap_per_image, rq.spec.max_regions));      // records per image that travel to the device
-        // one table: frames | counts | scales | streams | faces (60-byte records)
+        // one table: frames | counts | scales | streams | faces (60-byte records) | with ids, one int64 per face
+        const bool with_ids = rq.overlay && rq.ids;
         const size_t o_cnt = align256((size_t)n * sizeof(FrameDesc)), o_sc = o_cnt + align256((size_t)n * sizeof(int)),
                      o_st = o_sc + align256((size_t)n * sizeof(float)), o_face = o_st + align256((size_t)n * sizeof(int)),
-                     total = o_face + (size_t)n * fpi * sizeof(rf_face);
+                     o_id = o_face + align256((size_t)n * fpi * sizeof(rf_face)),
+                     total = with_ids ? o_id + (size_t)n * fpi * sizeof(int64_t) : o_face + (size_t)n * fpi * sizeof(rf_face);
         align_host_.assign(total, 0);
         FrameDesc *fd = (FrameDesc *)align_host_.data();
         int *cnt = (int *)(align_host_.data() + o_cnt);
@@ -1986,14 +1998,16 @@ public:
             strm[i] = t ? rq.stream_of_image[i] : -1;
             const int c = std::min(counts[i], fpi);
             if (c) memcpy(align_host_.data() + o_face + (size_t)i * fpi * sizeof(rf_face), faces + (size_t)i * cap_per_image, (size_t)c * sizeof(rf_face));
+            if (c && with_ids) memcpy(align_host_.data() + o_id + (size_t)i * fpi * sizeof(int64_t), rq.ids + (size_t)i * cap_per_image, (size_t)c * sizeof(int64_t));
         }
         uint8_t *d_tab = align_tab_.reserve(total);
         redact_open(rq, t, n, (const uint8_t *const *)frames, rows, cols);
         if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
         RF_HIP(hipMemcpyAsync(d_tab, align_host_.data(), total, hipMemcpyHostToDevice, align_stream_));
-        RedactParams rp = redact_params();
+        OverlayParams rp = redact_params();
         rp.frames = (const FrameDesc *)d_tab;
         rp.faces = d_tab + o_face; rp.face_stride = (int)sizeof(rf_face); rp.faces_per_image = fpi;
+        if (with_ids) { rp.ids = d_tab + o_id; rp.id_stride = (int)sizeof(int64_t); rp.ids_per_image = fpi; }
         rp.counts = (const int *)(d_tab + o_cnt); rp.count_cap = 0x7fffffff;
         rp.scale = (const float *)(d_tab + o_sc);
         rp.streams = t ? (const int *)(d_tab + o_st) : nullptr;
@@ -2004,10 +2018,12 @@ public:
         RF_HIP(hipGetLastError());
         RF_HIP(hipEventRecord(red_ev_[1], align_stream_));
         RF_HIP(hipStreamSynchronize(align_stream_));
-        if (hipEventElapsedTime(&red_launch_ms_, red_ev_[0], red_ev_[1]) != hipSuccess) red_launch_ms_ = -1.f;
+        float &ms = rq.overlay ? ov_launch_ms_ : red_launch_ms_;
+        if (hipEventElapsedTime(&ms, red_ev_[0], red_ev_[1]) != hipSuccess) ms = -1.f;
         redact_copy_out(rq, n, cut);
     }
     float redact_last_launch_ms() const override { return red_launch_ms_; }
+    float overlay_last_launch_ms() const override { return ov_launch_ms_; }
 
     void detect_redact(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device, float threshold,
                        rf_face *out, int cap_per_image, int *counts, bool *truncated, const RedactRequest &rq, bool *cut, uint8_t *const *out_bgr,
@@ -2069,7 +2085,7 @@ public:
         redact_check(rq, frames, rows, cols, steps, n, true);
         DeviceGuard guard(device_);
         launch_pending();
-        track_open_call(t, trq, n, cap_per_image);
+        track_open_call(t, trq, n, cap_per_image, rq.overlay);       // an overlay reads every face's id from its tag, whatever the caller's cap is
         trk_.records = nullptr; trk_.max_faces = kTrackMaxFaces;
         redact_open(rq, rq.tracker, n, frames, rows, cols);
         t.dirty = true;
@@ -2939,8 +2955,12 @@ private:
     void launch_lane_redact(Lane &s, int n) {
         if (n > cap_images_ || red_.next_image + n > red_.n) throw HipError("redaction: a launch carries images of another call");
         fill_lane_align_scale(s, n);
-        RedactParams rp = redact_params();
+        OverlayParams rp = redact_params();
         if (red_.tr) {
+            if (red_.overlay && trk_.on) {         // the tags the lane's track launch has just written, pinned like the result block
+                rp.ids = (const uint8_t *)trk_tags_.ptr + (size_t)red_.next_image * trk_.tag_stride * sizeof(rf_track_tag);
+                rp.id_stride = (int)sizeof(rf_track_tag); rp.ids_per_image = trk_.tag_stride; rp.ids_of_streams = 1;
+            }
             if (!s.h_red_streams) {
                 void *p = nullptr;
                 RF_HIP(hipHostMalloc(&p, std::max<size_t>((size_t)cap_images_ * sizeof(int), 256), hipHostMallocDefault));
@@ -3393,7 +3413,7 @@ private:
     hipEvent_t trk_ev_[2] = {nullptr, nullptr};   // around the track launch of track_update() (tools/track_bench.py reads the time)
     float trk_launch_ms_ = -1.f;
     hipEvent_t red_ev_[2] = {nullptr, nullptr};   // around the redaction launches of redact() (tools/redact_bench.py reads the time)
-    float red_launch_ms_ = -1.f;
+    float red_launch_ms_ = -1.f, ov_launch_ms_ = -1.f;
     struct { bool on = false; Tracker *tr = nullptr; const int *stream_of_image = nullptr; int n = 0, next_image = 0, tag_stride = 0, cap_ended = 0,
              max_faces = 0; const rf_face_quality *records = nullptr; hipEvent_t prev = nullptr; } trk_;
 
@@ -3403,7 +3423,9 @@ private:
     DeviceScratch red_shadow_;                    // a blurring call: offset table | the blurred owned pixels of every frame of the call
     std::vector<unsigned long long> red_shadow_off_;
     std::vector<int> red_host_;
-    struct { bool on = false; RedactSpec spec; Tracker *tr = nullptr; const int *stream_of_image = nullptr; int n = 0, next_image = 0; } red_;
+    struct { bool on = false; RedactSpec spec; Tracker *tr = nullptr; const int *stream_of_image = nullptr; int n = 0, next_image = 0;
+             bool overlay = false; OverlaySpec ospec; } red_;
+    DeviceScratch ov_regions_;                    // an overlay call's region records (overlay.h), in the place of red_regions_
 
     int last_n_ = 0;
     std::vector<int> last_cand_counts_;

@@ -156,6 +156,12 @@ struct RedactRequest {
     const int *stream_of_image = nullptr;
     int32_t *pixels = nullptr;
     int *region_counts = nullptr;
+    // An overlay call (overlay.h; rf_overlay_device / rf_detect_overlay_batch* / rf_detect_track_overlay_batch_device) is the same request
+    // with `overlay` set: the same list of regions is drawn instead of redacted.  spec then carries the overlay's max_regions and coast
+    // and is otherwise all defaults; ids (redact() only; host, as the faces; may be nullptr) are the faces' track ids.
+    bool overlay = false;
+    OverlaySpec ospec;
+    const int64_t *ids = nullptr;
 };
 
 class Engine {
@@ -339,6 +345,8 @@ public:
     }
     // hipEvent time of the redaction launches of the most recent redact() (negative: none yet)
     virtual float redact_last_launch_ms() const { return -1.f; }
+    // ... of the overlay launches of the most recent redact() with an overlay request
+    virtual float overlay_last_launch_ms() const { return -1.f; }
     int default_max_faces() const { return opt_.max_detections; }
     // asynchronous: frames on host (staged through pinned memory before the call returns, unless the caller registered
     // them with host_register) or on the device

@@ -10,6 +10,7 @@
 #include "align.h"
 #include "face_batch.h"
 #include "face_quality.h"
+#include "overlay.h"
 #include "redact.h"
 #include "pyramid.h"
 #include "rot.h"
@@ -374,6 +375,20 @@ void launch_redact_mean(hipStream_t s, const RedactParams &p);
 // shadow; launch_redact_write then copies owned pixels from the shadow into the frame
 void launch_redact_blur(hipStream_t s, const RedactParams &p);
 void launch_redact_write(hipStream_t s, const RedactParams &p);
+
+// ---- K_l: overlays (overlay.h) -- boxes, landmark discs and labels drawn in place into the frames of a launch, in two launches ordered
+//      on the stream.  launch_overlay_regions: redaction's list (the same code: faces, then the stream's coasting tracks) as overlay
+//      records; launch_overlay_draw paints them.  The RedactParams part means what it means there (spec.max_regions and coast are the
+//      overlay's; regions, cell_values and shadow are unused).
+struct OverlayParams : RedactParams {
+    OverlaySpec ospec;
+    OverlayRegion *oregions;              // call image c: oregions[c * max_regions + r]
+    const uint8_t *ids;                   // launch image i, face k: an int64 at ids + (i * ids_per_image + k) * id_stride; nullptr = no ids
+    int id_stride, ids_per_image;         // faces k >= ids_per_image have no id
+    int ids_of_streams;                   // 1: the ids are the tags of a track launch, which an image of stream -1 does not have
+};
+void launch_overlay_regions(hipStream_t s, const OverlayParams &p);
+void launch_overlay_draw(hipStream_t s, const OverlayParams &p);
 
 // ---- K_j: flip test-time augmentation (tta.h).
 //      mirror_rows: a dense left-right mirrored copy of a BGR frame (any source pitch and alignment), in front of a TTA call's launches.

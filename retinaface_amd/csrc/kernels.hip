@@ -5109,11 +5109,14 @@ void launch_shot_keep(hipStream_t s, const ShotParams &p) {
 constexpr int kRedactItemsPerImage = 256;      // workgroup slots per image the item list is dealt over
 constexpr int kRedactMaxGrid = 2048;
 
-// kMotion: the coasting-box variant -- a coasting track is redacted at its predicted box (motion.h) instead of where it was last seen.
+// The region list of image blockIdx.x, one workgroup per image (redact.h "list"; the overlay kernels draw the same list): its faces in
+// score order, then the stream's coasting tracks in slot order (prefix count by ballot + popcount) where each was last seen, cut at
+// max_regions; the owned-pixel counters are zeroed and the list's lengths written.  emit(slot, fd, face, scale, k, id) writes the
+// record of one entry: face = 15 floats (score, box, points), k = the face's index or -1 for a track, id = the track's id.
+// kMotion: the coasting-box variant -- a coasting track is listed at its predicted box (motion.h) instead of where it was last seen.
 // The plain instantiation takes the RedactArgs part alone and reads what it always read.
-template <bool kMotion>
-__global__ __launch_bounds__(kThreads) void redact_regions_kernel(typename std::conditional<kMotion, RedactParams, RedactArgs>::type a) {
-    __shared__ int s_cnt[kThreads / 64];
+template <bool kMotion, class A, class Emit>
+__device__ inline void region_list_build(const A &a, int *s_cnt, Emit emit) {
     const int i = blockIdx.x, tid = (int)threadIdx.x;
     const int M = a.spec.max_regions;
     const size_t slot0 = (size_t)(a.image0 + i) * M;
@@ -5125,11 +5128,8 @@ __global__ __launch_bounds__(kThreads) void redact_regions_kernel(typename std::
     int nf = cnt < a.faces_per_image ? cnt : a.faces_per_image;      // cnt stays the true count: the list's length before the cut
     nf = nf < M ? nf : M;
     const float scale = a.scale ? a.scale[i] : 1.f;
-    for (int k = tid; k < nf; k += kThreads) {
-        const float *src = (const float *)(a.faces + ((size_t)i * a.faces_per_image + k) * a.face_stride);
-        const float box[4] = {src[1], src[2], src[3], src[4]};
-        a.regions[slot0 + k] = redact_region_make(box, scale, a.spec.margin, a.spec.cells, fd.rows, fd.cols);
-    }
+    for (int k = tid; k < nf; k += kThreads)
+        emit(slot0 + k, fd, (const float *)(a.faces + ((size_t)i * a.faces_per_image + k) * a.face_stride), scale, k, 0ll);
     // the stream's coasting tracks, in slot order (prefix count by ballot + popcount), behind the faces: where each was last seen
     int coasting = 0;
     const int stream = (a.streams && a.track_state && !empty) ? a.streams[i] : -1;
@@ -5137,27 +5137,42 @@ __global__ __launch_bounds__(kThreads) void redact_regions_kernel(typename std::
         const rf_track *tab = (const rf_track *)(a.track_state + (size_t)stream * (sizeof(TrackHeader) + (size_t)a.max_tracks * sizeof(rf_track)) +
                                                  sizeof(TrackHeader));
         bool live = false;
-        float box[4] = {0.f, 0.f, 0.f, 0.f};
+        long long id = 0;
+        float face[15];
+        for (int j = 0; j < 15; j++) face[j] = 0.f;
         if (tid < a.max_tracks) {
             const rf_track *t = tab + tid;
             live = t->id != 0 && t->missed >= 1 && t->missed <= a.coast;
-            if (live) { box[0] = t->last.x1; box[1] = t->last.y1; box[2] = t->last.x2; box[3] = t->last.y2; }
+            if (live) {
+                id = t->id;
+                const float *lf = (const float *)&t->last;
+                for (int j = 0; j < 15; j++) face[j] = lf[j];
+            }
             if constexpr (kMotion) {
                 if (live) {
                     const int4 r = ((const int4 *)(a.motion + (size_t)stream * a.max_tracks))[tid];
-                    const float last[4] = {box[0], box[1], box[2], box[3]};
-                    motion_predict_box(last, __int_as_float(r.x), __int_as_float(r.y), r.z, motion_frames_ahead(t->missed, 0, a.horizon), box);
+                    const float last[4] = {face[1], face[2], face[3], face[4]};
+                    motion_predict_box(last, __int_as_float(r.x), __int_as_float(r.y), r.z, motion_frames_ahead(t->missed, 0, a.horizon), face + 1);
                 }
             }
         }
         const int pos = track_prefix_count(live, kThreads / 64, s_cnt, &coasting);
-        if (live && nf + pos < M) a.regions[slot0 + nf + pos] = redact_region_make(box, 1.f, a.spec.margin, a.spec.cells, fd.rows, fd.cols);
+        if (live && nf + pos < M) emit(slot0 + nf + pos, fd, face, 1.f, -1, id);
     }
     if (tid == 0) {
         const int total = cnt + coasting;
         a.true_counts[a.image0 + i] = total;
         a.nreg[a.image0 + i] = total < M ? total : M;
     }
+}
+
+template <bool kMotion>
+__global__ __launch_bounds__(kThreads) void redact_regions_kernel(typename std::conditional<kMotion, RedactParams, RedactArgs>::type a) {
+    __shared__ int s_cnt[kThreads / 64];
+    region_list_build<kMotion>(a, s_cnt, [&](size_t slot, const FrameDesc &fd, const float *face, float scale, int, long long) {
+        const float box[4] = {face[1], face[2], face[3], face[4]};
+        a.regions[slot] = redact_region_make(box, scale, a.spec.margin, a.spec.cells, fd.rows, fd.cols);
+    });
 }
 
 // the three channel sums of the workgroup's threads; the result is valid in thread 0
@@ -5558,6 +5573,119 @@ void launch_redact_write(hipStream_t s, const RedactParams &p) {
     redact_check(p);
     if (p.spec.blur) hipLaunchKernelGGL(redact_write_kernel<true>, dim3(redact_grid(p)), dim3(kThreads), 0, s, (const RedactArgs &)p, redact_per_image(p));
     else hipLaunchKernelGGL(redact_write_kernel<false>, dim3(redact_grid(p)), dim3(kThreads), 0, s, (const RedactArgs &)p, redact_per_image(p));
+}
+
+// =============================================================================================
+// K_l: overlays (overlay.h), drawn in place into the frames of a launch.  Two launches ordered on the stream.
+//      overlay_regions_kernel writes one record per entry of redaction's list (region_list_build: the same code).
+//      overlay_draw_kernel is primitive-centric: its work is the list of (image, region, piece) items -- the four strips of the outline,
+//      the five discs, the plate (overlay_piece_rect) -- dealt over a bounded grid as K_k deals its cells, so only the pixels of
+//      primitives are visited, never the frame.  Race-free by construction, in place, without a shadow copy and without atomics on
+//      pixels: a pixel's OWNER is the lowest-indexed region that covers it, overlay_paint names the one primitive of that region that
+//      wins there, and that primitive lies in exactly one piece (the strips are disjoint, a disc pixel belongs to the lowest k, the
+//      plate is one piece).  So at most one thread of the launch writes a pixel -- the thread of the owner's piece that visits it --
+//      and that thread reads nothing of the frame but that pixel's own three bytes, which no other thread writes: whichever order the
+//      workgroups run in, every blend sees the original.  Records and spec are read-only here.  The only atomic is the integer add of
+//      a piece's painted count to its region's counter.  Everything is bounded: 1024 regions, 10 pieces, the frame's pixels.
+// =============================================================================================
+template <bool kMotion>
+__global__ __launch_bounds__(kThreads) void overlay_regions_kernel(OverlayParams a) {
+    __shared__ int s_cnt[kThreads / 64];
+    region_list_build<kMotion>(a, s_cnt, [&](size_t slot, const FrameDesc &, const float *face, float scale, int k, long long id) {
+        if (k >= 0 && a.ids && k < a.ids_per_image && (!a.ids_of_streams || (a.streams && a.streams[blockIdx.x] >= 0)))
+            id = *(const long long *)(a.ids + ((size_t)blockIdx.x * a.ids_per_image + k) * a.id_stride);
+        a.oregions[slot] = overlay_region_make(a.ospec, face, id, scale, k < 0);
+    });
+}
+
+// One workgroup per item = one piece of one region, cut by the frame.  The lower-indexed regions whose bounding rectangles meet the
+// piece are gathered into LDS as indices in index order (256 candidates at a time: ballot + popcount prefix, as redact_write_kernel
+// does; 2 KB, so LDS never limits the waves per CU), then every pixel of the piece is tested: the region's winning primitive there
+// belongs to this piece, and no gathered region paints the pixel = this thread blends it.  A candidate's record is read at a
+// wave-uniform address (every lane tests the same candidate), so it is one cached broadcast per test.  Pixels are dealt row-major over
+// the piece: the lanes of a wave hold consecutive pixels of a row of a horizontal strip or a plate and store consecutive bytes.  Stores
+// are three byte stores per pixel: a frame may start at any address with any step, and the neighbouring bytes belong to other threads.
+__global__ __launch_bounds__(kThreads) void overlay_draw_kernel(OverlayParams a, int per_image) {
+    __shared__ uint16_t s_low[kRedactMaxRegions];
+    __shared__ int s_cnt[kThreads / 64];
+    const int tid = (int)threadIdx.x;
+    const int M = a.spec.max_regions;
+    const OverlaySpec sp = a.ospec;
+    for (int w = blockIdx.x; w < a.n * per_image; w += gridDim.x) {
+        const int i = w / per_image;
+        const int image = a.image0 + i;
+        const int items = a.nreg[image] * kOverlayPieces;
+        const FrameDesc fd = a.frames[i];
+        const OverlayRegion *regs = a.oregions + (size_t)image * M;
+        for (int item = w - i * per_image; item < items; item += per_image) {
+            const int r = item / kOverlayPieces, piece = item - r * kOverlayPieces;
+            const OverlayRegion reg = regs[r];
+            int bx0, by0, bx1, by1;
+            overlay_piece_rect(sp, reg, piece, &bx0, &by0, &bx1, &by1);
+            bx0 = bx0 > 0 ? bx0 : 0; by0 = by0 > 0 ? by0 : 0;
+            bx1 = bx1 < fd.cols - 1 ? bx1 : fd.cols - 1; by1 = by1 < fd.rows - 1 ? by1 : fd.rows - 1;
+            if (bx1 < bx0 || by1 < by0) continue;              // workgroup-uniform
+            int nlow = 0;
+            for (int q0 = 0; q0 < r; q0 += kThreads) {
+                const int q = q0 + tid;
+                bool meets = false;
+                if (q < r) {
+                    const OverlayRegion *o = regs + q;
+                    meets = (o->flags & kOverlayValid) && o->bx0 <= bx1 && o->bx1 >= bx0 && o->by0 <= by1 && o->by1 >= by0;
+                }
+                int total = 0;
+                const int pos = track_prefix_count(meets, kThreads / 64, s_cnt, &total);
+                if (meets) s_low[nlow + pos] = (uint16_t)q;
+                nlow += total;
+            }
+            __syncthreads();
+            const int bw = bx1 - bx0 + 1, npix = bw * (by1 - by0 + 1);
+            int painted = 0;
+            for (int idx = tid; idx < npix; idx += kThreads) {
+                const int yy = idx / bw, x = bx0 + idx - yy * bw, y = by0 + yy;
+                const int code = overlay_paint(sp, reg, x, y);
+                if (!code || !overlay_piece_holds(piece, code)) continue;
+                bool lower = false;
+                for (int k = 0; k < nlow && !lower; k++) lower = overlay_paint(sp, regs[s_low[k]], x, y) != kPaintNone;
+                if (lower) continue;
+                overlay_put((uint8_t *)fd.ptr + (size_t)y * fd.step + (size_t)3 * x, overlay_colour(sp, reg, code), sp.alpha);
+                painted++;
+            }
+            for (int d = 32; d >= 1; d >>= 1) painted += __shfl_xor(painted, d, 64);
+            __syncthreads();                                      // every reader of s_low and s_cnt is done
+            if ((tid & 63) == 0) s_cnt[tid >> 6] = painted;
+            __syncthreads();
+            if (tid == 0) {
+                int t = 0;
+                for (int k = 0; k < kThreads / 64; k++) t += s_cnt[k];
+                if (t) atomicAdd(a.pixels + (size_t)image * M + r, t);
+            }
+        }
+    }
+}
+
+static void overlay_check(const OverlayParams &p) {
+    if (p.spec.max_regions < 1 || p.spec.max_regions > kRedactMaxRegions) throw LaunchUnsupported("overlay: max_regions must be in [1, 1024]");
+    if (p.track_state && (p.max_tracks < 1 || p.max_tracks > kTrackMaxTracks)) throw LaunchUnsupported("overlay: max_tracks must be in [1, 256]");
+    const OverlaySpec &o = p.ospec;
+    if (o.thickness < 1 || o.thickness > kOverlayMaxThickness || o.radius > kOverlayMaxRadius || o.font < 1 || o.font > kOverlayMaxFont ||
+        o.alpha < 1 || o.alpha > 255)
+        throw LaunchUnsupported("overlay: thickness, radius, font_scale or alpha out of range");
+    if (!p.oregions) throw LaunchUnsupported("overlay: no region records");
+}
+void launch_overlay_regions(hipStream_t s, const OverlayParams &p) {
+    if (p.n <= 0) return;
+    overlay_check(p);
+    if (p.motion && p.track_state) hipLaunchKernelGGL(overlay_regions_kernel<true>, dim3(p.n), dim3(kThreads), 0, s, p);
+    else hipLaunchKernelGGL(overlay_regions_kernel<false>, dim3(p.n), dim3(kThreads), 0, s, p);
+}
+void launch_overlay_draw(hipStream_t s, const OverlayParams &p) {
+    if (p.n <= 0) return;
+    overlay_check(p);
+    const int items = p.spec.max_regions * kOverlayPieces;
+    const int per_image = items < kRedactItemsPerImage ? items : kRedactItemsPerImage;
+    const long total = (long)p.n * per_image;
+    hipLaunchKernelGGL(overlay_draw_kernel, dim3((int)(total < kRedactMaxGrid ? total : kRedactMaxGrid)), dim3(kThreads), 0, s, p, per_image);
 }
 
 // =============================================================================================

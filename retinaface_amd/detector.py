@@ -14,7 +14,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (rf_face, rf_face_batch_spec, rf_face_gate, rf_face_quality, rf_options, rf_redact_spec, rf_tile_spec, rf_track,
+from ._lib import (rf_face, rf_face_batch_spec, rf_face_gate, rf_face_quality, rf_options, rf_overlay_spec, rf_redact_spec, rf_tile_spec, rf_track,
                    rf_motion_spec, rf_pyramid_spec, rf_rot_spec, rf_shot, rf_track_motion, rf_track_spec, rf_track_tag, rf_tta_spec)
 
 PRECISION_FP32, PRECISION_FP16, PRECISION_INT8 = 0, 1, 2
@@ -367,6 +367,80 @@ def redact_host(img: np.ndarray, faces, coord_scale: float = 1.0, **spec):
     return pixels[:k], st == _lib.RF_ERR_TRUNCATED
 
 
+OVERLAY_LABEL_NONE, OVERLAY_LABEL_SCORE, OVERLAY_LABEL_ID = 0, 1, 2
+
+
+def overlay_spec(thickness: int = 0, radius: int = 0, box=(0, 0, 0), point=(0, 0, 0), text=(0, 0, 0), colors_set: bool = False,
+                 alpha: int = 0, label: int = 0, font_scale: int = 0, color_by_id: bool = False, max_regions: int = 0,
+                 coast: int = 0) -> rf_overlay_spec:
+    """rf_overlay_spec; 0 = the default (thickness 2, disc radius 2 -- negative = no landmarks, red boxes, green points, white digits,
+    opaque, no label, font scale 2, max_detections regions, coast = the tracker's max_missed -- negative = no coasting tracks).  Colours
+    are (B, G, R); colors_set makes all-zero colours mean black."""
+    s = rf_overlay_spec()
+    s.struct_size = C.sizeof(rf_overlay_spec)
+    s.thickness, s.radius, s.label, s.font_scale, s.max_regions, s.coast = (int(thickness), int(radius), int(label), int(font_scale),
+                                                                            int(max_regions), int(coast))
+    if not 0 <= int(alpha) <= 255:
+        raise ValueError("alpha must fit a byte (0 = opaque)")
+    s.alpha, s.colors_set, s.color_by_id = int(alpha), int(bool(colors_set)), int(bool(color_by_id))
+    for dst, src in ((s.box, box), (s.point, point), (s.text, text)):
+        dst[0], dst[1], dst[2] = (int(v) for v in src)
+    return s
+
+
+def _as_overlay_spec(spec):
+    if spec is None or isinstance(spec, rf_overlay_spec):
+        return spec
+    return overlay_spec(**spec)
+
+
+def overlay_region(face, rows: int, cols: int, coord_scale: float = 1.0, track_id: int = 0, **spec):
+    """rf_overlay_region (host only, no GPU): (valid, 24 int32: x0, y0, x1, y1, bounding rectangle bx0, by0, bx1, by1, digit count,
+    digits (4 bits each), plate left, plate top, colour B | G << 8 | R << 16, disc mask, cx[5], cy[5]) of one face; keywords as
+    overlay_spec()"""
+    lib = _lib.load_library()
+    f = rf_face.from_buffer_copy(_face_rows([face])[0].tobytes())
+    out = (C.c_int32 * 24)()
+    st = lib.rf_overlay_region(C.byref(overlay_spec(**spec)), C.byref(f), int(track_id), float(coord_scale), int(rows), int(cols), out)
+    if st < 0:
+        raise _lib.RFError(st, "rf_overlay_region: bad spec or argument")
+    return bool(st), np.array(out, np.int32)
+
+
+def _id_block(ids, n: int, cap: int):
+    """per-image track ids as one (n, cap) int64 block, or None"""
+    if ids is None:
+        return None
+    flat = np.zeros((max(n, 1), cap), np.int64)
+    for i, v in enumerate(ids):
+        v = np.asarray(v, np.int64).reshape(-1)
+        flat[i, :min(len(v), cap)] = v[:cap]
+    return flat
+
+
+def overlay_host(img: np.ndarray, faces, coord_scale: float = 1.0, ids=None, **spec):
+    """rf_overlay_host (host only, no GPU): draws boxes, landmark discs and labels into a uint8 H x W x 3 array (any row stride) in
+    place at the given faces (ids: one track id per face, or None).  Returns (pixels per region, truncated); keywords as
+    overlay_spec()."""
+    lib = _lib.load_library()
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3 or (img.size and (img.strides[2] != 1 or img.strides[1] != 3)):
+        raise ValueError("the frame must be uint8 H x W x 3 with dense pixels (CV_8UC3, BGR)")
+    if not img.flags.writeable:
+        raise ValueError("the frame is drawn into in place: it must be writeable")
+    rows_f = _face_rows(faces)
+    k = len(rows_f)
+    pixels = np.zeros(max(k, 1), np.int32)
+    flat = np.ascontiguousarray(rows_f) if k else np.zeros((1, 15), np.float32)
+    idb = _id_block([ids], 1, max(k, 1)) if ids is not None else None
+    st = lib.rf_overlay_host(C.byref(overlay_spec(**spec)), C.c_void_p(img.ctypes.data if img.size else None), img.shape[0], img.shape[1],
+                             img.strides[0] if img.size else 0, flat.ctypes.data_as(C.POINTER(rf_face)),
+                             idb.ctypes.data_as(C.POINTER(C.c_int64)) if idb is not None else None, k, float(coord_scale),
+                             pixels.ctypes.data_as(C.POINTER(C.c_int32)))
+    if st < 0 and st != _lib.RF_ERR_TRUNCATED:
+        raise _lib.RFError(st, "rf_overlay_host: bad spec or argument")
+    return pixels[:k], st == _lib.RF_ERR_TRUNCATED
+
+
 class Tracker:
     """rf_tracker: per-stream track tables that live in device memory between calls (RetinaFace.tracker() creates one).  After every
     tracked call last_tags ((n, cap) TRACK_TAG_DTYPE), last_ended ((n, cap_ended) TRACK_DTYPE) and last_ended_counts hold the call's
@@ -551,6 +625,33 @@ class Tracker:
         counts = (C.c_int * max(n, 1))()
         t, _, tags, ended, ce, ec = self._buffers(n, cap, cap_ended)
         st = _lib.check(self._lib.rf_detect_track_redact_batch_device(
+            det._h, p, r, c, s, n, float(threshold), out, cap, counts, t, (C.c_int * max(n, 1))(*streams), tags, ended, ce, ec,
+            C.byref(sp) if sp is not None else None, self.last_pixels.ctypes.data_as(C.POINTER(C.c_int32)),
+            self.last_region_counts.ctypes.data_as(C.POINTER(C.c_int))), det._h)
+        det.truncated = self.truncated = st == _lib.RF_ERR_TRUNCATED
+        det.last_out = _faces_to_array(out, max(n * cap, 1)).reshape(max(n, 1), cap, 15)
+        det.last_counts = [int(counts[i]) for i in range(n)]
+        return (det._collect(out, counts, n, cap),) + self._results(n, counts, cap)
+
+    def detect_tracked_overlay(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], streams: Sequence[int],
+                               threshold: float = 0.5, steps: Optional[Sequence[int]] = None, cap_ended: Optional[int] = None, spec=None):
+        """rf_detect_track_overlay_batch_device: RetinaFace.detect_tracked_device + boxes, landmarks and labels drawn in place, ids
+        from the tags of this frame's step, the coasting tracks of each stream dashed (each stream at most once per call).  Returns
+        (detections, tags, ended); last_pixels / last_region_counts hold the overlay's results."""
+        det = self._det
+        n = len(ptrs)
+        p = (C.c_void_p * max(n, 1))(*ptrs)
+        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
+        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        sp = _as_overlay_spec(spec)
+        mr = det._redact_regions(sp)
+        self.last_pixels = np.zeros((max(n, 1), mr), np.int32)
+        self.last_region_counts = np.zeros(max(n, 1), np.int32)
+        cap = det.max_detections
+        out = (rf_face * max(n * cap, 1))()
+        counts = (C.c_int * max(n, 1))()
+        t, _, tags, ended, ce, ec = self._buffers(n, cap, cap_ended)
+        st = _lib.check(self._lib.rf_detect_track_overlay_batch_device(
             det._h, p, r, c, s, n, float(threshold), out, cap, counts, t, (C.c_int * max(n, 1))(*streams), tags, ended, ce, ec,
             C.byref(sp) if sp is not None else None, self.last_pixels.ctypes.data_as(C.POINTER(C.c_int32)),
             self.last_region_counts.ctypes.data_as(C.POINTER(C.c_int))), det._h)
@@ -1467,6 +1568,96 @@ class RetinaFace:
                                                          C.byref(sp) if sp is not None else None, ptrs, steps,
                                                          self.last_pixels.ctypes.data_as(C.POINTER(C.c_int32))), self._h)
         self.truncated = st == _lib.RF_ERR_TRUNCATED
+        return self._collect(out, counts, n, cap)
+
+    # ------------------------------------------------------------------ overlays
+    def overlay_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], faces, *, ids=None,
+                       steps: Optional[Sequence[int]] = None, coord_scale: Optional[Sequence[float]] = None, spec=None,
+                       tracker: Optional[Tracker] = None, streams: Optional[Sequence[int]] = None, cap_per_image: Optional[int] = None):
+        """rf_overlay_device: draws the boxes, landmark discs and labels of faces the caller supplies in place into device-resident
+        frames; faces[i]: the faces of image i (a (k, 15) array, rows or Detections), ids[i]: their track ids (or ids = None).  spec:
+        overlay_spec() or its keywords as a dict.  With a tracker, streams[i] names the stream whose coasting tracks are drawn dashed
+        (-1 = faces only).  Returns (pixels (n, max_regions) int32, region_counts (n,) int32); truncated says whether a list was cut."""
+        n = len(ptrs)
+        per = [_face_rows(f) for f in faces]
+        if len(per) != n or (ids is not None and len(ids) != n):
+            raise ValueError("faces (and ids) must hold one entry per frame")
+        cap = int(cap_per_image) if cap_per_image is not None else max([len(r) for r in per] + [1])
+        flat = np.zeros((max(n, 1), cap, 15), np.float32)
+        counts = (C.c_int * max(n, 1))()
+        for i, r in enumerate(per):
+            flat[i, :min(len(r), cap)] = r[:cap]
+            counts[i] = len(r)
+        idb = _id_block(ids, n, cap)
+        p = (C.c_void_p * max(n, 1))(*ptrs)
+        r_, c_ = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
+        s_ = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        cs = (C.c_float * max(n, 1))(*[float(v) for v in coord_scale]) if coord_scale is not None else None
+        sp = _as_overlay_spec(spec)
+        pixels = np.zeros((max(n, 1), self._redact_regions(sp)), np.int32)
+        rc = np.zeros(max(n, 1), np.int32)
+        sv = (C.c_int * max(n, 1))(*streams) if streams is not None else None
+        st = _lib.check(self._lib.rf_overlay_device(
+            self._h, p, r_, c_, s_, n, flat.ctypes.data_as(C.POINTER(rf_face)),
+            idb.ctypes.data_as(C.POINTER(C.c_int64)) if idb is not None else None, cap, counts, cs, C.byref(sp) if sp is not None else None,
+            tracker._t if tracker is not None else None, sv, pixels.ctypes.data_as(C.POINTER(C.c_int32)),
+            rc.ctypes.data_as(C.POINTER(C.c_int))), self._h)
+        self.truncated = st == _lib.RF_ERR_TRUNCATED
+        return pixels[:n], rc[:n]
+
+    def overlay_last_launch_ms(self) -> float:
+        """rf_overlay_last_launch_ms: HIP-event time of the two overlay launches of the last overlay_device call"""
+        ms = C.c_float()
+        _lib.check(self._lib.rf_overlay_last_launch_ms(self._h, C.byref(ms)), self._h)
+        return float(ms.value)
+
+    def detect_overlay_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], threshold: float = 0.5,
+                              steps: Optional[Sequence[int]] = None, spec=None) -> List[List[Detection]]:
+        """rf_detect_overlay_batch_device: detect_device + the overlay of what it finds, in place in the device frames.  last_pixels
+        holds the pixels every region painted ((n, max_regions) int32)."""
+        n = len(ptrs)
+        p = (C.c_void_p * max(n, 1))(*ptrs)
+        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
+        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        sp = _as_overlay_spec(spec)
+        self.last_pixels = np.zeros((max(n, 1), self._redact_regions(sp)), np.int32)
+        cap = self.max_detections
+        out = (rf_face * max(n * cap, 1))()
+        counts = (C.c_int * max(n, 1))()
+        st = _lib.check(self._lib.rf_detect_overlay_batch_device(self._h, p, r, c, s, n, float(threshold), out, cap, counts,
+                                                                 C.byref(sp) if sp is not None else None,
+                                                                 self.last_pixels.ctypes.data_as(C.POINTER(C.c_int32))), self._h)
+        self.truncated = st == _lib.RF_ERR_TRUNCATED
+        self.last_out = _faces_to_array(out, max(n * cap, 1)).reshape(max(n, 1), cap, 15)
+        self.last_counts = [int(counts[i]) for i in range(n)]
+        return self._collect(out, counts, n, cap)
+
+    def detect_overlay(self, imgs: Sequence[np.ndarray], threshold: float = 0.5, spec=None) -> List[List[Detection]]:
+        """rf_detect_overlay_batch: detectBatchImages + the overlay; the frames (uint8 H x W x 3, dense pixels, any row stride,
+        writeable) are drawn into in place."""
+        n = len(imgs)
+        ptrs = (C.c_void_p * max(n, 1))()
+        rows, cols, steps = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
+        for i, im in enumerate(imgs):
+            if im is None or im.size == 0:
+                ptrs[i], rows[i], cols[i], steps[i] = None, 0, 0, 0
+                continue
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 or im.strides[2] != 1 or im.strides[1] != 3:
+                raise ValueError("frames must be uint8 H x W x 3 with dense pixels (CV_8UC3, BGR)")
+            if not im.flags.writeable:
+                raise ValueError("frames are drawn into in place: they must be writeable")
+            ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
+        sp = _as_overlay_spec(spec)
+        self.last_pixels = np.zeros((max(n, 1), self._redact_regions(sp)), np.int32)
+        cap = self.max_detections
+        out = (rf_face * max(n * cap, 1))()
+        counts = (C.c_int * max(n, 1))()
+        st = _lib.check(self._lib.rf_detect_overlay_batch(self._h, ptrs, rows, cols, steps, n, float(threshold), out, cap, counts,
+                                                          C.byref(sp) if sp is not None else None, ptrs, steps,
+                                                          self.last_pixels.ctypes.data_as(C.POINTER(C.c_int32))), self._h)
+        self.truncated = st == _lib.RF_ERR_TRUNCATED
+        self.last_out = _faces_to_array(out, max(n * cap, 1)).reshape(max(n, 1), cap, 15)
+        self.last_counts = [int(counts[i]) for i in range(n)]
         return self._collect(out, counts, n, cap)
 
     # ------------------------------------------------------------------ flip test-time augmentation
