@@ -1689,6 +1689,42 @@ int rf_plan_folded(const char *model_dir, const char *stem, const char *op, floa
             else if (tail == ".c") f = &p.ssh[i].conv_c;
             else if (tail == ".head") f = &p.ssh[i].head;
         }
+        // "stem2.<c0|c2|c3|c4|floor2|floor3>": the constants of the fp16 engine's first launch (stem2_kernel) that exist only inside the packed
+        // image, read back from the image WeightPack<half_t>::pack emits: c0 = conv0 weights + the offset-folded MFMA bias; c2 = conv2 weights +
+        // the bias centred by mu2; c3 = the equalised conv3 taps as the packed halves + its centred bias; c4 = the equalised conv4 weights + its
+        // bias with W mu3 folded in; floor2 / floor3 = the per-channel floors -mu2 / -mu3 of the two DC-centred tiles (in w and in b)
+        rf::FoldedConv s2;
+        if (!f && name.compare(0, 6, "stem2.") == 0 && p.blocks.size() >= 2) {
+            rf::WeightPack<rf::half_t> wp;
+            wp.pack(p);                                // host only: nothing is uploaded
+            const std::vector<unsigned char> &img = wp.arena_.host();
+            auto floats = [&](size_t off, int n) { std::vector<float> v(n); memcpy(v.data(), img.data() + off, (size_t)n * 4); return v; };
+            auto halves = [&](size_t off, int n) {
+                std::vector<float> v(n);
+                for (int j = 0; j < n; j++) { rf::half_t h; memcpy(&h, img.data() + off + 2 * (size_t)j, 2); v[j] = (float)h; }
+                return v;
+            };
+            const std::string t = name.substr(6);
+            rf::FoldedConv dwq = p.blocks[1].dw, pwq = p.blocks[1].pw;
+            rf::WeightPack<rf::half_t>::equalize_depthwise(dwq, pwq);
+            if (t == "c0") { s2 = p.conv0; s2.b = floats(wp.c0_b_mma_, 8); f = &s2; }
+            else if (t == "c2") { s2 = p.blocks[0].pw; s2.b = floats(wp.stem2_c2_b_, 16); f = &s2; }
+            else if (t == "c3") {
+                s2 = dwq;
+                const std::vector<float> taps = halves(wp.stem2_dw_.w, 9 * 16);          // [tap][channel]
+                for (int ch = 0; ch < 16; ch++)
+                    for (int tp = 0; tp < 9; tp++) s2.w[(size_t)ch * 9 + tp] = taps[(size_t)tp * 16 + ch];
+                s2.b = floats(wp.stem2_dw_.b, 16);
+                f = &s2;
+            }
+            else if (t == "c4") { s2 = pwq; s2.b = floats(wp.stem2_pw_.b, 32); f = &s2; }
+            else if (t == "floor2" || t == "floor3") {
+                s2.cout = 16; s2.cin = 1; s2.k = 1; s2.group = 1;
+                s2.w = halves(t == "floor2" ? wp.stem2_c2_floor_ : wp.stem2_c3_floor_, 16);
+                s2.b = s2.w;
+                f = &s2;
+            }
+        }
         if (!f) throw rf::ArgError("unknown plan op '" + name + "'");
         if (dims) { dims[0] = f->cout; dims[1] = f->k; dims[2] = f->k; dims[3] = f->cin / f->group; }
         if (w) { if (cap_w < f->w.size()) throw rf::ArgError("w too small"); memcpy(w, f->w.data(), f->w.size() * 4); }
