@@ -119,6 +119,26 @@ struct NetKind {
     std::function<void(const Plan &, const NetSite &, LaneNet *)> build_net;
 };
 
+// The open pass call: tiled, TTA, pyramid and rotation detection turn a call's frames into passes that go through detect()'s ordinary
+// launches, in call order, so image i of a launch is pass next_pass + i.  What differs between the modes is bound when the call is
+// opened (the two callables); the launch path (launch_lane_passes) does not know which mode it serves.
+constexpr size_t kPassEntryMax = std::max(std::max(sizeof(TileEntry), sizeof(TtaEntry)), std::max(sizeof(PyrEntry), sizeof(RotEntry)));
+struct PassCall {
+    // gather(stream, faces, face_stride, counts, table, n): the mode's gather over the n passes of one launch (table: their entries)
+    using Gather = std::function<void(hipStream_t, const uint8_t *, int, const int *, const void *, int)>;
+    // merge(stream, d_params): the call's merge, behind the gather of its last launch
+    using Merge = std::function<void(hipStream_t, const RunParams *)>;
+    bool on = false;
+    const char *name = "";                // the mode, as the two error messages spell it
+    std::vector<uint8_t> table;           // the call's pass table: `total` entries of entry_bytes
+    size_t entry_bytes = 0;
+    int total = 0, next_pass = 0;
+    std::vector<int> lanes_used;          // lanes that carried a launch of the call other than its last
+    hipEvent_t inputs_ready = nullptr;    // recorded behind the side-stream copies the passes read; null: the call made none
+    Gather gather;
+    Merge merge;
+};
+
 class EngineImpl final : public Engine {
 public:
     // `plan` may be a skeleton (no weights): everything weight-related comes packed in the WeightPack behind `kind` (built from
@@ -208,16 +228,14 @@ public:
         for (void *p : host_allocs_) (void)hipHostFree(p);
         if (align_stream_) { (void)hipStreamSynchronize(align_stream_); (void)hipStreamDestroy(align_stream_); }
         for (DeviceScratch *b : {&align_crops_, &align_mats_, &align_tab_, &fb_state_, &fq_records_, &fq_packed_, &fq_offsets_, &tile_cand_, &tile_count_, &tile_out_,
-                                 &tile_outcount_, &tile_tab_, &tile_frames_, &tta_cand_, &tta_count_, &tta_frames_, &tta_mirror_, &pyr_frames_, &pyr_zoom_, &rot_frames_, &rot_copies_,
+                                 &tile_outcount_, &tile_tab_, &pass_frames_, &tta_cand_, &tta_count_, &tta_mirror_, &pyr_zoom_, &rot_copies_,
                                  &red_regions_, &red_counts_, &red_cells_, &red_frames_, &red_shadow_}) b->release();
         for (HostScratch *b : {&trk_tags_, &trk_ended_, &trk_counts_, &tta_out_, &tta_votes_, &tta_outcount_, &shot_out_, &shot_info_}) b->release();
         for (auto &t : trackers_) t->release();
         for (hipEvent_t e : trk_ev_) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : shot_ev_) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : red_ev_) if (e) (void)hipEventDestroy(e);
-        if (tta_mirror_done_) (void)hipEventDestroy(tta_mirror_done_);
-        if (pyr_zoom_done_) (void)hipEventDestroy(pyr_zoom_done_);
-        if (rot_copies_done_) (void)hipEventDestroy(rot_copies_done_);
+        if (inputs_ready_) (void)hipEventDestroy(inputs_ready_);
         kind_.arena->release();
         for (auto &e : prof_ev_) (void)hipEventDestroy(e);
     }
@@ -598,6 +616,137 @@ public:
         else face_batch_copy_out(rq, d_tensor, d_mats, cnt, n, rq.spec.max_faces, overflow);
     }
 
+    // -------------------------------------------------------------------------------- pass calls
+    // What tiled, TTA, pyramid and rotation detection share (PassCall).  a..d: the arrays the entry point needs when n > 0.
+    static void pass_check_args(int n, const void *a, const void *b, const void *c, const void *d, rf_face *out, int cap_per_image, int max_faces) {
+        static_assert(kTileMaxFaces == 4096 && kTtaMaxFaces == 4096, "the message below names the bound");
+        if (n < 0 || (n > 0 && (!a || !b || !c || !d))) throw ArgError("null argument");
+        if (cap_per_image < 0 || (cap_per_image > 0 && !out)) throw ArgError("out is null");
+        if (max_faces < 1 || max_faces > 4096) throw ArgError("max_faces must be in [1, 4096]");
+    }
+
+    // the row pitch of each frame of a call (default cols * 3), every frame checked
+    std::vector<int> checked_steps(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n) const {
+        std::vector<int> st((size_t)std::max(n, 1));
+        for (int i = 0; i < n; i++) {
+            st[i] = steps ? steps[i] : cols[i] * 3;
+            check_frame(frames[i], rows[i], cols[i], st[i]);
+        }
+        return st;
+    }
+
+    // Where the passes of a call read frame i (null: not a live frame): the caller's device frame, or host frames uploaded once,
+    // densely, each at a 256-byte-aligned offset of one block (st[i] becomes cols * 3).  One block serves the four modes: their calls
+    // are synchronous and never overlap.
+    template <class Live>
+    std::vector<const uint8_t *> pass_frame_bases(const uint8_t *const *frames, const int *rows, const int *cols, std::vector<int> &st, int n,
+                                                  bool on_device, Live live) {
+        std::vector<const uint8_t *> base((size_t)n, nullptr);
+        if (on_device) {
+            for (int i = 0; i < n; i++) base[i] = live(i) ? frames[i] : nullptr;
+            return base;
+        }
+        size_t bytes = 0;
+        std::vector<size_t> off((size_t)n, 0);
+        for (int i = 0; i < n; i++)
+            if (live(i)) { off[i] = bytes; bytes += align256((size_t)rows[i] * cols[i] * 3); }
+        uint8_t *d = pass_frames_.reserve(bytes);
+        for (int i = 0; i < n; i++) {
+            if (!live(i)) continue;
+            RF_HIP(hipMemcpy2D(d + off[i], (size_t)cols[i] * 3, frames[i], (size_t)st[i], (size_t)cols[i] * 3, (size_t)rows[i], hipMemcpyHostToDevice));
+            base[i] = d + off[i];
+            st[i] = cols[i] * 3;
+        }
+        return base;
+    }
+
+    // the passes of a call as detect() takes them: views of the frames or of the copies made for the call (an empty pass stays null / 0)
+    struct PassViews {
+        std::vector<const uint8_t *> ptr;
+        std::vector<int> rows, cols, step;
+        explicit PassViews(int P) : ptr((size_t)P, nullptr), rows((size_t)P, 0), cols((size_t)P, 0), step((size_t)P, 0) {}
+        void set(int q, const uint8_t *p, int r, int c, int s) { ptr[q] = p; rows[q] = r; cols[q] = c; step[q] = s; }
+    };
+
+    // the event behind the mirrored / zoomed / rotated copies a call has just launched on the side stream (PassCall::inputs_ready)
+    hipEvent_t record_inputs_ready() {
+        if (!inputs_ready_) RF_HIP(hipEventCreateWithFlags(&inputs_ready_, hipEventDisableTiming));
+        RF_HIP(hipGetLastError());
+        RF_HIP(hipEventRecord(inputs_ready_, align_stream_));
+        return inputs_ready_;
+    }
+
+    // the mode's gather into a candidate block set (cand, count: read when it runs, after the set has been opened)
+    template <class Map, class Block> PassCall::Gather gather_into(int edge, const Block &cand, const Block &count, int cap) {
+        return [this, edge, &cand, &count, cap](hipStream_t st, const uint8_t *faces, int face_stride, const int *counts, const void *table, int n) {
+            PassGatherParams<typename Map::Entry> gp;
+            gp.faces = faces; gp.face_stride = face_stride; gp.faces_per_pass = opt_.max_detections;
+            gp.counts = counts; gp.table = (const typename Map::Entry *)table;
+            gp.n = n; gp.edge = edge; gp.rank_stride = opt_.max_detections;
+            gp.cand = (Candidate *)cand.ptr; gp.cand_count = (int *)count.ptr; gp.cap = cap;
+            launch_pass_gather<Map>(st, gp);
+        };
+    }
+
+    // Open a pass call and run it: a super-batch of earlier enqueues has been started (launch_pending()), so every launch detect()
+    // makes now carries passes of this call only.  `dirty` is the flag of the block set the call gathers into: set until the call has
+    // ended well, so that an error in between makes the next open zero the counters.  Returns detect()'s truncated.
+    template <class Entry>
+    bool run_passes(const char *name, const std::vector<Entry> &entries, const PassViews &v, float threshold, hipEvent_t inputs_ready,
+                    PassCall::Gather gather, PassCall::Merge merge, bool &dirty) {
+        const int P = (int)entries.size();
+        passes_.name = name;
+        passes_.table.assign((const uint8_t *)entries.data(), (const uint8_t *)(entries.data() + P));
+        passes_.entry_bytes = sizeof(Entry);
+        passes_.total = P; passes_.next_pass = 0;
+        passes_.lanes_used.clear();
+        passes_.inputs_ready = inputs_ready;
+        passes_.gather = std::move(gather); passes_.merge = std::move(merge);
+        passes_.on = true;
+        dirty = true;
+        struct Off { bool &on; ~Off() { on = false; } } off_guard{passes_.on};
+        std::vector<int> pass_counts((size_t)P);
+        bool tr = false;
+        detect(v.ptr.data(), v.rows.data(), v.cols.data(), v.step.data(), P, true, threshold, nullptr, 0, pass_counts.data(), &tr);
+        passes_.on = false;
+        if (passes_.next_pass != P) throw HipError(std::string(name) + ": the merge was not launched");
+        // every launch of the call has been waited for; the merge (and what it carries) ran in front of the last one's `done`
+        dirty = false;
+        return tr;
+    }
+
+    // The stand-alone merge of a mode: gather and merge over faces the caller brings, max_detections per pass.  One table -- run
+    // parameters | pass table | counts | faces (60-byte records) -- crosses in one copy on the side stream, which the host waits for.
+    // `open` opens the block set the gather writes, `dirty` is that set's flag (run_passes).
+    template <class Entry, class Open>
+    void merge_passes(const std::vector<Entry> &entries, int n, const rf_face *faces, const int *pass_counts, bool *truncated, Open open,
+                      const PassCall::Gather &gather, const PassCall::Merge &merge, bool &dirty) {
+        const int P = (int)entries.size(), md = opt_.max_detections;
+        for (int p = 0; p < P; p++)
+            if (pass_counts[p] < 0) throw ArgError("negative face count");
+        const size_t o_tab = 256, o_cnt = o_tab + align256((size_t)P * sizeof(Entry)), o_face = o_cnt + align256((size_t)P * sizeof(int)),
+                     total = o_face + (size_t)P * md * sizeof(rf_face);
+        align_host_.assign(total, 0);
+        *(RunParams *)align_host_.data() = RunParams{0.f, nms_threshold_, n, 0};
+        memcpy(align_host_.data() + o_tab, entries.data(), (size_t)P * sizeof(Entry));
+        int *cnt = (int *)(align_host_.data() + o_cnt);
+        for (int p = 0; p < P; p++) {
+            cnt[p] = std::min(pass_counts[p], md);
+            if (pass_counts[p] > md) *truncated = true;
+            if (cnt[p]) memcpy(align_host_.data() + o_face + (size_t)p * md * sizeof(rf_face), faces + (size_t)p * md, (size_t)cnt[p] * sizeof(rf_face));
+        }
+        uint8_t *d_tab = align_tab_.reserve(total);
+        open();
+        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+        dirty = true;
+        RF_HIP(hipMemcpyAsync(d_tab, align_host_.data(), total, hipMemcpyHostToDevice, align_stream_));
+        gather(align_stream_, d_tab + o_face, (int)sizeof(rf_face), (const int *)(d_tab + o_cnt), d_tab + o_tab, P);
+        merge(align_stream_, (const RunParams *)d_tab);
+        RF_HIP(hipGetLastError());
+        RF_HIP(hipStreamSynchronize(align_stream_));
+        dirty = false;
+    }
+
     // -------------------------------------------------------------------------------- tiled detection
     // The plans of a call's frames as one pass table (frames in call order, passes in plan order); first[i]: frame i's first pass.
     // A NULL / empty frame is one pass that gathers nothing (frame = -1).  `have_ptrs` false: tile_merge(), which has no pixels.
@@ -641,16 +790,6 @@ public:
             RF_HIP(hipDeviceSynchronize());
             tile_dirty_ = false;
         }
-    }
-
-    void tile_launch_gather(hipStream_t st, const uint8_t *faces, int face_stride, const int *counts, const TileEntry *table, int passes,
-                            const TileSpec &sp) {
-        TileGatherParams gp;
-        gp.faces = faces; gp.face_stride = face_stride; gp.faces_per_pass = opt_.max_detections;
-        gp.counts = counts; gp.table = table;
-        gp.n = passes; gp.edge = sp.edge; gp.rank_stride = opt_.max_detections;
-        gp.cand = (Candidate *)tile_cand_.ptr; gp.cand_count = (int *)tile_count_.ptr; gp.cap = kTileMergeCap;
-        launch_tile_gather(st, gp);
     }
 
     // the merge: the detector's own NMS kernel over the gathered candidates, one workgroup per frame (`anchor` holds g)
@@ -701,55 +840,29 @@ public:
                       bool *overflow) override {
         *truncated = false;
         *overflow = false;
-        if (n < 0 || (n > 0 && (!frames || !rows || !cols || !counts))) throw ArgError("null argument");
-        if (cap_per_image < 0 || (cap_per_image > 0 && !out)) throw ArgError("out is null");
-        if (rq.spec.max_faces < 1 || rq.spec.max_faces > kTileMaxFaces) throw ArgError("max_faces must be in [1, 4096]");
+        pass_check_args(n, frames, rows, cols, counts, out, cap_per_image, rq.spec.max_faces);
         if (rq.fb) {
             check_face_batch_request(*rq.fb);
             if ((long)n * rq.fb->spec.max_faces > (1L << 24)) throw ArgError("n x max_faces: more than 2^24 faces in one call");
         }
-        std::vector<int> st((size_t)std::max(n, 1));
-        for (int i = 0; i < n; i++) {
-            st[i] = steps ? steps[i] : cols[i] * 3;
-            check_frame(frames[i], rows[i], cols[i], st[i]);
-        }
+        std::vector<int> st = checked_steps(frames, rows, cols, steps, n);
         std::vector<TileEntry> entries;
         std::vector<int> first;
         tile_build_passes(rq.spec, frames, true, rows, cols, n, &entries, &first);
         if (n == 0) { if (rq.fb && rq.fb->offsets) rq.fb->offsets[0] = 0; return; }
         DeviceGuard guard(device_);
-        // host frames are uploaded once, densely; the passes are views of that copy
-        std::vector<const uint8_t *> base((size_t)n, nullptr);
-        if (!on_device) {
-            size_t bytes = 0;
-            std::vector<size_t> off((size_t)n, 0);
-            for (int i = 0; i < n; i++)
-                if (entries[first[i]].frame >= 0) { off[i] = bytes; bytes += align256((size_t)rows[i] * cols[i] * 3); }
-            uint8_t *d = tile_frames_.reserve(bytes);
-            for (int i = 0; i < n; i++) {
-                if (entries[first[i]].frame < 0) continue;
-                RF_HIP(hipMemcpy2D(d + off[i], (size_t)cols[i] * 3, frames[i], (size_t)st[i], (size_t)cols[i] * 3, (size_t)rows[i], hipMemcpyHostToDevice));
-                base[i] = d + off[i];
-                st[i] = cols[i] * 3;
-            }
-        } else {
-            for (int i = 0; i < n; i++) base[i] = entries[first[i]].frame >= 0 ? frames[i] : nullptr;
-        }
-        const int P = (int)entries.size();
-        std::vector<const uint8_t *> vp((size_t)P);
-        std::vector<int> vr((size_t)P), vc((size_t)P), vs((size_t)P), pass_counts((size_t)P);
+        // the passes are views of the frames (host frames: of their one dense copy)
+        const std::vector<const uint8_t *> base =
+            pass_frame_bases(frames, rows, cols, st, n, on_device, [&](int i) { return entries[first[i]].frame >= 0; });
+        PassViews v((int)entries.size());
         tile_fd_.assign((size_t)n, FrameDesc{nullptr, 0, 0, 0, 0});
         for (int i = 0; i < n; i++) {
             if (base[i]) tile_fd_[i] = FrameDesc{base[i], rows[i], cols[i], st[i], 0};
             for (int p = first[i]; p < first[i + 1]; p++) {
                 const TileEntry &e = entries[p];
-                if (e.frame < 0) { vp[p] = nullptr; vr[p] = vc[p] = vs[p] = 0; continue; }
-                vp[p] = base[i] + (size_t)e.y0 * st[i] + (size_t)3 * e.x0;
-                vr[p] = e.th; vc[p] = e.tw; vs[p] = st[i];
+                if (e.frame >= 0) v.set(p, base[i] + (size_t)e.y0 * st[i] + (size_t)3 * e.x0, e.th, e.tw, st[i]);
             }
         }
-        // as in detect_align(): a super-batch of earlier enqueues starts now, every later launch carries passes of this call only,
-        // in call order, so image i of a launch is pass tile_.next_pass + i
         launch_pending();
         tile_open(n, rq.spec);
         uint8_t *d_tensor = nullptr;
@@ -761,20 +874,15 @@ public:
             // the frame table of those launches is known now: it is on the device before the call's first launch
             RF_HIP(hipMemcpy(tile_tab_.reserve((size_t)n * sizeof(FrameDesc)), tile_fd_.data(), (size_t)n * sizeof(FrameDesc), hipMemcpyHostToDevice));
         }
-        tile_.rq = rq; tile_.entries.swap(entries);
-        tile_.n_frames = n; tile_.next_pass = 0;
-        tile_.lanes_used.clear();
-        tile_.d_tensor = d_tensor; tile_.d_mats = d_mats;
-        tile_.on = true;
-        tile_dirty_ = true;                      // until the call has ended well
-        struct Off { bool &on; ~Off() { on = false; } } off_guard{tile_.on};
-        bool tr = false;
-        detect(vp.data(), vr.data(), vc.data(), vs.data(), P, true, threshold, nullptr, 0, pass_counts.data(), &tr);
-        tile_.on = false;
-        if (tile_.next_pass != P) throw HipError("tiled detection: the merge was not launched");
-        // every launch of the call has been waited for; the merge (and rq.fb's launches) ran in front of the last one's `done`
-        tile_dirty_ = false;
-        *truncated = tr;
+        // behind the merge, for the fused call, the face-batch launches over the merged faces
+        const TileSpec sp = rq.spec;
+        const FaceBatchRequest *fb = rq.fb;
+        auto merge = [=](hipStream_t s, const RunParams *d_params) {
+            tile_launch_merge(s, n, sp, d_params);
+            if (fb) launch_tiled_face_batch(s, n, *fb, sp.max_faces, d_tensor, d_mats);
+        };
+        *truncated = run_passes("tiled detection", entries, v, threshold, nullptr,
+                                gather_into<TileMap>(sp.edge, tile_cand_, tile_count_, kTileMergeCap), merge, tile_dirty_);
         tile_copy_out(n, rq, out, cap_per_image, counts, truncated);
         if (rq.fb) {
             const int limit = std::min(rq.fb->spec.max_faces, rq.spec.max_faces);
@@ -786,39 +894,16 @@ public:
     void tile_merge(const int *rows, const int *cols, int n, const TileRequest &rq, const rf_face *faces, const int *pass_counts,
                     rf_face *out, int cap_per_image, int *counts, bool *truncated) override {
         *truncated = false;
-        if (n < 0 || (n > 0 && (!rows || !cols || !counts || !faces || !pass_counts))) throw ArgError("null argument");
-        if (cap_per_image < 0 || (cap_per_image > 0 && !out)) throw ArgError("out is null");
-        if (rq.spec.max_faces < 1 || rq.spec.max_faces > kTileMaxFaces) throw ArgError("max_faces must be in [1, 4096]");
+        pass_check_args(n, rows, cols, counts, faces && pass_counts ? faces : nullptr, out, cap_per_image, rq.spec.max_faces);
         std::vector<TileEntry> entries;
         std::vector<int> first;
         tile_build_passes(rq.spec, nullptr, false, rows, cols, n, &entries, &first);
         if (n == 0) return;
-        const int P = (int)entries.size(), md = opt_.max_detections;
-        for (int p = 0; p < P; p++)
-            if (pass_counts[p] < 0) throw ArgError("negative face count");
         DeviceGuard guard(device_);
-        // one table: run parameters | pass table | counts | faces (60-byte records, max_detections per pass)
-        const size_t o_tab = 256, o_cnt = o_tab + align256((size_t)P * sizeof(TileEntry)), o_face = o_cnt + align256((size_t)P * sizeof(int)),
-                     total = o_face + (size_t)P * md * sizeof(rf_face);
-        align_host_.assign(total, 0);
-        *(RunParams *)align_host_.data() = RunParams{0.f, nms_threshold_, n, 0};
-        memcpy(align_host_.data() + o_tab, entries.data(), (size_t)P * sizeof(TileEntry));
-        int *cnt = (int *)(align_host_.data() + o_cnt);
-        for (int p = 0; p < P; p++) {
-            cnt[p] = std::min(pass_counts[p], md);
-            if (pass_counts[p] > md) *truncated = true;
-            if (cnt[p]) memcpy(align_host_.data() + o_face + (size_t)p * md * sizeof(rf_face), faces + (size_t)p * md, (size_t)cnt[p] * sizeof(rf_face));
-        }
-        uint8_t *d_tab = align_tab_.reserve(total);
-        tile_open(n, rq.spec);
-        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
-        tile_dirty_ = true;
-        RF_HIP(hipMemcpyAsync(d_tab, align_host_.data(), total, hipMemcpyHostToDevice, align_stream_));
-        tile_launch_gather(align_stream_, d_tab + o_face, (int)sizeof(rf_face), (const int *)(d_tab + o_cnt), (const TileEntry *)(d_tab + o_tab), P, rq.spec);
-        tile_launch_merge(align_stream_, n, rq.spec, (const RunParams *)d_tab);
-        RF_HIP(hipGetLastError());
-        RF_HIP(hipStreamSynchronize(align_stream_));
-        tile_dirty_ = false;
+        const TileSpec sp = rq.spec;
+        merge_passes(entries, n, faces, pass_counts, truncated, [&] { tile_open(n, sp); },
+                     gather_into<TileMap>(sp.edge, tile_cand_, tile_count_, kTileMergeCap),
+                     [=](hipStream_t s, const RunParams *d_params) { tile_launch_merge(s, n, sp, d_params); }, tile_dirty_);
         tile_copy_out(n, rq, out, cap_per_image, counts, truncated);
     }
 
@@ -862,15 +947,6 @@ public:
         }
     }
 
-    void tta_launch_gather(hipStream_t st, const uint8_t *faces, int face_stride, const int *counts, const TtaEntry *table, int passes) {
-        TtaGatherParams gp;
-        gp.faces = faces; gp.face_stride = face_stride; gp.faces_per_pass = opt_.max_detections;
-        gp.counts = counts; gp.table = table;
-        gp.n = passes; gp.rank_stride = opt_.max_detections;
-        gp.cand = (Candidate *)tta_cand_.ptr; gp.cand_count = (int *)tta_count_.ptr; gp.cap = kTtaMergeCap;
-        launch_tta_gather(st, gp);
-    }
-
     void tta_launch_merge(hipStream_t st, int n, const TtaSpec &sp, const RunParams *d_params) {
         VoteMergeParams vp;
         vp.cand = (const Candidate *)tta_cand_.ptr; vp.cand_count = (int *)tta_count_.ptr; vp.cap = kTtaMergeCap;
@@ -902,13 +978,6 @@ public:
         }
     }
 
-    static void tta_check_args(int n, const void *a, const void *b, const void *c, const void *d, rf_face *out, int cap_per_image,
-                               const TtaSpec &sp) {
-        if (n < 0 || (n > 0 && (!a || !b || !c || !d))) throw ArgError("null argument");
-        if (cap_per_image < 0 || (cap_per_image > 0 && !out)) throw ArgError("out is null");
-        if (sp.max_faces < 1 || sp.max_faces > kTtaMaxFaces) throw ArgError("max_faces must be in [1, 4096]");
-    }
-
     void mirror(const void *d_src, int rows, int cols, int step, void *d_dst, int dst_step) override {
         if (rows < 0 || cols < 0) throw ArgError("negative frame size");
         if (rows == 0 || cols == 0) return;
@@ -923,121 +992,63 @@ public:
         RF_HIP(hipStreamSynchronize(align_stream_));
     }
 
+    // the voting merge of a TTA, pyramid or rotation call over n frames
+    PassCall::Merge vote_merge_of(int n, const TtaSpec &sp) {
+        return [=](hipStream_t s, const RunParams *d_params) { tta_launch_merge(s, n, sp, d_params); };
+    }
+
     void detect_tta(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,
                     float threshold, rf_face *out, int cap_per_image, int *counts, bool *truncated, const TtaRequest &rq) override {
         *truncated = false;
-        tta_check_args(n, frames, rows, cols, counts, out, cap_per_image, rq.spec);
-        std::vector<int> st((size_t)std::max(n, 1));
-        for (int i = 0; i < n; i++) {
-            st[i] = steps ? steps[i] : cols[i] * 3;
-            check_frame(frames[i], rows[i], cols[i], st[i]);
-        }
+        pass_check_args(n, frames, rows, cols, counts, out, cap_per_image, rq.spec.max_faces);
+        std::vector<int> st = checked_steps(frames, rows, cols, steps, n);
         std::vector<TtaEntry> entries;
         tta_build_passes(rq.spec, frames, true, rows, cols, n, &entries);
         if (n == 0) return;
         DeviceGuard guard(device_);
         const int PP = rq.spec.passes();
-        auto live = [&](int i) { return entries[(size_t)i * PP].frame >= 0; };
-        // host frames are uploaded once, densely
-        std::vector<const uint8_t *> base((size_t)n, nullptr);
-        if (!on_device) {
-            size_t bytes = 0;
-            std::vector<size_t> off((size_t)n, 0);
-            for (int i = 0; i < n; i++)
-                if (live(i)) { off[i] = bytes; bytes += align256((size_t)rows[i] * cols[i] * 3); }
-            uint8_t *d = tta_frames_.reserve(bytes);
-            for (int i = 0; i < n; i++) {
-                if (!live(i)) continue;
-                RF_HIP(hipMemcpy2D(d + off[i], (size_t)cols[i] * 3, frames[i], (size_t)st[i], (size_t)cols[i] * 3, (size_t)rows[i], hipMemcpyHostToDevice));
-                base[i] = d + off[i];
-                st[i] = cols[i] * 3;
-            }
-        } else {
-            for (int i = 0; i < n; i++) base[i] = live(i) ? frames[i] : nullptr;
-        }
-        // as in detect_tiled(): a super-batch of earlier enqueues starts now, every later launch carries passes of this call only
+        const std::vector<const uint8_t *> base =
+            pass_frame_bases(frames, rows, cols, st, n, on_device, [&](int i) { return entries[(size_t)i * PP].frame >= 0; });
         launch_pending();
         // The mirrored copies: dense, each at a 256-byte-aligned offset of one block (what a freshly allocated dense frame looks
         // like to conv0's staging), made on the side stream; every lane that launches a pass of the call waits for them on the device.
-        uint8_t *d_mirror = nullptr;
-        std::vector<size_t> moff((size_t)n, 0);
-        if (rq.spec.flip) {
-            size_t bytes = 0;
-            for (int i = 0; i < n; i++)
-                if (live(i)) { moff[i] = bytes; bytes += align256((size_t)rows[i] * cols[i] * 3); }
-            d_mirror = tta_mirror_.reserve(bytes);
-            if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
-            if (!tta_mirror_done_) RF_HIP(hipEventCreateWithFlags(&tta_mirror_done_, hipEventDisableTiming));
-            std::vector<MirrorParams> mp;
-            for (int i = 0; i < n; i++)
-                if (live(i)) mp.push_back(MirrorParams{base[i], rows[i], cols[i], st[i], d_mirror + moff[i], cols[i] * 3});
-            launch_mirror_rows(align_stream_, mp.data(), (int)mp.size());
-            RF_HIP(hipGetLastError());
-            RF_HIP(hipEventRecord(tta_mirror_done_, align_stream_));
-        }
-        const int P = (int)entries.size();
-        std::vector<const uint8_t *> vp((size_t)P, nullptr);
-        std::vector<int> vr((size_t)P, 0), vc((size_t)P, 0), vs((size_t)P, 0), pass_counts((size_t)P);
+        PassViews v((int)entries.size());
+        hipEvent_t mirrored = nullptr;
+        std::vector<MirrorParams> mp;
+        size_t bytes = 0;
+        for (int i = 0; i < n; i++)
+            if (base[i]) bytes += align256((size_t)rows[i] * cols[i] * 3);
+        uint8_t *d_mirror = rq.spec.flip ? tta_mirror_.reserve(bytes) : nullptr;
         for (int i = 0; i < n; i++) {
-            if (!live(i)) continue;
-            for (int p = 0; p < PP; p++) {
-                const size_t q = (size_t)i * PP + p;
-                vp[q] = p ? d_mirror + moff[i] : base[i];
-                vr[q] = rows[i]; vc[q] = cols[i]; vs[q] = p ? cols[i] * 3 : st[i];
-            }
+            if (!base[i]) continue;
+            v.set(i * PP, base[i], rows[i], cols[i], st[i]);
+            if (!rq.spec.flip) continue;
+            mp.push_back(MirrorParams{base[i], rows[i], cols[i], st[i], d_mirror, cols[i] * 3});
+            v.set(i * PP + 1, d_mirror, rows[i], cols[i], cols[i] * 3);
+            d_mirror += align256((size_t)rows[i] * cols[i] * 3);
+        }
+        if (rq.spec.flip) {
+            if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+            launch_mirror_rows(align_stream_, mp.data(), (int)mp.size());
+            mirrored = record_inputs_ready();
         }
         tta_open(n, rq.spec);
-        tta_.rq = rq; tta_.entries.swap(entries);
-        tta_.n_frames = n; tta_.next_pass = 0;
-        tta_.lanes_used.clear();
-        tta_.wait_mirror = rq.spec.flip != 0;
-        tta_.on = true;
-        tta_dirty_ = true;                       // until the call has ended well
-        struct Off { bool &on; ~Off() { on = false; } } off_guard{tta_.on};
-        bool tr = false;
-        detect(vp.data(), vr.data(), vc.data(), vs.data(), P, true, threshold, nullptr, 0, pass_counts.data(), &tr);
-        tta_.on = false;
-        if (tta_.next_pass != P) throw HipError("test-time augmentation: the merge was not launched");
-        // every launch of the call has been waited for; the merge ran in front of the last one's `done`
-        tta_dirty_ = false;
-        *truncated = tr;
+        *truncated = run_passes("test-time augmentation", entries, v, threshold, mirrored,
+                                gather_into<TtaMap>(0, tta_cand_, tta_count_, kTtaMergeCap), vote_merge_of(n, rq.spec), tta_dirty_);
         tta_copy_out(n, rq, out, cap_per_image, counts, truncated);
     }
 
     void tta_merge(const int *rows, const int *cols, int n, const TtaRequest &rq, const rf_face *faces, const int *pass_counts,
                    rf_face *out, int cap_per_image, int *counts, bool *truncated) override {
         *truncated = false;
-        tta_check_args(n, rows, cols, counts, faces, out, cap_per_image, rq.spec);
+        pass_check_args(n, rows, cols, counts, faces, out, cap_per_image, rq.spec.max_faces);
         if (n > 0 && !pass_counts) throw ArgError("null argument");
         std::vector<TtaEntry> entries;
         tta_build_passes(rq.spec, nullptr, false, rows, cols, n, &entries);
         if (n == 0) return;
-        const int P = (int)entries.size(), md = opt_.max_detections;
-        for (int p = 0; p < P; p++)
-            if (pass_counts[p] < 0) throw ArgError("negative face count");
         DeviceGuard guard(device_);
-        // one table: run parameters | pass table | counts | faces (60-byte records, max_detections per pass)
-        const size_t o_tab = 256, o_cnt = o_tab + align256((size_t)P * sizeof(TtaEntry)), o_face = o_cnt + align256((size_t)P * sizeof(int)),
-                     total = o_face + (size_t)P * md * sizeof(rf_face);
-        align_host_.assign(total, 0);
-        *(RunParams *)align_host_.data() = RunParams{0.f, nms_threshold_, n, 0};
-        memcpy(align_host_.data() + o_tab, entries.data(), (size_t)P * sizeof(TtaEntry));
-        int *cnt = (int *)(align_host_.data() + o_cnt);
-        for (int p = 0; p < P; p++) {
-            cnt[p] = std::min(pass_counts[p], md);
-            if (pass_counts[p] > md) *truncated = true;
-            if (cnt[p]) memcpy(align_host_.data() + o_face + (size_t)p * md * sizeof(rf_face), faces + (size_t)p * md, (size_t)cnt[p] * sizeof(rf_face));
-        }
-        uint8_t *d_tab = align_tab_.reserve(total);
-        tta_open(n, rq.spec);
-        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
-        tta_dirty_ = true;
-        RF_HIP(hipMemcpyAsync(d_tab, align_host_.data(), total, hipMemcpyHostToDevice, align_stream_));
-        tta_launch_gather(align_stream_, d_tab + o_face, (int)sizeof(rf_face), (const int *)(d_tab + o_cnt), (const TtaEntry *)(d_tab + o_tab), P);
-        tta_launch_merge(align_stream_, n, rq.spec, (const RunParams *)d_tab);
-        RF_HIP(hipGetLastError());
-        RF_HIP(hipStreamSynchronize(align_stream_));
-        tta_dirty_ = false;
+        merge_passes(entries, n, faces, pass_counts, truncated, [&] { tta_open(n, rq.spec); },
+                     gather_into<TtaMap>(0, tta_cand_, tta_count_, kTtaMergeCap), vote_merge_of(n, rq.spec), tta_dirty_);
         tta_copy_out(n, rq, out, cap_per_image, counts, truncated);
     }
 
@@ -1080,16 +1091,6 @@ public:
         return t;
     }
 
-    void pyr_launch_gather(hipStream_t st, const uint8_t *faces, int face_stride, const int *counts, const PyrEntry *table, int passes,
-                           const PyrSpec &sp) {
-        PyrGatherParams gp;
-        gp.faces = faces; gp.face_stride = face_stride; gp.faces_per_pass = opt_.max_detections;
-        gp.counts = counts; gp.table = table;
-        gp.n = passes; gp.edge = sp.tile.edge; gp.rank_stride = opt_.max_detections;
-        gp.cand = (Candidate *)tta_cand_.ptr; gp.cand_count = (int *)tta_count_.ptr; gp.cap = kTtaMergeCap;
-        launch_pyr_gather(st, gp);
-    }
-
     void zoom(const void *d_src, int rows, int cols, int step, int z, int x0, int y0, int tw, int th, void *d_dst, int dst_step) override {
         if (rows < 0 || cols < 0 || tw < 0 || th < 0) throw ArgError("negative frame or window size");
         if (z != 2 && z != 4) throw ArgError("zoom: z must be 2 or 4");
@@ -1110,43 +1111,22 @@ public:
                         float threshold, rf_face *out, int cap_per_image, int *counts, bool *truncated, const PyrRequest &rq) override {
         *truncated = false;
         const TtaRequest mrq = pyr_merge_request(rq);
-        tta_check_args(n, frames, rows, cols, counts, out, cap_per_image, mrq.spec);
-        std::vector<int> st((size_t)std::max(n, 1));
-        for (int i = 0; i < n; i++) {
-            st[i] = steps ? steps[i] : cols[i] * 3;
-            check_frame(frames[i], rows[i], cols[i], st[i]);
-        }
+        pass_check_args(n, frames, rows, cols, counts, out, cap_per_image, mrq.spec.max_faces);
+        std::vector<int> st = checked_steps(frames, rows, cols, steps, n);
         std::vector<PyrEntry> entries;
         std::vector<int> first;
         size_t zoom_bytes = 0;
         pyr_build_passes(rq.spec, frames, true, rows, cols, n, &entries, &first, &zoom_bytes);
         if (n == 0) return;
         DeviceGuard guard(device_);
-        auto live = [&](int i) { return entries[first[i]].frame >= 0; };
-        // host frames are uploaded once, densely; the 1x passes are views of that copy, the zoom kernel reads it
-        std::vector<const uint8_t *> base((size_t)n, nullptr);
-        if (!on_device) {
-            size_t bytes = 0;
-            std::vector<size_t> off((size_t)n, 0);
-            for (int i = 0; i < n; i++)
-                if (live(i)) { off[i] = bytes; bytes += align256((size_t)rows[i] * cols[i] * 3); }
-            uint8_t *d = pyr_frames_.reserve(bytes);
-            for (int i = 0; i < n; i++) {
-                if (!live(i)) continue;
-                RF_HIP(hipMemcpy2D(d + off[i], (size_t)cols[i] * 3, frames[i], (size_t)st[i], (size_t)cols[i] * 3, (size_t)rows[i], hipMemcpyHostToDevice));
-                base[i] = d + off[i];
-                st[i] = cols[i] * 3;
-            }
-        } else {
-            for (int i = 0; i < n; i++) base[i] = live(i) ? frames[i] : nullptr;
-        }
-        // as in detect_tiled(): a super-batch of earlier enqueues starts now, every later launch carries passes of this call only
+        // the 1x passes are views of the frames (host frames: of their one dense copy), the zoom kernel reads the same
+        const std::vector<const uint8_t *> base =
+            pass_frame_bases(frames, rows, cols, st, n, on_device, [&](int i) { return entries[first[i]].frame >= 0; });
         launch_pending();
         // The zoom tiles: dense, each at a 256-byte-aligned offset of one growing block (what a freshly allocated dense frame looks
         // like to conv0's staging), made on the side stream; every lane that launches a pass of the call waits for them on the device.
         const int P = (int)entries.size();
-        std::vector<const uint8_t *> vp((size_t)P, nullptr);
-        std::vector<int> vr((size_t)P, 0), vc((size_t)P, 0), vs((size_t)P, 0), pass_counts((size_t)P);
+        PassViews v(P);
         uint8_t *d_zoom = zoom_bytes ? pyr_zoom_.reserve(zoom_bytes) : nullptr;
         std::vector<ZoomParams> zp;
         size_t zoff = 0;
@@ -1154,39 +1134,24 @@ public:
             const PyrEntry &e = entries[q];
             if (e.frame < 0) continue;
             const int i = e.frame;
-            vr[q] = e.th; vc[q] = e.tw;
             if (e.z == 1) {
-                vp[q] = base[i] + (size_t)e.y0 * st[i] + (size_t)3 * e.x0;
-                vs[q] = st[i];
+                v.set(q, base[i] + (size_t)e.y0 * st[i] + (size_t)3 * e.x0, e.th, e.tw, st[i]);
                 continue;
             }
             uint8_t *dst = d_zoom + zoff;
             zoff += align256((size_t)e.tw * e.th * 3);
             zp.push_back(ZoomParams{base[i], rows[i], cols[i], st[i], e.z, e.x0, e.y0, e.tw, e.th, dst, e.tw * 3});
-            vp[q] = dst; vs[q] = e.tw * 3;
+            v.set(q, dst, e.th, e.tw, e.tw * 3);
         }
+        hipEvent_t zoomed = nullptr;
         if (!zp.empty()) {
             if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
-            if (!pyr_zoom_done_) RF_HIP(hipEventCreateWithFlags(&pyr_zoom_done_, hipEventDisableTiming));
             launch_zoom_tiles(align_stream_, zp.data(), (int)zp.size());
-            RF_HIP(hipGetLastError());
-            RF_HIP(hipEventRecord(pyr_zoom_done_, align_stream_));
+            zoomed = record_inputs_ready();
         }
         tta_open(n, mrq.spec);
-        pyr_.rq = rq; pyr_.entries.swap(entries);
-        pyr_.n_frames = n; pyr_.next_pass = 0;
-        pyr_.lanes_used.clear();
-        pyr_.wait_zoom = !zp.empty();
-        pyr_.on = true;
-        tta_dirty_ = true;                       // until the call has ended well
-        struct Off { bool &on; ~Off() { on = false; } } off_guard{pyr_.on};
-        bool tr = false;
-        detect(vp.data(), vr.data(), vc.data(), vs.data(), P, true, threshold, nullptr, 0, pass_counts.data(), &tr);
-        pyr_.on = false;
-        if (pyr_.next_pass != P) throw HipError("pyramid detection: the merge was not launched");
-        // every launch of the call has been waited for; the merge ran in front of the last one's `done`
-        tta_dirty_ = false;
-        *truncated = tr;
+        *truncated = run_passes("pyramid detection", entries, v, threshold, zoomed,
+                                gather_into<PyrMap>(rq.spec.tile.edge, tta_cand_, tta_count_, kTtaMergeCap), vote_merge_of(n, mrq.spec), tta_dirty_);
         tta_copy_out(n, mrq, out, cap_per_image, counts, truncated);
     }
 
@@ -1194,39 +1159,16 @@ public:
                        rf_face *out, int cap_per_image, int *counts, bool *truncated) override {
         *truncated = false;
         const TtaRequest mrq = pyr_merge_request(rq);
-        tta_check_args(n, rows, cols, counts, faces, out, cap_per_image, mrq.spec);
+        pass_check_args(n, rows, cols, counts, faces, out, cap_per_image, mrq.spec.max_faces);
         if (n > 0 && !pass_counts) throw ArgError("null argument");
         std::vector<PyrEntry> entries;
         std::vector<int> first;
         size_t zoom_bytes = 0;
         pyr_build_passes(rq.spec, nullptr, false, rows, cols, n, &entries, &first, &zoom_bytes);
         if (n == 0) return;
-        const int P = (int)entries.size(), md = opt_.max_detections;
-        for (int p = 0; p < P; p++)
-            if (pass_counts[p] < 0) throw ArgError("negative face count");
         DeviceGuard guard(device_);
-        // one table: run parameters | pass table | counts | faces (60-byte records, max_detections per pass)
-        const size_t o_tab = 256, o_cnt = o_tab + align256((size_t)P * sizeof(PyrEntry)), o_face = o_cnt + align256((size_t)P * sizeof(int)),
-                     total = o_face + (size_t)P * md * sizeof(rf_face);
-        align_host_.assign(total, 0);
-        *(RunParams *)align_host_.data() = RunParams{0.f, nms_threshold_, n, 0};
-        memcpy(align_host_.data() + o_tab, entries.data(), (size_t)P * sizeof(PyrEntry));
-        int *cnt = (int *)(align_host_.data() + o_cnt);
-        for (int p = 0; p < P; p++) {
-            cnt[p] = std::min(pass_counts[p], md);
-            if (pass_counts[p] > md) *truncated = true;
-            if (cnt[p]) memcpy(align_host_.data() + o_face + (size_t)p * md * sizeof(rf_face), faces + (size_t)p * md, (size_t)cnt[p] * sizeof(rf_face));
-        }
-        uint8_t *d_tab = align_tab_.reserve(total);
-        tta_open(n, mrq.spec);
-        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
-        tta_dirty_ = true;
-        RF_HIP(hipMemcpyAsync(d_tab, align_host_.data(), total, hipMemcpyHostToDevice, align_stream_));
-        pyr_launch_gather(align_stream_, d_tab + o_face, (int)sizeof(rf_face), (const int *)(d_tab + o_cnt), (const PyrEntry *)(d_tab + o_tab), P, rq.spec);
-        tta_launch_merge(align_stream_, n, mrq.spec, (const RunParams *)d_tab);
-        RF_HIP(hipGetLastError());
-        RF_HIP(hipStreamSynchronize(align_stream_));
-        tta_dirty_ = false;
+        merge_passes(entries, n, faces, pass_counts, truncated, [&] { tta_open(n, mrq.spec); },
+                     gather_into<PyrMap>(rq.spec.tile.edge, tta_cand_, tta_count_, kTtaMergeCap), vote_merge_of(n, mrq.spec), tta_dirty_);
         tta_copy_out(n, mrq, out, cap_per_image, counts, truncated);
     }
 
@@ -1267,15 +1209,6 @@ public:
         return t;
     }
 
-    void rot_launch_gather(hipStream_t st, const uint8_t *faces, int face_stride, const int *counts, const RotEntry *table, int passes) {
-        RotGatherParams gp;
-        gp.faces = faces; gp.face_stride = face_stride; gp.faces_per_pass = opt_.max_detections;
-        gp.counts = counts; gp.table = table;
-        gp.n = passes; gp.rank_stride = opt_.max_detections;
-        gp.cand = (Candidate *)tta_cand_.ptr; gp.cand_count = (int *)tta_count_.ptr; gp.cap = kTtaMergeCap;
-        launch_rot_gather(st, gp);
-    }
-
     void rotate(const void *d_src, int rows, int cols, int step, int k, void *d_dst, int dst_step) override {
         if (rows < 0 || cols < 0) throw ArgError("negative frame size");
         if (k < 0 || k > 3) throw ArgError("rotate: k must be in [0, 3]");
@@ -1295,84 +1228,48 @@ public:
                     float threshold, rf_face *out, int cap_per_image, int *counts, bool *truncated, const RotRequest &rq) override {
         *truncated = false;
         const TtaRequest mrq = rot_merge_request(rq);
-        tta_check_args(n, frames, rows, cols, counts, out, cap_per_image, mrq.spec);
-        std::vector<int> st((size_t)std::max(n, 1));
-        for (int i = 0; i < n; i++) {
-            st[i] = steps ? steps[i] : cols[i] * 3;
-            check_frame(frames[i], rows[i], cols[i], st[i]);
-        }
+        pass_check_args(n, frames, rows, cols, counts, out, cap_per_image, mrq.spec.max_faces);
+        std::vector<int> st = checked_steps(frames, rows, cols, steps, n);
         std::vector<RotEntry> entries;
         rot_build_passes(rq.spec, frames, true, rows, cols, n, &entries);
         if (n == 0) return;
         DeviceGuard guard(device_);
         const int PP = rq.spec.passes();
-        auto live = [&](int i) { return entries[(size_t)i * PP].frame >= 0; };
-        // host frames are uploaded once, densely
-        std::vector<const uint8_t *> base((size_t)n, nullptr);
-        if (!on_device) {
-            size_t bytes = 0;
-            std::vector<size_t> off((size_t)n, 0);
-            for (int i = 0; i < n; i++)
-                if (live(i)) { off[i] = bytes; bytes += align256((size_t)rows[i] * cols[i] * 3); }
-            uint8_t *d = rot_frames_.reserve(bytes);
-            for (int i = 0; i < n; i++) {
-                if (!live(i)) continue;
-                RF_HIP(hipMemcpy2D(d + off[i], (size_t)cols[i] * 3, frames[i], (size_t)st[i], (size_t)cols[i] * 3, (size_t)rows[i], hipMemcpyHostToDevice));
-                base[i] = d + off[i];
-                st[i] = cols[i] * 3;
-            }
-        } else {
-            for (int i = 0; i < n; i++) base[i] = live(i) ? frames[i] : nullptr;
-        }
-        // as in detect_tiled(): a super-batch of earlier enqueues starts now, every later launch carries passes of this call only
+        const std::vector<const uint8_t *> base =
+            pass_frame_bases(frames, rows, cols, st, n, on_device, [&](int i) { return entries[(size_t)i * PP].frame >= 0; });
         launch_pending();
         // The rotated copies: dense, each at a 256-byte-aligned offset of one block (what a freshly allocated dense frame looks like to
         // conv0's staging), made on the side stream; every lane that launches a pass of the call waits for them on the device.
         const int P = (int)entries.size();
         size_t copy_bytes = 0;
         for (int i = 0; i < n; i++)
-            if (live(i)) copy_bytes += align256((size_t)rows[i] * cols[i] * 3) * (size_t)__builtin_popcount((unsigned)rq.spec.rots & 14u);
+            if (base[i]) copy_bytes += align256((size_t)rows[i] * cols[i] * 3) * (size_t)__builtin_popcount((unsigned)rq.spec.rots & 14u);
         uint8_t *d_copies = copy_bytes ? rot_copies_.reserve(copy_bytes) : nullptr;
-        std::vector<const uint8_t *> vp((size_t)P, nullptr);
-        std::vector<int> vr((size_t)P, 0), vc((size_t)P, 0), vs((size_t)P, 0), pass_counts((size_t)P);
+        PassViews v(P);
         std::vector<RotateParams> rp;
         size_t coff = 0;
         for (int q = 0; q < P; q++) {
             const RotEntry &e = entries[q];
             if (e.frame < 0) continue;
-            const int i = e.frame;
-            vr[q] = rot_rows(e.k, rows[i], cols[i]); vc[q] = rot_cols(e.k, rows[i], cols[i]);
+            const int i = e.frame, rk = rot_rows(e.k, rows[i], cols[i]), ck = rot_cols(e.k, rows[i], cols[i]);
             if (e.k == 0) {
-                vp[q] = base[i]; vs[q] = st[i];
+                v.set(q, base[i], rk, ck, st[i]);
                 continue;
             }
             uint8_t *dst = d_copies + coff;
             coff += align256((size_t)rows[i] * cols[i] * 3);
-            rp.push_back(RotateParams{base[i], rows[i], cols[i], st[i], e.k, dst, vc[q] * 3});
-            vp[q] = dst; vs[q] = vc[q] * 3;
+            rp.push_back(RotateParams{base[i], rows[i], cols[i], st[i], e.k, dst, ck * 3});
+            v.set(q, dst, rk, ck, ck * 3);
         }
+        hipEvent_t rotated = nullptr;
         if (!rp.empty()) {
             if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
-            if (!rot_copies_done_) RF_HIP(hipEventCreateWithFlags(&rot_copies_done_, hipEventDisableTiming));
             launch_rotate_frames(align_stream_, rp.data(), (int)rp.size());
-            RF_HIP(hipGetLastError());
-            RF_HIP(hipEventRecord(rot_copies_done_, align_stream_));
+            rotated = record_inputs_ready();
         }
         tta_open(n, mrq.spec);
-        rot_.rq = rq; rot_.entries.swap(entries);
-        rot_.n_frames = n; rot_.next_pass = 0;
-        rot_.lanes_used.clear();
-        rot_.wait_copies = !rp.empty();
-        rot_.on = true;
-        tta_dirty_ = true;                       // until the call has ended well
-        struct Off { bool &on; ~Off() { on = false; } } off_guard{rot_.on};
-        bool tr = false;
-        detect(vp.data(), vr.data(), vc.data(), vs.data(), P, true, threshold, nullptr, 0, pass_counts.data(), &tr);
-        rot_.on = false;
-        if (rot_.next_pass != P) throw HipError("rotation detection: the merge was not launched");
-        // every launch of the call has been waited for; the merge ran in front of the last one's `done`
-        tta_dirty_ = false;
-        *truncated = tr;
+        *truncated = run_passes("rotation detection", entries, v, threshold, rotated,
+                                gather_into<RotMap>(0, tta_cand_, tta_count_, kTtaMergeCap), vote_merge_of(n, mrq.spec), tta_dirty_);
         tta_copy_out(n, mrq, out, cap_per_image, counts, truncated);
     }
 
@@ -1380,37 +1277,14 @@ public:
                    rf_face *out, int cap_per_image, int *counts, bool *truncated) override {
         *truncated = false;
         const TtaRequest mrq = rot_merge_request(rq);
-        tta_check_args(n, rows, cols, counts, faces, out, cap_per_image, mrq.spec);
+        pass_check_args(n, rows, cols, counts, faces, out, cap_per_image, mrq.spec.max_faces);
         if (n > 0 && !pass_counts) throw ArgError("null argument");
         std::vector<RotEntry> entries;
         rot_build_passes(rq.spec, nullptr, false, rows, cols, n, &entries);
         if (n == 0) return;
-        const int P = (int)entries.size(), md = opt_.max_detections;
-        for (int p = 0; p < P; p++)
-            if (pass_counts[p] < 0) throw ArgError("negative face count");
         DeviceGuard guard(device_);
-        // one table: run parameters | pass table | counts | faces (60-byte records, max_detections per pass)
-        const size_t o_tab = 256, o_cnt = o_tab + align256((size_t)P * sizeof(RotEntry)), o_face = o_cnt + align256((size_t)P * sizeof(int)),
-                     total = o_face + (size_t)P * md * sizeof(rf_face);
-        align_host_.assign(total, 0);
-        *(RunParams *)align_host_.data() = RunParams{0.f, nms_threshold_, n, 0};
-        memcpy(align_host_.data() + o_tab, entries.data(), (size_t)P * sizeof(RotEntry));
-        int *cnt = (int *)(align_host_.data() + o_cnt);
-        for (int p = 0; p < P; p++) {
-            cnt[p] = std::min(pass_counts[p], md);
-            if (pass_counts[p] > md) *truncated = true;
-            if (cnt[p]) memcpy(align_host_.data() + o_face + (size_t)p * md * sizeof(rf_face), faces + (size_t)p * md, (size_t)cnt[p] * sizeof(rf_face));
-        }
-        uint8_t *d_tab = align_tab_.reserve(total);
-        tta_open(n, mrq.spec);
-        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
-        tta_dirty_ = true;
-        RF_HIP(hipMemcpyAsync(d_tab, align_host_.data(), total, hipMemcpyHostToDevice, align_stream_));
-        rot_launch_gather(align_stream_, d_tab + o_face, (int)sizeof(rf_face), (const int *)(d_tab + o_cnt), (const RotEntry *)(d_tab + o_tab), P);
-        tta_launch_merge(align_stream_, n, mrq.spec, (const RunParams *)d_tab);
-        RF_HIP(hipGetLastError());
-        RF_HIP(hipStreamSynchronize(align_stream_));
-        tta_dirty_ = false;
+        merge_passes(entries, n, faces, pass_counts, truncated, [&] { tta_open(n, mrq.spec); },
+                     gather_into<RotMap>(0, tta_cand_, tta_count_, kTtaMergeCap), vote_merge_of(n, mrq.spec), tta_dirty_);
         tta_copy_out(n, mrq, out, cap_per_image, counts, truncated);
     }
 
@@ -2301,14 +2175,8 @@ private:
         float *h_align_scale = nullptr;       // detect_align(): pinned, per image of the launch its frame_scale (allocated on first use)
         int *d_face_off = nullptr;            // detect_face_batch(): packed offsets of the launch's images, written by its scan kernel (first use)
         hipEvent_t face_scan_done = nullptr;  // ... recorded behind that scan: the call's next launch (another lane) waits for it on the device
-        TileEntry *h_tile_tab = nullptr;      // detect_tiled(): pinned, per image of the launch the pass it is (allocated on first use)
-        hipEvent_t tile_done = nullptr;       // ... recorded behind the launch's gather: the call's merge (another lane) waits for it on the device
-        TtaEntry *h_tta_tab = nullptr;        // detect_tta(): pinned, per image of the launch the pass it is (allocated on first use)
-        hipEvent_t tta_done = nullptr;        // ... recorded behind the launch's gather, as tile_done
-        PyrEntry *h_pyr_tab = nullptr;        // detect_pyramid(): pinned, per image of the launch the pass it is (allocated on first use)
-        hipEvent_t pyr_done = nullptr;        // ... recorded behind the launch's gather, as tile_done
-        RotEntry *h_rot_tab = nullptr;        // detect_rot(): pinned, per image of the launch the pass it is (allocated on first use)
-        hipEvent_t rot_done = nullptr;        // ... recorded behind the launch's gather, as tile_done
+        uint8_t *h_pass_tab = nullptr;        // pass calls: pinned, per image of the launch the pass it is, in the mode's entry type (allocated on first use)
+        hipEvent_t pass_done = nullptr;       // ... recorded behind the launch's gather: the call's merge (another lane) waits for it on the device
         uint8_t *h_track_tab = nullptr;       // detect_track(): pinned, the launch's stream table and image table (allocated on first use)
         hipEvent_t track_done = nullptr;      // ... recorded behind the launch's track kernel: the call's next track launch (another lane) waits for it
         int32_t *h_shot_tab = nullptr;        // detect_track_shots(): pinned, per tracked image of the launch its stream entry (allocated on first use)
@@ -2355,10 +2223,7 @@ private:
         if (l.done) (void)hipEventDestroy(l.done);
         if (l.copy2_done) (void)hipEventDestroy(l.copy2_done);
         if (l.face_scan_done) (void)hipEventDestroy(l.face_scan_done);
-        if (l.tile_done) (void)hipEventDestroy(l.tile_done);
-        if (l.tta_done) (void)hipEventDestroy(l.tta_done);
-        if (l.pyr_done) (void)hipEventDestroy(l.pyr_done);
-        if (l.rot_done) (void)hipEventDestroy(l.rot_done);
+        if (l.pass_done) (void)hipEventDestroy(l.pass_done);
         if (l.track_done) (void)hipEventDestroy(l.track_done);
         if (l.shot_done) (void)hipEventDestroy(l.shot_done);
         if (l.copy2) { (void)hipStreamSynchronize(l.copy2); (void)hipStreamDestroy(l.copy2); }
@@ -2625,9 +2490,7 @@ private:
             RF_HIP(hipStreamWaitEvent(s.stream, s.copy2_done, 0));
             s.copy2_used = false;
         }
-        if (tta_.on && tta_.wait_mirror) RF_HIP(hipStreamWaitEvent(s.stream, tta_mirror_done_, 0));      // the launch reads mirrored copies
-        if (pyr_.on && pyr_.wait_zoom) RF_HIP(hipStreamWaitEvent(s.stream, pyr_zoom_done_, 0));          // the launch reads zoom tiles
-        if (rot_.on && rot_.wait_copies) RF_HIP(hipStreamWaitEvent(s.stream, rot_copies_done_, 0));      // the launch reads rotated copies
+        if (passes_.on && passes_.inputs_ready) RF_HIP(hipStreamWaitEvent(s.stream, passes_.inputs_ready, 0));      // the launch reads mirrored / zoomed / rotated copies
         double tt = trace_.on ? HostTrace::now() : 0.0;
         RF_HIP(hipMemcpyAsync(s.d_frames, s.h_frames, s.table_bytes, hipMemcpyHostToDevice, s.stream));
         trace_.add(2, tt);
@@ -2655,10 +2518,7 @@ private:
         if (eager_timed) RF_HIP(hipEventRecord(s.time_ev[3], s.stream));
         if (align_.on) launch_lane_align(s, n);      // ordinary launches behind the graph, before `done`: nothing waits in between
         if (fb_.on) launch_lane_face_batch(s, n);
-        if (tile_.on) launch_lane_tile(s, n);
-        if (tta_.on) launch_lane_tta(s, n);
-        if (pyr_.on) launch_lane_pyr(s, n);
-        if (rot_.on) launch_lane_rot(s, n);
+        if (passes_.on) launch_lane_passes(s, n);
         if (trk_.on) launch_lane_track(s, n);
         if (shot_.on) launch_lane_shots(s);
         if (red_.on) launch_lane_redact(s, n);
@@ -2733,131 +2593,42 @@ private:
         RF_HIP(hipGetLastError());
     }
 
-    // The tiled-detection launches of a super-batch of detect_tiled(): the gather reads the launch's faces and counts from the
-    // pinned result block the NMS kernel of the same stream has just written, and what each image of the launch is from a pinned
-    // per-lane pass table.  Behind the call's LAST launch this stream waits (on the device: hipStreamWaitEvent) for the gathers of
-    // the call's other lanes, then runs the merge and, for the fused call, the face-batch launches over the merged faces.  The
-    // lane's `done` event follows, so the host's ordinary wait for the last launch covers all of it.  No host wait anywhere.
-    void launch_lane_tile(Lane &s, int n) {
-        if (!s.h_tile_tab) {
+    // The pass-call launches of a super-batch of detect_tiled() / detect_tta() / detect_pyramid() / detect_rot(): the gather reads the
+    // launch's faces and counts from the pinned result block the NMS kernel of the same stream has just written, and what each image
+    // of the launch is from a pinned per-lane pass table.  A launch that is not the call's last records the lane's pass_done behind
+    // its gather.  Behind the call's LAST launch this stream waits (on the device: hipStreamWaitEvent) for the gathers of the call's
+    // other lanes, then runs the merge (for the fused tiled call also the face-batch launches over the merged faces).  The lane's
+    // `done` event follows, so the host's ordinary wait for the last launch covers all of it.  No host wait anywhere.
+    void launch_lane_passes(Lane &s, int n) {
+        if (!s.h_pass_tab) {
             void *p = nullptr;
-            RF_HIP(hipHostMalloc(&p, std::max<size_t>((size_t)cap_images_ * sizeof(TileEntry), 256), hipHostMallocDefault));
+            RF_HIP(hipHostMalloc(&p, std::max<size_t>((size_t)cap_images_ * kPassEntryMax, 256), hipHostMallocDefault));
             s.host_allocs.push_back(p);
-            s.h_tile_tab = (TileEntry *)p;
-            RF_HIP(hipEventCreateWithFlags(&s.tile_done, hipEventDisableTiming));
+            s.h_pass_tab = (uint8_t *)p;
+            RF_HIP(hipEventCreateWithFlags(&s.pass_done, hipEventDisableTiming));
         }
-        const int total = (int)tile_.entries.size();
-        if (n > cap_images_ || tile_.next_pass + n > total) throw HipError("tiled detection: a launch carries images of another call");
-        for (int i = 0; i < n; i++) s.h_tile_tab[i] = tile_.entries[tile_.next_pass + i];
-        const TileSpec &sp = tile_.rq.spec;
-        tile_launch_gather(s.stream, (const uint8_t *)s.h_out, (int)sizeof(Candidate), s.h_counts, s.h_tile_tab, n, sp);
+        PassCall &c = passes_;
+        if (n > cap_images_ || c.next_pass + n > c.total) throw HipError(std::string(c.name) + ": a launch carries images of another call");
+        memcpy(s.h_pass_tab, c.table.data() + (size_t)c.next_pass * c.entry_bytes, (size_t)n * c.entry_bytes);
+        c.gather(s.stream, (const uint8_t *)s.h_out, (int)sizeof(Candidate), s.h_counts, s.h_pass_tab, n);
         RF_HIP(hipGetLastError());
-        tile_.next_pass += n;
+        c.next_pass += n;
         const int me = (int)(&s - lanes_.data());
-        if (tile_.next_pass < total) {
-            RF_HIP(hipEventRecord(s.tile_done, s.stream));
-            if (std::find(tile_.lanes_used.begin(), tile_.lanes_used.end(), me) == tile_.lanes_used.end()) tile_.lanes_used.push_back(me);
+        if (c.next_pass < c.total) {
+            RF_HIP(hipEventRecord(s.pass_done, s.stream));
+            if (std::find(c.lanes_used.begin(), c.lanes_used.end(), me) == c.lanes_used.end()) c.lanes_used.push_back(me);
             return;
         }
-        for (int l : tile_.lanes_used)
-            if (l != me && l < (int)lanes_.size() && lanes_[l].tile_done) RF_HIP(hipStreamWaitEvent(s.stream, lanes_[l].tile_done, 0));
-        const int nf = tile_.n_frames;
-        tile_launch_merge(s.stream, nf, sp, s.d_params);
-        if (tile_.rq.fb) launch_tiled_face_batch(s.stream, nf);
-        RF_HIP(hipGetLastError());
-    }
-
-    // The TTA launches of a super-batch of detect_tta(), as launch_lane_tile(): the gather reads the launch's faces and counts from the
-    // pinned result block and what each image of the launch is from a pinned per-lane pass table; behind the call's LAST launch this
-    // stream waits on the device for the gathers of the call's other lanes, then runs the voting merge.  No host wait anywhere.
-    void launch_lane_tta(Lane &s, int n) {
-        if (!s.h_tta_tab) {
-            void *p = nullptr;
-            RF_HIP(hipHostMalloc(&p, std::max<size_t>((size_t)cap_images_ * sizeof(TtaEntry), 256), hipHostMallocDefault));
-            s.host_allocs.push_back(p);
-            s.h_tta_tab = (TtaEntry *)p;
-            RF_HIP(hipEventCreateWithFlags(&s.tta_done, hipEventDisableTiming));
-        }
-        const int total = (int)tta_.entries.size();
-        if (n > cap_images_ || tta_.next_pass + n > total) throw HipError("test-time augmentation: a launch carries images of another call");
-        for (int i = 0; i < n; i++) s.h_tta_tab[i] = tta_.entries[tta_.next_pass + i];
-        tta_launch_gather(s.stream, (const uint8_t *)s.h_out, (int)sizeof(Candidate), s.h_counts, s.h_tta_tab, n);
-        RF_HIP(hipGetLastError());
-        tta_.next_pass += n;
-        const int me = (int)(&s - lanes_.data());
-        if (tta_.next_pass < total) {
-            RF_HIP(hipEventRecord(s.tta_done, s.stream));
-            if (std::find(tta_.lanes_used.begin(), tta_.lanes_used.end(), me) == tta_.lanes_used.end()) tta_.lanes_used.push_back(me);
-            return;
-        }
-        for (int l : tta_.lanes_used)
-            if (l != me && l < (int)lanes_.size() && lanes_[l].tta_done) RF_HIP(hipStreamWaitEvent(s.stream, lanes_[l].tta_done, 0));
-        tta_launch_merge(s.stream, tta_.n_frames, tta_.rq.spec, s.d_params);
-        RF_HIP(hipGetLastError());
-    }
-
-    // The pyramid launches of a super-batch of detect_pyramid(), as launch_lane_tta(): the gather behind each launch, and behind the
-    // call's LAST launch the wait for the gathers of the call's other lanes and the voting merge.  No host wait anywhere.
-    void launch_lane_pyr(Lane &s, int n) {
-        if (!s.h_pyr_tab) {
-            void *p = nullptr;
-            RF_HIP(hipHostMalloc(&p, std::max<size_t>((size_t)cap_images_ * sizeof(PyrEntry), 256), hipHostMallocDefault));
-            s.host_allocs.push_back(p);
-            s.h_pyr_tab = (PyrEntry *)p;
-            RF_HIP(hipEventCreateWithFlags(&s.pyr_done, hipEventDisableTiming));
-        }
-        const int total = (int)pyr_.entries.size();
-        if (n > cap_images_ || pyr_.next_pass + n > total) throw HipError("pyramid detection: a launch carries images of another call");
-        for (int i = 0; i < n; i++) s.h_pyr_tab[i] = pyr_.entries[pyr_.next_pass + i];
-        pyr_launch_gather(s.stream, (const uint8_t *)s.h_out, (int)sizeof(Candidate), s.h_counts, s.h_pyr_tab, n, pyr_.rq.spec);
-        RF_HIP(hipGetLastError());
-        pyr_.next_pass += n;
-        const int me = (int)(&s - lanes_.data());
-        if (pyr_.next_pass < total) {
-            RF_HIP(hipEventRecord(s.pyr_done, s.stream));
-            if (std::find(pyr_.lanes_used.begin(), pyr_.lanes_used.end(), me) == pyr_.lanes_used.end()) pyr_.lanes_used.push_back(me);
-            return;
-        }
-        for (int l : pyr_.lanes_used)
-            if (l != me && l < (int)lanes_.size() && lanes_[l].pyr_done) RF_HIP(hipStreamWaitEvent(s.stream, lanes_[l].pyr_done, 0));
-        tta_launch_merge(s.stream, pyr_.n_frames, pyr_merge_spec(pyr_.rq.spec), s.d_params);
-        RF_HIP(hipGetLastError());
-    }
-
-    // The rotation launches of a super-batch of detect_rot(), as launch_lane_tta(): the gather behind each launch, and behind the
-    // call's LAST launch the wait for the gathers of the call's other lanes and the voting merge.  No host wait anywhere.
-    void launch_lane_rot(Lane &s, int n) {
-        if (!s.h_rot_tab) {
-            void *p = nullptr;
-            RF_HIP(hipHostMalloc(&p, std::max<size_t>((size_t)cap_images_ * sizeof(RotEntry), 256), hipHostMallocDefault));
-            s.host_allocs.push_back(p);
-            s.h_rot_tab = (RotEntry *)p;
-            RF_HIP(hipEventCreateWithFlags(&s.rot_done, hipEventDisableTiming));
-        }
-        const int total = (int)rot_.entries.size();
-        if (n > cap_images_ || rot_.next_pass + n > total) throw HipError("rotation detection: a launch carries images of another call");
-        for (int i = 0; i < n; i++) s.h_rot_tab[i] = rot_.entries[rot_.next_pass + i];
-        rot_launch_gather(s.stream, (const uint8_t *)s.h_out, (int)sizeof(Candidate), s.h_counts, s.h_rot_tab, n);
-        RF_HIP(hipGetLastError());
-        rot_.next_pass += n;
-        const int me = (int)(&s - lanes_.data());
-        if (rot_.next_pass < total) {
-            RF_HIP(hipEventRecord(s.rot_done, s.stream));
-            if (std::find(rot_.lanes_used.begin(), rot_.lanes_used.end(), me) == rot_.lanes_used.end()) rot_.lanes_used.push_back(me);
-            return;
-        }
-        for (int l : rot_.lanes_used)
-            if (l != me && l < (int)lanes_.size() && lanes_[l].rot_done) RF_HIP(hipStreamWaitEvent(s.stream, lanes_[l].rot_done, 0));
-        tta_launch_merge(s.stream, rot_.n_frames, rot_merge_spec(rot_.rq.spec), s.d_params);
+        for (int l : c.lanes_used)
+            if (l != me && l < (int)lanes_.size() && lanes_[l].pass_done) RF_HIP(hipStreamWaitEvent(s.stream, lanes_[l].pass_done, 0));
+        c.merge(s.stream, s.d_params);
         RF_HIP(hipGetLastError());
     }
 
     // the face-batch launches of the fused tiled call: face_batch()'s launches over the merged faces and counts in device memory
     // (Candidate records, max_faces per frame, coordinate scale 1), on the stream that has just run the merge
-    void launch_tiled_face_batch(hipStream_t st, int n) {
-        const FaceBatchRequest &rq = *tile_.rq.fb;
-        if (!(tile_.d_tensor || tile_.d_mats || rq.gated)) return;
-        const int fpi = tile_.rq.spec.max_faces;
+    void launch_tiled_face_batch(hipStream_t st, int n, const FaceBatchRequest &rq, int fpi, uint8_t *d_tensor, double *d_mats) {
+        if (!(d_tensor || d_mats || rq.gated)) return;
         for (int base = 0; base < n; base += kAlignImagesPerLaunch) {
             FaceSeq q;
             q.frames = (const FrameDesc *)tile_tab_.ptr + base;      // uploaded by detect_tiled() before the call's first launch
@@ -2868,7 +2639,7 @@ private:
             q.n = std::min(kAlignImagesPerLaunch, n - base); q.image0 = base;
             q.first = base == 0;
             q.offsets = (int *)fq_offsets_.ptr + base;
-            launch_face_seq(st, rq, q, tile_.d_tensor, tile_.d_mats);
+            launch_face_seq(st, rq, q, d_tensor, d_mats);
         }
     }
 
@@ -3336,36 +3107,21 @@ private:
              int next_image = 0; } fb_;
     // gated face batches: quality records and packed indices per face slot of the call, the call's packed offsets
     DeviceScratch fq_records_, fq_packed_, fq_offsets_;
+    // pass calls: the one that is open, the device copy of its host frames, the event behind its side-stream copies
+    PassCall passes_;
+    DeviceScratch pass_frames_;
+    hipEvent_t inputs_ready_ = nullptr;
     // tiled detection: per frame the gathered candidates and their counter, the merged records and counts, the frame table of the
-    // fused face batch, the device copy of host frames; the request detect_tiled() has open and its pass table
-    DeviceScratch tile_cand_, tile_count_, tile_out_, tile_outcount_, tile_tab_, tile_frames_;
+    // fused face batch
+    DeviceScratch tile_cand_, tile_count_, tile_out_, tile_outcount_, tile_tab_;
     bool tile_dirty_ = true;                  // the counters are not known to be zero (new block, or a call that ended in an error)
     std::vector<Candidate> tile_host_;
     std::vector<FrameDesc> tile_fd_;
-    struct { bool on = false; TileRequest rq; std::vector<TileEntry> entries; int n_frames = 0, next_pass = 0; std::vector<int> lanes_used;
-             uint8_t *d_tensor = nullptr; double *d_mats = nullptr; } tile_;
-
-    // flip test-time augmentation: per frame the gathered candidates and their counter, the merged records, member counts and
-    // counts, the device copy of host frames, the mirrored copies and the event behind them; the request detect_tta() has open
-    DeviceScratch tta_cand_, tta_count_, tta_frames_, tta_mirror_;
-    hipEvent_t tta_mirror_done_ = nullptr;
+    // flip test-time augmentation: per frame the gathered candidates and their counter, the mirrored copies; the merged records, member
+    // counts and counts are tta_out_ / tta_votes_ / tta_outcount_ below.  Pyramid and rotation calls use the same blocks
+    // (pyr_merge_spec, rot_merge_spec) and bring the zoom tiles / the rotated copies.
+    DeviceScratch tta_cand_, tta_count_, tta_mirror_, pyr_zoom_, rot_copies_;
     bool tta_dirty_ = true;
-    struct { bool on = false, wait_mirror = false; TtaRequest rq; std::vector<TtaEntry> entries; int n_frames = 0, next_pass = 0;
-             std::vector<int> lanes_used; } tta_;
-
-    // zoom-pyramid detection: the device copy of host frames, the zoom tiles and the event behind them; the request
-    // detect_pyramid() has open.  Candidates, counters and merged records are the TTA call's blocks (pyr_merge_spec).
-    DeviceScratch pyr_frames_, pyr_zoom_;
-    hipEvent_t pyr_zoom_done_ = nullptr;
-    struct { bool on = false, wait_zoom = false; PyrRequest rq; std::vector<PyrEntry> entries; int n_frames = 0, next_pass = 0;
-             std::vector<int> lanes_used; } pyr_;
-
-    // rotation detection (rot.h): the device copy of host frames, the rotated copies and the event behind them; the request detect_rot()
-    // has open.  Candidates, counters and merged records are the TTA call's blocks (rot_merge_spec).
-    DeviceScratch rot_frames_, rot_copies_;
-    hipEvent_t rot_copies_done_ = nullptr;
-    struct { bool on = false, wait_copies = false; RotRequest rq; std::vector<RotEntry> entries; int n_frames = 0, next_pass = 0;
-             std::vector<int> lanes_used; } rot_;
 
     // face tracks: the trackers of this handle, the call-level result buffers and the request a tracked call has open
     struct Tracker {

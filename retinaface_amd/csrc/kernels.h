@@ -265,20 +265,42 @@ struct FaceGateScanParams {
 void launch_face_gate_scan(hipStream_t s, const FaceGateScanParams &p);
 int face_quality_ring_rows(int crop);                // luma rows the quality kernel holds in LDS (exposed for tests and DESIGN.md)
 
-// ---- K_i: tiled detection (tile.h) -- the gather behind each detection launch of a tiled call: one workgroup per pass (image of the
-//      launch) applies the edge rule and the mapping to the faces the NMS kernel kept and appends them, as Candidate records whose
-//      `anchor` is the tie-break index g = t * rank_stride + k, to the candidate array of the pass's frame (an atomic counter per
-//      frame; the append order does not matter: the merge sorts on a total order).  The merge itself is launch_nms on those arrays.
-struct TileGatherParams {
+// ---- K_i: the pass gather of tiled, TTA, pyramid and rotation detection (tile.h, tta.h, pyramid.h, rot.h) -- behind each detection
+//      launch of such a call: one workgroup per pass (image of the launch) applies the mode's mapping (and, for tiles and the pyramid,
+//      its edge rule) to the faces the NMS kernel kept and appends the survivors, as Candidate records whose `anchor` is the tie-break
+//      index g = pass_id * rank_stride + k, to the candidate array of the pass's frame (an atomic counter per frame; the append order
+//      does not matter: the merge sorts on a total order).  The merge is launch_nms (tiles) or launch_vote_merge on those arrays.
+template <class Entry> struct PassGatherParams {
     const uint8_t *faces;                 // pass p, rank k: 15 floats at faces + (p * faces_per_pass + k) * face_stride
     int face_stride, faces_per_pass;      // bytes per record (rf_face 60, Candidate 64); records per pass
     const int *counts;                    // [n] faces of each pass (clamped to faces_per_pass here)
-    const TileEntry *table;               // [n] what each pass is (frame < 0: skipped)
-    int n, edge, rank_stride;             // passes of this launch; the spec's edge; max_detections
+    const Entry *table;                   // [n] what each pass is (frame < 0: skipped)
+    int n, edge, rank_stride;             // passes of this launch; the spec's edge (TTA and rotation ignore it); max_detections
     Candidate *cand; int *cand_count;     // per frame f: cand[f * cap + pos], pos from atomicAdd(cand_count + f); the counter keeps
     int cap;                              // counting past cap (the merge reports it), records at or beyond cap are not written
 };
-void launch_tile_gather(hipStream_t s, const TileGatherParams &p);
+// What differs between the modes: keep() maps a face in place and says whether it survives, pass_id() is the entry's pass number.
+struct TileMap {
+    using Entry = TileEntry;
+    __host__ __device__ static bool keep(const Entry &e, int edge, const float *in, float *out) { return tile_map_face(e, edge, in, out); }
+    __host__ __device__ static int pass_id(const Entry &e) { return e.t; }
+};
+struct TtaMap {
+    using Entry = TtaEntry;
+    __host__ __device__ static bool keep(const Entry &e, int, const float *in, float *out) { tta_map_face(e, in, out); return true; }
+    __host__ __device__ static int pass_id(const Entry &e) { return e.pass; }
+};
+struct PyrMap {
+    using Entry = PyrEntry;
+    __host__ __device__ static bool keep(const Entry &e, int edge, const float *in, float *out) { return pyr_map_face(e, edge, in, out); }
+    __host__ __device__ static int pass_id(const Entry &e) { return e.p; }
+};
+struct RotMap {
+    using Entry = RotEntry;
+    __host__ __device__ static bool keep(const Entry &e, int, const float *in, float *out) { rot_map_face(e, in, out); return true; }
+    __host__ __device__ static int pass_id(const Entry &e) { return e.k; }
+};
+template <class Map> void launch_pass_gather(hipStream_t s, const PassGatherParams<typename Map::Entry> &p);      // the four above
 
 // ---- K_j: face tracks (track.h) -- the frame steps of a launch's images: one workgroup per stream present in the launch walks that
 //      stream's images in order, its table in LDS, one thread per slot.  Every pointer is device-visible memory (the fused calls read
@@ -392,7 +414,7 @@ void launch_overlay_draw(hipStream_t s, const OverlayParams &p);
 
 // ---- K_j: flip test-time augmentation (tta.h).
 //      mirror_rows: a dense left-right mirrored copy of a BGR frame (any source pitch and alignment), in front of a TTA call's launches.
-//      tta_gather:  tile_gather's shape with tta_map_face as the mapping: one workgroup per pass of the launch, g = pass * rank_stride + k.
+//      The gather is launch_pass_gather<TtaMap>, g = pass * rank_stride + k.
 //      vote_merge:  nms_kernel's sort and greedy walk over the gathered candidates of a frame, which also records the head that
 //                   suppressed each candidate; a second sort groups the members by head and every kept head becomes the
 //                   score-weighted mean of its members.  One workgroup per frame; re-arms the frame counters as launch_nms does.
@@ -402,17 +424,6 @@ struct MirrorParams {
 };
 constexpr int kMirrorFramesPerLaunch = 16;       // frames of one launch: their descriptors travel as kernel arguments
 void launch_mirror_rows(hipStream_t s, const MirrorParams *frames, int n);
-
-struct TtaGatherParams {
-    const uint8_t *faces;                 // pass p, rank k: 15 floats at faces + (p * faces_per_pass + k) * face_stride
-    int face_stride, faces_per_pass;
-    const int *counts;                    // [n] faces of each pass (clamped to faces_per_pass here)
-    const TtaEntry *table;                // [n] what each pass is (frame < 0: skipped)
-    int n, rank_stride;                   // passes of this launch; max_detections
-    Candidate *cand; int *cand_count;     // as TileGatherParams
-    int cap;
-};
-void launch_tta_gather(hipStream_t s, const TtaGatherParams &p);
 
 struct VoteMergeParams {
     const Candidate *cand; int *cand_count; int cap;         // cap <= 4096; the counter is reset to 0 at the end
@@ -427,7 +438,7 @@ void launch_vote_merge(hipStream_t s, const VoteMergeParams &p, bool vote);     
 // ---- K_m: rotation-robust detection (rot.h).
 //      rotate_frames: dense or pitched quarter-turn rotations (np.rot90(F, k)) of BGR frames (any source pitch and alignment), in
 //                     front of a rotation call's launches.  k = 0 / 2: mirror_rows' 12-byte path; k = 1 / 3: an LDS-tiled transpose.
-//      rot_gather:    tta_gather's shape with rot_map_face as the mapping, g = k * rank_stride + j.
+//      The gather is launch_pass_gather<RotMap>, g = k * rank_stride + j.
 //      The merge is launch_vote_merge.
 struct RotateParams {
     const uint8_t *src; int rows, cols, step;     // the SOURCE frame: row y at src + y * step
@@ -437,21 +448,10 @@ struct RotateParams {
 constexpr int kRotateFramesPerLaunch = 16;       // rotations of one launch: their descriptors travel as kernel arguments
 void launch_rotate_frames(hipStream_t s, const RotateParams *frames, int n);
 
-struct RotGatherParams {
-    const uint8_t *faces;                 // pass p, rank j: 15 floats at faces + (p * faces_per_pass + j) * face_stride
-    int face_stride, faces_per_pass;
-    const int *counts;                    // [n] faces of each pass (clamped to faces_per_pass here)
-    const RotEntry *table;                // [n] what each pass is (frame < 0: skipped)
-    int n, rank_stride;                   // passes of this launch; max_detections
-    Candidate *cand; int *cand_count;     // as TileGatherParams
-    int cap;
-};
-void launch_rot_gather(hipStream_t s, const RotGatherParams &p);
-
 // ---- K_k: zoom-pyramid detection (pyramid.h).
 //      zoom_tile:  windows of frames enlarged 2x / 4x (integer bilinear, pyr_zoom_pixel) written as dense frames, in front of a
 //                  pyramid call's launches; mirror_rows' store discipline.
-//      pyr_gather: tta_gather's shape with pyr_map_face (edge rule and mapping) as the mapping, g = p * rank_stride + k.
+//      The gather is launch_pass_gather<PyrMap> (pyr_map_face: edge rule and mapping), g = p * rank_stride + k.
 //      The merge is launch_vote_merge.
 struct ZoomParams {
     const uint8_t *src; int rows, cols, step;     // the source frame: row y at src + y * step
@@ -460,17 +460,6 @@ struct ZoomParams {
 };
 constexpr int kZoomTilesPerLaunch = 16;          // tiles of one launch: their descriptors travel as kernel arguments
 void launch_zoom_tiles(hipStream_t s, const ZoomParams *tiles, int n);
-
-struct PyrGatherParams {
-    const uint8_t *faces;                 // pass p, rank k: 15 floats at faces + (p * faces_per_pass + k) * face_stride
-    int face_stride, faces_per_pass;
-    const int *counts;                    // [n] faces of each pass (clamped to faces_per_pass here)
-    const PyrEntry *table;                // [n] what each pass is (frame < 0: skipped)
-    int n, edge, rank_stride;             // passes of this launch; the spec's edge; max_detections
-    Candidate *cand; int *cand_count;     // as TileGatherParams
-    int cap;
-};
-void launch_pyr_gather(hipStream_t s, const PyrGatherParams &p);
 
 // LDS bytes / tile geometry chosen for a layer (exposed for tests and DESIGN.md tables)
 struct TileInfo { int th, tw; size_t lds_bytes; int blocks_per_image; };

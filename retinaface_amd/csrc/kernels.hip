@@ -4479,15 +4479,17 @@ void launch_face_gate_scan(hipStream_t s, const FaceGateScanParams &p) {
 }
 
 // =============================================================================================
-// K_i: tiled detection (tile.h).  tile_gather_kernel: one workgroup per pass of the launch.  Each thread takes one face of the pass's
-//      result, applies the edge rule and the mapping (tile_map_face, the code rf_tile_map_face runs on the host) and the survivors are
-//      appended to the candidate array of the pass's frame: one atomic add per wavefront (ballot + popcount of the lanes below) on the
-//      frame's counter in device memory.  Passes of one frame arrive from different launches on different streams in any order; the
-//      merge (nms_kernel on these arrays) sorts on the total order (score, g), so the append order never shows.
+// K_i: the pass gather of tiled, TTA, pyramid and rotation detection.  pass_gather_kernel<Map>: one workgroup per pass of the launch.
+//      Each thread takes one face of the pass's result and applies the mode's edge rule and mapping, Map::keep -- tile_map_face,
+//      tta_map_face, pyr_map_face or rot_map_face, the code the rf_*_map_face entry points run on the host; TTA and rotation drop
+//      nothing -- and the survivors are appended to the candidate array of the pass's frame: one atomic add per wavefront (ballot +
+//      popcount of the lanes below) on the frame's counter in device memory.  Passes of one frame arrive from different launches on
+//      different streams in any order; the merge (nms_kernel or vote_merge_kernel on these arrays) sorts on the total order
+//      (score, g), so the append order never shows.
 // =============================================================================================
-__global__ __launch_bounds__(kThreads) void tile_gather_kernel(TileGatherParams a) {
+template <class Map> __global__ __launch_bounds__(kThreads) void pass_gather_kernel(PassGatherParams<typename Map::Entry> a) {
     const int p = blockIdx.x;
-    const TileEntry e = a.table[p];
+    const typename Map::Entry e = a.table[p];
     if (e.frame < 0) return;
     int cnt = a.counts[p];
     cnt = cnt < 0 ? 0 : cnt < a.faces_per_pass ? cnt : a.faces_per_pass;
@@ -4500,7 +4502,7 @@ __global__ __launch_bounds__(kThreads) void tile_gather_kernel(TileGatherParams 
         if (k < cnt) {
             const float *src = (const float *)(a.faces + ((size_t)p * a.faces_per_pass + k) * a.face_stride);
             for (int i = 0; i < 15; i++) f[i] = src[i];
-            keep = tile_map_face(e, a.edge, f, f);
+            keep = Map::keep(e, a.edge, f, f);
         }
         const unsigned long long mask = __ballot(keep);
         if (!mask) continue;                                     // wave-uniform
@@ -4515,15 +4517,19 @@ __global__ __launch_bounds__(kThreads) void tile_gather_kernel(TileGatherParams 
         c.score = f[0];
         c.x1 = f[1]; c.y1 = f[2]; c.x2 = f[3]; c.y2 = f[4];
         for (int i = 0; i < 5; i++) { c.px[i] = f[5 + i]; c.py[i] = f[10 + i]; }
-        c.anchor = e.t * a.rank_stride + k;
+        c.anchor = Map::pass_id(e) * a.rank_stride + k;
         dst[pos] = c;
     }
 }
 
-void launch_tile_gather(hipStream_t s, const TileGatherParams &p) {
+template <class Map> void launch_pass_gather(hipStream_t s, const PassGatherParams<typename Map::Entry> &p) {
     if (p.n <= 0) return;
-    hipLaunchKernelGGL(tile_gather_kernel, dim3(p.n), dim3(kThreads), 0, s, p);
+    hipLaunchKernelGGL(pass_gather_kernel<Map>, dim3(p.n), dim3(kThreads), 0, s, p);
 }
+template void launch_pass_gather<TileMap>(hipStream_t, const PassGatherParams<TileEntry> &);
+template void launch_pass_gather<TtaMap>(hipStream_t, const PassGatherParams<TtaEntry> &);
+template void launch_pass_gather<PyrMap>(hipStream_t, const PassGatherParams<PyrEntry> &);
+template void launch_pass_gather<RotMap>(hipStream_t, const PassGatherParams<RotEntry> &);
 
 // =============================================================================================
 // K_j: face tracks (track.h).  track_kernel: one workgroup per stream present in the launch, one thread per slot (64 threads per 64
@@ -5758,50 +5764,6 @@ void launch_mirror_rows(hipStream_t s, const MirrorParams *frames, int n) {
     }
 }
 
-// tta_gather_kernel: tile_gather_kernel's shape -- one workgroup per pass of the launch, one face per thread, one atomic add per
-//      wavefront (ballot + popcount of the lanes below) on the frame's counter -- with tta_map_face, the code rf_tta_map_face runs on
-//      the host, as the mapping.  Nothing is dropped.  The two passes of a frame may arrive from different launches on different
-//      streams; the merge sorts on the total order (score, g), so the append order never shows.
-__global__ __launch_bounds__(kThreads) void tta_gather_kernel(TtaGatherParams a) {
-    const int p = blockIdx.x;
-    const TtaEntry e = a.table[p];
-    if (e.frame < 0) return;
-    int cnt = a.counts[p];
-    cnt = cnt < 0 ? 0 : cnt < a.faces_per_pass ? cnt : a.faces_per_pass;
-    const int lane = (int)threadIdx.x & 63;
-    Candidate *dst = a.cand + (size_t)e.frame * a.cap;
-    for (int k0 = 0; k0 < cnt; k0 += kThreads) {
-        const int k = k0 + (int)threadIdx.x;
-        const bool keep = k < cnt;
-        float f[15];
-        if (keep) {
-            const float *src = (const float *)(a.faces + ((size_t)p * a.faces_per_pass + k) * a.face_stride);
-            for (int i = 0; i < 15; i++) f[i] = src[i];
-            tta_map_face(e, f, f);
-        }
-        const unsigned long long mask = __ballot(keep);
-        if (!mask) continue;                                     // wave-uniform
-        const int leader = __ffsll((long long)mask) - 1;
-        int base = 0;
-        if (lane == leader) base = atomicAdd(a.cand_count + e.frame, __popcll(mask));
-        base = __shfl(base, leader);
-        if (!keep) continue;
-        const int pos = base + __popcll(mask & ((1ull << lane) - 1ull));
-        if (pos >= a.cap) continue;                              // the counter keeps the true number: the merge reports the overflow
-        Candidate c;
-        c.score = f[0];
-        c.x1 = f[1]; c.y1 = f[2]; c.x2 = f[3]; c.y2 = f[4];
-        for (int i = 0; i < 5; i++) { c.px[i] = f[5 + i]; c.py[i] = f[10 + i]; }
-        c.anchor = e.pass * a.rank_stride + k;
-        dst[pos] = c;
-    }
-}
-
-void launch_tta_gather(hipStream_t s, const TtaGatherParams &p) {
-    if (p.n <= 0) return;
-    hipLaunchKernelGGL(tta_gather_kernel, dim3(p.n), dim3(kThreads), 0, s, p);
-}
-
 // vote_merge_kernel: one workgroup per frame.  The first half is nms_kernel, copied (so that kernel's launches cannot change): the
 //      same three sort regimes on the key (score bits descending, g ascending) and the same greedy walk with the same suppression
 //      expression; the walk additionally writes, for every candidate, the rank of the head that kept or suppressed it (s_own, in
@@ -6061,49 +6023,6 @@ void launch_zoom_tiles(hipStream_t s, const ZoomParams *tiles, int n) {
     }
 }
 
-// pyr_gather_kernel: tta_gather_kernel's shape -- one workgroup per pass of the launch, one face per thread, one atomic add per
-//      wavefront (ballot + popcount of the lanes below) on the frame's counter -- with pyr_map_face, the code rf_pyramid_map_face runs
-//      on the host, as edge rule and mapping.  A kernel of its own, so the tiled and TTA gathers cannot change.
-__global__ __launch_bounds__(kThreads) void pyr_gather_kernel(PyrGatherParams a) {
-    const int p = blockIdx.x;
-    const PyrEntry e = a.table[p];
-    if (e.frame < 0) return;
-    int cnt = a.counts[p];
-    cnt = cnt < 0 ? 0 : cnt < a.faces_per_pass ? cnt : a.faces_per_pass;
-    const int lane = (int)threadIdx.x & 63;
-    Candidate *dst = a.cand + (size_t)e.frame * a.cap;
-    for (int k0 = 0; k0 < cnt; k0 += kThreads) {
-        const int k = k0 + (int)threadIdx.x;
-        float f[15];
-        bool keep = false;
-        if (k < cnt) {
-            const float *src = (const float *)(a.faces + ((size_t)p * a.faces_per_pass + k) * a.face_stride);
-            for (int i = 0; i < 15; i++) f[i] = src[i];
-            keep = pyr_map_face(e, a.edge, f, f);
-        }
-        const unsigned long long mask = __ballot(keep);
-        if (!mask) continue;                                     // wave-uniform
-        const int leader = __ffsll((long long)mask) - 1;
-        int base = 0;
-        if (lane == leader) base = atomicAdd(a.cand_count + e.frame, __popcll(mask));
-        base = __shfl(base, leader);
-        if (!keep) continue;
-        const int pos = base + __popcll(mask & ((1ull << lane) - 1ull));
-        if (pos >= a.cap) continue;                              // the counter keeps the true number: the merge reports the overflow
-        Candidate c;
-        c.score = f[0];
-        c.x1 = f[1]; c.y1 = f[2]; c.x2 = f[3]; c.y2 = f[4];
-        for (int i = 0; i < 5; i++) { c.px[i] = f[5 + i]; c.py[i] = f[10 + i]; }
-        c.anchor = e.p * a.rank_stride + k;
-        dst[pos] = c;
-    }
-}
-
-void launch_pyr_gather(hipStream_t s, const PyrGatherParams &p) {
-    if (p.n <= 0) return;
-    hipLaunchKernelGGL(pyr_gather_kernel, dim3(p.n), dim3(kThreads), 0, s, p);
-}
-
 // =============================================================================================
 // K_m: rotation-robust detection (rot.h).
 // rotate_frames_kernel: pass k of a frame, np.rot90(F, k).  One launch carries up to sixteen frame-rotations (blockIdx.y).
@@ -6258,50 +6177,6 @@ void launch_rotate_frames(hipStream_t s, const RotateParams *frames, int n) {
         if (!blocks) continue;
         hipLaunchKernelGGL(rotate_frames_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536), (unsigned)m), dim3(kThreads), 0, s, b);
     }
-}
-
-// rot_gather_kernel: tta_gather_kernel's shape -- one workgroup per pass of the launch, one face per thread, one atomic add per
-//      wavefront on the frame's counter -- with rot_map_face, the code rf_rot_map_face runs on the host, as the mapping.  Nothing is
-//      dropped.  The passes of a frame may arrive from different launches on different streams; the merge sorts on the total order
-//      (score, g), so the append order never shows.
-__global__ __launch_bounds__(kThreads) void rot_gather_kernel(RotGatherParams a) {
-    const int p = blockIdx.x;
-    const RotEntry e = a.table[p];
-    if (e.frame < 0) return;
-    int cnt = a.counts[p];
-    cnt = cnt < 0 ? 0 : cnt < a.faces_per_pass ? cnt : a.faces_per_pass;
-    const int lane = (int)threadIdx.x & 63;
-    Candidate *dst = a.cand + (size_t)e.frame * a.cap;
-    for (int j0 = 0; j0 < cnt; j0 += kThreads) {
-        const int j = j0 + (int)threadIdx.x;
-        const bool keep = j < cnt;
-        float f[15];
-        if (keep) {
-            const float *src = (const float *)(a.faces + ((size_t)p * a.faces_per_pass + j) * a.face_stride);
-            for (int i = 0; i < 15; i++) f[i] = src[i];
-            rot_map_face(e, f, f);
-        }
-        const unsigned long long mask = __ballot(keep);
-        if (!mask) continue;                                     // wave-uniform
-        const int leader = __ffsll((long long)mask) - 1;
-        int base = 0;
-        if (lane == leader) base = atomicAdd(a.cand_count + e.frame, __popcll(mask));
-        base = __shfl(base, leader);
-        if (!keep) continue;
-        const int pos = base + __popcll(mask & ((1ull << lane) - 1ull));
-        if (pos >= a.cap) continue;                              // the counter keeps the true number: the merge reports the overflow
-        Candidate c;
-        c.score = f[0];
-        c.x1 = f[1]; c.y1 = f[2]; c.x2 = f[3]; c.y2 = f[4];
-        for (int i = 0; i < 5; i++) { c.px[i] = f[5 + i]; c.py[i] = f[10 + i]; }
-        c.anchor = e.k * a.rank_stride + j;
-        dst[pos] = c;
-    }
-}
-
-void launch_rot_gather(hipStream_t s, const RotGatherParams &p) {
-    if (p.n <= 0) return;
-    hipLaunchKernelGGL(rot_gather_kernel, dim3(p.n), dim3(kThreads), 0, s, p);
 }
 
 #ifdef RF_KERNEL_TRACE

@@ -5,7 +5,7 @@ bilinear zoom with half-pixel centres, so that faces below the smallest anchor r
 tile passes the tile edge rule against the virtual (enlarged) frame, is moved into the virtual frame with one fp32 add and into the
 source frame with one exact fp32 multiply and one fp32 subtract per coordinate; the faces of all passes are merged by the voting
 merge of flip TTA on the total order (score, g = p * max_det + k).  The kernels (retinaface_amd/csrc/kernels.hip zoom_tile_kernel,
-pyr_gather_kernel, vote_merge_kernel), retinaface_amd/csrc/pyramid.h and the host entry points rf_pyramid_plan / rf_pyramid_map_face /
+pass_gather_kernel<PyrMap>, vote_merge_kernel), retinaface_amd/csrc/pyramid.h and the host entry points rf_pyramid_plan / rf_pyramid_map_face /
 rf_pyramid_merge_host / rf_zoom_host are checked byte for byte against this file.
 """
 import numpy as np

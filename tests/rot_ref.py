@@ -4,7 +4,7 @@ A frame is detected as it is (pass 0) and turned by one, two and three quarter t
 Every face is moved into source-frame pixels with one fp32 multiply per coordinate by the frame scale of the PASS's own shape, and one
 fp32 subtract where a coordinate flips; the landmarks keep their index.  The faces of all passes are merged by the flip-TTA merge
 (tests/tta_ref.py) with g = k * max_det + j, k the rotation.  The kernels (retinaface_amd/csrc/kernels.hip rotate_frames_kernel,
-rot_gather_kernel, vote_merge_kernel), retinaface_amd/csrc/rot.h and the host entry points rf_rot_map_face / rf_rot_merge_host /
+pass_gather_kernel<RotMap>, vote_merge_kernel), retinaface_amd/csrc/rot.h and the host entry points rf_rot_map_face / rf_rot_merge_host /
 rf_rotate_host are checked byte for byte against this file.
 """
 import numpy as np

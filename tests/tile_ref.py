@@ -4,7 +4,7 @@ A frame larger than the net is cut into net-sized tiles that overlap; every tile
 shrunk as one more pass; faces that reach a tile side which is not a frame side are dropped (the neighbour tile sees them whole), the
 rest are moved into source-frame pixels with ONE fp32 operation per coordinate and merged by the detector's own greedy NMS on a total
 order.  The plan is integer arithmetic; everything else is float32, one rounding per operation, in the order written below.  The kernel
-(retinaface_amd/csrc/kernels.hip tile_gather_kernel + nms_kernel as the merge), retinaface_amd/csrc/tile.h and the host entry points
+(retinaface_amd/csrc/kernels.hip pass_gather_kernel<TileMap> + nms_kernel as the merge), retinaface_amd/csrc/tile.h and the host entry points
 rf_tile_plan / rf_tile_map_face are checked byte for byte against this file.
 """
 import numpy as np

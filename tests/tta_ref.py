@@ -4,7 +4,7 @@ A frame is detected as it is (pass 0) and mirrored left-right (pass 1).  Every f
 multiply per coordinate; a face of the mirrored pass is moved back with one fp32 subtract per x coordinate and a swap of the left /
 right landmark pairs.  The faces of both passes are merged by the detector's greedy NMS on a total order, and with voting each kept
 head becomes the score-weighted mean of the candidates it suppressed, accumulated in float64 in the total order.  The kernels
-(retinaface_amd/csrc/kernels.hip mirror_rows_kernel, tta_gather_kernel, vote_merge_kernel), retinaface_amd/csrc/tta.h and the host
+(retinaface_amd/csrc/kernels.hip mirror_rows_kernel, pass_gather_kernel<TtaMap>, vote_merge_kernel), retinaface_amd/csrc/tta.h and the host
 entry points rf_tta_map_face / rf_tta_merge_host are checked byte for byte against this file.
 """
 import numpy as np

@@ -14,7 +14,7 @@ Per set five calls are timed in alternation, each in windows of at least --min-s
   by_hand     numpy zoom of every tile and its upload, passes, then mapping and vote on the host in numpy (the arithmetic of
               tests/pyramid_ref.py; its result is checked against the pyramid call's bytes)
 and the faces each finds are counted.  --zoom-only runs 50 pyramid calls of one set and nothing else: under
-`rocprofv3 --kernel-trace --stats` that gives zoom_tile_kernel (and pyr_gather_kernel) alone; `derived` holds the bytes one call's zoom
+`rocprofv3 --kernel-trace --stats` that gives zoom_tile_kernel (and the pyramid's pass_gather_kernel) alone; `derived` holds the bytes one call's zoom
 launches must move (every tile written once, every source frame read once) for the comparison with HBM peak.
 No speed-up is promised: the file records what was measured.
 
