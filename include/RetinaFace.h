@@ -115,6 +115,13 @@ public:
     const vector<int> &frameRotations() const { return frameRot_; }
     const vector<float> &rotScores() const { return rotScore_; }
 
+    /* additive: low-light detection (rf_detect_enhanced_batch): every frame is enhanced on the device (tile-adaptive contrast boost of
+       dark tiles, rf_enhance_spec) and detected; the frames themselves are not written.  Fills lastBatchResult() with what the plain
+       batch call returns for the enhanced frames; tilesEnhanced() holds, per frame, the number of tiles the enhancement touched
+       (0: the detector saw the frame as it is).  spec may be nullptr. */
+    void detectEnhanced(const vector<cv::Mat> &imgs, float threshold = 0.5, const rf_enhance_spec *spec = nullptr);
+    const vector<int> &tilesEnhanced() const { return tilesEnhanced_; }
+
     /* additive: zoom-pyramid detection (rf_detect_pyramid_batch): every frame is detected at 1x and as net-sized tiles of the frame enlarged
        2x / 4x on the device, so that faces below the smallest anchor are found; the faces of all passes are moved back and merged as in
        detectTta().  Fills lastBatchResult() with the merged faces in SOURCE-FRAME pixels (at most spec->max_faces per frame);
@@ -200,6 +207,7 @@ private:
     vector<vector<int>> ttaVotes_, ttaPasses_;
     vector<vector<int>> pyrVotes_, pyrPasses_;
     vector<vector<int>> rotVotes_, rotSrc_;
+    vector<int> tilesEnhanced_;
     vector<int> frameRot_;
     vector<float> rotScore_;
     vector<vector<rf_track_tag>> trackTags_;

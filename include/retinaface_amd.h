@@ -1160,6 +1160,65 @@ int rf_plan_cache_probe(const char *model_dir, const char *stem, int precision, 
 
 int rf_abi_version(void);
 
+/* ---- Low-light detection: a frame that is too dark (night streams, backlit doorways, a lit and an unlit half) loses its faces.  The
+ * enhancement is contrast-limited adaptive histogram equalisation of luma (CLAHE) over a grid of tiles, applied as a hue-preserving gain;
+ * only dark tiles are touched, and no pixel is ever darkened.  Exact integer arithmetic (DESIGN.md "Low-light detection" holds the
+ * definition; tests/enhance_ref.py restates it in numpy; host and device results are byte-exact against it):
+ *   luma     Y = (77 R + 150 G + 29 B + 128) >> 8 of a BGR pixel.
+ *   tiles    ceil(rows / T) x ceil(cols / T); tile (j, i) covers rows [jT, min((j + 1)T, rows)) and columns likewise (n >= 1 pixels).
+ *   LUT      h = the tile's luma histogram, c its inclusive prefix sum, p99 = the smallest v with 100 c[v] >= 99 n.  p99 >= dark_below:
+ *            the tile is lit, its LUT is the identity.  Otherwise the tile is flagged and lim = max(1, (clip n) >> 16),
+ *            ex = sum max(h[v] - lim, 0), h[v] = min(h[v], lim) + ex / 256 + (v < ex % 256 ? 1 : 0) (one redistribution pass),
+ *            LUT[v] = max(v, (2 * 255 * c[v] + n) / (2 n)) with c the prefix sum of the new h.
+ *   pixel    per axis, with D = 2T: p = 2y + 1 - T, q = floor(p / D), a0 = clamp(q, 0, nt - 1), a1 = clamp(q + 1, 0, nt - 1),
+ *            w = p < 0 ? 0 : p mod D (tile centres are the nominal ones, also for ragged edge tiles).  With (j0, j1, wy) from y and
+ *            (i0, i1, wx) from x: v = L[j0][i0][Y](D - wy)(D - wx) + L[j0][i1][Y](D - wy)wx + L[j1][i0][Y]wy(D - wx) + L[j1][i1][Y]wy wx,
+ *            Yn = (2v + D^2) / (2 D^2).
+ *   gain     Yn == Y: the three bytes are copied (so a frame of lit tiles comes back byte-identical).  Otherwise every channel c
+ *            becomes min(255, (2 c Yn + Yd) / (2 Yd)) with Yd = max(Y, 1).
+ * Appended after rf_abi_version: the ABI version stays 2. */
+typedef struct rf_enhance_spec {
+    uint32_t struct_size;   /* sizeof(rf_enhance_spec) */
+    int32_t tile;           /* tile edge T in pixels: 16, 32, 64 or 128; 0 = 64 */
+    int32_t clip;           /* contrast limit in 1/256ths of a tile's mean bin count, 256..65535; 0 = 2048 */
+    int32_t dark_below;     /* a tile is enhanced only when its p99 luma is below this, 1..256 (256: every tile); 0 = 64 */
+} rf_enhance_spec;
+
+/* Host only, no GPU, no handle -- the same code the kernels run, compiled for the host: the enhancement of the rows x cols BGR frame src
+ * (row pitch step) written as cols * 3 bytes per row at dst + y * dst_step (bytes beyond them are untouched).  dst may be src with the
+ * same pitch.  spec may be NULL (all defaults); *tiles_enhanced (may be NULL) receives the number of flagged tiles.  A bad spec, pitch
+ * or pointer: RF_ERR_INVALID_ARG. */
+int rf_enhance_host(const rf_enhance_spec *spec, const uint8_t *src, int rows, int cols, int step, uint8_t *dst, int dst_step,
+                    int *tiles_enhanced);
+
+/* The two enhance kernels on their own, for n frames in device memory (any source pitch and pointer alignment; ROI views are legal;
+ * steps / dst_steps may be NULL for cols * 3; a NULL / 0 x 0 frame is skipped).  d_dst[i] may be d_src[i] exactly (same pointer and
+ * pitch): every LUT is finished before a pixel is written.  Any other overlap between a destination and a source or another destination of
+ * the call is refused, as are a bad spec and a call with more than 262144 tiles in total (64 MB of LUTs; the LUT scratch grows on
+ * demand) -- all with RF_ERR_INVALID_ARG before any state changes.  tiles_enhanced (n ints, may be NULL) receives the number of flagged
+ * tiles of each frame.  Synchronous.  Multi-device handles return RF_ERR_UNSUPPORTED from this call and the next two. */
+int rf_enhance_device(rf_handle h, const rf_enhance_spec *spec, const void *const *d_src, const int *rows, const int *cols,
+                      const int *steps, int n, void *const *d_dst, const int *dst_steps, int *tiles_enhanced);
+
+/* Enhancement and detection in one call, for frames resident on the engine's device (frame limits as rf_detect_batch_device).  The
+ * enhance kernels run on the engine's side stream in front of the call's first detection launch and every launch of the call waits for
+ * them on the device -- no host synchronisation in between.  The caller's frames are never written: the enhanced copies go to
+ * d_enhanced[i] (row pitch enhanced_steps[i], NULL = cols * 3; overlap rules as rf_enhance_device, and d_enhanced[i] may not be the
+ * frame itself) so that the alignment, face-batch, redaction and overlay calls can be given the pixels the detector saw; with
+ * d_enhanced NULL they go to an engine-owned block.  out and counts are, to the byte, what rf_detect_batch_device returns at this
+ * threshold for the enhanced frames as dense frames (the copies are dense in the engine's block; a caller's d_enhanced is read where it
+ * lies, so pass dense 256-byte-aligned buffers where the last bits matter).  tiles_enhanced (n ints, may be NULL) as above: 0 means the
+ * frame's copy equals the frame.  spec may be NULL. */
+int rf_detect_enhanced_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                    float threshold, const rf_enhance_spec *spec, rf_face *out, int cap_per_image, int *counts,
+                                    void *const *d_enhanced, const int *enhanced_steps, int *tiles_enhanced);
+
+/* The same with frames in HOST memory (rf_detect_batch's convention): each frame is uploaded once, densely.  d_enhanced (device
+ * memory) may be NULL; tiles_enhanced comes back either way. */
+int rf_detect_enhanced_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                             float threshold, const rf_enhance_spec *spec, rf_face *out, int cap_per_image, int *counts,
+                             void *const *d_enhanced, const int *enhanced_steps, int *tiles_enhanced);
+
 #ifdef __cplusplus
 }
 #endif

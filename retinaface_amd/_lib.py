@@ -115,6 +115,10 @@ class rf_rot_spec(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("rots", C.c_int32), ("vote", C.c_int32), ("max_faces", C.c_int32)]
 
 
+class rf_enhance_spec(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("tile", C.c_int32), ("clip", C.c_int32), ("dark_below", C.c_int32)]
+
+
 class rf_pyramid_spec(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("levels", C.c_int32), ("overlap", C.c_int32), ("edge", C.c_int32),
                 ("full_frame", C.c_int32), ("max_faces", C.c_int32), ("vote", C.c_int32)]
@@ -290,6 +294,15 @@ SYMBOLS = {
                                       _PP(C.c_int), _PP(C.c_float)]),
     "rf_rot_merge_device": (C.c_int, [C.c_void_p, _PP(C.c_int), _PP(C.c_int), C.c_int, _PP(rf_rot_spec), _PP(rf_face), _PP(C.c_int),
                                       _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), _PP(C.c_float)]),
+    "rf_enhance_host": (C.c_int, [_PP(rf_enhance_spec), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, _PP(C.c_int)]),
+    "rf_enhance_device": (C.c_int, [C.c_void_p, _PP(rf_enhance_spec), _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                    _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int)]),
+    "rf_detect_enhanced_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int, C.c_float,
+                                                  _PP(rf_enhance_spec), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_void_p), _PP(C.c_int),
+                                                  _PP(C.c_int)]),
+    "rf_detect_enhanced_batch": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int, C.c_float,
+                                           _PP(rf_enhance_spec), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_void_p), _PP(C.c_int),
+                                           _PP(C.c_int)]),
     "rf_pyramid_plan": (C.c_int, [_PP(rf_pyramid_spec), C.c_int, C.c_int, C.c_int, C.c_int, _PP(C.c_int), C.c_int]),
     "rf_pyramid_map_face": (C.c_int, [_PP(rf_pyramid_spec), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _PP(rf_face), _PP(rf_face)]),
     "rf_pyramid_merge_host": (C.c_int, [_PP(rf_pyramid_spec), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _PP(rf_face),

@@ -329,6 +329,28 @@ void RetinaFace::detectRotated(const vector<cv::Mat> &imgs, float threshold, con
     }
 }
 
+void RetinaFace::detectEnhanced(const vector<cv::Mat> &imgs, float threshold, const rf_enhance_spec *spec) {
+    const int n = (int)imgs.size();
+    lastBatch_.assign(n, vector<FaceDetectInfo>());
+    tilesEnhanced_.assign(n, 0);
+    if (n == 0) return;
+    const int cap = maxDet_;
+    vector<const uint8_t *> ptrs(n);
+    vector<int> rows(n), cols(n), steps(n), counts(n, 0);
+    for (int i = 0; i < n; i++) {
+        ptrs[i] = imgs[i].empty() ? nullptr : imgs[i].data;
+        rows[i] = imgs[i].rows; cols[i] = imgs[i].cols; steps[i] = (int)(size_t)imgs[i].step;
+    }
+    vector<rf_face> faces((size_t)n * cap);
+    check(rf_detect_enhanced_batch(h_, ptrs.data(), rows.data(), cols.data(), steps.data(), n, threshold, spec, faces.data(), cap,
+                                   counts.data(), nullptr, nullptr, tilesEnhanced_.data()), h_, "RetinaFace::detectEnhanced");
+    for (int i = 0; i < n; i++) {
+        const int k = counts[i] < cap ? counts[i] : cap;
+        lastBatch_[i].resize(k);
+        if (k) memcpy(lastBatch_[i].data(), &faces[(size_t)i * cap], (size_t)k * sizeof(rf_face));
+    }
+}
+
 void RetinaFace::detectPyramid(const vector<cv::Mat> &imgs, float threshold, const rf_pyramid_spec *spec) {
     const int n = (int)imgs.size();
     lastBatch_.assign(n, vector<FaceDetectInfo>());

@@ -1381,6 +1381,66 @@ int rf_rot_merge_device(rf_handle h, const int *rows, const int *cols, int n, co
     });
 }
 
+// ---- low-light enhancement (enhance.h)
+int rf_enhance_host(const rf_enhance_spec *spec, const uint8_t *src, int rows, int cols, int step, uint8_t *dst, int dst_step,
+                    int *tiles_enhanced) {
+    rf::EnhanceSpec sp;
+    if (rf::enhance_spec_resolve(spec, &sp) || rows < 0 || cols < 0) return RF_ERR_INVALID_ARG;
+    if (tiles_enhanced) *tiles_enhanced = 0;
+    if (rows == 0 || cols == 0) return RF_OK;
+    if (!src || !dst || rows > 4096 * 3072 / cols || step < cols * 3 || dst_step < cols * 3) return RF_ERR_INVALID_ARG;
+    if (dst != src || dst_step != step) {       // the frame itself is the one legal overlap
+        const uintptr_t s0 = (uintptr_t)src, s1 = s0 + (size_t)(rows - 1) * step + (size_t)cols * 3;
+        const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + (size_t)(rows - 1) * dst_step + (size_t)cols * 3;
+        if (s0 < d1 && d0 < s1) return RF_ERR_INVALID_ARG;
+    }
+    const int flagged = rf::enhance_host(sp, src, rows, cols, step, dst, dst_step);
+    if (tiles_enhanced) *tiles_enhanced = flagged;
+    return RF_OK;
+}
+
+int rf_enhance_device(rf_handle h, const rf_enhance_spec *spec, const void *const *d_src, const int *rows, const int *cols,
+                      const int *steps, int n, void *const *d_dst, const int *dst_steps, int *tiles_enhanced) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        rf::EnhanceSpec sp;
+        if (const char *bad = rf::enhance_spec_resolve(spec, &sp)) throw rf::ArgError(bad);
+        h->eng->enhance(sp, d_src, rows, cols, steps, n, d_dst, dst_steps, tiles_enhanced);
+        return RF_OK;
+    });
+}
+
+namespace {
+int detect_enhanced_common(rf_handle h, const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n,
+                           bool on_device, float thr, const rf_enhance_spec *spec, rf_face *out, int cap, int *counts,
+                           void *const *d_enhanced, const int *enhanced_steps, int *tiles_enhanced) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        rf::EnhanceRequest rq;
+        if (const char *bad = rf::enhance_spec_resolve(spec, &rq.spec)) throw rf::ArgError(bad);
+        rq.d_enhanced = d_enhanced; rq.enhanced_steps = enhanced_steps; rq.tiles_enhanced = tiles_enhanced;
+        bool tr = false;
+        h->eng->detect_enhanced(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, rq);
+        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+}  // namespace
+
+int rf_detect_enhanced_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                    float threshold, const rf_enhance_spec *spec, rf_face *out, int cap_per_image, int *counts,
+                                    void *const *d_enhanced, const int *enhanced_steps, int *tiles_enhanced) {
+    return detect_enhanced_common(h, (const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, spec, out, cap_per_image, counts,
+                                  d_enhanced, enhanced_steps, tiles_enhanced);
+}
+
+int rf_detect_enhanced_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                             float threshold, const rf_enhance_spec *spec, rf_face *out, int cap_per_image, int *counts,
+                             void *const *d_enhanced, const int *enhanced_steps, int *tiles_enhanced) {
+    return detect_enhanced_common(h, bgr, rows, cols, steps, n, false, threshold, spec, out, cap_per_image, counts, d_enhanced,
+                                  enhanced_steps, tiles_enhanced);
+}
+
 // ---- zoom-pyramid detection (pyramid.h)
 namespace {
 // the plan of one frame for the host-only entry points: false = refused

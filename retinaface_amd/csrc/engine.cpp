@@ -134,7 +134,8 @@ struct PassCall {
     size_t entry_bytes = 0;
     int total = 0, next_pass = 0;
     std::vector<int> lanes_used;          // lanes that carried a launch of the call other than its last
-    hipEvent_t inputs_ready = nullptr;    // recorded behind the side-stream copies the passes read; null: the call made none
+    hipEvent_t inputs_ready = nullptr;    // recorded behind the side-stream copies the call's launches read; null: the call made none.
+                                          // Every launch waits for it, pass call or not (detect_enhanced() sets it with `on` false)
     Gather gather;
     Merge merge;
 };
@@ -228,9 +229,9 @@ public:
         for (void *p : host_allocs_) (void)hipHostFree(p);
         if (align_stream_) { (void)hipStreamSynchronize(align_stream_); (void)hipStreamDestroy(align_stream_); }
         for (DeviceScratch *b : {&align_crops_, &align_mats_, &align_tab_, &fb_state_, &fq_records_, &fq_packed_, &fq_offsets_, &tile_cand_, &tile_count_, &tile_out_,
-                                 &tile_outcount_, &tile_tab_, &pass_frames_, &tta_cand_, &tta_count_, &tta_mirror_, &pyr_zoom_, &rot_copies_,
+                                 &tile_outcount_, &tile_tab_, &pass_frames_, &tta_cand_, &tta_count_, &tta_mirror_, &pyr_zoom_, &rot_copies_, &enh_luts_, &enh_frames_,
                                  &red_regions_, &red_counts_, &red_cells_, &red_frames_, &red_shadow_}) b->release();
-        for (HostScratch *b : {&trk_tags_, &trk_ended_, &trk_counts_, &tta_out_, &tta_votes_, &tta_outcount_, &shot_out_, &shot_info_}) b->release();
+        for (HostScratch *b : {&trk_tags_, &trk_ended_, &trk_counts_, &enh_counts_, &tta_out_, &tta_votes_, &tta_outcount_, &shot_out_, &shot_info_}) b->release();
         for (auto &t : trackers_) t->release();
         for (hipEvent_t e : trk_ev_) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : shot_ev_) if (e) (void)hipEventDestroy(e);
@@ -704,7 +705,7 @@ public:
         passes_.gather = std::move(gather); passes_.merge = std::move(merge);
         passes_.on = true;
         dirty = true;
-        struct Off { bool &on; ~Off() { on = false; } } off_guard{passes_.on};
+        struct Off { PassCall &c; ~Off() { c.on = false; c.inputs_ready = nullptr; } } off_guard{passes_};
         std::vector<int> pass_counts((size_t)P);
         bool tr = false;
         detect(v.ptr.data(), v.rows.data(), v.cols.data(), v.step.data(), P, true, threshold, nullptr, 0, pass_counts.data(), &tr);
@@ -1286,6 +1287,137 @@ public:
         merge_passes(entries, n, faces, pass_counts, truncated, [&] { tta_open(n, mrq.spec); },
                      gather_into<RotMap>(0, tta_cand_, tta_count_, kTtaMergeCap), vote_merge_of(n, mrq.spec), tta_dirty_);
         tta_copy_out(n, mrq, out, cap_per_image, counts, truncated);
+    }
+
+    // -------------------------------------------------------------------------------- low-light enhancement
+    // The frames of an enhancement as the kernels take them, checked: destinations and pitches, the tile limit, and overlap -- a
+    // destination may be its own source exactly (same pointer and pitch, `in_place`), and touches no other source or destination of
+    // the call.  src[i] null with rows, cols > 0 (host frames that are yet to be uploaded): not compared.  Nothing has changed when
+    // this throws.
+    std::vector<EnhanceParams> enhance_frames(const EnhanceSpec &sp, const uint8_t *const *src, const int *rows, const int *cols,
+                                              const std::vector<int> &st, int n, const std::vector<uint8_t *> &dst,
+                                              const std::vector<int> &dst_st, const std::vector<char> &live, bool in_place) const {
+        std::vector<EnhanceParams> fp((size_t)n);
+        long long tiles = 0;
+        const int lt = sp.log2_tile();
+        for (int i = 0; i < n; i++) {
+            memset(&fp[i], 0, sizeof(EnhanceParams));
+            if (!live[i]) continue;
+            if (!dst[i] || dst_st[i] < cols[i] * 3) throw ArgError("enhance: null destination or destination step < cols * 3");
+            fp[i] = EnhanceParams{src[i], rows[i], cols[i], st[i], dst[i], dst_st[i], nullptr, nullptr, nullptr};
+            tiles += (long long)enh_tiles(rows[i], lt) * enh_tiles(cols[i], lt);
+            if (tiles > kEnhanceMaxTiles) throw ArgError("enhance: more than 262144 tiles in one call");
+        }
+        auto extent = [&](const uint8_t *p, int i, int step) { return (size_t)(rows[i] - 1) * step + (size_t)cols[i] * 3 + (uintptr_t)p; };
+        auto meet = [](uintptr_t a0, uintptr_t a1, uintptr_t b0, uintptr_t b1) { return a0 < b1 && b0 < a1; };
+        for (int i = 0; i < n; i++) {
+            if (!live[i]) continue;
+            const uintptr_t d0 = (uintptr_t)dst[i], d1 = extent(dst[i], i, dst_st[i]);
+            for (int j = 0; j < n; j++) {
+                if (!live[j]) continue;
+                if (src[j] && meet(d0, d1, (uintptr_t)src[j], extent(src[j], j, st[j])) &&
+                    !(in_place && i == j && dst[i] == src[i] && dst_st[i] == st[i]))
+                    throw ArgError("enhance: a destination overlaps a source frame (only the frame itself, same pointer and pitch, is legal)");
+                if (j < i && meet(d0, d1, (uintptr_t)dst[j], extent(dst[j], j, dst_st[j]))) throw ArgError("enhance: two destinations overlap");
+            }
+        }
+        return fp;
+    }
+
+    // The two launches on the side stream: the LUT scratch (LUTs | flags | one counter per frame) grows on demand.  Returns the
+    // counters (device), complete when the side stream has run what this enqueued.
+    const int *enhance_launch(const EnhanceSpec &sp, std::vector<EnhanceParams> &fp) {
+        const int n = (int)fp.size(), lt = sp.log2_tile();
+        size_t tiles = 0;
+        for (const EnhanceParams &p : fp)
+            if (p.rows > 0) tiles += (size_t)enh_tiles(p.rows, lt) * enh_tiles(p.cols, lt);
+        const size_t o_flags = tiles * 256, o_cnt = align256(o_flags + tiles);
+        uint8_t *d = enh_luts_.reserve(o_cnt + (size_t)n * sizeof(int));
+        size_t t0 = 0;
+        for (int i = 0; i < n; i++) {
+            if (fp[i].rows <= 0) continue;
+            fp[i].luts = d + t0 * 256; fp[i].flags = d + o_flags + t0; fp[i].count = (int *)(d + o_cnt) + i;
+            t0 += (size_t)enh_tiles(fp[i].rows, lt) * enh_tiles(fp[i].cols, lt);
+        }
+        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+        RF_HIP(hipMemsetAsync(d + o_cnt, 0, (size_t)n * sizeof(int), align_stream_));
+        launch_enhance_lut(align_stream_, sp, fp.data(), n);
+        launch_enhance_apply(align_stream_, sp, fp.data(), n);
+        RF_HIP(hipGetLastError());
+        return (const int *)(d + o_cnt);
+    }
+
+    void enhance(const EnhanceSpec &sp, const void *const *d_src, const int *rows, const int *cols, const int *steps, int n,
+                 void *const *d_dst, const int *dst_steps, int *tiles_enhanced) override {
+        if (n < 0 || (n > 0 && (!d_src || !rows || !cols || !d_dst))) throw ArgError("null argument");
+        std::vector<int> st = checked_steps((const uint8_t *const *)d_src, rows, cols, steps, n), dst_st((size_t)n, 0);
+        std::vector<uint8_t *> dst((size_t)n, nullptr);
+        std::vector<char> live((size_t)n, 0);
+        bool any = false;
+        for (int i = 0; i < n; i++) {
+            if (rows[i] < 0 || cols[i] < 0) throw ArgError("negative frame size");
+            live[i] = d_src[i] && rows[i] > 0 && cols[i] > 0;
+            any = any || live[i];
+            dst[i] = (uint8_t *)d_dst[i]; dst_st[i] = dst_steps ? dst_steps[i] : cols[i] * 3;
+            if (tiles_enhanced) tiles_enhanced[i] = 0;
+        }
+        std::vector<EnhanceParams> fp = enhance_frames(sp, (const uint8_t *const *)d_src, rows, cols, st, n, dst, dst_st, live, true);
+        if (!any) return;
+        DeviceGuard guard(device_);
+        const int *d_counts = enhance_launch(sp, fp);
+        RF_HIP(hipStreamSynchronize(align_stream_));
+        if (tiles_enhanced) RF_HIP(hipMemcpy(tiles_enhanced, d_counts, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    }
+
+    // Enhancement and detection in one call: the enhanced copies are made on the side stream in front of the call's first launch, every
+    // launch waits for them on its lane stream (PassCall::inputs_ready, DESIGN.md section 24 rule 1), and detect() runs over the copies
+    // as ordinary device frames -- no host wait between the two.
+    void detect_enhanced(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,
+                         float threshold, rf_face *out, int cap_per_image, int *counts, bool *truncated, const EnhanceRequest &rq) override {
+        *truncated = false;
+        if (n < 0 || (n > 0 && (!frames || !rows || !cols || !counts))) throw ArgError("null argument");
+        if (cap_per_image < 0 || (cap_per_image > 0 && !out)) throw ArgError("out is null");
+        std::vector<int> st = checked_steps(frames, rows, cols, steps, n), dst_st((size_t)n, 0);
+        std::vector<uint8_t *> dst((size_t)n, nullptr);
+        std::vector<char> live((size_t)n, 0);
+        std::vector<const uint8_t *> cmp((size_t)n, nullptr);         // host frames are not compared with device destinations
+        size_t own_bytes = 0;
+        bool any = false;
+        for (int i = 0; i < n; i++) {
+            live[i] = frames[i] && rows[i] > 0 && cols[i] > 0;
+            any = any || live[i];
+            if (on_device) cmp[i] = frames[i];
+            if (rq.tiles_enhanced) rq.tiles_enhanced[i] = 0;
+            if (!live[i]) continue;
+            if (rq.d_enhanced) { dst[i] = (uint8_t *)rq.d_enhanced[i]; dst_st[i] = rq.enhanced_steps ? rq.enhanced_steps[i] : cols[i] * 3; }
+            else { dst[i] = (uint8_t *)(uintptr_t)(256 + own_bytes); dst_st[i] = cols[i] * 3; own_bytes += align256((size_t)rows[i] * cols[i] * 3); }
+        }
+        // an engine-owned destination is an offset (+ 256, so that it is not null) until the block exists: offsets never overlap
+        std::vector<EnhanceParams> fp = enhance_frames(rq.spec, cmp.data(), rows, cols, st, n, dst, dst_st, live, false);
+        if (!any) {
+            detect(frames, rows, cols, st.data(), n, on_device, threshold, out, cap_per_image, counts, truncated);
+            return;
+        }
+        DeviceGuard guard(device_);
+        const std::vector<const uint8_t *> base = pass_frame_bases(frames, rows, cols, st, n, on_device, [&](int i) { return live[i] != 0; });
+        launch_pending();
+        uint8_t *own = rq.d_enhanced ? nullptr : enh_frames_.reserve(own_bytes);
+        PassViews v(n);
+        for (int i = 0; i < n; i++) {
+            if (!live[i]) continue;
+            fp[i].src = base[i]; fp[i].step = st[i];
+            if (own) fp[i].dst = own + ((uintptr_t)dst[i] - 256);
+            v.set(i, fp[i].dst, rows[i], cols[i], fp[i].dst_step);
+        }
+        int *h_counts = rq.tiles_enhanced ? (int *)enh_counts_.reserve((size_t)n * sizeof(int)) : nullptr;
+        const int *d_counts = enhance_launch(rq.spec, fp);
+        passes_.inputs_ready = record_inputs_ready();
+        struct Clear { hipEvent_t &e; ~Clear() { e = nullptr; } } clear{passes_.inputs_ready};
+        // the counters travel to pinned memory behind the event, while the detection runs
+        if (h_counts) RF_HIP(hipMemcpyAsync(h_counts, d_counts, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, align_stream_));
+        detect(v.ptr.data(), v.rows.data(), v.cols.data(), v.step.data(), n, true, threshold, out, cap_per_image, counts, truncated);
+        RF_HIP(hipStreamSynchronize(align_stream_));
+        if (h_counts) memcpy(rq.tiles_enhanced, h_counts, (size_t)n * sizeof(int));
     }
 
     // -------------------------------------------------------------------------------- face tracks
@@ -2490,7 +2622,7 @@ private:
             RF_HIP(hipStreamWaitEvent(s.stream, s.copy2_done, 0));
             s.copy2_used = false;
         }
-        if (passes_.on && passes_.inputs_ready) RF_HIP(hipStreamWaitEvent(s.stream, passes_.inputs_ready, 0));      // the launch reads mirrored / zoomed / rotated copies
+        if (passes_.inputs_ready) RF_HIP(hipStreamWaitEvent(s.stream, passes_.inputs_ready, 0));      // the launch reads mirrored / zoomed / rotated / enhanced copies
         double tt = trace_.on ? HostTrace::now() : 0.0;
         RF_HIP(hipMemcpyAsync(s.d_frames, s.h_frames, s.table_bytes, hipMemcpyHostToDevice, s.stream));
         trace_.add(2, tt);
@@ -3121,6 +3253,8 @@ private:
     // counts and counts are tta_out_ / tta_votes_ / tta_outcount_ below.  Pyramid and rotation calls use the same blocks
     // (pyr_merge_spec, rot_merge_spec) and bring the zoom tiles / the rotated copies.
     DeviceScratch tta_cand_, tta_count_, tta_mirror_, pyr_zoom_, rot_copies_;
+    // low-light enhancement (enhance.h): LUTs | flags | per-frame counts of a call, and the enhanced copies of a fused call
+    DeviceScratch enh_luts_, enh_frames_;
     bool tta_dirty_ = true;
 
     // face tracks: the trackers of this handle, the call-level result buffers and the request a tracked call has open
@@ -3158,7 +3292,7 @@ private:
         }
         void release() { if (ptr) (void)hipHostFree(ptr); ptr = nullptr; cap = 0; }
     };
-    HostScratch trk_tags_, trk_ended_, trk_counts_;
+    HostScratch trk_tags_, trk_ended_, trk_counts_, enh_counts_;
     // best-shot gallery: the call-level blocks the deliver kernel writes (shots, records; indexed image * cap_ended + e), the events
     // around the shot launches of track_shots() (tools/shot_bench.py reads the time) and the request a shot call has open
     HostScratch shot_out_, shot_info_;

@@ -126,6 +126,15 @@ struct RotRequest {
     int *src_rot = nullptr;
 };
 
+// An enhanced detection call (enhance.h; rf_detect_enhanced_batch*): the validated spec, where the enhanced copies go (device memory;
+// nullptr: an engine-owned block) and where the number of flagged tiles of each frame goes
+struct EnhanceRequest {
+    EnhanceSpec spec;
+    void *const *d_enhanced = nullptr;
+    const int *enhanced_steps = nullptr;        // nullptr: cols * 3
+    int *tiles_enhanced = nullptr;              // host, n ints, or nullptr
+};
+
 // A tracked call (track.h; rf_track_update_device / rf_detect_track_*): the tracker (what tracker_create returned), the stream of every
 // image (-1 = not tracked) and where tags, ended lists and their counts go (host; each may be nullptr)
 struct TrackRequest {
@@ -248,6 +257,17 @@ public:
     // the rotate kernel on its own: a device-resident frame turned by k quarter turns counter-clockwise
     virtual void rotate(const void *, int, int, int, int, void *, int) {
         throw Unsupported("rotation detection is not available on a multi-device handle");
+    }
+    // Low-light enhancement: the two enhance kernels over frames in device memory (synchronous), and the fused call -- the enhanced
+    // copies made on the side stream in front of the call's first launch, detect() over them, no host wait in between.
+    // Single-device engines only.
+    virtual void enhance(const EnhanceSpec &, const void *const *, const int *, const int *, const int *, int, void *const *, const int *,
+                         int *) {
+        throw Unsupported("low-light enhancement is not available on a multi-device handle");
+    }
+    virtual void detect_enhanced(const uint8_t *const *, const int *, const int *, const int *, int, bool, float, rf_face *, int, int *,
+                                 bool *, const EnhanceRequest &) {
+        throw Unsupported("low-light enhancement is not available on a multi-device handle");
     }
     // Zoom-pyramid detection: every frame becomes the passes of its pyramid plan -- 1x views, and tiles of the frame enlarged 2x / 4x
     // that a zoom kernel writes on the device in front of the call's first launch -- which go through detect()'s ordinary launches; a

@@ -8,6 +8,7 @@
 #include <stdexcept>
 
 #include "align.h"
+#include "enhance.h"
 #include "face_batch.h"
 #include "face_quality.h"
 #include "overlay.h"
@@ -460,6 +461,23 @@ struct ZoomParams {
 };
 constexpr int kZoomTilesPerLaunch = 16;          // tiles of one launch: their descriptors travel as kernel arguments
 void launch_zoom_tiles(hipStream_t s, const ZoomParams *tiles, int n);
+
+// ---- K_n: low-light enhancement (enhance.h), two launches ordered on the stream, up to sixteen frames each.
+//      enhance_lut:   one workgroup per (tile, frame): the tile's luma histogram in per-wave LDS sub-histograms, p99, clip,
+//                     redistribution, prefix scan -> 256 LUT bytes and a flag byte per tile; the frame's flag count by atomic add.
+//      enhance_apply: one workgroup per block of at most 64 x 64 pixels inside one interpolation cell (the rectangle between four
+//                     neighbouring tile centres): its four LUTs staged in LDS, mirror_rows' 12-byte load / store discipline.
+//                     dst may be src exactly (same pointer and pitch).
+struct EnhanceParams {
+    const uint8_t *src; int rows, cols, step;     // the source frame: row y at src + y * step
+    uint8_t *dst; int dst_step;                   // cols * 3 bytes per row are written
+    uint8_t *luts;                                // [tiles_y * tiles_x][256], row-major tiles
+    uint8_t *flags;                               // [tiles_y * tiles_x]
+    int *count;                                   // the frame's flagged tiles; zero before enhance_lut runs
+};
+constexpr int kEnhanceFramesPerLaunch = 16;      // frames of one launch: their descriptors travel as kernel arguments
+void launch_enhance_lut(hipStream_t s, const EnhanceSpec &sp, const EnhanceParams *frames, int n);
+void launch_enhance_apply(hipStream_t s, const EnhanceSpec &sp, const EnhanceParams *frames, int n);
 
 // LDS bytes / tile geometry chosen for a layer (exposed for tests and DESIGN.md tables)
 struct TileInfo { int th, tw; size_t lds_bytes; int blocks_per_image; };

@@ -6179,6 +6179,245 @@ void launch_rotate_frames(hipStream_t s, const RotateParams *frames, int n) {
     }
 }
 
+// =============================================================================================
+// K_n: low-light enhancement (enhance.h).  Two memory-bound passes over the frames of a launch (blockIdx.y), ordered on the stream.
+// enhance_lut_kernel: one workgroup per (tile, frame).  The tile's rows are read as rotate_frames_kernel reads them: one thread takes
+//      four pixels = 12 contiguous bytes, three dwords where the pitched source happens to be dword aligned and bytewise elsewhere.
+//      The luma histogram is built with LDS atomics.  A dark tile -- the case this feature exists for -- puts nearly all of its pixels
+//      into a handful of bins, and LDS atomics on one address serialise, so (a) a thread first merges equal lumas among its own four
+//      pixels into one add, and (b) every wave owns four sub-histograms, chosen by lane & 3, at a pitch of 264 dwords: bin v of sub r
+//      lies on bank (v + 8 r) mod 32, so the four adds of one bin from one wave's lanes go to four banks.  16 sub-histograms,
+//      16,896 bytes of LDS.  Thread v then sums bin v over the sixteen (consecutive lanes, consecutive banks), and the rest is
+//      enh_tile_lut() with its three prefix sums as block scans (wave scans by shuffle, the four wave totals through LDS): p99 as the
+//      number of bins whose prefix stays below 99 % of the tile, the excess over the clip limit, the prefix of the redistributed
+//      histogram.  256 LUT bytes leave as 64 dwords, the flag as a byte, and a flagged tile adds one to its frame's counter.
+// enhance_apply_kernel: one workgroup per block of at most 64 x 64 pixels inside ONE interpolation cell -- the rectangle between four
+//      neighbouring tile centres, T x T pixels, T / 2 wide at a frame edge -- so every pixel of the block blends the same four LUTs
+//      (1 KB, staged in LDS once; border cells see one or two distinct LUTs through the clamps).  Thread v also prepares the
+//      divider of the gain for Yd = v (enh_div_magic).  A cell whose four tiles are all lit has identity LUTs: its block is a plain
+//      copy, and nothing at all when dst is src.  Pixels move as in the LUT kernel: 12 bytes per thread, sixteen threads per row
+//      of the block, dword loads and stores where aligned; a thread reads its 12 bytes before it writes them, so dst may be src.
+//      No byte outside the cols * 3 bytes of a row is read or written.
+// =============================================================================================
+constexpr int kEnhSubs = 4;                   // sub-histograms per wave
+constexpr int kEnhSubPitch = 264;             // dwords between sub-histograms: 264 mod 32 = 8
+struct EnhanceBatch { EnhanceParams f[kEnhanceFramesPerLaunch]; int log2_tile, clip, dark_below; };
+
+// inclusive prefix sum of one value per thread over the 256 threads of the workgroup; *total: the sum.  s_w: four dwords of LDS.
+__device__ __forceinline__ uint32_t enh_block_scan(uint32_t x, uint32_t *s_w, uint32_t *total) {
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t y = __shfl_up(x, d);
+        if (lane >= d) x += y;
+    }
+    __syncthreads();                          // the last scan's totals have been read
+    if (lane == 63) s_w[wave] = x;
+    __syncthreads();
+    uint32_t off = 0, tot = 0;
+    for (int w = 0; w < kThreads / 64; w++) {
+        const uint32_t t = s_w[w];
+        if (w < wave) off += t;
+        tot += t;
+    }
+    *total = tot;
+    return x + off;
+}
+
+// twelve bytes as four pixels of 24 bits (B in the low byte)
+__device__ __forceinline__ void enh_unpack(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t *p) {
+    p[0] = w0 & 0xffffffu;
+    p[1] = (w0 >> 24 | w1 << 8) & 0xffffffu;
+    p[2] = (w1 >> 16 | w2 << 16) & 0xffffffu;
+    p[3] = w2 >> 8;
+}
+
+__global__ __launch_bounds__(kThreads) void enhance_lut_kernel(EnhanceBatch batch) {
+    __shared__ uint32_t s_hist[(kThreads / 64) * kEnhSubs * kEnhSubPitch];
+    __shared__ uint32_t s_w[kThreads / 64];
+    __shared__ uint32_t s_lut[64];
+    const EnhanceParams a = batch.f[blockIdx.y];
+    if (a.rows <= 0 || a.cols <= 0) return;
+    const int lt = batch.log2_tile, T = 1 << lt;
+    const int nx = enh_tiles(a.cols, lt), ny = enh_tiles(a.rows, lt);
+    const int tile = (int)blockIdx.x, tid = (int)threadIdx.x;
+    if (tile >= nx * ny) return;                                         // uniform over the workgroup
+    const int y0 = tile / nx * T, x0 = tile % nx * T;
+    const int th = a.rows - y0 < T ? a.rows - y0 : T, tw = a.cols - x0 < T ? a.cols - x0 : T;
+    for (int i = tid; i < (kThreads / 64) * kEnhSubs * kEnhSubPitch; i += kThreads) s_hist[i] = 0;
+    __syncthreads();
+    uint32_t *mine = s_hist + ((tid >> 6) * kEnhSubs + (tid & (kEnhSubs - 1))) * kEnhSubPitch;
+    const int gshift = lt - 2;                                           // T / 4 groups of four pixels per tile row
+    for (int item = tid; item < th << gshift; item += kThreads) {
+        const int r = item >> gshift, q = (item & ((1 << gshift) - 1)) << 2;
+        if (q >= tw) continue;
+        const int n = tw - q < 4 ? tw - q : 4;
+        const uint8_t *sp = a.src + (size_t)(y0 + r) * a.step + (size_t)3 * (x0 + q);
+        uint32_t Y[4] = {256u, 256u, 256u, 256u};                        // 256: no pixel
+        if (n < 4) {
+#pragma unroll
+            for (int j = 0; j < 3; j++)                                  // fixed indices: Y stays in registers
+                if (j < n) Y[j] = enh_luma(sp[3 * j], sp[3 * j + 1], sp[3 * j + 2]);
+        } else {
+            uint32_t w0, w1, w2, p[4];
+            rot_load12(sp, w0, w1, w2);
+            enh_unpack(w0, w1, w2, p);
+#pragma unroll
+            for (int j = 0; j < 4; j++) Y[j] = enh_luma(p[j] & 0xffu, (p[j] >> 8) & 0xffu, p[j] >> 16);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++) {                                    // equal lumas of the four pixels share one add
+            if (Y[j] > 255u) continue;
+            uint32_t cnt = 1;
+#pragma unroll
+            for (int k = j + 1; k < 4; k++)
+                if (Y[k] == Y[j]) { cnt++; Y[k] = 256u; }
+            atomicAdd(mine + Y[j], cnt);
+        }
+    }
+    __syncthreads();
+    uint32_t h = 0;
+    for (int s = 0; s < (kThreads / 64) * kEnhSubs; s++) h += s_hist[s * kEnhSubPitch + tid];
+    const uint32_t n = (uint32_t)th * (uint32_t)tw, v = (uint32_t)tid;
+    uint32_t tot, p99;
+    uint32_t c = enh_block_scan(h, s_w, &tot);
+    (void)enh_block_scan(100u * c < 99u * n ? 1u : 0u, s_w, &p99);       // c ascends: the bins below the 99th percentile come first
+    const bool dark = (int)p99 < batch.dark_below;                       // uniform
+    uint32_t lut = v;
+    if (dark) {
+        const uint32_t raw = ((uint32_t)batch.clip * n) >> 16, lim = raw < 1u ? 1u : raw;
+        uint32_t ex;
+        (void)enh_block_scan(h > lim ? h - lim : 0u, s_w, &ex);
+        c = enh_block_scan((h < lim ? h : lim) + (ex >> 8) + (v < (ex & 255u) ? 1u : 0u), s_w, &tot);
+        const uint32_t e = (2u * 255u * c + n) / (2u * n);
+        lut = e > v ? e : v;
+    }
+    ((uint8_t *)s_lut)[tid] = (uint8_t)lut;
+    __syncthreads();
+    if (tid < 64) ((uint32_t *)(a.luts + (size_t)tile * 256))[tid] = s_lut[tid];
+    if (tid == 0) {
+        a.flags[tile] = dark ? 1 : 0;
+        if (dark) atomicAdd(a.count, 1);
+    }
+}
+
+// one pixel (24 bits, B in the low byte) through the blend of the cell's four LUTs and the gain
+__device__ __forceinline__ uint32_t enh_pixel(uint32_t p, const uint8_t *s_lut, const uint32_t *s_magic, int wy, int wx, int lt) {
+    const uint32_t b = p & 0xffu, g = (p >> 8) & 0xffu, r = p >> 16, Y = enh_luma(b, g, r);
+    const uint32_t yn = enh_blend(s_lut[Y], s_lut[256 + Y], s_lut[512 + Y], s_lut[768 + Y], wy, wx, lt);
+    if (yn == Y) return p;
+    const uint32_t yd = Y < 1u ? 1u : Y, m = s_magic[yd];
+    return enh_gain(b, yn, yd, m) | enh_gain(g, yn, yd, m) << 8 | enh_gain(r, yn, yd, m) << 16;
+}
+
+__global__ __launch_bounds__(kThreads) void enhance_apply_kernel(EnhanceBatch batch) {
+    __shared__ uint32_t s_lut[256];                                      // four LUTs: (j0, i0), (j0, i1), (j1, i0), (j1, i1)
+    __shared__ uint32_t s_magic[256];
+    const EnhanceParams a = batch.f[blockIdx.y];
+    if (a.rows <= 0 || a.cols <= 0) return;
+    const int lt = batch.log2_tile, T = 1 << lt, tid = (int)threadIdx.x;
+    const int lb = lt < 6 ? lt : 6, B = 1 << lb, ls = lt - lb;           // block edge, log2 of the blocks per cell and axis
+    const int nx = enh_tiles(a.cols, lt), ny = enh_tiles(a.rows, lt);
+    const int bx_total = (((a.cols - 1 + T / 2) >> lt) + 1) << ls, by_total = (((a.rows - 1 + T / 2) >> lt) + 1) << ls;
+    if ((int)blockIdx.x >= bx_total * by_total) return;                  // uniform over the workgroup
+    const int by = (int)blockIdx.x / bx_total, bx = (int)blockIdx.x % bx_total;
+    const int cy = by >> ls, cx = bx >> ls;                              // the cell: q = cy - 1, cx - 1 of enh_axis
+    int ys = cy * T - T / 2 + (by & ((1 << ls) - 1)) * B, xs = cx * T - T / 2 + (bx & ((1 << ls) - 1)) * B;
+    int y1 = ys + B < a.rows ? ys + B : a.rows, x1 = xs + B < a.cols ? xs + B : a.cols;
+    ys = ys < 0 ? 0 : ys; xs = xs < 0 ? 0 : xs;
+    if (ys >= y1 || xs >= x1) return;                                    // the half of an edge cell that lies outside the frame
+    const int j0 = cy - 1 < 0 ? 0 : cy - 1 > ny - 1 ? ny - 1 : cy - 1, j1 = cy > ny - 1 ? ny - 1 : cy;
+    const int i0 = cx - 1 < 0 ? 0 : cx - 1 > nx - 1 ? nx - 1 : cx - 1, i1 = cx > nx - 1 ? nx - 1 : cx;
+    const int t00 = j0 * nx + i0, t01 = j0 * nx + i1, t10 = j1 * nx + i0, t11 = j1 * nx + i1;
+    const bool lit = !(a.flags[t00] | a.flags[t01] | a.flags[t10] | a.flags[t11]);      // uniform: four identity LUTs
+    const bool in_place = a.dst == a.src && a.dst_step == a.step;
+    if (lit && in_place) return;
+    if (!lit) {
+        const int k = tid >> 6, t = k == 0 ? t00 : k == 1 ? t01 : k == 2 ? t10 : t11;
+        s_lut[tid] = ((const uint32_t *)(a.luts + (size_t)t * 256))[tid & 63];
+        s_magic[tid] = tid ? enh_div_magic(2u * (uint32_t)tid) : 0u;
+        __syncthreads();
+    }
+    const int bw = x1 - xs, bh = y1 - ys;
+    for (int item = tid; item < bh << 4; item += kThreads) {
+        const int r = item >> 4, q = (item & 15) << 2;
+        if (q >= bw) continue;
+        const int n = bw - q < 4 ? bw - q : 4, y = ys + r, x = xs + q;
+        const uint8_t *sp = a.src + (size_t)y * a.step + (size_t)3 * x;
+        uint8_t *dp = a.dst + (size_t)y * a.dst_step + (size_t)3 * x;
+        uint32_t p[4] = {0u, 0u, 0u, 0u};
+        if (n < 4) {
+            for (int j = 0; j < n; j++) p[j] = sp[3 * j] | (uint32_t)sp[3 * j + 1] << 8 | (uint32_t)sp[3 * j + 2] << 16;
+        } else {
+            uint32_t w0, w1, w2;
+            rot_load12(sp, w0, w1, w2);
+            enh_unpack(w0, w1, w2, p);
+        }
+        if (!lit) {
+            int u0, u1, wy;
+            enh_axis(y, lt, ny, &u0, &u1, &wy);
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                int wx;
+                enh_axis(x + j, lt, nx, &u0, &u1, &wx);
+                if (j < n) p[j] = enh_pixel(p[j], (const uint8_t *)s_lut, s_magic, wy, wx, lt);
+            }
+        }
+        if (n < 4) {
+            for (int j = 0; j < n; j++) {
+                dp[3 * j] = (uint8_t)p[j]; dp[3 * j + 1] = (uint8_t)(p[j] >> 8); dp[3 * j + 2] = (uint8_t)(p[j] >> 16);
+            }
+            continue;
+        }
+        uint32_t o0, o1, o2;
+        rot_pack(p[0], p[1], p[2], p[3], o0, o1, o2);
+        rot_store12(dp, o0, o1, o2);
+    }
+}
+
+namespace {
+// the frames of one launch and the workgroups its largest frame needs
+template <class Blocks> long long enhance_batch(const EnhanceSpec &sp, const EnhanceParams *frames, int m, EnhanceBatch *b, Blocks blocks_of) {
+    memset(b, 0, sizeof(*b));
+    b->log2_tile = sp.log2_tile(); b->clip = sp.clip; b->dark_below = sp.dark_below;
+    long long blocks = 0;
+    for (int i = 0; i < m; i++) {
+        const EnhanceParams &p = frames[i];
+        if (p.rows <= 0 || p.cols <= 0) continue;                  // rows = 0: no items
+        if (!p.src || !p.dst || !p.luts || !p.flags || !p.count || ((uintptr_t)p.luts & 3)) throw std::invalid_argument("launch_enhance: null or misaligned block");
+        b->f[i] = p;
+        blocks = std::max(blocks, blocks_of(p));
+    }
+    if (blocks > 0x7fffffLL) throw std::invalid_argument("launch_enhance: too many tiles");
+    return blocks;
+}
+}  // namespace
+
+void launch_enhance_lut(hipStream_t s, const EnhanceSpec &sp, const EnhanceParams *frames, int n) {
+    const int lt = sp.log2_tile();
+    for (int f0 = 0; f0 < n; f0 += kEnhanceFramesPerLaunch) {
+        EnhanceBatch b;
+        const int m = n - f0 < kEnhanceFramesPerLaunch ? n - f0 : kEnhanceFramesPerLaunch;
+        const long long blocks = enhance_batch(sp, frames + f0, m, &b, [&](const EnhanceParams &p) {
+            return (long long)enh_tiles(p.rows, lt) * enh_tiles(p.cols, lt);
+        });
+        if (!blocks) continue;
+        hipLaunchKernelGGL(enhance_lut_kernel, dim3((unsigned)blocks, (unsigned)m), dim3(kThreads), 0, s, b);
+    }
+}
+
+void launch_enhance_apply(hipStream_t s, const EnhanceSpec &sp, const EnhanceParams *frames, int n) {
+    const int lt = sp.log2_tile(), T = 1 << lt, ls = lt < 6 ? 0 : lt - 6;
+    for (int f0 = 0; f0 < n; f0 += kEnhanceFramesPerLaunch) {
+        EnhanceBatch b;
+        const int m = n - f0 < kEnhanceFramesPerLaunch ? n - f0 : kEnhanceFramesPerLaunch;
+        const long long blocks = enhance_batch(sp, frames + f0, m, &b, [&](const EnhanceParams &p) {
+            return (long long)((((p.rows - 1 + T / 2) >> lt) + 1) << ls) * ((((p.cols - 1 + T / 2) >> lt) + 1) << ls);
+        });
+        if (!blocks) continue;
+        hipLaunchKernelGGL(enhance_apply_kernel, dim3((unsigned)blocks, (unsigned)m), dim3(kThreads), 0, s, b);
+    }
+}
+
 #ifdef RF_KERNEL_TRACE
 extern "C" int rf_trace_select(int kernel_id, unsigned grid) {
     static unsigned long long zeros[kTraceBlocks * kTraceSlots];

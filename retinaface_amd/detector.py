@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (rf_face, rf_face_batch_spec, rf_face_gate, rf_face_quality, rf_options, rf_overlay_spec, rf_redact_spec, rf_tile_spec, rf_track,
-                   rf_motion_spec, rf_pyramid_spec, rf_rot_spec, rf_shot, rf_track_motion, rf_track_spec, rf_track_tag, rf_tta_spec)
+                   rf_enhance_spec, rf_motion_spec, rf_pyramid_spec, rf_rot_spec, rf_shot, rf_track_motion, rf_track_spec, rf_track_tag, rf_tta_spec)
 
 PRECISION_FP32, PRECISION_FP16, PRECISION_INT8 = 0, 1, 2
 
@@ -807,6 +807,38 @@ def rotate_host(frame: np.ndarray, k: int, out: Optional[np.ndarray] = None) -> 
     if st < 0:
         raise _lib.RFError(st, "rf_rotate_host: k must be in 0..3 and the destination pitch at least cols_k * 3")
     return out
+
+
+def enhance_spec(tile: int = 0, clip: int = 0, dark_below: int = 0) -> rf_enhance_spec:
+    """An rf_enhance_spec: tile (the tile edge in pixels: 16, 32, 64 or 128; 0 = 64), clip (the contrast limit in 1/256ths of a tile's
+    mean bin count, 256..65535; 0 = 2048), dark_below (a tile is enhanced only when its p99 luma is below this, 1..256; 0 = 64)."""
+    sp = rf_enhance_spec()
+    sp.struct_size = C.sizeof(rf_enhance_spec)
+    sp.tile, sp.clip, sp.dark_below = int(tile), int(clip), int(dark_below)
+    return sp
+
+
+def enhance_host(frame: np.ndarray, tile: int = 0, clip: int = 0, dark_below: int = 0, out: Optional[np.ndarray] = None, spec=None):
+    """rf_enhance_host (host only, no GPU): the low-light enhancement of a BGR frame -- contrast-limited adaptive histogram
+    equalisation of luma over tile x tile tiles, applied to the dark tiles as a hue-preserving gain.  `out`: a uint8 (rows, >= cols, 3)
+    view to write into (its row pitch is kept; it may be `frame` itself).  Returns (enhanced frame, number of tiles enhanced)."""
+    lib = _lib.load_library()
+    if frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3:
+        raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
+    if frame.strides[2] != 1 or frame.strides[1] != 3:
+        frame = np.ascontiguousarray(frame)
+    rows, cols = frame.shape[:2]
+    if out is None:
+        out = np.zeros((rows, cols, 3), np.uint8)
+    if out.dtype != np.uint8 or out.ndim != 3 or out.shape[2] != 3 or out.strides[2] != 1 or out.strides[1] != 3 or out.shape[0] < rows:
+        raise ValueError("out must be a uint8 (rows, cols, 3) array or row-pitched view")
+    sp = spec if spec is not None else enhance_spec(tile, clip, dark_below)
+    tiles = C.c_int(0)
+    st = lib.rf_enhance_host(C.byref(sp), frame.ctypes.data, rows, cols, frame.strides[0] if rows else 3 * cols, out.ctypes.data,
+                             out.strides[0] if out.shape[0] else 3 * cols, C.byref(tiles))
+    if st < 0:
+        raise _lib.RFError(st, "rf_enhance_host: bad spec, a destination pitch below cols * 3, or a destination that overlaps the frame")
+    return out, int(tiles.value)
 
 
 def pyramid_spec(levels: int = 0, overlap: int = 0, edge: int = 0, full_frame: bool = True, max_faces: int = 0,
@@ -1837,6 +1869,70 @@ class RetinaFace:
         dc = rows if int(k) & 1 else cols
         _lib.check(self._lib.rf_rotate_device(self._h, src_ptr, int(rows), int(cols), int(step if step is not None else 3 * cols), int(k),
                                               dst_ptr, int(dst_step if dst_step is not None else 3 * dc)), self._h)
+
+    # ------------------------------------------------------------------ low-light detection
+    def detect_enhanced(self, imgs: Sequence[np.ndarray], threshold: float = 0.5, tile: int = 0, clip: int = 0, dark_below: int = 0,
+                        enhanced_ptrs: Optional[Sequence[int]] = None, enhanced_steps: Optional[Sequence[int]] = None):
+        """rf_detect_enhanced_batch: every frame is uploaded, enhanced on the device (enhance_host's arithmetic: the dark tiles get a
+        contrast boost, lit tiles stay as they are) and detected, with no host wait in between.  Returns what detect() returns for the
+        enhanced frames.  enhanced_ptrs: device buffers that receive the enhanced copies (row pitch enhanced_steps, default cols * 3).
+        self.tiles_enhanced holds, per frame, the number of tiles the enhancement touched."""
+        n = len(imgs)
+        ptrs = (C.c_void_p * max(n, 1))()
+        rows, cols, steps = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
+        keep = []
+        for i, im in enumerate(imgs):
+            if im is None or im.size == 0:
+                ptrs[i], rows[i], cols[i], steps[i] = None, 0, 0, 0
+                continue
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
+            if im.strides[2] != 1 or im.strides[1] != 3:
+                im = np.ascontiguousarray(im)
+            keep.append(im)
+            ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
+        return self._run_enhanced(self._lib.rf_detect_enhanced_batch, ptrs, rows, cols, steps, n, threshold,
+                                  enhance_spec(tile, clip, dark_below), enhanced_ptrs, enhanced_steps)
+
+    def detect_enhanced_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], threshold: float = 0.5,
+                               steps: Optional[Sequence[int]] = None, tile: int = 0, clip: int = 0, dark_below: int = 0,
+                               enhanced_ptrs: Optional[Sequence[int]] = None, enhanced_steps: Optional[Sequence[int]] = None):
+        """rf_detect_enhanced_batch_device: detect_enhanced for frames resident in device memory (0 / None: an empty frame).  The
+        frames are not written."""
+        n = len(ptrs)
+        p = (C.c_void_p * max(n, 1))(*ptrs)
+        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
+        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        return self._run_enhanced(self._lib.rf_detect_enhanced_batch_device, p, r, c, s, n, threshold, enhance_spec(tile, clip, dark_below),
+                                  enhanced_ptrs, enhanced_steps)
+
+    def _run_enhanced(self, fn, ptrs, rows, cols, steps, n, threshold, sp, enhanced_ptrs, enhanced_steps):
+        cap = self.max_detections
+        out = (rf_face * max(n * cap, 1))()
+        counts, tiles = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
+        d_enh = (C.c_void_p * max(n, 1))(*enhanced_ptrs) if enhanced_ptrs is not None else None
+        e_steps = (C.c_int * max(n, 1))(*enhanced_steps) if enhanced_steps is not None else None
+        st = _lib.check(fn(self._h, ptrs, rows, cols, steps, n, float(threshold), C.byref(sp), out, cap, counts, d_enh, e_steps, tiles),
+                        self._h)
+        self.truncated = st == _lib.RF_ERR_TRUNCATED
+        self.tiles_enhanced = [int(tiles[i]) for i in range(n)]
+        return self._collect(out, counts, n, cap)
+
+    def enhance_device(self, src_ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], dst_ptrs: Sequence[int],
+                       steps: Optional[Sequence[int]] = None, dst_steps: Optional[Sequence[int]] = None, tile: int = 0, clip: int = 0,
+                       dark_below: int = 0, spec=None) -> List[int]:
+        """rf_enhance_device: the two enhance kernels on their own -- destination i (rows dst_steps[i] bytes apart, cols * 3 bytes
+        written) is the enhancement of the BGR frame at src_ptrs[i] (row pitch steps[i], any alignment).  Both in device memory; a
+        destination may be its source exactly (same pointer and pitch).  Returns the number of tiles enhanced per frame."""
+        n = len(src_ptrs)
+        sp = spec if spec is not None else enhance_spec(tile, clip, dark_below)
+        p, d = (C.c_void_p * max(n, 1))(*src_ptrs), (C.c_void_p * max(n, 1))(*dst_ptrs)
+        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
+        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        ds = (C.c_int * max(n, 1))(*(dst_steps if dst_steps is not None else [3 * x for x in cols]))
+        tiles = (C.c_int * max(n, 1))()
+        _lib.check(self._lib.rf_enhance_device(self._h, C.byref(sp), p, r, c, s, n, d, ds, tiles), self._h)
+        return [int(tiles[i]) for i in range(n)]
 
     # ------------------------------------------------------------------ zoom-pyramid detection
     def detect_pyramid(self, imgs: Sequence[np.ndarray], threshold: float = 0.5, levels: int = 0, overlap: int = 0, edge: int = 0,
