@@ -252,7 +252,10 @@ int detect_align_common(rf_handle h, const uint8_t *const *frames, const int *ro
     if (!h) return RF_ERR_INVALID_ARG;
     return guarded(h, [&]() -> int {
         bool tr = false;
-        h->eng->detect_align(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, rq);
+        rf::StageCall sc;
+        rf::StageResult res;
+        sc.align = &rq;
+        h->eng->detect_staged(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, sc, &res);
         if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
         return RF_OK;
     });
@@ -301,10 +304,13 @@ int detect_face_batch_common(rf_handle h, const uint8_t *const *frames, const in
     return guarded(h, [&]() -> int {
         rf::FaceBatchRequest rq;
         face_batch_request(spec, h->eng->default_max_faces(), d_tensor, tensor, matrices, offsets, &rq);
-        bool tr = false, over = false;
-        h->eng->detect_face_batch(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, rq, &over);
+        bool tr = false;
+        rf::StageCall sc;
+        rf::StageResult res;
+        sc.face_batch = &rq;
+        h->eng->detect_staged(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, sc, &res);
         if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
-        if (over) { h->error = kFaceOverflow; return RF_ERR_TRUNCATED; }
+        if (res.overflow) { h->error = kFaceOverflow; return RF_ERR_TRUNCATED; }
         return RF_OK;
     });
 }
@@ -399,10 +405,13 @@ int detect_face_batch_gated_common(rf_handle h, const uint8_t *const *frames, co
         rf::FaceBatchRequest rq;
         face_batch_request(spec, h->eng->default_max_faces(), d_tensor, tensor, matrices, offsets, &rq);
         face_gate_request(gate, quality, &rq);
-        bool tr = false, over = false;
-        h->eng->detect_face_batch(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, rq, &over);
+        bool tr = false;
+        rf::StageCall sc;
+        rf::StageResult res;
+        sc.face_batch = &rq;
+        h->eng->detect_staged(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, sc, &res);
         if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
-        if (over) { h->error = kFaceOverflow; return RF_ERR_TRUNCATED; }
+        if (res.overflow) { h->error = kFaceOverflow; return RF_ERR_TRUNCATED; }
         return RF_OK;
     });
 }
@@ -610,10 +619,13 @@ int detect_track_common(rf_handle h, const uint8_t *const *frames, const int *ro
         if (h->eng->num_devices() > 1) throw rf::Unsupported("face tracks are not available on a multi-device handle");
         rf::TrackRequest rq;
         track_request(h, tracker, stream_of_image, tags, ended, cap_ended, ended_counts, &rq);
-        bool tr = false, cut = false;
-        h->eng->detect_track(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, rq, &cut);
+        bool tr = false;
+        rf::StageCall sc;
+        rf::StageResult res;
+        sc.track = &rq;
+        h->eng->detect_staged(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, sc, &res);
         if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
-        if (cut) { h->error = kTrackCut; return RF_ERR_TRUNCATED; }
+        if (res.track_cut) { h->error = kTrackCut; return RF_ERR_TRUNCATED; }
         return RF_OK;
     });
 }
@@ -713,12 +725,14 @@ int rf_detect_track_face_batch_device(rf_handle h, const void *const *d_bgr, con
         if (gate || quality) face_gate_request(gate, quality, &fb);
         rf::TrackRequest rq;
         track_request(h, tracker, stream_of_image, tags, ended, cap_ended, ended_counts, &rq);
-        bool tr = false, over = false, cut = false;
-        h->eng->detect_track_face_batch((const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, out, cap_per_image, counts, &tr,
-                                        fb, &over, rq, &cut);
+        bool tr = false;
+        rf::StageCall sc;
+        rf::StageResult res;
+        sc.face_batch = &fb; sc.track = &rq;
+        h->eng->detect_staged((const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, out, cap_per_image, counts, &tr, sc, &res);
         if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
-        if (over) { h->error = kFaceOverflow; return RF_ERR_TRUNCATED; }
-        if (cut) { h->error = kTrackCut; return RF_ERR_TRUNCATED; }
+        if (res.overflow) { h->error = kFaceOverflow; return RF_ERR_TRUNCATED; }
+        if (res.track_cut) { h->error = kTrackCut; return RF_ERR_TRUNCATED; }
         return RF_OK;
     });
 }
@@ -759,10 +773,13 @@ int detect_track_shots_common(rf_handle h, const uint8_t *const *frames, const i
         track_request(h, tracker, stream_of_image, tags, ended, cap_ended, ended_counts, &rq);
         rf::ShotRequest sq;
         shot_request(gate, quality, d_shots, shots, shot_info, &sq);
-        bool tr = false, cut = false;
-        h->eng->detect_track_shots(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, rq, sq, &cut);
+        bool tr = false;
+        rf::StageCall sc;
+        rf::StageResult res;
+        sc.track = &rq; sc.shots = &sq;
+        h->eng->detect_staged(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, sc, &res);
         if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
-        if (cut) { h->error = kTrackCut; return RF_ERR_TRUNCATED; }
+        if (res.track_cut) { h->error = kTrackCut; return RF_ERR_TRUNCATED; }
         return RF_OK;
     });
 }
@@ -953,10 +970,13 @@ int detect_redact_common(rf_handle h, const uint8_t *const *frames, const int *r
     return guarded(h, [&]() -> int {
         rf::RedactRequest rq;
         redact_request(h, spec, nullptr, nullptr, pixels, nullptr, &rq);
-        bool tr = false, cut = false;
-        h->eng->detect_redact(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, rq, &cut, out_bgr, out_steps);
+        bool tr = false;
+        rf::StageCall sc;
+        rf::StageResult res;
+        sc.redact = &rq; sc.out_bgr = out_bgr; sc.out_steps = out_steps;
+        h->eng->detect_staged(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, sc, &res);
         if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
-        if (cut) { h->error = kRedactCut; return RF_ERR_TRUNCATED; }
+        if (res.redact_cut) { h->error = kRedactCut; return RF_ERR_TRUNCATED; }
         return RF_OK;
     });
 }
@@ -984,12 +1004,14 @@ int rf_detect_track_redact_batch_device(rf_handle h, void *const *d_bgr, const i
         redact_request(h, spec, tracker, stream_of_image, pixels, region_counts, &rq);
         rf::TrackRequest trq;
         track_request(h, tracker, stream_of_image, tags, ended, cap_ended, ended_counts, &trq);
-        bool tr = false, tcut = false, cut = false;
-        h->eng->detect_track_redact((const uint8_t *const *)d_bgr, rows, cols, steps, n, threshold, out, cap_per_image, counts, &tr, trq, &tcut,
-                                    rq, &cut);
+        bool tr = false;
+        rf::StageCall sc;
+        rf::StageResult res;
+        sc.track = &trq; sc.redact = &rq;
+        h->eng->detect_staged((const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, out, cap_per_image, counts, &tr, sc, &res);
         if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
-        if (tcut) { h->error = kTrackCut; return RF_ERR_TRUNCATED; }
-        if (cut) { h->error = kRedactCut; return RF_ERR_TRUNCATED; }
+        if (res.track_cut) { h->error = kTrackCut; return RF_ERR_TRUNCATED; }
+        if (res.redact_cut) { h->error = kRedactCut; return RF_ERR_TRUNCATED; }
         return RF_OK;
     });
 }
@@ -1043,10 +1065,13 @@ int detect_overlay_common(rf_handle h, const uint8_t *const *frames, const int *
     return guarded(h, [&]() -> int {
         rf::RedactRequest rq;
         overlay_request(h, spec, nullptr, nullptr, pixels, nullptr, &rq);
-        bool tr = false, cut = false;
-        h->eng->detect_redact(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, rq, &cut, out_bgr, out_steps);
+        bool tr = false;
+        rf::StageCall sc;
+        rf::StageResult res;
+        sc.redact = &rq; sc.out_bgr = out_bgr; sc.out_steps = out_steps;
+        h->eng->detect_staged(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, sc, &res);
         if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
-        if (cut) { h->error = kRedactCut; return RF_ERR_TRUNCATED; }
+        if (res.redact_cut) { h->error = kRedactCut; return RF_ERR_TRUNCATED; }
         return RF_OK;
     });
 }
@@ -1099,12 +1124,14 @@ int rf_detect_track_overlay_batch_device(rf_handle h, void *const *d_bgr, const 
         overlay_request(h, spec, tracker, stream_of_image, pixels, region_counts, &rq);
         rf::TrackRequest trq;
         track_request(h, tracker, stream_of_image, tags, ended, cap_ended, ended_counts, &trq);
-        bool tr = false, tcut = false, cut = false;
-        h->eng->detect_track_redact((const uint8_t *const *)d_bgr, rows, cols, steps, n, threshold, out, cap_per_image, counts, &tr, trq, &tcut,
-                                    rq, &cut);
+        bool tr = false;
+        rf::StageCall sc;
+        rf::StageResult res;
+        sc.track = &trq; sc.redact = &rq;
+        h->eng->detect_staged((const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, out, cap_per_image, counts, &tr, sc, &res);
         if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
-        if (tcut) { h->error = kTrackCut; return RF_ERR_TRUNCATED; }
-        if (cut) { h->error = kRedactCut; return RF_ERR_TRUNCATED; }
+        if (res.track_cut) { h->error = kTrackCut; return RF_ERR_TRUNCATED; }
+        if (res.redact_cut) { h->error = kRedactCut; return RF_ERR_TRUNCATED; }
         return RF_OK;
     });
 }

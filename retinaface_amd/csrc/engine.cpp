@@ -320,26 +320,11 @@ public:
         if (rq.max_faces < 1 || rq.max_faces > kAlignMaxFaces) throw ArgError("max_faces must be in [1, 4096]");
     }
 
-    void detect_align(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,
-                      float threshold, rf_face *out, int cap_per_image, int *counts, bool *truncated, const AlignRequest &rq) override {
-        check_align_request(rq);
-        if (n < 0 || (n > 0 && (!frames || !rows || !cols || !counts))) throw ArgError("null argument");
-        if ((long)n * rq.max_faces > (1L << 24)) throw ArgError("n x max_faces: more than 2^24 crop slots in one call");
-        DeviceGuard guard(device_);
-        // a super-batch of earlier enqueues that is still being assembled starts now: from here on every launch carries images of
-        // this call only, in call order, so image i of a launch is slot image align_.next_image + i
-        launch_pending();
-        align_.rq = rq;
-        align_.d_crops = rq.d_crops;
-        if (!rq.d_crops && rq.crops) align_.d_crops = align_crops_.reserve((size_t)n * rq.max_faces * rq.crop * rq.crop * 3);
-        align_.d_mats = rq.matrices ? (double *)align_mats_.reserve((size_t)n * rq.max_faces * 6 * sizeof(double)) : nullptr;
-        align_.next_image = 0;
-        align_.on = align_.d_crops || align_.d_mats;
-        struct Off { bool &on; ~Off() { on = false; } } off{align_.on};
-        detect(frames, rows, cols, steps, n, on_device, threshold, out, cap_per_image, counts, truncated);
-        align_.on = false;
-        // every launch of the call has been waited for (its `done` event follows the alignment launch)
-        align_copy_out(rq, align_.d_crops, align_.d_mats, n, counts, opt_.max_detections);
+    // device blocks of an alignment call over n images: the caller's crops or scratch for the host copy, scratch for the matrices
+    void align_open(const AlignRequest &rq, int n, uint8_t **d_crops, double **d_mats) {
+        *d_crops = rq.d_crops;
+        if (!rq.d_crops && rq.crops) *d_crops = align_crops_.reserve((size_t)n * rq.max_faces * rq.crop * rq.crop * 3);
+        *d_mats = rq.matrices ? (double *)align_mats_.reserve((size_t)n * rq.max_faces * 6 * sizeof(double)) : nullptr;
     }
 
     void align(const void *const *frames, const int *rows, const int *cols, const int *steps, int n, const rf_face *faces,
@@ -352,36 +337,27 @@ public:
         DeviceGuard guard(device_);
         const int fpi = std::min(cap_per_image, rq.max_faces);          // records per image that travel to the device
         // one table: frames | counts | scales | faces (60-byte records)
-        const size_t o_cnt = align256((size_t)n * sizeof(FrameDesc)), o_sc = o_cnt + align256((size_t)n * sizeof(int)),
-                     o_face = o_sc + align256((size_t)n * sizeof(float)), total = o_face + (size_t)n * fpi * sizeof(rf_face);
-        align_host_.assign(total, 0);
-        FrameDesc *fd = (FrameDesc *)align_host_.data();
-        int *cnt = (int *)(align_host_.data() + o_cnt);
-        float *sc = (float *)(align_host_.data() + o_sc);
+        HostTable tb;
+        const size_t o_fd = tb.add((size_t)n * sizeof(FrameDesc)), o_cnt = tb.add((size_t)n * sizeof(int)), o_sc = tb.add((size_t)n * sizeof(float)),
+                     o_face = tb.add((size_t)n * fpi * sizeof(rf_face));
+        uint8_t *tab = table_open(tb);
+        int *cnt = (int *)(tab + o_cnt);
+        float *sc = (float *)(tab + o_sc);
+        const std::vector<char> empty = table_frames((FrameDesc *)(tab + o_fd), frames, rows, cols, steps, n, "align");
         for (int i = 0; i < n; i++) {
-            const int st = steps ? steps[i] : cols[i] * 3;
-            const uint8_t *p = (const uint8_t *)frames[i];
-            check_frame(p, rows[i], cols[i], st);
-            const bool empty = !p || rows[i] <= 0 || cols[i] <= 0;
-            if (!empty && check_residency_) {
-                const int where = foreign_device_of(p);
-                if (where >= 0 && where != device_) throw ArgError("align: frame is resident on another device");
-            }
-            fd[i] = empty ? FrameDesc{nullptr, 0, 0, 0, 0} : FrameDesc{p, rows[i], cols[i], st, 0};
-            cnt[i] = empty ? 0 : std::max(0, std::min(counts[i], fpi));
+            cnt[i] = empty[i] ? 0 : std::max(0, std::min(counts[i], fpi));
             sc[i] = coord_scale ? coord_scale[i] : 1.f;
-            if (cnt[i]) memcpy(align_host_.data() + o_face + (size_t)i * fpi * sizeof(rf_face), faces + (size_t)i * cap_per_image, (size_t)cnt[i] * sizeof(rf_face));
         }
-        uint8_t *d_tab = align_tab_.reserve(total);
-        uint8_t *d_crops = rq.d_crops;
-        if (!d_crops && rq.crops) d_crops = align_crops_.reserve((size_t)n * rq.max_faces * rq.crop * rq.crop * 3);
-        double *d_mats = rq.matrices ? (double *)align_mats_.reserve((size_t)n * rq.max_faces * 6 * sizeof(double)) : nullptr;
+        table_records(tab + o_face, fpi, faces, cap_per_image, sizeof(rf_face), cnt, fpi, n);
+        uint8_t *d_tab = align_tab_.reserve(tb.end);
+        uint8_t *d_crops = nullptr;
+        double *d_mats = nullptr;
+        align_open(rq, n, &d_crops, &d_mats);
         if (!d_crops && !d_mats) return;
-        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
-        RF_HIP(hipMemcpyAsync(d_tab, align_host_.data(), total, hipMemcpyHostToDevice, align_stream_));
+        table_upload(d_tab, tb);
         for (int base = 0; base < n; base += kAlignImagesPerLaunch) {
             AlignParams ap;
-            ap.frames = (const FrameDesc *)d_tab + base;
+            ap.frames = (const FrameDesc *)(d_tab + o_fd) + base;
             ap.faces = d_tab + o_face + (size_t)base * fpi * sizeof(rf_face);
             ap.face_stride = (int)sizeof(rf_face); ap.faces_per_image = fpi;
             ap.counts = (const int *)(d_tab + o_cnt) + base;
@@ -466,32 +442,6 @@ public:
         if (rq.matrices && d_mats) RF_HIP(hipMemcpy(rq.matrices, d_mats, written * 6 * sizeof(double), hipMemcpyDeviceToHost));
     }
 
-    void detect_face_batch(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,
-                           float threshold, rf_face *out, int cap_per_image, int *counts, bool *truncated, const FaceBatchRequest &rq,
-                           bool *overflow) override {
-        check_face_batch_request(rq);
-        if (n < 0 || (n > 0 && (!frames || !rows || !cols || !counts))) throw ArgError("null argument");
-        if ((long)n * rq.spec.max_faces > (1L << 24)) throw ArgError("n x max_faces: more than 2^24 faces in one call");
-        DeviceGuard guard(device_);
-        // as in detect_align(): a super-batch of earlier enqueues starts now, every later launch carries images of this call only
-        launch_pending();
-        uint8_t *d_tensor = nullptr;
-        double *d_mats = nullptr;
-        face_batch_open(rq, &d_tensor, &d_mats);
-        if (rq.gated) face_gate_open(rq, n);
-        fb_.rq = rq;
-        fb_.d_tensor = d_tensor; fb_.d_mats = d_mats;
-        fb_.first = true; fb_.prev_scan = nullptr; fb_.next_image = 0;
-        fb_.on = true;
-        struct Off { bool &on; ~Off() { on = false; } } off{fb_.on};
-        detect(frames, rows, cols, steps, n, on_device, threshold, out, cap_per_image, counts, truncated);
-        fb_.on = false;
-        // every launch of the call has been waited for (its `done` event follows the tensor launch); an empty frame has count 0
-        // (under a gate: the images of an empty frame hold no considered face either)
-        if (rq.gated) face_gated_copy_out(rq, d_tensor, d_mats, counts, n, std::min(rq.spec.max_faces, opt_.max_detections), overflow);
-        else face_batch_copy_out(rq, d_tensor, d_mats, counts, n, std::min(rq.spec.max_faces, opt_.max_detections), overflow);
-    }
-
     // The face-batch launches over n images of ONE table of faces, in stream order: (gated: the quality kernel,) the scan that packs
     // the counts and advances the call's running base, the tensor kernel.  Shared by the standalone call, the launches behind a
     // detection launch and the fused tiled call: they differ only in where frames, faces, counts and scales live.
@@ -570,37 +520,27 @@ public:
         const int fpi = std::min(cap_per_image, rq.spec.max_faces);     // records per image that travel to the device
         // one table: frames | counts | scales | offsets (written by the scan) | faces (60-byte records)
         const int per = std::min(n, kAlignImagesPerLaunch);
-        const size_t o_cnt = align256((size_t)n * sizeof(FrameDesc)), o_sc = o_cnt + align256((size_t)n * sizeof(int)),
-                     o_off = o_sc + align256((size_t)n * sizeof(float)), o_face = o_off + align256(((size_t)per + 1) * sizeof(int)),
-                     total = o_face + (size_t)n * fpi * sizeof(rf_face);
-        align_host_.assign(total, 0);
-        FrameDesc *fd = (FrameDesc *)align_host_.data();
-        int *cnt = (int *)(align_host_.data() + o_cnt);
-        float *sc = (float *)(align_host_.data() + o_sc);
+        HostTable tb;
+        const size_t o_fd = tb.add((size_t)n * sizeof(FrameDesc)), o_cnt = tb.add((size_t)n * sizeof(int)), o_sc = tb.add((size_t)n * sizeof(float)),
+                     o_off = tb.add(((size_t)per + 1) * sizeof(int)), o_face = tb.add((size_t)n * fpi * sizeof(rf_face));
+        uint8_t *tab = table_open(tb);
+        int *cnt = (int *)(tab + o_cnt);
+        float *sc = (float *)(tab + o_sc);
+        const std::vector<char> empty = table_frames((FrameDesc *)(tab + o_fd), frames, rows, cols, steps, n, "face batch");
         for (int i = 0; i < n; i++) {
-            const int st = steps ? steps[i] : cols[i] * 3;
-            const uint8_t *p = (const uint8_t *)frames[i];
-            check_frame(p, rows[i], cols[i], st);
-            const bool empty = !p || rows[i] <= 0 || cols[i] <= 0;
-            if (!empty && check_residency_) {
-                const int where = foreign_device_of(p);
-                if (where >= 0 && where != device_) throw ArgError("face batch: frame is resident on another device");
-            }
-            fd[i] = empty ? FrameDesc{nullptr, 0, 0, 0, 0} : FrameDesc{p, rows[i], cols[i], st, 0};
-            cnt[i] = empty ? 0 : std::min(counts[i], fpi);
+            cnt[i] = empty[i] ? 0 : std::min(counts[i], fpi);
             sc[i] = coord_scale ? coord_scale[i] : 1.f;
-            if (cnt[i]) memcpy(align_host_.data() + o_face + (size_t)i * fpi * sizeof(rf_face), faces + (size_t)i * cap_per_image, (size_t)cnt[i] * sizeof(rf_face));
         }
-        uint8_t *d_tab = align_tab_.reserve(total);
+        table_records(tab + o_face, fpi, faces, cap_per_image, sizeof(rf_face), cnt, fpi, n);
+        uint8_t *d_tab = align_tab_.reserve(tb.end);
         uint8_t *d_tensor = nullptr;
         double *d_mats = nullptr;
         face_batch_open(rq, &d_tensor, &d_mats);
         if (d_tensor || d_mats || rq.gated) {
-            if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
-            RF_HIP(hipMemcpyAsync(d_tab, align_host_.data(), total, hipMemcpyHostToDevice, align_stream_));
+            table_upload(d_tab, tb);
             for (int base = 0; base < n; base += per) {          // one stream: the scans and the tensor launches run in order
                 FaceSeq q;
-                q.frames = (const FrameDesc *)d_tab + base;
+                q.frames = (const FrameDesc *)(d_tab + o_fd) + base;
                 q.faces = d_tab + o_face + (size_t)base * fpi * sizeof(rf_face);
                 q.face_stride = (int)sizeof(rf_face); q.faces_per_image = fpi;
                 q.counts = (const int *)(d_tab + o_cnt) + base;
@@ -1494,88 +1434,37 @@ public:
         const int fpi = std::min(std::min(cap_per_image, max_faces), kTrackMaxFaces);      // records per image that travel to the device
         const int mq = std::min(max_faces, kTrackMaxFaces);                                 // quality records per image that do
         // one table: streams | images | counts | quality records | faces (60-byte records)
-        const size_t o_img = align256((size_t)n * sizeof(TrackStreamEntry)), o_cnt = o_img + align256((size_t)n * sizeof(TrackImageEntry)),
-                     o_q = o_cnt + align256((size_t)n * sizeof(int)), o_face = o_q + align256(quality ? (size_t)n * mq * sizeof(rf_face_quality) : 0),
-                     total = o_face + (size_t)n * fpi * sizeof(rf_face);
-        align_host_.assign(total, 0);
-        int *cnt = (int *)(align_host_.data() + o_cnt);
+        HostTable tb;
+        const size_t o_se = tb.add((size_t)n * sizeof(TrackStreamEntry)), o_img = tb.add((size_t)n * sizeof(TrackImageEntry)),
+                     o_cnt = tb.add((size_t)n * sizeof(int)), o_q = tb.add(quality ? (size_t)n * mq * sizeof(rf_face_quality) : 0),
+                     o_face = tb.add((size_t)n * fpi * sizeof(rf_face));
+        uint8_t *tab = table_open(tb);
+        int *cnt = (int *)(tab + o_cnt);
         std::vector<float> scale(n);
         std::vector<char> empty(n, 0);
         for (int i = 0; i < n; i++) {
             cnt[i] = counts[i];            // the true count: the kernel clamps it, and tags the faces beyond the clamp
             scale[i] = coord_scale ? coord_scale[i] : 1.f;
-            const int c = std::min(counts[i], fpi);
-            if (c) memcpy(align_host_.data() + o_face + (size_t)i * fpi * sizeof(rf_face), faces + (size_t)i * cap_per_image, (size_t)c * sizeof(rf_face));
-            if (quality && c) memcpy(align_host_.data() + o_q + (size_t)i * mq * sizeof(rf_face_quality), quality + (size_t)i * max_faces,
-                                     (size_t)std::min(c, mq) * sizeof(rf_face_quality));
         }
-        const int ns = track_build_table(rq.stream_of_image, 0, n, scale.data(), empty.data(), (TrackStreamEntry *)align_host_.data(),
-                                         (TrackImageEntry *)(align_host_.data() + o_img));
-        uint8_t *d_tab = align_tab_.reserve(total);
+        table_records(tab + o_face, fpi, faces, cap_per_image, sizeof(rf_face), cnt, fpi, n);
+        if (quality) table_records(tab + o_q, mq, quality, max_faces, sizeof(rf_face_quality), cnt, std::min(fpi, mq), n);
+        const int ns = track_build_table(rq.stream_of_image, 0, n, scale.data(), empty.data(), (TrackStreamEntry *)(tab + o_se),
+                                         (TrackImageEntry *)(tab + o_img));
+        uint8_t *d_tab = align_tab_.reserve(tb.end);
         track_open_call(t, rq, n, cap_per_image);
-        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
         t.dirty = true;
-        RF_HIP(hipMemcpyAsync(d_tab, align_host_.data(), total, hipMemcpyHostToDevice, align_stream_));
+        table_upload(d_tab, tb);
         TrackParams tp = track_params(t);
-        tp.streams = (const TrackStreamEntry *)d_tab; tp.n_streams = ns;
+        tp.streams = (const TrackStreamEntry *)(d_tab + o_se); tp.n_streams = ns;
         tp.images = (const TrackImageEntry *)(d_tab + o_img);
         tp.faces = d_tab + o_face; tp.face_stride = (int)sizeof(rf_face); tp.faces_per_image = fpi;
         tp.counts = (const int *)(d_tab + o_cnt);
         tp.records = quality ? (const rf_face_quality *)(d_tab + o_q) : nullptr;
         tp.max_faces = mq;
-        if (!trk_ev_[0]) { RF_HIP(hipEventCreate(&trk_ev_[0])); RF_HIP(hipEventCreate(&trk_ev_[1])); }
-        RF_HIP(hipEventRecord(trk_ev_[0], align_stream_));
-        launch_track(align_stream_, tp);
-        RF_HIP(hipGetLastError());
-        RF_HIP(hipEventRecord(trk_ev_[1], align_stream_));
-        RF_HIP(hipStreamSynchronize(align_stream_));
-        if (hipEventElapsedTime(&trk_launch_ms_, trk_ev_[0], trk_ev_[1]) != hipSuccess) trk_launch_ms_ = -1.f;
+        timed_launch(trk_ev_, trk_launch_ms_, [&] { launch_track(align_stream_, tp); });
         track_copy_out(t, rq, n, cap_per_image, counts, cut);
     }
     float track_last_launch_ms() const override { return trk_launch_ms_; }
-
-    void detect_track(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device, float threshold,
-                      rf_face *out, int cap_per_image, int *counts, bool *truncated, const TrackRequest &rq, bool *cut) override {
-        *cut = false;
-        if (n < 0 || (n > 0 && (!frames || !rows || !cols || !counts))) throw ArgError("null argument");
-        if (cap_per_image < 0 || (cap_per_image > 0 && !out)) throw ArgError("out is null");
-        Tracker &t = track_check(rq, n);
-        DeviceGuard guard(device_);
-        // as in detect_align(): a super-batch of earlier enqueues starts now, every later launch carries images of this call only
-        launch_pending();
-        track_open_call(t, rq, n, cap_per_image);
-        trk_.records = nullptr; trk_.max_faces = kTrackMaxFaces;
-        t.dirty = true;
-        trk_.on = n > 0;
-        struct Off { bool &on; ~Off() { on = false; } } off{trk_.on};
-        detect(frames, rows, cols, steps, n, on_device, threshold, out, cap_per_image, counts, truncated);
-        trk_.on = false;
-        // every launch of the call has been waited for (its `done` event follows the track launch)
-        track_copy_out(t, rq, n, cap_per_image, counts, cut);
-    }
-
-    void detect_track_face_batch(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,
-                                 float threshold, rf_face *out, int cap_per_image, int *counts, bool *truncated, const FaceBatchRequest &fb,
-                                 bool *overflow, const TrackRequest &rq, bool *cut) override {
-        *cut = false;
-        check_face_batch_request(fb);
-        if (n < 0 || (n > 0 && (!frames || !rows || !cols || !counts))) throw ArgError("null argument");
-        if (cap_per_image < 0 || (cap_per_image > 0 && !out)) throw ArgError("out is null");
-        if ((long)n * fb.spec.max_faces > (1L << 24)) throw ArgError("n x max_faces: more than 2^24 faces in one call");
-        Tracker &t = track_check(rq, n);
-        DeviceGuard guard(device_);
-        launch_pending();
-        track_open_call(t, rq, n, cap_per_image);
-        if (fb.gated) face_gate_open(fb, n);
-        trk_.records = fb.gated ? (const rf_face_quality *)fq_records_.ptr : nullptr;
-        trk_.max_faces = fb.spec.max_faces;
-        t.dirty = true;
-        trk_.on = n > 0;
-        struct Off { bool &on; ~Off() { on = false; } } off{trk_.on};
-        detect_face_batch(frames, rows, cols, steps, n, on_device, threshold, out, cap_per_image, counts, truncated, fb, overflow);
-        trk_.on = false;
-        track_copy_out(t, rq, n, cap_per_image, counts, cut);
-    }
 
     // -------------------------------------------------------------------------------- best-shot gallery
 private:
@@ -1704,32 +1593,32 @@ public:
     }
     void shot_open_call(const Tracker &t, const ShotRequest &sq, int n, int cap_ended) {
         const size_t slots = (size_t)std::max(n, 1) * std::max(cap_ended, 1);
-        shot_.d_out = sq.d_shots;
-        shot_.host = sq.shots != nullptr; shot_.info = sq.info != nullptr;
-        if (shot_.host) shot_out_.reserve(slots * t.shot_spec.bytes_per_face());
-        if (shot_.info) shot_info_.reserve(slots * sizeof(rf_shot));
-        shot_.last_streams = 0;
+        call_.shot.d_out = sq.d_shots;
+        call_.shot.host = sq.shots != nullptr; call_.shot.info = sq.info != nullptr;
+        if (call_.shot.host) shot_out_.reserve(slots * t.shot_spec.bytes_per_face());
+        if (call_.shot.info) shot_info_.reserve(slots * sizeof(rf_shot));
+        call_.shot.last_streams = 0;
     }
     // The two shot launches behind a track launch on stream st (what is common to both is in sp): deliver to the caller's device block
     // and / or the pinned call-level block the kernel writes straight into, then keep.
     void shot_launches(hipStream_t st, ShotParams sp) {
-        const Tracker &t = *trk_.tr;
+        const Tracker &t = *call_.trk.tr;
         sp.max_tracks = t.spec.max_tracks;
         sp.state = t.state.ptr;
-        sp.tags = (const rf_track_tag *)trk_tags_.ptr; sp.tag_stride = trk_.tag_stride;
-        sp.ended = (const rf_track *)trk_ended_.ptr; sp.cap_ended = trk_.cap_ended;
+        sp.tags = (const rf_track_tag *)trk_tags_.ptr; sp.tag_stride = call_.trk.tag_stride;
+        sp.ended = (const rf_track *)trk_ended_.ptr; sp.cap_ended = call_.trk.cap_ended;
         sp.ended_counts = (const int *)trk_counts_.ptr;
         sp.spec = t.shot_spec;
-        sp.max_faces = trk_.max_faces;
+        sp.max_faces = call_.trk.max_faces;
         sp.gallery = t.gallery.ptr; sp.records = (rf_shot *)t.shot_records.ptr;
-        sp.out_info = shot_.info ? (rf_shot *)shot_info_.ptr : nullptr;
-        if (shot_.host || !shot_.d_out) {
-            sp.out = shot_.host ? shot_out_.ptr : nullptr;
+        sp.out_info = call_.shot.info ? (rf_shot *)shot_info_.ptr : nullptr;
+        if (call_.shot.host || !call_.shot.d_out) {
+            sp.out = call_.shot.host ? shot_out_.ptr : nullptr;
             launch_shot_deliver(st, sp);
             sp.out_info = nullptr;
         }
-        if (shot_.d_out) {
-            sp.out = shot_.d_out;
+        if (call_.shot.d_out) {
+            sp.out = call_.shot.d_out;
             launch_shot_deliver(st, sp);
         }
         launch_shot_keep(st, sp);
@@ -1763,54 +1652,41 @@ public:
         const int fpi = std::min(std::min(cap_per_image, max_faces), kTrackMaxFaces);      // records per image that travel to the device
         const int mq = std::min(max_faces, kTrackMaxFaces);                                 // quality records per image that do
         // one table: streams | images | counts | stream entry of each image | frames | quality records | faces (60-byte records)
-        const size_t o_img = align256((size_t)n * sizeof(TrackStreamEntry)), o_cnt = o_img + align256((size_t)n * sizeof(TrackImageEntry)),
-                     o_ent = o_cnt + align256((size_t)n * sizeof(int)), o_fd = o_ent + align256((size_t)n * sizeof(int32_t)),
-                     o_q = o_fd + align256((size_t)n * sizeof(FrameDesc)), o_face = o_q + align256(quality ? (size_t)n * mq * sizeof(rf_face_quality) : 0),
-                     total = o_face + (size_t)n * fpi * sizeof(rf_face);
-        std::vector<uint8_t> tab(total, 0);
-        int *cnt = (int *)(tab.data() + o_cnt);
-        FrameDesc *fd = (FrameDesc *)(tab.data() + o_fd);
+        HostTable tb;
+        const size_t o_se = tb.add((size_t)n * sizeof(TrackStreamEntry)), o_img = tb.add((size_t)n * sizeof(TrackImageEntry)),
+                     o_cnt = tb.add((size_t)n * sizeof(int)), o_ent = tb.add((size_t)n * sizeof(int32_t)), o_fd = tb.add((size_t)n * sizeof(FrameDesc)),
+                     o_q = tb.add(quality ? (size_t)n * mq * sizeof(rf_face_quality) : 0), o_face = tb.add((size_t)n * fpi * sizeof(rf_face));
+        uint8_t *tab = table_open(tb);
+        int *cnt = (int *)(tab + o_cnt);
         std::vector<float> scale((size_t)n);
-        std::vector<char> empty((size_t)n, 0);
+        const std::vector<char> empty = table_frames((FrameDesc *)(tab + o_fd), frames, rows, cols, steps, n, "shots");
         for (int i = 0; i < n; i++) {
-            const int st = steps ? steps[i] : cols[i] * 3;
-            const uint8_t *p = (const uint8_t *)frames[i];
-            check_frame(p, rows[i], cols[i], st);
-            empty[i] = !p || rows[i] <= 0 || cols[i] <= 0;
-            if (!empty[i] && check_residency_) {
-                const int where = foreign_device_of(p);
-                if (where >= 0 && where != device_) throw ArgError("shots: frame is resident on another device");
-            }
-            fd[i] = empty[i] ? FrameDesc{nullptr, 0, 0, 0, 0} : FrameDesc{p, rows[i], cols[i], st, 0};
             cnt[i] = empty[i] ? 0 : counts[i];      // the true count: the kernel clamps it, and tags the faces beyond the clamp; a frame
             scale[i] = coord_scale ? coord_scale[i] : 1.f;      // without pixels has no faces
-            const int c = std::min(cnt[i], fpi);
-            if (c) memcpy(tab.data() + o_face + (size_t)i * fpi * sizeof(rf_face), faces + (size_t)i * cap_per_image, (size_t)c * sizeof(rf_face));
-            if (quality && c) memcpy(tab.data() + o_q + (size_t)i * mq * sizeof(rf_face_quality), quality + (size_t)i * max_faces,
-                                     (size_t)std::min(c, mq) * sizeof(rf_face_quality));
         }
+        table_records(tab + o_face, fpi, faces, cap_per_image, sizeof(rf_face), cnt, fpi, n);
+        if (quality) table_records(tab + o_q, mq, quality, max_faces, sizeof(rf_face_quality), cnt, std::min(fpi, mq), n);
         if (n == 0) return;
         DeviceGuard guard(device_);
-        TrackStreamEntry *se = (TrackStreamEntry *)tab.data();
-        const int ns = track_build_table(rq.stream_of_image, 0, n, scale.data(), empty.data(), se, (TrackImageEntry *)(tab.data() + o_img));
-        int32_t *ent = (int32_t *)(tab.data() + o_ent);
+        TrackStreamEntry *se = (TrackStreamEntry *)(tab + o_se);
+        const int ns = track_build_table(rq.stream_of_image, 0, n, scale.data(), empty.data(), se, (TrackImageEntry *)(tab + o_img));
+        int32_t *ent = (int32_t *)(tab + o_ent);
         int n_img = 0;
         for (int z = 0; z < ns; z++)
             for (int j = 0; j < se[z].n; j++) ent[n_img++] = z;
-        uint8_t *d_tab = align_tab_.reserve(total);
+        uint8_t *d_tab = align_tab_.reserve(tb.end);
         track_open_call(t, rq, n, cap_per_image);
         shot_open_call(t, sq, n, rq.cap_ended);
-        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
         t.dirty = true;
-        RF_HIP(hipMemcpyAsync(d_tab, tab.data(), total, hipMemcpyHostToDevice, align_stream_));
+        table_upload(d_tab, tb);
         TrackParams tp = track_params(t);
-        tp.streams = (const TrackStreamEntry *)d_tab; tp.n_streams = ns;
+        tp.streams = (const TrackStreamEntry *)(d_tab + o_se); tp.n_streams = ns;
         tp.images = (const TrackImageEntry *)(d_tab + o_img);
         tp.faces = d_tab + o_face; tp.face_stride = (int)sizeof(rf_face); tp.faces_per_image = fpi;
         tp.counts = (const int *)(d_tab + o_cnt);
         tp.records = quality ? (const rf_face_quality *)(d_tab + o_q) : nullptr;
         tp.max_faces = mq;
-        trk_.max_faces = mq;
+        call_.trk.max_faces = mq;
         launch_track(align_stream_, tp);
         RF_HIP(hipGetLastError());
         ShotParams sp;
@@ -1821,49 +1697,11 @@ public:
         sp.frames = (const FrameDesc *)(d_tab + o_fd);
         sp.faces = tp.faces; sp.face_stride = tp.face_stride; sp.faces_per_image = fpi;
         sp.counts = tp.counts;
-        if (!shot_ev_[0]) { RF_HIP(hipEventCreate(&shot_ev_[0])); RF_HIP(hipEventCreate(&shot_ev_[1])); }
-        RF_HIP(hipEventRecord(shot_ev_[0], align_stream_));
-        if (ns > 0) shot_launches(align_stream_, sp);
-        RF_HIP(hipEventRecord(shot_ev_[1], align_stream_));
-        RF_HIP(hipStreamSynchronize(align_stream_));
-        if (hipEventElapsedTime(&shot_launch_ms_, shot_ev_[0], shot_ev_[1]) != hipSuccess) shot_launch_ms_ = -1.f;
+        timed_launch(shot_ev_, shot_launch_ms_, [&] { if (ns > 0) shot_launches(align_stream_, sp); });
         track_copy_out(t, rq, n, cap_per_image, cnt, cut);
         shot_copy_out(t, rq, sq, n);
     }
     float shot_last_launch_ms() const override { return shot_launch_ms_; }
-
-    void detect_track_shots(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device, float threshold,
-                            rf_face *out, int cap_per_image, int *counts, bool *truncated, const TrackRequest &rq, const ShotRequest &sq,
-                            bool *cut) override {
-        *cut = false;
-        if (n < 0 || (n > 0 && (!frames || !rows || !cols || !counts))) throw ArgError("null argument");
-        if (cap_per_image < 0 || (cap_per_image > 0 && !out)) throw ArgError("out is null");
-        Tracker &t = track_check(rq, n, true);
-        shot_check(t, sq, n, rq.cap_ended);
-        FaceBatchRequest fb;                          // the quality launch of the gated face-batch path, for the gallery spec, no tensor
-        fb.spec = t.shot_spec;
-        fb.spec.capacity = std::max(1, n) * fb.spec.max_faces;
-        fb.gated = sq.gated; fb.has_gate = sq.has_gate; fb.gate = sq.gate; fb.quality = sq.quality;
-        if ((long)n * fb.spec.max_faces > (1L << 24)) throw ArgError("n x max_faces: more than 2^24 faces in one call");
-        DeviceGuard guard(device_);
-        launch_pending();
-        track_open_call(t, rq, n, cap_per_image, true);
-        shot_open_call(t, sq, n, rq.cap_ended);
-        if (fb.gated) face_gate_open(fb, n);
-        trk_.records = fb.gated ? (const rf_face_quality *)fq_records_.ptr : nullptr;
-        trk_.max_faces = fb.spec.max_faces;
-        t.dirty = true;
-        trk_.on = n > 0; shot_.on = n > 0;
-        struct Off { bool &a, &b; ~Off() { a = false; b = false; } } off{trk_.on, shot_.on};
-        if (fb.gated) {
-            bool overflow = false;
-            detect_face_batch(frames, rows, cols, steps, n, on_device, threshold, out, cap_per_image, counts, truncated, fb, &overflow);
-        } else detect(frames, rows, cols, steps, n, on_device, threshold, out, cap_per_image, counts, truncated);
-        trk_.on = false; shot_.on = false;
-        // every launch of the call has been waited for (its `done` event follows the keep launch)
-        track_copy_out(t, rq, n, cap_per_image, counts, cut);
-        shot_copy_out(t, rq, sq, n);
-    }
 
     // -------------------------------------------------------------------------------- face redaction
     // The arguments of a redacting call, checked before any state changes: the tracker and its streams (each at most once per call:
@@ -1878,7 +1716,8 @@ public:
         const std::string who = rq.overlay ? "overlay" : "redaction", verb = rq.overlay ? "drawn into" : "redacted";
         auto *t = rq.tracker ? &tracker_of(rq.tracker) : nullptr;
         if (t) {
-            if (t->dirty) throw ArgError("the tracker's last call failed: reset it first");            if (n > 0 && !rq.stream_of_image) throw ArgError("stream_of_image is null");
+            if (t->dirty) throw ArgError("the tracker's last call failed: reset it first");
+            if (n > 0 && !rq.stream_of_image) throw ArgError("stream_of_image is null");
             std::vector<int> seen;
             for (int i = 0; i < n; i++) {
                 const int st = rq.stream_of_image[i];
@@ -1926,31 +1765,31 @@ public:
             uint8_t *d = red_shadow_.reserve(bytes);
             RF_HIP(hipMemcpy(d, red_shadow_off_.data(), (size_t)n * sizeof(unsigned long long), hipMemcpyHostToDevice));
         }
-        red_.spec = rq.spec; red_.tr = tracker ? &tracker_of(tracker) : nullptr; red_.stream_of_image = rq.stream_of_image;
-        red_.n = n; red_.next_image = 0;
-        red_.overlay = rq.overlay; red_.ospec = rq.ospec;
+        call_.red.spec = rq.spec; call_.red.tr = tracker ? &tracker_of(tracker) : nullptr; call_.red.stream_of_image = rq.stream_of_image;
+        call_.red.n = n;
+        call_.red.overlay = rq.overlay; call_.red.ospec = rq.ospec;
     }
     // (the overlay part stays zero in a redacting call, whose launches take the RedactParams part alone)
     OverlayParams redact_params() const {
         OverlayParams rp;
         memset((void *)&rp, 0, sizeof(rp));
-        rp.spec = red_.spec;
-        if (red_.overlay) { rp.ospec = red_.ospec; rp.oregions = (OverlayRegion *)ov_regions_.ptr; }
-        if (red_.tr) {
-            rp.track_state = red_.tr->state.ptr;
-            rp.max_tracks = red_.tr->spec.max_tracks;
-            rp.coast = redact_coast(red_.spec.coast, red_.tr->spec.max_missed);
-            if (red_.tr->has_motion) { rp.motion = (const rf_track_motion *)red_.tr->motion.ptr; rp.horizon = red_.tr->motion_spec.horizon; }
+        rp.spec = call_.red.spec;
+        if (call_.red.overlay) { rp.ospec = call_.red.ospec; rp.oregions = (OverlayRegion *)ov_regions_.ptr; }
+        if (call_.red.tr) {
+            rp.track_state = call_.red.tr->state.ptr;
+            rp.max_tracks = call_.red.tr->spec.max_tracks;
+            rp.coast = redact_coast(call_.red.spec.coast, call_.red.tr->spec.max_missed);
+            if (call_.red.tr->has_motion) { rp.motion = (const rf_track_motion *)call_.red.tr->motion.ptr; rp.horizon = call_.red.tr->motion_spec.horizon; }
         }
         rp.regions = (RedactRegion *)red_regions_.ptr;
-        rp.nreg = (int *)red_counts_.ptr; rp.true_counts = (int *)red_counts_.ptr + std::max(red_.n, 1);
+        rp.nreg = (int *)red_counts_.ptr; rp.true_counts = (int *)red_counts_.ptr + std::max(call_.red.n, 1);
         rp.cell_values = (uint32_t *)red_cells_.ptr;
-        rp.pixels = (int *)red_counts_.ptr + 2 * std::max(red_.n, 1);
-        if (red_.spec.blur) { rp.shadow = red_shadow_.ptr; rp.shadow_off = (const unsigned long long *)red_shadow_.ptr; }
+        rp.pixels = (int *)red_counts_.ptr + 2 * std::max(call_.red.n, 1);
+        if (call_.red.spec.blur) { rp.shadow = red_shadow_.ptr; rp.shadow_off = (const unsigned long long *)red_shadow_.ptr; }
         return rp;
     }
     void redact_launch(hipStream_t st, const OverlayParams &rp) const {
-        if (red_.overlay) {
+        if (call_.red.overlay) {
             launch_overlay_regions(st, rp);
             launch_overlay_draw(st, rp);
             return;
@@ -1986,122 +1825,160 @@ public:
         const int fpi = std::max(1, std::min(cap_per_image, rq.spec.max_regions));      // records per image that travel to the device
         // one table: frames | counts | scales | streams | faces (60-byte records) | with ids, one int64 per face
         const bool with_ids = rq.overlay && rq.ids;
-        const size_t o_cnt = align256((size_t)n * sizeof(FrameDesc)), o_sc = o_cnt + align256((size_t)n * sizeof(int)),
-                     o_st = o_sc + align256((size_t)n * sizeof(float)), o_face = o_st + align256((size_t)n * sizeof(int)),
-                     o_id = o_face + align256((size_t)n * fpi * sizeof(rf_face)),
-                     total = with_ids ? o_id + (size_t)n * fpi * sizeof(int64_t) : o_face + (size_t)n * fpi * sizeof(rf_face);
-        align_host_.assign(total, 0);
-        FrameDesc *fd = (FrameDesc *)align_host_.data();
-        int *cnt = (int *)(align_host_.data() + o_cnt);
-        float *sc = (float *)(align_host_.data() + o_sc);
-        int *strm = (int *)(align_host_.data() + o_st);
+        HostTable tb;
+        const size_t o_fd = tb.add((size_t)n * sizeof(FrameDesc)), o_cnt = tb.add((size_t)n * sizeof(int)), o_sc = tb.add((size_t)n * sizeof(float)),
+                     o_st = tb.add((size_t)n * sizeof(int)), o_face = tb.add((size_t)n * fpi * sizeof(rf_face)),
+                     o_id = with_ids ? tb.add((size_t)n * fpi * sizeof(int64_t)) : 0;
+        uint8_t *tab = table_open(tb);
+        int *cnt = (int *)(tab + o_cnt);
+        float *sc = (float *)(tab + o_sc);
+        int *strm = (int *)(tab + o_st);
+        table_frames((FrameDesc *)(tab + o_fd), frames, rows, cols, steps, n, nullptr);      // checked by redact_check()
         for (int i = 0; i < n; i++) {
-            const uint8_t *p = (const uint8_t *)frames[i];
-            const bool empty = !p || rows[i] <= 0 || cols[i] <= 0;
-            fd[i] = empty ? FrameDesc{nullptr, 0, 0, 0, 0} : FrameDesc{p, rows[i], cols[i], steps ? steps[i] : cols[i] * 3, 0};
             cnt[i] = counts[i];             // the true count: the kernel cuts the list and reports its length
             sc[i] = coord_scale ? coord_scale[i] : 1.f;
             strm[i] = t ? rq.stream_of_image[i] : -1;
-            const int c = std::min(counts[i], fpi);
-            if (c) memcpy(align_host_.data() + o_face + (size_t)i * fpi * sizeof(rf_face), faces + (size_t)i * cap_per_image, (size_t)c * sizeof(rf_face));
-            if (c && with_ids) memcpy(align_host_.data() + o_id + (size_t)i * fpi * sizeof(int64_t), rq.ids + (size_t)i * cap_per_image, (size_t)c * sizeof(int64_t));
         }
-        uint8_t *d_tab = align_tab_.reserve(total);
+        table_records(tab + o_face, fpi, faces, cap_per_image, sizeof(rf_face), cnt, fpi, n);
+        if (with_ids) table_records(tab + o_id, fpi, rq.ids, cap_per_image, sizeof(int64_t), cnt, fpi, n);
+        uint8_t *d_tab = align_tab_.reserve(tb.end);
         redact_open(rq, t, n, (const uint8_t *const *)frames, rows, cols);
-        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
-        RF_HIP(hipMemcpyAsync(d_tab, align_host_.data(), total, hipMemcpyHostToDevice, align_stream_));
+        table_upload(d_tab, tb);
         OverlayParams rp = redact_params();
-        rp.frames = (const FrameDesc *)d_tab;
+        rp.frames = (const FrameDesc *)(d_tab + o_fd);
         rp.faces = d_tab + o_face; rp.face_stride = (int)sizeof(rf_face); rp.faces_per_image = fpi;
         if (with_ids) { rp.ids = d_tab + o_id; rp.id_stride = (int)sizeof(int64_t); rp.ids_per_image = fpi; }
         rp.counts = (const int *)(d_tab + o_cnt); rp.count_cap = 0x7fffffff;
         rp.scale = (const float *)(d_tab + o_sc);
         rp.streams = t ? (const int *)(d_tab + o_st) : nullptr;
         rp.n = n; rp.image0 = 0;
-        if (!red_ev_[0]) { RF_HIP(hipEventCreate(&red_ev_[0])); RF_HIP(hipEventCreate(&red_ev_[1])); }
-        RF_HIP(hipEventRecord(red_ev_[0], align_stream_));
-        redact_launch(align_stream_, rp);
-        RF_HIP(hipGetLastError());
-        RF_HIP(hipEventRecord(red_ev_[1], align_stream_));
-        RF_HIP(hipStreamSynchronize(align_stream_));
-        float &ms = rq.overlay ? ov_launch_ms_ : red_launch_ms_;
-        if (hipEventElapsedTime(&ms, red_ev_[0], red_ev_[1]) != hipSuccess) ms = -1.f;
+        timed_launch(red_ev_, rq.overlay ? ov_launch_ms_ : red_launch_ms_, [&] { redact_launch(align_stream_, rp); });
         redact_copy_out(rq, n, cut);
     }
     float redact_last_launch_ms() const override { return red_launch_ms_; }
     float overlay_last_launch_ms() const override { return ov_launch_ms_; }
 
-    void detect_redact(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device, float threshold,
-                       rf_face *out, int cap_per_image, int *counts, bool *truncated, const RedactRequest &rq, bool *cut, uint8_t *const *out_bgr,
-                       const int *out_steps) override {
-        *cut = false;
-        if (n < 0 || (n > 0 && (!frames || !rows || !cols || !counts))) throw ArgError("null argument");
-        if (cap_per_image < 0 || (cap_per_image > 0 && !out)) throw ArgError("out is null");
-        if (rq.tracker) throw ArgError("redaction: the tracked form is detect_track_redact");
-        if (!on_device && n > 0 && !out_bgr) throw ArgError("out_bgr is null");
-        redact_check(rq, frames, rows, cols, steps, n, on_device);
-        DeviceGuard guard(device_);
-        // host frames are uploaded once, densely: detection and redaction run on that copy
+    // -------------------------------------------------------------------------------- stage calls
+    // Host frames of a redacting call, uploaded once, densely, each at a 256-byte-aligned offset of one block: detection and redaction run
+    // on that copy (dev[i], rows of cols * 3 bytes), which goes to out_bgr[i] when the call has ended
+    std::vector<const uint8_t *> redact_upload(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n,
+                                               uint8_t *const *out_bgr, const int *out_steps) {
         std::vector<const uint8_t *> dev((size_t)n, nullptr);
-        std::vector<int> st((size_t)std::max(n, 1));
-        for (int i = 0; i < n; i++) st[i] = steps ? steps[i] : cols[i] * 3;
-        if (!on_device) {
-            size_t bytes = 0;
-            std::vector<size_t> off((size_t)n, 0);
-            for (int i = 0; i < n; i++) {
-                if (!frames[i] || rows[i] <= 0 || cols[i] <= 0) continue;
-                if (!out_bgr[i]) throw ArgError("out_bgr[i] is null");
-                if (out_steps && out_steps[i] < cols[i] * 3) throw ArgError("out_steps[i] smaller than cols*3");
-                off[i] = bytes; bytes += align256((size_t)rows[i] * cols[i] * 3);
-            }
-            uint8_t *d = red_frames_.reserve(bytes);
-            for (int i = 0; i < n; i++) {
-                if (!frames[i] || rows[i] <= 0 || cols[i] <= 0) continue;
-                RF_HIP(hipMemcpy2D(d + off[i], (size_t)cols[i] * 3, frames[i], (size_t)st[i], (size_t)cols[i] * 3, (size_t)rows[i], hipMemcpyHostToDevice));
-                dev[i] = d + off[i];
-                st[i] = cols[i] * 3;
-            }
-        } else {
-            for (int i = 0; i < n; i++) dev[i] = frames[i];
+        size_t bytes = 0;
+        std::vector<size_t> off((size_t)n, 0);
+        for (int i = 0; i < n; i++) {
+            if (!frames[i] || rows[i] <= 0 || cols[i] <= 0) continue;
+            if (!out_bgr[i]) throw ArgError("out_bgr[i] is null");
+            if (out_steps && out_steps[i] < cols[i] * 3) throw ArgError("out_steps[i] smaller than cols*3");
+            off[i] = bytes; bytes += align256((size_t)rows[i] * cols[i] * 3);
         }
-        // as in detect_align(): a super-batch of earlier enqueues starts now, every later launch carries images of this call only
-        launch_pending();
-        redact_open(rq, nullptr, n, dev.data(), rows, cols);
-        red_.on = n > 0;
-        struct Off { bool &on; ~Off() { on = false; } } off_guard{red_.on};
-        detect(dev.data(), rows, cols, st.data(), n, true, threshold, out, cap_per_image, counts, truncated);
-        red_.on = false;
-        if (red_.next_image != n) throw HipError("redaction: a launch of the call was not redacted");
-        // every launch of the call has been waited for (its `done` event follows the redaction launches)
-        redact_copy_out(rq, n, cut);
-        if (!on_device)
-            for (int i = 0; i < n; i++)
-                if (dev[i]) RF_HIP(hipMemcpy2D(out_bgr[i], out_steps ? (size_t)out_steps[i] : (size_t)cols[i] * 3, dev[i], (size_t)cols[i] * 3,
-                                               (size_t)cols[i] * 3, (size_t)rows[i], hipMemcpyDeviceToHost));
+        uint8_t *d = red_frames_.reserve(bytes);
+        for (int i = 0; i < n; i++) {
+            if (!frames[i] || rows[i] <= 0 || cols[i] <= 0) continue;
+            RF_HIP(hipMemcpy2D(d + off[i], (size_t)cols[i] * 3, frames[i], steps ? (size_t)steps[i] : (size_t)cols[i] * 3, (size_t)cols[i] * 3,
+                               (size_t)rows[i], hipMemcpyHostToDevice));
+            dev[i] = d + off[i];
+        }
+        return dev;
     }
 
-    void detect_track_redact(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, float threshold, rf_face *out,
-                             int cap_per_image, int *counts, bool *truncated, const TrackRequest &trq, bool *track_cut, const RedactRequest &rq,
-                             bool *cut) override {
-        *cut = false; *track_cut = false;
+    // The fused calls (StageCall): detect() with the call's stages armed behind every launch (launch_pending()).  Everything a stage
+    // needs is bound when the call opens; the launch path does not know which of the seven calls it serves.
+    void detect_staged(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device, float threshold,
+                       rf_face *out, int cap_per_image, int *counts, bool *truncated, const StageCall &sc, StageResult *res) override {
+        *res = StageResult{};
+        const AlignRequest *al = sc.align;
+        const FaceBatchRequest *fb = sc.face_batch;
+        const TrackRequest *trq = sc.track;
+        const ShotRequest *sq = sc.shots;
+        const RedactRequest *rq = sc.redact;
+        static const int kSets[7] = {1, 2, 4, 4 | 2, 4 | 8, 16, 4 | 16};
+        const int set = (al ? 1 : 0) | (fb ? 2 : 0) | (trq ? 4 : 0) | (sq ? 8 : 0) | (rq ? 16 : 0);
+        if (std::find(kSets, kSets + 7, set) == kSets + 7) throw ArgError("stage call: not a set of stages that run together");
+        // every check before any state changes; a call with two defects reports the one it always has
+        if (al) check_align_request(*al);
+        if (fb) check_face_batch_request(*fb);
         if (n < 0 || (n > 0 && (!frames || !rows || !cols || !counts))) throw ArgError("null argument");
-        if (cap_per_image < 0 || (cap_per_image > 0 && !out)) throw ArgError("out is null");
-        if (!rq.tracker || rq.tracker != trq.tracker || rq.stream_of_image != trq.stream_of_image) throw ArgError("redaction: not the tracked call's tracker");
-        Tracker &t = track_check(trq, n);
-        redact_check(rq, frames, rows, cols, steps, n, true);
+        if ((trq || rq) && (cap_per_image < 0 || (cap_per_image > 0 && !out))) throw ArgError("out is null");      // (otherwise detect() refuses it)
+        if (al && (long)n * al->max_faces > (1L << 24)) throw ArgError("n x max_faces: more than 2^24 crop slots in one call");
+        if (fb && (long)n * fb->spec.max_faces > (1L << 24)) throw ArgError("n x max_faces: more than 2^24 faces in one call");
+        if (rq && !trq) {
+            if (rq->tracker) throw ArgError("redaction: the tracked form is detect_track_redact");
+            if (!on_device && n > 0 && !sc.out_bgr) throw ArgError("out_bgr is null");
+        } else if (rq) {
+            if (!rq->tracker || rq->tracker != trq->tracker || rq->stream_of_image != trq->stream_of_image) throw ArgError("redaction: not the tracked call's tracker");
+            if (!on_device) throw ArgError("redaction: the tracked call takes frames in device memory");
+        }
+        Tracker *t = trq ? &track_check(*trq, n, sq != nullptr) : nullptr;
+        // shots: the quality launch of the gated face-batch path, for the gallery spec, no tensor; it runs only under a gate, the frame
+        // steps read max_faces from it either way
+        FaceBatchRequest shot_fb;
+        if (sq) {
+            shot_check(*t, *sq, n, trq->cap_ended);
+            shot_fb.spec = t->shot_spec;
+            shot_fb.spec.capacity = std::max(1, n) * shot_fb.spec.max_faces;
+            shot_fb.gated = sq->gated; shot_fb.has_gate = sq->has_gate; shot_fb.gate = sq->gate; shot_fb.quality = sq->quality;
+            if ((long)n * shot_fb.spec.max_faces > (1L << 24)) throw ArgError("n x max_faces: more than 2^24 faces in one call");
+            if (sq->gated) fb = &shot_fb;
+        }
+        const FaceBatchRequest *records_of = sq ? &shot_fb : fb;      // whose quality records and max_faces the frame steps read
+        if (rq) redact_check(*rq, frames, rows, cols, steps, n, on_device);
         DeviceGuard guard(device_);
+        std::vector<const uint8_t *> dev;
+        std::vector<int> dense;
+        const bool uploaded = rq && !on_device;
+        if (uploaded) {
+            dev = redact_upload(frames, rows, cols, steps, n, sc.out_bgr, sc.out_steps);
+            dense.resize((size_t)std::max(n, 1));
+            for (int i = 0; i < n; i++) dense[i] = cols[i] * 3;
+            frames = dev.data(); steps = dense.data(); on_device = true;
+        }
+        // a super-batch of earlier enqueues that is still being assembled starts now: from here on every launch carries images of
+        // this call only, in call order, so image i of a launch is image call_.next_image + i of the call for every stage
         launch_pending();
-        track_open_call(t, trq, n, cap_per_image, rq.overlay);       // an overlay reads every face's id from its tag, whatever the caller's cap is
-        trk_.records = nullptr; trk_.max_faces = kTrackMaxFaces;
-        redact_open(rq, rq.tracker, n, frames, rows, cols);
-        t.dirty = true;
-        trk_.on = n > 0; red_.on = n > 0;
-        struct Off { bool &a, &b; ~Off() { a = false; b = false; } } off{trk_.on, red_.on};
-        detect(frames, rows, cols, steps, n, true, threshold, out, cap_per_image, counts, truncated);
-        trk_.on = false; red_.on = false;
-        if (red_.next_image != n) throw HipError("redaction: a launch of the call was not redacted");
-        track_copy_out(t, trq, n, cap_per_image, counts, track_cut);
-        redact_copy_out(rq, n, cut);
+        call_.who = trq ? "face tracks" : rq ? "redaction" : fb ? "face batch" : "face alignment";
+        call_.n = n; call_.next_image = 0;
+        if (al) { call_.align.rq = *al; align_open(*al, n, &call_.align.d_crops, &call_.align.d_mats); }
+        // full tags: the shot kernels find faces by their tags, and an overlay reads every face's id from its tag, whatever the caller's cap is
+        if (trq) track_open_call(*t, *trq, n, cap_per_image, sq || (rq && rq->overlay));
+        if (sq) shot_open_call(*t, *sq, n, trq->cap_ended);
+        if (fb) {
+            call_.fb.rq = *fb;
+            face_batch_open(*fb, &call_.fb.d_tensor, &call_.fb.d_mats);
+            if (fb->gated) face_gate_open(*fb, n);
+            call_.fb.first = true; call_.fb.prev_scan = nullptr;
+        }
+        if (trq) {
+            call_.trk.records = records_of && records_of->gated ? (const rf_face_quality *)fq_records_.ptr : nullptr;
+            call_.trk.max_faces = records_of ? records_of->spec.max_faces : kTrackMaxFaces;
+        }
+        if (rq) redact_open(*rq, trq ? rq->tracker : nullptr, n, frames, rows, cols);
+        if (t) t->dirty = true;                        // until track_copy_out() has run: an error in between leaves the tracker refused
+        struct Disarm { StageOpen &c; ~Disarm() { c.disarm(); } } disarm{call_};
+        call_.align.on = al && (call_.align.d_crops || call_.align.d_mats);
+        call_.fb.on = fb != nullptr;
+        call_.trk.on = trq && n > 0; call_.shot.on = sq && n > 0; call_.red.on = rq && n > 0;
+        const bool armed = call_.armed();
+        detect(frames, rows, cols, steps, n, on_device, threshold, out, cap_per_image, counts, truncated);
+        call_.disarm();
+        if (armed && call_.next_image != n)
+            throw HipError(rq ? "redaction: a launch of the call was not redacted" : std::string(call_.who) + ": a launch of the call was not served");
+        // every launch of the call has been waited for (its `done` event follows the launches of its stages); an empty frame has count 0
+        if (al) align_copy_out(*al, call_.align.d_crops, call_.align.d_mats, n, counts, opt_.max_detections);
+        if (fb) {
+            const int limit = std::min(fb->spec.max_faces, opt_.max_detections);
+            bool over = false;
+            if (fb->gated) face_gated_copy_out(*fb, call_.fb.d_tensor, call_.fb.d_mats, counts, n, limit, &over);
+            else face_batch_copy_out(*fb, call_.fb.d_tensor, call_.fb.d_mats, counts, n, limit, &over);
+            res->overflow = over && !sq;
+        }
+        if (trq) track_copy_out(*t, *trq, n, cap_per_image, counts, &res->track_cut);
+        if (sq) shot_copy_out(*t, *trq, *sq, n);
+        if (rq) redact_copy_out(*rq, n, &res->redact_cut);
+        if (uploaded)
+            for (int i = 0; i < n; i++)
+                if (dev[i]) RF_HIP(hipMemcpy2D(sc.out_bgr[i], sc.out_steps ? (size_t)sc.out_steps[i] : (size_t)cols[i] * 3, dev[i], (size_t)cols[i] * 3,
+                                               (size_t)cols[i] * 3, (size_t)rows[i], hipMemcpyDeviceToHost));
     }
 
     void host_register(const void *ptr, size_t bytes) override {
@@ -2304,16 +2181,16 @@ private:
         // it back to back and cross PCIe as one DMA per enqueue
         uint8_t *h_stage = nullptr, *d_stage = nullptr;
         size_t stage_cap = 0, stage_used = 0;
-        float *h_align_scale = nullptr;       // detect_align(): pinned, per image of the launch its frame_scale (allocated on first use)
-        int *d_face_off = nullptr;            // detect_face_batch(): packed offsets of the launch's images, written by its scan kernel (first use)
+        float *h_align_scale = nullptr;       // the stage hooks (lane_view): pinned, per image of the launch its frame_scale (allocated on first use)
+        int *d_face_off = nullptr;            // the face-batch stage: packed offsets of the launch's images, written by its scan kernel (first use)
         hipEvent_t face_scan_done = nullptr;  // ... recorded behind that scan: the call's next launch (another lane) waits for it on the device
         uint8_t *h_pass_tab = nullptr;        // pass calls: pinned, per image of the launch the pass it is, in the mode's entry type (allocated on first use)
         hipEvent_t pass_done = nullptr;       // ... recorded behind the launch's gather: the call's merge (another lane) waits for it on the device
-        uint8_t *h_track_tab = nullptr;       // detect_track(): pinned, the launch's stream table and image table (allocated on first use)
+        uint8_t *h_track_tab = nullptr;       // the track stage: pinned, the launch's stream table and image table (allocated on first use)
         hipEvent_t track_done = nullptr;      // ... recorded behind the launch's track kernel: the call's next track launch (another lane) waits for it
-        int32_t *h_shot_tab = nullptr;        // detect_track_shots(): pinned, per tracked image of the launch its stream entry (allocated on first use)
+        int32_t *h_shot_tab = nullptr;        // the shot stage: pinned, per tracked image of the launch its stream entry (allocated on first use)
         hipEvent_t shot_done = nullptr;       // ... recorded behind the launch's keep kernel: with a gallery the call's next track launch waits for this one
-        int *h_red_streams = nullptr;         // detect_track_redact(): pinned, per image of the launch its stream (allocated on first use)
+        int *h_red_streams = nullptr;         // the redaction stage behind a track launch: pinned, per image of the launch its stream (allocated on first use)
         bool busy = false;                    // a launched super-batch whose results have not been harvested yet
         int n_images = 0;                     // images of the super-batch being assembled / in flight on this lane
         float threshold = 0.f;
@@ -2440,6 +2317,56 @@ private:
 
     // ------------------------------------------------------------------------------------------ run
     static size_t align256(size_t v) { return (v + 255) / 256 * 256; }
+
+    // The host table of a standalone call (align, face_batch, track_update, track_shots, redact): sections appended at 256-byte
+    // alignment, filled in align_host_ and sent to align_tab_ in one copy on the side stream.
+    struct HostTable {
+        size_t end = 0;
+        size_t add(size_t bytes) { const size_t at = align256(end); end = at + bytes; return at; }
+    };
+    uint8_t *table_open(const HostTable &tb) {
+        align_host_.assign(tb.end, 0);
+        return align_host_.data();
+    }
+    // The FrameDesc section; returns which frames have no pixels.  With `who` every frame is checked, and one that is resident on another
+    // device refused under that prefix (nullptr: the caller has checked the frames).
+    std::vector<char> table_frames(FrameDesc *fd, const void *const *frames, const int *rows, const int *cols, const int *steps, int n, const char *who) {
+        std::vector<char> empty((size_t)n, 0);
+        for (int i = 0; i < n; i++) {
+            const int st = steps ? steps[i] : cols[i] * 3;
+            const uint8_t *p = (const uint8_t *)frames[i];
+            if (who) check_frame(p, rows[i], cols[i], st);
+            empty[i] = !p || rows[i] <= 0 || cols[i] <= 0;
+            if (who && !empty[i] && check_residency_) {
+                const int where = foreign_device_of(p);
+                if (where >= 0 && where != device_) throw ArgError(std::string(who) + ": frame is resident on another device");
+            }
+            fd[i] = empty[i] ? FrameDesc{nullptr, 0, 0, 0, 0} : FrameDesc{p, rows[i], cols[i], st, 0};
+        }
+        return empty;
+    }
+    // A per-image record section (faces, quality records, ids): the first min(cnt[i], take) records of image i, `bytes` each, from the
+    // caller's array (src_per records per image) to the table's (dst_per per image).
+    static void table_records(uint8_t *dst, int dst_per, const void *src, int src_per, size_t bytes, const int *cnt, int take, int n) {
+        for (int i = 0; i < n; i++) {
+            const int c = std::min(cnt[i], take);
+            if (c > 0) memcpy(dst + (size_t)i * dst_per * bytes, (const uint8_t *)src + (size_t)i * src_per * bytes, (size_t)c * bytes);
+        }
+    }
+    void table_upload(uint8_t *d_tab, const HostTable &tb) {
+        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+        RF_HIP(hipMemcpyAsync(d_tab, align_host_.data(), tb.end, hipMemcpyHostToDevice, align_stream_));
+    }
+    // a launch of a standalone call on the side stream between two events, waited for; *ms: its hipEvent time, or -1
+    template <class Launch> void timed_launch(hipEvent_t (&ev)[2], float &ms, Launch launch) {
+        if (!ev[0]) { RF_HIP(hipEventCreate(&ev[0])); RF_HIP(hipEventCreate(&ev[1])); }
+        RF_HIP(hipEventRecord(ev[0], align_stream_));
+        launch();
+        RF_HIP(hipGetLastError());
+        RF_HIP(hipEventRecord(ev[1], align_stream_));
+        RF_HIP(hipStreamSynchronize(align_stream_));
+        if (hipEventElapsedTime(&ms, ev[0], ev[1]) != hipSuccess) ms = -1.f;
+    }
 
     // img.empty() (RetinaFace.cpp:578-580) is legal and yields count 0; everything else must be a sane CV_8UC3 view
     void check_frame(const uint8_t *ptr, int rows, int cols, int step) const {
@@ -2648,12 +2575,16 @@ private:
         trace_.add(3, tt);
         tt = trace_.on ? HostTrace::now() : 0.0;
         if (eager_timed) RF_HIP(hipEventRecord(s.time_ev[3], s.stream));
-        if (align_.on) launch_lane_align(s, n);      // ordinary launches behind the graph, before `done`: nothing waits in between
-        if (fb_.on) launch_lane_face_batch(s, n);
+        // the open call's stages: ordinary launches behind the graph, before `done`: nothing waits in between
+        const bool staged = call_.armed();
+        if (staged && (n > cap_images_ || call_.next_image + n > call_.n)) throw HipError(std::string(call_.who) + ": a launch carries images of another call");
+        if (call_.align.on) launch_lane_align(s, n);
+        if (call_.fb.on) launch_lane_face_batch(s, n);
         if (passes_.on) launch_lane_passes(s, n);
-        if (trk_.on) launch_lane_track(s, n);
-        if (shot_.on) launch_lane_shots(s);
-        if (red_.on) launch_lane_redact(s, n);
+        if (call_.trk.on) launch_lane_track(s, n);
+        if (call_.shot.on) launch_lane_shots(s);
+        if (call_.red.on) launch_lane_redact(s, n);
+        if (staged) call_.next_image += n;
         RF_HIP(hipEventRecord(s.done, s.stream));
         trace_.add(4, tt);
         s.busy = true;
@@ -2661,67 +2592,71 @@ private:
         for (int id : s.tickets) tickets_[id].state = Ticket::LAUNCHED;
     }
 
-    // The alignment launch of a super-batch of detect_align(): source frames from the launch's own frame table (the first half:
-    // full-resolution frames, also when the stem reads a shrunk canvas), faces and counts from the pinned result block the NMS
-    // kernel of the same stream has just written, each frame's coordinate scale from a pinned per-lane array.
+    // What every stage hook binds from the lane into its kernel parameters: faces and counts from the pinned result block the NMS
+    // kernel of the same stream has just written; where the struct has them, source frames from the launch's own frame table (the
+    // first half: full-resolution frames, also when the stem reads a shrunk canvas) and each frame's coordinate scale from the pinned
+    // per-lane array.
+    template <class P> void lane_faces(P &p, const Lane &s) const {
+        p.faces = (const uint8_t *)s.h_out;
+        p.face_stride = (int)sizeof(Candidate); p.faces_per_image = opt_.max_detections;
+        p.counts = s.h_counts;
+    }
+    void lane_view(TrackParams &p, const Lane &s) const { lane_faces(p, s); }
+    void lane_view(ShotParams &p, const Lane &s) const { p.frames = s.d_frames; lane_faces(p, s); }
+    template <class P> void lane_view(P &p, const Lane &s) const {      // AlignParams, FaceSeq, OverlayParams
+        p.frames = s.d_frames;
+        p.scale = s.h_align_scale;
+        lane_faces(p, s);
+    }
+
+    // a per-lane block allocated on first use and owned by the lane (pinned host memory, or device memory), with the event of its stage
+    template <class U> void lane_block(Lane &s, U *&block, size_t bytes, bool device = false, hipEvent_t *event = nullptr) {
+        if (block) return;
+        void *p = nullptr;
+        if (device) { RF_HIP(hipMalloc(&p, std::max<size_t>(bytes, 256))); s.dev_allocs.push_back(p); }
+        else { RF_HIP(hipHostMalloc(&p, std::max<size_t>(bytes, 256), hipHostMallocDefault)); s.host_allocs.push_back(p); }
+        block = (U *)p;
+        if (event) RF_HIP(hipEventCreateWithFlags(event, hipEventDisableTiming));
+    }
+
+    // the alignment launch of a super-batch of an aligning call
     void launch_lane_align(Lane &s, int n) {
         fill_lane_align_scale(s, n);
         AlignParams ap;
-        ap.frames = s.d_frames;
-        ap.faces = (const uint8_t *)s.h_out;
-        ap.face_stride = (int)sizeof(Candidate); ap.faces_per_image = opt_.max_detections;
-        ap.counts = s.h_counts;
-        ap.scale = s.h_align_scale;
-        ap.n = n; ap.max_faces = align_.rq.max_faces; ap.crop = align_.rq.crop;
-        ap.first_image = align_.next_image;
-        ap.crops = align_.d_crops; ap.mats = align_.d_mats;
+        lane_view(ap, s);
+        ap.n = n; ap.max_faces = call_.align.rq.max_faces; ap.crop = call_.align.rq.crop;
+        ap.first_image = call_.next_image;
+        ap.crops = call_.align.d_crops; ap.mats = call_.align.d_mats;
         launch_align(s.stream, ap);
         RF_HIP(hipGetLastError());
-        align_.next_image += n;
     }
 
-    // pinned per-lane array of each image's coordinate scale (rf_frame_scale), allocated on first use
+    // pinned per-lane array of each image's coordinate scale (rf_frame_scale)
     void fill_lane_align_scale(Lane &s, int n) {
-        if (!s.h_align_scale) {
-            void *p = nullptr;
-            RF_HIP(hipHostMalloc(&p, std::max<size_t>((size_t)cap_images_ * sizeof(float), 256), hipHostMallocDefault));
-            s.host_allocs.push_back(p);
-            s.h_align_scale = (float *)p;
-        }
+        lane_block(s, s.h_align_scale, (size_t)cap_images_ * sizeof(float));
         for (int i = 0; i < n; i++) {
             const FrameDesc &f = s.h_frames[i];
             s.h_align_scale[i] = f.ptr ? frame_scale(f.rows, f.cols, net_h_, net_w_) : 1.f;
         }
     }
 
-    // The face-batch launches of a super-batch of detect_face_batch(): frames, faces, counts and scales as launch_lane_align().
-    // Packed offsets continue across the launches of a call through ONE running base in device memory: this launch's scan waits
-    // (on the device: hipStreamWaitEvent) for the scan of the call's previous launch, which ran on another lane's stream; the
-    // detection launches in front of it do not wait and keep overlapping.  No host wait anywhere.
+    // The face-batch launches of a super-batch of a face-batch call.  Packed offsets continue across the launches of a call through
+    // ONE running base in device memory: this launch's scan waits (on the device: hipStreamWaitEvent) for the scan of the call's
+    // previous launch, which ran on another lane's stream; the detection launches in front of it do not wait and keep overlapping.
+    // No host wait anywhere.
     void launch_lane_face_batch(Lane &s, int n) {
         fill_lane_align_scale(s, n);
-        if (!s.d_face_off) {
-            void *p = nullptr;
-            RF_HIP(hipMalloc(&p, std::max<size_t>(((size_t)cap_images_ + 1) * sizeof(int), 256)));
-            s.dev_allocs.push_back(p);
-            s.d_face_off = (int *)p;
-            RF_HIP(hipEventCreateWithFlags(&s.face_scan_done, hipEventDisableTiming));
-        }
+        lane_block(s, s.d_face_off, ((size_t)cap_images_ + 1) * sizeof(int), true, &s.face_scan_done);
         FaceSeq q;
-        q.frames = s.d_frames;
-        q.faces = (const uint8_t *)s.h_out;
-        q.face_stride = (int)sizeof(Candidate); q.faces_per_image = opt_.max_detections;
-        q.counts = s.h_counts;
-        q.scale = s.h_align_scale;
-        q.n = n; q.image0 = fb_.next_image;
-        q.first = fb_.first;
-        q.offsets = fb_.rq.gated ? (int *)fq_offsets_.ptr + fb_.next_image : s.d_face_off;
-        q.wait_before_scan = (fb_.prev_scan && fb_.prev_scan != s.face_scan_done) ? fb_.prev_scan : nullptr;
+        lane_view(q, s);
+        q.n = n; q.image0 = call_.next_image;
+        q.first = call_.fb.first;
+        q.offsets = call_.fb.rq.gated ? (int *)fq_offsets_.ptr + call_.next_image : s.d_face_off;
+        q.wait_before_scan = (call_.fb.prev_scan && call_.fb.prev_scan != s.face_scan_done) ? call_.fb.prev_scan : nullptr;
         q.record_after_scan = s.face_scan_done;
-        launch_face_seq(s.stream, fb_.rq, q, fb_.d_tensor, fb_.d_mats);
-        fb_.prev_scan = s.face_scan_done;
-        fb_.first = false;
-        fb_.next_image += n;
+        launch_face_seq(s.stream, call_.fb.rq, q, call_.fb.d_tensor, call_.fb.d_mats);
+        call_.fb.prev_scan = s.face_scan_done;
+        call_.fb.first = false;
         RF_HIP(hipGetLastError());
     }
 
@@ -2732,13 +2667,7 @@ private:
     // other lanes, then runs the merge (for the fused tiled call also the face-batch launches over the merged faces).  The lane's
     // `done` event follows, so the host's ordinary wait for the last launch covers all of it.  No host wait anywhere.
     void launch_lane_passes(Lane &s, int n) {
-        if (!s.h_pass_tab) {
-            void *p = nullptr;
-            RF_HIP(hipHostMalloc(&p, std::max<size_t>((size_t)cap_images_ * kPassEntryMax, 256), hipHostMallocDefault));
-            s.host_allocs.push_back(p);
-            s.h_pass_tab = (uint8_t *)p;
-            RF_HIP(hipEventCreateWithFlags(&s.pass_done, hipEventDisableTiming));
-        }
+        lane_block(s, s.h_pass_tab, (size_t)cap_images_ * kPassEntryMax, false, &s.pass_done);
         PassCall &c = passes_;
         if (n > cap_images_ || c.next_pass + n > c.total) throw HipError(std::string(c.name) + ": a launch carries images of another call");
         memcpy(s.h_pass_tab, c.table.data() + (size_t)c.next_pass * c.entry_bytes, (size_t)n * c.entry_bytes);
@@ -2775,21 +2704,14 @@ private:
         }
     }
 
-    // The track launch of a super-batch of detect_track(): faces and counts from the pinned result block the NMS kernel of the same
-    // stream has just written (and, for the fused face batch, the quality records its quality kernel has just written), which images
-    // belong to which stream from a pinned per-lane table.  A stream's images may sit in several launches on different lanes, and the
-    // state is one block in device memory, so the track launches of a call form a chain: each waits (on the device: hipStreamWaitEvent)
-    // for the track launch of the call's previous launch and records its own event.  The detection launches in front do not wait and
-    // keep overlapping.  The lane's `done` event follows, so the host's ordinary wait covers it.  No host wait anywhere.
+    // The track launch of a super-batch of a tracked call: faces and counts as lane_view() binds them (and, for the fused face batch,
+    // the quality records its quality kernel has just written), which images belong to which stream from a pinned per-lane table.  A
+    // stream's images may sit in several launches on different lanes, and the state is one block in device memory, so the track
+    // launches of a call form a chain: each waits (on the device: hipStreamWaitEvent) for the track launch of the call's previous
+    // launch and records its own event.  The detection launches in front do not wait and keep overlapping.  The lane's `done` event
+    // follows, so the host's ordinary wait covers it.  No host wait anywhere.
     void launch_lane_track(Lane &s, int n) {
-        if (!s.h_track_tab) {
-            void *p = nullptr;
-            RF_HIP(hipHostMalloc(&p, std::max<size_t>((size_t)cap_images_ * (sizeof(TrackStreamEntry) + sizeof(TrackImageEntry)), 256), hipHostMallocDefault));
-            s.host_allocs.push_back(p);
-            s.h_track_tab = (uint8_t *)p;
-            RF_HIP(hipEventCreateWithFlags(&s.track_done, hipEventDisableTiming));
-        }
-        if (n > cap_images_ || trk_.next_image + n > trk_.n) throw HipError("face tracks: a launch carries images of another call");
+        lane_block(s, s.h_track_tab, (size_t)cap_images_ * (sizeof(TrackStreamEntry) + sizeof(TrackImageEntry)), false, &s.track_done);
         std::vector<float> scale(n);
         std::vector<char> empty(n);
         for (int i = 0; i < n; i++) {
@@ -2799,39 +2721,31 @@ private:
         }
         TrackStreamEntry *se = (TrackStreamEntry *)s.h_track_tab;
         TrackImageEntry *ie = (TrackImageEntry *)(se + cap_images_);
-        const int ns = track_build_table(trk_.stream_of_image, trk_.next_image, n, scale.data(), empty.data(), se, ie);
-        trk_.next_image += n;
-        shot_.last_streams = ns;
+        const int ns = track_build_table(call_.trk.stream_of_image, call_.next_image, n, scale.data(), empty.data(), se, ie);
+        call_.shot.last_streams = ns;
         if (ns == 0) return;
-        if (trk_.prev && trk_.prev != s.track_done) RF_HIP(hipStreamWaitEvent(s.stream, trk_.prev, 0));
-        TrackParams tp = track_params(*trk_.tr);
+        if (call_.trk.prev && call_.trk.prev != s.track_done) RF_HIP(hipStreamWaitEvent(s.stream, call_.trk.prev, 0));
+        TrackParams tp = track_params(*call_.trk.tr);
         tp.streams = se; tp.n_streams = ns;
         tp.images = ie;
-        tp.faces = (const uint8_t *)s.h_out; tp.face_stride = (int)sizeof(Candidate); tp.faces_per_image = opt_.max_detections;
-        tp.counts = s.h_counts;
-        tp.records = trk_.records;
-        tp.max_faces = trk_.max_faces;
+        lane_view(tp, s);
+        tp.records = call_.trk.records;
+        tp.max_faces = call_.trk.max_faces;
         launch_track(s.stream, tp);
         RF_HIP(hipGetLastError());
         RF_HIP(hipEventRecord(s.track_done, s.stream));
-        trk_.prev = s.track_done;
+        call_.trk.prev = s.track_done;
     }
 
-    // The shot launches of a super-batch of detect_track_shots(), behind its track launch: the tables launch_lane_track() has just
-    // filled, frames from the launch's own frame table (the first half: full-resolution frames), faces and counts from the pinned
-    // result block.  The keep launch reads the table the NEXT track launch of the call rewrites, and that launch's deliver reads the
-    // entries this keep writes, so with a gallery the chain runs through the event recorded here: the call's next track launch waits
-    // for this keep launch, not only for the track launch in front of it.  The lane's `done` event follows.  No host wait anywhere.
+    // The shot launches of a super-batch of a shot call, behind its track launch: the tables launch_lane_track() has just filled,
+    // frames, faces and counts as lane_view() binds them.  The keep launch reads the table the NEXT track launch of the call
+    // rewrites, and that launch's deliver reads the entries this keep writes, so with a gallery the chain runs through the event
+    // recorded here: the call's next track launch waits for this keep launch, not only for the track launch in front of it.  The
+    // lane's `done` event follows.  No host wait anywhere.
     void launch_lane_shots(Lane &s) {
-        const int ns = shot_.last_streams;
+        const int ns = call_.shot.last_streams;
         if (ns == 0) return;                          // no tracked image in this launch: launch_lane_track() launched nothing either
-        if (!s.h_shot_tab) {
-            void *p = nullptr;
-            RF_HIP(hipHostMalloc(&p, std::max<size_t>((size_t)cap_images_ * sizeof(int32_t), 256), hipHostMallocDefault));
-            s.host_allocs.push_back(p);
-            s.h_shot_tab = (int32_t *)p;
-            RF_HIP(hipEventCreateWithFlags(&s.shot_done, hipEventDisableTiming));
-        }
+        lane_block(s, s.h_shot_tab, (size_t)cap_images_ * sizeof(int32_t), false, &s.shot_done);
         const TrackStreamEntry *se = (const TrackStreamEntry *)s.h_track_tab;
         int n_img = 0;
         for (int z = 0; z < ns; z++)
@@ -2841,46 +2755,34 @@ private:
         sp.streams = se; sp.n_streams = ns;
         sp.images = (const TrackImageEntry *)(se + cap_images_); sp.n_images = n_img;
         sp.entry_of = s.h_shot_tab;
-        sp.frames = s.d_frames;
-        sp.faces = (const uint8_t *)s.h_out; sp.face_stride = (int)sizeof(Candidate); sp.faces_per_image = opt_.max_detections;
-        sp.counts = s.h_counts;
+        lane_view(sp, s);
         shot_launches(s.stream, sp);
         RF_HIP(hipEventRecord(s.shot_done, s.stream));
-        trk_.prev = s.shot_done;
+        call_.trk.prev = s.shot_done;
     }
 
-    // The redaction launches of a super-batch of detect_redact() / detect_track_redact(): frames from the launch's own frame table (the
-    // first half: the caller's full-resolution frames, which are written in place), faces and counts from the pinned result block the
-    // NMS kernel of the same stream has just written, each frame's coordinate scale from the pinned per-lane array.  With a tracker the
-    // launches sit behind the lane's track launch: every stream appears at most once in the call, so its table is the one after this
-    // frame's step.  Region records, cell values and pixel counts are indexed by the image's place in the call: launches on different
-    // lanes write different slices.  The lane's `done` event follows.  No host wait anywhere.
+    // The redaction launches of a super-batch of a redacting call: frames (the caller's, written in place), faces, counts and scales
+    // as lane_view() binds them.  With a tracker the launches sit behind the lane's track launch: every stream appears at most once
+    // in the call, so its table is the one after this frame's step.  Region records, cell values and pixel counts are indexed by the
+    // image's place in the call: launches on different lanes write different slices.  The lane's `done` event follows.  No host
+    // wait anywhere.
     void launch_lane_redact(Lane &s, int n) {
-        if (n > cap_images_ || red_.next_image + n > red_.n) throw HipError("redaction: a launch carries images of another call");
         fill_lane_align_scale(s, n);
         OverlayParams rp = redact_params();
-        if (red_.tr) {
-            if (red_.overlay && trk_.on) {         // the tags the lane's track launch has just written, pinned like the result block
-                rp.ids = (const uint8_t *)trk_tags_.ptr + (size_t)red_.next_image * trk_.tag_stride * sizeof(rf_track_tag);
-                rp.id_stride = (int)sizeof(rf_track_tag); rp.ids_per_image = trk_.tag_stride; rp.ids_of_streams = 1;
+        if (call_.red.tr) {
+            if (call_.red.overlay && call_.trk.on) {         // the tags the lane's track launch has just written, pinned like the result block
+                rp.ids = (const uint8_t *)trk_tags_.ptr + (size_t)call_.next_image * call_.trk.tag_stride * sizeof(rf_track_tag);
+                rp.id_stride = (int)sizeof(rf_track_tag); rp.ids_per_image = call_.trk.tag_stride; rp.ids_of_streams = 1;
             }
-            if (!s.h_red_streams) {
-                void *p = nullptr;
-                RF_HIP(hipHostMalloc(&p, std::max<size_t>((size_t)cap_images_ * sizeof(int), 256), hipHostMallocDefault));
-                s.host_allocs.push_back(p);
-                s.h_red_streams = (int *)p;
-            }
-            for (int i = 0; i < n; i++) s.h_red_streams[i] = red_.stream_of_image[red_.next_image + i];
+            lane_block(s, s.h_red_streams, (size_t)cap_images_ * sizeof(int));
+            for (int i = 0; i < n; i++) s.h_red_streams[i] = call_.red.stream_of_image[call_.next_image + i];
             rp.streams = s.h_red_streams;
         }
-        rp.frames = s.d_frames;
-        rp.faces = (const uint8_t *)s.h_out; rp.face_stride = (int)sizeof(Candidate); rp.faces_per_image = opt_.max_detections;
-        rp.counts = s.h_counts; rp.count_cap = opt_.max_detections;
-        rp.scale = s.h_align_scale;
-        rp.n = n; rp.image0 = red_.next_image;
+        lane_view(rp, s);
+        rp.count_cap = opt_.max_detections;
+        rp.n = n; rp.image0 = call_.next_image;
         redact_launch(s.stream, rp);
         RF_HIP(hipGetLastError());
-        red_.next_image += n;
     }
 
     // The stream table of images [image0, image0 + n) of a call: the streams present in order of first appearance, each with its
@@ -2939,12 +2841,12 @@ private:
     // call-level result blocks (pinned host memory): tags (tag_stride per image), ended lists, ended counts | status
     // (full_tags: the shot kernels find faces by their tags, so every face the step looks at gets one whatever the caller's cap is)
     void track_open_call(Tracker &t, const TrackRequest &rq, int n, int cap_per_image, bool full_tags = false) {
-        trk_.tr = &t;
-        trk_.stream_of_image = rq.stream_of_image;
-        trk_.n = n; trk_.next_image = 0; trk_.prev = nullptr;
-        trk_.tag_stride = full_tags ? kTrackMaxFaces : std::max(0, std::min(cap_per_image, kTrackMaxFaces));
-        trk_.cap_ended = rq.cap_ended;
-        trk_tags_.reserve((size_t)std::max(n, 1) * std::max(trk_.tag_stride, 1) * sizeof(rf_track_tag));
+        call_.trk.tr = &t;
+        call_.trk.stream_of_image = rq.stream_of_image;
+        call_.trk.n = n; call_.trk.prev = nullptr;
+        call_.trk.tag_stride = full_tags ? kTrackMaxFaces : std::max(0, std::min(cap_per_image, kTrackMaxFaces));
+        call_.trk.cap_ended = rq.cap_ended;
+        trk_tags_.reserve((size_t)std::max(n, 1) * std::max(call_.trk.tag_stride, 1) * sizeof(rf_track_tag));
         trk_ended_.reserve((size_t)std::max(n, 1) * std::max(rq.cap_ended, 1) * sizeof(rf_track));
         trk_counts_.reserve((size_t)std::max(n, 1) * 2 * sizeof(int));
     }
@@ -2953,17 +2855,17 @@ private:
         memset(&tp, 0, sizeof(tp));
         tp.spec = t.spec;
         tp.state = t.state.ptr;
-        tp.tags = (rf_track_tag *)trk_tags_.ptr; tp.tag_stride = trk_.tag_stride;
-        tp.ended = (rf_track *)trk_ended_.ptr; tp.cap_ended = trk_.cap_ended;
+        tp.tags = (rf_track_tag *)trk_tags_.ptr; tp.tag_stride = call_.trk.tag_stride;
+        tp.ended = (rf_track *)trk_ended_.ptr; tp.cap_ended = call_.trk.cap_ended;
         tp.ended_counts = (int *)trk_counts_.ptr;
-        tp.status = (int *)trk_counts_.ptr + std::max(trk_.n, 1);
+        tp.status = (int *)trk_counts_.ptr + std::max(call_.trk.n, 1);
         if (t.has_motion) { tp.motion = (rf_track_motion *)t.motion.ptr; tp.mspec = t.motion_spec; }
         return tp;
     }
     // Results of a finished tracked call, from the pinned blocks the kernel wrote; the host fills what the device never writes -- the
     // images of stream -1, the tags at or beyond the image's count and whatever lies behind an ended list.
     void track_copy_out(Tracker &t, const TrackRequest &rq, int n, int cap_per_image, const int *counts, bool *cut) {
-        const int ts = trk_.tag_stride;
+        const int ts = call_.trk.tag_stride;
         const int *cs = (const int *)trk_counts_.ptr;
         const rf_track_tag *tags = (const rf_track_tag *)trk_tags_.ptr;
         const rf_track *ended = (const rf_track *)trk_ended_.ptr;
@@ -3213,7 +3115,7 @@ private:
     int next_ticket_ = 0;
 
     // face alignment: device scratch that grows to the largest call seen (every alignment call is synchronous, so nothing is in
-    // flight on a block when it is replaced), the stream of the standalone call, and the request detect_align() has open
+    // flight on a block when it is replaced), and the side stream of the standalone calls
     struct DeviceScratch {
         uint8_t *ptr = nullptr; size_t cap = 0;
         uint8_t *reserve(size_t bytes) {
@@ -3232,11 +3134,8 @@ private:
     std::vector<uint8_t> align_host_;
     hipStream_t align_stream_ = nullptr;
     static constexpr int kAlignImagesPerLaunch = 32768;       // grid.z limit of one launch
-    struct { bool on = false; AlignRequest rq; uint8_t *d_crops = nullptr; double *d_mats = nullptr; int next_image = 0; } align_;
-    // face batches: the running base of packed offsets (one device int), and the request detect_face_batch() has open
+    // face batches: the running base of packed offsets (one device int)
     DeviceScratch fb_state_;
-    struct { bool on = false, first = true; FaceBatchRequest rq; uint8_t *d_tensor = nullptr; double *d_mats = nullptr; hipEvent_t prev_scan = nullptr;
-             int next_image = 0; } fb_;
     // gated face batches: quality records and packed indices per face slot of the call, the call's packed offsets
     DeviceScratch fq_records_, fq_packed_, fq_offsets_;
     // pass calls: the one that is open, the device copy of its host frames, the event behind its side-stream copies
@@ -3298,14 +3197,11 @@ private:
     HostScratch shot_out_, shot_info_;
     hipEvent_t shot_ev_[2] = {nullptr, nullptr};
     float shot_launch_ms_ = -1.f;
-    struct { bool on = false; uint8_t *d_out = nullptr; bool host = false, info = false; int last_streams = 0; } shot_;
     HostScratch tta_out_, tta_votes_, tta_outcount_;      // detect_tta() / tta_merge(): what the voting merge writes (see tta_open)
     hipEvent_t trk_ev_[2] = {nullptr, nullptr};   // around the track launch of track_update() (tools/track_bench.py reads the time)
     float trk_launch_ms_ = -1.f;
     hipEvent_t red_ev_[2] = {nullptr, nullptr};   // around the redaction launches of redact() (tools/redact_bench.py reads the time)
     float red_launch_ms_ = -1.f, ov_launch_ms_ = -1.f;
-    struct { bool on = false; Tracker *tr = nullptr; const int *stream_of_image = nullptr; int n = 0, next_image = 0, tag_stride = 0, cap_ended = 0,
-             max_faces = 0; const rf_face_quality *records = nullptr; hipEvent_t prev = nullptr; } trk_;
 
     // face redaction: region records, region counts (after | before the cut) + owned-pixel counts, and cell values of the call's
     // images, the device copy of host frames; the request a redacting call has open
@@ -3313,9 +3209,26 @@ private:
     DeviceScratch red_shadow_;                    // a blurring call: offset table | the blurred owned pixels of every frame of the call
     std::vector<unsigned long long> red_shadow_off_;
     std::vector<int> red_host_;
-    struct { bool on = false; RedactSpec spec; Tracker *tr = nullptr; const int *stream_of_image = nullptr; int n = 0, next_image = 0;
-             bool overlay = false; OverlaySpec ospec; } red_;
     DeviceScratch ov_regions_;                    // an overlay call's region records (overlay.h), in the place of red_regions_
+
+    // The open stage call (detect_staged()): what each stage has bound for the call, and ONE cursor -- every launch between the open and
+    // the end of the call carries images of this call only, in call order, so image i of a launch is image next_image + i of the call for
+    // every stage.  What remains per stage is what really differs: the face batch's scan chain (first, prev_scan), the track chain
+    // (prev) and the streams of the lane's last track launch (last_streams).  The standalone calls bind the same per-stage blocks
+    // (track_params(), shot_launches() and redact_params() read them) and never arm a stage.
+    struct StageOpen {
+        const char *who = "";                 // the stage the call's launch errors name
+        int n = 0, next_image = 0;
+        struct { bool on = false; AlignRequest rq; uint8_t *d_crops = nullptr; double *d_mats = nullptr; } align;
+        struct { bool on = false, first = true; FaceBatchRequest rq; uint8_t *d_tensor = nullptr; double *d_mats = nullptr; hipEvent_t prev_scan = nullptr; } fb;
+        struct { bool on = false; Tracker *tr = nullptr; const int *stream_of_image = nullptr; int n = 0, tag_stride = 0, cap_ended = 0, max_faces = 0;
+                 const rf_face_quality *records = nullptr; hipEvent_t prev = nullptr; } trk;
+        struct { bool on = false; uint8_t *d_out = nullptr; bool host = false, info = false; int last_streams = 0; } shot;
+        struct { bool on = false; RedactSpec spec; Tracker *tr = nullptr; const int *stream_of_image = nullptr; int n = 0; bool overlay = false;
+                 OverlaySpec ospec; } red;
+        bool armed() const { return align.on || fb.on || trk.on || shot.on || red.on; }
+        void disarm() { align.on = fb.on = trk.on = shot.on = red.on = false; }
+    } call_;
 
     int last_n_ = 0;
     std::vector<int> last_cand_counts_;

@@ -173,6 +173,35 @@ struct RedactRequest {
     const int64_t *ids = nullptr;
 };
 
+// What a fused call wants behind every detection launch, on the launch's stream and with no host synchronisation in between: the
+// stages read faces and counts from the device-visible result block the launch has just written, and each frame's frame_scale is
+// applied, so frames the engine shrank are sampled at full source resolution.  A null request: the stage is off.  The sets a call
+// may carry are {align}, {face_batch}, {track}, {track, face_batch}, {track, shots}, {redact} and {track, redact}.
+//   align       the aligned crops of the faces found (AlignRequest).
+//   face_batch  their face batch (face_batch.h): per launch a scan kernel packs the counts on the device and the tensor kernel
+//               follows; gated, the quality kernel runs in front.  max_faces 0 in the spec has been replaced by the caller with
+//               default_max_faces().  StageResult::overflow: more packed faces than the capacity.
+//   track       the frame step of every image (track.h), which reads the call's quality records when face_batch is gated; the
+//               track launches of a call wait for each other on the device.  StageResult::track_cut: a full table or a cut
+//               ended list.
+//   shots       with track, on a tracker that has a gallery: the gallery rules behind each track launch (shot.h).  The gate rides
+//               in the request; gated, the quality launch of the gated face-batch path runs for the gallery spec.
+//   redact      redaction (or, with `overlay`, drawing) of the faces found, in place in device-resident frames.  Host frames are
+//               uploaded once, detected and redacted on that copy, and the copy goes to out_bgr[i] (rows of out_steps[i] bytes;
+//               nullptr = dense).  With track (device frames only, the same tracker and streams in both requests) the launches
+//               sit behind each track launch: the coasting regions are those of the table after this call's frame step.
+//               StageResult::redact_cut: a region list was cut at max_regions.
+struct StageCall {
+    const AlignRequest *align = nullptr;
+    const FaceBatchRequest *face_batch = nullptr;
+    const TrackRequest *track = nullptr;
+    const ShotRequest *shots = nullptr;
+    const RedactRequest *redact = nullptr;
+    uint8_t *const *out_bgr = nullptr;          // redact over host frames: where the redacted copies go
+    const int *out_steps = nullptr;
+};
+struct StageResult { bool overflow = false, track_cut = false, redact_cut = false; };
+
 class Engine {
 public:
     // opt.devices.size() > 1 gives the image-sharding multi-device engine (multi.cpp), otherwise one single-device engine
@@ -186,25 +215,17 @@ public:
     virtual void detect(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n,
                         bool on_device, float threshold, rf_face *out, int cap_per_image, int *counts,
                         bool *truncated) = 0;
-    // detect() + aligned crops of the faces it finds: the alignment launches follow each detection launch on its stream and read
-    // faces and counts from the device-visible result block (no host synchronisation in between); coordinates are scaled by each
-    // frame's frame_scale, so frames the engine shrank are sampled at full source resolution.  Single-device engines only.
-    virtual void detect_align(const uint8_t *const *, const int *, const int *, const int *, int, bool, float, rf_face *, int, int *,
-                              bool *, const AlignRequest &) {
-        throw Unsupported("face alignment is not available on a multi-device handle");
+    // detect() + the stages of `stages` behind every detection launch (StageCall).  Single-device engines only.
+    virtual void detect_staged(const uint8_t *const *, const int *, const int *, const int *, int, bool, float, rf_face *, int, int *, bool *,
+                               const StageCall &stages, StageResult *) {
+        const char *what = stages.redact ? "face redaction is" : stages.track ? "face tracks are" : stages.face_batch ? "face batches are" : "face alignment is";
+        throw Unsupported(std::string(what) + " not available on a multi-device handle");
     }
     // aligned crops of faces the caller supplies (faces[i * cap_per_image + k], k < counts[i]) from device-resident frames;
     // coord_scale: per image, nullptr = 1
     virtual void align(const void *const *, const int *, const int *, const int *, int, const rf_face *, int, const int *,
                        const float *, const AlignRequest &) {
         throw Unsupported("face alignment is not available on a multi-device handle");
-    }
-    // detect() + the face batch of what it finds (face_batch.h): per launch a scan kernel packs the counts on the device and the
-    // tensor kernel follows, on the launch's stream, with no host synchronisation; *overflow: more packed faces than the capacity.
-    // max_faces 0 in the spec has been replaced by the caller with default_max_faces().  Single-device engines only.
-    virtual void detect_face_batch(const uint8_t *const *, const int *, const int *, const int *, int, bool, float, rf_face *, int,
-                                   int *, bool *, const FaceBatchRequest &, bool * /*overflow*/) {
-        throw Unsupported("face batches are not available on a multi-device handle");
     }
     // the face batch of faces the caller supplies, from device-resident frames
     virtual void face_batch(const void *const *, const int *, const int *, const int *, int, const rf_face *, int, const int *,
@@ -304,16 +325,6 @@ public:
     }
     // hipEvent time of the track launch of the most recent track_update() (negative: none yet)
     virtual float track_last_launch_ms() const { return -1.f; }
-    // detect() + the frame step of every image
-    virtual void detect_track(const uint8_t *const *, const int *, const int *, const int *, int, bool, float, rf_face *, int, int *, bool *,
-                              const TrackRequest &, bool * /*cut*/) {
-        throw Unsupported("face tracks are not available on a multi-device handle");
-    }
-    // detect_face_batch() + the frame steps, which read the call's quality records when the request is gated
-    virtual void detect_track_face_batch(const uint8_t *const *, const int *, const int *, const int *, int, bool, float, rf_face *, int,
-                                         int *, bool *, const FaceBatchRequest &, bool * /*overflow*/, const TrackRequest &, bool * /*cut*/) {
-        throw Unsupported("face tracks are not available on a multi-device handle");
-    }
     // Best-shot gallery (shot.h): a tracker may own n_streams x max_tracks face-batch crops and shot records in device memory; the two
     // shot launches follow each track launch on its stream and join the chain the track launches form.  Single-device engines only.
     virtual void tracker_enable_shots(void *, const FaceBatchSpec &) { throw Unsupported("face tracks are not available on a multi-device handle"); }
@@ -338,29 +349,12 @@ public:
                              const rf_face_quality *, bool * /*cut*/) {
         throw Unsupported("face tracks are not available on a multi-device handle");
     }
-    // detect_track() + the gallery rules; with rq.gated the quality launch of the gated face-batch path runs for the gallery spec
-    virtual void detect_track_shots(const uint8_t *const *, const int *, const int *, const int *, int, bool, float, rf_face *, int, int *, bool *,
-                                    const TrackRequest &, const ShotRequest &, bool * /*cut*/) {
-        throw Unsupported("face tracks are not available on a multi-device handle");
-    }
     // hipEvent time of the two shot launches of the most recent track_shots() (negative: none yet)
     virtual float shot_last_launch_ms() const { return -1.f; }
     // Face redaction, in place in device-resident frames: regions of faces the caller supplies (host memory) and, with a tracker in
     // the request, of its streams' coasting tracks.  *cut: a region list was cut at max_regions.  Single-device engines only.
     virtual void redact(const void *const *, const int *, const int *, const int *, int, const rf_face *, int, const int *, const float *,
                         const RedactRequest &, bool * /*cut*/) {
-        throw Unsupported("face redaction is not available on a multi-device handle");
-    }
-    // detect() + the redaction of what it finds: the redaction launches follow each detection launch on its stream and read faces and
-    // counts from the device-visible result block.  Host frames are uploaded once, detected and redacted on that copy, and the copy
-    // goes to out_bgr[i] (rows of out_steps[i] bytes; nullptr = dense).
-    virtual void detect_redact(const uint8_t *const *, const int *, const int *, const int *, int, bool, float, rf_face *, int, int *, bool *,
-                               const RedactRequest &, bool * /*cut*/, uint8_t *const * /*out_bgr*/, const int * /*out_steps*/) {
-        throw Unsupported("face redaction is not available on a multi-device handle");
-    }
-    // detect_track() + redaction behind each track launch: the coasting regions are those of the table after this call's frame step
-    virtual void detect_track_redact(const uint8_t *const *, const int *, const int *, const int *, int, float, rf_face *, int, int *, bool *,
-                                     const TrackRequest &, bool * /*track_cut*/, const RedactRequest &, bool * /*cut*/) {
         throw Unsupported("face redaction is not available on a multi-device handle");
     }
     // hipEvent time of the redaction launches of the most recent redact() (negative: none yet)
