@@ -115,6 +115,17 @@ public:
     const vector<int> &frameRotations() const { return frameRot_; }
     const vector<float> &rotScores() const { return rotScore_; }
 
+    /* additive: fisheye detection (rf_dewarper_create / rf_detect_dewarp_batch): createDewarper() makes a dewarper on this handle for
+       rows x cols frames -- the meshes planned from spec (rf_dewarp_plan) at viewW x viewH (0: the net size) -- which the destructor
+       frees; detectDewarped() detects every frame in the dewarper's views, made on the device, and merges the faces moved back through
+       the meshes.  Fills lastBatchResult() with the merged faces in SOURCE-FRAME pixels (at most spec->max_faces per frame; only vote,
+       max_faces and edge of spec are read, nullptr: the defaults); dewarpVotes() holds, per frame, how many candidates each face
+       merged, dewarpViews() the view its head came from. */
+    rf_dewarper createDewarper(int rows, int cols, const rf_dewarp_spec &spec, int viewW = 0, int viewH = 0);
+    void detectDewarped(const vector<cv::Mat> &imgs, rf_dewarper dewarper, float threshold = 0.5, const rf_dewarp_spec *spec = nullptr);
+    const vector<vector<int>> &dewarpVotes() const { return dewarpVotes_; }
+    const vector<vector<int>> &dewarpViews() const { return dewarpSrc_; }
+
     /* additive: low-light detection (rf_detect_enhanced_batch): every frame is enhanced on the device (tile-adaptive contrast boost of
        dark tiles, rf_enhance_spec) and detected; the frames themselves are not written.  Fills lastBatchResult() with what the plain
        batch call returns for the enhanced frames; tilesEnhanced() holds, per frame, the number of tiles the enhancement touched
@@ -207,6 +218,7 @@ private:
     vector<vector<int>> ttaVotes_, ttaPasses_;
     vector<vector<int>> pyrVotes_, pyrPasses_;
     vector<vector<int>> rotVotes_, rotSrc_;
+    vector<vector<int>> dewarpVotes_, dewarpSrc_;
     vector<int> tilesEnhanced_;
     vector<int> frameRot_;
     vector<float> rotScore_;

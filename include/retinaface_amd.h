@@ -955,6 +955,116 @@ int rf_rot_merge_device(rf_handle h, const int *rows, const int *cols, int n, co
                         const int *pass_counts, rf_face *out, int cap_per_image, int *counts, int *votes, int *src_rot, int *frame_rot,
                         float *rot_score);
 
+/* ---- Fisheye detection: under a ceiling or door camera with a fisheye lens a face sits on a circle around the lens centre, turned by its
+ * azimuth and stretched by the lens; quarter turns do not undo a lens.  A fisheye call makes up to 16 dewarped VIEWS (virtual pan / tilt
+ * cameras) of every frame on the device, detects them, moves the faces of all views back into the frame through the views' meshes and
+ * merges them on the device with the merge of the TTA call (DESIGN.md "Fisheye detection" holds the definition; tests/dewarp_ref.py
+ * restates it in numpy; every result is byte-exact against it):
+ *   mesh     a dewarper holds V views (1..16) of view_w x view_h pixels, both multiples of 16, at most 4096 x 3072.  Each view has a mesh of
+ *            (view_h / 16 + 1) x (view_w / 16 + 1) NODES: node (i, j) is the source position of view pixel (16 i, 16 j), two int32, x then
+ *            y, in 1/256 px, |value| <= 2^22.  Layout: view-major, then row-major nodes, x and y interleaved.  The device only ever sees
+ *            meshes; the lens trigonometry (rf_dewarp_plan) stays on the host, and a caller with their own calibration brings a mesh.
+ *   pixel    exact integers, >> arithmetic.  View pixel (X, Y): cell (X >> 4, Y >> 4), u = X & 15, v = Y & 15; per coordinate
+ *            S = n00 (16 - u)(16 - v) + n10 u (16 - v) + n01 (16 - u) v + n11 u v (fits int32); q = (S + 1024) >> 11 in 1/32 px;
+ *            x0 = q >> 5, w = q & 31.  The byte is (sum of tap * wx' * wy' + 512) >> 10 over the four taps (x0, y0) .. (x0 + 1, y0 + 1)
+ *            with weights 32 - w and w; a tap outside the rows x cols source reads as 0; the channels are independent.
+ *   passes   frame-major, ascending view.  A view is an ordinary image of the call: its result is exactly what rf_detect_batch_device
+ *            returns for it (the caveat of the rotation call holds: to the byte when ONE call holds all views as dense frames).  A NULL
+ *            frame finds nothing; a frame whose shape is not the dewarper's: RF_ERR_INVALID_ARG before any state changes.
+ *   mapping  face j of view v, on its 15 floats.  p = in * rf_frame_scale(view_h, view_w), one fp32 multiply.  pq = p * 256.0f, clamped to
+ *            [-4096, 256 dim + 4096] (dim = view_w for x, view_h for y) with two compares, c = pq > lo ? pq : lo; c = c < hi ? c : hi, so a
+ *            NaN becomes lo; q = (int)rintf(c).  cell = clamp(q >> 12, 0, cells - 1), u = q - 4096 cell: linear extrapolation over at most
+ *            one cell beyond the view.  Node weights 4096 - u and u per axis, the sum in int64; r = (S + 2^23) >> 24 in 1/256 px; the
+ *            result is (float)r * (1 / 256.f), exact.  Landmarks are mapped point by point; the score is untouched.  The box is the
+ *            min / max, in integers, over eight mapped points: the four corners and the four edge midpoints, xm = (x1q + x2q) >> 1 -- so
+ *            x1 <= x2 and y1 <= y2 stay.  Results are in SOURCE-FRAME pixels.
+ *   edge     with edge > 0 a face whose SCALED box has x1 < edge, y1 < edge, x2 > view_w - 1 - edge or y2 > view_h - 1 - edge is dropped
+ *            (its neighbour view sees it whole); 0, the default, drops nothing.
+ *   merge    rf_tta_spec's merge over the mapped faces of a frame's views, g = view * max_detections + j; src_view = g / max_detections.
+ *            vote: 0 / 2 = off (the default, as for rotation), 1 = on.  max_faces, outputs and caps (RF_ERR_TRUNCATED) as for the TTA call.
+ *   plan     rf_dewarp_plan, host only, doubles.  The lens: model (r = f theta, 2 f sin(theta / 2), 2 f tan(theta / 2), f sin theta), f in
+ *            px, the centre (cx, cy).  Views: yaw, pitch, roll, hfov in degrees; ring = N gives N views at yaw 360 j / N with one pitch and
+ *            one hfov, roll 0.  The node of view pixel (X, Y): fv = (view_w / 2) / tan(hfov / 2); d = R ((X - (view_w - 1) / 2) / fv,
+ *            (Y - (view_h - 1) / 2) / fv, 1) with R = Rz(yaw) Rx(pitch) Rz(roll); theta = atan2(hypot(dx, dy), dz), psi = atan2(dy, dx);
+ *            s = (cx + r(theta) cos psi, cy + r(theta) sin psi); node = lrint(256 s).  At yaw 0 and pitch > 0 the view's centre lies above
+ *            the lens centre and the view's up points away from it: where a standing person's head is under a ceiling camera.  Refused:
+ *            a view that reaches theta >= pi (orthographic: pi / 2), a node beyond +-2^22. */
+#define RF_DEWARP_MAX_VIEWS 16
+#define RF_LENS_EQUIDISTANT 0
+#define RF_LENS_EQUISOLID 1
+#define RF_LENS_STEREOGRAPHIC 2
+#define RF_LENS_ORTHOGRAPHIC 3
+typedef struct rf_dewarp_view {
+    double yaw, pitch, roll, hfov;   /* degrees */
+} rf_dewarp_view;
+typedef struct rf_dewarp_spec {
+    uint32_t struct_size;   /* sizeof(rf_dewarp_spec) */
+    int32_t model;          /* RF_LENS_* */
+    double f, cx, cy;       /* focal length and lens centre, source pixels */
+    int32_t views;          /* 1..16 explicit views in view[]; 0 with a ring */
+    int32_t ring;           /* 1..16: that many views at equal yaw steps with ring_pitch and ring_hfov; 0 with explicit views */
+    double ring_pitch, ring_hfov;
+    rf_dewarp_view view[RF_DEWARP_MAX_VIEWS];
+    int32_t vote;           /* 0 / 2 = off; 1 = kept boxes become the score-weighted mean of their cluster */
+    int32_t max_faces;      /* merged faces kept per frame on the device, 1..4096; 0 = the engine's max_detections */
+    int32_t edge;           /* the edge rule, view pixels, 0..1024; 0 = off */
+    int32_t reserved_;
+} rf_dewarp_spec;
+
+/* Host only, no GPU, no handle -- the same code the kernels run, compiled for the host.
+ * rf_dewarp_plan: the meshes of the spec's views at view_w x view_h (multiples of 16) into mesh, which holds cap_ints int32; *views
+ * receives the number of views (each (view_h / 16 + 1) * (view_w / 16 + 1) * 2 ints).  RF_ERR_INVALID_ARG for a bad or refused spec or a
+ * mesh that is too small.
+ * rf_dewarp_host: one view, whose nodes are view_mesh, of the rows x cols BGR frame src (row pitch step), written as view_w * 3 bytes per
+ * row at dst + y * dst_step (bytes beyond them are untouched).
+ * rf_dewarp_map_face: edge rule and mapping of one face of the view whose nodes are view_mesh.  Returns 1 (kept, out written; out may
+ * equal in), 0 (dropped by the edge rule) or RF_ERR_INVALID_ARG.
+ * rf_dewarp_merge_host: mapping and merge of ONE frame: view v holds pass_counts[v] faces (clamped to max_detections) at
+ * faces[v * max_detections + j]; mesh holds all views.  Only vote, max_faces and edge of spec are read; spec may be NULL.  *count is the
+ * true number of heads; out / votes / src_view (the last two may be NULL) receive the first min(*count, cap, max_faces).  Returns RF_OK,
+ * RF_ERR_TRUNCATED (a pass count above max_detections, or a cut list) or RF_ERR_INVALID_ARG. */
+int rf_dewarp_plan(const rf_dewarp_spec *spec, int view_w, int view_h, int32_t *mesh, int cap_ints, int *views);
+int rf_dewarp_host(const int32_t *view_mesh, int view_w, int view_h, const uint8_t *src, int rows, int cols, int step, uint8_t *dst,
+                   int dst_step);
+int rf_dewarp_map_face(const int32_t *view_mesh, int view_w, int view_h, int net_h, int net_w, int edge, const rf_face *in, rf_face *out);
+int rf_dewarp_merge_host(const rf_dewarp_spec *spec, const int32_t *mesh, int view_w, int view_h, int views, int net_h, int net_w,
+                         float nms_threshold, int max_detections, const rf_face *faces, const int *pass_counts, rf_face *out, int cap,
+                         int *count, int *votes, int *src_view);
+
+/* A dewarper: one camera's views on a handle -- the shape of its frames, the views' shape and their meshes, uploaded once.  view_w /
+ * view_h 0 = the net size.  Refused (RF_ERR_INVALID_ARG): rows * cols outside (0, 4096 x 3072], a bad view shape or count, a NULL mesh, a
+ * node beyond +-2^22.  Freed by rf_dewarper_destroy or with the handle; until the handle is destroyed, every call on a destroyed
+ * dewarper returns RF_ERR_INVALID_ARG.  Multi-device handles return RF_ERR_UNSUPPORTED. */
+typedef struct rf_dewarper_s *rf_dewarper;
+int rf_dewarper_create(rf_handle h, int rows, int cols, int view_w, int view_h, int views, const int32_t *mesh, rf_dewarper *out_dewarper);
+void rf_dewarper_destroy(rf_dewarper dewarper);
+
+/* The dewarp kernel on its own: view `view` of a frame of the dewarper's shape in device memory (any source pitch and pointer
+ * alignment) into a destination in device memory, view_w * 3 bytes per row at d_dst + y * dst_step.  Synchronous. */
+int rf_dewarp_device(rf_dewarper dewarper, int view, const void *d_src, int step, void *d_dst, int dst_step);
+
+/* Fisheye detection of frames resident on the engine's device.  rows and cols (each may be NULL: the dewarper's) name every frame's shape,
+ * which must be the dewarper's (0 x 0 or a NULL pointer: an empty frame); steps may be NULL (dense).  The views are made by one kernel on the
+ * device in front of the call's first detection launch; the views of all frames go through the engine's ordinary launches; a gather
+ * kernel behind each launch applies the edge rule and the mapping, and one merge launch behind the call's last launch waits for them on the
+ * device -- no host synchronisation in between.  Only vote, max_faces and edge of spec are read; spec may be NULL.  votes and src_view
+ * (indexed like out) may be NULL.  d_views, when not NULL, is device memory of n * V * view_h * view_w * 3 bytes that receives the views as
+ * dense frames, frame-major (a NULL frame's are left untouched): upright pixels for a recogniser.  The views' bytes and the faces do not
+ * depend on it when it is 256-byte aligned, as a fresh allocation is.  rf_last_anchor_indices / rf_last_candidate_counts afterwards
+ * describe the call's PASSES. */
+int rf_detect_dewarp_batch_device(rf_dewarper dewarper, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                  float threshold, const rf_dewarp_spec *spec, rf_face *out, int cap_per_image, int *counts, int *votes, int *src_view,
+                                  void *d_views);
+
+/* The same with frames in HOST memory (rf_detect_batch's convention): each frame is uploaded once, densely. */
+int rf_detect_dewarp_batch(rf_dewarper dewarper, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                           float threshold, const rf_dewarp_spec *spec, rf_face *out, int cap_per_image, int *counts, int *votes, int *src_view);
+
+/* Mapping and merge of per-view faces the CALLER supplies (host memory): view v of frame i holds pass_counts[i * V + v] faces (clamped to
+ * max_detections) at faces[(i * V + v) * max_detections + j].  No forward pass runs. */
+int rf_dewarp_merge_device(rf_dewarper dewarper, int n, const rf_dewarp_spec *spec, const rf_face *faces, const int *pass_counts,
+                           rf_face *out, int cap_per_image, int *counts, int *votes, int *src_view);
+
 /* ---- Zoom-pyramid detection: the smallest anchors are 16 px, so faces below about 16 px are not seen in a frame that already fits the
  * net.  A pyramid call detects every frame at 1x (the passes of its tile plan) and as net-sized tiles of the frame ENLARGED 2x and / or 4x
  * on the device, moves the faces of all passes back into the frame and merges them with the voting merge of the TTA call (DESIGN.md

@@ -17,6 +17,8 @@ from .detector import SHOT_DTYPE, shot_resolve  # noqa: F401
 from .detector import MOTION_DTYPE, motion_spec, track_predict  # noqa: F401
 from .detector import tta_map_face, tta_merge_host, tta_spec  # noqa: F401
 from .detector import rot_map_face, rot_merge_host, rot_spec, rotate_host  # noqa: F401
+from .detector import (LENS_EQUIDISTANT, LENS_EQUISOLID, LENS_ORTHOGRAPHIC, LENS_STEREOGRAPHIC, Dewarper, dewarp_host,  # noqa: F401
+                       dewarp_map_face, dewarp_merge_host, dewarp_plan, dewarp_spec)
 from .detector import enhance_host, enhance_spec  # noqa: F401
 from .detector import pyramid_map_face, pyramid_merge_host, pyramid_plan, pyramid_spec, zoom_host  # noqa: F401
 from .detector import (OVERLAY_LABEL_ID, OVERLAY_LABEL_NONE, OVERLAY_LABEL_SCORE, overlay_host, overlay_region,  # noqa: F401

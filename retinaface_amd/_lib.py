@@ -115,6 +115,20 @@ class rf_rot_spec(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("rots", C.c_int32), ("vote", C.c_int32), ("max_faces", C.c_int32)]
 
 
+class rf_dewarp_view(C.Structure):
+    _fields_ = [("yaw", C.c_double), ("pitch", C.c_double), ("roll", C.c_double), ("hfov", C.c_double)]
+
+
+class rf_dewarp_spec(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("model", C.c_int32), ("f", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("views", C.c_int32), ("ring", C.c_int32), ("ring_pitch", C.c_double), ("ring_hfov", C.c_double),
+                ("view", rf_dewarp_view * 16), ("vote", C.c_int32), ("max_faces", C.c_int32), ("edge", C.c_int32),
+                ("reserved_", C.c_int32)]
+
+
+RF_LENS_EQUIDISTANT, RF_LENS_EQUISOLID, RF_LENS_STEREOGRAPHIC, RF_LENS_ORTHOGRAPHIC = 0, 1, 2, 3
+
+
 class rf_enhance_spec(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("tile", C.c_int32), ("clip", C.c_int32), ("dark_below", C.c_int32)]
 
@@ -294,6 +308,21 @@ SYMBOLS = {
                                       _PP(C.c_int), _PP(C.c_float)]),
     "rf_rot_merge_device": (C.c_int, [C.c_void_p, _PP(C.c_int), _PP(C.c_int), C.c_int, _PP(rf_rot_spec), _PP(rf_face), _PP(C.c_int),
                                       _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), _PP(C.c_float)]),
+    "rf_dewarp_plan": (C.c_int, [_PP(rf_dewarp_spec), C.c_int, C.c_int, _PP(C.c_int32), C.c_int, _PP(C.c_int)]),
+    "rf_dewarp_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    "rf_dewarp_map_face": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _PP(rf_face), _PP(rf_face)]),
+    "rf_dewarp_merge_host": (C.c_int, [_PP(rf_dewarp_spec), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
+                                       _PP(rf_face), _PP(C.c_int), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int)]),
+    "rf_dewarper_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, _PP(C.c_void_p)]),
+    "rf_dewarper_destroy": (None, [C.c_void_p]),
+    "rf_dewarp_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "rf_detect_dewarp_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int, C.c_float,
+                                                _PP(rf_dewarp_spec), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int),
+                                                C.c_void_p]),
+    "rf_detect_dewarp_batch": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int, C.c_float,
+                                         _PP(rf_dewarp_spec), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int)]),
+    "rf_dewarp_merge_device": (C.c_int, [C.c_void_p, C.c_int, _PP(rf_dewarp_spec), _PP(rf_face), _PP(C.c_int), _PP(rf_face), C.c_int,
+                                         _PP(C.c_int), _PP(C.c_int), _PP(C.c_int)]),
     "rf_enhance_host": (C.c_int, [_PP(rf_enhance_spec), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, _PP(C.c_int)]),
     "rf_enhance_device": (C.c_int, [C.c_void_p, _PP(rf_enhance_spec), _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
                                     _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int)]),

@@ -329,6 +329,44 @@ void RetinaFace::detectRotated(const vector<cv::Mat> &imgs, float threshold, con
     }
 }
 
+rf_dewarper RetinaFace::createDewarper(int rows, int cols, const rf_dewarp_spec &spec, int viewW, int viewH) {
+    const int vw = viewW > 0 ? viewW : netW_, vh = viewH > 0 ? viewH : netH_;
+    if (vw < 16 || vh < 16 || vw > 4096 || vh > 3072) throw std::runtime_error("RetinaFace::createDewarper: bad view size");
+    vector<int32_t> mesh((size_t)RF_DEWARP_MAX_VIEWS * (vw / 16 + 1) * (vh / 16 + 1) * 2);
+    int views = 0;
+    if (rf_dewarp_plan(&spec, vw, vh, mesh.data(), (int)mesh.size(), &views) != RF_OK)
+        throw std::runtime_error("RetinaFace::createDewarper: the spec is not valid, or a view leaves what the lens images");
+    rf_dewarper d = nullptr;
+    check(rf_dewarper_create(h_, rows, cols, viewW, viewH, views, mesh.data(), &d), h_, "RetinaFace::createDewarper");
+    return d;
+}
+
+void RetinaFace::detectDewarped(const vector<cv::Mat> &imgs, rf_dewarper dewarper, float threshold, const rf_dewarp_spec *spec) {
+    const int n = (int)imgs.size();
+    lastBatch_.assign(n, vector<FaceDetectInfo>());
+    dewarpVotes_.assign(n, vector<int>());
+    dewarpSrc_.assign(n, vector<int>());
+    if (n == 0) return;
+    const int cap = spec && spec->max_faces > 0 ? spec->max_faces : maxDet_;
+    vector<const uint8_t *> ptrs(n);
+    vector<int> rows(n), cols(n), steps(n), counts(n, 0);
+    for (int i = 0; i < n; i++) {
+        ptrs[i] = imgs[i].empty() ? nullptr : imgs[i].data;
+        rows[i] = imgs[i].rows; cols[i] = imgs[i].cols; steps[i] = (int)(size_t)imgs[i].step;
+    }
+    vector<rf_face> faces((size_t)n * cap);
+    vector<int> votes((size_t)n * cap, 0), src((size_t)n * cap, 0);
+    check(rf_detect_dewarp_batch(dewarper, ptrs.data(), rows.data(), cols.data(), steps.data(), n, threshold, spec, faces.data(), cap,
+                                 counts.data(), votes.data(), src.data()), h_, "RetinaFace::detectDewarped");
+    for (int i = 0; i < n; i++) {
+        const int k = counts[i] < cap ? counts[i] : cap;
+        lastBatch_[i].resize(k);
+        if (k) memcpy(lastBatch_[i].data(), &faces[(size_t)i * cap], (size_t)k * sizeof(rf_face));
+        dewarpVotes_[i].assign(votes.begin() + (size_t)i * cap, votes.begin() + (size_t)i * cap + k);
+        dewarpSrc_[i].assign(src.begin() + (size_t)i * cap, src.begin() + (size_t)i * cap + k);
+    }
+}
+
 void RetinaFace::detectEnhanced(const vector<cv::Mat> &imgs, float threshold, const rf_enhance_spec *spec) {
     const int n = (int)imgs.size();
     lastBatch_.assign(n, vector<FaceDetectInfo>());

@@ -28,6 +28,7 @@ struct rf_engine {
     rf::EngineOptions opt;
     std::list<std::pair<std::pair<int, int>, std::unique_ptr<rf::Engine>>> pool;
     std::vector<rf_tracker_s *> trackers;              // rf_tracker_create: what rf_destroy still has to free
+    std::vector<rf_dewarper_s *> dewarpers;            // rf_dewarper_create: likewise
     ~rf_engine();
 };
 
@@ -37,8 +38,16 @@ struct rf_tracker_s {
     void *impl;
 };
 
+// a dewarper: the handle it lives on, the engine's object (null once destroyed) and its number of views
+struct rf_dewarper_s {
+    rf_engine *h;
+    void *impl;
+    int views;
+};
+
 rf_engine::~rf_engine() {
     for (rf_tracker_s *t : trackers) delete t;         // the engine frees the device state with itself
+    for (rf_dewarper_s *d : dewarpers) delete d;
 }
 
 namespace {
@@ -1403,6 +1412,155 @@ int rf_rot_merge_device(rf_handle h, const int *rows, const int *cols, int n, co
         bool tr = false;
         h->eng->rot_merge(rows, cols, n, rq, faces, pass_counts, out, cap_per_image, counts, &tr);
         rot_orient_call(rq, n, src_rot ? out : nullptr, cap_per_image, counts, src_rot, frame_rot, rot_score);
+        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+
+// ---- fisheye detection (dewarp.h)
+int rf_dewarp_plan(const rf_dewarp_spec *spec, int view_w, int view_h, int32_t *mesh, int cap_ints, int *views) {
+    if (!spec || !mesh || cap_ints < 0 || spec->struct_size != sizeof(rf_dewarp_spec)) return RF_ERR_INVALID_ARG;
+    if (view_w < 16 || view_h < 16 || (view_w & 15) || (view_h & 15) || view_w > rf::kDewarpMaxW || view_h > rf::kDewarpMaxH) return RF_ERR_INVALID_ARG;
+    rf_dewarp_view vw[rf::kDewarpMaxViews];
+    const int V = rf::dewarp_spec_views(*spec, vw);
+    if (!V || rf::dewarp_view_ints(view_w, view_h) * (size_t)V > (size_t)cap_ints) return RF_ERR_INVALID_ARG;
+    if (rf::dewarp_plan(*spec, view_w, view_h, mesh, views)) return RF_ERR_INVALID_ARG;
+    return RF_OK;
+}
+
+int rf_dewarp_host(const int32_t *view_mesh, int view_w, int view_h, const uint8_t *src, int rows, int cols, int step, uint8_t *dst,
+                   int dst_step) {
+    if (rf::dewarp_check_mesh(view_w, view_h, 1, view_mesh)) return RF_ERR_INVALID_ARG;
+    if (!src || !dst || rows <= 0 || cols <= 0 || rows > 4096 * 3072 / cols || step < cols * 3 || dst_step < view_w * 3) return RF_ERR_INVALID_ARG;
+    rf::dewarp_view_host(view_mesh, view_w, view_h, src, rows, cols, step, dst, dst_step);
+    return RF_OK;
+}
+
+int rf_dewarp_map_face(const int32_t *view_mesh, int view_w, int view_h, int net_h, int net_w, int edge, const rf_face *in, rf_face *out) {
+    if (!in || !out || net_h <= 0 || net_w <= 0 || edge < 0 || edge > 1024 || rf::dewarp_check_mesh(view_w, view_h, 1, view_mesh)) return RF_ERR_INVALID_ARG;
+    rf::DewarpEntry e{0, 0, 0, 0, view_w, view_h, rf::tile_frame_scale(view_h, view_w, net_h, net_w), 0, view_mesh};
+    float f[15];
+    memcpy(f, in, sizeof(f));
+    if (!rf::dewarp_map_face(e, edge, f, f)) return 0;
+    memcpy(out, f, sizeof(f));
+    return 1;
+}
+
+int rf_dewarp_merge_host(const rf_dewarp_spec *spec, const int32_t *mesh, int view_w, int view_h, int views, int net_h, int net_w,
+                         float nms_threshold, int max_detections, const rf_face *faces, const int *pass_counts, rf_face *out, int cap,
+                         int *count, int *votes, int *src_view) {
+    rf::DewarpSpec sp;
+    if (max_detections < 1 || max_detections > rf::kTtaMaxFaces || rf::dewarp_spec_resolve(spec, max_detections, &sp)) return RF_ERR_INVALID_ARG;
+    if (!faces || !pass_counts || !count || cap < 0 || (cap > 0 && !out) || net_h <= 0 || net_w <= 0) return RF_ERR_INVALID_ARG;
+    if (rf::dewarp_check_mesh(view_w, view_h, views, mesh)) return RF_ERR_INVALID_ARG;
+    for (int v = 0; v < views; v++)
+        if (pass_counts[v] < 0) return RF_ERR_INVALID_ARG;
+    bool truncated = false;
+    std::vector<float> cand;
+    std::vector<int> g;
+    const float scale = rf::tile_frame_scale(view_h, view_w, net_h, net_w);
+    for (int v = 0; v < views; v++) {
+        const rf::DewarpEntry e{0, v, 0, 0, view_w, view_h, scale, 0, mesh + (size_t)v * rf::dewarp_view_ints(view_w, view_h)};
+        if (pass_counts[v] > max_detections) truncated = true;
+        for (int j = 0; j < pass_counts[v] && j < max_detections; j++) {
+            float f[15];
+            memcpy(f, &faces[(size_t)v * max_detections + j], sizeof(f));
+            if (!rf::dewarp_map_face(e, sp.edge, f, f)) continue;
+            cand.insert(cand.end(), f, f + 15);
+            g.push_back(v * max_detections + j);
+        }
+    }
+    const int limit = cap < sp.max_faces ? cap : sp.max_faces;
+    std::vector<float> merged((size_t)limit * 15 + 1);
+    std::vector<int> vt((size_t)limit + 1), hg((size_t)limit + 1);
+    const int heads = rf::tta_merge_candidates(cand, g, nms_threshold, sp.vote != 0, limit, merged.data(), vt.data(), hg.data());
+    *count = heads;
+    const int emitted = heads < limit ? heads : limit;
+    for (int j = 0; j < emitted; j++) {
+        memset(&out[j], 0, sizeof(rf_face));
+        memcpy(&out[j], &merged[(size_t)j * 15], 15 * sizeof(float));
+        if (votes) votes[j] = vt[j];
+        if (src_view) src_view[j] = hg[j] / max_detections;
+    }
+    return truncated || heads > limit ? RF_ERR_TRUNCATED : RF_OK;
+}
+
+int rf_dewarper_create(rf_handle h, int rows, int cols, int view_w, int view_h, int views, const int32_t *mesh, rf_dewarper *out_dewarper) {
+    if (out_dewarper) *out_dewarper = nullptr;
+    if (!h || !out_dewarper) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        void *impl = h->eng->dewarper_create(rows, cols, view_w, view_h, views, mesh);
+        rf_dewarper_s *d = new rf_dewarper_s{h, impl, views};
+        h->dewarpers.push_back(d);
+        *out_dewarper = d;
+        return RF_OK;
+    });
+}
+
+void rf_dewarper_destroy(rf_dewarper dewarper) {
+    if (!dewarper) return;
+    rf_engine *h = dewarper->h;
+    (void)guarded(h, [&]() -> int {
+        h->eng->dewarper_destroy(dewarper->impl);
+        dewarper->impl = nullptr;          // the record stays until rf_destroy, so that a call on a destroyed dewarper is refused, not undefined
+        return RF_OK;
+    });
+}
+
+int rf_dewarp_device(rf_dewarper dewarper, int view, const void *d_src, int step, void *d_dst, int dst_step) {
+    if (!dewarper) return RF_ERR_INVALID_ARG;
+    return guarded(dewarper->h, [&]() -> int {
+        dewarper->h->eng->dewarp(dewarper->impl, view, d_src, step, d_dst, dst_step);
+        return RF_OK;
+    });
+}
+
+namespace {
+// a caller's fisheye spec with its defaults applied; refused before the engine is touched
+void dewarp_request(rf_dewarper dw, const rf_dewarp_spec *spec, int *votes, int *src_view, void *d_views, rf::DewarpRequest *rq) {
+    if (const char *bad = rf::dewarp_spec_resolve(spec, dw->h->eng->default_max_faces(), &rq->spec)) throw rf::ArgError(bad);
+    rq->dewarper = dw->impl;
+    rq->votes = votes; rq->src_view = src_view; rq->d_views = d_views;
+}
+
+int detect_dewarp_common(rf_dewarper dw, const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n,
+                         bool on_device, float thr, const rf_dewarp_spec *spec, rf_face *out, int cap, int *counts, int *votes,
+                         int *src_view, void *d_views) {
+    if (!dw) return RF_ERR_INVALID_ARG;
+    rf_engine *h = dw->h;
+    return guarded(h, [&]() -> int {
+        rf::DewarpRequest rq;
+        dewarp_request(dw, spec, votes, src_view, d_views, &rq);
+        bool tr = false;
+        h->eng->detect_dewarp(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, rq);
+        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+}  // namespace
+
+int rf_detect_dewarp_batch_device(rf_dewarper dewarper, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                  float threshold, const rf_dewarp_spec *spec, rf_face *out, int cap_per_image, int *counts, int *votes,
+                                  int *src_view, void *d_views) {
+    return detect_dewarp_common(dewarper, (const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, spec, out, cap_per_image, counts,
+                                votes, src_view, d_views);
+}
+
+int rf_detect_dewarp_batch(rf_dewarper dewarper, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                           float threshold, const rf_dewarp_spec *spec, rf_face *out, int cap_per_image, int *counts, int *votes,
+                           int *src_view) {
+    return detect_dewarp_common(dewarper, bgr, rows, cols, steps, n, false, threshold, spec, out, cap_per_image, counts, votes, src_view, nullptr);
+}
+
+int rf_dewarp_merge_device(rf_dewarper dewarper, int n, const rf_dewarp_spec *spec, const rf_face *faces, const int *pass_counts,
+                           rf_face *out, int cap_per_image, int *counts, int *votes, int *src_view) {
+    if (!dewarper) return RF_ERR_INVALID_ARG;
+    rf_engine *h = dewarper->h;
+    return guarded(h, [&]() -> int {
+        rf::DewarpRequest rq;
+        dewarp_request(dewarper, spec, votes, src_view, nullptr, &rq);
+        bool tr = false;
+        h->eng->dewarp_merge(n, rq, faces, pass_counts, out, cap_per_image, counts, &tr);
         if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
         return RF_OK;
     });

@@ -119,10 +119,10 @@ struct NetKind {
     std::function<void(const Plan &, const NetSite &, LaneNet *)> build_net;
 };
 
-// The open pass call: tiled, TTA, pyramid and rotation detection turn a call's frames into passes that go through detect()'s ordinary
+// The open pass call: tiled, TTA, pyramid, rotation and fisheye detection turn a call's frames into passes that go through detect()'s ordinary
 // launches, in call order, so image i of a launch is pass next_pass + i.  What differs between the modes is bound when the call is
 // opened (the two callables); the launch path (launch_lane_passes) does not know which mode it serves.
-constexpr size_t kPassEntryMax = std::max(std::max(sizeof(TileEntry), sizeof(TtaEntry)), std::max(sizeof(PyrEntry), sizeof(RotEntry)));
+constexpr size_t kPassEntryMax = std::max(std::max(std::max(sizeof(TileEntry), sizeof(TtaEntry)), std::max(sizeof(PyrEntry), sizeof(RotEntry))), sizeof(DewarpEntry));
 struct PassCall {
     // gather(stream, faces, face_stride, counts, table, n): the mode's gather over the n passes of one launch (table: their entries)
     using Gather = std::function<void(hipStream_t, const uint8_t *, int, const int *, const void *, int)>;
@@ -229,10 +229,11 @@ public:
         for (void *p : host_allocs_) (void)hipHostFree(p);
         if (align_stream_) { (void)hipStreamSynchronize(align_stream_); (void)hipStreamDestroy(align_stream_); }
         for (DeviceScratch *b : {&align_crops_, &align_mats_, &align_tab_, &fb_state_, &fq_records_, &fq_packed_, &fq_offsets_, &tile_cand_, &tile_count_, &tile_out_,
-                                 &tile_outcount_, &tile_tab_, &pass_frames_, &tta_cand_, &tta_count_, &tta_mirror_, &pyr_zoom_, &rot_copies_, &enh_luts_, &enh_frames_,
+                                 &tile_outcount_, &tile_tab_, &pass_frames_, &tta_cand_, &tta_count_, &tta_mirror_, &pyr_zoom_, &rot_copies_, &dewarp_views_, &enh_luts_, &enh_frames_,
                                  &red_regions_, &red_counts_, &red_cells_, &red_frames_, &red_shadow_}) b->release();
         for (HostScratch *b : {&trk_tags_, &trk_ended_, &trk_counts_, &enh_counts_, &tta_out_, &tta_votes_, &tta_outcount_, &shot_out_, &shot_info_}) b->release();
         for (auto &t : trackers_) t->release();
+        for (auto &d : dewarpers_) d->mesh.release();
         for (hipEvent_t e : trk_ev_) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : shot_ev_) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : red_ev_) if (e) (void)hipEventDestroy(e);
@@ -558,7 +559,7 @@ public:
     }
 
     // -------------------------------------------------------------------------------- pass calls
-    // What tiled, TTA, pyramid and rotation detection share (PassCall).  a..d: the arrays the entry point needs when n > 0.
+    // What tiled, TTA, pyramid, rotation and fisheye detection share (PassCall).  a..d: the arrays the entry point needs when n > 0.
     static void pass_check_args(int n, const void *a, const void *b, const void *c, const void *d, rf_face *out, int cap_per_image, int max_faces) {
         static_assert(kTileMaxFaces == 4096 && kTtaMaxFaces == 4096, "the message below names the bound");
         if (n < 0 || (n > 0 && (!a || !b || !c || !d))) throw ArgError("null argument");
@@ -609,7 +610,7 @@ public:
         void set(int q, const uint8_t *p, int r, int c, int s) { ptr[q] = p; rows[q] = r; cols[q] = c; step[q] = s; }
     };
 
-    // the event behind the mirrored / zoomed / rotated copies a call has just launched on the side stream (PassCall::inputs_ready)
+    // the event behind the mirrored / zoomed / rotated / dewarped copies a call has just launched on the side stream (PassCall::inputs_ready)
     hipEvent_t record_inputs_ready() {
         if (!inputs_ready_) RF_HIP(hipEventCreateWithFlags(&inputs_ready_, hipEventDisableTiming));
         RF_HIP(hipGetLastError());
@@ -1226,6 +1227,143 @@ public:
         DeviceGuard guard(device_);
         merge_passes(entries, n, faces, pass_counts, truncated, [&] { tta_open(n, mrq.spec); },
                      gather_into<RotMap>(0, tta_cand_, tta_count_, kTtaMergeCap), vote_merge_of(n, mrq.spec), tta_dirty_);
+        tta_copy_out(n, mrq, out, cap_per_image, counts, truncated);
+    }
+
+    // -------------------------------------------------------------------------------- fisheye detection
+private:
+    struct Dewarper;
+public:
+    void *dewarper_create(int rows, int cols, int view_w, int view_h, int views, const int32_t *mesh) override {
+        if (rows <= 0 || cols <= 0 || rows > 4096 * 3072 / cols) throw ArgError("dewarper: rows x cols must be in (0, 4096x3072]");
+        if (view_w < 0 || view_h < 0) throw ArgError("dewarper: negative view size");
+        if (!view_w) view_w = net_w_;
+        if (!view_h) view_h = net_h_;
+        if (const char *bad = dewarp_check_mesh(view_w, view_h, views, mesh)) throw ArgError(std::string("dewarper: ") + bad);
+        DeviceGuard guard(device_);
+        std::unique_ptr<Dewarper> d(new Dewarper);
+        d->rows = rows; d->cols = cols; d->view_w = view_w; d->view_h = view_h; d->views = views;
+        const size_t bytes = d->view_ints() * (size_t)views * sizeof(int32_t);
+        d->mesh.reserve(bytes);
+        try { RF_HIP(hipMemcpy(d->mesh.ptr, mesh, bytes, hipMemcpyHostToDevice)); } catch (...) { d->mesh.release(); throw; }
+        dewarpers_.push_back(std::move(d));
+        return dewarpers_.back().get();
+    }
+    void dewarper_destroy(void *p) override {
+        for (size_t i = 0; i < dewarpers_.size(); i++)
+            if (dewarpers_[i].get() == p) {
+                DeviceGuard guard(device_);
+                if (align_stream_) (void)hipStreamSynchronize(align_stream_);
+                dewarpers_[i]->mesh.release();
+                dewarpers_.erase(dewarpers_.begin() + i);
+                return;
+            }
+    }
+    Dewarper &dewarper_of(void *p) {
+        for (auto &d : dewarpers_)
+            if (d.get() == p) return *d;
+        throw ArgError("not a dewarper of this handle");
+    }
+
+    // The passes of a call's frames as one table, frame-major, ascending view.  A NULL frame keeps its passes, which gather nothing
+    // (frame = -1).  frames null: dewarp_merge(), which has no pixels.  rows: 0 for an empty frame.
+    void dewarp_build_passes(const Dewarper &dw, const uint8_t *const *frames, const int *rows, int n, std::vector<DewarpEntry> *entries) const {
+        entries->clear();
+        const float scale = tile_frame_scale(dw.view_h, dw.view_w, net_h_, net_w_);
+        for (int i = 0; i < n; i++) {
+            const bool empty = frames && (!frames[i] || rows[i] == 0);
+            for (int v = 0; v < dw.views; v++) {
+                DewarpEntry e;
+                memset(&e, 0, sizeof(e));
+                e.frame = empty ? -1 : i; e.view = v; e.rows = dw.rows; e.cols = dw.cols; e.view_w = dw.view_w; e.view_h = dw.view_h;
+                e.scale = scale; e.mesh = dw.view_mesh(v);
+                entries->push_back(e);
+            }
+        }
+    }
+
+    // the blocks of a fisheye call are those of a TTA call (tta_open): the two calls never overlap, and the merge is the same launch
+    static TtaRequest dewarp_merge_request(const DewarpRequest &rq) {
+        TtaRequest t;
+        t.spec.flip = 0; t.spec.vote = rq.spec.vote; t.spec.max_faces = rq.spec.max_faces;
+        t.votes = rq.votes; t.src_pass = rq.src_view;
+        return t;
+    }
+
+    void dewarp(void *p, int view, const void *d_src, int step, void *d_dst, int dst_step) override {
+        Dewarper &dw = dewarper_of(p);
+        if (view < 0 || view >= dw.views) throw ArgError("dewarp: view out of range");
+        if (!d_dst || dst_step < dw.view_w * 3) throw ArgError("dewarp: null destination or dst_step < view_w * 3");
+        check_frame((const uint8_t *)d_src, dw.rows, dw.cols, step);
+        if (!d_src) throw ArgError("null argument");
+        DeviceGuard guard(device_);
+        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+        const DewarpParams dp{(const uint8_t *)d_src, dw.rows, dw.cols, step, dw.view_mesh(view), dw.view_w, dw.view_h, (uint8_t *)d_dst, dst_step};
+        launch_dewarp_views(align_stream_, &dp, 1);
+        RF_HIP(hipGetLastError());
+        RF_HIP(hipStreamSynchronize(align_stream_));
+    }
+
+    void detect_dewarp(const uint8_t *const *frames, const int *frame_rows, const int *frame_cols, const int *steps, int n, bool on_device,
+                       float threshold, rf_face *out, int cap_per_image, int *counts, bool *truncated, const DewarpRequest &rq) override {
+        *truncated = false;
+        Dewarper &dw = dewarper_of(rq.dewarper);
+        const TtaRequest mrq = dewarp_merge_request(rq);
+        pass_check_args(n, frames, frames, frames, counts, out, cap_per_image, mrq.spec.max_faces);
+        std::vector<int> rows((size_t)std::max(n, 1), dw.rows), cols((size_t)std::max(n, 1), dw.cols);
+        for (int i = 0; i < n; i++) {
+            const int r = frame_rows ? frame_rows[i] : dw.rows, c = frame_cols ? frame_cols[i] : dw.cols;
+            if (!frames[i] || (r == 0 && c == 0)) { rows[i] = cols[i] = 0; continue; }      // an empty frame
+            if (r != dw.rows || c != dw.cols) throw ArgError("fisheye detection: a frame's shape is not the dewarper's");
+        }
+        std::vector<int> st = checked_steps(frames, rows.data(), cols.data(), steps, n);
+        std::vector<DewarpEntry> entries;
+        dewarp_build_passes(dw, frames, rows.data(), n, &entries);
+        if (n == 0) return;
+        DeviceGuard guard(device_);
+        const int V = dw.views;
+        const std::vector<const uint8_t *> base =
+            pass_frame_bases(frames, rows.data(), cols.data(), st, n, on_device, [&](int i) { return entries[(size_t)i * V].frame >= 0; });
+        launch_pending();
+        // The views: dense frames, frame-major, in the caller's block or in one of the engine's -- a view is a multiple of 768 bytes, so
+        // each starts 256-byte aligned (what a freshly allocated dense frame looks like to conv0's staging); made on the side stream,
+        // every lane that launches a pass of the call waits for them on the device.
+        const int P = (int)entries.size();
+        const size_t vb = dw.view_bytes();
+        uint8_t *d_views = rq.d_views ? (uint8_t *)rq.d_views : dewarp_views_.reserve(vb * (size_t)P);
+        PassViews v(P);
+        std::vector<DewarpParams> dp;
+        for (int q = 0; q < P; q++) {
+            const DewarpEntry &e = entries[q];
+            if (e.frame < 0) continue;
+            uint8_t *dst = d_views + vb * (size_t)q;
+            dp.push_back(DewarpParams{base[e.frame], dw.rows, dw.cols, st[e.frame], e.mesh, dw.view_w, dw.view_h, dst, dw.view_w * 3});
+            v.set(q, dst, dw.view_h, dw.view_w, dw.view_w * 3);
+        }
+        hipEvent_t dewarped = nullptr;
+        if (!dp.empty()) {
+            if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+            launch_dewarp_views(align_stream_, dp.data(), (int)dp.size());
+            dewarped = record_inputs_ready();
+        }
+        tta_open(n, mrq.spec);
+        *truncated = run_passes("fisheye detection", entries, v, threshold, dewarped,
+                                gather_into<DewarpMap>(rq.spec.edge, tta_cand_, tta_count_, kTtaMergeCap), vote_merge_of(n, mrq.spec), tta_dirty_);
+        tta_copy_out(n, mrq, out, cap_per_image, counts, truncated);
+    }
+
+    void dewarp_merge(int n, const DewarpRequest &rq, const rf_face *faces, const int *pass_counts, rf_face *out, int cap_per_image,
+                      int *counts, bool *truncated) override {
+        *truncated = false;
+        Dewarper &dw = dewarper_of(rq.dewarper);
+        const TtaRequest mrq = dewarp_merge_request(rq);
+        pass_check_args(n, faces, faces, counts, pass_counts, out, cap_per_image, mrq.spec.max_faces);
+        std::vector<DewarpEntry> entries;
+        dewarp_build_passes(dw, nullptr, nullptr, n, &entries);
+        if (n == 0) return;
+        DeviceGuard guard(device_);
+        merge_passes(entries, n, faces, pass_counts, truncated, [&] { tta_open(n, mrq.spec); },
+                     gather_into<DewarpMap>(rq.spec.edge, tta_cand_, tta_count_, kTtaMergeCap), vote_merge_of(n, mrq.spec), tta_dirty_);
         tta_copy_out(n, mrq, out, cap_per_image, counts, truncated);
     }
 
@@ -3152,6 +3290,17 @@ private:
     // counts and counts are tta_out_ / tta_votes_ / tta_outcount_ below.  Pyramid and rotation calls use the same blocks
     // (pyr_merge_spec, rot_merge_spec) and bring the zoom tiles / the rotated copies.
     DeviceScratch tta_cand_, tta_count_, tta_mirror_, pyr_zoom_, rot_copies_;
+    // fisheye detection (dewarp.h): the dewarpers of this handle (a camera's shapes and its meshes in device memory) and the views of a
+    // call; the call gathers into the TTA blocks too (dewarp_merge_spec)
+    struct Dewarper {
+        int rows = 0, cols = 0, view_w = 0, view_h = 0, views = 0;
+        DeviceScratch mesh;                   // views x nodes_y x nodes_x x 2 int32
+        size_t view_ints() const { return dewarp_view_ints(view_w, view_h); }
+        size_t view_bytes() const { return (size_t)view_w * view_h * 3; }      // a multiple of 768: dense views stay 256-byte aligned
+        const int32_t *view_mesh(int v) const { return (const int32_t *)mesh.ptr + (size_t)v * view_ints(); }
+    };
+    std::vector<std::unique_ptr<Dewarper>> dewarpers_;
+    DeviceScratch dewarp_views_;
     // low-light enhancement (enhance.h): LUTs | flags | per-frame counts of a call, and the enhanced copies of a fused call
     DeviceScratch enh_luts_, enh_frames_;
     bool tta_dirty_ = true;

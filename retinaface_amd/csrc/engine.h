@@ -126,6 +126,17 @@ struct RotRequest {
     int *src_rot = nullptr;
 };
 
+// A fisheye call (dewarp.h; rf_detect_dewarp_batch* / rf_dewarp_merge_device): the validated spec, the dewarper (what dewarper_create
+// returned), where the member count and the view of each merged face go, and where the views go (device memory; nullptr: an
+// engine-owned block)
+struct DewarpRequest {
+    DewarpSpec spec;
+    void *dewarper = nullptr;
+    int *votes = nullptr;                       // host, indexed like out, or nullptr
+    int *src_view = nullptr;
+    void *d_views = nullptr;                    // n * V * view_h * view_w * 3 bytes, dense, frame-major
+};
+
 // An enhanced detection call (enhance.h; rf_detect_enhanced_batch*): the validated spec, where the enhanced copies go (device memory;
 // nullptr: an engine-owned block) and where the number of flagged tiles of each frame goes
 struct EnhanceRequest {
@@ -278,6 +289,26 @@ public:
     // the rotate kernel on its own: a device-resident frame turned by k quarter turns counter-clockwise
     virtual void rotate(const void *, int, int, int, int, void *, int) {
         throw Unsupported("rotation detection is not available on a multi-device handle");
+    }
+    // Fisheye detection: a dewarper (the frame shape, the views' shape and meshes of one camera, uploaded once) lives on the handle;
+    // every frame of a call becomes its V views, made by one kernel on the device in front of the call's first launch, which go through
+    // detect()'s ordinary launches; a gather launch behind each of them and one voting merge behind the last (ordered by events on the
+    // device, no host wait).  view_w / view_h 0: the net size.  *truncated: a pass or the merge hit a cap.  Single-device engines only.
+    virtual void *dewarper_create(int /*rows*/, int /*cols*/, int /*view_w*/, int /*view_h*/, int /*views*/, const int32_t * /*mesh*/) {
+        throw Unsupported("fisheye detection is not available on a multi-device handle");
+    }
+    virtual void dewarper_destroy(void *) {}
+    // the dewarp kernel on its own: one view of a device-resident frame of the dewarper's shape
+    virtual void dewarp(void *, int /*view*/, const void *, int, void *, int) {
+        throw Unsupported("fisheye detection is not available on a multi-device handle");
+    }
+    // rows / cols (each may be null) of every frame must be the dewarper's, or 0 x 0 for an empty frame
+    virtual void detect_dewarp(const uint8_t *const *, const int *, const int *, const int *, int, bool, float, rf_face *, int, int *, bool *, const DewarpRequest &) {
+        throw Unsupported("fisheye detection is not available on a multi-device handle");
+    }
+    // edge rule, mapping and merge of per-view faces the caller supplies (faces[(i * V + v) * max_detections + j])
+    virtual void dewarp_merge(int, const DewarpRequest &, const rf_face *, const int *, rf_face *, int, int *, bool *) {
+        throw Unsupported("fisheye detection is not available on a multi-device handle");
     }
     // Low-light enhancement: the two enhance kernels over frames in device memory (synchronous), and the fused call -- the enhanced
     // copies made on the side stream in front of the call's first launch, detect() over them, no host wait in between.

@@ -15,6 +15,7 @@
 #include "redact.h"
 #include "pyramid.h"
 #include "rot.h"
+#include "dewarp.h"
 #include "tile.h"
 #include "tta.h"
 #include "track.h"
@@ -266,7 +267,7 @@ struct FaceGateScanParams {
 void launch_face_gate_scan(hipStream_t s, const FaceGateScanParams &p);
 int face_quality_ring_rows(int crop);                // luma rows the quality kernel holds in LDS (exposed for tests and DESIGN.md)
 
-// ---- K_i: the pass gather of tiled, TTA, pyramid and rotation detection (tile.h, tta.h, pyramid.h, rot.h) -- behind each detection
+// ---- K_i: the pass gather of tiled, TTA, pyramid, rotation and fisheye detection (tile.h, tta.h, pyramid.h, rot.h, dewarp.h) -- behind each detection
 //      launch of such a call: one workgroup per pass (image of the launch) applies the mode's mapping (and, for tiles and the pyramid,
 //      its edge rule) to the faces the NMS kernel kept and appends the survivors, as Candidate records whose `anchor` is the tie-break
 //      index g = pass_id * rank_stride + k, to the candidate array of the pass's frame (an atomic counter per frame; the append order
@@ -276,7 +277,7 @@ template <class Entry> struct PassGatherParams {
     int face_stride, faces_per_pass;      // bytes per record (rf_face 60, Candidate 64); records per pass
     const int *counts;                    // [n] faces of each pass (clamped to faces_per_pass here)
     const Entry *table;                   // [n] what each pass is (frame < 0: skipped)
-    int n, edge, rank_stride;             // passes of this launch; the spec's edge (TTA and rotation ignore it); max_detections
+    int n, edge, rank_stride;             // passes of this launch; the spec's edge (TTA and rotation ignore it; fisheye: view pixels); max_detections
     Candidate *cand; int *cand_count;     // per frame f: cand[f * cap + pos], pos from atomicAdd(cand_count + f); the counter keeps
     int cap;                              // counting past cap (the merge reports it), records at or beyond cap are not written
 };
@@ -301,7 +302,12 @@ struct RotMap {
     __host__ __device__ static bool keep(const Entry &e, int, const float *in, float *out) { rot_map_face(e, in, out); return true; }
     __host__ __device__ static int pass_id(const Entry &e) { return e.k; }
 };
-template <class Map> void launch_pass_gather(hipStream_t s, const PassGatherParams<typename Map::Entry> &p);      // the four above
+struct DewarpMap {
+    using Entry = DewarpEntry;
+    __host__ __device__ static bool keep(const Entry &e, int edge, const float *in, float *out) { return dewarp_map_face(e, edge, in, out); }
+    __host__ __device__ static int pass_id(const Entry &e) { return e.view; }
+};
+template <class Map> void launch_pass_gather(hipStream_t s, const PassGatherParams<typename Map::Entry> &p);      // the five above
 
 // ---- K_j: face tracks (track.h) -- the frame steps of a launch's images: one workgroup per stream present in the launch walks that
 //      stream's images in order, its table in LDS, one thread per slot.  Every pointer is device-visible memory (the fused calls read
@@ -448,6 +454,22 @@ struct RotateParams {
 };
 constexpr int kRotateFramesPerLaunch = 16;       // rotations of one launch: their descriptors travel as kernel arguments
 void launch_rotate_frames(hipStream_t s, const RotateParams *frames, int n);
+
+// ---- K_o: fisheye detection (dewarp.h).
+//      dewarp_views: dewarped views of BGR frames (any source pitch and alignment) as dense or pitched frames, in front of a fisheye
+//                    call's launches: the pixel rule of dewarp.h, a workgroup per 64 x 16 pixel tile of a view, its ten mesh nodes read
+//                    once, four source taps per pixel gathered from global memory, rows stored 12 bytes per thread.
+//      The gather is launch_pass_gather<DewarpMap> (dewarp_map_face: edge rule and mapping through the mesh), g = view * rank_stride + j.
+//      The merge is launch_vote_merge.
+struct DewarpParams {
+    const uint8_t *src; int rows, cols, step;     // the SOURCE frame: row y at src + y * step
+    const int32_t *mesh;                          // the VIEW's nodes, device memory
+    int view_w, view_h;                           // multiples of 16
+    uint8_t *dst; int dst_step;                   // view_w * 3 bytes per row are written, view_h rows
+};
+constexpr int kDewarpViewsPerLaunch = 16;        // views of one launch: their descriptors travel as kernel arguments
+constexpr int kDewarpTileW = 64, kDewarpTileH = 16;
+void launch_dewarp_views(hipStream_t s, const DewarpParams *views, int n);
 
 // ---- K_k: zoom-pyramid detection (pyramid.h).
 //      zoom_tile:  windows of frames enlarged 2x / 4x (integer bilinear, pyr_zoom_pixel) written as dense frames, in front of a

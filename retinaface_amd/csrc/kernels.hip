@@ -4479,9 +4479,9 @@ void launch_face_gate_scan(hipStream_t s, const FaceGateScanParams &p) {
 }
 
 // =============================================================================================
-// K_i: the pass gather of tiled, TTA, pyramid and rotation detection.  pass_gather_kernel<Map>: one workgroup per pass of the launch.
+// K_i: the pass gather of tiled, TTA, pyramid, rotation and fisheye detection.  pass_gather_kernel<Map>: one workgroup per pass of the launch.
 //      Each thread takes one face of the pass's result and applies the mode's edge rule and mapping, Map::keep -- tile_map_face,
-//      tta_map_face, pyr_map_face or rot_map_face, the code the rf_*_map_face entry points run on the host; TTA and rotation drop
+//      tta_map_face, pyr_map_face, rot_map_face or dewarp_map_face, the code the rf_*_map_face entry points run on the host; TTA and rotation drop
 //      nothing -- and the survivors are appended to the candidate array of the pass's frame: one atomic add per wavefront (ballot +
 //      popcount of the lanes below) on the frame's counter in device memory.  Passes of one frame arrive from different launches on
 //      different streams in any order; the merge (nms_kernel or vote_merge_kernel on these arrays) sorts on the total order
@@ -4530,6 +4530,7 @@ template void launch_pass_gather<TileMap>(hipStream_t, const PassGatherParams<Ti
 template void launch_pass_gather<TtaMap>(hipStream_t, const PassGatherParams<TtaEntry> &);
 template void launch_pass_gather<PyrMap>(hipStream_t, const PassGatherParams<PyrEntry> &);
 template void launch_pass_gather<RotMap>(hipStream_t, const PassGatherParams<RotEntry> &);
+template void launch_pass_gather<DewarpMap>(hipStream_t, const PassGatherParams<DewarpEntry> &);
 
 // =============================================================================================
 // K_j: face tracks (track.h).  track_kernel: one workgroup per stream present in the launch, one thread per slot (64 threads per 64
@@ -6176,6 +6177,76 @@ void launch_rotate_frames(hipStream_t s, const RotateParams *frames, int n) {
         }
         if (!blocks) continue;
         hipLaunchKernelGGL(rotate_frames_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536), (unsigned)m), dim3(kThreads), 0, s, b);
+    }
+}
+
+// =============================================================================================
+// K_o: fisheye detection (dewarp.h).
+// dewarp_views_kernel: the dewarped views of a call.  One launch carries up to sixteen views (blockIdx.y); a workgroup takes tiles of
+//      64 x 16 view pixels: four mesh cells side by side, whose 2 x 5 nodes it reads once into LDS (80 bytes).  Thread t owns the
+//      four pixels 4 (t & 15) .. + 3 of tile row t >> 4 -- they share a cell -- and runs dewarp.h's pixel rule on each: the cell's
+//      integer blend gives the source position in 1/32 px, four taps are gathered from global memory (a tile's footprint in the
+//      source is compact, its taps are shared by neighbouring pixels and threads and come from the cache; a tap outside the frame
+//      reads as 0 and is not addressed), and the twelve bytes go out as rotate_frames_kernel stores them: three dwords where the
+//      destination is dword aligned, bytewise elsewhere.  A wave writes four rows of 192 contiguous bytes.  view_w is a multiple of
+//      16, so a row has no pixel tail; no byte outside the view_w * 3 bytes of a row is written, and no source byte outside
+//      rows x cols is read.
+// =============================================================================================
+struct DewarpBatch { DewarpParams v[kDewarpViewsPerLaunch]; };
+constexpr int kDewarpTileNodes = kDewarpTileW / 16 + 1;
+
+__global__ __launch_bounds__(kThreads) void dewarp_views_kernel(DewarpBatch batch) {
+    static_assert(kThreads * 4 == kDewarpTileW * kDewarpTileH && kDewarpTileH == 16, "one thread per four pixels of a 64 x 16 tile");
+    __shared__ int32_t s_nodes[2 * kDewarpTileNodes * 2];
+    const DewarpParams a = batch.v[blockIdx.y];
+    if (a.view_w <= 0 || a.view_h <= 0) return;
+    const int tiles_x = (a.view_w + kDewarpTileW - 1) / kDewarpTileW, tiles = tiles_x * (a.view_h >> 4);
+    const int nx = dewarp_nodes_x(a.view_w);
+    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {       // uniform over the workgroup
+        const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+        const int X0 = tx * kDewarpTileW, Y0 = ty << 4;
+        const int cells = a.view_w - X0 < kDewarpTileW ? (a.view_w - X0) >> 4 : kDewarpTileW >> 4;
+        const int per_row = 2 * (cells + 1);                             // ints of one node row of the tile
+        if ((int)threadIdx.x < 2 * per_row) {
+            const int row = (int)threadIdx.x >= per_row, rem = (int)threadIdx.x - row * per_row;
+            s_nodes[row * 2 * kDewarpTileNodes + rem] = a.mesh[2 * ((size_t)(ty + row) * nx + (X0 >> 4)) + rem];
+        }
+        __syncthreads();
+        const int r = (int)threadIdx.x >> 4, q = ((int)threadIdx.x & 15) << 2;
+        if (X0 + q < a.view_w) {
+            uint8_t b[12];
+            for (int j = 0; j < 4; j++) {
+                int qx, qy;
+                dewarp_pixel_src(s_nodes, kDewarpTileNodes, q + j, r, &qx, &qy);      // the tile as a mesh of its own: one cell row
+                dewarp_sample(a.src, a.rows, a.cols, a.step, qx, qy, b + 3 * j);
+            }
+            const uint32_t o0 = b[0] | (uint32_t)b[1] << 8 | (uint32_t)b[2] << 16 | (uint32_t)b[3] << 24;
+            const uint32_t o1 = b[4] | (uint32_t)b[5] << 8 | (uint32_t)b[6] << 16 | (uint32_t)b[7] << 24;
+            const uint32_t o2 = b[8] | (uint32_t)b[9] << 8 | (uint32_t)b[10] << 16 | (uint32_t)b[11] << 24;
+            rot_store12(a.dst + (size_t)(Y0 + r) * a.dst_step + (size_t)3 * (X0 + q), o0, o1, o2);
+        }
+        __syncthreads();                                                 // the next tile overwrites s_nodes
+    }
+}
+
+// up to kDewarpViewsPerLaunch views per launch (blockIdx.y), the grid sized for the largest of them
+void launch_dewarp_views(hipStream_t s, const DewarpParams *views, int n) {
+    for (int f0 = 0; f0 < n; f0 += kDewarpViewsPerLaunch) {
+        DewarpBatch b;
+        memset(&b, 0, sizeof(b));
+        const int m = n - f0 < kDewarpViewsPerLaunch ? n - f0 : kDewarpViewsPerLaunch;
+        long long blocks = 0;
+        for (int i = 0; i < m; i++) {
+            const DewarpParams &p = views[f0 + i];
+            if (p.view_w <= 0 || p.view_h <= 0) continue;
+            if ((p.view_w & 15) || (p.view_h & 15) || !p.mesh || !p.src || !p.dst || p.rows <= 0 || p.cols <= 0 || p.step < p.cols * 3 ||
+                p.dst_step < p.view_w * 3)
+                throw std::invalid_argument("launch_dewarp_views: a view's shape, mesh, source or destination is not valid");
+            b.v[i] = p;
+            blocks = std::max(blocks, (long long)((p.view_w + kDewarpTileW - 1) / kDewarpTileW) * (p.view_h >> 4));
+        }
+        if (!blocks) continue;
+        hipLaunchKernelGGL(dewarp_views_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536), (unsigned)m), dim3(kThreads), 0, s, b);
     }
 }
 

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (rf_face, rf_face_batch_spec, rf_face_gate, rf_face_quality, rf_options, rf_overlay_spec, rf_redact_spec, rf_tile_spec, rf_track,
-                   rf_enhance_spec, rf_motion_spec, rf_pyramid_spec, rf_rot_spec, rf_shot, rf_track_motion, rf_track_spec, rf_track_tag, rf_tta_spec)
+                   rf_dewarp_spec, rf_enhance_spec, rf_motion_spec, rf_pyramid_spec, rf_rot_spec, rf_shot, rf_track_motion, rf_track_spec, rf_track_tag, rf_tta_spec)
 
 PRECISION_FP32, PRECISION_FP16, PRECISION_INT8 = 0, 1, 2
 
@@ -807,6 +807,139 @@ def rotate_host(frame: np.ndarray, k: int, out: Optional[np.ndarray] = None) -> 
     if st < 0:
         raise _lib.RFError(st, "rf_rotate_host: k must be in 0..3 and the destination pitch at least cols_k * 3")
     return out
+
+
+LENS_EQUIDISTANT, LENS_EQUISOLID, LENS_STEREOGRAPHIC, LENS_ORTHOGRAPHIC = 0, 1, 2, 3
+
+
+def dewarp_spec(model: int = LENS_EQUIDISTANT, f: float = 0.0, cx: float = 0.0, cy: float = 0.0, views=None, ring: int = 0,
+                pitch: float = 0.0, hfov: float = 0.0, vote: bool = False, max_faces: int = 0, edge: int = 0) -> rf_dewarp_spec:
+    """An rf_dewarp_spec: the lens (model, f in pixels, the centre cx, cy), the views -- `views`: up to 16 (yaw, pitch, roll, hfov)
+    tuples in degrees, or `ring` = N views at equal yaw steps with one pitch and hfov -- and the call-level fields vote (a kept box
+    becomes the score-weighted mean of its cluster; off by default), max_faces (0 = the engine's max_detections) and edge (a face
+    within this many view pixels of its view's border is dropped; 0 = off)."""
+    sp = rf_dewarp_spec()
+    sp.struct_size = C.sizeof(rf_dewarp_spec)
+    sp.model, sp.f, sp.cx, sp.cy = int(model), float(f), float(cx), float(cy)
+    views = list(views or [])
+    if len(views) > 16:
+        raise _lib.RFError(_lib.RF_ERR_INVALID_ARG, "rf_dewarp_spec: at most 16 views")
+    sp.views, sp.ring, sp.ring_pitch, sp.ring_hfov = len(views), int(ring), float(pitch), float(hfov)
+    for j, v in enumerate(views):
+        sp.view[j].yaw, sp.view[j].pitch, sp.view[j].roll, sp.view[j].hfov = (float(x) for x in v)
+    sp.vote, sp.max_faces, sp.edge = 1 if vote else 2, int(max_faces), int(edge)
+    return sp
+
+
+def _mesh_array(mesh, view_w: int, view_h: int, views: Optional[int] = None) -> np.ndarray:
+    m = np.ascontiguousarray(mesh, dtype=np.int32)
+    per = (view_h // 16 + 1) * (view_w // 16 + 1) * 2
+    if view_w < 16 or view_h < 16 or view_w % 16 or view_h % 16 or m.size % per or (views is not None and m.size != per * views):
+        raise _lib.RFError(_lib.RF_ERR_INVALID_ARG, "a mesh holds (view_h / 16 + 1) x (view_w / 16 + 1) x 2 int32 per view")
+    return m
+
+
+def dewarp_plan(spec: rf_dewarp_spec, view_w: int, view_h: int) -> np.ndarray:
+    """rf_dewarp_plan (host only, no GPU): the meshes of the spec's views, (V, view_h / 16 + 1, view_w / 16 + 1, 2) int32 -- per node
+    the source x and y of view pixel (16 i, 16 j) in 1/256 px.  Raises for a spec the plan refuses."""
+    lib = _lib.load_library()
+    if view_w < 16 or view_h < 16 or view_w % 16 or view_h % 16:
+        raise _lib.RFError(_lib.RF_ERR_INVALID_ARG, "rf_dewarp_plan: view_w / view_h must be multiples of 16")
+    ny, nx = view_h // 16 + 1, view_w // 16 + 1
+    mesh = np.zeros((16, ny, nx, 2), np.int32)
+    views = C.c_int(0)
+    st = lib.rf_dewarp_plan(C.byref(spec), int(view_w), int(view_h), mesh.ctypes.data_as(C.POINTER(C.c_int32)), mesh.size, C.byref(views))
+    if st < 0:
+        raise _lib.RFError(st, "rf_dewarp_plan: a bad spec, a view beyond what the lens images, or a node beyond +-2^22")
+    return np.ascontiguousarray(mesh[:views.value])
+
+
+def dewarp_host(frame: np.ndarray, view_mesh, view_w: int, view_h: int, out: Optional[np.ndarray] = None) -> np.ndarray:
+    """rf_dewarp_host (host only, no GPU): one view (its nodes: view_mesh) of the BGR frame.  `out`: a (view_h, view_w, 3) uint8
+    array or view whose pixels are contiguous (any row pitch)."""
+    lib = _lib.load_library()
+    m = _mesh_array(view_mesh, view_w, view_h, 1)
+    if frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3:
+        raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
+    if frame.strides[2] != 1 or frame.strides[1] != 3:
+        frame = np.ascontiguousarray(frame)
+    if out is None:
+        out = np.empty((view_h, view_w, 3), np.uint8)
+    if out.dtype != np.uint8 or out.shape != (view_h, view_w, 3) or out.strides[2] != 1 or out.strides[1] != 3:
+        raise ValueError("out must be a (view_h, view_w, 3) uint8 array with contiguous pixels")
+    st = lib.rf_dewarp_host(m.ctypes.data, int(view_w), int(view_h), frame.ctypes.data, frame.shape[0], frame.shape[1], frame.strides[0],
+                            out.ctypes.data, out.strides[0])
+    if st < 0:
+        raise _lib.RFError(st, "rf_dewarp_host: bad mesh, frame or destination pitch")
+    return out
+
+
+def dewarp_map_face(face, view_mesh, view_w: int, view_h: int, net_h: int, net_w: int, edge: int = 0):
+    """rf_dewarp_map_face (host only, no GPU): the face (a Detection or 15 floats) of the view whose nodes are view_mesh moved into the
+    frame, 15 float32 -- or None when the edge rule drops it."""
+    lib = _lib.load_library()
+    m = _mesh_array(view_mesh, view_w, view_h, 1)
+    f, g = rf_face(), rf_face()
+    C.memmove(C.byref(f), _face_rows([face]).ctypes.data, 60)
+    st = lib.rf_dewarp_map_face(m.ctypes.data, int(view_w), int(view_h), int(net_h), int(net_w), int(edge), C.byref(f), C.byref(g))
+    if st < 0:
+        raise _lib.RFError(st, "rf_dewarp_map_face: bad mesh, net size or edge")
+    return np.frombuffer(bytes(g)[:60], np.float32).copy() if st else None
+
+
+def dewarp_merge_host(passes, mesh, view_w: int, view_h: int, net_h: int, net_w: int, nms_threshold: float, max_detections: int,
+                      vote: bool = False, max_faces: int = 0, edge: int = 0, cap: Optional[int] = None, spec=None):
+    """rf_dewarp_merge_host (host only, no GPU): mapping and merge of ONE frame -- passes[v]: the faces of view v in score order.
+    Returns (faces (j, 15) float32, the true number of heads, votes (j,) int32, src_view (j,) int32, truncated)."""
+    lib = _lib.load_library()
+    sp = spec if spec is not None else dewarp_spec(vote=vote, max_faces=max_faces, edge=edge)
+    md = int(max_detections)
+    if md < 1:
+        raise _lib.RFError(_lib.RF_ERR_INVALID_ARG, "rf_dewarp_merge_host: max_detections must be positive")
+    rows_ = [_face_rows(p) for p in passes]
+    m = _mesh_array(mesh, view_w, view_h, len(rows_))
+    flat = np.zeros((max(len(rows_), 1), md, 15), np.float32)
+    pc = (C.c_int * max(len(rows_), 1))()
+    for p, r in enumerate(rows_):
+        flat[p, :min(len(r), md)] = r[:md]
+        pc[p] = len(r)
+    cap = int(cap) if cap is not None else (sp.max_faces or md)
+    out = (rf_face * max(cap, 1))()
+    votes, src = (C.c_int * max(cap, 1))(), (C.c_int * max(cap, 1))()
+    count = C.c_int(0)
+    st = lib.rf_dewarp_merge_host(C.byref(sp), m.ctypes.data, int(view_w), int(view_h), len(rows_), int(net_h), int(net_w),
+                                  float(nms_threshold), md, flat.ctypes.data_as(C.POINTER(rf_face)), pc, out, cap, C.byref(count), votes, src)
+    if st < 0 and st != _lib.RF_ERR_TRUNCATED:
+        raise _lib.RFError(st, "rf_dewarp_merge_host: bad spec, mesh, net size or counts")
+    k = min(count.value, cap, sp.max_faces or md)
+    return (_faces_to_array(out, max(cap, 1))[:k].copy(), int(count.value), np.array(votes[:k], np.int32), np.array(src[:k], np.int32),
+            st == _lib.RF_ERR_TRUNCATED)
+
+
+class Dewarper:
+    """One camera's dewarped views on a detector (rf_dewarper_create): the shape of its frames, view_w x view_h (0 = the net size) and the
+    meshes of its views -- an rf_dewarp_spec to plan them from, or a ready (V, ny, nx, 2) int32 mesh -- uploaded once."""
+
+    def __init__(self, det: "RetinaFace", rows: int, cols: int, spec=None, mesh=None, view_w: int = 0, view_h: int = 0):
+        self._det, self._d = det, None
+        self.rows, self.cols = int(rows), int(cols)
+        self.view_w, self.view_h = int(view_w) or det.net_w, int(view_h) or det.net_h
+        self.spec = spec
+        if mesh is None:
+            if spec is None:
+                raise ValueError("a dewarper needs a spec or a mesh")
+            mesh = dewarp_plan(spec, self.view_w, self.view_h)
+        self.mesh = _mesh_array(mesh, self.view_w, self.view_h).reshape(-1, self.view_h // 16 + 1, self.view_w // 16 + 1, 2)
+        self.views = len(self.mesh)
+        d = C.c_void_p()
+        _lib.check(det._lib.rf_dewarper_create(det._h, self.rows, self.cols, int(view_w), int(view_h), self.views, self.mesh.ctypes.data,
+                                               C.byref(d)), det._h)
+        self._d = d
+
+    def close(self):
+        if self._d is not None and self._det._h:
+            self._det._lib.rf_dewarper_destroy(self._d)
+        self._d = None
 
 
 def enhance_spec(tile: int = 0, clip: int = 0, dark_below: int = 0) -> rf_enhance_spec:
@@ -1869,6 +2002,95 @@ class RetinaFace:
         dc = rows if int(k) & 1 else cols
         _lib.check(self._lib.rf_rotate_device(self._h, src_ptr, int(rows), int(cols), int(step if step is not None else 3 * cols), int(k),
                                               dst_ptr, int(dst_step if dst_step is not None else 3 * dc)), self._h)
+
+    # ------------------------------------------------------------------ fisheye detection
+    def dewarper(self, rows: int, cols: int, spec=None, mesh=None, view_w: int = 0, view_h: int = 0) -> Dewarper:
+        """rf_dewarper_create: a camera's views on this detector (see Dewarper)."""
+        return Dewarper(self, rows, cols, spec, mesh, view_w, view_h)
+
+    def detect_dewarped(self, imgs: Sequence[np.ndarray], dewarper: Dewarper, threshold: float = 0.5, vote: bool = False,
+                        max_faces: int = 0, edge: int = 0, return_votes: bool = False):
+        """rf_detect_dewarp_batch: every frame (of the dewarper's shape; None: an empty frame) is detected in the dewarper's views, made
+        on the device; the faces of all views are moved back through the meshes and merged on the device.  Returns per frame the
+        merged detections in SOURCE-FRAME pixels (anchor_index is -1); with return_votes also, per frame, how many candidates each
+        face merged and the view its head came from.  self.dewarp_counts holds the true merged counts."""
+        n = len(imgs)
+        ptrs = (C.c_void_p * max(n, 1))()
+        rows, cols, steps = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
+        keep = []
+        for i, im in enumerate(imgs):
+            if im is None or im.size == 0:
+                ptrs[i], rows[i], cols[i], steps[i] = None, 0, 0, 0
+                continue
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
+            if im.strides[2] != 1 or im.strides[1] != 3:
+                im = np.ascontiguousarray(im)
+            keep.append(im)
+            ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
+        return self._run_dewarp(self._lib.rf_detect_dewarp_batch, dewarper, ptrs, rows, cols, steps, n, threshold,
+                                dewarp_spec(vote=vote, max_faces=max_faces, edge=edge), return_votes, None)
+
+    def detect_dewarped_device(self, ptrs: Sequence[int], dewarper: Dewarper, threshold: float = 0.5, steps: Optional[Sequence[int]] = None,
+                               rows: Optional[Sequence[int]] = None, cols: Optional[Sequence[int]] = None, vote: bool = False,
+                               max_faces: int = 0, edge: int = 0, views_ptr: Optional[int] = None, return_votes: bool = False):
+        """rf_detect_dewarp_batch_device: detect_dewarped for frames resident in device memory (0 / None: an empty frame).  views_ptr:
+        device memory of n * V * view_h * view_w * 3 bytes that receives the views as dense frames."""
+        n = len(ptrs)
+        p = (C.c_void_p * max(n, 1))(*ptrs)
+        r = (C.c_int * max(n, 1))(*(rows if rows is not None else [dewarper.rows if q else 0 for q in ptrs]))
+        c = (C.c_int * max(n, 1))(*(cols if cols is not None else [dewarper.cols if q else 0 for q in ptrs]))
+        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in c[:n]]))
+        return self._run_dewarp(self._lib.rf_detect_dewarp_batch_device, dewarper, p, r, c, s, n, threshold,
+                                dewarp_spec(vote=vote, max_faces=max_faces, edge=edge), return_votes, views_ptr)
+
+    def _collect_dewarp(self, out, counts, votes, src, n, cap, return_votes):
+        kept = getattr(self, "tta_counts", None)             # _collect_tta's layout is this call's too; its counts are not
+        res = self._collect_tta(out, counts, votes, src, n, cap, return_votes)
+        self.dewarp_counts, self.tta_counts = self.tta_counts, kept
+        return res
+
+    def _run_dewarp(self, fn, dewarper, ptrs, rows, cols, steps, n, threshold, sp, return_votes, views_ptr):
+        cap = sp.max_faces or self.max_detections
+        out = (rf_face * max(n * cap, 1))()
+        counts = (C.c_int * max(n, 1))()
+        votes, src = (C.c_int * max(n * cap, 1))(), (C.c_int * max(n * cap, 1))()
+        extra = () if fn is self._lib.rf_detect_dewarp_batch else (views_ptr,)
+        st = _lib.check(fn(dewarper._d, ptrs, rows, cols, steps, n, float(threshold), C.byref(sp), out, cap, counts, votes, src, *extra), self._h)
+        self.truncated = st == _lib.RF_ERR_TRUNCATED
+        return self._collect_dewarp(out, counts, votes, src, n, cap, return_votes)
+
+    def dewarp_merge(self, dewarper: Dewarper, per_view_faces, vote: bool = False, max_faces: int = 0, edge: int = 0,
+                     cap_per_image: Optional[int] = None, return_votes: bool = False):
+        """rf_dewarp_merge_device: edge rule, mapping and merge of per-view faces the caller supplies -- per_view_faces[i][v]: the faces
+        of view v of frame i (a (j, 15) array, rows of 15 floats or Detections, at most max_detections).  No forward pass runs.
+        Returns as detect_dewarped; self.dewarp_counts as there."""
+        n = len(per_view_faces)
+        sp = dewarp_spec(vote=vote, max_faces=max_faces, edge=edge)
+        md = self.max_detections
+        if any(len(frame) != dewarper.views for frame in per_view_faces):
+            raise ValueError("per_view_faces: one list of %d views per frame" % dewarper.views)
+        passes = [_face_rows(f) for frame in per_view_faces for f in frame]
+        flat = np.zeros((max(len(passes), 1), md, 15), np.float32)
+        pc = (C.c_int * max(len(passes), 1))()
+        for p, r in enumerate(passes):
+            flat[p, :min(len(r), md)] = r[:md]
+            pc[p] = len(r)
+        cap = int(cap_per_image) if cap_per_image is not None else (sp.max_faces or md)
+        out = (rf_face * max(n * cap, 1))()
+        counts = (C.c_int * max(n, 1))()
+        votes, src = (C.c_int * max(n * cap, 1))(), (C.c_int * max(n * cap, 1))()
+        st = _lib.check(self._lib.rf_dewarp_merge_device(dewarper._d, n, C.byref(sp), flat.ctypes.data_as(C.POINTER(rf_face)), pc, out, cap,
+                                                         counts, votes, src), self._h)
+        self.truncated = st == _lib.RF_ERR_TRUNCATED
+        return self._collect_dewarp(out, counts, votes, src, n, cap, return_votes)
+
+    def dewarp_device(self, dewarper: Dewarper, view: int, src_ptr: int, dst_ptr: int, step: Optional[int] = None,
+                      dst_step: Optional[int] = None):
+        """rf_dewarp_device: the dewarp kernel on its own -- view `view` of the BGR frame at src_ptr (the dewarper's shape, row pitch
+        `step`, any alignment) into the destination (rows dst_step bytes apart, view_w * 3 bytes written).  Both in device memory."""
+        _lib.check(self._lib.rf_dewarp_device(dewarper._d, int(view), src_ptr, int(step if step is not None else 3 * dewarper.cols), dst_ptr,
+                                              int(dst_step if dst_step is not None else 3 * dewarper.view_w)), self._h)
 
     # ------------------------------------------------------------------ low-light detection
     def detect_enhanced(self, imgs: Sequence[np.ndarray], threshold: float = 0.5, tile: int = 0, clip: int = 0, dark_below: int = 0,
