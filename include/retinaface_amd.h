@@ -1232,6 +1232,16 @@ int rf_profile(rf_handle h, const void *const *d_bgr, int n, int iters, int cap,
  *   bench.py's `useful` HBM fraction = these bytes / kernel time / peak (the layer-wise alg_bytes of rf_profile also count tensors
  *   that never leave LDS).  Returns the number of launches. */
 int rf_profile_compulsory_bytes(rf_handle h, int n, int cap, double *bytes);
+/* rf_debug_resident_cap: process-wide test hook for the persistent kernels' tile walk.  A persistent launch with more tiles than the
+ *   chip keeps workgroups resident gets fewer workgroups than tiles, each walking several; with `workgroups` > 0 that resident count is
+ *   replaced by `workgroups`, so small inputs walk as well (1 = one workgroup walks every tile).  0 (the default) = off, the production
+ *   grids.  Launches that are not persistent keep their grids.  Only this call sets it: no environment variable does.  An engine that
+ *   replays a captured graph keeps the grids it was captured with.  Also clears the log below.
+ * rf_debug_grid_log: the (tiles, grid) pairs the persistent launches were given since the last rf_debug_resident_cap call, in call order
+ *   (for a multi-level launch: all levels' tiles and the grid before it is shared out to the levels).  Writes up to `cap` pairs and returns
+ *   how many were recorded; recording stops after 256.  Both are single-threaded test hooks: call them while no other thread launches. */
+void rf_debug_resident_cap(int workgroups);
+int rf_debug_grid_log(int cap, int *tiles, int *grid);
 
 /* Offline: pack <prototxt, caffemodel[, int8 table]> into a .rfw file (the analogue of the reference's
  * first-run engine serialisation, trtnetbase.cpp:231-243).  int8_table may be NULL. */

@@ -1863,6 +1863,13 @@ long rf_debug_activation(rf_handle h, const char *blob_name, int image, float *d
     return st == RF_OK ? r : st;
 }
 
+void rf_debug_resident_cap(int workgroups) { rf::debug_resident_cap(workgroups); }
+
+int rf_debug_grid_log(int cap, int *tiles, int *grid) {
+    if (cap < 0 || (cap > 0 && (!tiles || !grid))) return RF_ERR_INVALID_ARG;
+    return rf::debug_grid_log(cap, tiles, grid);
+}
+
 int rf_profile(rf_handle h, const void *const *d_bgr, int n, int iters, int cap, const char **names, const char **kernels,
                float *avg_ms, double *alg_bytes, double *macs) {
     if (!h || !d_bgr) return RF_ERR_INVALID_ARG;

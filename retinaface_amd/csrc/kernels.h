@@ -39,7 +39,11 @@ void bind_launch_device(int device);
 // int8 engines: 0 when v_cvt_pk_u8_f32 on the bound device rounds to nearest even and saturates (what the requantising epilogues rely on),
 // 1 when it does not (cached per device), -1 when the probe could not run (a runtime error: not cached)
 int cvt_pk_u8_selfcheck();
-constexpr int kMaxDevices = 64;      // device ordinals a process may use (per-device launch state is sized by it; engine / multi.cpp enforce it)
+// Test hooks (C ABI rf_debug_resident_cap / rf_debug_grid_log): cap the resident workgroups the persistent launches size their grids by
+// (0 = off), and read back the (tiles, grid) pairs handed out since the cap was last set.  Process-wide, single-threaded use.
+void debug_resident_cap(int workgroups);
+int debug_grid_log(int cap, int *tiles, int *grid);
+constexpr int kMaxDevices = 64;     // device ordinals a process may use (per-device launch state is sized by it; engine / multi.cpp enforce it)
 
 // One input frame: CV_8UC3 BGR, row y at ptr + y*step (cv::Mat data/step; RetinaFace.cpp:594).
 struct FrameDesc {

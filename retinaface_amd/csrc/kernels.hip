@@ -146,8 +146,32 @@ static int num_cus() {
 }
 // Below `min_rounds` x resident tiles the hardware dispatcher's dynamic one-tile-per-workgroup schedule is at least as
 // good as walking two tiles in sequence, so the grid stays one workgroup per tile.
+// Test hook (rf_debug_resident_cap, tests/test_tile_walk_gpu.py): a positive cap stands in for the chip's resident workgroups, so
+// launches walk tiles at sizes where the chip would give every tile its own workgroup.  0 = off.  Every grid handed out since the
+// cap was last set is logged (first kGridLogCap pairs; single-threaded test hook: the slot counter alone is atomic).
+constexpr int kGridLogCap = 256;
+static std::atomic<int> g_resident_cap{0};
+static std::atomic<int> g_grid_log_n{0};
+static int g_grid_log[kGridLogCap][2];
+void debug_resident_cap(int workgroups) {
+    g_resident_cap.store(workgroups > 0 ? workgroups : 0, std::memory_order_relaxed);
+    g_grid_log_n.store(0, std::memory_order_relaxed);
+}
+int debug_grid_log(int cap, int *tiles, int *grid) {
+    int n = g_grid_log_n.load(std::memory_order_relaxed);
+    if (n > kGridLogCap) n = kGridLogCap;
+    for (int i = 0; i < n && i < cap; i++) { tiles[i] = g_grid_log[i][0]; grid[i] = g_grid_log[i][1]; }
+    return n;
+}
 static int persistent_grid(int tiles, int resident_per_cu) {
-    return persistent_grid_size(tiles, num_cus() * (resident_per_cu > 0 ? resident_per_cu : 1), 1.0f);      // min_rounds 1: measured on MI355X
+    const int g = persistent_grid_capped(tiles, num_cus() * (resident_per_cu > 0 ? resident_per_cu : 1), 1.0f,      // min_rounds 1: measured on MI355X
+                                         g_resident_cap.load(std::memory_order_relaxed));
+    const int i = g_grid_log_n.load(std::memory_order_relaxed);
+    if (i < kGridLogCap) {
+        const int slot = g_grid_log_n.fetch_add(1, std::memory_order_relaxed);
+        if (slot < kGridLogCap) { g_grid_log[slot][0] = tiles; g_grid_log[slot][1] = g; }
+    }
+    return g;
 }
 template <typename F> static int resident_per_cu(F kern, size_t lds_bytes) {
     int nb = 0;

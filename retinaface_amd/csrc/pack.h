@@ -137,6 +137,11 @@ RF_HD inline int persistent_grid_size(int tiles, int resident, float min_rounds)
     const int rounds = (tiles + resident - 1) / resident;
     return (tiles + rounds - 1) / rounds;
 }
+// The same under the test hook rf_debug_resident_cap (kernels.hip persistent_grid): cap 0 = off, the production grid; a positive cap
+// stands in for the chip's resident workgroups, so the launch walks ceil(tiles / cap) rounds on at most `cap` workgroups.
+RF_HD inline int persistent_grid_capped(int tiles, int resident, float min_rounds, int cap) {
+    return cap > 0 ? persistent_grid_size(tiles, cap, 1.0f) : persistent_grid_size(tiles, resident, min_rounds);
+}
 
 // Image sharding of one detectBatchImages() call over G devices (multi.cpp; the same rule as retinaface_amd/shard.py
 // shard_range): contiguous slices of ceil(n / G) images, trailing devices may get fewer or none.  lo[g] .. lo[g + 1].

@@ -1070,6 +1070,20 @@ def zoom_host(frame: np.ndarray, z: int, x0: int = 0, y0: int = 0, tw: Optional[
     return out
 
 
+def debug_resident_cap(workgroups: int = 0) -> None:
+    """rf_debug_resident_cap: process-wide test hook.  A positive value replaces the chip's resident workgroup count in the persistent
+    launches' grid rule, so small inputs walk several tiles per workgroup; 0 = the production grids.  Clears the grid log."""
+    _lib.load_library().rf_debug_resident_cap(int(workgroups))
+
+
+def debug_grid_log() -> List[tuple]:
+    """rf_debug_grid_log: the (tiles, grid) pairs the persistent launches were given since the last debug_resident_cap(), in call order."""
+    cap = 256
+    tiles, grid = (C.c_int * cap)(), (C.c_int * cap)()
+    n = _lib.check(_lib.load_library().rf_debug_grid_log(cap, tiles, grid))
+    return [(tiles[i], grid[i]) for i in range(min(n, cap))]
+
+
 def _faces_to_array(buf, n: int) -> np.ndarray:
     return np.ctypeslib.as_array(C.cast(buf, C.POINTER(C.c_float)), shape=(n, 15)).copy()
 

@@ -159,6 +159,17 @@ int main() {
             if (g < 1 || g > tiles || (!one_each && g > resident) || (one_each && g != tiles) || hi - lo > 1) { printf("FAIL persistent_grid_size(%d, %d, %.1f) = %d\n", tiles, resident, mr, g); bad++; }
         }
     }
+    // the test hook's cap: 0 = the production value, 1 = one workgroup, at or above the tile count = one workgroup per tile, and never
+    // more workgroups than the cap in between
+    for (int tiles : {1, 6, 18, 767, 2508, 25088}) for (int resident : {256, 1792}) {
+        if (persistent_grid_capped(tiles, resident, 1.0f, 0) != persistent_grid_size(tiles, resident, 1.0f) ||
+            persistent_grid_capped(tiles, resident, 1.0f, 1) != 1 || persistent_grid_capped(tiles, resident, 1.0f, tiles) != tiles ||
+            persistent_grid_capped(tiles, resident, 1.0f, tiles + 5) != tiles) { printf("FAIL persistent_grid_capped(%d, %d)\n", tiles, resident); bad++; }
+        for (int cap : {2, 3, 11}) {
+            const int g = persistent_grid_capped(tiles, resident, 1.0f, cap);
+            if (g < 1 || g > cap || g > tiles || (tiles > cap && g >= tiles)) { printf("FAIL persistent_grid_capped(%d, %d, cap %d) = %d\n", tiles, resident, cap, g); bad++; }
+        }
+    }
     // LDS rows: 16-byte aligned, at least as wide as asked, 32 mod 64 bytes
     if (lds_row<unsigned short>(64) != 80 || lds_row<unsigned short>(16) != 16 || lds_row<unsigned short>(32) != 48 || lds_row<float>(64) != 72 ||
         lds_row<signed char>(64) != 96 || lds_row<unsigned short>(48) != 48) { printf("FAIL lds_row\n"); bad++; }

@@ -4,7 +4,8 @@ The launch's inputs are the device's own stored tensors (debug_activation, or th
 (rf_plan_folded), and every element of every stored output must lie inside the interval the arithmetic allows -- no element excluded,
 nothing relative to the tensor's range, and therefore valid on weights nobody trained (`degenerate`, `ragged`).  Three distinct frames per
 call, all three judged: every launch indexes images beyond the first.  (A launch walks tiles across images only where it has more tiles
-than resident workgroups; test_gpu_parity.py's batch-composition tests hold that end to end at full size.)  Sizes: 64 x 96 (every tile of every kernel partial, a 2 x 3
+than resident workgroups, which none does at these sizes: test_tile_walk_gpu.py forces the walk at the same sizes and holds every stored
+tensor to the bytes judged here, and test_gpu_parity.py's batch-composition tests hold the production grids end to end at full size.)  Sizes: 64 x 96 (every tile of every kernel partial, a 2 x 3
 stride-32 map), 96 x 160 (odd tile counts, 3 x 5), 352 x 608 (mnet25: the odd-partial-tile size, and the only size here whose stride-8
 map is large enough for the fp16 engine's warp-specialised rf_c1_aggr instance; mnet-deconv-0517 runs that one launch there).
 After each eager engine is judged, the default engine (graph replay) must return byte-identical detections on the same frames.
