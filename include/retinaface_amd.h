@@ -1242,6 +1242,11 @@ int rf_profile_compulsory_bytes(rf_handle h, int n, int cap, double *bytes);
  *   how many were recorded; recording stops after 256.  Both are single-threaded test hooks: call them while no other thread launches. */
 void rf_debug_resident_cap(int workgroups);
 int rf_debug_grid_log(int cap, int *tiles, int *grid);
+/* rf_debug_face_bands: test hook, host only (no handle, no GPU call).  The crop rows one workgroup of the face-crop kernels covers for
+ *   `crop_size` in [16, 512] and `format` (RF_FACES_*) -- the band of rf_align_device, the face-batch calls and the gallery -- and the
+ *   luma rows the quality kernel keeps in LDS for that crop size (each of its bands brings ring_rows - 2 new rows).  Either pointer may be
+ *   NULL.  Returns RF_OK, or RF_ERR_INVALID_ARG for a crop size out of range or an unknown format. */
+int rf_debug_face_bands(int crop_size, int format, int *band_rows, int *ring_rows);
 
 /* Offline: pack <prototxt, caffemodel[, int8 table]> into a .rfw file (the analogue of the reference's
  * first-run engine serialisation, trtnetbase.cpp:231-243).  int8_table may be NULL. */

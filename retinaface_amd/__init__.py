@@ -14,7 +14,7 @@ from .detector import (PRECISION_FP16, PRECISION_FP32, PRECISION_INT8, QUALITY_D
 from .detector import (FACE_DTYPE, TRACK_BEST, TRACK_CONFIRMED, TRACK_DTYPE, TRACK_NEW, TRACK_OVERFLOW, TRACK_TAG_DTYPE, TRACK_UNTRACKED,  # noqa: F401
                        Tracker, track_spec, track_step)
 from .detector import SHOT_DTYPE, shot_resolve  # noqa: F401
-from .detector import debug_grid_log, debug_resident_cap  # noqa: F401
+from .detector import debug_face_bands, debug_grid_log, debug_resident_cap  # noqa: F401
 from .detector import MOTION_DTYPE, motion_spec, track_predict  # noqa: F401
 from .detector import tta_map_face, tta_merge_host, tta_spec  # noqa: F401
 from .detector import rot_map_face, rot_merge_host, rot_spec, rotate_host  # noqa: F401

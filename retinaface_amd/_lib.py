@@ -368,6 +368,7 @@ SYMBOLS = {
     "rf_profile_compulsory_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _PP(C.c_double)]),
     "rf_debug_resident_cap": (None, [C.c_int]),
     "rf_debug_grid_log": (C.c_int, [C.c_int, _PP(C.c_int), _PP(C.c_int)]),
+    "rf_debug_face_bands": (C.c_int, [C.c_int, C.c_int, _PP(C.c_int), _PP(C.c_int)]),
     "rf_convert_model": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p]),
     "rf_plan_cache_probe": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, _PP(C.c_size_t)]),
     "rf_plan_folded": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, _PP(C.c_float), C.c_size_t, _PP(C.c_float),

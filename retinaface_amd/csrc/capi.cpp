@@ -1870,6 +1870,14 @@ int rf_debug_grid_log(int cap, int *tiles, int *grid) {
     return rf::debug_grid_log(cap, tiles, grid);
 }
 
+int rf_debug_face_bands(int crop_size, int format, int *band_rows, int *ring_rows) {
+    if (crop_size < rf::kAlignMinCrop || crop_size > rf::kAlignMaxCrop) return RF_ERR_INVALID_ARG;
+    if (format != RF_FACES_U8_HWC && format != RF_FACES_F16_CHW && format != RF_FACES_F32_CHW) return RF_ERR_INVALID_ARG;
+    if (band_rows) *band_rows = rf::face_batch_band_rows(crop_size, format);
+    if (ring_rows) *ring_rows = rf::face_quality_ring_rows(crop_size);
+    return RF_OK;
+}
+
 int rf_profile(rf_handle h, const void *const *d_bgr, int n, int iters, int cap, const char **names, const char **kernels,
                float *avg_ms, double *alg_bytes, double *macs) {
     if (!h || !d_bgr) return RF_ERR_INVALID_ARG;

@@ -1084,6 +1084,14 @@ def debug_grid_log() -> List[tuple]:
     return [(tiles[i], grid[i]) for i in range(min(n, cap))]
 
 
+def debug_face_bands(crop_size: int, format: int) -> tuple:
+    """rf_debug_face_bands: host-only test hook.  (band_rows, ring_rows): the crop rows one workgroup of the face-crop kernels covers for
+    this crop size and format (RF_FACES_*: 0 u8 HWC, 1 f16 CHW, 2 f32 CHW), and the luma rows the quality kernel keeps in LDS."""
+    band, ring = C.c_int(), C.c_int()
+    _lib.check(_lib.load_library().rf_debug_face_bands(int(crop_size), int(format), C.byref(band), C.byref(ring)))
+    return band.value, ring.value
+
+
 def _faces_to_array(buf, n: int) -> np.ndarray:
     return np.ctypeslib.as_array(C.cast(buf, C.POINTER(C.c_float)), shape=(n, 15)).copy()
 
