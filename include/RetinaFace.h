@@ -159,6 +159,17 @@ public:
     vector<rf_track_motion> readMotion(rf_tracker tracker, int stream);
     static rf_face predictTrack(const rf_track &track, const rf_track_motion &motion, int ahead = 1, const rf_motion_spec *spec = nullptr);
 
+    /* additive: followed tracks (rf_tracker_enable_follow / rf_detect_track_follow_batch / rf_track_follow_batch): enableFollow() gives a
+       tracker a luma template per track (spec may be nullptr: radius 8, max_mad 16, max_run 8); such a tracker is stepped with
+       detectTrackFollow() on key frames -- detectTracked() plus the templates of the matched and opened tracks -- and with followTracks()
+       on the frames in between, which runs no forward pass: every live track's box is moved to where a block-matching search finds its
+       template in the new frame.  followTracks() fills lastBatchResult()[i] with the followed faces of stream streams[i] (slot order,
+       the score copied), lastTrackTags()[i] with their tags (RF_TRACK_FOLLOWED) and lastEndedTracks()[i].  Each stream at most once per
+       call. */
+    void enableFollow(rf_tracker tracker, const rf_follow_spec *spec = nullptr);
+    void detectTrackFollow(const vector<cv::Mat> &imgs, rf_tracker tracker, const vector<int> &streams, float threshold = 0.5);
+    void followTracks(const vector<cv::Mat> &imgs, rf_tracker tracker, const vector<int> &streams);
+
     /* additive: best-shot gallery (rf_tracker_enable_shots / rf_detect_track_shots_batch): enableShots() gives a tracker a gallery of
        face-batch crops (spec as detectFaceBatch(); capacity is not used) and returns the bytes of one shot; from then on the tracker is
        stepped with detectTrackShots(), which is detectTracked() plus the shots of the tracks that end: lastShots()[i] holds

@@ -815,6 +815,105 @@ int rf_tracker_enable_motion(rf_tracker tracker, const rf_motion_spec *mspec);
 /* Host copy of the first min(cap, max_tracks) motion records of a stream.  Returns max_tracks; RF_ERR_INVALID_ARG without motion. */
 int rf_tracker_read_motion(rf_tracker tracker, int stream, rf_track_motion *out, int cap);
 
+/* ---- Followed face tracks: a tracker may keep, per track slot, a template of the face's luma taken on a KEY frame (a frame with
+ * detections) and, on the frames in between, measure from the new frame's pixels -- without a forward pass -- where each tracked face
+ * went: a block-matching search over luma cell means moves the track's box by whole cells (DESIGN.md "Followed tracks" holds the
+ * definition; tests/follow_ref.py restates it in numpy; every result is byte-exact against it).  All arithmetic is integer, except one
+ * fp32 add per coordinate of a moved box, never contracted.  G = 32; luma Y = (29 B + 150 G + 77 R + 128) >> 8.
+ *   geometry   of a box (x1, y1, x2, y2; fp32, source-frame pixels): every coordinate must be finite and is clamped to [-4096, 8192];
+ *              ix = floor(.), W = ix2 - ix1 + 1, H likewise; invalid unless W >= 1 and H >= 1.  Cell edge q = max(1, (max(W, H) + G - 1) / G),
+ *              origin ox = floordiv(ix1 + ix2 + 1 - G q, 2), oy likewise.
+ *   cell value at cell origin (cx, cy): (sum of Y over the q x q pixels (cx + x, cy + y) + q q / 2) / (q q), every pixel coordinate clamped
+ *              into the frame (replicated border): nothing outside the frame is read, whatever the row step or base pointer.
+ *   template   of a slot: the G x G cell values (u8, row-major) at (ox + i q, oy + j q).
+ *   record     one rf_track_follow per slot; a free slot has the all-zero record.  dx, dy are pixels (du q, dv q).
+ *   search     in a new frame, radius R: the window is the (G + 2R)^2 cell values at (ox + (i - R) q, oy + (j - R) q); for du, dv in [-R, R]
+ *              SAD(du, dv) = sum |T[j][i] - Wn[j + dv + R][i + du + R]|.  A candidate is eligible only if the moved centre
+ *              (ox + du q + 16 q, oy + dv q + 16 q) lies inside the frame.  The winner is the eligible candidate with the smallest 64-bit
+ *              key SAD << 32 | (du^2 + dv^2) << 16 | ((dv + R)(2R + 1) + du + R): ties go to the smaller motion, then raster order, so a
+ *              flat frame answers "did not move".  The winner is accepted when SAD <= max_mad G G.
+ *   key step   rf_track_step, unchanged (a NULL / 0 x 0 frame has no faces); then every slot the step left free gets the zero record, and
+ *              for every face the step tagged with slot >= 0 the slot's template is retaken from this image at the track's `last` box
+ *              and its record becomes {1, 0, q, ox, oy, 0, 0, 0} -- the zero record for an invalid geometry.  Live tracks nobody
+ *              matched keep template and record.
+ *   follow step  f = the stream's frame counter, which advances by one.  Every live slot on its own: it is attempted when valid is set,
+ *              run < max_run and the frame is not NULL / 0 x 0.  Accepted: every x coordinate of `last` (x1, x2, px[0..4]) gets one
+ *              fp32 add of (float)(du q), every y coordinate of (float)(dv q); the score is copied; ox, oy move by the same integers;
+ *              run += 1; sad, dx, dy are stored; hits, missed, last_frame and best are untouched.  Otherwise missed += 1, sad = the
+ *              winner's SAD or -1 (no attempt, no eligible candidate), dx = dy = 0, and the track ends when missed > max_missed: ended
+ *              list in ascending slot order, slot freed, record zeroed.  No tracks are opened.  The output list of the image is the
+ *              accepted slots in ascending order: out = the moved `last`, tag as rf_track_step's for frame f with flag RF_TRACK_FOLLOWED.
+ * The template is taken only at key steps: every search compares against the same key-frame template on a lattice that moves by whole
+ * cells, so quantisation (at most q / 2 per axis) does not accumulate; max_run bounds how long appearance may drift. */
+enum { RF_TRACK_FOLLOWED = 32 };
+typedef struct rf_follow_spec {   /* 20 bytes; a field of 0 means its default, a NULL spec all defaults */
+    uint32_t struct_size;   /* sizeof(rf_follow_spec) */
+    int32_t radius;         /* search radius in cells, 1..16; 0 = 8 */
+    int32_t max_mad;        /* largest accepted mean absolute difference per cell, 1..255; 0 = 16 */
+    int32_t max_run;        /* most follow steps between two key steps, 1..65536; 0 = 8 */
+    int32_t reserved;       /* must be 0 */
+} rf_follow_spec;
+typedef struct rf_track_follow { int32_t valid, run, q, ox, oy, sad, dx, dy; } rf_track_follow;   /* 32 bytes, no padding */
+
+/* Host only, no GPU, no handle: the code the kernels run, compiled for the host.
+ * rf_follow_geometry: out = {q, ox, oy}; returns 1 (valid), 0 (invalid: out is zero) or RF_ERR_INVALID_ARG (NULL argument).
+ * rf_follow_template: the 1024 template bytes of the lattice (q, ox, oy) in a frame (rows of `step` bytes, step >= cols * 3).
+ * rf_follow_search: out = {state, sad, du, dv}; state 1 = no eligible candidate (sad -1), 2 = the winner.  q 1..385, radius 1..16.
+ * rf_track_step_follow_key / rf_track_step_follow: the two whole steps on a caller-held table, max_tracks records and
+ * max_tracks x 1024 template bytes (all zero to start).  The follow step writes the first min(*count, cap) accepted faces and tags;
+ * *count and *ended_count are the true numbers.  Returns as rf_track_step: 0, RF_ERR_TRUNCATED (a full table, a cut output or ended
+ * list) or RF_ERR_INVALID_ARG, which changes nothing. */
+int rf_follow_geometry(const float box[4], int32_t out[3]);
+int rf_follow_template(const uint8_t *bgr, int rows, int cols, int step, int q, int ox, int oy, uint8_t *tpl);
+int rf_follow_search(const uint8_t *bgr, int rows, int cols, int step, const uint8_t *tpl, int q, int ox, int oy, int radius, int32_t out[4]);
+int rf_track_step_follow_key(const rf_track_spec *spec, rf_track *table, rf_track_follow *records, uint8_t *templates, int64_t *frames,
+                             int64_t *next_id, const uint8_t *bgr, int rows, int cols, int step, const rf_face *faces, int count,
+                             float coord_scale, const rf_face_quality *quality, int max_faces, rf_track_tag *tags, rf_track *ended,
+                             int cap_ended, int *ended_count);
+int rf_track_step_follow(const rf_track_spec *spec, const rf_follow_spec *fspec, rf_track *table, rf_track_follow *records,
+                         const uint8_t *templates, int64_t *frames, const uint8_t *bgr, int rows, int cols, int step, rf_face *out,
+                         rf_track_tag *tags, int cap, int *count, rf_track *ended, int cap_ended, int *ended_count);
+
+/* Gives the tracker follow for its lifetime: n_streams x max_tracks records and templates (1024 bytes each, at most RF_SHOT_MAX_BYTES in
+ * all) in device memory.  Refused with RF_ERR_INVALID_ARG, changing nothing, for a bad spec, a tracker that has stepped a frame (any
+ * stream's frame counter non-zero) or one that has follow already.  It does not compose yet: a tracker that has a gallery or motion is
+ * refused here, and rf_tracker_enable_shots / rf_tracker_enable_motion refuse a tracker that has follow.  Every tracked call without
+ * "follow" in its name then refuses the tracker (RF_ERR_INVALID_ARG, nothing changes): it would leave a template stale.  In a
+ * follow call each stream may appear at most once (RF_ERR_INVALID_ARG otherwise); an image of stream -1 is skipped.
+ * rf_tracker_reset and rf_tracker_flush zero the records of the slots they free. */
+int rf_tracker_enable_follow(rf_tracker tracker, const rf_follow_spec *spec);
+/* Host copy of the first min(cap, max_tracks) records and templates (1024 bytes per slot; zeros where the record is not valid) of a
+ * stream; each may be NULL.  Returns max_tracks; RF_ERR_INVALID_ARG without follow. */
+int rf_tracker_read_follow(rf_tracker tracker, int stream, rf_track_follow *records, uint8_t *templates, int cap);
+
+/* Key steps.  rf_track_follow_update_device: rf_track_update_device over faces the caller supplies (host memory, in source-frame pixels
+ * after coord_scale) plus the frames they were found in (device memory), with the keep rule behind the track launch; what a tiled
+ * caller uses.  rf_detect_track_follow_batch_device / rf_detect_track_follow_batch: rf_detect_track_batch_device / rf_detect_track_batch
+ * plus the keep rule, with no host synchronisation between detection and the keep launch; out, counts, tags, ended lists and the table
+ * are the bytes of the plain tracked call. */
+int rf_track_follow_update_device(rf_handle h, rf_tracker tracker, const void *const *d_bgr, const int *rows, const int *cols, const int *steps,
+                                  int n, const int *stream_of_image, const rf_face *faces, int cap_per_image, const int *counts,
+                                  const float *coord_scale, const rf_face_quality *quality, rf_track_tag *tags, rf_track *ended,
+                                  int cap_ended, int *ended_counts);
+int rf_detect_track_follow_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                        float threshold, rf_face *out, int cap_per_image, int *counts, rf_tracker tracker,
+                                        const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_counts);
+int rf_detect_track_follow_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                                 float threshold, rf_face *out, int cap_per_image, int *counts, rf_tracker tracker,
+                                 const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_counts);
+/* Follow steps: no forward pass runs.  Frames in device memory (rf_track_follow_device) or host memory (rf_track_follow_batch: uploaded
+ * densely, as the redacting host call uploads them).  out / tags: image i's followed faces at out + i * cap_per_image (the first
+ * min(counts[i], cap_per_image)); counts[i]: the true number.  A cut output or ended list returns RF_ERR_TRUNCATED. */
+int rf_track_follow_device(rf_handle h, rf_tracker tracker, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                           const int *stream_of_image, rf_face *out, int cap_per_image, int *counts, rf_track_tag *tags, rf_track *ended,
+                           int cap_ended, int *ended_counts);
+int rf_track_follow_batch(rf_handle h, rf_tracker tracker, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                          const int *stream_of_image, rf_face *out, int cap_per_image, int *counts, rf_track_tag *tags, rf_track *ended,
+                          int cap_ended, int *ended_counts);
+/* Measurement hook: hipEvent time (ms) of the search and step launches of the most recent rf_track_follow_device call, on their stream
+ * (the upload and the copy-out are outside).  RF_ERR_INVALID_ARG before the first such call. */
+int rf_follow_last_launch_ms(rf_handle h, float *ms);
+
 /* ---- Flip test-time augmentation with box voting: every frame is detected as it is and mirrored left-right, the mirrored faces are
  * moved back into the frame, and overlapping boxes of both passes are merged on the device into a score-weighted mean (DESIGN.md "Flip
  * test-time augmentation" holds the definition; tests/tta_ref.py restates it in numpy; every result is byte-exact against it):

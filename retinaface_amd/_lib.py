@@ -85,6 +85,16 @@ class rf_track_motion(C.Structure):
     _fields_ = [("vx", C.c_float), ("vy", C.c_float), ("samples", C.c_int32), ("reserved", C.c_int32)]
 
 
+class rf_follow_spec(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("radius", C.c_int32), ("max_mad", C.c_int32), ("max_run", C.c_int32), ("reserved", C.c_int32)]
+
+
+class rf_track_follow(C.Structure):
+    _fields_ = [("valid", C.c_int32), ("run", C.c_int32), ("q", C.c_int32), ("ox", C.c_int32), ("oy", C.c_int32), ("sad", C.c_int32),
+                ("dx", C.c_int32), ("dy", C.c_int32)]
+
+
+RF_TRACK_FOLLOWED = 32
 RF_SHOT_NONE, RF_SHOT_STORED, RF_SHOT_LAUNCH = 0, 1, 2
 RF_SHOT_MAX_BYTES = 1 << 30
 
@@ -245,6 +255,33 @@ SYMBOLS = {
     "rf_track_predict": (C.c_int, [_PP(rf_motion_spec), _PP(rf_track), _PP(rf_track_motion), C.c_int, _PP(rf_face)]),
     "rf_tracker_enable_motion": (C.c_int, [C.c_void_p, _PP(rf_motion_spec)]),
     "rf_tracker_read_motion": (C.c_int, [C.c_void_p, C.c_int, _PP(rf_track_motion), C.c_int]),
+    "rf_follow_geometry": (C.c_int, [_PP(C.c_float), _PP(C.c_int32)]),
+    "rf_follow_template": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "rf_follow_search": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _PP(C.c_int32)]),
+    "rf_track_step_follow_key": (C.c_int, [_PP(rf_track_spec), _PP(rf_track), _PP(rf_track_follow), C.c_void_p, _PP(C.c_int64), _PP(C.c_int64),
+                                           C.c_void_p, C.c_int, C.c_int, C.c_int, _PP(rf_face), C.c_int, C.c_float, _PP(rf_face_quality),
+                                           C.c_int, _PP(rf_track_tag), _PP(rf_track), C.c_int, _PP(C.c_int)]),
+    "rf_track_step_follow": (C.c_int, [_PP(rf_track_spec), _PP(rf_follow_spec), _PP(rf_track), _PP(rf_track_follow), C.c_void_p,
+                                       _PP(C.c_int64), C.c_void_p, C.c_int, C.c_int, C.c_int, _PP(rf_face), _PP(rf_track_tag), C.c_int,
+                                       _PP(C.c_int), _PP(rf_track), C.c_int, _PP(C.c_int)]),
+    "rf_tracker_enable_follow": (C.c_int, [C.c_void_p, _PP(rf_follow_spec)]),
+    "rf_tracker_read_follow": (C.c_int, [C.c_void_p, C.c_int, _PP(rf_track_follow), C.c_void_p, C.c_int]),
+    "rf_track_follow_update_device": (C.c_int, [C.c_void_p, C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                                _PP(C.c_int), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_float), _PP(rf_face_quality),
+                                                _PP(rf_track_tag), _PP(rf_track), C.c_int, _PP(C.c_int)]),
+    "rf_detect_track_follow_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                                      C.c_float, _PP(rf_face), C.c_int, _PP(C.c_int), C.c_void_p, _PP(C.c_int),
+                                                      _PP(rf_track_tag), _PP(rf_track), C.c_int, _PP(C.c_int)]),
+    "rf_detect_track_follow_batch": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                               C.c_float, _PP(rf_face), C.c_int, _PP(C.c_int), C.c_void_p, _PP(C.c_int),
+                                               _PP(rf_track_tag), _PP(rf_track), C.c_int, _PP(C.c_int)]),
+    "rf_track_follow_device": (C.c_int, [C.c_void_p, C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                         _PP(C.c_int), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(rf_track_tag), _PP(rf_track), C.c_int,
+                                         _PP(C.c_int)]),
+    "rf_track_follow_batch": (C.c_int, [C.c_void_p, C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                        _PP(C.c_int), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(rf_track_tag), _PP(rf_track), C.c_int,
+                                        _PP(C.c_int)]),
+    "rf_follow_last_launch_ms": (C.c_int, [C.c_void_p, _PP(C.c_float)]),
     "rf_detect_track_shots_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
                                                      C.c_float, _PP(rf_face), C.c_int, _PP(C.c_int), C.c_void_p, _PP(C.c_int),
                                                      _PP(rf_track_tag), _PP(rf_track), C.c_int, _PP(C.c_int), _PP(rf_face_gate),

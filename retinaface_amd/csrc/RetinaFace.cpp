@@ -193,6 +193,52 @@ void RetinaFace::detectTracked(const vector<cv::Mat> &imgs, rf_tracker tracker, 
     }
 }
 
+void RetinaFace::enableFollow(rf_tracker tracker, const rf_follow_spec *spec) {
+    check(rf_tracker_enable_follow(tracker, spec), h_, "RetinaFace::enableFollow");
+}
+
+// key = true: rf_detect_track_follow_batch; false: rf_track_follow_batch (the faces are the followed ones)
+static void follow_call(rf_handle h, bool key, const vector<cv::Mat> &imgs, rf_tracker tracker, const vector<int> &streams, float threshold, int cap,
+                        vector<vector<FaceDetectInfo>> *batch, vector<vector<rf_track_tag>> *trackTags, vector<vector<rf_track>> *trackEnded) {
+    const int n = (int)imgs.size();
+    if ((int)streams.size() != n) throw std::runtime_error("RetinaFace: one stream per image");
+    batch->assign(n, vector<FaceDetectInfo>());
+    trackTags->assign(n, vector<rf_track_tag>());
+    trackEnded->assign(n, vector<rf_track>());
+    if (n == 0) return;
+    const int capEnded = 256;                          // a table holds at most 256 tracks: no list is ever cut
+    vector<const uint8_t *> ptrs(n);
+    vector<int> rows(n), cols(n), steps(n), counts(n, 0), endedCounts(n, 0);
+    for (int i = 0; i < n; i++) {
+        ptrs[i] = imgs[i].empty() ? nullptr : imgs[i].data;
+        rows[i] = imgs[i].rows; cols[i] = imgs[i].cols; steps[i] = (int)(size_t)imgs[i].step;
+    }
+    vector<rf_face> faces((size_t)n * cap);
+    vector<rf_track_tag> tags((size_t)n * cap);
+    vector<rf_track> ended((size_t)n * capEnded);
+    const int st = key ? rf_detect_track_follow_batch(h, ptrs.data(), rows.data(), cols.data(), steps.data(), n, threshold, faces.data(), cap,
+                                                      counts.data(), tracker, streams.data(), tags.data(), ended.data(), capEnded, endedCounts.data())
+                       : rf_track_follow_batch(h, tracker, ptrs.data(), rows.data(), cols.data(), steps.data(), n, streams.data(), faces.data(), cap,
+                                               counts.data(), tags.data(), ended.data(), capEnded, endedCounts.data());
+    check(st, h, key ? "RetinaFace::detectTrackFollow" : "RetinaFace::followTracks");
+    for (int i = 0; i < n; i++) {
+        const int k = counts[i] < cap ? counts[i] : cap;
+        (*batch)[i].resize(k);
+        if (k) memcpy((*batch)[i].data(), &faces[(size_t)i * cap], (size_t)k * sizeof(rf_face));
+        (*trackTags)[i].assign(tags.begin() + (size_t)i * cap, tags.begin() + (size_t)i * cap + k);
+        const int e = endedCounts[i] < capEnded ? endedCounts[i] : capEnded;
+        (*trackEnded)[i].assign(ended.begin() + (size_t)i * capEnded, ended.begin() + (size_t)i * capEnded + e);
+    }
+}
+
+void RetinaFace::detectTrackFollow(const vector<cv::Mat> &imgs, rf_tracker tracker, const vector<int> &streams, float threshold) {
+    follow_call(h_, true, imgs, tracker, streams, threshold, maxDet_, &lastBatch_, &trackTags_, &trackEnded_);
+}
+
+void RetinaFace::followTracks(const vector<cv::Mat> &imgs, rf_tracker tracker, const vector<int> &streams) {
+    follow_call(h_, false, imgs, tracker, streams, 0.f, 256, &lastBatch_, &trackTags_, &trackEnded_);
+}
+
 void RetinaFace::enableMotion(rf_tracker tracker, const rf_motion_spec *spec) {
     check(rf_tracker_enable_motion(tracker, spec), h_, "RetinaFace::enableMotion");
 }

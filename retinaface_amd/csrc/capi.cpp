@@ -850,6 +850,186 @@ int rf_tracker_read_motion(rf_tracker tracker, int stream, rf_track_motion *out,
     return guarded(tracker->h, [&]() -> int { return tracker->h->eng->tracker_read_motion(tracker->impl, stream, out, cap); });
 }
 
+// ---- followed tracks (follow.h)
+namespace {
+// a host frame as follow.h takes it; false: a frame that cannot be read (a NULL / 0 x 0 frame is legal: it has no pixels)
+bool follow_frame_arg(const uint8_t *bgr, int rows, int cols, int step, rf::FollowFrame *fd) {
+    if (rows < 0 || cols < 0) return false;
+    if (!bgr || rows == 0 || cols == 0) { *fd = rf::FollowFrame{nullptr, 0, 0, 0}; return true; }
+    if (rows > 4096 * 3072 / cols || step < cols * 3) return false;
+    *fd = rf::FollowFrame{bgr, rows, cols, step};
+    return true;
+}
+}  // namespace
+
+int rf_follow_geometry(const float box[4], int32_t out[3]) {
+    if (!box || !out) return RF_ERR_INVALID_ARG;
+    const rf::FollowGeom g = rf::follow_geometry(box);
+    out[0] = g.valid ? g.q : 0; out[1] = g.valid ? g.ox : 0; out[2] = g.valid ? g.oy : 0;
+    return g.valid;
+}
+
+int rf_follow_template(const uint8_t *bgr, int rows, int cols, int step, int q, int ox, int oy, uint8_t *tpl) {
+    rf::FollowFrame fd;
+    if (!tpl || !follow_frame_arg(bgr, rows, cols, step, &fd) || rf::follow_frame_empty(fd) || q < 1 || q > 385) return RF_ERR_INVALID_ARG;
+    if (ox < -(1 << 20) || ox > (1 << 20) || oy < -(1 << 20) || oy > (1 << 20)) return RF_ERR_INVALID_ARG;
+    rf::follow_template(fd, q, ox, oy, tpl);
+    return RF_OK;
+}
+
+int rf_follow_search(const uint8_t *bgr, int rows, int cols, int step, const uint8_t *tpl, int q, int ox, int oy, int radius, int32_t out[4]) {
+    rf::FollowFrame fd;
+    if (!tpl || !out || !follow_frame_arg(bgr, rows, cols, step, &fd) || rf::follow_frame_empty(fd) || q < 1 || q > 385) return RF_ERR_INVALID_ARG;
+    if (radius < 1 || radius > rf::kFollowMaxRadius) return RF_ERR_INVALID_ARG;
+    if (ox < -(1 << 20) || ox > (1 << 20) || oy < -(1 << 20) || oy > (1 << 20)) return RF_ERR_INVALID_ARG;
+    const rf::FollowResult r = rf::follow_search(fd, tpl, q, ox, oy, radius);
+    out[0] = r.state; out[1] = r.sad; out[2] = r.du; out[3] = r.dv;
+    return RF_OK;
+}
+
+int rf_track_step_follow_key(const rf_track_spec *spec, rf_track *table, rf_track_follow *records, uint8_t *templates, int64_t *frames,
+                             int64_t *next_id, const uint8_t *bgr, int rows, int cols, int step, const rf_face *faces, int count,
+                             float coord_scale, const rf_face_quality *quality, int max_faces, rf_track_tag *tags, rf_track *ended,
+                             int cap_ended, int *ended_count) {
+    rf::TrackSpec sp;
+    rf::FollowFrame fd;
+    if (rf::track_spec_resolve(spec, &sp) || !follow_frame_arg(bgr, rows, cols, step, &fd)) return RF_ERR_INVALID_ARG;
+    if (!table || !records || !templates || !frames || !next_id || !ended_count || count < 0 || max_faces < 1 || cap_ended < 0) return RF_ERR_INVALID_ARG;
+    if (count > 0 && (!faces || !tags)) return RF_ERR_INVALID_ARG;
+    if (cap_ended > 0 && !ended) return RF_ERR_INVALID_ARG;
+    if (rf::follow_frame_empty(fd)) count = 0;                               // a frame without pixels has no faces, as on the device
+    const int m = std::min(std::min(count, max_faces), rf::kTrackMaxFaces);
+    const int st = rf::track_step_follow_key(sp, table, records, templates, frames, next_id, fd, (const float *)faces,
+                                             (int)(sizeof(rf_face) / sizeof(float)), m, coord_scale, quality, tags, ended, cap_ended, ended_count);
+    for (int k = m; k < count; k++) tags[k] = rf::track_tag_untracked(0);
+    return st ? RF_ERR_TRUNCATED : RF_OK;
+}
+
+int rf_track_step_follow(const rf_track_spec *spec, const rf_follow_spec *fspec, rf_track *table, rf_track_follow *records,
+                         const uint8_t *templates, int64_t *frames, const uint8_t *bgr, int rows, int cols, int step, rf_face *out,
+                         rf_track_tag *tags, int cap, int *count, rf_track *ended, int cap_ended, int *ended_count) {
+    rf::TrackSpec sp;
+    rf::FollowSpec fs;
+    rf::FollowFrame fd;
+    if (rf::track_spec_resolve(spec, &sp) || rf::follow_spec_resolve(fspec, &fs) || !follow_frame_arg(bgr, rows, cols, step, &fd)) return RF_ERR_INVALID_ARG;
+    if (!table || !records || !templates || !frames || !count || !ended_count || cap < 0 || cap_ended < 0) return RF_ERR_INVALID_ARG;
+    if (cap > 0 && (!out || !tags)) return RF_ERR_INVALID_ARG;
+    if (cap_ended > 0 && !ended) return RF_ERR_INVALID_ARG;
+    for (int s = 0; s < sp.max_tracks; s++)                                  // a record the steps did not write is refused, not searched
+        if (records[s].valid && (records[s].q < 1 || records[s].q > 385 || records[s].ox < -(1 << 20) || records[s].ox > (1 << 20) ||
+                                 records[s].oy < -(1 << 20) || records[s].oy > (1 << 20)))
+            return RF_ERR_INVALID_ARG;
+    const int st = rf::track_step_follow(sp, fs, table, records, templates, frames, fd, out, tags, cap, count, ended, cap_ended, ended_count);
+    return st ? RF_ERR_TRUNCATED : RF_OK;
+}
+
+int rf_tracker_enable_follow(rf_tracker tracker, const rf_follow_spec *spec) {
+    if (!tracker) return RF_ERR_INVALID_ARG;
+    rf_engine *h = tracker->h;
+    return guarded(h, [&]() -> int {
+        if (h->eng->num_devices() > 1) throw rf::Unsupported("face tracks are not available on a multi-device handle");
+        rf::FollowSpec fs;
+        if (const char *bad = rf::follow_spec_resolve(spec, &fs)) throw rf::ArgError(bad);
+        h->eng->tracker_enable_follow(tracker->impl, fs);
+        return RF_OK;
+    });
+}
+
+int rf_tracker_read_follow(rf_tracker tracker, int stream, rf_track_follow *records, uint8_t *templates, int cap) {
+    if (!tracker) return RF_ERR_INVALID_ARG;
+    return guarded(tracker->h, [&]() -> int { return tracker->h->eng->tracker_read_follow(tracker->impl, stream, records, templates, cap); });
+}
+
+int rf_track_follow_update_device(rf_handle h, rf_tracker tracker, const void *const *d_bgr, const int *rows, const int *cols, const int *steps,
+                                  int n, const int *stream_of_image, const rf_face *faces, int cap_per_image, const int *counts,
+                                  const float *coord_scale, const rf_face_quality *quality, rf_track_tag *tags, rf_track *ended,
+                                  int cap_ended, int *ended_counts) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        if (h->eng->num_devices() > 1) throw rf::Unsupported("face tracks are not available on a multi-device handle");
+        rf::TrackRequest rq;
+        track_request(h, tracker, stream_of_image, tags, ended, cap_ended, ended_counts, &rq);
+        bool cut = false;
+        h->eng->track_follow_update(rq, d_bgr, rows, cols, steps, n, faces, cap_per_image, counts, coord_scale, quality, &cut);
+        if (cut) { h->error = kTrackCut; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+
+namespace {
+int detect_track_follow_common(rf_handle h, const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,
+                               float thr, rf_face *out, int cap, int *counts, rf_tracker tracker, const int *stream_of_image, rf_track_tag *tags,
+                               rf_track *ended, int cap_ended, int *ended_counts) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        if (h->eng->num_devices() > 1) throw rf::Unsupported("face tracks are not available on a multi-device handle");
+        rf::TrackRequest rq;
+        track_request(h, tracker, stream_of_image, tags, ended, cap_ended, ended_counts, &rq);
+        bool tr = false;
+        rf::StageCall sc;
+        rf::StageResult res;
+        sc.track = &rq; sc.follow = true;
+        h->eng->detect_staged(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, sc, &res);
+        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        if (res.track_cut) { h->error = kTrackCut; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+
+int track_follow_common(rf_handle h, rf_tracker tracker, const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n,
+                        bool on_device, const int *stream_of_image, rf_face *out, int cap_per_image, int *counts, rf_track_tag *tags,
+                        rf_track *ended, int cap_ended, int *ended_counts) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        if (h->eng->num_devices() > 1) throw rf::Unsupported("face tracks are not available on a multi-device handle");
+        rf::TrackRequest rq;
+        track_request(h, tracker, stream_of_image, tags, ended, cap_ended, ended_counts, &rq);
+        bool cut = false;
+        h->eng->track_follow(rq, frames, rows, cols, steps, n, on_device, out, cap_per_image, counts, &cut);
+        if (cut) { h->error = "a followed list or an ended list was cut"; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+}  // namespace
+
+int rf_detect_track_follow_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                        float threshold, rf_face *out, int cap_per_image, int *counts, rf_tracker tracker,
+                                        const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_counts) {
+    return detect_track_follow_common(h, (const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, out, cap_per_image, counts, tracker,
+                                      stream_of_image, tags, ended, cap_ended, ended_counts);
+}
+
+int rf_detect_track_follow_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                                 float threshold, rf_face *out, int cap_per_image, int *counts, rf_tracker tracker,
+                                 const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_counts) {
+    return detect_track_follow_common(h, bgr, rows, cols, steps, n, false, threshold, out, cap_per_image, counts, tracker, stream_of_image, tags,
+                                      ended, cap_ended, ended_counts);
+}
+
+int rf_track_follow_device(rf_handle h, rf_tracker tracker, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                           const int *stream_of_image, rf_face *out, int cap_per_image, int *counts, rf_track_tag *tags, rf_track *ended,
+                           int cap_ended, int *ended_counts) {
+    return track_follow_common(h, tracker, (const uint8_t *const *)d_bgr, rows, cols, steps, n, true, stream_of_image, out, cap_per_image, counts,
+                               tags, ended, cap_ended, ended_counts);
+}
+
+int rf_track_follow_batch(rf_handle h, rf_tracker tracker, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                          const int *stream_of_image, rf_face *out, int cap_per_image, int *counts, rf_track_tag *tags, rf_track *ended,
+                          int cap_ended, int *ended_counts) {
+    return track_follow_common(h, tracker, bgr, rows, cols, steps, n, false, stream_of_image, out, cap_per_image, counts, tags, ended,
+                               cap_ended, ended_counts);
+}
+
+int rf_follow_last_launch_ms(rf_handle h, float *ms) {
+    if (!h || !ms) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        const float v = h->eng->follow_last_launch_ms();
+        if (v < 0.f) throw rf::ArgError("no rf_track_follow_device call has been timed on this handle");
+        *ms = v;
+        return RF_OK;
+    });
+}
+
 int rf_tracker_read_shots(rf_tracker tracker, int stream, void *shots, rf_shot *shot_info, int cap) {
     if (!tracker) return RF_ERR_INVALID_ARG;
     return guarded(tracker->h, [&]() -> int { return tracker->h->eng->tracker_read_shots(tracker->impl, stream, (uint8_t *)shots, shot_info, cap); });

@@ -230,12 +230,13 @@ public:
         if (align_stream_) { (void)hipStreamSynchronize(align_stream_); (void)hipStreamDestroy(align_stream_); }
         for (DeviceScratch *b : {&align_crops_, &align_mats_, &align_tab_, &fb_state_, &fq_records_, &fq_packed_, &fq_offsets_, &tile_cand_, &tile_count_, &tile_out_,
                                  &tile_outcount_, &tile_tab_, &pass_frames_, &tta_cand_, &tta_count_, &tta_mirror_, &pyr_zoom_, &rot_copies_, &dewarp_views_, &enh_luts_, &enh_frames_,
-                                 &red_regions_, &red_counts_, &red_cells_, &red_frames_, &red_shadow_}) b->release();
-        for (HostScratch *b : {&trk_tags_, &trk_ended_, &trk_counts_, &enh_counts_, &tta_out_, &tta_votes_, &tta_outcount_, &shot_out_, &shot_info_}) b->release();
+                                 &red_regions_, &red_counts_, &red_cells_, &red_frames_, &red_shadow_, &fol_results_}) b->release();
+        for (HostScratch *b : {&trk_tags_, &trk_ended_, &trk_counts_, &enh_counts_, &tta_out_, &tta_votes_, &tta_outcount_, &shot_out_, &shot_info_, &fol_out_}) b->release();
         for (auto &t : trackers_) t->release();
         for (auto &d : dewarpers_) d->mesh.release();
         for (hipEvent_t e : trk_ev_) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : shot_ev_) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : fol_ev_) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : red_ev_) if (e) (void)hipEventDestroy(e);
         if (inputs_ready_) (void)hipEventDestroy(inputs_ready_);
         kind_.arena->release();
@@ -1555,6 +1556,10 @@ public:
             RF_HIP(hipMemset(t.motion.ptr + (size_t)stream * t.motion_bytes(), 0, t.motion_bytes()));
             RF_HIP(hipDeviceSynchronize());
         }
+        if (ended && t.has_follow) {
+            RF_HIP(hipMemset(t.follow_records.ptr + (size_t)stream * t.follow_bytes(), 0, t.follow_bytes()));
+            RF_HIP(hipDeviceSynchronize());
+        }
         return ended;
     }
 
@@ -1615,6 +1620,7 @@ public:
         check_face_batch_request(probe);
         if (t.dirty) throw ArgError("the tracker's last call failed: reset it first");
         if (t.has_shots) throw ArgError("the tracker has a shot gallery already");
+        if (t.has_follow) throw ArgError("the tracker has follow: a gallery does not compose with it yet");
         const size_t entries = (size_t)t.n_streams * t.spec.max_tracks;
         if (entries * spec.bytes_per_face() > (size_t)RF_SHOT_MAX_BYTES) throw ArgError("shot gallery: more than RF_SHOT_MAX_BYTES");
         DeviceGuard guard(device_);
@@ -1636,6 +1642,7 @@ public:
         Tracker &t = tracker_of(p);
         if (t.dirty) throw ArgError("the tracker's last call failed: reset it first");
         if (t.has_motion) throw ArgError("the tracker has motion already");
+        if (t.has_follow) throw ArgError("the tracker has follow: motion does not compose with it yet");
         DeviceGuard guard(device_);
         std::vector<TrackHeader> hd((size_t)t.n_streams);
         RF_HIP(hipMemcpy2D(hd.data(), sizeof(TrackHeader), t.state.ptr, t.stream_bytes(), sizeof(TrackHeader), (size_t)t.n_streams, hipMemcpyDeviceToHost));
@@ -1841,6 +1848,174 @@ public:
     }
     float shot_last_launch_ms() const override { return shot_launch_ms_; }
 
+    // -------------------------------------------------------------------------------- followed tracks
+    void tracker_enable_follow(void *p, const FollowSpec &spec) override {
+        Tracker &t = tracker_of(p);
+        if (t.dirty) throw ArgError("the tracker's last call failed: reset it first");
+        if (t.has_follow) throw ArgError("the tracker has follow already");
+        if (t.has_shots || t.has_motion) throw ArgError("follow does not compose with a shot gallery or motion yet");
+        const size_t entries = (size_t)t.n_streams * t.spec.max_tracks;
+        if (entries * kFollowCells > (size_t)RF_SHOT_MAX_BYTES) throw ArgError("follow: more than RF_SHOT_MAX_BYTES of templates");
+        DeviceGuard guard(device_);
+        std::vector<TrackHeader> hd((size_t)t.n_streams);
+        RF_HIP(hipMemcpy2D(hd.data(), sizeof(TrackHeader), t.state.ptr, t.stream_bytes(), sizeof(TrackHeader), (size_t)t.n_streams, hipMemcpyDeviceToHost));
+        for (const TrackHeader &h : hd)
+            if (h.frames != 0) throw ArgError("follow: the tracker has stepped a frame already");
+        try {
+            RF_HIP(hipMemset(t.follow_templates.reserve(entries * kFollowCells), 0, entries * kFollowCells));
+            RF_HIP(hipMemset(t.follow_records.reserve(entries * sizeof(rf_track_follow)), 0, entries * sizeof(rf_track_follow)));
+            RF_HIP(hipDeviceSynchronize());
+        } catch (...) { t.follow_templates.release(); t.follow_records.release(); throw; }
+        t.follow_spec = spec;
+        t.has_follow = true;
+    }
+    int tracker_read_follow(void *p, int stream, rf_track_follow *records, uint8_t *templates, int cap) override {
+        Tracker &t = tracker_of(p);
+        if (!t.has_follow) throw ArgError("the tracker has no follow (rf_tracker_enable_follow)");
+        if (stream < 0 || stream >= t.n_streams) throw ArgError("stream out of range");
+        if (cap < 0) throw ArgError("cap is negative");
+        if (t.dirty) throw ArgError("the tracker's last call failed: reset it first");
+        const int T = t.spec.max_tracks, m = std::min(cap, T);
+        if (m == 0 || (!records && !templates)) return T;
+        DeviceGuard guard(device_);
+        std::vector<rf_track_follow> rec((size_t)m);
+        RF_HIP(hipMemcpy(rec.data(), t.follow_records.ptr + (size_t)stream * t.follow_bytes(), (size_t)m * sizeof(rf_track_follow), hipMemcpyDeviceToHost));
+        if (records) memcpy(records, rec.data(), (size_t)m * sizeof(rf_track_follow));
+        if (templates) {
+            RF_HIP(hipMemcpy(templates, t.follow_templates.ptr + (size_t)stream * T * kFollowCells, (size_t)m * kFollowCells, hipMemcpyDeviceToHost));
+            for (int s = 0; s < m; s++)
+                if (!rec[s].valid) memset(templates + (size_t)s * kFollowCells, 0, kFollowCells);
+        }
+        return T;
+    }
+    // what every follow launch takes from the tracker and the open call's result blocks
+    FollowParams follow_params(const Tracker &t) const {
+        FollowParams fp;
+        memset((void *)&fp, 0, sizeof(fp));
+        fp.spec = t.spec; fp.fspec = t.follow_spec;
+        fp.state = t.state.ptr;
+        fp.records = (rf_track_follow *)t.follow_records.ptr;
+        fp.templates = t.follow_templates.ptr;
+        fp.tags = (rf_track_tag *)trk_tags_.ptr; fp.tag_stride = call_.trk.tag_stride;
+        fp.ended = (rf_track *)trk_ended_.ptr; fp.cap_ended = call_.trk.cap_ended;
+        fp.ended_counts = (int *)trk_counts_.ptr;
+        fp.status = (int *)trk_counts_.ptr + std::max(call_.trk.n, 1);
+        return fp;
+    }
+
+    // a key step over faces the caller supplies: track_update() against device-resident frames + the keep launch
+    void track_follow_update(const TrackRequest &rq, const void *const *frames, const int *rows, const int *cols, const int *steps, int n,
+                             const rf_face *faces, int cap_per_image, const int *counts, const float *coord_scale, const rf_face_quality *quality,
+                             bool *cut) override {
+        *cut = false;
+        if (n < 0 || (n > 0 && (!frames || !rows || !cols || !faces || !counts))) throw ArgError("null argument");
+        if (cap_per_image < 1) throw ArgError("cap_per_image must be >= 1");
+        for (int i = 0; i < n; i++)
+            if (counts[i] < 0) throw ArgError("negative face count");
+        Tracker &t = track_check(rq, n, false, true);
+        const int max_faces = opt_.max_detections;
+        const int fpi = std::min(std::min(cap_per_image, max_faces), kTrackMaxFaces);      // records per image that travel to the device
+        const int mq = std::min(max_faces, kTrackMaxFaces);                                 // quality records per image that do
+        // one table: streams | images | counts | frames | quality records | faces (60-byte records)
+        HostTable tb;
+        const size_t o_se = tb.add((size_t)n * sizeof(TrackStreamEntry)), o_img = tb.add((size_t)n * sizeof(TrackImageEntry)),
+                     o_cnt = tb.add((size_t)n * sizeof(int)), o_fd = tb.add((size_t)n * sizeof(FrameDesc)),
+                     o_q = tb.add(quality ? (size_t)n * mq * sizeof(rf_face_quality) : 0), o_face = tb.add((size_t)n * fpi * sizeof(rf_face));
+        uint8_t *tab = table_open(tb);
+        int *cnt = (int *)(tab + o_cnt);
+        std::vector<float> scale((size_t)n);
+        const std::vector<char> empty = table_frames((FrameDesc *)(tab + o_fd), frames, rows, cols, steps, n, "follow");
+        for (int i = 0; i < n; i++) {
+            cnt[i] = empty[i] ? 0 : counts[i];      // a frame without pixels has no faces
+            scale[i] = coord_scale ? coord_scale[i] : 1.f;
+        }
+        table_records(tab + o_face, fpi, faces, cap_per_image, sizeof(rf_face), cnt, fpi, n);
+        if (quality) table_records(tab + o_q, mq, quality, max_faces, sizeof(rf_face_quality), cnt, std::min(fpi, mq), n);
+        if (n == 0) return;
+        DeviceGuard guard(device_);
+        const int ns = track_build_table(rq.stream_of_image, 0, n, scale.data(), empty.data(), (TrackStreamEntry *)(tab + o_se),
+                                         (TrackImageEntry *)(tab + o_img));
+        uint8_t *d_tab = align_tab_.reserve(tb.end);
+        track_open_call(t, rq, n, cap_per_image);
+        t.dirty = true;
+        table_upload(d_tab, tb);
+        TrackParams tp = track_params(t);
+        tp.streams = (const TrackStreamEntry *)(d_tab + o_se); tp.n_streams = ns;
+        tp.images = (const TrackImageEntry *)(d_tab + o_img);
+        tp.faces = d_tab + o_face; tp.face_stride = (int)sizeof(rf_face); tp.faces_per_image = fpi;
+        tp.counts = (const int *)(d_tab + o_cnt);
+        tp.records = quality ? (const rf_face_quality *)(d_tab + o_q) : nullptr;
+        tp.max_faces = mq;
+        launch_track(align_stream_, tp);
+        RF_HIP(hipGetLastError());
+        FollowParams fp = follow_params(t);
+        fp.streams = tp.streams; fp.n_streams = ns;
+        fp.images = tp.images;
+        fp.frames = (const FrameDesc *)(d_tab + o_fd);
+        launch_follow_keep(align_stream_, fp);
+        RF_HIP(hipGetLastError());
+        RF_HIP(hipStreamSynchronize(align_stream_));
+        track_copy_out(t, rq, n, cap_per_image, cnt, cut);
+    }
+
+    // a follow step: the search and step launches over the frames alone
+    void track_follow(const TrackRequest &rq, const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,
+                      rf_face *out, int cap_per_image, int *counts, bool *cut) override {
+        *cut = false;
+        if (n < 0 || (n > 0 && (!frames || !rows || !cols || !counts))) throw ArgError("null argument");
+        if (cap_per_image < 0 || (cap_per_image > 0 && !out)) throw ArgError("out is null");
+        if ((long)n * std::max(cap_per_image, 1) > (1L << 24)) throw ArgError("n x cap_per_image: more than 2^24 faces in one call");
+        Tracker &t = track_check(rq, n, false, true);
+        if (!on_device)
+            for (int i = 0; i < n; i++) check_frame(frames[i], rows[i], cols[i], steps ? steps[i] : cols[i] * 3);
+        // one table: streams | images | frames
+        HostTable tb;
+        const size_t o_se = tb.add((size_t)n * sizeof(TrackStreamEntry)), o_img = tb.add((size_t)n * sizeof(TrackImageEntry)),
+                     o_fd = tb.add((size_t)n * sizeof(FrameDesc));
+        DeviceGuard guard(device_);
+        std::vector<const uint8_t *> dev;
+        std::vector<int> dense;
+        if (!on_device && n > 0) {                     // the dense upload of the redacting host call; nothing is copied back
+            dev = redact_upload(frames, rows, cols, steps, n, nullptr, nullptr);
+            dense.resize((size_t)n);
+            for (int i = 0; i < n; i++) dense[i] = cols[i] * 3;
+            frames = dev.data(); steps = dense.data();
+        }
+        uint8_t *tab = table_open(tb);
+        const std::vector<char> empty = table_frames((FrameDesc *)(tab + o_fd), (const void *const *)frames, rows, cols, steps, n, on_device ? "follow" : nullptr);
+        if (n == 0) return;
+        const std::vector<float> scale((size_t)n, 1.f);
+        const int ns = track_build_table(rq.stream_of_image, 0, n, scale.data(), empty.data(), (TrackStreamEntry *)(tab + o_se),
+                                         (TrackImageEntry *)(tab + o_img));
+        uint8_t *d_tab = align_tab_.reserve(tb.end);
+        track_open_call(t, rq, n, cap_per_image);
+        // followed faces of the call | their counts, pinned: the step kernel writes them; an image no workgroup serves has none
+        const size_t o_cnt = align256((size_t)n * std::max(cap_per_image, 1) * sizeof(rf_face));
+        uint8_t *h_out = fol_out_.reserve(o_cnt + (size_t)n * sizeof(int));
+        int *h_cnt = (int *)(h_out + o_cnt);
+        memset(h_cnt, 0, (size_t)n * sizeof(int));
+        memset(trk_counts_.ptr, 0, (size_t)n * 2 * sizeof(int));
+        t.dirty = true;
+        table_upload(d_tab, tb);
+        FollowParams fp = follow_params(t);
+        fp.streams = (const TrackStreamEntry *)(d_tab + o_se); fp.n_streams = ns;
+        fp.images = (const TrackImageEntry *)(d_tab + o_img);
+        fp.frames = (const FrameDesc *)(d_tab + o_fd);
+        fp.results = (FollowResult *)fol_results_.reserve((size_t)std::max(ns, 1) * t.spec.max_tracks * sizeof(FollowResult));
+        fp.out = (rf_face *)h_out; fp.cap_per_image = cap_per_image;
+        fp.counts = h_cnt;
+        float ms = -1.f;
+        timed_launch(fol_ev_, ms, [&] { launch_follow_search(align_stream_, fp); launch_follow_step(align_stream_, fp); });
+        if (on_device) fol_launch_ms_ = ms;
+        for (int i = 0; i < n; i++) {
+            counts[i] = h_cnt[i];
+            const int have = std::min(h_cnt[i], cap_per_image);
+            if (have > 0) memcpy((void *)(out + (size_t)i * cap_per_image), h_out + (size_t)i * cap_per_image * sizeof(rf_face), (size_t)have * sizeof(rf_face));
+        }
+        track_copy_out(t, rq, n, cap_per_image, counts, cut);
+    }
+    float follow_last_launch_ms() const override { return fol_launch_ms_; }
+
     // -------------------------------------------------------------------------------- face redaction
     // The arguments of a redacting call, checked before any state changes: the tracker and its streams (each at most once per call:
     // the coasting regions of a stream belong to one frame), the frames (in-place writes: no two frames of a call may share a byte,
@@ -2006,8 +2181,8 @@ public:
         std::vector<size_t> off((size_t)n, 0);
         for (int i = 0; i < n; i++) {
             if (!frames[i] || rows[i] <= 0 || cols[i] <= 0) continue;
-            if (!out_bgr[i]) throw ArgError("out_bgr[i] is null");
-            if (out_steps && out_steps[i] < cols[i] * 3) throw ArgError("out_steps[i] smaller than cols*3");
+            if (out_bgr && !out_bgr[i]) throw ArgError("out_bgr[i] is null");      // (out_bgr null: a follow step, nothing goes back)
+            if (out_bgr && out_steps && out_steps[i] < cols[i] * 3) throw ArgError("out_steps[i] smaller than cols*3");
             off[i] = bytes; bytes += align256((size_t)rows[i] * cols[i] * 3);
         }
         uint8_t *d = red_frames_.reserve(bytes);
@@ -2021,7 +2196,7 @@ public:
     }
 
     // The fused calls (StageCall): detect() with the call's stages armed behind every launch (launch_pending()).  Everything a stage
-    // needs is bound when the call opens; the launch path does not know which of the seven calls it serves.
+    // needs is bound when the call opens; the launch path does not know which of the eight calls it serves.
     void detect_staged(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device, float threshold,
                        rf_face *out, int cap_per_image, int *counts, bool *truncated, const StageCall &sc, StageResult *res) override {
         *res = StageResult{};
@@ -2030,9 +2205,9 @@ public:
         const TrackRequest *trq = sc.track;
         const ShotRequest *sq = sc.shots;
         const RedactRequest *rq = sc.redact;
-        static const int kSets[7] = {1, 2, 4, 4 | 2, 4 | 8, 16, 4 | 16};
-        const int set = (al ? 1 : 0) | (fb ? 2 : 0) | (trq ? 4 : 0) | (sq ? 8 : 0) | (rq ? 16 : 0);
-        if (std::find(kSets, kSets + 7, set) == kSets + 7) throw ArgError("stage call: not a set of stages that run together");
+        static const int kSets[8] = {1, 2, 4, 4 | 2, 4 | 8, 16, 4 | 16, 4 | 32};
+        const int set = (al ? 1 : 0) | (fb ? 2 : 0) | (trq ? 4 : 0) | (sq ? 8 : 0) | (rq ? 16 : 0) | (sc.follow ? 32 : 0);
+        if (std::find(kSets, kSets + 8, set) == kSets + 8) throw ArgError("stage call: not a set of stages that run together");
         // every check before any state changes; a call with two defects reports the one it always has
         if (al) check_align_request(*al);
         if (fb) check_face_batch_request(*fb);
@@ -2047,7 +2222,7 @@ public:
             if (!rq->tracker || rq->tracker != trq->tracker || rq->stream_of_image != trq->stream_of_image) throw ArgError("redaction: not the tracked call's tracker");
             if (!on_device) throw ArgError("redaction: the tracked call takes frames in device memory");
         }
-        Tracker *t = trq ? &track_check(*trq, n, sq != nullptr) : nullptr;
+        Tracker *t = trq ? &track_check(*trq, n, sq != nullptr, sc.follow) : nullptr;
         // shots: the quality launch of the gated face-batch path, for the gallery spec, no tensor; it runs only under a gate, the frame
         // steps read max_faces from it either way
         FaceBatchRequest shot_fb;
@@ -2095,7 +2270,7 @@ public:
         struct Disarm { StageOpen &c; ~Disarm() { c.disarm(); } } disarm{call_};
         call_.align.on = al && (call_.align.d_crops || call_.align.d_mats);
         call_.fb.on = fb != nullptr;
-        call_.trk.on = trq && n > 0; call_.shot.on = sq && n > 0; call_.red.on = rq && n > 0;
+        call_.trk.on = trq && n > 0; call_.shot.on = sq && n > 0; call_.red.on = rq && n > 0; call_.follow.on = sc.follow && n > 0;
         const bool armed = call_.armed();
         detect(frames, rows, cols, steps, n, on_device, threshold, out, cap_per_image, counts, truncated);
         call_.disarm();
@@ -2721,6 +2896,7 @@ private:
         if (passes_.on) launch_lane_passes(s, n);
         if (call_.trk.on) launch_lane_track(s, n);
         if (call_.shot.on) launch_lane_shots(s);
+        if (call_.follow.on) launch_lane_follow(s);
         if (call_.red.on) launch_lane_redact(s, n);
         if (staged) call_.next_image += n;
         RF_HIP(hipEventRecord(s.done, s.stream));
@@ -2899,6 +3075,22 @@ private:
         call_.trk.prev = s.shot_done;
     }
 
+    // The keep launch of a super-batch of a key call on a tracker with follow, behind its track launch: the tables launch_lane_track()
+    // has just filled and the launch's own frame table (full-resolution source frames).  Every stream appears once in the call, so the
+    // table the keep launch reads is the one after this frame's step; the lane's track event is recorded again behind it, so the track
+    // chain of the call runs through the keep launch.  The lane's `done` event follows.  No host wait anywhere.
+    void launch_lane_follow(Lane &s) {
+        const int ns = call_.shot.last_streams;
+        if (ns == 0) return;                          // no tracked image in this launch: launch_lane_track() launched nothing either
+        FollowParams fp = follow_params(*call_.trk.tr);
+        fp.streams = (const TrackStreamEntry *)s.h_track_tab; fp.n_streams = ns;
+        fp.images = (const TrackImageEntry *)(fp.streams + cap_images_);
+        fp.frames = s.d_frames;
+        launch_follow_keep(s.stream, fp);
+        RF_HIP(hipGetLastError());
+        RF_HIP(hipEventRecord(s.track_done, s.stream));
+    }
+
     // The redaction launches of a super-batch of a redacting call: frames (the caller's, written in place), faces, counts and scales
     // as lane_view() binds them.  With a tracker the launches sit behind the lane's track launch: every stream appears at most once
     // in the call, so its table is the one after this frame's step.  Region records, cell values and pixel counts are indexed by the
@@ -2962,11 +3154,17 @@ private:
             RF_HIP(hipMemset(t.motion.ptr + (size_t)first * t.motion_bytes(), 0, (size_t)count * t.motion_bytes()));
             RF_HIP(hipDeviceSynchronize());
         }
+        if (t.has_follow) {
+            RF_HIP(hipMemset(t.follow_records.ptr + (size_t)first * t.follow_bytes(), 0, (size_t)count * t.follow_bytes()));
+            RF_HIP(hipDeviceSynchronize());
+        }
     }
     // the arguments of a tracked call, checked before any state changes
-    Tracker &track_check(const TrackRequest &rq, int n, bool shots = false) {
+    Tracker &track_check(const TrackRequest &rq, int n, bool shots = false, bool follow = false) {
         Tracker &t = tracker_of(rq.tracker);
         if (t.dirty) throw ArgError("the tracker's last call failed: reset it first");
+        if (t.has_follow && !follow) throw ArgError("the tracker has follow: use the follow calls, this one would leave a template stale");
+        if (!t.has_follow && follow) throw ArgError("the tracker has no follow (rf_tracker_enable_follow)");
         if (t.has_shots && !shots) throw ArgError("the tracker has a shot gallery: use the shot calls, this one would leave it stale");
         if (!t.has_shots && shots) throw ArgError("the tracker has no shot gallery (rf_tracker_enable_shots)");
         if (n > 0 && !rq.stream_of_image) throw ArgError("stream_of_image is null");
@@ -2974,6 +3172,13 @@ private:
         if ((long)n * std::max(rq.cap_ended, 1) > (1L << 24)) throw ArgError("n x cap_ended: more than 2^24 records in one call");
         for (int i = 0; i < n; i++)
             if (rq.stream_of_image[i] < -1 || rq.stream_of_image[i] >= t.n_streams) throw ArgError("stream_of_image: stream out of range");
+        if (follow) {                                  // a stream's template belongs to one frame of the call
+            std::vector<int> seen;
+            for (int i = 0; i < n; i++)
+                if (rq.stream_of_image[i] >= 0) seen.push_back(rq.stream_of_image[i]);
+            std::sort(seen.begin(), seen.end());
+            if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) throw ArgError("follow: a stream appears more than once in the call");
+        }
         return t;
     }
     // call-level result blocks (pinned host memory): tags (tag_stride per image), ended lists, ended counts | status
@@ -3321,8 +3526,13 @@ private:
         MotionSpec motion_spec;
         DeviceScratch motion;
         size_t stream_bytes() const { return sizeof(TrackHeader) + (size_t)spec.max_tracks * sizeof(rf_track); }
+        // follow (follow.h), fixed by tracker_enable_follow(): n_streams x max_tracks rf_track_follow records and 1024-byte templates
+        bool has_follow = false;
+        FollowSpec follow_spec;
+        DeviceScratch follow_records, follow_templates;
         size_t motion_bytes() const { return (size_t)spec.max_tracks * sizeof(rf_track_motion); }
-        void release() { state.release(); gallery.release(); shot_records.release(); motion.release(); }
+        size_t follow_bytes() const { return (size_t)spec.max_tracks * sizeof(rf_track_follow); }
+        void release() { state.release(); gallery.release(); shot_records.release(); motion.release(); follow_records.release(); follow_templates.release(); }
     };
     std::vector<std::unique_ptr<Tracker>> trackers_;
     // (pinned host memory the kernel writes straight into, as the NMS kernel writes its result block: no copy after the call)
@@ -3347,6 +3557,12 @@ private:
     hipEvent_t shot_ev_[2] = {nullptr, nullptr};
     float shot_launch_ms_ = -1.f;
     HostScratch tta_out_, tta_votes_, tta_outcount_;      // detect_tta() / tta_merge(): what the voting merge writes (see tta_open)
+    // followed tracks: what the search launch hands to the step launch (device), the followed faces | their counts of a call (pinned,
+    // the step kernel writes them) and the events around the two launches of track_follow() (tools/follow_bench.py reads the time)
+    DeviceScratch fol_results_;
+    HostScratch fol_out_;
+    hipEvent_t fol_ev_[2] = {nullptr, nullptr};
+    float fol_launch_ms_ = -1.f;
     hipEvent_t trk_ev_[2] = {nullptr, nullptr};   // around the track launch of track_update() (tools/track_bench.py reads the time)
     float trk_launch_ms_ = -1.f;
     hipEvent_t red_ev_[2] = {nullptr, nullptr};   // around the redaction launches of redact() (tools/redact_bench.py reads the time)
@@ -3373,10 +3589,11 @@ private:
         struct { bool on = false; Tracker *tr = nullptr; const int *stream_of_image = nullptr; int n = 0, tag_stride = 0, cap_ended = 0, max_faces = 0;
                  const rf_face_quality *records = nullptr; hipEvent_t prev = nullptr; } trk;
         struct { bool on = false; uint8_t *d_out = nullptr; bool host = false, info = false; int last_streams = 0; } shot;
+        struct { bool on = false; } follow;   // the keep launch behind every track launch (launch_lane_follow())
         struct { bool on = false; RedactSpec spec; Tracker *tr = nullptr; const int *stream_of_image = nullptr; int n = 0; bool overlay = false;
                  OverlaySpec ospec; } red;
-        bool armed() const { return align.on || fb.on || trk.on || shot.on || red.on; }
-        void disarm() { align.on = fb.on = trk.on = shot.on = red.on = false; }
+        bool armed() const { return align.on || fb.on || trk.on || shot.on || red.on || follow.on; }
+        void disarm() { align.on = fb.on = trk.on = shot.on = red.on = follow.on = false; }
     } call_;
 
     int last_n_ = 0;

@@ -187,7 +187,7 @@ struct RedactRequest {
 // What a fused call wants behind every detection launch, on the launch's stream and with no host synchronisation in between: the
 // stages read faces and counts from the device-visible result block the launch has just written, and each frame's frame_scale is
 // applied, so frames the engine shrank are sampled at full source resolution.  A null request: the stage is off.  The sets a call
-// may carry are {align}, {face_batch}, {track}, {track, face_batch}, {track, shots}, {redact} and {track, redact}.
+// may carry are {align}, {face_batch}, {track}, {track, face_batch}, {track, shots}, {redact}, {track, redact} and {track, follow}.
 //   align       the aligned crops of the faces found (AlignRequest).
 //   face_batch  their face batch (face_batch.h): per launch a scan kernel packs the counts on the device and the tensor kernel
 //               follows; gated, the quality kernel runs in front.  max_faces 0 in the spec has been replaced by the caller with
@@ -208,6 +208,7 @@ struct StageCall {
     const TrackRequest *track = nullptr;
     const ShotRequest *shots = nullptr;
     const RedactRequest *redact = nullptr;
+    bool follow = false;                        // with track alone, on a tracker that has follow: the keep launch behind each track launch (follow.h)
     uint8_t *const *out_bgr = nullptr;          // redact over host frames: where the redacted copies go
     const int *out_steps = nullptr;
 };
@@ -382,6 +383,27 @@ public:
     }
     // hipEvent time of the two shot launches of the most recent track_shots() (negative: none yet)
     virtual float shot_last_launch_ms() const { return -1.f; }
+    // Followed tracks (follow.h): a tracker may own n_streams x max_tracks follow records and templates in device memory.  A key step is
+    // a track launch with the keep launch behind it on its stream (track_follow_update() over faces the caller supplies, or the fused
+    // call with StageCall::follow); a follow step (track_follow()) is the search and step launches over frames alone: no detection.
+    // Each stream appears at most once in such a call.  Single-device engines only.
+    virtual void tracker_enable_follow(void *, const FollowSpec &) { throw Unsupported("face tracks are not available on a multi-device handle"); }
+    // host copy of a stream's records and templates (zeros where the record is not valid); returns max_tracks
+    virtual int tracker_read_follow(void *, int /*stream*/, rf_track_follow *, uint8_t *, int /*cap*/) {
+        throw Unsupported("face tracks are not available on a multi-device handle");
+    }
+    virtual void track_follow_update(const TrackRequest &, const void *const *, const int *, const int *, const int *, int /*n*/, const rf_face *,
+                                     int /*cap_per_image*/, const int * /*counts*/, const float * /*coord_scale*/, const rf_face_quality *,
+                                     bool * /*cut*/) {
+        throw Unsupported("face tracks are not available on a multi-device handle");
+    }
+    // out / counts: the followed faces of every image (host); host frames are uploaded densely first
+    virtual void track_follow(const TrackRequest &, const uint8_t *const *, const int *, const int *, const int *, int /*n*/, bool /*on_device*/,
+                              rf_face *, int /*cap_per_image*/, int * /*counts*/, bool * /*cut*/) {
+        throw Unsupported("face tracks are not available on a multi-device handle");
+    }
+    // hipEvent time of the search and step launches of the most recent track_follow() over device frames (negative: none yet)
+    virtual float follow_last_launch_ms() const { return -1.f; }
     // Face redaction, in place in device-resident frames: regions of faces the caller supplies (host memory) and, with a tracker in
     // the request, of its streams' coasting tracks.  *cut: a region list was cut at max_regions.  Single-device engines only.
     virtual void redact(const void *const *, const int *, const int *, const int *, int, const rf_face *, int, const int *, const float *,

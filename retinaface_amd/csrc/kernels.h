@@ -21,6 +21,7 @@
 #include "track.h"
 #include "motion.h"
 #include "shot.h"
+#include "follow.h"
 
 namespace rf {
 
@@ -370,6 +371,33 @@ struct ShotParams {
 };
 void launch_shot_deliver(hipStream_t s, const ShotParams &p);
 void launch_shot_keep(hipStream_t s, const ShotParams &p);
+
+// ---- K_m: followed tracks (follow.h).  In a follow call every stream has at most one image, so streams[z] has n == 1 and its image is
+//      images[streams[z].first].  launch_follow_keep (a key step, behind launch_track on its stream): one workgroup per (stream of the
+//      launch, slot) reads the table after the step; a free slot gets the zero record, a slot the step matched or opened (last_frame is
+//      the step's frame: exactly the slots a tag of the image names) gets its template and record retaken.  launch_follow_search: one
+//      workgroup of four waves per (stream, slot) writes one FollowResult to `results`; launch_follow_step: one workgroup per stream, one
+//      thread per slot, applies them, ages and ends tracks and compacts the output and ended lists in slot order.
+struct FollowParams {
+    const TrackStreamEntry *streams; int n_streams;      // the grid; as TrackParams, the same tables
+    const TrackImageEntry *images;
+    const FrameDesc *frames;              // [launch images] SOURCE frames, indexed by images[j].local
+    TrackSpec spec;
+    FollowSpec fspec;
+    uint8_t *state;                       // as TrackParams
+    rf_track_follow *records;             // stream s, slot t: records[s * max_tracks + t]
+    uint8_t *templates;                   // ... templates + (s * max_tracks + t) * 1024
+    FollowResult *results;                // search -> step: stream entry z, slot t at results[z * max_tracks + t]
+    rf_face *out; int cap_per_image;      // step: call image c, followed face j at out[c * cap_per_image + j]
+    int *counts;                          // [call images] the true number of followed faces
+    rf_track_tag *tags; int tag_stride;   // call image c: tags[c * tag_stride + j], j < min(count, tag_stride)
+    rf_track *ended; int cap_ended;
+    int *ended_counts;                    // [call images] the true number
+    int *status;                          // [call images] kTrackOverflow (the output list was cut) or 0
+};
+void launch_follow_keep(hipStream_t s, const FollowParams &p);
+void launch_follow_search(hipStream_t s, const FollowParams &p);
+void launch_follow_step(hipStream_t s, const FollowParams &p);
 
 // ---- K_k: face redaction (redact.h) -- in place in the frames of a launch, in three launches ordered on the stream.
 //      launch_redact_regions: one workgroup per image turns its faces, and with a tracker its stream's coasting tracks, into region

@@ -5127,6 +5127,187 @@ void launch_shot_keep(hipStream_t s, const ShotParams &p) {
 #undef RF_SHOT_DISPATCH
 
 // =============================================================================================
+// K_m: followed tracks (follow.h).  Every stream of a follow call has one image, so a workgroup's image is images[streams[z].first].
+//      follow_keep_kernel (key step, behind track_kernel on its stream): one workgroup = one (stream, slot).  The step matched or
+//      opened the slot exactly when the record's last_frame is the step's frame (the header's counter - 1) -- the slots a tag of the
+//      image names -- so the decision needs the table alone, not a search of the tags.  Each thread owns four neighbouring cells of
+//      the template and stores them as one dword; a free slot gets the zero record.
+//      follow_search_kernel: one workgroup of four waves = one (stream, slot); the exit for free / unattempted slots reads only values
+//      every thread reads alike.  Phase 1: every window cell has one owner thread, lanes on neighbouring cells of a cell row (for
+//      q = 1 the wave reads one contiguous run of a pixel row); the byte goes to LDS at a pitch of 64.  Phase 2: one thread per
+//      candidate (du, dv); the template row is 8 aligned LDS dwords, the window row 9, shifted into place by v_alignbyte_b32 and summed
+//      four bytes at a time by v_sad_u8: 256 of them per candidate.  Phase 3: tree minimum of the 64-bit keys in LDS.
+//      follow_step_kernel: one workgroup per stream, one thread per slot (track_kernel's layout); output and ended positions are prefix
+//      counts, so slot order comes out without atomics.  Every loop is bounded: 4096 cells, q <= 385 pixels per cell edge, 1089
+//      candidates, 256 slots.  Nothing outside a frame is read (follow_cell clamps every coordinate).
+// =============================================================================================
+__device__ inline FollowFrame follow_frame(const FrameDesc &fd) {
+    FollowFrame f;
+    f.ptr = fd.ptr; f.rows = fd.rows; f.cols = fd.cols; f.step = fd.step;
+    return f;
+}
+
+__global__ __launch_bounds__(kThreads) void follow_keep_kernel(FollowParams a) {
+    const TrackStreamEntry se = a.streams[blockIdx.x];
+    const int slot = (int)blockIdx.y, T = a.spec.max_tracks, tid = (int)threadIdx.x;
+    const uint8_t *st = a.state + (size_t)se.stream * (sizeof(TrackHeader) + (size_t)T * sizeof(rf_track));
+    const rf_track *t = (const rf_track *)(st + sizeof(TrackHeader)) + slot;
+    const size_t entry = (size_t)se.stream * T + slot;
+    if (t->id == 0) {
+        if (tid < 8) ((int32_t *)(a.records + entry))[tid] = 0;
+        return;
+    }
+    if (t->last_frame != ((const TrackHeader *)st)->frames - 1) return;
+    const TrackImageEntry im = a.images[se.first];
+    const FollowFrame fd = follow_frame(a.frames[im.local]);
+    if (follow_frame_empty(fd)) return;                          // (a frame without pixels has no faces: nothing was matched in it)
+    const float box[4] = {t->last.x1, t->last.y1, t->last.x2, t->last.y2};
+    const FollowGeom g = follow_geometry(box);
+    if (tid == 0) a.records[entry] = follow_record_key(g);
+    if (!g.valid) return;
+    const int j = tid >> 3, i0 = (tid & 7) * 4;                  // cells (i0 .. i0 + 3, j)
+    uint32_t v = 0;
+    for (int k = 0; k < 4; k++) v |= follow_cell(fd, g.ox + (i0 + k) * g.q, g.oy + j * g.q, g.q) << (8 * k);
+    ((uint32_t *)(a.templates + entry * kFollowCells))[tid] = v;
+}
+
+__global__ __launch_bounds__(kThreads) void follow_search_kernel(FollowParams a) {
+    __shared__ __attribute__((aligned(16))) uint8_t s_win[kFollowWin * kFollowWin + 16];      // pitch 64; the last row's ninth dword
+    __shared__ __attribute__((aligned(16))) uint32_t s_tpl[kFollowCells / 4];
+    __shared__ unsigned long long s_key[kThreads];
+    const TrackStreamEntry se = a.streams[blockIdx.x];
+    const int slot = (int)blockIdx.y, T = a.spec.max_tracks, tid = (int)threadIdx.x, R = a.fspec.radius;
+    const uint8_t *st = a.state + (size_t)se.stream * (sizeof(TrackHeader) + (size_t)T * sizeof(rf_track));
+    const rf_track *t = (const rf_track *)(st + sizeof(TrackHeader)) + slot;
+    const size_t entry = (size_t)se.stream * T + slot;
+    FollowResult *res = a.results + (size_t)blockIdx.x * T + slot;
+    const rf_track_follow rec = a.records[entry];
+    const TrackImageEntry im = a.images[se.first];
+    const FollowFrame fd = follow_frame(a.frames[im.local]);
+    if (t->id == 0 || rec.q < 1 || !follow_attempted(rec, a.fspec.max_run, fd)) {      // the same for every thread of the workgroup
+        if (tid == 0) *res = FollowResult{0, -1, 0, 0};
+        return;
+    }
+    const int q = rec.q, ox = rec.ox, oy = rec.oy, Wc = kFollowG + 2 * R;
+    for (int c = tid; c < Wc * Wc; c += kThreads) {
+        const int j = c / Wc, i = c - j * Wc;
+        s_win[j * kFollowWin + i] = (uint8_t)follow_cell(fd, ox + (i - R) * q, oy + (j - R) * q, q);
+    }
+    s_tpl[tid] = ((const uint32_t *)(a.templates + entry * kFollowCells))[tid];
+    __syncthreads();
+
+    const int side = 2 * R + 1, n_cand = side * side;
+    unsigned long long best = kFollowNoKey;
+    for (int c = tid; c < n_cand; c += kThreads) {
+        const int dvr = c / side, dur = c - dvr * side;          // dv + R, du + R
+        if (!follow_eligible(ox, oy, q, dur - R, dvr - R, fd.rows, fd.cols)) continue;
+        const unsigned sh = (unsigned)(dur & 3);
+        const uint32_t *w = (const uint32_t *)s_win + dvr * (kFollowWin / 4) + (dur >> 2);
+        unsigned sad = 0;
+        for (int j = 0; j < kFollowG; j++, w += kFollowWin / 4) {
+            const uint32_t *tp = s_tpl + j * (kFollowG / 4);
+            uint32_t lo = w[0];
+#pragma unroll
+            for (int k = 0; k < kFollowG / 4; k++) {
+                const uint32_t hi = w[k + 1];
+                sad = __builtin_amdgcn_sad_u8(tp[k], __builtin_amdgcn_alignbyte(hi, lo, sh), sad);
+                lo = hi;
+            }
+        }
+        const unsigned long long key = follow_key(sad, dur - R, dvr - R, R);
+        best = key < best ? key : best;
+    }
+    s_key[tid] = best;
+    __syncthreads();
+    for (int d = kThreads / 2; d >= 1; d >>= 1) {
+        if (tid < d) { const unsigned long long o = s_key[tid + d]; if (o < s_key[tid]) s_key[tid] = o; }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        FollowResult r = {1, -1, 0, 0};
+        const unsigned long long key = s_key[0];
+        if (key != kFollowNoKey) { r.state = 2; follow_key_decode(key, R, &r.sad, &r.du, &r.dv); }
+        *res = r;
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void follow_step_kernel(FollowParams a) {
+#pragma clang fp contract(off)
+    __shared__ int s_cnt[kThreads / 64];
+    constexpr int kWords = (int)(sizeof(rf_track) / 4);
+    const int tid = (int)threadIdx.x, nw = (int)blockDim.x >> 6;
+    const TrackStreamEntry se = a.streams[blockIdx.x];
+    const int T = a.spec.max_tracks;
+    uint8_t *st = a.state + (size_t)se.stream * (sizeof(TrackHeader) + (size_t)T * sizeof(rf_track));
+    TrackHeader *hdr = (TrackHeader *)st;
+    rf_track *g = (rf_track *)(st + sizeof(TrackHeader));
+    const TrackImageEntry im = a.images[se.first];
+    const long long f = hdr->frames;
+    const bool has_slot = tid < T;
+    const bool live = has_slot && g[has_slot ? tid : 0].id != 0;
+    const size_t entry = (size_t)se.stream * T + (has_slot ? tid : 0);
+    bool accepted = false, ends = false;
+    rf_track_follow rec = follow_record_zero();
+    if (live) {
+        rec = a.records[entry];
+        const FollowResult r = a.results[(size_t)blockIdx.x * T + tid];
+        accepted = follow_accepted(r, a.fspec.max_mad);
+        if (accepted) {
+            rf_face last = g[tid].last;
+            follow_move(&last, &rec, r);
+            g[tid].last = last;
+        } else {
+            follow_reject(&rec, r);
+            ends = track_age(&g[tid], a.spec.max_missed);
+        }
+    }
+    int n_out = 0;
+    const int opos = track_prefix_count(accepted, nw, s_cnt, &n_out);
+    if (accepted && opos < a.cap_per_image) {
+        a.out[(size_t)im.image * a.cap_per_image + opos] = g[tid].last;
+        if (opos < a.tag_stride) a.tags[(size_t)im.image * a.tag_stride + opos] = track_tag(&g[tid], tid, f, a.spec.min_hits, RF_TRACK_FOLLOWED);
+    }
+    int n_ended = 0;
+    const int epos = track_prefix_count(ends, nw, s_cnt, &n_ended);
+    if (ends) {
+        uint32_t *rec32 = (uint32_t *)&g[tid];
+        if (epos < a.cap_ended) {
+            uint32_t *dst = (uint32_t *)(a.ended + (size_t)im.image * a.cap_ended + epos);
+            for (int i = 0; i < kWords; i++) dst[i] = rec32[i];
+        }
+        for (int i = 0; i < kWords; i++) rec32[i] = 0u;
+        rec = follow_record_zero();
+    }
+    if (live) a.records[entry] = rec;
+    if (tid == 0) {
+        a.counts[im.image] = n_out;
+        a.ended_counts[im.image] = n_ended;
+        a.status[im.image] = n_out > a.cap_per_image ? kTrackOverflow : 0;
+        hdr->frames = f + 1;
+    }
+}
+
+static void follow_check(const FollowParams &p) {
+    if (p.spec.max_tracks < 1 || p.spec.max_tracks > kTrackMaxTracks) throw Unsupported("follow: max_tracks must be in [1, 256]");
+    if (p.fspec.radius < 1 || p.fspec.radius > kFollowMaxRadius) throw Unsupported("follow: radius must be in [1, 16]");
+}
+void launch_follow_keep(hipStream_t s, const FollowParams &p) {
+    if (p.n_streams <= 0) return;
+    follow_check(p);
+    hipLaunchKernelGGL(follow_keep_kernel, dim3(p.n_streams, p.spec.max_tracks), dim3(kThreads), 0, s, p);
+}
+void launch_follow_search(hipStream_t s, const FollowParams &p) {
+    if (p.n_streams <= 0) return;
+    follow_check(p);
+    hipLaunchKernelGGL(follow_search_kernel, dim3(p.n_streams, p.spec.max_tracks), dim3(kThreads), 0, s, p);
+}
+void launch_follow_step(hipStream_t s, const FollowParams &p) {
+    if (p.n_streams <= 0) return;
+    follow_check(p);
+    hipLaunchKernelGGL(follow_step_kernel, dim3(p.n_streams), dim3((p.spec.max_tracks + 63) / 64 * 64), 0, s, p);
+}
+
+// =============================================================================================
 // K_k: face redaction (redact.h), in place in the frames of a launch.  Three launches ordered on the stream, race-free by
 //      construction: redact_regions_kernel writes region records, redact_mean_kernel only READS frames and writes cell values,
 //      redact_write_kernel reads only records, cell values and spec constants and writes the pixels each region owns -- every pixel

@@ -15,7 +15,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import (rf_face, rf_face_batch_spec, rf_face_gate, rf_face_quality, rf_options, rf_overlay_spec, rf_redact_spec, rf_tile_spec, rf_track,
-                   rf_dewarp_spec, rf_enhance_spec, rf_motion_spec, rf_pyramid_spec, rf_rot_spec, rf_shot, rf_track_motion, rf_track_spec, rf_track_tag, rf_tta_spec)
+                   rf_dewarp_spec, rf_enhance_spec, rf_motion_spec, rf_pyramid_spec, rf_rot_spec, rf_shot, rf_track_motion, rf_track_spec, rf_track_tag, rf_tta_spec,
+                   rf_follow_spec, rf_track_follow)
 
 PRECISION_FP32, PRECISION_FP16, PRECISION_INT8 = 0, 1, 2
 
@@ -311,6 +312,126 @@ def track_step(table: np.ndarray, frames: int, next_id: int, faces, coord_scale:
     return tags[:count], ended[:min(ne.value, cap_ended)], f.value, nid.value, st == _lib.RF_ERR_TRUNCATED
 
 
+# ---- followed tracks (follow.h): one rf_track_follow record (32 bytes); a template is 32 x 32 bytes
+FOLLOW_DTYPE = np.dtype([(k, "<i4") for k in ("valid", "run", "q", "ox", "oy", "sad", "dx", "dy")])
+FOLLOW_G = 32
+TRACK_FOLLOWED = _lib.RF_TRACK_FOLLOWED
+
+
+def follow_spec(radius: int = 0, max_mad: int = 0, max_run: int = 0) -> rf_follow_spec:
+    """rf_follow_spec; 0 = the default (radius 8 cells, mean absolute difference 16, 8 follow steps between key steps)"""
+    s = rf_follow_spec()
+    s.struct_size = C.sizeof(rf_follow_spec)
+    s.radius, s.max_mad, s.max_run, s.reserved = int(radius), int(max_mad), int(max_run), 0
+    return s
+
+
+def _as_follow_spec(spec):
+    if spec is None or isinstance(spec, rf_follow_spec):
+        return spec
+    return follow_spec(**spec)
+
+
+def _frame_view(frame):
+    """(address, rows, cols, step) of a (rows, cols, 3) u8 view whose pixels are contiguous (rows may be strided); None: no pixels"""
+    if frame is None or frame.size == 0:
+        return None, 0, 0, 0
+    if frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3 or frame.strides[2] != 1 or frame.strides[1] != 3:
+        raise ValueError("frame must be a (rows, cols, 3) uint8 view with contiguous pixels")
+    return frame.ctypes.data, frame.shape[0], frame.shape[1], frame.strides[0]
+
+
+def follow_geometry(box):
+    """rf_follow_geometry (host only): (q, ox, oy) of a box (x1, y1, x2, y2), or None for an invalid geometry"""
+    b = (C.c_float * 4)(*[float(v) for v in box])
+    out = (C.c_int32 * 3)()
+    st = _lib.load_library().rf_follow_geometry(b, out)
+    if st < 0:
+        raise _lib.RFError(st, "rf_follow_geometry: bad argument")
+    return (out[0], out[1], out[2]) if st else None
+
+
+def follow_template(frame: np.ndarray, q: int, ox: int, oy: int) -> np.ndarray:
+    """rf_follow_template (host only): the (32, 32) u8 template of the lattice (q, ox, oy) in a frame"""
+    ptr, rows, cols, step = _frame_view(frame)
+    tpl = np.zeros((FOLLOW_G, FOLLOW_G), np.uint8)
+    st = _lib.load_library().rf_follow_template(ptr, rows, cols, step, int(q), int(ox), int(oy), tpl.ctypes.data)
+    if st < 0:
+        raise _lib.RFError(st, "rf_follow_template: bad argument")
+    return tpl
+
+
+def follow_search(frame: np.ndarray, tpl: np.ndarray, q: int, ox: int, oy: int, radius: int = 8):
+    """rf_follow_search (host only): (state, sad, du, dv); state 1 = no eligible candidate, 2 = the winner"""
+    ptr, rows, cols, step = _frame_view(frame)
+    t = np.ascontiguousarray(tpl, np.uint8)
+    if t.size != FOLLOW_G * FOLLOW_G:
+        raise ValueError("a template is 32 x 32 bytes")
+    out = (C.c_int32 * 4)()
+    st = _lib.load_library().rf_follow_search(ptr, rows, cols, step, t.ctypes.data, int(q), int(ox), int(oy), int(radius), out)
+    if st < 0:
+        raise _lib.RFError(st, "rf_follow_search: bad argument")
+    return tuple(int(v) for v in out)
+
+
+def _follow_state(table, records, templates):
+    T = len(table)
+    if records.dtype != FOLLOW_DTYPE or len(records) != T or not records.flags.c_contiguous:
+        raise ValueError("records must be a contiguous FOLLOW_DTYPE array with one record per slot")
+    if templates.dtype != np.uint8 or templates.size != T * FOLLOW_G * FOLLOW_G or not templates.flags.c_contiguous:
+        raise ValueError("templates must be a contiguous (max_tracks, 32, 32) uint8 array")
+
+
+def track_step_follow_key(table: np.ndarray, records: np.ndarray, templates: np.ndarray, frames: int, next_id: int, frame, faces,
+                          coord_scale: float = 1.0, quality=None, max_faces: int = 256, cap_ended: Optional[int] = None, **spec):
+    """rf_track_step_follow_key (host only): track_step() plus the keep rule on caller-held records (FOLLOW_DTYPE) and templates
+    ((max_tracks, 32, 32) u8), all updated in place.  Returns (tags, ended, frames, next_id, truncated)."""
+    lib = _lib.load_library()
+    sp = track_spec(**spec)
+    _follow_state(table, records, templates)
+    ptr, rows, cols, step = _frame_view(frame)
+    fr = _face_rows(faces)
+    count = len(fr)
+    cap_ended = len(table) if cap_ended is None else int(cap_ended)
+    tags = np.zeros(max(count, 1), TRACK_TAG_DTYPE)
+    ended = np.zeros(max(cap_ended, 1), TRACK_DTYPE)
+    f, nid, ne = C.c_int64(frames), C.c_int64(next_id), C.c_int(0)
+    q = np.ascontiguousarray(quality, QUALITY_DTYPE) if quality is not None else None
+    st = lib.rf_track_step_follow_key(C.byref(sp), table.ctypes.data_as(C.POINTER(rf_track)), records.ctypes.data_as(C.POINTER(rf_track_follow)),
+                                      templates.ctypes.data, C.byref(f), C.byref(nid), ptr, rows, cols, step,
+                                      fr.ctypes.data_as(C.POINTER(rf_face)), count, float(coord_scale),
+                                      q.ctypes.data_as(C.POINTER(rf_face_quality)) if q is not None else None, int(max_faces),
+                                      tags.ctypes.data_as(C.POINTER(rf_track_tag)), ended.ctypes.data_as(C.POINTER(rf_track)), cap_ended, C.byref(ne))
+    if st < 0 and st != _lib.RF_ERR_TRUNCATED:
+        raise _lib.RFError(st, "rf_track_step_follow_key: bad spec or argument")
+    return tags[:count if ptr else 0], ended[:min(ne.value, cap_ended)], f.value, nid.value, st == _lib.RF_ERR_TRUNCATED
+
+
+def track_step_follow(table: np.ndarray, records: np.ndarray, templates: np.ndarray, frames: int, frame, cap: Optional[int] = None,
+                      cap_ended: Optional[int] = None, fspec=None, **spec):
+    """rf_track_step_follow (host only): one follow step on caller-held state.  Returns (followed faces (k, 15) float32, tags, count,
+    ended, ended_count, frames, truncated); fspec: follow_spec() or its keywords as a dict."""
+    lib = _lib.load_library()
+    sp = track_spec(**spec)
+    fs = _as_follow_spec(fspec)
+    _follow_state(table, records, templates)
+    ptr, rows, cols, step = _frame_view(frame)
+    cap = len(table) if cap is None else int(cap)
+    cap_ended = len(table) if cap_ended is None else int(cap_ended)
+    out = np.zeros((max(cap, 1), 15), np.float32)
+    tags = np.zeros(max(cap, 1), TRACK_TAG_DTYPE)
+    ended = np.zeros(max(cap_ended, 1), TRACK_DTYPE)
+    f, cnt, ne = C.c_int64(frames), C.c_int(0), C.c_int(0)
+    st = lib.rf_track_step_follow(C.byref(sp), C.byref(fs) if fs is not None else None, table.ctypes.data_as(C.POINTER(rf_track)),
+                                  records.ctypes.data_as(C.POINTER(rf_track_follow)), templates.ctypes.data, C.byref(f), ptr, rows, cols, step,
+                                  out.ctypes.data_as(C.POINTER(rf_face)), tags.ctypes.data_as(C.POINTER(rf_track_tag)), cap, C.byref(cnt),
+                                  ended.ctypes.data_as(C.POINTER(rf_track)), cap_ended, C.byref(ne))
+    if st < 0 and st != _lib.RF_ERR_TRUNCATED:
+        raise _lib.RFError(st, "rf_track_step_follow: bad spec or argument")
+    k = min(cnt.value, cap)
+    return out[:k], tags[:k], cnt.value, ended[:min(ne.value, cap_ended)], ne.value, f.value, st == _lib.RF_ERR_TRUNCATED
+
+
 REDACT_PIXELATE, REDACT_FILL = _lib.RF_REDACT_PIXELATE, _lib.RF_REDACT_FILL
 REDACT_RECT, REDACT_ELLIPSE = _lib.RF_REDACT_RECT, _lib.RF_REDACT_ELLIPSE
 
@@ -446,9 +567,10 @@ class Tracker:
     tracked call last_tags ((n, cap) TRACK_TAG_DTYPE), last_ended ((n, cap_ended) TRACK_DTYPE) and last_ended_counts hold the call's
     whole buffers and truncated says whether a table was full or an ended list was cut."""
 
-    def __init__(self, det: "RetinaFace", n_streams: int, motion=None, **spec):
+    def __init__(self, det: "RetinaFace", n_streams: int, motion=None, follow=None, **spec):
         self._det, self._lib = det, det._lib
         self.motion_spec = None
+        self.follow_spec = None
         self.spec = track_spec(**spec)
         self.max_tracks = self.spec.max_tracks or 64
         self.n_streams = int(n_streams)
@@ -460,6 +582,12 @@ class Tracker:
         if motion is not None:
             try:
                 self.enable_motion(**({} if motion is True else motion))
+            except Exception:
+                self.close()
+                raise
+        if follow is not None:
+            try:
+                self.enable_follow(**({} if follow is True else follow))
             except Exception:
                 self.close()
                 raise
@@ -524,6 +652,93 @@ class Tracker:
         _lib.check(self._lib.rf_tracker_read_motion(self._t, int(stream), rec.ctypes.data_as(C.POINTER(rf_track_motion)), self.max_tracks),
                    self._det._h)
         return rec
+
+    # ------------------------------------------------------------------ followed tracks
+    def enable_follow(self, **spec):
+        """rf_tracker_enable_follow: give the tracker templates; keywords as follow_spec().  From then on only the follow calls take it."""
+        sp = follow_spec(**spec)
+        _lib.check(self._lib.rf_tracker_enable_follow(self._t, C.byref(sp)), self._det._h)
+        self.follow_spec = sp
+        return self
+
+    def read_follow(self, stream: int):
+        """rf_tracker_read_follow: (records (max_tracks,) FOLLOW_DTYPE, templates (max_tracks, 32, 32) u8) of a stream"""
+        rec = np.zeros(self.max_tracks, FOLLOW_DTYPE)
+        tpl = np.zeros((self.max_tracks, FOLLOW_G, FOLLOW_G), np.uint8)
+        _lib.check(self._lib.rf_tracker_read_follow(self._t, int(stream), rec.ctypes.data_as(C.POINTER(rf_track_follow)), tpl.ctypes.data,
+                                                    self.max_tracks), self._det._h)
+        return rec, tpl
+
+    def _frame_args(self, ptrs, rows, cols, steps):
+        n = len(ptrs)
+        p = (C.c_void_p * max(n, 1))(*ptrs)
+        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
+        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        return p, r, c, s
+
+    def update_follow(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], streams: Sequence[int], faces, *,
+                      steps: Optional[Sequence[int]] = None, coord_scale: Optional[Sequence[float]] = None, quality=None,
+                      cap_per_image: Optional[int] = None, cap_ended: Optional[int] = None):
+        """rf_track_follow_update_device: a key step -- update() against frames resident in device memory + the keep rule.  Returns
+        (tags per image, ended tracks per image)."""
+        n = len(streams)
+        per = [_face_rows(f) for f in faces]
+        mf = self._det.max_detections
+        cap = int(cap_per_image) if cap_per_image is not None else max([len(r) for r in per] + [1])
+        flat = np.zeros((max(n, 1), cap, 15), np.float32)
+        counts = (C.c_int * max(n, 1))()
+        for i, r in enumerate(per):
+            flat[i, :min(len(r), cap)] = r[:cap]
+            counts[i] = len(r)
+        q = None
+        if quality is not None:
+            q = np.zeros((max(n, 1), mf), QUALITY_DTYPE)
+            for i, rec in enumerate(quality):
+                if rec is not None and len(rec):
+                    q[i, :min(len(rec), mf)] = np.asarray(rec, QUALITY_DTYPE)[:mf]
+        cs = (C.c_float * max(n, 1))(*coord_scale) if coord_scale is not None else None
+        p, r, c, s = self._frame_args(ptrs, rows, cols, steps)
+        t, _, tags, ended, ce, ec = self._buffers(n, cap, cap_ended)
+        st = _lib.check(self._lib.rf_track_follow_update_device(self._det._h, t, p, r, c, s, n, (C.c_int * max(n, 1))(*streams),
+                                                                flat.ctypes.data_as(C.POINTER(rf_face)), cap, counts, cs,
+                                                                q.ctypes.data_as(C.POINTER(rf_face_quality)) if q is not None else None, tags, ended,
+                                                                ce, ec), self._det._h)
+        self.truncated = st == _lib.RF_ERR_TRUNCATED
+        self.last_counts = [0 if not ptrs[i] or rows[i] <= 0 or cols[i] <= 0 else int(counts[i]) for i in range(n)]
+        return self._results(n, self.last_counts, cap)
+
+    def _follow_call(self, fn, ptrs, rows, cols, streams, steps, cap_per_image, cap_ended):
+        n = len(streams)
+        cap = self.max_tracks if cap_per_image is None else int(cap_per_image)
+        p, r, c, s = self._frame_args(ptrs, rows, cols, steps)
+        self.last_out = np.zeros((max(n, 1), max(cap, 1), 15), np.float32)
+        counts = (C.c_int * max(n, 1))()
+        t, _, tags, ended, ce, ec = self._buffers(n, cap, cap_ended)
+        st = _lib.check(fn(self._det._h, t, p, r, c, s, n, (C.c_int * max(n, 1))(*streams), self.last_out.ctypes.data_as(C.POINTER(rf_face)), cap,
+                           counts, tags, ended, ce, ec), self._det._h)
+        self.truncated = st == _lib.RF_ERR_TRUNCATED
+        self.last_counts = [int(counts[i]) for i in range(n)]
+        faces = [self.last_out[i, :min(self.last_counts[i], cap)].copy() for i in range(n)]
+        return (faces,) + self._results(n, self.last_counts, cap)
+
+    def follow_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], streams: Sequence[int], *,
+                      steps: Optional[Sequence[int]] = None, cap_per_image: Optional[int] = None, cap_ended: Optional[int] = None):
+        """rf_track_follow_device: a follow step over frames resident in device memory -- no forward pass.  Returns (followed faces
+        per image ((k, 15) float32, slot-ascending), their tags, ended tracks per image); last_counts holds the true numbers."""
+        return self._follow_call(self._lib.rf_track_follow_device, ptrs, rows, cols, streams, steps, cap_per_image, cap_ended)
+
+    def follow(self, imgs: Sequence[np.ndarray], streams: Sequence[int], *, cap_per_image: Optional[int] = None,
+               cap_ended: Optional[int] = None):
+        """rf_track_follow_batch: follow_device() over host frames ((rows, cols, 3) u8 views; None or empty = no pixels)"""
+        views = [_frame_view(im) for im in imgs]
+        return self._follow_call(self._lib.rf_track_follow_batch, [v[0] for v in views], [v[1] for v in views], [v[2] for v in views], streams,
+                                 [v[3] for v in views], cap_per_image, cap_ended)
+
+    def follow_last_launch_ms(self) -> float:
+        """rf_follow_last_launch_ms: HIP-event time of the search and step launches of the most recent follow_device()"""
+        ms = C.c_float()
+        _lib.check(self._lib.rf_follow_last_launch_ms(self._det._h, C.byref(ms)), self._det._h)
+        return float(ms.value)
 
     # ------------------------------------------------------------------ best-shot gallery
     def enable_shots(self, **spec):
@@ -1546,10 +1761,11 @@ class RetinaFace:
         return (self._collect_tiled(out, counts, src, n, cap, False),) + res
 
     # ------------------------------------------------------------------ face tracks
-    def tracker(self, n_streams: int = 1, motion=None, **spec) -> Tracker:
+    def tracker(self, n_streams: int = 1, motion=None, follow=None, **spec) -> Tracker:
         """rf_tracker_create: a tracker on this handle; keywords as track_spec().  motion: True or motion_spec()'s keywords as a dict
-        also gives it motion (Tracker.enable_motion)."""
-        return Tracker(self, n_streams, motion=motion, **spec)
+        also gives it motion (Tracker.enable_motion); follow: True or follow_spec()'s keywords as a dict gives it follow
+        (Tracker.enable_follow)."""
+        return Tracker(self, n_streams, motion=motion, follow=follow, **spec)
 
     def _run_tracked(self, fn, ptrs, rows, cols, steps, n, threshold, tracker, streams, cap_ended):
         cap = self.max_detections
@@ -1591,6 +1807,32 @@ class RetinaFace:
         r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
         s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
         return self._run_tracked(self._lib.rf_detect_track_batch_device, p, r, c, s, n, threshold, tracker, streams, cap_ended)
+
+    def detect_track_follow_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], tracker: Tracker, streams: Sequence[int],
+                                   threshold: float = 0.5, steps: Optional[Sequence[int]] = None, cap_ended: Optional[int] = None):
+        """rf_detect_track_follow_batch_device: a key step -- detect_tracked_device on a tracker with follow, the templates of the matched
+        and opened tracks retaken behind the track launch (each stream at most once per call)."""
+        n = len(ptrs)
+        p = (C.c_void_p * max(n, 1))(*ptrs)
+        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
+        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        return self._run_tracked(self._lib.rf_detect_track_follow_batch_device, p, r, c, s, n, threshold, tracker, streams, cap_ended)
+
+    def detect_followed(self, imgs: Sequence[np.ndarray], tracker: Tracker, streams: Sequence[int], key: bool, threshold: float = 0.5,
+                        cap_ended: Optional[int] = None):
+        """The key / follow schedule over host frames on a tracker with follow: key=True runs rf_detect_track_follow_batch (detection +
+        frame step + templates) and returns (detections, tags, ended); key=False runs rf_track_follow_batch (no forward pass) and
+        returns (followed faces per image as (k, 15) float32, tags, ended)."""
+        if not key:
+            return tracker.follow(imgs, streams, cap_ended=cap_ended)
+        n = len(imgs)
+        keep = [im if im is None or im.size == 0 or (im.strides[2] == 1 and im.strides[1] == 3) else np.ascontiguousarray(im) for im in imgs]
+        views = [_frame_view(im) for im in keep]
+        ptrs = (C.c_void_p * max(n, 1))(*[v[0] for v in views])
+        rows, cols, steps = ((C.c_int * max(n, 1))(*[v[k] for v in views]) for k in (1, 2, 3))
+        res = self._run_tracked(self._lib.rf_detect_track_follow_batch, ptrs, rows, cols, steps, n, threshold, tracker, streams, cap_ended)
+        del keep
+        return res
 
     def detect_track_face_batch_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], tracker: Tracker,
                                        streams: Sequence[int], threshold: float = 0.5, steps: Optional[Sequence[int]] = None,
