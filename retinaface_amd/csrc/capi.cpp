@@ -78,6 +78,38 @@ template <typename F> int guarded(rf_engine *h, F &&f) {
     } catch (const std::exception &e) { err = e.what(); return RF_ERR_INVALID_ARG; }
 }
 
+// guarded() for a call that can run into the engine's caps: f(bool *truncated) does all of the call's work and returns the status it
+// would have without that flag (with h->error set where that is not RF_OK); a set flag wins over it.
+template <typename F> int guarded_caps(rf_engine *h, F &&f) {
+    return guarded(h, [&]() -> int {
+        bool truncated = false;
+        const int st = f(&truncated);
+        if (truncated) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        return st;
+    });
+}
+
+// What the four rf_*_merge_host calls share once the mapped candidates of their passes are gathered (group g = pass * max_detections
+// + index): the merge, the heads emitted to the caller (at most min(cap, max_faces)), the true count, and the status.  *emitted: the
+// number of heads written, for a caller that goes on with them.
+int merge_host_emit(const std::vector<float> &cand, const std::vector<int> &g, float nms_threshold, bool vote, int cap, int max_faces,
+                    int max_detections, bool truncated, rf_face *out, int *count, int *votes, int *src, int *emitted = nullptr) {
+    const int limit = cap < max_faces ? cap : max_faces;
+    std::vector<float> merged((size_t)limit * 15 + 1);
+    std::vector<int> vt((size_t)limit + 1), hg((size_t)limit + 1);
+    const int heads = rf::tta_merge_candidates(cand, g, nms_threshold, vote, limit, merged.data(), vt.data(), hg.data());
+    *count = heads;
+    const int k = heads < limit ? heads : limit;
+    for (int j = 0; j < k; j++) {
+        memset(&out[j], 0, sizeof(rf_face));
+        memcpy(&out[j], &merged[(size_t)j * 15], 15 * sizeof(float));
+        if (votes) votes[j] = vt[j];
+        if (src) src[j] = hg[j] / max_detections;
+    }
+    if (emitted) *emitted = k;
+    return truncated || heads > limit ? RF_ERR_TRUNCATED : RF_OK;
+}
+
 
 rf::AlignRequest align_request(int crop_size, int max_faces, void *d_crops, uint8_t *crops, double *matrices) {
     rf::AlignRequest rq;
@@ -162,10 +194,8 @@ int rf_get_net_size(rf_handle h, int *net_h, int *net_w, int *max_batch) {
 static int detect_common(rf_handle h, const uint8_t *const *frames, const int *rows, const int *cols, const int *steps,
                          int n, bool on_device, float thr, rf_face *out, int cap, int *counts) {
     if (!h) return RF_ERR_INVALID_ARG;
-    return guarded(h, [&]() -> int {
-        bool tr = false;
-        h->eng->detect(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr);
-        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+    return guarded_caps(h, [&](bool *tr) -> int {
+        h->eng->detect(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, tr);
         return RF_OK;
     });
 }
@@ -206,10 +236,9 @@ rf::Engine *pool_engine(rf_engine *h, int hs, int ws) {
 int rf_detect_batch_pad32(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
                           int on_device, float threshold, rf_face *out, int cap_per_image, int *counts) {
     if (!h) return RF_ERR_INVALID_ARG;
-    return guarded(h, [&]() -> int {
+    return guarded_caps(h, [&](bool *truncated) -> int {
         if (n < 0 || (n > 0 && (!bgr || !rows || !cols || !counts))) throw rf::ArgError("null argument");
         std::vector<char> done(n, 0);
-        bool truncated = false;
         for (int i = 0; i < n; i++) {
             if (done[i]) continue;
             if (!bgr[i] || rows[i] <= 0 || cols[i] <= 0) { counts[i] = 0; done[i] = 1; continue; }    // img.empty(), :945-947
@@ -225,10 +254,10 @@ int rf_detect_batch_pad32(rf_handle h, const uint8_t *const *bgr, const int *row
             std::vector<int> r(m), c(m), st(m), cnt(m);
             for (int k = 0; k < m; k++) { f[k] = bgr[idx[k]]; r[k] = rows[idx[k]]; c[k] = cols[idx[k]]; st[k] = steps ? steps[idx[k]] : cols[idx[k]] * 3; }
             std::vector<rf_face> tmp((size_t)m * std::max(cap_per_image, 0));
-            bool tr = false;
+            bool cut = false;
             eng.detect(f.data(), r.data(), c.data(), st.data(), m, on_device != 0, threshold, out ? tmp.data() : nullptr, cap_per_image,
-                       cnt.data(), &tr);
-            truncated = truncated || tr;
+                       cnt.data(), &cut);
+            *truncated = *truncated || cut;
             for (int k = 0; k < m; k++) {
                 counts[idx[k]] = cnt[k];
                 if (out)
@@ -237,7 +266,6 @@ int rf_detect_batch_pad32(rf_handle h, const uint8_t *const *bgr, const int *row
                 done[idx[k]] = 1;
             }
         }
-        if (truncated) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
         return RF_OK;
     });
 }
@@ -259,13 +287,11 @@ namespace {
 int detect_align_common(rf_handle h, const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n,
                         bool on_device, float thr, rf_face *out, int cap, int *counts, const rf::AlignRequest &rq) {
     if (!h) return RF_ERR_INVALID_ARG;
-    return guarded(h, [&]() -> int {
-        bool tr = false;
+    return guarded_caps(h, [&](bool *tr) -> int {
         rf::StageCall sc;
         rf::StageResult res;
         sc.align = &rq;
-        h->eng->detect_staged(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, sc, &res);
-        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        h->eng->detect_staged(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, tr, sc, &res);
         return RF_OK;
     });
 }
@@ -310,15 +336,13 @@ int detect_face_batch_common(rf_handle h, const uint8_t *const *frames, const in
                              bool on_device, float thr, rf_face *out, int cap, int *counts, const rf_face_batch_spec *spec,
                              void *d_tensor, void *tensor, double *matrices, int *offsets) {
     if (!h) return RF_ERR_INVALID_ARG;
-    return guarded(h, [&]() -> int {
+    return guarded_caps(h, [&](bool *tr) -> int {
         rf::FaceBatchRequest rq;
         face_batch_request(spec, h->eng->default_max_faces(), d_tensor, tensor, matrices, offsets, &rq);
-        bool tr = false;
         rf::StageCall sc;
         rf::StageResult res;
         sc.face_batch = &rq;
-        h->eng->detect_staged(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, sc, &res);
-        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        h->eng->detect_staged(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, tr, sc, &res);
         if (res.overflow) { h->error = kFaceOverflow; return RF_ERR_TRUNCATED; }
         return RF_OK;
     });
@@ -410,16 +434,14 @@ int detect_face_batch_gated_common(rf_handle h, const uint8_t *const *frames, co
                                    void *d_tensor, void *tensor, double *matrices, int *offsets, const rf_face_gate *gate,
                                    rf_face_quality *quality) {
     if (!h) return RF_ERR_INVALID_ARG;
-    return guarded(h, [&]() -> int {
+    return guarded_caps(h, [&](bool *tr) -> int {
         rf::FaceBatchRequest rq;
         face_batch_request(spec, h->eng->default_max_faces(), d_tensor, tensor, matrices, offsets, &rq);
         face_gate_request(gate, quality, &rq);
-        bool tr = false;
         rf::StageCall sc;
         rf::StageResult res;
         sc.face_batch = &rq;
-        h->eng->detect_staged(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, sc, &res);
-        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        h->eng->detect_staged(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, tr, sc, &res);
         if (res.overflow) { h->error = kFaceOverflow; return RF_ERR_TRUNCATED; }
         return RF_OK;
     });
@@ -538,12 +560,11 @@ void tile_request(rf_handle h, const rf_tile_spec *spec, int *src_tile, rf::Tile
 int detect_tiled_common(rf_handle h, const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,
                         float thr, const rf_tile_spec *spec, rf_face *out, int cap, int *counts, int *src_tile) {
     if (!h) return RF_ERR_INVALID_ARG;
-    return guarded(h, [&]() -> int {
+    return guarded_caps(h, [&](bool *tr) -> int {
         rf::TileRequest rq;
         tile_request(h, spec, src_tile, &rq);
-        bool tr = false, over = false;
-        h->eng->detect_tiled(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, rq, &over);
-        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        bool over = false;
+        h->eng->detect_tiled(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, tr, rq, &over);
         return RF_OK;
     });
 }
@@ -563,12 +584,10 @@ int rf_detect_tiled_batch(rf_handle h, const uint8_t *const *bgr, const int *row
 int rf_tile_merge_device(rf_handle h, const int *rows, const int *cols, int n, const rf_tile_spec *spec, const rf_face *faces,
                          const int *pass_counts, rf_face *out, int cap_per_image, int *counts, int *src_tile) {
     if (!h) return RF_ERR_INVALID_ARG;
-    return guarded(h, [&]() -> int {
+    return guarded_caps(h, [&](bool *tr) -> int {
         rf::TileRequest rq;
         tile_request(h, spec, src_tile, &rq);
-        bool tr = false;
-        h->eng->tile_merge(rows, cols, n, rq, faces, pass_counts, out, cap_per_image, counts, &tr);
-        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        h->eng->tile_merge(rows, cols, n, rq, faces, pass_counts, out, cap_per_image, counts, tr);
         return RF_OK;
     });
 }
@@ -578,16 +597,15 @@ int rf_detect_tiled_face_batch_device(rf_handle h, const void *const *d_bgr, con
                                       int *src_tile, const rf_face_batch_spec *fb_spec, void *d_tensor, void *tensor, double *matrices,
                                       int *offsets, const rf_face_gate *gate, rf_face_quality *quality) {
     if (!h) return RF_ERR_INVALID_ARG;
-    return guarded(h, [&]() -> int {
+    return guarded_caps(h, [&](bool *tr) -> int {
         rf::TileRequest rq;
         tile_request(h, tile_spec, src_tile, &rq);
         rf::FaceBatchRequest fb;
         face_batch_request(fb_spec, h->eng->default_max_faces(), d_tensor, tensor, matrices, offsets, &fb);
         if (gate || quality) face_gate_request(gate, quality, &fb);
         rq.fb = &fb;
-        bool tr = false, over = false;
-        h->eng->detect_tiled((const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, out, cap_per_image, counts, &tr, rq, &over);
-        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        bool over = false;
+        h->eng->detect_tiled((const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, out, cap_per_image, counts, tr, rq, &over);
         if (over) { h->error = kFaceOverflow; return RF_ERR_TRUNCATED; }
         return RF_OK;
     });
@@ -624,16 +642,14 @@ int detect_track_common(rf_handle h, const uint8_t *const *frames, const int *ro
                         float thr, rf_face *out, int cap, int *counts, rf_tracker tracker, const int *stream_of_image, rf_track_tag *tags,
                         rf_track *ended, int cap_ended, int *ended_counts) {
     if (!h) return RF_ERR_INVALID_ARG;
-    return guarded(h, [&]() -> int {
+    return guarded_caps(h, [&](bool *tr) -> int {
         if (h->eng->num_devices() > 1) throw rf::Unsupported("face tracks are not available on a multi-device handle");
         rf::TrackRequest rq;
         track_request(h, tracker, stream_of_image, tags, ended, cap_ended, ended_counts, &rq);
-        bool tr = false;
         rf::StageCall sc;
         rf::StageResult res;
         sc.track = &rq;
-        h->eng->detect_staged(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, sc, &res);
-        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        h->eng->detect_staged(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, tr, sc, &res);
         if (res.track_cut) { h->error = kTrackCut; return RF_ERR_TRUNCATED; }
         return RF_OK;
     });
@@ -727,19 +743,17 @@ int rf_detect_track_face_batch_device(rf_handle h, const void *const *d_bgr, con
                                       rf_face_quality *quality, rf_tracker tracker, const int *stream_of_image, rf_track_tag *tags,
                                       rf_track *ended, int cap_ended, int *ended_counts) {
     if (!h) return RF_ERR_INVALID_ARG;
-    return guarded(h, [&]() -> int {
+    return guarded_caps(h, [&](bool *tr) -> int {
         if (h->eng->num_devices() > 1) throw rf::Unsupported("face tracks are not available on a multi-device handle");
         rf::FaceBatchRequest fb;
         face_batch_request(spec, h->eng->default_max_faces(), d_tensor, tensor, matrices, offsets, &fb);
         if (gate || quality) face_gate_request(gate, quality, &fb);
         rf::TrackRequest rq;
         track_request(h, tracker, stream_of_image, tags, ended, cap_ended, ended_counts, &rq);
-        bool tr = false;
         rf::StageCall sc;
         rf::StageResult res;
         sc.face_batch = &fb; sc.track = &rq;
-        h->eng->detect_staged((const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, out, cap_per_image, counts, &tr, sc, &res);
-        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        h->eng->detect_staged((const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, out, cap_per_image, counts, tr, sc, &res);
         if (res.overflow) { h->error = kFaceOverflow; return RF_ERR_TRUNCATED; }
         if (res.track_cut) { h->error = kTrackCut; return RF_ERR_TRUNCATED; }
         return RF_OK;
@@ -776,18 +790,16 @@ int detect_track_shots_common(rf_handle h, const uint8_t *const *frames, const i
                               rf_track *ended, int cap_ended, int *ended_counts, const rf_face_gate *gate, rf_face_quality *quality,
                               void *d_shots, void *shots, rf_shot *shot_info) {
     if (!h) return RF_ERR_INVALID_ARG;
-    return guarded(h, [&]() -> int {
+    return guarded_caps(h, [&](bool *tr) -> int {
         if (h->eng->num_devices() > 1) throw rf::Unsupported("face tracks are not available on a multi-device handle");
         rf::TrackRequest rq;
         track_request(h, tracker, stream_of_image, tags, ended, cap_ended, ended_counts, &rq);
         rf::ShotRequest sq;
         shot_request(gate, quality, d_shots, shots, shot_info, &sq);
-        bool tr = false;
         rf::StageCall sc;
         rf::StageResult res;
         sc.track = &rq; sc.shots = &sq;
-        h->eng->detect_staged(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, sc, &res);
-        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        h->eng->detect_staged(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, tr, sc, &res);
         if (res.track_cut) { h->error = kTrackCut; return RF_ERR_TRUNCATED; }
         return RF_OK;
     });
@@ -961,16 +973,14 @@ int detect_track_follow_common(rf_handle h, const uint8_t *const *frames, const 
                                float thr, rf_face *out, int cap, int *counts, rf_tracker tracker, const int *stream_of_image, rf_track_tag *tags,
                                rf_track *ended, int cap_ended, int *ended_counts) {
     if (!h) return RF_ERR_INVALID_ARG;
-    return guarded(h, [&]() -> int {
+    return guarded_caps(h, [&](bool *tr) -> int {
         if (h->eng->num_devices() > 1) throw rf::Unsupported("face tracks are not available on a multi-device handle");
         rf::TrackRequest rq;
         track_request(h, tracker, stream_of_image, tags, ended, cap_ended, ended_counts, &rq);
-        bool tr = false;
         rf::StageCall sc;
         rf::StageResult res;
         sc.track = &rq; sc.follow = true;
-        h->eng->detect_staged(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, sc, &res);
-        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        h->eng->detect_staged(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, tr, sc, &res);
         if (res.track_cut) { h->error = kTrackCut; return RF_ERR_TRUNCATED; }
         return RF_OK;
     });
@@ -1156,15 +1166,13 @@ int detect_redact_common(rf_handle h, const uint8_t *const *frames, const int *r
                          float thr, rf_face *out, int cap, int *counts, const rf_redact_spec *spec, uint8_t *const *out_bgr, const int *out_steps,
                          int32_t *pixels) {
     if (!h) return RF_ERR_INVALID_ARG;
-    return guarded(h, [&]() -> int {
+    return guarded_caps(h, [&](bool *tr) -> int {
         rf::RedactRequest rq;
         redact_request(h, spec, nullptr, nullptr, pixels, nullptr, &rq);
-        bool tr = false;
         rf::StageCall sc;
         rf::StageResult res;
         sc.redact = &rq; sc.out_bgr = out_bgr; sc.out_steps = out_steps;
-        h->eng->detect_staged(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, sc, &res);
-        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        h->eng->detect_staged(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, tr, sc, &res);
         if (res.redact_cut) { h->error = kRedactCut; return RF_ERR_TRUNCATED; }
         return RF_OK;
     });
@@ -1188,17 +1196,15 @@ int rf_detect_track_redact_batch_device(rf_handle h, void *const *d_bgr, const i
                                         const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_counts,
                                         const rf_redact_spec *spec, int32_t *pixels, int *region_counts) {
     if (!h) return RF_ERR_INVALID_ARG;
-    return guarded(h, [&]() -> int {
+    return guarded_caps(h, [&](bool *tr) -> int {
         rf::RedactRequest rq;
         redact_request(h, spec, tracker, stream_of_image, pixels, region_counts, &rq);
         rf::TrackRequest trq;
         track_request(h, tracker, stream_of_image, tags, ended, cap_ended, ended_counts, &trq);
-        bool tr = false;
         rf::StageCall sc;
         rf::StageResult res;
         sc.track = &trq; sc.redact = &rq;
-        h->eng->detect_staged((const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, out, cap_per_image, counts, &tr, sc, &res);
-        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        h->eng->detect_staged((const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, out, cap_per_image, counts, tr, sc, &res);
         if (res.track_cut) { h->error = kTrackCut; return RF_ERR_TRUNCATED; }
         if (res.redact_cut) { h->error = kRedactCut; return RF_ERR_TRUNCATED; }
         return RF_OK;
@@ -1251,15 +1257,13 @@ int detect_overlay_common(rf_handle h, const uint8_t *const *frames, const int *
                           float thr, rf_face *out, int cap, int *counts, const rf_overlay_spec *spec, uint8_t *const *out_bgr, const int *out_steps,
                           int32_t *pixels) {
     if (!h) return RF_ERR_INVALID_ARG;
-    return guarded(h, [&]() -> int {
+    return guarded_caps(h, [&](bool *tr) -> int {
         rf::RedactRequest rq;
         overlay_request(h, spec, nullptr, nullptr, pixels, nullptr, &rq);
-        bool tr = false;
         rf::StageCall sc;
         rf::StageResult res;
         sc.redact = &rq; sc.out_bgr = out_bgr; sc.out_steps = out_steps;
-        h->eng->detect_staged(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, sc, &res);
-        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        h->eng->detect_staged(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, tr, sc, &res);
         if (res.redact_cut) { h->error = kRedactCut; return RF_ERR_TRUNCATED; }
         return RF_OK;
     });
@@ -1308,17 +1312,15 @@ int rf_detect_track_overlay_batch_device(rf_handle h, void *const *d_bgr, const 
                                          const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_counts,
                                          const rf_overlay_spec *spec, int32_t *pixels, int *region_counts) {
     if (!h) return RF_ERR_INVALID_ARG;
-    return guarded(h, [&]() -> int {
+    return guarded_caps(h, [&](bool *tr) -> int {
         rf::RedactRequest rq;
         overlay_request(h, spec, tracker, stream_of_image, pixels, region_counts, &rq);
         rf::TrackRequest trq;
         track_request(h, tracker, stream_of_image, tags, ended, cap_ended, ended_counts, &trq);
-        bool tr = false;
         rf::StageCall sc;
         rf::StageResult res;
         sc.track = &trq; sc.redact = &rq;
-        h->eng->detect_staged((const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, out, cap_per_image, counts, &tr, sc, &res);
-        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        h->eng->detect_staged((const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, out, cap_per_image, counts, tr, sc, &res);
         if (res.track_cut) { h->error = kTrackCut; return RF_ERR_TRUNCATED; }
         if (res.redact_cut) { h->error = kRedactCut; return RF_ERR_TRUNCATED; }
         return RF_OK;
@@ -1362,18 +1364,7 @@ int rf_tta_merge_host(const rf_tta_spec *spec, int rows, int cols, int net_h, in
             }
         }
     }
-    const int limit = cap < sp.max_faces ? cap : sp.max_faces;
-    std::vector<float> merged((size_t)limit * 15 + 1);
-    std::vector<int> vt((size_t)limit + 1), hg((size_t)limit + 1);
-    const int heads = rf::tta_merge_candidates(cand, g, nms_threshold, sp.vote != 0, limit, merged.data(), vt.data(), hg.data());
-    *count = heads;
-    for (int k = 0; k < heads && k < limit; k++) {
-        memset(&out[k], 0, sizeof(rf_face));
-        memcpy(&out[k], &merged[(size_t)k * 15], 15 * sizeof(float));
-        if (votes) votes[k] = vt[k];
-        if (src_pass) src_pass[k] = hg[k] / max_detections;
-    }
-    return truncated || heads > limit ? RF_ERR_TRUNCATED : RF_OK;
+    return merge_host_emit(cand, g, nms_threshold, sp.vote != 0, cap, sp.max_faces, max_detections, truncated, out, count, votes, src_pass);
 }
 
 namespace {
@@ -1387,12 +1378,10 @@ void tta_request(rf_handle h, const rf_tta_spec *spec, int *votes, int *src_pass
 int detect_tta_common(rf_handle h, const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,
                       float thr, const rf_tta_spec *spec, rf_face *out, int cap, int *counts, int *votes, int *src_pass) {
     if (!h) return RF_ERR_INVALID_ARG;
-    return guarded(h, [&]() -> int {
+    return guarded_caps(h, [&](bool *tr) -> int {
         rf::TtaRequest rq;
         tta_request(h, spec, votes, src_pass, &rq);
-        bool tr = false;
-        h->eng->detect_tta(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, rq);
-        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        h->eng->detect_tta(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, tr, rq);
         return RF_OK;
     });
 }
@@ -1421,12 +1410,10 @@ int rf_detect_tta_batch(rf_handle h, const uint8_t *const *bgr, const int *rows,
 int rf_tta_merge_device(rf_handle h, const int *rows, const int *cols, int n, const rf_tta_spec *spec, const rf_face *faces,
                         const int *pass_counts, rf_face *out, int cap_per_image, int *counts, int *votes, int *src_pass) {
     if (!h) return RF_ERR_INVALID_ARG;
-    return guarded(h, [&]() -> int {
+    return guarded_caps(h, [&](bool *tr) -> int {
         rf::TtaRequest rq;
         tta_request(h, spec, votes, src_pass, &rq);
-        bool tr = false;
-        h->eng->tta_merge(rows, cols, n, rq, faces, pass_counts, out, cap_per_image, counts, &tr);
-        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        h->eng->tta_merge(rows, cols, n, rq, faces, pass_counts, out, cap_per_image, counts, tr);
         return RF_OK;
     });
 }
@@ -1493,23 +1480,13 @@ int rf_rot_merge_host(const rf_rot_spec *spec, int rows, int cols, int net_h, in
             p++;
         }
     }
-    const int limit = cap < sp.max_faces ? cap : sp.max_faces;
-    std::vector<float> merged((size_t)limit * 15 + 1);
-    std::vector<int> vt((size_t)limit + 1), hg((size_t)limit + 1);
-    std::vector<rf_face> heads_out((size_t)limit + 1);
-    const int heads = rf::tta_merge_candidates(cand, g, nms_threshold, sp.vote != 0, limit, merged.data(), vt.data(), hg.data());
-    *count = heads;
-    const int emitted = heads < limit ? heads : limit;
-    for (int j = 0; j < emitted; j++) {
-        memset(&heads_out[j], 0, sizeof(rf_face));
-        memcpy(&heads_out[j], &merged[(size_t)j * 15], 15 * sizeof(float));
-        out[j] = heads_out[j];
-        hg[j] /= max_detections;
-        if (votes) votes[j] = vt[j];
-        if (src_rot) src_rot[j] = hg[j];
-    }
-    rot_orientation(heads_out.data(), hg.data(), emitted, frame_rot, rot_score);
-    return truncated || heads > limit ? RF_ERR_TRUNCATED : RF_OK;
+    std::vector<int> own;                        // the orientation outputs need the rotation of every head
+    if (!src_rot) { own.resize((size_t)cap + 1); src_rot = own.data(); }
+    int emitted = 0;
+    const int st = merge_host_emit(cand, g, nms_threshold, sp.vote != 0, cap, sp.max_faces, max_detections, truncated, out, count, votes,
+                                   src_rot, &emitted);
+    rot_orientation(out, src_rot, emitted, frame_rot, rot_score);
+    return st;
 }
 
 int rf_rotate_host(const uint8_t *src, int rows, int cols, int step, int k, uint8_t *dst, int dst_step) {
@@ -1544,15 +1521,13 @@ int detect_rot_common(rf_handle h, const uint8_t *const *frames, const int *rows
                       float thr, const rf_rot_spec *spec, rf_face *out, int cap, int *counts, int *votes, int *src_rot, int *frame_rot,
                       float *rot_score) {
     if (!h) return RF_ERR_INVALID_ARG;
-    return guarded(h, [&]() -> int {
+    return guarded_caps(h, [&](bool *tr) -> int {
         rf::RotRequest rq;
         std::vector<int> own;                    // the orientation outputs need the rotation of every head
         if (!src_rot && (frame_rot || rot_score) && n > 0 && cap > 0) { own.assign((size_t)n * cap, 0); src_rot = own.data(); }
         rot_request(h, spec, votes, src_rot, &rq);
-        bool tr = false;
-        h->eng->detect_rot(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, rq);
+        h->eng->detect_rot(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, tr, rq);
         rot_orient_call(rq, n, src_rot ? out : nullptr, cap, counts, src_rot, frame_rot, rot_score);
-        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
         return RF_OK;
     });
 }
@@ -1584,15 +1559,13 @@ int rf_rot_merge_device(rf_handle h, const int *rows, const int *cols, int n, co
                         const int *pass_counts, rf_face *out, int cap_per_image, int *counts, int *votes, int *src_rot, int *frame_rot,
                         float *rot_score) {
     if (!h) return RF_ERR_INVALID_ARG;
-    return guarded(h, [&]() -> int {
+    return guarded_caps(h, [&](bool *tr) -> int {
         rf::RotRequest rq;
         std::vector<int> own;
         if (!src_rot && (frame_rot || rot_score) && n > 0 && cap_per_image > 0) { own.assign((size_t)n * cap_per_image, 0); src_rot = own.data(); }
         rot_request(h, spec, votes, src_rot, &rq);
-        bool tr = false;
-        h->eng->rot_merge(rows, cols, n, rq, faces, pass_counts, out, cap_per_image, counts, &tr);
+        h->eng->rot_merge(rows, cols, n, rq, faces, pass_counts, out, cap_per_image, counts, tr);
         rot_orient_call(rq, n, src_rot ? out : nullptr, cap_per_image, counts, src_rot, frame_rot, rot_score);
-        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
         return RF_OK;
     });
 }
@@ -1650,19 +1623,7 @@ int rf_dewarp_merge_host(const rf_dewarp_spec *spec, const int32_t *mesh, int vi
             g.push_back(v * max_detections + j);
         }
     }
-    const int limit = cap < sp.max_faces ? cap : sp.max_faces;
-    std::vector<float> merged((size_t)limit * 15 + 1);
-    std::vector<int> vt((size_t)limit + 1), hg((size_t)limit + 1);
-    const int heads = rf::tta_merge_candidates(cand, g, nms_threshold, sp.vote != 0, limit, merged.data(), vt.data(), hg.data());
-    *count = heads;
-    const int emitted = heads < limit ? heads : limit;
-    for (int j = 0; j < emitted; j++) {
-        memset(&out[j], 0, sizeof(rf_face));
-        memcpy(&out[j], &merged[(size_t)j * 15], 15 * sizeof(float));
-        if (votes) votes[j] = vt[j];
-        if (src_view) src_view[j] = hg[j] / max_detections;
-    }
-    return truncated || heads > limit ? RF_ERR_TRUNCATED : RF_OK;
+    return merge_host_emit(cand, g, nms_threshold, sp.vote != 0, cap, sp.max_faces, max_detections, truncated, out, count, votes, src_view);
 }
 
 int rf_dewarper_create(rf_handle h, int rows, int cols, int view_w, int view_h, int views, const int32_t *mesh, rf_dewarper *out_dewarper) {
@@ -1708,12 +1669,10 @@ int detect_dewarp_common(rf_dewarper dw, const uint8_t *const *frames, const int
                          int *src_view, void *d_views) {
     if (!dw) return RF_ERR_INVALID_ARG;
     rf_engine *h = dw->h;
-    return guarded(h, [&]() -> int {
+    return guarded_caps(h, [&](bool *tr) -> int {
         rf::DewarpRequest rq;
         dewarp_request(dw, spec, votes, src_view, d_views, &rq);
-        bool tr = false;
-        h->eng->detect_dewarp(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, rq);
-        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        h->eng->detect_dewarp(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, tr, rq);
         return RF_OK;
     });
 }
@@ -1736,12 +1695,10 @@ int rf_dewarp_merge_device(rf_dewarper dewarper, int n, const rf_dewarp_spec *sp
                            rf_face *out, int cap_per_image, int *counts, int *votes, int *src_view) {
     if (!dewarper) return RF_ERR_INVALID_ARG;
     rf_engine *h = dewarper->h;
-    return guarded(h, [&]() -> int {
+    return guarded_caps(h, [&](bool *tr) -> int {
         rf::DewarpRequest rq;
         dewarp_request(dewarper, spec, votes, src_view, nullptr, &rq);
-        bool tr = false;
-        h->eng->dewarp_merge(n, rq, faces, pass_counts, out, cap_per_image, counts, &tr);
-        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        h->eng->dewarp_merge(n, rq, faces, pass_counts, out, cap_per_image, counts, tr);
         return RF_OK;
     });
 }
@@ -1780,13 +1737,11 @@ int detect_enhanced_common(rf_handle h, const uint8_t *const *frames, const int 
                            bool on_device, float thr, const rf_enhance_spec *spec, rf_face *out, int cap, int *counts,
                            void *const *d_enhanced, const int *enhanced_steps, int *tiles_enhanced) {
     if (!h) return RF_ERR_INVALID_ARG;
-    return guarded(h, [&]() -> int {
+    return guarded_caps(h, [&](bool *tr) -> int {
         rf::EnhanceRequest rq;
         if (const char *bad = rf::enhance_spec_resolve(spec, &rq.spec)) throw rf::ArgError(bad);
         rq.d_enhanced = d_enhanced; rq.enhanced_steps = enhanced_steps; rq.tiles_enhanced = tiles_enhanced;
-        bool tr = false;
-        h->eng->detect_enhanced(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, rq);
-        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        h->eng->detect_enhanced(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, tr, rq);
         return RF_OK;
     });
 }
@@ -1875,18 +1830,8 @@ int rf_pyramid_merge_host(const rf_pyramid_spec *spec, int rows, int cols, int n
             g.push_back(p * max_detections + k);
         }
     }
-    const int limit = cap < sp.tile.max_faces ? cap : sp.tile.max_faces;
-    std::vector<float> merged((size_t)limit * 15 + 1);
-    std::vector<int> vt((size_t)limit + 1), hg((size_t)limit + 1);
-    const int heads = rf::tta_merge_candidates(cand, g, nms_threshold, sp.vote != 0, limit, merged.data(), vt.data(), hg.data());
-    *count = heads;
-    for (int k = 0; k < heads && k < limit; k++) {
-        memset(&out[k], 0, sizeof(rf_face));
-        memcpy(&out[k], &merged[(size_t)k * 15], 15 * sizeof(float));
-        if (votes) votes[k] = vt[k];
-        if (src_pass) src_pass[k] = hg[k] / max_detections;
-    }
-    return truncated || heads > limit ? RF_ERR_TRUNCATED : RF_OK;
+    return merge_host_emit(cand, g, nms_threshold, sp.vote != 0, cap, sp.tile.max_faces, max_detections, truncated, out, count, votes,
+                           src_pass);
 }
 
 int rf_zoom_host(const uint8_t *src, int rows, int cols, int step, int z, int x0, int y0, int tw, int th, uint8_t *dst, int dst_step) {
@@ -1913,12 +1858,10 @@ int detect_pyramid_common(rf_handle h, const uint8_t *const *frames, const int *
                           bool on_device, float thr, const rf_pyramid_spec *spec, rf_face *out, int cap, int *counts, int *votes,
                           int *src_pass) {
     if (!h) return RF_ERR_INVALID_ARG;
-    return guarded(h, [&]() -> int {
+    return guarded_caps(h, [&](bool *tr) -> int {
         rf::PyrRequest rq;
         pyr_request(h, spec, votes, src_pass, &rq);
-        bool tr = false;
-        h->eng->detect_pyramid(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, rq);
-        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        h->eng->detect_pyramid(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, tr, rq);
         return RF_OK;
     });
 }
@@ -1949,12 +1892,10 @@ int rf_detect_pyramid_batch(rf_handle h, const uint8_t *const *bgr, const int *r
 int rf_pyramid_merge_device(rf_handle h, const int *rows, const int *cols, int n, const rf_pyramid_spec *spec, const rf_face *faces,
                             const int *pass_counts, rf_face *out, int cap_per_image, int *counts, int *votes, int *src_pass) {
     if (!h) return RF_ERR_INVALID_ARG;
-    return guarded(h, [&]() -> int {
+    return guarded_caps(h, [&](bool *tr) -> int {
         rf::PyrRequest rq;
         pyr_request(h, spec, votes, src_pass, &rq);
-        bool tr = false;
-        h->eng->pyramid_merge(rows, cols, n, rq, faces, pass_counts, out, cap_per_image, counts, &tr);
-        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        h->eng->pyramid_merge(rows, cols, n, rq, faces, pass_counts, out, cap_per_image, counts, tr);
         return RF_OK;
     });
 }
@@ -2005,10 +1946,8 @@ int rf_launch_stats(rf_handle h, long long *launches, long long *images) {
 
 int rf_wait(rf_handle h, int ticket, rf_face *out, int cap_per_image, int *counts) {
     if (!h) return RF_ERR_INVALID_ARG;
-    return guarded(h, [&]() -> int {
-        bool tr = false;
-        h->eng->wait(ticket, out, cap_per_image, counts, &tr);
-        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+    return guarded_caps(h, [&](bool *tr) -> int {
+        h->eng->wait(ticket, out, cap_per_image, counts, tr);
         return RF_OK;
     });
 }

@@ -8,6 +8,7 @@ H x W x 3 BGR arrays.  Unlike the reference, which returns ``void`` and drops it
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple as _namedtuple
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
@@ -341,6 +342,72 @@ def _frame_view(frame):
     return frame.ctypes.data, frame.shape[0], frame.shape[1], frame.strides[0]
 
 
+def _dense_frame(frame: np.ndarray) -> np.ndarray:
+    """The rule of every call that reads a host frame: uint8 H x W x 3; pixels that are not dense (strides[1] != 3) are copied, a row
+    pitch is kept.  The caller owns the copy for as long as C reads it."""
+    if frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3:
+        raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
+    if frame.strides[2] != 1 or frame.strides[1] != 3:
+        frame = np.ascontiguousarray(frame)
+    return frame
+
+
+_HostFrames = _namedtuple("_HostFrames", "args keep")
+
+
+def _host_frames(imgs, in_place: Optional[str] = None) -> _HostFrames:
+    """The C arguments of a batch of host frames: args = (ptrs, rows, cols, steps, n), the first four ctypes arrays of max(n, 1)
+    entries, and keep = the arrays ptrs points into.  None and zero-size frames become (NULL, 0, 0, 0).
+
+    LIFETIME: ptrs holds raw addresses.  A frame whose pixels are not dense is copied (_dense_frame), and that copy is referenced by
+    `keep` ALONE -- so the caller must hold the returned tuple until the C call that was given ptrs has returned.  Passing args on and
+    dropping the tuple frees the copy under a host upload that is still reading it.
+
+    in_place ("redacted", "drawn into"): the call writes into the caller's frames, so nothing may be copied -- pixels that are not
+    dense and read-only frames are refused."""
+    n = len(imgs)
+    ptrs = (C.c_void_p * max(n, 1))()
+    rows, cols, steps = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
+    keep = []
+    for i, im in enumerate(imgs):
+        if im is None or im.size == 0:
+            continue                                   # the arrays are zero-initialised
+        if in_place is None:
+            im = _dense_frame(im)
+        elif im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 or im.strides[2] != 1 or im.strides[1] != 3:
+            raise ValueError("frames must be uint8 H x W x 3 with dense pixels (CV_8UC3, BGR)")
+        elif not im.flags.writeable:
+            raise ValueError("frames are %s in place: they must be writeable" % in_place)
+        keep.append(im)
+        ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
+    return _HostFrames((ptrs, rows, cols, steps, n), keep)
+
+
+def _device_frames(ptrs, rows, cols, steps=None):
+    """The C arguments (ptrs, rows, cols, steps; ctypes arrays of max(n, 1) entries) of a batch of frames resident in device memory;
+    a pointer may be 0 or None (an empty frame), steps defaults to dense rows (3 * cols)."""
+    n = len(ptrs)
+    return ((C.c_void_p * max(n, 1))(*ptrs), (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols),
+            (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols])))
+
+
+def _pack_passes(per_pass_faces, md: int):
+    """(flat, pass_counts) of a list of face lists: a (passes, md, 15) float32 block and a ctypes int array.  A list longer than md is
+    cut in the block, but its count stays the true length -- the C side reports the truncation from that."""
+    rows = [_face_rows(f) for f in per_pass_faces]
+    flat = np.zeros((max(len(rows), 1), md, 15), np.float32)
+    pass_counts = (C.c_int * max(len(rows), 4))()      # (at least four: the host merges read one count per pass of their spec)
+    for p, r in enumerate(rows):
+        flat[p, :min(len(r), md)] = r[:md]
+        pass_counts[p] = len(r)
+    return flat, pass_counts
+
+
+def _detection(row, anchor_index: int = -1) -> Detection:
+    v = row.tolist()
+    return Detection(v[0], tuple(v[1:5]), tuple(v[5:10]), tuple(v[10:15]), anchor_index)
+
+
 def follow_geometry(box):
     """rf_follow_geometry (host only): (q, ox, oy) of a box (x1, y1, x2, y2), or None for an invalid geometry"""
     b = (C.c_float * 4)(*[float(v) for v in box])
@@ -669,13 +736,6 @@ class Tracker:
                                                     self.max_tracks), self._det._h)
         return rec, tpl
 
-    def _frame_args(self, ptrs, rows, cols, steps):
-        n = len(ptrs)
-        p = (C.c_void_p * max(n, 1))(*ptrs)
-        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
-        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
-        return p, r, c, s
-
     def update_follow(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], streams: Sequence[int], faces, *,
                       steps: Optional[Sequence[int]] = None, coord_scale: Optional[Sequence[float]] = None, quality=None,
                       cap_per_image: Optional[int] = None, cap_ended: Optional[int] = None):
@@ -697,7 +757,7 @@ class Tracker:
                 if rec is not None and len(rec):
                     q[i, :min(len(rec), mf)] = np.asarray(rec, QUALITY_DTYPE)[:mf]
         cs = (C.c_float * max(n, 1))(*coord_scale) if coord_scale is not None else None
-        p, r, c, s = self._frame_args(ptrs, rows, cols, steps)
+        p, r, c, s = _device_frames(ptrs, rows, cols, steps)
         t, _, tags, ended, ce, ec = self._buffers(n, cap, cap_ended)
         st = _lib.check(self._lib.rf_track_follow_update_device(self._det._h, t, p, r, c, s, n, (C.c_int * max(n, 1))(*streams),
                                                                 flat.ctypes.data_as(C.POINTER(rf_face)), cap, counts, cs,
@@ -710,7 +770,7 @@ class Tracker:
     def _follow_call(self, fn, ptrs, rows, cols, streams, steps, cap_per_image, cap_ended):
         n = len(streams)
         cap = self.max_tracks if cap_per_image is None else int(cap_per_image)
-        p, r, c, s = self._frame_args(ptrs, rows, cols, steps)
+        p, r, c, s = _device_frames(ptrs, rows, cols, steps)
         self.last_out = np.zeros((max(n, 1), max(cap, 1), 15), np.float32)
         counts = (C.c_int * max(n, 1))()
         t, _, tags, ended, ce, ec = self._buffers(n, cap, cap_ended)
@@ -802,9 +862,7 @@ class Tracker:
                 if rec is not None and len(rec):
                     q[i, :min(len(rec), mf)] = np.asarray(rec, QUALITY_DTYPE)[:mf]
         cs = (C.c_float * max(n, 1))(*coord_scale) if coord_scale is not None else None
-        p = (C.c_void_p * max(n, 1))(*ptrs)
-        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
-        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        p, r, c, s = _device_frames(ptrs, rows, cols, steps)
         t, _, tags, ended, ce, ec = self._buffers(n, cap, cap_ended)
         shots, info = self._shot_buffers(n, cap_ended, host_shots)
         st = _lib.check(self._lib.rf_track_shots_device(self._det._h, t, p, r, c, s, n, (C.c_int * max(n, 1))(*streams),
@@ -828,9 +886,7 @@ class Tracker:
         hold the redaction's results."""
         det = self._det
         n = len(ptrs)
-        p = (C.c_void_p * max(n, 1))(*ptrs)
-        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
-        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        p, r, c, s = _device_frames(ptrs, rows, cols, steps)
         sp = _as_redact_spec(spec)
         mr = det._redact_regions(sp)
         self.last_pixels = np.zeros((max(n, 1), mr), np.int32)
@@ -855,9 +911,7 @@ class Tracker:
         (detections, tags, ended); last_pixels / last_region_counts hold the overlay's results."""
         det = self._det
         n = len(ptrs)
-        p = (C.c_void_p * max(n, 1))(*ptrs)
-        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
-        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        p, r, c, s = _device_frames(ptrs, rows, cols, steps)
         sp = _as_overlay_spec(spec)
         mr = det._redact_regions(sp)
         self.last_pixels = np.zeros((max(n, 1), mr), np.int32)
@@ -924,17 +978,13 @@ def tta_merge_host(passes, rows: int, cols: int, net_h: int, net_w: int, nms_thr
     md = int(max_detections)
     if md < 1:
         raise _lib.RFError(_lib.RF_ERR_INVALID_ARG, "rf_tta_merge_host: max_detections must be positive")
-    rows_ = [_face_rows(p) for p in passes]
-    flat = np.zeros((max(len(rows_), 1), md, 15), np.float32)
-    pc = (C.c_int * max(len(rows_), 2))()
-    for p, r in enumerate(rows_):
-        flat[p, :min(len(r), md)] = r[:md]
-        pc[p] = len(r)
+    passes = list(passes)
+    flat, pc = _pack_passes(passes, md)
     cap = int(cap) if cap is not None else (sp.max_faces or md)
     out = (rf_face * max(cap, 1))()
     votes, src = (C.c_int * max(cap, 1))(), (C.c_int * max(cap, 1))()
     count = C.c_int(0)
-    if len(rows_) != (1 if sp.flip == 2 else 2):
+    if len(passes) != (1 if sp.flip == 2 else 2):
         raise _lib.RFError(_lib.RF_ERR_INVALID_ARG, "rf_tta_merge_host: one pass per frame with flip off, two otherwise")
     st = lib.rf_tta_merge_host(C.byref(sp), int(rows), int(cols), int(net_h), int(net_w), float(nms_threshold), md,
                                flat.ctypes.data_as(C.POINTER(rf_face)), pc, out, cap, C.byref(count), votes, src)
@@ -981,18 +1031,14 @@ def rot_merge_host(passes, rows: int, cols: int, net_h: int, net_w: int, nms_thr
     md = int(max_detections)
     if md < 1:
         raise _lib.RFError(_lib.RF_ERR_INVALID_ARG, "rf_rot_merge_host: max_detections must be positive")
-    rows_ = [_face_rows(p) for p in passes]
-    flat = np.zeros((max(len(rows_), 1), md, 15), np.float32)
-    pc = (C.c_int * max(len(rows_), 4))()
-    for p, r in enumerate(rows_):
-        flat[p, :min(len(r), md)] = r[:md]
-        pc[p] = len(r)
+    passes = list(passes)
+    flat, pc = _pack_passes(passes, md)
     cap = int(cap) if cap is not None else (sp.max_faces or md)
     out = (rf_face * max(cap, 1))()
     votes, src = (C.c_int * max(cap, 1))(), (C.c_int * max(cap, 1))()
     count, frame_rot = C.c_int(0), C.c_int(-1)
     score = (C.c_float * 4)()
-    if 0 <= sp.rots <= 15 and len(rows_) != len(_rot_list(sp.rots)):
+    if 0 <= sp.rots <= 15 and len(passes) != len(_rot_list(sp.rots)):
         raise _lib.RFError(_lib.RF_ERR_INVALID_ARG, "rf_rot_merge_host: one pass per rotation of rots")
     st = lib.rf_rot_merge_host(C.byref(sp), int(rows), int(cols), int(net_h), int(net_w), float(nms_threshold), md,
                                flat.ctypes.data_as(C.POINTER(rf_face)), pc, out, cap, C.byref(count), votes, src, C.byref(frame_rot), score)
@@ -1007,10 +1053,7 @@ def rotate_host(frame: np.ndarray, k: int, out: Optional[np.ndarray] = None) -> 
     """rf_rotate_host (host only, no GPU): the BGR frame turned by k (0..3) quarter turns counter-clockwise, np.rot90(frame, k).
     `out`: a uint8 (rows_k, >= cols_k, 3) view to write into (its row pitch is kept); returned either way."""
     lib = _lib.load_library()
-    if frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3:
-        raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
-    if frame.strides[2] != 1 or frame.strides[1] != 3:
-        frame = np.ascontiguousarray(frame)
+    frame = _dense_frame(frame)
     rows, cols = frame.shape[:2]
     dr, dc = (cols, rows) if int(k) & 1 else (rows, cols)
     if out is None:
@@ -1074,10 +1117,7 @@ def dewarp_host(frame: np.ndarray, view_mesh, view_w: int, view_h: int, out: Opt
     array or view whose pixels are contiguous (any row pitch)."""
     lib = _lib.load_library()
     m = _mesh_array(view_mesh, view_w, view_h, 1)
-    if frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3:
-        raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
-    if frame.strides[2] != 1 or frame.strides[1] != 3:
-        frame = np.ascontiguousarray(frame)
+    frame = _dense_frame(frame)
     if out is None:
         out = np.empty((view_h, view_w, 3), np.uint8)
     if out.dtype != np.uint8 or out.shape != (view_h, view_w, 3) or out.strides[2] != 1 or out.strides[1] != 3:
@@ -1111,18 +1151,14 @@ def dewarp_merge_host(passes, mesh, view_w: int, view_h: int, net_h: int, net_w:
     md = int(max_detections)
     if md < 1:
         raise _lib.RFError(_lib.RF_ERR_INVALID_ARG, "rf_dewarp_merge_host: max_detections must be positive")
-    rows_ = [_face_rows(p) for p in passes]
-    m = _mesh_array(mesh, view_w, view_h, len(rows_))
-    flat = np.zeros((max(len(rows_), 1), md, 15), np.float32)
-    pc = (C.c_int * max(len(rows_), 1))()
-    for p, r in enumerate(rows_):
-        flat[p, :min(len(r), md)] = r[:md]
-        pc[p] = len(r)
+    passes = list(passes)
+    flat, pc = _pack_passes(passes, md)
+    m = _mesh_array(mesh, view_w, view_h, len(passes))
     cap = int(cap) if cap is not None else (sp.max_faces or md)
     out = (rf_face * max(cap, 1))()
     votes, src = (C.c_int * max(cap, 1))(), (C.c_int * max(cap, 1))()
     count = C.c_int(0)
-    st = lib.rf_dewarp_merge_host(C.byref(sp), m.ctypes.data, int(view_w), int(view_h), len(rows_), int(net_h), int(net_w),
+    st = lib.rf_dewarp_merge_host(C.byref(sp), m.ctypes.data, int(view_w), int(view_h), len(passes), int(net_h), int(net_w),
                                   float(nms_threshold), md, flat.ctypes.data_as(C.POINTER(rf_face)), pc, out, cap, C.byref(count), votes, src)
     if st < 0 and st != _lib.RF_ERR_TRUNCATED:
         raise _lib.RFError(st, "rf_dewarp_merge_host: bad spec, mesh, net size or counts")
@@ -1171,10 +1207,7 @@ def enhance_host(frame: np.ndarray, tile: int = 0, clip: int = 0, dark_below: in
     equalisation of luma over tile x tile tiles, applied to the dark tiles as a hue-preserving gain.  `out`: a uint8 (rows, >= cols, 3)
     view to write into (its row pitch is kept; it may be `frame` itself).  Returns (enhanced frame, number of tiles enhanced)."""
     lib = _lib.load_library()
-    if frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3:
-        raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
-    if frame.strides[2] != 1 or frame.strides[1] != 3:
-        frame = np.ascontiguousarray(frame)
+    frame = _dense_frame(frame)
     rows, cols = frame.shape[:2]
     if out is None:
         out = np.zeros((rows, cols, 3), np.uint8)
@@ -1242,12 +1275,7 @@ def pyramid_merge_host(passes, rows: int, cols: int, net_h: int, net_w: int, nms
     want = lib.rf_pyramid_plan(C.byref(sp), int(rows), int(cols), int(net_h), int(net_w), None, 0)
     if want < 0 or len(passes) != want:
         raise _lib.RFError(_lib.RF_ERR_INVALID_ARG, "rf_pyramid_merge_host: bad spec or frame, or not one list of faces per pass of the plan")
-    rows_ = [_face_rows(p) for p in passes]
-    flat = np.zeros((max(len(rows_), 1), md, 15), np.float32)
-    pc = (C.c_int * max(len(rows_), 1))()
-    for p, r in enumerate(rows_):
-        flat[p, :min(len(r), md)] = r[:md]
-        pc[p] = len(r)
+    flat, pc = _pack_passes(passes, md)
     cap = int(cap) if cap is not None else (sp.max_faces or md)
     out = (rf_face * max(cap, 1))()
     votes, src = (C.c_int * max(cap, 1))(), (C.c_int * max(cap, 1))()
@@ -1267,10 +1295,7 @@ def zoom_host(frame: np.ndarray, z: int, x0: int = 0, y0: int = 0, tw: Optional[
     bilinear, half-pixel centres; default: the whole enlarged frame).  `out`: a uint8 (th, >= tw, 3) view to write into (its row
     pitch is kept); returned either way."""
     lib = _lib.load_library()
-    if frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3:
-        raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
-    if frame.strides[2] != 1 or frame.strides[1] != 3:
-        frame = np.ascontiguousarray(frame)
+    frame = _dense_frame(frame)
     rows, cols = frame.shape[:2]
     tw = int(z) * cols - int(x0) if tw is None else int(tw)
     th = int(z) * rows - int(y0) if th is None else int(th)
@@ -1371,20 +1396,8 @@ class RetinaFace:
         n = len(imgs)
         if n == 0:
             return []
-        ptrs = (C.c_void_p * n)()
-        rows, cols, steps = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
-        keep = []
-        for i, im in enumerate(imgs):
-            if im is None or im.size == 0:
-                ptrs[i], rows[i], cols[i], steps[i] = None, 0, 0, 0
-                continue
-            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
-                raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
-            if im.strides[2] != 1 or im.strides[1] != 3:
-                im = np.ascontiguousarray(im)
-            keep.append(im)
-            ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
-        return self._run(self._lib.rf_detect_batch, ptrs, rows, cols, steps, n, threshold)
+        f = _host_frames(imgs)
+        return self._run(self._lib.rf_detect_batch, *f.args, threshold)
 
     def frame_scale(self, rows: int, cols: int) -> float:
         """Multiply returned coordinates by this to get source-frame pixels (1.0 unless the frame is larger than the net)."""
@@ -1397,23 +1410,11 @@ class RetinaFace:
         n = len(imgs)
         if n == 0:
             return []
-        ptrs = (C.c_void_p * n)()
-        rows, cols, steps = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
-        keep = []
-        for i, im in enumerate(imgs):
-            if im is None or im.size == 0:
-                ptrs[i], rows[i], cols[i], steps[i] = None, 0, 0, 0
-                continue
-            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
-                raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
-            if im.strides[2] != 1 or im.strides[1] != 3:
-                im = np.ascontiguousarray(im)
-            keep.append(im)
-            ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
+        f = _host_frames(imgs)
         cap = self.max_detections
         out = (rf_face * (n * cap))()
         counts = (C.c_int * n)()
-        st = _lib.check(self._lib.rf_detect_batch_pad32(self._h, ptrs, rows, cols, steps, n, 0, float(threshold), out, cap, counts), self._h)
+        st = _lib.check(self._lib.rf_detect_batch_pad32(self._h, *f.args, 0, float(threshold), out, cap, counts), self._h)
         self.truncated = st == _lib.RF_ERR_TRUNCATED
         return self._collect(out, counts, n, cap, anchors=False)
 
@@ -1421,9 +1422,7 @@ class RetinaFace:
     def detect_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], threshold: float = 0.5,
                       steps: Optional[Sequence[int]] = None) -> List[List[Detection]]:
         n = len(ptrs)
-        p = (C.c_void_p * n)(*ptrs)
-        r, c = (C.c_int * n)(*rows), (C.c_int * n)(*cols)
-        s = (C.c_int * n)(*(steps if steps is not None else [3 * x for x in cols]))
+        p, r, c, s = _device_frames(ptrs, rows, cols, steps)
         return self._run(self._lib.rf_detect_batch_device, p, r, c, s, n, threshold)
 
     # ------------------------------------------------------------------ face alignment
@@ -1446,9 +1445,7 @@ class RetinaFace:
         for i, r in enumerate(rows_f):
             flat[i, :len(r)] = r
             counts[i] = len(r)
-        p = (C.c_void_p * max(n, 1))(*ptrs)
-        r_, c_ = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
-        s_ = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        p, r_, c_, s_ = _device_frames(ptrs, rows, cols, steps)
         cs = None
         if coord_scale is not None:
             cs = (C.c_float * max(n, 1))(*[float(v) for v in coord_scale])
@@ -1470,20 +1467,8 @@ class RetinaFace:
         n = len(imgs)
         if n == 0:
             return [], [], []
-        ptrs = (C.c_void_p * n)()
-        rows, cols, steps = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
-        keep = []
-        for i, im in enumerate(imgs):
-            if im is None or im.size == 0:
-                ptrs[i], rows[i], cols[i], steps[i] = None, 0, 0, 0
-                continue
-            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
-                raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
-            if im.strides[2] != 1 or im.strides[1] != 3:
-                im = np.ascontiguousarray(im)
-            keep.append(im)
-            ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
-        return self._run_aligned(self._lib.rf_detect_align_batch, ptrs, rows, cols, steps, n, threshold, crop_size, max_faces, None, True)
+        f = _host_frames(imgs)
+        return self._run_aligned(self._lib.rf_detect_align_batch, *f.args, threshold, crop_size, max_faces, None, True)
 
     def detect_aligned_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], threshold: float = 0.5,
                               steps: Optional[Sequence[int]] = None, crop_size: int = 112, max_faces: Optional[int] = None,
@@ -1494,9 +1479,7 @@ class RetinaFace:
         n = len(ptrs)
         if n == 0:
             return [], [], []
-        p = (C.c_void_p * n)(*ptrs)
-        r, c = (C.c_int * n)(*rows), (C.c_int * n)(*cols)
-        s = (C.c_int * n)(*(steps if steps is not None else [3 * x for x in cols]))
+        p, r, c, s = _device_frames(ptrs, rows, cols, steps)
         return self._run_aligned(self._lib.rf_detect_align_batch_device, p, r, c, s, n, threshold, crop_size, max_faces, d_crops, host)
 
     def _run_aligned(self, fn, ptrs, rows, cols, steps, n, threshold, crop_size, max_faces, d_crops, host):
@@ -1529,30 +1512,14 @@ class RetinaFace:
         (k < min(faces, max_faces)), kept or dropped.  With neither, the ungated C entry point is called.
         antialias=True supersamples faces that are larger in the frame than their crop, with up to aa_max (1, 2, 4, 8; 0 = 4)
         sub-samples per axis (face_aa_factor gives a face's factor); the records' luma numbers are then the antialiased crop's."""
-        n = len(imgs)
-        ptrs = (C.c_void_p * max(n, 1))()
-        rows, cols, steps = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
-        keep = []
-        for i, im in enumerate(imgs):
-            if im is None or im.size == 0:
-                ptrs[i], rows[i], cols[i], steps[i] = None, 0, 0, 0
-                continue
-            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
-                raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
-            if im.strides[2] != 1 or im.strides[1] != 3:
-                im = np.ascontiguousarray(im)
-            keep.append(im)
-            ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
-        return self._run_face_batch(self._lib.rf_detect_face_batch, self._lib.rf_detect_face_batch_gated, ptrs, rows, cols, steps, n,
-                                    threshold, **kw)
+        f = _host_frames(imgs)
+        return self._run_face_batch(self._lib.rf_detect_face_batch, self._lib.rf_detect_face_batch_gated, *f.args, threshold, **kw)
 
     def detect_face_batch_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], threshold: float = 0.5,
                                  steps: Optional[Sequence[int]] = None, **kw):
         """rf_detect_face_batch_device: detect_face_batch for frames resident in device memory."""
         n = len(ptrs)
-        p = (C.c_void_p * max(n, 1))(*ptrs)
-        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
-        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        p, r, c, s = _device_frames(ptrs, rows, cols, steps)
         return self._run_face_batch(self._lib.rf_detect_face_batch_device, self._lib.rf_detect_face_batch_gated_device, p, r, c, s, n,
                                     threshold, **kw)
 
@@ -1570,9 +1537,7 @@ class RetinaFace:
         for i, r in enumerate(rows_f):
             flat[i, :len(r)] = r
             counts[i] = len(r)
-        p = (C.c_void_p * max(n, 1))(*ptrs)
-        r_, c_ = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
-        s_ = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        p, r_, c_, s_ = _device_frames(ptrs, rows, cols, steps)
         cs = (C.c_float * max(n, 1))(*[float(v) for v in coord_scale]) if coord_scale is not None else None
 
         def fn(h, spec, d_out, tensor, mats, offsets, gate=None, quality=None):
@@ -1602,9 +1567,7 @@ class RetinaFace:
         for i, r in enumerate(rows_f):
             flat[i, :len(r)] = r
             counts[i] = len(r)
-        p = (C.c_void_p * max(n, 1))(*ptrs)
-        r_, c_ = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
-        s_ = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        p, r_, c_, s_ = _device_frames(ptrs, rows, cols, steps)
         cs = (C.c_float * max(n, 1))(*[float(v) for v in coord_scale]) if coord_scale is not None else None
         g = _as_gate(gate)
         q = np.zeros((max(n, 1), max(mf, 1)), QUALITY_DTYPE)
@@ -1655,6 +1618,44 @@ class RetinaFace:
         res = (tensor[:got] if host else None), mats[:got], offsets
         return res + (quality,) if return_quality else res
 
+    # ------------------------------------------------------------------ merged calls: tiled, TTA, rotation, dewarp, pyramid
+    # Every C call of these five families ends (..., out, cap_per_image, counts, [votes,] src, extra outputs): per frame up to cap merged
+    # faces in source-frame pixels and the true count, per face the pass it came from and -- all but tiled -- how many candidates it merged.
+    def _merged_buffers(self, n, cap, votes=True):
+        """(out, counts, per_face): per_face = ([votes,] src), one int per face slot each"""
+        m = max(n * cap, 1)
+        return (rf_face * m)(), (C.c_int * max(n, 1))(), tuple((C.c_int * m)() for _ in range(2 if votes else 1))
+
+    def _merged_results(self, out, counts, per_face, n, cap, counts_attr, with_per_face):
+        """Per frame the Detections of a merged call (anchor_index -1); with_per_face also each per-face array cut the same way.  The true
+        counts go to self.<counts_attr> -- that attribute alone: one family's call leaves the counts of the others as they are."""
+        rows = _faces_to_array(out, max(n * cap, 1))
+        cut = [slice(i * cap, i * cap + min(counts[i], cap)) for i in range(n)]
+        dets = [[_detection(r) for r in rows[s]] for s in cut]
+        setattr(self, counts_attr, [int(counts[i]) for i in range(n)])
+        return (dets,) + tuple([np.array(a[s], np.int32) for s in cut] for a in per_face) if with_per_face else dets
+
+    def _merged_call(self, fn, head, n, cap, counts_attr, with_per_face, votes=True, tail=()):
+        """fn(*head, out, cap, counts, [votes,] src, *tail) with fresh buffers; sets self.truncated.  tail: the extra outputs of the call."""
+        out, counts, per_face = self._merged_buffers(n, cap, votes)
+        st = _lib.check(fn(*head, out, cap, counts, *per_face, *tail), self._h)
+        self.truncated = st == _lib.RF_ERR_TRUNCATED
+        return self._merged_results(out, counts, per_face, n, cap, counts_attr, with_per_face)
+
+    def _detect_merged(self, fn, handle, frames, threshold, sp, counts_attr, with_per_face, votes=True, tail=()):
+        """The detect call of a merged family: fn(handle, ptrs, rows, cols, steps, n, threshold, spec, ...), frames = those five."""
+        head = (handle,) + tuple(frames) + (float(threshold), C.byref(sp))
+        return self._merged_call(fn, head, frames[4], sp.max_faces or self.max_detections, counts_attr, with_per_face, votes, tail)
+
+    def _merge_call(self, fn, rows, cols, sp, per_pass_faces, cap_per_image, counts_attr, with_per_face, votes=True, tail=()):
+        """The stand-alone merge of a family, over per-pass faces the caller supplies: fn(handle, rows, cols, n, spec, faces, pass_counts,
+        ...)"""
+        n = len(rows)
+        flat, pc = _pack_passes([f for frame in per_pass_faces for f in frame], self.max_detections)
+        cap = int(cap_per_image) if cap_per_image is not None else (sp.max_faces or self.max_detections)
+        head = (self._h, (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols), n, C.byref(sp), flat.ctypes.data_as(C.POINTER(rf_face)), pc)
+        return self._merged_call(fn, head, n, cap, counts_attr, with_per_face, votes, tail)
+
     # ------------------------------------------------------------------ tiled detection
     def detect_tiled(self, imgs: Sequence[np.ndarray], threshold: float = 0.5, overlap: int = 0, edge: int = 0, full_frame: bool = True,
                      max_faces: int = 0, return_tiles: bool = False):
@@ -1662,79 +1663,26 @@ class RetinaFace:
         (plus the whole frame shrunk, with full_frame), and the faces are merged on the device.  Returns per frame the merged
         detections in SOURCE-FRAME pixels (anchor_index is -1); with return_tiles also, per frame, the pass each came from (tile_plan
         gives the passes).  Keywords as tile_spec()."""
-        n = len(imgs)
-        ptrs = (C.c_void_p * max(n, 1))()
-        rows, cols, steps = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
-        keep = []
-        for i, im in enumerate(imgs):
-            if im is None or im.size == 0:
-                ptrs[i], rows[i], cols[i], steps[i] = None, 0, 0, 0
-                continue
-            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
-                raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
-            if im.strides[2] != 1 or im.strides[1] != 3:
-                im = np.ascontiguousarray(im)
-            keep.append(im)
-            ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
-        return self._run_tiled(self._lib.rf_detect_tiled_batch, ptrs, rows, cols, steps, n, threshold,
-                               tile_spec(overlap, edge, full_frame, max_faces), return_tiles)
+        f = _host_frames(imgs)
+        return self._detect_merged(self._lib.rf_detect_tiled_batch, self._h, f.args, threshold, tile_spec(overlap, edge, full_frame, max_faces),
+                                   "tiled_counts", return_tiles, votes=False)
 
     def detect_tiled_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], threshold: float = 0.5,
                             steps: Optional[Sequence[int]] = None, overlap: int = 0, edge: int = 0, full_frame: bool = True,
                             max_faces: int = 0, return_tiles: bool = False):
         """rf_detect_tiled_batch_device: detect_tiled for frames resident in device memory."""
-        n = len(ptrs)
-        p = (C.c_void_p * max(n, 1))(*ptrs)
-        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
-        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
-        return self._run_tiled(self._lib.rf_detect_tiled_batch_device, p, r, c, s, n, threshold,
-                               tile_spec(overlap, edge, full_frame, max_faces), return_tiles)
-
-    def _tiled_cap(self, sp) -> int:
-        return sp.max_faces or self.max_detections
-
-    def _collect_tiled(self, out, counts, src, n, cap, return_tiles):
-        rows = _faces_to_array(out, max(n * cap, 1))
-        dets, tiles = [], []
-        for i in range(n):
-            k = min(counts[i], cap)
-            dets.append([Detection(float(r[0]), tuple(float(v) for v in r[1:5]), tuple(float(v) for v in r[5:10]),
-                                   tuple(float(v) for v in r[10:15]), -1) for r in rows[i * cap:i * cap + k]])
-            tiles.append(np.array(src[i * cap:i * cap + k], np.int32))
-        self.tiled_counts = [int(counts[i]) for i in range(n)]
-        return (dets, tiles) if return_tiles else dets
-
-    def _run_tiled(self, fn, ptrs, rows, cols, steps, n, threshold, sp, return_tiles):
-        cap = self._tiled_cap(sp)
-        out = (rf_face * max(n * cap, 1))()
-        counts = (C.c_int * max(n, 1))()
-        src = (C.c_int * max(n * cap, 1))()
-        st = _lib.check(fn(self._h, ptrs, rows, cols, steps, n, float(threshold), C.byref(sp), out, cap, counts, src), self._h)
-        self.truncated = st == _lib.RF_ERR_TRUNCATED
-        return self._collect_tiled(out, counts, src, n, cap, return_tiles)
+        frames = _device_frames(ptrs, rows, cols, steps) + (len(ptrs),)
+        return self._detect_merged(self._lib.rf_detect_tiled_batch_device, self._h, frames, threshold,
+                                   tile_spec(overlap, edge, full_frame, max_faces), "tiled_counts", return_tiles, votes=False)
 
     def tile_merge(self, rows: Sequence[int], cols: Sequence[int], per_pass_faces, overlap: int = 0, edge: int = 0, full_frame: bool = True,
                    max_faces: int = 0, cap_per_image: Optional[int] = None, return_tiles: bool = False):
         """rf_tile_merge_device: edge rule, mapping and merge of per-pass faces the caller supplies -- per_pass_faces[i][t]: the faces
         of pass t of frame i (a (k, 15) array, rows of 15 floats or Detections, at most max_detections), passes as tile_plan gives
         them.  No forward pass runs.  Returns as detect_tiled; self.tiled_counts holds the true merged counts."""
-        n = len(rows)
         sp = tile_spec(overlap, edge, full_frame, max_faces)
-        md = self.max_detections
-        passes = [_face_rows(f) for frame in per_pass_faces for f in frame]
-        flat = np.zeros((max(len(passes), 1), md, 15), np.float32)
-        pc = (C.c_int * max(len(passes), 1))()
-        for p, r in enumerate(passes):
-            flat[p, :min(len(r), md)] = r[:md]
-            pc[p] = len(r)
-        cap = int(cap_per_image) if cap_per_image is not None else self._tiled_cap(sp)
-        out = (rf_face * max(n * cap, 1))()
-        counts = (C.c_int * max(n, 1))()
-        src = (C.c_int * max(n * cap, 1))()
-        st = _lib.check(self._lib.rf_tile_merge_device(self._h, (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols), n, C.byref(sp),
-                                                       flat.ctypes.data_as(C.POINTER(rf_face)), pc, out, cap, counts, src), self._h)
-        self.truncated = st == _lib.RF_ERR_TRUNCATED
-        return self._collect_tiled(out, counts, src, n, cap, return_tiles)
+        return self._merge_call(self._lib.rf_tile_merge_device, rows, cols, sp, per_pass_faces, cap_per_image, "tiled_counts", return_tiles,
+                                votes=False)
 
     def detect_tiled_face_batch_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], threshold: float = 0.5,
                                        steps: Optional[Sequence[int]] = None, overlap: int = 0, edge: int = 0, full_frame: bool = True,
@@ -1743,14 +1691,10 @@ class RetinaFace:
         Keywords as detect_face_batch_device (gate= / return_quality= select the gated launches); returns (detections, tensor,
         matrices, offsets[, quality]) with the detections in source-frame pixels."""
         n = len(ptrs)
-        p = (C.c_void_p * max(n, 1))(*ptrs)
-        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
-        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        p, r, c, s = _device_frames(ptrs, rows, cols, steps)
         tsp = tile_spec(overlap, edge, full_frame, tile_max_faces)
-        cap = self._tiled_cap(tsp)
-        out = (rf_face * max(n * cap, 1))()
-        counts = (C.c_int * max(n, 1))()
-        src = (C.c_int * max(n * cap, 1))()
+        cap = tsp.max_faces or self.max_detections
+        out, counts, (src,) = self._merged_buffers(n, cap, votes=False)
 
         def call(h, spec, d_out, tensor, mats, offsets, gate=None, quality=None):
             return self._lib.rf_detect_tiled_face_batch_device(h, p, r, c, s, n, float(threshold), C.byref(tsp), out, cap, counts, src,
@@ -1758,7 +1702,7 @@ class RetinaFace:
         res = self._face_batch_call(call, n, **kw)
         if len(res) == 4:
             res = res[:3] + ([res[3][i, :min(counts[i], res[3].shape[1], cap)] for i in range(n)],)
-        return (self._collect_tiled(out, counts, src, n, cap, False),) + res
+        return (self._merged_results(out, counts, (src,), n, cap, "tiled_counts", False),) + res
 
     # ------------------------------------------------------------------ face tracks
     def tracker(self, n_streams: int = 1, motion=None, follow=None, **spec) -> Tracker:
@@ -1783,29 +1727,14 @@ class RetinaFace:
                        cap_ended: Optional[int] = None):
         """rf_detect_track_batch: detectBatchImages + the frame step of every image (streams[i]: its stream, -1 = not tracked).
         Returns (detections, tags per image, ended tracks per image); tracks live in source-frame pixels."""
-        n = len(imgs)
-        ptrs = (C.c_void_p * max(n, 1))()
-        rows, cols, steps = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
-        keep = []
-        for i, im in enumerate(imgs):
-            if im is None or im.size == 0:
-                ptrs[i], rows[i], cols[i], steps[i] = None, 0, 0, 0
-                continue
-            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
-                raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
-            if im.strides[2] != 1 or im.strides[1] != 3:
-                im = np.ascontiguousarray(im)
-            keep.append(im)
-            ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
-        return self._run_tracked(self._lib.rf_detect_track_batch, ptrs, rows, cols, steps, n, threshold, tracker, streams, cap_ended)
+        f = _host_frames(imgs)
+        return self._run_tracked(self._lib.rf_detect_track_batch, *f.args, threshold, tracker, streams, cap_ended)
 
     def detect_tracked_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], tracker: Tracker, streams: Sequence[int],
                               threshold: float = 0.5, steps: Optional[Sequence[int]] = None, cap_ended: Optional[int] = None):
         """rf_detect_track_batch_device: detect_tracked for frames resident in device memory (a 0 pointer is a frame with no faces)."""
         n = len(ptrs)
-        p = (C.c_void_p * max(n, 1))(*ptrs)
-        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
-        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        p, r, c, s = _device_frames(ptrs, rows, cols, steps)
         return self._run_tracked(self._lib.rf_detect_track_batch_device, p, r, c, s, n, threshold, tracker, streams, cap_ended)
 
     def detect_track_follow_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], tracker: Tracker, streams: Sequence[int],
@@ -1813,9 +1742,7 @@ class RetinaFace:
         """rf_detect_track_follow_batch_device: a key step -- detect_tracked_device on a tracker with follow, the templates of the matched
         and opened tracks retaken behind the track launch (each stream at most once per call)."""
         n = len(ptrs)
-        p = (C.c_void_p * max(n, 1))(*ptrs)
-        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
-        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        p, r, c, s = _device_frames(ptrs, rows, cols, steps)
         return self._run_tracked(self._lib.rf_detect_track_follow_batch_device, p, r, c, s, n, threshold, tracker, streams, cap_ended)
 
     def detect_followed(self, imgs: Sequence[np.ndarray], tracker: Tracker, streams: Sequence[int], key: bool, threshold: float = 0.5,
@@ -1840,9 +1767,7 @@ class RetinaFace:
         """rf_detect_track_face_batch_device: detect_face_batch_device + the frame steps; with gate= / return_quality= the best shots go
         by sharpness.  Returns (detections, tensor, matrices, offsets[, quality], tags, ended)."""
         n = len(ptrs)
-        p = (C.c_void_p * max(n, 1))(*ptrs)
-        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
-        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        p, r, c, s = _device_frames(ptrs, rows, cols, steps)
         cap = self.max_detections
         out = (rf_face * max(n * cap, 1))()
         counts = (C.c_int * max(n, 1))()
@@ -1884,31 +1809,16 @@ class RetinaFace:
         """rf_detect_track_shots_batch_device: detect_tracked_device on a tracker with a gallery (Tracker.enable_shots); the tracks that
         end hand over their best shots.  Returns (detections, tags, ended, shots, shot records[, quality])."""
         n = len(ptrs)
-        p = (C.c_void_p * max(n, 1))(*ptrs)
-        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
-        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        p, r, c, s = _device_frames(ptrs, rows, cols, steps)
         return self._run_shots(self._lib.rf_detect_track_shots_batch_device, p, r, c, s, n, threshold, tracker, streams, cap_ended, gate,
                                return_quality, d_shots, host_shots)
 
     def detect_track_shots(self, imgs: Sequence[np.ndarray], tracker: Tracker, streams: Sequence[int], threshold: float = 0.5,
                            cap_ended: Optional[int] = None, gate=None, return_quality: bool = False):
         """rf_detect_track_shots_batch: detect_track_shots_device for frames in host memory"""
-        n = len(imgs)
-        ptrs = (C.c_void_p * max(n, 1))()
-        rows, cols, steps = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
-        keep = []
-        for i, im in enumerate(imgs):
-            if im is None or im.size == 0:
-                ptrs[i], rows[i], cols[i], steps[i] = None, 0, 0, 0
-                continue
-            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
-                raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
-            if im.strides[2] != 1 or im.strides[1] != 3:
-                im = np.ascontiguousarray(im)
-            keep.append(im)
-            ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
-        return self._run_shots(self._lib.rf_detect_track_shots_batch, ptrs, rows, cols, steps, n, threshold, tracker, streams, cap_ended, gate,
-                               return_quality, 0, True)
+        f = _host_frames(imgs)
+        return self._run_shots(self._lib.rf_detect_track_shots_batch, *f.args, threshold, tracker, streams, cap_ended, gate, return_quality, 0,
+                               True)
 
     # ------------------------------------------------------------------ face redaction
     def _redact_regions(self, sp) -> int:
@@ -1931,9 +1841,7 @@ class RetinaFace:
         for i, r in enumerate(per):
             flat[i, :min(len(r), cap)] = r[:cap]
             counts[i] = len(r)
-        p = (C.c_void_p * max(n, 1))(*ptrs)
-        r_, c_ = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
-        s_ = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        p, r_, c_, s_ = _device_frames(ptrs, rows, cols, steps)
         cs = (C.c_float * max(n, 1))(*[float(v) for v in coord_scale]) if coord_scale is not None else None
         sp = _as_redact_spec(spec)
         pixels = np.zeros((max(n, 1), self._redact_regions(sp)), np.int32)
@@ -1957,9 +1865,7 @@ class RetinaFace:
         """rf_detect_redact_batch_device: detect_device + redaction of what it finds, in place in the device frames.  last_pixels holds
         the pixels every region owns ((n, max_regions) int32)."""
         n = len(ptrs)
-        p = (C.c_void_p * max(n, 1))(*ptrs)
-        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
-        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        p, r, c, s = _device_frames(ptrs, rows, cols, steps)
         sp = _as_redact_spec(spec)
         self.last_pixels = np.zeros((max(n, 1), self._redact_regions(sp)), np.int32)
         cap = self.max_detections
@@ -1976,18 +1882,8 @@ class RetinaFace:
     def detect_redacted(self, imgs: Sequence[np.ndarray], threshold: float = 0.5, spec=None) -> List[List[Detection]]:
         """rf_detect_redact_batch: detectBatchImages + redaction; the frames (uint8 H x W x 3, dense pixels, any row stride, writeable)
         are redacted in place."""
-        n = len(imgs)
-        ptrs = (C.c_void_p * max(n, 1))()
-        rows, cols, steps = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
-        for i, im in enumerate(imgs):
-            if im is None or im.size == 0:
-                ptrs[i], rows[i], cols[i], steps[i] = None, 0, 0, 0
-                continue
-            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 or im.strides[2] != 1 or im.strides[1] != 3:
-                raise ValueError("frames must be uint8 H x W x 3 with dense pixels (CV_8UC3, BGR)")
-            if not im.flags.writeable:
-                raise ValueError("frames are redacted in place: they must be writeable")
-            ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
+        f = _host_frames(imgs, in_place="redacted")
+        ptrs, rows, cols, steps, n = f.args
         sp = _as_redact_spec(spec)
         self.last_pixels = np.zeros((max(n, 1), self._redact_regions(sp)), np.int32)
         cap = self.max_detections
@@ -2018,9 +1914,7 @@ class RetinaFace:
             flat[i, :min(len(r), cap)] = r[:cap]
             counts[i] = len(r)
         idb = _id_block(ids, n, cap)
-        p = (C.c_void_p * max(n, 1))(*ptrs)
-        r_, c_ = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
-        s_ = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        p, r_, c_, s_ = _device_frames(ptrs, rows, cols, steps)
         cs = (C.c_float * max(n, 1))(*[float(v) for v in coord_scale]) if coord_scale is not None else None
         sp = _as_overlay_spec(spec)
         pixels = np.zeros((max(n, 1), self._redact_regions(sp)), np.int32)
@@ -2045,9 +1939,7 @@ class RetinaFace:
         """rf_detect_overlay_batch_device: detect_device + the overlay of what it finds, in place in the device frames.  last_pixels
         holds the pixels every region painted ((n, max_regions) int32)."""
         n = len(ptrs)
-        p = (C.c_void_p * max(n, 1))(*ptrs)
-        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
-        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        p, r, c, s = _device_frames(ptrs, rows, cols, steps)
         sp = _as_overlay_spec(spec)
         self.last_pixels = np.zeros((max(n, 1), self._redact_regions(sp)), np.int32)
         cap = self.max_detections
@@ -2064,18 +1956,8 @@ class RetinaFace:
     def detect_overlay(self, imgs: Sequence[np.ndarray], threshold: float = 0.5, spec=None) -> List[List[Detection]]:
         """rf_detect_overlay_batch: detectBatchImages + the overlay; the frames (uint8 H x W x 3, dense pixels, any row stride,
         writeable) are drawn into in place."""
-        n = len(imgs)
-        ptrs = (C.c_void_p * max(n, 1))()
-        rows, cols, steps = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
-        for i, im in enumerate(imgs):
-            if im is None or im.size == 0:
-                ptrs[i], rows[i], cols[i], steps[i] = None, 0, 0, 0
-                continue
-            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 or im.strides[2] != 1 or im.strides[1] != 3:
-                raise ValueError("frames must be uint8 H x W x 3 with dense pixels (CV_8UC3, BGR)")
-            if not im.flags.writeable:
-                raise ValueError("frames are drawn into in place: they must be writeable")
-            ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
+        f = _host_frames(imgs, in_place="drawn into")
+        ptrs, rows, cols, steps, n = f.args
         sp = _as_overlay_spec(spec)
         self.last_pixels = np.zeros((max(n, 1), self._redact_regions(sp)), np.int32)
         cap = self.max_detections
@@ -2096,53 +1978,17 @@ class RetinaFace:
         overlapping boxes of both passes are merged on the device into a score-weighted mean.  Returns per frame the merged
         detections in SOURCE-FRAME pixels (anchor_index is -1); with return_votes also, per frame, how many candidates each face
         merged and the pass (0: the frame, 1: mirrored) its head came from.  self.tta_counts holds the true merged counts."""
-        n = len(imgs)
-        ptrs = (C.c_void_p * max(n, 1))()
-        rows, cols, steps = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
-        keep = []
-        for i, im in enumerate(imgs):
-            if im is None or im.size == 0:
-                ptrs[i], rows[i], cols[i], steps[i] = None, 0, 0, 0
-                continue
-            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
-                raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
-            if im.strides[2] != 1 or im.strides[1] != 3:
-                im = np.ascontiguousarray(im)
-            keep.append(im)
-            ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
-        return self._run_tta(self._lib.rf_detect_tta_batch, ptrs, rows, cols, steps, n, threshold, tta_spec(flip, vote, max_faces),
-                             return_votes)
+        f = _host_frames(imgs)
+        return self._detect_merged(self._lib.rf_detect_tta_batch, self._h, f.args, threshold, tta_spec(flip, vote, max_faces), "tta_counts",
+                                   return_votes)
 
     def detect_tta_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], threshold: float = 0.5,
                           steps: Optional[Sequence[int]] = None, flip: bool = True, vote: bool = True, max_faces: int = 0,
                           return_votes: bool = False):
         """rf_detect_tta_batch_device: detect_tta for frames resident in device memory (0 / None: an empty frame)."""
-        n = len(ptrs)
-        p = (C.c_void_p * max(n, 1))(*ptrs)
-        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
-        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
-        return self._run_tta(self._lib.rf_detect_tta_batch_device, p, r, c, s, n, threshold, tta_spec(flip, vote, max_faces), return_votes)
-
-    def _collect_tta(self, out, counts, votes, src, n, cap, return_votes):
-        rows = _faces_to_array(out, max(n * cap, 1))
-        dets, vt, ps = [], [], []
-        for i in range(n):
-            k = min(counts[i], cap)
-            dets.append([Detection(float(r[0]), tuple(float(v) for v in r[1:5]), tuple(float(v) for v in r[5:10]),
-                                   tuple(float(v) for v in r[10:15]), -1) for r in rows[i * cap:i * cap + k]])
-            vt.append(np.array(votes[i * cap:i * cap + k], np.int32))
-            ps.append(np.array(src[i * cap:i * cap + k], np.int32))
-        self.tta_counts = [int(counts[i]) for i in range(n)]
-        return (dets, vt, ps) if return_votes else dets
-
-    def _run_tta(self, fn, ptrs, rows, cols, steps, n, threshold, sp, return_votes):
-        cap = sp.max_faces or self.max_detections
-        out = (rf_face * max(n * cap, 1))()
-        counts = (C.c_int * max(n, 1))()
-        votes, src = (C.c_int * max(n * cap, 1))(), (C.c_int * max(n * cap, 1))()
-        st = _lib.check(fn(self._h, ptrs, rows, cols, steps, n, float(threshold), C.byref(sp), out, cap, counts, votes, src), self._h)
-        self.truncated = st == _lib.RF_ERR_TRUNCATED
-        return self._collect_tta(out, counts, votes, src, n, cap, return_votes)
+        frames = _device_frames(ptrs, rows, cols, steps) + (len(ptrs),)
+        return self._detect_merged(self._lib.rf_detect_tta_batch_device, self._h, frames, threshold, tta_spec(flip, vote, max_faces),
+                                   "tta_counts", return_votes)
 
     def tta_merge(self, rows: Sequence[int], cols: Sequence[int], per_pass_faces, flip: bool = True, vote: bool = True, max_faces: int = 0,
                   cap_per_image: Optional[int] = None, return_votes: bool = False):
@@ -2151,24 +1997,10 @@ class RetinaFace:
         off.  No forward pass runs.  Returns as detect_tta; self.tta_counts holds the true merged counts."""
         n = len(rows)
         sp = tta_spec(flip, vote, max_faces)
-        md = self.max_detections
         per = 2 if flip else 1
         if any(len(frame) != per for frame in per_pass_faces) or len(per_pass_faces) != n:
             raise ValueError("per_pass_faces: one list of %d passes per frame" % per)
-        passes = [_face_rows(f) for frame in per_pass_faces for f in frame]
-        flat = np.zeros((max(len(passes), 1), md, 15), np.float32)
-        pc = (C.c_int * max(len(passes), 1))()
-        for p, r in enumerate(passes):
-            flat[p, :min(len(r), md)] = r[:md]
-            pc[p] = len(r)
-        cap = int(cap_per_image) if cap_per_image is not None else (sp.max_faces or md)
-        out = (rf_face * max(n * cap, 1))()
-        counts = (C.c_int * max(n, 1))()
-        votes, src = (C.c_int * max(n * cap, 1))(), (C.c_int * max(n * cap, 1))()
-        st = _lib.check(self._lib.rf_tta_merge_device(self._h, (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols), n, C.byref(sp),
-                                                      flat.ctypes.data_as(C.POINTER(rf_face)), pc, out, cap, counts, votes, src), self._h)
-        self.truncated = st == _lib.RF_ERR_TRUNCATED
-        return self._collect_tta(out, counts, votes, src, n, cap, return_votes)
+        return self._merge_call(self._lib.rf_tta_merge_device, rows, cols, sp, per_pass_faces, cap_per_image, "tta_counts", return_votes)
 
     def mirror_device(self, src_ptr: int, rows: int, cols: int, dst_ptr: int, step: Optional[int] = None, dst_step: Optional[int] = None):
         """rf_mirror_device: the mirror kernel on its own -- row y of the destination (dst_step bytes apart, cols * 3 bytes written)
@@ -2185,51 +2017,25 @@ class RetinaFace:
         return_votes also, per frame, how many candidates each face merged and the rotation (0..3) its head came from.
         self.rot_counts holds the true merged counts, self.frame_rot per frame the quarter turns counter-clockwise that make it
         upright (-1: no face), self.rot_score the (n, 4) score sums behind that."""
-        n = len(imgs)
-        ptrs = (C.c_void_p * max(n, 1))()
-        rows, cols, steps = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
-        keep = []
-        for i, im in enumerate(imgs):
-            if im is None or im.size == 0:
-                ptrs[i], rows[i], cols[i], steps[i] = None, 0, 0, 0
-                continue
-            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
-                raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
-            if im.strides[2] != 1 or im.strides[1] != 3:
-                im = np.ascontiguousarray(im)
-            keep.append(im)
-            ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
-        return self._run_rot(self._lib.rf_detect_rot_batch, ptrs, rows, cols, steps, n, threshold, rot_spec(rots, vote, max_faces),
-                             return_votes)
+        f = _host_frames(imgs)
+        return self._rot_call(len(imgs), lambda tail: self._detect_merged(self._lib.rf_detect_rot_batch, self._h, f.args, threshold,
+                                                                          rot_spec(rots, vote, max_faces), "rot_counts", return_votes, tail=tail))
 
     def detect_rotated_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], threshold: float = 0.5,
                               steps: Optional[Sequence[int]] = None, rots: int = 0, vote: bool = False, max_faces: int = 0,
                               return_votes: bool = False):
         """rf_detect_rot_batch_device: detect_rotated for frames resident in device memory (0 / None: an empty frame)."""
-        n = len(ptrs)
-        p = (C.c_void_p * max(n, 1))(*ptrs)
-        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
-        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
-        return self._run_rot(self._lib.rf_detect_rot_batch_device, p, r, c, s, n, threshold, rot_spec(rots, vote, max_faces), return_votes)
+        frames = _device_frames(ptrs, rows, cols, steps) + (len(ptrs),)
+        return self._rot_call(len(ptrs), lambda tail: self._detect_merged(self._lib.rf_detect_rot_batch_device, self._h, frames, threshold,
+                                                                          rot_spec(rots, vote, max_faces), "rot_counts", return_votes, tail=tail))
 
-    def _collect_rot(self, out, counts, votes, src, frame_rot, score, n, cap, return_votes):
-        kept = getattr(self, "tta_counts", None)             # _collect_tta's layout is this call's too; its counts are not
-        res = self._collect_tta(out, counts, votes, src, n, cap, return_votes)
-        self.rot_counts, self.tta_counts = self.tta_counts, kept
+    def _rot_call(self, n, call):
+        """A rotation call with its two extra outputs: call((frame_rot, rot_score)) makes the C call; sets self.frame_rot / self.rot_score."""
+        frame_rot, score = (C.c_int * max(n, 1))(), (C.c_float * max(4 * n, 1))()
+        res = call((frame_rot, score))
         self.frame_rot = [int(frame_rot[i]) for i in range(n)]
         self.rot_score = np.array(score[:4 * n], np.float32).reshape(n, 4)
         return res
-
-    def _run_rot(self, fn, ptrs, rows, cols, steps, n, threshold, sp, return_votes):
-        cap = sp.max_faces or self.max_detections
-        out = (rf_face * max(n * cap, 1))()
-        counts, frame_rot = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
-        score = (C.c_float * max(4 * n, 1))()
-        votes, src = (C.c_int * max(n * cap, 1))(), (C.c_int * max(n * cap, 1))()
-        st = _lib.check(fn(self._h, ptrs, rows, cols, steps, n, float(threshold), C.byref(sp), out, cap, counts, votes, src, frame_rot,
-                           score), self._h)
-        self.truncated = st == _lib.RF_ERR_TRUNCATED
-        return self._collect_rot(out, counts, votes, src, frame_rot, score, n, cap, return_votes)
 
     def rot_merge(self, rows: Sequence[int], cols: Sequence[int], per_pass_faces, rots: int = 0, vote: bool = False, max_faces: int = 0,
                   cap_per_image: Optional[int] = None, return_votes: bool = False):
@@ -2238,26 +2044,11 @@ class RetinaFace:
         forward pass runs.  Returns as detect_rotated; self.rot_counts, self.frame_rot and self.rot_score as there."""
         n = len(rows)
         sp = rot_spec(rots, vote, max_faces)
-        md = self.max_detections
         per = len(_rot_list(rots)) if 0 <= int(rots) <= 15 else 4
         if any(len(frame) != per for frame in per_pass_faces) or len(per_pass_faces) != n:
             raise ValueError("per_pass_faces: one list of %d passes per frame" % per)
-        passes = [_face_rows(f) for frame in per_pass_faces for f in frame]
-        flat = np.zeros((max(len(passes), 1), md, 15), np.float32)
-        pc = (C.c_int * max(len(passes), 1))()
-        for p, r in enumerate(passes):
-            flat[p, :min(len(r), md)] = r[:md]
-            pc[p] = len(r)
-        cap = int(cap_per_image) if cap_per_image is not None else (sp.max_faces or md)
-        out = (rf_face * max(n * cap, 1))()
-        counts, frame_rot = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
-        score = (C.c_float * max(4 * n, 1))()
-        votes, src = (C.c_int * max(n * cap, 1))(), (C.c_int * max(n * cap, 1))()
-        st = _lib.check(self._lib.rf_rot_merge_device(self._h, (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols), n, C.byref(sp),
-                                                      flat.ctypes.data_as(C.POINTER(rf_face)), pc, out, cap, counts, votes, src, frame_rot,
-                                                      score), self._h)
-        self.truncated = st == _lib.RF_ERR_TRUNCATED
-        return self._collect_rot(out, counts, votes, src, frame_rot, score, n, cap, return_votes)
+        return self._rot_call(n, lambda tail: self._merge_call(self._lib.rf_rot_merge_device, rows, cols, sp, per_pass_faces, cap_per_image,
+                                                               "rot_counts", return_votes, tail=tail))
 
     def rotate_device(self, src_ptr: int, rows: int, cols: int, k: int, dst_ptr: int, step: Optional[int] = None,
                       dst_step: Optional[int] = None):
@@ -2278,51 +2069,20 @@ class RetinaFace:
         on the device; the faces of all views are moved back through the meshes and merged on the device.  Returns per frame the
         merged detections in SOURCE-FRAME pixels (anchor_index is -1); with return_votes also, per frame, how many candidates each
         face merged and the view its head came from.  self.dewarp_counts holds the true merged counts."""
-        n = len(imgs)
-        ptrs = (C.c_void_p * max(n, 1))()
-        rows, cols, steps = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
-        keep = []
-        for i, im in enumerate(imgs):
-            if im is None or im.size == 0:
-                ptrs[i], rows[i], cols[i], steps[i] = None, 0, 0, 0
-                continue
-            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
-                raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
-            if im.strides[2] != 1 or im.strides[1] != 3:
-                im = np.ascontiguousarray(im)
-            keep.append(im)
-            ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
-        return self._run_dewarp(self._lib.rf_detect_dewarp_batch, dewarper, ptrs, rows, cols, steps, n, threshold,
-                                dewarp_spec(vote=vote, max_faces=max_faces, edge=edge), return_votes, None)
+        f = _host_frames(imgs)
+        return self._detect_merged(self._lib.rf_detect_dewarp_batch, dewarper._d, f.args, threshold,
+                                   dewarp_spec(vote=vote, max_faces=max_faces, edge=edge), "dewarp_counts", return_votes)
 
     def detect_dewarped_device(self, ptrs: Sequence[int], dewarper: Dewarper, threshold: float = 0.5, steps: Optional[Sequence[int]] = None,
                                rows: Optional[Sequence[int]] = None, cols: Optional[Sequence[int]] = None, vote: bool = False,
                                max_faces: int = 0, edge: int = 0, views_ptr: Optional[int] = None, return_votes: bool = False):
         """rf_detect_dewarp_batch_device: detect_dewarped for frames resident in device memory (0 / None: an empty frame).  views_ptr:
         device memory of n * V * view_h * view_w * 3 bytes that receives the views as dense frames."""
-        n = len(ptrs)
-        p = (C.c_void_p * max(n, 1))(*ptrs)
-        r = (C.c_int * max(n, 1))(*(rows if rows is not None else [dewarper.rows if q else 0 for q in ptrs]))
-        c = (C.c_int * max(n, 1))(*(cols if cols is not None else [dewarper.cols if q else 0 for q in ptrs]))
-        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in c[:n]]))
-        return self._run_dewarp(self._lib.rf_detect_dewarp_batch_device, dewarper, p, r, c, s, n, threshold,
-                                dewarp_spec(vote=vote, max_faces=max_faces, edge=edge), return_votes, views_ptr)
-
-    def _collect_dewarp(self, out, counts, votes, src, n, cap, return_votes):
-        kept = getattr(self, "tta_counts", None)             # _collect_tta's layout is this call's too; its counts are not
-        res = self._collect_tta(out, counts, votes, src, n, cap, return_votes)
-        self.dewarp_counts, self.tta_counts = self.tta_counts, kept
-        return res
-
-    def _run_dewarp(self, fn, dewarper, ptrs, rows, cols, steps, n, threshold, sp, return_votes, views_ptr):
-        cap = sp.max_faces or self.max_detections
-        out = (rf_face * max(n * cap, 1))()
-        counts = (C.c_int * max(n, 1))()
-        votes, src = (C.c_int * max(n * cap, 1))(), (C.c_int * max(n * cap, 1))()
-        extra = () if fn is self._lib.rf_detect_dewarp_batch else (views_ptr,)
-        st = _lib.check(fn(dewarper._d, ptrs, rows, cols, steps, n, float(threshold), C.byref(sp), out, cap, counts, votes, src, *extra), self._h)
-        self.truncated = st == _lib.RF_ERR_TRUNCATED
-        return self._collect_dewarp(out, counts, votes, src, n, cap, return_votes)
+        rows = rows if rows is not None else [dewarper.rows if q else 0 for q in ptrs]
+        cols = cols if cols is not None else [dewarper.cols if q else 0 for q in ptrs]
+        frames = _device_frames(ptrs, rows, cols, steps) + (len(ptrs),)
+        return self._detect_merged(self._lib.rf_detect_dewarp_batch_device, dewarper._d, frames, threshold,
+                                   dewarp_spec(vote=vote, max_faces=max_faces, edge=edge), "dewarp_counts", return_votes, tail=(views_ptr,))
 
     def dewarp_merge(self, dewarper: Dewarper, per_view_faces, vote: bool = False, max_faces: int = 0, edge: int = 0,
                      cap_per_image: Optional[int] = None, return_votes: bool = False):
@@ -2331,23 +2091,12 @@ class RetinaFace:
         Returns as detect_dewarped; self.dewarp_counts as there."""
         n = len(per_view_faces)
         sp = dewarp_spec(vote=vote, max_faces=max_faces, edge=edge)
-        md = self.max_detections
         if any(len(frame) != dewarper.views for frame in per_view_faces):
             raise ValueError("per_view_faces: one list of %d views per frame" % dewarper.views)
-        passes = [_face_rows(f) for frame in per_view_faces for f in frame]
-        flat = np.zeros((max(len(passes), 1), md, 15), np.float32)
-        pc = (C.c_int * max(len(passes), 1))()
-        for p, r in enumerate(passes):
-            flat[p, :min(len(r), md)] = r[:md]
-            pc[p] = len(r)
-        cap = int(cap_per_image) if cap_per_image is not None else (sp.max_faces or md)
-        out = (rf_face * max(n * cap, 1))()
-        counts = (C.c_int * max(n, 1))()
-        votes, src = (C.c_int * max(n * cap, 1))(), (C.c_int * max(n * cap, 1))()
-        st = _lib.check(self._lib.rf_dewarp_merge_device(dewarper._d, n, C.byref(sp), flat.ctypes.data_as(C.POINTER(rf_face)), pc, out, cap,
-                                                         counts, votes, src), self._h)
-        self.truncated = st == _lib.RF_ERR_TRUNCATED
-        return self._collect_dewarp(out, counts, votes, src, n, cap, return_votes)
+        flat, pc = _pack_passes([f for frame in per_view_faces for f in frame], self.max_detections)
+        cap = int(cap_per_image) if cap_per_image is not None else (sp.max_faces or self.max_detections)
+        head = (dewarper._d, n, C.byref(sp), flat.ctypes.data_as(C.POINTER(rf_face)), pc)        # (a dewarper knows its frames' shape)
+        return self._merged_call(self._lib.rf_dewarp_merge_device, head, n, cap, "dewarp_counts", return_votes)
 
     def dewarp_device(self, dewarper: Dewarper, view: int, src_ptr: int, dst_ptr: int, step: Optional[int] = None,
                       dst_step: Optional[int] = None):
@@ -2363,22 +2112,9 @@ class RetinaFace:
         contrast boost, lit tiles stay as they are) and detected, with no host wait in between.  Returns what detect() returns for the
         enhanced frames.  enhanced_ptrs: device buffers that receive the enhanced copies (row pitch enhanced_steps, default cols * 3).
         self.tiles_enhanced holds, per frame, the number of tiles the enhancement touched."""
-        n = len(imgs)
-        ptrs = (C.c_void_p * max(n, 1))()
-        rows, cols, steps = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
-        keep = []
-        for i, im in enumerate(imgs):
-            if im is None or im.size == 0:
-                ptrs[i], rows[i], cols[i], steps[i] = None, 0, 0, 0
-                continue
-            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
-                raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
-            if im.strides[2] != 1 or im.strides[1] != 3:
-                im = np.ascontiguousarray(im)
-            keep.append(im)
-            ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
-        return self._run_enhanced(self._lib.rf_detect_enhanced_batch, ptrs, rows, cols, steps, n, threshold,
-                                  enhance_spec(tile, clip, dark_below), enhanced_ptrs, enhanced_steps)
+        f = _host_frames(imgs)
+        return self._run_enhanced(self._lib.rf_detect_enhanced_batch, *f.args, threshold, enhance_spec(tile, clip, dark_below), enhanced_ptrs,
+                                  enhanced_steps)
 
     def detect_enhanced_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], threshold: float = 0.5,
                                steps: Optional[Sequence[int]] = None, tile: int = 0, clip: int = 0, dark_below: int = 0,
@@ -2386,9 +2122,7 @@ class RetinaFace:
         """rf_detect_enhanced_batch_device: detect_enhanced for frames resident in device memory (0 / None: an empty frame).  The
         frames are not written."""
         n = len(ptrs)
-        p = (C.c_void_p * max(n, 1))(*ptrs)
-        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
-        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
+        p, r, c, s = _device_frames(ptrs, rows, cols, steps)
         return self._run_enhanced(self._lib.rf_detect_enhanced_batch_device, p, r, c, s, n, threshold, enhance_spec(tile, clip, dark_below),
                                   enhanced_ptrs, enhanced_steps)
 
@@ -2412,10 +2146,8 @@ class RetinaFace:
         destination may be its source exactly (same pointer and pitch).  Returns the number of tiles enhanced per frame."""
         n = len(src_ptrs)
         sp = spec if spec is not None else enhance_spec(tile, clip, dark_below)
-        p, d = (C.c_void_p * max(n, 1))(*src_ptrs), (C.c_void_p * max(n, 1))(*dst_ptrs)
-        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
-        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
-        ds = (C.c_int * max(n, 1))(*(dst_steps if dst_steps is not None else [3 * x for x in cols]))
+        p, r, c, s = _device_frames(src_ptrs, rows, cols, steps)
+        d, _, _, ds = _device_frames(dst_ptrs, rows, cols, dst_steps)
         tiles = (C.c_int * max(n, 1))()
         _lib.check(self._lib.rf_enhance_device(self._h, C.byref(sp), p, r, c, s, n, d, ds, tiles), self._h)
         return [int(tiles[i]) for i in range(n)]
@@ -2428,48 +2160,17 @@ class RetinaFace:
         faces of all passes are moved back and merged as in detect_tta.  Returns per frame the merged detections in SOURCE-FRAME
         pixels (anchor_index is -1); with return_votes also, per frame, how many candidates each face merged and the pass of the
         plan (pyramid_plan) its head came from.  self.pyramid_counts holds the true merged counts."""
-        n = len(imgs)
-        ptrs = (C.c_void_p * max(n, 1))()
-        rows, cols, steps = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
-        keep = []
-        for i, im in enumerate(imgs):
-            if im is None or im.size == 0:
-                ptrs[i], rows[i], cols[i], steps[i] = None, 0, 0, 0
-                continue
-            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
-                raise ValueError("frames must be uint8 H x W x 3 (CV_8UC3, BGR)")
-            if im.strides[2] != 1 or im.strides[1] != 3:
-                im = np.ascontiguousarray(im)
-            keep.append(im)
-            ptrs[i], rows[i], cols[i], steps[i] = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
-        return self._run_pyramid(self._lib.rf_detect_pyramid_batch, ptrs, rows, cols, steps, n, threshold,
-                                 pyramid_spec(levels, overlap, edge, full_frame, max_faces, vote), return_votes)
+        f = _host_frames(imgs)
+        return self._detect_merged(self._lib.rf_detect_pyramid_batch, self._h, f.args, threshold,
+                                   pyramid_spec(levels, overlap, edge, full_frame, max_faces, vote), "pyramid_counts", return_votes)
 
     def detect_pyramid_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], threshold: float = 0.5,
                               steps: Optional[Sequence[int]] = None, levels: int = 0, overlap: int = 0, edge: int = 0,
                               full_frame: bool = True, max_faces: int = 0, vote: bool = True, return_votes: bool = False):
         """rf_detect_pyramid_batch_device: detect_pyramid for frames resident in device memory (0 / None: an empty frame)."""
-        n = len(ptrs)
-        p = (C.c_void_p * max(n, 1))(*ptrs)
-        r, c = (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols)
-        s = (C.c_int * max(n, 1))(*(steps if steps is not None else [3 * x for x in cols]))
-        return self._run_pyramid(self._lib.rf_detect_pyramid_batch_device, p, r, c, s, n, threshold,
-                                 pyramid_spec(levels, overlap, edge, full_frame, max_faces, vote), return_votes)
-
-    def _collect_pyramid(self, out, counts, votes, src, n, cap, return_votes):
-        kept = getattr(self, "tta_counts", None)             # _collect_tta's layout is this call's too; its counts are not
-        res = self._collect_tta(out, counts, votes, src, n, cap, return_votes)
-        self.pyramid_counts, self.tta_counts = self.tta_counts, kept
-        return res
-
-    def _run_pyramid(self, fn, ptrs, rows, cols, steps, n, threshold, sp, return_votes):
-        cap = sp.max_faces or self.max_detections
-        out = (rf_face * max(n * cap, 1))()
-        counts = (C.c_int * max(n, 1))()
-        votes, src = (C.c_int * max(n * cap, 1))(), (C.c_int * max(n * cap, 1))()
-        st = _lib.check(fn(self._h, ptrs, rows, cols, steps, n, float(threshold), C.byref(sp), out, cap, counts, votes, src), self._h)
-        self.truncated = st == _lib.RF_ERR_TRUNCATED
-        return self._collect_pyramid(out, counts, votes, src, n, cap, return_votes)
+        frames = _device_frames(ptrs, rows, cols, steps) + (len(ptrs),)
+        return self._detect_merged(self._lib.rf_detect_pyramid_batch_device, self._h, frames, threshold,
+                                   pyramid_spec(levels, overlap, edge, full_frame, max_faces, vote), "pyramid_counts", return_votes)
 
     def pyramid_merge(self, rows: Sequence[int], cols: Sequence[int], per_pass_faces, levels: int = 0, overlap: int = 0, edge: int = 0,
                       full_frame: bool = True, max_faces: int = 0, vote: bool = True, cap_per_image: Optional[int] = None,
@@ -2479,7 +2180,6 @@ class RetinaFace:
         forward pass runs.  Returns as detect_pyramid; self.pyramid_counts holds the true merged counts."""
         n = len(rows)
         sp = pyramid_spec(levels, overlap, edge, full_frame, max_faces, vote)
-        md = self.max_detections
         if len(per_pass_faces) != n:
             raise ValueError("per_pass_faces: one list of passes per frame")
         for i in range(n):
@@ -2487,21 +2187,8 @@ class RetinaFace:
                                                                                     self.net_w, None, 0)
             if want >= 0 and len(per_pass_faces[i]) != want:
                 raise ValueError("per_pass_faces[%d]: %d passes, the plan has %d" % (i, len(per_pass_faces[i]), want))
-        passes = [_face_rows(f) for frame in per_pass_faces for f in frame]
-        flat = np.zeros((max(len(passes), 1), md, 15), np.float32)
-        pc = (C.c_int * max(len(passes), 1))()
-        for p, r in enumerate(passes):
-            flat[p, :min(len(r), md)] = r[:md]
-            pc[p] = len(r)
-        cap = int(cap_per_image) if cap_per_image is not None else (sp.max_faces or md)
-        out = (rf_face * max(n * cap, 1))()
-        counts = (C.c_int * max(n, 1))()
-        votes, src = (C.c_int * max(n * cap, 1))(), (C.c_int * max(n * cap, 1))()
-        st = _lib.check(self._lib.rf_pyramid_merge_device(self._h, (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols), n,
-                                                          C.byref(sp), flat.ctypes.data_as(C.POINTER(rf_face)), pc, out, cap, counts, votes,
-                                                          src), self._h)
-        self.truncated = st == _lib.RF_ERR_TRUNCATED
-        return self._collect_pyramid(out, counts, votes, src, n, cap, return_votes)
+        return self._merge_call(self._lib.rf_pyramid_merge_device, rows, cols, sp, per_pass_faces, cap_per_image, "pyramid_counts",
+                                return_votes)
 
     def zoom_device(self, src_ptr: int, rows: int, cols: int, z: int, x0: int, y0: int, tw: int, th: int, dst_ptr: int,
                     step: Optional[int] = None, dst_step: Optional[int] = None):
@@ -2514,9 +2201,7 @@ class RetinaFace:
 
     def enqueue_device(self, ptrs, rows, cols, threshold: float = 0.5, steps: Optional[Sequence[int]] = None) -> int:
         n = len(ptrs)
-        p = (C.c_void_p * n)(*ptrs)
-        r, c = (C.c_int * n)(*rows), (C.c_int * n)(*cols)
-        s = (C.c_int * n)(*(steps if steps is not None else [3 * x for x in cols]))
+        p, r, c, s = _device_frames(ptrs, rows, cols, steps)
         t = C.c_int()
         _lib.check(self._lib.rf_enqueue_batch_device(self._h, p, r, c, s, n, float(threshold), C.byref(t)), self._h)
         return t.value
@@ -2566,9 +2251,7 @@ class RetinaFace:
     def prepare_device_batch(self, ptrs, rows, cols, steps=None):
         """Build the C argument arrays of rf_enqueue_batch_device once for a batch of device frames that is submitted
         repeatedly (a ring of camera buffers): what a C/C++ caller keeps on its side anyway.  Returns an opaque batch."""
-        n = len(ptrs)
-        steps = [3 * x for x in cols] if steps is None else steps
-        return ((C.c_void_p * n)(*ptrs), (C.c_int * n)(*rows), (C.c_int * n)(*cols), (C.c_int * n)(*steps), n, C.c_int())
+        return _device_frames(ptrs, rows, cols, steps) + (len(ptrs), C.c_int())
 
     def enqueue_prepared(self, batch, threshold: float = 0.5) -> int:
         p, r, c, s, n, t = batch
@@ -2669,10 +2352,5 @@ class RetinaFace:
             k = min(counts[i], cap)
             idx = (C.c_int32 * max(k, 1))()
             got = self._lib.rf_last_anchor_indices(self._h, i, idx, k) if anchors else -1
-            dets = []
-            for j in range(k):
-                r = rows[i * cap + j]
-                dets.append(Detection(float(r[0]), tuple(float(v) for v in r[1:5]), tuple(float(v) for v in r[5:10]),
-                                      tuple(float(v) for v in r[10:15]), int(idx[j]) if got >= 0 else -1))
-            res.append(dets)
+            res.append([_detection(rows[i * cap + j], int(idx[j]) if got >= 0 else -1) for j in range(k)])
         return res
