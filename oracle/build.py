@@ -35,12 +35,12 @@ def lib() -> C.CDLL:
     if _lib is None:
         _lib = C.CDLL(build())
         _lib.rfo_decode.restype = C.c_int
-        _lib.rfo_decode.argtypes = [C.POINTER(C.POINTER(C.c_float)), C.c_int, C.c_int, C.c_float, C.POINTER(_Face),
-                                    C.POINTER(C.c_int32), C.c_int]
+        _lib.rfo_decode.argtypes = [C.POINTER(C.POINTER(C.c_float)), C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.c_int,
+                                    C.POINTER(_Face), C.POINTER(C.c_int32), C.c_int]
         _lib.rfo_nms.restype = C.c_int
         _lib.rfo_nms.argtypes = [C.POINTER(_Face), C.POINTER(C.c_int32), C.c_int, C.c_float]
         _lib.rfo_anchors_plane.restype = None
-        _lib.rfo_anchors_plane.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        _lib.rfo_anchors_plane.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float)]
     return _lib
 
 
@@ -58,17 +58,27 @@ def cv_resize_linear(img, fx: float, fy: float):
     return out
 
 
-def decode_nms(heads9, net_h: int, net_w: int, threshold: float, nms_threshold: float, cap: int = 1 << 16):
+def _ratios(ratios):
+    r = (C.c_float * max(len(ratios), 1))(*ratios)
+    return r, len(ratios)
+
+
+def decode_nms(heads9, net_h: int, net_w: int, threshold: float, nms_threshold: float, cap: int = 1 << 16, ratios=(1.0,)):
     """heads9: the 9 blobs of ONE image (C,H,W fp32) in binding order (stride 32,16,8 x prob,bbox,landmark).
+    `ratios`: the anchor ratios of the network preset ("net3": (1.0,), "net3a": (1.0, 1.5)); the blobs carry 2 * len(ratios) anchors.
     Returns (candidate rows [n,15], candidate anchor idx [n], kept rows [k,15], kept anchor idx [k])."""
     l = lib()
     arrs = [np.ascontiguousarray(a, dtype=np.float32) for a in heads9]
+    na = 2 * len(ratios)
+    assert all(a.shape[0] == c * na for a, c in zip(arrs, (2, 4, 10) * 3)), ([a.shape for a in arrs], na)
+    rat, nrat = _ratios(ratios)
     ptrs = (C.POINTER(C.c_float) * 9)(*[a.ctypes.data_as(C.POINTER(C.c_float)) for a in arrs])
     faces = (_Face * cap)()
     idx = (C.c_int32 * cap)()
-    n = l.rfo_decode(ptrs, net_h, net_w, threshold, faces, idx, cap)
+    n = l.rfo_decode(ptrs, net_h, net_w, threshold, rat, nrat, faces, idx, cap)
+    assert n >= 0, n
     if n > cap:
-        return decode_nms(heads9, net_h, net_w, threshold, nms_threshold, cap=n)
+        return decode_nms(heads9, net_h, net_w, threshold, nms_threshold, cap=n, ratios=ratios)
     cand = np.ctypeslib.as_array(C.cast(faces, C.POINTER(C.c_float)), shape=(cap, 15))[:n].copy()
     cidx = np.array(idx[:n], dtype=np.int32)
     k = l.rfo_nms(faces, idx, n, nms_threshold)
@@ -77,7 +87,8 @@ def decode_nms(heads9, net_h: int, net_w: int, threshold: float, nms_threshold: 
     return cand, cidx, kept, kidx
 
 
-def anchors_plane(stride_index: int, h: int, w: int) -> np.ndarray:
-    out = np.empty((2 * h * w, 4), np.float32)
-    lib().rfo_anchors_plane(stride_index, h, w, out.ctypes.data_as(C.POINTER(C.c_float)))
+def anchors_plane(stride_index: int, h: int, w: int, ratios=(1.0,)) -> np.ndarray:
+    out = np.empty((2 * len(ratios) * h * w, 4), np.float32)
+    rat, nrat = _ratios(ratios)
+    lib().rfo_anchors_plane(stride_index, h, w, rat, nrat, out.ctypes.data_as(C.POINTER(C.c_float)))
     return out

@@ -5,7 +5,7 @@
  * cpu_baseline leg, never by the product.
  *
  * Follows, function by function:
- *   rfo_anchors_plane   retinaface/RetinaFace.cpp:127-154  (base anchors of :34-125, net3 cfg :245-268)
+ *   rfo_anchors_plane   retinaface/RetinaFace.cpp:127-154  (base anchors of :34-125, net3 / net3a cfg :215-221, :245-268)
  *   rfo_bbox_pred       retinaface/RetinaFace.cpp:378-398
  *   rfo_clip_box        retinaface/RetinaFace.cpp:179-199
  *   rfo_landmark_pred   retinaface/RetinaFace.cpp:418-432
@@ -29,17 +29,19 @@ typedef struct { float score; rfo_box rect; float px[5]; float py[5]; } rfo_face
 static const int kStrides[3] = {32, 16, 8};
 static const int kScales[3][2] = {{32, 16}, {8, 4}, {2, 1}};
 
-/* base anchors: generate_anchors(base 16, ratio {1.0}, scales) -- RetinaFace.cpp:34-103 */
-static void base_anchor(int scale, rfo_box *out)
+/* base anchors: generate_anchors(base 16, ratios, scales) -- RetinaFace.cpp:34-103.  "net3" has the one ratio 1.0, "net3a" the
+ * ratios {1.0, 1.5} (:215-221); A = 2 * n_ratios anchors per cell, ratios outer, scales inner (:86-91). */
+#define RFO_MAX_RATIOS 4
+static void base_anchor(float ratio, int scale, rfo_box *out)
 {
     rfo_box b = {0.f, 0.f, 15.f, 15.f};
-    /* _ratio_enum with ratio 1.0 */
+    /* _ratio_enum */
     float w = b.x2 - b.x1 + 1, h = b.y2 - b.y1 + 1;
     float xc = b.x1 + 0.5 * (w - 1), yc = b.y1 + 0.5 * (h - 1);
     float size = w * h;
-    float sc = size / 1.0f;
+    float sc = size / ratio;
     float w2 = roundf(sqrtf(sc));
-    float h2 = roundf(w2 * 1.0f);
+    float h2 = roundf(w2 * ratio);
     rfo_box r;
     r.x1 = xc - 0.5 * (w2 - 1); r.y1 = yc - 0.5 * (h2 - 1);
     r.x2 = xc + 0.5 * (w2 - 1); r.y2 = yc + 0.5 * (h2 - 1);
@@ -51,14 +53,14 @@ static void base_anchor(int scale, rfo_box *out)
     out->x2 = xc + 0.5 * (w - 1); out->y2 = yc + 0.5 * (h - 1);
 }
 
-/* out: [2*height*width] boxes, k-major then row then col */
-void rfo_anchors_plane(int stride_index, int height, int width, rfo_box *out)
+/* out: [2*n_ratios*height*width] boxes, k-major (k = ratio * 2 + scale) then row then col */
+void rfo_anchors_plane(int stride_index, int height, int width, const float *ratios, int n_ratios, rfo_box *out)
 {
     int stride = kStrides[stride_index];
     size_t n = 0;
-    for (int k = 0; k < 2; k++) {
+    for (int k = 0; k < 2 * n_ratios; k++) {
         rfo_box b;
-        base_anchor(kScales[stride_index][k], &b);
+        base_anchor(ratios[k / 2], kScales[stride_index][k % 2], &b);
         for (int ih = 0; ih < height; ih++) {
             int sh = ih * stride;
             for (int iw = 0; iw < width; iw++) {
@@ -110,25 +112,27 @@ static void rfo_landmark_pred(rfo_box anchor, const float pts[10], float px[5], 
 }
 
 /*
- * heads[9]: for stride 32,16,8: cls_prob_reshape (4,h,w), bbox_pred (8,h,w), landmark_pred (20,h,w),
+ * heads[9]: for stride 32,16,8: cls_prob_reshape (2A,h,w), bbox_pred (4A,h,w), landmark_pred (10A,h,w) with A = 2 * n_ratios,
  * NCHW fp32 for ONE image.  Writes up to cap candidates in the reference's visiting order together with
  * their global anchor index; returns the number found (may exceed cap: caller must re-run with more room).
  */
-int rfo_decode(const float *const heads[9], int net_h, int net_w, float threshold,
+int rfo_decode(const float *const heads[9], int net_h, int net_w, float threshold, const float *ratios, int n_ratios,
                rfo_face *out, int32_t *anchor_index, int cap)
 {
     int n = 0;
+    if (n_ratios < 0 || n_ratios > RFO_MAX_RATIOS) return -1;
+    const size_t na = 2 * (size_t)n_ratios;
     int goff = 0;
     for (int si = 0; si < 3; si++) {
         int stride = kStrides[si];
         int h = net_h / stride, w = net_w / stride;
         size_t count = (size_t)h * w;
-        const float *score = heads[si * 3 + 0] + 2 * count;   /* second half of the blob */
+        const float *score = heads[si * 3 + 0] + na * count;   /* second half of the blob */
         const float *bbox = heads[si * 3 + 1];
         const float *lmk = heads[si * 3 + 2];
-        rfo_box *anchors = (rfo_box *)malloc(sizeof(rfo_box) * 2 * count);
-        rfo_anchors_plane(si, h, w, anchors);
-        for (size_t num = 0; num < 2; num++) {
+        rfo_box *anchors = (rfo_box *)malloc(sizeof(rfo_box) * (na ? na : 1) * count);
+        rfo_anchors_plane(si, h, w, ratios, n_ratios, anchors);
+        for (size_t num = 0; num < na; num++) {
             for (size_t j = 0; j < count; j++) {
                 float conf = score[j + count * num];
                 if (conf <= threshold) continue;
@@ -149,7 +153,7 @@ int rfo_decode(const float *const heads[9], int net_h, int net_w, float threshol
                 n++;
             }
         }
-        goff += (int)(2 * count);
+        goff += (int)(na * count);
         free(anchors);
     }
     return n;

@@ -37,6 +37,23 @@ use the same wiring (anchor a of a cell, wires of that cell's pixel):
 Candidates are read at threshold THR = 0.02 (logit -3.9): an open gate gives logit >= 0, a closed one <= -59, so the count is the number of
 open gates in fp32 and fp16 alike (more than 3 logits of margin on either side).
 
+Four anchors per cell ("net3a": ratios 1 and 1.5, anchors 2 and 3 of stride 8 are 26 x 40 and 13 x 20 px, the latter at fractional
+coordinates).  conv0 has eight channels, hence eight wires: the A = 4 sets (HEAD_SETS4) spend four on gates and give up SF and SN --
+wire 3 is GATE2, wire 7 is GATE3.  The heads of the net are widened first (net3a_models.widen_heads: shapes only, every weight is then
+written here):
+  foreground logit   bias_a - 0.25 * GATE_a + SC / 32         256 score levels over logits 0 .. 8; the anchors of a cell read the same SC and are
+                                                              told apart by bias_a, a multiple of 1 / 128 (a quarter of a level): 1024 distinct logits
+  dw, dh             SZ * DWW4[a], SZ * DHW4[a]               0 -> the anchor's own width AND height exactly
+  dx, dy             DX * DXW4[a], DY * DYW4[a]               negative for anchors 0, 2, positive for anchors 1, 3
+  landmarks          from the bias alone (LMK4[a] = LMK * (1 + a / 4)): x and y offsets differ, so a landmark y computed with the width
+                     lands elsewhere
+                     -- eight weights and ten biases per anchor, all different from those of the three other anchors of the cell
+  `std4`     stride 8 only, foreground biases 3/128, 1/128, 0, 2/128 for anchors 0 .. 3: within a cell the order is 0, 3, 1, 2
+  `tied4`    `std4` with all four biases 0: the four anchors of a cell tie exactly
+  `strides4` all three strides, foreground bias 1 + the `std4` bias + one score level per stride (0, 1/32, 2/32: coincident cells read the
+             same score pixel and must not tie): a gate painted on a stride-32 cell's pixel opens the coincident cells of stride 16 and 8; a
+             gate on a stride-8 cell with an odd coordinate opens that cell alone
+
 SCENARIOS is the table: name -> Scenario(net, heads, frame builder, condition).  `check(sc, cand, cidx, kept, kidx)` asserts a scenario's
 condition on a restatement result (oracle.build.decode_nms), whoever produced the head blobs: a scenario that silently missed its regime
 fails.  Tie conditions (`ties=True`) are only asserted where the caller says the blobs are fp32.
@@ -78,9 +95,42 @@ HEAD_SETS = {"std": {8: (_anchor(0, 2.0 ** -13), _anchor(1))},
              "strides": {s: (_anchor(0, 1.0), _anchor(1, 1.0)) for s in STRIDES}}
 
 
+# four anchors per cell: wires 3 (SF) and 7 (SN) become the gates of anchors 2 and 3
+GATE2, GATE3 = SF, SN
+GATE4 = (GATE0, GATE1, GATE2, GATE3)
+RATIOS4 = (1.0, 1.5)                                          # "net3a"
+FG_BIAS4 = tuple(F32(v / 128) for v in (3, 1, 0, 2))          # order within a cell: anchors 0, 3, 1, 2
+STRIDE_BIAS4 = {32: F32(0), 16: F32(1 / 32), 8: F32(2 / 32)}  # `strides4`: coincident cells of the three strides read ONE score pixel; one level apart
+
+
+# Every box and landmark row of a cell differs from every other: a kernel that took anchor a ^ 2's (or a ^ 1's) channels, or dy for dx, or
+# dh for dw, decodes other numbers.  All dyadic, so a wire painted 0 still gives the anchor itself exactly.
+DXW4 = tuple(F32(v) for v in (-1 / 32, 1 / 32, -1 / 64, 1 / 16))
+DYW4 = tuple(F32(v) for v in (-1 / 64, 1 / 16, -1 / 32, 1 / 32))
+DWW4 = tuple(F32(v) for v in (1 / 32, 3 / 128, 1 / 64, 5 / 128))
+DHW4 = tuple(F32(v) for v in (3 / 128, 1 / 32, 5 / 128, 1 / 64))
+LMK4 = tuple(tuple(F32(v * (1 + a / 4)) for v in LMK) for a in range(4))      # multiples of 1 / 8: products with 13 .. 512 stay exact
+
+
+def _anchor4(a: int, bias: float):
+    return dict(fg=(F32(bias), {GATE4[a]: F32(-0.25), SC: F32(1 / 32)}),
+                dx=(F32(0), {DX: DXW4[a]}), dy=(F32(0), {DY: DYW4[a]}),
+                dw=(F32(0), {SZ: DWW4[a]}), dh=(F32(0), {SZ: DHW4[a]}), lmk=LMK4[a])
+
+
+HEAD_SETS4 = {"std4": {8: tuple(_anchor4(a, FG_BIAS4[a]) for a in range(4))},
+              "tied4": {8: tuple(_anchor4(a, 0.0) for a in range(4))},
+              "strides4": {s: tuple(_anchor4(a, 1.0 + STRIDE_BIAS4[s] + FG_BIAS4[a]) for a in range(4)) for s in STRIDES}}
+
+
 def wire_net(net, heads: Optional[str] = None):
-    """A copy of `net` (a NetSpec) under the wire set, without calibrated weights; `heads` names a head set (None: heads all 0)."""
-    out = copy.deepcopy(net)
+    """A copy of `net` (a NetSpec) under the wire set, without calibrated weights; `heads` names a head set (None: heads all 0).  A set of
+    HEAD_SETS4 gets heads of four anchors per cell."""
+    if heads in HEAD_SETS4:
+        from net3a_models import widen_heads
+        out = widen_heads(net)
+    else:
+        out = copy.deepcopy(net)
     out.int8_qweights = {}
     for l in out.layers:
         if l.type == "Convolution":
@@ -108,7 +158,7 @@ def wire_net(net, heads: Optional[str] = None):
             if l.scale_bias:
                 l.blobs[1][...] = 0
     if heads is not None:
-        set_heads(out, HEAD_SETS[heads])
+        set_heads(out, HEAD_SETS4[heads] if heads in HEAD_SETS4 else HEAD_SETS[heads])
     return out
 
 
@@ -117,7 +167,8 @@ def set_heads(net, head_set) -> None:
     for s in STRIDES:
         cls, box, lmk = (net.layer(f"face_rpn_{n}_stride{s}") for n in ("cls_score", "bbox_pred", "landmark_pred"))
         na = cls.blobs[0].shape[0] // 2
-        assert na == 2 and box.blobs[0].shape[0] == 4 * na and lmk.blobs[0].shape[0] == 10 * na
+        assert na in (2, 4) and box.blobs[0].shape[0] == 4 * na and lmk.blobs[0].shape[0] == 10 * na
+        assert s not in head_set or len(head_set[s]) == na, (s, na)
         for a in range(na):
             spec = head_set[s][a] if s in head_set else None
             if spec is None:
@@ -137,10 +188,10 @@ def wire_view(frame: np.ndarray, stride: int, wire: int) -> np.ndarray:
     return frame[dy::stride, dx::stride, 2 - colour]
 
 
-def paint(hw: Tuple[int, int], stride: int, wires: Dict[int, np.ndarray]) -> np.ndarray:
+def paint(hw: Tuple[int, int], stride: int, wires: Dict[int, np.ndarray], gates=GATE) -> np.ndarray:
     """A BGR uint8 frame of size hw: every gate closed, every other wire 0, then `wires` {wire: uint8 array over the cells of `stride`}."""
     frame = np.zeros((hw[0], hw[1], 3), np.uint8)
-    for g in GATE:
+    for g in gates:
         wire_view(frame, 8, g)[...] = OFF
     for wire, values in wires.items():
         v = wire_view(frame, stride, wire)
@@ -277,6 +328,8 @@ class Scenario(NamedTuple):
     extra: Optional[str] = None          # a named condition of `check`
     max_tie: int = 1                     # the largest group of equal scores the design makes (1: all distinct; the reference's std::sort
                                          # leaves the order of equal scores open, so its build is compared only where groups stay small)
+    na: int = 2                          # anchors per cell: 2 ("net3") or 4 ("net3a")
+    expect: Optional[Callable[[], list]] = None      # the global anchor indices of the candidates, ascending, where the design names them
 
 
 SCENARIOS: Dict[str, Scenario] = {}
@@ -304,6 +357,205 @@ for _n in MIXED:
     SCENARIOS[f"mixed{_n}"] = Scenario(LARGE, "std", (lambda n=_n: counts_frame(LARGE, n)), n=_n, kept="some" if _n >= 63 else None)
 
 
+# ------------------------------------------------------------------------------------------------------------ four anchors per cell
+SIZES4 = ((128, 160), (96, 160))                             # stride-8 maps 16 x 20 (blocks of 64 pixels filled exactly) and 12 x 20; on the
+                                                              # second the last block of every level is partial: 15, 60 and 240 cells
+
+
+def network_of(sc) -> str:
+    return "net3a" if sc.na == 4 else "net3"
+
+
+def ratios_of(sc) -> Tuple[float, ...]:
+    return RATIOS4 if sc.na == 4 else (1.0,)
+
+
+def _blank4(hw):
+    h, w = hw[0] // 8, hw[1] // 8
+    return {k: np.zeros((h, w), np.uint8) for k in (SC, SZ, DX, DY)} | {g: np.full((h, w), OFF, np.uint8) for g in GATE4}
+
+
+def _paint4(hw, w):
+    return paint(hw, 8, w, gates=GATE4)
+
+
+def _levels4(hw, w):
+    """distinct score levels and distinct (DX, DY) per stride-8 cell: SC a bijection of the cell's rank (maps of up to 256 cells are all
+    distinct; the scenarios open fewer cells than that), DX, DY below 64 (up to 2 anchor sizes)"""
+    for r, (i, j) in enumerate(_cells(hw)):
+        w[SC][i, j] = (r * 37) % 256
+        w[DX][i, j], w[DY][i, j] = (7 * i + 3 * j) % 64, (5 * i + 11 * j + 1) % 64
+
+
+def global_index(hw, stride, a, i, j, na=4) -> int:
+    """anchor_offset(stride) + a * h * w + cell of the net of size hw"""
+    off = anchor_offsets(hw, na)[stride]
+    h, w = hw[0] // stride, hw[1] // stride
+    return off + a * h * w + i * w + j
+
+
+def alone_cells(hw):
+    """The stride-8 cells the `alone` frames open: every cell with both coordinates a multiple of 4 (which opens the coincident stride-32
+    and stride-16 cells), the stride-16 cells (2, 2 + 4k) (stride-8 cells (4, 4 + 8k): not on the stride-32 grid) and the stride-8 cells
+    (odd, odd) of every sixth column."""
+    h, w = hw[0] // 8, hw[1] // 8
+    cells = {(i, j) for i in range(0, h, 4) for j in range(0, w, 4)} | {(4 * 1, 4 + 8 * k) for k in range(w // 8)}
+    cells |= {(2, 6 + 8 * k) for k in range((w - 6 + 7) // 8)} | {(i, j) for i in range(1, h, 4) for j in range(1, w, 6)}
+    return sorted(cells)
+
+
+def alone_frame(hw, a):
+    """Head set `strides4`: the gate of anchor a alone, on alone_cells; distinct DX, DY and score level per cell."""
+    w = _blank4(hw)
+    _levels4(hw, w)
+    for r, (i, j) in enumerate(alone_cells(hw)):
+        w[GATE4[a]][i, j], w[SC][i, j] = 0, 3 * r          # every third level: the strides' biases (STRIDE_BIAS4) fill the two between
+    assert 3 * r <= 255
+    return _paint4(hw, w)
+
+
+def alone_expect(hw, a):
+    idx = []
+    for i, j in alone_cells(hw):
+        for s in STRIDES:
+            q = s // 8
+            if i % q == 0 and j % q == 0:
+                idx.append(global_index(hw, s, a, i // q, j // q))
+    return sorted(idx)
+
+
+def all4_cells(hw):
+    h, w = hw[0] // 8, hw[1] // 8
+    return [(i, j) for i in (3, h - 4) for j in (3, w - 4)]
+
+
+def all4_frame(hw, tied=False):
+    """All four gates open on four cells far apart (`std4`: four distinct scores per cell; `tied4`: one score on all sixteen), every
+    regression wire 0: each box is its anchor exactly, and the square and the tall box of one cell overlap (IoU 0.675)."""
+    w = _blank4(hw)
+    for r, (i, j) in enumerate(all4_cells(hw)):
+        for g in GATE4:
+            w[g][i, j] = 0
+        w[SC][i, j] = 8 if tied else 16 + 40 * r
+    if tied:
+        w[SC][...] = 8
+    return _paint4(hw, w)
+
+
+def asym_cells(hw):
+    h, w = hw[0] // 8, hw[1] // 8
+    return [(i, j) for i in (4, h - 5) for j in (5, 10, w - 6)]
+
+
+def asym_frame(hw):
+    """Anchors 2 (26 x 40) and 3 (13 x 20) alone, on interior cells far apart: dx = -0.625 / +2.5, dy = -0.25 / +0.25 (DX = 40, DY = 8),
+    dw = dh = 0."""
+    w = _blank4(hw)
+    for r, (i, j) in enumerate(asym_cells(hw)):
+        w[GATE2][i, j] = w[GATE3][i, j] = 0
+        w[SC][i, j], w[DX][i, j], w[DY][i, j] = 10 + 30 * r, 40, 8
+    return _paint4(hw, w)
+
+
+def clip4_frame(hw):
+    """All four anchors on the four corner cells (the non-square anchors clip on every border; anchor 3 of the top-left cell keeps its
+    fractional x1 = 1.5), on a cell whose boxes are 50 .. 20000 times the anchor (clipped on all four borders), and on cells whose DX / DY carry
+    the boxes outside: to the left / above for anchors 0 and 2, to the right / below for anchors 1 and 3 -- clipped on ONE side only, which
+    leaves x2 - x1 < 0 (y2 - y1 < 0)."""
+    w = _blank4(hw)
+    h, ww = hw[0] // 8, hw[1] // 8
+    spots = {(0, 0): {}, (0, ww - 1): {}, (h - 1, 0): {}, (h - 1, ww - 1): {}, (h // 2, ww // 2): {SZ: 255}, (3, 5): {DX: 255}, (5, 13): {DY: 255},
+             (h - 3, 9): {DX: 255, DY: 255, SZ: 20}, (1, 1): {SZ: 40}, (h - 2, ww - 2): {DX: 30, DY: 90}}
+    for r, ((i, j), kv) in enumerate(spots.items()):
+        for g in GATE4:
+            w[g][i, j] = 0
+        w[SC][i, j] = 5 + 23 * r
+        for k, v in kv.items():
+            w[k][i, j] = v
+    return _paint4(hw, w)
+
+
+def _slots4(hw, n):
+    """the first n (anchor, i, j): the four anchors of a cell, then the next cell of the stride-8 map (row-major)"""
+    slots = [(a, i, j) for i, j in _cells(hw) for a in range(4)]
+    assert n <= len(slots)
+    return slots[:n]
+
+
+def count4_frame(hw, n):
+    """n open gates, every regression wire 0 (each box is its anchor EXACTLY: rows of an overflowing launch compare bit for bit), a distinct
+    score level per cell."""
+    w = _blank4(hw)
+    assert n <= 4 * 256
+    for r, (i, j) in enumerate(_cells(hw)):
+        w[SC][i, j] = (r * 37) % 256
+    for a, i, j in _slots4(hw, n):
+        w[GATE4[a]][i, j] = 0
+    return _paint4(hw, w)
+
+
+def sparse4_frame(hw, n):
+    """n boxes that do not meet, the anchors in turn: all kept."""
+    w = _blank4(hw)
+    h, ww = hw[0] // 8, hw[1] // 8
+    cells = [(i, j) for i in range(1, h, 5)[:3] for j in range(1, ww, 5)]
+    assert n <= len(cells)
+    for r, (i, j) in enumerate(cells[:n]):
+        w[GATE4[r % 4]][i, j], w[SC][i, j] = 0, 20 + 9 * r
+    return _paint4(hw, w)
+
+
+def tag4(hw) -> str:
+    return f"{hw[0]}x{hw[1]}"
+
+
+for _hw in SIZES4:                                            # the A = 4 scenarios, per size: a4_<what>_<size>; SCENARIOS4 lists their names
+    _t = tag4(_hw)
+    for _a in range(4):
+        SCENARIOS[f"a4_alone{_a}_{_t}"] = Scenario(_hw, "strides4", (lambda hw=_hw, a=_a: alone_frame(hw, a)), extra=f"alone{_a}", na=4,
+                                                   expect=(lambda hw=_hw, a=_a: alone_expect(hw, a)))
+    SCENARIOS[f"a4_all_{_t}"] = Scenario(_hw, "std4", (lambda hw=_hw: all4_frame(hw)), n=16, extra="all4", na=4)
+    SCENARIOS[f"a4_alltied_{_t}"] = Scenario(_hw, "tied4", (lambda hw=_hw: all4_frame(hw, tied=True)), n=16, one_score=True, extra="all4", max_tie=16, na=4)
+    SCENARIOS[f"a4_asym_{_t}"] = Scenario(_hw, "std4", (lambda hw=_hw: asym_frame(hw)), n=12, kept="all", extra="asym", na=4)
+    SCENARIOS[f"a4_clip_{_t}"] = Scenario(_hw, "std4", (lambda hw=_hw: clip4_frame(hw)), n=40, extra="clip4", na=4)
+    for _n in (64, 65, 300):
+        SCENARIOS[f"a4_count{_n}_{_t}"] = Scenario(_hw, "std4", (lambda hw=_hw, n=_n: count4_frame(hw, n)), n=_n, kept="some", na=4)
+    for _n in (8, 9):
+        SCENARIOS[f"a4_kept{_n}_{_t}"] = Scenario(_hw, "std4", (lambda hw=_hw, n=_n: sparse4_frame(hw, n)), n=_n, kept="all", na=4)
+SCENARIOS4 = [n for n in SCENARIOS if n.startswith("a4_")]
+
+
+def anchor_numbers(idx, hw, na):
+    """global anchor indices -> (stride, anchor number within the cell, cell index) arrays"""
+    idx = np.asarray(idx, np.int64)
+    st, an, gp = (np.full(idx.shape, -1, np.int64) for _ in range(3))
+    offs = anchor_offsets(hw, na)
+    for s in STRIDES:
+        cells = (hw[0] // s) * (hw[1] // s)
+        m = (idx >= offs[s]) & (idx < offs[s] + na * cells)
+        st[m], an[m], gp[m] = s, (idx[m] - offs[s]) // cells, (idx[m] - offs[s]) % cells
+    assert (st > 0).all()
+    return st, an, gp
+
+
+def base_anchors4():
+    from oracle.retinaface_post import base_anchors
+    return base_anchors(RATIOS4)
+
+
+def swap_moves(row, idx, hw) -> float:
+    """By how many pixels the box centre of candidate `row` (anchor `idx` of a four-anchor net) would move if bbox_pred multiplied dx by the
+    anchor's height and dy by its width: |dx| * |height - width| and |dy| * |width - height|, the larger; dx, dy recovered from the row."""
+    st, an, gp = (int(v[0]) for v in anchor_numbers([idx], hw, 4))
+    b = base_anchors4()[st][an].astype(np.float64)
+    ww = hw[1] // st
+    width, height = b[2] - b[0] + 1, b[3] - b[1] + 1
+    ctr_x, ctr_y = b[0] + 0.5 * (width - 1) + st * (gp % ww), b[1] + 0.5 * (height - 1) + st * (gp // ww)
+    dx = (0.5 * (float(row[1]) + float(row[3])) - ctr_x) / width
+    dy = (0.5 * (float(row[2]) + float(row[4])) - ctr_y) / height
+    return max(abs(dx) * abs(height - width), abs(dy) * abs(height - width))
+
+
 def iou_f32(a, b) -> np.float32:
     """IoU of two boxes (x1, y1, x2, y2) with the +1 convention in float32, the restatement's op order (rf_post_ref.c rfo_nms); 0 where the
     restatement skips the pair."""
@@ -325,11 +577,11 @@ def sorted_candidates(cand, cidx):
     return cand[order], cidx[order]
 
 
-def anchor_offsets(hw):
+def anchor_offsets(hw, na=2):
     offs, acc = {}, 0
     for s in STRIDES:
         offs[s] = acc
-        acc += 2 * (hw[0] // s) * (hw[1] // s)
+        acc += na * (hw[0] // s) * (hw[1] // s)
     return offs
 
 
@@ -375,6 +627,64 @@ def check(sc: Scenario, cand, cidx, kept, kidx, ties: bool = True, nms: float = 
         srt, _ = sorted_candidates(cand, cidx)
         i, j = pairs_pick(srt)
         assert F32(0.2) < iou_f32(srt[i, 1:5], srt[j, 1:5]) < F32(0.8)
+    if sc.na == 4:
+        check4(sc, cand, cidx, kept, kidx, ties, nms)
+
+
+def check4(sc: Scenario, cand, cidx, kept, kidx, ties: bool, nms: float) -> None:
+    """The conditions of the four-anchor scenarios."""
+    hw = sc.hw
+    st, an, gp = anchor_numbers(cidx, hw, 4)
+    kst, kan, kgp = anchor_numbers(kidx, hw, 4)
+    if sc.expect is not None:
+        assert sorted(cidx.tolist()) == sc.expect(), (sorted(cidx.tolist()), sc.expect())
+    if sc.extra and sc.extra.startswith("alone"):
+        a = int(sc.extra[5:])
+        assert (an == a).all() and (kan == a).all()               # every index is anchor_offset + a * hw + gp of the one open anchor
+        for s in STRIDES:
+            assert (st == s).sum() >= 3 and (kst == s).sum() >= 1, (s, int((st == s).sum()), int((kst == s).sum()))
+        c8 = cand[st == 8]                                        # (the 512- and 128-px anchors of the coarser strides clip to the frame)
+        assert len(np.unique(c8[:, 1:5], axis=0)) == len(c8)      # distinct DX, DY per cell: no two boxes alike
+        assert len(np.unique(cand[:, 5:15], axis=0)) == len(cand)
+    if sc.extra == "all4":
+        cells = sorted(set(gp.tolist()))
+        assert len(cells) == 4 and all(sorted(an[gp == c].tolist()) == [0, 1, 2, 3] for c in cells)      # all four survive decode
+        assert 0 < len(kidx) < len(cidx)
+        for c in cells:
+            rows = {int(a): cand[(gp == c) & (an == a)][0] for a in range(4)}
+            assert iou_f32(rows[0][1:5], rows[2][1:5]) > F32(nms) and iou_f32(rows[1][1:5], rows[3][1:5]) > F32(nms)      # square and tall overlap
+            assert iou_f32(rows[0][1:5], rows[1][1:5]) < F32(nms) and iou_f32(rows[2][1:5], rows[3][1:5]) < F32(nms)
+            if ties:
+                # NMS across the four: the better of each (square, tall) pair stays -- anchors 0 and 3 by score, 0 and 1 by index when tied
+                want = [0, 1] if sc.one_score else [0, 3]
+                assert sorted(kan[kgp == c].tolist()) == want, (c, kan[kgp == c].tolist())
+                if not sc.one_score:
+                    order = [int(a) for a in an[gp == c][np.argsort(-cand[gp == c, 0].astype(np.float64))]]
+                    assert order == [0, 3, 1, 2], order              # the order inside a cell: the foreground biases
+    if sc.extra == "asym":
+        assert set(an.tolist()) == {2, 3} and (st == 8).all()
+        bw, bh = cand[:, 3] - cand[:, 1] + 1, cand[:, 4] - cand[:, 2] + 1
+        # dw = dh = 0: the anchor's own 26 x 40 / 13 x 20 (the centre is no dyadic number any more, so the corners round: 1e-3 px)
+        assert np.abs(bw - np.where(an == 2, 26, 13)).max() < 1e-3 and np.abs(bh - np.where(an == 2, 40, 20)).max() < 1e-3
+        for row, i in zip(kept, kidx):
+            assert swap_moves(row, int(i), hw) > 1.0, (int(i), swap_moves(row, int(i), hw))      # width taken for height moves it by > 1 px
+        assert np.abs(cand[:, 5:10] - cand[:, 10:15]).min() > 1.0  # LMK: every landmark's x differs from its y
+    if sc.extra == "clip4":
+        H, W = hw
+        for a in (2, 3):
+            c = cand[an == a]
+            assert (c[:, 1] == 0).any() and (c[:, 2] == 0).any() and (c[:, 3] == W - 1).any() and (c[:, 4] == H - 1).any(), a
+            assert ((c[:, 1] == 0) & (c[:, 2] == 0) & (c[:, 3] == W - 1) & (c[:, 4] == H - 1)).any(), a      # clipped on all four borders
+            assert (c[:, 3] - c[:, 1] < 0).any() and (c[:, 4] - c[:, 2] < 0).any(), a                        # x2 - x1 < 0 after clipping
+        c = cand[an == 3]
+        assert ((c[:, 1] % 1 == 0.5) & (c[:, 3] % 1 == 0.5)).any()                                         # the fractional anchor, unclipped in x
+        c = cand[(an == 0) | (an == 2)]
+        assert (c[:, 3] < 0).any() and (c[:, 4] < 0).any()          # carried outside left / above: x2, y2 are not clipped there
+        c = cand[(an == 1) | (an == 3)]
+        assert (c[:, 1] > W - 1).any() and (c[:, 2] > H - 1).any()  # carried outside right / below: x1, y1 are not clipped there
+    if sc.extra is None:
+        assert set(an.tolist()) == {0, 1, 2, 3} or len(cidx) < 4
+        assert set(kan.tolist()) == {0, 1, 2, 3} or sc.kept != "all" or len(kidx) < 4
 
 
 def pairs_pick(srt):

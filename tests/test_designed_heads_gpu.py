@@ -9,7 +9,10 @@ restatement; candidate counts equal, kept anchor indices equal in order, scores 
 oracle forward runs here and no tolerance is new.  Each scenario's condition is asserted again on the restatement's result for the
 device's blobs (designed_heads.check), so a frame that missed its regime on the device fails; tie conditions only for fp32.  Engines: fp32
 and fp16 on mnet25's structure; every test checks an eager engine (keep_outputs) and then requires the default engine (graph replay) to
-return byte-identical detections."""
+return byte-identical detections.
+
+The four-anchor scenarios (a4_*, "net3a" engines on widened wire sets, 128 x 160 and 96 x 160) go through the same judge; the restatement
+is given the preset's ratios, nothing else differs."""
 import time
 
 import numpy as np
@@ -42,26 +45,26 @@ def packed(nets, tmp_path):
     return pack
 
 
-def _engine(rfa, model_dir, prec, hw, nms=dh.NMS, eager=False, **kw):
+def _engine(rfa, model_dir, prec, hw, nms=dh.NMS, eager=False, network="net3", **kw):
     if eager:
         kw.update(keep_outputs=True, use_graph=False)
     kw.setdefault("max_batch", 1)
     kw.setdefault("max_detections", 4096)
-    return rfa.RetinaFace(model_dir, "net3", nms, precision=prec, net_hw=hw, model_stem=STEM, plan_cache=False, **kw)
+    return rfa.RetinaFace(model_dir, network, nms, precision=prec, net_hw=hw, model_stem=STEM, plan_cache=False, **kw)
 
 
 def _rows(got):
     return np.stack([d.as_row() for d in got]) if got else np.zeros((0, 15), np.float32)
 
 
-def _restate(det, img, hw, thr, nms):
+def _restate(det, img, hw, thr, nms, ratios=(1.0,)):
     heads9 = [det.get_output(n, img) for s in HEAD_STRIDES for n in head_names(s)]
-    return obuild.decode_nms(heads9, hw[0], hw[1], thr, nms)
+    return obuild.decode_nms(heads9, hw[0], hw[1], thr, nms, ratios=ratios)
 
 
-def _judge(det, hw, got, thr=dh.THR, nms=dh.NMS, img=0, max_det=None):
+def _judge(det, hw, got, thr=dh.THR, nms=dh.NMS, img=0, max_det=None, ratios=(1.0,)):
     """The device's detections of image `img` against the restatement fed the device's own head blobs."""
-    cand, cidx, kept, kidx = _restate(det, img, hw, thr, nms)
+    cand, cidx, kept, kidx = _restate(det, img, hw, thr, nms, ratios)
     assert det.last_candidate_counts(img + 1)[img] == len(cidx)
     want_idx, want = (kidx, kept) if max_det is None else (kidx[:max_det], kept[:max_det])
     assert [d.anchor_index for d in got] == want_idx.tolist()
@@ -86,10 +89,10 @@ def _iou_matrix(a, b):
     return np.where((w <= 0) | (h <= 0), np.float32(0), iou)
 
 
-def _assert_overflow(det, hw, got, true_n, nms=dh.NMS):
+def _assert_overflow(det, hw, got, true_n, nms=dh.NMS, ratios=(1.0,)):
     """More candidates than the cap: which of them won a slot is not deterministic.  What must hold: truncated, the true count, every
     returned row bit-equal to a candidate of the restatement, (score desc, anchor asc) order, and no row suppressing another."""
-    cand, cidx, _, _ = _restate(det, 0, hw, dh.THR, nms)
+    cand, cidx, _, _ = _restate(det, 0, hw, dh.THR, nms, ratios)
     assert det.truncated
     assert len(cidx) == true_n and det.last_candidate_counts(1)[0] == true_n
     assert len(got) > 0
@@ -118,13 +121,16 @@ def _run_rows(rfa, packed, prec, hw, names, after=None, **kw):
 def _run_set(rfa, model_dir, prec, hw, names, after, **kw):
     frames = {n: SC[n].frame() for n in names}
     eager, res = {}, {}
+    assert len({SC[n].na for n in names}) == 1 and all(SC[n].hw == hw for n in names)
+    ratios = dh.ratios_of(SC[names[0]])
+    kw["network"] = dh.network_of(SC[names[0]])
     det = _engine(rfa, model_dir, prec, hw, eager=True, **kw)
     try:
         for n in names:
             t0 = time.perf_counter()
             got = det.detect(frames[n], dh.THR)
             ms = (time.perf_counter() - t0) * 1e3
-            res[n] = _judge(det, hw, got)
+            res[n] = _judge(det, hw, got, ratios=ratios)
             assert not det.truncated, n
             dh.check(SC[n], *res[n], ties=prec == FP32)
             eager[n] = _key([got])
@@ -287,3 +293,77 @@ def test_mixed_regimes_in_one_launch(rfa, packed, prec):
         assert _key(det.detectBatchImages(frames, dh.THR)) == want
     finally:
         det.close()
+
+
+# ------------------------------------------------------------------------------------------------------------ four anchors per cell
+SIZES4 = dh.SIZES4
+A4_ROWS = [f"a4_alone{a}" for a in range(4)] + ["a4_all", "a4_alltied", "a4_asym", "a4_clip", "a4_count300"]
+
+
+def _a4(name, hw):
+    return f"{name}_{dh.tag4(hw)}"
+
+
+@pytest.mark.parametrize("hw", SIZES4, ids=dh.tag4)
+@pytest.mark.parametrize("prec", PRECS)
+def test_four_anchor_head_on_designed_outputs(rfa, packed, prec, hw):
+    """head_kernel<T, 4> and decode_anchor on the non-square anchors of "net3a": each anchor's gate alone on all three strides (every index
+    is anchor_offset + a * hw + gp of the open anchor, with distinct dx, dy per cell); all four anchors of a cell with distinct scores and
+    tied (the square and the tall box of a cell overlap: NMS across the four); dx != dy on the 26 x 40 and 13 x 20 anchors, where taking
+    the width for the height moves a box by more than 1 px; clipping on all four borders with x2 - x1 < 0; 300 candidates (the bitonic
+    path).  128 x 160 fills the blocks of 64 pixels of the stride-8 map exactly; at 96 x 160 the last block of every level is partial."""
+    res = _run_rows(rfa, packed, prec, hw, [_a4(n, hw) for n in A4_ROWS])
+    for a in range(4):
+        cidx = res[_a4(f"a4_alone{a}", hw)][1]
+        assert sorted(cidx.tolist()) == SC[_a4(f"a4_alone{a}", hw)].expect()
+
+
+@pytest.mark.parametrize("hw", SIZES4, ids=dh.tag4)
+@pytest.mark.parametrize("prec", PRECS)
+def test_four_anchor_max_detections_bound(rfa, packed, prec, hw):
+    """test_max_detections_bound at A = 4: eight survivors (two of each anchor) fill max_detections = 8, nine report `truncated`."""
+    model = packed("std4")
+    names = [_a4(n, hw) for n in ("a4_kept8", "a4_kept9")]
+    frames = {n: SC[n].frame() for n in names}
+    want = {}
+    for eager in (True, False):
+        det = _engine(rfa, model, prec, hw, eager=eager, network="net3a", max_detections=8)
+        try:
+            for n, over in ((names[0], False), (names[1], True), (names[0], False)):
+                got = det.detect(frames[n], dh.THR)
+                assert det.truncated == over and len(got) == 8, (n, det.truncated, len(got))
+                if eager:
+                    res = _judge(det, hw, got, max_det=8, ratios=dh.RATIOS4)
+                    dh.check(SC[n], *res, ties=prec == FP32)
+                    want[n] = _key([got])
+                else:
+                    assert _key([got]) == want[n]
+        finally:
+            det.close()
+
+
+@pytest.mark.parametrize("hw", SIZES4, ids=dh.tag4)
+@pytest.mark.parametrize("prec", PRECS)
+def test_four_anchor_candidate_cap_bound(rfa, packed, prec, hw):
+    """test_candidate_cap_bound at A = 4: 64 candidates (sixteen cells, all four anchors) fill max_candidates = 64 exactly, 65 overflow it,
+    then 64 again."""
+    model = packed("std4")
+    n64, n65 = _a4("a4_count64", hw), _a4("a4_count65", hw)
+    frames = {n: SC[n].frame() for n in (n64, n65)}
+    want = None
+    for eager in (True, False):
+        det = _engine(rfa, model, prec, hw, eager=True, network="net3a", max_candidates=64) if eager else \
+            _engine(rfa, model, prec, hw, keep_outputs=True, network="net3a", max_candidates=64)
+        try:
+            for n in (n64, n65, n64):
+                got = det.detect(frames[n], dh.THR)
+                if n == n65:
+                    _assert_overflow(det, hw, got, 65, ratios=dh.RATIOS4)
+                    continue
+                assert not det.truncated
+                res = _judge(det, hw, got, ratios=dh.RATIOS4)
+                dh.check(SC[n], *res, ties=prec == FP32)
+                want = want or _key([got])
+                assert _key([got]) == want
+        finally:
+            det.close()

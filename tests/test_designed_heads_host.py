@@ -2,7 +2,9 @@
 condition the GPU tests (tests/test_designed_heads_gpu.py) rely on -- candidate counts on the regime boundaries, exact ties, lane 63,
 decode's edges -- by the reference restatements alone.  The numpy restatement (OracleDetector.detect) and the plain-C one
 (oracle.build.decode_nms) must agree on candidates, kept anchors and order, ties included; the reference build's own postProcess
-(oracle/build_ref.py) is compared bit for bit where it is present and the scenario's scores are distinct."""
+(oracle/build_ref.py) is compared bit for bit where it is present and the scenario's scores are distinct.  The four-anchor scenarios
+(a4_*) go the same way with the ratios of "net3a": the C restatement takes them as an argument, and the reference build is created
+with network "net3a"."""
 import numpy as np
 import pytest
 
@@ -22,7 +24,7 @@ WIRE_REL = 1.65e-4 + 30 * 6e-8
 @pytest.fixture(scope="module")
 def wired(nets):
     from oracle.pipeline import OracleDetector
-    return {k: OracleDetector(dh.wire_net(nets["mnet25"], k)) for k in dh.HEAD_SETS}
+    return {k: OracleDetector(dh.wire_net(nets["mnet25"], k)) for k in list(dh.HEAD_SETS) + list(dh.HEAD_SETS4)}
 
 
 @pytest.mark.parametrize("stem", STEMS)
@@ -61,30 +63,76 @@ def test_scenario_reaches_its_condition_on_the_oracle(wired, name):
     The numpy restatement gives the same candidates in the same order and keeps the same anchors in the same order, bit for bit.  Where
     the reference build is present and no two candidates tie (its std::sort leaves the order of equal scores open) its postProcess returns
     the same rows."""
+    from oracle import retinaface_post as post
     from oracle.pipeline import OracleDetector
     sc = dh.SCENARIOS[name]
     od = wired[sc.heads]
     h9 = _oracle_heads(od, sc)
-    cand, cidx, kept, kidx = obuild.decode_nms(h9, sc.hw[0], sc.hw[1], dh.THR, dh.NMS)
+    ratios = dh.ratios_of(sc)
+    assert h9[0].shape[0] == 2 * sc.na and len(ratios) * 2 == sc.na
+    cand, cidx, kept, kidx = obuild.decode_nms(h9, sc.hw[0], sc.hw[1], dh.THR, dh.NMS, ratios=ratios)
     dh.check(sc, cand, cidx, kept, kidx)
     assert isinstance(od, OracleDetector)
-    ref = od.detect(sc.frame(), dh.THR, dh.NMS, net_hw=sc.hw)
-    assert [d.anchor_index for d in ref.candidates] == cidx.tolist()
-    assert ref.anchor_indices().tolist() == kidx.tolist()
-    assert np.array_equal(ref.rows(), kept)
-    crow = np.stack([d.as_row() for d in ref.candidates]) if ref.candidates else np.zeros((0, 15), np.float32)
-    assert np.array_equal(crow, cand)
+    names = [n for s in HEAD_STRIDES for n in head_names(s)]
+    cands = post.decode({n: a[None] for n, a in zip(names, h9)}, sc.hw[0], sc.hw[1], dh.THR, ratios=ratios)
+    dets = post.nms(list(cands), dh.NMS)
+    assert [d.anchor_index for d in cands] == cidx.tolist()
+    assert [d.anchor_index for d in dets] == kidx.tolist()
+    rows = lambda ds: np.stack([d.as_row() for d in ds]) if ds else np.zeros((0, 15), np.float32)
+    assert np.array_equal(rows(dets), kept)
+    assert np.array_equal(rows(cands), cand)
+    if sc.na == 2:                                                             # and the detector call itself, which decodes "net3"
+        ref = od.detect(sc.frame(), dh.THR, dh.NMS, net_hw=sc.hw)
+        assert ref.anchor_indices().tolist() == kidx.tolist() and np.array_equal(ref.rows(), kept)
     print(f"designed heads (oracle) {name}: {len(cidx)} candidates, {len(kidx)} kept, {len(np.unique(cand[:, 0]))} distinct scores")
     if build_ref.available() and sc.max_tie <= REF_MAX_TIE:
-        r = build_ref.ReferenceRetinaFace(sc.hw[0], sc.hw[1])
+        r = build_ref.ReferenceRetinaFace(sc.hw[0], sc.hw[1], network=dh.network_of(sc), head_anchors=sc.na)
         try:
             r.set_heads(0, h9)
-            assert np.array_equal(r.postprocess(0, dh.THR), kept)
+            assert np.array_equal(r.postprocess(0, dh.THR), kept)             # all 15 floats of every face, in order
         finally:
             r.close()
 
 
 REF_MAX_TIE = 16
+
+
+def test_the_four_anchor_scenarios_are_compared_with_the_reference_build():
+    """Every a4_* scenario stays within REF_MAX_TIE, so none is left out of the comparison above where the reference build is present."""
+    assert dh.SCENARIOS4 and all(dh.SCENARIOS[n].max_tie <= REF_MAX_TIE and dh.SCENARIOS[n].na == 4 for n in dh.SCENARIOS4)
+
+
+@pytest.mark.parametrize("hw", dh.SIZES4, ids=dh.tag4)
+def test_swapping_width_and_height_moves_the_asymmetric_boxes(wired, hw):
+    """`a4_asym`: bbox_pred restated with `width` and `height` exchanged in the centre terms moves every kept box by more than 1 px -- four
+    orders of magnitude beyond the 1e-4 px of the GPU judge -- and landmark_pred with `height` replaced by `width` moves every kept
+    landmark y by more than 1 px.  dh.swap_moves, which the GPU test applies to the device's rows, predicts the box figure."""
+    from oracle import retinaface_post as post
+    sc = dh.SCENARIOS[f"a4_asym_{dh.tag4(hw)}"]
+    h9 = _oracle_heads(wired[sc.heads], sc)
+    cand, cidx, kept, kidx = obuild.decode_nms(h9, hw[0], hw[1], dh.THR, dh.NMS, ratios=dh.RATIOS4)
+    assert len(kidx) == 12
+    base = post.base_anchors(dh.RATIOS4)[8]
+    st, an, gp = dh.anchor_numbers(kidx, hw, 4)
+    w8 = hw[1] // 8
+    for row, i, a, g in zip(kept, kidx, an, gp):
+        anchor = base[a] + np.array([8 * (g % w8), 8 * (g // w8)] * 2, np.float32)
+        reg = [h9[7][a * 4 + c].reshape(-1)[g] for c in range(4)]
+        pts = [h9[8][a * 10 + c].reshape(-1)[g] for c in range(10)]
+        good = np.array(post.clip_box(post.bbox_pred(anchor, reg), hw[1], hw[0]))
+        assert np.array_equal(good, row[1:5])
+        x1, y1, x2, y2 = anchor
+        turned = np.array([x1, y1, x1 + (y2 - y1), y1 + (x2 - x1)], np.float32)      # the anchor with width and height exchanged ...
+        bad = np.array(post.bbox_pred(turned, reg))
+        ctr = lambda b: np.array([b[0] + b[2], b[1] + b[3]]) / 2
+        shift = ctr(turned) - ctr(anchor)                                           # ... recentred: what is left is dx * height, dy * width
+        moved = np.abs(ctr(bad) - shift - ctr(good)).max()
+        assert moved > 1.0 and abs(moved - dh.swap_moves(row, int(i), hw)) < 1e-2, moved
+        ys = np.array(post.landmark_pred(anchor, pts)[1])
+        assert np.array_equal(ys, row[10:15])
+        width, height = x2 - x1 + 1, y2 - y1 + 1
+        ys_bad = np.array([np.float32(pts[2 * k + 1]) * width + (y1 + 0.5 * (height - 1)) for k in range(5)])
+        assert np.abs(ys_bad - ys)[[0, 1, 3, 4]].min() > 1.0                         # (landmark 2 has offset 0 in y)
 
 
 def test_pairs_iou_is_a_threshold_that_decides(wired):

@@ -393,10 +393,10 @@ def _int8_start_blob(det):
     raise AssertionError("the int8 engine exposes neither relu2 nor relu4")
 
 
-def _assert_int8_image_bit_exact(det, q, img, hw, thr, got):
+def _assert_int8_image_bit_exact(det, q, img, hw, thr, got, ratios=(1.0,)):
     """One image of the engine's last batch against oracle/int8_forward.py continued from the engine's own front-end output:
     every int8 activation np.array_equal, raw head outputs np.array_equal, probabilities within 1e-6 (device expf), candidates
-    and detections identical (anchors; scores 1e-6; coordinates 1e-4 px)."""
+    and detections identical (anchors; scores 1e-6; coordinates 1e-4 px).  `ratios`: the anchor ratios of the engine's preset."""
     start = _int8_start_blob(det)
     x = det.debug_activation(start + "#raw", img)
     assert np.array_equal(x, np.rint(x)) and x.min() >= 0 and x.max() <= 127
@@ -418,7 +418,7 @@ def _assert_int8_image_bit_exact(det, q, img, hw, thr, got):
         assert np.array_equal(det.get_output(bn, img), heads[bn]) and np.array_equal(det.get_output(ln, img), heads[ln]), s
         assert np.abs(det.get_output(pn, img) - heads[pn]).max() <= 1e-6
     h9 = [heads[n] for s in HEAD_STRIDES for n in head_names(s)]
-    cand, cidx, kept, kidx = obuild.decode_nms(h9, hw[0], hw[1], thr, 0.4)
+    cand, cidx, kept, kidx = obuild.decode_nms(h9, hw[0], hw[1], thr, 0.4, ratios=ratios)
     border = sum(int((np.abs(heads[head_names(s)[0]] - thr) <= 2e-6).sum()) for s in HEAD_STRIDES)
     assert abs(det.last_candidate_counts(img + 1)[img] - len(cidx)) <= border
     if border == 0:

@@ -9,6 +9,7 @@ tensor to the bytes judged here, and test_gpu_parity.py's batch-composition test
 stride-32 map), 96 x 160 (odd tile counts, 3 x 5), 352 x 608 (mnet25: the odd-partial-tile size, and the only size here whose stride-8
 map is large enough for the fp16 engine's warp-specialised rf_c1_aggr instance; mnet-deconv-0517 runs that one launch there).
 After each eager engine is judged, the default engine (graph replay) must return byte-identical detections on the same frames.
+The four-anchor head launches ("net3a" engines on the widened models of tests/net3a_models.py) are judged the same way at the two small sizes.
 """
 import os
 
@@ -16,7 +17,8 @@ import numpy as np
 import pytest
 
 import launch_ref as lr
-from conftest import ASSETS
+import net3a_models as nm
+from conftest import ASSETS, STEMS
 
 pytestmark = pytest.mark.gpu
 
@@ -37,7 +39,9 @@ def rfa(built_lib):
 @pytest.fixture(scope="module")
 def model_dirs(nets, tmp_path_factory):
     """weight set -> model directory (shipped: the assets; derived: written at run time, nothing is stored)"""
-    return lr.weight_set_dirs(nets, ASSETS, lambda name: str(tmp_path_factory.mktemp(name)))
+    dirs = lr.weight_set_dirs(nets, ASSETS, lambda name: str(tmp_path_factory.mktemp(name)))
+    dirs["net3a"] = nm.write_model_dir(nets, str(tmp_path_factory.mktemp("net3a")))
+    return dirs
 
 
 _consts = {}
@@ -70,11 +74,13 @@ def _device_blobs(det, launches, frames):
     return blobs
 
 
-def _judge_engine(rfa, built_lib, model_dir, ws, stem, prec, hw, base_frame, only=None):
+def _judge_engine(rfa, built_lib, model_dir, ws, stem, prec, hw, base_frame, only=None, network="net3", replay=None):
+    """`network`: the preset the engines are created with (the model must carry its anchors); `replay`: compare the default engine's
+    detections too (default: where every launch was judged)."""
     frames = lr.case_frames(base_frame, hw)
     k = consts(built_lib, model_dir, stem, prec)
     launches = [L for L in lr.launches(prec) if only is None or L.name in only]
-    det = rfa.RetinaFace(model_dir, "net3", 0.4, precision=prec, net_hw=hw, model_stem=stem, keep_outputs=True, use_graph=False,
+    det = rfa.RetinaFace(model_dir, network, 0.4, precision=prec, net_hw=hw, model_stem=stem, keep_outputs=True, use_graph=False,
                          plan_cache=False, max_batch=8)
     try:
         eager = det.detectBatchImages(frames, 0.5)
@@ -92,13 +98,14 @@ def _judge_engine(rfa, built_lib, model_dir, ws, stem, prec, hw, base_frame, onl
             if not v.ok:
                 failures.append(v.message())
     assert not failures, "\n".join(failures[:8])
-    if only is None:
+    if only is None if replay is None else replay:
         # the default engine (graph replay) must return the eager engine's detections byte for byte
-        det = rfa.RetinaFace(model_dir, "net3", 0.4, precision=prec, net_hw=hw, model_stem=stem, plan_cache=False, max_batch=8)
+        det = rfa.RetinaFace(model_dir, network, 0.4, precision=prec, net_hw=hw, model_stem=stem, plan_cache=False, max_batch=8)
         try:
             assert _key(det.detectBatchImages(frames, 0.5)) == _key(eager)
         finally:
             det.close()
+    return blobs
 
 
 SHIPPED = lr.SHIPPED_CASES
@@ -114,6 +121,23 @@ def test_warp_specialised_aggregation_instance_on_the_other_model(rfa, built_lib
     """kernels.hip conv3_select: fp16 maps of >= 48 x 48 pixels with even sides run rf_c1_aggr on conv3x3_up_dma_kernel, which no small size
     reaches.  mnet25 covers it at 352 x 608; mnet-deconv-0517 runs that launch alone there."""
     _judge_engine(rfa, built_lib, model_dirs["shipped"], "shipped", "mnet-deconv-0517", FP16, BIG, base_frame, only=("aggr1",))
+
+
+NET3A = [(stem, hw) for stem in STEMS for hw in SMALL]
+
+
+@pytest.mark.parametrize("prec", [FP32, FP16], ids=["fp32", "fp16"])
+@pytest.mark.parametrize("stem,hw", NET3A, ids=[f"{s}-{h}x{w}" for s, (h, w) in NET3A])
+def test_four_anchor_head_launches_inside_their_intervals(rfa, built_lib, model_dirs, base_frame, stem, hw, prec):
+    """head_kernel<T, 4> (64 output channels, one wave per 16 of them, all 256 threads in the softmax; the fp16 hi + lo head weights over
+    64 rows): head0, head1 and head2 of "net3a" engines on the widened shipped weights, three frames per call, every element inside its
+    interval.  Every anchor number has a candidate at 0.5 and at 0.02 among the judged frames."""
+    blobs = _judge_engine(rfa, built_lib, model_dirs["net3a"], "net3a", stem, prec, hw, base_frame, only=("head0", "head1", "head2"),
+                          network="net3a", replay=True)
+    probs = [blobs[lr.head_names(s)[0]] for s in lr.STRIDES]
+    assert probs[0].shape[1] == 8
+    for thr in (0.5, 0.02):
+        assert nm.anchors_with_candidates(probs, thr) == {0, 1, 2, 3}, thr
 
 
 DERIVED = lr.DERIVED_CASES

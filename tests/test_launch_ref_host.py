@@ -6,12 +6,15 @@
     reversed, pairwise inside blocks of the MFMA K step) and the storage roundings at the model's points lies inside every interval, on
     every frame, model and weight set the GPU test runs -- the inputs chosen keep the reference itself inside the bar;
   * the judge REJECTS mutants of that emulation, each on the launch it is named for;
-  * the derived weight sets meet their conditions.
+  * the derived weight sets meet their conditions;
+  * the four-anchor heads ("net3a", the widened models of tests/net3a_models.py) are judged by the same function: their emulation is
+    accepted, and rejected with two channels of anchor 2 exchanged.
 """
 import numpy as np
 import pytest
 
 import launch_ref as lr
+import net3a_models as nm
 from conftest import ASSETS, STEMS
 
 FP32, FP16 = lr.FP32, lr.FP16
@@ -21,7 +24,9 @@ ORDERS = ("natural", "reversed", "blocked")
 
 @pytest.fixture(scope="module")
 def model_dirs(nets, tmp_path_factory):
-    return lr.weight_set_dirs(nets, ASSETS, lambda name: str(tmp_path_factory.mktemp(name)))
+    dirs = lr.weight_set_dirs(nets, ASSETS, lambda name: str(tmp_path_factory.mktemp(name)))
+    dirs["net3a"] = nm.write_model_dir(nets, str(tmp_path_factory.mktemp("net3a")))
+    return dirs
 
 
 _consts = {}
@@ -269,3 +274,40 @@ def test_degenerate_reaches_the_float_models_cold_branches(built_lib, nets, mode
     assert all(np.isfinite(v).all() for v in blobs.values())
     hot = blobs[lr.relu_blob(12)][..., ed["mobilenet0_conv12_fwd:beta"]]
     assert hot.min() > 5e3 and hot.max() < 6e4
+
+
+# ------------------------------------------------------------------------------------------------ four anchors per cell
+HEADS = ("head0", "head1", "head2")
+NET3A_CASES = [(s, hw) for s in STEMS for hw in lr.SMALL_SIZES]
+
+
+@pytest.mark.parametrize("prec", [FP32, FP16], ids=["fp32", "fp16"])
+@pytest.mark.parametrize("stem,hw", NET3A_CASES, ids=[f"{s}-{h}x{w}" for s, (h, w) in NET3A_CASES])
+def test_the_judge_accepts_the_emulated_four_anchor_heads(built_lib, model_dirs, base_frame, stem, hw, prec):
+    """The widened models: 64 head channels per stride (K = 65, fp16: the hi + lo pair, K = 129), softmax over (a, A + a) with A = 4.  The
+    emulation's head launches lie inside their intervals in all three summation orders, on the frames and sizes the GPU test judges;
+    every anchor number has a probability above 0.5 and above 0.02 somewhere, so the intervals of all four softmax pairs are judged on
+    both sides of the thresholds."""
+    k = consts(built_lib, model_dirs["net3a"], stem, prec)
+    assert k.anchors == 4 and k.ops["ssh0.head"].w.shape[0] == 64 and k.ops["ssh0.head"].K == (129 if prec == FP16 else 65)
+    frames = lr.case_frames(base_frame, hw)
+    for order in ORDERS:
+        blobs = lr.emulate(k, frames, order)
+        verdicts = _judge_all(k, blobs, only=HEADS)
+        assert len(verdicts) == 9 and all(v.ok for v in verdicts), (order, [v.message() for v in verdicts if not v.ok][:4])
+        probs = [blobs[lr.head_names(s)[0]] for s in lr.STRIDES]
+        assert probs[0].shape[1] == 8
+        for thr in (0.5, 0.02):
+            assert nm.anchors_with_candidates(probs, thr) == {0, 1, 2, 3}, (order, thr)
+
+
+@pytest.mark.parametrize("prec", [FP32, FP16], ids=["fp32", "fp16"])
+@pytest.mark.parametrize("c,blob", [(8 + 2 * 4, "bbox_pred"), (24 + 2 * 10 + 1, "landmark_pred"), (4 + 2, "cls_prob")])
+def test_the_judge_rejects_exchanged_channels_of_anchor_2(built_lib, model_dirs, base_frame, prec, c, blob):
+    """Head channels c and c + 1 of the stride-8 head exchanged in the emulation (dx / dy of anchor 2; y0 / x1 of its landmarks; the
+    foreground logits of anchors 2 and 3): head2 rejects it on the blob named, head0 and head1 stay inside."""
+    k = consts(built_lib, model_dirs["net3a"], "mnet25", prec)
+    blobs = lr.emulate(k, lr.case_frames(base_frame, (64, 96)), "blocked", lr.Mutant("swap_channels", "ssh2.head", (c,)))
+    assert all(v.ok for v in _judge_all(k, blobs, only=("head0", "head1")))
+    failed = [v for v in _judge_all(k, blobs, only=("head2",)) if not v.ok]
+    assert failed and all(blob in v.blob for v in failed), [v.message() for v in failed]
