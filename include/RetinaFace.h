@@ -126,6 +126,16 @@ public:
     const vector<vector<int>> &dewarpVotes() const { return dewarpVotes_; }
     const vector<vector<int>> &dewarpViews() const { return dewarpSrc_; }
 
+    /* additive: region detection (rf_detect_roi_batch): every frame is detected only in its regions (rois[i]: frame i's, at most 256),
+       which are packed several to a net-sized view on the device; the faces are moved back and merged.  Fills lastBatchResult() with
+       the merged faces in SOURCE-FRAME pixels (at most spec->max_faces per frame; nullptr: the defaults); roiVotes() holds, per frame,
+       how many candidates each face merged, roiRegions() the region it came from.  roisFromFaces() turns a frame's faces into the
+       regions of the next call (rf_roi_from_faces; margin_q8 0: a quarter of the longer side). */
+    void detectRois(const vector<cv::Mat> &imgs, const vector<vector<rf_roi>> &rois, float threshold = 0.5, const rf_roi_spec *spec = nullptr);
+    const vector<vector<int>> &roiVotes() const { return roiVotes_; }
+    const vector<vector<int>> &roiRegions() const { return roiSrc_; }
+    static vector<rf_roi> roisFromFaces(const vector<FaceDetectInfo> &faces, float coordScale = 1.f, int margin_q8 = 0);
+
     /* additive: low-light detection (rf_detect_enhanced_batch): every frame is enhanced on the device (tile-adaptive contrast boost of
        dark tiles, rf_enhance_spec) and detected; the frames themselves are not written.  Fills lastBatchResult() with what the plain
        batch call returns for the enhanced frames; tilesEnhanced() holds, per frame, the number of tiles the enhancement touched
@@ -230,6 +240,7 @@ private:
     vector<vector<int>> pyrVotes_, pyrPasses_;
     vector<vector<int>> rotVotes_, rotSrc_;
     vector<vector<int>> dewarpVotes_, dewarpSrc_;
+    vector<vector<int>> roiVotes_, roiSrc_;
     vector<int> tilesEnhanced_;
     vector<int> frameRot_;
     vector<float> rotScore_;

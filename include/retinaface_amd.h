@@ -1164,6 +1164,104 @@ int rf_detect_dewarp_batch(rf_dewarper dewarper, const uint8_t *const *bgr, cons
 int rf_dewarp_merge_device(rf_dewarper dewarper, int n, const rf_dewarp_spec *spec, const rf_face *faces, const int *pass_counts,
                            rf_face *out, int cap_per_image, int *counts, int *votes, int *src_view);
 
+/* ---- Region detection: run the detector only where told to.  The caller names up to 256 REGIONS of every frame (the last key frame's
+ * faces grown by a margin, a person detector's boxes, a motion mask); a region call packs them, several to a net-sized VIEW, on the
+ * device, detects the views, moves the faces back into the frame and merges them on the device with the merge of the TTA call: true
+ * boxes, landmarks and scores for a fraction of the tiled call's passes (DESIGN.md "Region detection" holds the definition;
+ * tests/roi_ref.py restates it in numpy; every result is byte-exact against it):
+ *   region   rf_roi {x, y, w, h}, int32 source pixels: w, h in [1, 16384], |x|, |y| <= 2^20.  It may reach outside the frame or lie
+ *            wholly outside it.  Each frame has its own list; the lists of a call are concatenated frame-major in `rois`,
+ *            roi_counts[i] (0..256) entries for frame i.
+ *   grid     a view of net_w x net_h is cut into grid x grid cells (grid 1, 2 or 4) of cw = net_w / grid by ch = net_h / grid pixels;
+ *            net_w and net_h must divide evenly and cw must be a multiple of 4.  Region r of a frame goes to cell r mod grid^2
+ *            (row-major) of pass r / grid^2.  A frame without regions has no pass and no faces; unused cells of the last pass are 0.
+ *   step     each region is shown at one of five levels, x4, x2, x1, x1/2, x1/4 (rf_roi_cell.level = 2, 1, 0, -1, -2): the largest not
+ *            above max_zoom with w z <= cw and h z <= ch.  None fits: x1/4, the cell shows the region's centre, flags = RF_ROI_CROPPED.
+ *   level    x2 / x4: the pyramid call's zoom (half-pixel centres, clamped at the frame border); x1: the frame; x1/2, x1/4: the rounded
+ *            box mean (sum + k^2 / 2) / k^2 of the k x k source block, source coordinates clamped into the frame, a level image of
+ *            ceil(cols / k) x ceil(rows / k) pixels.
+ *   cell     c2 = 2 x + w (twice the centre); the cell's origin in level pixels is x0 = floor((c2 z - cw) / 2) for z >= 1 and
+ *            x0 = floor((c2 - k cw) / (2 k)) for a shrink by k; y0 likewise.  Cell pixel (i, j) is level pixel (x0 + i, y0 + j); a level
+ *            pixel outside the level image is 0.  The cell is filled with the real pixels around the region, not with padding.
+ *   faces    on the 15 floats of a face of a view.  Its cell is the one its box centre (x1 + x2) * 0.5f, (y1 + y2) * 0.5f lies in; a
+ *            cell without a region drops it.  Every coordinate gets one fp32 add of the integer x0 - cell_x (y0 - cell_y), then for a
+ *            zoom * (1 / z) - (z - 1) / 2z, for a shrink * k + (k - 1) / 2.  The face is kept only when its mapped centre lies in
+ *            [x, x + w) x [y, y + h): a neighbour that shows up in a cell's context is its own region's business.  Scores are untouched.
+ *   merge    rf_tta_spec's merge over the kept faces of a frame, g = region * max_detections + j; src_roi = g / max_detections.
+ *            vote: 0 / 2 = off (the default), 1 = on.  max_faces, outputs and caps (RF_ERR_TRUNCATED) as for the TTA call. */
+#define RF_ROI_MAX_REGIONS 256
+#define RF_ROI_CROPPED 1
+typedef struct rf_roi {
+    int32_t x, y, w, h;
+} rf_roi;
+typedef struct rf_roi_cell {
+    rf_roi roi;
+    int32_t level;          /* log2 of the step: 2, 1, 0, -1, -2 */
+    int32_t x0, y0;         /* the cell's origin in level pixels */
+    int32_t flags;          /* RF_ROI_CROPPED */
+} rf_roi_cell;
+typedef struct rf_roi_spec {
+    uint32_t struct_size;   /* sizeof(rf_roi_spec) */
+    int32_t grid;           /* 1, 2 or 4; 0 = 4 */
+    int32_t max_zoom;       /* 1, 2 or 4; 0 = 2 */
+    int32_t vote;           /* 0 / 2 = off; 1 = kept boxes become the score-weighted mean of their cluster */
+    int32_t max_faces;      /* merged faces kept per frame on the device, 1..4096; 0 = the engine's max_detections */
+    int32_t reserved;       /* 0 */
+} rf_roi_spec;
+
+/* Host only, no GPU, no handle -- the same code the kernels run, compiled for the host.  Only grid and max_zoom of spec are read where
+ * no merge happens; spec may be NULL.  view_w x view_h is the view's size (the net's in a region call).
+ * rf_roi_plan: the cells of n regions (0..256) into cells[n]; *passes (may be NULL) receives ceil(n / grid^2).
+ * rf_roi_from_faces: the regions of n faces: each box times coord_scale, grown on every side by margin_q8 / 256 of its longer side
+ * (0 = 64, a quarter), lower edges floored, upper edges ceiled, sides held to [1, 16384].  Faces whose box is not finite, is empty or
+ * lies beyond +-2^20 are skipped.  Returns the number of regions written to rois (at most n), so that one call's result can be handed
+ * to the next call.
+ * rf_roi_atlas_host: all passes of the regions of the rows x cols BGR frame src (row pitch step): pass p is written as view_w * 3 bytes
+ * per row at dst + (p * view_h + y) * dst_step (bytes beyond a row are untouched).
+ * rf_roi_map_face: the face rule for one face of pass `pass` of the n regions.  Returns 1 (kept, out written, *region (may be NULL) its
+ * region; out may equal in), 0 (dropped) or RF_ERR_INVALID_ARG.
+ * rf_roi_merge_host: mapping and merge of ONE frame: pass p holds pass_counts[p] faces (clamped to max_detections) at
+ * faces[p * max_detections + j].  *count is the true number of heads; out / votes / src_roi (the last two may be NULL) receive the
+ * first min(*count, cap, max_faces).  Returns RF_OK, RF_ERR_TRUNCATED (a pass count above max_detections, or a cut list) or
+ * RF_ERR_INVALID_ARG. */
+int rf_roi_plan(const rf_roi_spec *spec, int view_w, int view_h, const rf_roi *rois, int n, rf_roi_cell *cells, int *passes);
+int rf_roi_from_faces(const rf_face *faces, int n, float coord_scale, int margin_q8, rf_roi *rois);
+int rf_roi_atlas_host(const rf_roi_spec *spec, int view_w, int view_h, const uint8_t *src, int rows, int cols, int step, const rf_roi *rois,
+                      int n, uint8_t *dst, int dst_step);
+int rf_roi_map_face(const rf_roi_spec *spec, int view_w, int view_h, const rf_roi *rois, int n, int pass, const rf_face *in, rf_face *out,
+                    int *region);
+int rf_roi_merge_host(const rf_roi_spec *spec, int view_w, int view_h, const rf_roi *rois, int n, float nms_threshold, int max_detections,
+                      const rf_face *faces, const int *pass_counts, rf_face *out, int cap, int *count, int *votes, int *src_roi);
+
+/* The atlas kernel on its own: all passes of the n regions of a frame in device memory (any source pitch and pointer alignment) into a
+ * destination in device memory laid out as rf_roi_atlas_host's, at any view size that meets the cell rule.  Synchronous.  Multi-device
+ * handles return RF_ERR_UNSUPPORTED from this call and the next three. */
+int rf_roi_atlas_device(rf_handle h, const void *d_src, int rows, int cols, int step, const rf_roi *rois, int n, const rf_roi_spec *spec,
+                        int view_w, int view_h, void *d_dst, int dst_step);
+
+/* Region detection of frames resident on the engine's device (a NULL pointer or 0 x 0: an empty frame, which finds nothing; steps may be
+ * NULL: dense).  The views of all frames are made by one kernel on the device in front of the call's first detection launch and go
+ * through the engine's ordinary launches; a gather kernel behind each launch applies the face rule, and one merge launch behind the
+ * call's last launch waits for them on the device -- no host synchronisation in between.  Everything is checked before any state
+ * changes: a bad spec, a net that does not meet the cell rule, a region out of range, a count outside 0..256 are RF_ERR_INVALID_ARG.
+ * votes and src_roi (indexed like out) may be NULL.  d_views, when not NULL, is device memory of P * net_h * net_w * 3 bytes, P the
+ * call's passes (frame-major, ascending region; sum of ceil(roi_counts[i] / grid^2)), that receives the views as dense frames (a NULL
+ * frame's are left untouched).  rf_last_anchor_indices / rf_last_candidate_counts afterwards describe the call's PASSES. */
+int rf_detect_roi_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                               const rf_roi *rois, const int *roi_counts, float threshold, const rf_roi_spec *spec, rf_face *out,
+                               int cap_per_image, int *counts, int *votes, int *src_roi, void *d_views);
+
+/* The same with frames in HOST memory (rf_detect_batch's convention): each frame is uploaded once, densely. */
+int rf_detect_roi_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n, const rf_roi *rois,
+                        const int *roi_counts, float threshold, const rf_roi_spec *spec, rf_face *out, int cap_per_image, int *counts,
+                        int *votes, int *src_roi);
+
+/* Face rule and merge of per-pass faces the CALLER supplies (host memory): the call's passes in the order above, pass q holds
+ * pass_counts[q] faces (clamped to max_detections) at faces[q * max_detections + j].  No forward pass runs. */
+int rf_roi_merge_device(rf_handle h, const int *rows, const int *cols, int n, const rf_roi *rois, const int *roi_counts,
+                        const rf_roi_spec *spec, const rf_face *faces, const int *pass_counts, rf_face *out, int cap_per_image, int *counts,
+                        int *votes, int *src_roi);
+
 /* ---- Zoom-pyramid detection: the smallest anchors are 16 px, so faces below about 16 px are not seen in a frame that already fits the
  * net.  A pyramid call detects every frame at 1x (the passes of its tile plan) and as net-sized tiles of the frame ENLARGED 2x and / or 4x
  * on the device, moves the faces of all passes back into the frame and merges them with the voting merge of the TTA call (DESIGN.md

@@ -139,6 +139,22 @@ class rf_dewarp_spec(C.Structure):
 RF_LENS_EQUIDISTANT, RF_LENS_EQUISOLID, RF_LENS_STEREOGRAPHIC, RF_LENS_ORTHOGRAPHIC = 0, 1, 2, 3
 
 
+class rf_roi(C.Structure):
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32)]
+
+
+class rf_roi_cell(C.Structure):
+    _fields_ = [("roi", rf_roi), ("level", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("flags", C.c_int32)]
+
+
+class rf_roi_spec(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("grid", C.c_int32), ("max_zoom", C.c_int32), ("vote", C.c_int32), ("max_faces", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+RF_ROI_MAX_REGIONS, RF_ROI_CROPPED = 256, 1
+
+
 class rf_enhance_spec(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("tile", C.c_int32), ("clip", C.c_int32), ("dark_below", C.c_int32)]
 
@@ -360,6 +376,22 @@ SYMBOLS = {
                                          _PP(rf_dewarp_spec), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int)]),
     "rf_dewarp_merge_device": (C.c_int, [C.c_void_p, C.c_int, _PP(rf_dewarp_spec), _PP(rf_face), _PP(C.c_int), _PP(rf_face), C.c_int,
                                          _PP(C.c_int), _PP(C.c_int), _PP(C.c_int)]),
+    "rf_roi_plan": (C.c_int, [_PP(rf_roi_spec), C.c_int, C.c_int, _PP(rf_roi), C.c_int, _PP(rf_roi_cell), _PP(C.c_int)]),
+    "rf_roi_from_faces": (C.c_int, [_PP(rf_face), C.c_int, C.c_float, C.c_int, _PP(rf_roi)]),
+    "rf_roi_atlas_host": (C.c_int, [_PP(rf_roi_spec), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, _PP(rf_roi), C.c_int, C.c_void_p,
+                                    C.c_int]),
+    "rf_roi_map_face": (C.c_int, [_PP(rf_roi_spec), C.c_int, C.c_int, _PP(rf_roi), C.c_int, C.c_int, _PP(rf_face), _PP(rf_face), _PP(C.c_int)]),
+    "rf_roi_merge_host": (C.c_int, [_PP(rf_roi_spec), C.c_int, C.c_int, _PP(rf_roi), C.c_int, C.c_float, C.c_int, _PP(rf_face), _PP(C.c_int),
+                                    _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int)]),
+    "rf_roi_atlas_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _PP(rf_roi), C.c_int, _PP(rf_roi_spec), C.c_int, C.c_int,
+                                      C.c_void_p, C.c_int]),
+    "rf_detect_roi_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int, _PP(rf_roi),
+                                             _PP(C.c_int), C.c_float, _PP(rf_roi_spec), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int),
+                                             _PP(C.c_int), C.c_void_p]),
+    "rf_detect_roi_batch": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int, _PP(rf_roi), _PP(C.c_int),
+                                      C.c_float, _PP(rf_roi_spec), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int)]),
+    "rf_roi_merge_device": (C.c_int, [C.c_void_p, _PP(C.c_int), _PP(C.c_int), C.c_int, _PP(rf_roi), _PP(C.c_int), _PP(rf_roi_spec), _PP(rf_face),
+                                      _PP(C.c_int), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int)]),
     "rf_enhance_host": (C.c_int, [_PP(rf_enhance_spec), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, _PP(C.c_int)]),
     "rf_enhance_device": (C.c_int, [C.c_void_p, _PP(rf_enhance_spec), _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
                                     _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int)]),

@@ -413,6 +413,45 @@ void RetinaFace::detectDewarped(const vector<cv::Mat> &imgs, rf_dewarper dewarpe
     }
 }
 
+void RetinaFace::detectRois(const vector<cv::Mat> &imgs, const vector<vector<rf_roi>> &rois, float threshold, const rf_roi_spec *spec) {
+    const int n = (int)imgs.size();
+    if ((int)rois.size() != n) throw std::runtime_error("RetinaFace::detectRois: one list of regions per frame");
+    lastBatch_.assign(n, vector<FaceDetectInfo>());
+    roiVotes_.assign(n, vector<int>());
+    roiSrc_.assign(n, vector<int>());
+    if (n == 0) return;
+    const int cap = spec && spec->max_faces > 0 ? spec->max_faces : maxDet_;
+    vector<const uint8_t *> ptrs(n);
+    vector<int> rows(n), cols(n), steps(n), counts(n, 0), roiCounts(n);
+    vector<rf_roi> flat;
+    for (int i = 0; i < n; i++) {
+        ptrs[i] = imgs[i].empty() ? nullptr : imgs[i].data;
+        rows[i] = imgs[i].rows; cols[i] = imgs[i].cols; steps[i] = (int)(size_t)imgs[i].step;
+        roiCounts[i] = (int)rois[i].size();
+        flat.insert(flat.end(), rois[i].begin(), rois[i].end());
+    }
+    vector<rf_face> faces((size_t)n * cap);
+    vector<int> votes((size_t)n * cap, 0), src((size_t)n * cap, 0);
+    check(rf_detect_roi_batch(h_, ptrs.data(), rows.data(), cols.data(), steps.data(), n, flat.data(), roiCounts.data(), threshold, spec,
+                              faces.data(), cap, counts.data(), votes.data(), src.data()), h_, "RetinaFace::detectRois");
+    for (int i = 0; i < n; i++) {
+        const int k = counts[i] < cap ? counts[i] : cap;
+        lastBatch_[i].resize(k);
+        if (k) memcpy(lastBatch_[i].data(), &faces[(size_t)i * cap], (size_t)k * sizeof(rf_face));
+        roiVotes_[i].assign(votes.begin() + (size_t)i * cap, votes.begin() + (size_t)i * cap + k);
+        roiSrc_[i].assign(src.begin() + (size_t)i * cap, src.begin() + (size_t)i * cap + k);
+    }
+}
+
+vector<rf_roi> RetinaFace::roisFromFaces(const vector<FaceDetectInfo> &faces, float coordScale, int margin_q8) {
+    static_assert(sizeof(FaceDetectInfo) == sizeof(rf_face), "a FaceDetectInfo is an rf_face");
+    vector<rf_roi> out(faces.size());
+    const int k = rf_roi_from_faces((const rf_face *)faces.data(), (int)faces.size(), coordScale, margin_q8, out.data());
+    if (k < 0) throw std::runtime_error("RetinaFace::roisFromFaces: bad coordScale or margin");
+    out.resize((size_t)k);
+    return out;
+}
+
 void RetinaFace::detectEnhanced(const vector<cv::Mat> &imgs, float threshold, const rf_enhance_spec *spec) {
     const int n = (int)imgs.size();
     lastBatch_.assign(n, vector<FaceDetectInfo>());

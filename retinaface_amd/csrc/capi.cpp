@@ -1703,6 +1703,180 @@ int rf_dewarp_merge_device(rf_dewarper dewarper, int n, const rf_dewarp_spec *sp
     });
 }
 
+// ---- region detection (roi.h)
+namespace {
+// the host entry points' common checks: the spec (max_faces irrelevant where nothing is merged), the view and the regions
+int roi_host_args(const rf_roi_spec *spec, int default_max_faces, int view_w, int view_h, const rf_roi *rois, int n, rf::RoiSpec *sp) {
+    if (rf::roi_spec_resolve(spec, default_max_faces, sp)) return RF_ERR_INVALID_ARG;
+    if (rf::roi_check_view(view_w, view_h, sp->grid)) return RF_ERR_INVALID_ARG;
+    if (n < 0 || n > rf::kRoiMaxRegions || (n > 0 && !rois)) return RF_ERR_INVALID_ARG;
+    for (int r = 0; r < n; r++)
+        if (!rf::roi_valid(rois[r])) return RF_ERR_INVALID_ARG;
+    return RF_OK;
+}
+
+void roi_cells_of(const rf::RoiSpec &sp, int view_w, int view_h, const rf_roi *rois, int n, std::vector<rf::RoiCell> *cells) {
+    cells->resize((size_t)n);
+    for (int r = 0; r < n; r++) (*cells)[r] = rf::roi_plan(rois[r], view_w / sp.grid, view_h / sp.grid, sp.max_zoom);
+}
+}  // namespace
+
+int rf_roi_plan(const rf_roi_spec *spec, int view_w, int view_h, const rf_roi *rois, int n, rf_roi_cell *cells, int *passes) {
+    rf::RoiSpec sp;
+    if (roi_host_args(spec, 1, view_w, view_h, rois, n, &sp) || (n > 0 && !cells)) return RF_ERR_INVALID_ARG;
+    std::vector<rf::RoiCell> c;
+    roi_cells_of(sp, view_w, view_h, rois, n, &c);
+    if (n) memcpy(cells, c.data(), (size_t)n * sizeof(rf_roi_cell));
+    if (passes) *passes = rf::roi_passes(n, sp.grid);
+    return RF_OK;
+}
+
+int rf_roi_from_faces(const rf_face *faces, int n, float coord_scale, int margin_q8, rf_roi *rois) {
+    if (n < 0 || (n > 0 && (!faces || !rois)) || margin_q8 < 0 || margin_q8 > 65536 || !(coord_scale > 0.f) || !(coord_scale <= 65536.f)) return RF_ERR_INVALID_ARG;
+    int k = 0;
+    for (int i = 0; i < n; i++) {
+        float f[15];
+        memcpy(f, &faces[i], sizeof(f));
+        if (rf::roi_from_face(f, coord_scale, margin_q8 ? margin_q8 : 64, &rois[k])) k++;
+    }
+    return k;
+}
+
+int rf_roi_atlas_host(const rf_roi_spec *spec, int view_w, int view_h, const uint8_t *src, int rows, int cols, int step, const rf_roi *rois,
+                      int n, uint8_t *dst, int dst_step) {
+    rf::RoiSpec sp;
+    if (roi_host_args(spec, 1, view_w, view_h, rois, n, &sp)) return RF_ERR_INVALID_ARG;
+    if (!src || !dst || rows <= 0 || cols <= 0 || rows > 4096 * 3072 / cols || step < cols * 3 || dst_step < view_w * 3) return RF_ERR_INVALID_ARG;
+    std::vector<rf::RoiCell> c;
+    roi_cells_of(sp, view_w, view_h, rois, n, &c);
+    const int GG = sp.grid * sp.grid;
+    for (int p = 0; p < rf::roi_passes(n, sp.grid); p++)
+        rf::roi_atlas_host(src, rows, cols, step, c.data() + (size_t)p * GG, std::min(GG, n - p * GG), sp.grid, view_w, view_h,
+                           dst + (size_t)p * view_h * dst_step, dst_step);
+    return RF_OK;
+}
+
+int rf_roi_map_face(const rf_roi_spec *spec, int view_w, int view_h, const rf_roi *rois, int n, int pass, const rf_face *in, rf_face *out,
+                    int *region) {
+    rf::RoiSpec sp;
+    if (!in || !out || roi_host_args(spec, 1, view_w, view_h, rois, n, &sp)) return RF_ERR_INVALID_ARG;
+    if (pass < 0 || pass >= rf::roi_passes(n, sp.grid)) return RF_ERR_INVALID_ARG;
+    std::vector<rf::RoiCell> c;
+    roi_cells_of(sp, view_w, view_h, rois, n, &c);
+    const int GG = sp.grid * sp.grid;
+    const rf::RoiEntry e{0, pass, 0, 0, sp.grid, std::min(GG, n - pass * GG), view_w, view_h, c.data() + (size_t)pass * GG};
+    float f[15];
+    memcpy(f, in, sizeof(f));
+    int r = 0;
+    if (!rf::roi_map_face(e, f, f, &r)) return 0;
+    memcpy(out, f, sizeof(f));
+    if (region) *region = r;
+    return 1;
+}
+
+int rf_roi_merge_host(const rf_roi_spec *spec, int view_w, int view_h, const rf_roi *rois, int n, float nms_threshold, int max_detections,
+                      const rf_face *faces, const int *pass_counts, rf_face *out, int cap, int *count, int *votes, int *src_roi) {
+    rf::RoiSpec sp;
+    if (max_detections < 1 || max_detections > rf::kTtaMaxFaces || roi_host_args(spec, max_detections, view_w, view_h, rois, n, &sp)) return RF_ERR_INVALID_ARG;
+    const int P = rf::roi_passes(n, sp.grid), GG = sp.grid * sp.grid;
+    if (!count || cap < 0 || (cap > 0 && !out) || (P > 0 && (!faces || !pass_counts))) return RF_ERR_INVALID_ARG;
+    for (int p = 0; p < P; p++)
+        if (pass_counts[p] < 0) return RF_ERR_INVALID_ARG;
+    std::vector<rf::RoiCell> c;
+    roi_cells_of(sp, view_w, view_h, rois, n, &c);
+    bool truncated = false;
+    std::vector<float> cand;
+    std::vector<int> g;
+    for (int p = 0; p < P; p++) {
+        const rf::RoiEntry e{0, p, 0, 0, sp.grid, std::min(GG, n - p * GG), view_w, view_h, c.data() + (size_t)p * GG};
+        if (pass_counts[p] > max_detections) truncated = true;
+        for (int j = 0; j < pass_counts[p] && j < max_detections; j++) {
+            float f[15];
+            memcpy(f, &faces[(size_t)p * max_detections + j], sizeof(f));
+            int r = 0;
+            if (!rf::roi_map_face(e, f, f, &r)) continue;
+            cand.insert(cand.end(), f, f + 15);
+            g.push_back(r * max_detections + j);
+        }
+    }
+    const int limit = cap < sp.max_faces ? cap : sp.max_faces;
+    std::vector<float> merged((size_t)limit * 15 + 1);
+    std::vector<int> vt((size_t)limit + 1), hg((size_t)limit + 1);
+    const int heads = rf::tta_merge_candidates(cand, g, nms_threshold, sp.vote != 0, limit, merged.data(), vt.data(), hg.data());
+    *count = heads;
+    const int emitted = heads < limit ? heads : limit;
+    for (int j = 0; j < emitted; j++) {
+        memset(&out[j], 0, sizeof(rf_face));
+        memcpy(&out[j], &merged[(size_t)j * 15], 15 * sizeof(float));
+        if (votes) votes[j] = vt[j];
+        if (src_roi) src_roi[j] = hg[j] / max_detections;
+    }
+    return truncated || heads > limit ? RF_ERR_TRUNCATED : RF_OK;
+}
+
+int rf_roi_atlas_device(rf_handle h, const void *d_src, int rows, int cols, int step, const rf_roi *rois, int n, const rf_roi_spec *spec,
+                        int view_w, int view_h, void *d_dst, int dst_step) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        rf::RoiSpec sp;
+        if (const char *bad = rf::roi_spec_resolve(spec, h->eng->default_max_faces(), &sp)) throw rf::ArgError(bad);
+        h->eng->roi_atlas(d_src, rows, cols, step, rois, n, sp, view_w, view_h, d_dst, dst_step);
+        return RF_OK;
+    });
+}
+
+namespace {
+// a caller's region spec with its defaults applied; refused before the engine is touched
+void roi_request(rf_handle h, const rf_roi_spec *spec, const rf_roi *rois, const int *roi_counts, int *votes, int *src_roi, void *d_views,
+                 rf::RoiRequest *rq) {
+    if (const char *bad = rf::roi_spec_resolve(spec, h->eng->default_max_faces(), &rq->spec)) throw rf::ArgError(bad);
+    rq->rois = rois; rq->roi_counts = roi_counts;
+    rq->votes = votes; rq->src_roi = src_roi; rq->d_views = d_views;
+}
+
+int detect_roi_common(rf_handle h, const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,
+                      const rf_roi *rois, const int *roi_counts, float thr, const rf_roi_spec *spec, rf_face *out, int cap, int *counts,
+                      int *votes, int *src_roi, void *d_views) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        rf::RoiRequest rq;
+        roi_request(h, spec, rois, roi_counts, votes, src_roi, d_views, &rq);
+        bool tr = false;
+        h->eng->detect_rois(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, &tr, rq);
+        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+}  // namespace
+
+int rf_detect_roi_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                               const rf_roi *rois, const int *roi_counts, float threshold, const rf_roi_spec *spec, rf_face *out,
+                               int cap_per_image, int *counts, int *votes, int *src_roi, void *d_views) {
+    return detect_roi_common(h, (const uint8_t *const *)d_bgr, rows, cols, steps, n, true, rois, roi_counts, threshold, spec, out, cap_per_image,
+                             counts, votes, src_roi, d_views);
+}
+
+int rf_detect_roi_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n, const rf_roi *rois,
+                        const int *roi_counts, float threshold, const rf_roi_spec *spec, rf_face *out, int cap_per_image, int *counts,
+                        int *votes, int *src_roi) {
+    return detect_roi_common(h, bgr, rows, cols, steps, n, false, rois, roi_counts, threshold, spec, out, cap_per_image, counts, votes, src_roi,
+                             nullptr);
+}
+
+int rf_roi_merge_device(rf_handle h, const int *rows, const int *cols, int n, const rf_roi *rois, const int *roi_counts,
+                        const rf_roi_spec *spec, const rf_face *faces, const int *pass_counts, rf_face *out, int cap_per_image, int *counts,
+                        int *votes, int *src_roi) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        rf::RoiRequest rq;
+        roi_request(h, spec, rois, roi_counts, votes, src_roi, nullptr, &rq);
+        bool tr = false;
+        h->eng->roi_merge(rows, cols, n, rq, faces, pass_counts, out, cap_per_image, counts, &tr);
+        if (tr) { h->error = "more candidates / detections than the configured caps"; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+
 // ---- low-light enhancement (enhance.h)
 int rf_enhance_host(const rf_enhance_spec *spec, const uint8_t *src, int rows, int cols, int step, uint8_t *dst, int dst_step,
                     int *tiles_enhanced) {

@@ -119,10 +119,11 @@ struct NetKind {
     std::function<void(const Plan &, const NetSite &, LaneNet *)> build_net;
 };
 
-// The open pass call: tiled, TTA, pyramid, rotation and fisheye detection turn a call's frames into passes that go through detect()'s ordinary
+// The open pass call: tiled, TTA, pyramid, rotation, fisheye and region detection turn a call's frames into passes that go through detect()'s ordinary
 // launches, in call order, so image i of a launch is pass next_pass + i.  What differs between the modes is bound when the call is
 // opened (the two callables); the launch path (launch_lane_passes) does not know which mode it serves.
 constexpr size_t kPassEntryMax = std::max(std::max(std::max(sizeof(TileEntry), sizeof(TtaEntry)), std::max(sizeof(PyrEntry), sizeof(RotEntry))), sizeof(DewarpEntry));
+static_assert(sizeof(RoiEntry) <= kPassEntryMax, "a region pass is no larger than the largest pass entry: its cell records travel in a block of their own");
 struct PassCall {
     // gather(stream, faces, face_stride, counts, table, n): the mode's gather over the n passes of one launch (table: their entries)
     using Gather = std::function<void(hipStream_t, const uint8_t *, int, const int *, const void *, int)>;
@@ -229,9 +230,9 @@ public:
         for (void *p : host_allocs_) (void)hipHostFree(p);
         if (align_stream_) { (void)hipStreamSynchronize(align_stream_); (void)hipStreamDestroy(align_stream_); }
         for (DeviceScratch *b : {&align_crops_, &align_mats_, &align_tab_, &fb_state_, &fq_records_, &fq_packed_, &fq_offsets_, &tile_cand_, &tile_count_, &tile_out_,
-                                 &tile_outcount_, &tile_tab_, &pass_frames_, &tta_cand_, &tta_count_, &tta_mirror_, &pyr_zoom_, &rot_copies_, &dewarp_views_, &enh_luts_, &enh_frames_,
+                                 &tile_outcount_, &tile_tab_, &pass_frames_, &tta_cand_, &tta_count_, &tta_mirror_, &pyr_zoom_, &rot_copies_, &dewarp_views_, &roi_cells_, &roi_views_, &enh_luts_, &enh_frames_,
                                  &red_regions_, &red_counts_, &red_cells_, &red_frames_, &red_shadow_, &fol_results_}) b->release();
-        for (HostScratch *b : {&trk_tags_, &trk_ended_, &trk_counts_, &enh_counts_, &tta_out_, &tta_votes_, &tta_outcount_, &shot_out_, &shot_info_, &fol_out_}) b->release();
+        for (HostScratch *b : {&trk_tags_, &trk_ended_, &trk_counts_, &enh_counts_, &roi_cells_pin_, &tta_out_, &tta_votes_, &tta_outcount_, &shot_out_, &shot_info_, &fol_out_}) b->release();
         for (auto &t : trackers_) t->release();
         for (auto &d : dewarpers_) d->mesh.release();
         for (hipEvent_t e : trk_ev_) if (e) (void)hipEventDestroy(e);
@@ -1365,6 +1366,163 @@ public:
         DeviceGuard guard(device_);
         merge_passes(entries, n, faces, pass_counts, truncated, [&] { tta_open(n, mrq.spec); },
                      gather_into<DewarpMap>(rq.spec.edge, tta_cand_, tta_count_, kTtaMergeCap), vote_merge_of(n, mrq.spec), tta_dirty_);
+        tta_copy_out(n, mrq, out, cap_per_image, counts, truncated);
+    }
+
+    // -------------------------------------------------------------------------------- region detection
+    // The regions of a call, checked, as cell records (frame-major, the call's order) and as one pass table, frame-major, ascending
+    // region: frame i's passes are ceil(roi_counts[i] / grid^2) views of the net's size.  Entries point into `d_cells`, the address
+    // the records will have on the device.  A NULL frame keeps its passes, which gather nothing (frame = -1).  frames null:
+    // roi_merge(), which has no pixels.
+    void roi_build_passes(const RoiRequest &rq, const uint8_t *const *frames, const int *rows, const int *cols, int n,
+                          std::vector<RoiCell> *cells, std::vector<RoiEntry> *entries, std::vector<int> *first_cell) const {
+        const int G = rq.spec.grid, GG = G * G;
+        if (const char *bad = roi_check_view(net_w_, net_h_, G)) throw ArgError(std::string("region detection: ") + bad);
+        if (n > 0 && !rq.roi_counts) throw ArgError("null argument");
+        cells->clear(); entries->clear(); first_cell->clear();
+        size_t total = 0;
+        for (int i = 0; i < n; i++) {
+            if (rq.roi_counts[i] < 0 || rq.roi_counts[i] > kRoiMaxRegions) throw ArgError("region detection: a frame has 0 to 256 regions");
+            total += (size_t)rq.roi_counts[i];
+        }
+        if (total && !rq.rois) throw ArgError("null argument");
+        for (size_t r = 0; r < total; r++)
+            if (!roi_valid(rq.rois[r])) throw ArgError("region detection: a region's w, h must be in [1, 16384], |x|, |y| at most 2^20");
+        const int cw = net_w_ / G, ch = net_h_ / G;
+        const rf_roi *roi = rq.rois;
+        for (int i = 0; i < n; i++) {
+            const int R = rq.roi_counts[i];
+            const bool empty = frames && (!frames[i] || rows[i] <= 0 || cols[i] <= 0);
+            for (int p = 0; p < roi_passes(R, G); p++) {
+                RoiEntry e;
+                memset(&e, 0, sizeof(e));
+                e.frame = empty ? -1 : i; e.pass = p; e.rows = rows[i]; e.cols = cols[i]; e.grid = G; e.used = std::min(GG, R - p * GG);
+                e.net_w = net_w_; e.net_h = net_h_;
+                first_cell->push_back((int)cells->size() + p * GG);
+                entries->push_back(e);
+            }
+            for (int r = 0; r < R; r++) cells->push_back(roi_plan(roi[r], cw, ch, rq.spec.max_zoom));
+            roi += R;
+        }
+    }
+
+    // The cell records of a call in device memory: staged in a pinned host block and copied on the side stream (in front of the atlas
+    // kernel and of inputs_ready, as a dewarper's meshes are in front of its first call); the entries then point at them.  Every
+    // caller has the side stream waited for before it returns (the call's last launch waits for inputs_ready; merge_passes
+    // synchronises), so the pinned block is free again at the next call.
+    void roi_upload_cells(const std::vector<RoiCell> &cells, std::vector<RoiEntry> &entries, const std::vector<int> &first_cell) {
+        const size_t bytes = std::max<size_t>(cells.size(), 1) * sizeof(RoiCell);
+        uint8_t *pin = roi_cells_pin_.reserve(bytes);
+        const RoiCell *d = (const RoiCell *)roi_cells_.reserve(bytes);
+        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+        if (!cells.empty()) {
+            memcpy(pin, cells.data(), cells.size() * sizeof(RoiCell));
+            RF_HIP(hipMemcpyAsync(roi_cells_.ptr, pin, cells.size() * sizeof(RoiCell), hipMemcpyHostToDevice, align_stream_));
+        }
+        for (size_t q = 0; q < entries.size(); q++) entries[q].cells = d + first_cell[q];
+    }
+
+    // the blocks of a region call are those of a TTA call (tta_open): the two calls never overlap, and the merge is the same launch
+    static TtaRequest roi_merge_request(const RoiRequest &rq) {
+        TtaRequest t;
+        t.spec.flip = 0; t.spec.vote = rq.spec.vote; t.spec.max_faces = rq.spec.max_faces;
+        t.votes = rq.votes; t.src_pass = rq.src_roi;
+        return t;
+    }
+
+    void roi_atlas(const void *d_src, int rows, int cols, int step, const rf_roi *rois, int n, const RoiSpec &sp, int view_w, int view_h,
+                   void *d_dst, int dst_step) override {
+        if (const char *bad = roi_check_view(view_w, view_h, sp.grid)) throw ArgError(std::string("region atlas: ") + bad);
+        if (n < 0 || n > kRoiMaxRegions || (n > 0 && !rois)) throw ArgError("region atlas: 0 to 256 regions");
+        for (int r = 0; r < n; r++)
+            if (!roi_valid(rois[r])) throw ArgError("region atlas: a region's w, h must be in [1, 16384], |x|, |y| at most 2^20");
+        if (!d_dst || dst_step < view_w * 3) throw ArgError("region atlas: null destination or dst_step < view_w * 3");
+        check_frame((const uint8_t *)d_src, rows, cols, step);
+        if (!d_src || rows <= 0 || cols <= 0) throw ArgError("null argument");
+        if (n == 0) return;
+        DeviceGuard guard(device_);
+        const int GG = sp.grid * sp.grid, P = roi_passes(n, sp.grid);
+        std::vector<RoiCell> cells;
+        for (int r = 0; r < n; r++) cells.push_back(roi_plan(rois[r], view_w / sp.grid, view_h / sp.grid, sp.max_zoom));
+        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+        const RoiCell *d = (const RoiCell *)roi_cells_.reserve(cells.size() * sizeof(RoiCell));
+        RF_HIP(hipMemcpy(roi_cells_.ptr, cells.data(), cells.size() * sizeof(RoiCell), hipMemcpyHostToDevice));
+        std::vector<RoiAtlasParams> ap;
+        for (int p = 0; p < P; p++)
+            ap.push_back(RoiAtlasParams{(const uint8_t *)d_src, rows, cols, step, d + (size_t)p * GG, std::min(GG, n - p * GG), sp.grid, view_w, view_h,
+                                        (uint8_t *)d_dst + (size_t)p * view_h * dst_step, dst_step,
+                                        roi_min_level(cells.data() + (size_t)p * GG, std::min(GG, n - p * GG))});
+        launch_roi_views(align_stream_, ap.data(), P);
+        RF_HIP(hipGetLastError());
+        RF_HIP(hipStreamSynchronize(align_stream_));
+    }
+
+    void detect_rois(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device, float threshold,
+                     rf_face *out, int cap_per_image, int *counts, bool *truncated, const RoiRequest &rq) override {
+        *truncated = false;
+        const TtaRequest mrq = roi_merge_request(rq);
+        pass_check_args(n, frames, rows, cols, counts, out, cap_per_image, mrq.spec.max_faces);
+        std::vector<int> st = checked_steps(frames, rows, cols, steps, n);
+        std::vector<RoiCell> cells;
+        std::vector<RoiEntry> entries;
+        std::vector<int> first_cell;
+        roi_build_passes(rq, frames, rows, cols, n, &cells, &entries, &first_cell);
+        for (int i = 0; i < n; i++) counts[i] = 0;
+        const int P = (int)entries.size();
+        if (P == 0) return;                                       // no frame has a region: no pass, no faces
+        DeviceGuard guard(device_);
+        std::vector<char> live((size_t)n, 0);
+        for (const RoiEntry &e : entries)
+            if (e.frame >= 0) live[e.frame] = 1;
+        const std::vector<const uint8_t *> base = pass_frame_bases(frames, rows, cols, st, n, on_device, [&](int i) { return live[i] != 0; });
+        launch_pending();
+        // The views: dense frames, frame-major, in the caller's block or in one of the engine's -- a view of the net's size is a multiple
+        // of 768 bytes, so each starts 256-byte aligned; made on the side stream behind the copy of the cell records, every lane that
+        // launches a pass of the call waits for them on the device.
+        const size_t vb = (size_t)net_w_ * net_h_ * 3;
+        uint8_t *d_views = rq.d_views ? (uint8_t *)rq.d_views : roi_views_.reserve(vb * (size_t)P);
+        bool any_live = false;
+        for (char l : live) any_live = any_live || l;
+        if (any_live) roi_upload_cells(cells, entries, first_cell);      // (the passes of NULL frames never read their records)
+        PassViews v(P);
+        std::vector<RoiAtlasParams> ap;
+        for (int q = 0; q < P; q++) {
+            const RoiEntry &e = entries[q];
+            if (e.frame < 0) continue;
+            uint8_t *dst = d_views + vb * (size_t)q;
+            ap.push_back(RoiAtlasParams{base[e.frame], e.rows, e.cols, st[e.frame], e.cells, e.used, e.grid, net_w_, net_h_, dst, net_w_ * 3,
+                                        roi_min_level(cells.data() + first_cell[q], e.used)});
+            v.set(q, dst, net_h_, net_w_, net_w_ * 3);
+        }
+        hipEvent_t packed = nullptr;
+        if (!ap.empty()) {
+            launch_roi_views(align_stream_, ap.data(), (int)ap.size());
+            packed = record_inputs_ready();
+        }
+        tta_open(n, mrq.spec);
+        *truncated = run_passes("region detection", entries, v, threshold, packed,
+                                gather_into<RoiMap>(0, tta_cand_, tta_count_, kTtaMergeCap), vote_merge_of(n, mrq.spec), tta_dirty_);
+        tta_copy_out(n, mrq, out, cap_per_image, counts, truncated);
+    }
+
+    void roi_merge(const int *rows, const int *cols, int n, const RoiRequest &rq, const rf_face *faces, const int *pass_counts, rf_face *out,
+                   int cap_per_image, int *counts, bool *truncated) override {
+        *truncated = false;
+        const TtaRequest mrq = roi_merge_request(rq);
+        pass_check_args(n, rows, cols, counts, rq.roi_counts, out, cap_per_image, mrq.spec.max_faces);
+        for (int i = 0; i < n; i++)
+            if (rows[i] < 0 || cols[i] < 0) throw ArgError("negative frame size");
+        std::vector<RoiCell> cells;
+        std::vector<RoiEntry> entries;
+        std::vector<int> first_cell;
+        roi_build_passes(rq, nullptr, rows, cols, n, &cells, &entries, &first_cell);
+        if (!entries.empty() && (!faces || !pass_counts)) throw ArgError("null argument");
+        for (int i = 0; i < n; i++) counts[i] = 0;
+        if (entries.empty()) return;
+        DeviceGuard guard(device_);
+        roi_upload_cells(cells, entries, first_cell);             // on the side stream, in front of the table's copy and the gather
+        merge_passes(entries, n, faces, pass_counts, truncated, [&] { tta_open(n, mrq.spec); },
+                     gather_into<RoiMap>(0, tta_cand_, tta_count_, kTtaMergeCap), vote_merge_of(n, mrq.spec), tta_dirty_);
         tta_copy_out(n, mrq, out, cap_per_image, counts, truncated);
     }
 
@@ -3506,6 +3664,9 @@ private:
     };
     std::vector<std::unique_ptr<Dewarper>> dewarpers_;
     DeviceScratch dewarp_views_;
+    // region detection (roi.h): the cell records of a call (device block; roi_cells_pin_ below stages them) and its views; the call gathers into the TTA
+    // blocks too (roi_merge_request)
+    DeviceScratch roi_cells_, roi_views_;
     // low-light enhancement (enhance.h): LUTs | flags | per-frame counts of a call, and the enhanced copies of a fused call
     DeviceScratch enh_luts_, enh_frames_;
     bool tta_dirty_ = true;
@@ -3550,7 +3711,7 @@ private:
         }
         void release() { if (ptr) (void)hipHostFree(ptr); ptr = nullptr; cap = 0; }
     };
-    HostScratch trk_tags_, trk_ended_, trk_counts_, enh_counts_;
+    HostScratch trk_tags_, trk_ended_, trk_counts_, enh_counts_, roi_cells_pin_;
     // best-shot gallery: the call-level blocks the deliver kernel writes (shots, records; indexed image * cap_ended + e), the events
     // around the shot launches of track_shots() (tools/shot_bench.py reads the time) and the request a shot call has open
     HostScratch shot_out_, shot_info_;

@@ -137,6 +137,18 @@ struct DewarpRequest {
     void *d_views = nullptr;                    // n * V * view_h * view_w * 3 bytes, dense, frame-major
 };
 
+// A region call (roi.h; rf_detect_roi_batch* / rf_roi_merge_device): the validated spec, the regions of the call's frames (frame-major,
+// roi_counts[i] of frame i), where the member count and the region of each merged face go, and where the views go (device memory;
+// nullptr: an engine-owned block)
+struct RoiRequest {
+    RoiSpec spec;
+    const rf_roi *rois = nullptr;
+    const int *roi_counts = nullptr;
+    int *votes = nullptr;                       // host, indexed like out, or nullptr
+    int *src_roi = nullptr;
+    void *d_views = nullptr;                    // P * net_h * net_w * 3 bytes, dense, frame-major
+};
+
 // An enhanced detection call (enhance.h; rf_detect_enhanced_batch*): the validated spec, where the enhanced copies go (device memory;
 // nullptr: an engine-owned block) and where the number of flagged tiles of each frame goes
 struct EnhanceRequest {
@@ -310,6 +322,21 @@ public:
     // edge rule, mapping and merge of per-view faces the caller supplies (faces[(i * V + v) * max_detections + j])
     virtual void dewarp_merge(int, const DewarpRequest &, const rf_face *, const int *, rf_face *, int, int *, bool *) {
         throw Unsupported("fisheye detection is not available on a multi-device handle");
+    }
+    // Region detection: the regions of every frame are packed, grid x grid to a net-sized view, by one kernel on the device in front of
+    // the call's first launch; the views go through detect()'s ordinary launches; a gather launch behind each of them and one voting
+    // merge behind the last (ordered by events on the device, no host wait).  *truncated: a pass or the merge hit a cap.
+    // Single-device engines only.
+    virtual void detect_rois(const uint8_t *const *, const int *, const int *, const int *, int, bool, float, rf_face *, int, int *, bool *, const RoiRequest &) {
+        throw Unsupported("region detection is not available on a multi-device handle");
+    }
+    // face rule and merge of per-pass faces the caller supplies (faces[q * max_detections + j], q over the call's passes)
+    virtual void roi_merge(const int *, const int *, int, const RoiRequest &, const rf_face *, const int *, rf_face *, int, int *, bool *) {
+        throw Unsupported("region detection is not available on a multi-device handle");
+    }
+    // the atlas kernel on its own: all passes of n regions of a device-resident frame, pass p at d_dst + p * view_h * dst_step
+    virtual void roi_atlas(const void *, int, int, int, const rf_roi *, int, const RoiSpec &, int, int, void *, int) {
+        throw Unsupported("region detection is not available on a multi-device handle");
     }
     // Low-light enhancement: the two enhance kernels over frames in device memory (synchronous), and the fused call -- the enhanced
     // copies made on the side stream in front of the call's first launch, detect() over them, no host wait in between.

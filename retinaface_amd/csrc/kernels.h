@@ -16,6 +16,7 @@
 #include "pyramid.h"
 #include "rot.h"
 #include "dewarp.h"
+#include "roi.h"
 #include "tile.h"
 #include "tta.h"
 #include "track.h"
@@ -312,7 +313,14 @@ struct DewarpMap {
     __host__ __device__ static bool keep(const Entry &e, int edge, const float *in, float *out) { return dewarp_map_face(e, edge, in, out); }
     __host__ __device__ static int pass_id(const Entry &e) { return e.view; }
 };
-template <class Map> void launch_pass_gather(hipStream_t s, const PassGatherParams<typename Map::Entry> &p);      // the five above
+// region detection: the pass of a face does not name its region, so the rule reports it (keep_region in place of keep); pass_id is
+// the first region of the pass, the id a face carries until its rule has named its own
+struct RoiMap {
+    using Entry = RoiEntry;
+    __host__ __device__ static bool keep_region(const Entry &e, int, const float *in, float *out, int *region) { return roi_map_face(e, in, out, region); }
+    __host__ __device__ static int pass_id(const Entry &e) { return e.pass * e.grid * e.grid; }
+};
+template <class Map> void launch_pass_gather(hipStream_t s, const PassGatherParams<typename Map::Entry> &p);      // the six above
 
 // ---- K_j: face tracks (track.h) -- the frame steps of a launch's images: one workgroup per stream present in the launch walks that
 //      stream's images in order, its table in LDS, one thread per slot.  Every pointer is device-visible memory (the fused calls read
@@ -502,6 +510,23 @@ struct DewarpParams {
 constexpr int kDewarpViewsPerLaunch = 16;        // views of one launch: their descriptors travel as kernel arguments
 constexpr int kDewarpTileW = 64, kDewarpTileH = 16;
 void launch_dewarp_views(hipStream_t s, const DewarpParams *views, int n);
+
+// ---- K_p: region detection (roi.h).
+//      roi_atlas:  the atlas views of a call (any source pitch and alignment) as dense or pitched frames, in front of a region call's
+//                  launches: the pixel rule of roi.h, a workgroup per 64 x 16 pixel tile of ONE cell (the cell's record is uniform over
+//                  the workgroup), a thread per four neighbouring pixels of a row, rows stored 12 bytes per thread.
+//      The gather is launch_pass_gather<RoiMap> (roi_map_face: the face rule), g = region * rank_stride + j.
+//      The merge is launch_vote_merge.
+struct RoiAtlasParams {
+    const uint8_t *src; int rows, cols, step;     // the SOURCE frame: row y at src + y * step
+    const RoiCell *cells; int used;               // the view's first `used` cells, device memory; the others are zero
+    int grid, view_w, view_h;                     // roi_check_view
+    uint8_t *dst; int dst_step;                   // view_w * 3 bytes per row are written, view_h rows
+    int min_level;                                // roi_min_level of the cells: 0, -1 or -2 (the launch sizes its LDS by it)
+};
+constexpr int kRoiViewsPerLaunch = 16;           // views of one launch: their descriptors travel as kernel arguments
+constexpr int kRoiTileW = 64, kRoiTileH = 16;
+void launch_roi_views(hipStream_t s, const RoiAtlasParams *views, int n);
 
 // ---- K_k: zoom-pyramid detection (pyramid.h).
 //      zoom_tile:  windows of frames enlarged 2x / 4x (integer bilinear, pyr_zoom_pixel) written as dense frames, in front of a

@@ -4511,10 +4511,15 @@ void launch_face_gate_scan(hipStream_t s, const FaceGateScanParams &p) {
 //      different streams in any order; the merge (nms_kernel or vote_merge_kernel on these arrays) sorts on the total order
 //      (score, g), so the append order never shows.
 // =============================================================================================
+// a Map whose rule names the face's pass itself (RoiMap::keep_region: the region); every other Map's pass is the entry's
+template <class Map, class = void> struct MapNamesPass : std::false_type {};
+template <class Map> struct MapNamesPass<Map, std::void_t<decltype(&Map::keep_region)>> : std::true_type {};
+
 template <class Map> __global__ __launch_bounds__(kThreads) void pass_gather_kernel(PassGatherParams<typename Map::Entry> a) {
     const int p = blockIdx.x;
     const typename Map::Entry e = a.table[p];
     if (e.frame < 0) return;
+    const int entry_id = Map::pass_id(e);
     int cnt = a.counts[p];
     cnt = cnt < 0 ? 0 : cnt < a.faces_per_pass ? cnt : a.faces_per_pass;
     const int lane = (int)threadIdx.x & 63;
@@ -4523,10 +4528,12 @@ template <class Map> __global__ __launch_bounds__(kThreads) void pass_gather_ker
         const int k = k0 + (int)threadIdx.x;
         float f[15];
         bool keep = false;
+        int id = entry_id;
         if (k < cnt) {
             const float *src = (const float *)(a.faces + ((size_t)p * a.faces_per_pass + k) * a.face_stride);
             for (int i = 0; i < 15; i++) f[i] = src[i];
-            keep = Map::keep(e, a.edge, f, f);
+            if constexpr (MapNamesPass<Map>::value) keep = Map::keep_region(e, a.edge, f, f, &id);
+            else keep = Map::keep(e, a.edge, f, f);
         }
         const unsigned long long mask = __ballot(keep);
         if (!mask) continue;                                     // wave-uniform
@@ -4541,7 +4548,7 @@ template <class Map> __global__ __launch_bounds__(kThreads) void pass_gather_ker
         c.score = f[0];
         c.x1 = f[1]; c.y1 = f[2]; c.x2 = f[3]; c.y2 = f[4];
         for (int i = 0; i < 5; i++) { c.px[i] = f[5 + i]; c.py[i] = f[10 + i]; }
-        c.anchor = Map::pass_id(e) * a.rank_stride + k;
+        c.anchor = id * a.rank_stride + k;
         dst[pos] = c;
     }
 }
@@ -4555,6 +4562,7 @@ template void launch_pass_gather<TtaMap>(hipStream_t, const PassGatherParams<Tta
 template void launch_pass_gather<PyrMap>(hipStream_t, const PassGatherParams<PyrEntry> &);
 template void launch_pass_gather<RotMap>(hipStream_t, const PassGatherParams<RotEntry> &);
 template void launch_pass_gather<DewarpMap>(hipStream_t, const PassGatherParams<DewarpEntry> &);
+template void launch_pass_gather<RoiMap>(hipStream_t, const PassGatherParams<RoiEntry> &);
 
 // =============================================================================================
 // K_j: face tracks (track.h).  track_kernel: one workgroup per stream present in the launch, one thread per slot (64 threads per 64
@@ -6452,6 +6460,138 @@ void launch_dewarp_views(hipStream_t s, const DewarpParams *views, int n) {
         }
         if (!blocks) continue;
         hipLaunchKernelGGL(dewarp_views_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536), (unsigned)m), dim3(kThreads), 0, s, b);
+    }
+}
+
+// =============================================================================================
+// K_p: region detection (roi.h).
+// roi_atlas_kernel: the atlas views of a call.  One launch carries up to sixteen views (blockIdx.y); a workgroup takes tiles of 64 x 16
+//      pixels of ONE cell (a cell is cut into its own tiles, so a tile never straddles two cells): the cell's record -- region, level,
+//      origin -- is the same for every thread of the workgroup and is read through a uniform address into scalar registers.  Thread t
+//      owns the four pixels 4 (t & 15) .. + 3 of tile row t >> 4 (a cell's width is a multiple of 4: the four are in the cell or not)
+//      and runs roi.h's pixel rule on each, the code rf_roi_atlas_host runs: x1 copies the pixel, x2 / x4 blend four taps
+//      (pyr_zoom_pixel), x1/2 / x1/4 average the k x k source block; the taps are gathered from global memory -- a tile's footprint in
+//      the source is an axis-aligned rectangle whose rows neighbouring threads share, so they come from the cache.  The twelve bytes
+//      go out as rotate_frames_kernel stores them: three dwords where the destination is dword aligned, bytewise elsewhere; a wave
+//      writes four rows of 192 contiguous bytes.  A cell without a region is written as zeros.  The shrunk levels of a tile whose
+//      source box lies inside the frame go through roi_shrink_staged instead (the box copied into LDS with dword loads, measured
+//      1.3 x and 1.7 x faster per output byte at x1/2 and x1/4); the gather is their path at the border.  No byte outside the view_w * 3 bytes
+//      of a row is written, no source byte outside rows x cols is read (a level pixel outside the level image is 0 and addresses
+//      nothing); every loop is bounded by the tile count or by k <= 4.
+// =============================================================================================
+struct RoiBatch { RoiAtlasParams v[kRoiViewsPerLaunch]; int lds_bytes; };
+extern __shared__ uint32_t s_roi_src[];
+// dwords a tile's source rows take at x1/2 and x1/4: (64 k pixels * 3 bytes / 4) * (16 k rows)
+constexpr int kRoiStageBytesHalf = (kRoiTileW * 2 * 3 / 4) * (kRoiTileH * 2) * 4, kRoiStageBytesQuarter = (kRoiTileW * 4 * 3 / 4) * (kRoiTileH * 4) * 4;
+
+// The shrunk levels, staged: the source rows of a tw x th tile of a cell at x1/K (K = 1 << S) are a box of tw K x th K source pixels.
+// When that box lies inside the frame with a pixel to spare on its left and right, the workgroup copies it into LDS with dword loads
+// -- a wave takes a row, reads the aligned dwords that cover it (the row's address has any alignment; v_alignbyte puts the bytes in
+// place; with a pixel to spare the up to three bytes in front of and behind the box are still the row's own) -- and each thread sums
+// its 4 K x K pixels from 3 K dwords per row.  Uniform over the workgroup; returns false, having done nothing, for a box that
+// touches the frame's border (the gather path clamps there) or does not fit the launch's LDS.  The sums and the rounding are
+// roi_level_pixel's, so the bytes are.
+template <int S>
+__device__ __forceinline__ bool roi_shrink_staged(const RoiAtlasParams &a, const RoiCell &c, int lds_bytes, int i0, int j0, int tw, int th,
+                                                  bool active, int q, int r, uint8_t *b) {
+    constexpr int K = 1 << S;
+    const int SX0 = (c.x0 + i0) * K, SY0 = (c.y0 + j0) * K, W = tw * K, H = th * K;
+    if (SX0 < 1 || SY0 < 0 || SX0 + W + 1 > a.cols || SY0 + H > a.rows) return false;
+    const int nd = W * 3 / 4;                                            // W is a multiple of 4
+    if (nd * H * 4 > lds_bytes) return false;
+    const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+    for (int row = wave; row < H; row += kThreads / 64) {
+        const uint8_t *g = a.src + (size_t)(SY0 + row) * a.step + (size_t)3 * SX0;
+        const uint32_t al = (uint32_t)((uintptr_t)g & 3);
+        const uint32_t *p = (const uint32_t *)(g - al);
+        for (int d = lane; d < nd; d += 64) {
+            const uint32_t lo = p[d], hi = al ? p[d + 1] : 0u;           // al is the wave's: no divergence
+            s_roi_src[row * nd + d] = __builtin_amdgcn_alignbyte(hi, lo, al);
+        }
+    }
+    __syncthreads();
+    if (active) {
+        int acc[12];
+#pragma unroll
+        for (int k = 0; k < 12; k++) acc[k] = 0;
+#pragma unroll
+        for (int dy = 0; dy < K; dy++) {
+            const uint32_t *w = s_roi_src + (r * K + dy) * nd + 3 * K * q / 4;      // q is a multiple of 4
+            uint32_t v[3 * K];
+#pragma unroll
+            for (int k = 0; k < 3 * K; k++) v[k] = w[k];
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+#pragma unroll
+                for (int dx = 0; dx < K; dx++)
+#pragma unroll
+                    for (int ch = 0; ch < 3; ch++) {
+                        const int at = 3 * (K * j + dx) + ch;
+                        acc[3 * j + ch] += (int)((v[at >> 2] >> (8 * (at & 3))) & 255u);
+                    }
+        }
+#pragma unroll
+        for (int k = 0; k < 12; k++) b[k] = (uint8_t)((acc[k] + (K * K >> 1)) >> (2 * S));
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(kThreads) void roi_atlas_kernel(RoiBatch batch) {
+    static_assert(kThreads * 4 == kRoiTileW * kRoiTileH && kRoiTileH == 16, "one thread per four pixels of a 64 x 16 tile");
+    const RoiAtlasParams a = batch.v[blockIdx.y];
+    if (a.view_w <= 0 || a.view_h <= 0) return;
+    const int cw = a.view_w / a.grid, ch = a.view_h / a.grid;
+    const int tiles_x = (cw + kRoiTileW - 1) / kRoiTileW, per_cell = tiles_x * ((ch + kRoiTileH - 1) / kRoiTileH);
+    const int tiles = per_cell * a.grid * a.grid;
+    const int q = ((int)threadIdx.x & 15) << 2, r = (int)threadIdx.x >> 4;
+    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {       // uniform over the workgroup
+        const int cell = tile / per_cell, t = tile - cell * per_cell;
+        const int ty = t / tiles_x, tx = t - ty * tiles_x;
+        const int cj = cell / a.grid, ci = cell - cj * a.grid;
+        const int i0 = tx * kRoiTileW, j0 = ty * kRoiTileH;
+        const int tw = cw - i0 < kRoiTileW ? cw - i0 : kRoiTileW, th = ch - j0 < kRoiTileH ? ch - j0 : kRoiTileH;
+        const bool active = q < tw && r < th;
+        const int i = i0 + q, j = j0 + r;
+        uint8_t b[12];
+        for (int k = 0; k < 12; k++) b[k] = 0;
+        bool staged = false;
+        if (cell < a.used) {
+            const RoiCell c = a.cells[cell];
+            if (c.level == -1) staged = roi_shrink_staged<1>(a, c, batch.lds_bytes, i0, j0, tw, th, active, q, r, b);
+            else if (c.level == -2) staged = roi_shrink_staged<2>(a, c, batch.lds_bytes, i0, j0, tw, th, active, q, r, b);
+            if (!staged && active)
+                for (int k = 0; k < 4; k++) roi_cell_pixel(a.src, a.rows, a.cols, (size_t)a.step, c, i + k, j, b + 3 * k);
+        }
+        if (active) {
+            const uint32_t o0 = b[0] | (uint32_t)b[1] << 8 | (uint32_t)b[2] << 16 | (uint32_t)b[3] << 24;
+            const uint32_t o1 = b[4] | (uint32_t)b[5] << 8 | (uint32_t)b[6] << 16 | (uint32_t)b[7] << 24;
+            const uint32_t o2 = b[8] | (uint32_t)b[9] << 8 | (uint32_t)b[10] << 16 | (uint32_t)b[11] << 24;
+            rot_store12(a.dst + (size_t)(cj * ch + j) * a.dst_step + (size_t)3 * (ci * cw + i), o0, o1, o2);
+        }
+        if (staged) __syncthreads();                                     // the next tile overwrites the staged rows
+    }
+}
+
+// up to kRoiViewsPerLaunch views per launch (blockIdx.y), the grid sized for the largest of them, the LDS for the smallest level
+void launch_roi_views(hipStream_t s, const RoiAtlasParams *views, int n) {
+    for (int f0 = 0; f0 < n; f0 += kRoiViewsPerLaunch) {
+        RoiBatch b;
+        memset(&b, 0, sizeof(b));
+        const int m = n - f0 < kRoiViewsPerLaunch ? n - f0 : kRoiViewsPerLaunch;
+        long long blocks = 0;
+        for (int i = 0; i < m; i++) {
+            const RoiAtlasParams &p = views[f0 + i];
+            if (p.view_w <= 0 || p.view_h <= 0) continue;
+            if ((p.grid != 1 && p.grid != 2 && p.grid != 4) || roi_check_view(p.view_w, p.view_h, p.grid) || p.used < 0 || p.used > p.grid * p.grid ||
+                (p.used > 0 && (!p.cells || !p.src || p.rows <= 0 || p.cols <= 0 || p.step < p.cols * 3)) || !p.dst || p.dst_step < p.view_w * 3)
+                throw std::invalid_argument("launch_roi_views: a view's shape, cells, source or destination is not valid");
+            b.v[i] = p;
+            const int cw = p.view_w / p.grid, ch = p.view_h / p.grid;
+            blocks = std::max(blocks, (long long)((cw + kRoiTileW - 1) / kRoiTileW) * ((ch + kRoiTileH - 1) / kRoiTileH) * p.grid * p.grid);
+            b.lds_bytes = std::max(b.lds_bytes, p.min_level <= -2 ? kRoiStageBytesQuarter : p.min_level == -1 ? kRoiStageBytesHalf : 0);
+        }
+        if (!blocks) continue;
+        hipLaunchKernelGGL(roi_atlas_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536), (unsigned)m), dim3(kThreads), (size_t)b.lds_bytes, s, b);
     }
 }
 

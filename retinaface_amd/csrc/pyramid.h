@@ -89,7 +89,7 @@ __host__ __device__ inline void pyr_zoom_axis(int X, int z, int n, int *i0, int 
     const int lg = z == 2 ? 2 : 3;                  // log2 D
     const int num = 2 * X + 1 - z;
     const int f = num >> lg;                        // floor(num / D): an arithmetic shift, also for num < 0
-    *w = num - (f << lg);
+    *w = num - f * (1 << lg);                       // (a multiply: f is -1 at the first pixels, and shifting a negative left is undefined)
     *i0 = f < 0 ? 0 : f > n - 1 ? n - 1 : f;
     *i1 = f + 1 < 0 ? 0 : f + 1 > n - 1 ? n - 1 : f + 1;
 }

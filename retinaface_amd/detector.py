@@ -16,7 +16,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (rf_face, rf_face_batch_spec, rf_face_gate, rf_face_quality, rf_options, rf_overlay_spec, rf_redact_spec, rf_tile_spec, rf_track,
-                   rf_dewarp_spec, rf_enhance_spec, rf_motion_spec, rf_pyramid_spec, rf_rot_spec, rf_shot, rf_track_motion, rf_track_spec, rf_track_tag, rf_tta_spec,
+                   rf_dewarp_spec, rf_enhance_spec, rf_roi, rf_roi_spec, rf_motion_spec, rf_pyramid_spec, rf_rot_spec, rf_shot, rf_track_motion, rf_track_spec, rf_track_tag, rf_tta_spec,
                    rf_follow_spec, rf_track_follow)
 
 PRECISION_FP32, PRECISION_FP16, PRECISION_INT8 = 0, 1, 2
@@ -1193,6 +1193,120 @@ class Dewarper:
         self._d = None
 
 
+ROI_CROPPED = _lib.RF_ROI_CROPPED
+
+
+def roi_spec(grid: int = 0, max_zoom: int = 0, vote: bool = False, max_faces: int = 0) -> rf_roi_spec:
+    """An rf_roi_spec: grid (cells per axis of a view: 1, 2 or 4; 0 = 4), max_zoom (the largest enlargement of a region: 1, 2 or 4;
+    0 = 2), vote (a kept box becomes the score-weighted mean of its cluster; off by default) and max_faces (0 = the engine's
+    max_detections)."""
+    sp = rf_roi_spec()
+    sp.struct_size = C.sizeof(rf_roi_spec)
+    sp.grid, sp.max_zoom, sp.vote, sp.max_faces, sp.reserved = int(grid), int(max_zoom), 1 if vote else 2, int(max_faces), 0
+    return sp
+
+
+def _roi_array(rois):
+    """a ctypes rf_roi array (at least one entry) of (x, y, w, h) rows, and their number"""
+    rows = [tuple(int(v) for v in r) for r in rois]
+    arr = (rf_roi * max(len(rows), 1))()
+    for i, (x, y, w, h) in enumerate(rows):
+        arr[i].x, arr[i].y, arr[i].w, arr[i].h = x, y, w, h
+    return arr, len(rows)
+
+
+def _roi_lists(rois_per_frame):
+    """the regions of a call's frames as (rf_roi array, frame-major; per-frame counts as a ctypes int array; the counts as a list)"""
+    counts = [len(r) for r in rois_per_frame]
+    arr, _ = _roi_array([r for frame in rois_per_frame for r in frame])
+    return arr, (C.c_int * max(len(counts), 1))(*counts), counts
+
+
+def roi_plan(rois, view_w: int, view_h: int, grid: int = 0, max_zoom: int = 0):
+    """rf_roi_plan (host only, no GPU): (cells, passes) of one frame's regions in views of view_w x view_h -- cells: an (n, 8) int32 array
+    of x, y, w, h, level (log2 of the step), x0, y0 (the cell's origin in level pixels) and flags (ROI_CROPPED)."""
+    lib = _lib.load_library()
+    arr, n = _roi_array(rois)
+    cells = (_lib.rf_roi_cell * max(n, 1))()
+    passes = C.c_int(0)
+    st = lib.rf_roi_plan(C.byref(roi_spec(grid, max_zoom)), int(view_w), int(view_h), arr, n, cells, C.byref(passes))
+    if st < 0:
+        raise _lib.RFError(st, "rf_roi_plan: bad spec, view size or region")
+    out = np.array([[c.roi.x, c.roi.y, c.roi.w, c.roi.h, c.level, c.x0, c.y0, c.flags] for c in cells[:n]], np.int32).reshape(n, 8)
+    return out, int(passes.value)
+
+
+def rois_from_faces(faces, coord_scale: float = 1.0, margin: Optional[float] = None):
+    """rf_roi_from_faces (host only, no GPU): the regions (x, y, w, h) of faces (Detections or rows of 15 floats) -- each box times
+    coord_scale, grown on every side by `margin` of its longer side (passed on in 1/256ths; None: the C default, a quarter), lower
+    edges floored, upper edges ceiled.  The C ABI reads a margin of 0 as its default, so a margin that rounds to 0 / 256 is refused
+    here rather than silently becoming a quarter.  A call's detections can so be handed to the next call as its regions."""
+    lib = _lib.load_library()
+    rows = _face_rows(faces)
+    n = len(rows)
+    q8 = 0 if margin is None else int(round(margin * 256))
+    if margin is not None and q8 == 0:
+        raise _lib.RFError(_lib.RF_ERR_INVALID_ARG, "rois_from_faces: a margin below 1 / 512 cannot be expressed (0 means the default); pass None for the default")
+    out = (rf_roi * max(n, 1))()
+    k = lib.rf_roi_from_faces(rows.ctypes.data_as(C.POINTER(rf_face)), n, float(coord_scale), q8, out)
+    if k < 0:
+        raise _lib.RFError(k, "rf_roi_from_faces: bad coord_scale or margin")
+    return [(out[i].x, out[i].y, out[i].w, out[i].h) for i in range(k)]
+
+
+def roi_atlas_host(frame: np.ndarray, rois, view_w: int, view_h: int, grid: int = 0, max_zoom: int = 0) -> np.ndarray:
+    """rf_roi_atlas_host (host only, no GPU): the views of one frame's regions, a (passes, view_h, view_w, 3) uint8 array."""
+    lib = _lib.load_library()
+    frame = _dense_frame(frame)
+    arr, n = _roi_array(rois)
+    g = int(grid) or 4
+    out = np.zeros((-(-n // (g * g)), int(view_h), int(view_w), 3), np.uint8)
+    st = lib.rf_roi_atlas_host(C.byref(roi_spec(grid, max_zoom)), int(view_w), int(view_h), frame.ctypes.data, frame.shape[0], frame.shape[1],
+                               frame.strides[0], arr, n, out.ctypes.data, 3 * int(view_w))
+    if st < 0:
+        raise _lib.RFError(st, "rf_roi_atlas_host: bad spec, view size, region or frame")
+    return out
+
+
+def roi_map_face(face, rois, pass_index: int, view_w: int, view_h: int, grid: int = 0, max_zoom: int = 0):
+    """rf_roi_map_face (host only, no GPU): the face (a Detection or 15 floats) of pass `pass_index` of one frame's regions moved into
+    the frame, (15 float32, its region) -- or None when the face rule drops it."""
+    lib = _lib.load_library()
+    arr, n = _roi_array(rois)
+    f, g = rf_face(), rf_face()
+    C.memmove(C.byref(f), _face_rows([face]).ctypes.data, 60)
+    region = C.c_int(0)
+    st = lib.rf_roi_map_face(C.byref(roi_spec(grid, max_zoom)), int(view_w), int(view_h), arr, n, int(pass_index), C.byref(f), C.byref(g),
+                             C.byref(region))
+    if st < 0:
+        raise _lib.RFError(st, "rf_roi_map_face: bad spec, view size, region or pass")
+    return (np.frombuffer(bytes(g)[:60], np.float32).copy(), int(region.value)) if st else None
+
+
+def roi_merge_host(passes, rois, view_w: int, view_h: int, nms_threshold: float, max_detections: int, grid: int = 0, max_zoom: int = 0,
+                   vote: bool = False, max_faces: int = 0, cap: Optional[int] = None):
+    """rf_roi_merge_host (host only, no GPU): face rule and merge of ONE frame -- passes[p]: the faces of pass p in score order.
+    Returns (faces (j, 15) float32, the true number of heads, votes (j,) int32, src_roi (j,) int32, truncated)."""
+    lib = _lib.load_library()
+    sp = roi_spec(grid, max_zoom, vote, max_faces)
+    md = int(max_detections)
+    if md < 1:
+        raise _lib.RFError(_lib.RF_ERR_INVALID_ARG, "rf_roi_merge_host: max_detections must be positive")
+    arr, n = _roi_array(rois)
+    flat, pc = _pack_passes(passes, md)
+    cap = int(cap) if cap is not None else (sp.max_faces or md)
+    out = (rf_face * max(cap, 1))()
+    votes, src = (C.c_int * max(cap, 1))(), (C.c_int * max(cap, 1))()
+    count = C.c_int(0)
+    st = lib.rf_roi_merge_host(C.byref(sp), int(view_w), int(view_h), arr, n, float(nms_threshold), md, flat.ctypes.data_as(C.POINTER(rf_face)),
+                               pc, out, cap, C.byref(count), votes, src)
+    if st < 0 and st != _lib.RF_ERR_TRUNCATED:
+        raise _lib.RFError(st, "rf_roi_merge_host: bad spec, view size, regions or counts")
+    k = min(count.value, cap, sp.max_faces or md)
+    return (_faces_to_array(out, max(cap, 1))[:k].copy(), int(count.value), np.array(votes[:k], np.int32), np.array(src[:k], np.int32),
+            st == _lib.RF_ERR_TRUNCATED)
+
+
 def enhance_spec(tile: int = 0, clip: int = 0, dark_below: int = 0) -> rf_enhance_spec:
     """An rf_enhance_spec: tile (the tile edge in pixels: 16, 32, 64 or 128; 0 = 64), clip (the contrast limit in 1/256ths of a tile's
     mean bin count, 256..65535; 0 = 2048), dark_below (a tile is enhanced only when its p99 luma is below this, 1..256; 0 = 64)."""
@@ -2104,6 +2218,61 @@ class RetinaFace:
         `step`, any alignment) into the destination (rows dst_step bytes apart, view_w * 3 bytes written).  Both in device memory."""
         _lib.check(self._lib.rf_dewarp_device(dewarper._d, int(view), src_ptr, int(step if step is not None else 3 * dewarper.cols), dst_ptr,
                                               int(dst_step if dst_step is not None else 3 * dewarper.view_w)), self._h)
+
+    # ------------------------------------------------------------------ region detection
+    def detect_rois(self, imgs: Sequence[np.ndarray], rois, threshold: float = 0.5, grid: int = 0, max_zoom: int = 0, vote: bool = False,
+                    max_faces: int = 0, return_src_roi: bool = False):
+        """rf_detect_roi_batch: every frame (None: an empty frame) is detected only in its regions -- rois[i]: frame i's (x, y, w, h)
+        list, at most 256 -- which are packed grid x grid to a net-sized view on the device, each at the largest power-of-two step
+        (x max_zoom .. x1/4) at which it fits its cell; the faces are moved back and merged on the device.  Returns per frame the
+        merged detections in SOURCE-FRAME pixels (anchor_index is -1); with return_src_roi also, per frame, how many candidates each
+        face merged and the region it came from.  self.roi_counts holds the true merged counts."""
+        f = _host_frames(imgs)
+        arr, rc, _ = _roi_lists(rois)
+        if len(rois) != len(imgs):
+            raise ValueError("rois: one list of regions per frame")
+        sp = roi_spec(grid, max_zoom, vote, max_faces)
+        head = (self._h,) + tuple(f.args) + (arr, rc, float(threshold), C.byref(sp))
+        return self._merged_call(self._lib.rf_detect_roi_batch, head, f.args[4], sp.max_faces or self.max_detections, "roi_counts", return_src_roi)
+
+    def detect_rois_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], rois, threshold: float = 0.5,
+                           steps: Optional[Sequence[int]] = None, grid: int = 0, max_zoom: int = 0, vote: bool = False, max_faces: int = 0,
+                           views_ptr: Optional[int] = None, return_src_roi: bool = False):
+        """rf_detect_roi_batch_device: detect_rois for frames resident in device memory (0 / None: an empty frame).  views_ptr: device
+        memory of passes * net_h * net_w * 3 bytes that receives the views as dense frames."""
+        if len(rois) != len(ptrs):
+            raise ValueError("rois: one list of regions per frame")
+        arr, rc, _ = _roi_lists(rois)
+        sp = roi_spec(grid, max_zoom, vote, max_faces)
+        head = (self._h,) + _device_frames(ptrs, rows, cols, steps) + (len(ptrs), arr, rc, float(threshold), C.byref(sp))
+        return self._merged_call(self._lib.rf_detect_roi_batch_device, head, len(ptrs), sp.max_faces or self.max_detections, "roi_counts",
+                                 return_src_roi, tail=(views_ptr,))
+
+    def roi_merge(self, rows: Sequence[int], cols: Sequence[int], rois, per_pass_faces, grid: int = 0, max_zoom: int = 0, vote: bool = False,
+                  max_faces: int = 0, cap_per_image: Optional[int] = None, return_src_roi: bool = False):
+        """rf_roi_merge_device: face rule and merge of per-pass faces the caller supplies -- per_pass_faces[i][p]: the faces of pass p
+        of frame i (a (j, 15) array, rows of 15 floats or Detections, at most max_detections), ceil(len(rois[i]) / grid^2) passes.
+        No forward pass runs.  Returns as detect_rois; self.roi_counts as there."""
+        n = len(rows)
+        sp = roi_spec(grid, max_zoom, vote, max_faces)
+        arr, rc, counts = _roi_lists(rois)
+        gg = (sp.grid or 4) ** 2
+        if len(rois) != n or len(per_pass_faces) != n or any(len(f) != -(-c // gg) for f, c in zip(per_pass_faces, counts)):
+            raise ValueError("per_pass_faces: one list of ceil(regions / grid^2) passes per frame")
+        flat, pc = _pack_passes([f for frame in per_pass_faces for f in frame], self.max_detections)
+        cap = int(cap_per_image) if cap_per_image is not None else (sp.max_faces or self.max_detections)
+        head = (self._h, (C.c_int * max(n, 1))(*rows), (C.c_int * max(n, 1))(*cols), n, arr, rc, C.byref(sp), flat.ctypes.data_as(C.POINTER(rf_face)), pc)
+        return self._merged_call(self._lib.rf_roi_merge_device, head, n, cap, "roi_counts", return_src_roi)
+
+    def roi_atlas_device(self, src_ptr: int, rows: int, cols: int, rois, dst_ptr: int, view_w: int, view_h: int, step: Optional[int] = None,
+                         dst_step: Optional[int] = None, grid: int = 0, max_zoom: int = 0):
+        """rf_roi_atlas_device: the atlas kernel on its own -- all passes of the regions of the BGR frame at src_ptr (row pitch `step`,
+        any alignment) into the destination: pass p's row y at dst_ptr + (p * view_h + y) * dst_step, view_w * 3 bytes written.  Both
+        in device memory."""
+        arr, n = _roi_array(rois)
+        _lib.check(self._lib.rf_roi_atlas_device(self._h, src_ptr, int(rows), int(cols), int(step if step is not None else 3 * cols), arr, n,
+                                                 C.byref(roi_spec(grid, max_zoom)), int(view_w), int(view_h), dst_ptr,
+                                                 int(dst_step if dst_step is not None else 3 * view_w)), self._h)
 
     # ------------------------------------------------------------------ low-light detection
     def detect_enhanced(self, imgs: Sequence[np.ndarray], threshold: float = 0.5, tile: int = 0, clip: int = 0, dark_below: int = 0,
