@@ -136,6 +136,16 @@ public:
     const vector<vector<int>> &roiRegions() const { return roiSrc_; }
     static vector<rf_roi> roisFromFaces(const vector<FaceDetectInfo> &faces, float coordScale = 1.f, int margin_q8 = 0);
 
+    /* additive: tracked region detection (rf_detect_track_roi_batch): the regions of frame i are planned on the device from the table
+       of stream streams[i] of `tracker` (slot r is region r; a free slot is a void cell; -1: no regions, no faces, no step), and the
+       merged faces go straight into the frame step -- "key frame (detectTracked), then regions around the faces of the last frame"
+       with no host step in between.  Fills lastBatchResult() (SOURCE-FRAME pixels), roiVotes(), roiRegions() (the slot whose region
+       found the face), lastTrackTags(), lastEndedTracks() and trackedRoiCells() (per frame the max_tracks records the device
+       planned).  margin_q8 0: a quarter of the longer side.  Each stream at most once per call. */
+    void detectTrackedRois(const vector<cv::Mat> &imgs, rf_tracker tracker, const vector<int> &streams, float threshold = 0.5,
+                           const rf_roi_spec *spec = nullptr, int margin_q8 = 0);
+    const vector<vector<rf_roi_cell>> &trackedRoiCells() const { return roiCells_; }
+
     /* additive: low-light detection (rf_detect_enhanced_batch): every frame is enhanced on the device (tile-adaptive contrast boost of
        dark tiles, rf_enhance_spec) and detected; the frames themselves are not written.  Fills lastBatchResult() with what the plain
        batch call returns for the enhanced frames; tilesEnhanced() holds, per frame, the number of tiles the enhancement touched
@@ -245,6 +255,7 @@ private:
     vector<int> frameRot_;
     vector<float> rotScore_;
     vector<vector<rf_track_tag>> trackTags_;
+    vector<vector<rf_roi_cell>> roiCells_;
     vector<vector<rf_track>> trackEnded_;
     vector<vector<int32_t>> redactPixels_;
     vector<vector<int32_t>> overlayPixels_;

@@ -1191,6 +1191,7 @@ int rf_dewarp_merge_device(rf_dewarper dewarper, int n, const rf_dewarp_spec *sp
  *            vote: 0 / 2 = off (the default), 1 = on.  max_faces, outputs and caps (RF_ERR_TRUNCATED) as for the TTA call. */
 #define RF_ROI_MAX_REGIONS 256
 #define RF_ROI_CROPPED 1
+#define RF_ROI_VOID 2       /* a cell without a region: every other field 0 (tracked region detection, below) */
 typedef struct rf_roi {
     int32_t x, y, w, h;
 } rf_roi;
@@ -1198,7 +1199,7 @@ typedef struct rf_roi_cell {
     rf_roi roi;
     int32_t level;          /* log2 of the step: 2, 1, 0, -1, -2 */
     int32_t x0, y0;         /* the cell's origin in level pixels */
-    int32_t flags;          /* RF_ROI_CROPPED */
+    int32_t flags;          /* RF_ROI_CROPPED, or RF_ROI_VOID alone */
 } rf_roi_cell;
 typedef struct rf_roi_spec {
     uint32_t struct_size;   /* sizeof(rf_roi_spec) */
@@ -1261,6 +1262,50 @@ int rf_detect_roi_batch(rf_handle h, const uint8_t *const *bgr, const int *rows,
 int rf_roi_merge_device(rf_handle h, const int *rows, const int *cols, int n, const rf_roi *rois, const int *roi_counts,
                         const rf_roi_spec *spec, const rf_face *faces, const int *pass_counts, rf_face *out, int cap_per_image, int *counts,
                         int *votes, int *src_roi);
+
+/* ---- Tracked region detection: the regions of a frame are planned ON THE DEVICE from a tracker's table, and the merged faces go
+ * straight into the frame step -- "key frame, then regions around the faces of the last frame" with no host synchronisation between the
+ * table and the tags (DESIGN.md "Tracked region detection" holds the definition; tests/roi_track_ref.py restates it in numpy):
+ *   slot = region   region r of an image is slot r of the image's stream, so every live tracked image has ceil(max_tracks / grid^2)
+ *            passes whatever the table holds; pass p has min(grid^2, max_tracks - p grid^2) cells.  A caller who wants one pass per
+ *            frame creates the tracker with max_tracks <= grid^2.
+ *   cell     a free slot gets the VOID record (every field 0, flags = RF_ROI_VOID).  A live slot's box is its track's `last` box, or
+ *            for a tracker with motion the predicted box the next frame step matches against; the region is rf_roi_from_faces' of that
+ *            box at coord_scale 1 and margin_q8 (0 = 64), the cell rf_roi_plan's.  A box rf_roi_from_faces would skip: void.
+ *   void     a void cell is zero pixels, addresses no source byte and drops every face whose centre falls in it.  rf_roi_atlas_host,
+ *            rf_roi_atlas_device and rf_roi_map_face take the void region {0, 0, 0, 0} in their lists from this version on; rf_roi_plan
+ *            and the region calls above refuse it as before and never produce a void record.
+ *   step     after the merge one frame step per image (rf_track_step, or rf_track_step_motion) runs over the merged faces in merge
+ *            order at coord_scale 1, m = min(count, max_faces, 256); nothing about the step changes -- a face found in slot s's region
+ *            is not forced onto slot s.  src_roi[k] is the slot whose region found face k, tags[k].slot the slot that claimed it.
+ *   frames   a NULL / 0 x 0 frame has no passes and no faces, its stream still takes a step and ages; an image of stream -1 has no
+ *            regions, no faces and no step.  Each stream may appear at most once per call.
+ * Refused before any state changes (RF_ERR_INVALID_ARG): a bad spec, a net that does not meet the cell rule, margin_q8 outside
+ * [0, 65535], a stream twice in the call, a tracker with a shot gallery or with follow (they do not compose yet), a tracker in the
+ * error state.  Multi-device handles: RF_ERR_UNSUPPORTED.
+ *
+ * rf_roi_cells_from_tracks (host only, no GPU, no handle): the max_tracks cell records of one stream's table -- the code the plan kernel
+ * runs.  spec (may be NULL) is checked only; motion NULL: a plain tracker, else max_tracks records read with mspec (NULL: its defaults).
+ * rf_roi_track_cells_device: the plan kernel alone over the tables of `tracker`: image i's max_tracks records at cells[i * max_tracks]
+ * (an image of stream -1: void records).  Synchronous; changes nothing.
+ * rf_detect_track_roi_batch_device / rf_detect_track_roi_batch: the fused call.  Frames, out, cap_per_image, counts, tracker,
+ * stream_of_image, tags, ended, cap_ended, ended_counts as rf_detect_track_batch*; votes, src_roi (may be NULL) and d_views (may be NULL:
+ * device memory of P * net_h * net_w * 3 bytes, P = ceil(max_tracks / grid^2) per live tracked frame, frame-major) as
+ * rf_detect_roi_batch_device; cells (may be NULL) receives the n * max_tracks records the device planned (void for images without
+ * passes).  Returns RF_ERR_TRUNCATED as the region call and the tracked calls do.  An error after the step was enqueued leaves the
+ * tracker in the error state until it is reset. */
+int rf_roi_cells_from_tracks(const rf_track_spec *spec, const rf_motion_spec *mspec, const rf_track *table, const rf_track_motion *motion,
+                             int max_tracks, int margin_q8, int net_w, int net_h, const rf_roi_spec *roi_spec, rf_roi_cell *cells);
+int rf_roi_track_cells_device(rf_handle h, rf_tracker tracker, const int *stream_of_image, int n, int margin_q8, const rf_roi_spec *roi_spec,
+                              rf_roi_cell *cells);
+int rf_detect_track_roi_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                     float threshold, const rf_roi_spec *roi_spec, int margin_q8, rf_face *out, int cap_per_image, int *counts,
+                                     int *src_roi, int *votes, rf_roi_cell *cells, void *d_views, rf_tracker tracker,
+                                     const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_counts);
+int rf_detect_track_roi_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n, float threshold,
+                              const rf_roi_spec *roi_spec, int margin_q8, rf_face *out, int cap_per_image, int *counts, int *src_roi, int *votes,
+                              rf_roi_cell *cells, void *d_views, rf_tracker tracker, const int *stream_of_image, rf_track_tag *tags,
+                              rf_track *ended, int cap_ended, int *ended_counts);
 
 /* ---- Zoom-pyramid detection: the smallest anchors are 16 px, so faces below about 16 px are not seen in a frame that already fits the
  * net.  A pyramid call detects every frame at 1x (the passes of its tile plan) and as net-sized tiles of the frame ENLARGED 2x and / or 4x

@@ -152,7 +152,7 @@ class rf_roi_spec(C.Structure):
                 ("reserved", C.c_int32)]
 
 
-RF_ROI_MAX_REGIONS, RF_ROI_CROPPED = 256, 1
+RF_ROI_MAX_REGIONS, RF_ROI_CROPPED, RF_ROI_VOID = 256, 1, 2
 
 
 class rf_enhance_spec(C.Structure):
@@ -392,6 +392,17 @@ SYMBOLS = {
                                       C.c_float, _PP(rf_roi_spec), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int)]),
     "rf_roi_merge_device": (C.c_int, [C.c_void_p, _PP(C.c_int), _PP(C.c_int), C.c_int, _PP(rf_roi), _PP(C.c_int), _PP(rf_roi_spec), _PP(rf_face),
                                       _PP(C.c_int), _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int)]),
+    "rf_roi_cells_from_tracks": (C.c_int, [_PP(rf_track_spec), _PP(rf_motion_spec), _PP(rf_track), _PP(rf_track_motion), C.c_int, C.c_int, C.c_int,
+                                           C.c_int, _PP(rf_roi_spec), _PP(rf_roi_cell)]),
+    "rf_roi_track_cells_device": (C.c_int, [C.c_void_p, C.c_void_p, _PP(C.c_int), C.c_int, C.c_int, _PP(rf_roi_spec), _PP(rf_roi_cell)]),
+    "rf_detect_track_roi_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int, C.c_float,
+                                                   _PP(rf_roi_spec), C.c_int, _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int),
+                                                   _PP(rf_roi_cell), C.c_void_p, C.c_void_p, _PP(C.c_int), _PP(rf_track_tag), _PP(rf_track), C.c_int,
+                                                   _PP(C.c_int)]),
+    "rf_detect_track_roi_batch": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int, C.c_float,
+                                            _PP(rf_roi_spec), C.c_int, _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int),
+                                            _PP(rf_roi_cell), C.c_void_p, C.c_void_p, _PP(C.c_int), _PP(rf_track_tag), _PP(rf_track), C.c_int,
+                                            _PP(C.c_int)]),
     "rf_enhance_host": (C.c_int, [_PP(rf_enhance_spec), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, _PP(C.c_int)]),
     "rf_enhance_device": (C.c_int, [C.c_void_p, _PP(rf_enhance_spec), _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
                                     _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int)]),

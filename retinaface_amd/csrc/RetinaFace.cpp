@@ -443,6 +443,50 @@ void RetinaFace::detectRois(const vector<cv::Mat> &imgs, const vector<vector<rf_
     }
 }
 
+void RetinaFace::detectTrackedRois(const vector<cv::Mat> &imgs, rf_tracker tracker, const vector<int> &streams, float threshold,
+                                   const rf_roi_spec *spec, int margin_q8) {
+    const int n = (int)imgs.size();
+    if ((int)streams.size() != n) throw std::runtime_error("RetinaFace::detectTrackedRois: one stream per image");
+    lastBatch_.assign(n, vector<FaceDetectInfo>());
+    roiVotes_.assign(n, vector<int>());
+    roiSrc_.assign(n, vector<int>());
+    trackTags_.assign(n, vector<rf_track_tag>());
+    trackEnded_.assign(n, vector<rf_track>());
+    roiCells_.assign(n, vector<rf_roi_cell>());
+    if (n == 0) return;
+    const int cap = spec && spec->max_faces > 0 ? spec->max_faces : maxDet_, capEnded = 256, maxTracks = 256;      // no list is ever cut
+    vector<const uint8_t *> ptrs(n);
+    vector<int> rows(n), cols(n), steps(n), counts(n, 0), endedCounts(n, 0);
+    for (int i = 0; i < n; i++) {
+        ptrs[i] = imgs[i].empty() ? nullptr : imgs[i].data;
+        rows[i] = imgs[i].rows; cols[i] = imgs[i].cols; steps[i] = (int)(size_t)imgs[i].step;
+    }
+    int T = 0;                                         // the tracker's max_tracks: what rf_tracker_read returns for cap 0
+    for (int i = 0; i < n && T == 0; i++)
+        if (streams[i] >= 0) T = rf_tracker_read(tracker, streams[i], nullptr, 0, nullptr, nullptr);
+    if (T < 0) check(T, h_, "RetinaFace::detectTrackedRois");
+    if (T == 0 || T > maxTracks) T = maxTracks;
+    vector<rf_face> faces((size_t)n * cap);
+    vector<int> votes((size_t)n * cap, 0), src((size_t)n * cap, 0);
+    vector<rf_track_tag> tags((size_t)n * cap);
+    vector<rf_track> ended((size_t)n * capEnded);
+    vector<rf_roi_cell> cells((size_t)n * T);
+    check(rf_detect_track_roi_batch(h_, ptrs.data(), rows.data(), cols.data(), steps.data(), n, threshold, spec, margin_q8, faces.data(), cap,
+                                    counts.data(), src.data(), votes.data(), cells.data(), nullptr, tracker, streams.data(), tags.data(),
+                                    ended.data(), capEnded, endedCounts.data()), h_, "RetinaFace::detectTrackedRois");
+    for (int i = 0; i < n; i++) {
+        const int k = counts[i] < cap ? counts[i] : cap;
+        lastBatch_[i].resize(k);
+        if (k) memcpy(lastBatch_[i].data(), &faces[(size_t)i * cap], (size_t)k * sizeof(rf_face));
+        roiVotes_[i].assign(votes.begin() + (size_t)i * cap, votes.begin() + (size_t)i * cap + k);
+        roiSrc_[i].assign(src.begin() + (size_t)i * cap, src.begin() + (size_t)i * cap + k);
+        trackTags_[i].assign(tags.begin() + (size_t)i * cap, tags.begin() + (size_t)i * cap + k);
+        const int e = endedCounts[i] < capEnded ? endedCounts[i] : capEnded;
+        trackEnded_[i].assign(ended.begin() + (size_t)i * capEnded, ended.begin() + (size_t)i * capEnded + e);
+        roiCells_[i].assign(cells.begin() + (size_t)i * T, cells.begin() + (size_t)(i + 1) * T);
+    }
+}
+
 vector<rf_roi> RetinaFace::roisFromFaces(const vector<FaceDetectInfo> &faces, float coordScale, int margin_q8) {
     static_assert(sizeof(FaceDetectInfo) == sizeof(rf_face), "a FaceDetectInfo is an rf_face");
     vector<rf_roi> out(faces.size());

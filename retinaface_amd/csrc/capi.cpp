@@ -1706,18 +1706,21 @@ int rf_dewarp_merge_device(rf_dewarper dewarper, int n, const rf_dewarp_spec *sp
 // ---- region detection (roi.h)
 namespace {
 // the host entry points' common checks: the spec (max_faces irrelevant where nothing is merged), the view and the regions
-int roi_host_args(const rf_roi_spec *spec, int default_max_faces, int view_w, int view_h, const rf_roi *rois, int n, rf::RoiSpec *sp) {
+// (allow_void: the entry point takes the void region, four zeros, which stands for the void record)
+int roi_host_args(const rf_roi_spec *spec, int default_max_faces, int view_w, int view_h, const rf_roi *rois, int n, rf::RoiSpec *sp,
+                  bool allow_void = false) {
     if (rf::roi_spec_resolve(spec, default_max_faces, sp)) return RF_ERR_INVALID_ARG;
     if (rf::roi_check_view(view_w, view_h, sp->grid)) return RF_ERR_INVALID_ARG;
     if (n < 0 || n > rf::kRoiMaxRegions || (n > 0 && !rois)) return RF_ERR_INVALID_ARG;
     for (int r = 0; r < n; r++)
-        if (!rf::roi_valid(rois[r])) return RF_ERR_INVALID_ARG;
+        if (!rf::roi_valid(rois[r]) && !(allow_void && rf::roi_is_void(rois[r]))) return RF_ERR_INVALID_ARG;
     return RF_OK;
 }
 
 void roi_cells_of(const rf::RoiSpec &sp, int view_w, int view_h, const rf_roi *rois, int n, std::vector<rf::RoiCell> *cells) {
     cells->resize((size_t)n);
-    for (int r = 0; r < n; r++) (*cells)[r] = rf::roi_plan(rois[r], view_w / sp.grid, view_h / sp.grid, sp.max_zoom);
+    for (int r = 0; r < n; r++)
+        (*cells)[r] = rf::roi_is_void(rois[r]) ? rf::roi_void_cell() : rf::roi_plan(rois[r], view_w / sp.grid, view_h / sp.grid, sp.max_zoom);
 }
 }  // namespace
 
@@ -1745,7 +1748,7 @@ int rf_roi_from_faces(const rf_face *faces, int n, float coord_scale, int margin
 int rf_roi_atlas_host(const rf_roi_spec *spec, int view_w, int view_h, const uint8_t *src, int rows, int cols, int step, const rf_roi *rois,
                       int n, uint8_t *dst, int dst_step) {
     rf::RoiSpec sp;
-    if (roi_host_args(spec, 1, view_w, view_h, rois, n, &sp)) return RF_ERR_INVALID_ARG;
+    if (roi_host_args(spec, 1, view_w, view_h, rois, n, &sp, true)) return RF_ERR_INVALID_ARG;
     if (!src || !dst || rows <= 0 || cols <= 0 || rows > 4096 * 3072 / cols || step < cols * 3 || dst_step < view_w * 3) return RF_ERR_INVALID_ARG;
     std::vector<rf::RoiCell> c;
     roi_cells_of(sp, view_w, view_h, rois, n, &c);
@@ -1759,7 +1762,7 @@ int rf_roi_atlas_host(const rf_roi_spec *spec, int view_w, int view_h, const uin
 int rf_roi_map_face(const rf_roi_spec *spec, int view_w, int view_h, const rf_roi *rois, int n, int pass, const rf_face *in, rf_face *out,
                     int *region) {
     rf::RoiSpec sp;
-    if (!in || !out || roi_host_args(spec, 1, view_w, view_h, rois, n, &sp)) return RF_ERR_INVALID_ARG;
+    if (!in || !out || roi_host_args(spec, 1, view_w, view_h, rois, n, &sp, true)) return RF_ERR_INVALID_ARG;
     if (pass < 0 || pass >= rf::roi_passes(n, sp.grid)) return RF_ERR_INVALID_ARG;
     std::vector<rf::RoiCell> c;
     roi_cells_of(sp, view_w, view_h, rois, n, &c);
@@ -1861,6 +1864,72 @@ int rf_detect_roi_batch(rf_handle h, const uint8_t *const *bgr, const int *rows,
                         int *votes, int *src_roi) {
     return detect_roi_common(h, bgr, rows, cols, steps, n, false, rois, roi_counts, threshold, spec, out, cap_per_image, counts, votes, src_roi,
                              nullptr);
+}
+
+// ---- tracked region detection (roi.h roi_track_cell)
+int rf_roi_cells_from_tracks(const rf_track_spec *spec, const rf_motion_spec *mspec, const rf_track *table, const rf_track_motion *motion,
+                             int max_tracks, int margin_q8, int net_w, int net_h, const rf_roi_spec *roi_spec, rf_roi_cell *cells) {
+    rf::TrackSpec ts;
+    rf::MotionSpec ms;
+    rf::RoiSpec sp;
+    if (rf::track_spec_resolve(spec, &ts) || rf::motion_spec_resolve(mspec, &ms) || rf::roi_spec_resolve(roi_spec, 1, &sp)) return RF_ERR_INVALID_ARG;
+    if (rf::roi_check_view(net_w, net_h, sp.grid)) return RF_ERR_INVALID_ARG;
+    if (max_tracks < 1 || max_tracks > rf::kTrackMaxTracks || margin_q8 < 0 || margin_q8 > 65535 || !table || !cells) return RF_ERR_INVALID_ARG;
+    rf::roi_cells_from_tracks(table, motion, ms, max_tracks, margin_q8, net_w / sp.grid, net_h / sp.grid, sp.max_zoom, cells);
+    return RF_OK;
+}
+
+int rf_roi_track_cells_device(rf_handle h, rf_tracker tracker, const int *stream_of_image, int n, int margin_q8, const rf_roi_spec *roi_spec,
+                              rf_roi_cell *cells) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        if (h->eng->num_devices() > 1) throw rf::Unsupported("region detection is not available on a multi-device handle");
+        rf::RoiTrackRequest rq;
+        if (const char *bad = rf::roi_spec_resolve(roi_spec, h->eng->default_max_faces(), &rq.spec)) throw rf::ArgError(bad);
+        rq.margin_q8 = margin_q8;
+        rf::TrackRequest trq;
+        track_request(h, tracker, stream_of_image, nullptr, nullptr, 0, nullptr, &trq);
+        h->eng->roi_track_cells(trq, n, rq, cells);
+        return RF_OK;
+    });
+}
+
+namespace {
+int detect_track_roi_common(rf_handle h, const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,
+                            float thr, const rf_roi_spec *roi_spec, int margin_q8, rf_face *out, int cap, int *counts, int *src_roi, int *votes,
+                            rf_roi_cell *cells, void *d_views, rf_tracker tracker, const int *stream_of_image, rf_track_tag *tags,
+                            rf_track *ended, int cap_ended, int *ended_counts) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded_caps(h, [&](bool *tr) -> int {
+        if (h->eng->num_devices() > 1) throw rf::Unsupported("region detection is not available on a multi-device handle");
+        rf::RoiTrackRequest rq;
+        if (const char *bad = rf::roi_spec_resolve(roi_spec, h->eng->default_max_faces(), &rq.spec)) throw rf::ArgError(bad);
+        rq.margin_q8 = margin_q8;
+        rq.votes = votes; rq.src_roi = src_roi; rq.cells = cells; rq.d_views = d_views;
+        rf::TrackRequest trq;
+        track_request(h, tracker, stream_of_image, tags, ended, cap_ended, ended_counts, &trq);
+        bool cut = false;
+        h->eng->detect_track_rois(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, tr, rq, trq, &cut);
+        if (cut) { h->error = kTrackCut; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+}  // namespace
+
+int rf_detect_track_roi_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                     float threshold, const rf_roi_spec *roi_spec, int margin_q8, rf_face *out, int cap_per_image, int *counts,
+                                     int *src_roi, int *votes, rf_roi_cell *cells, void *d_views, rf_tracker tracker,
+                                     const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_counts) {
+    return detect_track_roi_common(h, (const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, roi_spec, margin_q8, out, cap_per_image,
+                                   counts, src_roi, votes, cells, d_views, tracker, stream_of_image, tags, ended, cap_ended, ended_counts);
+}
+
+int rf_detect_track_roi_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n, float threshold,
+                              const rf_roi_spec *roi_spec, int margin_q8, rf_face *out, int cap_per_image, int *counts, int *src_roi, int *votes,
+                              rf_roi_cell *cells, void *d_views, rf_tracker tracker, const int *stream_of_image, rf_track_tag *tags,
+                              rf_track *ended, int cap_ended, int *ended_counts) {
+    return detect_track_roi_common(h, bgr, rows, cols, steps, n, false, threshold, roi_spec, margin_q8, out, cap_per_image, counts, src_roi, votes,
+                                   cells, d_views, tracker, stream_of_image, tags, ended, cap_ended, ended_counts);
 }
 
 int rf_roi_merge_device(rf_handle h, const int *rows, const int *cols, int n, const rf_roi *rois, const int *roi_counts,

@@ -1434,8 +1434,8 @@ public:
                    void *d_dst, int dst_step) override {
         if (const char *bad = roi_check_view(view_w, view_h, sp.grid)) throw ArgError(std::string("region atlas: ") + bad);
         if (n < 0 || n > kRoiMaxRegions || (n > 0 && !rois)) throw ArgError("region atlas: 0 to 256 regions");
-        for (int r = 0; r < n; r++)
-            if (!roi_valid(rois[r])) throw ArgError("region atlas: a region's w, h must be in [1, 16384], |x|, |y| at most 2^20");
+        for (int r = 0; r < n; r++)                                // (four zeros: the void region, whose cell is the void record)
+            if (!roi_valid(rois[r]) && !roi_is_void(rois[r])) throw ArgError("region atlas: a region's w, h must be in [1, 16384], |x|, |y| at most 2^20");
         if (!d_dst || dst_step < view_w * 3) throw ArgError("region atlas: null destination or dst_step < view_w * 3");
         check_frame((const uint8_t *)d_src, rows, cols, step);
         if (!d_src || rows <= 0 || cols <= 0) throw ArgError("null argument");
@@ -1443,7 +1443,8 @@ public:
         DeviceGuard guard(device_);
         const int GG = sp.grid * sp.grid, P = roi_passes(n, sp.grid);
         std::vector<RoiCell> cells;
-        for (int r = 0; r < n; r++) cells.push_back(roi_plan(rois[r], view_w / sp.grid, view_h / sp.grid, sp.max_zoom));
+        for (int r = 0; r < n; r++)
+            cells.push_back(roi_is_void(rois[r]) ? roi_void_cell() : roi_plan(rois[r], view_w / sp.grid, view_h / sp.grid, sp.max_zoom));
         if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
         const RoiCell *d = (const RoiCell *)roi_cells_.reserve(cells.size() * sizeof(RoiCell));
         RF_HIP(hipMemcpy(roi_cells_.ptr, cells.data(), cells.size() * sizeof(RoiCell), hipMemcpyHostToDevice));
@@ -1524,6 +1525,164 @@ public:
         merge_passes(entries, n, faces, pass_counts, truncated, [&] { tta_open(n, mrq.spec); },
                      gather_into<RoiMap>(0, tta_cand_, tta_count_, kTtaMergeCap), vote_merge_of(n, mrq.spec), tta_dirty_);
         tta_copy_out(n, mrq, out, cap_per_image, counts, truncated);
+    }
+
+    // -------------------------------------------------------------------------------- tracked region detection
+private:
+    struct Tracker;
+public:
+    // The arguments of a tracked region call, checked before any state changes: the cell rule, the margin, the tracker (no gallery, no
+    // follow, not in the error state: track_check), and every stream at most once -- the cells of a call are planned before any of its
+    // steps runs, so a second image of a stream would be planned from a table the first has yet to step.
+    Tracker &roi_track_check(const TrackRequest &trq, int n, const RoiTrackRequest &rq) {
+        if (const char *bad = roi_check_view(net_w_, net_h_, rq.spec.grid)) throw ArgError(std::string("region detection: ") + bad);
+        if (rq.margin_q8 < 0 || rq.margin_q8 > 65535) throw ArgError("region detection: margin_q8 must be in [0, 65535]");
+        if (n < 0) throw ArgError("null argument");
+        Tracker &t = track_check(trq, n);
+        std::vector<int> seen;
+        for (int i = 0; i < n; i++)
+            if (trq.stream_of_image[i] >= 0) seen.push_back(trq.stream_of_image[i]);
+        std::sort(seen.begin(), seen.end());
+        if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) throw ArgError("tracked region detection: a stream appears more than once in the call");
+        return t;
+    }
+
+    // The plan launch of a call on the side stream: plans[i] = the stream whose table plans image i, or -1 (stream -1, a frame without
+    // pixels); the table travels in a pinned block the kernel reads.  Returns the records' device block, n * max_tracks of them.
+    RoiCell *roi_track_plan(const Tracker &t, const RoiTrackRequest &rq, const int *plans, int n, size_t pin_extra, uint8_t **pin_tail) {
+        const size_t o_tail = align256((size_t)std::max(n, 1) * sizeof(int32_t));
+        uint8_t *pin = roi_cells_pin_.reserve(o_tail + pin_extra);
+        memcpy(pin, plans, (size_t)n * sizeof(int32_t));
+        if (pin_tail) *pin_tail = pin + o_tail;
+        RoiCell *d = (RoiCell *)roi_cells_.reserve((size_t)std::max(n, 1) * t.spec.max_tracks * sizeof(RoiCell));
+        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+        RoiTrackCellsParams cp;
+        memset((void *)&cp, 0, sizeof(cp));
+        cp.streams = (const int32_t *)pin; cp.n = n;
+        cp.spec = t.spec;
+        cp.state = t.state.ptr;
+        if (t.has_motion) { cp.motion = (const rf_track_motion *)t.motion.ptr; cp.mspec = t.motion_spec; }
+        cp.margin_q8 = rq.margin_q8; cp.cw = net_w_ / rq.spec.grid; cp.ch = net_h_ / rq.spec.grid; cp.max_zoom = rq.spec.max_zoom;
+        cp.cells = d;
+        launch_roi_track_cells(align_stream_, cp);
+        RF_HIP(hipGetLastError());
+        return d;
+    }
+
+    // the planned records of a finished call to the host: what the kernel wrote, the void record for the images it skipped
+    void roi_track_cells_out(const RoiCell *d_cells, const int *plans, int n, int T, rf_roi_cell *cells) {
+        if (!cells || n == 0) return;
+        RF_HIP(hipMemcpy(cells, d_cells, (size_t)n * T * sizeof(RoiCell), hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; i++)
+            if (plans[i] < 0)
+                for (int s = 0; s < T; s++) cells[(size_t)i * T + s] = roi_void_cell();
+    }
+
+    void roi_track_cells(const TrackRequest &trq, int n, const RoiTrackRequest &rq, rf_roi_cell *cells) override {
+        Tracker &t = roi_track_check(trq, n, rq);
+        if (n > 0 && !cells) throw ArgError("null argument");
+        if (n == 0) return;
+        DeviceGuard guard(device_);
+        std::vector<int> plans((size_t)n);
+        for (int i = 0; i < n; i++) plans[i] = trq.stream_of_image[i];
+        const RoiCell *d = roi_track_plan(t, rq, plans.data(), n, 0, nullptr);
+        RF_HIP(hipStreamSynchronize(align_stream_));
+        roi_track_cells_out(d, plans.data(), n, t.spec.max_tracks, cells);
+    }
+
+    // A seventh user of the pass-call skeleton.  On the side stream, in order: the plan launch, the atlas launches (their `cells` are
+    // device addresses the plan launch fills; sized for the x1/4 level, which the host cannot rule out), inputs_ready.  Then the passes
+    // with the region gather, and behind the vote merge, on its stream, the track launch over the merged faces (source pixels, score
+    // order) in the merge's device-visible output blocks.  The tracked calls are synchronous, so the table the plan kernel reads is
+    // settled when the call starts.  An error after the step was enqueued leaves the tracker in the error state.
+    void detect_track_rois(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device, float threshold,
+                           rf_face *out, int cap_per_image, int *counts, bool *truncated, const RoiTrackRequest &rq, const TrackRequest &trq,
+                           bool *cut) override {
+        *truncated = false;
+        *cut = false;
+        TtaRequest mrq;
+        mrq.spec.flip = 0; mrq.spec.vote = rq.spec.vote; mrq.spec.max_faces = rq.spec.max_faces;
+        mrq.votes = rq.votes; mrq.src_pass = rq.src_roi;
+        pass_check_args(n, frames, rows, cols, counts, out, cap_per_image, mrq.spec.max_faces);
+        if (cap_per_image < 1 && trq.tags) throw ArgError("cap_per_image must be >= 1");
+        std::vector<int> st = checked_steps(frames, rows, cols, steps, n);
+        Tracker &t = roi_track_check(trq, n, rq);
+        for (int i = 0; i < n; i++) counts[i] = 0;
+        if (n == 0) return;
+        const int T = t.spec.max_tracks, G = rq.spec.grid, GG = G * G, PP = roi_passes(T, G);
+        std::vector<int> plans((size_t)n);
+        std::vector<char> empty((size_t)n);
+        for (int i = 0; i < n; i++) {
+            empty[i] = !frames[i] || rows[i] <= 0 || cols[i] <= 0;
+            plans[i] = empty[i] ? -1 : trq.stream_of_image[i];
+        }
+        DeviceGuard guard(device_);
+        const std::vector<const uint8_t *> base = pass_frame_bases(frames, rows, cols, st, n, on_device, [&](int i) { return plans[i] >= 0; });
+        launch_pending();
+        // the pinned block: plans | stream table | image table (the track kernel reads both tables from pinned memory)
+        uint8_t *tail = nullptr;
+        const size_t o_img = align256((size_t)n * sizeof(TrackStreamEntry));
+        const RoiCell *d_cells = roi_track_plan(t, rq, plans.data(), n, o_img + (size_t)n * sizeof(TrackImageEntry), &tail);
+        TrackStreamEntry *se = (TrackStreamEntry *)tail;
+        TrackImageEntry *ie = (TrackImageEntry *)(tail + o_img);
+        const std::vector<float> scale((size_t)n, 1.f);
+        const int ns = track_build_table(trq.stream_of_image, 0, n, scale.data(), empty.data(), se, ie);
+        // the passes: PP per live tracked frame, frame-major
+        std::vector<RoiEntry> entries;
+        for (int i = 0; i < n; i++) {
+            if (plans[i] < 0) continue;
+            for (int p = 0; p < PP; p++) {
+                RoiEntry e;
+                memset(&e, 0, sizeof(e));
+                e.frame = i; e.pass = p; e.rows = rows[i]; e.cols = cols[i]; e.grid = G; e.used = std::min(GG, T - p * GG);
+                e.net_w = net_w_; e.net_h = net_h_;
+                e.cells = d_cells + (size_t)i * T + (size_t)p * GG;
+                entries.push_back(e);
+            }
+        }
+        const int P = (int)entries.size();
+        const size_t vb = (size_t)net_w_ * net_h_ * 3;
+        uint8_t *d_views = rq.d_views ? (uint8_t *)rq.d_views : roi_views_.reserve(vb * (size_t)std::max(P, 1));
+        PassViews v(P);
+        std::vector<RoiAtlasParams> ap;
+        for (int q = 0; q < P; q++) {
+            const RoiEntry &e = entries[q];
+            uint8_t *dst = d_views + vb * (size_t)q;
+            ap.push_back(RoiAtlasParams{base[e.frame], e.rows, e.cols, st[e.frame], e.cells, e.used, e.grid, net_w_, net_h_, dst, net_w_ * 3, -2});
+            v.set(q, dst, net_h_, net_w_, net_w_ * 3);
+        }
+        hipEvent_t packed = nullptr;
+        if (P) {
+            launch_roi_views(align_stream_, ap.data(), P);
+            packed = record_inputs_ready();
+        }
+        tta_open(n, mrq.spec);
+        track_open_call(t, trq, n, cap_per_image);
+        TrackParams tp = track_params(t);
+        tp.streams = se; tp.n_streams = ns;
+        tp.images = ie;
+        tp.faces = tta_out_.ptr; tp.face_stride = (int)sizeof(Candidate); tp.faces_per_image = mrq.spec.max_faces;
+        tp.counts = (const int *)tta_outcount_.ptr;
+        tp.records = nullptr;
+        tp.max_faces = mrq.spec.max_faces;
+        t.dirty = true;                                // until track_copy_out() has run
+        if (P) {
+            const TtaSpec msp = mrq.spec;
+            auto merge = [=](hipStream_t s, const RunParams *d_params) {
+                tta_launch_merge(s, n, msp, d_params);
+                if (ns > 0) launch_track(s, tp);
+            };
+            *truncated = run_passes("tracked region detection", entries, v, threshold, packed,
+                                    gather_into<RoiMap>(0, tta_cand_, tta_count_, kTtaMergeCap), merge, tta_dirty_);
+            tta_copy_out(n, mrq, out, cap_per_image, counts, truncated);
+        } else {                                       // no image has a pass: the streams of the frames without pixels still step and age
+            RF_HIP(hipStreamSynchronize(align_stream_));
+            if (ns > 0) launch_track(align_stream_, tp);
+            RF_HIP(hipGetLastError());
+            RF_HIP(hipStreamSynchronize(align_stream_));
+        }
+        track_copy_out(t, trq, n, cap_per_image, counts, cut);
+        roi_track_cells_out(d_cells, plans.data(), n, T, rq.cells);
     }
 
     // -------------------------------------------------------------------------------- low-light enhancement
@@ -1768,9 +1927,6 @@ public:
     float track_last_launch_ms() const override { return trk_launch_ms_; }
 
     // -------------------------------------------------------------------------------- best-shot gallery
-private:
-    struct Tracker;
-public:
     void tracker_enable_shots(void *p, const FaceBatchSpec &spec) override {
         Tracker &t = tracker_of(p);
         FaceBatchRequest probe;

@@ -149,6 +149,18 @@ struct RoiRequest {
     void *d_views = nullptr;                    // P * net_h * net_w * 3 bytes, dense, frame-major
 };
 
+// A tracked region call (roi.h; rf_detect_track_roi_batch* / rf_roi_track_cells_device): the validated spec, the margin the tracks'
+// boxes are grown by (in 1/256ths; 0 = 64), where the member count and the slot of each merged face go, where the n * max_tracks cell
+// records the device planned go (host, or nullptr) and where the views go (device memory; nullptr: an engine-owned block)
+struct RoiTrackRequest {
+    RoiSpec spec;
+    int margin_q8 = 0;
+    int *votes = nullptr;
+    int *src_roi = nullptr;
+    rf_roi_cell *cells = nullptr;
+    void *d_views = nullptr;                    // P * net_h * net_w * 3 bytes, dense, frame-major; P: roi_passes(max_tracks, grid) per live tracked frame
+};
+
 // An enhanced detection call (enhance.h; rf_detect_enhanced_batch*): the validated spec, where the enhanced copies go (device memory;
 // nullptr: an engine-owned block) and where the number of flagged tiles of each frame goes
 struct EnhanceRequest {
@@ -336,6 +348,15 @@ public:
     }
     // the atlas kernel on its own: all passes of n regions of a device-resident frame, pass p at d_dst + p * view_h * dst_step
     virtual void roi_atlas(const void *, int, int, int, const rf_roi *, int, const RoiSpec &, int, int, void *, int) {
+        throw Unsupported("region detection is not available on a multi-device handle");
+    }
+    // Tracked region detection: the plan kernel alone (image i's max_tracks records at cells + i * max_tracks; stream -1: void records),
+    // and the fused call -- regions planned on the device from the tracker's tables, the frame steps behind the merge
+    virtual void roi_track_cells(const TrackRequest &, int, const RoiTrackRequest &, rf_roi_cell *) {
+        throw Unsupported("region detection is not available on a multi-device handle");
+    }
+    virtual void detect_track_rois(const uint8_t *const *, const int *, const int *, const int *, int, bool, float, rf_face *, int, int *, bool *,
+                                   const RoiTrackRequest &, const TrackRequest &, bool *) {
         throw Unsupported("region detection is not available on a multi-device handle");
     }
     // Low-light enhancement: the two enhance kernels over frames in device memory (synchronous), and the fused call -- the enhanced

@@ -527,6 +527,20 @@ struct RoiAtlasParams {
 constexpr int kRoiViewsPerLaunch = 16;           // views of one launch: their descriptors travel as kernel arguments
 constexpr int kRoiTileW = 64, kRoiTileH = 16;
 void launch_roi_views(hipStream_t s, const RoiAtlasParams *views, int n);
+//      roi_track_cells: the cell records of a tracked region call, planned from the tracker's tables (roi.h roi_track_cell): one thread
+//                  per (image of the call, slot) writes image i's max_tracks records at cells + i * max_tracks; an image whose
+//                  stream is < 0 (stream -1, or a frame without pixels: it has no passes) gets nothing written.  Views made from
+//                  such records carry min_level = -2: the host cannot know their levels, so the launch is sized for x1/4.
+struct RoiTrackCellsParams {
+    const int32_t *streams; int n;                // [n] the stream whose table plans image i, or < 0; device-visible
+    TrackSpec spec;
+    const uint8_t *state;                         // as TrackArgs
+    const rf_track_motion *motion;                // as TrackParams, or nullptr: a plain tracker
+    MotionSpec mspec;
+    int margin_q8, cw, ch, max_zoom;
+    RoiCell *cells;                               // device memory, n * max_tracks records
+};
+void launch_roi_track_cells(hipStream_t s, const RoiTrackCellsParams &p);
 
 // ---- K_k: zoom-pyramid detection (pyramid.h).
 //      zoom_tile:  windows of frames enlarged 2x / 4x (integer bilinear, pyr_zoom_pixel) written as dense frames, in front of a

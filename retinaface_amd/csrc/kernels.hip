@@ -6473,7 +6473,7 @@ void launch_dewarp_views(hipStream_t s, const DewarpParams *views, int n) {
 //      (pyr_zoom_pixel), x1/2 / x1/4 average the k x k source block; the taps are gathered from global memory -- a tile's footprint in
 //      the source is an axis-aligned rectangle whose rows neighbouring threads share, so they come from the cache.  The twelve bytes
 //      go out as rotate_frames_kernel stores them: three dwords where the destination is dword aligned, bytewise elsewhere; a wave
-//      writes four rows of 192 contiguous bytes.  A cell without a region is written as zeros.  The shrunk levels of a tile whose
+//      writes four rows of 192 contiguous bytes.  A cell without a region, or with the void record, is written as zeros.  The shrunk levels of a tile whose
 //      source box lies inside the frame go through roi_shrink_staged instead (the box copied into LDS with dword loads, measured
 //      1.3 x and 1.7 x faster per output byte at x1/2 and x1/4); the gather is their path at the border.  No byte outside the view_w * 3 bytes
 //      of a row is written, no source byte outside rows x cols is read (a level pixel outside the level image is 0 and addresses
@@ -6557,10 +6557,12 @@ __global__ __launch_bounds__(kThreads) void roi_atlas_kernel(RoiBatch batch) {
         bool staged = false;
         if (cell < a.used) {
             const RoiCell c = a.cells[cell];
-            if (c.level == -1) staged = roi_shrink_staged<1>(a, c, batch.lds_bytes, i0, j0, tw, th, active, q, r, b);
-            else if (c.level == -2) staged = roi_shrink_staged<2>(a, c, batch.lds_bytes, i0, j0, tw, th, active, q, r, b);
-            if (!staged && active)
-                for (int k = 0; k < 4; k++) roi_cell_pixel(a.src, a.rows, a.cols, (size_t)a.step, c, i + k, j, b + 3 * k);
+            if (!roi_cell_is_void(c)) {                                  // uniform: a void cell stays zero, no staged path, no source read
+                if (c.level == -1) staged = roi_shrink_staged<1>(a, c, batch.lds_bytes, i0, j0, tw, th, active, q, r, b);
+                else if (c.level == -2) staged = roi_shrink_staged<2>(a, c, batch.lds_bytes, i0, j0, tw, th, active, q, r, b);
+                if (!staged && active)
+                    for (int k = 0; k < 4; k++) roi_cell_pixel(a.src, a.rows, a.cols, (size_t)a.step, c, i + k, j, b + 3 * k);
+            }
         }
         if (active) {
             const uint32_t o0 = b[0] | (uint32_t)b[1] << 8 | (uint32_t)b[2] << 16 | (uint32_t)b[3] << 24;
@@ -6593,6 +6595,35 @@ void launch_roi_views(hipStream_t s, const RoiAtlasParams *views, int n) {
         if (!blocks) continue;
         hipLaunchKernelGGL(roi_atlas_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536), (unsigned)m), dim3(kThreads), (size_t)b.lds_bytes, s, b);
     }
+}
+
+// roi_track_cells_kernel: the cell records of a tracked region call.  One thread per (image, slot): it reads its slot's record from the
+//      stream's table in the tracker's state block (and its motion record where the tracker has motion), runs roi_track_cell -- the code
+//      rf_roi_cells_from_tracks runs; fp64 only inside roi_from_face -- and writes the 32-byte record as two 16-byte stores.  Images
+//      whose stream is < 0 write nothing.  Bounds: gid < n * max_tracks; stream < the tracker's streams (checked by the host).
+__global__ __launch_bounds__(kThreads) void roi_track_cells_kernel(RoiTrackCellsParams a) {
+    const int T = a.spec.max_tracks;
+    const long long gid = (long long)blockIdx.x * kThreads + (long long)threadIdx.x;
+    if (gid >= (long long)a.n * T) return;
+    const int image = (int)(gid / T), slot = (int)(gid - (long long)image * T);
+    const int stream = a.streams[image];
+    if (stream < 0) return;
+    const rf_track *table = (const rf_track *)(a.state + (size_t)stream * (sizeof(TrackHeader) + (size_t)T * sizeof(rf_track)) + sizeof(TrackHeader));
+    const rf_track_motion *m = a.motion ? a.motion + (size_t)stream * T + slot : nullptr;
+    const RoiCell c = roi_track_cell(table[slot], m, a.mspec, a.margin_q8, a.cw, a.ch, a.max_zoom);
+    int4 *dst = (int4 *)(a.cells + (size_t)image * T + slot);
+    dst[0] = make_int4(c.roi.x, c.roi.y, c.roi.w, c.roi.h);
+    dst[1] = make_int4(c.level, c.x0, c.y0, c.flags);
+}
+
+void launch_roi_track_cells(hipStream_t s, const RoiTrackCellsParams &p) {
+    const int T = p.spec.max_tracks;
+    if (p.n <= 0) return;
+    if (T < 1 || T > kTrackMaxTracks || !p.streams || !p.state || !p.cells || p.cw < 4 || p.ch < 1 || p.margin_q8 < 0 || p.margin_q8 > 65535 ||
+        ((uintptr_t)p.cells & 15))
+        throw std::invalid_argument("launch_roi_track_cells: a table, the cell size, the margin or the cell block is not valid");
+    const long long threads = (long long)p.n * T;
+    hipLaunchKernelGGL(roi_track_cells_kernel, dim3((unsigned)((threads + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, p);
 }
 
 // =============================================================================================

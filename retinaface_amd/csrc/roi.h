@@ -7,6 +7,13 @@
 // voting merge of tta.h (DESIGN.md "Region detection").  The pixels are integer arithmetic; the mapping is one fp32 add and at most
 // one exact fp32 multiply and one fp32 add per coordinate, never contracted, so host and device agree bit for bit with each other
 // and with tests/roi_ref.py.
+//
+// Tracked region detection (DESIGN.md "Tracked region detection"; tests/roi_track_ref.py): the regions of a frame are planned from a
+// tracker's table, on the device by roi_track_cells_kernel and on the host by rf_roi_cells_from_tracks, both through roi_track_cell
+// below.  Slot = region: region r of an image is slot r of the image's stream, so every image has roi_passes(max_tracks, grid) passes
+// whatever the table holds, and neither the host nor the launch grid ever needs a count from the device.  A caller who wants one pass
+// per frame creates the tracker with max_tracks <= grid^2.  A slot that yields no region (a free slot, a box roi_from_face refuses) gets
+// the VOID record -- every field zero, flags = RF_ROI_VOID: its cell is zero pixels, addresses no source byte and drops every face.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -14,6 +21,7 @@
 #include <string.h>
 
 #include "../../include/retinaface_amd.h"
+#include "motion.h"
 #include "pyramid.h"
 #include "tta.h"
 
@@ -82,6 +90,17 @@ inline int roi_min_level(const RoiCell *cells, int used) {
     return m;
 }
 
+// the void record, and the region (four zeros) that stands for it where an entry point takes regions
+__host__ __device__ inline RoiCell roi_void_cell() {
+    RoiCell c;
+    c.roi.x = c.roi.y = c.roi.w = c.roi.h = 0;
+    c.level = c.x0 = c.y0 = 0;
+    c.flags = RF_ROI_VOID;
+    return c;
+}
+__host__ __device__ inline bool roi_cell_is_void(const RoiCell &c) { return (c.flags & RF_ROI_VOID) != 0; }
+inline bool roi_is_void(const rf_roi &r) { return r.x == 0 && r.y == 0 && r.w == 0 && r.h == 0; }
+
 inline int roi_passes(int regions, int grid) { return (regions + grid * grid - 1) / (grid * grid); }
 
 __host__ __device__ inline int roi_floordiv(long long a, int b) {      // b > 0
@@ -92,7 +111,7 @@ __host__ __device__ inline int roi_floordiv(long long a, int b) {      // b > 0
 // ---- the plan
 // The cell of one (valid) region in cells of cw x ch pixels: the largest step not above max_zoom at which it fits; none: x1/4, the cell
 // shows the region's centre, RF_ROI_CROPPED.
-inline RoiCell roi_plan(const rf_roi &r, int cw, int ch, int max_zoom) {
+__host__ __device__ inline RoiCell roi_plan(const rf_roi &r, int cw, int ch, int max_zoom) {
     RoiCell c;
     c.roi = r;
     c.flags = 0;
@@ -153,7 +172,7 @@ __host__ __device__ inline void roi_cell_pixel(const uint8_t *src, int rows, int
 }
 
 // Host: one view of view_w x view_h pixels (roi_check_view) whose first `used` cells are `cells`, written as view_w * 3 bytes per row
-// at dst + y * dst_step; bytes beyond a row are untouched, the cells behind `used` are zero.
+// at dst + y * dst_step; bytes beyond a row are untouched, the cells behind `used` and the void cells are zero.
 inline void roi_atlas_host(const uint8_t *src, int rows, int cols, int step, const RoiCell *cells, int used, int grid, int view_w,
                            int view_h, uint8_t *dst, int dst_step) {
     const int cw = view_w / grid, ch = view_h / grid;
@@ -161,7 +180,7 @@ inline void roi_atlas_host(const uint8_t *src, int rows, int cols, int step, con
         uint8_t *d = dst + (size_t)y * dst_step;
         for (int x = 0; x < view_w; x++) {
             const int c = (y / ch) * grid + x / cw;
-            if (c < used) roi_cell_pixel(src, rows, cols, (size_t)step, cells[c], x % cw, y % ch, d + 3 * x);
+            if (c < used && !roi_cell_is_void(cells[c])) roi_cell_pixel(src, rows, cols, (size_t)step, cells[c], x % cw, y % ch, d + 3 * x);
             else d[3 * x] = d[3 * x + 1] = d[3 * x + 2] = 0;
         }
     }
@@ -169,8 +188,8 @@ inline void roi_atlas_host(const uint8_t *src, int rows, int cols, int step, con
 
 // ---- the face rule
 // One face of a pass.  in / out: 15 floats (score, x1, y1, x2, y2, px[5], py[5]), they may alias.  The face's cell is the one its box
-// centre lies in (compares against the cell borders: a NaN lands in cell 0 and fails the last test); a cell without a region drops
-// it.  Every coordinate: one fp32 add of the integer x0 - cell_x (y0 - cell_y), then for a zoom * (1 / z) - (z - 1) / 2z, for a shrink
+// centre lies in (compares against the cell borders: a NaN lands in cell 0 and fails the last test); a cell without a region, or a
+// void one, drops it.  Every coordinate: one fp32 add of the integer x0 - cell_x (y0 - cell_y), then for a zoom * (1 / z) - (z - 1) / 2z, for a shrink
 // * k + (k - 1) / 2 (all constants exact).  Kept only when the mapped centre lies inside the region; *region: its index in the frame.
 __host__ __device__ inline bool roi_map_face(const RoiEntry &e, const float *in, float *out, int *region) {
 #pragma clang fp contract(off)
@@ -184,6 +203,7 @@ __host__ __device__ inline bool roi_map_face(const RoiEntry &e, const float *in,
     const int cell = cj * e.grid + ci;
     if (cell >= e.used) return false;
     const RoiCell c = e.cells[cell];
+    if (roi_cell_is_void(c)) return false;
     const float ax = (float)(c.x0 - ci * cw), ay = (float)(c.y0 - cj * ch);
     float mul = 1.f, add = 0.f;
     switch (c.level) {
@@ -209,11 +229,11 @@ __host__ __device__ inline bool roi_map_face(const RoiEntry &e, const float *in,
     return true;
 }
 
-// ---- regions from faces (host only)
+// ---- regions from faces
 // The region of one face: the box times coord_scale (one fp32 multiply per coordinate), grown on every side by margin_q8 / 256 of
 // its longer side (doubles), lower edges floored, upper edges ceiled, the sides held to [1, 16384].  False for a box that is not
 // finite, is empty or starts beyond +-2^20.
-inline bool roi_from_face(const float *face, float coord_scale, int margin_q8, rf_roi *out) {
+__host__ __device__ inline bool roi_from_face(const float *face, float coord_scale, int margin_q8, rf_roi *out) {
 #pragma clang fp contract(off)
     double b[4];
     for (int i = 0; i < 4; i++) {
@@ -232,6 +252,29 @@ inline bool roi_from_face(const float *face, float coord_scale, int margin_q8, r
     h = h < 1 ? 1 : h > kRoiMaxSide ? kRoiMaxSide : h;
     out->x = (int32_t)x1; out->y = (int32_t)y1; out->w = (int32_t)w; out->h = (int32_t)h;
     return true;
+}
+
+// ---- regions from tracks
+// The cell of one track slot: void for a free slot; otherwise the region of the box the next frame step matches against -- `last` for
+// a plain tracker (m null), track_step_motion's pred[s] for one with motion -- grown by margin_q8 / 256 (0 = 64, as at the C ABI) at
+// coord scale 1 (tracks live in source pixels), planned into a cell of cw x ch pixels; void when roi_from_face refuses the box.
+__host__ __device__ inline RoiCell roi_track_cell(const rf_track &t, const rf_track_motion *m, const MotionSpec &ms, int margin_q8, int cw,
+                                                  int ch, int max_zoom) {
+    if (t.id == 0) return roi_void_cell();
+    float f[5];
+    f[0] = 0.f;
+    const float last[4] = {t.last.x1, t.last.y1, t.last.x2, t.last.y2};
+    if (m) motion_predict_box(last, m->vx, m->vy, m->samples, motion_frames_ahead(t.missed, 1, ms.horizon), f + 1);
+    else { f[1] = last[0]; f[2] = last[1]; f[3] = last[2]; f[4] = last[3]; }
+    rf_roi r;
+    if (!roi_from_face(f, 1.f, margin_q8 ? margin_q8 : 64, &r)) return roi_void_cell();
+    return roi_plan(r, cw, ch, max_zoom);
+}
+
+// Host: the cells of a stream's table (max_tracks slots; motion null: a plain tracker) -- the code roi_track_cells_kernel runs
+inline void roi_cells_from_tracks(const rf_track *table, const rf_track_motion *motion, const MotionSpec &ms, int max_tracks, int margin_q8,
+                                  int cw, int ch, int max_zoom, RoiCell *cells) {
+    for (int s = 0; s < max_tracks; s++) cells[s] = roi_track_cell(table[s], motion ? motion + s : nullptr, ms, margin_q8, cw, ch, max_zoom);
 }
 
 }  // namespace rf

@@ -16,7 +16,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (rf_face, rf_face_batch_spec, rf_face_gate, rf_face_quality, rf_options, rf_overlay_spec, rf_redact_spec, rf_tile_spec, rf_track,
-                   rf_dewarp_spec, rf_enhance_spec, rf_roi, rf_roi_spec, rf_motion_spec, rf_pyramid_spec, rf_rot_spec, rf_shot, rf_track_motion, rf_track_spec, rf_track_tag, rf_tta_spec,
+                   rf_dewarp_spec, rf_enhance_spec, rf_roi, rf_roi_cell, rf_roi_spec, rf_motion_spec, rf_pyramid_spec, rf_rot_spec, rf_shot, rf_track_motion, rf_track_spec, rf_track_tag, rf_tta_spec,
                    rf_follow_spec, rf_track_follow)
 
 PRECISION_FP32, PRECISION_FP16, PRECISION_INT8 = 0, 1, 2
@@ -929,6 +929,54 @@ class Tracker:
         det.last_counts = [int(counts[i]) for i in range(n)]
         return (det._collect(out, counts, n, cap),) + self._results(n, counts, cap)
 
+    # ------------------------------------------------------------------ tracked region detection
+    def roi_cells(self, streams: Sequence[int], margin: Optional[float] = None, grid: int = 0, max_zoom: int = 0) -> np.ndarray:
+        """rf_roi_track_cells_device: the plan kernel alone -- the (n, max_tracks, 8) int32 cell records (roi_plan()'s columns) the
+        device plans from the tables of streams[i] (-1: void records).  Changes nothing."""
+        n = len(streams)
+        cells = (rf_roi_cell * max(n * self.max_tracks, 1))()
+        _lib.check(self._lib.rf_roi_track_cells_device(self._det._h, self._t, (C.c_int * max(n, 1))(*streams), n, _margin_q8(margin),
+                                                       C.byref(roi_spec(grid, max_zoom)), cells), self._det._h)
+        return _cell_rows(cells, n * self.max_tracks).reshape(n, self.max_tracks, 8)
+
+    def _tracked_rois(self, fn, frames, streams, threshold, margin, grid, max_zoom, vote, max_faces, views_ptr, cap_ended, return_src_roi):
+        det = self._det
+        n = frames[4]
+        sp = roi_spec(grid, max_zoom, vote, max_faces)
+        cap = sp.max_faces or det.max_detections
+        cells = (rf_roi_cell * max(n * self.max_tracks, 1))()
+        t, _, tags, ended, ce, ec = self._buffers(n, cap, cap_ended)
+        head = (det._h,) + tuple(frames) + (float(threshold), C.byref(sp), _margin_q8(margin))
+        tail = (cells, views_ptr, t, (C.c_int * max(n, 1))(*streams), tags, ended, ce, ec)
+        dets, src, votes = det._merged_call(fn, head, n, cap, "roi_counts", True, tail=tail)      # the C call takes src_roi, then votes
+        self.truncated = det.truncated
+        self.last_cells = _cell_rows(cells, n * self.max_tracks).reshape(n, self.max_tracks, 8)
+        res = (dets,) + self._results(n, det.roi_counts, cap)
+        return res + (votes, src) if return_src_roi else res
+
+    def detect_tracked_rois(self, imgs: Sequence[np.ndarray], streams: Sequence[int], threshold: float = 0.5, margin: Optional[float] = None,
+                            grid: int = 0, max_zoom: int = 0, vote: bool = False, max_faces: int = 0, cap_ended: Optional[int] = None,
+                            return_src_roi: bool = False):
+        """rf_detect_track_roi_batch: every frame (None: an empty frame, whose stream ages) is detected only in the regions the device
+        plans from the table of its stream (streams[i]; -1: no regions, no faces, no step) -- slot r is region r, a free slot a void
+        cell; a live slot's region is its last (with motion: its predicted) box grown by `margin` of its longer side (None: a quarter)
+        -- and the merged faces go straight into the frame step.  Returns (detections in SOURCE-FRAME pixels, tags per image, ended
+        tracks per image); with return_src_roi also, per frame, how many candidates each face merged and the slot whose region found
+        it.  self.last_cells holds the (n, max_tracks, 8) cell records the device planned; the detector's roi_counts the true counts."""
+        f = _host_frames(imgs)
+        return self._tracked_rois(self._lib.rf_detect_track_roi_batch, f.args, streams, threshold, margin, grid, max_zoom, vote, max_faces, None,
+                                  cap_ended, return_src_roi)
+
+    def detect_tracked_rois_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], streams: Sequence[int],
+                                   threshold: float = 0.5, steps: Optional[Sequence[int]] = None, margin: Optional[float] = None, grid: int = 0,
+                                   max_zoom: int = 0, vote: bool = False, max_faces: int = 0, views_ptr: Optional[int] = None,
+                                   cap_ended: Optional[int] = None, return_src_roi: bool = False):
+        """rf_detect_track_roi_batch_device: detect_tracked_rois for frames resident in device memory (0 / None: an empty frame).
+        views_ptr: device memory of passes * net_h * net_w * 3 bytes that receives the views as dense frames."""
+        frames = _device_frames(ptrs, rows, cols, steps) + (len(ptrs),)
+        return self._tracked_rois(self._lib.rf_detect_track_roi_batch_device, frames, streams, threshold, margin, grid, max_zoom, vote, max_faces,
+                                  views_ptr, cap_ended, return_src_roi)
+
     def read(self, stream: int):
         """rf_tracker_read: (table, frames, next_id) of a stream"""
         table = np.zeros(self.max_tracks, TRACK_DTYPE)
@@ -1194,6 +1242,7 @@ class Dewarper:
 
 
 ROI_CROPPED = _lib.RF_ROI_CROPPED
+ROI_VOID = _lib.RF_ROI_VOID
 
 
 def roi_spec(grid: int = 0, max_zoom: int = 0, vote: bool = False, max_faces: int = 0) -> rf_roi_spec:
@@ -1220,6 +1269,43 @@ def _roi_lists(rois_per_frame):
     counts = [len(r) for r in rois_per_frame]
     arr, _ = _roi_array([r for frame in rois_per_frame for r in frame])
     return arr, (C.c_int * max(len(counts), 1))(*counts), counts
+
+
+def _cell_rows(cells, n: int) -> np.ndarray:
+    """(n, 8) int32 rows of x, y, w, h, level, x0, y0, flags of a ctypes rf_roi_cell array"""
+    return np.frombuffer(cells, np.int32, 8 * n).reshape(n, 8).copy() if n else np.zeros((0, 8), np.int32)
+
+
+def _margin_q8(margin: Optional[float]) -> int:
+    """a margin in 1/256ths for the C ABI, which reads 0 as its default (a quarter): None is that default, a margin that rounds to 0 is
+    refused here rather than silently becoming a quarter"""
+    if margin is None:
+        return 0
+    q8 = int(round(margin * 256))
+    if q8 == 0:
+        raise _lib.RFError(_lib.RF_ERR_INVALID_ARG, "a margin below 1 / 512 cannot be expressed (0 means the default); pass None for the default")
+    return q8
+
+
+def roi_cells_from_tracks(table, view_w: int, view_h: int, motion=None, mspec=None, margin: Optional[float] = None, grid: int = 0,
+                          max_zoom: int = 0) -> np.ndarray:
+    """rf_roi_cells_from_tracks (host only, no GPU): the (max_tracks, 8) int32 cell records (roi_plan()'s columns) of one stream's
+    table (TRACK_DTYPE) -- slot r is region r; a free slot, or a box rois_from_faces() would skip, is the void record (zeros, flags
+    ROI_VOID).  motion: None (a plain tracker) or the stream's MOTION_DTYPE records, read with mspec (an rf_motion_spec or motion_spec()'s keywords; None: the defaults)."""
+    lib = _lib.load_library()
+    table = np.ascontiguousarray(table)
+    T = len(table)
+    m = np.ascontiguousarray(motion) if motion is not None else None
+    if table.ndim != 1 or table.dtype.itemsize != TRACK_DTYPE.itemsize or (m is not None and (m.shape != (T,) or m.dtype.itemsize != MOTION_DTYPE.itemsize)):
+        raise ValueError("table: a 1-d array of TRACK_DTYPE records; motion: one MOTION_DTYPE record per slot")
+    cells = (rf_roi_cell * max(T, 1))()
+    ms = _as_motion_spec(mspec)
+    st = lib.rf_roi_cells_from_tracks(None, C.byref(ms) if ms is not None else None, table.ctypes.data_as(C.POINTER(rf_track)),
+                                      m.ctypes.data_as(C.POINTER(rf_track_motion)) if m is not None else None, T, _margin_q8(margin),
+                                      int(view_w), int(view_h), C.byref(roi_spec(grid, max_zoom)), cells)
+    if st < 0:
+        raise _lib.RFError(st, "rf_roi_cells_from_tracks: bad spec, view size, margin or table")
+    return _cell_rows(cells, T)
 
 
 def roi_plan(rois, view_w: int, view_h: int, grid: int = 0, max_zoom: int = 0):
