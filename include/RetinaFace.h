@@ -146,6 +146,21 @@ public:
                            const rf_roi_spec *spec = nullptr, int margin_q8 = 0);
     const vector<vector<rf_roi_cell>> &trackedRoiCells() const { return roiCells_; }
 
+    /* additive: change regions (rf_changer_create / rf_change_regions_device / rf_detect_change_roi_batch): createChanger() makes a
+       changer on this handle for frames of rows x cols and nStreams streams (freed with the handle, or by rf_changer_destroy).
+       changeRegions() runs the two kernels alone over frames in DEVICE memory: it steps the references and returns, per frame, the
+       spec's max_regions cell records; changeInfo() holds the info records.  detectChanged() is the fused call over host frames: the
+       references of streams[i] step, every frame is detected inside its change regions -- with a tracker (may be null) also inside
+       the regions of its stream's track slots, region r < max_tracks being slot r -- and the merged faces go into the frame step.
+       Fills lastBatchResult() (SOURCE-FRAME pixels), roiVotes(), roiRegions(), trackedRoiCells() (per frame the T + R records),
+       changeInfo() and, with a tracker, lastTrackTags() and lastEndedTracks(). */
+    rf_changer createChanger(int rows, int cols, int nStreams = 1, const rf_change_spec *spec = nullptr);
+    vector<vector<rf_roi_cell>> changeRegions(rf_changer changer, const vector<const void *> &dFrames, const vector<int> &steps,
+                                              const vector<int> &streams, const rf_roi_spec *spec = nullptr, int margin_q8 = 0);
+    void detectChanged(const vector<cv::Mat> &imgs, rf_changer changer, const vector<int> &streams, rf_tracker tracker = nullptr,
+                       float threshold = 0.5, const rf_roi_spec *spec = nullptr, int margin_q8 = 0);
+    const vector<rf_change_info> &changeInfo() const { return changeInfo_; }
+
     /* additive: low-light detection (rf_detect_enhanced_batch): every frame is enhanced on the device (tile-adaptive contrast boost of
        dark tiles, rf_enhance_spec) and detected; the frames themselves are not written.  Fills lastBatchResult() with what the plain
        batch call returns for the enhanced frames; tilesEnhanced() holds, per frame, the number of tiles the enhancement touched
@@ -256,6 +271,9 @@ private:
     vector<float> rotScore_;
     vector<vector<rf_track_tag>> trackTags_;
     vector<vector<rf_roi_cell>> roiCells_;
+    vector<rf_change_info> changeInfo_;
+    struct ChangerShape { rf_changer changer; int rows, cols, regions; };
+    vector<ChangerShape> changers_;
     vector<vector<rf_track>> trackEnded_;
     vector<vector<int32_t>> redactPixels_;
     vector<vector<int32_t>> overlayPixels_;

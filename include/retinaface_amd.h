@@ -258,7 +258,9 @@ int rf_detect_face_batch(rf_handle h, const uint8_t *const *bgr, const int *rows
                          void *d_tensor, void *tensor, double *matrices, int *offsets);
 
 /* The face batch of faces the CALLER supplies (the packed counterpart of rf_align_batch_device; faces, counts and coord_scale as
- * there).  RF_ERR_TRUNCATED when total > capacity. */
+ * there).  RF_ERR_TRUNCATED when total > capacity. 
+ * Work the caller has pending on the default stream when the call starts (a fill of d_out, say) is ordered in front of the call's writes
+ * to d_out. */
 int rf_face_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
                          const rf_face *faces, int cap_per_image, const int *counts, const float *coord_scale,
                          const rf_face_batch_spec *spec, void *d_tensor, void *tensor, double *matrices, int *offsets);
@@ -1306,6 +1308,85 @@ int rf_detect_track_roi_batch(rf_handle h, const uint8_t *const *bgr, const int 
                               const rf_roi_spec *roi_spec, int margin_q8, rf_face *out, int cap_per_image, int *counts, int *src_roi, int *votes,
                               rf_roi_cell *cells, void *d_views, rf_tracker tracker, const int *stream_of_image, rf_track_tag *tags,
                               rf_track *ended, int cap_ended, int *ended_counts);
+
+/* ---- Change regions: a region exists above only where a track already is, so a face that enters the scene between two key frames is
+ * seen by nothing until the next key frame.  A CHANGER keeps a small per-stream reference image in device memory -- one luma sum per
+ * block of the frame -- and turns the blocks of a frame that differ from it into regions ON THE DEVICE; they go through the same atlas,
+ * launches, gather and merge, alone or next to a tracker's regions in one call (DESIGN.md "Change regions" holds the definition;
+ * tests/change_ref.py restates it in numpy; everything up to the regions is integer arithmetic and byte-exact against it):
+ *   spec     a zero field means its default.  block B: 8, 16 or 32 (16).  thr_q4: 1..65535, the mean luma difference of a block in
+ *            1/16 grey levels (128 = 8 grey levels).  adapt_shift a: 0..8 (0: the reference becomes the frame).  dilate: 0 / 1 = grow
+ *            the mask by one block, 8-neighbourhood; 2 = off.  min_blocks: 1..65535 (2).  max_regions R: 1..64 (16).
+ *   changer  made for one frame shape and n_streams (1..1024) streams, as a dewarper is made for one shape.  The block grid is
+ *            bw = ceil(cols / B) by bh = ceil(rows / B), bw * bh <= 16384 (4K at B = 32, 1080p at B = 16); anything else is refused.
+ *   value    S(block) = sum of 29 b + 150 g + 77 r over the block's pixels inside the frame (uint32).  This is 256 x luma WITHOUT the
+ *            per-pixel rounding of the face-quality luma ((29 b + 150 g + 77 r + 128) >> 8): the sum is taken over the packed bytes
+ *            with 4-byte dot products and never unpacks a pixel.
+ *   step     each stream keeps ref[bh * bw] (int32) and a frame counter.  The first step after creation or reset SEEDS: ref = S, no
+ *            block is changed, every cell is void, info.flags = 1.  Every other step, per block with npix pixels inside the frame:
+ *            changed = |S - ref| > 16 * thr_q4 * npix, then ref += (S - ref) >> a (arithmetic, floors).
+ *   regions  the mask is dilated as the spec says; the 8-connected sets of marked blocks are the components: label = the smallest
+ *            raster index, count = marked blocks after dilation, box = bounding box in blocks.  Components with count < min_blocks
+ *            are dropped, the rest ordered by count descending, then label ascending, the first R kept.  Kept component k: the pixel
+ *            rectangle x = bx0 B, y = by0 B, x2 = min(cols, (bx1 + 1) B), y2 = min(rows, (by1 + 1) B) goes as a face box through
+ *            rf_roi_from_faces' rule at coord_scale 1 and margin_q8 (0 = 64) and rf_roi_plan's into cell k.  Slots k >= kept, and every
+ *            slot of a seeding step, get the void record.  A whole-frame change (lights, a moved camera) is one large region, which
+ *            may be RF_ROI_CROPPED; info.changed_blocks is how a caller recognises it and runs a key frame instead.
+ *   info     changed_blocks (before dilation), components (before the min_blocks drop), kept, flags (1: the step seeded).
+ *   fused    every image with pixels has ceil((T + R) / grid^2) passes, T = the tracker's max_tracks (0 without one), T + R <= 256:
+ *            region r < T is track slot r exactly as in tracked region detection, region T + k is change slot k; src_roi indexes that
+ *            list and cells receives n * (T + R) records.  With a tracker the merged faces go into the frame step: a newcomer gets its
+ *            id on the frame it appears in.  One index names the stream of both the changer and the tracker, whose n_streams must
+ *            match; a stream may appear once per call.  A NULL / 0 x 0 frame has no passes and does not touch the reference (with a
+ *            tracker its stream still steps and ages); stream -1: nothing happens for the image.
+ * Refused before any state changes (RF_ERR_INVALID_ARG): a bad spec, a net that does not meet the cell rule, margin_q8 outside
+ * [0, 65535], T + R > 256, mismatched stream counts, a stream twice in the call, a frame whose shape is not the changer's, a tracker
+ * with a gallery or with follow, a changer or tracker in the error state.  Multi-device handles: RF_ERR_UNSUPPORTED.  An error after
+ * the step was enqueued leaves the changer (and the tracker) in the error state until rf_changer_reset(changer, -1).
+ *
+ * rf_changer_create / rf_changer_destroy: as for a dewarper; freed with the handle at the latest.  rf_changer_reset: stream (-1: all)
+ * seeds again.  rf_changer_read: the reference (bw * bh int32), the frame counter and the last mask (bw * bh bytes, the changed blocks
+ * BEFORE dilation) of a stream; each may be NULL; returns bw * bh.
+ * rf_change_step_host (host only, no GPU, no handle): one step of one stream -- the code the kernels run.  ref (bw * bh) and *counter
+ * in and out; mask (bw * bh bytes), regions and cells (max_regions records each; zeros / void records behind info->kept) and info out.
+ * rf_change_regions_device: the two kernels alone over frames in device memory; they STEP the reference.  Image i's R records at
+ * cells[i * R], its info at info[i] (stream -1 or no pixels: void records, zero info).  Synchronous.
+ * rf_detect_change_roi_batch_device / rf_detect_change_roi_batch: the fused call.  Arguments as rf_detect_track_roi_batch*; tracker
+ * may be NULL (then tags, ended, ended_counts are not written); info (may be NULL) receives n records. */
+typedef struct rf_change_spec {
+    uint32_t struct_size;   /* sizeof(rf_change_spec) */
+    int32_t block;
+    int32_t thr_q4;
+    int32_t adapt_shift;
+    int32_t dilate;
+    int32_t min_blocks;
+    int32_t max_regions;
+    int32_t reserved;       /* 0 */
+} rf_change_spec;
+typedef struct rf_change_info {
+    int32_t changed_blocks, components, kept, flags;
+} rf_change_info;
+typedef struct rf_changer_s *rf_changer;
+int rf_changer_create(rf_handle h, const rf_change_spec *spec, int rows, int cols, int n_streams, rf_changer *out_changer);
+void rf_changer_destroy(rf_changer changer);
+int rf_changer_reset(rf_changer changer, int stream);
+int rf_changer_read(rf_changer changer, int stream, int32_t *ref, int64_t *frames, uint8_t *mask);
+int rf_change_step_host(const rf_change_spec *spec, const uint8_t *bgr, int rows, int cols, int step, int32_t *ref, int64_t *counter,
+                        int margin_q8, int net_w, int net_h, const rf_roi_spec *roi_spec, uint8_t *mask, rf_roi *regions, rf_roi_cell *cells,
+                        rf_change_info *info);
+int rf_change_regions_device(rf_handle h, rf_changer changer, const void *const *d_bgr, const int *rows, const int *cols, const int *steps,
+                             const int *stream_of_image, int n, int margin_q8, const rf_roi_spec *roi_spec, rf_roi_cell *cells,
+                             rf_change_info *info);
+int rf_detect_change_roi_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                      float threshold, const rf_roi_spec *roi_spec, int margin_q8, rf_face *out, int cap_per_image, int *counts,
+                                      int *src_roi, int *votes, rf_roi_cell *cells, void *d_views, rf_changer changer, rf_change_info *info,
+                                      rf_tracker tracker, const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended,
+                                      int *ended_counts);
+int rf_detect_change_roi_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                               float threshold, const rf_roi_spec *roi_spec, int margin_q8, rf_face *out, int cap_per_image, int *counts,
+                               int *src_roi, int *votes, rf_roi_cell *cells, void *d_views, rf_changer changer, rf_change_info *info,
+                               rf_tracker tracker, const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended,
+                               int *ended_counts);
 
 /* ---- Zoom-pyramid detection: the smallest anchors are 16 px, so faces below about 16 px are not seen in a frame that already fits the
  * net.  A pyramid call detects every frame at 1x (the passes of its tile plan) and as net-sized tiles of the frame ENLARGED 2x and / or 4x

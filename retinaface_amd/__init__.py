@@ -21,6 +21,7 @@ from .detector import rot_map_face, rot_merge_host, rot_spec, rotate_host  # noq
 from .detector import (LENS_EQUIDISTANT, LENS_EQUISOLID, LENS_ORTHOGRAPHIC, LENS_STEREOGRAPHIC, Dewarper, dewarp_host,  # noqa: F401
                        dewarp_map_face, dewarp_merge_host, dewarp_plan, dewarp_spec)
 from .detector import ROI_VOID, roi_cells_from_tracks  # noqa: F401
+from .detector import Changer, change_spec, change_step_host  # noqa: F401
 from .detector import ROI_CROPPED, roi_atlas_host, roi_map_face, roi_merge_host, roi_plan, roi_spec, rois_from_faces  # noqa: F401
 from .detector import enhance_host, enhance_spec  # noqa: F401
 from .detector import pyramid_map_face, pyramid_merge_host, pyramid_plan, pyramid_spec, zoom_host  # noqa: F401

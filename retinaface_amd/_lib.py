@@ -155,6 +155,15 @@ class rf_roi_spec(C.Structure):
 RF_ROI_MAX_REGIONS, RF_ROI_CROPPED, RF_ROI_VOID = 256, 1, 2
 
 
+class rf_change_spec(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("block", C.c_int32), ("thr_q4", C.c_int32), ("adapt_shift", C.c_int32), ("dilate", C.c_int32),
+                ("min_blocks", C.c_int32), ("max_regions", C.c_int32), ("reserved", C.c_int32)]
+
+
+class rf_change_info(C.Structure):
+    _fields_ = [("changed_blocks", C.c_int32), ("components", C.c_int32), ("kept", C.c_int32), ("flags", C.c_int32)]
+
+
 class rf_enhance_spec(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("tile", C.c_int32), ("clip", C.c_int32), ("dark_below", C.c_int32)]
 
@@ -403,6 +412,22 @@ SYMBOLS = {
                                             _PP(rf_roi_spec), C.c_int, _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int),
                                             _PP(rf_roi_cell), C.c_void_p, C.c_void_p, _PP(C.c_int), _PP(rf_track_tag), _PP(rf_track), C.c_int,
                                             _PP(C.c_int)]),
+    "rf_changer_create": (C.c_int, [C.c_void_p, _PP(rf_change_spec), C.c_int, C.c_int, C.c_int, _PP(C.c_void_p)]),
+    "rf_changer_destroy": (None, [C.c_void_p]),
+    "rf_changer_reset": (C.c_int, [C.c_void_p, C.c_int]),
+    "rf_changer_read": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, _PP(C.c_int64), C.c_void_p]),
+    "rf_change_step_host": (C.c_int, [_PP(rf_change_spec), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, _PP(C.c_int64), C.c_int, C.c_int,
+                                      C.c_int, _PP(rf_roi_spec), C.c_void_p, _PP(rf_roi), _PP(rf_roi_cell), _PP(rf_change_info)]),
+    "rf_change_regions_device": (C.c_int, [C.c_void_p, C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
+                                           C.c_int, _PP(rf_roi_spec), _PP(rf_roi_cell), _PP(rf_change_info)]),
+    "rf_detect_change_roi_batch_device": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int, C.c_float,
+                                                    _PP(rf_roi_spec), C.c_int, _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int),
+                                                    _PP(rf_roi_cell), C.c_void_p, C.c_void_p, _PP(rf_change_info), C.c_void_p, _PP(C.c_int),
+                                                    _PP(rf_track_tag), _PP(rf_track), C.c_int, _PP(C.c_int)]),
+    "rf_detect_change_roi_batch": (C.c_int, [C.c_void_p, _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int, C.c_float,
+                                             _PP(rf_roi_spec), C.c_int, _PP(rf_face), C.c_int, _PP(C.c_int), _PP(C.c_int), _PP(C.c_int),
+                                             _PP(rf_roi_cell), C.c_void_p, C.c_void_p, _PP(rf_change_info), C.c_void_p, _PP(C.c_int),
+                                             _PP(rf_track_tag), _PP(rf_track), C.c_int, _PP(C.c_int)]),
     "rf_enhance_host": (C.c_int, [_PP(rf_enhance_spec), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, _PP(C.c_int)]),
     "rf_enhance_device": (C.c_int, [C.c_void_p, _PP(rf_enhance_spec), _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int), _PP(C.c_int), C.c_int,
                                     _PP(C.c_void_p), _PP(C.c_int), _PP(C.c_int)]),

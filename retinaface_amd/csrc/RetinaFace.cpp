@@ -487,6 +487,85 @@ void RetinaFace::detectTrackedRois(const vector<cv::Mat> &imgs, rf_tracker track
     }
 }
 
+rf_changer RetinaFace::createChanger(int rows, int cols, int nStreams, const rf_change_spec *spec) {
+    rf_changer c = nullptr;
+    check(rf_changer_create(h_, spec, rows, cols, nStreams, &c), h_, "RetinaFace::createChanger");
+    changers_.push_back(ChangerShape{c, rows, cols, spec && spec->max_regions > 0 ? spec->max_regions : 16});      // (the header's default)
+    return c;
+}
+
+vector<vector<rf_roi_cell>> RetinaFace::changeRegions(rf_changer changer, const vector<const void *> &dFrames, const vector<int> &steps,
+                                                      const vector<int> &streams, const rf_roi_spec *spec, int margin_q8) {
+    const int n = (int)dFrames.size();
+    if ((int)streams.size() != n || (int)steps.size() != n) throw std::runtime_error("RetinaFace::changeRegions: one step and one stream per frame");
+    const ChangerShape *cs = nullptr;
+    for (const ChangerShape &c : changers_)
+        if (c.changer == changer) cs = &c;
+    if (!cs) throw std::runtime_error("RetinaFace::changeRegions: not a changer of this object");
+    vector<int> rows(n), cols(n);
+    for (int i = 0; i < n; i++) { rows[i] = dFrames[i] ? cs->rows : 0; cols[i] = dFrames[i] ? cs->cols : 0; }
+    vector<rf_roi_cell> cells((size_t)n * cs->regions);
+    changeInfo_.assign(n, rf_change_info{0, 0, 0, 0});
+    vector<vector<rf_roi_cell>> out(n);
+    if (n == 0) return out;
+    check(rf_change_regions_device(h_, changer, dFrames.data(), rows.data(), cols.data(), steps.data(), streams.data(), n, margin_q8, spec,
+                                   cells.data(), changeInfo_.data()), h_, "RetinaFace::changeRegions");
+    for (int i = 0; i < n; i++) out[i].assign(cells.begin() + (size_t)i * cs->regions, cells.begin() + (size_t)(i + 1) * cs->regions);
+    return out;
+}
+
+void RetinaFace::detectChanged(const vector<cv::Mat> &imgs, rf_changer changer, const vector<int> &streams, rf_tracker tracker, float threshold,
+                               const rf_roi_spec *spec, int margin_q8) {
+    const int n = (int)imgs.size();
+    if ((int)streams.size() != n) throw std::runtime_error("RetinaFace::detectChanged: one stream per image");
+    const ChangerShape *cs = nullptr;
+    for (const ChangerShape &c : changers_)
+        if (c.changer == changer) cs = &c;
+    if (!cs) throw std::runtime_error("RetinaFace::detectChanged: not a changer of this object");
+    lastBatch_.assign(n, vector<FaceDetectInfo>());
+    roiVotes_.assign(n, vector<int>());
+    roiSrc_.assign(n, vector<int>());
+    trackTags_.assign(n, vector<rf_track_tag>());
+    trackEnded_.assign(n, vector<rf_track>());
+    roiCells_.assign(n, vector<rf_roi_cell>());
+    changeInfo_.assign(n, rf_change_info{0, 0, 0, 0});
+    if (n == 0) return;
+    const int cap = spec && spec->max_faces > 0 ? spec->max_faces : maxDet_, capEnded = 256;
+    vector<const uint8_t *> ptrs(n);
+    vector<int> rows(n), cols(n), steps(n), counts(n, 0), endedCounts(n, 0);
+    for (int i = 0; i < n; i++) {
+        ptrs[i] = imgs[i].empty() ? nullptr : imgs[i].data;
+        rows[i] = imgs[i].rows; cols[i] = imgs[i].cols; steps[i] = (int)(size_t)imgs[i].step;
+    }
+    int T = 0;                                         // the tracker's max_tracks: what rf_tracker_read returns for cap 0
+    if (tracker) {
+        T = rf_tracker_read(tracker, 0, nullptr, 0, nullptr, nullptr);
+        if (T < 0) check(T, h_, "RetinaFace::detectChanged");
+    }
+    const int S = T + cs->regions;
+    vector<rf_face> faces((size_t)n * cap);
+    vector<int> votes((size_t)n * cap, 0), src((size_t)n * cap, 0);
+    vector<rf_track_tag> tags((size_t)n * cap);
+    vector<rf_track> ended((size_t)n * capEnded);
+    vector<rf_roi_cell> cells((size_t)n * S);
+    check(rf_detect_change_roi_batch(h_, ptrs.data(), rows.data(), cols.data(), steps.data(), n, threshold, spec, margin_q8, faces.data(), cap,
+                                     counts.data(), src.data(), votes.data(), cells.data(), nullptr, changer, changeInfo_.data(), tracker,
+                                     streams.data(), tracker ? tags.data() : nullptr, tracker ? ended.data() : nullptr, tracker ? capEnded : 0,
+                                     tracker ? endedCounts.data() : nullptr), h_, "RetinaFace::detectChanged");
+    for (int i = 0; i < n; i++) {
+        const int k = counts[i] < cap ? counts[i] : cap;
+        lastBatch_[i].resize(k);
+        if (k) memcpy(lastBatch_[i].data(), &faces[(size_t)i * cap], (size_t)k * sizeof(rf_face));
+        roiVotes_[i].assign(votes.begin() + (size_t)i * cap, votes.begin() + (size_t)i * cap + k);
+        roiSrc_[i].assign(src.begin() + (size_t)i * cap, src.begin() + (size_t)i * cap + k);
+        roiCells_[i].assign(cells.begin() + (size_t)i * S, cells.begin() + (size_t)(i + 1) * S);
+        if (!tracker) continue;
+        trackTags_[i].assign(tags.begin() + (size_t)i * cap, tags.begin() + (size_t)i * cap + k);
+        const int e = endedCounts[i] < capEnded ? endedCounts[i] : capEnded;
+        trackEnded_[i].assign(ended.begin() + (size_t)i * capEnded, ended.begin() + (size_t)i * capEnded + e);
+    }
+}
+
 vector<rf_roi> RetinaFace::roisFromFaces(const vector<FaceDetectInfo> &faces, float coordScale, int margin_q8) {
     static_assert(sizeof(FaceDetectInfo) == sizeof(rf_face), "a FaceDetectInfo is an rf_face");
     vector<rf_roi> out(faces.size());

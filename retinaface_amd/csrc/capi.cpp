@@ -29,7 +29,14 @@ struct rf_engine {
     std::list<std::pair<std::pair<int, int>, std::unique_ptr<rf::Engine>>> pool;
     std::vector<rf_tracker_s *> trackers;              // rf_tracker_create: what rf_destroy still has to free
     std::vector<rf_dewarper_s *> dewarpers;            // rf_dewarper_create: likewise
+    std::vector<rf_changer_s *> changers;              // rf_changer_create: likewise
     ~rf_engine();
+};
+
+// a changer: the handle it lives on and the engine's object (null once destroyed)
+struct rf_changer_s {
+    rf_engine *h;
+    void *impl;
 };
 
 // a tracker: the handle it lives on and the engine's object
@@ -48,6 +55,7 @@ struct rf_dewarper_s {
 rf_engine::~rf_engine() {
     for (rf_tracker_s *t : trackers) delete t;         // the engine frees the device state with itself
     for (rf_dewarper_s *d : dewarpers) delete d;
+    for (rf_changer_s *c : changers) delete c;
 }
 
 namespace {
@@ -1930,6 +1938,123 @@ int rf_detect_track_roi_batch(rf_handle h, const uint8_t *const *bgr, const int 
                               rf_track *ended, int cap_ended, int *ended_counts) {
     return detect_track_roi_common(h, bgr, rows, cols, steps, n, false, threshold, roi_spec, margin_q8, out, cap_per_image, counts, src_roi, votes,
                                    cells, d_views, tracker, stream_of_image, tags, ended, cap_ended, ended_counts);
+}
+
+// ---- change regions (change.h)
+int rf_changer_create(rf_handle h, const rf_change_spec *spec, int rows, int cols, int n_streams, rf_changer *out_changer) {
+    rf::ChangeSpec sp;
+    if (out_changer) *out_changer = nullptr;
+    const char *bad = rf::change_spec_resolve(spec, &sp);             // spec, shape and range first: refused without a GPU
+    int bw = 0, bh = 0;
+    if (!bad) bad = rf::change_check_shape(rows, cols, sp, &bw, &bh);
+    if (!bad && (n_streams < 1 || n_streams > rf::kChangeMaxStreams)) bad = "n_streams must be in [1, 1024]";
+    if (!h || !out_changer) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        if (bad) throw rf::ArgError(std::string("changer: ") + bad);
+        void *impl = h->eng->changer_create(sp, rows, cols, n_streams);
+        rf_changer_s *c = new rf_changer_s{h, impl};
+        h->changers.push_back(c);
+        *out_changer = c;
+        return RF_OK;
+    });
+}
+
+void rf_changer_destroy(rf_changer changer) {
+    if (!changer) return;
+    rf_engine *h = changer->h;
+    (void)guarded(h, [&]() -> int {
+        h->eng->changer_destroy(changer->impl);
+        changer->impl = nullptr;           // the record stays until rf_destroy, so that a call on a destroyed changer is refused, not undefined
+        return RF_OK;
+    });
+}
+
+int rf_changer_reset(rf_changer changer, int stream) {
+    if (!changer) return RF_ERR_INVALID_ARG;
+    return guarded(changer->h, [&]() -> int { changer->h->eng->changer_reset(changer->impl, stream); return RF_OK; });
+}
+
+int rf_changer_read(rf_changer changer, int stream, int32_t *ref, int64_t *frames, uint8_t *mask) {
+    if (!changer) return RF_ERR_INVALID_ARG;
+    return guarded(changer->h, [&]() -> int { return changer->h->eng->changer_read(changer->impl, stream, ref, frames, mask); });
+}
+
+int rf_change_step_host(const rf_change_spec *spec, const uint8_t *bgr, int rows, int cols, int step, int32_t *ref, int64_t *counter,
+                        int margin_q8, int net_w, int net_h, const rf_roi_spec *roi_spec, uint8_t *mask, rf_roi *regions, rf_roi_cell *cells,
+                        rf_change_info *info) {
+    rf::ChangeSpec sp;
+    rf::RoiSpec rs;
+    int bw = 0, bh = 0;
+    if (rf::change_spec_resolve(spec, &sp) || rf::roi_spec_resolve(roi_spec, 1, &rs)) return RF_ERR_INVALID_ARG;
+    if (rf::change_check_shape(rows, cols, sp, &bw, &bh) || rf::roi_check_view(net_w, net_h, rs.grid)) return RF_ERR_INVALID_ARG;
+    if (!bgr || step < cols * 3 || margin_q8 < 0 || margin_q8 > 65535 || !ref || !counter || *counter < 0 || !mask || !regions || !cells || !info)
+        return RF_ERR_INVALID_ARG;
+    rf::change_step_host(sp, bgr, rows, cols, (size_t)step, bw, bh, ref, counter, margin_q8, net_w / rs.grid, net_h / rs.grid, rs.max_zoom, mask,
+                         regions, cells, info);
+    return RF_OK;
+}
+
+namespace {
+void change_request(rf_handle h, rf_changer changer, const rf_roi_spec *roi_spec, int margin_q8, const int *stream_of_image, rf::ChangeRequest *rq) {
+    if (h->eng->num_devices() > 1) throw rf::Unsupported("change regions are not available on a multi-device handle");
+    if (!changer || changer->h != h || !changer->impl) throw rf::ArgError("not a changer of this handle");
+    if (const char *bad = rf::roi_spec_resolve(roi_spec, h->eng->default_max_faces(), &rq->spec)) throw rf::ArgError(bad);
+    rq->changer = changer->impl;
+    rq->margin_q8 = margin_q8;
+    rq->stream_of_image = stream_of_image;
+}
+}  // namespace
+
+int rf_change_regions_device(rf_handle h, rf_changer changer, const void *const *d_bgr, const int *rows, const int *cols, const int *steps,
+                             const int *stream_of_image, int n, int margin_q8, const rf_roi_spec *roi_spec, rf_roi_cell *cells,
+                             rf_change_info *info) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded(h, [&]() -> int {
+        rf::ChangeRequest rq;
+        change_request(h, changer, roi_spec, margin_q8, stream_of_image, &rq);
+        rq.cells = cells; rq.info = info;
+        h->eng->change_regions(d_bgr, rows, cols, steps, n, rq);
+        return RF_OK;
+    });
+}
+
+namespace {
+int detect_change_roi_common(rf_handle h, const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,
+                             float thr, const rf_roi_spec *roi_spec, int margin_q8, rf_face *out, int cap, int *counts, int *src_roi, int *votes,
+                             rf_roi_cell *cells, void *d_views, rf_changer changer, rf_change_info *info, rf_tracker tracker,
+                             const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended, int *ended_counts) {
+    if (!h) return RF_ERR_INVALID_ARG;
+    return guarded_caps(h, [&](bool *tr) -> int {
+        rf::ChangeRequest rq;
+        change_request(h, changer, roi_spec, margin_q8, stream_of_image, &rq);
+        rq.votes = votes; rq.src_roi = src_roi; rq.cells = cells; rq.info = info; rq.d_views = d_views;
+        rf::TrackRequest trq;
+        if (tracker) track_request(h, tracker, stream_of_image, tags, ended, cap_ended, ended_counts, &trq);
+        bool cut = false;
+        h->eng->detect_change_rois(frames, rows, cols, steps, n, on_device, thr, out, cap, counts, tr, rq, trq, &cut);
+        if (cut) { h->error = kTrackCut; return RF_ERR_TRUNCATED; }
+        return RF_OK;
+    });
+}
+}  // namespace
+
+int rf_detect_change_roi_batch_device(rf_handle h, const void *const *d_bgr, const int *rows, const int *cols, const int *steps, int n,
+                                      float threshold, const rf_roi_spec *roi_spec, int margin_q8, rf_face *out, int cap_per_image, int *counts,
+                                      int *src_roi, int *votes, rf_roi_cell *cells, void *d_views, rf_changer changer, rf_change_info *info,
+                                      rf_tracker tracker, const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended,
+                                      int *ended_counts) {
+    return detect_change_roi_common(h, (const uint8_t *const *)d_bgr, rows, cols, steps, n, true, threshold, roi_spec, margin_q8, out, cap_per_image,
+                                    counts, src_roi, votes, cells, d_views, changer, info, tracker, stream_of_image, tags, ended, cap_ended,
+                                    ended_counts);
+}
+
+int rf_detect_change_roi_batch(rf_handle h, const uint8_t *const *bgr, const int *rows, const int *cols, const int *steps, int n,
+                               float threshold, const rf_roi_spec *roi_spec, int margin_q8, rf_face *out, int cap_per_image, int *counts,
+                               int *src_roi, int *votes, rf_roi_cell *cells, void *d_views, rf_changer changer, rf_change_info *info,
+                               rf_tracker tracker, const int *stream_of_image, rf_track_tag *tags, rf_track *ended, int cap_ended,
+                               int *ended_counts) {
+    return detect_change_roi_common(h, bgr, rows, cols, steps, n, false, threshold, roi_spec, margin_q8, out, cap_per_image, counts, src_roi, votes,
+                                    cells, d_views, changer, info, tracker, stream_of_image, tags, ended, cap_ended, ended_counts);
 }
 
 int rf_roi_merge_device(rf_handle h, const int *rows, const int *cols, int n, const rf_roi *rois, const int *roi_counts,

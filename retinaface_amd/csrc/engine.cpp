@@ -235,11 +235,13 @@ public:
         for (HostScratch *b : {&trk_tags_, &trk_ended_, &trk_counts_, &enh_counts_, &roi_cells_pin_, &tta_out_, &tta_votes_, &tta_outcount_, &shot_out_, &shot_info_, &fol_out_}) b->release();
         for (auto &t : trackers_) t->release();
         for (auto &d : dewarpers_) d->mesh.release();
+        for (auto &c : changers_) c->release();
         for (hipEvent_t e : trk_ev_) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : shot_ev_) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : fol_ev_) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : red_ev_) if (e) (void)hipEventDestroy(e);
         if (inputs_ready_) (void)hipEventDestroy(inputs_ready_);
+        if (caller_ready_) (void)hipEventDestroy(caller_ready_);
         kind_.arena->release();
         for (auto &e : prof_ev_) (void)hipEventDestroy(e);
     }
@@ -541,6 +543,13 @@ public:
         face_batch_open(rq, &d_tensor, &d_mats);
         if (d_tensor || d_mats || rq.gated) {
             table_upload(d_tab, tb);
+            // The caller's tensor: what the caller has pending on it on the default stream (a fill, say) comes first -- the side
+            // stream does not wait for the default stream by itself, and a late fill would land on top of the tensor kernel's output.
+            if (rq.d_tensor) {
+                if (!caller_ready_) RF_HIP(hipEventCreateWithFlags(&caller_ready_, hipEventDisableTiming));
+                RF_HIP(hipEventRecord(caller_ready_, nullptr));
+                RF_HIP(hipStreamWaitEvent(align_stream_, caller_ready_, 0));
+            }
             for (int base = 0; base < n; base += per) {          // one stream: the scans and the tensor launches run in order
                 FaceSeq q;
                 q.frames = (const FrameDesc *)(d_tab + o_fd) + base;
@@ -1547,26 +1556,19 @@ public:
         return t;
     }
 
-    // The plan launch of a call on the side stream: plans[i] = the stream whose table plans image i, or -1 (stream -1, a frame without
-    // pixels); the table travels in a pinned block the kernel reads.  Returns the records' device block, n * max_tracks of them.
-    RoiCell *roi_track_plan(const Tracker &t, const RoiTrackRequest &rq, const int *plans, int n, size_t pin_extra, uint8_t **pin_tail) {
-        const size_t o_tail = align256((size_t)std::max(n, 1) * sizeof(int32_t));
-        uint8_t *pin = roi_cells_pin_.reserve(o_tail + pin_extra);
-        memcpy(pin, plans, (size_t)n * sizeof(int32_t));
-        if (pin_tail) *pin_tail = pin + o_tail;
-        RoiCell *d = (RoiCell *)roi_cells_.reserve((size_t)std::max(n, 1) * t.spec.max_tracks * sizeof(RoiCell));
-        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+    // The track-cells launch of a call on the side stream: streams[i] (device-visible) = the stream whose table plans image i, or -1
+    // (stream -1, a frame without pixels); image i's records at d + i * stride (0: max_tracks).
+    void roi_track_cells_launch(const Tracker &t, const RoiSpec &spec, int margin_q8, const int32_t *streams, int n, RoiCell *d, int stride) {
         RoiTrackCellsParams cp;
         memset((void *)&cp, 0, sizeof(cp));
-        cp.streams = (const int32_t *)pin; cp.n = n;
+        cp.streams = streams; cp.n = n;
         cp.spec = t.spec;
         cp.state = t.state.ptr;
         if (t.has_motion) { cp.motion = (const rf_track_motion *)t.motion.ptr; cp.mspec = t.motion_spec; }
-        cp.margin_q8 = rq.margin_q8; cp.cw = net_w_ / rq.spec.grid; cp.ch = net_h_ / rq.spec.grid; cp.max_zoom = rq.spec.max_zoom;
-        cp.cells = d;
+        cp.margin_q8 = margin_q8; cp.cw = net_w_ / spec.grid; cp.ch = net_h_ / spec.grid; cp.max_zoom = spec.max_zoom;
+        cp.cells = d; cp.stride = stride;
         launch_roi_track_cells(align_stream_, cp);
         RF_HIP(hipGetLastError());
-        return d;
     }
 
     // the planned records of a finished call to the host: what the kernel wrote, the void record for the images it skipped
@@ -1583,60 +1585,227 @@ public:
         if (n > 0 && !cells) throw ArgError("null argument");
         if (n == 0) return;
         DeviceGuard guard(device_);
-        std::vector<int> plans((size_t)n);
+        int32_t *plans = (int32_t *)roi_cells_pin_.reserve((size_t)n * sizeof(int32_t));
         for (int i = 0; i < n; i++) plans[i] = trq.stream_of_image[i];
-        const RoiCell *d = roi_track_plan(t, rq, plans.data(), n, 0, nullptr);
+        RoiCell *d = (RoiCell *)roi_cells_.reserve((size_t)n * t.spec.max_tracks * sizeof(RoiCell));
+        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+        roi_track_cells_launch(t, rq.spec, rq.margin_q8, plans, n, d, 0);
         RF_HIP(hipStreamSynchronize(align_stream_));
-        roi_track_cells_out(d, plans.data(), n, t.spec.max_tracks, cells);
+        roi_track_cells_out(d, plans, n, t.spec.max_tracks, cells);
     }
 
-    // A seventh user of the pass-call skeleton.  On the side stream, in order: the plan launch, the atlas launches (their `cells` are
-    // device addresses the plan launch fills; sized for the x1/4 level, which the host cannot rule out), inputs_ready.  Then the passes
-    // with the region gather, and behind the vote merge, on its stream, the track launch over the merged faces (source pixels, score
-    // order) in the merge's device-visible output blocks.  The tracked calls are synchronous, so the table the plan kernel reads is
-    // settled when the call starts.  An error after the step was enqueued leaves the tracker in the error state.
+    // A seventh user of the pass-call skeleton: detect_slot_rois() below without a changer.
     void detect_track_rois(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device, float threshold,
                            rf_face *out, int cap_per_image, int *counts, bool *truncated, const RoiTrackRequest &rq, const TrackRequest &trq,
                            bool *cut) override {
+        ChangeRequest crq;
+        crq.spec = rq.spec; crq.margin_q8 = rq.margin_q8; crq.stream_of_image = trq.stream_of_image;
+        crq.votes = rq.votes; crq.src_roi = rq.src_roi; crq.cells = rq.cells; crq.d_views = rq.d_views;
+        detect_slot_rois("tracked region detection", frames, rows, cols, steps, n, on_device, threshold, out, cap_per_image, counts, truncated, crq, trq, cut);
+    }
+
+    // -------------------------------------------------------------------------------- change regions
+private:
+    struct Changer;
+public:
+    void *changer_create(const ChangeSpec &spec, int rows, int cols, int n_streams) override {
+        if (n_streams < 1 || n_streams > kChangeMaxStreams) throw ArgError("changer: n_streams must be in [1, 1024]");
+        int bw = 0, bh = 0;
+        if (const char *bad = change_check_shape(rows, cols, spec, &bw, &bh)) throw ArgError(std::string("changer: ") + bad);
+        DeviceGuard guard(device_);
+        std::unique_ptr<Changer> c(new Changer);
+        c->spec = spec; c->rows = rows; c->cols = cols; c->bw = bw; c->bh = bh; c->n_streams = n_streams;
+        try {
+            c->ref.reserve((size_t)n_streams * bw * bh * sizeof(int32_t));
+            c->mask.reserve((size_t)n_streams * c->mask_pitch());
+            c->frames.reserve((size_t)n_streams * sizeof(int64_t));
+            changer_reset_impl(*c, -1);
+        } catch (...) { c->release(); throw; }
+        changers_.push_back(std::move(c));
+        return changers_.back().get();
+    }
+    void changer_destroy(void *p) override {
+        for (size_t i = 0; i < changers_.size(); i++)
+            if (changers_[i].get() == p) {
+                DeviceGuard guard(device_);
+                if (align_stream_) (void)hipStreamSynchronize(align_stream_);
+                changers_[i]->release();
+                changers_.erase(changers_.begin() + i);
+                return;
+            }
+    }
+    Changer &changer_of(void *p) {
+        for (auto &c : changers_)
+            if (c.get() == p) return *c;
+        throw ArgError("not a changer of this handle");
+    }
+    // a stream's (or every stream's) empty state: counter 0 (the next step seeds), reference and mask zero
+    void changer_reset_impl(Changer &c, int stream) {
+        const int first = stream < 0 ? 0 : stream, count = stream < 0 ? c.n_streams : 1;
+        const size_t nb = (size_t)c.bw * c.bh;
+        RF_HIP(hipMemset(c.ref.ptr + (size_t)first * nb * sizeof(int32_t), 0, (size_t)count * nb * sizeof(int32_t)));
+        RF_HIP(hipMemset(c.mask.ptr + (size_t)first * c.mask_pitch(), 0, (size_t)count * c.mask_pitch()));
+        RF_HIP(hipMemset(c.frames.ptr + (size_t)first * sizeof(int64_t), 0, (size_t)count * sizeof(int64_t)));
+        RF_HIP(hipDeviceSynchronize());
+    }
+    void changer_reset(void *p, int stream) override {
+        Changer &c = changer_of(p);
+        if (stream < -1 || stream >= c.n_streams) throw ArgError("stream out of range");
+        DeviceGuard guard(device_);
+        changer_reset_impl(c, stream);
+        if (stream < 0) c.dirty = false;
+    }
+    int changer_read(void *p, int stream, int32_t *ref, int64_t *frames, uint8_t *mask) override {
+        Changer &c = changer_of(p);
+        if (stream < 0 || stream >= c.n_streams) throw ArgError("stream out of range");
+        if (c.dirty) throw ArgError("the changer's last call failed: reset it first");
+        DeviceGuard guard(device_);
+        const size_t nb = (size_t)c.bw * c.bh;
+        if (ref) RF_HIP(hipMemcpy(ref, c.ref.ptr + (size_t)stream * nb * sizeof(int32_t), nb * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (frames) RF_HIP(hipMemcpy(frames, c.frames.ptr + (size_t)stream * sizeof(int64_t), sizeof(int64_t), hipMemcpyDeviceToHost));
+        if (mask) RF_HIP(hipMemcpy(mask, c.mask.ptr + (size_t)stream * c.mask_pitch(), nb, hipMemcpyDeviceToHost));
+        return (int)nb;
+    }
+
+    // The arguments of a change-region call, checked before any state changes: the changer, the cell rule, the margin, the streams
+    // (each at most once: two images of a stream would step one reference from two workgroups), the shape of every frame that will be
+    // stepped and, with a tracker, T + R and the stream counts.  frames null: no frame is looked at.
+    Changer &change_check(const ChangeRequest &rq, const void *const *frames, const int *rows, const int *cols, int n, const Tracker *t) {
+        Changer &c = changer_of(rq.changer);
+        if (c.dirty) throw ArgError("the changer's last call failed: reset it first");
+        if (const char *bad = roi_check_view(net_w_, net_h_, rq.spec.grid)) throw ArgError(std::string("region detection: ") + bad);
+        if (rq.margin_q8 < 0 || rq.margin_q8 > 65535) throw ArgError("region detection: margin_q8 must be in [0, 65535]");
+        if (n < 0 || (n > 0 && !rq.stream_of_image)) throw ArgError("stream_of_image is null");
+        if (t && t->spec.max_tracks + c.spec.max_regions > kRoiMaxRegions) throw ArgError("change regions: max_tracks + max_regions must not exceed 256");
+        if (t && t->n_streams != c.n_streams) throw ArgError("change regions: the tracker and the changer must have the same number of streams");
+        std::vector<int> seen;
+        for (int i = 0; i < n; i++) {
+            const int s = rq.stream_of_image[i];
+            if (s < -1 || s >= c.n_streams) throw ArgError("stream_of_image: stream out of range");
+            if (s < 0) continue;
+            seen.push_back(s);
+            if (frames && frames[i] && rows[i] > 0 && cols[i] > 0 && (rows[i] != c.rows || cols[i] != c.cols))
+                throw ArgError("change regions: a frame's shape is not the changer's");
+        }
+        std::sort(seen.begin(), seen.end());
+        if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) throw ArgError("change regions: a stream appears more than once in the call");
+        return c;
+    }
+
+    // The two launches of a step on the side stream.  images: the pinned table (src null or stream < 0: the image is not stepped);
+    // image i's records at d_cells + i * stride + first, its info at d_info + i.
+    void change_launch(const Changer &c, const ChangeRequest &rq, const ChangeImage *images, int n, RoiCell *d_cells, int stride, int first,
+                       rf_change_info *d_info) {
+        ChangeParams cp;
+        memset((void *)&cp, 0, sizeof(cp));
+        cp.images = images; cp.n = n;
+        cp.spec = c.spec;
+        cp.rows = c.rows; cp.cols = c.cols; cp.bw = c.bw; cp.bh = c.bh;
+        cp.ref = (int32_t *)c.ref.ptr; cp.mask = c.mask.ptr; cp.mask_pitch = (int)c.mask_pitch(); cp.frames = (int64_t *)c.frames.ptr;
+        cp.margin_q8 = rq.margin_q8; cp.cw = net_w_ / rq.spec.grid; cp.ch = net_h_ / rq.spec.grid; cp.max_zoom = rq.spec.max_zoom;
+        cp.cells = d_cells; cp.cell_stride = stride; cp.cell_first = first;
+        cp.info = d_info;
+        launch_change_blocks(align_stream_, cp);
+        launch_change_regions(align_stream_, cp);
+        RF_HIP(hipGetLastError());
+    }
+
+    void change_regions(const void *const *d_frames, const int *rows, const int *cols, const int *steps, int n, const ChangeRequest &rq) override {
+        if (n < 0 || (n > 0 && (!d_frames || !rows || !cols))) throw ArgError("null argument");
+        const std::vector<int> st = checked_steps((const uint8_t *const *)d_frames, rows, cols, steps, n);
+        Changer &c = change_check(rq, d_frames, rows, cols, n, nullptr);
+        if (n == 0) return;
+        DeviceGuard guard(device_);
+        const int R = c.spec.max_regions;
+        ChangeImage *images = (ChangeImage *)roi_cells_pin_.reserve((size_t)n * sizeof(ChangeImage));
+        for (int i = 0; i < n; i++) {
+            const bool live = rq.stream_of_image[i] >= 0 && d_frames[i] && rows[i] > 0 && cols[i] > 0;
+            images[i] = ChangeImage{live ? (const uint8_t *)d_frames[i] : nullptr, st[i], live ? rq.stream_of_image[i] : -1};
+        }
+        const size_t o_info = align256((size_t)n * R * sizeof(RoiCell));
+        uint8_t *d = roi_cells_.reserve(o_info + (size_t)n * sizeof(rf_change_info));
+        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+        c.dirty = true;                                // until the results are back
+        change_launch(c, rq, images, n, (RoiCell *)d, R, 0, (rf_change_info *)(d + o_info));
+        RF_HIP(hipStreamSynchronize(align_stream_));
+        if (rq.cells) RF_HIP(hipMemcpy(rq.cells, d, (size_t)n * R * sizeof(RoiCell), hipMemcpyDeviceToHost));
+        if (rq.info) RF_HIP(hipMemcpy(rq.info, d + o_info, (size_t)n * sizeof(rf_change_info), hipMemcpyDeviceToHost));
+        c.dirty = false;
+    }
+
+    // An eighth user of the pass-call skeleton.
+    void detect_change_rois(const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device, float threshold,
+                            rf_face *out, int cap_per_image, int *counts, bool *truncated, const ChangeRequest &rq, const TrackRequest &trq,
+                            bool *cut) override {
+        if (!rq.changer) throw ArgError("not a changer of this handle");
+        detect_slot_rois("change region detection", frames, rows, cols, steps, n, on_device, threshold, out, cap_per_image, counts, truncated, rq, trq, cut);
+    }
+
+    // The one body of the tracked region call (no changer: R = 0) and of the change-region call (a changer, the tracker optional).
+    // Every image with pixels has roi_passes(T + R, grid) passes: records 0 .. T - 1 of its block are the tracker's slots, T .. T + R - 1
+    // the change slots.  On the side stream, in order: the blocks kernel and the regions kernel (with a changer), the track-cells kernel
+    // (with a tracker), the atlas launches (their `cells` are device addresses those launches fill; sized for the x1/4 level, which the
+    // host cannot rule out), inputs_ready.  Then the passes with the region gather, and behind the vote merge, on its stream, the
+    // track launch over the merged faces (source pixels, score order) in the merge's device-visible output blocks.  The calls are
+    // synchronous, so the tables the plan kernels read are settled when the call starts.  An error after the step was enqueued leaves
+    // the changer and the tracker in the error state.
+    void detect_slot_rois(const char *what, const uint8_t *const *frames, const int *rows, const int *cols, const int *steps, int n, bool on_device,
+                          float threshold, rf_face *out, int cap_per_image, int *counts, bool *truncated, const ChangeRequest &rq,
+                          const TrackRequest &trq, bool *cut) {
         *truncated = false;
         *cut = false;
         TtaRequest mrq;
         mrq.spec.flip = 0; mrq.spec.vote = rq.spec.vote; mrq.spec.max_faces = rq.spec.max_faces;
         mrq.votes = rq.votes; mrq.src_pass = rq.src_roi;
         pass_check_args(n, frames, rows, cols, counts, out, cap_per_image, mrq.spec.max_faces);
-        if (cap_per_image < 1 && trq.tags) throw ArgError("cap_per_image must be >= 1");
+        const bool tracked = trq.tracker || !rq.changer;
+        if (tracked && cap_per_image < 1 && trq.tags) throw ArgError("cap_per_image must be >= 1");
         std::vector<int> st = checked_steps(frames, rows, cols, steps, n);
-        Tracker &t = roi_track_check(trq, n, rq);
+        RoiTrackRequest prq;
+        prq.spec = rq.spec; prq.margin_q8 = rq.margin_q8;
+        Tracker *t = tracked ? &roi_track_check(trq, n, prq) : nullptr;
+        Changer *c = rq.changer ? &change_check(rq, (const void *const *)frames, rows, cols, n, t) : nullptr;
         for (int i = 0; i < n; i++) counts[i] = 0;
         if (n == 0) return;
-        const int T = t.spec.max_tracks, G = rq.spec.grid, GG = G * G, PP = roi_passes(T, G);
-        std::vector<int> plans((size_t)n);
+        const int T = t ? t->spec.max_tracks : 0, R = c ? c->spec.max_regions : 0, S = T + R, G = rq.spec.grid, GG = G * G, PP = roi_passes(S, G);
         std::vector<char> empty((size_t)n);
+        DeviceGuard guard(device_);
+        // the pinned block: plans | stream table | image table | change images; the device block: records | info
+        const size_t o_str = align256((size_t)n * sizeof(int32_t)), o_img = o_str + align256((size_t)n * sizeof(TrackStreamEntry));
+        const size_t o_chg = o_img + align256((size_t)n * sizeof(TrackImageEntry));
+        uint8_t *pin = roi_cells_pin_.reserve(o_chg + (size_t)n * sizeof(ChangeImage));
+        int32_t *plans = (int32_t *)pin;
         for (int i = 0; i < n; i++) {
             empty[i] = !frames[i] || rows[i] <= 0 || cols[i] <= 0;
-            plans[i] = empty[i] ? -1 : trq.stream_of_image[i];
+            plans[i] = empty[i] ? -1 : rq.stream_of_image[i];
         }
-        DeviceGuard guard(device_);
         const std::vector<const uint8_t *> base = pass_frame_bases(frames, rows, cols, st, n, on_device, [&](int i) { return plans[i] >= 0; });
         launch_pending();
-        // the pinned block: plans | stream table | image table (the track kernel reads both tables from pinned memory)
-        uint8_t *tail = nullptr;
-        const size_t o_img = align256((size_t)n * sizeof(TrackStreamEntry));
-        const RoiCell *d_cells = roi_track_plan(t, rq, plans.data(), n, o_img + (size_t)n * sizeof(TrackImageEntry), &tail);
-        TrackStreamEntry *se = (TrackStreamEntry *)tail;
-        TrackImageEntry *ie = (TrackImageEntry *)(tail + o_img);
+        const size_t rec_bytes = (size_t)n * S * sizeof(RoiCell), o_info = align256(rec_bytes), info_bytes = (size_t)n * sizeof(rf_change_info);
+        RoiCell *d_cells = (RoiCell *)roi_cells_.reserve(c ? o_info + info_bytes : rec_bytes);
+        const rf_change_info *d_info = (const rf_change_info *)((const uint8_t *)d_cells + o_info);
+        if (!align_stream_) RF_HIP(hipStreamCreateWithFlags(&align_stream_, hipStreamNonBlocking));
+        if (c) {
+            ChangeImage *images = (ChangeImage *)(pin + o_chg);
+            for (int i = 0; i < n; i++) images[i] = ChangeImage{plans[i] >= 0 ? base[i] : nullptr, st[i], plans[i]};
+            c->dirty = true;                           // until the results are back
+            change_launch(*c, rq, images, n, d_cells, S, T, (rf_change_info *)((uint8_t *)d_cells + o_info));
+        }
+        if (t) roi_track_cells_launch(*t, rq.spec, rq.margin_q8, plans, n, d_cells, c ? S : 0);
+        TrackStreamEntry *se = (TrackStreamEntry *)(pin + o_str);
+        TrackImageEntry *ie = (TrackImageEntry *)(pin + o_img);
         const std::vector<float> scale((size_t)n, 1.f);
-        const int ns = track_build_table(trq.stream_of_image, 0, n, scale.data(), empty.data(), se, ie);
-        // the passes: PP per live tracked frame, frame-major
+        const int ns = t ? track_build_table(trq.stream_of_image, 0, n, scale.data(), empty.data(), se, ie) : 0;
+        // the passes: PP per image with pixels, frame-major
         std::vector<RoiEntry> entries;
         for (int i = 0; i < n; i++) {
             if (plans[i] < 0) continue;
             for (int p = 0; p < PP; p++) {
                 RoiEntry e;
                 memset(&e, 0, sizeof(e));
-                e.frame = i; e.pass = p; e.rows = rows[i]; e.cols = cols[i]; e.grid = G; e.used = std::min(GG, T - p * GG);
+                e.frame = i; e.pass = p; e.rows = rows[i]; e.cols = cols[i]; e.grid = G; e.used = std::min(GG, S - p * GG);
                 e.net_w = net_w_; e.net_h = net_h_;
-                e.cells = d_cells + (size_t)i * T + (size_t)p * GG;
+                e.cells = d_cells + (size_t)i * S + (size_t)p * GG;
                 entries.push_back(e);
             }
         }
@@ -1657,23 +1826,26 @@ public:
             packed = record_inputs_ready();
         }
         tta_open(n, mrq.spec);
-        track_open_call(t, trq, n, cap_per_image);
-        TrackParams tp = track_params(t);
-        tp.streams = se; tp.n_streams = ns;
-        tp.images = ie;
-        tp.faces = tta_out_.ptr; tp.face_stride = (int)sizeof(Candidate); tp.faces_per_image = mrq.spec.max_faces;
-        tp.counts = (const int *)tta_outcount_.ptr;
-        tp.records = nullptr;
-        tp.max_faces = mrq.spec.max_faces;
-        t.dirty = true;                                // until track_copy_out() has run
+        TrackParams tp;
+        memset((void *)&tp, 0, sizeof(tp));
+        if (t) {
+            track_open_call(*t, trq, n, cap_per_image);
+            tp = track_params(*t);
+            tp.streams = se; tp.n_streams = ns;
+            tp.images = ie;
+            tp.faces = tta_out_.ptr; tp.face_stride = (int)sizeof(Candidate); tp.faces_per_image = mrq.spec.max_faces;
+            tp.counts = (const int *)tta_outcount_.ptr;
+            tp.records = nullptr;
+            tp.max_faces = mrq.spec.max_faces;
+            t->dirty = true;                           // until track_copy_out() has run
+        }
         if (P) {
             const TtaSpec msp = mrq.spec;
             auto merge = [=](hipStream_t s, const RunParams *d_params) {
                 tta_launch_merge(s, n, msp, d_params);
                 if (ns > 0) launch_track(s, tp);
             };
-            *truncated = run_passes("tracked region detection", entries, v, threshold, packed,
-                                    gather_into<RoiMap>(0, tta_cand_, tta_count_, kTtaMergeCap), merge, tta_dirty_);
+            *truncated = run_passes(what, entries, v, threshold, packed, gather_into<RoiMap>(0, tta_cand_, tta_count_, kTtaMergeCap), merge, tta_dirty_);
             tta_copy_out(n, mrq, out, cap_per_image, counts, truncated);
         } else {                                       // no image has a pass: the streams of the frames without pixels still step and age
             RF_HIP(hipStreamSynchronize(align_stream_));
@@ -1681,9 +1853,14 @@ public:
             RF_HIP(hipGetLastError());
             RF_HIP(hipStreamSynchronize(align_stream_));
         }
-        track_copy_out(t, trq, n, cap_per_image, counts, cut);
-        roi_track_cells_out(d_cells, plans.data(), n, T, rq.cells);
+        if (t) track_copy_out(*t, trq, n, cap_per_image, counts, cut);
+        roi_track_cells_out(d_cells, plans, n, S, rq.cells);
+        if (c) {
+            if (rq.info) RF_HIP(hipMemcpy(rq.info, d_info, info_bytes, hipMemcpyDeviceToHost));
+            c->dirty = false;
+        }
     }
+
 
     // -------------------------------------------------------------------------------- low-light enhancement
     // The frames of an enhancement as the kernels take them, checked: destinations and pitches, the tile limit, and overlap -- a
@@ -3799,6 +3976,7 @@ private:
     PassCall passes_;
     DeviceScratch pass_frames_;
     hipEvent_t inputs_ready_ = nullptr;
+    hipEvent_t caller_ready_ = nullptr;       // face_batch(): the default stream's work on a caller's tensor, recorded in front of the launches
     // tiled detection: per frame the gathered candidates and their counter, the merged records and counts, the frame table of the
     // fused face batch
     DeviceScratch tile_cand_, tile_count_, tile_out_, tile_outcount_, tile_tab_;
@@ -3823,6 +4001,17 @@ private:
     // region detection (roi.h): the cell records of a call (device block; roi_cells_pin_ below stages them) and its views; the call gathers into the TTA
     // blocks too (roi_merge_request)
     DeviceScratch roi_cells_, roi_views_;
+    // change regions (change.h): the changers of this handle -- per stream the reference image, the last mask (before dilation) and
+    // the frame counter, in device memory; a call's records and info share roi_cells_
+    struct Changer {
+        ChangeSpec spec;
+        int rows = 0, cols = 0, bw = 0, bh = 0, n_streams = 0;
+        DeviceScratch ref, mask, frames;
+        bool dirty = false;                   // a call on it ended in an error: refused until it is reset
+        size_t mask_pitch() const { return align256((size_t)bw * bh); }
+        void release() { ref.release(); mask.release(); frames.release(); }
+    };
+    std::vector<std::unique_ptr<Changer>> changers_;
     // low-light enhancement (enhance.h): LUTs | flags | per-frame counts of a call, and the enhanced copies of a fused call
     DeviceScratch enh_luts_, enh_frames_;
     bool tta_dirty_ = true;

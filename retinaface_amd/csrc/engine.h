@@ -161,6 +161,21 @@ struct RoiTrackRequest {
     void *d_views = nullptr;                    // P * net_h * net_w * 3 bytes, dense, frame-major; P: roi_passes(max_tracks, grid) per live tracked frame
 };
 
+// A change-region call (change.h; rf_change_regions_device / rf_detect_change_roi_batch*): the changer, the region spec and margin as
+// for a tracked region call, the stream of each image, and where the results go -- cells: n * (T + R) records for the fused call
+// (T: the tracker's max_tracks, 0 without one), n * R for the kernels alone; info: n records; each may be nullptr
+struct ChangeRequest {
+    void *changer = nullptr;
+    RoiSpec spec;
+    int margin_q8 = 0;
+    const int *stream_of_image = nullptr;
+    int *votes = nullptr;
+    int *src_roi = nullptr;
+    rf_roi_cell *cells = nullptr;
+    rf_change_info *info = nullptr;
+    void *d_views = nullptr;                    // P * net_h * net_w * 3 bytes, dense, frame-major; P: roi_passes(T + R, grid) per frame with pixels
+};
+
 // An enhanced detection call (enhance.h; rf_detect_enhanced_batch*): the validated spec, where the enhanced copies go (device memory;
 // nullptr: an engine-owned block) and where the number of flagged tiles of each frame goes
 struct EnhanceRequest {
@@ -358,6 +373,25 @@ public:
     virtual void detect_track_rois(const uint8_t *const *, const int *, const int *, const int *, int, bool, float, rf_face *, int, int *, bool *,
                                    const RoiTrackRequest &, const TrackRequest &, bool *) {
         throw Unsupported("region detection is not available on a multi-device handle");
+    }
+    // Change regions (change.h): a changer of one frame shape and n_streams streams; its reset (stream -1: all, which also clears the
+    // error state) and a host copy of a stream's reference, frame counter and last mask (each may be null; returns bw * bh); the two
+    // kernels alone over frames in device memory (synchronous; they step the reference); and the fused call, whose TrackRequest has a
+    // null tracker when no tracker takes part
+    virtual void *changer_create(const ChangeSpec &, int /*rows*/, int /*cols*/, int /*n_streams*/) {
+        throw Unsupported("change regions are not available on a multi-device handle");
+    }
+    virtual void changer_destroy(void *) {}
+    virtual void changer_reset(void *, int /*stream*/) { throw Unsupported("change regions are not available on a multi-device handle"); }
+    virtual int changer_read(void *, int /*stream*/, int32_t *, int64_t *, uint8_t *) {
+        throw Unsupported("change regions are not available on a multi-device handle");
+    }
+    virtual void change_regions(const void *const *, const int *, const int *, const int *, int, const ChangeRequest &) {
+        throw Unsupported("change regions are not available on a multi-device handle");
+    }
+    virtual void detect_change_rois(const uint8_t *const *, const int *, const int *, const int *, int, bool, float, rf_face *, int, int *, bool *,
+                                    const ChangeRequest &, const TrackRequest &, bool *) {
+        throw Unsupported("change regions are not available on a multi-device handle");
     }
     // Low-light enhancement: the two enhance kernels over frames in device memory (synchronous), and the fused call -- the enhanced
     // copies made on the side stream in front of the call's first launch, detect() over them, no host wait in between.

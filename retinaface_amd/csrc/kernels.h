@@ -17,6 +17,7 @@
 #include "rot.h"
 #include "dewarp.h"
 #include "roi.h"
+#include "change.h"
 #include "tile.h"
 #include "tta.h"
 #include "track.h"
@@ -539,8 +540,36 @@ struct RoiTrackCellsParams {
     MotionSpec mspec;
     int margin_q8, cw, ch, max_zoom;
     RoiCell *cells;                               // device memory, n * max_tracks records
+    int stride;                                   // records between two images' blocks; 0: max_tracks (change regions follow the slots)
 };
 void launch_roi_track_cells(hipStream_t s, const RoiTrackCellsParams &p);
+
+// ---- K_o: change regions (change.h), two launches ordered on the stream.
+//      change_blocks:  one workgroup per (32 block columns of one block row, image): every byte of the frame is read once, 16 bytes per
+//                      lane where a chunk lies inside the row and bytewise at a row's head and tail, summed with rotated-weight
+//                      4-byte dot products into per-block LDS accumulators; then per block the step rule: the mask byte and the new
+//                      reference value.
+//      change_regions: one workgroup of 1024 threads per image: the mask dilated and labelled in LDS (label equivalence: link, then
+//                      pointer jumping, until nothing changes), per-root counts, the selection, the boxes of the kept components, their cell records
+//                      (image i's at cells + i * cell_stride + cell_first), the info record and the stream's frame counter.
+//      An image whose stream is < 0 or whose src is null is not stepped: void records, zero info.
+struct ChangeImage {
+    const uint8_t *src; int32_t step, stream;     // row y at src + y * step
+};
+struct ChangeParams {
+    const ChangeImage *images; int n;             // [n], device-visible
+    ChangeSpec spec;
+    int rows, cols, bw, bh;                       // the changer's shape and block grid
+    int32_t *ref;                                 // per stream bw * bh values
+    uint8_t *mask; int mask_pitch;                // per stream mask_pitch bytes, the first bw * bh used
+    int64_t *frames;                              // per stream the frame counter; 0: the next step seeds
+    int margin_q8, cw, ch, max_zoom;
+    RoiCell *cells; int cell_stride, cell_first;  // device memory, 16-byte aligned
+    rf_change_info *info;                         // [n], device memory
+};
+constexpr int kChangeSegBlocks = 32, kChangeThreads = 1024;
+void launch_change_blocks(hipStream_t s, const ChangeParams &p);
+void launch_change_regions(hipStream_t s, const ChangeParams &p);
 
 // ---- K_k: zoom-pyramid detection (pyramid.h).
 //      zoom_tile:  windows of frames enlarged 2x / 4x (integer bilinear, pyr_zoom_pixel) written as dense frames, in front of a

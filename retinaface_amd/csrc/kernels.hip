@@ -6611,7 +6611,7 @@ __global__ __launch_bounds__(kThreads) void roi_track_cells_kernel(RoiTrackCells
     const rf_track *table = (const rf_track *)(a.state + (size_t)stream * (sizeof(TrackHeader) + (size_t)T * sizeof(rf_track)) + sizeof(TrackHeader));
     const rf_track_motion *m = a.motion ? a.motion + (size_t)stream * T + slot : nullptr;
     const RoiCell c = roi_track_cell(table[slot], m, a.mspec, a.margin_q8, a.cw, a.ch, a.max_zoom);
-    int4 *dst = (int4 *)(a.cells + (size_t)image * T + slot);
+    int4 *dst = (int4 *)(a.cells + (size_t)image * (a.stride ? a.stride : T) + slot);
     dst[0] = make_int4(c.roi.x, c.roi.y, c.roi.w, c.roi.h);
     dst[1] = make_int4(c.level, c.x0, c.y0, c.flags);
 }
@@ -6620,10 +6620,291 @@ void launch_roi_track_cells(hipStream_t s, const RoiTrackCellsParams &p) {
     const int T = p.spec.max_tracks;
     if (p.n <= 0) return;
     if (T < 1 || T > kTrackMaxTracks || !p.streams || !p.state || !p.cells || p.cw < 4 || p.ch < 1 || p.margin_q8 < 0 || p.margin_q8 > 65535 ||
-        ((uintptr_t)p.cells & 15))
+        ((uintptr_t)p.cells & 15) || (p.stride != 0 && p.stride < T))
         throw std::invalid_argument("launch_roi_track_cells: a table, the cell size, the margin or the cell block is not valid");
     const long long threads = (long long)p.n * T;
     hipLaunchKernelGGL(roi_track_cells_kernel, dim3((unsigned)((threads + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, p);
+}
+
+// =============================================================================================
+// K_o: change regions (change.h).  Two launches ordered on the stream.
+// change_blocks_kernel: one workgroup per (kChangeSegBlocks block columns of one block row, image).  The segment's bytes of a frame row
+//      are cut into the 16-byte-aligned chunks of MEMORY they lie in, whatever the pointer and the pitch are; a lane takes one chunk.  A
+//      chunk inside the segment is one 16-byte load and four dot products whose weight word rotates with the byte's channel
+//      (change_weights); a dword that straddles a block border is split by masking.  The chunk at a row's head and at its tail is read
+//      bytewise, only the bytes of the row, as the atlas and enhance kernels treat theirs -- no byte outside the cols * 3 bytes of a
+//      row is read.  A chunk is shorter than a block row (16 < 3 B), so it feeds at most two blocks: two sums, two LDS adds.  Then one
+//      thread per block applies change_step_block (or seeds) and stores the reference value and the mask byte.
+//      Bounds: block index < bw * bh by construction; stream < the changer's streams (checked by the host).
+// change_regions_kernel: one workgroup per image.  LDS: the mask (16 KiB), the labels (uint16, 32 KiB), the selection (about 2 KiB).
+//      A marked block starts with its raster index as label; the labels are then merged by label equivalence (link the tree of a
+//      block's label under the smallest label in its 8-neighbourhood, then pointer jumping), every step in parallel over all blocks: a
+//      winding component costs a few iterations of log-many jump rounds, not a scan per bend (row and column scans, one thread per
+//      row, took 5.4 ms on a 128 x 128 spiral).  Every store lowers a label towards the same fixed point, the
+//      smallest raster index of the component, so the result does not depend on the order.  A root then keeps 0x8000 | (count - 1) in its own slot (its
+//      label is its index), counted with LDS adds on the half word; the selection is one block-wide maximum of
+//      (count, -label) per kept component; a kept root becomes 0xc000 | k and its members build the box with LDS min / max.
+// =============================================================================================
+__global__ __launch_bounds__(kThreads) void change_blocks_kernel(ChangeParams a) {
+    __shared__ uint32_t s_acc[kChangeSegBlocks];
+    const ChangeImage im = a.images[blockIdx.y];
+    if (im.stream < 0 || !im.src) return;                                // uniform
+    const int B = a.spec.block, lb = a.spec.log2_block, tid = (int)threadIdx.x;
+    const int segs = (a.bw + kChangeSegBlocks - 1) / kChangeSegBlocks;
+    const int by = (int)blockIdx.x / segs, seg = (int)blockIdx.x - by * segs;
+    if (by >= a.bh) return;
+    const int bx0 = seg * kChangeSegBlocks, nbx = a.bw - bx0 < kChangeSegBlocks ? a.bw - bx0 : kChangeSegBlocks;
+    const int y0 = by << lb, h = a.rows - y0 < B ? a.rows - y0 : B;
+    const int s0 = 3 * (bx0 << lb), e1 = 3 * ((bx0 + nbx) << lb), s1 = e1 < 3 * a.cols ? e1 : 3 * a.cols;      // the segment's bytes of a row
+    const int nch = ((s1 - s0 + 15) >> 4) + 1;                           // chunks a row's segment can touch at any alignment
+    if (tid < kChangeSegBlocks) s_acc[tid] = 0;
+    __syncthreads();
+    for (int item = tid; item < h * nch; item += kThreads) {
+        const int r = item / nch, c = item - r * nch;
+        const uint8_t *row = im.src + (size_t)(y0 + r) * (size_t)im.step;
+        const uintptr_t lo = (uintptr_t)(row + s0), hi = (uintptr_t)(row + s1);
+        const uintptr_t p = (lo & ~(uintptr_t)15) + (uintptr_t)16 * (uintptr_t)c;
+        if (p >= hi) continue;
+        uint32_t sum_a = 0, sum_b = 0;
+        int blk_a;
+        if (p >= lo && p + 16 <= hi) {
+            const uint4 v = *(const uint4 *)p;
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+            const int o = (int)(p - (uintptr_t)row);
+            int px = o / 3, ph = o - 3 * px;
+            blk_a = (px >> lb) - bx0;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {                                // the dword holds 3 - ph bytes of pixel px and ph + 1 of pixel px + 1
+                const uint32_t W = change_weights(ph);
+                const bool first_b = (px >> lb) - bx0 != blk_a;
+                if (((px + 1) & (B - 1)) != 0) {
+                    if (first_b) sum_b = change_dot4(w[k], W, sum_b);
+                    else sum_a = change_dot4(w[k], W, sum_a);
+                } else {                                                 // pixel px + 1 opens the next block (then px is in blk_a: a chunk spans two)
+                    const uint32_t m = 0xffffffffu >> (8 * (ph + 1));
+                    sum_a = change_dot4(w[k] & m, W, sum_a);
+                    sum_b = change_dot4(w[k] & ~m, W, sum_b);
+                }
+                px += ph == 2 ? 2 : 1;
+                ph = ph == 2 ? 0 : ph + 1;
+            }
+        } else {
+            const uintptr_t q0 = p > lo ? p : lo, q1 = p + 16 < hi ? p + 16 : hi;
+            blk_a = (((int)(q0 - (uintptr_t)row) / 3) >> lb) - bx0;
+            for (uintptr_t q = q0; q < q1; q++) {
+                const int o = (int)(q - (uintptr_t)row), px = o / 3, ph = o - 3 * px;
+                const uint32_t t = (uint32_t)*(const uint8_t *)q * (change_weights(ph) & 0xffu);
+                if ((px >> lb) - bx0 == blk_a) sum_a += t;
+                else sum_b += t;
+            }
+        }
+        atomicAdd(&s_acc[blk_a], sum_a);
+        if (blk_a + 1 < nbx) atomicAdd(&s_acc[blk_a + 1], sum_b);        // (a chunk whose first block is the segment's last holds no byte of another: sum_b is 0)
+    }
+    __syncthreads();
+    if (tid < nbx) {
+        const int bx = bx0 + tid, w = a.cols - (bx << lb) < B ? a.cols - (bx << lb) : B;
+        const size_t nb = (size_t)a.bw * a.bh, i = (size_t)by * a.bw + bx;
+        int32_t *ref = a.ref + (size_t)im.stream * nb + i;
+        uint8_t *mask = a.mask + (size_t)im.stream * a.mask_pitch + i;
+        const uint32_t S = s_acc[tid];
+        if (a.frames[im.stream] == 0) {
+            *ref = (int32_t)S;
+            *mask = 0;
+        } else {
+            int32_t v = *ref;
+            const bool changed = change_step_block(S, w * h, a.spec.thr_q4, a.spec.adapt_shift, &v);
+            *ref = v;
+            *mask = changed ? 1 : 0;
+        }
+    }
+}
+
+__device__ __forceinline__ void change_store_cell(RoiCell *dst, const RoiCell &c) {
+    ((int4 *)dst)[0] = make_int4(c.roi.x, c.roi.y, c.roi.w, c.roi.h);
+    ((int4 *)dst)[1] = make_int4(c.level, c.x0, c.y0, c.flags);
+}
+
+// the 16-bit value at labels[idx] lowered to v (v < 0x10000), by compare-and-swap on the 32-bit word that holds it
+__device__ __forceinline__ void change_min16(uint16_t *labels, uint32_t idx, uint32_t v) {
+    uint32_t *w = (uint32_t *)labels + (idx >> 1);
+    const int sh = 16 * (int)(idx & 1);
+    uint32_t old = *(volatile uint32_t *)w;
+    while (((old >> sh) & 0xffffu) > v) {
+        const uint32_t prev = atomicCAS(w, old, (old & ~(0xffffu << sh)) | (v << sh));
+        if (prev == old) return;
+        old = prev;
+    }
+}
+
+__global__ __launch_bounds__(kChangeThreads) void change_regions_kernel(ChangeParams a) {
+    __shared__ __attribute__((aligned(16))) uint16_t s_lab[kChangeMaxBlocks];
+    __shared__ uint8_t s_mask[kChangeMaxBlocks];
+    __shared__ uint32_t s_box[kChangeMaxRegions][4];
+    __shared__ int s_cnt[kChangeMaxRegions];
+    __shared__ uint32_t s_red[kChangeThreads / 64];
+    __shared__ int s_flag, s_changed, s_comps;
+    const int image = (int)blockIdx.x, tid = (int)threadIdx.x;
+    const ChangeImage im = a.images[image];
+    const int R = a.spec.max_regions, bw = a.bw, bh = a.bh, nb = bw * bh;
+    RoiCell *cells = a.cells + (size_t)image * a.cell_stride + a.cell_first;
+    const bool skip = im.stream < 0 || !im.src;                          // uniform
+    if (tid == 0) {
+        s_flag = skip ? -1 : a.frames[im.stream] == 0 ? 1 : 0;
+        s_changed = 0; s_comps = 0;
+    }
+    __syncthreads();
+    const int seed = s_flag;
+    int changed = 0;
+    if (seed == 0) {
+        const uint8_t *mask = a.mask + (size_t)im.stream * a.mask_pitch;
+        int mine = 0;
+        for (int i = tid; i < nb; i += kChangeThreads) {
+            const uint8_t m = mask[i];
+            s_mask[i] = m;
+            mine += m != 0;
+        }
+        if (mine) atomicAdd(&s_changed, mine);
+        __syncthreads();
+        changed = s_changed;
+    }
+    if (seed != 0 || changed == 0) {                                     // uniform: nothing to label
+        if (tid < R) change_store_cell(cells + tid, roi_void_cell());
+        if (tid == 0) {
+            *(int4 *)(a.info + image) = make_int4(0, 0, 0, seed == 1 ? 1 : 0);
+            if (!skip) a.frames[im.stream] += 1;
+        }
+        return;
+    }
+    for (int i = tid; i < nb; i += kChangeThreads)
+        s_lab[i] = change_dilated(s_mask, bw, bh, i % bw, i / bw, a.spec.dilate) ? (uint16_t)i : (uint16_t)kChangeNone;
+    __syncthreads();
+    // Label equivalence.  Invariants: a label is the index of a marked block of the same component, and lab[i] <= i; every store lowers a
+    // label, so the loop ends.  (1) link: a block whose neighbourhood holds a smaller label m than its own label l lowers the slot of
+    // BLOCK l to m (a 16-bit minimum by compare-and-swap on the word): the tree of l hangs under a smaller one.  (2) jump: lab[i] =
+    // lab[lab[i]] until no label moves -- a chain halves per round.  When (1) finds nothing, every block's label is at most its
+    // neighbours', so it is constant on a component, and by lab[i] <= i it is the component's smallest index.  Reads race with
+    // stores only on values that are valid at either time.
+    volatile uint16_t *lab = s_lab;
+    for (int iter = 0; iter < nb; iter++) {
+        int moved = 0;
+        for (int i = tid; i < nb; i += kChangeThreads) {
+            const uint32_t l = lab[i];
+            if (l == kChangeNone) continue;
+            const int x = i % bw, y = i / bw;
+            uint32_t m = l;
+            for (int dy = -1; dy <= 1; dy++)
+                for (int dx = -1; dx <= 1; dx++) {
+                    const int xx = x + dx, yy = y + dy;
+                    if (xx < 0 || yy < 0 || xx >= bw || yy >= bh) continue;
+                    const uint32_t t = lab[yy * bw + xx];                 // unmarked = 0xffff, the largest: the minimum passes it over
+                    m = t < m ? t : m;
+                }
+            if (m < l) { change_min16(s_lab, l, m); moved = 1; }
+        }
+        if (!__syncthreads_or(moved)) break;                             // uniform
+        for (int round = 0; round < 16; round++) {
+            int jumped = 0;
+            for (int i = tid; i < nb; i += kChangeThreads) {
+                const uint32_t l = lab[i];
+                if (l == kChangeNone) continue;
+                const uint32_t t = lab[l];
+                if (t < l) { lab[i] = (uint16_t)t; jumped = 1; }
+            }
+            if (!__syncthreads_or(jumped)) break;
+        }
+    }
+    __syncthreads();
+    // roots: the slot of a block whose label is its own index becomes 0x8000 | (count - 1)
+    int roots = 0;
+    for (int i = tid; i < nb; i += kChangeThreads)
+        if (s_lab[i] == (uint16_t)i) { s_lab[i] = 0x8000; roots++; }
+    if (roots) atomicAdd(&s_comps, roots);
+    __syncthreads();
+    for (int i = tid; i < nb; i += kChangeThreads) {
+        const uint32_t l = s_lab[i];
+        if (l < 0x4000u) atomicAdd((uint32_t *)s_lab + (l >> 1), 1u << (16 * (l & 1)));      // count - 1 <= 16383: no carry out of the half
+    }
+    __syncthreads();
+    // the selection: per kept component one maximum of count << 14 | (16383 - label) over the roots not taken yet
+    int kept = 0;
+    for (; kept < R; kept++) {
+        uint32_t best = 0;
+        for (int i = tid; i < nb; i += kChangeThreads) {
+            const uint32_t s = s_lab[i];
+            if ((s & 0xc000u) != 0x8000u) continue;
+            const uint32_t cnt = (s & 0x3fffu) + 1;
+            if ((int)cnt < a.spec.min_blocks) continue;
+            const uint32_t key = cnt << 14 | (uint32_t)(16383 - i);
+            best = key > best ? key : best;
+        }
+        for (int d = 32; d >= 1; d >>= 1) {
+            const uint32_t o = __shfl_xor(best, d);
+            best = o > best ? o : best;
+        }
+        if ((tid & 63) == 0) s_red[tid >> 6] = best;
+        __syncthreads();
+        best = 0;
+        for (int w = 0; w < kChangeThreads / 64; w++) best = s_red[w] > best ? s_red[w] : best;
+        if (best == 0) break;                                            // uniform
+        if (tid == 0) {
+            const int i = 16383 - (int)(best & 0x3fffu);
+            s_lab[i] = (uint16_t)(0xc000u | (uint32_t)kept);
+            s_cnt[kept] = (int)(best >> 14);
+            s_box[kept][0] = (uint32_t)bw; s_box[kept][1] = (uint32_t)bh; s_box[kept][2] = 0; s_box[kept][3] = 0;
+        }
+        __syncthreads();
+    }
+    __syncthreads();
+    for (int i = tid; i < nb; i += kChangeThreads) {
+        const uint32_t s = s_lab[i];
+        if (s == kChangeNone) continue;
+        const uint32_t rs = (s & 0x8000u) ? s : s_lab[s];
+        if ((rs & 0xc000u) != 0xc000u) continue;
+        const int k = (int)(rs & 0x3fffu);
+        const uint32_t x = (uint32_t)(i % bw), y = (uint32_t)(i / bw);
+        atomicMin(&s_box[k][0], x); atomicMin(&s_box[k][1], y);
+        atomicMax(&s_box[k][2], x); atomicMax(&s_box[k][3], y);
+    }
+    __syncthreads();
+    if (tid < R) {
+        RoiCell c = roi_void_cell();
+        if (tid < kept) {
+            rf_roi region;
+            c = change_region((int)s_box[tid][0], (int)s_box[tid][1], (int)s_box[tid][2], (int)s_box[tid][3], a.spec.block, a.rows, a.cols,
+                              a.margin_q8, a.cw, a.ch, a.max_zoom, &region);
+        }
+        change_store_cell(cells + tid, c);
+    }
+    if (tid == 0) {
+        *(int4 *)(a.info + image) = make_int4(changed, s_comps, kept, 0);
+        a.frames[im.stream] += 1;
+    }
+}
+
+namespace {
+void change_check_params(const ChangeParams &p) {
+    const long long nb = (long long)p.bw * p.bh;
+    if (!p.images || !p.ref || !p.mask || !p.frames || !p.cells || !p.info || p.bw < 1 || p.bh < 1 || nb > kChangeMaxBlocks || p.mask_pitch < nb ||
+        p.bw != (p.cols + p.spec.block - 1) >> p.spec.log2_block || p.bh != (p.rows + p.spec.block - 1) >> p.spec.log2_block ||
+        p.spec.block != 1 << p.spec.log2_block || p.spec.log2_block < 3 || p.spec.log2_block > 5 || p.spec.max_regions < 1 ||
+        p.spec.max_regions > kChangeMaxRegions || p.cell_first < 0 || p.cell_stride < p.cell_first + p.spec.max_regions || p.cw < 4 || p.ch < 1 ||
+        p.margin_q8 < 0 || p.margin_q8 > 65535 || ((uintptr_t)p.cells & 15) || ((uintptr_t)p.info & 15))
+        throw std::invalid_argument("launch_change: the changer's blocks, the grid, the cell block or the margin is not valid");
+}
+}  // namespace
+
+void launch_change_blocks(hipStream_t s, const ChangeParams &p) {
+    if (p.n <= 0) return;
+    change_check_params(p);
+    const int segs = (p.bw + kChangeSegBlocks - 1) / kChangeSegBlocks;
+    hipLaunchKernelGGL(change_blocks_kernel, dim3((unsigned)(segs * p.bh), (unsigned)p.n), dim3(kThreads), 0, s, p);
+}
+
+void launch_change_regions(hipStream_t s, const ChangeParams &p) {
+    if (p.n <= 0) return;
+    change_check_params(p);
+    hipLaunchKernelGGL(change_regions_kernel, dim3((unsigned)p.n), dim3(kChangeThreads), 0, s, p);
 }
 
 // =============================================================================================

@@ -16,7 +16,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (rf_face, rf_face_batch_spec, rf_face_gate, rf_face_quality, rf_options, rf_overlay_spec, rf_redact_spec, rf_tile_spec, rf_track,
-                   rf_dewarp_spec, rf_enhance_spec, rf_roi, rf_roi_cell, rf_roi_spec, rf_motion_spec, rf_pyramid_spec, rf_rot_spec, rf_shot, rf_track_motion, rf_track_spec, rf_track_tag, rf_tta_spec,
+                   rf_change_spec, rf_dewarp_spec, rf_enhance_spec, rf_roi, rf_roi_cell, rf_roi_spec, rf_motion_spec, rf_pyramid_spec, rf_rot_spec, rf_shot, rf_track_motion, rf_track_spec, rf_track_tag, rf_tta_spec,
                    rf_follow_spec, rf_track_follow)
 
 PRECISION_FP32, PRECISION_FP16, PRECISION_INT8 = 0, 1, 2
@@ -1241,6 +1241,147 @@ class Dewarper:
         self._d = None
 
 
+def change_spec(block: int = 0, thr_q4: int = 0, adapt_shift: int = 0, dilate: int = 0, min_blocks: int = 0, max_regions: int = 0) -> rf_change_spec:
+    """An rf_change_spec; a zero means the default: block 8, 16 or 32 (16); thr_q4, the mean luma difference of a block in 1/16 grey
+    levels (128); adapt_shift 0..8 (0: the reference becomes the frame); dilate 0 / 1 = grow the mask by one block, 2 = off;
+    min_blocks (2); max_regions 1..64 (16)."""
+    return rf_change_spec(C.sizeof(rf_change_spec), int(block), int(thr_q4), int(adapt_shift), int(dilate), int(min_blocks), int(max_regions), 0)
+
+
+def _as_change_spec(spec) -> rf_change_spec:
+    return spec if isinstance(spec, rf_change_spec) else change_spec(**(spec or {}))
+
+
+def _change_grid(sp: rf_change_spec, rows: int, cols: int):
+    b = sp.block or 16
+    return -(-int(cols) // b), -(-int(rows) // b)
+
+
+def change_step_host(frame: np.ndarray, ref: np.ndarray, counter: int, view_w: int, view_h: int, spec=None, margin: Optional[float] = None,
+                     grid: int = 0, max_zoom: int = 0):
+    """rf_change_step_host (host only, no GPU): one step of one stream -- the code the kernels run.  ref: the (bh, bw) int32 reference
+    (not written), counter: the stream's frame counter (0: this step seeds).  Returns (ref, counter, mask, regions, cells, info): the
+    new reference and counter, the (bh, bw) uint8 mask of changed blocks BEFORE dilation, the (R, 4) int32 regions, the (R, 8) int32
+    cell records (roi_plan()'s columns; void behind info[2]) and info = (changed_blocks, components, kept, flags)."""
+    lib = _lib.load_library()
+    sp = _as_change_spec(spec)
+    frame = _dense_frame(frame)
+    bw, bh = _change_grid(sp, frame.shape[0], frame.shape[1])
+    ref = np.array(ref, np.int32).reshape(-1)
+    if ref.size != bw * bh:
+        raise ValueError("ref: one int32 per block (%d x %d)" % (bh, bw))
+    R = sp.max_regions or 16
+    cnt = C.c_int64(int(counter))
+    mask = np.full(max(bw * bh, 1), 0xAB, np.uint8)
+    regions, cells, info = (rf_roi * max(R, 1))(), (rf_roi_cell * max(R, 1))(), _lib.rf_change_info()
+    st = lib.rf_change_step_host(C.byref(sp), frame.ctypes.data, frame.shape[0], frame.shape[1], frame.strides[0], ref.ctypes.data, C.byref(cnt),
+                                 _margin_q8(margin), int(view_w), int(view_h), C.byref(roi_spec(grid, max_zoom)), mask.ctypes.data, regions,
+                                 cells, C.byref(info))
+    if st < 0:
+        raise _lib.RFError(st, "rf_change_step_host: bad spec, frame shape, view size, margin or counter")
+    return (ref.reshape(bh, bw), int(cnt.value), mask.reshape(bh, bw), np.frombuffer(regions, np.int32, 4 * R).reshape(R, 4).copy(),
+            _cell_rows(cells, R), np.array([info.changed_blocks, info.components, info.kept, info.flags], np.int32))
+
+
+class Changer:
+    """Change regions on a detector (rf_changer_create): a per-stream reference image of one frame shape -- one luma sum per block --
+    in device memory.  Every step marks the blocks of a frame that differ from it, updates it and turns the marked blocks into at most
+    max_regions regions on the device; detect_changed() detects inside them, next to a tracker's regions when one is given."""
+
+    def __init__(self, det: "RetinaFace", rows: int, cols: int, n_streams: int = 1, **spec):
+        self._det, self._c = det, None
+        self.rows, self.cols, self.n_streams = int(rows), int(cols), int(n_streams)
+        self.spec = change_spec(**spec)
+        self.max_regions = self.spec.max_regions or 16
+        self.bw, self.bh = _change_grid(self.spec, rows, cols)
+        c = C.c_void_p()
+        _lib.check(det._lib.rf_changer_create(det._h, C.byref(self.spec), self.rows, self.cols, self.n_streams, C.byref(c)), det._h)
+        self._c = c
+        self.truncated = False
+        self.last_cells = self.last_info = None
+
+    def close(self):
+        if self._c is not None and getattr(self._det, "_h", None):
+            self._det._lib.rf_changer_destroy(self._c)
+        self._c = None
+
+    def reset(self, stream: int = -1):
+        """rf_changer_reset: the stream (-1: every stream, which also clears the error state) seeds again on its next step"""
+        _lib.check(self._det._lib.rf_changer_reset(self._c, int(stream)), self._det._h)
+
+    def read(self, stream: int):
+        """rf_changer_read: (ref, frames, mask) of a stream -- the (bh, bw) int32 reference, the frame counter and the (bh, bw) uint8
+        mask of the blocks the last step found changed (before dilation)"""
+        ref = np.zeros((self.bh, self.bw), np.int32)
+        mask = np.zeros((self.bh, self.bw), np.uint8)
+        frames = C.c_int64()
+        _lib.check(self._det._lib.rf_changer_read(self._c, int(stream), ref.ctypes.data, C.byref(frames), mask.ctypes.data), self._det._h)
+        return ref, int(frames.value), mask
+
+    def _info_rows(self, info, n):
+        return np.frombuffer(info, np.int32, 4 * n).reshape(n, 4).copy() if n else np.zeros((0, 4), np.int32)
+
+    def regions_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], streams: Sequence[int],
+                       steps: Optional[Sequence[int]] = None, margin: Optional[float] = None, grid: int = 0, max_zoom: int = 0):
+        """rf_change_regions_device: the two kernels alone over frames in device memory; they STEP the reference of streams[i] (-1, or
+        a 0 / None pointer: nothing happens for the image).  Returns (cells, info): the (n, max_regions, 8) int32 cell records and the
+        (n, 4) int32 info records (changed_blocks, components, kept, flags)."""
+        n, R = len(ptrs), self.max_regions
+        cells, info = (rf_roi_cell * max(n * R, 1))(), (_lib.rf_change_info * max(n, 1))()
+        det = self._det
+        _lib.check(det._lib.rf_change_regions_device(det._h, self._c, *_device_frames(ptrs, rows, cols, steps), (C.c_int * max(n, 1))(*streams), n,
+                                                     _margin_q8(margin), C.byref(roi_spec(grid, max_zoom)), cells, info), det._h)
+        return _cell_rows(cells, n * R).reshape(n, R, 8), self._info_rows(info, n)
+
+    def _changed(self, fn, frames, streams, tracker, threshold, margin, grid, max_zoom, vote, max_faces, views_ptr, cap_ended, return_src_roi):
+        det = self._det
+        n = frames[4]
+        sp = roi_spec(grid, max_zoom, vote, max_faces)
+        cap = sp.max_faces or det.max_detections
+        S = (tracker.max_tracks if tracker is not None else 0) + self.max_regions
+        cells, info = (rf_roi_cell * max(n * S, 1))(), (_lib.rf_change_info * max(n, 1))()
+        sarr = (C.c_int * max(n, 1))(*streams)
+        if tracker is not None:
+            t, _, tags, ended, ce, ec = tracker._buffers(n, cap, cap_ended)
+        else:
+            t, tags, ended, ce, ec = None, None, None, 0, None
+        head = (det._h,) + tuple(frames) + (float(threshold), C.byref(sp), _margin_q8(margin))
+        tail = (cells, views_ptr, self._c, info, t, sarr, tags, ended, ce, ec)
+        dets, src, votes = det._merged_call(fn, head, n, cap, "roi_counts", True, tail=tail)      # the C call takes src_roi, then votes
+        self.truncated = det.truncated
+        self.last_cells = _cell_rows(cells, n * S).reshape(n, S, 8)
+        self.last_info = self._info_rows(info, n)
+        res = (dets,)
+        if tracker is not None:
+            tracker.truncated = det.truncated
+            res += tracker._results(n, det.roi_counts, cap)
+        return res + (votes, src) if return_src_roi else (res if tracker is not None else dets)
+
+    def detect_changed(self, imgs: Sequence[np.ndarray], streams: Sequence[int], tracker: Optional["Tracker"] = None, threshold: float = 0.5,
+                       margin: Optional[float] = None, grid: int = 0, max_zoom: int = 0, vote: bool = False, max_faces: int = 0,
+                       cap_ended: Optional[int] = None, return_src_roi: bool = False):
+        """rf_detect_change_roi_batch: every frame (of the changer's shape; None: an empty frame) steps the reference of streams[i]
+        (-1: nothing happens) and is detected inside the change regions -- with `tracker` also inside the regions of its stream's track
+        slots, exactly as Tracker.detect_tracked_rois(), region r < max_tracks being slot r and region max_tracks + k change slot k; the
+        merged faces then go into the frame step, so a newcomer gets its id on the frame it appears in.  Returns the detections per
+        frame in SOURCE-FRAME pixels; with a tracker (detections, tags per image, ended tracks per image); with return_src_roi also
+        the member counts and the region of each face.  self.last_cells: the (n, T + R, 8) cell records, self.last_info: the (n, 4)
+        info records."""
+        f = _host_frames(imgs)
+        return self._changed(self._det._lib.rf_detect_change_roi_batch, f.args, streams, tracker, threshold, margin, grid, max_zoom, vote,
+                             max_faces, None, cap_ended, return_src_roi)
+
+    def detect_changed_device(self, ptrs: Sequence[int], rows: Sequence[int], cols: Sequence[int], streams: Sequence[int],
+                              tracker: Optional["Tracker"] = None, threshold: float = 0.5, steps: Optional[Sequence[int]] = None,
+                              margin: Optional[float] = None, grid: int = 0, max_zoom: int = 0, vote: bool = False, max_faces: int = 0,
+                              views_ptr: Optional[int] = None, cap_ended: Optional[int] = None, return_src_roi: bool = False):
+        """rf_detect_change_roi_batch_device: detect_changed for frames resident in device memory (0 / None: an empty frame).
+        views_ptr: device memory of passes * net_h * net_w * 3 bytes that receives the views as dense frames."""
+        frames = _device_frames(ptrs, rows, cols, steps) + (len(ptrs),)
+        return self._changed(self._det._lib.rf_detect_change_roi_batch_device, frames, streams, tracker, threshold, margin, grid, max_zoom, vote,
+                             max_faces, views_ptr, cap_ended, return_src_roi)
+
+
 ROI_CROPPED = _lib.RF_ROI_CROPPED
 ROI_VOID = _lib.RF_ROI_VOID
 
@@ -2257,6 +2398,11 @@ class RetinaFace:
         dc = rows if int(k) & 1 else cols
         _lib.check(self._lib.rf_rotate_device(self._h, src_ptr, int(rows), int(cols), int(step if step is not None else 3 * cols), int(k),
                                               dst_ptr, int(dst_step if dst_step is not None else 3 * dc)), self._h)
+
+    # ------------------------------------------------------------------ change regions
+    def changer(self, rows: int, cols: int, n_streams: int = 1, **spec) -> Changer:
+        """rf_changer_create: change regions for frames of rows x cols on this detector (see Changer; keywords as change_spec())."""
+        return Changer(self, rows, cols, n_streams, **spec)
 
     # ------------------------------------------------------------------ fisheye detection
     def dewarper(self, rows: int, cols: int, spec=None, mesh=None, view_w: int = 0, view_h: int = 0) -> Dewarper:
